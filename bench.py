@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- Msamples/s of the spectral integrator on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1 runs one process per GPU over RCCL: either launched by torch.distributed.run (the driver's way:
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment) or, when WORLD_SIZE is not set, this
@@ -16,13 +16,18 @@ is exact, so the sum is the image).  Inputs (scene tables, texture) are resident
 timed region; the timed region is K x (render [+ reduce] + copy of the combined XYZA image into pinned host memory on
 rank 0): the metric as SURVEY.md section 8(d) defines it ("framebuffer reduce + D2H of XYZA included").  The copies run on their
 own stream between two device and two host images, so step k's image travels while step k+1 renders; all K images are in host
-memory when the timed region ends.  The same K steps without the copy are timed afterwards and reported as value_device_resident.
+memory when the timed region ends.
 
-Prints ONE JSON line on rank 0 -- and only for an image that passed: the last timed step's image (from pinned host memory) is compared
-with the CPU oracle on six 8x8 tiles at full spp ("check"), every rank's record is gathered ("ranks": device uuid / bus id, hostname, ms per
-step, path kernel ms, share of parked units), two ranks on one device or overlapping rank images end the run without a line ("distributed"),
-and at N = 1 the HBM traffic of the path and generate kernels is measured in the run by two rocprofv3 --pmc passes over a child run of the
-same workload (roofline.traffic; replayed from profiles/traffic.json with a staleness stamp when counters are unavailable).
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0 (roofline.traffic replayed from profiles/traffic.json
+with a staleness stamp).  --dump-outputs DIR also writes the combined XYZA image of the last timed step, as it arrived in pinned host
+memory, to DIR/xyza.npy (float32 [H, W, 4]; above 64 MB a fixed, seeded sample of its pixels, DIR/xyza_sample.npy).
+
+--full adds what the headline figure does not need, and then prints the line only for an image that passed: the same K steps without the
+copy are timed afterwards and reported as value_device_resident; the last timed step's image (from pinned host memory) is compared with
+the CPU oracle on six 8x8 tiles at full spp ("check"); every rank's record is gathered ("ranks": device uuid / bus id, hostname, ms per
+step, path kernel ms, share of parked units), two ranks on one device or overlapping rank images end the run without a line ("distributed");
+at N = 1 the HBM traffic of the path and generate kernels is measured in the run by two rocprofv3 --pmc passes over a child run of the
+same workload (roofline.traffic; replayed as above when counters are unavailable), and the CPU baseline is timed ("cpu_baseline").
 """
 import argparse
 import json
@@ -228,6 +233,25 @@ def oracle_check(img, scene, W, H, spp_total, observer, texture, n_tiles=6):
             "against": "oracle/libssx_oracle.so (CPU restatement), uint32 compare of float4 XYZA", "mean_alpha": round(alpha, 5), "seconds": round(time.time() - t, 2)}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, img):
+    """--dump-outputs: what a caller of the timed path receives, the combined XYZA image of the last timed step as it arrived in pinned
+    host memory -> out_dir/xyza.npy (float32 [H, W, 4]).  An image above DUMP_MAX_BYTES is written as a sample of its pixels instead,
+    the same for every run of the same arguments (seed 0): out_dir/xyza_sample.npy (float32 [n, 4], pixels in row-major order)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    img = np.ascontiguousarray(img, dtype=np.float32)
+    if img.nbytes <= DUMP_MAX_BYTES:
+        np.save(os.path.join(out_dir, "xyza.npy"), img)
+        return
+    px = img.reshape(-1, img.shape[-1])
+    n = DUMP_MAX_BYTES // px[0].nbytes
+    pick = np.sort(np.random.default_rng(0).choice(px.shape[0], size=n, replace=False))
+    np.save(os.path.join(out_dir, "xyza_sample.npy"), px[pick])
+
+
 def n1_reference(src_id=None):
     """The N = 1 figure the efficiency field is quoted against -- only one taken on THIS build's kernel sources counts (VERDICT r05 item 5:
     a figure of another round's kernel must be refused, not divided by): the driver's N = 1 records in the tree (BENCH_rNN.json, whose
@@ -303,7 +327,7 @@ def pmc_passes(args):
     if not os.path.exists(prof):
         return None, "rocprofv3 not found"
     out_root = os.path.join(ROOT, "gpurun_out") if os.path.isdir(os.path.join(ROOT, "gpurun_out")) else tempfile.gettempdir()
-    child = [sys.executable, os.path.abspath(__file__), "--pmc-child", "--steps", "2", "--warmup", "1", "--scene", args.scene, "--res", str(args.res), "--spp", str(args.spp),
+    child = [sys.executable, os.path.abspath(__file__), "--pmc-child", "--full", "--steps", "2", "--warmup", "1", "--scene", args.scene, "--res", str(args.res), "--spp", str(args.spp),
              "--observer", str(args.observer), "--uplift", args.uplift, "--texture", args.texture, "--batch", str(args.batch), "--scratch-cap-gb", str(args.scratch_cap_gb)]
     env = dict(os.environ, TMPDIR="/tmp")
     got = {}
@@ -374,7 +398,7 @@ def measured_traffic(args, world):
             return by_kernel["path"], detail, "measured in this run: two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) over a child run of the same workload; FETCH_SIZE x 2 (gfx950 wide-read correction), KiB -> bytes; path kernel (traffic) and generate kernel (traffic_detail.bytes_per_launch)"
         why = detail
     else:
-        why = "--no-pmc" if world == 1 else "N > 1: counters are collected at N = 1"
+        why = ("--no-pmc" if args.full else "measured with --full only") if world == 1 else "N > 1: counters are collected at N = 1"
     try:
         t = json.load(open(path))
         detail = dict(t.get(key + " detail") or {})
@@ -539,9 +563,14 @@ def main():
     ap.add_argument("--dist-dry-run", action="store_true", help="no benchmark: go through the multi-GPU plumbing on whatever devices exist (process group, a timed framebuffer reduce, ssx_rccl_probe, per-rank scratch) and REPORT what was found in one JSON line")
     ap.add_argument("--update-traffic", action="store_true", help="also write the measured HBM traffic into the tracked replay file profiles/traffic.json (a round's closing run)")
     ap.add_argument("--quick", action="store_true", help="= --no-cpu-baseline --no-check --no-pmc (A/B and profiling scripts)")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline figure does not need: value_device_resident, the oracle check of the timed "
+                    "image, the ranks' records and partition (N > 1), HBM traffic by rocprofv3 --pmc passes (N = 1), the CPU baseline; a plain run does none of these")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's combined XYZA image (float32) to DIR/xyza.npy (rank 0)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)  # the run under rocprofv3 --pmc: renders, prints nothing
     args = ap.parse_args()
-    if args.pmc_child or args.quick:
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs --steps >= 1")
+    if args.pmc_child or args.quick or not args.full:
         args.no_check = args.no_cpu_baseline = args.no_pmc = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -671,22 +700,28 @@ def main():
     stage_ms = {k: v / max(args.steps, 1) for k, v in r.get_timing().items()}
     pipeline_ms = sum(stage_ms.values())  # the kernels of a step, first to last (events without a system fence: csrc/ssx_api.hip timing_events)
     r.set_timing(False)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_host_img)
     # The same K steps without the copy to the host (rounds 1-3 reported this figure as `value`): value_device_resident.
-    fence()
-    t1 = time.perf_counter()
-    for k in range(args.steps):
-        step()
-    fence()
-    elapsed_resident = time.perf_counter() - t1
+    elapsed_resident = None
+    if args.full:
+        fence()
+        t1 = time.perf_counter()
+        for k in range(args.steps):
+            step()
+        fence()
+        elapsed_resident = time.perf_counter() - t1
     # The integrator is two kernels since round 3: ssx_generate_kernel* (camera rays AND their closest hits, traced
     # coherently) and the path megakernel (everything behind the first hit).  The algorithmic flop figure of SURVEY 8(d)
     # covers both, so the roofline is quoted over both durations (rocprofv3: the two rows of kernel_stats.csv).
     path_ms = stage_ms["path"]
     kernel_ms = stage_ms["path"] + stage_ms["generate"]
     if use_dist:
-        tt = torch.tensor([elapsed, kernel_ms, elapsed_resident, path_ms], dtype=torch.float64, device="cpu" if test_one_gpu else "cuda")
+        tt = torch.tensor([elapsed, kernel_ms, elapsed_resident or 0.0, path_ms], dtype=torch.float64, device="cpu" if test_one_gpu else "cuda")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        elapsed, kernel_ms, elapsed_resident, path_ms = float(tt[0]), float(tt[1]), float(tt[2]), float(tt[3])
+        elapsed, kernel_ms, path_ms = float(tt[0]), float(tt[1]), float(tt[3])
+        if args.full:
+            elapsed_resident = float(tt[2])
     # ---- who took part: one record per rank, gathered on rank 0; a run in which two ranks share a device, or in which
     # two ranks' images overlap (a pixel nonzero on both: the partition is wrong), does not print a bench line.
     my_ms, my_path_ms = elapsed_local / max(args.steps, 1) * 1e3, stage_ms["path"]
@@ -704,7 +739,7 @@ def main():
     ranks = [me]
     overlap = None
     evidence_error = None
-    if use_dist:
+    if use_dist and args.full:
         # Every rank takes the same path through the collectives: the work that can fail on ONE rank -- an extra render, its
         # buffers -- comes first, without a collective in it; the ranks then agree on an ok flag (MIN), and only if every rank is fine do they
         # gather the records and sum the row masks.  A rank that failed reports why; nobody is left waiting in a collective the other skipped.
@@ -786,10 +821,8 @@ def main():
             "ms_per_step": round(elapsed / max(args.steps, 1) * 1e3, 3), "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             # `value`: every step ends with the combined image in (pinned) host memory on rank 0 -- the metric as SURVEY 8(d) defines it
-            # ("framebuffer reduce + D2H of XYZA included"); value_device_resident: the same steps without that copy (what rounds 1-3
+            # ("framebuffer reduce + D2H of XYZA included"); value_device_resident (--full): the same steps without that copy (what rounds 1-3
             # reported as `value`; value_host_inclusive is kept as an alias of `value` for readers of those rounds)
-            "value_device_resident": round(samples_per_step * args.steps / elapsed_resident / 1e6, 2),
-            "ms_per_step_device_resident": round(elapsed_resident / max(args.steps, 1) * 1e3, 3),
             "value_host_inclusive": round(value, 2),
             "config": {"workload": "%s %dx%d spp=%d/GPU (total spp %d) CIE%d uplift=%s hero-wavelength megakernel" % (args.scene, W, H, args.spp, spp_total, args.observer, args.uplift),
                        "parallelism": "tile-split x%d (round-robin over the tile list, rows rotated: tile_skew 1) + RCCL reduce" % world if world > 1 else ("single GPU + RCCL reduce (world size 1, SSX_BENCH_FORCE_DIST)" if force_dist else "single GPU"),
@@ -823,10 +856,13 @@ def main():
                          "plan": plan},
         }
         line["check"] = check
-        line["ranks"] = ranks
-        line["distributed"] = {"backend": dist.get_backend() if use_dist else None, "world_size": dist.get_world_size() if use_dist else 1,
-                               "devices_distinct": (len(set(devs)) == len(devs)) if len(ranks) == world else None, "overlap": overlap, "evidence_error": evidence_error,
-                               "slowest_rank_ms": max(x["ms_per_step"] for x in ranks), "fastest_rank_ms": min(x["ms_per_step"] for x in ranks)}
+        if args.full:
+            line["value_device_resident"] = round(samples_per_step * args.steps / elapsed_resident / 1e6, 2)
+            line["ms_per_step_device_resident"] = round(elapsed_resident / max(args.steps, 1) * 1e3, 3)
+            line["ranks"] = ranks
+            line["distributed"] = {"backend": dist.get_backend() if use_dist else None, "world_size": dist.get_world_size() if use_dist else 1,
+                                   "devices_distinct": (len(set(devs)) == len(devs)) if len(ranks) == world else None, "overlap": overlap, "evidence_error": evidence_error,
+                                   "slowest_rank_ms": max(x["ms_per_step"] for x in ranks), "fastest_rank_ms": min(x["ms_per_step"] for x in ranks)}
         # weak-scaling efficiency against a stated N = 1 figure (the driver computes its own from its per-N runs; this one names what it used)
         line["efficiency_vs_n1_reference"] = {"value": round(value / (world * n1["value"]), 4) if n1["value"] else None, "n1_value": n1["value"], "n1_source": n1["source"],
                                               "kernel_source_id": n1.get("kernel_source_id"), "refused": n1.get("refused")}

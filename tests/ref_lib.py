@@ -1,15 +1,39 @@
-"""ctypes access to oracle/_ref/*.so -- the reference's OWN self-contained sources (rgb2spec.c,
-Meng et al.'s spectrum_grid.h, lodepng.cpp), compiled in place from /root/reference by
-`make -C oracle ref` (TEST INFRASTRUCTURE).  The built files travel to the GPU box; where they are
-absent (a checkout without /root/reference) the tests that need them skip.
+"""What the reference's OWN self-contained sources (rgb2spec.c, Meng et al.'s spectrum_grid.h, lodepng.cpp) compute
+(TEST INFRASTRUCTURE): vectors() and meng_table() read tests/golden/ref_vectors.npz and ref_digests.json, which the tests
+use; the rest is ctypes access to oracle/_ref/*.so, those sources compiled in place by `make -C oracle ref` where the
+reference is at hand, from which tests/golden/make_ref_vectors.py records those files.
 """
 import ctypes as C
+import json
 import os
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_DIR = os.path.join(ROOT, "oracle", "_ref")
+VECTORS = os.path.join(ROOT, "tests", "golden", "ref_vectors.npz")      # what the tests need as data: the Meng grid, a PNG file
+DIGESTS = os.path.join(ROOT, "tests", "golden", "ref_digests.json")     # everything else: SHA-256 digests, error codes
+
+
+def vectors():
+    """the recorded outputs of the reference's code (tests/golden/make_ref_vectors.py): one dict of arrays and digests"""
+    if "vectors" not in _cache:
+        with np.load(VECTORS) as z:
+            v = {k: z[k] for k in z.files}
+        with open(DIGESTS) as f:
+            v.update(json.load(f))
+        _cache["vectors"] = v
+    return _cache["vectors"]
+
+
+def meng_table():
+    """The Meng et al. grid as the reference's header defines it (recorded in tests/golden/ref_vectors.npz): the dict of
+    meng_table_from_library()."""
+    v = vectors()
+    t = {k: int(v["meng_" + k]) for k in ("grid_w", "grid_h", "n_points", "n_samples")}
+    t.update({k: float(v["meng_" + k]) for k in ("sample_min", "sample_max", "equal_energy_reflectance")})
+    t.update(xy_to_uv=v["meng_xy_to_uv"], cells=v["meng_cells"], points=v["meng_points"])
+    return t
 
 
 def _load(name):
@@ -87,7 +111,7 @@ def lodepng_decode(path, rgba=False):
     return 0, arr
 
 
-def meng_table():
+def meng_table_from_library():
     """The Meng et al. grid as arrays read out of the reference's header (via libref_meng.so):
     dict(grid_w, grid_h, n_points, n_samples, sample_min, sample_max, xy_to_uv[6], cells[w*h,8] i32,
     points[n, 4+n_samples] f32)."""

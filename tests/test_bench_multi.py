@@ -23,7 +23,7 @@ def test_bench_two_ranks_json_line_and_image(tmp_path, launcher, world):
     env = dict(os.environ, SSX_BENCH_TEST_ONE_GPU="1", SSX_BENCH_DUMP=dump)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    args = ["--gpus", str(world), "--steps", "2", "--warmup", "1", "--res", "64", "--spp", "4", "--texture", "test-img.png", "--no-cpu-baseline"]
+    args = ["--gpus", str(world), "--steps", "2", "--warmup", "1", "--res", "64", "--spp", "4", "--texture", "test-img.png", "--full", "--no-cpu-baseline"]
     if launcher == "self-spawn":
         cmd = [sys.executable, os.path.join(ROOT, "bench.py")] + args
     else:
@@ -66,7 +66,7 @@ def test_bench_refuses_a_line_when_two_ranks_share_a_device(tmp_path):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "SSX_BENCH_TEST_ONE_GPU", "SSX_BENCH_FORCE_DIST"):
         env.pop(k, None)
     env["NCCL_DEBUG"] = "WARN"
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--res", "64", "--spp", "4", "--texture", "test-img.png", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--res", "64", "--spp", "4", "--texture", "test-img.png", "--full", "--no-cpu-baseline"]
     try:
         r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     except subprocess.TimeoutExpired:
@@ -87,7 +87,7 @@ def test_bench_one_rank_through_rccl(tmp_path):
         env.pop(k, None)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--res", "64", "--spp", "8",
-           "--texture", "test-img.png", "--no-cpu-baseline", "--no-pmc"]
+           "--texture", "test-img.png", "--full", "--no-cpu-baseline", "--no-pmc"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -113,7 +113,7 @@ def test_bench_measures_its_hbm_traffic_in_the_run(tmp_path):
     env = dict(os.environ, SSX_BENCH_TRAFFIC_JSON=tj)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "SSX_BENCH_TEST_ONE_GPU", "SSX_BENCH_FORCE_DIST", "SSX_BENCH_NO_PMC"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--res", "256", "--spp", "32", "--no-cpu-baseline", "--update-traffic"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--res", "256", "--spp", "32", "--full", "--no-cpu-baseline", "--update-traffic"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
@@ -158,3 +158,30 @@ def test_bench_dry_run_reports_the_multi_gpu_plumbing(world):
         assert x["sample_bytes_needed"] > 0 and x["scratch_after_upload"]["log_bytes"] > 0
     p = d["rccl_probe_single_process"]
     assert p["visible_devices"] >= 1 and p["returned"] == p["devices_reduced_ok"] == p["visible_devices"] and p["rccl"] == "ok" and p["reduce_elements_wrong"] == 0
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_its_steps_and_dumps_what_they_computed(tmp_path):
+    """A plain `bench.py --gpus 1` does only what its headline figure needs (no check, no second timing, no counters, no CPU baseline:
+    those are --full's), and --dump-outputs writes the combined image of the last timed step: the oracle's image, bit for bit."""
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "SSX_BENCH_TEST_ONE_GPU", "SSX_BENCH_FORCE_DIST", "SSX_BENCH_DUMP"):
+        env.pop(k, None)
+    out_dir = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--res", "64", "--spp", "8",
+           "--texture", "test-img.png", "--dump-outputs", str(out_dir)]
+    r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    line = json.loads(lines[0])
+    assert line["metric"].startswith("Msamples/s") and line["unit"] == "Msamples/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert abs(line["value"] - 64 * 64 * 8 / (line["ms_per_step"] * 1e3)) <= 0.02 * line["value"]
+    assert line["check"] is None and "cpu_baseline" not in line and "value_device_resident" not in line and "ranks" not in line
+    assert "REPLAYED" in (line["roofline"]["traffic_source"] or "REPLAYED")
+    assert sorted(os.listdir(out_dir)) == ["xyza.npy"]
+    img = np.load(out_dir / "xyza.npy")
+    assert img.dtype == np.float32 and img.shape == (64, 64, 4)
+    ref = ol.Oracle("cornell-srgb", texture="test-img.png").render(64, 64, 8)
+    assert np.array_equal(img.view(np.uint32), ref.view(np.uint32))

@@ -363,12 +363,10 @@ def test_without_explicit_light_sampling_bit_exact(scene):
 
 @pytest.fixture(scope="module")
 def meng_grid(tmp_path_factory):
-    """The Meng et al. grid, read out of the reference's own header through oracle/_ref/libref_meng.so
-    (built in place by `make -C oracle ref`; the .so travels to the GPU box, the header does not)."""
+    """The Meng et al. grid, as read out of the reference's own header through oracle/_ref/libref_meng.so
+    (recorded in tests/golden/ref_vectors.npz by tests/golden/make_ref_vectors.py)."""
     import ref_lib
     from simple_spectral_amd import meng
-    if ref_lib.meng() is None:
-        pytest.skip("oracle/_ref/libref_meng.so not built (needs /root/reference at build time)")
     table = ref_lib.meng_table()
     path = str(tmp_path_factory.mktemp("meng") / "grid.bin")
     meng.save_table(path, table)

@@ -1,13 +1,17 @@
-"""Pins against the REAL reference code (oracle/_ref, built in place from /root/reference by
-`make -C oracle ref`): the three self-contained third-party pieces the reference vendors.
+"""Pins against the REAL reference code: the three self-contained third-party pieces the reference vendors, compiled as they are
+(oracle/_ref, `make -C oracle ref`), with their outputs on the inputs below recorded in tests/golden/ref_vectors.npz by
+tests/golden/make_ref_vectors.py.  The pins compare against that record, so they need nothing outside the repository.
 
   * rgb2spec.c  (src/jakob-and-hanika-2019/rgb2spec.c:60-134)  <- oracle + host JH fetch/eval + file format
   * lodepng.cpp (src/util/lodepng/)                            <- the host's own PNG decoder / encoder
   * spectrum_grid.h (src/meng-et-al.-2015/)                    <- oracle Meng restatement (test_meng_*)
 
-CPU only.  Skipped when oracle/_ref is absent and cannot be built (no /root/reference).
+CPU only.  The reference's outputs are recorded as SHA-256 digests of blocks of BLOCK rows (bit equality, as before, in a file a
+fraction of their size); the PNG files are generated here from fixed seeds and each recorded decode carries the SHA-256 of the file it
+was taken on.
 """
 import ctypes as C
+import hashlib
 import os
 import struct
 import zlib
@@ -27,60 +31,99 @@ def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
-def same_or_both_nan(a, b):
-    a = np.asarray(a, np.float32); b = np.asarray(b, np.float32)
-    return bool(np.all((bits(a) == bits(b)) | (np.isnan(a) & np.isnan(b))))
+def file_sha(path):
+    return hashlib.sha256(open(path, "rb").read()).hexdigest()
+
+
+def array_sha(a):
+    a = np.ascontiguousarray(a)
+    return hashlib.sha256(repr((a.dtype.str, a.shape)).encode() + a.tobytes()).hexdigest()
+
+
+BLOCK = 1024
+
+
+def block_shas(a):
+    """SHA-256 of each run of BLOCK rows: what the reference's outputs are recorded as (every bit counts; a mismatch names its rows)"""
+    a = np.ascontiguousarray(a)
+    return [array_sha(a[i:i + BLOCK]) for i in range(0, len(a), BLOCK)]
+
+
+def assert_same_bits(got, want_shas, what):
+    have = block_shas(got)
+    assert len(have) == len(want_shas), (what, len(got))
+    bad = [i for i, (x, y) in enumerate(zip(have, want_shas)) if x != y]
+    assert not bad, "%s differs from the reference's output in rows %d..%d (and %d more blocks of %d)" % (
+        what, bad[0] * BLOCK, min(len(got), bad[0] * BLOCK + BLOCK) - 1, len(bad) - 1, BLOCK)
+
+
+def canonical_nan(a):
+    """one bit pattern for every NaN (the pins compare NaN with NaN of any payload)"""
+    a = np.array(a, np.float32)
+    a[np.isnan(a)] = np.float32("nan")
+    return a
+
+
+@pytest.fixture(scope="module")
+def ref():
+    """what the reference's code returned (tests/golden/make_ref_vectors.py)"""
+    return ref_lib.vectors()
 
 
 # ------------------------------------------------------------------------------------------------
 # Jakob-Hanika: reference loader reads the file the host wrote; fetch/eval bit-identical
 # ------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def jh_setup(tmp_path_factory):
-    lib = ref_lib.rgb2spec()
-    if lib is None:
-        pytest.skip("oracle/_ref/libref_rgb2spec.so not built (needs /root/reference)")
-    path = str(tmp_path_factory.mktemp("jh") / "model.coeff")
-    scene = Scene("cornell-srgb", texture="test-img.png", uplift="jh", jh_res=16, jh_coeff_path=path)
-    res, scale, data = scene.jh_model()
-    model = lib.rgb2spec_load(path.encode())
-    assert bool(model), "the reference's rgb2spec_load rejected the file written by the host"
-    orc = ol.Oracle("cornell-srgb", texture="test-img.png", jh=(res, scale, data))
-    yield lib, model, orc, (res, scale, data)
-    lib.rgb2spec_free(model)
+def jh_scene(path):
+    return Scene("cornell-srgb", texture="test-img.png", uplift="jh", jh_res=16, jh_coeff_path=path)
 
 
-def test_jh_file_written_by_host_loads_in_reference(jh_setup):
-    lib, model, _, (res, scale, data) = jh_setup
-    m = model.contents
-    assert m.res == res                                                      # rgb2spec.c:28-33 header "SPEC", res
-    assert np.array_equal(np.ctypeslib.as_array(m.scale, shape=(res,)), scale)
-    assert np.array_equal(np.ctypeslib.as_array(m.data, shape=(data.size,)), data)
-
-
-def test_jh_fetch_and_eval_bit_identical_to_reference(jh_setup):
-    lib, model, orc, _ = jh_setup
+def jh_inputs():
     rng = np.random.default_rng(7)
     rgbs = [rng.random(3, dtype=np.float32) for _ in range(20000)]
     rgbs += [np.array(v, np.float32) for v in ([1, 1, 1], [1, 0, 0], [0, 1, 0], [0, 0, 1], [0.5, 0.5, 0.5], [0.2, 0.2, 0.7],
                                                [0.7, 0.7, 0.2], [1, 1, 0.999], [1e-6, 1e-7, 1e-8], [0, 0, 0], [0.25, 0.25, 0.25])]
     rgbs += [np.round(rng.random(3) * 255).astype(np.float32) / np.float32(255) for _ in range(5000)]   # texel-like
-    fp = C.POINTER(C.c_float)
     lams = np.concatenate([np.linspace(380, 780, 9, dtype=np.float32), rng.uniform(380, 780, 7).astype(np.float32)])
-    n_nan = 0
-    for rgb in rgbs:
-        ref = np.zeros(3, np.float32); got = np.zeros(3, np.float32)
-        lib.rgb2spec_fetch(model, rgb.ctypes.data_as(fp), ref.ctypes.data_as(fp))
+    return rgbs, lams
+
+
+def jh_eval_lams(k, lams):
+    return lams if k == 0 else lams[:4]
+
+
+@pytest.fixture(scope="module")
+def jh_setup(tmp_path_factory, ref):
+    path = str(tmp_path_factory.mktemp("jh") / "model.coeff")
+    scene = jh_scene(path)
+    res, scale, data = scene.jh_model()
+    assert file_sha(path) == str(ref["jh_file_sha256"]), "the host wrote another file than the one the reference's rgb2spec_load read"
+    orc = ol.Oracle("cornell-srgb", texture="test-img.png", jh=(res, scale, data))
+    return orc, (res, scale, data)
+
+
+def test_jh_file_written_by_host_loads_in_reference(jh_setup, ref):
+    _, (res, scale, data) = jh_setup
+    assert int(ref["jh_res"]) == res                                         # rgb2spec.c:28-33 header "SPEC", res
+    assert array_sha(np.asarray(scale, np.float32).reshape(-1)) == ref["jh_scale_sha256"]
+    assert array_sha(np.asarray(data, np.float32).reshape(-1)) == ref["jh_data_sha256"]
+
+
+def test_jh_fetch_and_eval_bit_identical_to_reference(jh_setup, ref):
+    orc, _ = jh_setup
+    rgbs, lams = jh_inputs()
+    assert array_sha(np.array(rgbs)) + array_sha(lams) == str(ref["jh_inputs_sha256"])             # the inputs the reference was run on
+    fp = C.POINTER(C.c_float)
+    fetched = np.zeros((len(rgbs), 3), np.float32)
+    evals = []
+    for k, rgb in enumerate(rgbs):
+        got = fetched[k]
         orc.lib.orc_jh_fetch(orc.color, rgb.ctypes.data_as(fp), got.ctypes.data_as(fp))
-        assert same_or_both_nan(ref, got), (rgb, ref, got)
-        n_nan += int(np.isnan(ref).any())
-        if np.isnan(ref).any():
+        if np.isnan(got).any():
             continue
-        for lam in lams[:4] if rgb is not rgbs[0] else lams:
-            a = lib.rgb2spec_eval_precise(ref.ctypes.data_as(fp), C.c_float(lam))
-            b = orc.lib.orc_jh_eval_precise(got.ctypes.data_as(fp), C.c_float(lam))
-            assert struct.pack("f", a) == struct.pack("f", b), (rgb, lam, a, b)
-    assert n_nan == 1          # only black divides by zero (rgb2spec.c:88)
+        evals += [orc.lib.orc_jh_eval_precise(got.ctypes.data_as(fp), C.c_float(lam)) for lam in jh_eval_lams(k, lams)]
+    assert_same_bits(canonical_nan(fetched), ref["jh_fetch_sha256"], "rgb2spec_fetch")
+    assert_same_bits(np.array(evals, np.float32), ref["jh_eval_sha256"], "rgb2spec_eval_precise")
+    assert int(np.isnan(fetched).any(axis=1).sum()) == 1          # only black divides by zero (rgb2spec.c:88)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -169,42 +212,40 @@ def host_decode(path):
     return 0, arr
 
 
-@pytest.fixture(scope="module")
-def png_ref():
-    if ref_lib.lodepng() is None:
-        pytest.skip("oracle/_ref/libref_lodepng.so not built (needs /root/reference)")
-    return ref_lib
-
-
-def test_png_decoder_matches_lodepng_on_shipped_textures(png_ref):
+def test_png_decoder_matches_lodepng_on_shipped_textures(ref):
     for name in ("test-img.png", "crystal-lizard-512.png"):
         p = os.path.join(DATA, "scenes", name)
-        err, ref = png_ref.lodepng_decode(p)
+        assert file_sha(p) == str(ref["png_shipped_%s_sha256" % name]), name
         rc, got = host_decode(p)
-        assert err == 0 and rc == 0
-        assert np.array_equal(ref, got), name
+        assert rc == 0
+        assert array_sha(got) == str(ref["png_shipped_%s_decoded_sha256" % name]), name
 
 
 VARIANTS = [(0, d) for d in (1, 2, 4, 8, 16)] + [(2, 8), (2, 16)] + [(3, d) for d in (1, 2, 4, 8)] + [(4, 8), (4, 16), (6, 8), (6, 16)]
 
 
-@pytest.mark.parametrize("interlace", [0, 1])
-@pytest.mark.parametrize("ctype,depth", VARIANTS)
-def test_png_decoder_matches_lodepng_on_every_variant(png_ref, tmp_path, ctype, depth, interlace):
+def png_variant_files(tmp_path, ctype, depth, interlace):
     rng = np.random.default_rng(100 * ctype + depth + 7 * interlace)
     for (w, h) in ((1, 1), (3, 2), (5, 9), (8, 8), (13, 17), (33, 5)):
-        p = str(tmp_path / ("v_%d_%d_%d_%dx%d.png" % (ctype, depth, interlace, w, h)))
+        key = "png_var_%d_%d_%d_%dx%d" % (ctype, depth, interlace, w, h)
+        p = os.path.join(str(tmp_path), key + ".png")
         make_png(p, w, h, ctype, depth, interlace, rng, palette_size=min(1 << depth, 200) if ctype == 3 else None)
-        err, ref = png_ref.lodepng_decode(p)
+        yield key, p
+
+
+@pytest.mark.parametrize("interlace", [0, 1])
+@pytest.mark.parametrize("ctype,depth", VARIANTS)
+def test_png_decoder_matches_lodepng_on_every_variant(ref, tmp_path, ctype, depth, interlace):
+    for key, p in png_variant_files(tmp_path, ctype, depth, interlace):
+        assert file_sha(p) == str(ref[key + "_sha256"]), key      # the file lodepng decoded (0 = no error: make_ref_vectors.py)
         rc, got = host_decode(p)
-        assert err == 0, "lodepng rejected the generated file (%d)" % err
         assert rc == 0
-        assert np.array_equal(ref, got), (ctype, depth, interlace, w, h)
+        assert array_sha(got) == ref[key + "_decoded_sha256"], key
 
 
-def test_png_decoder_rejects_what_lodepng_rejects(png_ref, tmp_path):
+def png_bad_files(tmp_path):
     rng = np.random.default_rng(3)
-    good = str(tmp_path / "good.png")
+    good = os.path.join(str(tmp_path), "good.png")
     make_png(good, 9, 7, 2, 8, 0, rng)
     blob = open(good, "rb").read()
     cases = {"sig": b"\x88" + blob[1:], "crc": blob[:40] + bytes([blob[40] ^ 1]) + blob[41:], "trunc": blob[:len(blob) // 2],
@@ -215,29 +256,39 @@ def test_png_decoder_rejects_what_lodepng_rejects(png_ref, tmp_path):
     payload = bytearray(blob[ihdr_end + 8:ihdr_end + 8 + ln]); payload[len(payload) // 2] ^= 0x55; payload[0] ^= 0x0F
     cases["zlib"] = blob[:ihdr_end] + _chunk(b"IDAT", bytes(payload)) + blob[ihdr_end + 12 + ln:]
     for name, data in cases.items():
-        p = str(tmp_path / ("bad_%s.png" % name))
+        p = os.path.join(str(tmp_path), "bad_%s.png" % name)
         open(p, "wb").write(data)
-        err, _ = png_ref.lodepng_decode(p)
+        yield name, p
+
+
+def test_png_decoder_rejects_what_lodepng_rejects(ref, tmp_path):
+    for name, p in png_bad_files(tmp_path):
+        assert file_sha(p) == str(ref["png_bad_%s_sha256" % name]), name
         rc, _ = host_decode(p)
-        assert err != 0, name
+        assert int(ref["png_bad_%s_error" % name]) != 0, name
         assert rc == -1, name                      # "Could not load texture" -> SSX_ERR_DATA (src/material.cpp:15-18)
 
 
-def test_png_writer_round_trips_through_lodepng_and_back(png_ref, tmp_path):
-    """Framebuffer::save PNG branch (src/framebuffer.cpp:148-171): clamp, *255, round, flip, RGBA8."""
+def png_writer_inputs():
     rng = np.random.default_rng(11)
     W, H = 37, 21
     fb = rng.uniform(-0.2, 1.3, size=(H, W, 4)).astype(np.float32)
     fb[0, 0] = (0.5 / 255, 1.5 / 255, 2.5 / 255, 1.0)                        # round-half cases
+    expect = np.floor(np.clip(fb, 0.0, 1.0).astype(np.float32) * np.float32(255.0) + np.float32(0.5)).astype(np.uint8)[::-1].copy()
+    return fb, expect
+
+
+def test_png_writer_round_trips_through_lodepng_and_back(ref, tmp_path):
+    """Framebuffer::save PNG branch (src/framebuffer.cpp:148-171): clamp, *255, round, flip, RGBA8."""
+    fb, expect = png_writer_inputs()
+    H, W = fb.shape[:2]
     ours = str(tmp_path / "ours.png")
     assert _capi.host_lib().ssh_save_image(ours.encode(), fb.ctypes.data, W, H) == 0
-    err, dec = png_ref.lodepng_decode(ours, rgba=True)
-    assert err == 0
-    expect = np.floor(np.clip(fb, 0.0, 1.0).astype(np.float32) * np.float32(255.0) + np.float32(0.5)).astype(np.uint8)[::-1].copy()
-    assert np.array_equal(dec, expect)
+    assert file_sha(ours) == str(ref["png_writer_ours_sha256"])             # the file lodepng decoded (RGBA) to:
+    assert ref["png_writer_ours_decoded_sha256"] == array_sha(expect)
     # and a file written by the reference's encoder decodes identically with the host's decoder
     theirs = str(tmp_path / "theirs.png")
-    assert png_ref.lodepng().ref_png_encode_rgba8(theirs.encode(), expect.ctypes.data, W, H) == 0
+    ref["png_writer_theirs_file"].tofile(theirs)
     rc, got = host_decode(theirs)
     assert rc == 0 and np.array_equal(got, expect[..., :3])
 
@@ -246,13 +297,10 @@ def test_png_writer_round_trips_through_lodepng_and_back(png_ref, tmp_path):
 # Meng et al. 2015: oracle restatement against the reference's own spectrum_xyz_to_p
 # ------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def meng_setup():
-    lib = ref_lib.meng()
-    if lib is None:
-        pytest.skip("oracle/_ref/libref_meng.so not built (needs /root/reference)")
+def meng_setup(ref):
     table = ref_lib.meng_table()
     orc = ol.Oracle("cornell-srgb", texture="test-img.png", meng=table)
-    return lib, table, orc
+    return ref, table, orc
 
 
 def test_meng_grid_shape(meng_setup):
@@ -262,44 +310,58 @@ def test_meng_grid_shape(meng_setup):
     assert t["cells"][:, 1].max() <= 6 and t["cells"][:, 2:].max() < t["n_points"]
 
 
-def test_meng_xyz_to_p_bit_identical_to_reference(meng_setup):
-    lib, t, orc = meng_setup
+def meng_xyz_to_p_inputs():
     rng = np.random.default_rng(5)
-    fp = C.POINTER(C.c_float)
     M = np.array([[0.41231515, 0.3576, 0.1805], [0.2126, 0.7152, 0.0722], [0.01932727, 0.1192, 0.95063333]], np.float32) * np.float32(100)
     xyzs = [(M @ rng.random(3, dtype=np.float32)).astype(np.float32) for _ in range(30000)]          # in-gamut colours
     xyzs += [rng.random(3, dtype=np.float32) * np.float32(100) for _ in range(30000)]                # anything, incl. outside the grid
     xyzs += [np.array(v, np.float32) for v in ([0, 0, 0], [1, 1, 1], [100, 0, 0], [0, 100, 0], [0, 0, 100], [1e-30, 1e-30, 1e-30],
                                                [1e-40, 0, 0], [95.047, 100.0, 108.883])]
     lams = [380.0, 780.0, 555.5, 400.0, 779.999]
-    n_nonzero = 0; n_fan = 0
-    for k, xyz in enumerate(xyzs):
-        for lam in (lams if k % 50 == 0 else (float(rng.uniform(380, 780)),)):
-            a = lib.ref_meng_xyz_to_p(C.c_float(lam), xyz.ctypes.data_as(fp))
-            b = orc.lib.orc_meng_xyz_to_p(orc.color, C.c_float(lam), xyz.ctypes.data_as(fp))
-            assert struct.pack("f", a) == struct.pack("f", b), (xyz, lam, a, b)
-            n_nonzero += a != 0.0
-    assert n_nonzero > 40000          # both the bilinear cells and the boundary fans were exercised
+    xyz, lam = [], []
+    for k, v in enumerate(xyzs):
+        for l in (lams if k % 50 == 0 else (float(rng.uniform(380, 780)),)):
+            xyz.append(v); lam.append(l)
+    return np.array(xyz, np.float32), np.array(lam, np.float32)
+
+
+def test_meng_xyz_to_p_bit_identical_to_reference(meng_setup):
+    ref, t, orc = meng_setup
+    fp = C.POINTER(C.c_float)
+    xyzs, lams = meng_xyz_to_p_inputs()
+    assert array_sha(xyzs) + array_sha(lams) == str(ref["meng_xyz_to_p_inputs_sha256"])          # the inputs the reference was run on
+    got = np.array([orc.lib.orc_meng_xyz_to_p(orc.color, C.c_float(lam), xyz.ctypes.data_as(fp)) for xyz, lam in zip(xyzs, lams)], np.float32)
+    assert_same_bits(got, ref["meng_xyz_to_p_sha256"], "spectrum_xyz_to_p")
+    assert int((got != 0.0).sum()) > 40000          # both the bilinear cells and the boundary fans were exercised
+
+
+def meng_specrefl_inputs():
+    """-> the texels' linear RGB and first hero wavelengths, and what the reference function is asked for: xyz [n, 3] at the four
+    hero wavelengths [n, 4]"""
+    rng = np.random.default_rng(6)
+    rows = np.array([[0.41231515, 0.3576, 0.1805], [0.2126, 0.7152, 0.0722], [0.01932727, 0.1192, 0.95063333]], np.float32)
+    m100 = rows * np.float32(100.0)
+    lrgbs, lam0s, xyzs, lams = [], [], [], []
+    for _ in range(2000):
+        lrgb = rng.random(3, dtype=np.float32)
+        lam0 = np.float32(rng.uniform(380, 480))
+        lrgbs.append(lrgb); lam0s.append(lam0)
+        xyzs.append(((m100[:, 0] * lrgb[0] + m100[:, 1] * lrgb[1]) + m100[:, 2] * lrgb[2]).astype(np.float32))
+        lams.append([np.float32(lam0 + np.float32(i) * np.float32(100.0)) for i in range(4)])
+    return lrgbs, lam0s, np.array(xyzs, np.float32), np.array(lams, np.float32)
 
 
 def test_meng_lrgb_to_specrefl_uses_reference_function(meng_setup):
     """color.cpp:175-201: the oracle's per-texel uplift = reference spectrum_xyz_to_p at the 4 hero wavelengths."""
-    lib, t, orc = meng_setup
+    ref, t, orc = meng_setup
     fp = C.POINTER(C.c_float)
-    rng = np.random.default_rng(6)
     orc.lib.orc_lrgb_to_specrefl.argtypes = [C.c_void_p, fp, C.c_float, fp]
-    rows = np.array([[0.41231515, 0.3576, 0.1805], [0.2126, 0.7152, 0.0722], [0.01932727, 0.1192, 0.95063333]], np.float32)
-    for _ in range(2000):
-        lrgb = rng.random(3, dtype=np.float32)
-        lam0 = np.float32(rng.uniform(380, 480))
-        out = np.zeros(4, np.float32)
-        orc.lib.orc_lrgb_to_specrefl(orc.color, lrgb.ctypes.data_as(fp), C.c_float(lam0), out.ctypes.data_as(fp))
-        m100 = rows * np.float32(100.0)
-        xyz = ((m100[:, 0] * lrgb[0] + m100[:, 1] * lrgb[1]) + m100[:, 2] * lrgb[2]).astype(np.float32)
-        for i in range(4):
-            lam = np.float32(lam0 + np.float32(i) * np.float32(100.0))
-            ref = lib.ref_meng_xyz_to_p(C.c_float(lam), xyz.ctypes.data_as(fp))
-            assert struct.pack("f", ref) == struct.pack("f", out[i])
+    lrgbs, lam0s, xyzs, lams = meng_specrefl_inputs()
+    assert array_sha(xyzs) + array_sha(lams) == str(ref["meng_specrefl_inputs_sha256"])          # the inputs the reference was run on
+    out = np.zeros((len(lrgbs), 4), np.float32)
+    for k, (lrgb, lam0) in enumerate(zip(lrgbs, lam0s)):
+        orc.lib.orc_lrgb_to_specrefl(orc.color, lrgb.ctypes.data_as(fp), C.c_float(lam0), out[k].ctypes.data_as(fp))
+    assert_same_bits(out, ref["meng_specrefl_sha256"], "spectrum_xyz_to_p at the hero wavelengths")
 
 
 def test_meng_header_converter_file_format_and_host_scene(meng_setup, tmp_path):

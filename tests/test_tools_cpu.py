@@ -95,3 +95,22 @@ def test_runtime_preload_reads_sonames_from_the_elf_files():
     assert "libz.so.1" in needed or any(n.startswith("libz") for n in needed)
     assert _capi._elf_dynamic(__file__) == (None, [])          # not an ELF file
     assert _capi._elf_dynamic("/nonexistent") == (None, [])
+
+
+def test_bench_dump_outputs_writes_the_image_or_a_fixed_sample_of_it(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the image as it is up to the size cap; above it, the same seeded sample of its pixels in every run."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    img = np.random.default_rng(1).random((32, 48, 4)).astype(np.float32)
+    bench.dump_outputs(str(tmp_path / "a"), img)
+    assert os.listdir(tmp_path / "a") == ["xyza.npy"] and np.array_equal(np.load(tmp_path / "a" / "xyza.npy"), img)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 16 * 100)
+    bench.dump_outputs(str(tmp_path / "b"), img)
+    bench.dump_outputs(str(tmp_path / "c"), img)
+    assert os.listdir(tmp_path / "b") == ["xyza_sample.npy"]
+    s = np.load(tmp_path / "b" / "xyza_sample.npy")
+    assert s.dtype == np.float32 and s.shape == (100, 4) and s.nbytes <= bench.DUMP_MAX_BYTES
+    assert np.array_equal(s, np.load(tmp_path / "c" / "xyza_sample.npy"))
+    px = {tuple(p) for p in img.reshape(-1, 4).tolist()}
+    assert all(tuple(p) in px for p in s.tolist()) and len({tuple(p) for p in s.tolist()}) == 100

@@ -5,9 +5,9 @@
 # (FORMAL_N, FUZZ_FIRST, FUZZ_N, WARPED_FIRST, WARPED_N from the environment)
 O=gpurun_out/${1:-closing}; mkdir -p $O $O/plane
 python -m pytest tests -m gpu -q -rf > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?"; grep -E "^FAILED|^ERROR| passed| failed" $O/pytest_gpu.log | tail -3 | cut -c1-300
-python bench.py --steps 20 --warmup 5 --update-traffic > $O/bench.json 2> $O/bench.err; python -c "
+python bench.py --full --steps 20 --warmup 5 --update-traffic > $O/bench.json 2> $O/bench.err; python -c "
 import json; d=json.load(open('$O/bench.json')); print({k:d[k] for k in ('value','ms_per_step','value_device_resident')}, d['roofline']['frac'], d['roofline']['stage_ms'], d['roofline']['traffic'], d['cpu_baseline']['value'], d['cpu_baseline']['reference_equivalent']['value'])"
-python bench.py --steps 10 --warmup 2 --scene plane-srgb --res 1024 --spp 1024 --update-traffic > $O/plane/bench.json 2> $O/plane/bench.err; python -c "
+python bench.py --full --steps 10 --warmup 2 --scene plane-srgb --res 1024 --spp 1024 --update-traffic > $O/plane/bench.json 2> $O/plane/bench.err; python -c "
 import json; d=json.load(open('$O/plane/bench.json')); r=d['roofline']; print('plane', {k:d[k] for k in ('value','ms_per_step')}, r['frac'], r['frac_without_eliminated_work'], r['stage_ms'], r['traffic'], r['hbm']['traffic_bytes_per_sample'], d['check']['differing_floats'], d['cpu_baseline']['value'])"
 bash tools/profile_round.sh ${1:-closing}/prof > $O/profile_round.log 2>&1; tail -2 $O/profile_round.log | cut -c1-200
 BENCH_ARGS="--scene plane-srgb --res 1024 --spp 1024" bash tools/profile_round.sh ${1:-closing}/plane/prof > $O/plane/profile_round.log 2>&1; tail -2 $O/plane/profile_round.log | cut -c1-200
