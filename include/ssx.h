@@ -32,7 +32,7 @@ extern "C" {
  *      SSX_MAX_TEXTURES and the struct sizes grew; ssx_set_jit takes a mode (default: background compilation); ssx_jit_status,
  *      ssx_jit_counters, ssx_sums_info, ssx_rccl_groups_made, ssx_done_tiles and ssx_render_params.tile_major and tile_skew (the
  *      struct grew by 8 bytes) are new.  Added since without a change of existing entry points or structures (same version): ssx_units_info,
- *      ssx_rccl_probe (round 6). */
+ *      ssx_rccl_probe (round 6); ssx_render_params.libm, appended (a caller with the struct_size before it gets SSX_LIBM_BUILD). */
 #define SSX_ABI_VERSION 2
 
 enum {
@@ -181,7 +181,15 @@ typedef struct ssx_render_params {
 	                             the image does not depend on it.  Any value is accepted and taken modulo the number of tile columns (the
 	                             rotation (ty * tile_skew) % tiles_x is what enters: kernels, C++ host and Python mask agree for every value). */
 	uint64_t seed;            /* seeding contract below */
+	uint32_t libm;            /* Which sinf / cosf / acosf the integrator evaluates (the reference calls the platform's, src/util/random.cpp,
+	                             src/util/spherical-tri.cpp).  SSX_LIBM_BUILD (0, default): the functions include/ssx_fmath.h defines, the same
+	                             on every platform.  SSX_LIBM_GLIBC_2_35: glibc 2.35's x86-64 functions (FMA variant), restated by
+	                             include/ssx_glibc_math.h -- the image of the reference built and run on a stock x86-64 glibc 2.35 system.  The
+	                             kernels are the *_glibc twins of the default ones.  Other values: SSX_ERR_ARG.  (Appended: a caller that passes
+	                             struct_size = offsetof(ssx_render_params, libm) gets SSX_LIBM_BUILD.) */
+	uint32_t reserved3;       /* padding (the struct's size is a multiple of 8); ignored */
 } ssx_render_params;
+enum { SSX_LIBM_BUILD = 0, SSX_LIBM_GLIBC_2_35 = 1 };
 
 /* Seeding contract (build-defined; the shipped reference is racy):
  * sample k of pixel p=j*W+i uses its own PCG32 stream
@@ -312,7 +320,11 @@ int ssx_kernel_variant(ssx_ctx* ctx);
  *   SSX_JIT_AT_UPLOAD             ssx_upload_scene compiles on the calling thread when nobody has the code yet.
  *   SSX_JIT_OFF                   generic kernel.
  * Same bits in every case.  A failure of any kind -- no libhiprtc, no HIP headers ($SSX_ROCM_INCLUDE, $ROCM_PATH/include,
- * /opt/rocm/include), a compile error, an unwritable cache -- leaves the scene on the generic kernel; ssx_jit_status tells. */
+ * /opt/rocm/include), a compile error, an unwritable cache -- leaves the scene on the generic kernel; ssx_jit_status tells.
+ * libm (ssx_render_params.libm): the two modes' kernels of a pattern are separate code objects (and cache files).  SSX_JIT_AT_UPLOAD compiles
+ * the default mode's; SSX_JIT_BACKGROUND asks for those of the libm the context renders in at the time.  Once the context runs its own
+ * kernels, the first render in the other libm compiles that mode's on the calling thread (or takes them from memory / the disk cache);
+ * should that fail, the render fails (SSX_ERR_STATE: the generic kernels cannot read the specialised scene tables). */
 enum { SSX_JIT_OFF = 0, SSX_JIT_AT_UPLOAD = 1, SSX_JIT_BACKGROUND = 2 };
 int ssx_set_jit(ssx_ctx* ctx, int mode);
 /* Where the uploaded scene's own kernels stand.  wait_ms != 0 first asks for the compilation if nobody has (whatever the context has
@@ -327,7 +339,8 @@ int ssx_jit_status(ssx_ctx* ctx, int wait_ms, char* message, size_t message_size
 void ssx_jit_counters(uint64_t* compiled, uint64_t* disk_hits);
 /* The name of the path kernel the context launches for the uploaded scene, as a profiler lists it
  * ("ssx_render_kernel", "..._cornell", "..._plane", each also with "_nq": the variants with narrow shadow-ray
- * queue entries, taken where they let one more workgroup live on a CU).  NULL: no scene. */
+ * queue entries, taken where they let one more workgroup live on a CU; after a render with libm = SSX_LIBM_GLIBC_2_35
+ * the same names with "_glibc" appended -- the run-time compiled "ssx_render_kernel_jit" keeps its name).  NULL: no scene. */
 const char* ssx_kernel_name(ssx_ctx* ctx);
 
 /* ---- Diagnostics for the parity tests (not part of the reference's interface) ---------------------
@@ -344,7 +357,10 @@ enum {
 	SSX_DBG_RAND_CHOICE = 7,  /* in: rng[4], n                          out: choice, rng state lo, hi (src/util/random.hpp:75-78) */
 	SSX_DBG_ALBEDO = 8,       /* in: quad, st[2], lambda_0              out: albedo[4] (src/material.cpp:45-143) */
 	SSX_DBG_FLUX_TO_XYZ = 9,  /* in: flux[4], lambda_0                  out: X, Y, Z (src/util/color.hpp:115-139) */
-	SSX_DBG_RAND_1F = 10      /* in: rng[4]                             out: rand_1f, rng state lo, hi (src/util/random.hpp:68-70) */
+	SSX_DBG_RAND_1F = 10,     /* in: rng[4]                             out: rand_1f, rng state lo, hi (src/util/random.hpp:68-70) */
+	/* libm = glibc-2.35 (ssx_render_params.libm): the units the _glibc kernels inline, same inputs and outputs as the op above them */
+	SSX_DBG_GLIBC_MATH = 11,  /* in: x                                  out: sinf, cosf, acosf, sincosf.s, sincosf.c (include/ssx_glibc_math.h) */
+	SSX_DBG_SPHTRI_GLIBC = 12, SSX_DBG_ARVO_GLIBC = 13, SSX_DBG_SAMPLE_LIGHT_GLIBC = 14, SSX_DBG_COSHEMI_GLIBC = 15
 };
 /* rng[4] = PCG32 {state lo, state hi, inc lo, inc hi} */
 /* ssx_debug_sweep: device-side comparison of a cheaper device function with the function that DEFINES the
@@ -367,7 +383,13 @@ enum {
 	 * value the independent evaluation decides on (or not NaN outside the domain; for sin and cos also: where ssx_sincosf returns another
 	 * float than ssx_sinf / ssx_cosf), result[1] = inputs whose value lies within 2^-70 of a
 	 * float rounding boundary, which it does not decide; examples (result[3..]): the input pattern, | 1 << 32 for an undecided one */
-	SSX_SWEEP_SIN_PROOF = 11, SSX_SWEEP_COS_PROOF = 12, SSX_SWEEP_ACOS_PROOF = 13
+	SSX_SWEEP_SIN_PROOF = 11, SSX_SWEEP_COS_PROOF = 12, SSX_SWEEP_ACOS_PROOF = 13,
+	/* libm = glibc-2.35, run with the LDS table of the _glibc kernels.  Digests of include/ssx_glibc_math.h as the device evaluates it, for the
+	 * host to recompute with the same header: result[1] = sum over the patterns x of splitmix64(x << 32 | f(x)) mod 2^64, any NaN result
+	 * counted as 0x7FC00000; result[0] = inputs where ssx_glibc_sincosf returns another float than ssx_glibc_sinf / ssx_glibc_cosf. */
+	SSX_SWEEP_GLIBC_SIN = 14, SSX_SWEEP_GLIBC_COS = 15, SSX_SWEEP_GLIBC_ACOS = 16,
+	SSX_SWEEP_GLIBC_COS_LDS = 17 /* the one ssx_fmath.h function the _glibc kernels keep (ssx_cosf_lds, random.cpp:134) with their LDS
+	                                table vs ssx_cosf: result[0] = mismatches */
 };
 int ssx_debug_sweep(ssx_ctx* ctx, uint32_t op, uint32_t lo, uint64_t count, uint64_t result[11]);
 /* The text of the pass-1 function ssx_set_jit would compile for the sharing pattern vid[n_quads][4] (distinct-vertex ids of

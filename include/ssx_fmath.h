@@ -25,6 +25,10 @@
  * input but 0x39826222 (2.4868647e-4) and 0x328885A3 (1.5893255e-8) (2^-57 and 2^-54.5 from a
  * boundary).  These five values are part of the definition: oracle and kernels share them.
  *
+ * These are the functions of the default libm mode ("build").  The mode "glibc-2.35" (include/ssx.h ssx_render_params.libm) evaluates
+ * glibc 2.35's x86-64 functions instead (include/ssx_glibc_math.h); it still takes ssx_cosf for the reference's (float)cos((double)x),
+ * which is the same function on the arguments the integrator passes.
+ *
  * Plain C99 / C++17 / HIP.  Compile every user of this header with -ffp-contract=off.
  */
 #ifndef SSX_FMATH_H

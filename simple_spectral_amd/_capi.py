@@ -60,7 +60,11 @@ class SsxRenderParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("spp", C.c_uint32),
                 ("indirect_only", C.c_uint32), ("tile_first", C.c_uint32), ("tile_stride", C.c_uint32),
                 ("spp_per_launch", C.c_uint32), ("no_explicit_light_sampling", C.c_uint32), ("no_flat_field_correction", C.c_uint32),
-                ("tile_major", C.c_uint32), ("tile_skew", C.c_uint32), ("seed", C.c_uint64)]
+                ("tile_major", C.c_uint32), ("tile_skew", C.c_uint32), ("seed", C.c_uint64), ("libm", C.c_uint32), ("reserved3", C.c_uint32)]
+
+
+SSX_LIBM_BUILD, SSX_LIBM_GLIBC_2_35 = 0, 1
+LIBM_MODES = {"build": SSX_LIBM_BUILD, "glibc-2.35": SSX_LIBM_GLIBC_2_35}
 
 
 SSX_MODE_RGB, SSX_UPLIFT_OURS, SSX_UPLIFT_MENG, SSX_UPLIFT_JH = 0, 1, 2, 3
@@ -81,6 +85,9 @@ HIP_SYMBOLS = ["ssx_create", "ssx_destroy", "ssx_upload_scene", "ssx_render_star
 # ssx_debug_eval ops (include/ssx.h)
 (SSX_DBG_FMATH, SSX_DBG_SPHTRI, SSX_DBG_ARVO, SSX_DBG_SAMPLE_LIGHT, SSX_DBG_COSHEMI, SSX_DBG_TRACE, SSX_DBG_RAND_CHOICE,
  SSX_DBG_ALBEDO, SSX_DBG_FLUX_TO_XYZ, SSX_DBG_RAND_1F) = range(1, 11)
+# ... and of libm = glibc-2.35 (the _glibc kernels' units), with the sweeps of include/ssx_glibc_math.h on the device
+(SSX_DBG_GLIBC_MATH, SSX_DBG_SPHTRI_GLIBC, SSX_DBG_ARVO_GLIBC, SSX_DBG_SAMPLE_LIGHT_GLIBC, SSX_DBG_COSHEMI_GLIBC) = range(11, 16)
+(SSX_SWEEP_GLIBC_SIN, SSX_SWEEP_GLIBC_COS, SSX_SWEEP_GLIBC_ACOS, SSX_SWEEP_GLIBC_COS_LDS) = range(14, 18)
 HOST_SYMBOLS = ["ssh_scene_create", "ssh_scene_create_ex", "ssh_scene_destroy", "ssh_scene_desc", "ssh_xyza_to_srgba", "ssh_save_image",
                 "ssh_load_png_rgb8", "ssh_free", "ssh_color_values", "ssh_last_error"]
 

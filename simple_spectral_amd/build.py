@@ -20,7 +20,7 @@ HOST_LIB = os.path.join(PKG, "libssx_host.so")
 
 HIP_SRC = [os.path.join(PKG, "csrc", f) for f in ("ssx_api.hip",)]
 HIP_DEPS = [os.path.join(PKG, "csrc", f) for f in ("ssx_api.hip", "ssx_kernels.hip", "ssx_debug.hip", "ssx_blob.h", "ssx_exact.h", "ssx_lanestat.h", "ssx_pass1_gen.h", "ssx_jit.h", "ssx_ddmath.h")] + [
-    os.path.join(ROOT, "include", f) for f in ("ssx.h", "ssx_fmath.h")]
+    os.path.join(ROOT, "include", f) for f in ("ssx.h", "ssx_fmath.h", "ssx_glibc_math.h")]
 HOST_SRC = [os.path.join(PKG, "host", f) for f in
             ("spectrum.cpp", "color.cpp", "jh2019.cpp", "meng2015.cpp", "scene.cpp", "image_io.cpp", "renderer.cpp", "host_api.cpp")]
 HOST_DEPS = HOST_SRC + [os.path.join(PKG, "host", f) for f in
@@ -75,7 +75,8 @@ def check_toolchain():
 # path kernels around a pass 1 generated for the uploaded scene's mesh topology).  Generated, not committed.
 EMBED = (("kernels_hip", os.path.join(PKG, "csrc", "ssx_kernels.hip")), ("blob_h", os.path.join(PKG, "csrc", "ssx_blob.h")),
          ("exact_h", os.path.join(PKG, "csrc", "ssx_exact.h")), ("lanestat_h", os.path.join(PKG, "csrc", "ssx_lanestat.h")),
-         ("fmath_h", os.path.join(ROOT, "include", "ssx_fmath.h")), ("pass1_gen_h", os.path.join(PKG, "csrc", "ssx_pass1_gen.h")))
+         ("fmath_h", os.path.join(ROOT, "include", "ssx_fmath.h")), ("pass1_gen_h", os.path.join(PKG, "csrc", "ssx_pass1_gen.h")),
+         ("glibc_math_h", os.path.join(ROOT, "include", "ssx_glibc_math.h")))
 SOURCES_GEN = os.path.join(PKG, "csrc", "ssx_sources_gen.h")
 
 
@@ -127,6 +128,34 @@ def build_host(force=False, verbose=False):
             print(" ".join(cmd))
         subprocess.check_call(cmd)
     return HOST_LIB
+
+
+# The CPU oracle in libm = glibc-2.35 mode (tests/glibc_oracle.py): oracle/*.c built as oracle/Makefile builds libssx_oracle_libm.so (glibc's
+# sinf / cosf / acosf called), linked with tests/glibc_shim.c, whose hidden definitions of those functions come from include/ssx_glibc_math.h
+# -- so the result does not depend on the C library of the machine that runs the tests.  Written next to the Makefile's libraries, under the
+# name tests/oracle_lib.py loads for its variant "glibc" (git-ignored like them: *.so; it travels with the tree); the object file goes to build/.
+GLIBC_ORACLE = os.path.join(ROOT, "oracle", "libssx_oracle_glibc.so")
+ORACLE_CFLAGS = ["-O2", "-std=gnu11", "-fPIC", "-ffp-contract=off", "-fno-fast-math"]
+
+
+def build_glibc_oracle(force=False, verbose=False):
+    odir = os.path.join(ROOT, "oracle")
+    srcs = [os.path.join(odir, f) for f in ("oracle_color.c", "oracle_math.c", "oracle_scene.c", "oracle_render.c")]
+    shim = os.path.join(ROOT, "tests", "glibc_shim.c")
+    deps = srcs + [shim] + [os.path.join(odir, f) for f in ("oracle.h", "oracle_internal.h")] + [
+        os.path.join(ROOT, "include", f) for f in ("ssx_fmath.h", "ssx_glibc_math.h")]
+    if not (force or _stale(GLIBC_ORACLE, deps)):
+        return GLIBC_ORACLE
+    out = os.path.join(ROOT, "build", "glibc_oracle")
+    os.makedirs(out, exist_ok=True)
+    shim_o = os.path.join(out, "glibc_shim.o")
+    cmds = [["gcc"] + ORACLE_CFLAGS + ["-fno-builtin", "-I" + os.path.join(ROOT, "include"), "-c", shim, "-o", shim_o],
+            ["gcc"] + ORACLE_CFLAGS + ["-DORACLE_USE_LIBM", "-shared", "-o", GLIBC_ORACLE] + srcs + [shim_o, "-lm", "-lpthread"]]
+    for cmd in cmds:
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+    return GLIBC_ORACLE
 
 
 def build_all(force=False, verbose=False, formal=False):

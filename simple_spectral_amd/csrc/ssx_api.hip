@@ -59,6 +59,8 @@ struct ssx_ctx {
 	uint32_t topology = 0;        // 0, the built-in mesh topology the scene matched (csrc/ssx_pass1_gen.h), or 3: its own, compiled at upload
 	int jit_mode = SSX_JIT_BACKGROUND; // ssx_set_jit: how pass 1 gets specialised for scenes that match no built-in topology
 	const ssx_jit::Kernels* jit_kernels = nullptr; // the run-time compiled kernels of the uploaded scene (topology 3)
+	const ssx_jit::Kernels* jit_kernels_glibc = nullptr; // ... the same in libm = glibc-2.35 (compiled when a glibc-mode render first needs them)
+	uint32_t libm = SSX_LIBM_BUILD; // the libm of the current (or last) render: which kernel twins run (path_kernel_ref)
 	// A scene waiting for its own kernels runs the generic one meanwhile: its second blob (packed for topology 3 at upload, the
 	// caller's description is gone later) waits on the device, and the context swaps at the start of a render once the code is
 	// there (maybe_swap_jit).  The compilation is asked for once the context has launched kJitAfterSamples on the generic kernel.
@@ -412,12 +414,28 @@ int pack_blob(ssx_ctx* ctx, const ssx_scene_desc* s, const std::vector<uint8_t*>
 
 int check_params(ssx_ctx* ctx, const ssx_render_params* p) {
 	if (!p || p->struct_size != sizeof(ssx_render_params)) return fail(ctx, SSX_ERR_ARG, "ssx_render_params.struct_size mismatch");
+	if (p->libm != SSX_LIBM_BUILD && p->libm != SSX_LIBM_GLIBC_2_35) return fail(ctx, SSX_ERR_ARG, "ssx_render_params.libm: unknown value");
 	if (!ctx->have_scene) return fail(ctx, SSX_ERR_STATE, "no scene uploaded");
 	if (p->width == 0 || p->height == 0 || p->spp == 0) return fail(ctx, SSX_ERR_ARG, "width, height and spp must be positive");
 	if ((uint64_t)p->width * p->height > (1ull << 28)) return fail(ctx, SSX_ERR_ARG, "image too large");
 	if (p->tile_stride == 0 || p->tile_first >= p->tile_stride) return fail(ctx, SSX_ERR_ARG, "need tile_first < tile_stride");
 	if (p->no_flat_field_correction && !ctx->have_cam_dir) return fail(ctx, SSX_ERR_ARG, "no_flat_field_correction needs ssx_scene_desc.cam_dir (caller built against an older ssx.h)");
 	return SSX_OK;
+}
+
+// The caller's parameters as this library's struct: a caller built before ssx_render_params.libm (struct_size = offsetof(.., libm)) gets
+// SSX_LIBM_BUILD.  Then check_params; and the context's kernels follow the render's libm (the plan of the resident workgroups is redone
+// when it changes: the twins are different kernels).
+int take_params(ssx_ctx* ctx, const ssx_render_params* in, ssx_render_params* out) {
+	if (!in) return fail(ctx, SSX_ERR_ARG, "ssx_render_params is NULL");
+	memset(out, 0, sizeof *out);
+	if (in->struct_size == offsetof(ssx_render_params, libm)) { memcpy(out, in, offsetof(ssx_render_params, libm)); out->struct_size = sizeof *out; }
+	else memcpy(out, in, in->struct_size == sizeof *out ? sizeof *out : sizeof out->struct_size);
+	return check_params(ctx, out);
+}
+void set_libm(ssx_ctx* ctx, uint32_t libm) {
+	// (a scene still waiting for its own kernels asks again, for this mode's: maybe_swap_jit)
+	if (ctx->libm != libm) { ctx->libm = libm; ctx->resident_blocks = 0; ctx->jit_requested = false; }
 }
 
 // The pixel sums are laid out per 8x8 tile as [tile][X, Y, Z, alpha][pixel of the tile] (binary64), so that the 64 lanes of a
@@ -633,17 +651,24 @@ size_t path_lds_bytes(uint32_t blob_words, uint32_t queue_words) {
 }
 // the path megakernel for a pass-1 variant (0 generic, 1 Cornell topology, 2 plane topology) and queue entry size
 typedef void (*path_kernel_t)(SsxKernelArgs);
-path_kernel_t path_kernel_of(uint32_t topology, bool narrow) {
+path_kernel_t path_kernel_of(uint32_t topology, bool narrow, uint32_t libm = SSX_LIBM_BUILD) {
+	if (libm == SSX_LIBM_GLIBC_2_35) {
+		if (topology == 1u) return narrow ? ssx_render_kernel_cornell_nq_glibc : ssx_render_kernel_cornell_glibc;
+		if (topology == 2u) return narrow ? ssx_render_kernel_plane_nq_glibc : ssx_render_kernel_plane_glibc;
+		return narrow ? ssx_render_kernel_nq_glibc : ssx_render_kernel_glibc;
+	}
 	if (topology == 1u) return narrow ? ssx_render_kernel_cornell_nq : ssx_render_kernel_cornell;
 	if (topology == 2u) return narrow ? ssx_render_kernel_plane_nq : ssx_render_kernel_plane;
 	return narrow ? ssx_render_kernel_nq : ssx_render_kernel;
 }
-// A kernel of this library (host function) or of a run-time compiled module (topology 3)
+// A kernel of this library (host function) or of a run-time compiled module (topology 3), for the context's libm.  A glibc-mode render of a
+// specialised scene has its kernels (ensure_libm_kernels) before it gets here.
 struct KernelRef { const void* host = nullptr; hipFunction_t mod = nullptr; };
 KernelRef path_kernel_ref(const ssx_ctx* ctx, bool narrow) {
 	KernelRef k;
-	if (ctx->topology == 3u && ctx->jit_kernels) k.mod = narrow ? ctx->jit_kernels->path_nq : ctx->jit_kernels->path;
-	else k.host = (const void*)path_kernel_of(ctx->topology, narrow);
+	const ssx_jit::Kernels* jk = ctx->libm == SSX_LIBM_GLIBC_2_35 ? ctx->jit_kernels_glibc : ctx->jit_kernels;
+	if (ctx->topology == 3u && jk) k.mod = narrow ? jk->path_nq : jk->path;
+	else k.host = (const void*)path_kernel_of(ctx->topology, narrow, ctx->libm);
 	return k;
 }
 int occupancy_of(ssx_ctx* ctx, const KernelRef& k, size_t lds, int* per_cu) {
@@ -764,23 +789,40 @@ int enqueue_front(ssx_ctx* ctx, const LaunchPlan& pl, Batch& b, hipStream_t stre
 // compilation is requested once the generic kernel has served kJitAfterSamples (a test's 8 x 8 image is not worth a core-second
 // of hipRTC; a production render passes the mark in its first launch and has its kernels a second or two later).
 constexpr uint64_t kJitAfterSamples = (uint64_t)32 << 20;
+// The kernels asked for and looked for are those of the render's libm (ctx->libm): each mode's first code object of the pattern comes the
+// same way; the other mode's, should a render of it follow the swap, is compiled by ensure_libm_kernels.
 void maybe_swap_jit(ssx_ctx* ctx, uint64_t samples) {
 	if (!ctx->jit_pending) return;
 	std::string err;
 	const ssx_jit::Kernels* k = nullptr;
-	const ssx_jit::State st = ssx_jit::lookup(ctx->device, ctx->jit_vid, &k, &err);
+	const ssx_jit::State st = ssx_jit::lookup(ctx->device, ctx->jit_vid, &k, &err, ctx->libm);
 	if (st == ssx_jit::State::Ready) {
 		std::swap(ctx->d_blob, ctx->d_blob_jit);
 		ctx->blob_words = ctx->blob_jit_words; ctx->path_blob_words = ctx->path_blob_jit_words;
-		ctx->topology = 3u; ctx->jit_kernels = k;
+		ctx->topology = 3u;
+		(ctx->libm == SSX_LIBM_GLIBC_2_35 ? ctx->jit_kernels_glibc : ctx->jit_kernels) = k;
 		ctx->resident_blocks = 0; ctx->gen_blocks = 0; // the blob's LDS footprint changed
 		ctx->jit_pending = false; ctx->jit_state = SSX_JIT_STATE_SPECIALISED;
 	} else if (st == ssx_jit::State::Failed) {
 		ctx->jit_pending = false; ctx->jit_state = SSX_JIT_STATE_FAILED; ctx->jit_message = err;
 	} else {
 		ctx->generic_samples += samples;
-		if (!ctx->jit_requested && ctx->generic_samples >= kJitAfterSamples) { ssx_jit::request(ctx->jit_vid); ctx->jit_requested = true; }
+		if (!ctx->jit_requested && ctx->generic_samples >= kJitAfterSamples) { ssx_jit::request(ctx->jit_vid, ctx->libm); ctx->jit_requested = true; }
 	}
+}
+
+// A render in one libm of a scene that already runs on its own run-time compiled kernels (topology 3, its blob packed for them) but has
+// only the other mode's: this mode's are compiled here, on the calling thread, the first time (or come from this process's memory / the disk
+// cache: the mode is part of the pattern's key and of the compile flags, csrc/ssx_jit.h).  No fall-back: the generic kernels cannot read
+// that blob.  Called before the context switches to `libm` (set_libm): a failure leaves it in the mode it was in.
+int ensure_libm_kernels(ssx_ctx* ctx, uint32_t libm) {
+	const ssx_jit::Kernels*& have = libm == SSX_LIBM_GLIBC_2_35 ? ctx->jit_kernels_glibc : ctx->jit_kernels;
+	if (ctx->topology != 3u || have) return SSX_OK;
+	std::string err;
+	const ssx_jit::Kernels* k = ssx_jit::get(ctx->device, ctx->jit_vid, &err, libm);
+	if (!k) return fail(ctx, SSX_ERR_STATE, "the scene's specialised kernels for this libm could not be compiled: " + err);
+	have = k;
+	return SSX_OK;
 }
 
 // samples [k0, k1) of every owned pixel, in stream order
@@ -1088,7 +1130,7 @@ int ssx_upload_scene(ssx_ctx* ctx, const ssx_scene_desc* s) {
 		SSX_HIP(ctx, hipMemcpy(ctx->d_jh_data, s->jh_data, bytes, hipMemcpyHostToDevice));
 	}
 	std::vector<uint32_t> blob, blob_jit;
-	ctx->jit_kernels = nullptr;
+	ctx->jit_kernels = nullptr; ctx->jit_kernels_glibc = nullptr;
 	ctx->jit_pending = ctx->jit_requested = false; ctx->generic_samples = 0; ctx->jit_vid.clear();
 	ctx->jit_state = SSX_JIT_STATE_NONE; ctx->jit_message.clear();
 	if (ctx->d_blob_jit) { (void)hipFree(ctx->d_blob_jit); ctx->d_blob_jit = nullptr; }
@@ -1109,7 +1151,7 @@ int ssx_upload_scene(ssx_ctx* ctx, const ssx_scene_desc* s) {
 		}
 		if (st == ssx_jit::State::Failed) { ctx->jit_state = SSX_JIT_STATE_FAILED; ctx->jit_message = err; }
 		else if ((rc = pack_blob(ctx, s, ctx->d_textures, ctx->d_jh_data, blob_jit, 3, nullptr))) return rc;
-		else if (st == ssx_jit::State::Ready) { blob.swap(blob_jit); blob_jit.clear(); ctx->jit_kernels = k; ctx->jit_state = SSX_JIT_STATE_SPECIALISED; }
+		else if (st == ssx_jit::State::Ready) { blob.swap(blob_jit); blob_jit.clear(); ctx->jit_kernels = k; ctx->jit_vid = info.vid; ctx->jit_state = SSX_JIT_STATE_SPECIALISED; }
 		else { ctx->jit_pending = true; ctx->jit_vid = info.vid; ctx->jit_state = SSX_JIT_STATE_GENERIC_MEANWHILE; ctx->jit_requested = (st == ssx_jit::State::Pending); }
 	}
 	if (ctx->jit_pending) {
@@ -1152,10 +1194,12 @@ static uint32_t device_batch(const ssx_render_params* p, const LaunchPlan& pl) {
 	return batch;
 }
 
-int ssx_render_device(ssx_ctx* ctx, const ssx_render_params* p, void* d_xyza_out, void* hip_stream) {
+int ssx_render_device(ssx_ctx* ctx, const ssx_render_params* p_in, void* d_xyza_out, void* hip_stream) {
 	if (!ctx) return SSX_ERR_ARG;
-	int rc = check_params(ctx, p);
+	ssx_render_params pp;
+	int rc = take_params(ctx, p_in, &pp);
 	if (rc) return rc;
+	const ssx_render_params* const p = &pp;
 	if (!d_xyza_out) return fail(ctx, SSX_ERR_ARG, "d_xyza_out is NULL");
 	if (ctx->rendering.load()) return fail(ctx, SSX_ERR_STATE, "asynchronous render in progress");
 	hipStream_t stream = (hipStream_t)hip_stream;
@@ -1171,6 +1215,8 @@ int ssx_render_device(ssx_ctx* ctx, const ssx_render_params* p, void* d_xyza_out
 	(void)hipStreamIsCapturing(stream, &capture);
 	const bool capturing = capture == hipStreamCaptureStatusActive;
 	if (ctx->device_pending && capturing) return fail(ctx, SSX_ERR_STATE, "a render of this context may still be queued: ssx_render_device_wait before capturing another into a graph");
+	// (the kernels of another libm may need a compilation and change the plan of the resident workgroups: not while capturing)
+	if (capturing && ctx->libm != p->libm) return fail(ctx, SSX_ERR_STATE, "ssx_render_params.libm differs from the context's last render: run it once outside the stream capture first");
 	if (ctx->device_pending) SSX_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev_device_done, 0));
 	{
 		LaunchPlan probe = make_plan(ctx, p, !capturing);
@@ -1186,6 +1232,8 @@ int ssx_render_device(ssx_ctx* ctx, const ssx_render_params* p, void* d_xyza_out
 			ctx->device_pending = false;
 		}
 	}
+	if ((rc = ensure_libm_kernels(ctx, p->libm))) return rc;
+	set_libm(ctx, p->libm);
 	if ((rc = ensure_buffers(ctx, p->width, p->height, false))) return rc;
 	SSX_HIP(ctx, hipMemsetAsync(ctx->d_accum, 0, accum_slots(p->width, p->height) * 4 * sizeof(double), stream));
 	if (!capturing) maybe_swap_jit(ctx, (uint64_t)p->width * p->height * p->spp / p->tile_stride);
@@ -1213,14 +1261,18 @@ int ssx_render_device_wait(ssx_ctx* ctx) {
 	return SSX_OK;
 }
 
-int ssx_render_start(ssx_ctx* ctx, const ssx_render_params* p) {
+int ssx_render_start(ssx_ctx* ctx, const ssx_render_params* p_in) {
 	if (!ctx) return SSX_ERR_ARG;
-	int rc = check_params(ctx, p);
+	ssx_render_params pp;
+	int rc = take_params(ctx, p_in, &pp);
 	if (rc) return rc;
+	const ssx_render_params* const p = &pp;
 	if (ctx->rendering.load()) return fail(ctx, SSX_ERR_STATE, "render already in progress");
 	if (ctx->worker.joinable()) ctx->worker.join();
 	SSX_HIP(ctx, hipSetDevice(ctx->device));
 	if (ctx->device_pending) { SSX_HIP(ctx, hipEventSynchronize(ctx->ev_device_done)); ctx->device_pending = false; } // a queued ssx_render_device uses the same buffers
+	if ((rc = ensure_libm_kernels(ctx, p->libm))) return rc;
+	set_libm(ctx, p->libm);
 	if ((rc = ensure_buffers(ctx, p->width, p->height, true))) return rc;
 	ctx->cur = *p;
 	ctx->total_spp = p->spp;
@@ -1454,7 +1506,10 @@ int ssx_debug_eval(ssx_ctx* ctx, uint32_t op, const void* in, uint32_t in_words,
 		SsxKernelArgs a{};
 		a.blob = ctx->d_blob; a.blob_words = ctx->blob_words; a.rgb_mode = ctx->rgb_mode ? 1u : 0u;
 		const size_t lds = ((size_t)ctx->blob_words + SSX_LDS_PREFIX_WORDS) * 4;
-		hipLaunchKernelGGL(ssx_debug_eval_kernel, dim3((n + 255u) / 256u), dim3(256), lds, ctx->stream, a, op, d_in, in_words, d_out, out_words, n);
+		if (op >= SSX_DBG_GLIBC_MATH) // the units of libm = glibc-2.35: a kernel that stages the _glibc kernels' LDS table
+			hipLaunchKernelGGL(ssx_debug_eval_glibc_kernel, dim3((n + 255u) / 256u), dim3(256), lds, ctx->stream, a, op, d_in, in_words, d_out, out_words, n);
+		else
+			hipLaunchKernelGGL(ssx_debug_eval_kernel, dim3((n + 255u) / 256u), dim3(256), lds, ctx->stream, a, op, d_in, in_words, d_out, out_words, n);
 		SSX_HIP(ctx, hipGetLastError());
 		SSX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 		SSX_HIP(ctx, hipMemcpy(out, d_out, (size_t)n * out_words * 4, hipMemcpyDeviceToHost));
@@ -1477,7 +1532,10 @@ int ssx_debug_sweep(ssx_ctx* ctx, uint32_t op, uint32_t lo, uint64_t count, uint
 		SsxKernelArgs a{};
 		a.blob = ctx->d_blob; a.blob_words = ctx->blob_words;
 		const size_t lds = ((size_t)ctx->blob_words + SSX_LDS_PREFIX_WORDS) * 4;
-		hipLaunchKernelGGL(ssx_debug_sweep_kernel, dim3(256 * 16), dim3(256), lds, ctx->stream, a, op, lo, (uint64_t)count, d_res);
+		if (op >= SSX_SWEEP_GLIBC_SIN) // libm = glibc-2.35 (see ssx_debug_eval)
+			hipLaunchKernelGGL(ssx_debug_sweep_glibc_kernel, dim3(256 * 16), dim3(256), lds, ctx->stream, a, op, lo, (uint64_t)count, d_res);
+		else
+			hipLaunchKernelGGL(ssx_debug_sweep_kernel, dim3(256 * 16), dim3(256), lds, ctx->stream, a, op, lo, (uint64_t)count, d_res);
 		SSX_HIP(ctx, hipGetLastError());
 		SSX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 		SSX_HIP(ctx, hipMemcpy(result, d_res, 11 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
@@ -1488,14 +1546,18 @@ int ssx_debug_sweep(ssx_ctx* ctx, uint32_t op, uint32_t lo, uint64_t count, uint
 	return rc;
 }
 
-int ssx_debug_samples(ssx_ctx* ctx, const ssx_render_params* p, float* xyza, uint64_t* rng_state, uint32_t* levels) {
+int ssx_debug_samples(ssx_ctx* ctx, const ssx_render_params* p_in, float* xyza, uint64_t* rng_state, uint32_t* levels) {
 	if (!ctx) return SSX_ERR_ARG;
-	int rc = check_params(ctx, p);
+	ssx_render_params pp;
+	int rc = take_params(ctx, p_in, &pp);
 	if (rc) return rc;
+	const ssx_render_params* const p = &pp;
 	if (ctx->rendering.load()) return fail(ctx, SSX_ERR_STATE, "render in progress");
 	if (p->tile_first != 0 || p->tile_stride != 1) return fail(ctx, SSX_ERR_ARG, "ssx_debug_samples renders the whole image");
 	SSX_HIP(ctx, hipSetDevice(ctx->device));
 	if (ctx->device_pending) { SSX_HIP(ctx, hipEventSynchronize(ctx->ev_device_done)); ctx->device_pending = false; }
+	if ((rc = ensure_libm_kernels(ctx, p->libm))) return rc;
+	set_libm(ctx, p->libm);
 	if ((rc = ensure_buffers(ctx, p->width, p->height, false))) return rc;
 	LaunchPlan pl = make_plan(ctx, p);
 	if (p->spp > pl.max_spp_per_launch) return fail(ctx, SSX_ERR_ARG, "ssx_debug_samples: too many samples for one launch");
@@ -1548,8 +1610,8 @@ int ssx_jit_status(ssx_ctx* ctx, int wait_ms, char* message, size_t message_size
 	if (ctx->rendering.load()) return fail(ctx, SSX_ERR_STATE, "render in progress");
 	if (ctx->jit_pending && wait_ms != 0) {
 		if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, SSX_ERR_DEVICE, "hipSetDevice failed");
-		if (!ctx->jit_requested) { ssx_jit::request(ctx->jit_vid); ctx->jit_requested = true; }
-		(void)ssx_jit::wait(ctx->jit_vid, wait_ms < 0 ? 600000 : wait_ms);
+		if (!ctx->jit_requested) { ssx_jit::request(ctx->jit_vid, ctx->libm); ctx->jit_requested = true; }
+		(void)ssx_jit::wait(ctx->jit_vid, wait_ms < 0 ? 600000 : wait_ms, ctx->libm);
 		maybe_swap_jit(ctx, 0);
 	}
 	if (message && message_size) { const size_t n = ctx->jit_message.size() < message_size - 1 ? ctx->jit_message.size() : message_size - 1; memcpy(message, ctx->jit_message.data(), n); message[n] = '\0'; }
@@ -1614,9 +1676,13 @@ const char* ssx_kernel_name(ssx_ctx* ctx) {
 	if (hipSetDevice(ctx->device) != hipSuccess) return nullptr;
 	uint32_t qw = 0;
 	if (pick_queue(ctx, ctx->path_blob_words, &qw, nullptr) != SSX_OK) return nullptr;
-	static const char* const names[4][2] = { { "ssx_render_kernel", "ssx_render_kernel_nq" }, { "ssx_render_kernel_cornell", "ssx_render_kernel_cornell_nq" },
-	                                         { "ssx_render_kernel_plane", "ssx_render_kernel_plane_nq" }, { "ssx_render_kernel_jit", "ssx_render_kernel_jit_nq" } };
-	return names[ctx->topology < 4u ? ctx->topology : 0u][qw == SSX_QUEUE_WORDS_NARROW ? 1 : 0];
+	static const char* const names[2][4][2] = {
+		{ { "ssx_render_kernel", "ssx_render_kernel_nq" }, { "ssx_render_kernel_cornell", "ssx_render_kernel_cornell_nq" },
+		  { "ssx_render_kernel_plane", "ssx_render_kernel_plane_nq" }, { "ssx_render_kernel_jit", "ssx_render_kernel_jit_nq" } },
+		// libm = glibc-2.35 (the run-time compiled twins keep their names: their module is another one)
+		{ { "ssx_render_kernel_glibc", "ssx_render_kernel_nq_glibc" }, { "ssx_render_kernel_cornell_glibc", "ssx_render_kernel_cornell_nq_glibc" },
+		  { "ssx_render_kernel_plane_glibc", "ssx_render_kernel_plane_nq_glibc" }, { "ssx_render_kernel_jit", "ssx_render_kernel_jit_nq" } } };
+	return names[ctx->libm == SSX_LIBM_GLIBC_2_35 ? 1 : 0][ctx->topology < 4u ? ctx->topology : 0u][qw == SSX_QUEUE_WORDS_NARROW ? 1 : 0];
 }
 
 int ssx_plan_info(ssx_ctx* ctx, float* frames_per_sample, int* fold_in_path_kernel) {

@@ -196,3 +196,97 @@ extern "C" __global__ void __launch_bounds__(256) ssx_debug_eval_kernel(SsxKerne
 	if (gid < n)
 		for (uint32_t k = 0; k < out_words && k < 12u; ++k) out[(size_t)gid * out_words + k] = o[k];
 }
+
+// ---- libm = glibc-2.35: the same diagnostics for the _glibc kernels, in kernels of their own (they stage the LDS table of the _glibc
+// kernels, stage_lds<true>: the glibc coefficients over ssx_fmath.h's arc-cosine slots)
+// Digest word of one input and its result (include/ssx.h SSX_SWEEP_GLIBC_*; tests/glibc_math_check.c computes the same on the host).
+__device__ __forceinline__ unsigned long long glibc_digest_word(uint32_t x, float y) {
+	unsigned long long z = ((unsigned long long)x << 32) | (y != y ? 0x7FC00000u : __float_as_uint(y));
+	z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+	z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+	return z ^ (z >> 31);
+}
+extern "C" __global__ void __launch_bounds__(256) ssx_debug_sweep_glibc_kernel(SsxKernelArgs a, uint32_t op, uint32_t lo, uint64_t count, unsigned long long* res) {
+	Lds L; L.w = stage_lds<true>(a);
+	(void)L;
+	unsigned long long bad = 0, digest = 0;
+	uint32_t example = 0; bool have_example = false;
+	for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (uint64_t)gridDim.x * blockDim.x) {
+		const uint32_t bits = lo + (uint32_t)i;
+		const float x = __uint_as_float(bits);
+		bool ok = true;
+		switch (op) {
+		case SSX_SWEEP_GLIBC_SIN: case SSX_SWEEP_GLIBC_COS: {
+			const bool c = op == SSX_SWEEP_GLIBC_COS;
+			const float y = c ? ssx_glibc_cosf(x) : ssx_glibc_sinf(x);
+			float s2, c2;
+			ssx_glibc_sincosf(x, &s2, &c2);
+			ok = same_float(c ? c2 : s2, y);
+			digest += glibc_digest_word(bits, y);
+			break;
+		}
+		case SSX_SWEEP_GLIBC_ACOS: digest += glibc_digest_word(bits, ssx_glibc_acosf(x)); break;
+		case SSX_SWEEP_GLIBC_COS_LDS: ok = same_float(ssx_cosf_lds(x), ssx_cosf(x)); break;
+		default: break;
+		}
+		if (!ok) { ++bad; if (!have_example) { example = bits; have_example = true; } }
+	}
+	if (bad) {
+		atomicAdd(&res[0], bad);
+		const unsigned long long slot = atomicAdd(&res[2], 1ull);
+		if (slot < 8ull) res[3 + slot] = example;
+	}
+	if (digest) atomicAdd(&res[1], digest);
+}
+
+extern "C" __global__ void __launch_bounds__(256) ssx_debug_eval_glibc_kernel(SsxKernelArgs a, uint32_t op, const uint32_t* in, uint32_t in_words,
+                                                                             uint32_t* out, uint32_t out_words, uint32_t n) {
+	Lds L; L.w = stage_lds<true>(a);
+	const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
+	const uint32_t item = gid < n ? gid : n - 1u;
+	const uint32_t* x = in + (size_t)item * in_words;
+	uint32_t o[12];
+#pragma unroll
+	for (int k = 0; k < 12; ++k) o[k] = 0u;
+	switch (op) {
+	case SSX_DBG_GLIBC_MATH: { // in: x -> sinf, cosf, acosf, sincosf.s, sincosf.c
+		float s, c;
+		ssx_glibc_sincosf(f(x[0]), &s, &c);
+		o[0] = u(ssx_glibc_sinf(f(x[0]))); o[1] = u(ssx_glibc_cosf(f(x[0]))); o[2] = u(ssx_glibc_acosf(f(x[0]))); o[3] = u(s); o[4] = u(c);
+		break;
+	}
+	case SSX_DBG_SPHTRI_GLIBC: {
+		SphTri t;
+		sphtri_make<true>(mk(f(x[0]), f(x[1]), f(x[2])), mk(f(x[3]), f(x[4]), f(x[5])), mk(f(x[6]), f(x[7]), f(x[8])), t);
+		o[0] = u(t.b); o[1] = u(t.cos_c); o[2] = u(t.alpha); o[3] = u(t.cos_alpha); o[4] = u(t.area);
+		break;
+	}
+	case SSX_DBG_ARVO_GLIBC: {
+		SphTri t;
+		t.A = mk(f(x[0]), f(x[1]), f(x[2])); t.B = mk(f(x[3]), f(x[4]), f(x[5])); t.C = mk(f(x[6]), f(x[7]), f(x[8]));
+		t.b = f(x[9]); t.cos_c = f(x[10]); t.alpha = f(x[11]); t.cos_alpha = f(x[12]); t.area = f(x[13]);
+		t.sin_alpha = ssx_glibc_sinf(t.alpha); // (what sphtri_make<true> stores: random.cpp:108)
+		Rng r = load_rng(x + 14);
+		V3 d = rand_toward_sphericaltri<true>(r, t);
+		o[0] = u(d.x); o[1] = u(d.y); o[2] = u(d.z); o[3] = (uint32_t)r.state; o[4] = (uint32_t)(r.state >> 32);
+		break;
+	}
+	case SSX_DBG_SAMPLE_LIGHT_GLIBC: {
+		Rng r = load_rng(x + 3);
+		V3 d; uint32_t lq; float pdf;
+		sample_light<true>(L, r, mk(f(x[0]), f(x[1]), f(x[2])), d, lq, pdf);
+		o[0] = u(d.x); o[1] = u(d.y); o[2] = u(d.z); o[3] = lq; o[4] = u(pdf); o[5] = (uint32_t)r.state; o[6] = (uint32_t)(r.state >> 32);
+		break;
+	}
+	case SSX_DBG_COSHEMI_GLIBC: {
+		Rng r = load_rng(x + 3);
+		float pdf;
+		V3 w = get_rotated_to(rand_coshemi<true>(r, pdf), mk(f(x[0]), f(x[1]), f(x[2])));
+		o[0] = u(w.x); o[1] = u(w.y); o[2] = u(w.z); o[3] = u(pdf); o[4] = (uint32_t)r.state; o[5] = (uint32_t)(r.state >> 32);
+		break;
+	}
+	default: break;
+	}
+	if (gid < n)
+		for (uint32_t k = 0; k < out_words && k < 12u; ++k) out[(size_t)gid * out_words + k] = o[k];
+}

@@ -42,13 +42,31 @@ extern __shared__ __attribute__((aligned(16))) uint32_t ssx_lds[];
 #else
 #include "../../include/ssx_fmath.h"
 #endif
+// libm = glibc-2.35 (the _glibc kernels, GLIBC = true below): glibc's sinf / cosf / sincosf / acosf restated by ssx_glibc_math.h.  Its
+// binary64 coefficients take the LDS slots of the arc-cosine part of the table above (A11 .. PI_LO): a glibc-mode kernel never evaluates
+// ssx_fmath.h's acos (ssx_acosf_lds, ssx_acos_sin_lds), only its cosine (ssx_cosf_lds: reference random.cpp:134 is (float)cos(double),
+// which equals ssx_cosf on the whole argument range [0, pi), tests/test_glibc_math_cpu.py), whose coefficients stay where they are.
+#define SSX_GM_TABLE (SSX_FM_TABLE + SSX_FM_I_A11)
+#ifdef SSX_JIT_BUILD
+#include "ssx_glibc_math.h"
+#else
+#include "../../include/ssx_glibc_math.h"
+#endif
 __device__ const double ssx_fm_coeff_values[SSX_FM_N_COEFF] = SSX_FM_COEFF_INIT;
+__device__ const double ssx_gm_coeff_values[SSX_GM_N_COEFF] = SSX_GM_COEFF_INIT;
 static_assert(2 * SSX_FM_N_COEFF <= SSX_LDS_PREFIX_WORDS, "coefficient table");
+static_assert(SSX_FM_I_A11 + SSX_GM_N_COEFF <= SSX_FM_N_COEFF, "glibc coefficients in the arc-cosine slots");
 // stages the coefficient table and the scene blob; returns the blob's LDS address
+template <bool GLIBC = false>
 __device__ __forceinline__ uint32_t* stage_lds(const SsxKernelArgs& a) {
 	uint32_t* blob = ssx_lds + SSX_LDS_PREFIX_WORDS;
 	for (uint32_t w = threadIdx.x; w < a.blob_words; w += blockDim.x) blob[w] = a.blob[w];
-	if (threadIdx.x < (uint32_t)SSX_FM_N_COEFF) reinterpret_cast<double*>(ssx_lds)[threadIdx.x] = ssx_fm_coeff_values[threadIdx.x];
+	if (!GLIBC) {
+		if (threadIdx.x < (uint32_t)SSX_FM_N_COEFF) reinterpret_cast<double*>(ssx_lds)[threadIdx.x] = ssx_fm_coeff_values[threadIdx.x];
+	} else {
+		const uint32_t t = threadIdx.x, g = t - (uint32_t)SSX_FM_I_A11;
+		if (t < (uint32_t)SSX_FM_N_COEFF) reinterpret_cast<double*>(ssx_lds)[t] = g < (uint32_t)SSX_GM_N_COEFF ? ssx_gm_coeff_values[g] : ssx_fm_coeff_values[t];
+	}
 	__syncthreads();
 	return blob;
 }
@@ -677,16 +695,20 @@ struct SphTri {
 // util/spherical-tri.cpp:18-124 as written (only the members rand_toward_sphericaltri and the pdf read): every
 // clamp with glm's NaN behaviour, the degenerate ladder.  sphtri_make runs it only for the lanes its fast path
 // does not cover (a NaN vertex, or a side of 0 / pi).
+// GLIBC: the reference's functions are glibc's (ssx_glibc_math.h), evaluated as called.
+template <bool GLIBC = false>
 __device__ __forceinline__ void sphtri_make_general(V3 A, V3 B, V3 C, SphTri& t) {
+	auto acos_ = [](float x) { return GLIBC ? ssx_glibc_acosf(x) : ssx_acosf_lds(x); };
+	auto sin_ = [](float x) { return GLIBC ? ssx_glibc_sinf(x) : ssx_sinf_lds(x); };
 	const float under_pi = __uint_as_float(0x40490FDAu);
 	const float nanv = __uint_as_float(0x7FC00000u);
 	float cos_a = clamp_glm(dot3(B, C), -1.0f, 1.0f);
 	float cos_b = clamp_glm(dot3(A, C), -1.0f, 1.0f);
 	float cos_c = clamp_glm(dot3(A, B), -1.0f, 1.0f);
-	float a = clamp_glm(ssx_acosf_lds(cos_a), 0.0f, under_pi);
-	float b = clamp_glm(ssx_acosf_lds(cos_b), 0.0f, under_pi);
-	float c = clamp_glm(ssx_acosf_lds(cos_c), 0.0f, under_pi);
-	float sin_a = ssx_sinf_lds(a), sin_b = ssx_sinf_lds(b), sin_c = ssx_sinf_lds(c);
+	float a = clamp_glm(acos_(cos_a), 0.0f, under_pi);
+	float b = clamp_glm(acos_(cos_b), 0.0f, under_pi);
+	float c = clamp_glm(acos_(cos_c), 0.0f, under_pi);
+	float sin_a = sin_(a), sin_b = sin_(b), sin_c = sin_(c);
 	float numer0 = cos_a - cos_b * cos_c;
 	float numer1 = cos_b - cos_c * cos_a;
 	float numer2 = cos_c - cos_a * cos_b;
@@ -697,13 +719,13 @@ __device__ __forceinline__ void sphtri_make_general(V3 A, V3 B, V3 C, SphTri& t)
 	// cos_alpha = clamp(numer0/denom0) and acos of it are shared by the regular case (:64,:67) and
 	// the "only a is 0 or pi" case (:111-112)
 	const float cos_alpha0 = clamp_glm(numer0 / denom0, -1.0f, 1.0f);
-	const float alpha_raw = ssx_acosf_lds(cos_alpha0);
+	const float alpha_raw = acos_(cos_alpha0);
 	float alpha = clamp_glm(alpha_raw, 0.0f, under_pi), cos_alpha = cos_alpha0, area = 0.0f;
 	if (regular) {
 		float cos_beta  = clamp_glm(numer1 / denom1, -1.0f, 1.0f);
 		float cos_gamma = clamp_glm(numer2 / denom2, -1.0f, 1.0f);
-		float beta  = clamp_glm(ssx_acosf_lds(cos_beta ), 0.0f, under_pi);
-		float gamma = clamp_glm(ssx_acosf_lds(cos_gamma), 0.0f, under_pi);
+		float beta  = clamp_glm(acos_(cos_beta ), 0.0f, under_pi);
+		float gamma = clamp_glm(acos_(cos_gamma), 0.0f, under_pi);
 		area = alpha + beta + gamma - SSX_PI_F;
 		if (area >= 0); else area = 0;
 	} else {
@@ -716,7 +738,7 @@ __device__ __forceinline__ void sphtri_make_general(V3 A, V3 B, V3 C, SphTri& t)
 	}
 	t.b = b; t.cos_c = cos_c;
 	t.alpha = alpha; t.cos_alpha = cos_alpha; t.area = area;
-	t.sin_alpha = ssx_sinf_lds(alpha);
+	t.sin_alpha = sin_(alpha);
 }
 
 // The same results for the case every lane is in almost always (no NaN in the vertices, all three sides
@@ -727,9 +749,12 @@ __device__ __forceinline__ void sphtri_make_general(V3 A, V3 B, V3 C, SphTri& t)
 //     sin alpha in rand_toward_sphericaltri) come from ssx_acos_sin_lds: sqrt(1 - x^2) plus a first-order
 //     correction for the arc's rounding, with a rounding test that sends the rare ambiguous case to ssx_sinf_lds.
 // Every value is the float the general code produces; lanes that leave the case are redone by the general code.
+// These shortcuts hold for ssx_fmath.h's functions only: in glibc mode every lane runs the general code, with glibc's functions.
+template <bool GLIBC = false>
 __device__ __forceinline__ void sphtri_make(V3 A, V3 B, V3 C, SphTri& t) {
 	const float under_pi = __uint_as_float(0x40490FDAu);
 	t.A = A; t.B = B; t.C = C;
+	if (GLIBC) { sphtri_make_general<true>(A, B, C, t); return; }
 	const float da = dot3(B, C), db = dot3(A, C), dc = dot3(A, B);
 	const float cos_a = __builtin_amdgcn_fmed3f(da, -1.0f, 1.0f);
 	const float cos_b = __builtin_amdgcn_fmed3f(db, -1.0f, 1.0f);
@@ -773,6 +798,7 @@ __device__ __forceinline__ V3 func_bar(V3 x, V3 y) { // util/random.cpp:139-144
 }
 
 // util/random.cpp:101-154 (Arvo)
+template <bool GLIBC = false>
 __device__ __forceinline__ V3 rand_toward_sphericaltri(Rng& rng, const SphTri& tri) {
 	float r0 = rand_1f(rng);
 	float r1 = rand_1f(rng);
@@ -782,14 +808,14 @@ __device__ __forceinline__ V3 rand_toward_sphericaltri(Rng& rng, const SphTri& t
 		float random_area = r0 * tri.area;
 		float phi = random_area - tri.alpha;
 		float s, t;
-		ssx_sincosf(phi, &s, &t);
+		if (GLIBC) ssx_glibc_sincosf(phi, &s, &t); else ssx_sincosf(phi, &s, &t);
 		float u = t - tri.cos_alpha;
 		float v = s + sin_alpha * tri.cos_c;
 		float denom = (v * s + u * t) * sin_alpha;
 		if (denom != 0.0f) q = ((v * t - u * s) * tri.cos_alpha - v) / denom;
 		else q = tri.cos_c;
 	} else {
-		q = ssx_cosf_lds(tri.b * r0); // random.cpp:134 (double cos of a float, rounded back)
+		q = ssx_cosf_lds(tri.b * r0); // random.cpp:134 (double cos of a float, rounded back; glibc's too: see SSX_GM_TABLE)
 	}
 	q = clamp_glm(q, -1.0f, 1.0f);
 	V3 C_hat = add(scl(q, tri.A), scl(ssx_exact::sqrt_normal(1 - q * q), func_bar(tri.C, tri.A)));
@@ -799,6 +825,7 @@ __device__ __forceinline__ V3 rand_toward_sphericaltri(Rng& rng, const SphTri& t
 }
 
 // scene.cpp:417-431 -> geometry.cpp:141-145 -> geometry.cpp:103-116
+template <bool GLIBC = false>
 __device__ __forceinline__ void sample_light(const Lds& L, Rng& rng, V3 from, V3& dir, uint32_t& light_quad, float& pdf) {
 	const uint32_t nl = L.hdr().n_lights;
 	// one light (wave-uniform test): uniform_int_distribution(0, 0) still draws once (range 1: product = draw, its low
@@ -816,10 +843,10 @@ __device__ __forceinline__ void sample_light(const Lds& L, Rng& rng, V3 from, V3
 	const float* p1 = first ? Q.pos[1] : Q.pos[2];
 	const float* p2 = first ? Q.pos[2] : Q.pos[3];
 	SphTri st;
-	sphtri_make(normalize3_any(sub(mk(p0[0], p0[1], p0[2]), from)),
+	sphtri_make<GLIBC>(normalize3_any(sub(mk(p0[0], p0[1], p0[2]), from)),
 	            normalize3_any(sub(mk(p1[0], p1[1], p1[2]), from)),
 	            normalize3_any(sub(mk(p2[0], p2[1], p2[2]), from)), st);
-	dir = rand_toward_sphericaltri(rng, st);
+	dir = rand_toward_sphericaltri<GLIBC>(rng, st);
 	pdf = ssx_exact::rcp(st.area);
 	if (!is_tri) pdf *= 0.5f;
 	pdf = ssx_exact::div64_by(pdf, L.hdr().n_lights_recip); // pdf /= float(n_lights): the divisor's binary64 reciprocal comes with the scene
@@ -847,12 +874,13 @@ __device__ __forceinline__ void skip_coshemi_draws(Rng& rng) {
 
 // ------------------------------------------------------------------ BSDF sampling ----
 // util/random.cpp:29-49
+template <bool GLIBC = false>
 __device__ __forceinline__ V3 rand_coshemi(Rng& rng, float& pdf) {
 	V3 result;
 	do {
 		float angle = rand_1f(rng) * (2.0f * SSX_PI_F);
 		float s, c;
-		ssx_sincosf(angle, &s, &c);
+		if (GLIBC) ssx_glibc_sincosf(angle, &s, &c); else ssx_sincosf(angle, &s, &c);
 		float radius_sq = rand_1f(rng);
 		float radius = ssx_exact::sqrt_normal(radius_sq);
 		result = mk(radius * c, ssx_exact::sqrt_normal(1 - radius_sq), radius * s);
@@ -1027,7 +1055,7 @@ __device__ __forceinline__ void hit_st(const SsxBlobQuad& Q, uint32_t which, con
 // BLACK: the kernel knows the shortcut for black surfaces (below).  It changes no result, so a kernel may leave it out: the kernels of the Cornell
 // topology do -- the scenes that have it rarely hold a black surface, and the test and the merge behind the branch cost their loop 25 instructions
 // per iteration (+0.7 % of the headline's time, profiles/r06/NOTES.md section 8).
-template <bool NARROW, bool BLACK>
+template <bool NARROW, bool BLACK, bool GLIBC = false>
 __device__ __forceinline__ bool path_step(const Lds& L, const ShadowQ& q, const SsxKernelArgs& a, const LogRef& lg, Path& p, bool& pushed, uint32_t& level_word) {
 	const SsxBlobHeader& h = L.hdr();
 	// what the level's entry (or the path's tail word) says about this level: slot of its next-event term << 13 | has an emission term << 26
@@ -1089,7 +1117,7 @@ __device__ __forceinline__ bool path_step(const Lds& L, const ShadowQ& q, const 
 	if (els && (!a.indirect_only || p.depth > 0u)) {
 		V3 sdir; uint32_t light; float spdf;
 		SSX_STAT(8); // light sampling
-		sample_light(L, p.rng, hit_pos, sdir, light, spdf);
+		sample_light<GLIBC>(L, p.rng, hit_pos, sdir, light, spdf);
 		float n_dot_l = dot3(sdir, N);
 		if (n_dot_l > 0.0f) {
 			SSX_STAT(9); // next-event contribution
@@ -1132,7 +1160,7 @@ __device__ __forceinline__ bool path_step(const Lds& L, const ShadowQ& q, const 
 	V3 w_i; float pdf_w_i; float f_s[4];
 	if (M.kind == 0u) {
 		SSX_STAT(11); // BSDF sample
-		w_i = rand_coshemi(p.rng, pdf_w_i);
+		w_i = rand_coshemi<GLIBC>(p.rng, pdf_w_i);
 		w_i = get_rotated_to(w_i, N);
 #pragma unroll
 		for (int k = 0; k < 4; ++k) f_s[k] = f_lamb[k];
@@ -1689,7 +1717,8 @@ __device__ __forceinline__ void generate_unit(const Lds& L, const WorkUnit& u, u
 }
 
 // CALIB: the calibration render of ssx_upload_scene (ssx_calibrate_kernel) also counts the rays that leave the scene
-template <int TOPO, bool NARROW, bool CALIB = false>
+// GLIBC: libm = glibc-2.35 (the _glibc kernels): glibc's transcendentals instead of ssx_fmath.h's
+template <int TOPO, bool NARROW, bool CALIB = false, bool GLIBC = false>
 __device__ __forceinline__ void render_body(const SsxKernelArgs& a) {
 	constexpr bool FUSE_GEN = TOPO == 2; // the kernels that can make their samples themselves (SsxKernelArgs::fuse_gen): the plane topology's, whose scenes trace camera rays in the path loop
 	// ... and, in builds with -DSSX_FUSE_UNIT only, the Cornell topology's, per work unit (generate_unit), where camera rays are traced ahead of the
@@ -1701,7 +1730,7 @@ __device__ __forceinline__ void render_body(const SsxKernelArgs& a) {
 #else
 	constexpr bool FUSE_UNIT = false;
 #endif
-	uint32_t* const lds_words = stage_lds(a);
+	uint32_t* const lds_words = stage_lds<GLIBC>(a);
 	Lds L; L.w = lds_words;
 
 	const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63u; // (wave: an SGPR, and with it everything derived from it)
@@ -1876,7 +1905,7 @@ __device__ __forceinline__ void render_body(const SsxKernelArgs& a) {
 				LogRef lg;
 				lg.cnt = log_cnt; lg.wave_base = wave_slot * 2u * a.unit_cohorts; lg.tagw = p_tag;
 				uint32_t level_word;
-				if (!path_step<NARROW, TOPO != 1>(L, sq, a, lg, p, pushed, level_word)) end_path(level_word, 1u);
+				if (!path_step<NARROW, TOPO != 1, GLIBC>(L, sq, a, lg, p, pushed, level_word)) end_path(level_word, 1u);
 			}
 			sq.count += (uint32_t)__popcll(__ballot(pushed));
 		}
@@ -1922,9 +1951,17 @@ __device__ __forceinline__ void render_body(const SsxKernelArgs& a) {
 // size (wide / narrow, ssx_blob.h); the host picks.
 #define SSX_PATH_KERNEL(name, topo, narrow, waves) \
 	extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(waves))) name(SsxKernelArgs a) { render_body<topo, narrow>(a); }
+// libm = glibc-2.35: the same kernels with glibc's transcendentals (render_body's GLIBC), named <default name>_glibc
+#define SSX_PATH_KERNEL_GLIBC(name, topo, narrow, waves) \
+	extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(waves))) name(SsxKernelArgs a) { render_body<topo, narrow, false, true>(a); }
 #ifdef SSX_JIT_BUILD // the run-time compilation holds the two path kernels of the uploaded scene's topology, nothing else
+#if SSX_JIT_GLIBC // (the libm mode is a compile flag of the run-time compilation, and so part of its cache key: csrc/ssx_jit.h)
+SSX_PATH_KERNEL_GLIBC(ssx_render_kernel_jit, 3, false, SSX_WAVES_PER_EU)
+SSX_PATH_KERNEL_GLIBC(ssx_render_kernel_jit_nq, 3, true, SSX_WAVES_PER_EU)
+#else
 SSX_PATH_KERNEL(ssx_render_kernel_jit, 3, false, SSX_WAVES_PER_EU)
 SSX_PATH_KERNEL(ssx_render_kernel_jit_nq, 3, true, SSX_WAVES_PER_EU)
+#endif
 #else
 SSX_PATH_KERNEL(ssx_render_kernel, 0, false, SSX_WAVES_PER_EU)
 SSX_PATH_KERNEL(ssx_render_kernel_cornell, 1, false, SSX_WAVES_PER_EU)
@@ -1933,9 +1970,16 @@ SSX_PATH_KERNEL(ssx_render_kernel_plane, 2, false, SSX_WAVES_PER_EU)
 SSX_PATH_KERNEL(ssx_render_kernel_nq, 0, true, SSX_WAVES_PER_EU)
 SSX_PATH_KERNEL(ssx_render_kernel_cornell_nq, 1, true, SSX_WAVES_PER_EU)
 SSX_PATH_KERNEL(ssx_render_kernel_plane_nq, 2, true, SSX_WAVES_PER_EU)
+SSX_PATH_KERNEL_GLIBC(ssx_render_kernel_glibc, 0, false, SSX_WAVES_PER_EU)
+SSX_PATH_KERNEL_GLIBC(ssx_render_kernel_cornell_glibc, 1, false, SSX_WAVES_PER_EU)
+SSX_PATH_KERNEL_GLIBC(ssx_render_kernel_plane_glibc, 2, false, SSX_WAVES_PER_EU)
+SSX_PATH_KERNEL_GLIBC(ssx_render_kernel_nq_glibc, 0, true, SSX_WAVES_PER_EU)
+SSX_PATH_KERNEL_GLIBC(ssx_render_kernel_cornell_nq_glibc, 1, true, SSX_WAVES_PER_EU)
+SSX_PATH_KERNEL_GLIBC(ssx_render_kernel_plane_nq_glibc, 2, true, SSX_WAVES_PER_EU)
 #endif
 // The generic kernel under another name for the calibration render of ssx_upload_scene (64x64x4 samples), so that
-// kernel traces and statistics of ssx_render_kernel* contain real launches only.  Narrow queue entries: it stages the
+// kernel traces and statistics of ssx_render_kernel* contain real launches only.  It stays on ssx_fmath.h's functions in glibc mode too:
+// its image is thrown away, only its ray counts size the plan (and a render's image does not depend on the plan).  Narrow queue entries: it stages the
 // whole blob, which may only fit with them.
 extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) ssx_calibrate_kernel(SsxKernelArgs a) { render_body<0, true, true>(a); }
 #endif

@@ -33,7 +33,7 @@ void print_usage() {
 		"    `--indirect-only`/`-io`\n"
 		"          Render only indirect illumination.\n"
 		"  MI355X build:\n"
-		"    `--gpus=<n>` `--seed=<n>` `--observer=1931|2006` `--uplift=ours|meng|jh` `--jh-coeff=<file>` `--meng-grid=<file>` `--rgb` `--no-explicit-light-sampling` `--no-flat-field-correction` `--tile-major` `--reduce=peer|rccl`\n"
+		"    `--gpus=<n>` `--seed=<n>` `--observer=1931|2006` `--uplift=ours|meng|jh` `--jh-coeff=<file>` `--meng-grid=<file>` `--rgb` `--no-explicit-light-sampling` `--no-flat-field-correction` `--tile-major` `--reduce=peer|rccl` `--libm=build|glibc-2.35`\n"
 		"    `--texture=<png>` `--light-scale=<x>` `--data-dir=<dir>`\n");
 }
 
@@ -106,6 +106,10 @@ void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o) {
 	if (a.take("--no-explicit-light-sampling", "", &v)) o->explicit_light_sampling = false;
 	if (a.take("--no-flat-field-correction", "", &v)) o->flat_field_correction = false;
 	if (a.take("--tile-major", "", &v)) o->tile_major = true;
+	if (a.take("--libm", "", &v)) {
+		if (v == "build") o->libm = SSX_LIBM_BUILD; else if (v == "glibc-2.35") o->libm = SSX_LIBM_GLIBC_2_35;
+		else { std::fprintf(stderr, "Invalid value for --libm (build|glibc-2.35)!\n"); throw -2; }
+	}
 	if (a.take("--reduce", "", &v)) {
 		if (v == "rccl") o->reduce_rccl = true;
 		else if (v != "peer") { std::fprintf(stderr, "Unrecognized --reduce \"%s\" (peer | rccl)\n", v.c_str()); throw -2; }

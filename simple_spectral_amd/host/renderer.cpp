@@ -159,6 +159,7 @@ void Renderer::render_start() {
 		p.spp_per_launch = 0;
 		p.tile_major = options.tile_major ? 1u : 0u;
 		p.seed = options.seed;
+		p.libm = options.libm;
 		int rc = api_->render_start(ctxs_[d], &p);
 		if (rc) throw HostError{ rc, std::string("ssx_render_start: ") + api_->last_error(ctxs_[d]) };
 	}

@@ -60,6 +60,9 @@ class Options:
     spp_per_launch: int = 0
     tile_major: bool = False             # ssx_render_params.tile_major: walk through the tiles like the reference (a stopped render keeps
     #                                       finished tiles at full sample count, the rest untouched) instead of through the samples
+    libm: str = "build"                  # ssx_render_params.libm: "build" (include/ssx_fmath.h's sinf / cosf / acosf, the same on every
+    #                                       platform) | "glibc-2.35" (glibc 2.35's x86-64 functions: the image of the reference as built on a stock
+    #                                       x86-64 glibc 2.35 system)
     data_dir: str = field(default=DEFAULT_DATA_DIR)
 
 
@@ -184,6 +187,9 @@ class Renderer:
         p.spp_per_launch = o.spp_per_launch
         p.tile_major = int(o.tile_major)
         p.seed = o.seed
+        if o.libm not in _capi.LIBM_MODES:
+            raise ValueError("Options.libm: %r is not one of %s" % (o.libm, ", ".join(sorted(_capi.LIBM_MODES))))
+        p.libm = _capi.LIBM_MODES[o.libm]
         for k, v in over.items():
             setattr(p, k, v)
         return p
