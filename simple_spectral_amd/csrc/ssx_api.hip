@@ -58,8 +58,7 @@ struct ssx_ctx {
 	uint32_t path_blob_words = 0; // what the path kernel stages: without the per-quad vertex table when a specialised kernel runs
 	uint32_t topology = 0;        // 0, the built-in mesh topology the scene matched (csrc/ssx_pass1_gen.h), or 3: its own, compiled at upload
 	int jit_mode = SSX_JIT_BACKGROUND; // ssx_set_jit: how pass 1 gets specialised for scenes that match no built-in topology
-	const ssx_jit::Kernels* jit_kernels = nullptr; // the run-time compiled kernels of the uploaded scene (topology 3)
-	const ssx_jit::Kernels* jit_kernels_glibc = nullptr; // ... the same in libm = glibc-2.35 (compiled when a glibc-mode render first needs them)
+	const ssx_jit::Kernels* jit_kernels[2] = {}; // [libm] the run-time compiled kernels of the uploaded scene (topology 3), a mode's when its first render needs them
 	uint32_t libm = SSX_LIBM_BUILD; // the libm of the current (or last) render: which kernel twins run (path_kernel_ref)
 	// A scene waiting for its own kernels runs the generic one meanwhile: its second blob (packed for topology 3 at upload, the
 	// caller's description is gone later) waits on the device, and the context swaps at the start of a render once the code is
@@ -625,9 +624,8 @@ Batch make_batch(ssx_ctx* ctx, const LaunchPlan& pl, uint32_t k0, uint32_t k1) {
 	a.unit_cohorts = (a.group_spp + SSX_COHORT_KS - 1u) / SSX_COHORT_KS;
 	b.units = a.my_tiles * a.n_groups;
 	// units per grab (ssx_kernels.hip rotate_fetch): four where paths are short and a wave's lanes run dry together (plane-srgb: +0.9 %), one where they are
-	// long (Cornell box: four cost 0.3 %); SSX_UNIT_GRAB=n under SSX_DEBUG_ENV=1 for A/B runs
+	// long (Cornell box: four cost 0.3 %)
 	a.unit_grab = ctx->calib_frames >= 2.0f ? 1u : 4u;
-	if (const char* e = debug_env("SSX_UNIT_GRAB")) { const int v = atoi(e); if (v >= 1 && v <= 16) a.unit_grab = (uint32_t)v; }
 	b.n_rec = a.n_records;
 	// sample arrays and logs are shared by all batches of a render: their kernels run one after the other in stream order
 	b.rc = ensure_logs(ctx, a.unit_cohorts);
@@ -649,26 +647,27 @@ size_t path_lds_bytes(uint32_t blob_words, uint32_t queue_words) {
 #endif
 	return n;
 }
-// the path megakernel for a pass-1 variant (0 generic, 1 Cornell topology, 2 plane topology) and queue entry size
-typedef void (*path_kernel_t)(SsxKernelArgs);
-path_kernel_t path_kernel_of(uint32_t topology, bool narrow, uint32_t libm = SSX_LIBM_BUILD) {
-	if (libm == SSX_LIBM_GLIBC_2_35) {
-		if (topology == 1u) return narrow ? ssx_render_kernel_cornell_nq_glibc : ssx_render_kernel_cornell_glibc;
-		if (topology == 2u) return narrow ? ssx_render_kernel_plane_nq_glibc : ssx_render_kernel_plane_glibc;
-		return narrow ? ssx_render_kernel_nq_glibc : ssx_render_kernel_glibc;
-	}
-	if (topology == 1u) return narrow ? ssx_render_kernel_cornell_nq : ssx_render_kernel_cornell;
-	if (topology == 2u) return narrow ? ssx_render_kernel_plane_nq : ssx_render_kernel_plane;
-	return narrow ? ssx_render_kernel_nq : ssx_render_kernel;
-}
+// The path megakernels of this library: [libm][pass-1 variant: 0 generic, 1 Cornell topology, 2 plane topology][narrow queue entries].
+// Topology 3 runs the run-time compiled pair of the scene's pattern (ssx_ctx::jit_kernels), named the same in both modes (other modules).
+struct PathKernel { const char* name; void (*host)(SsxKernelArgs); };
+#define SSX_PK(k) { #k, k }
+static const PathKernel kPathKernels[2][3][2] = {
+	{ { SSX_PK(ssx_render_kernel), SSX_PK(ssx_render_kernel_nq) }, { SSX_PK(ssx_render_kernel_cornell), SSX_PK(ssx_render_kernel_cornell_nq) },
+	  { SSX_PK(ssx_render_kernel_plane), SSX_PK(ssx_render_kernel_plane_nq) } },
+	{ { SSX_PK(ssx_render_kernel_glibc), SSX_PK(ssx_render_kernel_nq_glibc) }, { SSX_PK(ssx_render_kernel_cornell_glibc), SSX_PK(ssx_render_kernel_cornell_nq_glibc) },
+	  { SSX_PK(ssx_render_kernel_plane_glibc), SSX_PK(ssx_render_kernel_plane_nq_glibc) } } };
+#undef SSX_PK
+static const char* const kJitKernelNames[2] = { "ssx_render_kernel_jit", "ssx_render_kernel_jit_nq" };
+// this library's kernel for the context's libm and topology (a scene still waiting for its own kernels runs the generic one)
+const PathKernel& path_kernel_of(const ssx_ctx* ctx, bool narrow) { return kPathKernels[ctx->libm][ctx->topology < 3u ? ctx->topology : 0u][narrow]; }
 // A kernel of this library (host function) or of a run-time compiled module (topology 3), for the context's libm.  A glibc-mode render of a
 // specialised scene has its kernels (ensure_libm_kernels) before it gets here.
 struct KernelRef { const void* host = nullptr; hipFunction_t mod = nullptr; };
 KernelRef path_kernel_ref(const ssx_ctx* ctx, bool narrow) {
 	KernelRef k;
-	const ssx_jit::Kernels* jk = ctx->libm == SSX_LIBM_GLIBC_2_35 ? ctx->jit_kernels_glibc : ctx->jit_kernels;
+	const ssx_jit::Kernels* jk = ctx->jit_kernels[ctx->libm];
 	if (ctx->topology == 3u && jk) k.mod = narrow ? jk->path_nq : jk->path;
-	else k.host = (const void*)path_kernel_of(ctx->topology, narrow, ctx->libm);
+	else k.host = (const void*)path_kernel_of(ctx, narrow).host;
 	return k;
 }
 int occupancy_of(ssx_ctx* ctx, const KernelRef& k, size_t lds, int* per_cu) {
@@ -708,22 +707,10 @@ int enqueue_front(ssx_ctx* ctx, const LaunchPlan& pl, Batch& b, hipStream_t stre
 	// masks -- live behind the sample arrays: make_batch)
 	// Kernels of the plane topology make their samples in the path loop where camera rays are traced there anyway (SsxKernelArgs::fuse_gen,
 	// ssx_kernels.hip refill): no generate kernel for such a launch.  (SSX_FUSE_GEN=0 under SSX_DEBUG_ENV=1: A/B runs and tests.)
-	// Kernels of the Cornell topology do the same per WORK UNIT where camera rays are traced ahead of the path loop (pre_hits): the wave that
-	// fetches a unit makes its samples and traces their camera rays with all 64 lanes, then runs them (generate_unit) -- only the tile masks
-	// are computed ahead.  Only in builds with -DSSX_FUSE_UNIT, and there only with SSX_FUSE_GEN=1: measured, not kept (profiles/r06/NOTES.md section 3).
 	const char* fuse_env = debug_env("SSX_FUSE_GEN");
 	// (the unit carries its tile's column and row in 16 bits each: WorkUnit::txy -- an image more than 524 280 pixels wide or high keeps the generate kernel)
 	const bool tiles_fit = b.a.tiles_x <= 0xFFFFu && (b.a.height + 7u) / 8u <= 0xFFFFu;
 	b.a.fuse_gen = (!calibration && ctx->topology == 2u && !b.a.pre_hits && tiles_fit && !(fuse_env && fuse_env[0] == '0')) ? 1u : 0u;
-#ifdef SSX_FUSE_UNIT
-	if (!calibration && ctx->topology == 1u && b.a.pre_hits && fuse_env && fuse_env[0] == '1') b.a.fuse_gen = 1u;
-#endif
-	if (b.a.fuse_gen && b.a.pre_hits) {
-		SsxKernelArgs ga = b.a;
-		ga.blob_words = ctx->blob_words;
-		hipLaunchKernelGGL(ssx_tile_mask_kernel, dim3((ga.my_tiles + 3u) / 4u), dim3(256), 0, stream, ga);
-		SSX_HIP(ctx, hipGetLastError());
-	}
 	if (!b.a.fuse_gen) {
 		// camera rays + (where the scene pre-traces them) their closest hits: persistent workgroups striding over the record
 		// waves; they stage the whole blob -- the trace is the generic one, restricted per tile to the primitives its frustum
@@ -800,7 +787,7 @@ void maybe_swap_jit(ssx_ctx* ctx, uint64_t samples) {
 		std::swap(ctx->d_blob, ctx->d_blob_jit);
 		ctx->blob_words = ctx->blob_jit_words; ctx->path_blob_words = ctx->path_blob_jit_words;
 		ctx->topology = 3u;
-		(ctx->libm == SSX_LIBM_GLIBC_2_35 ? ctx->jit_kernels_glibc : ctx->jit_kernels) = k;
+		ctx->jit_kernels[ctx->libm] = k;
 		ctx->resident_blocks = 0; ctx->gen_blocks = 0; // the blob's LDS footprint changed
 		ctx->jit_pending = false; ctx->jit_state = SSX_JIT_STATE_SPECIALISED;
 	} else if (st == ssx_jit::State::Failed) {
@@ -816,7 +803,7 @@ void maybe_swap_jit(ssx_ctx* ctx, uint64_t samples) {
 // cache: the mode is part of the pattern's key and of the compile flags, csrc/ssx_jit.h).  No fall-back: the generic kernels cannot read
 // that blob.  Called before the context switches to `libm` (set_libm): a failure leaves it in the mode it was in.
 int ensure_libm_kernels(ssx_ctx* ctx, uint32_t libm) {
-	const ssx_jit::Kernels*& have = libm == SSX_LIBM_GLIBC_2_35 ? ctx->jit_kernels_glibc : ctx->jit_kernels;
+	const ssx_jit::Kernels*& have = ctx->jit_kernels[libm];
 	if (ctx->topology != 3u || have) return SSX_OK;
 	std::string err;
 	const ssx_jit::Kernels* k = ssx_jit::get(ctx->device, ctx->jit_vid, &err, libm);
@@ -1130,7 +1117,7 @@ int ssx_upload_scene(ssx_ctx* ctx, const ssx_scene_desc* s) {
 		SSX_HIP(ctx, hipMemcpy(ctx->d_jh_data, s->jh_data, bytes, hipMemcpyHostToDevice));
 	}
 	std::vector<uint32_t> blob, blob_jit;
-	ctx->jit_kernels = nullptr; ctx->jit_kernels_glibc = nullptr;
+	for (auto& k : ctx->jit_kernels) k = nullptr;
 	ctx->jit_pending = ctx->jit_requested = false; ctx->generic_samples = 0; ctx->jit_vid.clear();
 	ctx->jit_state = SSX_JIT_STATE_NONE; ctx->jit_message.clear();
 	if (ctx->d_blob_jit) { (void)hipFree(ctx->d_blob_jit); ctx->d_blob_jit = nullptr; }
@@ -1151,7 +1138,7 @@ int ssx_upload_scene(ssx_ctx* ctx, const ssx_scene_desc* s) {
 		}
 		if (st == ssx_jit::State::Failed) { ctx->jit_state = SSX_JIT_STATE_FAILED; ctx->jit_message = err; }
 		else if ((rc = pack_blob(ctx, s, ctx->d_textures, ctx->d_jh_data, blob_jit, 3, nullptr))) return rc;
-		else if (st == ssx_jit::State::Ready) { blob.swap(blob_jit); blob_jit.clear(); ctx->jit_kernels = k; ctx->jit_vid = info.vid; ctx->jit_state = SSX_JIT_STATE_SPECIALISED; }
+		else if (st == ssx_jit::State::Ready) { blob.swap(blob_jit); blob_jit.clear(); ctx->jit_kernels[SSX_LIBM_BUILD] = k; ctx->jit_vid = info.vid; ctx->jit_state = SSX_JIT_STATE_SPECIALISED; }
 		else { ctx->jit_pending = true; ctx->jit_vid = info.vid; ctx->jit_state = SSX_JIT_STATE_GENERIC_MEANWHILE; ctx->jit_requested = (st == ssx_jit::State::Pending); }
 	}
 	if (ctx->jit_pending) {
@@ -1168,11 +1155,11 @@ int ssx_upload_scene(ssx_ctx* ctx, const ssx_scene_desc* s) {
 		SsxBlobHeader* bh = reinterpret_cast<SsxBlobHeader*>(blob.data());
 		ctx->topology = bh->topology;
 		ctx->path_blob_words = (bh->topology || bh->perm_hbm) ? bh->words_without_perm : ctx->blob_words;
-		if (bh->perm_hbm || bh->topology) { // the permuted vertex table is read from this copy (large scenes; the camera rays a Cornell-topology kernel traces for its own units): tell the kernels where it is
+		if (bh->perm_hbm) { // the permuted vertex table is read from this copy (large scenes): tell the kernels where it is
 			const uint64_t at = (uint64_t)(uintptr_t)(ctx->d_blob + bh->off_perm);
 			bh->perm_ptr_lo = (uint32_t)at; bh->perm_ptr_hi = (uint32_t)(at >> 32);
 			SSX_HIP(ctx, hipMemcpy(ctx->d_blob, blob.data(), sizeof(SsxBlobHeader), hipMemcpyHostToDevice));
-			if (bh->perm_hbm) ctx->blob_words = bh->words_without_perm; // ... and stage only what precedes it
+			ctx->blob_words = bh->words_without_perm; // ... and stage only what precedes it
 		}
 	}
 	ctx->have_cam_dir = have_cam_dir;
@@ -1676,13 +1663,8 @@ const char* ssx_kernel_name(ssx_ctx* ctx) {
 	if (hipSetDevice(ctx->device) != hipSuccess) return nullptr;
 	uint32_t qw = 0;
 	if (pick_queue(ctx, ctx->path_blob_words, &qw, nullptr) != SSX_OK) return nullptr;
-	static const char* const names[2][4][2] = {
-		{ { "ssx_render_kernel", "ssx_render_kernel_nq" }, { "ssx_render_kernel_cornell", "ssx_render_kernel_cornell_nq" },
-		  { "ssx_render_kernel_plane", "ssx_render_kernel_plane_nq" }, { "ssx_render_kernel_jit", "ssx_render_kernel_jit_nq" } },
-		// libm = glibc-2.35 (the run-time compiled twins keep their names: their module is another one)
-		{ { "ssx_render_kernel_glibc", "ssx_render_kernel_nq_glibc" }, { "ssx_render_kernel_cornell_glibc", "ssx_render_kernel_cornell_nq_glibc" },
-		  { "ssx_render_kernel_plane_glibc", "ssx_render_kernel_plane_nq_glibc" }, { "ssx_render_kernel_jit", "ssx_render_kernel_jit_nq" } } };
-	return names[ctx->libm == SSX_LIBM_GLIBC_2_35 ? 1 : 0][ctx->topology < 4u ? ctx->topology : 0u][qw == SSX_QUEUE_WORDS_NARROW ? 1 : 0];
+	const bool narrow = qw == SSX_QUEUE_WORDS_NARROW;
+	return ctx->topology == 3u ? kJitKernelNames[narrow] : path_kernel_of(ctx, narrow).name;
 }
 
 int ssx_plan_info(ssx_ctx* ctx, float* frames_per_sample, int* fold_in_path_kernel) {

@@ -50,9 +50,6 @@ struct SsxBlobSpectrum { // 4 words
 // different records; a dword read is banked (address / 4) mod 32, and with a stride of 40 words the records q and q + 4 share their banks -- the
 // ~10 distinct quads a 32-lane group holds fall into 4 bank classes (2-3 way conflicts on every field).  The records must stay 16-byte aligned
 // (their table descriptors are read as 16 bytes), so the stride is a multiple of 4 words and the best period is 8 (stride 4 mod 8 words: 36, 44).
-#ifndef SSX_QUAD_PAD_WORDS
-#define SSX_QUAD_PAD_WORDS 0
-#endif
 struct SsxBlobQuad {   // 40 words (160 B): 16-byte aligned, stride 40 mod 32 = 8 banks
 	float pos[4][3];   // v00, v10, v11, v01 (light sampling needs the unpermuted positions)
 	float st[4][2];
@@ -64,9 +61,9 @@ struct SsxBlobQuad {   // 40 words (160 B): 16-byte aligned, stride 40 mod 32 = 
 	SsxBlobSpectrum albedo;
 	SsxBlobSpectrum emission;
 	uint32_t is_tri;      // the primitive is a PrimTri of v00, v10, v11 (SSX_PRIM_TRI): no second triangle, sampled as a triangle
-	uint32_t pad[1 + SSX_QUAD_PAD_WORDS];
+	uint32_t pad[1];
 };
-static_assert(sizeof(SsxBlobQuad) == 160 + 4 * SSX_QUAD_PAD_WORDS && sizeof(SsxBlobQuad) % 16 == 0, "layout");
+static_assert(sizeof(SsxBlobQuad) == 160, "layout");
 
 struct SsxBlobHeader {
 	double pv_inv[16];

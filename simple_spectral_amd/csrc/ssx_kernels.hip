@@ -543,9 +543,7 @@ namespace {
 // vertices up in the distinct-vertex table.  Same floats, same candidates, same hits either way.
 // quad_mask (TOPO 0 only): wave-uniform bit per primitive, or nullptr; primitives whose bit is clear are known not to be
 // hit by any ray of the wave (ssx_tile_mask_kernel: the camera rays of a pixel tile) and are left out of pass 1.
-// PERM_FROM_HBM (TOPO 0): the per-quad vertex table is read from the blob's copy in HBM whatever the header says -- the generic trace inside a
-// topology-specialised kernel, which does not stage that table (generate_unit).
-template <int TOPO, bool PERM_FROM_HBM = false>
+template <int TOPO>
 __device__ __forceinline__ void trace(const Lds& L, V3 orig, V3 dir, int ignore_quad, bool has_ray, HitInfo& hit, int stat_base = 0, const uint32_t* quad_mask = nullptr, SsxTimer* tm = nullptr) {
 	const RaySetup rs = ray_setup(orig, dir);
 	const SsxBlobHeader& hd = L.hdr();
@@ -555,7 +553,7 @@ __device__ __forceinline__ void trace(const Lds& L, V3 orig, V3 dir, int ignore_
 	hit.U = hit.V = hit.W = hit.det_recip = 0.0f;
 	SSX_STAT(stat_base); // lanes holding a ray (of the lanes that called)
 	// Large scenes (generic kernel): the permuted vertex table stays in HBM when it does not fit into LDS (wave-uniform)
-	const bool perm_hbm = TOPO == 0 && (PERM_FROM_HBM || hd.perm_hbm != 0u);
+	const bool perm_hbm = TOPO == 0 && hd.perm_hbm != 0u;
 	const float* const gperm = reinterpret_cast<const float*>(((uint64_t)hd.perm_ptr_hi << 32) | (uint64_t)hd.perm_ptr_lo);
 	// "Mixed" flag of a triangle = sign bit of fma(min3, max3, +0): negative iff min < 0 < max strictly (a zero
 	// edge value gives -0 + +0 = +0, an underflowing product keeps its sign) -- one v_fma instead of two
@@ -958,14 +956,7 @@ __device__ __forceinline__ uint32_t log_region(const SsxKernelArgs& a, uint32_t 
 // it with release semantics at WAVEFRONT scope; the fold starts with an acquire load of it.  Read-modify-writes continue
 // each other's release sequences, so the one load synchronises with every such store of the wave: the hand-over is a
 // release/acquire pair of the HIP memory model at the scope it happens in, at the cost of one LDS atomic per site.
-#ifdef SSX_RELEASE_ONE_LANE // (measurement only, profiles/r06/NOTES.md section 4: what the all-lanes read-modify-write of ONE LDS word costs in bank-conflict cycles)
-__device__ __forceinline__ void wave_release(uint32_t* cnt) {
-	const unsigned long long m = __ballot(1);
-	if ((threadIdx.x & 63u) == (unsigned)__builtin_ctzll(m)) (void)__hip_atomic_fetch_add(cnt + 4u * SSX_UNIT_COHORTS, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WAVEFRONT);
-}
-#else
 __device__ __forceinline__ void wave_release(uint32_t* cnt) { (void)__hip_atomic_fetch_add(cnt + 4u * SSX_UNIT_COHORTS, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WAVEFRONT); }
-#endif
 __device__ __forceinline__ void wave_acquire(uint32_t* cnt) { (void)__hip_atomic_load(cnt + 4u * SSX_UNIT_COHORTS, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WAVEFRONT); }
 __device__ __forceinline__ uint32_t log_append(const LogRef& lg, uint32_t which) {
 	return __hip_atomic_fetch_add(lg.cnt + 2u * lg.group() + which, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
@@ -1245,12 +1236,9 @@ __device__ __forceinline__ void shadow_flush(const Lds& L, const SsxKernelArgs& 
 // radiance, renderer.cpp:262-263), and the sample {X, Y, Z, alpha} ({R, G, B, alpha} in RGB mode) is added to the lane's pixel sum `acc`.
 // A record's levels are a chain through its unit's log: the tail word names the entry of the last continued
 // level, every entry's `link` names the entry below and the level's own next-event term, and the chain word of
-// the next level is fetched one round trip ahead, so a level costs one round trip.  SSX_RESOLVE_WAYS records of the
+// the next level is fetched one round trip ahead, so a level costs one round trip.  SSX_COHORT_KS records of the
 // lane (consecutive k of its pixel) are folded side by side: independent chains.
-#ifndef SSX_RESOLVE_WAYS
-#define SSX_RESOLVE_WAYS SSX_COHORT_KS // measured: 4 ways spill 13 VGPRs in the path loop (-1.3 %), 3: +2.4 %, 2: +2.7 % (one box, r02t)
-#endif
-static_assert(SSX_RESOLVE_WAYS == SSX_COHORT_KS, "a pass of the fold takes one cohort");
+// (measured ways: 4 spill 13 VGPRs in the path loop (-1.3 %), 3: +2.4 %, 2: +2.7 % (one box, r02t))
 // The kernel's arguments once more, for code that runs once per work unit (fold, hand-over, unit set-up): read from the kernarg
 // segment through a pointer the compiler cannot see through, where they are needed -- not kept in SGPRs across the path loop, which
 // has none to spare (every spilled SGPR costs the hot code a v_readlane, and the allocator a VGPR copy of what it cannot keep).
@@ -1649,9 +1637,9 @@ __device__ __forceinline__ void unit_fold(const Lds& L, const SsxKernelArgs& a, 
 	double acc[4] = { 0.0, 0.0, 0.0, 0.0 }; // the pixel's running sums: in registers across the unit's passes (per pass: 0.6 % slower)
 	if (mine && has_px) { acc[0] = ld_agent(px); acc[1] = ld_agent(px + 64); acc[2] = ld_agent(px + 128); acc[3] = ld_agent(px + 192); }
 	if (has_px)
-		for (uint32_t kq = 0, n_kq = u.n_kq(), rec_base = u.rec_base(a); kq < n_kq; kq += SSX_RESOLVE_WAYS) { // one cohort per pass
+		for (uint32_t kq = 0, n_kq = u.n_kq(), rec_base = u.rec_base(a); kq < n_kq; kq += SSX_COHORT_KS) { // one cohort per pass
 			const uint32_t log_rec = log_region(a, wave_slot, tag, kq / SSX_COHORT_KS);
-			resolve_records<SSX_RESOLVE_WAYS, NARROW>(L, a, rec_base + kq * 64u + lane, 64u, min(SSX_RESOLVE_WAYS, n_kq - kq), log_rec * SSX_MAX_FRAMES, log_rec * SSX_MAX_LEVELS, lane, acc, !mine);
+			resolve_records<SSX_COHORT_KS, NARROW>(L, a, rec_base + kq * 64u + lane, 64u, min(SSX_COHORT_KS, n_kq - kq), log_rec * SSX_MAX_FRAMES, log_rec * SSX_MAX_LEVELS, lane, acc, !mine);
 		}
 	if (mine) {
 		if (has_px) { st_agent(px, acc[0]); st_agent(px + 64, acc[1]); st_agent(px + 128, acc[2]); st_agent(px + 192, acc[3]); }
@@ -1681,55 +1669,11 @@ __device__ __forceinline__ void unit_fold(const Lds& L, const SsxKernelArgs& a, 
 	}
 }
 
-// What ssx_generate_kernel does for the 64 x n_kq samples of ONE work unit, done by the wave that has just fetched the unit (kernels of the
-// Cornell topology with SsxKernelArgs::fuse_gen, scenes whose camera rays are traced ahead of the path loop): lane = pixel of the tile, one
-// round per sample of the pixel -- stream, camera ray, lambda_0 (generate_sample), the camera ray's closest hit by the generic trace over
-// the primitives of the tile's frustum (ssx_tile_mask_kernel; the vertex table from HBM, this kernel does not stage it), and the same three
-// records the generate kernel writes.  The refill reads them back (its acquire pairs with the release here: other lanes take the samples).
-// Why: the generate kernel's binary64 / 64-bit integer instruction stream runs at ~4.4 cycles per instruction on its own; inside the path
-// kernel it overlaps with the other waves' f32 work (plane-srgb, where the refill makes the samples: 10.0 ms of generate kernel became
-// 3.3 ms of path kernel, profiles/r06/NOTES.md).
-__device__ __forceinline__ void generate_unit(const Lds& L, const WorkUnit& u, uint32_t lane, V3 cam, uint32_t* cnt) {
-	const __attribute__((address_space(4))) SsxKernelArgs& c = cold_args();
-	const SsxBlobHeader& h = L.hdr();
-	const uint32_t i = (u.txy & 0xFFFFu) * 8u + (lane & 7u), j = (u.txy >> 16) * 8u + (lane >> 3);
-	const bool inside = (lane & 7u) < u.tw() && (lane >> 3) < u.th(); // lanes outside a ragged tile have no record
-	const uint32_t rec0 = (u.slot * (c.k1 - c.k0) + u.grp * c.group_spp) * 64u + lane, k_first = c.k0 + u.grp * c.group_spp;
-	for (uint32_t kq = 0, n_kq = u.n_kq(); kq < n_kq; ++kq) {
-		float4 ray = make_float4(0.0f, 0.0f, 1.0f, 0.0f); uint4 st = make_uint4(0u, 0u, 0u, 0u);
-		if (inside) generate_sample(h, c, i, j, k_first + kq, ray, st);
-		HitInfo hit;
-		trace<0, true>(L, cam, mk(ray.x, ray.y, ray.z), -1, inside, hit, 16, c.tile_mask + 4u * u.slot);
-		if (inside) {
-			float st_x = 0.0f, st_y = 0.0f;
-			if (hit.tri >= 0) {
-				const SsxBlobQuad& Q = L.quad((uint32_t)hit.tri >> 1);
-				if (Q.albedo_mode != 0u) hit_st(Q, (uint32_t)hit.tri & 1u, hit, st_x, st_y);
-			} else {
-				st = make_uint4(__float_as_uint(ray.w), (SSX_NO_SLOT << 6) | (SSX_NO_SLOT << 19), st.x, st.y); // a path that ends at level 0 without a hit (generate_body)
-			}
-			const uint32_t r = rec0 + kq * 64u;
-			c.ray[r] = ray; c.st[r] = st;
-			c.hit[r] = make_float4(hit.dist, st_x, st_y, __int_as_float(hit.tri));
-		}
-	}
-	wave_release(cnt);
-}
-
 // CALIB: the calibration render of ssx_upload_scene (ssx_calibrate_kernel) also counts the rays that leave the scene
 // GLIBC: libm = glibc-2.35 (the _glibc kernels): glibc's transcendentals instead of ssx_fmath.h's
 template <int TOPO, bool NARROW, bool CALIB = false, bool GLIBC = false>
 __device__ __forceinline__ void render_body(const SsxKernelArgs& a) {
 	constexpr bool FUSE_GEN = TOPO == 2; // the kernels that can make their samples themselves (SsxKernelArgs::fuse_gen): the plane topology's, whose scenes trace camera rays in the path loop
-	// ... and, in builds with -DSSX_FUSE_UNIT only, the Cornell topology's, per work unit (generate_unit), where camera rays are traced ahead of the
-	// loop.  Built, bit-exact on the whole parity suites, and NOT kept: +0.3 ... +1.0 % per step on one box (path kernel +0.95 ms for the 1.10 ms of
-	// generate kernel it replaces, HBM traffic unchanged: profiles/r06/ab_fuse_unit_cornell.log), below the 1.5 % the attempt was given beforehand
-	// (profiles/r06/NOTES.md section 3) -- and it costs the kernel 5 KB of code and 6 spilled SGPRs whether used or not.
-#ifdef SSX_FUSE_UNIT
-	constexpr bool FUSE_UNIT = TOPO == 1;
-#else
-	constexpr bool FUSE_UNIT = false;
-#endif
 	uint32_t* const lds_words = stage_lds<GLIBC>(a);
 	Lds L; L.w = lds_words;
 
@@ -1785,7 +1729,6 @@ __device__ __forceinline__ void render_body(const SsxKernelArgs& a) {
 		const uint32_t n_items = cur.n_items();
 		if (!(cur_valid && next_item < n_items)) return;
 		const uint64_t idle = __ballot(!active);
-		if (FUSE_UNIT && a.fuse_gen) wave_acquire(log_cnt); // the records were stored by this wave's lanes in generate_unit: any lane may take any of them
 		if (!active) {
 			const uint32_t item = next_item + __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
 			if (item < n_items) {
@@ -1877,7 +1820,6 @@ __device__ __forceinline__ void render_body(const SsxKernelArgs& a) {
 			}
 			if (u < total) {
 				unit_setup(a, u, cur); cur_tag ^= 1u; next_item = 0; cur_valid = true;
-				if (FUSE_UNIT && a.fuse_gen) generate_unit(L, cur, lane, cam, log_cnt);
 				if (lane < 2u * SSX_UNIT_COHORTS) log_cnt[2u * SSX_UNIT_COHORTS * cur_tag + lane] = 0u; // the logs of its cohorts are empty (the last unit with this tag has been folded)
 			}
 			else more = false;
@@ -1949,33 +1891,30 @@ __device__ __forceinline__ void render_body(const SsxKernelArgs& a) {
 // 4 waves per SIMD (128 VGPRs): four 256-lane workgroups per CU where the LDS allows.  One kernel per pass-1 variant
 // (generic / specialised to the mesh topology of the reference's Cornell box / plane scene) and shadow-queue entry
 // size (wide / narrow, ssx_blob.h); the host picks.
-#define SSX_PATH_KERNEL(name, topo, narrow, waves) \
-	extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(waves))) name(SsxKernelArgs a) { render_body<topo, narrow>(a); }
-// libm = glibc-2.35: the same kernels with glibc's transcendentals (render_body's GLIBC), named <default name>_glibc
-#define SSX_PATH_KERNEL_GLIBC(name, topo, narrow, waves) \
-	extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(waves))) name(SsxKernelArgs a) { render_body<topo, narrow, false, true>(a); }
-#ifdef SSX_JIT_BUILD // the run-time compilation holds the two path kernels of the uploaded scene's topology, nothing else
-#if SSX_JIT_GLIBC // (the libm mode is a compile flag of the run-time compilation, and so part of its cache key: csrc/ssx_jit.h)
-SSX_PATH_KERNEL_GLIBC(ssx_render_kernel_jit, 3, false, SSX_WAVES_PER_EU)
-SSX_PATH_KERNEL_GLIBC(ssx_render_kernel_jit_nq, 3, true, SSX_WAVES_PER_EU)
-#else
-SSX_PATH_KERNEL(ssx_render_kernel_jit, 3, false, SSX_WAVES_PER_EU)
-SSX_PATH_KERNEL(ssx_render_kernel_jit_nq, 3, true, SSX_WAVES_PER_EU)
+#ifndef SSX_JIT_GLIBC
+#define SSX_JIT_GLIBC 0
 #endif
+// glibc: libm = glibc-2.35, the same kernel with glibc's transcendentals (render_body's GLIBC), named <default name>_glibc
+#define SSX_PATH_KERNEL(name, topo, narrow, glibc) \
+	extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SSX_WAVES_PER_EU))) name(SsxKernelArgs a) { render_body<topo, narrow, false, glibc>(a); }
+#ifdef SSX_JIT_BUILD // the run-time compilation holds the two path kernels of the uploaded scene's topology, nothing else; the libm mode is
+// a compile flag of it, and so part of its cache key (csrc/ssx_jit.h)
+SSX_PATH_KERNEL(ssx_render_kernel_jit, 3, false, SSX_JIT_GLIBC)
+SSX_PATH_KERNEL(ssx_render_kernel_jit_nq, 3, true, SSX_JIT_GLIBC)
 #else
-SSX_PATH_KERNEL(ssx_render_kernel, 0, false, SSX_WAVES_PER_EU)
-SSX_PATH_KERNEL(ssx_render_kernel_cornell, 1, false, SSX_WAVES_PER_EU)
+SSX_PATH_KERNEL(ssx_render_kernel, 0, false, false)
+SSX_PATH_KERNEL(ssx_render_kernel_cornell, 1, false, false)
 #ifndef SSX_PROBE_BUILD // tools/kernel_resources.py --probe: the two kernels above only (register pressure experiments)
-SSX_PATH_KERNEL(ssx_render_kernel_plane, 2, false, SSX_WAVES_PER_EU)
-SSX_PATH_KERNEL(ssx_render_kernel_nq, 0, true, SSX_WAVES_PER_EU)
-SSX_PATH_KERNEL(ssx_render_kernel_cornell_nq, 1, true, SSX_WAVES_PER_EU)
-SSX_PATH_KERNEL(ssx_render_kernel_plane_nq, 2, true, SSX_WAVES_PER_EU)
-SSX_PATH_KERNEL_GLIBC(ssx_render_kernel_glibc, 0, false, SSX_WAVES_PER_EU)
-SSX_PATH_KERNEL_GLIBC(ssx_render_kernel_cornell_glibc, 1, false, SSX_WAVES_PER_EU)
-SSX_PATH_KERNEL_GLIBC(ssx_render_kernel_plane_glibc, 2, false, SSX_WAVES_PER_EU)
-SSX_PATH_KERNEL_GLIBC(ssx_render_kernel_nq_glibc, 0, true, SSX_WAVES_PER_EU)
-SSX_PATH_KERNEL_GLIBC(ssx_render_kernel_cornell_nq_glibc, 1, true, SSX_WAVES_PER_EU)
-SSX_PATH_KERNEL_GLIBC(ssx_render_kernel_plane_nq_glibc, 2, true, SSX_WAVES_PER_EU)
+SSX_PATH_KERNEL(ssx_render_kernel_plane, 2, false, false)
+SSX_PATH_KERNEL(ssx_render_kernel_nq, 0, true, false)
+SSX_PATH_KERNEL(ssx_render_kernel_cornell_nq, 1, true, false)
+SSX_PATH_KERNEL(ssx_render_kernel_plane_nq, 2, true, false)
+SSX_PATH_KERNEL(ssx_render_kernel_glibc, 0, false, true)
+SSX_PATH_KERNEL(ssx_render_kernel_cornell_glibc, 1, false, true)
+SSX_PATH_KERNEL(ssx_render_kernel_plane_glibc, 2, false, true)
+SSX_PATH_KERNEL(ssx_render_kernel_nq_glibc, 0, true, true)
+SSX_PATH_KERNEL(ssx_render_kernel_cornell_nq_glibc, 1, true, true)
+SSX_PATH_KERNEL(ssx_render_kernel_plane_nq_glibc, 2, true, true)
 #endif
 // The generic kernel under another name for the calibration render of ssx_upload_scene (64x64x4 samples), so that
 // kernel traces and statistics of ssx_render_kernel* contain real launches only.  It stays on ssx_fmath.h's functions in glibc mode too:

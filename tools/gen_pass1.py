@@ -137,11 +137,7 @@ def generate():
            "// Pass 1 of trace() straight-line for the mesh topologies of the reference's built-in scenes.",
            "#pragma once",
            "// sign bit set iff the three scaled depths are all < 0 (or -0): the triangle lies behind the ray's origin and is no candidate (tools/gen_pass1.py)",
-           "#ifdef SSX_NO_BEHIND_CULL // (A/B builds)",
-           "#define SSX_P1_BEHIND(a, b, c) 0u",
-           "#else",
-           "#define SSX_P1_BEHIND(a, b, c) __float_as_uint(__builtin_fmaxf(__builtin_fmaxf((a), (b)), (c)))",
-           "#endif", ""]
+           "#define SSX_P1_BEHIND(a, b, c) __float_as_uint(__builtin_fmaxf(__builtin_fmaxf((a), (b)), (c)))", ""]
     host = ["// corner -> distinct-vertex id per quad (v00, v10, v11, v01), numbered by first occurrence: what ssx_upload_scene",
             "// compares an uploaded scene's sharing pattern with, and what pass 2 of the specialised kernels looks vertices up by",
             "struct SsxTopology { uint32_t id, n_quads, n_verts; const uint8_t (*vid)[4]; };"]

@@ -262,7 +262,7 @@ def weights(lanestat_path):
             ent[m.group(1).strip()] = int(m.group(2))
             lanes[m.group(1).strip()] = float(m.group(3))
     it = ent["iteration: lanes with a path"]
-    ways = 2.0  # SSX_RESOLVE_WAYS: the counter sits inside the unrolled way loop
+    ways = 2.0  # SSX_COHORT_KS: the counter sits inside the unrolled way loop
     passes = ent["flux -> XYZ"] / ways
     e = lambda name, default=0.0: ent.get(name, default)   # (a scene without the region -- plane-srgb has no emission lookup, no camera pre-trace -- has no line)
     w = {

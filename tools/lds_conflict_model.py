@@ -4,7 +4,7 @@ mentions banks.)  No counter attributes conflicts to instructions, so this is a 
 (section LDS: lane groups and bank function per instruction; every extra distinct address on a busy bank within a group costs one LDS cycle)
 applied by Monte Carlo to the kernel's LDS reads whose address differs from lane to lane, with the blob's real offsets and strides (csrc/ssx_blob.h)
 and the lane populations of profiles/r05/lanestat.log.  It is checked against the one thing that can be measured: the change of the counter when
-the quad records' stride changes (40 -> 44 words, build -DSSX_QUAD_PAD_WORDS=4: profiles/r06/ab_third_call.log).
+the quad records' stride changes (40 -> 44 words, a padding build switch since removed: profiles/r06/ab_third_call.log).
     python tools/lds_conflict_model.py [--quads 19 --trials 4000]"""
 import argparse
 import random
