@@ -542,7 +542,7 @@ def test_black_surfaces_end_the_path_on_the_random_draws_alone():
 def test_image_wider_than_65535_tiles_plane_kernel_reads_its_samples():
     """The plane-topology kernels make a sample where a lane takes it, from the tile's column and row the work unit carries in 16 bits each
     (csrc/ssx_kernels.hip WorkUnit::txy); an image of more than 65 535 tiles in a direction keeps the generate kernel (csrc/ssx_api.hip
-    enqueue_front).  One pixel row of 65 537 tiles, ragged at the end, against the oracle."""
+    fuses_generate).  One pixel row of 65 537 tiles, ragged at the end, against the oracle."""
     W, H, spp = 8 * 65536 + 3, 1, 1
     r = Renderer(Options(scene_name="plane-srgb", res=(W, H), spp=spp, seed=5, texture="test-img.png"))
     r.render_start(); r.render_wait()
