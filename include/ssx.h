@@ -343,6 +343,69 @@ void ssx_jit_counters(uint64_t* compiled, uint64_t* disk_hits);
  * the same names with "_glibc" appended -- the run-time compiled "ssx_render_kernel_jit" keeps its name).  NULL: no scene. */
 const char* ssx_kernel_name(ssx_ctx* ctx);
 
+/* ---- Progressive rendering: continue, checkpoint / resume, noise estimate (appended; same ABI version) --------------------------------
+ * A pixel's sum is double += float(sample * 0.001f) in ascending k and is scaled by 1000 / spp only when the image is made (seeding
+ * contract above), so samples [0,a) followed by [a,b) leave the same bits as [0,b): a render can be taken up again where it ended.
+ * The context keeps a CONTINUABLE state -- the render parameters, ssx_done_spp and valid sums.  It is set by an ssx_render_start that walked
+ * through the samples (tile_major = 0) and finished or was stopped, by a tile_major one that FINISHED, and by ssx_sums_import; it is cleared
+ * by ssx_upload_scene, ssx_render_device, ssx_debug_samples, a failed render and a stopped tile_major render. */
+
+/* Samples [done, done + spp_more) of every owned pixel with the stored parameters, onto the existing sums; asynchronous like
+ * ssx_render_start (stop / wait / is_rendering as there; ssx_progress is this call's fraction, ssx_done_spp counts from zero over the whole
+ * history).  The image is then the mean over done + spp_more samples (or over the count reached when stopped).  The launch size is chosen
+ * as ssx_render_start chooses it, from spp_more.  SSX_ERR_STATE: nothing to continue, or a render is running; SSX_ERR_ARG: spp_more == 0, or
+ * more than 2^32 - 1 samples in all. */
+int ssx_render_continue(ssx_ctx* ctx, uint32_t spp_more);
+
+/* What a set of exported sums belongs to. */
+typedef struct ssx_sums_info_t {
+	uint32_t struct_size;     /* sizeof(ssx_sums_info_t) */
+	uint32_t width, height;
+	uint32_t done_spp;        /* samples per pixel the sums hold */
+	uint64_t seed;
+	uint32_t indirect_only, no_explicit_light_sampling, no_flat_field_correction, libm; /* as in ssx_render_params */
+	uint32_t rgb_mode;        /* scene uploaded with uplift == SSX_MODE_RGB */
+	uint32_t tile_first, tile_stride, tile_skew; /* whose tiles the exporter owned (every other pixel is +0) */
+	uint32_t noise_batches;   /* B of the noise estimate below; 0: none */
+	uint32_t reserved;
+	uint64_t scene_digest;    /* ssx_scene_digest of the exporter's scene */
+} ssx_sums_info_t;
+/* A 64-bit digest of the uploaded scene: its packed tables (without device addresses), the uplift's table and the texels.  The same
+ * description gives the same value in every process and on every device.  0: no scene. */
+uint64_t ssx_scene_digest(ssx_ctx* ctx);
+/* The raw binary64 accumulators, row-major [height][width][4] (row 0 = bottom), +0 for pixels the context does not own; noise_s2
+ * ([height][width] or NULL) receives S2 of the noise estimate (zeros when there is none: info->noise_batches == 0).  One kernel turns the
+ * device's [tile][component][pixel] layout into this one; the host gets one contiguous copy.  Needs the continuable state. */
+int ssx_sums_export(ssx_ctx* ctx, ssx_sums_info_t* info, double* sums, double* noise_s2);
+/* The inverse: the context takes, from the whole array, the tiles it owns under `params` (tile_first / tile_stride / tile_skew may differ
+ * from the exporter's; params->spp is ignored), becomes continuable at info->done_spp and makes the image, so that ssx_read_framebuffer
+ * returns the checkpointed one.  SSX_ERR_ARG when size, seed, a flag (indirect_only, no_explicit_light_sampling, no_flat_field_correction,
+ * libm, rgb_mode) or scene_digest differ from params and the uploaded scene, or when the context would own a tile the exporter did not
+ * (info->tile_first / tile_stride / tile_skew: one rank's unmerged export holds +0 there): ssx_last_error names the field.  With the noise estimate on,
+ * noise_s2 and info->noise_batches carry it on; without them the imported sum counts as one batch. */
+int ssx_sums_import(ssx_ctx* ctx, const ssx_render_params* params, const ssx_sums_info_t* info, const double* sums, const double* noise_s2);
+
+/* Noise estimate by batch means (default off: nothing runs and nothing is allocated).  When on, the sample-walking render loop (start and
+ * continue) runs one small kernel after each launch range [k0,k1): per owned pixel, on component 1 of the sums (Y; G in RGB mode), in
+ * binary64 without contraction
+ *     d = A_now - A_prev;   S2 += d*d / (double)(k1-k0);   A_prev = A_now
+ * -- 16 bytes of state per pixel and a batch count B on the host.  ssx_render_start resets the state, ssx_render_continue and
+ * ssx_sums_import carry it on (after an import A_prev is the imported sum).  With N = ssx_done_spp and A the current sum, the variance of the
+ * pixel's MEAN is
+ *     v = ((S2 - A*A/N) / (B-1)) / N
+ * the between-batch estimator, exact in expectation also for batches of unequal size; undefined for B < 2.  The device evaluates it with
+ * + - * / only and clamps at 0 by a compare, so it is reproducible bit for bit; square roots and ratios are the host's.
+ * (Switching it on while continuable sums exist counts those as one batch; so do the sums of a finished tile_major render, which takes no
+ * batches itself.)  Not while a render runs. */
+int ssx_set_noise_estimate(ssx_ctx* ctx, int enable);
+/* v per pixel (v_out: [height][width] or NULL; 0 for pixels the context does not own) and summary = { sum of v, sum of A/N, owned pixels, B }
+ * over the owned pixels, added on the host one after the other in row-major order -- the ranks of a multi-GPU render are combined by adding
+ * their summaries.  The image-level figure is defined as
+ *     noise = sqrt(summary[0] / n) / (summary[1] / n),   n = summary[2]
+ * the RMS standard error of the pixel means relative to the mean luminance (both in units of sample * 0.001: the constant 1000 of the image
+ * cancels).  SSX_ERR_STATE: the estimate is off, or B < 2. */
+int ssx_noise_info(ssx_ctx* ctx, double* v_out, double summary[4]);
+
 /* ---- Diagnostics for the parity tests (not part of the reference's interface) ---------------------
  * ssx_debug_eval runs one building block of the path kernel -- the same device function the kernel
  * inlines -- on n items, one per lane: `in` holds in_words 32-bit words per item, `out` receives

@@ -56,6 +56,19 @@ void ssh_free(void* p);
  * lrgb_to_xyz (9)}; returns the number of floats written. */
 int ssh_color_values(const ssh_scene* scene, const char* name, float* out, int capacity);
 
+/* The checkpoint file of a render: what ssx_sums_export hands out (ssx.h), in one file -- magic "SSXCKPT1", the ssx_sums_info_t, the scene's
+ * name and an options text ("key=value" lines: what rebuilds the scene), the [height][width][4] sums, the [height][width] S2 of the noise
+ * estimate when noise_s2 is not NULL, and a trailing 64-bit checksum.  Written next to `path` and renamed over it. */
+int ssh_checkpoint_save(const char* path, const ssx_sums_info_t* info, const char* scene_name, const char* options_text,
+                        const double* sums, const double* noise_s2);
+/* Reads one.  *sums_out and *noise_s2_out (NULL in the file without S2) are malloc'ed: release with ssh_free.  scene_name / options_text
+ * (optional) receive the terminated texts, cut to their buffers.  A truncated or altered file, or one with another magic: SSX_ERR_DATA. */
+int ssh_checkpoint_load(const char* path, ssx_sums_info_t* info, char* scene_name, size_t scene_name_size, char* options_text, size_t options_text_size,
+                        double** sums_out, double** noise_s2_out);
+/* The combine of the ranks' exports: dst's pixels that src_info's exporter owns (tile_first / tile_stride / tile_skew) <- src's, bit for bit
+ * -- by ownership mask, not by adding (-0.0 stays -0.0).  dst_s2 / src_s2: the same for S2, or NULL. */
+int ssh_sums_merge(double* dst, double* dst_s2, const double* src, const double* src_s2, const ssx_sums_info_t* src_info);
+
 const char* ssh_last_error(void);
 
 #ifdef __cplusplus

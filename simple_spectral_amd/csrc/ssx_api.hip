@@ -1,7 +1,8 @@
 // ssx_api.hip -- C ABI (include/ssx.h) over the gfx950 megakernel.  One translation unit with the
 // kernels so the host launches them directly.  No CPU fallback of any kind lives here: every
 // entry point either drives the HIP kernels or returns an error.
-// The context, its launches, the render entry points and the diagnostics are here; scene packing is in ssx_pack.h, RCCL in ssx_rccl.h.
+// The context, its launches, the render entry points and the diagnostics are here; scene packing is in ssx_pack.h, RCCL in ssx_rccl.h,
+// continue / export / import of the sums and the noise estimate (entry points and their kernels) in ssx_progressive.hip.
 #include "ssx_kernels.hip"
 #include "ssx_debug.hip"
 
@@ -120,6 +121,16 @@ struct ssx_ctx {
 	int worker_rc = 0;
 	std::atomic<uint64_t> units_enqueued{0}; // work units of every path-kernel launch so far: added to by the worker, read by ssx_units_info
 	ssx_render_params cur{};
+	// progressive rendering (csrc/ssx_progressive.hip): the sums hold samples [0, done_spp) of `cur` and may be continued or exported
+	bool continuable = false;
+	uint32_t k_begin = 0;               // first sample of the running call: 0 (ssx_render_start) or the count ssx_render_continue took up
+	bool continuing = false;            // the worker continues the sums (no clear, sample-walking whatever cur.tile_major says)
+	uint64_t scene_digest = 0;          // ssx_scene_digest
+	// noise estimate by batch means (ssx_set_noise_estimate): per pixel A_prev | S2 (row-major, 2 x width x height doubles)
+	bool noise_on = false, noise_valid = false;
+	DeviceBuffer d_noise;
+	DeviceBuffer d_stage;               // row-major staging of ssx_sums_export / ssx_sums_import / ssx_noise_info: kept from call to call (render_until asks every step)
+	uint32_t noise_batches = 0;         // B
 
 	// optional per-kernel timing (ssx_set_timing): events around each stage of each batch
 	bool timing = false;
@@ -621,25 +632,35 @@ int launch_finalize(ssx_ctx* ctx, const ssx_render_params* p, uint32_t spp, floa
 	return SSX_OK;
 }
 
+// the noise estimate's part in the render loop (csrc/ssx_progressive.hip)
+int noise_begin(ssx_ctx* ctx, const ssx_render_params* p, bool continuing);
+int noise_batch(ssx_ctx* ctx, const ssx_render_params* p, uint32_t n_k, hipStream_t stream);
+
 void worker_main(ssx_ctx* ctx) {
 	const ssx_render_params p = ctx->cur;
 	int rc = SSX_OK;
 	auto run = [&]() -> int {
 		SSX_HIP(ctx, hipSetDevice(ctx->device));
 		size_t pixels = (size_t)p.width * p.height;
-		{ int r = clear_sums(ctx, p.width, p.height, ctx->stream); if (r) return r; }
+		// ssx_render_continue: samples [k_begin, p.spp) onto the sums as they are, walking through the samples
+		const bool continuing = ctx->continuing;
+		const uint32_t k_begin = continuing ? ctx->k_begin : 0u, span = p.spp - k_begin;
+		if (!continuing) { int r = clear_sums(ctx, p.width, p.height, ctx->stream); if (r) return r; }
+		// (a tile_major render takes no batches: its sums, once finished, are adopted as ONE batch by the continue that follows -- noise_begin there)
+		if (p.tile_major && !continuing) ctx->noise_valid = false;
+		else { int r = noise_begin(ctx, &p, continuing); if (r) return r; }
 		maybe_swap_jit(ctx, 0);
 		LaunchPlan pl = make_plan(ctx, &p);
 		// progress / cancel granularity: 1/32 of the render, but at least ~32 M samples (~20 ms) per launch so
 		// that the synchronisation between launches stays a few percent
-		uint32_t chunk = p.spp_per_launch ? p.spp_per_launch : (p.spp + 31u) / 32u;
+		uint32_t chunk = p.spp_per_launch ? p.spp_per_launch : (span + 31u) / 32u;
 		if (!p.spp_per_launch) {
 			const uint64_t min_spp = ((uint64_t)32 << 20) / (pixels ? pixels : 1) + 1u;
-			if (chunk < min_spp) chunk = (uint32_t)(min_spp < p.spp ? min_spp : p.spp);
+			if (chunk < min_spp) chunk = (uint32_t)(min_spp < span ? min_spp : span);
 		}
 		if (chunk == 0) chunk = 1;
 		if (chunk > pl.max_spp_per_launch) chunk = pl.max_spp_per_launch;
-		if (p.tile_major) {
+		if (p.tile_major && !continuing) {
 			// The reference's walk (src/renderer.cpp:340-409): the tile list from tile (0,0) upwards, every tile to the full sample count.
 			// A launch takes as many of the device's tiles as make ~32 M samples (cancel granularity as below, at least one), all their
 			// samples (in sample ranges where one launch cannot hold them); a stop between launches leaves finished tiles next to
@@ -675,10 +696,11 @@ void worker_main(ssx_ctx* ctx) {
 			int r = launch_finalize(ctx, &p, p.spp, ctx->d_out.as<float>(), ctx->stream, done);
 			if (r) return r;
 			SSX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+			ctx->continuable = done == owned; // finished: every owned pixel holds [0, spp); stopped: tiles at different counts
 			return SSX_OK;
 		}
-		{ int r = ensure_samples(ctx, pl, chunk < p.spp ? chunk : p.spp); if (r) return r; }
-		for (uint32_t k0 = 0; k0 < p.spp && !ctx->stop_flag.load(); k0 += chunk) {
+		{ int r = ensure_samples(ctx, pl, chunk < span ? chunk : span); if (r) return r; }
+		for (uint32_t k0 = k_begin; k0 < p.spp && !ctx->stop_flag.load(); k0 += chunk) {
 			uint32_t k1 = (p.spp - k0 < chunk) ? p.spp : k0 + chunk;
 			if (ctx->jit_pending) { // between launches the device is idle: the kernels may change here (same bits)
 				maybe_swap_jit(ctx, (uint64_t)pixels * (k1 - k0) / p.tile_stride);
@@ -686,6 +708,7 @@ void worker_main(ssx_ctx* ctx) {
 			}
 			int r = launch_range(ctx, pl, k0, k1, ctx->stream);
 			if (r) return r;
+			if (ctx->noise_on && (r = noise_batch(ctx, &p, k1 - k0, ctx->stream))) return r;
 			SSX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 			ctx->done_spp.store(k1);
 		}
@@ -698,11 +721,44 @@ void worker_main(ssx_ctx* ctx) {
 		if (r) return r;
 		SSX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 		ctx->done_tiles.store(pl.args.my_tiles);
+		ctx->continuable = true;
 		return SSX_OK;
 	};
 	rc = run();
 	ctx->worker_rc = rc;
 	ctx->rendering.store(0);
+}
+
+// ssx_scene_digest: the scene's tables packed without device addresses (no texel or table pointers: the same words in every process),
+// then the uplift's table and the texels as the caller described them.  Eight bytes at a time through the splitmix64 finaliser.
+uint64_t digest_mix(uint64_t h, uint64_t w) {
+	uint64_t z = (h ^ w) + 0x9E3779B97F4A7C15ull;
+	z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+	z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+	return z ^ (z >> 31);
+}
+uint64_t digest_bytes(uint64_t h, const void* data, size_t n) {
+	const uint8_t* p = static_cast<const uint8_t*>(data);
+	h = digest_mix(h, (uint64_t)n);
+	for (; n >= 8; n -= 8, p += 8) { uint64_t w; memcpy(&w, p, 8); h = digest_mix(h, w); }
+	if (n) { uint64_t w = 0; memcpy(&w, p, n); h = digest_mix(h, w); }
+	return h;
+}
+uint64_t scene_digest_of(const ssx_scene_desc* s) {
+	std::vector<uint32_t> blob;
+	std::string err;
+	const std::vector<const void*> no_tex(s->n_textures, nullptr);
+	if (pack_blob(s, no_tex, nullptr, blob, err) != SSX_OK) return 0;
+	uint64_t h = digest_bytes(0x5353584449474553ull, blob.data(), blob.size() * 4);
+	for (uint32_t i = 0; i < s->n_textures; ++i) h = digest_bytes(h, s->textures[i].rgb, (size_t)3 * s->textures[i].width * s->textures[i].height);
+	if (s->uplift == SSX_UPLIFT_JH) h = digest_bytes(h, s->jh_data, (size_t)3 * s->jh_res * s->jh_res * s->jh_res * 3 * sizeof(float));
+	if (s->uplift == SSX_UPLIFT_MENG) {
+		const ssx_meng_grid* g = s->meng;
+		h = digest_bytes(h, g, offsetof(ssx_meng_grid, cells));
+		h = digest_bytes(h, g->cells, (size_t)g->grid_w * g->grid_h * 32);
+		h = digest_bytes(h, g->points, (size_t)g->n_points * (4 + (size_t)g->n_samples) * 4);
+	}
+	return h ? h : 1; // (0 means "no scene")
 }
 
 // the bounded, terminated copy of a text into a caller's buffer
@@ -819,6 +875,7 @@ int ssx_upload_scene(ssx_ctx* ctx, const ssx_scene_desc* s) {
 	ctx->device_pending = false;
 	ctx->d_textures.clear();
 	ctx->have_scene = false;
+	ctx->continuable = false; ctx->noise_valid = false; ctx->scene_digest = 0;
 	for (uint32_t i = 0; i < s->n_textures && i < SSX_MAX_TEXTURES; ++i) {
 		const ssx_texture& t = s->textures[i];
 		if (!t.rgb || t.width == 0 || t.height == 0) return fail(ctx, SSX_ERR_DATA, "Could not load texture"); // material.cpp:15-18
@@ -914,6 +971,7 @@ int ssx_upload_scene(ssx_ctx* ctx, const ssx_scene_desc* s) {
 	ctx->have_cam_dir = have_cam_dir;
 	ctx->resident_blocks = 0; ctx->gen_blocks = 0; // depend on the blob's LDS footprint
 	ctx->have_scene = true;
+	ctx->scene_digest = scene_digest_of(s);
 	return calibrate(ctx);
 }
 
@@ -966,6 +1024,7 @@ int ssx_render_device(ssx_ctx* ctx, const ssx_render_params* p_in, void* d_xyza_
 		if (grow && (rc = wait_device_pending(ctx))) return rc;
 	}
 	if ((rc = ready_to_launch(ctx, p, false))) return rc;
+	ctx->continuable = false; ctx->noise_valid = false; // the sums become this render's, which is not continued
 	if ((rc = clear_sums(ctx, p->width, p->height, stream))) return rc;
 	if (!capturing) maybe_swap_jit(ctx, (uint64_t)p->width * p->height * p->spp / p->tile_stride);
 	LaunchPlan pl = make_plan(ctx, p, !capturing);
@@ -1001,6 +1060,7 @@ int ssx_render_start(ssx_ctx* ctx, const ssx_render_params* p_in) {
 	if ((rc = ready_to_launch(ctx, p, true))) return rc;
 	ctx->cur = *p;
 	ctx->total_spp = p->spp;
+	ctx->continuable = false; ctx->continuing = false; ctx->k_begin = 0; // (the worker sets `continuable` when it leaves valid sums)
 	ctx->done_spp.store(0);
 	ctx->done_tiles.store(0);
 	ctx->stop_flag.store(0);
@@ -1020,7 +1080,8 @@ int ssx_is_rendering(ssx_ctx* ctx) { return ctx ? ctx->rendering.load() : 0; }
 
 float ssx_progress(ssx_ctx* ctx) {
 	if (!ctx || ctx->total_spp == 0) return 0.0f;
-	return (float)ctx->done_spp.load() / (float)ctx->total_spp;
+	const uint32_t done = ctx->done_spp.load(); // (a continued render: this call's fraction)
+	return done > ctx->k_begin ? (float)(done - ctx->k_begin) / (float)ctx->total_spp : 0.0f;
 }
 
 uint32_t ssx_done_spp(ssx_ctx* ctx) { return ctx ? ctx->done_spp.load() : 0u; }
@@ -1142,6 +1203,7 @@ int ssx_debug_samples(ssx_ctx* ctx, const ssx_render_params* p_in, float* xyza, 
 	LaunchPlan pl = make_plan(ctx, p);
 	if (p->spp > pl.max_spp_per_launch) return fail(ctx, SSX_ERR_ARG, "ssx_debug_samples: too many samples for one launch");
 	if ((rc = ensure_samples(ctx, pl, p->spp))) return rc;
+	ctx->continuable = false; ctx->noise_valid = false;
 	if ((rc = clear_sums(ctx, p->width, p->height, ctx->stream))) return rc;
 	Batch b = make_batch(ctx, pl, 0, p->spp);
 	b.a.keep_samples = 1u; // the fold leaves every sample's {X, Y, Z, alpha} in ray[]
@@ -1292,3 +1354,5 @@ int ssx_kernel_info(ssx_ctx* ctx, int* vgprs, int* sgprs, int* lds_bytes, int* s
 }
 
 } // extern "C"
+
+#include "ssx_progressive.hip"

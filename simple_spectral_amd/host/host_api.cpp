@@ -1,6 +1,7 @@
 // host_api.cpp -- C entry points of libssx_host.so (include/ssx_host.h).
 #include "../../include/ssx_host.h"
 
+#include "checkpoint.hpp"
 #include "color.hpp"
 #include "image_io.hpp"
 #include "scene.hpp"
@@ -8,6 +9,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <memory>
+#include <new>
+#include <vector>
 
 struct ssh_scene {
 	std::unique_ptr<ssx::ColorData> color;
@@ -110,6 +113,47 @@ int ssh_load_png_rgb8(const char* path, uint8_t** rgb_out, uint32_t* width, uint
 	} catch (const ssx::HostError& e) { return report(e); }
 }
 void ssh_free(void* p) { free(p); }
+
+int ssh_checkpoint_save(const char* path, const ssx_sums_info_t* info, const char* scene_name, const char* options_text,
+                        const double* sums, const double* noise_s2) {
+	if (!path || !info || !sums) { g_error = "NULL argument"; return SSX_ERR_ARG; }
+	try {
+		ssx::Checkpoint c;
+		c.info = *info;
+		c.scene_name = scene_name ? scene_name : ""; c.options_text = options_text ? options_text : "";
+		const size_t pixels = (size_t)info->width * info->height;
+		c.sums.assign(sums, sums + pixels * 4);
+		if (noise_s2) c.s2.assign(noise_s2, noise_s2 + pixels);
+		ssx::checkpoint_save(path, c);
+		return SSX_OK;
+	} catch (const ssx::HostError& e) { return report(e); }
+	catch (const std::exception& e) { g_error = e.what(); return SSX_ERR_DATA; }
+}
+
+int ssh_checkpoint_load(const char* path, ssx_sums_info_t* info, char* scene_name, size_t scene_name_size, char* options_text, size_t options_text_size,
+                        double** sums_out, double** noise_s2_out) {
+	if (!path || !info || !sums_out) { g_error = "NULL argument"; return SSX_ERR_ARG; }
+	*sums_out = nullptr;
+	if (noise_s2_out) *noise_s2_out = nullptr;
+	try {
+		const ssx::Checkpoint c = ssx::checkpoint_load(path);
+		auto text = [](const std::string& s, char* out, size_t n) { if (out && n) { const size_t k = s.size() < n - 1 ? s.size() : n - 1; memcpy(out, s.data(), k); out[k] = '\0'; } };
+		auto copy = [](const std::vector<double>& v) { double* p = static_cast<double*>(malloc(v.size() * sizeof(double))); if (!p) throw std::bad_alloc(); memcpy(p, v.data(), v.size() * sizeof(double)); return p; };
+		*info = c.info;
+		text(c.scene_name, scene_name, scene_name_size);
+		text(c.options_text, options_text, options_text_size);
+		*sums_out = copy(c.sums);
+		if (noise_s2_out && !c.s2.empty()) *noise_s2_out = copy(c.s2);
+		return SSX_OK;
+	} catch (const ssx::HostError& e) { return report(e); }
+	catch (const std::exception& e) { free(*sums_out); *sums_out = nullptr; g_error = e.what(); return SSX_ERR_DATA; }
+}
+
+int ssh_sums_merge(double* dst, double* dst_s2, const double* src, const double* src_s2, const ssx_sums_info_t* src_info) {
+	if (!dst || !src || !src_info || src_info->struct_size != sizeof *src_info) { g_error = "NULL argument or ssx_sums_info_t.struct_size mismatch"; return SSX_ERR_ARG; }
+	ssx::sums_merge(dst, dst_s2, src, src_s2, *src_info);
+	return SSX_OK;
+}
 
 int ssh_color_values(const ssh_scene* scene, const char* name, float* out, int capacity) {
 	if (!scene || !name || !out) return SSX_ERR_ARG;

@@ -4,6 +4,9 @@
 // --help; `name=value` or bare flags; unknown arguments produce a warning).  Additive options,
 // long names only so that none collides: --gpus=N --seed=S --observer=1931|2006 --texture=PATH
 // --light-scale=X --data-dir=DIR --uplift=ours|meng|jh --jh-coeff=FILE --meng-grid=FILE --no-explicit-light-sampling --no-flat-field-correction --tile-major --reduce=peer|rccl --rgb.
+// Progressive rendering (not with --tile-major): --checkpoint=PATH writes the pixel sums at the end of the render and on abort; --resume=PATH
+// takes them up again, -spp then being the TOTAL wanted (at or below the checkpoint's count: the image is written as it is);
+// --noise-target=X --max-samples=N [--noise-step=S] renders in steps of S samples until the noise estimate falls to X or N samples are done.
 #include "renderer.hpp"
 
 #include <chrono>
@@ -34,7 +37,8 @@ void print_usage() {
 		"          Render only indirect illumination.\n"
 		"  MI355X build:\n"
 		"    `--gpus=<n>` `--seed=<n>` `--observer=1931|2006` `--uplift=ours|meng|jh` `--jh-coeff=<file>` `--meng-grid=<file>` `--rgb` `--no-explicit-light-sampling` `--no-flat-field-correction` `--tile-major` `--reduce=peer|rccl` `--libm=build|glibc-2.35`\n"
-		"    `--texture=<png>` `--light-scale=<x>` `--data-dir=<dir>`\n");
+		"    `--texture=<png>` `--light-scale=<x>` `--data-dir=<dir>`\n"
+		"    `--checkpoint=<file>` `--resume=<file>` (`-spp` is then the total) `--noise-target=<x> --max-samples=<n> [--noise-step=<s>]`\n");
 }
 
 struct ArgList {
@@ -72,7 +76,13 @@ unsigned to_pos(const std::string& s) { // Str::to_pos (src/util/string.hpp:43-5
 	return static_cast<unsigned>(v);
 }
 
-void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o) {
+struct Progressive { // the flags of the progressive modes
+	std::string checkpoint, resume;
+	double noise_target = -1.0; // < 0: none
+	size_t max_samples = 0, noise_step = 16;
+};
+
+void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progressive* g) {
 	ArgList a;
 	for (int i = 0; i < argc; ++i) a.args.emplace_back(argv[i]);
 	o->scene_name = a.require("--scene", "-s");
@@ -114,6 +124,19 @@ void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o) {
 		if (v == "rccl") o->reduce_rccl = true;
 		else if (v != "peer") { std::fprintf(stderr, "Unrecognized --reduce \"%s\" (peer | rccl)\n", v.c_str()); throw -2; }
 	}
+	if (a.take("--checkpoint", "", &v)) g->checkpoint = v;
+	if (a.take("--resume", "", &v)) g->resume = v;
+	try {
+		if (a.take("--noise-target", "", &v)) { size_t used = 0; g->noise_target = std::stod(v, &used); if (used != v.size() || !(g->noise_target >= 0.0)) throw -2; }
+		if (a.take("--max-samples", "", &v)) g->max_samples = to_pos(v);
+		if (a.take("--noise-step", "", &v)) g->noise_step = to_pos(v);
+	} catch (...) { std::fprintf(stderr, "Invalid value for --noise-target/--max-samples/--noise-step!\n"); throw -2; }
+	if (o->tile_major && (!g->resume.empty() || !g->checkpoint.empty() || g->noise_target >= 0.0)) {
+		std::fprintf(stderr, "`--resume`, `--checkpoint` and `--noise-target` cannot be combined with `--tile-major`: only a render that walks through the samples can be continued!\n");
+		throw -2;
+	}
+	if (g->noise_target >= 0.0 && g->max_samples == 0) { std::fprintf(stderr, "`--noise-target` needs `--max-samples=<n>`!\n"); throw -2; }
+	if (g->noise_target >= 0.0 && !g->resume.empty()) { std::fprintf(stderr, "`--noise-target` cannot be combined with `--resume`!\n"); throw -2; }
 	if (a.take("--texture", "", &v)) o->texture_path = v;
 	if (a.take("--data-dir", "", &v)) o->data_dir = v;
 	if (a.args.size() > 1) {
@@ -133,8 +156,9 @@ void on_sigint(int) { g_abort = 1; }
 
 int main(int argc, char* argv[]) {
 	ssx::Renderer::Options options;
+	Progressive prog;
 	try {
-		parse_arguments(argc, argv, &options);
+		parse_arguments(argc, argv, &options, &prog);
 	} catch (int) {
 		print_usage();
 		return -1;
@@ -142,14 +166,37 @@ int main(int argc, char* argv[]) {
 	try {
 		ssx::Renderer renderer(options);
 		std::signal(SIGINT, on_sigint);
-		renderer.render_start();
 		bool stop_sent = false;
-		while (renderer.is_rendering()) { // the reference prints from its workers every 10 ms (src/renderer.cpp:352-358)
-			if (g_abort && !stop_sent) { renderer.render_stop(); stop_sent = true; std::fprintf(stderr, "\nAborting: saving the partial render ...\n"); }
-			renderer.print_progress();
-			std::this_thread::sleep_for(std::chrono::milliseconds(10));
+		if (prog.noise_target >= 0.0) {
+			const auto r = renderer.render_until(prog.noise_target, prog.noise_step, prog.max_samples, [&]() {
+				renderer.print_progress();
+				if (!g_abort || stop_sent) return false;
+				stop_sent = true; std::fprintf(stderr, "\nAborting: saving the partial render ...\n");
+				return true;
+			});
+			std::fprintf(stderr, "Noise %.6g after %zu samples per pixel (target %.6g).\n", r.second, r.first, prog.noise_target);
+		} else {
+			if (!prog.resume.empty()) {
+				try { renderer.load_checkpoint(prog.resume); }
+				catch (const ssx::HostError& e) { // not this render's checkpoint (or no checkpoint at all): bad data, as the reference exits on it
+					std::fprintf(stderr, "Cannot resume from \"%s\": %s\n", prog.resume.c_str(), e.message.c_str());
+					return -1;
+				}
+				const size_t done = renderer.done_spp();
+				std::fprintf(stderr, "Resuming \"%s\": %zu samples per pixel done, %zu wanted.\n", prog.resume.c_str(), done, options.spp);
+				if (options.spp > done) renderer.render_continue(options.spp - done);
+			} else renderer.render_start();
+			while (renderer.is_rendering()) { // the reference prints from its workers every 10 ms (src/renderer.cpp:352-358)
+				if (g_abort && !stop_sent) { renderer.render_stop(); stop_sent = true; std::fprintf(stderr, "\nAborting: saving the partial render ...\n"); }
+				renderer.print_progress();
+				std::this_thread::sleep_for(std::chrono::milliseconds(10));
+			}
 		}
+		// An aborted multi-GPU render: the devices stopped at different counts.  With a checkpoint asked for they are brought level first (the
+		// laggards finish the launches the others had done), so that the image written now is the one the checkpoint resumes from.
+		if (!prog.checkpoint.empty()) renderer.level_devices();
 		renderer.render_wait();
+		if (!prog.checkpoint.empty()) renderer.save_checkpoint(prog.checkpoint);
 	} catch (const ssx::HostError& e) {
 		std::fprintf(stderr, "%s\n", e.message.c_str());
 		return e.code;

@@ -1,5 +1,6 @@
 #include "renderer.hpp"
 
+#include "checkpoint.hpp"
 #include "image_io.hpp"
 
 #include <dlfcn.h>
@@ -9,6 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <thread>
 
 namespace ssx {
 
@@ -41,6 +43,11 @@ struct Renderer::Api {
 	uint32_t (*done_spp)(ssx_ctx*) = nullptr;
 	uint32_t (*done_tiles)(ssx_ctx*) = nullptr;
 	int (*reduce_rccl)(ssx_ctx**, int, uint32_t, uint32_t) = nullptr;
+	int (*render_continue)(ssx_ctx*, uint32_t) = nullptr;
+	int (*sums_export)(ssx_ctx*, ssx_sums_info_t*, double*, double*) = nullptr;
+	int (*sums_import)(ssx_ctx*, const ssx_render_params*, const ssx_sums_info_t*, const double*, const double*) = nullptr;
+	int (*set_noise_estimate)(ssx_ctx*, int) = nullptr;
+	int (*noise_info)(ssx_ctx*, double*, double*) = nullptr;
 
 	explicit Api(const std::string& path) {
 		handle = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
@@ -69,6 +76,11 @@ struct Renderer::Api {
 		done_spp = reinterpret_cast<decltype(done_spp)>(sym("ssx_done_spp"));
 		done_tiles = reinterpret_cast<decltype(done_tiles)>(sym("ssx_done_tiles"));
 		reduce_rccl = reinterpret_cast<decltype(reduce_rccl)>(sym("ssx_reduce_rccl"));
+		render_continue = reinterpret_cast<decltype(render_continue)>(sym("ssx_render_continue"));
+		sums_export = reinterpret_cast<decltype(sums_export)>(sym("ssx_sums_export"));
+		sums_import = reinterpret_cast<decltype(sums_import)>(sym("ssx_sums_import"));
+		set_noise_estimate = reinterpret_cast<decltype(set_noise_estimate)>(sym("ssx_set_noise_estimate"));
+		noise_info = reinterpret_cast<decltype(noise_info)>(sym("ssx_noise_info"));
 	}
 	~Api() { if (handle) dlclose(handle); }
 };
@@ -144,26 +156,164 @@ Renderer::~Renderer() {
 	for (ssx_ctx* c : ctxs_) api_->destroy(c);
 }
 
-void Renderer::render_start() {
+ssx_render_params Renderer::params_for_(size_t d, size_t spp, size_t spp_per_launch) const {
+	ssx_render_params p{};
+	p.struct_size = sizeof p;
+	p.width = static_cast<uint32_t>(options.res[0]); p.height = static_cast<uint32_t>(options.res[1]);
+	p.spp = static_cast<uint32_t>(spp);
+	p.indirect_only = options.indirect_only ? 1u : 0u;
+	p.no_explicit_light_sampling = options.explicit_light_sampling ? 0u : 1u;
+	p.no_flat_field_correction = options.flat_field_correction ? 0u : 1u;
+	p.tile_first = static_cast<uint32_t>(d); p.tile_stride = static_cast<uint32_t>(ctxs_.size());
+	p.tile_skew = ctxs_.size() > 1 ? 1u : 0u; // several devices: diagonals instead of vertical stripes of the image (include/ssx.h)
+	p.spp_per_launch = static_cast<uint32_t>(spp_per_launch);
+	p.tile_major = options.tile_major ? 1u : 0u;
+	p.seed = options.seed;
+	p.libm = options.libm;
+	return p;
+}
+
+void Renderer::check_(int rc, const char* what, ssx_ctx* c) const {
+	if (rc) throw HostError{ rc, std::string(what) + ": " + api_->last_error(c) };
+}
+
+void Renderer::start_(size_t spp, size_t spp_per_launch) {
 	time_start_ = std::chrono::steady_clock::now();
 	for (size_t d = 0; d < ctxs_.size(); ++d) {
-		ssx_render_params p{};
-		p.struct_size = sizeof p;
-		p.width = static_cast<uint32_t>(options.res[0]); p.height = static_cast<uint32_t>(options.res[1]);
-		p.spp = static_cast<uint32_t>(options.spp);
-		p.indirect_only = options.indirect_only ? 1u : 0u;
-		p.no_explicit_light_sampling = options.explicit_light_sampling ? 0u : 1u;
-		p.no_flat_field_correction = options.flat_field_correction ? 0u : 1u;
-		p.tile_first = static_cast<uint32_t>(d); p.tile_stride = static_cast<uint32_t>(ctxs_.size());
-		p.tile_skew = ctxs_.size() > 1 ? 1u : 0u; // several devices: diagonals instead of vertical stripes of the image (include/ssx.h)
-		p.spp_per_launch = 0;
-		p.tile_major = options.tile_major ? 1u : 0u;
-		p.seed = options.seed;
-		p.libm = options.libm;
-		int rc = api_->render_start(ctxs_[d], &p);
-		if (rc) throw HostError{ rc, std::string("ssx_render_start: ") + api_->last_error(ctxs_[d]) };
+		const ssx_render_params p = params_for_(d, spp, spp_per_launch);
+		check_(api_->render_start(ctxs_[d], &p), "ssx_render_start", ctxs_[d]);
 	}
-	started_ = true;
+	started_ = need_join_ = true;
+	expected_spp_ = spp;
+}
+
+void Renderer::render_start() { start_(options.spp, 0); }
+
+// Starts ssx_render_continue on the devices that are short of `target`; should one refuse, the ones already started are stopped and
+// joined before the error leaves (no worker is left behind unjoined).
+void Renderer::continue_to_(size_t target) {
+	std::vector<ssx_ctx*> begun;
+	for (ssx_ctx* c : ctxs_) {
+		const size_t mine = api_->done_spp(c);
+		if (mine >= target) continue;
+		const int rc = api_->render_continue(c, static_cast<uint32_t>(target - mine));
+		if (rc) {
+			const std::string why = std::string("ssx_render_continue: ") + api_->last_error(c);
+			for (ssx_ctx* b : begun) { api_->render_stop(b); (void)api_->render_wait(b, nullptr); }
+			throw HostError{ rc, why };
+		}
+		begun.push_back(c);
+	}
+	for (ssx_ctx* c : begun) check_(api_->render_wait(c, nullptr), "ssx_render_wait", c);
+}
+
+void Renderer::level_devices() {
+	wait_workers_();
+	size_t top = 0;
+	for (ssx_ctx* c : ctxs_) { const size_t n = api_->done_spp(c); if (n > top) top = n; }
+	continue_to_(top);
+}
+
+void Renderer::render_continue(size_t spp) {
+	level_devices(); // devices that stopped at different counts: the laggards catch up first, then all render `spp` more
+	const size_t done = done_spp();
+	std::vector<ssx_ctx*> begun;
+	for (ssx_ctx* c : ctxs_) {
+		const int rc = api_->render_continue(c, static_cast<uint32_t>(spp));
+		if (rc) {
+			const std::string why = std::string("ssx_render_continue: ") + api_->last_error(c);
+			for (ssx_ctx* b : begun) { api_->render_stop(b); (void)api_->render_wait(b, nullptr); }
+			throw HostError{ rc, why };
+		}
+		begun.push_back(c);
+	}
+	started_ = need_join_ = true;
+	expected_spp_ = done + spp;
+}
+
+size_t Renderer::done_spp() const {
+	size_t done = SIZE_MAX;
+	for (ssx_ctx* c : ctxs_) { const size_t n = api_->done_spp(c); if (n < done) done = n; }
+	return ctxs_.empty() ? 0 : done;
+}
+
+void Renderer::wait_workers_() {
+	if (!need_join_) return;
+	need_join_ = false;
+	for (ssx_ctx* c : ctxs_) check_(api_->render_wait(c, nullptr), "ssx_render_wait", c);
+}
+
+void Renderer::set_noise_estimate(bool on) {
+	for (ssx_ctx* c : ctxs_) check_(api_->set_noise_estimate(c, on ? 1 : 0), "ssx_set_noise_estimate", c);
+}
+
+double Renderer::noise(std::vector<double>* v_map) {
+	wait_workers_();
+	const size_t pixels = options.res[0] * options.res[1];
+	double total[3] = { 0.0, 0.0, 0.0 };
+	std::vector<double> v(v_map ? pixels : 0);
+	if (v_map) v_map->assign(pixels, 0.0);
+	for (ssx_ctx* c : ctxs_) { // the ranks' partial sums add up; every pixel's v is nonzero on its owner alone
+		double s[4];
+		check_(api_->noise_info(c, v_map ? v.data() : nullptr, s), "ssx_noise_info", c);
+		for (int k = 0; k < 3; ++k) total[k] += s[k];
+		if (v_map) for (size_t p = 0; p < pixels; ++p) (*v_map)[p] += v[p];
+	}
+	return std::sqrt(total[0] / total[2]) / (total[1] / total[2]);
+}
+
+std::pair<size_t, double> Renderer::render_until(double target, size_t step, size_t max_spp, const std::function<bool()>& tick) {
+	if (step == 0 || max_spp == 0) throw HostError{ SSX_ERR_ARG, "render_until: step and max_spp must be positive" };
+	set_noise_estimate(true);
+	double level = INFINITY;
+	bool stopped = false;
+	for (size_t n = 0;; ++n) {
+		if (n == 0) start_(step, step); else render_continue(step);
+		while (tick && is_rendering()) {
+			if (!stopped && tick()) { render_stop(); stopped = true; }
+			std::this_thread::sleep_for(std::chrono::milliseconds(10));
+		}
+		wait_workers_();
+		if (n >= 1 && !stopped) level = noise();
+		if (stopped || level <= target || done_spp() >= max_spp) break;
+	}
+	return { done_spp(), level };
+}
+
+void Renderer::save_checkpoint(const std::string& path) {
+	level_devices(); // a stopped multi-device render: one count for the file
+	const size_t pixels = options.res[0] * options.res[1];
+	Checkpoint ck;
+	ck.sums.assign(pixels * 4, 0.0);
+	std::vector<double> sums(pixels * 4), s2(pixels);
+	bool have_s2 = true;
+	uint32_t batches = 0;
+	for (size_t d = 0; d < ctxs_.size(); ++d) {
+		ssx_sums_info_t info{};
+		check_(api_->sums_export(ctxs_[d], &info, sums.data(), s2.data()), "ssx_sums_export", ctxs_[d]);
+		if (d == 0) { ck.info = info; batches = info.noise_batches; ck.s2.assign(pixels, 0.0); }
+		have_s2 = have_s2 && info.noise_batches != 0 && info.noise_batches == batches; // (devices brought level apart have taken different batches: not one estimate)
+		sums_merge(ck.sums.data(), ck.s2.data(), sums.data(), s2.data(), info);
+	}
+	ck.info.tile_first = 0; ck.info.tile_stride = 1; ck.info.tile_skew = 0; // the merged array is the whole image
+	if (!have_s2) { ck.s2.clear(); ck.info.noise_batches = 0; }
+	ck.scene_name = options.scene_name;
+	ck.options_text = "observer=" + std::to_string(options.observer) + "\ntexture=" + options.texture_path + "\nlight_scale=" + std::to_string(options.light_scale) +
+	                  "\nuplift=" + std::to_string(options.uplift) + "\nrgb=" + (options.rgb_mode ? "1" : "0") +
+	                  "\nexplicit_light_sampling=" + (options.explicit_light_sampling ? "1" : "0") + "\n";
+	checkpoint_save(path, ck);
+}
+
+void Renderer::load_checkpoint(const std::string& path) {
+	wait_workers_();
+	const Checkpoint ck = checkpoint_load(path);
+	for (size_t d = 0; d < ctxs_.size(); ++d) {
+		const ssx_render_params p = params_for_(d, ck.info.done_spp ? ck.info.done_spp : 1u, 0);
+		check_(api_->sums_import(ctxs_[d], &p, &ck.info, ck.sums.data(), ck.s2.empty() ? nullptr : ck.s2.data()), "ssx_sums_import", ctxs_[d]);
+	}
+	time_start_ = std::chrono::steady_clock::now();
+	started_ = true; need_join_ = false;
+	expected_spp_ = ck.info.done_spp;
 }
 
 void Renderer::render_stop() { for (ssx_ctx* c : ctxs_) api_->render_stop(c); }
@@ -207,15 +357,12 @@ void Renderer::print_progress() const {
 
 void Renderer::render_wait() {
 	if (!started_) return;
+	wait_workers_();
 	// Every device's share stays in its own HBM (ssx_render_wait without a host buffer).  The combine is
 	// the path's one exchange step (north_star: reduce of the per-GPU framebuffers over xGMI): device 0
 	// pulls each peer's framebuffer with a device-to-device copy and adds it with a kernel.  Every pixel
 	// is nonzero in exactly one device's buffer and x + 0 is exact, so the sum is bit for bit the image
 	// a single device produces (the multi-process path, bench.py, does the same with one RCCL reduce).
-	for (ssx_ctx* c : ctxs_) {
-		int rc = api_->render_wait(c, nullptr);
-		if (rc) throw HostError{ rc, std::string("ssx_render_wait: ") + api_->last_error(c) };
-	}
 	// a stopped render: every device's share is the mean over the samples IT accumulated (ssx.h: ssx_done_spp); say so when the
 	// counts differ from the request, as the image then is not what the reference would have left (finished tiles next to
 	// untouched ones, src/renderer.cpp:388-394)
@@ -228,8 +375,8 @@ void Renderer::render_wait() {
 		const size_t owned = n_tiles > d ? (n_tiles - d + ctxs_.size() - 1) / ctxs_.size() : 0;
 		if (options.tile_major) {
 			if (done_tiles[d] < owned) { partial_tiles = true; std::fprintf(stderr, "Render stopped: device %d finished %u of its %zu tiles; the others keep the checkerboard.\n", api_->device_index(ctxs_[d]), done_tiles[d], owned); }
-		} else if (done != static_cast<uint32_t>(options.spp))
-			std::fprintf(stderr, "Render stopped: device %d accumulated %u of %zu samples per pixel; its tiles hold the mean over those.\n", api_->device_index(ctxs_[d]), done, static_cast<size_t>(options.spp));
+		} else if (done != static_cast<uint32_t>(expected_spp_))
+			std::fprintf(stderr, "Render stopped: device %d accumulated %u of %zu samples per pixel; its tiles hold the mean over those.\n", api_->device_index(ctxs_[d]), done, expected_spp_);
 	}
 	ssx_ctx* root = ctxs_[0];
 	if (options.reduce_rccl) { // one RCCL reduce over all devices (a single context: RCCL with one rank)

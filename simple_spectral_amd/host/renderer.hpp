@@ -9,6 +9,7 @@
 #include "scene.hpp"
 
 #include <chrono>
+#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
@@ -74,12 +75,39 @@ public:
 	double progress() const;        // the `part` of _print_progress (src/renderer.cpp:75)
 	void print_progress() const;    // src/renderer.cpp:53-101
 
+	// Progressive rendering (include/ssx.h: the sums of a render that walked through the samples can be taken up again, bit for bit).
+	void render_continue(size_t spp);        // `spp` more samples per pixel onto what exists; asynchronous like render_start (then render_wait)
+	size_t done_spp() const;                 // samples per pixel accumulated over the whole history (the smallest count among the devices)
+	// After render_stop the devices of a multi-GPU render may hold different counts: the laggards render the missing samples (blocking; a
+	// few launches at most), so that image, checkpoint and whatever follows speak of ONE count.  render_continue and save_checkpoint do it
+	// themselves; call it BEFORE render_wait when the image written there is to be the checkpoint's.
+	void level_devices();
+	// One file with the sums of all devices, merged by ownership (host/checkpoint.hpp), after level_devices().  Not while rendering.
+	void save_checkpoint(const std::string& path);
+	// Every device takes its own tiles from the file's array; render_wait() then yields the checkpointed image, render_continue goes on from it.
+	// Throws HostError with the library's reason when the file belongs to another scene, size, seed or set of flags.
+	void load_checkpoint(const std::string& path);
+	void set_noise_estimate(bool on);        // ssx_set_noise_estimate on every device
+	// sqrt(sum v / n) / (sum A/N / n) over all devices (include/ssx.h ssx_noise_info); v_map: the per-pixel variances [height][width]
+	double noise(std::vector<double>* v_map = nullptr);
+	// Renders in steps of `step` samples per pixel (one launch, one batch of the estimate, each) until noise() <= target -- checked after every step
+	// from the second on -- or done_spp() >= max_spp; returns {done_spp, noise}.  Blocking; `tick` (optional) is called every 10 ms meanwhile
+	// and stops the render by returning true.  The decision reads only the sums: the same call gives the same count.  Then render_wait().
+	std::pair<size_t, double> render_until(double target, size_t step, size_t max_spp, const std::function<bool()>& tick = {});
+
 private:
 	struct Api;
 	std::unique_ptr<Api> api_;
 	std::vector<ssx_ctx*> ctxs_;
 	std::chrono::steady_clock::time_point time_start_;
 	bool started_ = false;
+	bool need_join_ = false;    // a worker of every context is running or waits to be joined
+	size_t expected_spp_ = 0;   // the count the running (or last) call renders to: what render_wait compares ssx_done_spp with
+	ssx_render_params params_for_(size_t d, size_t spp, size_t spp_per_launch) const;
+	void start_(size_t spp, size_t spp_per_launch);
+	void wait_workers_();
+	void continue_to_(size_t target);
+	void check_(int rc, const char* what, ssx_ctx* c) const;
 };
 
 } // namespace ssx

@@ -149,6 +149,34 @@ class Scene:
             pass
 
 
+def load_checkpoint_file(path):
+    """ssh_checkpoint_load -> (SsxSumsInfo, sums [H, W, 4], S2 [H, W] or None, scene name, options text)."""
+    host = _capi.host_lib()
+    info = _capi.SsxSumsInfo()
+    name, text = C.create_string_buffer(256), C.create_string_buffer(4096)
+    ps, p2 = C.POINTER(C.c_double)(), C.POINTER(C.c_double)()
+    rc = host.ssh_checkpoint_load(os.fsencode(path), C.byref(info), name, len(name), text, len(text), C.byref(ps), C.byref(p2))
+    if rc != 0:
+        raise SsxError(rc, host.ssh_last_error().decode())
+    try:
+        sums = np.ctypeslib.as_array(ps, shape=(info.height, info.width, 4)).copy()
+        s2 = np.ctypeslib.as_array(p2, shape=(info.height, info.width)).copy() if p2 else None
+    finally:
+        host.ssh_free(ps)
+        if p2:
+            host.ssh_free(p2)
+    return info, sums, s2, name.value.decode(), text.value.decode()
+
+
+def merge_sums(dst, dst_s2, src, src_s2, src_info):
+    """ssh_sums_merge: dst's pixels that src_info's exporter owns <- src's, bit for bit (by ownership mask, not by adding)."""
+    assert dst.dtype == np.float64 and dst.flags.c_contiguous and src.dtype == np.float64 and src.flags.c_contiguous
+    rc = _capi.host_lib().ssh_sums_merge(dst.ctypes.data, None if dst_s2 is None or src_s2 is None else dst_s2.ctypes.data, src.ctypes.data,
+                                         None if dst_s2 is None or src_s2 is None else src_s2.ctypes.data, C.byref(src_info))
+    if rc != 0:
+        raise SsxError(rc, _capi.host_lib().ssh_last_error().decode())
+
+
 class Renderer:
     """Renderer (src/renderer.hpp:14-82): render_start / render_stop / render_wait / is_rendering,
     public `framebuffer` and `scene`."""
@@ -220,6 +248,90 @@ class Renderer:
         if self.options.output_path:
             self.save(self.options.output_path)
         return self.framebuffer
+
+    # ---- progressive rendering (include/ssx.h: continue, checkpoint / resume, noise estimate) ----
+
+    def render_continue(self, spp):
+        """ssx_render_continue: `spp` more samples per pixel onto the existing sums (asynchronous: then render_wait).  The image is
+        bit for bit the one a single render of done_spp() + spp samples gives."""
+        self._check(self._lib.ssx_render_continue(self._ctx, int(spp)))
+
+    def read_framebuffer(self):
+        """The image the context holds (after load_checkpoint / import_sums: the checkpointed one) -> self.xyza, self.framebuffer."""
+        self._check(self._lib.ssx_read_framebuffer(self._ctx, self.xyza.ctypes.data))
+        self.framebuffer = self.scene.xyza_to_srgba(self.xyza)
+        return self.framebuffer
+
+    def scene_digest(self):
+        return int(self._lib.ssx_scene_digest(self._ctx))
+
+    def set_noise_estimate(self, enable=True):
+        self._check(self._lib.ssx_set_noise_estimate(self._ctx, int(bool(enable))))
+
+    def export_sums(self):
+        """ssx_sums_export -> (SsxSumsInfo, sums float64 [H, W, 4], S2 float64 [H, W] or None when the noise estimate holds nothing)."""
+        W, H = self.options.res
+        info = _capi.SsxSumsInfo()
+        sums = np.zeros((H, W, 4), dtype=np.float64)
+        s2 = np.zeros((H, W), dtype=np.float64)
+        self._check(self._lib.ssx_sums_export(self._ctx, C.byref(info), sums.ctypes.data, s2.ctypes.data))
+        return info, sums, (s2 if info.noise_batches else None)
+
+    def import_sums(self, info, sums, s2=None, **over):
+        """ssx_sums_import: the context keeps the tiles it owns under its own options (tile_first / tile_stride / tile_skew) and is
+        continuable at info.done_spp; self.xyza is the checkpointed image."""
+        sums = np.ascontiguousarray(sums, dtype=np.float64)
+        s2 = None if s2 is None else np.ascontiguousarray(s2, dtype=np.float64)
+        if sums.size != info.width * info.height * 4 or (s2 is not None and s2.size != info.width * info.height):
+            raise ValueError("import_sums: sums must have shape [info.height, info.width, 4], S2 [info.height, info.width]")
+        p = self.params(**over)
+        self._check(self._lib.ssx_sums_import(self._ctx, C.byref(p), C.byref(info), sums.ctypes.data, None if s2 is None else s2.ctypes.data))
+        self.read_framebuffer()
+
+    def save_checkpoint(self, path):
+        """The sums (and the noise estimate's S2) into one file (libssx_host.so ssh_checkpoint_save; host/checkpoint.hpp has the format)."""
+        info, sums, s2 = self.export_sums()
+        o = self.options
+        text = "observer=%d\ntexture=%s\nlight_scale=%r\nuplift=%s\nrender_mode=%s\nexplicit_light_sampling=%d\n" % (
+            o.observer, o.texture if isinstance(o.texture, str) else "", o.light_scale, o.uplift, o.render_mode, int(o.explicit_light_sampling))
+        host = _capi.host_lib()
+        rc = host.ssh_checkpoint_save(os.fsencode(path), C.byref(info), o.scene_name.encode(), text.encode(), sums.ctypes.data, None if s2 is None else s2.ctypes.data)
+        if rc != 0:
+            raise SsxError(rc, host.ssh_last_error().decode())
+
+    def load_checkpoint(self, path):
+        """Reads a checkpoint and imports it (SsxError SSX_ERR_DATA for a damaged file, SSX_ERR_ARG with the library's reason for one
+        of another scene, size, seed or set of flags).  Returns its SsxSumsInfo."""
+        info, sums, s2, _, _ = load_checkpoint_file(path)
+        self.import_sums(info, sums, s2)
+        return info
+
+    def noise(self):
+        """ssx_noise_info -> (noise, v_map): noise = sqrt(sum v / n) / (sum A/N / n), the RMS standard error of the pixel means relative to
+        the mean luminance; v_map float64 [H, W], the variance of each pixel's mean.  self.noise_summary keeps {sum v, sum A/N, n, B}."""
+        W, H = self.options.res
+        v = np.zeros((H, W), dtype=np.float64)
+        s = (C.c_double * 4)()
+        self._check(self._lib.ssx_noise_info(self._ctx, v.ctypes.data, s))
+        self.noise_summary = [float(x) for x in s]
+        return float(np.sqrt(s[0] / s[2]) / (s[1] / s[2])), v
+
+    def render_until(self, target, step, max_spp):
+        """Renders `step` samples per pixel at a time (one launch = one batch of the estimate) until noise() <= target -- checked after every
+        step from the second on -- or done_spp() >= max_spp.  Returns (done_spp, noise).  Deterministic: the decision reads only the sums."""
+        if step < 1 or max_spp < 1:
+            raise ValueError("render_until: step and max_spp must be positive")
+        self.set_noise_estimate(True)
+        self._check(self._lib.ssx_render_start(self._ctx, C.byref(self.params(spp=int(step), spp_per_launch=int(step)))))
+        self.render_wait()
+        level = float("inf")
+        while self.done_spp() < max_spp:
+            self.render_continue(step)
+            self.render_wait()
+            level, _ = self.noise()
+            if level <= target:
+                break
+        return self.done_spp(), level
 
     def render_device(self, d_ptr, stream=0, **over):
         """Enqueue the render on `stream` into the device buffer at d_ptr (W*H float4)."""
