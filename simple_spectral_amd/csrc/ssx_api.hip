@@ -1,8 +1,9 @@
 // ssx_api.hip -- C ABI (include/ssx.h) over the gfx950 megakernel.  One translation unit with the
 // kernels so the host launches them directly.  No CPU fallback of any kind lives here: every
 // entry point either drives the HIP kernels or returns an error.
-// The context, its launches, the render entry points and the diagnostics are here; scene packing is in ssx_pack.h, RCCL in ssx_rccl.h,
-// continue / export / import of the sums and the noise estimate (entry points and their kernels) in ssx_progressive.hip.
+// The context, its launches, the render worker (render_sample_walk / render_tile_walk behind start_worker), the render entry points and the
+// diagnostics are here; scene packing is in ssx_pack.h, RCCL in ssx_rccl.h, the pixel ownership rule in ssx_pixel_grid.h, continue / export /
+// import of the sums and the noise estimate (entry points and their kernels) in ssx_progressive.hip.
 #include "ssx_kernels.hip"
 #include "ssx_debug.hip"
 
@@ -121,16 +122,16 @@ struct ssx_ctx {
 	int worker_rc = 0;
 	std::atomic<uint64_t> units_enqueued{0}; // work units of every path-kernel launch so far: added to by the worker, read by ssx_units_info
 	ssx_render_params cur{};
-	// progressive rendering (csrc/ssx_progressive.hip): the sums hold samples [0, done_spp) of `cur` and may be continued or exported
-	bool continuable = false;
-	uint32_t k_begin = 0;               // first sample of the running call: 0 (ssx_render_start) or the count ssx_render_continue took up
-	bool continuing = false;            // the worker continues the sums (no clear, sample-walking whatever cur.tile_major says)
+	// Progressive rendering (csrc/ssx_progressive.hip).  What d_accum holds -- continuable: every owned pixel holds samples [0, done_spp) of `cur`,
+	// the sums may be continued or exported; noise_valid: d_noise describes them, after noise_batches batches (B).  Written by sums_invalidate /
+	// sums_publish and, for the estimate, the noise_* helpers; nowhere else.
+	struct SumsState { bool continuable = false, noise_valid = false; uint32_t noise_batches = 0; } sums;
+	uint32_t k_begin = 0;               // first sample of the running call: 0 (ssx_render_start) or the count ssx_render_continue took up (ssx_progress)
 	uint64_t scene_digest = 0;          // ssx_scene_digest
 	// noise estimate by batch means (ssx_set_noise_estimate): per pixel A_prev | S2 (row-major, 2 x width x height doubles)
-	bool noise_on = false, noise_valid = false;
+	bool noise_on = false;
 	DeviceBuffer d_noise;
 	DeviceBuffer d_stage;               // row-major staging of ssx_sums_export / ssx_sums_import / ssx_noise_info: kept from call to call (render_until asks every step)
-	uint32_t noise_batches = 0;         // B
 
 	// optional per-kernel timing (ssx_set_timing): events around each stage of each batch
 	bool timing = false;
@@ -205,9 +206,22 @@ uint32_t tiles_across(uint32_t pixels) { return (pixels + 7u) / 8u; } // 8x8 til
 size_t accum_bytes(uint32_t width, uint32_t height) { return (size_t)tiles_across(width) * tiles_across(height) * 64u * 4 * sizeof(double); }
 size_t image_bytes(uint32_t width, uint32_t height) { return (size_t)width * height * 4 * sizeof(float); } // float XYZA (d_out, d_peer)
 
+SsxPixelGrid pixel_grid(const ssx_render_params* p) { // (tile_skew reduced as in make_plan)
+	const uint32_t tx = tiles_across(p->width);
+	return SsxPixelGrid{ p->width, p->height, tx, p->tile_first, p->tile_stride, p->tile_skew % tx };
+}
+dim3 pixel_blocks(const ssx_render_params* p) { return dim3((p->width * p->height + 255u) / 256u); } // the grid of a per-pixel kernel
+
 int clear_sums(ssx_ctx* ctx, uint32_t width, uint32_t height, hipStream_t stream) {
 	SSX_HIP(ctx, hipMemsetAsync(ctx->d_accum.ptr, 0, accum_bytes(width, height), stream));
 	return SSX_OK;
+}
+// Whoever is about to overwrite or reinterpret d_accum (another render, another scene, an import) says so first; a render that fails leaves it at that.
+void sums_invalidate(ssx_ctx* ctx) { ctx->sums = ssx_ctx::SumsState{}; }
+// ... and whoever leaves samples [0, done_spp) of ctx->cur in every owned pixel says that.  (noise_batches: the estimate arrived with the sums, ssx_sums_import.)
+void sums_publish(ssx_ctx* ctx, uint32_t done_spp, int64_t noise_batches = -1) {
+	if (noise_batches >= 0) { ctx->sums.noise_valid = true; ctx->sums.noise_batches = (uint32_t)noise_batches; }
+	ctx->done_spp.store(done_spp); ctx->sums.continuable = true;
 }
 
 // Every launch keeps 48 bytes per sample ([tile slot][k][64]: camera ray, stream / tail word, camera hit) from the generate
@@ -224,6 +238,9 @@ size_t sample_bytes(size_t records) { return records / 64u * kBytesPer64Records;
 size_t sample_slots(const ssx_ctx* ctx) { return ctx->d_samples.bytes / kBytesPer64Records * 64u; } // record capacity of the allocation
 size_t log_records(const ssx_ctx* ctx) { return ctx->d_logs.bytes / SSX_LOG_BYTES_PER_RECORD; }     // log-record capacity
 constexpr uint32_t kMinUnits = 3072;                   // one wave work unit per wave slot of the GPU (256 CUs x 4 SIMDs x 3 waves)
+// Samples an asynchronous render launches between two host synchronisations, about (~20 ms): the granularity of progress and ssx_render_stop, large
+// enough that the synchronisation between launches stays a few percent.
+constexpr uint64_t kSamplesPerSync = (uint64_t)32 << 20;
 
 struct LaunchPlan { SsxKernelArgs args; uint32_t max_spp_per_launch; };
 
@@ -518,7 +535,7 @@ int launch_batch(ssx_ctx* ctx, Batch& b, hipStream_t stream) {
 // blob and the compiled kernels -- work already queued keeps the first blob, which stays allocated -- ; not asked for yet: the
 // compilation is requested once the generic kernel has served kJitAfterSamples (a test's 8 x 8 image is not worth a core-second
 // of hipRTC; a production render passes the mark in its first launch and has its kernels a second or two later).
-constexpr uint64_t kJitAfterSamples = (uint64_t)32 << 20;
+constexpr uint64_t kJitAfterSamples = kSamplesPerSync; // (a threshold of its own meaning, tied to the launch size by "in its first launch")
 // The kernels asked for and looked for are those of the render's libm (ctx->libm): each mode's first code object of the pattern comes the
 // same way; the other mode's, should a render of it follow the swap, is compiled by ensure_libm_kernels.
 void maybe_swap_jit(ssx_ctx* ctx, uint64_t samples) {
@@ -624,109 +641,135 @@ int calibrate(ssx_ctx* ctx) {
 
 // `spp` = the samples per pixel actually accumulated (Options::spp, or fewer after ssx_render_stop)
 int launch_finalize(ssx_ctx* ctx, const ssx_render_params* p, uint32_t spp, float* d_out, hipStream_t stream, uint32_t done_tiles = 0xFFFFFFFFu) {
-	uint32_t pixels = p->width * p->height;
-	hipLaunchKernelGGL(ssx_finalize_kernel, dim3((pixels + 255u) / 256u), dim3(256), 0, stream,
-	                   ctx->d_accum.as<const double>(), (float4*)d_out, p->width, p->height, tiles_across(p->width),
-	                   p->tile_first, p->tile_stride, spp, ctx->rgb_mode ? 1u : 0u, done_tiles, p->tile_skew % tiles_across(p->width));
+	hipLaunchKernelGGL(ssx_finalize_kernel, pixel_blocks(p), dim3(256), 0, stream,
+	                   ctx->d_accum.as<const double>(), (float4*)d_out, pixel_grid(p), spp, ctx->rgb_mode ? 1u : 0u, done_tiles);
 	SSX_HIP(ctx, hipGetLastError());
 	return SSX_OK;
 }
 
 // the noise estimate's part in the render loop (csrc/ssx_progressive.hip)
-int noise_begin(ssx_ctx* ctx, const ssx_render_params* p, bool continuing);
+int noise_begin(ssx_ctx* ctx, const ssx_render_params* p, uint32_t k_begin, bool continuing);
 int noise_batch(ssx_ctx* ctx, const ssx_render_params* p, uint32_t n_k, hipStream_t stream);
 
-void worker_main(ssx_ctx* ctx) {
-	const ssx_render_params p = ctx->cur;
-	int rc = SSX_OK;
-	auto run = [&]() -> int {
-		SSX_HIP(ctx, hipSetDevice(ctx->device));
-		size_t pixels = (size_t)p.width * p.height;
-		// ssx_render_continue: samples [k_begin, p.spp) onto the sums as they are, walking through the samples
-		const bool continuing = ctx->continuing;
-		const uint32_t k_begin = continuing ? ctx->k_begin : 0u, span = p.spp - k_begin;
-		if (!continuing) { int r = clear_sums(ctx, p.width, p.height, ctx->stream); if (r) return r; }
-		// (a tile_major render takes no batches: its sums, once finished, are adopted as ONE batch by the continue that follows -- noise_begin there)
-		if (p.tile_major && !continuing) ctx->noise_valid = false;
-		else { int r = noise_begin(ctx, &p, continuing); if (r) return r; }
-		maybe_swap_jit(ctx, 0);
-		LaunchPlan pl = make_plan(ctx, &p);
-		// progress / cancel granularity: 1/32 of the render, but at least ~32 M samples (~20 ms) per launch so
-		// that the synchronisation between launches stays a few percent
-		uint32_t chunk = p.spp_per_launch ? p.spp_per_launch : (span + 31u) / 32u;
-		if (!p.spp_per_launch) {
-			const uint64_t min_spp = ((uint64_t)32 << 20) / (pixels ? pixels : 1) + 1u;
-			if (chunk < min_spp) chunk = (uint32_t)(min_spp < span ? min_spp : span);
+// The asynchronous render: one worker thread per call of ssx_render_start / ssx_render_continue, walking through the samples or the tiles.  The end
+// of either walk: the image of what the sums hold, on the device, the stream idle.
+int finish_walk(ssx_ctx* ctx, const ssx_render_params& p, uint32_t spp, uint32_t done_tiles) {
+	if (const int rc = launch_finalize(ctx, &p, spp, ctx->d_out.as<float>(), ctx->stream, done_tiles)) return rc;
+	SSX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	return SSX_OK;
+}
+
+// Samples per pixel of one launch of the sample walk over `span` samples: what the caller asked for, or 1/32 of the span raised to
+// kSamplesPerSync per launch; never more than the sample arrays' budget allows.
+uint32_t sample_walk_chunk(const ssx_render_params& p, uint32_t span, const LaunchPlan& pl) {
+	const size_t pixels = (size_t)p.width * p.height;
+	const uint64_t min_spp = kSamplesPerSync / (pixels ? pixels : 1) + 1u;
+	uint32_t chunk = p.spp_per_launch ? p.spp_per_launch : (span + 31u) / 32u;
+	if (!p.spp_per_launch && chunk < min_spp) chunk = (uint32_t)(min_spp < span ? min_spp : span);
+	if (chunk == 0) chunk = 1;
+	return chunk > pl.max_spp_per_launch ? pl.max_spp_per_launch : chunk;
+}
+
+// One launch of the tile walk: as many of the device's tiles as make kSamplesPerSync (at least one), all their samples -- in sample ranges of `spp` where one
+// launch cannot hold them.  The sample arrays are sized by tiles x samples per launch: both are brought under the budget of make_plan (it assumed all tiles).
+struct TileLaunch { uint32_t tiles, spp; };
+TileLaunch tile_walk_launch(const ssx_render_params& p, const LaunchPlan& pl) {
+	const uint32_t owned = pl.args.my_tiles;
+	uint32_t spp_l = p.spp_per_launch ? p.spp_per_launch : p.spp;
+	if (spp_l > p.spp) spp_l = p.spp;
+	uint64_t per_launch = kSamplesPerSync / ((uint64_t)64 * p.spp) + 1u;
+	if (const char* e = debug_env("SSX_TILES_PER_LAUNCH")) { const int v = atoi(e); if (v >= 1) per_launch = (uint64_t)v; } // tests (under SSX_DEBUG_ENV=1)
+	if (per_launch > owned) per_launch = owned;
+	const uint64_t budget_records = (uint64_t)pl.max_spp_per_launch * owned * 64u;
+	while (spp_l > 1u && (uint64_t)spp_l * 64u > budget_records) spp_l = (spp_l + 1u) / 2u;
+	const uint64_t fit = budget_records / ((uint64_t)spp_l * 64u);
+	if (per_launch > fit) per_launch = fit ? fit : 1u;
+	return TileLaunch{ (uint32_t)per_launch, spp_l };
+}
+
+// Every owned tile, sample range by sample range: samples [k_begin, p.spp) onto cleared sums, or (continuing: ssx_render_continue) onto the
+// sums as they are.  A stop between two launches leaves every pixel at the same count.
+int render_sample_walk(ssx_ctx* ctx, const ssx_render_params& p, uint32_t k_begin, bool continuing) {
+	int rc;
+	if (!continuing && (rc = clear_sums(ctx, p.width, p.height, ctx->stream))) return rc;
+	if ((rc = noise_begin(ctx, &p, k_begin, continuing))) return rc;
+	maybe_swap_jit(ctx, 0); // (the scene's own kernels, if they have arrived: the plan is of the blob that is current now)
+	LaunchPlan pl = make_plan(ctx, &p);
+	const uint32_t span = p.spp - k_begin, chunk = sample_walk_chunk(p, span, pl);
+	if ((rc = ensure_samples(ctx, pl, chunk < span ? chunk : span))) return rc;
+	for (uint32_t k0 = k_begin; k0 < p.spp && !ctx->stop_flag.load(); k0 += chunk) {
+		const uint32_t k1 = (p.spp - k0 < chunk) ? p.spp : k0 + chunk;
+		if (ctx->jit_pending) { // between launches the device is idle: the kernels may change here (same bits)
+			maybe_swap_jit(ctx, (uint64_t)p.width * p.height * (k1 - k0) / p.tile_stride);
+			if (!ctx->jit_pending) { const uint32_t cap = pl.max_spp_per_launch; pl = make_plan(ctx, &p); pl.max_spp_per_launch = cap; }
 		}
-		if (chunk == 0) chunk = 1;
-		if (chunk > pl.max_spp_per_launch) chunk = pl.max_spp_per_launch;
-		if (p.tile_major && !continuing) {
-			// The reference's walk (src/renderer.cpp:340-409): the tile list from tile (0,0) upwards, every tile to the full sample count.
-			// A launch takes as many of the device's tiles as make ~32 M samples (cancel granularity as below, at least one), all their
-			// samples (in sample ranges where one launch cannot hold them); a stop between launches leaves finished tiles next to
-			// untouched ones.  Same units, same kernels, same bits -- only the order of the work differs.
-			const uint32_t owned = pl.args.my_tiles;
-			uint32_t spp_l = p.spp_per_launch ? p.spp_per_launch : p.spp;
-			if (spp_l > p.spp) spp_l = p.spp;
-			uint64_t per_launch = (((uint64_t)32 << 20) / ((uint64_t)64 * p.spp)) + 1u;
-			if (const char* e = debug_env("SSX_TILES_PER_LAUNCH")) { const int v = atoi(e); if (v >= 1) per_launch = (uint64_t)v; } // tests (under SSX_DEBUG_ENV=1)
-			if (per_launch > owned) per_launch = owned;
-			{ // the sample arrays are sized by tiles x samples per launch: bring the launch under the budget of make_plan (it assumed all tiles)
-				const uint64_t budget_records = (uint64_t)pl.max_spp_per_launch * owned * 64u;
-				while (spp_l > 1u && (uint64_t)spp_l * 64u > budget_records) spp_l = (spp_l + 1u) / 2u;
-				const uint64_t fit = budget_records / ((uint64_t)spp_l * 64u);
-				if (per_launch > fit) per_launch = fit ? fit : 1u;
-			}
-			LaunchPlan sized = pl; sized.args.my_tiles = (uint32_t)per_launch;
-			{ int r = ensure_samples(ctx, sized, spp_l); if (r) return r; }
-			for (uint32_t j0 = 0; j0 < owned && !ctx->stop_flag.load(); j0 += (uint32_t)per_launch) {
-				const uint32_t j1 = (owned - j0 < per_launch) ? owned : j0 + (uint32_t)per_launch;
-				maybe_swap_jit(ctx, (uint64_t)(j1 - j0) * 64u * p.spp);
-				LaunchPlan part = make_plan(ctx, &p);
-				part.args.tile_first = p.tile_first + p.tile_stride * j0; // the device's tiles j0 .. j1-1 of its list
-				part.args.my_tiles = j1 - j0;
-				int r = launch_batches(ctx, part, p.spp, spp_l, ctx->stream);
-				if (r) return r;
-				SSX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-				ctx->done_tiles.store(j1);
-				ctx->done_spp.store((uint32_t)((uint64_t)p.spp * j1 / owned)); // (progress; the finished tiles hold all p.spp samples)
-			}
-			const uint32_t done = ctx->done_tiles.load();
-			if (done == owned) ctx->done_spp.store(p.spp);
-			int r = launch_finalize(ctx, &p, p.spp, ctx->d_out.as<float>(), ctx->stream, done);
-			if (r) return r;
-			SSX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-			ctx->continuable = done == owned; // finished: every owned pixel holds [0, spp); stopped: tiles at different counts
-			return SSX_OK;
-		}
-		{ int r = ensure_samples(ctx, pl, chunk < span ? chunk : span); if (r) return r; }
-		for (uint32_t k0 = k_begin; k0 < p.spp && !ctx->stop_flag.load(); k0 += chunk) {
-			uint32_t k1 = (p.spp - k0 < chunk) ? p.spp : k0 + chunk;
-			if (ctx->jit_pending) { // between launches the device is idle: the kernels may change here (same bits)
-				maybe_swap_jit(ctx, (uint64_t)pixels * (k1 - k0) / p.tile_stride);
-				if (!ctx->jit_pending) { const uint32_t cap = pl.max_spp_per_launch; pl = make_plan(ctx, &p); pl.max_spp_per_launch = cap; }
-			}
-			int r = launch_range(ctx, pl, k0, k1, ctx->stream);
-			if (r) return r;
-			if (ctx->noise_on && (r = noise_batch(ctx, &p, k1 - k0, ctx->stream))) return r;
-			SSX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-			ctx->done_spp.store(k1);
-		}
-		// like the reference's last worker (renderer.cpp:388-394) the image is produced even after a
-		// stop.  The reference then holds finished tiles next to untouched ones; here every pixel holds
-		// the mean of the samples accumulated so far (divisor = samples done, not Options::spp), i.e. a
-		// noisier image of the right brightness with alpha as after a full render.
-		const uint32_t done = ctx->done_spp.load();
-		int r = launch_finalize(ctx, &p, done ? done : p.spp, ctx->d_out.as<float>(), ctx->stream);
-		if (r) return r;
+		if ((rc = launch_range(ctx, pl, k0, k1, ctx->stream))) return rc;
+		if (ctx->noise_on && (rc = noise_batch(ctx, &p, k1 - k0, ctx->stream))) return rc;
 		SSX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-		ctx->done_tiles.store(pl.args.my_tiles);
-		ctx->continuable = true;
-		return SSX_OK;
-	};
-	rc = run();
+		ctx->done_spp.store(k1);
+	}
+	// like the reference's last worker (renderer.cpp:388-394) the image is produced even after a stop.  The reference then holds finished tiles next
+	// to untouched ones; here every pixel holds the mean of the samples accumulated so far (divisor = samples done, not Options::spp), i.e. a noisier
+	// image of the right brightness with alpha as after a full render.
+	const uint32_t done = ctx->done_spp.load();
+	if ((rc = finish_walk(ctx, p, done ? done : p.spp, 0xFFFFFFFFu))) return rc;
+	ctx->done_tiles.store(pl.args.my_tiles);
+	sums_publish(ctx, done);
+	return SSX_OK;
+}
+
+// The reference's walk (src/renderer.cpp:340-409; ssx_render_params::tile_major): the device's tile list from its first tile upwards, a few tiles per
+// launch, every tile to the full sample count; a stop between launches leaves finished tiles next to untouched ones.  Same units, same kernels, same bits
+// -- only the order of the work differs.  It takes no batches of the noise estimate: its sums, once finished, are adopted as ONE by the continue that follows.
+int render_tile_walk(ssx_ctx* ctx, const ssx_render_params& p) {
+	int rc;
+	if ((rc = clear_sums(ctx, p.width, p.height, ctx->stream))) return rc;
+	maybe_swap_jit(ctx, 0);
+	const LaunchPlan pl = make_plan(ctx, &p);
+	const uint32_t owned = pl.args.my_tiles;
+	const TileLaunch per = tile_walk_launch(p, pl);
+	LaunchPlan sized = pl; sized.args.my_tiles = per.tiles;
+	if ((rc = ensure_samples(ctx, sized, per.spp))) return rc;
+	for (uint32_t j0 = 0; j0 < owned && !ctx->stop_flag.load(); j0 += per.tiles) {
+		const uint32_t j1 = (owned - j0 < per.tiles) ? owned : j0 + per.tiles;
+		maybe_swap_jit(ctx, (uint64_t)(j1 - j0) * 64u * p.spp);
+		LaunchPlan part = make_plan(ctx, &p);
+		part.args.tile_first = p.tile_first + p.tile_stride * j0; // the device's tiles j0 .. j1-1 of its list
+		part.args.my_tiles = j1 - j0;
+		if ((rc = launch_batches(ctx, part, p.spp, per.spp, ctx->stream))) return rc;
+		SSX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+		ctx->done_tiles.store(j1);
+		ctx->done_spp.store((uint32_t)((uint64_t)p.spp * j1 / owned)); // (progress; the finished tiles hold all p.spp samples)
+	}
+	const uint32_t done = ctx->done_tiles.load();
+	if ((rc = finish_walk(ctx, p, p.spp, done))) return rc;
+	if (done == owned) sums_publish(ctx, p.spp); // finished: every owned pixel holds [0, spp); stopped: tiles at different counts, nothing to continue
+	return SSX_OK;
+}
+
+// The worker thread of one call: ctx->cur, from sample k_begin on.  A continued render walks through the samples whatever cur.tile_major says.
+int render_walk(ssx_ctx* ctx, const ssx_render_params p, uint32_t k_begin, bool continuing) { // (its own copy of the parameters)
+	SSX_HIP(ctx, hipSetDevice(ctx->device));
+	return (p.tile_major && !continuing) ? render_tile_walk(ctx, p) : render_sample_walk(ctx, p, k_begin, continuing);
+}
+void worker_main(ssx_ctx* ctx, uint32_t k_begin, bool continuing) {
+	const int rc = render_walk(ctx, ctx->cur, k_begin, continuing);
+	if (rc) sums_invalidate(ctx); // (a continued render had valid sums until here)
 	ctx->worker_rc = rc;
 	ctx->rendering.store(0);
+}
+
+// The tail of ssx_render_start and ssx_render_continue, behind their own checks (the context's device current): `p` becomes ctx->cur and a
+// worker renders samples [k_begin, p.spp) of it, total_spp of them (ssx_progress).
+int start_worker(ssx_ctx* ctx, const ssx_render_params& p, uint32_t k_begin, bool continuing, uint32_t total_spp) {
+	if (ctx->worker.joinable()) ctx->worker.join();
+	if (const int rc = ready_to_launch(ctx, &p, true)) return rc;
+	ctx->cur = p; ctx->total_spp = total_spp; ctx->k_begin = k_begin;
+	if (!continuing) { sums_invalidate(ctx); ctx->done_spp.store(0); ctx->done_tiles.store(0); } // (the worker publishes the sums it leaves)
+	ctx->stop_flag.store(0); ctx->worker_rc = 0;
+	ctx->rendering.store(1);
+	ctx->worker = std::thread(worker_main, ctx, k_begin, continuing);
+	return SSX_OK;
 }
 
 // ssx_scene_digest: the scene's tables packed without device addresses (no texel or table pointers: the same words in every process),
@@ -875,7 +918,7 @@ int ssx_upload_scene(ssx_ctx* ctx, const ssx_scene_desc* s) {
 	ctx->device_pending = false;
 	ctx->d_textures.clear();
 	ctx->have_scene = false;
-	ctx->continuable = false; ctx->noise_valid = false; ctx->scene_digest = 0;
+	sums_invalidate(ctx); ctx->scene_digest = 0;
 	for (uint32_t i = 0; i < s->n_textures && i < SSX_MAX_TEXTURES; ++i) {
 		const ssx_texture& t = s->textures[i];
 		if (!t.rgb || t.width == 0 || t.height == 0) return fail(ctx, SSX_ERR_DATA, "Could not load texture"); // material.cpp:15-18
@@ -1024,7 +1067,7 @@ int ssx_render_device(ssx_ctx* ctx, const ssx_render_params* p_in, void* d_xyza_
 		if (grow && (rc = wait_device_pending(ctx))) return rc;
 	}
 	if ((rc = ready_to_launch(ctx, p, false))) return rc;
-	ctx->continuable = false; ctx->noise_valid = false; // the sums become this render's, which is not continued
+	sums_invalidate(ctx); // the sums become this render's, which is not continued
 	if ((rc = clear_sums(ctx, p->width, p->height, stream))) return rc;
 	if (!capturing) maybe_swap_jit(ctx, (uint64_t)p->width * p->height * p->spp / p->tile_stride);
 	LaunchPlan pl = make_plan(ctx, p, !capturing);
@@ -1053,21 +1096,9 @@ int ssx_render_start(ssx_ctx* ctx, const ssx_render_params* p_in) {
 	ssx_render_params pp;
 	int rc = begin_render(ctx, p_in, &pp, "render already in progress");
 	if (rc) return rc;
-	const ssx_render_params* const p = &pp;
-	if (ctx->worker.joinable()) ctx->worker.join();
 	SSX_HIP(ctx, hipSetDevice(ctx->device));
 	if ((rc = wait_device_pending(ctx))) return rc;
-	if ((rc = ready_to_launch(ctx, p, true))) return rc;
-	ctx->cur = *p;
-	ctx->total_spp = p->spp;
-	ctx->continuable = false; ctx->continuing = false; ctx->k_begin = 0; // (the worker sets `continuable` when it leaves valid sums)
-	ctx->done_spp.store(0);
-	ctx->done_tiles.store(0);
-	ctx->stop_flag.store(0);
-	ctx->worker_rc = 0;
-	ctx->rendering.store(1);
-	ctx->worker = std::thread(worker_main, ctx);
-	return SSX_OK;
+	return start_worker(ctx, pp, 0, false, pp.spp);
 }
 
 int ssx_render_stop(ssx_ctx* ctx) {
@@ -1203,7 +1234,7 @@ int ssx_debug_samples(ssx_ctx* ctx, const ssx_render_params* p_in, float* xyza, 
 	LaunchPlan pl = make_plan(ctx, p);
 	if (p->spp > pl.max_spp_per_launch) return fail(ctx, SSX_ERR_ARG, "ssx_debug_samples: too many samples for one launch");
 	if ((rc = ensure_samples(ctx, pl, p->spp))) return rc;
-	ctx->continuable = false; ctx->noise_valid = false;
+	sums_invalidate(ctx);
 	if ((rc = clear_sums(ctx, p->width, p->height, ctx->stream))) return rc;
 	Batch b = make_batch(ctx, pl, 0, p->spp);
 	b.a.keep_samples = 1u; // the fold leaves every sample's {X, Y, Z, alpha} in ray[]

@@ -1389,7 +1389,8 @@ __device__ __forceinline__ void resolve_records(const Lds& L, const SsxKernelArg
 // The device's tile list: slot -> tile.  The walk t' = tile_first + slot * tile_stride runs over the row-major tile list with tile row ty
 // rotated by ty * tile_skew columns (ssx_render_params::tile_skew; 0: the plain list): with N devices and a tile row of a multiple of N
 // tiles the plain list hands every device vertical stripes of the image -- the outer stripes of the Cornell box are 7 % cheaper than the
-// inner ones --, the rotated one diagonals.  Returns the tile's row-major index and its column / row.
+// inner ones --, the rotated one diagonals.  Returns the tile's row-major index and its column / row.  (The map from a pixel to its tile's
+// place in that list, for everything that asks "whose pixel is this": ssx_shared_tile, ssx_pixel_grid.h.)
 template <typename Args>
 __device__ __forceinline__ uint32_t tile_of_slot(const Args& a, uint32_t slot, uint32_t& tx, uint32_t& ty) {
 	const uint32_t t = a.tile_first + slot * a.tile_stride;
@@ -1924,32 +1925,32 @@ extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_pe
 #endif
 
 #ifndef SSX_JIT_BUILD
+#include "ssx_pixel_grid.h"
 // renderer.cpp:296,298: avg *= 1000.0/spp, then the float conversion of CIEXYZ_32F(avg) / avg.a.
 // Pixels of tiles this device does not own are written as 0 (x+0 is exact in the framebuffer sum).
 // done_tiles: how many of the device's tiles (ascending tile order) hold a result -- all of them, except after a stopped tile-major
 // render (ssx_render_params::tile_major), whose unfinished tiles stay zero like foreign ones.
-extern "C" __global__ void __launch_bounds__(256) ssx_finalize_kernel(const double* accum, float4* out, uint32_t width, uint32_t height,
-                                                  uint32_t tiles_x, uint32_t tile_first, uint32_t tile_stride, uint32_t spp, uint32_t rgb_mode, uint32_t done_tiles, uint32_t tile_skew) {
-	uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-	if (p >= width * height) return;
-	uint32_t i = p % width, j = p / width;
-	const uint32_t tile_rm = (j >> 3) * tiles_x + (i >> 3);                                      // row-major: the tile's block of the pixel sums
-	uint32_t tile = (j >> 3) * tiles_x + ((i >> 3) + ((j >> 3) * tile_skew) % tiles_x) % tiles_x;   // its place in the (rotated) list the devices share out: tile_of_slot
+extern "C" __global__ void __launch_bounds__(256) ssx_finalize_kernel(const double* accum, float4* out, SsxPixelGrid g, uint32_t spp, uint32_t rgb_mode, uint32_t done_tiles) {
+	const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+	if (p >= g.width * g.height) return;
+	const uint32_t i = p % g.width, j = p / g.width;
+	const uint32_t tile = ssx_shared_tile(g, i, j);
 	float4 o = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-	const double* const px = accum + (size_t)tile_rm * 256u + ((j & 7u) * 8u + (i & 7u)); // [tile][component][pixel of the tile] (unit_fold)
-	if (tile % tile_stride != tile_first || tile / tile_stride >= done_tiles) { out[p] = o; return; }
-	if (tile % tile_stride == tile_first && rgb_mode) { // renderer.cpp:304: avg /= double(spp)
-		const double n = (double)spp;
-		o.x = (float)(px[0] / n);
-		o.y = (float)(px[64] / n);
-		o.z = (float)(px[128] / n);
-		o.w = (float)(px[192] / n);
-	} else if (tile % tile_stride == tile_first) {
-		double sc = 1000.0 / (double)spp;
-		o.x = (float)(px[0] * sc);
-		o.y = (float)(px[64] * sc);
-		o.z = (float)(px[128] * sc);
-		o.w = (float)(px[192] * sc);
+	if (tile % g.tile_stride == g.tile_first && tile / g.tile_stride < done_tiles) {
+		const double* const px = accum + ssx_sum_slot(i, j, g.tiles_x);
+		if (rgb_mode) { // renderer.cpp:304: avg /= double(spp)
+			const double n = (double)spp;
+			o.x = (float)(px[0] / n);
+			o.y = (float)(px[64] / n);
+			o.z = (float)(px[128] / n);
+			o.w = (float)(px[192] / n);
+		} else {
+			const double sc = 1000.0 / (double)spp;
+			o.x = (float)(px[0] * sc);
+			o.y = (float)(px[64] * sc);
+			o.z = (float)(px[128] * sc);
+			o.w = (float)(px[192] * sc);
+		}
 	}
 	out[p] = o;
 }

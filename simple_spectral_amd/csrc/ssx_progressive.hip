@@ -2,24 +2,12 @@
 // "Progressive rendering").  Part of ssx_api.hip's translation unit (included behind its context and launch helpers).  Nothing here touches
 // the path, generate or finalize kernels: the kernels below are small per-pixel ones that run between the launches of a render, or on request.
 
-// Does the device own pixel (i, j)?  The rule of ssx_finalize_kernel: the pixel's tile, at its place in the (rotated) list the devices share out.
-__host__ __device__ inline bool ssx_owns_pixel(uint32_t i, uint32_t j, uint32_t tiles_x, uint32_t tile_first, uint32_t tile_stride, uint32_t tile_skew) {
-	const uint32_t tile = (j >> 3) * tiles_x + ((i >> 3) + ((j >> 3) * tile_skew) % tiles_x) % tiles_x;
-	return tile % tile_stride == tile_first;
-}
-// the pixel's X sum in the accumulator's [tile][component][pixel of the tile] layout (components 64 doubles apart)
-__device__ __forceinline__ size_t ssx_sum_slot(uint32_t i, uint32_t j, uint32_t tiles_x) {
-	return (size_t)((j >> 3) * tiles_x + (i >> 3)) * 256u + ((j & 7u) * 8u + (i & 7u));
-}
-
-struct SsxPixelGrid { uint32_t width, height, tiles_x, tile_first, tile_stride, tile_skew; };
-
 // accumulator -> row-major [height][width][4] (+0 for foreign pixels); s2_out (optional) <- S2 of the noise state (or zeros)
 extern "C" __global__ void __launch_bounds__(256) ssx_sums_export_kernel(const double* accum, const double* noise, double* sums, double* s2_out, SsxPixelGrid g) {
 	const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x, n = g.width * g.height;
 	if (p >= n) return;
 	const uint32_t i = p % g.width, j = p / g.width;
-	const bool own = ssx_owns_pixel(i, j, g.tiles_x, g.tile_first, g.tile_stride, g.tile_skew);
+	const bool own = ssx_owns_pixel(g, i, j);
 	const double* const px = accum + ssx_sum_slot(i, j, g.tiles_x);
 	double4 o = make_double4(0.0, 0.0, 0.0, 0.0);
 	if (own) o = make_double4(px[0], px[64], px[128], px[192]);
@@ -33,7 +21,7 @@ extern "C" __global__ void __launch_bounds__(256) ssx_sums_import_kernel(double*
 	const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x, n = g.width * g.height;
 	if (p >= n) return;
 	const uint32_t i = p % g.width, j = p / g.width;
-	if (!ssx_owns_pixel(i, j, g.tiles_x, g.tile_first, g.tile_stride, g.tile_skew)) {
+	if (!ssx_owns_pixel(g, i, j)) {
 		if (noise) { noise[p] = 0.0; noise[(size_t)n + p] = 0.0; }
 		return;
 	}
@@ -51,7 +39,7 @@ extern "C" __global__ void __launch_bounds__(256) ssx_noise_adopt_kernel(const d
 	const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x, n = g.width * g.height;
 	if (p >= n) return;
 	const uint32_t i = p % g.width, j = p / g.width;
-	const bool own = ssx_owns_pixel(i, j, g.tiles_x, g.tile_first, g.tile_stride, g.tile_skew);
+	const bool own = ssx_owns_pixel(g, i, j);
 	const double a = own ? accum[ssx_sum_slot(i, j, g.tiles_x) + 64u] : 0.0;
 	noise[p] = a;
 	noise[(size_t)n + p] = done_spp ? a * a / (double)done_spp : 0.0;
@@ -62,7 +50,7 @@ extern "C" __global__ void __launch_bounds__(256) ssx_noise_kernel(const double*
 	const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x, n = g.width * g.height;
 	if (p >= n) return;
 	const uint32_t i = p % g.width, j = p / g.width;
-	if (!ssx_owns_pixel(i, j, g.tiles_x, g.tile_first, g.tile_stride, g.tile_skew)) return;
+	if (!ssx_owns_pixel(g, i, j)) return;
 	const double a = accum[ssx_sum_slot(i, j, g.tiles_x) + 64u];
 	const double d = a - noise[p];
 	noise[(size_t)n + p] += d * d / n_k;
@@ -75,7 +63,7 @@ extern "C" __global__ void __launch_bounds__(256) ssx_noise_variance_kernel(cons
 	if (p >= n) return;
 	const uint32_t i = p % g.width, j = p / g.width;
 	double v = 0.0, a = 0.0;
-	if (ssx_owns_pixel(i, j, g.tiles_x, g.tile_first, g.tile_stride, g.tile_skew)) {
+	if (ssx_owns_pixel(g, i, j)) {
 		a = accum[ssx_sum_slot(i, j, g.tiles_x) + 64u];
 		v = ((noise[(size_t)n + p] - a * a / N) / (B - 1.0)) / N;
 		if (!(v > 0.0)) v = 0.0;
@@ -85,26 +73,21 @@ extern "C" __global__ void __launch_bounds__(256) ssx_noise_variance_kernel(cons
 
 namespace {
 
-SsxPixelGrid pixel_grid(const ssx_render_params* p) {
-	const uint32_t tx = tiles_across(p->width);
-	return SsxPixelGrid{ p->width, p->height, tx, p->tile_first, p->tile_stride, p->tile_skew % tx };
-}
-dim3 pixel_blocks(const ssx_render_params* p) { return dim3((p->width * p->height + 255u) / 256u); }
 size_t noise_bytes(const ssx_render_params* p) { return (size_t)p->width * p->height * 2 * sizeof(double); }
 
-// Start of a render's worker: ssx_render_start resets the estimate; a continued render carries it on, or adopts the sums it finds as one batch.
-int noise_begin(ssx_ctx* ctx, const ssx_render_params* p, bool continuing) {
-	if (!ctx->noise_on) { ctx->noise_valid = false; return SSX_OK; }
-	if (continuing && ctx->noise_valid) return SSX_OK;
+// Start of a sample walk: ssx_render_start resets the estimate; a continued render carries it on, or adopts the k_begin samples it finds as one batch.
+int noise_begin(ssx_ctx* ctx, const ssx_render_params* p, uint32_t k_begin, bool continuing) {
+	if (!ctx->noise_on) { ctx->sums.noise_valid = false; return SSX_OK; }
+	if (continuing && ctx->sums.noise_valid) return SSX_OK;
 	SSX_HIP(ctx, ctx->d_noise.reserve(noise_bytes(p)));
-	const uint32_t done = continuing ? ctx->k_begin : 0u;
+	const uint32_t done = continuing ? k_begin : 0u;
 	if (!done) SSX_HIP(ctx, hipMemsetAsync(ctx->d_noise.ptr, 0, noise_bytes(p), ctx->stream));
 	else {
 		hipLaunchKernelGGL(ssx_noise_adopt_kernel, pixel_blocks(p), dim3(256), 0, ctx->stream, ctx->d_accum.as<const double>(), ctx->d_noise.as<double>(), pixel_grid(p), done);
 		SSX_HIP(ctx, hipGetLastError());
 	}
-	ctx->noise_batches = done ? 1u : 0u;
-	ctx->noise_valid = true;
+	ctx->sums.noise_batches = done ? 1u : 0u;
+	ctx->sums.noise_valid = true;
 	return SSX_OK;
 }
 
@@ -112,14 +95,17 @@ int noise_begin(ssx_ctx* ctx, const ssx_render_params* p, bool continuing) {
 int noise_batch(ssx_ctx* ctx, const ssx_render_params* p, uint32_t n_k, hipStream_t stream) {
 	hipLaunchKernelGGL(ssx_noise_kernel, pixel_blocks(p), dim3(256), 0, stream, ctx->d_accum.as<const double>(), ctx->d_noise.as<double>(), pixel_grid(p), (double)n_k);
 	SSX_HIP(ctx, hipGetLastError());
-	++ctx->noise_batches;
+	++ctx->sums.noise_batches;
 	return SSX_OK;
 }
+
+// the estimate switched off: its state goes, the sums stay what they are
+void noise_drop(ssx_ctx* ctx) { if (hipSetDevice(ctx->device) == hipSuccess) ctx->d_noise.release(); ctx->sums.noise_valid = false; ctx->sums.noise_batches = 0; }
 
 // entry points that read or replace the sums: a context with continuable sums and no render running, its device current
 int sums_ready(ssx_ctx* ctx, const char* what) {
 	if (ctx->rendering.load()) return fail(ctx, SSX_ERR_STATE, "render in progress");
-	if (!ctx->continuable) return fail(ctx, SSX_ERR_STATE, fmt("%s: the context holds no sums that can be continued (render with ssx_render_start, or ssx_sums_import, first)", what));
+	if (!ctx->sums.continuable) return fail(ctx, SSX_ERR_STATE, fmt("%s: the context holds no sums that can be continued (render with ssx_render_start, or ssx_sums_import, first)", what));
 	SSX_HIP(ctx, hipSetDevice(ctx->device)); // (the worker of the last render has left the device idle: `rendering` is its last word)
 	return wait_device_pending(ctx);
 }
@@ -139,18 +125,7 @@ int ssx_render_continue(ssx_ctx* ctx, uint32_t spp_more) {
 	if ((uint64_t)done + spp_more > 0xFFFFFFFFull) return fail(ctx, SSX_ERR_ARG, "more than 2^32 - 1 samples per pixel in all");
 	ssx_render_params p = ctx->cur;
 	p.spp = done + spp_more;
-	if (ctx->worker.joinable()) ctx->worker.join();
-	if ((rc = ready_to_launch(ctx, &p, true))) return rc;
-	ctx->cur = p;
-	ctx->total_spp = spp_more;
-	ctx->k_begin = done;
-	ctx->continuing = true;
-	ctx->continuable = false; // until the worker leaves valid sums again (a failed render does not)
-	ctx->stop_flag.store(0);
-	ctx->worker_rc = 0;
-	ctx->rendering.store(1);
-	ctx->worker = std::thread(worker_main, ctx);
-	return SSX_OK;
+	return start_worker(ctx, p, done, true, spp_more);
 }
 
 int ssx_sums_export(ssx_ctx* ctx, ssx_sums_info_t* info, double* sums, double* noise_s2) {
@@ -158,14 +133,14 @@ int ssx_sums_export(ssx_ctx* ctx, ssx_sums_info_t* info, double* sums, double* n
 	int rc = sums_ready(ctx, "ssx_sums_export");
 	if (rc) return rc;
 	const ssx_render_params& p = ctx->cur;
-	const bool have_noise = ctx->noise_on && ctx->noise_valid;
+	const bool have_noise = ctx->noise_on && ctx->sums.noise_valid;
 	memset(info, 0, sizeof *info);
 	info->struct_size = sizeof *info;
 	info->width = p.width; info->height = p.height; info->done_spp = ctx->done_spp.load(); info->seed = p.seed;
 	info->indirect_only = p.indirect_only ? 1u : 0u; info->no_explicit_light_sampling = p.no_explicit_light_sampling ? 1u : 0u;
 	info->no_flat_field_correction = p.no_flat_field_correction ? 1u : 0u; info->libm = p.libm; info->rgb_mode = ctx->rgb_mode ? 1u : 0u;
 	info->tile_first = p.tile_first; info->tile_stride = p.tile_stride; info->tile_skew = p.tile_skew;
-	info->noise_batches = have_noise ? ctx->noise_batches : 0u;
+	info->noise_batches = have_noise ? ctx->sums.noise_batches : 0u;
 	info->scene_digest = ctx->scene_digest;
 	const size_t pixels = (size_t)p.width * p.height;
 	DeviceBuffer& stage = ctx->d_stage;
@@ -203,10 +178,10 @@ int ssx_sums_import(ssx_ctx* ctx, const ssx_render_params* params, const ssx_sum
 	  // checkpoint: all of them; one rank's export: only a partition inside its own).
 		const uint32_t tiles_x = tiles_across(pp.width), n_tiles = tiles_x * tiles_across(pp.height);
 		if (info->tile_stride == 0 || info->tile_first >= info->tile_stride) return fail(ctx, SSX_ERR_ARG, "ssx_sums_import: tile_first / tile_stride of these sums are invalid");
-		const uint32_t skew_mine = pp.tile_skew % tiles_x, skew_theirs = info->tile_skew % tiles_x;
+		const SsxPixelGrid mine = pixel_grid(&pp), theirs{ pp.width, pp.height, tiles_x, info->tile_first, info->tile_stride, info->tile_skew % tiles_x };
 		for (uint32_t t = 0; info->tile_stride > 1u && t < n_tiles; ++t) {
 			const uint32_t i = (t % tiles_x) * 8u, j = (t / tiles_x) * 8u;
-			if (ssx_owns_pixel(i, j, tiles_x, pp.tile_first, pp.tile_stride, skew_mine) && !ssx_owns_pixel(i, j, tiles_x, info->tile_first, info->tile_stride, skew_theirs))
+			if (ssx_owns_pixel(mine, i, j) && !ssx_owns_pixel(theirs, i, j))
 				return fail(ctx, SSX_ERR_ARG, fmt("ssx_sums_import: tile ownership differs: these sums hold the tiles of tile_first %u / tile_stride %u / tile_skew %u only, this render "
 				                                  "owns tile %u outside them (merge the ranks' exports by ownership first)", info->tile_first, info->tile_stride, info->tile_skew, t));
 		}
@@ -217,7 +192,7 @@ int ssx_sums_import(ssx_ctx* ctx, const ssx_render_params* params, const ssx_sum
 	if ((rc = wait_device_pending(ctx))) return rc;
 	pp.spp = info->done_spp ? info->done_spp : 1u;
 	if ((rc = ready_to_launch(ctx, &pp, true))) return rc;
-	ctx->continuable = false; ctx->noise_valid = false;
+	sums_invalidate(ctx);
 	const size_t pixels = (size_t)pp.width * pp.height;
 	const bool s2_given = noise_s2 && info->noise_batches;
 	DeviceBuffer& stage = ctx->d_stage;
@@ -233,11 +208,9 @@ int ssx_sums_import(ssx_ctx* ctx, const ssx_render_params* params, const ssx_sum
 	if ((rc = launch_finalize(ctx, &pp, pp.spp, ctx->d_out.as<float>(), ctx->stream))) return rc;
 	SSX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	ctx->cur = pp;
-	ctx->total_spp = 0; ctx->k_begin = 0; ctx->continuing = false;
-	ctx->done_spp.store(info->done_spp);
+	ctx->total_spp = 0; ctx->k_begin = 0;
 	ctx->done_tiles.store(0);
-	if (ctx->noise_on) { ctx->noise_valid = true; ctx->noise_batches = s2_given ? info->noise_batches : (info->done_spp ? 1u : 0u); }
-	ctx->continuable = true;
+	sums_publish(ctx, info->done_spp, !ctx->noise_on ? -1 : s2_given ? (int64_t)info->noise_batches : (info->done_spp ? 1 : 0)); // (the kernel made one batch of sums without S2)
 	return SSX_OK;
 }
 
@@ -245,10 +218,7 @@ int ssx_set_noise_estimate(ssx_ctx* ctx, int enable) {
 	if (!ctx) return SSX_ERR_ARG;
 	if (ctx->rendering.load()) return fail(ctx, SSX_ERR_STATE, "render in progress");
 	ctx->noise_on = enable != 0;
-	if (!ctx->noise_on) {
-		if (hipSetDevice(ctx->device) == hipSuccess) ctx->d_noise.release();
-		ctx->noise_valid = false; ctx->noise_batches = 0;
-	}
+	if (!ctx->noise_on) noise_drop(ctx);
 	return SSX_OK;
 }
 
@@ -257,10 +227,10 @@ int ssx_noise_info(ssx_ctx* ctx, double* v_out, double summary[4]) {
 	if (!ctx->noise_on) return fail(ctx, SSX_ERR_STATE, "ssx_noise_info: the noise estimate is off (ssx_set_noise_estimate)");
 	int rc = sums_ready(ctx, "ssx_noise_info");
 	if (rc) return rc;
-	if (!ctx->noise_valid || ctx->noise_batches < 2u) return fail(ctx, SSX_ERR_STATE, fmt("ssx_noise_info: %u batch(es) so far; the between-batch variance needs two", ctx->noise_valid ? ctx->noise_batches : 0u));
+	if (!ctx->sums.noise_valid || ctx->sums.noise_batches < 2u) return fail(ctx, SSX_ERR_STATE, fmt("ssx_noise_info: %u batch(es) so far; the between-batch variance needs two", ctx->sums.noise_valid ? ctx->sums.noise_batches : 0u));
 	const ssx_render_params& p = ctx->cur;
 	const size_t pixels = (size_t)p.width * p.height;
-	const double N = (double)ctx->done_spp.load(), B = (double)ctx->noise_batches;
+	const double N = (double)ctx->done_spp.load(), B = (double)ctx->sums.noise_batches;
 	DeviceBuffer& stage = ctx->d_stage;
 	SSX_HIP(ctx, stage.reserve(pixels * 2 * sizeof(double)));
 	hipLaunchKernelGGL(ssx_noise_variance_kernel, pixel_blocks(&p), dim3(256), 0, ctx->stream, ctx->d_accum.as<const double>(), ctx->d_noise.as<const double>(),
@@ -272,7 +242,7 @@ int ssx_noise_info(ssx_ctx* ctx, double* v_out, double summary[4]) {
 	const SsxPixelGrid g = pixel_grid(&p);
 	double sum_v = 0.0, sum_mean = 0.0, owned = 0.0;
 	for (uint32_t j = 0; j < p.height; ++j) for (uint32_t i = 0; i < p.width; ++i) { // one after the other, row-major
-		if (!ssx_owns_pixel(i, j, g.tiles_x, g.tile_first, g.tile_stride, g.tile_skew)) continue;
+		if (!ssx_owns_pixel(g, i, j)) continue;
 		const size_t q = (size_t)j * p.width + i;
 		sum_v += va[q]; sum_mean += va[pixels + q] / N; owned += 1.0;
 	}

@@ -99,9 +99,8 @@ Checkpoint checkpoint_load(const std::string& path) {
 }
 
 bool sums_owner(const ssx_sums_info_t& info, size_t i, size_t j) {
-	const size_t tiles_x = (info.width + 7u) / 8u, stride = info.tile_stride ? info.tile_stride : 1u;
-	const size_t tile = (j / 8) * tiles_x + (i / 8 + ((j / 8) * (info.tile_skew % tiles_x)) % tiles_x) % tiles_x;
-	return tile % stride == info.tile_first;
+	const size_t stride = info.tile_stride ? info.tile_stride : 1u;
+	return shared_tile(info.width, info.tile_skew, i, j) % stride == info.tile_first;
 }
 
 void sums_merge(double* dst, double* dst_s2, const double* src, const double* src_s2, const ssx_sums_info_t& src_info) {

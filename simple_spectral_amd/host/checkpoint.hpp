@@ -26,7 +26,14 @@ struct Checkpoint {
 void checkpoint_save(const std::string& path, const Checkpoint& c); // throws HostError
 Checkpoint checkpoint_load(const std::string& path);               // throws HostError{SSX_ERR_DATA}
 
-// Does the exporter described by `info` own pixel (i, j)?  (The rule of the kernels: include/ssx.h tile_first / tile_stride / tile_skew.)
+// The ownership rule of this library (the kernels': include/ssx.h tile_first / tile_stride / tile_skew): the place of pixel (i, j)'s 8x8 tile in the
+// list the devices share out -- row-major, tile row ty rotated by ty * tile_skew columns.  Tile t belongs to the device with tile_first == t % tile_stride,
+// as the (t / tile_stride)-th of its tiles.
+inline size_t shared_tile(size_t width, size_t tile_skew, size_t i, size_t j) {
+	const size_t tiles_x = (width + 7u) / 8u;
+	return (j / 8) * tiles_x + (i / 8 + ((j / 8) * (tile_skew % tiles_x)) % tiles_x) % tiles_x;
+}
+// Does the exporter described by `info` own pixel (i, j)?
 bool sums_owner(const ssx_sums_info_t& info, size_t i, size_t j);
 // dst's pixels that `src_info` owns <- src's, bit for bit (a merge by ownership mask, not a sum: -0.0 stays -0.0); s2 likewise where both are given
 void sums_merge(double* dst, double* dst_s2, const double* src, const double* src_s2, const ssx_sums_info_t& src_info);

@@ -189,22 +189,27 @@ void Renderer::start_(size_t spp, size_t spp_per_launch) {
 
 void Renderer::render_start() { start_(options.spp, 0); }
 
-// Starts ssx_render_continue on the devices that are short of `target`; should one refuse, the ones already started are stopped and
-// joined before the error leaves (no worker is left behind unjoined).
+// Starts ssx_render_continue on every (context, samples more) pair; should one refuse, the ones already started are stopped and joined
+// before the error leaves (no worker is left behind unjoined).
+void Renderer::continue_each_(const std::vector<std::pair<ssx_ctx*, uint32_t>>& more) {
+	for (size_t n = 0; n < more.size(); ++n) {
+		const int rc = api_->render_continue(more[n].first, more[n].second);
+		if (!rc) continue;
+		const std::string why = std::string("ssx_render_continue: ") + api_->last_error(more[n].first);
+		for (size_t b = 0; b < n; ++b) { api_->render_stop(more[b].first); (void)api_->render_wait(more[b].first, nullptr); }
+		throw HostError{ rc, why };
+	}
+}
+
+// the devices that are short of `target` render up to it (blocking)
 void Renderer::continue_to_(size_t target) {
-	std::vector<ssx_ctx*> begun;
+	std::vector<std::pair<ssx_ctx*, uint32_t>> more;
 	for (ssx_ctx* c : ctxs_) {
 		const size_t mine = api_->done_spp(c);
-		if (mine >= target) continue;
-		const int rc = api_->render_continue(c, static_cast<uint32_t>(target - mine));
-		if (rc) {
-			const std::string why = std::string("ssx_render_continue: ") + api_->last_error(c);
-			for (ssx_ctx* b : begun) { api_->render_stop(b); (void)api_->render_wait(b, nullptr); }
-			throw HostError{ rc, why };
-		}
-		begun.push_back(c);
+		if (mine < target) more.emplace_back(c, static_cast<uint32_t>(target - mine));
 	}
-	for (ssx_ctx* c : begun) check_(api_->render_wait(c, nullptr), "ssx_render_wait", c);
+	continue_each_(more);
+	for (const auto& m : more) check_(api_->render_wait(m.first, nullptr), "ssx_render_wait", m.first);
 }
 
 void Renderer::level_devices() {
@@ -217,16 +222,9 @@ void Renderer::level_devices() {
 void Renderer::render_continue(size_t spp) {
 	level_devices(); // devices that stopped at different counts: the laggards catch up first, then all render `spp` more
 	const size_t done = done_spp();
-	std::vector<ssx_ctx*> begun;
-	for (ssx_ctx* c : ctxs_) {
-		const int rc = api_->render_continue(c, static_cast<uint32_t>(spp));
-		if (rc) {
-			const std::string why = std::string("ssx_render_continue: ") + api_->last_error(c);
-			for (ssx_ctx* b : begun) { api_->render_stop(b); (void)api_->render_wait(b, nullptr); }
-			throw HostError{ rc, why };
-		}
-		begun.push_back(c);
-	}
+	std::vector<std::pair<ssx_ctx*, uint32_t>> more;
+	for (ssx_ctx* c : ctxs_) more.emplace_back(c, static_cast<uint32_t>(spp));
+	continue_each_(more);
 	started_ = need_join_ = true;
 	expected_spp_ = done + spp;
 }
@@ -398,9 +396,9 @@ void Renderer::render_wait() {
 	else { // a stopped tile-major render: like the reference's, the framebuffer keeps its checkerboard where no tile was finished (src/framebuffer.cpp:15-32)
 		std::vector<float> all(xyza.size());
 		color->xyza_to_srgba(xyza.data(), all.data(), options.res[0] * options.res[1]);
+		const size_t skew = params_for_(0, 1, 0).tile_skew; // (what the devices rendered with)
 		for (size_t j = 0; j < options.res[1]; ++j) for (size_t i = 0; i < options.res[0]; ++i) {
-			const size_t skew = ctxs_.size() > 1 ? 1 : 0;
-			const size_t tile = (j / 8) * tiles_x + (i / 8 + (j / 8) * skew) % tiles_x, d = tile % ctxs_.size(); // its place in the shared-out list (tile_skew)
+			const size_t tile = shared_tile(options.res[0], skew, i, j), d = tile % ctxs_.size();
 			if (tile / ctxs_.size() < done_tiles[d]) std::memcpy(framebuffer(i, j), &all[4 * (j * options.res[0] + i)], 4 * sizeof(float));
 		}
 	}

@@ -106,6 +106,7 @@ private:
 	ssx_render_params params_for_(size_t d, size_t spp, size_t spp_per_launch) const;
 	void start_(size_t spp, size_t spp_per_launch);
 	void wait_workers_();
+	void continue_each_(const std::vector<std::pair<ssx_ctx*, uint32_t>>& more);
 	void continue_to_(size_t target);
 	void check_(int rc, const char* what, ssx_ctx* c) const;
 };

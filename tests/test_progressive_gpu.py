@@ -221,6 +221,23 @@ def test_continue_is_refused_without_continuable_sums():
     r.render_stop()
     wait(r)
     cont(r, 1)                                                           # (the stopped sample-walking render is continuable)
+    r.close()
+    # Every entry point that overwrites or reinterprets the sums leaves nothing to continue or to export, and a render brings both back.
+    # 16 x 16: two tiles per row.  (An ssx_sums_import refused AFTER its argument checks would belong here: only a failing HIP call gets that far.)
+    s = Renderer(Options(scene_name="cornell-srgb", res=(16, 16), seed=1, texture=TEX))
+
+    def render_device():
+        s.render_device(s._lib.ssx_device_framebuffer(s._ctx), spp=2)
+        s.render_device_wait()
+
+    for overwrite in (lambda: s.upload_scene_desc(s.scene.desc), render_device, lambda: s.debug_samples(spp=2)):
+        start(s, 2)
+        assert s.export_sums()[0].done_spp == 2                          # continuable sums ...
+        overwrite()
+        refused(lambda: s.render_continue(2), _capi.SSX_ERR_STATE)       # ... are gone
+        refused(s.export_sums, _capi.SSX_ERR_STATE)
+    start(s, 2)
+    assert np.array_equal(bits(cont(s, 2)), bits(want("cornell-srgb", "", 16, 16, 4, 1))) and s.export_sums()[0].done_spp == 4
 
 
 def test_import_is_refused_for_other_renders():
