@@ -32,7 +32,8 @@ extern "C" {
  *      SSX_MAX_TEXTURES and the struct sizes grew; ssx_set_jit takes a mode (default: background compilation); ssx_jit_status,
  *      ssx_jit_counters, ssx_sums_info, ssx_rccl_groups_made, ssx_done_tiles and ssx_render_params.tile_major and tile_skew (the
  *      struct grew by 8 bytes) are new.  Added since without a change of existing entry points or structures (same version): ssx_units_info,
- *      ssx_rccl_probe (round 6); ssx_render_params.libm, appended (a caller with the struct_size before it gets SSX_LIBM_BUILD). */
+ *      ssx_rccl_probe (round 6); ssx_render_params.libm, appended (a caller with the struct_size before it gets SSX_LIBM_BUILD); the progressive
+ *      rendering and spectral output entry points below. */
 #define SSX_ABI_VERSION 2
 
 enum {
@@ -289,7 +290,7 @@ int ssx_plan_info(ssx_ctx* ctx, float* frames_per_sample, int* fold_in_path_kern
  * performance choice only: same bits.  The environment variable SSX_PRE_HITS=0/1 at upload overrides it. */
 int ssx_calibration_info(ssx_ctx* ctx, float* frames_per_sample, float* rays_left_per_sample, int* camera_rays_pretraced);
 /* Device scratch the context holds right now: the per-sample arrays of the largest launch so far (48 bytes per sample in
- * flight: camera ray / result, stream / tail word, camera hit) and the persistent waves' level logs (a fixed size per
+ * flight: camera ray / result, stream / tail word, camera hit; 64 while spectral output is on: + hero flux) and the persistent waves' level logs (a fixed size per
  * device and unit size: wave slots x 2 units x cohorts x 128 records x 582 bytes). */
 int ssx_scratch_info(ssx_ctx* ctx, uint64_t* sample_bytes, uint64_t* log_bytes);
 /* How the ordered binary64 pixel sums (src/renderer.cpp:292-295: a pixel's samples are added in ascending k) went, counted since
@@ -340,7 +341,8 @@ void ssx_jit_counters(uint64_t* compiled, uint64_t* disk_hits);
 /* The name of the path kernel the context launches for the uploaded scene, as a profiler lists it
  * ("ssx_render_kernel", "..._cornell", "..._plane", each also with "_nq": the variants with narrow shadow-ray
  * queue entries, taken where they let one more workgroup live on a CU; after a render with libm = SSX_LIBM_GLIBC_2_35
- * the same names with "_glibc" appended -- the run-time compiled "ssx_render_kernel_jit" keeps its name).  NULL: no scene. */
+ * the same names with "_glibc" appended, after one with spectral output on with "_flux" -- the run-time compiled "ssx_render_kernel_jit" keeps
+ * its name).  NULL: no scene. */
 const char* ssx_kernel_name(ssx_ctx* ctx);
 
 /* ---- Progressive rendering: continue, checkpoint / resume, noise estimate (appended; same ABI version) --------------------------------
@@ -406,6 +408,44 @@ int ssx_set_noise_estimate(ssx_ctx* ctx, int enable);
  * cancels).  SSX_ERR_STATE: the estimate is off, or B < 2. */
 int ssx_noise_info(ssx_ctx* ctx, double* v_out, double summary[4]);
 
+/* ---- Spectral radiance output: per-pixel wavelength bins (appended; same ABI version) ------------------------------------------------
+ * The integrator carries four hero wavelengths per sample, lambda_0 + i * lambda_step (i = 0..3; lambda_0 drawn in [lambda_min, lambda_min +
+ * lambda_step]), and projects their fluxes onto the observer at once (flux_to_xyz).  With spectral output on, the fluxes are also binned by wavelength.
+ * The definition is this library's (the reference has no such output):
+ *   B bins, B in {4, 8, ..., 64} (a multiple of 4), M = B / 4.  Bin b covers [lambda_min + b*w, lambda_min + (b+1)*w) with w = lambda_step / M, so
+ *   component i of a sample always falls into bin i*M + m, with one m per sample.  For sample k of pixel p, with f[0..3] the hero flux handed to
+ *   flux_to_xyz (i.e. after the no_flat_field_correction multiply):
+ *       t = (lambda_0 - lambda_min) / lambda_step          binary32, IEEE division, no contraction
+ *       m = min(M-1, (uint32)(t * (float)M))               binary32 multiply, truncation
+ *       S[p][i*M + m] += (double)f[i]   (i = 0..3);   N[p][m] += 1
+ *   in ascending k, like the pixel sums (binary64 addition is not associative): the result does not depend on tile partition, launch size or device
+ *   count.  mean[p][b] = N[p][b % M] ? (float)(S[p][b] / (double)N[p][b % M]) : 0.0f.  A sample that hit nothing contributes f = 0 and counts; a
+ *   non-finite flux is added as it is; pixels a context does not own read as 0.
+ * The state is valid from zero samples or not at all: an ssx_render_start that walks through the samples (tile_major = 0) resets it and accumulates,
+ * ssx_render_continue carries it on; whatever invalidates the pixel sums (ssx_upload_scene, ssx_debug_samples, a failed render) and a changed bin
+ * count clear it; ssx_sums_import leaves it invalid (the checkpoint file carries no bins: a continue after an import renders normally, and
+ * ssx_spectral_read returns SSX_ERR_STATE).  The XYZ image of a render does not depend on whether spectral output is on.
+ * While it is on, refused with SSX_ERR_ARG: renders of a scene in SSX_MODE_RGB, libm = SSX_LIBM_GLIBC_2_35, tile_major renders and
+ * ssx_render_device.  These are out of scope so far, not limits of the design (the flux-storing kernels exist for the default libm only, and only
+ * the sample walk runs the binning kernel between its launches). */
+
+/* bins: 0 = off (default: nothing allocated, nothing launched, the default kernels), else B.  While on, the path kernels are the "_flux" twins of the
+ * default ones, which also store every sample's hero flux (16 more bytes per sample in flight: ssx_scratch_info), and the sample walk runs one small
+ * kernel per launch that bins them.  Not while a render runs (SSX_ERR_STATE); other values of bins: SSX_ERR_ARG. */
+int ssx_set_spectral_bins(ssx_ctx* ctx, uint32_t bins);
+typedef struct ssx_spectral_info_t {
+	uint32_t struct_size;     /* sizeof(ssx_spectral_info_t) */
+	uint32_t width, height;
+	uint32_t bins;            /* B */
+	uint32_t done_spp;        /* samples per pixel the bins hold (== ssx_done_spp) */
+	uint32_t reserved;
+	float lambda_min;         /* lower edge of bin 0 */
+	float bin_width;          /* w = lambda_step / M (binary32); bin b's centre is lambda_min + (b + 0.5) * w */
+} ssx_spectral_info_t;
+/* Row-major (row 0 = bottom) mean [height][width][B] (float), sums [height][width][B] (the binary64 accumulators S) and counts [height][width][M];
+ * any of the three may be NULL.  info is filled.  SSX_ERR_STATE: spectral output is off, a render runs, or the context holds no valid bins. */
+int ssx_spectral_read(ssx_ctx* ctx, ssx_spectral_info_t* info, float* mean, double* sums, uint32_t* counts);
+
 /* ---- Diagnostics for the parity tests (not part of the reference's interface) ---------------------
  * ssx_debug_eval runs one building block of the path kernel -- the same device function the kernel
  * inlines -- on n items, one per lane: `in` holds in_words 32-bit words per item, `out` receives
@@ -465,6 +505,9 @@ int ssx_debug_eval(ssx_ctx* ctx, uint32_t op, const void* in, uint32_t in_words,
  * xyza = what Renderer::_render_sample returns (float4), rng_state = the sample's PCG32 state after its
  * last draw (i.e. the number of draws consumed), levels = continued recursion levels.  Any may be NULL. */
 int ssx_debug_samples(ssx_ctx* ctx, const ssx_render_params* params, float* xyza, uint64_t* rng_state, uint32_t* levels);
+/* The same launch with spectral output on (ssx_set_spectral_bins; off: SSX_ERR_STATE): flux [j][i][k][4] = every sample's hero flux as handed to
+ * flux_to_xyz, lambda_0 [j][i][k] = its first hero wavelength.  Either may be NULL. */
+int ssx_debug_sample_flux(ssx_ctx* ctx, const ssx_render_params* params, float* flux, float* lambda_0);
 
 #ifdef __cplusplus
 }

@@ -69,6 +69,10 @@ int ssh_checkpoint_load(const char* path, ssx_sums_info_t* info, char* scene_nam
  * -- by ownership mask, not by adding (-0.0 stays -0.0).  dst_s2 / src_s2: the same for S2, or NULL. */
 int ssh_sums_merge(double* dst, double* dst_s2, const double* src, const double* src_s2, const ssx_sums_info_t* src_info);
 
+/* A NumPy .npy file (format version 1.0, '<f4', C order) of `data` with the given shape: what np.load reads, and the bytes np.save writes for the
+ * same array.  The CLI's --spectral-output writes the spectral image with it: shape (height, width, bins), row 0 = bottom. */
+int ssh_save_npy_f32(const char* path, const float* data, const uint32_t* shape, uint32_t ndim);
+
 const char* ssh_last_error(void);
 
 #ifdef __cplusplus

@@ -71,6 +71,12 @@ class SsxSumsInfo(C.Structure):
                 ("noise_batches", C.c_uint32), ("reserved", C.c_uint32), ("scene_digest", C.c_uint64)]
 
 
+class SsxSpectralInfo(C.Structure):
+    """ssx_spectral_info_t: what ssx_spectral_read's arrays belong to."""
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("bins", C.c_uint32), ("done_spp", C.c_uint32),
+                ("reserved", C.c_uint32), ("lambda_min", C.c_float), ("bin_width", C.c_float)]
+
+
 SSX_LIBM_BUILD, SSX_LIBM_GLIBC_2_35 = 0, 1
 LIBM_MODES = {"build": SSX_LIBM_BUILD, "glibc-2.35": SSX_LIBM_GLIBC_2_35}
 
@@ -88,7 +94,8 @@ HIP_SYMBOLS = ["ssx_create", "ssx_destroy", "ssx_upload_scene", "ssx_render_star
                "ssx_abi_version", "ssx_kernel_info", "ssx_plan_info", "ssx_set_timing", "ssx_get_timing",
                "ssx_device_framebuffer", "ssx_device_index", "ssx_read_framebuffer", "ssx_accumulate_peer",
                "ssx_debug_eval", "ssx_debug_samples", "ssx_debug_sweep", "ssx_kernel_variant", "ssx_kernel_name", "ssx_scratch_info", "ssx_calibration_info", "ssx_set_jit", "ssx_debug_pass1_source", "ssx_done_spp", "ssx_reduce_rccl", "ssx_sums_info", "ssx_rccl_groups_made", "ssx_jit_status", "ssx_jit_counters", "ssx_done_tiles", "ssx_render_device_wait", "ssx_units_info", "ssx_rccl_probe",
-               "ssx_render_continue", "ssx_scene_digest", "ssx_sums_export", "ssx_sums_import", "ssx_set_noise_estimate", "ssx_noise_info"]
+               "ssx_render_continue", "ssx_scene_digest", "ssx_sums_export", "ssx_sums_import", "ssx_set_noise_estimate", "ssx_noise_info",
+               "ssx_set_spectral_bins", "ssx_spectral_read", "ssx_debug_sample_flux"]
 (SSX_SWEEP_RCP, SSX_SWEEP_SQRT, SSX_SWEEP_INVERSESQRT, SSX_SWEEP_SIN, SSX_SWEEP_COS, SSX_SWEEP_ACOS, SSX_SWEEP_DIV_PI,
  SSX_SWEEP_RCP64, SSX_SWEEP_DIV_PAIRS, SSX_SWEEP_ACOS_SIN, SSX_SWEEP_SIN_PROOF, SSX_SWEEP_COS_PROOF, SSX_SWEEP_ACOS_PROOF) = range(1, 14)
 # ssx_debug_eval ops (include/ssx.h)
@@ -98,7 +105,7 @@ HIP_SYMBOLS = ["ssx_create", "ssx_destroy", "ssx_upload_scene", "ssx_render_star
 (SSX_DBG_GLIBC_MATH, SSX_DBG_SPHTRI_GLIBC, SSX_DBG_ARVO_GLIBC, SSX_DBG_SAMPLE_LIGHT_GLIBC, SSX_DBG_COSHEMI_GLIBC) = range(11, 16)
 (SSX_SWEEP_GLIBC_SIN, SSX_SWEEP_GLIBC_COS, SSX_SWEEP_GLIBC_ACOS, SSX_SWEEP_GLIBC_COS_LDS) = range(14, 18)
 HOST_SYMBOLS = ["ssh_scene_create", "ssh_scene_create_ex", "ssh_scene_destroy", "ssh_scene_desc", "ssh_xyza_to_srgba", "ssh_save_image",
-                "ssh_load_png_rgb8", "ssh_free", "ssh_color_values", "ssh_last_error", "ssh_checkpoint_save", "ssh_checkpoint_load", "ssh_sums_merge"]
+                "ssh_load_png_rgb8", "ssh_free", "ssh_color_values", "ssh_last_error", "ssh_checkpoint_save", "ssh_checkpoint_load", "ssh_sums_merge", "ssh_save_npy_f32"]
 
 _hip = None
 _host = None
@@ -130,6 +137,7 @@ def host_lib():
         lib.ssh_checkpoint_load.argtypes = [C.c_char_p, C.POINTER(SsxSumsInfo), C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t,
                                             C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.POINTER(C.c_double))]
         lib.ssh_sums_merge.argtypes = [vp, vp, vp, vp, C.POINTER(SsxSumsInfo)]
+        lib.ssh_save_npy_f32.argtypes = [C.c_char_p, vp, C.POINTER(C.c_uint32), C.c_uint32]
         _host = lib
     return _host
 
@@ -286,6 +294,10 @@ def hip_lib():
             lib.ssx_sums_import.argtypes = [vp, C.POINTER(SsxRenderParams), C.POINTER(SsxSumsInfo), vp, vp]
             lib.ssx_set_noise_estimate.argtypes = [vp, C.c_int]
             lib.ssx_noise_info.argtypes = [vp, vp, C.POINTER(C.c_double)]
+        if not override or hasattr(lib, "ssx_set_spectral_bins"):  # spectral output
+            lib.ssx_set_spectral_bins.argtypes = [vp, C.c_uint32]
+            lib.ssx_spectral_read.argtypes = [vp, C.POINTER(SsxSpectralInfo), vp, vp, vp]
+            lib.ssx_debug_sample_flux.argtypes = [vp, C.POINTER(SsxRenderParams), vp, vp]
         lib.ssx_kernel_variant.argtypes = [vp]
         lib.ssx_kernel_name.argtypes = [vp]
         lib.ssx_kernel_name.restype = C.c_char_p

@@ -3,7 +3,7 @@
 // entry point either drives the HIP kernels or returns an error.
 // The context, its launches, the render worker (render_sample_walk / render_tile_walk behind start_worker), the render entry points and the
 // diagnostics are here; scene packing is in ssx_pack.h, RCCL in ssx_rccl.h, the pixel ownership rule in ssx_pixel_grid.h, continue / export /
-// import of the sums and the noise estimate (entry points and their kernels) in ssx_progressive.hip.
+// import of the sums and the noise estimate (entry points and their kernels) in ssx_progressive.hip, the spectral output in ssx_spectral.hip.
 #include "ssx_kernels.hip"
 #include "ssx_debug.hip"
 
@@ -82,8 +82,9 @@ struct ssx_ctx {
 	uint32_t path_blob_words = 0; // what the path kernel stages: without the per-quad vertex table when a specialised kernel runs
 	uint32_t topology = 0;        // 0, the built-in mesh topology the scene matched (csrc/ssx_pass1_gen.h), or 3: its own, compiled at upload
 	int jit_mode = SSX_JIT_BACKGROUND; // ssx_set_jit: how pass 1 gets specialised for scenes that match no built-in topology
-	const ssx_jit::Kernels* jit_kernels[2] = {}; // [libm] the run-time compiled kernels of the uploaded scene (topology 3), a mode's when its first render needs them
-	uint32_t libm = SSX_LIBM_BUILD; // the libm of the current (or last) render: which kernel twins run (path_kernel_ref)
+	const ssx_jit::Kernels* jit_kernels[ssx_jit::kVariants] = {}; // [variant: libm, or ssx_jit::kVariantFlux] the run-time compiled kernels of the uploaded scene (topology 3), a mode's when its first render needs them
+	uint32_t libm = SSX_LIBM_BUILD; // the libm of the current (or last) render
+	uint32_t variant = SSX_LIBM_BUILD; // which kernel twins that render runs (path_kernel_ref): its libm, or ssx_jit::kVariantFlux -- the default libm's _flux twins -- while spectral output is on
 	// A scene waiting for its own kernels runs the generic one meanwhile: its second blob (packed for topology 3 at upload, the
 	// caller's description is gone later) waits on the device, and the context swaps at the start of a render once the code is
 	// there (maybe_swap_jit).  The compilation is asked for once the context has launched kJitAfterSamples on the generic kernel.
@@ -125,13 +126,20 @@ struct ssx_ctx {
 	// Progressive rendering (csrc/ssx_progressive.hip).  What d_accum holds -- continuable: every owned pixel holds samples [0, done_spp) of `cur`,
 	// the sums may be continued or exported; noise_valid: d_noise describes them, after noise_batches batches (B).  Written by sums_invalidate /
 	// sums_publish and, for the estimate, the noise_* helpers; nowhere else.
-	struct SumsState { bool continuable = false, noise_valid = false; uint32_t noise_batches = 0; } sums;
+	// spectral_valid: d_spectral_sums / d_spectral_counts hold the bins of exactly those samples (valid from zero samples or not at all: ssx_spectral.hip).
+	struct SumsState { bool continuable = false, noise_valid = false, spectral_valid = false; uint32_t noise_batches = 0; } sums;
 	uint32_t k_begin = 0;               // first sample of the running call: 0 (ssx_render_start) or the count ssx_render_continue took up (ssx_progress)
 	uint64_t scene_digest = 0;          // ssx_scene_digest
 	// noise estimate by batch means (ssx_set_noise_estimate): per pixel A_prev | S2 (row-major, 2 x width x height doubles)
 	bool noise_on = false;
 	DeviceBuffer d_noise;
-	DeviceBuffer d_stage;               // row-major staging of ssx_sums_export / ssx_sums_import / ssx_noise_info: kept from call to call (render_until asks every step)
+	DeviceBuffer d_stage;               // row-major staging of ssx_sums_export / ssx_sums_import / ssx_noise_info / ssx_spectral_read: kept from call to call (render_until asks every step)
+	// spectral output (ssx_set_spectral_bins; csrc/ssx_spectral.hip): B bins, 0 = off -- then nothing below is allocated, no kernel of it runs and the
+	// sample arrays have no flux[].  S[tile slot][bin][pixel of the tile] binary64, N[tile slot][m][pixel of the tile].
+	uint32_t spectral_bins = 0;
+	DeviceBuffer d_spectral_sums, d_spectral_counts;
+	std::string spectral_note;          // why sums that can be continued come without spectral state (ssx_spectral_read says it)
+	float lambda_min = 0.0f, lambda_step = 0.0f; // of the uploaded scene
 
 	// optional per-kernel timing (ssx_set_timing): events around each stage of each batch
 	bool timing = false;
@@ -228,14 +236,15 @@ void sums_publish(ssx_ctx* ctx, uint32_t done_spp, int64_t noise_batches = -1) {
 // kernel until the path kernel has folded the sample; the buffer bounds how many samples per pixel one launch may cover.  The
 // levels of the recursion live in the persistent waves' logs (ensure_logs), whose size does not depend on the launch.
 constexpr size_t kSampleBufferBudget = (size_t)16 << 30; // bytes of per-sample arrays one launch may use (512^2 x 256 spp = 3.2 GB; 16 GiB = 358 M samples ~ 110 ms of rendering)
-constexpr size_t kBytesPerSampleInFlight = SSX_BYTES_PER_SAMPLE;
+// (64 while spectral output is on: the fold of the _flux kernels leaves every sample's hero flux in a fourth array, ssx_blob.h)
+size_t bytes_per_sample(const ssx_ctx* ctx) { return ctx->spectral_bins ? SSX_BYTES_PER_SAMPLE_FLUX : SSX_BYTES_PER_SAMPLE; }
 // Behind the per-sample arrays, per launch: unit_state (1 word per work unit) and tile_mask (4 words per tile slot).  A launch of R records
 // has at most R / 64 tile slots and R / 64 units: 5 words per 64 records bound both, so the words are part of the sample allocation
 // (sized before anything is enqueued: ensure_samples) and never grown in the enqueue path.
 constexpr size_t kAuxWordsPer64Records = 5;
-constexpr size_t kBytesPer64Records = 64u * kBytesPerSampleInFlight + kAuxWordsPer64Records * sizeof(uint32_t);
-size_t sample_bytes(size_t records) { return records / 64u * kBytesPer64Records; } // the allocation for `records` (64 per tile and sample: a multiple of 64)
-size_t sample_slots(const ssx_ctx* ctx) { return ctx->d_samples.bytes / kBytesPer64Records * 64u; } // record capacity of the allocation
+size_t bytes_per_64_records(const ssx_ctx* ctx) { return 64u * bytes_per_sample(ctx) + kAuxWordsPer64Records * sizeof(uint32_t); }
+size_t sample_bytes(const ssx_ctx* ctx, size_t records) { return records / 64u * bytes_per_64_records(ctx); } // the allocation for `records` (64 per tile and sample: a multiple of 64)
+size_t sample_slots(const ssx_ctx* ctx) { return ctx->d_samples.bytes / bytes_per_64_records(ctx) * 64u; } // record capacity of the allocation
 size_t log_records(const ssx_ctx* ctx) { return ctx->d_logs.bytes / SSX_LOG_BYTES_PER_RECORD; }     // log-record capacity
 constexpr uint32_t kMinUnits = 3072;                   // one wave work unit per wave slot of the GPU (256 CUs x 4 SIMDs x 3 waves)
 // Samples an asynchronous render launches between two host synchronisations, about (~20 ms): the granularity of progress and ssx_render_stop, large
@@ -263,11 +272,11 @@ LaunchPlan make_plan(ssx_ctx* ctx, const ssx_render_params* p, bool ask_device =
 	a.fuse_resolve = ctx->fuse_resolve ? 1u : 0u;
 	a.pre_hits = ctx->pre_hits ? 1u : 0u;
 	a.my_tiles = a.n_tiles > p->tile_first ? (a.n_tiles - p->tile_first + p->tile_stride - 1u) / p->tile_stride : 0u;
-	size_t per_spp = (size_t)(a.my_tiles ? a.my_tiles : 1u) * 64u * kBytesPerSampleInFlight;
+	size_t per_spp = (size_t)(a.my_tiles ? a.my_tiles : 1u) * 64u * bytes_per_sample(ctx);
 	// the budget, or 80 % of what is free on the device right now (plus what this context already holds)
 	size_t budget = kSampleBufferBudget, free_b = 0, total_b = 0;
 	if (ask_device && hipMemGetInfo(&free_b, &total_b) == hipSuccess) { // (not while the stream is being captured: the buffers have their size then)
-		const size_t avail = (size_t)((double)(free_b + sample_slots(ctx) * kBytesPerSampleInFlight) * 0.8);
+		const size_t avail = (size_t)((double)(free_b + sample_slots(ctx) * bytes_per_sample(ctx)) * 0.8);
 		if (avail < budget) budget = avail;
 	}
 	size_t cap = budget / per_spp;
@@ -290,7 +299,7 @@ void cap_to_allocation(const ssx_ctx* ctx, LaunchPlan& pl) {
 
 int ensure_samples(ssx_ctx* ctx, const LaunchPlan& pl, uint32_t n_k) {
 	const size_t need = (size_t)pl.args.my_tiles * 64u * n_k;
-	const hipError_t e = ctx->d_samples.reserve(sample_bytes(need));
+	const hipError_t e = ctx->d_samples.reserve(sample_bytes(ctx, need));
 	if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(ctx, SSX_ERR_DEVICE, fmt("out of device memory for %zu samples in flight; lower spp_per_launch", need)); }
 	SSX_HIP(ctx, e);
 	return SSX_OK;
@@ -317,10 +326,11 @@ int ensure_logs(ssx_ctx* ctx, uint32_t unit_cohorts) {
 }
 
 // the per-sample arrays of one batch inside a region of `cap` records starting at `base`, and the waves' logs (ssx_blob.h)
-void bind_arrays(SsxKernelArgs& a, uint8_t* base, uint64_t cap, uint8_t* logs, uint64_t log_cap) {
+void bind_arrays(SsxKernelArgs& a, uint8_t* base, uint64_t cap, uint8_t* logs, uint64_t log_cap, bool with_flux) {
 	a.ray = reinterpret_cast<float4*>(base);                      base += cap * 16u;
 	a.st = reinterpret_cast<uint4*>(base);                        base += cap * 16u;
-	a.hit = reinterpret_cast<float4*>(base);
+	a.hit = reinterpret_cast<float4*>(base);                      base += cap * 16u;
+	a.flux = with_flux ? reinterpret_cast<float4*>(base) : nullptr; // (spectral output on: the allocation counts 64 bytes per record)
 	a.logs = logs; a.log_cap = (uint32_t)log_cap; // fs | nee | direct | np | link | vis (ssx_kernels.hip: log_fs ...)
 }
 
@@ -390,10 +400,10 @@ Batch make_batch(ssx_ctx* ctx, const LaunchPlan& pl, uint32_t k0, uint32_t k1) {
 	b.n_rec = a.n_records;
 	// sample arrays and logs are shared by all batches of a render: their kernels run one after the other in stream order
 	b.rc = ensure_logs(ctx, a.unit_cohorts);
-	if (b.rc == SSX_OK) bind_arrays(a, ctx->d_samples.as<uint8_t>(), a.n_records, ctx->d_logs.as<uint8_t>(), log_records(ctx));
+	if (b.rc == SSX_OK) bind_arrays(a, ctx->d_samples.as<uint8_t>(), a.n_records, ctx->d_logs.as<uint8_t>(), log_records(ctx), ctx->spectral_bins != 0u);
 	a.accum = ctx->d_accum.as<double>();
 	// the launch's per-unit and per-tile words, behind the sample arrays' capacity: unit_state | tile_mask
-	uint32_t* const aux = reinterpret_cast<uint32_t*>(ctx->d_samples.as<uint8_t>() + sample_slots(ctx) * kBytesPerSampleInFlight);
+	uint32_t* const aux = reinterpret_cast<uint32_t*>(ctx->d_samples.as<uint8_t>() + sample_slots(ctx) * bytes_per_sample(ctx));
 	a.unit_state = aux;
 	a.tile_mask = aux + b.units;
 	if (b.rc == SSX_OK && (size_t)a.my_tiles * 4u + b.units > (sample_slots(ctx) / 64u) * kAuxWordsPer64Records) b.rc = fail(ctx, SSX_ERR_STATE, "internal: launch larger than the sample allocation");
@@ -408,25 +418,28 @@ size_t path_lds_bytes(uint32_t blob_words, uint32_t queue_words) {
 #endif
 	return n;
 }
-// The path megakernels of this library: [libm][pass-1 variant: 0 generic, 1 Cornell topology, 2 plane topology][narrow queue entries].
+// The path megakernels of this library: [variant: libm 0 / 1, or 2 = the default libm's _flux twins (spectral output)][pass-1 variant: 0 generic, 1 Cornell
+// topology, 2 plane topology][narrow queue entries].
 // Topology 3 runs the run-time compiled pair of the scene's pattern (ssx_ctx::jit_kernels), named the same in both modes (other modules).
 struct PathKernel { const char* name; void (*host)(SsxKernelArgs); };
 #define SSX_PK(k) { #k, k }
-static const PathKernel kPathKernels[2][3][2] = {
+static const PathKernel kPathKernels[ssx_jit::kVariants][3][2] = {
 	{ { SSX_PK(ssx_render_kernel), SSX_PK(ssx_render_kernel_nq) }, { SSX_PK(ssx_render_kernel_cornell), SSX_PK(ssx_render_kernel_cornell_nq) },
 	  { SSX_PK(ssx_render_kernel_plane), SSX_PK(ssx_render_kernel_plane_nq) } },
 	{ { SSX_PK(ssx_render_kernel_glibc), SSX_PK(ssx_render_kernel_nq_glibc) }, { SSX_PK(ssx_render_kernel_cornell_glibc), SSX_PK(ssx_render_kernel_cornell_nq_glibc) },
-	  { SSX_PK(ssx_render_kernel_plane_glibc), SSX_PK(ssx_render_kernel_plane_nq_glibc) } } };
+	  { SSX_PK(ssx_render_kernel_plane_glibc), SSX_PK(ssx_render_kernel_plane_nq_glibc) } },
+	{ { SSX_PK(ssx_render_kernel_flux), SSX_PK(ssx_render_kernel_nq_flux) }, { SSX_PK(ssx_render_kernel_cornell_flux), SSX_PK(ssx_render_kernel_cornell_nq_flux) },
+	  { SSX_PK(ssx_render_kernel_plane_flux), SSX_PK(ssx_render_kernel_plane_nq_flux) } } };
 #undef SSX_PK
 static const char* const kJitKernelNames[2] = { "ssx_render_kernel_jit", "ssx_render_kernel_jit_nq" };
 // this library's kernel for the context's libm and topology (a scene still waiting for its own kernels runs the generic one)
-const PathKernel& path_kernel_of(const ssx_ctx* ctx, bool narrow) { return kPathKernels[ctx->libm][ctx->topology < 3u ? ctx->topology : 0u][narrow]; }
+const PathKernel& path_kernel_of(const ssx_ctx* ctx, bool narrow) { return kPathKernels[ctx->variant][ctx->topology < 3u ? ctx->topology : 0u][narrow]; }
 // A kernel of this library (host function) or of a run-time compiled module (topology 3), for the context's libm.  A glibc-mode render of a
 // specialised scene has its kernels (ensure_libm_kernels) before it gets here.
 struct KernelRef { const void* host = nullptr; hipFunction_t mod = nullptr; };
 KernelRef path_kernel_ref(const ssx_ctx* ctx, bool narrow) {
 	KernelRef k;
-	const ssx_jit::Kernels* jk = ctx->jit_kernels[ctx->libm];
+	const ssx_jit::Kernels* jk = ctx->jit_kernels[ctx->variant];
 	if (ctx->topology == 3u && jk) k.mod = narrow ? jk->path_nq : jk->path;
 	else k.host = (const void*)path_kernel_of(ctx, narrow).host;
 	return k;
@@ -542,19 +555,19 @@ void maybe_swap_jit(ssx_ctx* ctx, uint64_t samples) {
 	if (!ctx->jit_pending) return;
 	std::string err;
 	const ssx_jit::Kernels* k = nullptr;
-	const ssx_jit::State st = ssx_jit::lookup(ctx->device, ctx->jit_vid, &k, &err, ctx->libm);
+	const ssx_jit::State st = ssx_jit::lookup(ctx->device, ctx->jit_vid, &k, &err, ctx->variant);
 	if (st == ssx_jit::State::Ready) {
 		std::swap(ctx->d_blob, ctx->d_blob_jit);
 		ctx->blob_words = ctx->blob_jit_words; ctx->path_blob_words = ctx->path_blob_jit_words;
 		ctx->topology = 3u;
-		ctx->jit_kernels[ctx->libm] = k;
+		ctx->jit_kernels[ctx->variant] = k;
 		ctx->resident_blocks = 0; ctx->gen_blocks = 0; // the blob's LDS footprint changed
 		ctx->jit_pending = false; ctx->jit_state = SSX_JIT_STATE_SPECIALISED;
 	} else if (st == ssx_jit::State::Failed) {
 		ctx->jit_pending = false; ctx->jit_state = SSX_JIT_STATE_FAILED; ctx->jit_message = err;
 	} else {
 		ctx->generic_samples += samples;
-		if (!ctx->jit_requested && ctx->generic_samples >= kJitAfterSamples) { ssx_jit::request(ctx->jit_vid, ctx->libm); ctx->jit_requested = true; }
+		if (!ctx->jit_requested && ctx->generic_samples >= kJitAfterSamples) { ssx_jit::request(ctx->jit_vid, ctx->variant); ctx->jit_requested = true; }
 	}
 }
 
@@ -575,10 +588,14 @@ int ensure_libm_kernels(ssx_ctx* ctx, uint32_t libm) {
 // The context ready to launch a render with `p`: the kernels of its libm there and current (the plan of the resident workgroups is
 // redone when the libm changes: the twins are different kernels), the pixel sums and -- asked for -- the output image sized.
 int ready_to_launch(ssx_ctx* ctx, const ssx_render_params* p, bool need_out) {
-	const int rc = ensure_libm_kernels(ctx, p->libm);
+	// spectral output on: the _flux twins (a specialised scene's are compiled here, on the calling thread, at its first spectral render).  They exist for the
+	// default libm and spectral scenes only; the entry points refuse the rest while it is on (spectral_refuses)
+	const uint32_t variant = (ctx->spectral_bins && p->libm == SSX_LIBM_BUILD && !ctx->rgb_mode) ? ssx_jit::kVariantFlux : p->libm;
+	const int rc = ensure_libm_kernels(ctx, variant);
 	if (rc) return rc;
 	// (a scene still waiting for its own kernels asks again, for this mode's: maybe_swap_jit)
-	if (ctx->libm != p->libm) { ctx->libm = p->libm; ctx->resident_blocks = 0; ctx->jit_requested = false; }
+	ctx->libm = p->libm;
+	if (ctx->variant != variant) { ctx->variant = variant; ctx->resident_blocks = 0; ctx->jit_requested = false; }
 	SSX_HIP(ctx, ctx->d_accum.reserve(accum_bytes(p->width, p->height)));
 	if (need_out) SSX_HIP(ctx, ctx->d_out.reserve(image_bytes(p->width, p->height)));
 	return SSX_OK;
@@ -650,6 +667,10 @@ int launch_finalize(ssx_ctx* ctx, const ssx_render_params* p, uint32_t spp, floa
 // the noise estimate's part in the render loop (csrc/ssx_progressive.hip)
 int noise_begin(ssx_ctx* ctx, const ssx_render_params* p, uint32_t k_begin, bool continuing);
 int noise_batch(ssx_ctx* ctx, const ssx_render_params* p, uint32_t n_k, hipStream_t stream);
+// ... and the spectral output's (csrc/ssx_spectral.hip)
+int spectral_refuses(ssx_ctx* ctx, const ssx_render_params& p, bool tile_walk);
+int spectral_begin(ssx_ctx* ctx, uint32_t my_tiles, bool continuing, bool* active);
+int spectral_batch(ssx_ctx* ctx, const ssx_render_params* p, const LaunchPlan& pl, uint32_t n_k, hipStream_t stream);
 
 // The asynchronous render: one worker thread per call of ssx_render_start / ssx_render_continue, walking through the samples or the tiles.  The end
 // of either walk: the image of what the sums hold, on the device, the stream idle.
@@ -695,6 +716,8 @@ int render_sample_walk(ssx_ctx* ctx, const ssx_render_params& p, uint32_t k_begi
 	if ((rc = noise_begin(ctx, &p, k_begin, continuing))) return rc;
 	maybe_swap_jit(ctx, 0); // (the scene's own kernels, if they have arrived: the plan is of the blob that is current now)
 	LaunchPlan pl = make_plan(ctx, &p);
+	bool spectral = false;
+	if ((rc = spectral_begin(ctx, pl.args.my_tiles, continuing, &spectral))) return rc;
 	const uint32_t span = p.spp - k_begin, chunk = sample_walk_chunk(p, span, pl);
 	if ((rc = ensure_samples(ctx, pl, chunk < span ? chunk : span))) return rc;
 	for (uint32_t k0 = k_begin; k0 < p.spp && !ctx->stop_flag.load(); k0 += chunk) {
@@ -705,6 +728,7 @@ int render_sample_walk(ssx_ctx* ctx, const ssx_render_params& p, uint32_t k_begi
 		}
 		if ((rc = launch_range(ctx, pl, k0, k1, ctx->stream))) return rc;
 		if (ctx->noise_on && (rc = noise_batch(ctx, &p, k1 - k0, ctx->stream))) return rc;
+		if (spectral && (rc = spectral_batch(ctx, &p, pl, k1 - k0, ctx->stream))) return rc;
 		SSX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 		ctx->done_spp.store(k1);
 	}
@@ -714,6 +738,8 @@ int render_sample_walk(ssx_ctx* ctx, const ssx_render_params& p, uint32_t k_begi
 	const uint32_t done = ctx->done_spp.load();
 	if ((rc = finish_walk(ctx, p, done ? done : p.spp, 0xFFFFFFFFu))) return rc;
 	ctx->done_tiles.store(pl.args.my_tiles);
+	ctx->sums.spectral_valid = spectral; // (the bins of the launches that ran: exactly the samples the sums hold)
+	if (!spectral) ctx->spectral_note = "the render that made these sums ran without them (it continued sums that had none)";
 	sums_publish(ctx, done);
 	return SSX_OK;
 }
@@ -763,6 +789,7 @@ void worker_main(ssx_ctx* ctx, uint32_t k_begin, bool continuing) {
 // worker renders samples [k_begin, p.spp) of it, total_spp of them (ssx_progress).
 int start_worker(ssx_ctx* ctx, const ssx_render_params& p, uint32_t k_begin, bool continuing, uint32_t total_spp) {
 	if (ctx->worker.joinable()) ctx->worker.join();
+	if (const int rc = spectral_refuses(ctx, p, p.tile_major && !continuing)) return rc;
 	if (const int rc = ready_to_launch(ctx, &p, true)) return rc;
 	ctx->cur = p; ctx->total_spp = total_spp; ctx->k_begin = k_begin;
 	if (!continuing) { sums_invalidate(ctx); ctx->done_spp.store(0); ctx->done_tiles.store(0); } // (the worker publishes the sums it leaves)
@@ -1012,6 +1039,7 @@ int ssx_upload_scene(ssx_ctx* ctx, const ssx_scene_desc* s) {
 		}
 	}
 	ctx->have_cam_dir = have_cam_dir;
+	ctx->lambda_min = s->lambda_min; ctx->lambda_step = s->lambda_step;
 	ctx->resident_blocks = 0; ctx->gen_blocks = 0; // depend on the blob's LDS footprint
 	ctx->have_scene = true;
 	ctx->scene_digest = scene_digest_of(s);
@@ -1038,6 +1066,7 @@ int ssx_render_device(ssx_ctx* ctx, const ssx_render_params* p_in, void* d_xyza_
 	if (rc) return rc;
 	const ssx_render_params* const p = &pp;
 	if (!d_xyza_out) return fail(ctx, SSX_ERR_ARG, "d_xyza_out is NULL");
+	if (ctx->spectral_bins) return fail(ctx, SSX_ERR_ARG, "spectral output is on (ssx_set_spectral_bins): ssx_render_device does not bin its samples; use ssx_render_start");
 	if (ctx->rendering.load()) return fail(ctx, SSX_ERR_STATE, "asynchronous render in progress");
 	hipStream_t stream = (hipStream_t)hip_stream;
 	SSX_HIP(ctx, hipSetDevice(ctx->device));
@@ -1053,7 +1082,7 @@ int ssx_render_device(ssx_ctx* ctx, const ssx_render_params* p_in, void* d_xyza_
 	const bool capturing = capture == hipStreamCaptureStatusActive;
 	if (ctx->device_pending && capturing) return fail(ctx, SSX_ERR_STATE, "a render of this context may still be queued: ssx_render_device_wait before capturing another into a graph");
 	// (the kernels of another libm may need a compilation and change the plan of the resident workgroups: not while capturing)
-	if (capturing && ctx->libm != p->libm) return fail(ctx, SSX_ERR_STATE, "ssx_render_params.libm differs from the context's last render: run it once outside the stream capture first");
+	if (capturing && ctx->variant != p->libm) return fail(ctx, SSX_ERR_STATE, "ssx_render_params.libm differs from the context's last render: run it once outside the stream capture first");
 	if (ctx->device_pending) SSX_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev_device_done, 0));
 	{
 		LaunchPlan probe = make_plan(ctx, p, !capturing);
@@ -1062,7 +1091,7 @@ int ssx_render_device(ssx_ctx* ctx, const ssx_render_params* p_in, void* d_xyza_
 		if (capturing) cap_to_allocation(ctx, probe);
 		const uint32_t probe_batch = device_batch(p, probe);
 		const size_t need = (size_t)probe.args.my_tiles * 64u * probe_batch;
-		const bool grow = ctx->d_accum.bytes < accum_bytes(p->width, p->height) || ctx->d_samples.bytes < sample_bytes(need);
+		const bool grow = ctx->d_accum.bytes < accum_bytes(p->width, p->height) || ctx->d_samples.bytes < sample_bytes(ctx, need);
 		if (grow && capturing) return fail(ctx, SSX_ERR_STATE, "the context's buffers have to grow for this render: run it once outside the stream capture first");
 		if (grow && (rc = wait_device_pending(ctx))) return rc;
 	}
@@ -1228,6 +1257,7 @@ int ssx_debug_samples(ssx_ctx* ctx, const ssx_render_params* p_in, float* xyza, 
 	if (rc) return rc;
 	const ssx_render_params* const p = &pp;
 	if (p->tile_first != 0 || p->tile_stride != 1) return fail(ctx, SSX_ERR_ARG, "ssx_debug_samples renders the whole image");
+	if ((rc = spectral_refuses(ctx, pp, false))) return rc;
 	SSX_HIP(ctx, hipSetDevice(ctx->device));
 	if ((rc = wait_device_pending(ctx))) return rc;
 	if ((rc = ready_to_launch(ctx, p, false))) return rc;
@@ -1283,8 +1313,8 @@ int ssx_jit_status(ssx_ctx* ctx, int wait_ms, char* message, size_t message_size
 	if (ctx->rendering.load()) return fail(ctx, SSX_ERR_STATE, "render in progress");
 	if (ctx->jit_pending && wait_ms != 0) {
 		if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, SSX_ERR_DEVICE, "hipSetDevice failed");
-		if (!ctx->jit_requested) { ssx_jit::request(ctx->jit_vid, ctx->libm); ctx->jit_requested = true; }
-		(void)ssx_jit::wait(ctx->jit_vid, wait_ms < 0 ? 600000 : wait_ms, ctx->libm);
+		if (!ctx->jit_requested) { ssx_jit::request(ctx->jit_vid, ctx->variant); ctx->jit_requested = true; }
+		(void)ssx_jit::wait(ctx->jit_vid, wait_ms < 0 ? 600000 : wait_ms, ctx->variant);
 		maybe_swap_jit(ctx, 0);
 	}
 	copy_text(ctx->jit_message, message, message_size);
@@ -1318,7 +1348,7 @@ int ssx_calibration_info(ssx_ctx* ctx, float* frames_per_sample, float* rays_lef
 
 int ssx_scratch_info(ssx_ctx* ctx, uint64_t* sample_bytes, uint64_t* log_bytes) {
 	if (!ctx) return SSX_ERR_ARG;
-	if (sample_bytes) *sample_bytes = (uint64_t)sample_slots(ctx) * kBytesPerSampleInFlight;
+	if (sample_bytes) *sample_bytes = (uint64_t)sample_slots(ctx) * bytes_per_sample(ctx);
 	if (log_bytes) *log_bytes = (uint64_t)ctx->d_logs.bytes;
 	return SSX_OK;
 }
@@ -1387,3 +1417,4 @@ int ssx_kernel_info(ssx_ctx* ctx, int* vgprs, int* sgprs, int* lds_bytes, int* s
 } // extern "C"
 
 #include "ssx_progressive.hip"
+#include "ssx_spectral.hip"

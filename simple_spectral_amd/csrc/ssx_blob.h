@@ -124,6 +124,8 @@ struct SsxBlobTexture { // 4 words: device pointer of the RGB8 texels (rows top 
 //                    state} (the final state = draws consumed, for the per-sample tests).  Tail word (D = number
 //                    of continued levels = the path's last level): hit_anything | level D has an emission term << 1
 //                    | D << 2 | slot of level D-1's entry << 6 | slot of level D's next-event term << 19
+//   flux[r]  float4  only while spectral output is on (ssx_set_spectral_bins; 64 bytes per sample then): the fold of the _flux kernels
+//                    leaves the sample's four hero-wavelength fluxes here, for ssx_spectral_bin_kernel (csrc/ssx_spectral.hip)
 // The levels of the recursion are NOT stored per record (paths have 0..9 levels, a [level][record] array is
 // read and written in 128-byte lines of which the deep levels use one record in three): they go to LOGS,
 // entries appended in the order the wave produces them, so that the stores of one wave iteration and the fold's
@@ -165,6 +167,7 @@ struct SsxBlobTexture { // 4 words: device pointer of the RGB8 texels (rows top 
 #define SSX_UNIT_PARKED 1u
 #define SSX_UNIT_TURN 2u
 #define SSX_BYTES_PER_SAMPLE (16u + 16u + 16u)         // ray, st, hit
+#define SSX_BYTES_PER_SAMPLE_FLUX (SSX_BYTES_PER_SAMPLE + 16u) // ... and flux, while spectral output is on
 #define SSX_LOG_BYTES_PER_RECORD ((16u + 8u + 4u) * SSX_MAX_FRAMES + (16u + 16u + 1u) * SSX_MAX_LEVELS) // fs, np, link; nee, direct, vis
 
 struct SsxKernelArgs {
@@ -206,4 +209,5 @@ struct SsxKernelArgs {
 	double inv_width, inv_height; // 1.0 / width, 1.0 / height (binary64): for a power-of-two image size (i + subpixel) / res is the exact product with them (camera_dir)
 	uint32_t fuse_gen;        // 1 (only with pre_hits == 0, kernels of the plane topology): no ssx_generate_kernel ran -- the path kernel's refill makes a sample's
 	                          // stream, camera ray and lambda_0 where it hands the sample to a lane (generate_sample), and ray[] / st[] are not read there
+	float4* flux;             // the _flux kernels only (spectral output; else NULL): per sample the hero flux {f0, f1, f2, f3} handed to flux_to_xyz
 };

@@ -1282,7 +1282,9 @@ __device__ __forceinline__ float4 nee_term(const SsxKernelArgs& a, uint32_t i, b
 }
 // fs_base / nee_base: index of slot 0 of the cohort's logs (log_rec * 9, log_rec * 10); rc0: the lane's pixel of the tile
 // (its first sample within the cohort; way s is sample rc0 + 64 s); acc: the lane's pixel sums (unit_fold)
-template <uint32_t WAYS, bool NARROW>
+// FLUX (the _flux kernels: spectral output, include/ssx.h ssx_set_spectral_bins): every sample's Hero flux -- what flux_to_xyz is handed, i.e. behind
+// the no_flat_field multiply -- also goes to flux[r], the sample's own record of a fourth per-sample array; parked samples included.
+template <uint32_t WAYS, bool NARROW, bool FLUX = false>
 __device__ __forceinline__ void resolve_records(const Lds& L, const SsxKernelArgs& a, uint32_t r0, uint32_t stride, uint32_t count, uint32_t fs_base, uint32_t nee_base, uint32_t rc0, double acc[4], bool stage) {
 	float rad[WAYS][4];
 	uint32_t depth[WAYS]; // hit_anything << 4 | number of continued levels
@@ -1353,6 +1355,7 @@ __device__ __forceinline__ void resolve_records(const Lds& L, const SsxKernelArg
 				rad[s][0] *= d; rad[s][1] *= d; rad[s][2] *= d; rad[s][3] *= d;
 			}
 			Hero flux; flux.v[0] = rad[s][0]; flux.v[1] = rad[s][1]; flux.v[2] = rad[s][2]; flux.v[3] = rad[s][3];
+			if (FLUX) c.flux[r0 + s * stride] = make_float4(rad[s][0], rad[s][1], rad[s][2], rad[s][3]);
 			float xyz[3];
 			if (rgb_mode) { xyz[0] = rad[s][0]; xyz[1] = rad[s][1]; xyz[2] = rad[s][2]; } // renderer.cpp:274-276: lRGB_A_F32(pixel_flux_est, hit)
 			else flux_to_xyz(L, flux, __uint_as_float(a.st[r0 + s * stride].x), xyz); // lambda_0 (re-read: a register per way less across the chain walk)
@@ -1617,7 +1620,7 @@ __device__ __forceinline__ void sums_chain(uint32_t slot, uint32_t grp, uint32_t
 		if (lane == 0u) atomicAdd(a.unit_counter + 3, 1u); // statistics (ssx_sums_info): parked units added by the wave in front of them
 	}
 }
-template <bool NARROW>
+template <bool NARROW, bool FLUX = false>
 __device__ __forceinline__ void unit_fold(const Lds& L, const SsxKernelArgs& a, const WorkUnit& u, uint32_t wave_slot, uint32_t tag, uint32_t* cnt) {
 	// see "Memory-ordering contract" above: the acquire side of the wave's hand-over; then wait for this wave's stores and
 	// drop the CU's L1 lines
@@ -1640,7 +1643,7 @@ __device__ __forceinline__ void unit_fold(const Lds& L, const SsxKernelArgs& a, 
 	if (has_px)
 		for (uint32_t kq = 0, n_kq = u.n_kq(), rec_base = u.rec_base(a); kq < n_kq; kq += SSX_COHORT_KS) { // one cohort per pass
 			const uint32_t log_rec = log_region(a, wave_slot, tag, kq / SSX_COHORT_KS);
-			resolve_records<SSX_COHORT_KS, NARROW>(L, a, rec_base + kq * 64u + lane, 64u, min(SSX_COHORT_KS, n_kq - kq), log_rec * SSX_MAX_FRAMES, log_rec * SSX_MAX_LEVELS, lane, acc, !mine);
+			resolve_records<SSX_COHORT_KS, NARROW, FLUX>(L, a, rec_base + kq * 64u + lane, 64u, min(SSX_COHORT_KS, n_kq - kq), log_rec * SSX_MAX_FRAMES, log_rec * SSX_MAX_LEVELS, lane, acc, !mine);
 		}
 	if (mine) {
 		if (has_px) { st_agent(px, acc[0]); st_agent(px + 64, acc[1]); st_agent(px + 128, acc[2]); st_agent(px + 192, acc[3]); }
@@ -1672,7 +1675,8 @@ __device__ __forceinline__ void unit_fold(const Lds& L, const SsxKernelArgs& a, 
 
 // CALIB: the calibration render of ssx_upload_scene (ssx_calibrate_kernel) also counts the rays that leave the scene
 // GLIBC: libm = glibc-2.35 (the _glibc kernels): glibc's transcendentals instead of ssx_fmath.h's
-template <int TOPO, bool NARROW, bool CALIB = false, bool GLIBC = false>
+// FLUX: the _flux kernels (spectral output): the fold also stores every sample's hero flux (resolve_records)
+template <int TOPO, bool NARROW, bool CALIB = false, bool GLIBC = false, bool FLUX = false>
 __device__ __forceinline__ void render_body(const SsxKernelArgs& a) {
 	constexpr bool FUSE_GEN = TOPO == 2; // the kernels that can make their samples themselves (SsxKernelArgs::fuse_gen): the plane topology's, whose scenes trace camera rays in the path loop
 	uint32_t* const lds_words = stage_lds<GLIBC>(a);
@@ -1788,7 +1792,7 @@ __device__ __forceinline__ void render_body(const SsxKernelArgs& a) {
 			SSX_TIME(tm, 5); // (shadow flush: queue read, result store; its trace is timed inside)
 		}
 		if (fold_old) {
-			if (a.fuse_resolve) unit_fold<NARROW>(L, a, old, wave_slot, old_tag, log_cnt);
+			if (a.fuse_resolve) unit_fold<NARROW, FLUX>(L, a, old, wave_slot, old_tag, log_cnt);
 			old_pending = false;
 			SSX_TIME(tm, 6); // (fold)
 		}
@@ -1896,26 +1900,36 @@ __device__ __forceinline__ void render_body(const SsxKernelArgs& a) {
 #define SSX_JIT_GLIBC 0
 #endif
 // glibc: libm = glibc-2.35, the same kernel with glibc's transcendentals (render_body's GLIBC), named <default name>_glibc
-#define SSX_PATH_KERNEL(name, topo, narrow, glibc) \
-	extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SSX_WAVES_PER_EU))) name(SsxKernelArgs a) { render_body<topo, narrow, false, glibc>(a); }
+// flux: the default-libm kernel that also stores every sample's hero flux (render_body's FLUX), named <default name>_flux
+#ifndef SSX_JIT_FLUX
+#define SSX_JIT_FLUX 0
+#endif
+#define SSX_PATH_KERNEL(name, topo, narrow, glibc, flux) \
+	extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SSX_WAVES_PER_EU))) name(SsxKernelArgs a) { render_body<topo, narrow, false, glibc, flux>(a); }
 #ifdef SSX_JIT_BUILD // the run-time compilation holds the two path kernels of the uploaded scene's topology, nothing else; the libm mode is
 // a compile flag of it, and so part of its cache key (csrc/ssx_jit.h)
-SSX_PATH_KERNEL(ssx_render_kernel_jit, 3, false, SSX_JIT_GLIBC)
-SSX_PATH_KERNEL(ssx_render_kernel_jit_nq, 3, true, SSX_JIT_GLIBC)
+SSX_PATH_KERNEL(ssx_render_kernel_jit, 3, false, SSX_JIT_GLIBC, SSX_JIT_FLUX)
+SSX_PATH_KERNEL(ssx_render_kernel_jit_nq, 3, true, SSX_JIT_GLIBC, SSX_JIT_FLUX)
 #else
-SSX_PATH_KERNEL(ssx_render_kernel, 0, false, false)
-SSX_PATH_KERNEL(ssx_render_kernel_cornell, 1, false, false)
+SSX_PATH_KERNEL(ssx_render_kernel, 0, false, false, false)
+SSX_PATH_KERNEL(ssx_render_kernel_cornell, 1, false, false, false)
 #ifndef SSX_PROBE_BUILD // tools/kernel_resources.py --probe: the two kernels above only (register pressure experiments)
-SSX_PATH_KERNEL(ssx_render_kernel_plane, 2, false, false)
-SSX_PATH_KERNEL(ssx_render_kernel_nq, 0, true, false)
-SSX_PATH_KERNEL(ssx_render_kernel_cornell_nq, 1, true, false)
-SSX_PATH_KERNEL(ssx_render_kernel_plane_nq, 2, true, false)
-SSX_PATH_KERNEL(ssx_render_kernel_glibc, 0, false, true)
-SSX_PATH_KERNEL(ssx_render_kernel_cornell_glibc, 1, false, true)
-SSX_PATH_KERNEL(ssx_render_kernel_plane_glibc, 2, false, true)
-SSX_PATH_KERNEL(ssx_render_kernel_nq_glibc, 0, true, true)
-SSX_PATH_KERNEL(ssx_render_kernel_cornell_nq_glibc, 1, true, true)
-SSX_PATH_KERNEL(ssx_render_kernel_plane_nq_glibc, 2, true, true)
+SSX_PATH_KERNEL(ssx_render_kernel_plane, 2, false, false, false)
+SSX_PATH_KERNEL(ssx_render_kernel_nq, 0, true, false, false)
+SSX_PATH_KERNEL(ssx_render_kernel_cornell_nq, 1, true, false, false)
+SSX_PATH_KERNEL(ssx_render_kernel_plane_nq, 2, true, false, false)
+SSX_PATH_KERNEL(ssx_render_kernel_glibc, 0, false, true, false)
+SSX_PATH_KERNEL(ssx_render_kernel_cornell_glibc, 1, false, true, false)
+SSX_PATH_KERNEL(ssx_render_kernel_plane_glibc, 2, false, true, false)
+SSX_PATH_KERNEL(ssx_render_kernel_nq_glibc, 0, true, true, false)
+SSX_PATH_KERNEL(ssx_render_kernel_cornell_nq_glibc, 1, true, true, false)
+SSX_PATH_KERNEL(ssx_render_kernel_plane_nq_glibc, 2, true, true, false)
+SSX_PATH_KERNEL(ssx_render_kernel_flux, 0, false, false, true)
+SSX_PATH_KERNEL(ssx_render_kernel_cornell_flux, 1, false, false, true)
+SSX_PATH_KERNEL(ssx_render_kernel_plane_flux, 2, false, false, true)
+SSX_PATH_KERNEL(ssx_render_kernel_nq_flux, 0, true, false, true)
+SSX_PATH_KERNEL(ssx_render_kernel_cornell_nq_flux, 1, true, false, true)
+SSX_PATH_KERNEL(ssx_render_kernel_plane_nq_flux, 2, true, false, true)
 #endif
 // The generic kernel under another name for the calibration render of ssx_upload_scene (64x64x4 samples), so that
 // kernel traces and statistics of ssx_render_kernel* contain real launches only.  It stays on ssx_fmath.h's functions in glibc mode too:

@@ -193,6 +193,7 @@ int ssx_sums_import(ssx_ctx* ctx, const ssx_render_params* params, const ssx_sum
 	pp.spp = info->done_spp ? info->done_spp : 1u;
 	if ((rc = ready_to_launch(ctx, &pp, true))) return rc;
 	sums_invalidate(ctx);
+	ctx->spectral_note = "the sums came from ssx_sums_import, which carries no spectral state";
 	const size_t pixels = (size_t)pp.width * pp.height;
 	const bool s2_given = noise_s2 && info->noise_batches;
 	DeviceBuffer& stage = ctx->d_stage;

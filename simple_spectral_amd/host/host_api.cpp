@@ -155,6 +155,16 @@ int ssh_sums_merge(double* dst, double* dst_s2, const double* src, const double*
 	return SSX_OK;
 }
 
+int ssh_save_npy_f32(const char* path, const float* data, const uint32_t* shape, uint32_t ndim) {
+	if (!path || !data || !shape || ndim == 0 || ndim > 8) { g_error = "NULL argument or ndim outside 1..8"; return SSX_ERR_ARG; }
+	try {
+		size_t dims[8];
+		for (uint32_t d = 0; d < ndim; ++d) dims[d] = shape[d];
+		ssx::save_npy_f32(path, data, dims, ndim);
+		return SSX_OK;
+	} catch (const ssx::HostError& e) { return report(e); }
+}
+
 int ssh_color_values(const ssh_scene* scene, const char* name, float* out, int capacity) {
 	if (!scene || !name || !out) return SSX_ERR_ARG;
 	const ssx::ColorData& c = *scene->color;

@@ -232,4 +232,19 @@ void save_image(const std::string& path, const float* srgba, size_t W, size_t H)
 	std::fclose(file);
 }
 
+void save_npy_f32(const std::string& path, const float* data, const size_t* shape, size_t ndim) {
+	std::string dims;
+	size_t count = 1;
+	for (size_t d = 0; d < ndim; ++d) { dims += std::to_string(shape[d]) + (d + 1 < ndim || ndim == 1 ? "," : "") + (d + 1 < ndim ? " " : ""); count *= shape[d]; }
+	std::string header = "{'descr': '<f4', 'fortran_order': False, 'shape': (" + dims + "), }";
+	header.append(63 - (10 + header.size()) % 64, ' '); // magic (6) + version (2) + length (2) + header + '\n': a multiple of 64
+	header.push_back('\n');
+	if (header.size() > 0xFFFFu) throw HostError{ SSX_ERR_ARG, "save_npy_f32: shape too long for a version 1.0 header" };
+	const unsigned char head[10] = { 0x93, 'N', 'U', 'M', 'P', 'Y', 1, 0, static_cast<unsigned char>(header.size() & 0xFFu), static_cast<unsigned char>(header.size() >> 8) };
+	FILE* f = std::fopen(path.c_str(), "wb");
+	if (!f) throw HostError{ SSX_ERR_DATA, "Could not open \"" + path + "\" for writing" };
+	const bool ok = std::fwrite(head, 1, 10, f) == 10 && std::fwrite(header.data(), 1, header.size(), f) == header.size() && std::fwrite(data, sizeof(float), count, f) == count;
+	if (std::fclose(f) != 0 || !ok) throw HostError{ SSX_ERR_DATA, "Could not write \"" + path + "\"" };
+}
+
 } // namespace ssx

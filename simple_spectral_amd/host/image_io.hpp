@@ -25,4 +25,8 @@ Texture load_texture(const std::string& path);
 // (src/framebuffer.hpp:26-34).
 void save_image(const std::string& path, const float* srgba, size_t width, size_t height);
 
+// A NumPy .npy file, format version 1.0: little-endian float32 ('<f4'), C order, the given shape -- the header np.save writes (padded to a
+// multiple of 64 bytes), then the values as they lie in memory.  The spectral image: shape (height, width, bins), row 0 = bottom.
+void save_npy_f32(const std::string& path, const float* data, const size_t* shape, size_t ndim);
+
 } // namespace ssx

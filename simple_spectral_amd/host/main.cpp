@@ -7,6 +7,8 @@
 // Progressive rendering (not with --tile-major): --checkpoint=PATH writes the pixel sums at the end of the render and on abort; --resume=PATH
 // takes them up again, -spp then being the TOTAL wanted (at or below the checkpoint's count: the image is written as it is);
 // --noise-target=X --max-samples=N [--noise-step=S] renders in steps of S samples until the noise estimate falls to X or N samples are done.
+// Spectral output: --spectral-output=PATH.npy [--spectral-bins=N, default 16] also writes the per-pixel wavelength bins (include/ssx.h), a NumPy file of
+// shape (height, width, N), row 0 = bottom, after the image.  Not with --resume (a checkpoint carries no bins), --tile-major, --rgb or --libm=glibc-2.35.
 #include "renderer.hpp"
 
 #include <chrono>
@@ -38,7 +40,8 @@ void print_usage() {
 		"  MI355X build:\n"
 		"    `--gpus=<n>` `--seed=<n>` `--observer=1931|2006` `--uplift=ours|meng|jh` `--jh-coeff=<file>` `--meng-grid=<file>` `--rgb` `--no-explicit-light-sampling` `--no-flat-field-correction` `--tile-major` `--reduce=peer|rccl` `--libm=build|glibc-2.35`\n"
 		"    `--texture=<png>` `--light-scale=<x>` `--data-dir=<dir>`\n"
-		"    `--checkpoint=<file>` `--resume=<file>` (`-spp` is then the total) `--noise-target=<x> --max-samples=<n> [--noise-step=<s>]`\n");
+		"    `--checkpoint=<file>` `--resume=<file>` (`-spp` is then the total) `--noise-target=<x> --max-samples=<n> [--noise-step=<s>]`\n"
+		"    `--spectral-output=<file.npy>` [`--spectral-bins=<n>`: 4, 8, ..., 64; default 16] (not with `--resume`)\n");
 }
 
 struct ArgList {
@@ -80,6 +83,8 @@ struct Progressive { // the flags of the progressive modes
 	std::string checkpoint, resume;
 	double noise_target = -1.0; // < 0: none
 	size_t max_samples = 0, noise_step = 16;
+	std::string spectral_output; // --spectral-output: "" = none
+	size_t spectral_bins = 16;
 };
 
 void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progressive* g) {
@@ -137,6 +142,19 @@ void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progress
 	}
 	if (g->noise_target >= 0.0 && g->max_samples == 0) { std::fprintf(stderr, "`--noise-target` needs `--max-samples=<n>`!\n"); throw -2; }
 	if (g->noise_target >= 0.0 && !g->resume.empty()) { std::fprintf(stderr, "`--noise-target` cannot be combined with `--resume`!\n"); throw -2; }
+	if (a.take("--spectral-output", "", &v)) g->spectral_output = v;
+	if (a.take("--spectral-bins", "", &v)) {
+		try { g->spectral_bins = to_pos(v); } catch (int) { g->spectral_bins = 0; }
+		if (g->spectral_bins == 0 || g->spectral_bins > 64 || g->spectral_bins % 4) { std::fprintf(stderr, "Invalid value for --spectral-bins (a multiple of 4 up to 64)!\n"); throw -2; }
+	}
+	if (!g->spectral_output.empty() && !g->resume.empty()) {
+		std::fprintf(stderr, "`--spectral-output` cannot be combined with `--resume`: a checkpoint holds the pixel sums only, not the wavelength bins of the samples behind them!\n");
+		throw -2;
+	}
+	if (!g->spectral_output.empty() && (o->tile_major || o->rgb_mode || o->libm != SSX_LIBM_BUILD)) {
+		std::fprintf(stderr, "`--spectral-output` cannot be combined with `--tile-major`, `--rgb` or `--libm=glibc-2.35`!\n");
+		throw -2;
+	}
 	if (a.take("--texture", "", &v)) o->texture_path = v;
 	if (a.take("--data-dir", "", &v)) o->data_dir = v;
 	if (a.args.size() > 1) {
@@ -166,6 +184,7 @@ int main(int argc, char* argv[]) {
 	try {
 		ssx::Renderer renderer(options);
 		std::signal(SIGINT, on_sigint);
+		if (!prog.spectral_output.empty()) renderer.set_spectral_bins(prog.spectral_bins);
 		bool stop_sent = false;
 		if (prog.noise_target >= 0.0) {
 			const auto r = renderer.render_until(prog.noise_target, prog.noise_step, prog.max_samples, [&]() {
@@ -196,6 +215,7 @@ int main(int argc, char* argv[]) {
 		// laggards finish the launches the others had done), so that the image written now is the one the checkpoint resumes from.
 		if (!prog.checkpoint.empty()) renderer.level_devices();
 		renderer.render_wait();
+		if (!prog.spectral_output.empty()) renderer.save_spectral_image(prog.spectral_output);
 		if (!prog.checkpoint.empty()) renderer.save_checkpoint(prog.checkpoint);
 	} catch (const ssx::HostError& e) {
 		std::fprintf(stderr, "%s\n", e.message.c_str());

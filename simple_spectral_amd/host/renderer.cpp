@@ -48,6 +48,8 @@ struct Renderer::Api {
 	int (*sums_import)(ssx_ctx*, const ssx_render_params*, const ssx_sums_info_t*, const double*, const double*) = nullptr;
 	int (*set_noise_estimate)(ssx_ctx*, int) = nullptr;
 	int (*noise_info)(ssx_ctx*, double*, double*) = nullptr;
+	int (*set_spectral_bins)(ssx_ctx*, uint32_t) = nullptr;
+	int (*spectral_read)(ssx_ctx*, ssx_spectral_info_t*, float*, double*, uint32_t*) = nullptr;
 
 	explicit Api(const std::string& path) {
 		handle = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
@@ -81,6 +83,8 @@ struct Renderer::Api {
 		sums_import = reinterpret_cast<decltype(sums_import)>(sym("ssx_sums_import"));
 		set_noise_estimate = reinterpret_cast<decltype(set_noise_estimate)>(sym("ssx_set_noise_estimate"));
 		noise_info = reinterpret_cast<decltype(noise_info)>(sym("ssx_noise_info"));
+		set_spectral_bins = reinterpret_cast<decltype(set_spectral_bins)>(sym("ssx_set_spectral_bins"));
+		spectral_read = reinterpret_cast<decltype(spectral_read)>(sym("ssx_spectral_read"));
 	}
 	~Api() { if (handle) dlclose(handle); }
 };
@@ -258,6 +262,44 @@ double Renderer::noise(std::vector<double>* v_map) {
 		if (v_map) for (size_t p = 0; p < pixels; ++p) (*v_map)[p] += v[p];
 	}
 	return std::sqrt(total[0] / total[2]) / (total[1] / total[2]);
+}
+
+void Renderer::set_spectral_bins(size_t bins) {
+	wait_workers_();
+	for (ssx_ctx* c : ctxs_) check_(api_->set_spectral_bins(c, static_cast<uint32_t>(bins)), "ssx_set_spectral_bins", c);
+	spectral_bins_ = bins;
+}
+
+void Renderer::spectral_image(std::vector<float>* mean, std::vector<uint32_t>* counts, std::vector<float>* centres) {
+	wait_workers_();
+	if (!spectral_bins_) throw HostError{ SSX_ERR_STATE, "spectral_image: spectral output is off (set_spectral_bins)" };
+	const size_t W = options.res[0], H = options.res[1], B = spectral_bins_, M = B / 4, n = ctxs_.size();
+	if (mean) mean->assign(W * H * B, 0.0f);
+	if (counts) counts->assign(W * H * M, 0u);
+	std::vector<float> part(mean ? W * H * B : 0);
+	std::vector<uint32_t> part_n(counts ? W * H * M : 0);
+	const size_t skew = params_for_(0, 1, 0).tile_skew; // (what the devices rendered with)
+	for (size_t d = 0; d < n; ++d) { // every pixel from the device that owns it, bit for bit (a merge by ownership mask, like sums_merge)
+		ssx_spectral_info_t info{};
+		check_(api_->spectral_read(ctxs_[d], &info, mean ? part.data() : nullptr, nullptr, counts ? part_n.data() : nullptr), "ssx_spectral_read", ctxs_[d]);
+		if (d == 0 && centres) {
+			centres->resize(B);
+			for (size_t b = 0; b < B; ++b) (*centres)[b] = info.lambda_min + (static_cast<float>(b) + 0.5f) * info.bin_width;
+		}
+		for (size_t j = 0; j < H; ++j) for (size_t i = 0; i < W; ++i) {
+			if (shared_tile(W, skew, i, j) % n != d) continue;
+			const size_t p = j * W + i;
+			if (mean) std::memcpy(&(*mean)[p * B], &part[p * B], B * sizeof(float));
+			if (counts) std::memcpy(&(*counts)[p * M], &part_n[p * M], M * sizeof(uint32_t));
+		}
+	}
+}
+
+void Renderer::save_spectral_image(const std::string& path) {
+	std::vector<float> mean;
+	spectral_image(&mean);
+	const size_t shape[3] = { options.res[1], options.res[0], spectral_bins_ };
+	save_npy_f32(path, mean.data(), shape, 3);
 }
 
 std::pair<size_t, double> Renderer::render_until(double target, size_t step, size_t max_spp, const std::function<bool()>& tick) {

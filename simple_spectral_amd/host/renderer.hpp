@@ -95,6 +95,14 @@ public:
 	// and stops the render by returning true.  The decision reads only the sums: the same call gives the same count.  Then render_wait().
 	std::pair<size_t, double> render_until(double target, size_t step, size_t max_spp, const std::function<bool()>& tick = {});
 
+	// Spectral radiance output (include/ssx.h ssx_set_spectral_bins): `bins` wavelength bins per pixel (a multiple of 4 up to 64; 0 = off) on every
+	// device, for the renders that follow.  Not while rendering.
+	void set_spectral_bins(size_t bins);
+	// The bins of the last render, the devices' shares combined by ownership mask: mean [height][width][bins] (row 0 = bottom), counts
+	// [height][width][bins / 4] (optional), centres [bins] (optional): lambda_min + (b + 0.5) * bin_width in binary32.  After render_wait().
+	void spectral_image(std::vector<float>* mean, std::vector<uint32_t>* counts = nullptr, std::vector<float>* centres = nullptr);
+	void save_spectral_image(const std::string& path); // spectral_image's mean as a .npy file (image_io.hpp save_npy_f32)
+
 private:
 	struct Api;
 	std::unique_ptr<Api> api_;
@@ -102,6 +110,7 @@ private:
 	std::chrono::steady_clock::time_point time_start_;
 	bool started_ = false;
 	bool need_join_ = false;    // a worker of every context is running or waits to be joined
+	size_t spectral_bins_ = 0;
 	size_t expected_spp_ = 0;   // the count the running (or last) call renders to: what render_wait compares ssx_done_spp with
 	ssx_render_params params_for_(size_t d, size_t spp, size_t spp_per_launch) const;
 	void start_(size_t spp, size_t spp_per_launch);

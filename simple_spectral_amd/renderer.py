@@ -149,6 +149,24 @@ class Scene:
             pass
 
 
+def spectral_bin_index(lambda_0, lambda_min, lambda_step, bins):
+    """The m of include/ssx.h's spectral output for first hero wavelengths lambda_0 (float32 array or scalar): component i of the sample falls
+    into bin i * M + m, M = bins / 4.  t = (lambda_0 - lambda_min) / lambda_step and t * M in binary32, truncated, clamped to M - 1."""
+    M = np.float32(bins // 4)
+    t = (np.asarray(lambda_0, dtype=np.float32) - np.float32(lambda_min)) / np.float32(lambda_step)
+    return np.minimum((t * M).astype(np.uint32), np.uint32(bins // 4 - 1))
+
+
+def save_npy(path, array):
+    """ssh_save_npy_f32 (libssx_host.so): `array` as a float32 .npy file, the writer the CLI's --spectral-output uses."""
+    a = np.ascontiguousarray(array, dtype=np.float32)
+    shape = (C.c_uint32 * a.ndim)(*a.shape)
+    host = _capi.host_lib()
+    rc = host.ssh_save_npy_f32(os.fsencode(path), a.ctypes.data, shape, a.ndim)
+    if rc != 0:
+        raise SsxError(rc, host.ssh_last_error().decode())
+
+
 def load_checkpoint_file(path):
     """ssh_checkpoint_load -> (SsxSumsInfo, sums [H, W, 4], S2 [H, W] or None, scene name, options text)."""
     host = _capi.host_lib()
@@ -332,6 +350,38 @@ class Renderer:
             if level <= target:
                 break
         return self.done_spp(), level
+
+    # ---- spectral radiance output (include/ssx.h: per-pixel wavelength bins) ----
+
+    def set_spectral_bins(self, n):
+        """ssx_set_spectral_bins: n wavelength bins per pixel (a multiple of 4 up to 64) for the renders that follow; 0 switches it off."""
+        self._check(self._lib.ssx_set_spectral_bins(self._ctx, int(n)))
+
+    def spectral_read(self, sums=False):
+        """ssx_spectral_read -> (SsxSpectralInfo, mean float32 [H, W, B], counts uint32 [H, W, B/4], sums float64 [H, W, B] or None)."""
+        info = _capi.SsxSpectralInfo()
+        self._check(self._lib.ssx_spectral_read(self._ctx, C.byref(info), None, None, None))
+        H, W, B = info.height, info.width, info.bins
+        mean = np.zeros((H, W, B), dtype=np.float32)
+        counts = np.zeros((H, W, B // 4), dtype=np.uint32)
+        s = np.zeros((H, W, B), dtype=np.float64) if sums else None
+        self._check(self._lib.ssx_spectral_read(self._ctx, C.byref(info), mean.ctypes.data, None if s is None else s.ctypes.data, counts.ctypes.data))
+        return info, mean, counts, s
+
+    def spectral_image(self):
+        """(mean [H, W, B] float32, counts [H, W, B/4] uint32, centres [B] float32) of the last render: mean[j, i, b] is the mean flux of the samples of
+        pixel (i, j) (row 0 = bottom) whose wavelength fell into bin b, centres[b] = lambda_min + (b + 0.5) * bin_width the bin's middle wavelength."""
+        info, mean, counts, _ = self.spectral_read()
+        centres = np.float32(info.lambda_min) + (np.arange(info.bins, dtype=np.float32) + np.float32(0.5)) * np.float32(info.bin_width)
+        return mean, counts, centres.astype(np.float32)
+
+    def debug_sample_flux(self, **over):
+        """ssx_debug_sample_flux (spectral output on): per-sample (flux [H, W, spp, 4] float32, lambda_0 [H, W, spp] float32)."""
+        p = self.params(**over)
+        flux = np.zeros((p.height, p.width, p.spp, 4), dtype=np.float32)
+        lambda_0 = np.zeros((p.height, p.width, p.spp), dtype=np.float32)
+        self._check(self._lib.ssx_debug_sample_flux(self._ctx, C.byref(p), flux.ctypes.data, lambda_0.ctypes.data))
+        return flux, lambda_0
 
     def render_device(self, d_ptr, stream=0, **over):
         """Enqueue the render on `stream` into the device buffer at d_ptr (W*H float4)."""
