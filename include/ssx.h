@@ -33,7 +33,7 @@ extern "C" {
  *      ssx_jit_counters, ssx_sums_info, ssx_rccl_groups_made, ssx_done_tiles and ssx_render_params.tile_major and tile_skew (the
  *      struct grew by 8 bytes) are new.  Added since without a change of existing entry points or structures (same version): ssx_units_info,
  *      ssx_rccl_probe (round 6); ssx_render_params.libm, appended (a caller with the struct_size before it gets SSX_LIBM_BUILD); the progressive
- *      rendering and spectral output entry points below. */
+ *      rendering, spectral output and denoising entry points below. */
 #define SSX_ABI_VERSION 2
 
 enum {
@@ -445,6 +445,62 @@ typedef struct ssx_spectral_info_t {
 /* Row-major (row 0 = bottom) mean [height][width][B] (float), sums [height][width][B] (the binary64 accumulators S) and counts [height][width][M];
  * any of the three may be NULL.  info is filled.  SSX_ERR_STATE: spectral output is off, a render runs, or the context holds no valid bins. */
 int ssx_spectral_read(ssx_ctx* ctx, ssx_spectral_info_t* info, float* mean, double* sums, uint32_t* counts);
+
+/* ---- Denoising: first-hit guide buffers and a variance-guided a-trous filter (appended; same ABI version) -----------------------------------
+ * The definitions are this library's (the reference has nothing like them).  Unless said otherwise everything is binary32 with IEEE + - * / and sqrtf,
+ * no contraction, no transcendental, operations in the order written: a restatement in numpy gives the same bits (tests/denoise_ref.py).
+ *
+ * GUIDE BUFFERS, for every pixel (i, j) of a width x height image; they do not depend on ownership, seed or spp.  One camera ray through the pixel
+ * centre -- camera_dir at ((double)i + 0.5, (double)j + 0.5), normalised and rounded to float exactly as a sample's ray is, no random number -- is
+ * traced by the device function behind SSX_DBG_TRACE with no quad ignored:
+ *     prim    uint32: the primitive's index, 0xFFFFFFFF for a miss
+ *     depth   the hit distance, 0.0f for a miss
+ *     normal  [3]: the hit triangle's stored normal (ssx_quad.normal0 / normal1), zeros for a miss
+ *     albedo  [4]: what the device function behind SSX_DBG_ALBEDO returns for (prim, st of the hit, lambda_g), zeros for a miss; emission is no part of it.
+ *             lambda_g = lambda_min + 0.5f * lambda_step; in SSX_MODE_RGB lambda_g = 0 (the components are then r, g, b, 0)
+ *
+ * VARIANCE IN IMAGE UNITS.  var[p] = (float)(v[p] * (s * s)), the product in binary64, with v what ssx_noise_info returns per pixel and s the factor the
+ * image applies to the mean of the sums: 1000, or 1 in SSX_MODE_RGB.
+ *
+ * FILTER.  Parameters: levels L in 1..6, sigma_l > 0, sigma_a > 0.  Inputs per pixel: c = (X, Y, Z, A), var (>= 0 where finite), prim, albedo[4].
+ * valid(p): X, Y, Z and var are all finite.  h = {1/16, 1/4, 3/8, 1/4, 1/16}; inv_sa2 = 1.0f / (sigma_a * sigma_a).  Levels l = 0 .. L-1 with step
+ * st = 2^l, each reading the previous level's c and var.  An invalid p keeps its c and var at every level.  For a valid p:
+ *     g   = sum k3*var[q] / sum k3 over the 3x3 neighbours q at distance 1 (not st) that are inside the image and valid, k3 = {1,2,1} x {1,2,1},
+ *           both sums accumulated row-major (dy outer, dx inner, ascending), centre included
+ *     den = sigma_l * sqrtf(g) + 1e-6f
+ *     sw = 0, sc = (0,0,0), sv = 0
+ *     for dy in -2..2, dx in -2..2 (row-major), q = p + st*(dx,dy); skip q outside the image, invalid, or with prim[q] != prim[p]:
+ *         k   = h[dy+2] * h[dx+2]
+ *         x   = fabsf(Y[q] - Y[p]) / den;                    wl = 1.0f / (1.0f + x*x)
+ *         d_i = albedo[q][i] - albedo[p][i];   da2 = ((d0*d0 + d1*d1) + d2*d2) + d3*d3;   wa = 1.0f / (1.0f + da2*inv_sa2)
+ *         w   = (k * wl) * wa
+ *         sw += w;   sc.xyz += w * c[q].xyz;   sv += (w*w) * var[q]
+ *     c'[p].xyz = sc.xyz / sw;   c'[p].w = c[p].w;   var'[p] = sv / (sw*sw)
+ * The centre tap always counts (sw >= 9/64); the misses form one "primitive"; the primitives are planar, so "same primitive" is an exact geometric edge
+ * stop.  The weights are rational on purpose: the definition is reproducible bit for bit.  (The ideas are those of Dammertz et al. 2010 and Schied et al.
+ * 2017; Y is component 1, i.e. G in SSX_MODE_RGB.) */
+
+/* The guide buffers of the uploaded scene, row-major (row 0 = bottom): prim [height][width], depth [height][width], normal [height][width][3], albedo
+ * [height][width][4]; any pointer may be NULL.  Computed by one kernel (one lane per pixel) and kept on the device per (scene upload, width, height).
+ * SSX_ERR_STATE: no scene, or a render runs. */
+int ssx_guides(ssx_ctx* ctx, uint32_t width, uint32_t height, uint32_t* prim, float* depth, float* normal, float* albedo);
+typedef struct ssx_denoise_params {
+	uint32_t struct_size;  /* sizeof(ssx_denoise_params) */
+	uint32_t levels;       /* L, 1..6 */
+	float sigma_l, sigma_a;
+} ssx_denoise_params;      /* NULL where one is expected: levels 5, sigma_l 1.0, sigma_a 0.1 (chosen on CPU renders: DESIGN.md section 12; Schied et al. publish sigma_l = 4) */
+/* The filter as a pure function of its arguments (one kernel launch per level on ctx's device; needs no scene): xyza [height][width][4], var and prim
+ * [height][width], albedo [height][width][4] -> xyza_out, var_out (may be NULL).  SSX_ERR_ARG: levels outside 1..6, a sigma that is not finite and
+ * positive, a NULL input. */
+int ssx_denoise_images(ssx_ctx* ctx, const ssx_denoise_params* params, uint32_t width, uint32_t height, const float* xyza, const float* var,
+                       const uint32_t* prim, const float* albedo, float* xyza_out, float* var_out);
+/* The same from the context's own state, without leaving the device: the image of the sums (what ssx_read_framebuffer returns), the variance in image units
+ * from the noise estimate, the guide buffers of the scene.  xyza_out [height][width][4] and var_out [height][width] of the render's size; either may be NULL.
+ * It reads only -- sums, image, noise and spectral state stay as they are, so an ssx_render_continue afterwards leaves the bits of a one-shot render -- and
+ * works in SSX_MODE_RGB and with either libm.  SSX_ERR_STATE, with the reason in ssx_last_error: no scene, a render runs, no continuable sums, the noise
+ * estimate off or with fewer than two batches, or a context that owns only part of the image (tile_stride != 1: combine the ranks' images and v by
+ * ownership and call ssx_denoise_images).  SSX_ERR_ARG: as above. */
+int ssx_denoise(ssx_ctx* ctx, const ssx_denoise_params* params, float* xyza_out, float* var_out);
 
 /* ---- Diagnostics for the parity tests (not part of the reference's interface) ---------------------
  * ssx_debug_eval runs one building block of the path kernel -- the same device function the kernel

@@ -3,7 +3,8 @@
 // entry point either drives the HIP kernels or returns an error.
 // The context, its launches, the render worker (render_sample_walk / render_tile_walk behind start_worker), the render entry points and the
 // diagnostics are here; scene packing is in ssx_pack.h, RCCL in ssx_rccl.h, the pixel ownership rule in ssx_pixel_grid.h, continue / export /
-// import of the sums and the noise estimate (entry points and their kernels) in ssx_progressive.hip, the spectral output in ssx_spectral.hip.
+// import of the sums and the noise estimate (entry points and their kernels) in ssx_progressive.hip, the spectral output in ssx_spectral.hip,
+// the guide buffers and the denoising filter in ssx_denoise.hip.
 #include "ssx_kernels.hip"
 #include "ssx_debug.hip"
 
@@ -140,6 +141,10 @@ struct ssx_ctx {
 	DeviceBuffer d_spectral_sums, d_spectral_counts;
 	std::string spectral_note;          // why sums that can be continued come without spectral state (ssx_spectral_read says it)
 	float lambda_min = 0.0f, lambda_step = 0.0f; // of the uploaded scene
+	// denoising (csrc/ssx_denoise.hip): nothing is allocated until ssx_guides / ssx_denoise / ssx_denoise_images is called.  d_guides holds the guide buffers of
+	// the uploaded scene at guides_width x guides_height (0: none; ssx_upload_scene drops them), d_denoise the filter's inputs and ping-pong buffers.
+	DeviceBuffer d_guides, d_denoise;
+	uint32_t guides_width = 0, guides_height = 0;
 
 	// optional per-kernel timing (ssx_set_timing): events around each stage of each batch
 	bool timing = false;
@@ -946,6 +951,7 @@ int ssx_upload_scene(ssx_ctx* ctx, const ssx_scene_desc* s) {
 	ctx->d_textures.clear();
 	ctx->have_scene = false;
 	sums_invalidate(ctx); ctx->scene_digest = 0;
+	ctx->guides_width = ctx->guides_height = 0; // (the guide buffers were the last scene's)
 	for (uint32_t i = 0; i < s->n_textures && i < SSX_MAX_TEXTURES; ++i) {
 		const ssx_texture& t = s->textures[i];
 		if (!t.rgb || t.width == 0 || t.height == 0) return fail(ctx, SSX_ERR_DATA, "Could not load texture"); // material.cpp:15-18
@@ -1418,3 +1424,4 @@ int ssx_kernel_info(ssx_ctx* ctx, int* vgprs, int* sgprs, int* lds_bytes, int* s
 
 #include "ssx_progressive.hip"
 #include "ssx_spectral.hip"
+#include "ssx_denoise.hip"

@@ -9,6 +9,10 @@
 // --noise-target=X --max-samples=N [--noise-step=S] renders in steps of S samples until the noise estimate falls to X or N samples are done.
 // Spectral output: --spectral-output=PATH.npy [--spectral-bins=N, default 16] also writes the per-pixel wavelength bins (include/ssx.h), a NumPy file of
 // shape (height, width, N), row 0 = bottom, after the image.  Not with --resume (a checkpoint carries no bins), --tile-major, --rgb or --libm=glibc-2.35.
+// Denoising: --denoise [--denoise-levels=N, 1..6, default 5] [--denoise-sigma=L,A, default 1,0.1] writes the image filtered by the variance-guided a-trous filter
+// of include/ssx.h to --output instead of the plain one.  It switches the noise estimate on and renders in launches of --noise-step samples (ceil(spp / 8) when
+// that is not given), so that the estimate has its two batches; not with -spp=1 or --tile-major.  --guides-output=PATH.npy writes the first-hit guide buffers,
+// float32 (height, width, 9) = {primitive (-1: none), depth, normal xyz, albedo 0..3}, row 0 = bottom.
 #include "renderer.hpp"
 
 #include <chrono>
@@ -41,7 +45,9 @@ void print_usage() {
 		"    `--gpus=<n>` `--seed=<n>` `--observer=1931|2006` `--uplift=ours|meng|jh` `--jh-coeff=<file>` `--meng-grid=<file>` `--rgb` `--no-explicit-light-sampling` `--no-flat-field-correction` `--tile-major` `--reduce=peer|rccl` `--libm=build|glibc-2.35`\n"
 		"    `--texture=<png>` `--light-scale=<x>` `--data-dir=<dir>`\n"
 		"    `--checkpoint=<file>` `--resume=<file>` (`-spp` is then the total) `--noise-target=<x> --max-samples=<n> [--noise-step=<s>]`\n"
-		"    `--spectral-output=<file.npy>` [`--spectral-bins=<n>`: 4, 8, ..., 64; default 16] (not with `--resume`)\n");
+		"    `--spectral-output=<file.npy>` [`--spectral-bins=<n>`: 4, 8, ..., 64; default 16] (not with `--resume`)\n"
+		"    `--denoise` [`--denoise-levels=<n>`: 1..6; default 5] [`--denoise-sigma=<l>,<a>`; default 1,0.1] (the output image is the filtered one; not with `-spp=1`)\n"
+		"    `--guides-output=<file.npy>` (first hit per pixel: primitive, depth, normal, albedo)\n");
 }
 
 struct ArgList {
@@ -85,6 +91,10 @@ struct Progressive { // the flags of the progressive modes
 	size_t max_samples = 0, noise_step = 16;
 	std::string spectral_output; // --spectral-output: "" = none
 	size_t spectral_bins = 16;
+	bool denoise = false;        // --denoise
+	bool noise_step_given = false;
+	ssx::Renderer::DenoiseParams denoise_params;
+	std::string guides_output;   // --guides-output: "" = none
 };
 
 void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progressive* g) {
@@ -134,7 +144,7 @@ void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progress
 	try {
 		if (a.take("--noise-target", "", &v)) { size_t used = 0; g->noise_target = std::stod(v, &used); if (used != v.size() || !(g->noise_target >= 0.0)) throw -2; }
 		if (a.take("--max-samples", "", &v)) g->max_samples = to_pos(v);
-		if (a.take("--noise-step", "", &v)) g->noise_step = to_pos(v);
+		if (a.take("--noise-step", "", &v)) { g->noise_step = to_pos(v); g->noise_step_given = true; }
 	} catch (...) { std::fprintf(stderr, "Invalid value for --noise-target/--max-samples/--noise-step!\n"); throw -2; }
 	if (o->tile_major && (!g->resume.empty() || !g->checkpoint.empty() || g->noise_target >= 0.0)) {
 		std::fprintf(stderr, "`--resume`, `--checkpoint` and `--noise-target` cannot be combined with `--tile-major`: only a render that walks through the samples can be continued!\n");
@@ -155,6 +165,35 @@ void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progress
 		std::fprintf(stderr, "`--spectral-output` cannot be combined with `--tile-major`, `--rgb` or `--libm=glibc-2.35`!\n");
 		throw -2;
 	}
+	if (a.take("--denoise", "", &v)) {
+		if (v != "--denoise") { std::fprintf(stderr, "`--denoise` does not take a value!\n"); throw -2; }
+		g->denoise = true;
+	}
+	if (a.take("--denoise-levels", "", &v)) {
+		unsigned n = 0;
+		try { n = to_pos(v); } catch (int) { n = 0; }
+		if (n < 1 || n > 6) { std::fprintf(stderr, "Invalid value for --denoise-levels (1..6)!\n"); throw -2; }
+		g->denoise_params.levels = n;
+	}
+	if (a.take("--denoise-sigma", "", &v)) {
+		bool ok = false;
+		try {
+			const size_t comma = v.find(',');
+			if (comma != std::string::npos) {
+				size_t u0 = 0, u1 = 0;
+				const std::string l = v.substr(0, comma), s2 = v.substr(comma + 1);
+				g->denoise_params.sigma_l = std::stof(l, &u0); g->denoise_params.sigma_a = std::stof(s2, &u1);
+				ok = u0 == l.size() && u1 == s2.size() && g->denoise_params.sigma_l > 0.0f && g->denoise_params.sigma_a > 0.0f &&
+				     g->denoise_params.sigma_l < 1e30f && g->denoise_params.sigma_a < 1e30f;
+			}
+		} catch (...) { ok = false; }
+		if (!ok) { std::fprintf(stderr, "Invalid value for --denoise-sigma (<l>,<a>, both positive)!\n"); throw -2; }
+	}
+	if (g->denoise && o->spp < 2) { std::fprintf(stderr, "`--denoise` needs at least two samples per pixel: its variance estimate compares batches of samples!\n"); throw -2; }
+	if (g->denoise && o->tile_major) { std::fprintf(stderr, "`--denoise` cannot be combined with `--tile-major`: only a render that walks through the samples takes batches!\n"); throw -2; }
+	if (g->denoise) o->spp_per_launch = g->noise_step_given ? g->noise_step : (o->spp + 7) / 8; // at least two launches = two batches
+	if (g->denoise && o->spp_per_launch >= o->spp) { std::fprintf(stderr, "`--denoise` needs `--noise-step` below the number of samples (two batches at least)!\n"); throw -2; }
+	if (a.take("--guides-output", "", &v)) g->guides_output = v;
 	if (a.take("--texture", "", &v)) o->texture_path = v;
 	if (a.take("--data-dir", "", &v)) o->data_dir = v;
 	if (a.args.size() > 1) {
@@ -182,8 +221,11 @@ int main(int argc, char* argv[]) {
 		return -1;
 	}
 	try {
+		const std::string denoised_path = options.output_path;
+		if (prog.denoise) options.output_path.clear(); // (render_wait writes the plain image there; the filtered one is written below)
 		ssx::Renderer renderer(options);
 		std::signal(SIGINT, on_sigint);
+		if (prog.denoise) renderer.set_noise_estimate(true);
 		if (!prog.spectral_output.empty()) renderer.set_spectral_bins(prog.spectral_bins);
 		bool stop_sent = false;
 		if (prog.noise_target >= 0.0) {
@@ -215,6 +257,8 @@ int main(int argc, char* argv[]) {
 		// laggards finish the launches the others had done), so that the image written now is the one the checkpoint resumes from.
 		if (!prog.checkpoint.empty()) renderer.level_devices();
 		renderer.render_wait();
+		if (prog.denoise) renderer.denoise(prog.denoise_params).save(denoised_path);
+		if (!prog.guides_output.empty()) renderer.save_guides(prog.guides_output);
 		if (!prog.spectral_output.empty()) renderer.save_spectral_image(prog.spectral_output);
 		if (!prog.checkpoint.empty()) renderer.save_checkpoint(prog.checkpoint);
 	} catch (const ssx::HostError& e) {

@@ -50,6 +50,9 @@ struct Renderer::Api {
 	int (*noise_info)(ssx_ctx*, double*, double*) = nullptr;
 	int (*set_spectral_bins)(ssx_ctx*, uint32_t) = nullptr;
 	int (*spectral_read)(ssx_ctx*, ssx_spectral_info_t*, float*, double*, uint32_t*) = nullptr;
+	int (*guides)(ssx_ctx*, uint32_t, uint32_t, uint32_t*, float*, float*, float*) = nullptr;
+	int (*denoise_images)(ssx_ctx*, const ssx_denoise_params*, uint32_t, uint32_t, const float*, const float*, const uint32_t*, const float*, float*, float*) = nullptr;
+	int (*denoise)(ssx_ctx*, const ssx_denoise_params*, float*, float*) = nullptr;
 
 	explicit Api(const std::string& path) {
 		handle = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
@@ -85,6 +88,9 @@ struct Renderer::Api {
 		noise_info = reinterpret_cast<decltype(noise_info)>(sym("ssx_noise_info"));
 		set_spectral_bins = reinterpret_cast<decltype(set_spectral_bins)>(sym("ssx_set_spectral_bins"));
 		spectral_read = reinterpret_cast<decltype(spectral_read)>(sym("ssx_spectral_read"));
+		guides = reinterpret_cast<decltype(guides)>(sym("ssx_guides"));
+		denoise_images = reinterpret_cast<decltype(denoise_images)>(sym("ssx_denoise_images"));
+		denoise = reinterpret_cast<decltype(denoise)>(sym("ssx_denoise"));
 	}
 	~Api() { if (handle) dlclose(handle); }
 };
@@ -191,7 +197,7 @@ void Renderer::start_(size_t spp, size_t spp_per_launch) {
 	expected_spp_ = spp;
 }
 
-void Renderer::render_start() { start_(options.spp, 0); }
+void Renderer::render_start() { start_(options.spp, options.spp_per_launch); }
 
 // Starts ssx_render_continue on every (context, samples more) pair; should one refuse, the ones already started are stopped and joined
 // before the error leaves (no worker is left behind unjoined).
@@ -300,6 +306,57 @@ void Renderer::save_spectral_image(const std::string& path) {
 	spectral_image(&mean);
 	const size_t shape[3] = { options.res[1], options.res[0], spectral_bins_ };
 	save_npy_f32(path, mean.data(), shape, 3);
+}
+
+Renderer::Guides Renderer::guides() {
+	wait_workers_();
+	const size_t W = options.res[0], H = options.res[1];
+	Guides g;
+	g.prim.assign(W * H, 0u); g.depth.assign(W * H, 0.0f); g.normal.assign(W * H * 3, 0.0f); g.albedo.assign(W * H * 4, 0.0f);
+	check_(api_->guides(ctxs_[0], static_cast<uint32_t>(W), static_cast<uint32_t>(H), g.prim.data(), g.depth.data(), g.normal.data(), g.albedo.data()), "ssx_guides", ctxs_[0]);
+	return g;
+}
+
+void Renderer::save_guides(const std::string& path) {
+	const Guides g = guides();
+	const size_t pixels = options.res[0] * options.res[1];
+	std::vector<float> all(pixels * 9);
+	for (size_t p = 0; p < pixels; ++p) {
+		float* o = &all[p * 9];
+		o[0] = g.prim[p] == 0xFFFFFFFFu ? -1.0f : static_cast<float>(g.prim[p]);
+		o[1] = g.depth[p];
+		std::memcpy(o + 2, &g.normal[p * 3], 3 * sizeof(float));
+		std::memcpy(o + 5, &g.albedo[p * 4], 4 * sizeof(float));
+	}
+	const size_t shape[3] = { options.res[1], options.res[0], 9 };
+	save_npy_f32(path, all.data(), shape, 3);
+}
+
+Framebuffer Renderer::denoise(const DenoiseParams& params, std::vector<float>* xyza_out) {
+	wait_workers_();
+	const size_t W = options.res[0], H = options.res[1], pixels = W * H;
+	ssx_denoise_params dp{};
+	dp.struct_size = sizeof dp; dp.levels = params.levels; dp.sigma_l = params.sigma_l; dp.sigma_a = params.sigma_a;
+	std::vector<float> out(pixels * 4);
+	ssx_ctx* root = ctxs_[0];
+	if (ctxs_.size() == 1) check_(api_->denoise(root, &dp, out.data(), nullptr), "ssx_denoise", root);
+	else {
+		// every device holds its own tiles: the image was combined by render_wait (xyza), the variances are combined here (each pixel's v is nonzero on its
+		// owner alone), the guides do not depend on ownership.  var = (float)(v * (s * s)) in binary64, s = what the image multiplies the mean by.
+		level_devices(); // (a stopped render: one sample count behind every pixel's v)
+		std::vector<double> v;
+		(void)noise(&v);
+		const double s = options.rgb_mode ? 1.0 : 1000.0;
+		std::vector<float> var(pixels);
+		for (size_t p = 0; p < pixels; ++p) var[p] = static_cast<float>(v[p] * (s * s));
+		const Guides g = guides();
+		check_(api_->denoise_images(root, &dp, static_cast<uint32_t>(W), static_cast<uint32_t>(H), xyza.data(), var.data(), g.prim.data(), g.albedo.data(), out.data(), nullptr),
+		       "ssx_denoise_images", root);
+	}
+	Framebuffer fb(options.res);
+	color->xyza_to_srgba(out.data(), fb.data(), pixels);
+	if (xyza_out) xyza_out->swap(out);
+	return fb;
 }
 
 std::pair<size_t, double> Renderer::render_until(double target, size_t step, size_t max_spp, const std::function<bool()>& tick) {

@@ -56,6 +56,7 @@ public:
 		std::string jh_coeff_path;   // default data/jakob-and-hanika-2019-srgb.coeff (src/util/color.cpp:144); fitted and written when absent
 		std::string data_dir = "data"; // CWD-relative like the reference's paths
 		std::string hip_library;     // default: libssx_hip.so next to libssx_host.so
+		size_t spp_per_launch = 0;   // render_start: samples per pixel of one launch (0: the library's choice); one launch is one batch of the noise estimate
 	};
 	const Options options;
 	Framebuffer framebuffer;
@@ -102,6 +103,17 @@ public:
 	// [height][width][bins / 4] (optional), centres [bins] (optional): lambda_min + (b + 0.5) * bin_width in binary32.  After render_wait().
 	void spectral_image(std::vector<float>* mean, std::vector<uint32_t>* counts = nullptr, std::vector<float>* centres = nullptr);
 	void save_spectral_image(const std::string& path); // spectral_image's mean as a .npy file (image_io.hpp save_npy_f32)
+
+
+	// Denoising (include/ssx.h: first-hit guide buffers and the variance-guided a-trous filter).
+	struct Guides { std::vector<uint32_t> prim; std::vector<float> depth, normal, albedo; }; // [height][width] x {1, 1, 3, 4}, row 0 = bottom; prim 0xFFFFFFFF = miss
+	Guides guides();                                  // ssx_guides of device 0 at the options' resolution (they depend on the scene and the size only)
+	void save_guides(const std::string& path);        // float32 [height][width][9] = {prim (-1: miss), depth, normal xyz, albedo 0..3} as a .npy file
+	struct DenoiseParams { uint32_t levels = 5; float sigma_l = 1.0f, sigma_a = 0.1f; };
+	// The image of the render so far, filtered.  Needs set_noise_estimate(true) before a render of at least two launches; after render_wait().  One device:
+	// ssx_denoise, all on the device.  Several: the devices' images and variances combined by ownership (render_wait, noise), then ssx_denoise_images on
+	// device 0 -- the same bits.  xyza_out (optional): the filtered XYZ + alpha behind the returned sRGB framebuffer.  Nothing the devices hold changes.
+	Framebuffer denoise(const DenoiseParams& params, std::vector<float>* xyza_out = nullptr);
 
 private:
 	struct Api;

@@ -375,6 +375,54 @@ class Renderer:
         centres = np.float32(info.lambda_min) + (np.arange(info.bins, dtype=np.float32) + np.float32(0.5)) * np.float32(info.bin_width)
         return mean, counts, centres.astype(np.float32)
 
+    # ---- denoising (include/ssx.h: guide buffers and the variance-guided a-trous filter) ----
+
+    def guides(self, res=None):
+        """ssx_guides -> {"prim": uint32 [H, W] (0xFFFFFFFF: miss), "depth": float32 [H, W], "normal": float32 [H, W, 3], "albedo": float32 [H, W, 4]}:
+        the first hit of the ray through each pixel centre (row 0 = bottom), at the options' resolution or `res` = (W, H)."""
+        W, H = res if res is not None else self.options.res
+        g = {"prim": np.zeros((H, W), dtype=np.uint32), "depth": np.zeros((H, W), dtype=np.float32),
+             "normal": np.zeros((H, W, 3), dtype=np.float32), "albedo": np.zeros((H, W, 4), dtype=np.float32)}
+        self._check(self._lib.ssx_guides(self._ctx, W, H, g["prim"].ctypes.data, g["depth"].ctypes.data, g["normal"].ctypes.data, g["albedo"].ctypes.data))
+        return g
+
+    @staticmethod
+    def _denoise_params(levels, sigma_l, sigma_a):
+        p = _capi.SsxDenoiseParams()
+        p.struct_size = C.sizeof(_capi.SsxDenoiseParams)
+        p.levels, p.sigma_l, p.sigma_a = int(levels), float(sigma_l), float(sigma_a)
+        return p
+
+    def denoise(self, levels=5, sigma_l=1.0, sigma_a=0.1, return_variance=False):
+        """ssx_denoise: the image the context holds, filtered on the device with the noise estimate's variance and the scene's guide buffers -> xyza
+        float32 [H, W, 4] (with return_variance: and the filtered variance float32 [H, W]).  Needs set_noise_estimate(True) before the render, at least
+        two launches (batches) and the whole image on this device; nothing the context holds changes."""
+        W, H = self.options.res
+        out = np.zeros((H, W, 4), dtype=np.float32)
+        var = np.zeros((H, W), dtype=np.float32) if return_variance else None
+        p = self._denoise_params(levels, sigma_l, sigma_a)
+        self._check(self._lib.ssx_denoise(self._ctx, C.byref(p), out.ctypes.data, None if var is None else var.ctypes.data))
+        return (out, var) if return_variance else out
+
+    def denoise_images(self, xyza, var, prim, albedo, levels=5, sigma_l=1.0, sigma_a=0.1, return_variance=False):
+        """ssx_denoise_images: the same filter as a pure function of its arguments: xyza [H, W, 4], var [H, W] (image units), prim [H, W] uint32,
+        albedo [H, W, 4]."""
+        xyza = np.ascontiguousarray(xyza, dtype=np.float32)
+        if xyza.ndim != 3 or xyza.shape[2] != 4:
+            raise ValueError("denoise_images: xyza must have shape [H, W, 4]")
+        H, W = xyza.shape[:2]
+        var = np.ascontiguousarray(var, dtype=np.float32)
+        prim = np.ascontiguousarray(prim, dtype=np.uint32)
+        albedo = np.ascontiguousarray(albedo, dtype=np.float32)
+        if var.shape != (H, W) or prim.shape != (H, W) or albedo.shape != (H, W, 4):
+            raise ValueError("denoise_images: var and prim must have shape [H, W], albedo [H, W, 4]")
+        out = np.zeros((H, W, 4), dtype=np.float32)
+        vout = np.zeros((H, W), dtype=np.float32) if return_variance else None
+        p = self._denoise_params(levels, sigma_l, sigma_a)
+        self._check(self._lib.ssx_denoise_images(self._ctx, C.byref(p), W, H, xyza.ctypes.data, var.ctypes.data, prim.ctypes.data, albedo.ctypes.data,
+                                                 out.ctypes.data, None if vout is None else vout.ctypes.data))
+        return (out, vout) if return_variance else out
+
     def debug_sample_flux(self, **over):
         """ssx_debug_sample_flux (spectral output on): per-sample (flux [H, W, spp, 4] float32, lambda_0 [H, W, spp] float32)."""
         p = self.params(**over)
