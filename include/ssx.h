@@ -502,6 +502,40 @@ int ssx_denoise_images(ssx_ctx* ctx, const ssx_denoise_params* params, uint32_t 
  * ownership and call ssx_denoise_images).  SSX_ERR_ARG: as above. */
 int ssx_denoise(ssx_ctx* ctx, const ssx_denoise_params* params, float* xyza_out, float* var_out);
 
+/* ---- Denoising the spectral bins: extra channels under the filter's weights (appended; same ABI version) ------------------------------------------
+ * As above: binary32 with IEEE + - * /, no contraction, no transcendental, in the order written, except the channel set-up, which is binary64 where said;
+ * a restatement in numpy gives the same bits (tests/denoise_spectral_ref.py).
+ *
+ * EXTRA CHANNELS.  FILTER above is extended by E extra channels per pixel, e[p][0..E-1], 1 <= E <= 80.  At every level each extra channel of a valid p is
+ * treated as c.xyz is: the same taps in the same row-major order, the same w = (k * wl) * wa,
+ *     se[j] = 0;   se[j] += w * e[q][j] for every tap q that is not skipped;   e'[p][j] = se[j] / sw
+ * A skipped tap (outside the image, invalid, or of another primitive) is skipped, not added with weight 0: 0 * inf is NaN.  An invalid p keeps its e at
+ * every level.  A non-finite e[q][j] of a counted tap goes through the arithmetic as it is: validity is decided by X, Y, Z and var only.  The weights never
+ * depend on e; c' and var' are those of FILTER, bit for bit.
+ *
+ * SPECTRAL CHANNELS.  n = ssx_done_spp, B bins, M = B / 4, S and N the sums and counts of "Spectral radiance output"; E = B + M:
+ *     e0[p][b]     = (float)(S[p][b] / (double)n)            b = 0..B-1   (binary64 division, then rounded)
+ *     e0[p][B + m] = (float)((double)N[p][m] / (double)n)    m = 0..M-1
+ *     eL = e0 after the L levels
+ *     out[p][b] = eL[p][B + b%M] > 0 ? eL[p][b] / eL[p][B + b%M] : 0.0f
+ * out is a ratio of filtered sums to filtered counts: every neighbour's bin enters with the number of samples behind it, the inverse-variance weight of a
+ * mean of N samples, and the weighting composes linearly across the levels.  A bin without a sample at p is filled from the neighbours that have some
+ * (filtering mean[p][b] itself would average their values with the zeros of the empty bins). */
+
+/* FILTER with E = channels extra channels as a pure function of its arguments (needs no scene): the inputs of ssx_denoise_images, and extra -> extra_out,
+ * both row-major [height][width][E].  xyza_out and var_out may be NULL and are those of ssx_denoise_images; extra and extra_out may not.  On the device the
+ * channels lie in groups of four (two ping-pong buffers of ceil(E / 4) * width * height * 16 bytes); every level is one more kernel launch next to the
+ * filter's.  SSX_ERR_ARG: as ssx_denoise_images; channels outside 1..80; a NULL extra or extra_out; an image at which one of those channel buffers would
+ * exceed 2 GiB (2^31 bytes). */
+int ssx_denoise_channels(ssx_ctx* ctx, const ssx_denoise_params* params, uint32_t width, uint32_t height, const float* xyza, const float* var,
+                         const uint32_t* prim, const float* albedo, uint32_t channels, const float* extra /* [H][W][E] */,
+                         float* xyza_out, float* var_out, float* extra_out /* [H][W][E] */);
+/* SPECTRAL CHANNELS from the context's own state, without leaving the device: mean_out [height][width][B] receives `out`, xyza_out and var_out what
+ * ssx_denoise returns; any of the three may be NULL.  The rules of ssx_denoise, and one more: spectral output must be on and the context must hold valid
+ * bins (after ssx_sums_import it holds none) -- otherwise SSX_ERR_STATE with the reason in ssx_last_error.  It reads only: image, sums, noise and spectral
+ * state stay as they are, so an ssx_render_continue afterwards leaves the bits of a one-shot render in the image and in ssx_spectral_read. */
+int ssx_denoise_spectral(ssx_ctx* ctx, const ssx_denoise_params* params, float* mean_out /* [H][W][B] */, float* xyza_out, float* var_out);
+
 /* ---- Diagnostics for the parity tests (not part of the reference's interface) ---------------------
  * ssx_debug_eval runs one building block of the path kernel -- the same device function the kernel
  * inlines -- on n items, one per lane: `in` holds in_words 32-bit words per item, `out` receives

@@ -101,7 +101,7 @@ HIP_SYMBOLS = ["ssx_create", "ssx_destroy", "ssx_upload_scene", "ssx_render_star
                "ssx_debug_eval", "ssx_debug_samples", "ssx_debug_sweep", "ssx_kernel_variant", "ssx_kernel_name", "ssx_scratch_info", "ssx_calibration_info", "ssx_set_jit", "ssx_debug_pass1_source", "ssx_done_spp", "ssx_reduce_rccl", "ssx_sums_info", "ssx_rccl_groups_made", "ssx_jit_status", "ssx_jit_counters", "ssx_done_tiles", "ssx_render_device_wait", "ssx_units_info", "ssx_rccl_probe",
                "ssx_render_continue", "ssx_scene_digest", "ssx_sums_export", "ssx_sums_import", "ssx_set_noise_estimate", "ssx_noise_info",
                "ssx_set_spectral_bins", "ssx_spectral_read", "ssx_debug_sample_flux",
-               "ssx_guides", "ssx_denoise_images", "ssx_denoise"]
+               "ssx_guides", "ssx_denoise_images", "ssx_denoise", "ssx_denoise_channels", "ssx_denoise_spectral"]
 (SSX_SWEEP_RCP, SSX_SWEEP_SQRT, SSX_SWEEP_INVERSESQRT, SSX_SWEEP_SIN, SSX_SWEEP_COS, SSX_SWEEP_ACOS, SSX_SWEEP_DIV_PI,
  SSX_SWEEP_RCP64, SSX_SWEEP_DIV_PAIRS, SSX_SWEEP_ACOS_SIN, SSX_SWEEP_SIN_PROOF, SSX_SWEEP_COS_PROOF, SSX_SWEEP_ACOS_PROOF) = range(1, 14)
 # ssx_debug_eval ops (include/ssx.h)
@@ -308,6 +308,9 @@ def hip_lib():
             lib.ssx_guides.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
             lib.ssx_denoise_images.argtypes = [vp, C.POINTER(SsxDenoiseParams), C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp]
             lib.ssx_denoise.argtypes = [vp, C.POINTER(SsxDenoiseParams), vp, vp]
+        if not override or hasattr(lib, "ssx_denoise_spectral"):  # extra channels under the filter's weights
+            lib.ssx_denoise_channels.argtypes = [vp, C.POINTER(SsxDenoiseParams), C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp]
+            lib.ssx_denoise_spectral.argtypes = [vp, C.POINTER(SsxDenoiseParams), vp, vp, vp]
         lib.ssx_kernel_variant.argtypes = [vp]
         lib.ssx_kernel_name.argtypes = [vp]
         lib.ssx_kernel_name.restype = C.c_char_p

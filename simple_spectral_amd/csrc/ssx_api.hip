@@ -142,8 +142,9 @@ struct ssx_ctx {
 	std::string spectral_note;          // why sums that can be continued come without spectral state (ssx_spectral_read says it)
 	float lambda_min = 0.0f, lambda_step = 0.0f; // of the uploaded scene
 	// denoising (csrc/ssx_denoise.hip): nothing is allocated until ssx_guides / ssx_denoise / ssx_denoise_images is called.  d_guides holds the guide buffers of
-	// the uploaded scene at guides_width x guides_height (0: none; ssx_upload_scene drops them), d_denoise the filter's inputs and ping-pong buffers.
-	DeviceBuffer d_guides, d_denoise;
+	// the uploaded scene at guides_width x guides_height (0: none; ssx_upload_scene drops them), d_denoise the filter's inputs and ping-pong buffers,
+	// d_denoise_channels those of the extra channels (ssx_denoise_channels / ssx_denoise_spectral only).
+	DeviceBuffer d_guides, d_denoise, d_denoise_channels;
 	uint32_t guides_width = 0, guides_height = 0;
 
 	// optional per-kernel timing (ssx_set_timing): events around each stage of each batch

@@ -66,6 +66,18 @@ struct SsxAtrousArgs {
 __device__ __forceinline__ bool ssx_finite(float x) { return (__float_as_uint(x) & 0x7F800000u) != 0x7F800000u; }
 __device__ __forceinline__ bool ssx_denoise_valid(const float4 c, float var) { return ssx_finite(c.x) && ssx_finite(c.y) && ssx_finite(c.z) && ssx_finite(var); }
 
+// w = (k * wl) * wa of one tap (include/ssx.h FILTER) for ssx_atrous_channels_kernel.  ssx_atrous_kernel below states the same six lines itself: calling
+// this function from it made the compiler commute the operands of its additions (the same sums, other instructions), and that kernel is to come out as it
+// was.  tests/test_denoise_spectral_gpu.py holds the two against each other: c' and var' next to extra channels X, Y, Z, bit for bit.
+__device__ __forceinline__ float ssx_atrous_tap_weight(float k, float y_q, float y_p, float den, const float4 al_q, const float4 al_p, float inv_sa2) {
+	const float xl = __builtin_fabsf(y_q - y_p) / den;
+	const float wl = 1.0f / (1.0f + xl * xl);
+	const float d0 = al_q.x - al_p.x, d1 = al_q.y - al_p.y, d2 = al_q.z - al_p.z, d3 = al_q.w - al_p.w;
+	const float da2 = ((d0 * d0 + d1 * d1) + d2 * d2) + d3 * d3;
+	const float wa = 1.0f / (1.0f + da2 * inv_sa2);
+	return (k * wl) * wa;
+}
+
 // A 16x16-pixel workgroup (4 waves), one lane per pixel, plain gather: a tap reads c and albedo as one 16-byte load each, prim and var as 4 bytes (40 bytes
 // per tap, 25 taps and the 9 variance taps of g per pixel).  Neighbouring lanes read neighbouring pixels at every step, so a wave's tap is four 256-byte runs
 // (c, albedo) and four 64-byte ones; the working set of a level -- 40 bytes per pixel, 10 MB at 512^2 -- stays in the L2 / MALL from one level to the next.
@@ -129,6 +141,231 @@ extern "C" __global__ void __launch_bounds__(256) ssx_atrous_kernel(SsxAtrousArg
 	}
 	a.c_out[p] = make_float4(scx / sw, scy / sw, scz / sw, cp.w); // (the centre tap always counts: sw >= 9/64)
 	a.var_out[p] = sv / (sw * sw);
+}
+
+// ---- extra channels (include/ssx.h "EXTRA CHANNELS", "SPECTRAL CHANNELS") ---------------------------------------------------------------------------------
+// The E extra channels of a pixel lie on the device planar in groups of four: e[group][pixel] as float4, groups = ceil(E / 4), the spare components of the
+// last group +0 (they are filtered like the rest and never leave the device).  A tap is then one 16-byte load per group, neighbouring lanes reading
+// neighbouring pixels: the access pattern of c in ssx_atrous_kernel, `groups` times.  groups * width * height <= 2^27 (channels_check_size): 32-bit indices.
+struct SsxAtrousChannelsArgs {
+	const float4* c; const float* var; const uint32_t* prim; const float4* albedo; // the level's input, as ssx_atrous_kernel reads it (which writes its c', var')
+	const float4* e; float4* e_out;                                                // [groups][height][width]
+	uint32_t width, height, step, groups;
+	float sigma_l, inv_sa2;
+};
+
+__device__ __forceinline__ float ssx_channel(const float4* e, uint32_t plane, uint32_t p, uint32_t ch) {
+	return reinterpret_cast<const float*>(e + (size_t)(ch >> 2) * plane + p)[ch & 3u];
+}
+
+// One level for the extra channels, launched next to ssx_atrous_kernel on the same input: the same 16x16-pixel workgroup, one lane per pixel.  The lane
+// recomputes the level's 25 weights and sw -- the expressions of ssx_atrous_kernel in its order, through ssx_atrous_tap_weight -- once, into 25 registers (both
+// tap loops are unrolled, so every index is static) and two 25-bit masks: `inside` (the tap is in the image: its address may be read) and `counted` (it
+// takes part: inside, valid, same primitive).  Then it walks the groups: 25 loads of 16 bytes, from the tap where it is inside the image and from the
+// lane's own pixel where it is not, and a select per component that adds w * e[q] for a counted tap and leaves the sum alone for any other -- skipped, not
+// added with weight 0.  The offsets (dy * width + dx) * step are the same for every lane (scalar registers).  No atomics, no LDS, no barriers; a lane
+// writes its own pixel only.
+extern "C" __global__ void __launch_bounds__(256) ssx_atrous_channels_kernel(SsxAtrousChannelsArgs a) {
+	const int W = (int)a.width, H = (int)a.height;
+	const int x = (int)(blockIdx.x * 16u + threadIdx.x), y = (int)(blockIdx.y * 16u + threadIdx.y);
+	if (x >= W || y >= H) return;
+	const uint32_t plane = a.width * a.height, p = (uint32_t)y * a.width + (uint32_t)x;
+	const float4 cp = a.c[p];
+	const float vp = a.var[p];
+	if (!ssx_denoise_valid(cp, vp)) { // an invalid pixel keeps what it has, at every level
+		for (uint32_t g = 0; g < a.groups; ++g) a.e_out[(size_t)g * plane + p] = a.e[(size_t)g * plane + p];
+		return;
+	}
+	float gs = 0.0f, ks = 0.0f;
+#pragma unroll
+	for (int dy = -1; dy <= 1; ++dy) {
+#pragma unroll
+		for (int dx = -1; dx <= 1; ++dx) {
+			const int qx = x + dx, qy = y + dy;
+			if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+			const uint32_t q = (uint32_t)qy * a.width + (uint32_t)qx;
+			const float vq = a.var[q];
+			if (!ssx_denoise_valid(a.c[q], vq)) continue;
+			const float k3 = (dy == 0 ? 2.0f : 1.0f) * (dx == 0 ? 2.0f : 1.0f);
+			gs += k3 * vq; ks += k3;
+		}
+	}
+	const float g3 = gs / ks;
+	const float den = a.sigma_l * __builtin_sqrtf(g3) + 1e-6f;
+	const uint32_t prim_p = a.prim[p];
+	const float4 al_p = a.albedo[p];
+	const int step = (int)a.step;
+	float w[25];
+	uint32_t inside = 0u, counted = 0u;
+	float sw = 0.0f;
+#pragma unroll
+	for (int dy = -2; dy <= 2; ++dy) {
+#pragma unroll
+		for (int dx = -2; dx <= 2; ++dx) {
+			const int t = (dy + 2) * 5 + (dx + 2);
+			w[t] = 0.0f;
+			const int qx = x + step * dx, qy = y + step * dy;
+			if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+			inside |= 1u << t;
+			const uint32_t q = (uint32_t)qy * a.width + (uint32_t)qx;
+			if (a.prim[q] != prim_p) continue;
+			const float4 cq = a.c[q];
+			if (!ssx_denoise_valid(cq, a.var[q])) continue;
+			const float hy = dy == 0 ? 0.375f : ((dy == -1 || dy == 1) ? 0.25f : 0.0625f);
+			const float hx = dx == 0 ? 0.375f : ((dx == -1 || dx == 1) ? 0.25f : 0.0625f);
+			w[t] = ssx_atrous_tap_weight(hy * hx, cq.y, cp.y, den, a.albedo[q], al_p, a.inv_sa2);
+			counted |= 1u << t;
+			sw += w[t];
+		}
+	}
+	for (uint32_t g = 0; g < a.groups; ++g) {
+		const float4* const eg = a.e + (size_t)g * plane + p;
+		float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
+#pragma unroll
+		for (int t = 0; t < 25; ++t) {
+			const ptrdiff_t off = (ptrdiff_t)((t / 5 - 2) * W + (t % 5 - 2)) * step; // inside the planes wherever `inside` says so
+			const float4 v = eg[(inside >> t) & 1u ? off : (ptrdiff_t)0];
+			const bool on = ((counted >> t) & 1u) != 0u;
+			s0 = on ? s0 + w[t] * v.x : s0; s1 = on ? s1 + w[t] * v.y : s1; s2 = on ? s2 + w[t] * v.z : s2; s3 = on ? s3 + w[t] * v.w : s3;
+		}
+		a.e_out[(size_t)g * plane + p] = make_float4(s0 / sw, s1 / sw, s2 / sw, s3 / sw); // (the centre tap always counts)
+	}
+}
+
+// The same level with the taps staged in LDS, for the steps at which a workgroup's taps overlap: at step s the 25 taps of its 16x16 pixels lie in a tile of
+// T x T pixels, T = 16 + 4 s (20 at step 1, 24 at step 2), so a value that the plain gather fetches up to 25 times is fetched T^2 / 256 = 1.6 or 2.3 times.
+// Per group of four channels the 256 lanes copy the tile (zeros outside the image) into one of two LDS buffers of 576 float4, one barrier, and every lane
+// takes its 25 taps from there at the static offsets (dy T + dx) s from its own place; the next group goes to the other buffer, so one barrier per group is
+// enough (a lane that writes buffer b for group g + 2 has passed the barrier of group g + 1, which every lane reaches after its reads of group g).  All 256
+// lanes stay to the end for the barriers: lanes outside the image and invalid pixels compute no weights; the former store nothing, the latter store the
+// centre of the tile, i.e. what they had.  Weights, order of the additions and the select per component are those of ssx_atrous_channels_kernel: the same bits.
+// Only for step <= 2 (launch_atrous).
+constexpr uint32_t kChannelsLdsTileMax = 24u * 24u;
+extern "C" __global__ void __launch_bounds__(256) ssx_atrous_channels_lds_kernel(SsxAtrousChannelsArgs a) {
+	__shared__ float4 tile[2][kChannelsLdsTileMax];
+	const int W = (int)a.width, H = (int)a.height, step = (int)a.step, T = 16 + 4 * step;
+	const int x = (int)(blockIdx.x * 16u + threadIdx.x), y = (int)(blockIdx.y * 16u + threadIdx.y);
+	const bool in_image = x < W && y < H;
+	const uint32_t plane = a.width * a.height, p = in_image ? (uint32_t)y * a.width + (uint32_t)x : 0u;
+	float4 cp = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+	float vp = 0.0f;
+	if (in_image) { cp = a.c[p]; vp = a.var[p]; }
+	const bool valid = in_image && ssx_denoise_valid(cp, vp);
+	float w[25];
+#pragma unroll
+	for (int t = 0; t < 25; ++t) w[t] = 0.0f;
+	uint32_t counted = 0u;
+	float sw = 1.0f; // (a lane without weights divides nothing it stores)
+	if (valid) {
+		float gs = 0.0f, ks = 0.0f;
+#pragma unroll
+		for (int dy = -1; dy <= 1; ++dy) {
+#pragma unroll
+			for (int dx = -1; dx <= 1; ++dx) {
+				const int qx = x + dx, qy = y + dy;
+				if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+				const uint32_t q = (uint32_t)qy * a.width + (uint32_t)qx;
+				const float vq = a.var[q];
+				if (!ssx_denoise_valid(a.c[q], vq)) continue;
+				const float k3 = (dy == 0 ? 2.0f : 1.0f) * (dx == 0 ? 2.0f : 1.0f);
+				gs += k3 * vq; ks += k3;
+			}
+		}
+		const float g3 = gs / ks;
+		const float den = a.sigma_l * __builtin_sqrtf(g3) + 1e-6f;
+		const uint32_t prim_p = a.prim[p];
+		const float4 al_p = a.albedo[p];
+		sw = 0.0f;
+#pragma unroll
+		for (int dy = -2; dy <= 2; ++dy) {
+#pragma unroll
+			for (int dx = -2; dx <= 2; ++dx) {
+				const int t = (dy + 2) * 5 + (dx + 2);
+				const int qx = x + step * dx, qy = y + step * dy;
+				if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+				const uint32_t q = (uint32_t)qy * a.width + (uint32_t)qx;
+				if (a.prim[q] != prim_p) continue;
+				const float4 cq = a.c[q];
+				if (!ssx_denoise_valid(cq, a.var[q])) continue;
+				const float hy = dy == 0 ? 0.375f : ((dy == -1 || dy == 1) ? 0.25f : 0.0625f);
+				const float hx = dx == 0 ? 0.375f : ((dx == -1 || dx == 1) ? 0.25f : 0.0625f);
+				w[t] = ssx_atrous_tap_weight(hy * hx, cq.y, cp.y, den, a.albedo[q], al_p, a.inv_sa2);
+				counted |= 1u << t;
+				sw += w[t];
+			}
+		}
+	}
+	const int tid = (int)(threadIdx.y * 16u + threadIdx.x), cells = T * T;
+	const int ox = (int)(blockIdx.x * 16u) - 2 * step, oy = (int)(blockIdx.y * 16u) - 2 * step;       // the tile's corner in the image
+	const int mine = ((int)threadIdx.y + 2 * step) * T + ((int)threadIdx.x + 2 * step);            // the lane's own pixel in the tile: taps at mine + (dy T + dx) step, in 0 .. T^2 - 1
+	int src[3]; // the up to three cells tid + 256 k the lane copies per group: its pixel in the plane, -1 outside the image (zeros), -2 past the tile (nothing)
+#pragma unroll
+	for (int k = 0; k < 3; ++k) {
+		const int cell = tid + 256 * k, gx = ox + cell % T, gy = oy + cell / T;
+		src[k] = cell >= cells ? -2 : ((gx >= 0 && gx < W && gy >= 0 && gy < H) ? gy * W + gx : -1);
+	}
+	for (uint32_t g = 0; g < a.groups; ++g) {
+		const float4* const eg = a.e + (size_t)g * plane;
+		float4* const buf = tile[g & 1u];
+#pragma unroll
+		for (int k = 0; k < 3; ++k)
+			if (src[k] != -2) buf[tid + 256 * k] = src[k] >= 0 ? eg[src[k]] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+		__syncthreads();
+		float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
+#pragma unroll
+		for (int t = 0; t < 25; ++t) {
+			const float4 v = buf[mine + ((t / 5 - 2) * T + (t % 5 - 2)) * step];
+			const bool on = ((counted >> t) & 1u) != 0u;
+			s0 = on ? s0 + w[t] * v.x : s0; s1 = on ? s1 + w[t] * v.y : s1; s2 = on ? s2 + w[t] * v.z : s2; s3 = on ? s3 + w[t] * v.w : s3;
+		}
+		if (in_image) a.e_out[(size_t)g * plane + p] = valid ? make_float4(s0 / sw, s1 / sw, s2 / sw, s3 / sw) : buf[mine];
+	}
+}
+
+// Which levels take their taps from LDS: the one place that decides.  0: none (every level is the plain gather); at most 2 (the tile buffers hold step <= 2).
+#ifndef SSX_CHANNELS_LDS_LEVELS
+#define SSX_CHANNELS_LDS_LEVELS 2
+#endif
+static_assert(SSX_CHANNELS_LDS_LEVELS >= 0 && SSX_CHANNELS_LDS_LEVELS <= 2, "the LDS tile of ssx_atrous_channels_lds_kernel holds steps 1 and 2 only");
+constexpr bool ssx_channels_level_in_lds(uint32_t level) { return level < (uint32_t)SSX_CHANNELS_LDS_LEVELS; }
+
+// The C ABI's interleaved [height][width][E] <-> the groups of four; one lane per float4 on the way in, per float on the way out.
+extern "C" __global__ void __launch_bounds__(256) ssx_channels_pack_kernel(const float* in, float4* e, uint32_t pixels, uint32_t E, uint32_t groups) {
+	const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+	if (idx >= pixels * groups) return;
+	const uint32_t ch = 4u * (idx / pixels), p = idx % pixels;
+	const float* const src = in + (size_t)p * E;
+	e[idx] = make_float4(src[ch], ch + 1u < E ? src[ch + 1u] : 0.0f, ch + 2u < E ? src[ch + 2u] : 0.0f, ch + 3u < E ? src[ch + 3u] : 0.0f);
+}
+extern "C" __global__ void __launch_bounds__(256) ssx_channels_unpack_kernel(const float4* e, float* out, uint32_t pixels, uint32_t E) {
+	const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+	if (idx >= pixels * E) return;
+	out[idx] = ssx_channel(e, pixels, idx / E, idx % E);
+}
+
+// e0 of the spectral bins (include/ssx.h "SPECTRAL CHANNELS") from the persistent S[tile slot][bin][pixel of the tile] and N[tile slot][m][pixel of the tile]
+// of a context that owns the whole image: channels 0..B-1 = (float)(S / n), B..B+M-1 = (float)((double)N / n), both divisions binary64; one lane per float4.
+extern "C" __global__ void __launch_bounds__(256) ssx_spectral_channels_kernel(const double* S, const uint32_t* N, float4* e, SsxPixelGrid g, uint32_t M, double n) {
+	const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x, pixels = g.width * g.height, B = 4u * M, groups = (B + M + 3u) / 4u;
+	if (idx >= pixels * groups) return;
+	const uint32_t ch0 = 4u * (idx / pixels), p = idx % pixels, i = p % g.width, j = p / g.width;
+	const size_t slot = ssx_shared_tile(g, i, j) / g.tile_stride, lane = (j & 7u) * 8u + (i & 7u);
+	float v[4];
+#pragma unroll
+	for (uint32_t k = 0; k < 4u; ++k) {
+		const uint32_t ch = ch0 + k;
+		v[k] = ch < B ? (float)(S[(slot * B + ch) * 64u + lane] / n) : (ch < B + M ? (float)((double)N[(slot * M + (ch - B)) * 64u + lane] / n) : 0.0f);
+	}
+	e[idx] = make_float4(v[0], v[1], v[2], v[3]);
+}
+
+// out[p][b] = eL[p][B + b % M] > 0 ? eL[p][b] / eL[p][B + b % M] : 0.0f, row-major [height][width][B]; one lane per float
+extern "C" __global__ void __launch_bounds__(256) ssx_spectral_ratio_kernel(const float4* e, float* out, uint32_t pixels, uint32_t M) {
+	const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x, B = 4u * M;
+	if (idx >= pixels * B) return;
+	const uint32_t p = idx / B, b = idx % B;
+	const float den = ssx_channel(e, pixels, p, B + b % M);
+	out[idx] = den > 0.0f ? ssx_channel(e, pixels, p, b) / den : 0.0f;
 }
 
 namespace {
@@ -195,9 +432,31 @@ int denoise_buffers(ssx_ctx* ctx, size_t pixels, DenoiseBuffers* b) {
 	return SSX_OK;
 }
 
+// d_denoise_channels: the extra channels' ping-pong buffers e[0] | e[1] (groups x pixels float4 each) and, behind them, the row-major staging of what the
+// entry point takes or returns ([pixels][stage_channels] floats).  Allocated by the two entry points that filter extra channels, by nothing else.
+struct ChannelBuffers { float4* e[2]; float* stage; uint32_t groups; };
+constexpr uint32_t kDenoiseMaxChannels = 80;
+constexpr uint64_t kChannelBufferLimit = 1ull << 31; // bytes of one ping-pong buffer: the kernels index them with 32 bits
+int channels_check_size(ssx_ctx* ctx, size_t pixels, uint32_t channels, const char* what) {
+	if ((uint64_t)pixels * ((channels + 3u) / 4u) * 16u > kChannelBufferLimit)
+		return fail(ctx, SSX_ERR_ARG, fmt("%s: %u channels at this size need channel buffers of more than 2 GiB each", what, channels));
+	return SSX_OK;
+}
+int channel_buffers(ssx_ctx* ctx, size_t pixels, uint32_t channels, uint32_t stage_channels, ChannelBuffers* cb) {
+	cb->groups = (channels + 3u) / 4u;
+	const size_t plane = pixels * cb->groups;
+	SSX_HIP(ctx, ctx->d_denoise_channels.reserve(plane * 32u + pixels * stage_channels * sizeof(float)));
+	cb->e[0] = ctx->d_denoise_channels.as<float4>(); cb->e[1] = cb->e[0] + plane;
+	cb->stage = reinterpret_cast<float*>(cb->e[1] + plane);
+	return SSX_OK;
+}
+dim3 blocks_of(size_t lanes) { return dim3((uint32_t)((lanes + 255u) / 256u)); }
+
 // The levels, one launch each, ping-pong between b.c / b.var[0] and [1]; none of the four inputs is written.  The result is in b.c / b.var[(levels - 1) & 1]
-// once the stream has been waited for.
-int launch_atrous(ssx_ctx* ctx, const ssx_denoise_params& dp, uint32_t width, uint32_t height, const float4* c, const float* var, const uint32_t* prim, const float4* albedo, const DenoiseBuffers& b) {
+// once the stream has been waited for.  With extra channels (cb; NULL: none, and nothing more is launched) every level also runs ssx_atrous_channels_kernel (or, where ssx_channels_level_in_lds says so, its LDS-staged twin) on
+// the same input, from cb->e[l & 1] to cb->e[(l + 1) & 1]: the caller has put the channels into cb->e[0] and finds them in cb->e[levels & 1].
+int launch_atrous(ssx_ctx* ctx, const ssx_denoise_params& dp, uint32_t width, uint32_t height, const float4* c, const float* var, const uint32_t* prim, const float4* albedo, const DenoiseBuffers& b,
+                  const ChannelBuffers* cb = nullptr) {
 	SsxAtrousArgs a{};
 	a.prim = prim; a.albedo = albedo;
 	a.width = width; a.height = height;
@@ -209,6 +468,15 @@ int launch_atrous(ssx_ctx* ctx, const ssx_denoise_params& dp, uint32_t width, ui
 		a.step = 1u << l;
 		hipLaunchKernelGGL(ssx_atrous_kernel, grid, block, 0, ctx->stream, a);
 		SSX_HIP(ctx, hipGetLastError());
+		if (!cb) continue;
+		SsxAtrousChannelsArgs ca{};
+		ca.c = a.c; ca.var = a.var; ca.prim = prim; ca.albedo = albedo;
+		ca.e = cb->e[l & 1u]; ca.e_out = cb->e[(l + 1u) & 1u];
+		ca.width = width; ca.height = height; ca.step = a.step; ca.groups = cb->groups;
+		ca.sigma_l = a.sigma_l; ca.inv_sa2 = a.inv_sa2;
+		if (ssx_channels_level_in_lds(l)) hipLaunchKernelGGL(ssx_atrous_channels_lds_kernel, grid, block, 0, ctx->stream, ca);
+		else hipLaunchKernelGGL(ssx_atrous_channels_kernel, grid, block, 0, ctx->stream, ca);
+		SSX_HIP(ctx, hipGetLastError());
 	}
 	return SSX_OK;
 }
@@ -218,6 +486,34 @@ int denoise_read_back(ssx_ctx* ctx, const ssx_denoise_params& dp, size_t pixels,
 	const uint32_t last = (dp.levels - 1u) & 1u;
 	if (xyza_out) SSX_HIP(ctx, hipMemcpy(xyza_out, b.c[last], pixels * sizeof(float4), hipMemcpyDeviceToHost));
 	if (var_out) SSX_HIP(ctx, hipMemcpy(var_out, b.var[last], pixels * sizeof(float), hipMemcpyDeviceToHost));
+	return SSX_OK;
+}
+
+// What ssx_denoise and ssx_denoise_spectral ask of the context's own state before they touch the device (the reasons as ssx_last_error gives them); on
+// return the context's device is current and idle, and the guide buffers of the render's size exist.
+int denoise_own_state_ready(ssx_ctx* ctx, const char* what, bool spectral) {
+	if (!ctx->have_scene) return fail(ctx, SSX_ERR_STATE, "no scene uploaded");
+	if (spectral && !ctx->spectral_bins) return fail(ctx, SSX_ERR_STATE, fmt("%s: spectral output is off (ssx_set_spectral_bins)", what));
+	if (const int rc = sums_ready(ctx, what)) return rc;
+	if (spectral && !ctx->sums.spectral_valid) return fail(ctx, SSX_ERR_STATE, fmt("%s: the context holds no spectral bins: ", what) + ctx->spectral_note);
+	if (!ctx->noise_on) return fail(ctx, SSX_ERR_STATE, fmt("%s: the noise estimate is off (ssx_set_noise_estimate): the filter is guided by its variance", what));
+	if (!ctx->sums.noise_valid || ctx->sums.noise_batches < 2u)
+		return fail(ctx, SSX_ERR_STATE, fmt("%s: %u batch(es) so far; the between-batch variance needs two", what, ctx->sums.noise_valid ? ctx->sums.noise_batches : 0u));
+	const ssx_render_params& p = ctx->cur;
+	if (p.tile_stride != 1u)
+		return fail(ctx, SSX_ERR_STATE, fmt("%s: the context owns a part of the image only (tile_stride = %u): combine the ranks and use %s", what, p.tile_stride, spectral ? "ssx_denoise_channels" : "ssx_denoise_images"));
+	if (!ctx->d_out.ptr) return fail(ctx, SSX_ERR_STATE, fmt("%s: the context holds no image", what));
+	return ensure_guides(ctx, p.width, p.height);
+}
+
+// ... and the filter's buffers with the variance in image units in b->var_in (queued on the context's stream)
+int denoise_own_inputs(ssx_ctx* ctx, DenoiseBuffers* b) {
+	const ssx_render_params& p = ctx->cur;
+	if (const int rc = denoise_buffers(ctx, (size_t)p.width * p.height, b)) return rc;
+	const double s = ctx->rgb_mode ? 1.0 : 1000.0; // what ssx_finalize_kernel multiplies A / N by
+	hipLaunchKernelGGL(ssx_denoise_var_kernel, pixel_blocks(&p), dim3(256), 0, ctx->stream, ctx->d_accum.as<const double>(), ctx->d_noise.as<const double>(), b->var_in,
+	                   pixel_grid(&p), (double)ctx->done_spp.load(), (double)ctx->sums.noise_batches, s * s);
+	SSX_HIP(ctx, hipGetLastError());
 	return SSX_OK;
 }
 
@@ -270,25 +566,74 @@ int ssx_denoise(ssx_ctx* ctx, const ssx_denoise_params* params, float* xyza_out,
 	ssx_denoise_params dp;
 	int rc = denoise_take_params(ctx, params, &dp);
 	if (rc) return rc;
-	if (!ctx->have_scene) return fail(ctx, SSX_ERR_STATE, "no scene uploaded");
-	if ((rc = sums_ready(ctx, "ssx_denoise"))) return rc;
-	if (!ctx->noise_on) return fail(ctx, SSX_ERR_STATE, "ssx_denoise: the noise estimate is off (ssx_set_noise_estimate): the filter is guided by its variance");
-	if (!ctx->sums.noise_valid || ctx->sums.noise_batches < 2u)
-		return fail(ctx, SSX_ERR_STATE, fmt("ssx_denoise: %u batch(es) so far; the between-batch variance needs two", ctx->sums.noise_valid ? ctx->sums.noise_batches : 0u));
+	if ((rc = denoise_own_state_ready(ctx, "ssx_denoise", false))) return rc;
 	const ssx_render_params& p = ctx->cur;
-	if (p.tile_stride != 1u) return fail(ctx, SSX_ERR_STATE, fmt("ssx_denoise: the context owns a part of the image only (tile_stride = %u): combine the ranks and use ssx_denoise_images", p.tile_stride));
-	if (!ctx->d_out.ptr) return fail(ctx, SSX_ERR_STATE, "ssx_denoise: the context holds no image");
-	if ((rc = ensure_guides(ctx, p.width, p.height))) return rc;
 	const size_t pixels = (size_t)p.width * p.height;
 	DenoiseBuffers b;
-	if ((rc = denoise_buffers(ctx, pixels, &b))) return rc;
-	const double s = ctx->rgb_mode ? 1.0 : 1000.0; // what ssx_finalize_kernel multiplies A / N by
-	hipLaunchKernelGGL(ssx_denoise_var_kernel, pixel_blocks(&p), dim3(256), 0, ctx->stream, ctx->d_accum.as<const double>(), ctx->d_noise.as<const double>(), b.var_in,
-	                   pixel_grid(&p), (double)ctx->done_spp.load(), (double)ctx->sums.noise_batches, s * s);
-	SSX_HIP(ctx, hipGetLastError());
+	if ((rc = denoise_own_inputs(ctx, &b))) return rc;
 	const SsxGuides g = guides_of(ctx, pixels);
 	if ((rc = launch_atrous(ctx, dp, p.width, p.height, ctx->d_out.as<const float4>(), b.var_in, g.prim, g.albedo, b))) return rc;
 	return denoise_read_back(ctx, dp, pixels, b, xyza_out, var_out);
+}
+
+int ssx_denoise_channels(ssx_ctx* ctx, const ssx_denoise_params* params, uint32_t width, uint32_t height, const float* xyza, const float* var,
+                         const uint32_t* prim, const float* albedo, uint32_t channels, const float* extra, float* xyza_out, float* var_out, float* extra_out) {
+	if (!ctx) return SSX_ERR_ARG;
+	if (channels < 1u || channels > kDenoiseMaxChannels) return fail(ctx, SSX_ERR_ARG, fmt("ssx_denoise_channels: channels = %u: need 1..%u", channels, kDenoiseMaxChannels));
+	if (!xyza || !var || !prim || !albedo || !extra || !extra_out)
+		return fail(ctx, SSX_ERR_ARG, "ssx_denoise_channels: xyza, var, prim, albedo, extra and extra_out must not be NULL");
+	ssx_denoise_params dp;
+	int rc = denoise_take_params(ctx, params, &dp);
+	if (rc) return rc;
+	if ((rc = denoise_check_size(ctx, width, height, "ssx_denoise_channels"))) return rc;
+	const size_t pixels = (size_t)width * height;
+	if ((rc = channels_check_size(ctx, pixels, channels, "ssx_denoise_channels"))) return rc;
+	if (ctx->rendering.load()) return fail(ctx, SSX_ERR_STATE, "render in progress");
+	SSX_HIP(ctx, hipSetDevice(ctx->device));
+	if ((rc = wait_device_pending(ctx))) return rc;
+	DenoiseBuffers b;
+	ChannelBuffers cb;
+	if ((rc = denoise_buffers(ctx, pixels, &b))) return rc;
+	if ((rc = channel_buffers(ctx, pixels, channels, channels, &cb))) return rc;
+	SSX_HIP(ctx, hipMemcpyAsync(b.c_in, xyza, pixels * 16u, hipMemcpyHostToDevice, ctx->stream));
+	SSX_HIP(ctx, hipMemcpyAsync(b.albedo_in, albedo, pixels * 16u, hipMemcpyHostToDevice, ctx->stream));
+	SSX_HIP(ctx, hipMemcpyAsync(b.var_in, var, pixels * 4u, hipMemcpyHostToDevice, ctx->stream));
+	SSX_HIP(ctx, hipMemcpyAsync(b.prim_in, prim, pixels * 4u, hipMemcpyHostToDevice, ctx->stream));
+	SSX_HIP(ctx, hipMemcpyAsync(cb.stage, extra, pixels * channels * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+	hipLaunchKernelGGL(ssx_channels_pack_kernel, blocks_of(pixels * cb.groups), dim3(256), 0, ctx->stream, cb.stage, cb.e[0], (uint32_t)pixels, channels, cb.groups);
+	SSX_HIP(ctx, hipGetLastError());
+	if ((rc = launch_atrous(ctx, dp, width, height, b.c_in, b.var_in, b.prim_in, b.albedo_in, b, &cb))) return rc;
+	hipLaunchKernelGGL(ssx_channels_unpack_kernel, blocks_of(pixels * channels), dim3(256), 0, ctx->stream, cb.e[dp.levels & 1u], cb.stage, (uint32_t)pixels, channels);
+	SSX_HIP(ctx, hipGetLastError());
+	if ((rc = denoise_read_back(ctx, dp, pixels, b, xyza_out, var_out))) return rc; // (waits for the stream)
+	SSX_HIP(ctx, hipMemcpy(extra_out, cb.stage, pixels * channels * sizeof(float), hipMemcpyDeviceToHost));
+	return SSX_OK;
+}
+
+int ssx_denoise_spectral(ssx_ctx* ctx, const ssx_denoise_params* params, float* mean_out, float* xyza_out, float* var_out) {
+	if (!ctx) return SSX_ERR_ARG;
+	ssx_denoise_params dp;
+	int rc = denoise_take_params(ctx, params, &dp);
+	if (rc) return rc;
+	if ((rc = denoise_own_state_ready(ctx, "ssx_denoise_spectral", true))) return rc;
+	const ssx_render_params& p = ctx->cur;
+	const size_t pixels = (size_t)p.width * p.height;
+	const uint32_t B = ctx->spectral_bins, M = B / 4u;
+	if ((rc = channels_check_size(ctx, pixels, B + M, "ssx_denoise_spectral"))) return rc;
+	DenoiseBuffers b;
+	ChannelBuffers cb;
+	if ((rc = denoise_own_inputs(ctx, &b))) return rc;
+	if ((rc = channel_buffers(ctx, pixels, B + M, B, &cb))) return rc;
+	hipLaunchKernelGGL(ssx_spectral_channels_kernel, blocks_of(pixels * cb.groups), dim3(256), 0, ctx->stream, ctx->d_spectral_sums.as<const double>(),
+	                   ctx->d_spectral_counts.as<const uint32_t>(), cb.e[0], pixel_grid(&p), M, (double)ctx->done_spp.load());
+	SSX_HIP(ctx, hipGetLastError());
+	const SsxGuides g = guides_of(ctx, pixels);
+	if ((rc = launch_atrous(ctx, dp, p.width, p.height, ctx->d_out.as<const float4>(), b.var_in, g.prim, g.albedo, b, &cb))) return rc;
+	hipLaunchKernelGGL(ssx_spectral_ratio_kernel, blocks_of(pixels * B), dim3(256), 0, ctx->stream, cb.e[dp.levels & 1u], cb.stage, (uint32_t)pixels, M);
+	SSX_HIP(ctx, hipGetLastError());
+	if ((rc = denoise_read_back(ctx, dp, pixels, b, xyza_out, var_out))) return rc; // (waits for the stream)
+	if (mean_out) SSX_HIP(ctx, hipMemcpy(mean_out, cb.stage, pixels * B * sizeof(float), hipMemcpyDeviceToHost));
+	return SSX_OK;
 }
 
 } // extern "C"

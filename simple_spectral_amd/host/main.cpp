@@ -13,6 +13,9 @@
 // of include/ssx.h to --output instead of the plain one.  It switches the noise estimate on and renders in launches of --noise-step samples (ceil(spp / 8) when
 // that is not given), so that the estimate has its two batches; not with -spp=1 or --tile-major.  --guides-output=PATH.npy writes the first-hit guide buffers,
 // float32 (height, width, 9) = {primitive (-1: none), depth, normal xyz, albedo 0..3}, row 0 = bottom.
+// --spectral-denoise (with --spectral-output): the file holds the bins filtered with the weights of that filter (include/ssx.h "Denoising the spectral bins").  It
+// renders as --denoise does (noise estimate on, the same launch rule and refusals) and takes --denoise-levels and --denoise-sigma; the output image is the
+// filtered one only if --denoise is given too.
 #include "renderer.hpp"
 
 #include <chrono>
@@ -47,7 +50,8 @@ void print_usage() {
 		"    `--checkpoint=<file>` `--resume=<file>` (`-spp` is then the total) `--noise-target=<x> --max-samples=<n> [--noise-step=<s>]`\n"
 		"    `--spectral-output=<file.npy>` [`--spectral-bins=<n>`: 4, 8, ..., 64; default 16] (not with `--resume`)\n"
 		"    `--denoise` [`--denoise-levels=<n>`: 1..6; default 5] [`--denoise-sigma=<l>,<a>`; default 1,0.1] (the output image is the filtered one; not with `-spp=1`)\n"
-		"    `--guides-output=<file.npy>` (first hit per pixel: primitive, depth, normal, albedo)\n");
+		"    `--guides-output=<file.npy>` (first hit per pixel: primitive, depth, normal, albedo)\n"
+		"    `--spectral-denoise` (with `--spectral-output`: the file holds the bins filtered with `--denoise`'s weights, levels and sigmas; not with `-spp=1`)\n");
 }
 
 struct ArgList {
@@ -92,6 +96,7 @@ struct Progressive { // the flags of the progressive modes
 	std::string spectral_output; // --spectral-output: "" = none
 	size_t spectral_bins = 16;
 	bool denoise = false;        // --denoise
+	bool spectral_denoise = false; // --spectral-denoise
 	bool noise_step_given = false;
 	ssx::Renderer::DenoiseParams denoise_params;
 	std::string guides_output;   // --guides-output: "" = none
@@ -189,10 +194,17 @@ void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progress
 		} catch (...) { ok = false; }
 		if (!ok) { std::fprintf(stderr, "Invalid value for --denoise-sigma (<l>,<a>, both positive)!\n"); throw -2; }
 	}
-	if (g->denoise && o->spp < 2) { std::fprintf(stderr, "`--denoise` needs at least two samples per pixel: its variance estimate compares batches of samples!\n"); throw -2; }
-	if (g->denoise && o->tile_major) { std::fprintf(stderr, "`--denoise` cannot be combined with `--tile-major`: only a render that walks through the samples takes batches!\n"); throw -2; }
-	if (g->denoise) o->spp_per_launch = g->noise_step_given ? g->noise_step : (o->spp + 7) / 8; // at least two launches = two batches
-	if (g->denoise && o->spp_per_launch >= o->spp) { std::fprintf(stderr, "`--denoise` needs `--noise-step` below the number of samples (two batches at least)!\n"); throw -2; }
+	if (a.take("--spectral-denoise", "", &v)) {
+		if (v != "--spectral-denoise") { std::fprintf(stderr, "`--spectral-denoise` does not take a value!\n"); throw -2; }
+		if (g->spectral_output.empty()) { std::fprintf(stderr, "`--spectral-denoise` needs `--spectral-output=<file.npy>`: it filters the bins written there!\n"); throw -2; }
+		g->spectral_denoise = true;
+	}
+	const bool filters = g->denoise || g->spectral_denoise; // both render for the filter: the noise estimate on, two batches at least
+	const char* const flag = g->denoise ? "--denoise" : "--spectral-denoise";
+	if (filters && o->spp < 2) { std::fprintf(stderr, "`%s` needs at least two samples per pixel: its variance estimate compares batches of samples!\n", flag); throw -2; }
+	if (filters && o->tile_major) { std::fprintf(stderr, "`%s` cannot be combined with `--tile-major`: only a render that walks through the samples takes batches!\n", flag); throw -2; }
+	if (filters) o->spp_per_launch = g->noise_step_given ? g->noise_step : (o->spp + 7) / 8; // at least two launches = two batches
+	if (filters && o->spp_per_launch >= o->spp) { std::fprintf(stderr, "`%s` needs `--noise-step` below the number of samples (two batches at least)!\n", flag); throw -2; }
 	if (a.take("--guides-output", "", &v)) g->guides_output = v;
 	if (a.take("--texture", "", &v)) o->texture_path = v;
 	if (a.take("--data-dir", "", &v)) o->data_dir = v;
@@ -225,7 +237,7 @@ int main(int argc, char* argv[]) {
 		if (prog.denoise) options.output_path.clear(); // (render_wait writes the plain image there; the filtered one is written below)
 		ssx::Renderer renderer(options);
 		std::signal(SIGINT, on_sigint);
-		if (prog.denoise) renderer.set_noise_estimate(true);
+		if (prog.denoise || prog.spectral_denoise) renderer.set_noise_estimate(true);
 		if (!prog.spectral_output.empty()) renderer.set_spectral_bins(prog.spectral_bins);
 		bool stop_sent = false;
 		if (prog.noise_target >= 0.0) {
@@ -257,9 +269,14 @@ int main(int argc, char* argv[]) {
 		// laggards finish the launches the others had done), so that the image written now is the one the checkpoint resumes from.
 		if (!prog.checkpoint.empty()) renderer.level_devices();
 		renderer.render_wait();
-		if (prog.denoise) renderer.denoise(prog.denoise_params).save(denoised_path);
+		std::vector<float> filtered_bins;
+		if (prog.spectral_denoise) { // (one run of the filter serves both outputs)
+			const ssx::Framebuffer fb = renderer.denoise_spectral(prog.denoise_params, &filtered_bins);
+			if (prog.denoise) fb.save(denoised_path);
+		} else if (prog.denoise) renderer.denoise(prog.denoise_params).save(denoised_path);
 		if (!prog.guides_output.empty()) renderer.save_guides(prog.guides_output);
-		if (!prog.spectral_output.empty()) renderer.save_spectral_image(prog.spectral_output);
+		if (prog.spectral_denoise) renderer.save_spectral_image(prog.spectral_output, filtered_bins);
+		else if (!prog.spectral_output.empty()) renderer.save_spectral_image(prog.spectral_output);
 		if (!prog.checkpoint.empty()) renderer.save_checkpoint(prog.checkpoint);
 	} catch (const ssx::HostError& e) {
 		std::fprintf(stderr, "%s\n", e.message.c_str());

@@ -53,6 +53,8 @@ struct Renderer::Api {
 	int (*guides)(ssx_ctx*, uint32_t, uint32_t, uint32_t*, float*, float*, float*) = nullptr;
 	int (*denoise_images)(ssx_ctx*, const ssx_denoise_params*, uint32_t, uint32_t, const float*, const float*, const uint32_t*, const float*, float*, float*) = nullptr;
 	int (*denoise)(ssx_ctx*, const ssx_denoise_params*, float*, float*) = nullptr;
+	int (*denoise_channels)(ssx_ctx*, const ssx_denoise_params*, uint32_t, uint32_t, const float*, const float*, const uint32_t*, const float*, uint32_t, const float*, float*, float*, float*) = nullptr;
+	int (*denoise_spectral)(ssx_ctx*, const ssx_denoise_params*, float*, float*, float*) = nullptr;
 
 	explicit Api(const std::string& path) {
 		handle = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
@@ -91,6 +93,8 @@ struct Renderer::Api {
 		guides = reinterpret_cast<decltype(guides)>(sym("ssx_guides"));
 		denoise_images = reinterpret_cast<decltype(denoise_images)>(sym("ssx_denoise_images"));
 		denoise = reinterpret_cast<decltype(denoise)>(sym("ssx_denoise"));
+		denoise_channels = reinterpret_cast<decltype(denoise_channels)>(sym("ssx_denoise_channels"));
+		denoise_spectral = reinterpret_cast<decltype(denoise_spectral)>(sym("ssx_denoise_spectral"));
 	}
 	~Api() { if (handle) dlclose(handle); }
 };
@@ -304,8 +308,13 @@ void Renderer::spectral_image(std::vector<float>* mean, std::vector<uint32_t>* c
 void Renderer::save_spectral_image(const std::string& path) {
 	std::vector<float> mean;
 	spectral_image(&mean);
+	save_spectral_image(path, mean);
+}
+
+void Renderer::save_spectral_image(const std::string& path, const std::vector<float>& bins) {
 	const size_t shape[3] = { options.res[1], options.res[0], spectral_bins_ };
-	save_npy_f32(path, mean.data(), shape, 3);
+	if (bins.size() != shape[0] * shape[1] * shape[2]) throw HostError{ SSX_ERR_ARG, "save_spectral_image: the array is not [height][width][bins]" };
+	save_npy_f32(path, bins.data(), shape, 3);
 }
 
 Renderer::Guides Renderer::guides() {
@@ -355,6 +364,53 @@ Framebuffer Renderer::denoise(const DenoiseParams& params, std::vector<float>* x
 	}
 	Framebuffer fb(options.res);
 	color->xyza_to_srgba(out.data(), fb.data(), pixels);
+	if (xyza_out) xyza_out->swap(out);
+	return fb;
+}
+
+Framebuffer Renderer::denoise_spectral(const DenoiseParams& params, std::vector<float>* bins, std::vector<float>* xyza_out) {
+	wait_workers_();
+	if (!spectral_bins_) throw HostError{ SSX_ERR_STATE, "denoise_spectral: spectral output is off (set_spectral_bins)" };
+	const size_t W = options.res[0], H = options.res[1], pixels = W * H, B = spectral_bins_, M = B / 4, E = B + M, n_dev = ctxs_.size();
+	ssx_denoise_params dp{};
+	dp.struct_size = sizeof dp; dp.levels = params.levels; dp.sigma_l = params.sigma_l; dp.sigma_a = params.sigma_a;
+	std::vector<float> out(pixels * 4), mean(pixels * B);
+	ssx_ctx* root = ctxs_[0];
+	if (n_dev == 1) check_(api_->denoise_spectral(root, &dp, mean.data(), out.data(), nullptr), "ssx_denoise_spectral", root);
+	else {
+		// as denoise() combines image and variance; the sums S and counts N come from the device that owns the pixel, bit for bit (spectral_image's merge)
+		level_devices();
+		std::vector<double> v;
+		(void)noise(&v);
+		const double s = options.rgb_mode ? 1.0 : 1000.0;
+		std::vector<float> var(pixels);
+		for (size_t p = 0; p < pixels; ++p) var[p] = static_cast<float>(v[p] * (s * s));
+		const Guides g = guides();
+		std::vector<double> part_s(pixels * B);
+		std::vector<uint32_t> part_n(pixels * M);
+		std::vector<float> e0(pixels * E), eL(pixels * E);
+		const size_t skew = params_for_(0, 1, 0).tile_skew;
+		for (size_t d = 0; d < n_dev; ++d) {
+			ssx_spectral_info_t info{};
+			check_(api_->spectral_read(ctxs_[d], &info, nullptr, part_s.data(), part_n.data()), "ssx_spectral_read", ctxs_[d]);
+			const double n = static_cast<double>(info.done_spp);
+			for (size_t j = 0; j < H; ++j) for (size_t i = 0; i < W; ++i) {
+				if (shared_tile(W, skew, i, j) % n_dev != d) continue;
+				const size_t p = j * W + i;
+				for (size_t b = 0; b < B; ++b) e0[p * E + b] = static_cast<float>(part_s[p * B + b] / n);                      // binary64 division, then rounded
+				for (size_t m = 0; m < M; ++m) e0[p * E + B + m] = static_cast<float>(static_cast<double>(part_n[p * M + m]) / n);
+			}
+		}
+		check_(api_->denoise_channels(root, &dp, static_cast<uint32_t>(W), static_cast<uint32_t>(H), xyza.data(), var.data(), g.prim.data(), g.albedo.data(),
+		                              static_cast<uint32_t>(E), e0.data(), out.data(), nullptr, eL.data()), "ssx_denoise_channels", root);
+		for (size_t p = 0; p < pixels; ++p) for (size_t b = 0; b < B; ++b) {
+			const float den = eL[p * E + B + b % M];
+			mean[p * B + b] = den > 0.0f ? eL[p * E + b] / den : 0.0f;
+		}
+	}
+	Framebuffer fb(options.res);
+	color->xyza_to_srgba(out.data(), fb.data(), pixels);
+	if (bins) bins->swap(mean);
 	if (xyza_out) xyza_out->swap(out);
 	return fb;
 }

@@ -114,6 +114,13 @@ public:
 	// ssx_denoise, all on the device.  Several: the devices' images and variances combined by ownership (render_wait, noise), then ssx_denoise_images on
 	// device 0 -- the same bits.  xyza_out (optional): the filtered XYZ + alpha behind the returned sRGB framebuffer.  Nothing the devices hold changes.
 	Framebuffer denoise(const DenoiseParams& params, std::vector<float>* xyza_out = nullptr);
+	// The wavelength bins of the render so far, filtered with the weights denoise() applies to the image (include/ssx.h "Denoising the spectral bins"):
+	// *bins [height][width][B], the ratio of the filtered per-bin sums to the filtered sample counts.  Needs what denoise() needs, and set_spectral_bins before
+	// the render.  One device: ssx_denoise_spectral, all on the device.  Several: the devices' sums, counts, images and variances combined by ownership, the
+	// channels e0 built here by the header's formula, ssx_denoise_channels on device 0, the ratio formed here -- the same bits.  Returns the filtered image,
+	// which is denoise()'s (xyza_out as there).  Nothing the devices hold changes.
+	Framebuffer denoise_spectral(const DenoiseParams& params, std::vector<float>* bins, std::vector<float>* xyza_out = nullptr);
+	void save_spectral_image(const std::string& path, const std::vector<float>& bins); // a [height][width][B] array, e.g. denoise_spectral's, in spectral_image's .npy layout
 
 private:
 	struct Api;

@@ -356,6 +356,7 @@ class Renderer:
     def set_spectral_bins(self, n):
         """ssx_set_spectral_bins: n wavelength bins per pixel (a multiple of 4 up to 64) for the renders that follow; 0 switches it off."""
         self._check(self._lib.ssx_set_spectral_bins(self._ctx, int(n)))
+        self._spectral_bins = int(n)
 
     def spectral_read(self, sums=False):
         """ssx_spectral_read -> (SsxSpectralInfo, mean float32 [H, W, B], counts uint32 [H, W, B/4], sums float64 [H, W, B] or None)."""
@@ -422,6 +423,43 @@ class Renderer:
         self._check(self._lib.ssx_denoise_images(self._ctx, C.byref(p), W, H, xyza.ctypes.data, var.ctypes.data, prim.ctypes.data, albedo.ctypes.data,
                                                  out.ctypes.data, None if vout is None else vout.ctypes.data))
         return (out, vout) if return_variance else out
+
+    def denoise_channels(self, xyza, var, prim, albedo, extra, levels=5, sigma_l=1.0, sigma_a=0.1, return_image=False):
+        """ssx_denoise_channels: the filter of denoise_images applied, with the weights it computes from xyza, var, prim and albedo, to `extra` [H, W, E]
+        (1 <= E <= 80) -> float32 [H, W, E]; with return_image: (extra, xyza, var), the last two those of denoise_images."""
+        xyza = np.ascontiguousarray(xyza, dtype=np.float32)
+        if xyza.ndim != 3 or xyza.shape[2] != 4:
+            raise ValueError("denoise_channels: xyza must have shape [H, W, 4]")
+        H, W = xyza.shape[:2]
+        var = np.ascontiguousarray(var, dtype=np.float32)
+        prim = np.ascontiguousarray(prim, dtype=np.uint32)
+        albedo = np.ascontiguousarray(albedo, dtype=np.float32)
+        extra = np.ascontiguousarray(extra, dtype=np.float32)
+        if var.shape != (H, W) or prim.shape != (H, W) or albedo.shape != (H, W, 4) or extra.ndim != 3 or extra.shape[:2] != (H, W):
+            raise ValueError("denoise_channels: var and prim must have shape [H, W], albedo [H, W, 4], extra [H, W, E]")
+        E = extra.shape[2]
+        eout = np.zeros((H, W, E), dtype=np.float32)
+        out = np.zeros((H, W, 4), dtype=np.float32) if return_image else None
+        vout = np.zeros((H, W), dtype=np.float32) if return_image else None
+        p = self._denoise_params(levels, sigma_l, sigma_a)
+        self._check(self._lib.ssx_denoise_channels(self._ctx, C.byref(p), W, H, xyza.ctypes.data, var.ctypes.data, prim.ctypes.data, albedo.ctypes.data, E,
+                                                   extra.ctypes.data, None if out is None else out.ctypes.data,
+                                                   None if vout is None else vout.ctypes.data, eout.ctypes.data))
+        return (eout, out, vout) if return_image else eout
+
+    def denoise_spectral(self, levels=5, sigma_l=1.0, sigma_a=0.1, return_image=False):
+        """ssx_denoise_spectral: the wavelength bins the context holds, filtered on the device with the weights denoise() applies to the image -> float32
+        [H, W, B], the ratio of the filtered per-bin sums to the filtered sample counts (include/ssx.h); with return_image: (bins, xyza, var), the last
+        two those of denoise().  Needs what denoise() needs, and set_spectral_bins before the render; nothing the context holds changes."""
+        W, H = self.options.res
+        B = getattr(self, "_spectral_bins", 0)                                     # what set_spectral_bins set; 0: off, and ssx_denoise_spectral says so
+        mean = np.zeros((H, W, B), dtype=np.float32)
+        out = np.zeros((H, W, 4), dtype=np.float32) if return_image else None
+        var = np.zeros((H, W), dtype=np.float32) if return_image else None
+        p = self._denoise_params(levels, sigma_l, sigma_a)
+        self._check(self._lib.ssx_denoise_spectral(self._ctx, C.byref(p), mean.ctypes.data if B else None, None if out is None else out.ctypes.data,
+                                                   None if var is None else var.ctypes.data))
+        return (mean, out, var) if return_image else mean
 
     def debug_sample_flux(self, **over):
         """ssx_debug_sample_flux (spectral output on): per-sample (flux [H, W, spp, 4] float32, lambda_0 [H, W, spp] float32)."""

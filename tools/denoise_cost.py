@@ -3,7 +3,10 @@
 level, alternating between the two in one process and on one context (the guide buffers are cached after the first call, the buffers allocated: what is timed
 is the variance kernel, the L launches of ssx_atrous_kernel, the synchronisation and -- asked for with --read-back -- the copy of the image to the host).
 Medians of wall-clock times per call; the figure is to be read next to the render time of the headline workload (21.3 ms).
-Prints one JSON line.      python tools/denoise_cost.py [--calls 64] [--levels 5] [--res 512] [--spp 16]"""
+Prints one JSON line.      python tools/denoise_cost.py [--calls 64] [--levels 5] [--res 512] [--spp 16]
+With --spectral B the same for ssx_denoise_spectral with B bins (mean_out NULL unless --read-back), alternating with ssx_denoise at the same L in the same
+loop -- the XYZ filter is the baseline the spectral filter is read against -- and next to the wall-clock time of the render of that image (spectral output and
+noise estimate on, --spp samples in four launches) and the bytes a level must move: 40 + 4E read and 20 + 4E written per pixel, E = B + B / 4."""
 import argparse
 import ctypes
 import json
@@ -23,11 +26,16 @@ def main():
     ap.add_argument("--res", type=int, default=512)
     ap.add_argument("--spp", type=int, default=16)
     ap.add_argument("--read-back", action="store_true")
+    ap.add_argument("--spectral", type=int, default=0, metavar="B")
     a = ap.parse_args()
     r = Renderer(Options(scene_name="cornell-srgb", res=(a.res, a.res), spp=a.spp, spp_per_launch=max(1, a.spp // 4), texture="crystal-lizard-512.png"))
     r.set_noise_estimate(True)
+    if a.spectral:
+        r.set_spectral_bins(a.spectral)
     r.render_start(); r.render_wait()
     import numpy as np
+    if a.spectral:
+        return spectral(a, r, np)
     out = np.zeros((a.res, a.res, 4), dtype=np.float32)
     dst = out.ctypes.data if a.read_back else None
 
@@ -51,6 +59,45 @@ def main():
                       "ms_per_further_level": round(per_level, 4), "guides_first_call_ms": round(guides_ms, 3),
                       "bytes_per_level_compulsory": pixels * 60, "bytes_per_level_gathered": pixels * (25 * 40 + 9 * 20 + 20),
                       "headline_render_ms_parent": 21.3}))
+
+
+def spectral(a, r, np):
+    B, pixels = a.spectral, a.res * a.res
+    E = B + B // 4
+    mean = np.zeros((a.res, a.res, B), dtype=np.float32)
+    image = np.zeros((a.res, a.res, 4), dtype=np.float32)
+
+    def call(which, levels):
+        p = r._denoise_params(levels, 1.0, 0.1)
+        t = time.perf_counter()
+        if which == "spectral":
+            r._check(r._lib.ssx_denoise_spectral(r._ctx, ctypes.byref(p), mean.ctypes.data if a.read_back else None, image.ctypes.data if a.read_back else None, None))
+        else:
+            r._check(r._lib.ssx_denoise(r._ctx, ctypes.byref(p), image.ctypes.data if a.read_back else None, None))
+        return (time.perf_counter() - t) * 1e3
+
+    def render():
+        t = time.perf_counter()
+        r._check(r._lib.ssx_render_start(r._ctx, ctypes.byref(r.params())))
+        r._check(r._lib.ssx_render_wait(r._ctx, None))
+        return (time.perf_counter() - t) * 1e3
+
+    kinds = (("spectral", a.levels), ("spectral", 1), ("xyz", a.levels))
+    for k in kinds + kinds:  # warm-up: guides, buffers
+        call(*k)
+    ms = {k: [] for k in kinds}
+    for _ in range(a.calls):
+        for k in kinds:
+            ms[k].append(call(*k))
+    renders = [render() for _ in range(5)][1:]
+    summary = lambda v: {"median_ms": round(statistics.median(v), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4), "n": len(v)}
+    per_level = (statistics.median(ms[kinds[0]]) - statistics.median(ms[kinds[1]])) / max(1, a.levels - 1)
+    must = pixels * ((40 + 4 * E) + (20 + 4 * E))
+    print(json.dumps({"image": "cornell-srgb %d^2" % a.res, "bins": B, "channels": E, "levels": a.levels, "read_back": bool(a.read_back),
+                      "denoise_spectral": summary(ms[kinds[0]]), "denoise_spectral_one_level": summary(ms[kinds[1]]), "denoise_xyz": summary(ms[kinds[2]]),
+                      "ms_per_further_level": round(per_level, 4), "render_ms_spp_%d" % a.spp: summary(renders),
+                      "bytes_per_level_must_move": must, "bytes_per_level_gathered": pixels * (25 * 40 + 9 * 20 + 25 * 16 * ((E + 3) // 4) + 16 * ((E + 3) // 4)),
+                      "must_move_GBps_at_per_level_time": round(must / max(per_level, 1e-9) / 1e6, 1)}))
 
 
 if __name__ == "__main__":
