@@ -33,7 +33,7 @@ extern "C" {
  *      ssx_jit_counters, ssx_sums_info, ssx_rccl_groups_made, ssx_done_tiles and ssx_render_params.tile_major and tile_skew (the
  *      struct grew by 8 bytes) are new.  Added since without a change of existing entry points or structures (same version): ssx_units_info,
  *      ssx_rccl_probe (round 6); ssx_render_params.libm, appended (a caller with the struct_size before it gets SSX_LIBM_BUILD); the progressive
- *      rendering, spectral output and denoising entry points below. */
+ *      rendering, spectral output, denoising and develop entry points below. */
 #define SSX_ABI_VERSION 2
 
 enum {
@@ -535,6 +535,60 @@ int ssx_denoise_channels(ssx_ctx* ctx, const ssx_denoise_params* params, uint32_
  * bins (after ssx_sums_import it holds none) -- otherwise SSX_ERR_STATE with the reason in ssx_last_error.  It reads only: image, sums, noise and spectral
  * state stay as they are, so an ssx_render_continue afterwards leaves the bits of a one-shot render in the image and in ssx_spectral_read. */
 int ssx_denoise_spectral(ssx_ctx* ctx, const ssx_denoise_params* params, float* mean_out /* [H][W][B] */, float* xyza_out, float* var_out);
+
+/* ---- Developing the spectral bins: observers, filters, sensors (appended; same ABI version) -------------------------------------------------------
+ * The way back from the bins, raw or denoised, to a colour image: one linear map per pixel from B bins to C output channels, so that a render can be viewed
+ * under another observer, through a colour filter, with a camera's response curves or under another illuminant without rendering again.  The definition is
+ * this library's; a restatement in numpy gives the same bits (tests/develop_ref.py).
+ *
+ * DEVELOP.  Per pixel p, B values q[p][b] (B in {4, 8, ..., 64}) and a weight matrix W[c][b], C output channels, 1 <= C <= 16:
+ *     out[p][c] = sum over b of q[p][b] * W[c][b]
+ * in binary32: acc = 0.0f, then acc = acc + (q[p][b] * W[c][b]) for b = 0, 1, ..., B-1 -- the product is rounded before the add, no contraction, no
+ * reassociation.  Non-finite values go through the arithmetic as they are.
+ *
+ * SOURCES OF q.
+ *   raw       from the context's state, n = ssx_done_spp, M = B / 4, S the sums of "Spectral radiance output":
+ *                 q[p][b] = (float)((S[p][b] * (double)M) / (double)n)        the multiply, then the divide, both binary64
+ *             This is NOT mean[p][b]: at 16 spp and 64 bins a third of the sub-bins hold no sample and mean reads 0 there.  S * M / n is the estimator the
+ *             integrator itself uses for the pixel (every sample counts once; the sub-bin of a sample is drawn uniformly among M, so each holds n / M in
+ *             expectation), with the observer replaced by its average over the bin: an empty sub-bin costs nothing and biases nothing.  Pixels the context
+ *             does not own read +0 in every channel.
+ *   denoised  q[p][b] = out[p][b] of ssx_denoise_spectral (the ratio of "Denoising the spectral bins") for the same parameters.
+ *   caller's  any [height][width][B] float array, through ssx_develop_images.
+ *
+ * WEIGHTS are built on the host (libssx_host.so ssh_develop_weights, include/ssx_host.h), in binary64, and rounded to binary32 once at the end.  A tabulated
+ * spectrum T -- n samples s_0 .. s_(n-1) over [low, high] -- is the function the host Spectrum's linear sampler evaluates, restated in binary64:
+ *     delta = ((double)high - (double)low) / (n - 1);   pos = (lambda - (double)low) / delta;   i = floor(pos);   f = pos - i
+ *     T(lambda) = s(i) * (1.0 - f) + s(i + 1) * f,      s(k) = (double)s_k for 0 <= k < n and 0 otherwise
+ * OUTSIDE THE TABLE'S RANGE the sampler does not clamp: the table runs linearly to zero over one step beyond either end (knots low - delta and high + delta
+ * carry the value 0) and is zero beyond.  T is piecewise linear with knots low + k * delta, k = -1 .. n.
+ * Bin b covers [e_b, e_(b+1)], e_b = (double)lambda_min + b * ((double)lambda_step / M).  For response curves r_c, an optional filter g (a missing g is 1) and an
+ * optional gain per bin (a missing one is 1):
+ *     I[c][b] = integral over [e_b, e_(b+1)] of r_c(lambda) * g(lambda) dlambda;        W[c][b] = (float)(gain[b] * I[c][b])
+ * integrated exactly, piecewise: the breakpoints are e_b, e_(b+1) and every knot of either table strictly between them, sorted, equal ones taken once; on each
+ * piece [a, z] the integrand is a quadratic at most, so Simpson's rule is exact: ((z - a) / 6.0) * ((F(a) + 4.0 * F(0.5 * (a + z))) + F(z)), F = r_c * g (or
+ * r_c); the pieces are added in ascending order starting from 0.0.  The bin's width is inside W: q is flux per nm and out has the units of the XYZ image.
+ * Output space: xyz -- the weights as integrated; lrgb -- the host's XYZ -> BT.709 matrix m (ssh_color_values "xyz_to_lrgb", column-major) applied to the three
+ * rows in binary64 before the rounding: (m[0][r] * X + m[1][r] * Y) + m[2][r] * Z with X, Y, Z = gain[b] * I[0..2][b].
+ * RELIGHTING.  relight_gain(old, new)[b] = (integral of new over bin b) / (integral of old over bin b), 0 where the integral of old is 0 (ssh_relight_gain);
+ * it is passed as the gain.  This is exact only when every emitter of the scene carries `old` up to a scale -- all light then has the factor old(lambda) -- and
+ * only up to the variation of new / old inside a bin.
+ *
+ * ON THE DEVICE the map is one memory-bound kernel: one wave per owned 8x8 tile (raw; it reads S[tile slot][bin][pixel of the tile], 512 consecutive bytes
+ * per bin) or one lane per pixel (images), the weights read at wave-uniform addresses from a buffer of at most 4 KB, up to 16 accumulators in registers.
+ * With the feature unused nothing is allocated and nothing is launched. */
+
+/* DEVELOP as a pure function of its arguments (needs no scene): q [height][width][bins], weights [channels][bins] -> out [height][width][channels], all
+ * row-major floats.  SSX_ERR_ARG: channels outside 1..16, bins not a multiple of 4 in 4..64, a NULL pointer, an empty or too large image. */
+int ssx_develop_images(ssx_ctx* ctx, uint32_t width, uint32_t height, uint32_t bins, const float* q /* [H][W][B] */, const float* weights /* [C][B] */,
+                       uint32_t channels, float* out /* [H][W][C] */);
+/* DEVELOP from the context's own state, without the bins leaving the device: denoise == NULL selects the raw source, otherwise the denoised source with these
+ * parameters (the filter runs as in ssx_denoise_spectral and its ratio is developed where it lies).  out: [height][width][channels] of the render's size, row
+ * 0 = bottom (NULL: the kernels run and the result stays on the device -- for measurements).  It reads only: image, sums, noise and spectral state stay as they are, so an
+ * ssx_render_continue afterwards leaves the bits of a one-shot render in the image and in ssx_spectral_read.  SSX_ERR_STATE, with the reason in
+ * ssx_last_error: spectral output is off, a render runs, the context holds no valid bins (nothing rendered, or ssx_sums_import, or a changed bin count),
+ * ssx_done_spp == 0, and, for the denoised source, whatever ssx_denoise_spectral refuses.  SSX_ERR_ARG: channels outside 1..16, a NULL weights. */
+int ssx_spectral_develop(ssx_ctx* ctx, const ssx_denoise_params* denoise, const float* weights /* [C][B] */, uint32_t channels, float* out /* [H][W][C] */);
 
 /* ---- Diagnostics for the parity tests (not part of the reference's interface) ---------------------
  * ssx_debug_eval runs one building block of the path kernel -- the same device function the kernel

@@ -73,6 +73,24 @@ int ssh_sums_merge(double* dst, double* dst_s2, const double* src, const double*
  * same array.  The CLI's --spectral-output writes the spectral image with it: shape (height, width, bins), row 0 = bottom. */
 int ssh_save_npy_f32(const char* path, const float* data, const uint32_t* shape, uint32_t ndim);
 
+/* ---- Developing the spectral bins (ssx.h "Developing the spectral bins": the definitions are there, operation by operation) ----------------------------------- */
+typedef struct ssh_spectrum_t { const float* samples; uint32_t n; float low, high; } ssh_spectrum_t; /* n >= 2 uniform samples over [low, high] */
+enum { SSH_SPACE_XYZ = 0, SSH_SPACE_LRGB = 1 };
+/* The weight matrix W[channels][bins] of ssx_develop_images / ssx_spectral_develop for bins of a render with this lambda_min and lambda_step (ssx_scene_desc).
+ * responses: `channels` response curves (a camera's, 1..16), or NULL for the x-bar, y-bar, z-bar tables of `observer` (1931 | 2006, from data_dir; channels must
+ * then be 3).  filter: an optional spectrum in front of the lens (NULL: none).  gain: an optional factor per bin, e.g. ssh_relight_gain's (NULL: none).  space:
+ * SSH_SPACE_XYZ -- the weights as integrated; SSH_SPACE_LRGB -- three rows, taken to linear BT.709 by the XYZ -> lRGB matrix of `observer`'s colour tables (needs
+ * observer and data_dir also with responses given).  weights: float [channels][bins]; weights64 (optional): the same before the final rounding. */
+int ssh_develop_weights(const char* data_dir, int observer, const ssh_spectrum_t* responses, uint32_t channels, const ssh_spectrum_t* filter, const double* gain,
+                        int space, uint32_t bins, float lambda_min, float lambda_step, float* weights, double* weights64);
+/* gain[b] = integral of to_spectrum over bin b / integral of from_spectrum, 0 where the latter is 0.  As a gain it turns a render lit by from_spectrum into one lit
+ * by to_spectrum -- exactly only when every emitter of the scene carries from_spectrum up to a scale (ssh_emitter_spectrum), and up to the variation of the ratio
+ * inside a bin. */
+int ssh_relight_gain(const ssh_spectrum_t* from_spectrum, const ssh_spectrum_t* to_spectrum, uint32_t bins, float lambda_min, float lambda_step, double* gain);
+/* *spectrum = index (in desc->spectra) of the emission spectrum that all emissive materials of the scene share up to a scale.  SSX_ERR_SCENE, with the reason in
+ * ssh_last_error, when two of them differ or none is emissive: what the CLI's --develop-relight refuses. */
+int ssh_emitter_spectrum(const ssx_scene_desc* desc, uint32_t* spectrum);
+
 const char* ssh_last_error(void);
 
 #ifdef __cplusplus

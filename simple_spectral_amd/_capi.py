@@ -82,6 +82,12 @@ class SsxDenoiseParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("levels", C.c_uint32), ("sigma_l", C.c_float), ("sigma_a", C.c_float)]
 
 
+class SshSpectrum(C.Structure):
+    """ssh_spectrum_t: n uniform samples over [low, high] (include/ssx_host.h)."""
+    _fields_ = [("samples", C.POINTER(C.c_float)), ("n", C.c_uint32), ("low", C.c_float), ("high", C.c_float)]
+
+
+SSH_SPACE_XYZ, SSH_SPACE_LRGB = 0, 1
 SSX_LIBM_BUILD, SSX_LIBM_GLIBC_2_35 = 0, 1
 LIBM_MODES = {"build": SSX_LIBM_BUILD, "glibc-2.35": SSX_LIBM_GLIBC_2_35}
 
@@ -101,7 +107,8 @@ HIP_SYMBOLS = ["ssx_create", "ssx_destroy", "ssx_upload_scene", "ssx_render_star
                "ssx_debug_eval", "ssx_debug_samples", "ssx_debug_sweep", "ssx_kernel_variant", "ssx_kernel_name", "ssx_scratch_info", "ssx_calibration_info", "ssx_set_jit", "ssx_debug_pass1_source", "ssx_done_spp", "ssx_reduce_rccl", "ssx_sums_info", "ssx_rccl_groups_made", "ssx_jit_status", "ssx_jit_counters", "ssx_done_tiles", "ssx_render_device_wait", "ssx_units_info", "ssx_rccl_probe",
                "ssx_render_continue", "ssx_scene_digest", "ssx_sums_export", "ssx_sums_import", "ssx_set_noise_estimate", "ssx_noise_info",
                "ssx_set_spectral_bins", "ssx_spectral_read", "ssx_debug_sample_flux",
-               "ssx_guides", "ssx_denoise_images", "ssx_denoise", "ssx_denoise_channels", "ssx_denoise_spectral"]
+               "ssx_guides", "ssx_denoise_images", "ssx_denoise", "ssx_denoise_channels", "ssx_denoise_spectral",
+               "ssx_develop_images", "ssx_spectral_develop"]
 (SSX_SWEEP_RCP, SSX_SWEEP_SQRT, SSX_SWEEP_INVERSESQRT, SSX_SWEEP_SIN, SSX_SWEEP_COS, SSX_SWEEP_ACOS, SSX_SWEEP_DIV_PI,
  SSX_SWEEP_RCP64, SSX_SWEEP_DIV_PAIRS, SSX_SWEEP_ACOS_SIN, SSX_SWEEP_SIN_PROOF, SSX_SWEEP_COS_PROOF, SSX_SWEEP_ACOS_PROOF) = range(1, 14)
 # ssx_debug_eval ops (include/ssx.h)
@@ -111,7 +118,8 @@ HIP_SYMBOLS = ["ssx_create", "ssx_destroy", "ssx_upload_scene", "ssx_render_star
 (SSX_DBG_GLIBC_MATH, SSX_DBG_SPHTRI_GLIBC, SSX_DBG_ARVO_GLIBC, SSX_DBG_SAMPLE_LIGHT_GLIBC, SSX_DBG_COSHEMI_GLIBC) = range(11, 16)
 (SSX_SWEEP_GLIBC_SIN, SSX_SWEEP_GLIBC_COS, SSX_SWEEP_GLIBC_ACOS, SSX_SWEEP_GLIBC_COS_LDS) = range(14, 18)
 HOST_SYMBOLS = ["ssh_scene_create", "ssh_scene_create_ex", "ssh_scene_destroy", "ssh_scene_desc", "ssh_xyza_to_srgba", "ssh_save_image",
-                "ssh_load_png_rgb8", "ssh_free", "ssh_color_values", "ssh_last_error", "ssh_checkpoint_save", "ssh_checkpoint_load", "ssh_sums_merge", "ssh_save_npy_f32"]
+                "ssh_load_png_rgb8", "ssh_free", "ssh_color_values", "ssh_last_error", "ssh_checkpoint_save", "ssh_checkpoint_load", "ssh_sums_merge", "ssh_save_npy_f32",
+                "ssh_develop_weights", "ssh_relight_gain", "ssh_emitter_spectrum"]
 
 _hip = None
 _host = None
@@ -144,6 +152,10 @@ def host_lib():
                                             C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.POINTER(C.c_double))]
         lib.ssh_sums_merge.argtypes = [vp, vp, vp, vp, C.POINTER(SsxSumsInfo)]
         lib.ssh_save_npy_f32.argtypes = [C.c_char_p, vp, C.POINTER(C.c_uint32), C.c_uint32]
+        lib.ssh_develop_weights.argtypes = [C.c_char_p, C.c_int, C.POINTER(SshSpectrum), C.c_uint32, C.POINTER(SshSpectrum), vp, C.c_int, C.c_uint32,
+                                            C.c_float, C.c_float, vp, vp]
+        lib.ssh_relight_gain.argtypes = [C.POINTER(SshSpectrum), C.POINTER(SshSpectrum), C.c_uint32, C.c_float, C.c_float, vp]
+        lib.ssh_emitter_spectrum.argtypes = [C.POINTER(SsxSceneDesc), C.POINTER(C.c_uint32)]
         _host = lib
     return _host
 
@@ -311,6 +323,9 @@ def hip_lib():
         if not override or hasattr(lib, "ssx_denoise_spectral"):  # extra channels under the filter's weights
             lib.ssx_denoise_channels.argtypes = [vp, C.POINTER(SsxDenoiseParams), C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp]
             lib.ssx_denoise_spectral.argtypes = [vp, C.POINTER(SsxDenoiseParams), vp, vp, vp]
+        if not override or hasattr(lib, "ssx_spectral_develop"):  # developing the spectral bins
+            lib.ssx_develop_images.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, vp]
+            lib.ssx_spectral_develop.argtypes = [vp, C.POINTER(SsxDenoiseParams), vp, C.c_uint32, vp]
         lib.ssx_kernel_variant.argtypes = [vp]
         lib.ssx_kernel_name.argtypes = [vp]
         lib.ssx_kernel_name.restype = C.c_char_p

@@ -4,7 +4,7 @@
 // The context, its launches, the render worker (render_sample_walk / render_tile_walk behind start_worker), the render entry points and the
 // diagnostics are here; scene packing is in ssx_pack.h, RCCL in ssx_rccl.h, the pixel ownership rule in ssx_pixel_grid.h, continue / export /
 // import of the sums and the noise estimate (entry points and their kernels) in ssx_progressive.hip, the spectral output in ssx_spectral.hip,
-// the guide buffers and the denoising filter in ssx_denoise.hip.
+// the guide buffers and the denoising filter in ssx_denoise.hip, the develop of the spectral bins in ssx_develop.hip.
 #include "ssx_kernels.hip"
 #include "ssx_debug.hip"
 
@@ -145,6 +145,7 @@ struct ssx_ctx {
 	// the uploaded scene at guides_width x guides_height (0: none; ssx_upload_scene drops them), d_denoise the filter's inputs and ping-pong buffers,
 	// d_denoise_channels those of the extra channels (ssx_denoise_channels / ssx_denoise_spectral only).
 	DeviceBuffer d_guides, d_denoise, d_denoise_channels;
+	DeviceBuffer d_develop;             // ssx_develop_images / ssx_spectral_develop (csrc/ssx_develop.hip): weights | output | the caller's bins; nothing until one of them is called
 	uint32_t guides_width = 0, guides_height = 0;
 
 	// optional per-kernel timing (ssx_set_timing): events around each stage of each batch
@@ -1426,3 +1427,4 @@ int ssx_kernel_info(ssx_ctx* ctx, int* vgprs, int* sgprs, int* lds_bytes, int* s
 #include "ssx_progressive.hip"
 #include "ssx_spectral.hip"
 #include "ssx_denoise.hip"
+#include "ssx_develop.hip"

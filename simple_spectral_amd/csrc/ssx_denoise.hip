@@ -517,6 +517,27 @@ int denoise_own_inputs(ssx_ctx* ctx, DenoiseBuffers* b) {
 	return SSX_OK;
 }
 
+// The device part of ssx_denoise_spectral, shared with ssx_spectral_develop (ssx_develop.hip), after denoise_own_state_ready(.., true): the channels e0 of the
+// bins, the L levels and the ratio, all queued on the context's stream.  On return (not yet waited for) the filtered image and variance are in b->c / b->var
+// [(levels - 1) & 1] and out[p][b], row-major [height][width][B], in cb->stage.
+int denoise_spectral_device(ssx_ctx* ctx, const ssx_denoise_params& dp, DenoiseBuffers* b, ChannelBuffers* cb) {
+	const ssx_render_params& p = ctx->cur;
+	const size_t pixels = (size_t)p.width * p.height;
+	const uint32_t B = ctx->spectral_bins, M = B / 4u;
+	int rc = channels_check_size(ctx, pixels, B + M, "ssx_denoise_spectral");
+	if (rc) return rc;
+	if ((rc = denoise_own_inputs(ctx, b))) return rc;
+	if ((rc = channel_buffers(ctx, pixels, B + M, B, cb))) return rc;
+	hipLaunchKernelGGL(ssx_spectral_channels_kernel, blocks_of(pixels * cb->groups), dim3(256), 0, ctx->stream, ctx->d_spectral_sums.as<const double>(),
+	                   ctx->d_spectral_counts.as<const uint32_t>(), cb->e[0], pixel_grid(&p), M, (double)ctx->done_spp.load());
+	SSX_HIP(ctx, hipGetLastError());
+	const SsxGuides g = guides_of(ctx, pixels);
+	if ((rc = launch_atrous(ctx, dp, p.width, p.height, ctx->d_out.as<const float4>(), b->var_in, g.prim, g.albedo, *b, cb))) return rc;
+	hipLaunchKernelGGL(ssx_spectral_ratio_kernel, blocks_of(pixels * B), dim3(256), 0, ctx->stream, cb->e[dp.levels & 1u], cb->stage, (uint32_t)pixels, M);
+	SSX_HIP(ctx, hipGetLastError());
+	return SSX_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -618,21 +639,11 @@ int ssx_denoise_spectral(ssx_ctx* ctx, const ssx_denoise_params* params, float* 
 	if ((rc = denoise_own_state_ready(ctx, "ssx_denoise_spectral", true))) return rc;
 	const ssx_render_params& p = ctx->cur;
 	const size_t pixels = (size_t)p.width * p.height;
-	const uint32_t B = ctx->spectral_bins, M = B / 4u;
-	if ((rc = channels_check_size(ctx, pixels, B + M, "ssx_denoise_spectral"))) return rc;
 	DenoiseBuffers b;
 	ChannelBuffers cb;
-	if ((rc = denoise_own_inputs(ctx, &b))) return rc;
-	if ((rc = channel_buffers(ctx, pixels, B + M, B, &cb))) return rc;
-	hipLaunchKernelGGL(ssx_spectral_channels_kernel, blocks_of(pixels * cb.groups), dim3(256), 0, ctx->stream, ctx->d_spectral_sums.as<const double>(),
-	                   ctx->d_spectral_counts.as<const uint32_t>(), cb.e[0], pixel_grid(&p), M, (double)ctx->done_spp.load());
-	SSX_HIP(ctx, hipGetLastError());
-	const SsxGuides g = guides_of(ctx, pixels);
-	if ((rc = launch_atrous(ctx, dp, p.width, p.height, ctx->d_out.as<const float4>(), b.var_in, g.prim, g.albedo, b, &cb))) return rc;
-	hipLaunchKernelGGL(ssx_spectral_ratio_kernel, blocks_of(pixels * B), dim3(256), 0, ctx->stream, cb.e[dp.levels & 1u], cb.stage, (uint32_t)pixels, M);
-	SSX_HIP(ctx, hipGetLastError());
+	if ((rc = denoise_spectral_device(ctx, dp, &b, &cb))) return rc;
 	if ((rc = denoise_read_back(ctx, dp, pixels, b, xyza_out, var_out))) return rc; // (waits for the stream)
-	if (mean_out) SSX_HIP(ctx, hipMemcpy(mean_out, cb.stage, pixels * B * sizeof(float), hipMemcpyDeviceToHost));
+	if (mean_out) SSX_HIP(ctx, hipMemcpy(mean_out, cb.stage, pixels * ctx->spectral_bins * sizeof(float), hipMemcpyDeviceToHost));
 	return SSX_OK;
 }
 

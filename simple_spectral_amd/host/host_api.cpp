@@ -3,6 +3,7 @@
 
 #include "checkpoint.hpp"
 #include "color.hpp"
+#include "develop.hpp"
 #include "image_io.hpp"
 #include "scene.hpp"
 
@@ -163,6 +164,50 @@ int ssh_save_npy_f32(const char* path, const float* data, const uint32_t* shape,
 		ssx::save_npy_f32(path, data, dims, ndim);
 		return SSX_OK;
 	} catch (const ssx::HostError& e) { return report(e); }
+}
+
+int ssh_develop_weights(const char* data_dir, int observer, const ssh_spectrum_t* responses, uint32_t channels, const ssh_spectrum_t* filter, const double* gain,
+                        int space, uint32_t bins, float lambda_min, float lambda_step, float* weights, double* weights64) {
+	if (!weights) { g_error = "NULL argument"; return SSX_ERR_ARG; }
+	if (space != SSH_SPACE_XYZ && space != SSH_SPACE_LRGB) { g_error = "ssh_develop_weights: space must be SSH_SPACE_XYZ or SSH_SPACE_LRGB"; return SSX_ERR_ARG; }
+	if ((!responses || space == SSH_SPACE_LRGB) && !data_dir) { g_error = "ssh_develop_weights: the observer's tables need data_dir"; return SSX_ERR_ARG; }
+	if (!responses && channels != 3) { g_error = "ssh_develop_weights: an observer has three channels"; return SSX_ERR_ARG; }
+	try {
+		std::unique_ptr<ssx::ColorData> color;
+		if (!responses || space == SSH_SPACE_LRGB) color = std::make_unique<ssx::ColorData>(data_dir, observer);
+		auto table = [](const ssh_spectrum_t& t) {
+			if (!t.samples) throw ssx::HostError{ SSX_ERR_ARG, "a spectrum table without samples" };
+			return ssx::Spectrum(std::vector<float>(t.samples, t.samples + t.n), t.low, t.high);
+		};
+		std::vector<ssx::Spectrum> r;
+		if (responses) for (uint32_t c = 0; c < channels; ++c) r.push_back(table(responses[c]));
+		else r = { color->std_obs_xbar, color->std_obs_ybar, color->std_obs_zbar };
+		ssx::Spectrum g;
+		if (filter) g = table(*filter);
+		const std::vector<double> w = ssx::develop_weights(r, filter ? &g : nullptr, gain, space == SSH_SPACE_LRGB ? &color->matr_xyz_to_lrgb.m[0][0] : nullptr,
+		                                                   bins, lambda_min, lambda_step);
+		for (size_t i = 0; i < w.size(); ++i) { weights[i] = static_cast<float>(w[i]); if (weights64) weights64[i] = w[i]; }
+		return SSX_OK;
+	} catch (const ssx::HostError& e) { return report(e); }
+	catch (const std::exception& e) { g_error = e.what(); return SSX_ERR_DATA; }
+}
+
+int ssh_relight_gain(const ssh_spectrum_t* from_spectrum, const ssh_spectrum_t* to_spectrum, uint32_t bins, float lambda_min, float lambda_step, double* gain) {
+	if (!from_spectrum || !to_spectrum || !from_spectrum->samples || !to_spectrum->samples || !gain) { g_error = "NULL argument"; return SSX_ERR_ARG; }
+	try {
+		const ssx::Spectrum a(std::vector<float>(from_spectrum->samples, from_spectrum->samples + from_spectrum->n), from_spectrum->low, from_spectrum->high);
+		const ssx::Spectrum b(std::vector<float>(to_spectrum->samples, to_spectrum->samples + to_spectrum->n), to_spectrum->low, to_spectrum->high);
+		const std::vector<double> g = ssx::relight_gain(a, b, bins, lambda_min, lambda_step);
+		memcpy(gain, g.data(), g.size() * sizeof(double));
+		return SSX_OK;
+	} catch (const ssx::HostError& e) { return report(e); }
+	catch (const std::exception& e) { g_error = e.what(); return SSX_ERR_DATA; }
+}
+
+int ssh_emitter_spectrum(const ssx_scene_desc* desc, uint32_t* spectrum) {
+	if (!desc || !spectrum) { g_error = "NULL argument"; return SSX_ERR_ARG; }
+	try { *spectrum = ssx::emitter_spectrum(*desc); return SSX_OK; }
+	catch (const ssx::HostError& e) { return report(e); }
 }
 
 int ssh_color_values(const ssh_scene* scene, const char* name, float* out, int capacity) {

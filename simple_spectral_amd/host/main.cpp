@@ -16,10 +16,18 @@
 // --spectral-denoise (with --spectral-output): the file holds the bins filtered with the weights of that filter (include/ssx.h "Denoising the spectral bins").  It
 // renders as --denoise does (noise estimate on, the same launch rule and refusals) and takes --denoise-levels and --denoise-sigma; the output image is the
 // filtered one only if --denoise is given too.
+// Developing the bins (include/ssx.h "Developing the spectral bins"): --develop-output=PATH with --spectral-bins=N writes the image developed from the bins on the
+// device -- through the same XYZ -> sRGB store and writers as --output -- under --develop-observer=1931|2006 (default: the render's), through --develop-filter=FILE.csv
+// (a spectrum in the format of data/*.csv, its range in the name: NAME-LOW+STEP+HIGH.csv) and relit by --develop-relight=NEW.csv (the emitters' spectrum replaced by
+// NEW; refused unless all emissive materials share one spectrum up to a scale).  With --spectral-denoise the filtered bins are developed.  It does not need
+// --spectral-output, and has its refusals (--resume, --tile-major, --rgb, --libm=glibc-2.35).
 #include "renderer.hpp"
+
+#include "develop.hpp"
 
 #include <chrono>
 #include <csignal>
+#include <memory>
 #include <cstdio>
 #include <string>
 #include <thread>
@@ -51,7 +59,9 @@ void print_usage() {
 		"    `--spectral-output=<file.npy>` [`--spectral-bins=<n>`: 4, 8, ..., 64; default 16] (not with `--resume`)\n"
 		"    `--denoise` [`--denoise-levels=<n>`: 1..6; default 5] [`--denoise-sigma=<l>,<a>`; default 1,0.1] (the output image is the filtered one; not with `-spp=1`)\n"
 		"    `--guides-output=<file.npy>` (first hit per pixel: primitive, depth, normal, albedo)\n"
-		"    `--spectral-denoise` (with `--spectral-output`: the file holds the bins filtered with `--denoise`'s weights, levels and sigmas; not with `-spp=1`)\n");
+		"    `--spectral-denoise` (with `--spectral-output`: the file holds the bins filtered with `--denoise`'s weights, levels and sigmas; not with `-spp=1`)\n"
+		"    `--develop-output=<image>` (needs `--spectral-bins=<n>`) [`--develop-observer=1931|2006`] [`--develop-filter=<name-low+step+high.csv>`] [`--develop-relight=<new.csv>`]\n"
+		"          (the image developed from the wavelength bins; with `--spectral-denoise` from the filtered bins)\n");
 }
 
 struct ArgList {
@@ -100,6 +110,9 @@ struct Progressive { // the flags of the progressive modes
 	bool noise_step_given = false;
 	ssx::Renderer::DenoiseParams denoise_params;
 	std::string guides_output;   // --guides-output: "" = none
+	std::string develop_output, develop_filter, develop_relight; // --develop-output / --develop-filter / --develop-relight: "" = none
+	int develop_observer = 0;    // --develop-observer: 0 = the render's
+	bool spectral_bins_given = false;
 };
 
 void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progressive* g) {
@@ -158,7 +171,15 @@ void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progress
 	if (g->noise_target >= 0.0 && g->max_samples == 0) { std::fprintf(stderr, "`--noise-target` needs `--max-samples=<n>`!\n"); throw -2; }
 	if (g->noise_target >= 0.0 && !g->resume.empty()) { std::fprintf(stderr, "`--noise-target` cannot be combined with `--resume`!\n"); throw -2; }
 	if (a.take("--spectral-output", "", &v)) g->spectral_output = v;
+	if (a.take("--develop-output", "", &v)) g->develop_output = v;
+	if (a.take("--develop-filter", "", &v)) g->develop_filter = v;
+	if (a.take("--develop-relight", "", &v)) g->develop_relight = v;
+	if (a.take("--develop-observer", "", &v)) {
+		if (v == "1931") g->develop_observer = 1931; else if (v == "2006") g->develop_observer = 2006;
+		else { std::fprintf(stderr, "Invalid value for --develop-observer (1931|2006)!\n"); throw -2; }
+	}
 	if (a.take("--spectral-bins", "", &v)) {
+		g->spectral_bins_given = true;
 		try { g->spectral_bins = to_pos(v); } catch (int) { g->spectral_bins = 0; }
 		if (g->spectral_bins == 0 || g->spectral_bins > 64 || g->spectral_bins % 4) { std::fprintf(stderr, "Invalid value for --spectral-bins (a multiple of 4 up to 64)!\n"); throw -2; }
 	}
@@ -168,6 +189,18 @@ void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progress
 	}
 	if (!g->spectral_output.empty() && (o->tile_major || o->rgb_mode || o->libm != SSX_LIBM_BUILD)) {
 		std::fprintf(stderr, "`--spectral-output` cannot be combined with `--tile-major`, `--rgb` or `--libm=glibc-2.35`!\n");
+		throw -2;
+	}
+	if (g->develop_output.empty() && (!g->develop_filter.empty() || !g->develop_relight.empty() || g->develop_observer)) {
+		std::fprintf(stderr, "`--develop-observer`, `--develop-filter` and `--develop-relight` need `--develop-output=<image>`!\n");
+		throw -2;
+	}
+	if (!g->develop_output.empty() && !g->spectral_bins_given) {
+		std::fprintf(stderr, "`--develop-output` needs `--spectral-bins=<n>`: it develops the wavelength bins of the render!\n");
+		throw -2;
+	}
+	if (!g->develop_output.empty() && (!g->resume.empty() || o->tile_major || o->rgb_mode || o->libm != SSX_LIBM_BUILD)) {
+		std::fprintf(stderr, "`--develop-output` cannot be combined with `--resume`, `--tile-major`, `--rgb` or `--libm=glibc-2.35`: such a render has no wavelength bins!\n");
 		throw -2;
 	}
 	if (a.take("--denoise", "", &v)) {
@@ -196,7 +229,7 @@ void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progress
 	}
 	if (a.take("--spectral-denoise", "", &v)) {
 		if (v != "--spectral-denoise") { std::fprintf(stderr, "`--spectral-denoise` does not take a value!\n"); throw -2; }
-		if (g->spectral_output.empty()) { std::fprintf(stderr, "`--spectral-denoise` needs `--spectral-output=<file.npy>`: it filters the bins written there!\n"); throw -2; }
+		if (g->spectral_output.empty() && g->develop_output.empty()) { std::fprintf(stderr, "`--spectral-denoise` needs `--spectral-output=<file.npy>`: it filters the bins written there!\n"); throw -2; }
 		g->spectral_denoise = true;
 	}
 	const bool filters = g->denoise || g->spectral_denoise; // both render for the filter: the noise estimate on, two batches at least
@@ -238,7 +271,27 @@ int main(int argc, char* argv[]) {
 		ssx::Renderer renderer(options);
 		std::signal(SIGINT, on_sigint);
 		if (prog.denoise || prog.spectral_denoise) renderer.set_noise_estimate(true);
-		if (!prog.spectral_output.empty()) renderer.set_spectral_bins(prog.spectral_bins);
+		if (!prog.spectral_output.empty() || !prog.develop_output.empty()) renderer.set_spectral_bins(prog.spectral_bins);
+		// what --develop-output applies, built (and refused) before the render: the observer's tables over the bins, times the filter, times the relighting gain
+		std::vector<float> develop_weights;
+		std::unique_ptr<ssx::ColorData> develop_color;
+		if (!prog.develop_output.empty()) {
+			const ssx_scene_desc& d = renderer.scene->desc();
+			develop_color = std::make_unique<ssx::ColorData>(options.data_dir, prog.develop_observer ? prog.develop_observer : options.observer);
+			develop_color->meng_output_transform = renderer.color->meng_output_transform;
+			const uint32_t B = static_cast<uint32_t>(prog.spectral_bins);
+			ssx::Spectrum filter;
+			if (!prog.develop_filter.empty()) filter = ssx::load_spectrum_csv(prog.develop_filter);
+			std::vector<double> gain;
+			if (!prog.develop_relight.empty()) {
+				const ssx_spectrum& e = d.spectra[ssx::emitter_spectrum(d)];
+				const ssx::Spectrum from(std::vector<float>(d.samples + e.offset, d.samples + e.offset + e.n), e.low, e.high);
+				gain = ssx::relight_gain(from, ssx::load_spectrum_csv(prog.develop_relight), B, d.lambda_min, d.lambda_step);
+			}
+			const std::vector<double> w = ssx::develop_weights({ develop_color->std_obs_xbar, develop_color->std_obs_ybar, develop_color->std_obs_zbar },
+			                                                   prog.develop_filter.empty() ? nullptr : &filter, gain.empty() ? nullptr : gain.data(), nullptr, B, d.lambda_min, d.lambda_step);
+			develop_weights.assign(w.begin(), w.end()); // (rounded to binary32 here, once)
+		}
 		bool stop_sent = false;
 		if (prog.noise_target >= 0.0) {
 			const auto r = renderer.render_until(prog.noise_target, prog.noise_step, prog.max_samples, [&]() {
@@ -270,13 +323,22 @@ int main(int argc, char* argv[]) {
 		if (!prog.checkpoint.empty()) renderer.level_devices();
 		renderer.render_wait();
 		std::vector<float> filtered_bins;
-		if (prog.spectral_denoise) { // (one run of the filter serves both outputs)
+		if (prog.spectral_denoise && (prog.denoise || !prog.spectral_output.empty())) { // (one run of the filter serves both outputs)
 			const ssx::Framebuffer fb = renderer.denoise_spectral(prog.denoise_params, &filtered_bins);
 			if (prog.denoise) fb.save(denoised_path);
 		} else if (prog.denoise) renderer.denoise(prog.denoise_params).save(denoised_path);
 		if (!prog.guides_output.empty()) renderer.save_guides(prog.guides_output);
-		if (prog.spectral_denoise) renderer.save_spectral_image(prog.spectral_output, filtered_bins);
+		if (prog.spectral_denoise && !prog.spectral_output.empty()) renderer.save_spectral_image(prog.spectral_output, filtered_bins);
 		else if (!prog.spectral_output.empty()) renderer.save_spectral_image(prog.spectral_output);
+		if (!prog.develop_output.empty()) { // X, Y, Z from the bins, the alpha of the render's image, then the store of --output
+			const std::vector<float> xyz = renderer.develop(develop_weights.data(), 3, prog.spectral_denoise ? &prog.denoise_params : nullptr);
+			const size_t pixels = options.res[0] * options.res[1];
+			std::vector<float> xyza(pixels * 4);
+			for (size_t p = 0; p < pixels; ++p) { xyza[4 * p] = xyz[3 * p]; xyza[4 * p + 1] = xyz[3 * p + 1]; xyza[4 * p + 2] = xyz[3 * p + 2]; xyza[4 * p + 3] = renderer.xyza[4 * p + 3]; }
+			ssx::Framebuffer fb(options.res);
+			develop_color->xyza_to_srgba(xyza.data(), fb.data(), pixels);
+			fb.save(prog.develop_output);
+		}
 		if (!prog.checkpoint.empty()) renderer.save_checkpoint(prog.checkpoint);
 	} catch (const ssx::HostError& e) {
 		std::fprintf(stderr, "%s\n", e.message.c_str());

@@ -55,6 +55,8 @@ struct Renderer::Api {
 	int (*denoise)(ssx_ctx*, const ssx_denoise_params*, float*, float*) = nullptr;
 	int (*denoise_channels)(ssx_ctx*, const ssx_denoise_params*, uint32_t, uint32_t, const float*, const float*, const uint32_t*, const float*, uint32_t, const float*, float*, float*, float*) = nullptr;
 	int (*denoise_spectral)(ssx_ctx*, const ssx_denoise_params*, float*, float*, float*) = nullptr;
+	int (*develop_images)(ssx_ctx*, uint32_t, uint32_t, uint32_t, const float*, const float*, uint32_t, float*) = nullptr;
+	int (*spectral_develop)(ssx_ctx*, const ssx_denoise_params*, const float*, uint32_t, float*) = nullptr;
 
 	explicit Api(const std::string& path) {
 		handle = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
@@ -95,6 +97,8 @@ struct Renderer::Api {
 		denoise = reinterpret_cast<decltype(denoise)>(sym("ssx_denoise"));
 		denoise_channels = reinterpret_cast<decltype(denoise_channels)>(sym("ssx_denoise_channels"));
 		denoise_spectral = reinterpret_cast<decltype(denoise_spectral)>(sym("ssx_denoise_spectral"));
+		develop_images = reinterpret_cast<decltype(develop_images)>(sym("ssx_develop_images"));
+		spectral_develop = reinterpret_cast<decltype(spectral_develop)>(sym("ssx_spectral_develop"));
 	}
 	~Api() { if (handle) dlclose(handle); }
 };
@@ -413,6 +417,36 @@ Framebuffer Renderer::denoise_spectral(const DenoiseParams& params, std::vector<
 	if (bins) bins->swap(mean);
 	if (xyza_out) xyza_out->swap(out);
 	return fb;
+}
+
+std::vector<float> Renderer::develop(const float* weights, size_t channels, const DenoiseParams* denoise) {
+	wait_workers_();
+	if (!spectral_bins_) throw HostError{ SSX_ERR_STATE, "develop: spectral output is off (set_spectral_bins)" };
+	const size_t W = options.res[0], H = options.res[1], pixels = W * H, B = spectral_bins_, C = channels, n_dev = ctxs_.size();
+	const uint32_t c32 = static_cast<uint32_t>(C);
+	std::vector<float> out(pixels * (C ? C : 1));
+	ssx_ctx* root = ctxs_[0];
+	ssx_denoise_params dp{};
+	if (denoise) { dp.struct_size = sizeof dp; dp.levels = denoise->levels; dp.sigma_l = denoise->sigma_l; dp.sigma_a = denoise->sigma_a; }
+	if (n_dev == 1) check_(api_->spectral_develop(root, denoise ? &dp : nullptr, weights, c32, out.data()), "ssx_spectral_develop", root);
+	else if (denoise) {
+		std::vector<float> bins;
+		(void)denoise_spectral(*denoise, &bins);
+		check_(api_->develop_images(root, static_cast<uint32_t>(W), static_cast<uint32_t>(H), static_cast<uint32_t>(B), bins.data(), weights, c32, out.data()), "ssx_develop_images", root);
+	} else {
+		level_devices(); // (a stopped render: one sample count behind every pixel)
+		std::vector<float> part(out.size());
+		const size_t skew = params_for_(0, 1, 0).tile_skew;
+		for (size_t d = 0; d < n_dev; ++d) { // every pixel from the device that owns it, bit for bit (a merge by ownership mask, like sums_merge)
+			check_(api_->spectral_develop(ctxs_[d], nullptr, weights, c32, part.data()), "ssx_spectral_develop", ctxs_[d]);
+			for (size_t j = 0; j < H; ++j) for (size_t i = 0; i < W; ++i) {
+				if (shared_tile(W, skew, i, j) % n_dev != d) continue;
+				const size_t p = j * W + i;
+				std::memcpy(&out[p * C], &part[p * C], C * sizeof(float));
+			}
+		}
+	}
+	return out;
 }
 
 std::pair<size_t, double> Renderer::render_until(double target, size_t step, size_t max_spp, const std::function<bool()>& tick) {

@@ -122,6 +122,12 @@ public:
 	Framebuffer denoise_spectral(const DenoiseParams& params, std::vector<float>* bins, std::vector<float>* xyza_out = nullptr);
 	void save_spectral_image(const std::string& path, const std::vector<float>& bins); // a [height][width][B] array, e.g. denoise_spectral's, in spectral_image's .npy layout
 
+	// Developing the bins (include/ssx.h "Developing the spectral bins"): weights [channels][B] (host/develop.hpp builds them) -> [height][width][channels], row 0 =
+	// bottom.  denoise == nullptr: the raw source -- every device develops its own pixels (ssx_spectral_develop) and the shares are combined by ownership mask.
+	// Otherwise the denoised source: one device runs ssx_spectral_develop with the parameters, all on the device; several follow denoise_spectral's path and
+	// then ssx_develop_images on device 0.  Either way the same bits as one device.  After render_wait(); nothing the devices hold changes.
+	std::vector<float> develop(const float* weights, size_t channels, const DenoiseParams* denoise = nullptr);
+
 private:
 	struct Api;
 	std::unique_ptr<Api> api_;

@@ -167,6 +167,85 @@ def save_npy(path, array):
         raise SsxError(rc, host.ssh_last_error().decode())
 
 
+def _spectrum_arg(spec):
+    """(samples, low, high) -> (SshSpectrum, the array that keeps its samples alive)"""
+    samples, low, high = spec
+    a = np.ascontiguousarray(samples, dtype=np.float32)
+    if a.ndim != 1 or a.size < 2:
+        raise ValueError("a spectrum is (samples [n >= 2], low, high)")
+    return _capi.SshSpectrum(a.ctypes.data_as(C.POINTER(C.c_float)), a.size, float(low), float(high)), a
+
+
+def load_spectrum_csv(path):
+    """A file in the format of data/*.csv -> (samples float32 [n], low, high) of its first column; the range is in the name: NAME-LOW+STEP+HIGH.csv."""
+    import re
+    m = re.search(r"-([0-9.]+)\+([0-9.]+)\+([0-9.]+)\.csv$", os.path.basename(path))
+    if not m:
+        raise ValueError("%r: a spectrum file names its range, NAME-LOW+STEP+HIGH.csv" % (path,))
+    low, step, high = (float(x) for x in m.groups())
+    rows = [ln.replace(",", " ").split() for ln in open(path) if ln.strip()]
+    samples = np.array([float(r[0]) for r in rows], dtype=np.float32)
+    if samples.size != (high - low) / step + 1:
+        raise ValueError("%r: %d rows do not match the range in the file's name" % (path, samples.size))
+    return samples, low, high
+
+
+def develop_weights(bins, lambda_min, lambda_step, observer=1931, responses=None, filter=None, gain=None, space="xyz", data_dir=DEFAULT_DATA_DIR, return_float64=False):
+    """ssh_develop_weights (include/ssx.h "Developing the spectral bins"): the float32 [C, bins] matrix that Renderer.develop / develop_images apply to bins of
+    a render with this lambda_min and lambda_step (Scene.desc.contents).  responses: a list of (samples, low, high) response curves, or None for the x-bar,
+    y-bar, z-bar of `observer` (1931 | 2006); filter: an optional (samples, low, high) spectrum in front of the lens; gain: an optional float64 [bins] factor
+    per bin (relight_gain); space: "xyz" or "lrgb" (three rows taken to linear BT.709 with `observer`'s matrix).  Integrated exactly in binary64 and rounded
+    once; with return_float64: (float32, float64 before the rounding)."""
+    if space not in ("xyz", "lrgb"):
+        raise ValueError("develop_weights: space must be 'xyz' or 'lrgb'")
+    keep, resp, n_ch = [], None, 3
+    if responses is not None:
+        n_ch = len(responses)
+        resp = (_capi.SshSpectrum * max(1, n_ch))()
+        for k, spec in enumerate(responses):
+            resp[k], a = _spectrum_arg(spec)
+            keep.append(a)
+    flt = None
+    if filter is not None:
+        flt, a = _spectrum_arg(filter)
+        keep.append(a)
+    g = None if gain is None else np.ascontiguousarray(gain, dtype=np.float64)
+    if g is not None and g.shape != (bins,):
+        raise ValueError("develop_weights: gain must have shape [bins]")
+    w = np.zeros((n_ch, bins), dtype=np.float32)
+    w64 = np.zeros((n_ch, bins), dtype=np.float64)
+    host = _capi.host_lib()
+    rc = host.ssh_develop_weights(os.fsencode(data_dir), int(observer), resp, n_ch, None if flt is None else C.byref(flt), None if g is None else g.ctypes.data,
+                                  _capi.SSH_SPACE_LRGB if space == "lrgb" else _capi.SSH_SPACE_XYZ, int(bins), C.c_float(lambda_min), C.c_float(lambda_step),
+                                  w.ctypes.data, w64.ctypes.data)
+    if rc != 0:
+        raise SsxError(rc, host.ssh_last_error().decode())
+    return (w, w64) if return_float64 else w
+
+
+def relight_gain(old, new, bins, lambda_min, lambda_step):
+    """ssh_relight_gain: float64 [bins], the integral of `new` over each bin divided by that of `old` (both (samples, low, high)), 0 where the latter is 0.  Passed
+    as develop_weights' gain it turns a render lit by `old` into one lit by `new` -- exactly only when every emitter of the scene carries `old` up to a scale."""
+    a, ka = _spectrum_arg(old)
+    b, kb = _spectrum_arg(new)
+    g = np.zeros(bins, dtype=np.float64)
+    host = _capi.host_lib()
+    rc = host.ssh_relight_gain(C.byref(a), C.byref(b), int(bins), C.c_float(lambda_min), C.c_float(lambda_step), g.ctypes.data)
+    if rc != 0:
+        raise SsxError(rc, host.ssh_last_error().decode())
+    return g
+
+
+def emitter_spectrum(desc):
+    """ssh_emitter_spectrum: the index (in desc.spectra) of the emission spectrum all emissive materials share up to a scale; SsxError SSX_ERR_SCENE otherwise."""
+    idx = C.c_uint32()
+    host = _capi.host_lib()
+    rc = host.ssh_emitter_spectrum(desc if hasattr(desc, "contents") else C.byref(desc), C.byref(idx))
+    if rc != 0:
+        raise SsxError(rc, host.ssh_last_error().decode())
+    return idx.value
+
+
 def load_checkpoint_file(path):
     """ssh_checkpoint_load -> (SsxSumsInfo, sums [H, W, 4], S2 [H, W] or None, scene name, options text)."""
     host = _capi.host_lib()
@@ -460,6 +539,34 @@ class Renderer:
         self._check(self._lib.ssx_denoise_spectral(self._ctx, C.byref(p), mean.ctypes.data if B else None, None if out is None else out.ctypes.data,
                                                    None if var is None else var.ctypes.data))
         return (mean, out, var) if return_image else mean
+
+    # ---- developing the bins (include/ssx.h: observers, filters, sensors) ----
+
+    def develop(self, weights, denoise=None):
+        """ssx_spectral_develop: the bins the context holds, mapped on the device by weights [C, B] (develop_weights) -> float32 [H, W, C], row 0 = bottom.
+        denoise None: the raw source, q = S * M / n; a dict of denoise_spectral's parameters (levels, sigma_l, sigma_a; {} for the defaults): the filtered bins,
+        developed without leaving the device.  Nothing the context holds changes."""
+        W, H = self.options.res
+        w = np.ascontiguousarray(weights, dtype=np.float32)
+        if w.ndim != 2:
+            raise ValueError("develop: weights must have shape [C, B]")
+        out = np.zeros((H, W, w.shape[0]), dtype=np.float32)
+        p = None if denoise is None else self._denoise_params(denoise.get("levels", 5), denoise.get("sigma_l", 1.0), denoise.get("sigma_a", 0.1))
+        if getattr(self, "_spectral_bins", 0) not in (0, w.shape[1]):
+            raise ValueError("develop: weights for %d bins, the context holds %d" % (w.shape[1], self._spectral_bins))
+        self._check(self._lib.ssx_spectral_develop(self._ctx, None if p is None else C.byref(p), w.ctypes.data, w.shape[0], out.ctypes.data))
+        return out
+
+    def develop_images(self, q, weights):
+        """ssx_develop_images: the same map as a pure function: q [H, W, B], weights [C, B] -> float32 [H, W, C]."""
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        w = np.ascontiguousarray(weights, dtype=np.float32)
+        if q.ndim != 3 or w.ndim != 2 or w.shape[1] != q.shape[2]:
+            raise ValueError("develop_images: q must have shape [H, W, B], weights [C, B]")
+        H, W, B = q.shape
+        out = np.zeros((H, W, w.shape[0]), dtype=np.float32)
+        self._check(self._lib.ssx_develop_images(self._ctx, W, H, B, q.ctypes.data, w.ctypes.data, w.shape[0], out.ctypes.data))
+        return out
 
     def debug_sample_flux(self, **over):
         """ssx_debug_sample_flux (spectral output on): per-sample (flux [H, W, spp, 4] float32, lambda_0 [H, W, spp] float32)."""
