@@ -215,6 +215,14 @@ int wait_device_pending(ssx_ctx* ctx) {
 	return SSX_OK;
 }
 
+// What the entry points that neither start a render nor need the context's sums ask first: no render running; then the context's device is current and
+// nothing queued by ssx_render_device is left on it.
+int idle_on_device(ssx_ctx* ctx) {
+	if (ctx->rendering.load()) return fail(ctx, SSX_ERR_STATE, "render in progress");
+	SSX_HIP(ctx, hipSetDevice(ctx->device));
+	return wait_device_pending(ctx);
+}
+
 uint32_t tiles_across(uint32_t pixels) { return (pixels + 7u) / 8u; } // 8x8 tiles along a width or a height
 // The pixel sums are laid out per 8x8 tile as [tile][X, Y, Z, alpha][pixel of the tile] (binary64), so that the 64 lanes of a
 // folding wave read and write 512 consecutive bytes per component: one slot per pixel of every (whole) tile of the image.
@@ -224,6 +232,11 @@ size_t image_bytes(uint32_t width, uint32_t height) { return (size_t)width * hei
 SsxPixelGrid pixel_grid(const ssx_render_params* p) { // (tile_skew reduced as in make_plan)
 	const uint32_t tx = tiles_across(p->width);
 	return SsxPixelGrid{ p->width, p->height, tx, p->tile_first, p->tile_stride, p->tile_skew % tx };
+}
+// how many of the image's 8x8 tiles the context owns: tiles tile_first, tile_first + tile_stride, ... of the (skewed) tile list
+uint32_t owned_tiles(const ssx_render_params& p) {
+	const uint32_t n_tiles = tiles_across(p.width) * tiles_across(p.height);
+	return n_tiles > p.tile_first ? (n_tiles - p.tile_first + p.tile_stride - 1u) / p.tile_stride : 0u;
 }
 dim3 pixel_blocks(const ssx_render_params* p) { return dim3((p->width * p->height + 255u) / 256u); } // the grid of a per-pixel kernel
 
@@ -278,7 +291,7 @@ LaunchPlan make_plan(ssx_ctx* ctx, const ssx_render_params* p, bool ask_device =
 	a.rgb_mode = ctx->rgb_mode ? 1u : 0u;
 	a.fuse_resolve = ctx->fuse_resolve ? 1u : 0u;
 	a.pre_hits = ctx->pre_hits ? 1u : 0u;
-	a.my_tiles = a.n_tiles > p->tile_first ? (a.n_tiles - p->tile_first + p->tile_stride - 1u) / p->tile_stride : 0u;
+	a.my_tiles = owned_tiles(*p);
 	size_t per_spp = (size_t)(a.my_tiles ? a.my_tiles : 1u) * 64u * bytes_per_sample(ctx);
 	// the budget, or 80 % of what is free on the device right now (plus what this context already holds)
 	size_t budget = kSampleBufferBudget, free_b = 0, total_b = 0;
@@ -417,9 +430,11 @@ Batch make_batch(ssx_ctx* ctx, const LaunchPlan& pl, uint32_t k0, uint32_t k1) {
 	return b;
 }
 
-// dynamic LDS of a path-kernel workgroup: coefficient table + staged blob + 4 waves' shadow-ray queues and log counters
+// dynamic LDS of a kernel that stages `blob_words` of the blob (ssx_kernels.hip stage_lds): the coefficient table in front of them
+size_t staged_blob_lds(uint32_t blob_words) { return ((size_t)blob_words + SSX_LDS_PREFIX_WORDS) * 4; }
+// ... and of a path-kernel workgroup: that + 4 waves' shadow-ray queues and log counters
 size_t path_lds_bytes(uint32_t blob_words, uint32_t queue_words) {
-	size_t n = ((size_t)blob_words + SSX_LDS_PREFIX_WORDS) * 4 + 4u * ((size_t)SSX_QUEUE_ENTRIES * queue_words + SSX_WAVE_COUNTER_WORDS) * 4u;
+	size_t n = staged_blob_lds(blob_words) + 4u * ((size_t)SSX_QUEUE_ENTRIES * queue_words + SSX_WAVE_COUNTER_WORDS) * 4u;
 #ifdef SSX_REGTIME // profiling build: the waves' region timers (ssx_lanestat.h SSX_TIME)
 	n += 4u * SSX_NTIME * 8u;
 #endif
@@ -507,7 +522,7 @@ int enqueue_generate(ssx_ctx* ctx, const Batch& b, hipStream_t stream) {
 		SSX_HIP(ctx, hipGetLastError());
 	}
 	const KernelRef gen_kernel{ (const void*)ssx_generate_kernel };
-	const size_t gen_lds = ((size_t)ga.blob_words + SSX_LDS_PREFIX_WORDS) * 4;
+	const size_t gen_lds = staged_blob_lds(ga.blob_words);
 	if (ctx->gen_blocks == 0) { const int rc = blocks_that_fit(ctx, gen_kernel, gen_lds, &ctx->gen_blocks); if (rc) return rc; }
 	const uint64_t want = (b.n_rec + 255u) / 256u;
 	return launch_kernel(ctx, gen_kernel, (uint32_t)(want < (uint64_t)ctx->gen_blocks ? want : (uint64_t)ctx->gen_blocks), gen_lds, stream, ga);
@@ -1230,7 +1245,7 @@ int ssx_debug_eval(ssx_ctx* ctx, uint32_t op, const void* in, uint32_t in_words,
 	SSX_HIP(ctx, hipMemcpy(d_in.ptr, in, (size_t)n * in_words * 4, hipMemcpyHostToDevice));
 	SsxKernelArgs a{};
 	a.blob = ctx->d_blob.as<uint32_t>(); a.blob_words = ctx->blob_words; a.rgb_mode = ctx->rgb_mode ? 1u : 0u;
-	const size_t lds = ((size_t)ctx->blob_words + SSX_LDS_PREFIX_WORDS) * 4;
+	const size_t lds = staged_blob_lds(ctx->blob_words);
 	const auto kernel = op >= SSX_DBG_GLIBC_MATH ? ssx_debug_eval_glibc_kernel : ssx_debug_eval_kernel; // the units of libm = glibc-2.35: a kernel that stages the _glibc kernels' LDS table
 	hipLaunchKernelGGL(kernel, dim3((n + 255u) / 256u), dim3(256), lds, ctx->stream, a, op, d_in.as<uint32_t>(), in_words, d_out.as<uint32_t>(), out_words, n);
 	SSX_HIP(ctx, hipGetLastError());
@@ -1249,7 +1264,7 @@ int ssx_debug_sweep(ssx_ctx* ctx, uint32_t op, uint32_t lo, uint64_t count, uint
 	SSX_HIP(ctx, hipMemsetAsync(d_res.ptr, 0, 11 * sizeof(unsigned long long), ctx->stream));
 	SsxKernelArgs a{};
 	a.blob = ctx->d_blob.as<uint32_t>(); a.blob_words = ctx->blob_words;
-	const size_t lds = ((size_t)ctx->blob_words + SSX_LDS_PREFIX_WORDS) * 4;
+	const size_t lds = staged_blob_lds(ctx->blob_words);
 	const auto kernel = op >= SSX_SWEEP_GLIBC_SIN ? ssx_debug_sweep_glibc_kernel : ssx_debug_sweep_kernel; // libm = glibc-2.35 (see ssx_debug_eval)
 	hipLaunchKernelGGL(kernel, dim3(256 * 16), dim3(256), lds, ctx->stream, a, op, lo, (uint64_t)count, d_res.as<unsigned long long>());
 	SSX_HIP(ctx, hipGetLastError());

@@ -1,6 +1,9 @@
 // ssx_denoise.hip -- first-hit guide buffers and the variance-guided edge-stopping a-trous filter (include/ssx.h, "Denoising").  Part of ssx_api.hip's
 // translation unit (included behind its context and launch helpers, like ssx_progressive.hip and ssx_spectral.hip).  Nothing here touches the generate,
-// path or finalize kernels, and nothing here runs or is allocated unless one of the three entry points at the end is called.
+// path or finalize kernels, and nothing here runs or is allocated unless one of the entry points at the end is called.
+// The filter is stated once: ssx_atrous_den (the 3x3 Gaussian of the variance), ssx_atrous_tap_weight (a tap's w), ssx_atrous_weights (a pixel's 25 weights,
+// masks and sw) and ssx_atrous_apply (the 25 taps of one group of channels).  ssx_atrous_kernel (image and variance) loops over the first two; the two shapes
+// of the extra channels' kernel, plain gather and LDS-staged, take their weights from the third; the gather sums through the fourth, the LDS kernel keeps that loop in its own text.
 
 // What the per-pixel kernels below write and read: one array per quantity, pixel p = j * width + i (row 0 = bottom).
 struct SsxGuides { uint32_t* prim; float* depth; float* normal /* [p][3] */; float4* albedo; };
@@ -55,20 +58,44 @@ extern "C" __global__ void __launch_bounds__(256) ssx_denoise_var_kernel(const d
 	var[p] = (float)(v * scale2);
 }
 
-// One level of the filter.
-struct SsxAtrousArgs {
-	const float4* c; const float* var; const uint32_t* prim; const float4* albedo; // what the level reads: the previous level's c and var, the guides
-	float4* c_out; float* var_out;
-	uint32_t width, height, step;   // step = 2^level
+// What one level of the filter reads, the same for its three kernels: the previous level's c and var and the guides.  launch_atrous fills it once per level.
+struct SsxAtrousInput {
+	const float4* c; const float* var; const uint32_t* prim; const float4* albedo;
+	uint32_t width, height, step;   // step = 2^level; width * height <= 2^28 (denoise_check_size): a pixel's index fits 32 bits
 	float sigma_l, inv_sa2;         // inv_sa2 = 1.0f / (sigma_a * sigma_a), by the host (the same float division)
 };
+struct SsxAtrousArgs { SsxAtrousInput in; float4* c_out; float* var_out; };
+// (e, e_out: [groups][height][width], see "extra channels" below)
+struct SsxAtrousChannelsArgs { SsxAtrousInput in; const float4* e; float4* e_out; uint32_t groups; };
 
 __device__ __forceinline__ bool ssx_finite(float x) { return (__float_as_uint(x) & 0x7F800000u) != 0x7F800000u; }
 __device__ __forceinline__ bool ssx_denoise_valid(const float4 c, float var) { return ssx_finite(c.x) && ssx_finite(c.y) && ssx_finite(c.z) && ssx_finite(var); }
 
-// w = (k * wl) * wa of one tap (include/ssx.h FILTER) for ssx_atrous_channels_kernel.  ssx_atrous_kernel below states the same six lines itself: calling
-// this function from it made the compiler commute the operands of its additions (the same sums, other instructions), and that kernel is to come out as it
-// was.  tests/test_denoise_spectral_gpu.py holds the two against each other: c' and var' next to extra channels X, Y, Z, bit for bit.
+// den = sigma_l * sqrt(g) + 1e-6f of the valid pixel (x, y) (include/ssx.h FILTER), g the 3x3 Gaussian of the variance over the valid neighbours at distance 1
+// (not `step`), centre included: rows outer, columns inner.
+__device__ __forceinline__ float ssx_atrous_den(const SsxAtrousInput& in, int x, int y) {
+	const int W = (int)in.width, H = (int)in.height;
+	float gs = 0.0f, ks = 0.0f;
+#pragma unroll
+	for (int dy = -1; dy <= 1; ++dy) {
+#pragma unroll
+		for (int dx = -1; dx <= 1; ++dx) {
+			const int qx = x + dx, qy = y + dy;
+			if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+			const uint32_t q = (uint32_t)qy * in.width + (uint32_t)qx;
+			const float vq = in.var[q];
+			if (!ssx_denoise_valid(in.c[q], vq)) continue;
+			const float k3 = (dy == 0 ? 2.0f : 1.0f) * (dx == 0 ? 2.0f : 1.0f);
+			gs += k3 * vq; ks += k3;
+		}
+	}
+	return in.sigma_l * __builtin_sqrtf(gs / ks) + 1e-6f;
+}
+
+// The 5-tap B3 spline h = (1/16, 1/4, 3/8, 1/4, 1/16) at offset d in -2 .. 2; a tap's k = ssx_atrous_h(dy) * ssx_atrous_h(dx).
+__device__ __forceinline__ float ssx_atrous_h(int d) { return d == 0 ? 0.375f : ((d == -1 || d == 1) ? 0.25f : 0.0625f); }
+
+// w = (k * wl) * wa of one tap (include/ssx.h FILTER): the one statement of the weight, for the image and for the extra channels.
 __device__ __forceinline__ float ssx_atrous_tap_weight(float k, float y_q, float y_p, float den, const float4 al_q, const float4 al_p, float inv_sa2) {
 	const float xl = __builtin_fabsf(y_q - y_p) / den;
 	const float wl = 1.0f / (1.0f + xl * xl);
@@ -82,58 +109,36 @@ __device__ __forceinline__ float ssx_atrous_tap_weight(float k, float y_q, float
 // per tap, 25 taps and the 9 variance taps of g per pixel).  Neighbouring lanes read neighbouring pixels at every step, so a wave's tap is four 256-byte runs
 // (c, albedo) and four 64-byte ones; the working set of a level -- 40 bytes per pixel, 10 MB at 512^2 -- stays in the L2 / MALL from one level to the next.
 // No atomics, no barriers, no LDS.  Every operation is binary32 in the order include/ssx.h writes it, divisions and the square root IEEE, nothing contracted:
-// tests/denoise_ref.py restates it in numpy and the results are compared bit for bit.
+// tests/denoise_ref.py restates it in numpy and the results are compared bit for bit.  The rows stay a rolled loop that skips a row outside the image as a
+// whole, and the sums are five scalars: that is what keeps the kernel at its registers (profiles/r15/NOTES.md).
 extern "C" __global__ void __launch_bounds__(256) ssx_atrous_kernel(SsxAtrousArgs a) {
-	const int W = (int)a.width, H = (int)a.height;
+	const SsxAtrousInput& in = a.in;
+	const int W = (int)in.width, H = (int)in.height;
 	const int x = (int)(blockIdx.x * 16u + threadIdx.x), y = (int)(blockIdx.y * 16u + threadIdx.y);
 	if (x >= W || y >= H) return;
-	const size_t p = (size_t)y * a.width + (size_t)x;
-	const float4 cp = a.c[p];
-	const float vp = a.var[p];
+	const size_t p = (size_t)y * in.width + (size_t)x;
+	const float4 cp = in.c[p];
+	const float vp = in.var[p];
 	if (!ssx_denoise_valid(cp, vp)) { a.c_out[p] = cp; a.var_out[p] = vp; return; } // an invalid pixel keeps what it has, at every level
-	// g: the 3x3 Gaussian of the variance over the valid neighbours at distance 1 (not `step`), centre included
-	float gs = 0.0f, ks = 0.0f;
-#pragma unroll
-	for (int dy = -1; dy <= 1; ++dy) {
-#pragma unroll
-		for (int dx = -1; dx <= 1; ++dx) {
-			const int qx = x + dx, qy = y + dy;
-			if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
-			const size_t q = (size_t)qy * a.width + (size_t)qx;
-			const float vq = a.var[q];
-			if (!ssx_denoise_valid(a.c[q], vq)) continue;
-			const float k3 = (dy == 0 ? 2.0f : 1.0f) * (dx == 0 ? 2.0f : 1.0f);
-			gs += k3 * vq; ks += k3;
-		}
-	}
-	const float g = gs / ks;
-	const float den = a.sigma_l * __builtin_sqrtf(g) + 1e-6f;
-	const uint32_t prim_p = a.prim[p];
-	const float4 al_p = a.albedo[p];
-	const int step = (int)a.step;
+	const float den = ssx_atrous_den(in, x, y);
+	const uint32_t prim_p = in.prim[p];
+	const float4 al_p = in.albedo[p];
+	const int step = (int)in.step;
 	float sw = 0.0f, scx = 0.0f, scy = 0.0f, scz = 0.0f, sv = 0.0f;
 	for (int dy = -2; dy <= 2; ++dy) {
 		const int qy = y + step * dy;
 		if (qy < 0 || qy >= H) continue;
-		const float hy = dy == 0 ? 0.375f : ((dy == -1 || dy == 1) ? 0.25f : 0.0625f);
+		const float hy = ssx_atrous_h(dy);
 #pragma unroll
 		for (int dx = -2; dx <= 2; ++dx) {
 			const int qx = x + step * dx;
 			if (qx < 0 || qx >= W) continue;
-			const size_t q = (size_t)qy * a.width + (size_t)qx;
-			if (a.prim[q] != prim_p) continue;
-			const float4 cq = a.c[q];
-			const float vq = a.var[q];
+			const size_t q = (size_t)qy * in.width + (size_t)qx;
+			if (in.prim[q] != prim_p) continue;
+			const float4 cq = in.c[q];
+			const float vq = in.var[q];
 			if (!ssx_denoise_valid(cq, vq)) continue;
-			const float4 al_q = a.albedo[q];
-			const float hx = dx == 0 ? 0.375f : ((dx == -1 || dx == 1) ? 0.25f : 0.0625f);
-			const float k = hy * hx;
-			const float xl = __builtin_fabsf(cq.y - cp.y) / den;
-			const float wl = 1.0f / (1.0f + xl * xl);
-			const float d0 = al_q.x - al_p.x, d1 = al_q.y - al_p.y, d2 = al_q.z - al_p.z, d3 = al_q.w - al_p.w;
-			const float da2 = ((d0 * d0 + d1 * d1) + d2 * d2) + d3 * d3;
-			const float wa = 1.0f / (1.0f + da2 * a.inv_sa2);
-			const float w = (k * wl) * wa;
+			const float w = ssx_atrous_tap_weight(hy * ssx_atrous_h(dx), cq.y, cp.y, den, in.albedo[q], al_p, in.inv_sa2);
 			sw += w;
 			scx += w * cq.x; scy += w * cq.y; scz += w * cq.z;
 			sv += (w * w) * vq;
@@ -147,57 +152,22 @@ extern "C" __global__ void __launch_bounds__(256) ssx_atrous_kernel(SsxAtrousArg
 // The E extra channels of a pixel lie on the device planar in groups of four: e[group][pixel] as float4, groups = ceil(E / 4), the spare components of the
 // last group +0 (they are filtered like the rest and never leave the device).  A tap is then one 16-byte load per group, neighbouring lanes reading
 // neighbouring pixels: the access pattern of c in ssx_atrous_kernel, `groups` times.  groups * width * height <= 2^27 (channels_check_size): 32-bit indices.
-struct SsxAtrousChannelsArgs {
-	const float4* c; const float* var; const uint32_t* prim; const float4* albedo; // the level's input, as ssx_atrous_kernel reads it (which writes its c', var')
-	const float4* e; float4* e_out;                                                // [groups][height][width]
-	uint32_t width, height, step, groups;
-	float sigma_l, inv_sa2;
-};
-
 __device__ __forceinline__ float ssx_channel(const float4* e, uint32_t plane, uint32_t p, uint32_t ch) {
 	return reinterpret_cast<const float*>(e + (size_t)(ch >> 2) * plane + p)[ch & 3u];
 }
 
-// One level for the extra channels, launched next to ssx_atrous_kernel on the same input: the same 16x16-pixel workgroup, one lane per pixel.  The lane
-// recomputes the level's 25 weights and sw -- the expressions of ssx_atrous_kernel in its order, through ssx_atrous_tap_weight -- once, into 25 registers (both
-// tap loops are unrolled, so every index is static) and two 25-bit masks: `inside` (the tap is in the image: its address may be read) and `counted` (it
-// takes part: inside, valid, same primitive).  Then it walks the groups: 25 loads of 16 bytes, from the tap where it is inside the image and from the
-// lane's own pixel where it is not, and a select per component that adds w * e[q] for a counted tap and leaves the sum alone for any other -- skipped, not
-// added with weight 0.  The offsets (dy * width + dx) * step are the same for every lane (scalar registers).  No atomics, no LDS, no barriers; a lane
-// writes its own pixel only.
-extern "C" __global__ void __launch_bounds__(256) ssx_atrous_channels_kernel(SsxAtrousChannelsArgs a) {
-	const int W = (int)a.width, H = (int)a.height;
-	const int x = (int)(blockIdx.x * 16u + threadIdx.x), y = (int)(blockIdx.y * 16u + threadIdx.y);
-	if (x >= W || y >= H) return;
-	const uint32_t plane = a.width * a.height, p = (uint32_t)y * a.width + (uint32_t)x;
-	const float4 cp = a.c[p];
-	const float vp = a.var[p];
-	if (!ssx_denoise_valid(cp, vp)) { // an invalid pixel keeps what it has, at every level
-		for (uint32_t g = 0; g < a.groups; ++g) a.e_out[(size_t)g * plane + p] = a.e[(size_t)g * plane + p];
-		return;
-	}
-	float gs = 0.0f, ks = 0.0f;
-#pragma unroll
-	for (int dy = -1; dy <= 1; ++dy) {
-#pragma unroll
-		for (int dx = -1; dx <= 1; ++dx) {
-			const int qx = x + dx, qy = y + dy;
-			if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
-			const uint32_t q = (uint32_t)qy * a.width + (uint32_t)qx;
-			const float vq = a.var[q];
-			if (!ssx_denoise_valid(a.c[q], vq)) continue;
-			const float k3 = (dy == 0 ? 2.0f : 1.0f) * (dx == 0 ? 2.0f : 1.0f);
-			gs += k3 * vq; ks += k3;
-		}
-	}
-	const float g3 = gs / ks;
-	const float den = a.sigma_l * __builtin_sqrtf(g3) + 1e-6f;
-	const uint32_t prim_p = a.prim[p];
-	const float4 al_p = a.albedo[p];
-	const int step = (int)a.step;
-	float w[25];
-	uint32_t inside = 0u, counted = 0u;
+// The level's 25 weights of the valid pixel (x, y) with image cp, for the extra channels: the expressions of ssx_atrous_kernel in its order (ssx_atrous_den,
+// ssx_atrous_tap_weight), tap t = (dy + 2) * 5 + (dx + 2).  Returns sw; w[t] is +0 for a tap that does not take part; two 25-bit masks: `inside` (the tap is
+// in the image: its address may be read) and `counted` (it takes part: inside, valid, same primitive).  Both loops are unrolled, so every index into w is
+// static and w stays in registers.
+__device__ __forceinline__ float ssx_atrous_weights(const SsxAtrousInput& in, int x, int y, const float4 cp, float (&w)[25], uint32_t& inside, uint32_t& counted) {
+	const int W = (int)in.width, H = (int)in.height, step = (int)in.step;
+	const float den = ssx_atrous_den(in, x, y);
+	const uint32_t p = (uint32_t)y * in.width + (uint32_t)x;
+	const uint32_t prim_p = in.prim[p];
+	const float4 al_p = in.albedo[p];
 	float sw = 0.0f;
+	inside = 0u; counted = 0u;
 #pragma unroll
 	for (int dy = -2; dy <= 2; ++dy) {
 #pragma unroll
@@ -207,28 +177,58 @@ extern "C" __global__ void __launch_bounds__(256) ssx_atrous_channels_kernel(Ssx
 			const int qx = x + step * dx, qy = y + step * dy;
 			if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
 			inside |= 1u << t;
-			const uint32_t q = (uint32_t)qy * a.width + (uint32_t)qx;
-			if (a.prim[q] != prim_p) continue;
-			const float4 cq = a.c[q];
-			if (!ssx_denoise_valid(cq, a.var[q])) continue;
-			const float hy = dy == 0 ? 0.375f : ((dy == -1 || dy == 1) ? 0.25f : 0.0625f);
-			const float hx = dx == 0 ? 0.375f : ((dx == -1 || dx == 1) ? 0.25f : 0.0625f);
-			w[t] = ssx_atrous_tap_weight(hy * hx, cq.y, cp.y, den, a.albedo[q], al_p, a.inv_sa2);
+			const uint32_t q = (uint32_t)qy * in.width + (uint32_t)qx;
+			if (in.prim[q] != prim_p) continue;
+			const float4 cq = in.c[q];
+			if (!ssx_denoise_valid(cq, in.var[q])) continue;
+			w[t] = ssx_atrous_tap_weight(ssx_atrous_h(dy) * ssx_atrous_h(dx), cq.y, cp.y, den, in.albedo[q], al_p, in.inv_sa2);
 			counted |= 1u << t;
 			sw += w[t];
 		}
 	}
+	return sw;
+}
+
+// One group of four channels of one pixel: the 25 taps fetch(t) in the order of t, a select per component that adds w[t] * tap for a counted tap and leaves
+// the sum alone for any other -- skipped, not added with weight 0 --, and the four divisions by sw.  Unrolled: t is static in w[t] and in fetch(t).
+template <class Fetch>
+__device__ __forceinline__ float4 ssx_atrous_apply(const float (&w)[25], uint32_t counted, float sw, Fetch fetch) {
+	float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
+#pragma unroll
+	for (int t = 0; t < 25; ++t) {
+		const float4 v = fetch(t);
+		const bool on = ((counted >> t) & 1u) != 0u;
+		s0 = on ? s0 + w[t] * v.x : s0; s1 = on ? s1 + w[t] * v.y : s1; s2 = on ? s2 + w[t] * v.z : s2; s3 = on ? s3 + w[t] * v.w : s3;
+	}
+	return make_float4(s0 / sw, s1 / sw, s2 / sw, s3 / sw);
+}
+
+// One level for the extra channels, launched next to ssx_atrous_kernel on the same input: the same 16x16-pixel workgroup, one lane per pixel.  The lane
+// computes the level's weights once (ssx_atrous_weights: 25 registers and the two masks), then walks the groups (ssx_atrous_apply): 25 loads of 16 bytes, from
+// the tap where it is inside the image and from the lane's own pixel where it is not.  The offsets (dy * width + dx) * step are the same for every lane
+// (scalar registers).  No atomics, no LDS, no barriers; a lane writes its own pixel only.
+extern "C" __global__ void __launch_bounds__(256) ssx_atrous_channels_kernel(SsxAtrousChannelsArgs a) {
+	const SsxAtrousInput& in = a.in;
+	const int W = (int)in.width, H = (int)in.height;
+	const int x = (int)(blockIdx.x * 16u + threadIdx.x), y = (int)(blockIdx.y * 16u + threadIdx.y);
+	if (x >= W || y >= H) return;
+	const uint32_t plane = in.width * in.height, p = (uint32_t)y * in.width + (uint32_t)x;
+	const float4 cp = in.c[p];
+	const float vp = in.var[p];
+	if (!ssx_denoise_valid(cp, vp)) { // an invalid pixel keeps what it has, at every level
+		for (uint32_t g = 0; g < a.groups; ++g) a.e_out[(size_t)g * plane + p] = a.e[(size_t)g * plane + p];
+		return;
+	}
+	const int step = (int)in.step;
+	float w[25];
+	uint32_t inside, counted;
+	const float sw = ssx_atrous_weights(in, x, y, cp, w, inside, counted); // (the centre tap always counts: sw >= 9/64)
 	for (uint32_t g = 0; g < a.groups; ++g) {
 		const float4* const eg = a.e + (size_t)g * plane + p;
-		float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
-#pragma unroll
-		for (int t = 0; t < 25; ++t) {
+		a.e_out[(size_t)g * plane + p] = ssx_atrous_apply(w, counted, sw, [&](int t) {
 			const ptrdiff_t off = (ptrdiff_t)((t / 5 - 2) * W + (t % 5 - 2)) * step; // inside the planes wherever `inside` says so
-			const float4 v = eg[(inside >> t) & 1u ? off : (ptrdiff_t)0];
-			const bool on = ((counted >> t) & 1u) != 0u;
-			s0 = on ? s0 + w[t] * v.x : s0; s1 = on ? s1 + w[t] * v.y : s1; s2 = on ? s2 + w[t] * v.z : s2; s3 = on ? s3 + w[t] * v.w : s3;
-		}
-		a.e_out[(size_t)g * plane + p] = make_float4(s0 / sw, s1 / sw, s2 / sw, s3 / sw); // (the centre tap always counts)
+			return eg[(inside >> t) & 1u ? off : (ptrdiff_t)0];
+		});
 	}
 }
 
@@ -238,63 +238,26 @@ extern "C" __global__ void __launch_bounds__(256) ssx_atrous_channels_kernel(Ssx
 // takes its 25 taps from there at the static offsets (dy T + dx) s from its own place; the next group goes to the other buffer, so one barrier per group is
 // enough (a lane that writes buffer b for group g + 2 has passed the barrier of group g + 1, which every lane reaches after its reads of group g).  All 256
 // lanes stay to the end for the barriers: lanes outside the image and invalid pixels compute no weights; the former store nothing, the latter store the
-// centre of the tile, i.e. what they had.  Weights, order of the additions and the select per component are those of ssx_atrous_channels_kernel: the same bits.
+// centre of the tile, i.e. what they had.  Weights are those of ssx_atrous_channels_kernel by the same function, the sums by the same loop: the same bits.
 // Only for step <= 2 (launch_atrous).
 constexpr uint32_t kChannelsLdsTileMax = 24u * 24u;
 extern "C" __global__ void __launch_bounds__(256) ssx_atrous_channels_lds_kernel(SsxAtrousChannelsArgs a) {
 	__shared__ float4 tile[2][kChannelsLdsTileMax];
-	const int W = (int)a.width, H = (int)a.height, step = (int)a.step, T = 16 + 4 * step;
+	const SsxAtrousInput& in = a.in;
+	const int W = (int)in.width, H = (int)in.height, step = (int)in.step, T = 16 + 4 * step;
 	const int x = (int)(blockIdx.x * 16u + threadIdx.x), y = (int)(blockIdx.y * 16u + threadIdx.y);
 	const bool in_image = x < W && y < H;
-	const uint32_t plane = a.width * a.height, p = in_image ? (uint32_t)y * a.width + (uint32_t)x : 0u;
+	const uint32_t plane = in.width * in.height, p = in_image ? (uint32_t)y * in.width + (uint32_t)x : 0u;
 	float4 cp = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 	float vp = 0.0f;
-	if (in_image) { cp = a.c[p]; vp = a.var[p]; }
+	if (in_image) { cp = in.c[p]; vp = in.var[p]; }
 	const bool valid = in_image && ssx_denoise_valid(cp, vp);
 	float w[25];
 #pragma unroll
 	for (int t = 0; t < 25; ++t) w[t] = 0.0f;
-	uint32_t counted = 0u;
+	uint32_t inside = 0u, counted = 0u; // (`inside` is not used here: every tap is in the tile)
 	float sw = 1.0f; // (a lane without weights divides nothing it stores)
-	if (valid) {
-		float gs = 0.0f, ks = 0.0f;
-#pragma unroll
-		for (int dy = -1; dy <= 1; ++dy) {
-#pragma unroll
-			for (int dx = -1; dx <= 1; ++dx) {
-				const int qx = x + dx, qy = y + dy;
-				if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
-				const uint32_t q = (uint32_t)qy * a.width + (uint32_t)qx;
-				const float vq = a.var[q];
-				if (!ssx_denoise_valid(a.c[q], vq)) continue;
-				const float k3 = (dy == 0 ? 2.0f : 1.0f) * (dx == 0 ? 2.0f : 1.0f);
-				gs += k3 * vq; ks += k3;
-			}
-		}
-		const float g3 = gs / ks;
-		const float den = a.sigma_l * __builtin_sqrtf(g3) + 1e-6f;
-		const uint32_t prim_p = a.prim[p];
-		const float4 al_p = a.albedo[p];
-		sw = 0.0f;
-#pragma unroll
-		for (int dy = -2; dy <= 2; ++dy) {
-#pragma unroll
-			for (int dx = -2; dx <= 2; ++dx) {
-				const int t = (dy + 2) * 5 + (dx + 2);
-				const int qx = x + step * dx, qy = y + step * dy;
-				if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
-				const uint32_t q = (uint32_t)qy * a.width + (uint32_t)qx;
-				if (a.prim[q] != prim_p) continue;
-				const float4 cq = a.c[q];
-				if (!ssx_denoise_valid(cq, a.var[q])) continue;
-				const float hy = dy == 0 ? 0.375f : ((dy == -1 || dy == 1) ? 0.25f : 0.0625f);
-				const float hx = dx == 0 ? 0.375f : ((dx == -1 || dx == 1) ? 0.25f : 0.0625f);
-				w[t] = ssx_atrous_tap_weight(hy * hx, cq.y, cp.y, den, a.albedo[q], al_p, a.inv_sa2);
-				counted |= 1u << t;
-				sw += w[t];
-			}
-		}
-	}
+	if (valid) sw = ssx_atrous_weights(in, x, y, cp, w, inside, counted);
 	const int tid = (int)(threadIdx.y * 16u + threadIdx.x), cells = T * T;
 	const int ox = (int)(blockIdx.x * 16u) - 2 * step, oy = (int)(blockIdx.y * 16u) - 2 * step;       // the tile's corner in the image
 	const int mine = ((int)threadIdx.y + 2 * step) * T + ((int)threadIdx.x + 2 * step);            // the lane's own pixel in the tile: taps at mine + (dy T + dx) step, in 0 .. T^2 - 1
@@ -311,6 +274,8 @@ extern "C" __global__ void __launch_bounds__(256) ssx_atrous_channels_lds_kernel
 		for (int k = 0; k < 3; ++k)
 			if (src[k] != -2) buf[tid + 256 * k] = src[k] >= 0 ? eg[src[k]] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 		__syncthreads();
+		// The loop of ssx_atrous_apply with buf[mine + ...] as its fetch(t), spelled out: called through the function, with the tap as a lambda (captures by
+		// reference or by value), this kernel lost 2 % at 64 bins and two levels, measured; with a functor it needed 124 VGPRs (profiles/r15/NOTES.md).
 		float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
 #pragma unroll
 		for (int t = 0; t < 25; ++t) {
@@ -413,8 +378,7 @@ int ensure_guides(ssx_ctx* ctx, uint32_t width, uint32_t height) {
 	a.blob = ctx->d_blob.as<uint32_t>(); a.blob_words = ctx->blob_words; a.rgb_mode = ctx->rgb_mode ? 1u : 0u;
 	a.width = width; a.height = height;
 	a.inv_width = 1.0 / (double)width; a.inv_height = 1.0 / (double)height;
-	const size_t lds = ((size_t)ctx->blob_words + SSX_LDS_PREFIX_WORDS) * 4;
-	hipLaunchKernelGGL(ssx_guides_kernel, dim3((uint32_t)((pixels + 255u) / 256u)), dim3(256), lds, ctx->stream, a, guides_of(ctx, pixels));
+	hipLaunchKernelGGL(ssx_guides_kernel, dim3((uint32_t)((pixels + 255u) / 256u)), dim3(256), staged_blob_lds(ctx->blob_words), ctx->stream, a, guides_of(ctx, pixels));
 	SSX_HIP(ctx, hipGetLastError());
 	SSX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	ctx->guides_width = width; ctx->guides_height = height;
@@ -429,6 +393,15 @@ int denoise_buffers(ssx_ctx* ctx, size_t pixels, DenoiseBuffers* b) {
 	b->c_in = f4; b->albedo_in = f4 + pixels; b->c[0] = f4 + 2u * pixels; b->c[1] = f4 + 3u * pixels;
 	float* const f1 = reinterpret_cast<float*>(f4 + 4u * pixels);
 	b->var_in = f1; b->prim_in = reinterpret_cast<uint32_t*>(f1 + pixels); b->var[0] = f1 + 2u * pixels; b->var[1] = f1 + 3u * pixels;
+	return SSX_OK;
+}
+// ... with the caller's four filter inputs in c_in, albedo_in, var_in and prim_in (queued on the context's stream)
+int denoise_upload_inputs(ssx_ctx* ctx, size_t pixels, const float* xyza, const float* var, const uint32_t* prim, const float* albedo, DenoiseBuffers* b) {
+	if (const int rc = denoise_buffers(ctx, pixels, b)) return rc;
+	SSX_HIP(ctx, hipMemcpyAsync(b->c_in, xyza, pixels * 16u, hipMemcpyHostToDevice, ctx->stream));
+	SSX_HIP(ctx, hipMemcpyAsync(b->albedo_in, albedo, pixels * 16u, hipMemcpyHostToDevice, ctx->stream));
+	SSX_HIP(ctx, hipMemcpyAsync(b->var_in, var, pixels * 4u, hipMemcpyHostToDevice, ctx->stream));
+	SSX_HIP(ctx, hipMemcpyAsync(b->prim_in, prim, pixels * 4u, hipMemcpyHostToDevice, ctx->stream));
 	return SSX_OK;
 }
 
@@ -457,23 +430,18 @@ dim3 blocks_of(size_t lanes) { return dim3((uint32_t)((lanes + 255u) / 256u)); }
 // the same input, from cb->e[l & 1] to cb->e[(l + 1) & 1]: the caller has put the channels into cb->e[0] and finds them in cb->e[levels & 1].
 int launch_atrous(ssx_ctx* ctx, const ssx_denoise_params& dp, uint32_t width, uint32_t height, const float4* c, const float* var, const uint32_t* prim, const float4* albedo, const DenoiseBuffers& b,
                   const ChannelBuffers* cb = nullptr) {
-	SsxAtrousArgs a{};
-	a.prim = prim; a.albedo = albedo;
-	a.width = width; a.height = height;
-	a.sigma_l = dp.sigma_l; a.inv_sa2 = 1.0f / (dp.sigma_a * dp.sigma_a);
+	SsxAtrousInput in{};
+	in.prim = prim; in.albedo = albedo;
+	in.width = width; in.height = height;
+	in.sigma_l = dp.sigma_l; in.inv_sa2 = 1.0f / (dp.sigma_a * dp.sigma_a);
 	const dim3 grid((width + 15u) / 16u, (height + 15u) / 16u), block(16, 16);
 	for (uint32_t l = 0; l < dp.levels; ++l) {
-		a.c = l ? b.c[(l - 1u) & 1u] : c; a.var = l ? b.var[(l - 1u) & 1u] : var;
-		a.c_out = b.c[l & 1u]; a.var_out = b.var[l & 1u];
-		a.step = 1u << l;
-		hipLaunchKernelGGL(ssx_atrous_kernel, grid, block, 0, ctx->stream, a);
+		in.c = l ? b.c[(l - 1u) & 1u] : c; in.var = l ? b.var[(l - 1u) & 1u] : var;
+		in.step = 1u << l;
+		hipLaunchKernelGGL(ssx_atrous_kernel, grid, block, 0, ctx->stream, SsxAtrousArgs{ in, b.c[l & 1u], b.var[l & 1u] });
 		SSX_HIP(ctx, hipGetLastError());
 		if (!cb) continue;
-		SsxAtrousChannelsArgs ca{};
-		ca.c = a.c; ca.var = a.var; ca.prim = prim; ca.albedo = albedo;
-		ca.e = cb->e[l & 1u]; ca.e_out = cb->e[(l + 1u) & 1u];
-		ca.width = width; ca.height = height; ca.step = a.step; ca.groups = cb->groups;
-		ca.sigma_l = a.sigma_l; ca.inv_sa2 = a.inv_sa2;
+		const SsxAtrousChannelsArgs ca{ in, cb->e[l & 1u], cb->e[(l + 1u) & 1u], cb->groups };
 		if (ssx_channels_level_in_lds(l)) hipLaunchKernelGGL(ssx_atrous_channels_lds_kernel, grid, block, 0, ctx->stream, ca);
 		else hipLaunchKernelGGL(ssx_atrous_channels_kernel, grid, block, 0, ctx->stream, ca);
 		SSX_HIP(ctx, hipGetLastError());
@@ -545,11 +513,9 @@ extern "C" {
 int ssx_guides(ssx_ctx* ctx, uint32_t width, uint32_t height, uint32_t* prim, float* depth, float* normal, float* albedo) {
 	if (!ctx) return SSX_ERR_ARG;
 	if (!ctx->have_scene) return fail(ctx, SSX_ERR_STATE, "no scene uploaded");
-	if (ctx->rendering.load()) return fail(ctx, SSX_ERR_STATE, "render in progress");
-	int rc = denoise_check_size(ctx, width, height, "ssx_guides");
+	int rc = idle_on_device(ctx); // (before the size check, so that a running render is refused first, as it was; a bad size is now refused with the device current)
 	if (rc) return rc;
-	SSX_HIP(ctx, hipSetDevice(ctx->device));
-	if ((rc = wait_device_pending(ctx))) return rc;
+	if ((rc = denoise_check_size(ctx, width, height, "ssx_guides"))) return rc;
 	if ((rc = ensure_guides(ctx, width, height))) return rc;
 	const size_t pixels = (size_t)width * height;
 	const SsxGuides g = guides_of(ctx, pixels);
@@ -568,16 +534,10 @@ int ssx_denoise_images(ssx_ctx* ctx, const ssx_denoise_params* params, uint32_t 
 	int rc = denoise_take_params(ctx, params, &dp);
 	if (rc) return rc;
 	if ((rc = denoise_check_size(ctx, width, height, "ssx_denoise_images"))) return rc;
-	if (ctx->rendering.load()) return fail(ctx, SSX_ERR_STATE, "render in progress");
-	SSX_HIP(ctx, hipSetDevice(ctx->device));
-	if ((rc = wait_device_pending(ctx))) return rc;
+	if ((rc = idle_on_device(ctx))) return rc;
 	const size_t pixels = (size_t)width * height;
 	DenoiseBuffers b;
-	if ((rc = denoise_buffers(ctx, pixels, &b))) return rc;
-	SSX_HIP(ctx, hipMemcpyAsync(b.c_in, xyza, pixels * 16u, hipMemcpyHostToDevice, ctx->stream));
-	SSX_HIP(ctx, hipMemcpyAsync(b.albedo_in, albedo, pixels * 16u, hipMemcpyHostToDevice, ctx->stream));
-	SSX_HIP(ctx, hipMemcpyAsync(b.var_in, var, pixels * 4u, hipMemcpyHostToDevice, ctx->stream));
-	SSX_HIP(ctx, hipMemcpyAsync(b.prim_in, prim, pixels * 4u, hipMemcpyHostToDevice, ctx->stream));
+	if ((rc = denoise_upload_inputs(ctx, pixels, xyza, var, prim, albedo, &b))) return rc;
 	if ((rc = launch_atrous(ctx, dp, width, height, b.c_in, b.var_in, b.prim_in, b.albedo_in, b))) return rc;
 	return denoise_read_back(ctx, dp, pixels, b, xyza_out, var_out);
 }
@@ -609,17 +569,11 @@ int ssx_denoise_channels(ssx_ctx* ctx, const ssx_denoise_params* params, uint32_
 	if ((rc = denoise_check_size(ctx, width, height, "ssx_denoise_channels"))) return rc;
 	const size_t pixels = (size_t)width * height;
 	if ((rc = channels_check_size(ctx, pixels, channels, "ssx_denoise_channels"))) return rc;
-	if (ctx->rendering.load()) return fail(ctx, SSX_ERR_STATE, "render in progress");
-	SSX_HIP(ctx, hipSetDevice(ctx->device));
-	if ((rc = wait_device_pending(ctx))) return rc;
+	if ((rc = idle_on_device(ctx))) return rc;
 	DenoiseBuffers b;
 	ChannelBuffers cb;
-	if ((rc = denoise_buffers(ctx, pixels, &b))) return rc;
+	if ((rc = denoise_upload_inputs(ctx, pixels, xyza, var, prim, albedo, &b))) return rc;
 	if ((rc = channel_buffers(ctx, pixels, channels, channels, &cb))) return rc;
-	SSX_HIP(ctx, hipMemcpyAsync(b.c_in, xyza, pixels * 16u, hipMemcpyHostToDevice, ctx->stream));
-	SSX_HIP(ctx, hipMemcpyAsync(b.albedo_in, albedo, pixels * 16u, hipMemcpyHostToDevice, ctx->stream));
-	SSX_HIP(ctx, hipMemcpyAsync(b.var_in, var, pixels * 4u, hipMemcpyHostToDevice, ctx->stream));
-	SSX_HIP(ctx, hipMemcpyAsync(b.prim_in, prim, pixels * 4u, hipMemcpyHostToDevice, ctx->stream));
 	SSX_HIP(ctx, hipMemcpyAsync(cb.stage, extra, pixels * channels * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
 	hipLaunchKernelGGL(ssx_channels_pack_kernel, blocks_of(pixels * cb.groups), dim3(256), 0, ctx->stream, cb.stage, cb.e[0], (uint32_t)pixels, channels, cb.groups);
 	SSX_HIP(ctx, hipGetLastError());

@@ -147,9 +147,7 @@ int ssx_develop_images(ssx_ctx* ctx, uint32_t width, uint32_t height, uint32_t b
 	if (bins < 4u || bins > 64u || (bins & 3u)) return fail(ctx, SSX_ERR_ARG, fmt("ssx_develop_images: %u bins: need a multiple of 4 up to 64", bins));
 	if (!q || !out) return fail(ctx, SSX_ERR_ARG, "ssx_develop_images: q and out must not be NULL");
 	if ((rc = denoise_check_size(ctx, width, height, "ssx_develop_images"))) return rc;
-	if (ctx->rendering.load()) return fail(ctx, SSX_ERR_STATE, "render in progress");
-	SSX_HIP(ctx, hipSetDevice(ctx->device));
-	if ((rc = wait_device_pending(ctx))) return rc;
+	if ((rc = idle_on_device(ctx))) return rc;
 	const size_t pixels = (size_t)width * height;
 	DevelopBuffers d;
 	if ((rc = develop_buffers(ctx, pixels, bins, channels, weights, pixels * bins, &d))) return rc;
@@ -194,10 +192,8 @@ int ssx_spectral_develop(ssx_ctx* ctx, const ssx_denoise_params* denoise, const 
 		a.S = ctx->d_spectral_sums.as<const double>();
 		a.g = pixel_grid(&p);
 		a.M = (double)(B / 4u); a.n = (double)done;
-		const uint32_t n_tiles = tiles_across(p.width) * tiles_across(p.height);
-		const uint32_t my_tiles = n_tiles > p.tile_first ? (n_tiles - p.tile_first + p.tile_stride - 1u) / p.tile_stride : 0u;
 		if (p.tile_stride != 1u) SSX_HIP(ctx, hipMemsetAsync(d.out, 0, pixels * channels * sizeof(float), ctx->stream)); // pixels of other contexts: +0
-		if ((rc = launch_develop_state(ctx, a, my_tiles))) return rc;
+		if ((rc = launch_develop_state(ctx, a, owned_tiles(p)))) return rc;
 	}
 	return develop_read_back(ctx, d, pixels, channels, out);
 }
