@@ -236,3 +236,150 @@ def warped_builtin(seed):
     c.set_camera(tuple(eye), tuple(target), up=tuple(up), vfov_deg=float(g.uniform(30.0, 70.0)))
     opts = dict(indirect_only=bool(g.integers(0, 4) == 0), els=bool(g.integers(0, 4) != 0), flat_field=bool(g.integers(0, 4) != 0))
     return c, base, opts
+
+
+# ---- the scene and option matrix of tests/test_pipeline_matrix_{cpu,gpu}.py -------------------------------------------------------------------------------
+# Every scene and switch the path kernel is tested on, as (oracle, renderer) pairs for the kernels behind it: the _flux twins, the bin kernel, the guides,
+# the noise estimate, the filter chain and the develop.
+
+MATRIX_TEX = "test-img.png"
+# "fuzz" has triangles, so it runs the generic kernel; "warped" keeps the mesh topology of its built-in scene and with it the built-in topology kernel, whatever
+# ssx_set_jit says; "moved-corner" matches no built-in topology and is the case with its run-time compiled kernels (jit_pass1=True: the plain ones at upload,
+# their _flux twins at the first render with spectral output on).  "plane-indirect" is black (MATRIX_BLACK); "cornell-indirect" is the indirect_only case in
+# which light does arrive.
+MATRIX_CASES = ("triangles", "prims70", "prims128-2006", "textures", "shared-edge", "fuzz", "warped", "moved-corner", "mirror", "observer2006", "jh", "meng",
+                "cornell-no-els", "prims70-no-els", "plane-indirect", "cornell-indirect", "cornell-no-ffc")
+JIT_PASS1 = "scene topology (compiled at upload)"
+FUZZ_SEED, WARPED_SEED = 7, 3
+MATRIX_BLACK = ("plane-indirect",)    # every camera ray hits, no flux arrives: the bins hold counts and sums of 0 (and one primitive fills the view)
+
+
+class MatrixCase:
+    """One case: `oracle` (ol.Oracle, with the case's observer, uplift and materials), `flags` (indirect_only / els / flat_field for Oracle.render and
+    Oracle.samples), `pass1` (the kernel variant plan_info() must name), `scene` (the CustomScene, or None for a built-in one) and `renderer(res)`."""
+
+    def __init__(self, name, oracle, options, flags=None, scene=None, pass1="generic", mirror_quads=None):
+        self.name, self.oracle, self.options, self.scene, self.pass1, self.mirror_quads = name, oracle, options, scene, pass1, mirror_quads
+        self.jit = pass1 == JIT_PASS1
+        self.flags = dict(indirect_only=False, els=True, flat_field=True)
+        self.flags.update(flags or {})
+        self._keep = []
+
+    def renderer(self, res, seed=5, **opts):
+        import ctypes as C
+        from simple_spectral_amd import Options, Renderer, _capi
+        o = dict(res=res, seed=seed, jit_pass1=self.jit, indirect_only=self.flags["indirect_only"], explicit_light_sampling=self.flags["els"],
+                 flat_field_correction=self.flags["flat_field"])
+        o.update(self.options); o.update(opts)
+        r = Renderer(Options(**o))
+        if self.scene is not None:
+            r.upload_scene_desc(self.scene.desc(self.oracle))
+        if self.mirror_quads is not None:                                # as tests/test_gpu_parity.py test_mirror_material_bit_exact switches them
+            d = r.scene.desc.contents
+            mats = (_capi.SsxMaterial * d.n_materials)(*[d.materials[i] for i in range(d.n_materials)])
+            for q in range(d.n_quads):
+                if self.mirror_quads(q):
+                    mats[d.quads[q].material].kind = 1                    # SSX_MTL_MIRROR
+            d2 = _capi.SsxSceneDesc.from_buffer_copy(d)
+            d2.materials = C.cast(mats, C.POINTER(_capi.SsxMaterial))
+            self._keep.append(mats)
+            r._check(r._lib.ssx_upload_scene(r._ctx, C.byref(d2)))
+        return r
+
+    def render_ref(self, W, H, spp, seed=5):
+        return self.oracle.render(W, H, spp, seed=seed, **self.flags)
+
+    def samples_ref(self, W, H, spp, seed=5):
+        return self.oracle.samples(W, H, spp, seed=seed, **self.flags)
+
+    def light_prims(self):
+        import ctypes as C
+        nl = C.c_int()
+        self.oracle.lib.orc_scene_counts(self.oracle.scene, None, C.byref(nl), None)
+        return {int(self.oracle.lib.orc_scene_light(self.oracle.scene, i)) for i in range(nl.value)}
+
+
+_matrix_cache = {}
+
+
+def _meng_grid():
+    """(table, path of the grid file the host library reads): the table of tests/golden/ref_vectors.npz, written once per process"""
+    if "meng" not in _matrix_cache:
+        import atexit, os, tempfile
+        import ref_lib
+        from simple_spectral_amd import meng
+        table = ref_lib.meng_table()
+        fd, path = tempfile.mkstemp(suffix=".bin", prefix="ssx-meng-grid-")
+        os.close(fd)
+        meng.save_table(path, table)
+        atexit.register(lambda: os.path.exists(path) and os.remove(path))
+        _matrix_cache["meng"] = (table, path)
+    return _matrix_cache["meng"]
+
+
+def matrix_case(name):
+    """The case `name` of MATRIX_CASES; one object per process (a CustomScene's description points into the scene's own arrays)."""
+    if name in _matrix_cache:
+        return _matrix_cache[name]
+    import oracle_lib as ol
+    from simple_spectral_amd.renderer import Scene
+    T = MATRIX_TEX
+    custom = lambda c, **kw: MatrixCase(name, c.oracle(), dict(scene_name="cornell", observer=c.observer), scene=c, **kw)
+    builtin = lambda scene, oracle, pass1, flags=None, mirror_quads=None, **o: MatrixCase(name, oracle, dict(scene_name=scene, texture=T, **o), flags=flags,
+                                                                                         pass1=pass1, mirror_quads=mirror_quads)
+    if name == "triangles":
+        case = custom(triangle_scene())
+    elif name == "prims70":
+        case = custom(many_prims_scene(70, 1931))
+    elif name == "prims128-2006":
+        case = custom(many_prims_scene(128, 2006))
+    elif name == "textures":
+        case = custom(many_textures_scene(), pass1="cornell topology")      # (materials and textures changed, the mesh is the Cornell box's)
+    elif name == "shared-edge":
+        case = custom(shared_edge_scene())
+    elif name == "fuzz":
+        c, o = random_scene(FUZZ_SEED)
+        case = custom(c, flags=o)
+    elif name == "warped":
+        c, base, o = warped_builtin(WARPED_SEED)
+        case = MatrixCase(name, c.oracle(), dict(scene_name=base, observer=c.observer, texture=None if base == "cornell" else T), flags=o, scene=c,
+                          pass1="plane topology" if base == "plane-srgb" else "cornell topology")
+    elif name == "moved-corner":
+        # The Cornell box with one corner moved apart from its twins: a corner that no other test module moves (the compiled code of a sharing pattern stays
+        # in the process's memory, and the modules that upload their own moved-corner boxes expect the generic kernel for them when they run first).
+        c = cs.CustomScene("cornell-srgb")
+        pos, st, m = c.quads[3]
+        pos = pos.copy(); pos[2, 1] += 0.5
+        c.quads[3] = (pos, st, m)
+        case = MatrixCase(name, c.oracle(), dict(scene_name="cornell-srgb", texture=T), scene=c, pass1=JIT_PASS1)
+    elif name == "cornell-indirect":
+        case = builtin("cornell-srgb", ol.Oracle("cornell-srgb", texture=T), "cornell topology", flags=dict(indirect_only=True))
+    elif name == "mirror":
+        orc = ol.Oracle("cornell-srgb", texture=T)
+        pick = lambda q: q >= 9
+        nq = ol.C.c_int()
+        orc.lib.orc_scene_counts(orc.scene, ol.C.byref(nq), None, None)
+        for q in range(nq.value):
+            if pick(q):
+                assert orc.lib.orc_scene_set_material_kind(orc.scene, orc.lib.orc_scene_quad_material(orc.scene, q), 1) == 0
+        case = builtin("cornell-srgb", orc, "cornell topology", mirror_quads=pick)
+    elif name == "observer2006":
+        case = builtin("cornell-srgb", ol.Oracle("cornell-srgb", observer=2006, texture=T), "cornell topology", observer=2006)
+    elif name == "jh":
+        model = Scene("cornell-srgb", texture=T, uplift="jh", jh_res=16).jh_model()
+        case = builtin("cornell-srgb", ol.Oracle("cornell-srgb", texture=T, jh=model), "cornell topology", uplift="jh", jh_res=16)
+    elif name == "meng":
+        table, path = _meng_grid()
+        case = builtin("cornell-srgb", ol.Oracle("cornell-srgb", texture=T, meng=table), "cornell topology", uplift="meng", meng_grid_path=path)
+    elif name == "cornell-no-els":
+        case = builtin("cornell-srgb", ol.Oracle("cornell-srgb", texture=T), "cornell topology", flags=dict(els=False))
+    elif name == "prims70-no-els":
+        case = custom(many_prims_scene(70, 1931), flags=dict(els=False))
+    elif name == "plane-indirect":
+        case = builtin("plane-srgb", ol.Oracle("plane-srgb", texture=T), "plane topology", flags=dict(indirect_only=True))
+    elif name == "cornell-no-ffc":
+        case = builtin("cornell-srgb", ol.Oracle("cornell-srgb", texture=T), "cornell topology", flags=dict(flat_field=False))
+    else:
+        raise KeyError(name)
+    _matrix_cache[name] = case
+    return case

@@ -115,3 +115,56 @@ def table_extrema_over(t, a, z):
     """(min, max) of the piecewise-linear T over [a, z]: taken at a, z or a knot inside."""
     v = [table_at(t, x) for x in [a, z] + _knots_inside(t, a, z)]
     return min(v), max(v)
+
+
+# ---- inputs at the edges of binary32, and the bound of the develop against the image -------------------------------------------------------------------------
+
+def extreme_inputs(W, H, bins, channels, seed):
+    """(q [H, W, bins], weights [channels, bins]) whose products and sums are denormal or overflow.  Rows of the image in four groups: q denormal, q about
+    1e-20, q about +-1e30, q in [-4, 9]; weights: channel 0 ordinary, 1 denormal, 2 about 1e-20, 3 about 1e30, the rest ordinary (channels >= 4; fewer
+    channels take the first of them)."""
+    g = np.random.default_rng(seed)
+    F = np.float32
+    q = g.uniform(-4, 9, size=(H, W, bins)).astype(F)
+    sign = lambda shape: np.where(g.integers(0, 2, size=shape) == 1, F(1), F(-1))
+    rows = np.arange(H) % 4
+    n = int((rows == 0).sum())
+    q[rows == 0] = g.integers(1, 0x007FFFFF, size=(n, W, bins)).astype(np.uint32).view(F) * sign((n, W, bins))
+    n = int((rows == 1).sum())
+    q[rows == 1] = (g.uniform(0.5, 2, size=(n, W, bins)) * 1e-20).astype(F) * sign((n, W, bins))
+    n = int((rows == 2).sum())
+    big = (g.uniform(0.5, 2, size=(n, W, bins)) * 1e30).astype(F) * sign((n, W, 1))      # one sign per pixel: the sum is +inf or -inf ...
+    big[0, 0, 0] = -big[0, 0, 0]                                                          # ... and in one pixel inf - inf
+    q[rows == 2] = big
+    w = g.uniform(-2, 3, size=(channels, bins)).astype(F)
+    if channels > 1:
+        w[1] = g.integers(1, 0x007FFFFF, size=bins).astype(np.uint32).view(F) * sign(bins)
+    if channels > 2:
+        w[2] = (g.uniform(0.5, 2, size=bins) * 1e-20).astype(F)
+    if channels > 3:
+        w[3] = (g.uniform(0.5, 2, size=bins) * 1e30).astype(F)
+    return q, w
+
+
+def bin_average_bound(flux, lam, q, w, w64, tables, bins, lambda_min, lambda_step, spp):
+    """The bound of tests/test_develop_gpu.py test_raw_develop_under_the_renders_observer_is_the_image_up_to_the_bin_average, [H, W, 3]:
+    (1/n) sum_k sum_i |f_ki| max over the bin of |bar_c - avg_b(bar_c)| lambda_step, plus the rounding slack (B + 4) 2^-23 sum_b |q_b W_cb|.  The
+    derivation holds for any observer: `tables` are the render's own x-bar, y-bar, z-bar (observer_tables), w / w64 its develop weights."""
+    from simple_spectral_amd.renderer import spectral_bin_index
+    M = bins // 4
+    dev = np.zeros((3, bins))
+    for b in range(bins):
+        a, z = bin_edge(b, bins, lambda_min, lambda_step), bin_edge(b + 1, bins, lambda_min, lambda_step)
+        for c in range(3):
+            avg = w64[c, b] / (z - a)
+            lo, hi = table_extrema_over(tables[c], a, z)
+            dev[c, b] = max(abs(hi - avg), abs(lo - avg))
+    m = spectral_bin_index(lam, np.float32(lambda_min), np.float32(lambda_step), bins).astype(np.int64)
+    bound = np.zeros(lam.shape[:2] + (3,))
+    for i in range(4):
+        f = np.abs(flux[..., i].astype(np.float64))
+        for c in range(3):
+            bound[..., c] += (f * dev[c][i * M + m]).sum(axis=2)
+    bound *= lambda_step / spp
+    slack = (bins + 4) * 2.0 ** -23 * np.einsum("hwb,cb->hwc", np.abs(q.astype(np.float64)), np.abs(w.astype(np.float64)))
+    return bound + slack

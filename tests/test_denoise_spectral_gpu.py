@@ -29,24 +29,7 @@ def filter_context():
 
 # ---- 1. the extra channels as a pure function ------------------------------------------------------------------------------------------------------------
 
-def extras_with_specials(c, var, seed):
-    """80 channels; in valid pixels: a NaN, negative zeros and a denormal in channel 0 (what E = 1 sees), an infinity in channel 1, a channel of negative
-    zeros (2), a channel of denormals (4), an infinity in the last"""
-    H, W = var.shape
-    g = np.random.default_rng(seed)
-    e = g.uniform(-2, 6, size=(H, W, 80)).astype(F)
-    ok = np.flatnonzero(dr.valid_mask(c, var))
-    at = ok[g.permutation(len(ok))]
-    flat = e.reshape(-1, 80)
-    flat[at[0], 0] = F(np.nan)
-    flat[at[1 % len(at)], 1] = F(np.inf)
-    flat[at[2 % len(at)], 0] = F(-0.0); flat[at[3 % len(at)], 0] = F(-0.0)
-    flat[at[4 % len(at)], 0] = np.uint32(0x00000007).view(F)
-    flat[:, 2] = F(-0.0)
-    flat[:, 4] = g.integers(1, 0x007FFFFF, size=H * W).astype(np.uint32).view(F) * np.where(g.integers(0, 2, size=H * W) == 1, F(1), F(-1))
-    flat[at[5 % len(at)], 79] = F(np.inf)
-    assert np.isnan(e).sum() == 1 and np.isinf(e).sum() == 2 and np.signbit(e[e == 0]).all()
-    return e
+extras_with_specials = dr.extras_with_specials          # (shared with tests/test_pipeline_matrix_gpu.py)
 
 
 @pytest.mark.parametrize("res", SIZES)

@@ -249,7 +249,6 @@ def test_raw_develop_under_the_renders_observer_is_the_image_up_to_the_bin_avera
     r = renderer("cornell-srgb")
     report = {}
     for bins in (4, 16, 64):
-        M = bins // 4
         r.set_spectral_bins(bins)
         image = start(r)
         if bins == 64:
@@ -259,25 +258,11 @@ def test_raw_develop_under_the_renders_observer_is_the_image_up_to_the_bin_avera
         report[bins] = abs(float(out[..., 1].astype(np.float64).mean()) / float(image[..., 1].astype(np.float64).mean()) - 1.0)
         if bins != 64:
             continue
-        dev = np.zeros((3, bins))
-        for b in range(bins):
-            a, z = ref.bin_edge(b, bins, lmin, lstep), ref.bin_edge(b + 1, bins, lmin, lstep)
-            for c in range(3):
-                avg = w64[c, b] / (z - a)
-                lo, hi = ref.table_extrema_over(tables[c], a, z)
-                dev[c, b] = max(abs(hi - avg), abs(lo - avg))
-        m = spectral_bin_index(lam, F(lmin), F(lstep), bins).astype(np.int64)                           # [H, W, n]
-        bound = np.zeros((H, W, 3))
-        for i in range(4):
-            f = np.abs(flux[..., i].astype(np.float64))                                                  # [H, W, n]
-            for c in range(3):
-                bound[..., c] += (f * dev[c][i * M + m]).sum(axis=2)
-        bound *= lstep / SPP
-        q = ref.raw_q(r.spectral_read(sums=True)[3], SPP).astype(np.float64)
-        slack = (bins + 4) * 2.0 ** -23 * np.einsum("hwb,cb->hwc", np.abs(q), np.abs(w.astype(np.float64)))
+        q = ref.raw_q(r.spectral_read(sums=True)[3], SPP)
+        bound = ref.bin_average_bound(flux, lam, q, w, w64, tables, bins, lmin, lstep, SPP)             # the docstring's bound, slack included
         diff = np.abs(out.astype(np.float64) - image[..., :3].astype(np.float64))
-        assert np.isfinite(diff).all() and (diff <= bound + slack).all(), "largest excess %g" % float((diff - bound - slack).max())
-        print("develop vs image at B = 64: largest |difference| / bound = %.4f" % float((diff[diff > 0] / (bound + slack)[diff > 0]).max()))   # (a black pixel is 0 against 0)
+        assert np.isfinite(diff).all() and (diff <= bound).all(), "largest excess %g" % float((diff - bound).max())
+        print("develop vs image at B = 64: largest |difference| / bound = %.4f" % float((diff[diff > 0] / bound[diff > 0]).max()))   # (a black pixel is 0 against 0)
     print("relative difference of the image-mean Y, develop against render: " + ", ".join("B = %d: %.3e" % kv for kv in sorted(report.items())))
 
 

@@ -12,6 +12,7 @@ import pytest
 
 import custom_scene as cs
 import oracle_lib as ol
+import spectral_ref
 from simple_spectral_amd import Options, Renderer, _capi
 from simple_spectral_amd.dist import tile_owner_mask
 from simple_spectral_amd.renderer import Scene, SsxError, spectral_bin_index
@@ -83,18 +84,7 @@ def lambda_range(scene):
 def restated(scene, spp, bins):
     """The definition, sequentially: (sums float64 [H, W, B], counts uint32 [H, W, M], mean float32 [H, W, B]) from the per-sample flux and lambda_0."""
     flux, lam, _ = per_sample(scene, spp)
-    lmin, lstep = lambda_range(scene)
-    M = bins // 4
-    m = spectral_bin_index(lam, lmin, lstep, bins)
-    S, N = np.zeros((H, W, bins), dtype=np.float64), np.zeros((H, W, M), dtype=np.uint32)
-    J, I = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
-    for k in range(spp):                       # ascending k; every pixel appears once per statement
-        for i in range(4):
-            S[J, I, i * M + m[:, :, k]] += flux[:, :, k, i].astype(np.float64)
-        N[J, I, m[:, :, k]] += np.uint32(1)
-    n = np.tile(N, (1, 1, 4)).astype(np.float64)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        mean = np.where(n > 0, S / n, 0.0).astype(np.float32)
+    S, N, mean = spectral_ref.restate_bins(flux, lam, *lambda_range(scene), bins)
     for a in (S, N, mean):
         a.setflags(write=False)
     return S, N, mean
@@ -118,18 +108,7 @@ def test_flux_projects_onto_the_oracles_sample(scene, flat_field, indirect_only)
     flux, lam, xyza = per_sample(scene, spp, flat_field, indirect_only)
     o = oracle(scene)
     ref, _, _ = o.samples(W, H, spp, seed=SEED, indirect_only=indirect_only, flat_field=flat_field)
-    lmin, lstep = lambda_range(scene)
-    rng, out = ol.Rng(), (C.c_float * 3)()
-    proj, lam_ref = np.zeros((H, W, spp, 3), dtype=np.float32), np.zeros((H, W, spp), dtype=np.float32)
-    for j in range(H):
-        for i in range(W):
-            for k in range(spp):
-                f = (C.c_float * 4)(*[float(x) for x in flux[j, i, k]])
-                o.lib.orc_specradflux_to_ciexyz_hero(o.color, f, C.c_float(float(lam[j, i, k])), out)
-                proj[j, i, k] = out[:]
-                o.lib.orc_seed_sample(SEED, j * W + i, k, C.byref(rng))       # renderer.cpp:113,138: two doubles of sub-pixel offset, then the wavelength
-                o.lib.orc_rand_1d(C.byref(rng)); o.lib.orc_rand_1d(C.byref(rng))
-                lam_ref[j, i, k] = lmin + np.float32(o.lib.orc_rand_1f(C.byref(rng))) * lstep
+    proj, lam_ref = spectral_ref.project_flux(o, flux, lam, SEED, *lambda_range(scene))
     assert np.array_equal(bits(lam), bits(lam_ref))
     assert np.array_equal(bits(xyza), bits(ref))
     same = (bits(proj) == bits(ref[..., :3])) | (np.isnan(proj) & np.isnan(ref[..., :3]))
