@@ -33,7 +33,7 @@ extern "C" {
  *      ssx_jit_counters, ssx_sums_info, ssx_rccl_groups_made, ssx_done_tiles and ssx_render_params.tile_major and tile_skew (the
  *      struct grew by 8 bytes) are new.  Added since without a change of existing entry points or structures (same version): ssx_units_info,
  *      ssx_rccl_probe (round 6); ssx_render_params.libm, appended (a caller with the struct_size before it gets SSX_LIBM_BUILD); the progressive
- *      rendering, spectral output, denoising and develop entry points below. */
+ *      rendering, spectral output, denoising, develop and demodulated-denoising entry points below. */
 #define SSX_ABI_VERSION 2
 
 enum {
@@ -589,6 +589,66 @@ int ssx_develop_images(ssx_ctx* ctx, uint32_t width, uint32_t height, uint32_t b
  * ssx_last_error: spectral output is off, a render runs, the context holds no valid bins (nothing rendered, or ssx_sums_import, or a changed bin count),
  * ssx_done_spp == 0, and, for the denoised source, whatever ssx_denoise_spectral refuses.  SSX_ERR_ARG: channels outside 1..16, a NULL weights. */
 int ssx_spectral_develop(ssx_ctx* ctx, const ssx_denoise_params* denoise, const float* weights /* [C][B] */, uint32_t channels, float* out /* [H][W][C] */);
+
+/* ---- Demodulated denoising: the filter on illumination, the albedo divided out per bin (appended; same ABI version) ---------------------------------
+ * The filter of Schied et al. runs on illumination -- radiance divided by the first-hit albedo -- and multiplies the albedo back afterwards; on a textured
+ * surface every texel boundary is otherwise a luminance edge and the filter averages texels of like colour only.  A spectral renderer knows the albedo per
+ * wavelength, and the bins of "Spectral radiance output" are aligned with the hero slots, so the bins are demodulated exactly, bin by bin.  The definition is
+ * this library's.  Binary32 with IEEE + - * /, no contraction, in the order written; a restatement in numpy gives the same bits (tests/demod_ref.py).
+ *
+ * ALBEDO BINS.  rho[p][b] for every pixel p = (i, j) of a width x height image, B bins (B in {4, 8, ..., 64}, M = B / 4) and K in {1, 2, 4} rays per axis;
+ * independent of seed, spp and ownership; refused in SSX_MODE_RGB, as spectral output is.
+ *     acc[0..B-1] = 0
+ *     for c = 0..K-1 (outer), a = 0..K-1 (inner): the ray through ((double)i + ((double)a + 0.5) / K, (double)j + ((double)c + 0.5) / K) -- camera_dir, normalised and
+ *         rounded to float and traced exactly as a ray of GUIDE BUFFERS is -- and for m = 0..M-1:
+ *             lambda_0 = lambda_min + ((float)m + 0.5f) * (lambda_step / (float)M)
+ *             al = what the device function behind SSX_DBG_ALBEDO returns for (prim, st of the hit, lambda_0); +0 in all four components for a miss
+ *             acc[i*M + m] = acc[i*M + m] + al[i]     (i = 0..3)
+ *     rho[p][b] = acc[b] / (float)(K*K)
+ * At K = 1, B = 4 rho is the albedo of GUIDE BUFFERS bit for bit (lambda_0 is lambda_g).
+ *
+ * CHANNEL ALBEDO.  Given weights Wc[3][B] (X, Y, Z rows; the hosts default them to the develop weights of the render's own observer):
+ *     num[p][c] = DEVELOP of rho[p][.] with Wc[c][.];   den[c] = the same accumulation with every q = 1.0f;   rho_c[p][c] = num[p][c] / den[c]
+ * den[c] <= 0 (or NaN) is refused.
+ *
+ * DEMODULATE.  f = albedo_floor;  r~[p][b] = rho[p][b] > f ? rho[p][b] : f;  r~_c[p][c] likewise from rho_c.  valid(p) as in FILTER, of the inputs c and var.  For a
+ * valid p, with e0 the SPECTRAL CHANNELS:
+ *     e0'[p][b] = e0[p][b] / r~[p][b]   (b = 0..B-1; the M count channels stay);   c'[p][k] = c[p][k] / r~_c[p][k]   (k = X, Y, Z; alpha stays)
+ *     var'[p] = var[p] / (r~_c[p][1] * r~_c[p][1])
+ * An invalid p keeps e0, c and var, and is not remodulated either: it passes through the whole mode untouched.
+ * Below the floor a dark texel is under-demodulated and darkens its neighbours' estimate; above it the mode stops doing anything.
+ *
+ * FILTER.  FILTER with EXTRA CHANNELS, unchanged, on c', var', e0', with the scene's prim guide and an ALL-ZERO albedo guide: wa = 1.0f / (1.0f + 0.0f) is exactly
+ * 1 -- the demodulation replaces the albedo stop.  sigma_a is IGNORED in this mode (any value, also an invalid one, is accepted).
+ *
+ * REMODULATE.  With cL, varL, eL the filter's results, for a p that was valid on input:
+ *     out[p][b]   = eL[p][B + b%M] > 0 ? (eL[p][b] / eL[p][B + b%M]) * r~[p][b] : 0.0f
+ *     c_out[p][k] = cL[p][k] * r~_c[p][k]   (alpha stays);      var_out[p] = varL[p] * (r~_c[p][1] * r~_c[p][1])
+ * and without the multiplications for a p that was not. */
+
+/* rho_out [height][width][bins], row-major (row 0 = bottom); NULL: computed and kept only.  Two kernels: the albedo kernel (one lane per pixel and pair of sub-bins m; an
+ * odd M: per sub-bin; on the device the bins lie planar in groups of four, float4 [bins / 4][height][width], the layout of the filter's channel buffers) and the
+ * copy into the row-major array returned here; cached per (scene upload, width, height, bins, supersample) and
+ * dropped by ssx_upload_scene, as the guide buffers are.  SSX_ERR_STATE: no scene, a render runs, a scene in SSX_MODE_RGB.  SSX_ERR_ARG: bins not a multiple of
+ * 4 in 4..64, supersample not 1, 2 or 4, an empty or too large image. */
+int ssx_albedo_bins(ssx_ctx* ctx, uint32_t width, uint32_t height, uint32_t bins, uint32_t supersample, float* rho_out /* [H][W][B] */);
+#define SSX_DEMOD_DEFAULT_FLOOR 0.0625f  /* 1/16 */
+#define SSX_DEMOD_DEFAULT_SIGMA_L 1.0f
+typedef struct ssx_demod_params {
+	uint32_t struct_size;  /* sizeof(ssx_demod_params) */
+	uint32_t supersample;  /* K: 1, 2 or 4 */
+	float albedo_floor;    /* finite and positive */
+} ssx_demod_params;        /* NULL where one is expected: supersample 2, albedo_floor SSX_DEMOD_DEFAULT_FLOOR (chosen on CPU renders: DESIGN.md section 15) */
+/* ssx_denoise_spectral in this mode, from the context's own state and without leaving the device: mean_out [height][width][B] receives `out`, xyza_out c_out,
+ * var_out var_out; any of the three may be NULL.  params == NULL: levels 5, sigma_l SSX_DEMOD_DEFAULT_SIGMA_L (the mode's own default: DESIGN.md section 15).
+ * weights_xyz is Wc.  The state rules of ssx_denoise_spectral: it reads only -- image, sums, noise and spectral state stay as they are, so an ssx_render_continue
+ * afterwards leaves the bits of a one-shot render -- and refuses what that refuses.  SSX_ERR_ARG also: a NULL weights_xyz, a row of it whose den is not positive,
+ * supersample or albedo_floor out of range.  (A scene in SSX_MODE_RGB never holds valid bins.) */
+int ssx_denoise_spectral_demod(ssx_ctx* ctx, const ssx_denoise_params* params, const ssx_demod_params* demod, const float* weights_xyz /* [3][B] */,
+                               float* mean_out /* [H][W][B] */, float* xyza_out, float* var_out);
+/* ssx_spectral_develop with this mode's `out` as the source q: the remodulated bins are developed where they lie.  weights [channels][B] and out as there. */
+int ssx_spectral_develop_demod(ssx_ctx* ctx, const ssx_denoise_params* denoise, const ssx_demod_params* demod, const float* weights_xyz /* [3][B] */,
+                               const float* weights /* [C][B] */, uint32_t channels, float* out /* [H][W][C] */);
 
 /* ---- Diagnostics for the parity tests (not part of the reference's interface) ---------------------
  * ssx_debug_eval runs one building block of the path kernel -- the same device function the kernel

@@ -77,6 +77,14 @@ class SsxSpectralInfo(C.Structure):
                 ("reserved", C.c_uint32), ("lambda_min", C.c_float), ("bin_width", C.c_float)]
 
 
+class SsxDemodParams(C.Structure):
+    """ssx_demod_params: rays per pixel axis of the albedo bins and the floor under the albedo a pixel is divided by."""
+    _fields_ = [("struct_size", C.c_uint32), ("supersample", C.c_uint32), ("albedo_floor", C.c_float)]
+
+
+SSX_DEMOD_DEFAULT_SUPERSAMPLE, SSX_DEMOD_DEFAULT_FLOOR, SSX_DEMOD_DEFAULT_SIGMA_L = 2, 0.0625, 1.0  # include/ssx.h; DESIGN.md section 15
+
+
 class SsxDenoiseParams(C.Structure):
     """ssx_denoise_params: levels of the a-trous filter and its two edge-stopping scales."""
     _fields_ = [("struct_size", C.c_uint32), ("levels", C.c_uint32), ("sigma_l", C.c_float), ("sigma_a", C.c_float)]
@@ -108,7 +116,8 @@ HIP_SYMBOLS = ["ssx_create", "ssx_destroy", "ssx_upload_scene", "ssx_render_star
                "ssx_render_continue", "ssx_scene_digest", "ssx_sums_export", "ssx_sums_import", "ssx_set_noise_estimate", "ssx_noise_info",
                "ssx_set_spectral_bins", "ssx_spectral_read", "ssx_debug_sample_flux",
                "ssx_guides", "ssx_denoise_images", "ssx_denoise", "ssx_denoise_channels", "ssx_denoise_spectral",
-               "ssx_develop_images", "ssx_spectral_develop"]
+               "ssx_develop_images", "ssx_spectral_develop",
+               "ssx_albedo_bins", "ssx_denoise_spectral_demod", "ssx_spectral_develop_demod"]
 (SSX_SWEEP_RCP, SSX_SWEEP_SQRT, SSX_SWEEP_INVERSESQRT, SSX_SWEEP_SIN, SSX_SWEEP_COS, SSX_SWEEP_ACOS, SSX_SWEEP_DIV_PI,
  SSX_SWEEP_RCP64, SSX_SWEEP_DIV_PAIRS, SSX_SWEEP_ACOS_SIN, SSX_SWEEP_SIN_PROOF, SSX_SWEEP_COS_PROOF, SSX_SWEEP_ACOS_PROOF) = range(1, 14)
 # ssx_debug_eval ops (include/ssx.h)
@@ -326,6 +335,10 @@ def hip_lib():
         if not override or hasattr(lib, "ssx_spectral_develop"):  # developing the spectral bins
             lib.ssx_develop_images.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, vp]
             lib.ssx_spectral_develop.argtypes = [vp, C.POINTER(SsxDenoiseParams), vp, C.c_uint32, vp]
+        if not override or hasattr(lib, "ssx_albedo_bins"):  # demodulated denoising
+            lib.ssx_albedo_bins.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp]
+            lib.ssx_denoise_spectral_demod.argtypes = [vp, C.POINTER(SsxDenoiseParams), C.POINTER(SsxDemodParams), vp, vp, vp, vp]
+            lib.ssx_spectral_develop_demod.argtypes = [vp, C.POINTER(SsxDenoiseParams), C.POINTER(SsxDemodParams), vp, vp, C.c_uint32, vp]
         lib.ssx_kernel_variant.argtypes = [vp]
         lib.ssx_kernel_name.argtypes = [vp]
         lib.ssx_kernel_name.restype = C.c_char_p

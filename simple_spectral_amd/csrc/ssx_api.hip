@@ -147,6 +147,14 @@ struct ssx_ctx {
 	DeviceBuffer d_guides, d_denoise, d_denoise_channels;
 	DeviceBuffer d_develop;             // ssx_develop_images / ssx_spectral_develop (csrc/ssx_develop.hip): weights | output | the caller's bins; nothing until one of them is called
 	uint32_t guides_width = 0, guides_height = 0;
+	// demodulated denoising (csrc/ssx_demod.hip): nothing is allocated until ssx_albedo_bins or one of the two _demod entry points is called.  d_albedo_bins
+	// holds the albedo bins of the uploaded scene at abins_width x abins_height, abins_bins bins, abins_supersample^2 rays per pixel (0 x 0: none;
+	// ssx_upload_scene drops them), d_demod the channel albedo, the demodulated image and variance, the zero albedo guide and the remodulated results.
+	DeviceBuffer d_albedo_bins, d_demod;
+	uint32_t abins_width = 0, abins_height = 0, abins_bins = 0, abins_supersample = 0;
+	uint64_t abins_serial = 0;          // counts the computations of the albedo bins: what the cached channel albedo below was made from
+	// the channel albedo r~_c and the zero guide inside d_demod are kept from call to call: made from these albedo bins, weights and floor, in this allocation (nullptr: none)
+	const void* demod_rc_base = nullptr; uint64_t demod_rc_bins_serial = 0; float demod_rc_floor = 0.0f; std::vector<float> demod_rc_weights;
 
 	// optional per-kernel timing (ssx_set_timing): events around each stage of each batch
 	bool timing = false;
@@ -969,6 +977,7 @@ int ssx_upload_scene(ssx_ctx* ctx, const ssx_scene_desc* s) {
 	ctx->have_scene = false;
 	sums_invalidate(ctx); ctx->scene_digest = 0;
 	ctx->guides_width = ctx->guides_height = 0; // (the guide buffers were the last scene's)
+	ctx->abins_width = ctx->abins_height = 0;   // (and so were the albedo bins)
 	for (uint32_t i = 0; i < s->n_textures && i < SSX_MAX_TEXTURES; ++i) {
 		const ssx_texture& t = s->textures[i];
 		if (!t.rgb || t.width == 0 || t.height == 0) return fail(ctx, SSX_ERR_DATA, "Could not load texture"); // material.cpp:15-18
@@ -1443,3 +1452,4 @@ int ssx_kernel_info(ssx_ctx* ctx, int* vgprs, int* sgprs, int* lds_bytes, int* s
 #include "ssx_spectral.hip"
 #include "ssx_denoise.hip"
 #include "ssx_develop.hip"
+#include "ssx_demod.hip"

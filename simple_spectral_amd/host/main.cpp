@@ -21,6 +21,9 @@
 // (a spectrum in the format of data/*.csv, its range in the name: NAME-LOW+STEP+HIGH.csv) and relit by --develop-relight=NEW.csv (the emitters' spectrum replaced by
 // NEW; refused unless all emissive materials share one spectrum up to a scale).  With --spectral-denoise the filtered bins are developed.  It does not need
 // --spectral-output, and has its refusals (--resume, --tile-major, --rgb, --libm=glibc-2.35).
+// Demodulated denoising (include/ssx.h "Demodulated denoising"): --demodulate[=K] with --spectral-denoise runs that filter on illumination -- bins, image and
+// variance divided by the first-hit albedo per bin (K x K rays per pixel, K = 1, 2 or 4; default 2) before it and multiplied by it afterwards; the albedo part of
+// --denoise-sigma is ignored then.  --albedo-output=PATH.npy (needs --spectral-bins=N) writes those albedo bins, [height][width][N] float32.
 #include "renderer.hpp"
 
 #include "develop.hpp"
@@ -61,7 +64,9 @@ void print_usage() {
 		"    `--guides-output=<file.npy>` (first hit per pixel: primitive, depth, normal, albedo)\n"
 		"    `--spectral-denoise` (with `--spectral-output`: the file holds the bins filtered with `--denoise`'s weights, levels and sigmas; not with `-spp=1`)\n"
 		"    `--develop-output=<image>` (needs `--spectral-bins=<n>`) [`--develop-observer=1931|2006`] [`--develop-filter=<name-low+step+high.csv>`] [`--develop-relight=<new.csv>`]\n"
-		"          (the image developed from the wavelength bins; with `--spectral-denoise` from the filtered bins)\n");
+		"          (the image developed from the wavelength bins; with `--spectral-denoise` from the filtered bins)\n"
+		"    `--demodulate[=1|2|4]` (with `--spectral-denoise`: filter illumination -- divide by the first-hit albedo per bin, <k> x <k> rays per pixel, before; multiply after)\n"
+		"    `--albedo-output=<file.npy>` (needs `--spectral-bins=<n>`: the first-hit albedo per wavelength bin)\n");
 }
 
 struct ArgList {
@@ -113,6 +118,9 @@ struct Progressive { // the flags of the progressive modes
 	std::string develop_output, develop_filter, develop_relight; // --develop-output / --develop-filter / --develop-relight: "" = none
 	int develop_observer = 0;    // --develop-observer: 0 = the render's
 	bool spectral_bins_given = false;
+	bool demodulate = false;     // --demodulate[=K]
+	ssx::Renderer::DemodParams demod_params;
+	std::string albedo_output;   // --albedo-output: "" = none
 };
 
 void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progressive* g) {
@@ -232,6 +240,18 @@ void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progress
 		if (g->spectral_output.empty() && g->develop_output.empty()) { std::fprintf(stderr, "`--spectral-denoise` needs `--spectral-output=<file.npy>`: it filters the bins written there!\n"); throw -2; }
 		g->spectral_denoise = true;
 	}
+	if (a.take("--demodulate", "", &v)) {
+		if (!g->spectral_denoise) { std::fprintf(stderr, "`--demodulate` needs `--spectral-denoise`: it is a mode of that filter!\n"); throw -2; }
+		if (v != "--demodulate") {
+			if (v != "1" && v != "2" && v != "4") { std::fprintf(stderr, "Invalid value for --demodulate (1, 2 or 4 rays per pixel axis)!\n"); throw -2; }
+			g->demod_params.supersample = static_cast<uint32_t>(v[0] - '0');
+		}
+		g->demodulate = true;
+	}
+	if (a.take("--albedo-output", "", &v)) {
+		if (!g->spectral_bins_given || o->rgb_mode) { std::fprintf(stderr, "`--albedo-output` needs `--spectral-bins=<n>` and a spectral render: it writes the albedo of those bins!\n"); throw -2; }
+		g->albedo_output = v;
+	}
 	const bool filters = g->denoise || g->spectral_denoise; // both render for the filter: the noise estimate on, two batches at least
 	const char* const flag = g->denoise ? "--denoise" : "--spectral-denoise";
 	if (filters && o->spp < 2) { std::fprintf(stderr, "`%s` needs at least two samples per pixel: its variance estimate compares batches of samples!\n", flag); throw -2; }
@@ -324,14 +344,15 @@ int main(int argc, char* argv[]) {
 		renderer.render_wait();
 		std::vector<float> filtered_bins;
 		if (prog.spectral_denoise && (prog.denoise || !prog.spectral_output.empty())) { // (one run of the filter serves both outputs)
-			const ssx::Framebuffer fb = renderer.denoise_spectral(prog.denoise_params, &filtered_bins);
+			const ssx::Framebuffer fb = renderer.denoise_spectral(prog.denoise_params, &filtered_bins, nullptr, prog.demodulate ? &prog.demod_params : nullptr);
 			if (prog.denoise) fb.save(denoised_path);
 		} else if (prog.denoise) renderer.denoise(prog.denoise_params).save(denoised_path);
 		if (!prog.guides_output.empty()) renderer.save_guides(prog.guides_output);
+		if (!prog.albedo_output.empty()) renderer.save_albedo_bins(prog.albedo_output, prog.spectral_bins, prog.demod_params.supersample);
 		if (prog.spectral_denoise && !prog.spectral_output.empty()) renderer.save_spectral_image(prog.spectral_output, filtered_bins);
 		else if (!prog.spectral_output.empty()) renderer.save_spectral_image(prog.spectral_output);
 		if (!prog.develop_output.empty()) { // X, Y, Z from the bins, the alpha of the render's image, then the store of --output
-			const std::vector<float> xyz = renderer.develop(develop_weights.data(), 3, prog.spectral_denoise ? &prog.denoise_params : nullptr);
+			const std::vector<float> xyz = renderer.develop(develop_weights.data(), 3, prog.spectral_denoise ? &prog.denoise_params : nullptr, prog.demodulate ? &prog.demod_params : nullptr);
 			const size_t pixels = options.res[0] * options.res[1];
 			std::vector<float> xyza(pixels * 4);
 			for (size_t p = 0; p < pixels; ++p) { xyza[4 * p] = xyz[3 * p]; xyza[4 * p + 1] = xyz[3 * p + 1]; xyza[4 * p + 2] = xyz[3 * p + 2]; xyza[4 * p + 3] = renderer.xyza[4 * p + 3]; }

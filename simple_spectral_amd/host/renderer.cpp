@@ -1,6 +1,7 @@
 #include "renderer.hpp"
 
 #include "checkpoint.hpp"
+#include "develop.hpp"
 #include "image_io.hpp"
 
 #include <dlfcn.h>
@@ -57,6 +58,9 @@ struct Renderer::Api {
 	int (*denoise_spectral)(ssx_ctx*, const ssx_denoise_params*, float*, float*, float*) = nullptr;
 	int (*develop_images)(ssx_ctx*, uint32_t, uint32_t, uint32_t, const float*, const float*, uint32_t, float*) = nullptr;
 	int (*spectral_develop)(ssx_ctx*, const ssx_denoise_params*, const float*, uint32_t, float*) = nullptr;
+	int (*albedo_bins)(ssx_ctx*, uint32_t, uint32_t, uint32_t, uint32_t, float*) = nullptr;
+	int (*denoise_spectral_demod)(ssx_ctx*, const ssx_denoise_params*, const ssx_demod_params*, const float*, float*, float*, float*) = nullptr;
+	int (*spectral_develop_demod)(ssx_ctx*, const ssx_denoise_params*, const ssx_demod_params*, const float*, const float*, uint32_t, float*) = nullptr;
 
 	explicit Api(const std::string& path) {
 		handle = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
@@ -99,6 +103,9 @@ struct Renderer::Api {
 		denoise_spectral = reinterpret_cast<decltype(denoise_spectral)>(sym("ssx_denoise_spectral"));
 		develop_images = reinterpret_cast<decltype(develop_images)>(sym("ssx_develop_images"));
 		spectral_develop = reinterpret_cast<decltype(spectral_develop)>(sym("ssx_spectral_develop"));
+		albedo_bins = reinterpret_cast<decltype(albedo_bins)>(sym("ssx_albedo_bins"));
+		denoise_spectral_demod = reinterpret_cast<decltype(denoise_spectral_demod)>(sym("ssx_denoise_spectral_demod"));
+		spectral_develop_demod = reinterpret_cast<decltype(spectral_develop_demod)>(sym("ssx_spectral_develop_demod"));
 	}
 	~Api() { if (handle) dlclose(handle); }
 };
@@ -372,7 +379,32 @@ Framebuffer Renderer::denoise(const DenoiseParams& params, std::vector<float>* x
 	return fb;
 }
 
-Framebuffer Renderer::denoise_spectral(const DenoiseParams& params, std::vector<float>* bins, std::vector<float>* xyza_out) {
+std::vector<float> Renderer::albedo_bins(size_t bins, uint32_t supersample) {
+	wait_workers_();
+	const size_t W = options.res[0], H = options.res[1];
+	std::vector<float> rho(W * H * bins);
+	check_(api_->albedo_bins(ctxs_[0], static_cast<uint32_t>(W), static_cast<uint32_t>(H), static_cast<uint32_t>(bins), supersample, rho.data()), "ssx_albedo_bins", ctxs_[0]);
+	return rho;
+}
+
+void Renderer::save_albedo_bins(const std::string& path, size_t bins, uint32_t supersample) {
+	const std::vector<float> rho = albedo_bins(bins, supersample);
+	const size_t shape[3] = { options.res[1], options.res[0], bins };
+	save_npy_f32(path, rho.data(), shape, 3);
+}
+
+std::vector<float> Renderer::demod_weights_(const DemodParams& demod) const {
+	const size_t B = spectral_bins_;
+	if (!demod.weights_xyz.empty()) {
+		if (demod.weights_xyz.size() != 3 * B) throw HostError{ SSX_ERR_ARG, "DemodParams.weights_xyz is not [3][bins]" };
+		return demod.weights_xyz;
+	}
+	const ssx_scene_desc& d = scene->desc();
+	const std::vector<double> w = develop_weights({ color->std_obs_xbar, color->std_obs_ybar, color->std_obs_zbar }, nullptr, nullptr, nullptr, static_cast<uint32_t>(B), d.lambda_min, d.lambda_step);
+	return std::vector<float>(w.begin(), w.end()); // (rounded to binary32 here, once)
+}
+
+Framebuffer Renderer::denoise_spectral(const DenoiseParams& params, std::vector<float>* bins, std::vector<float>* xyza_out, const DemodParams* demod) {
 	wait_workers_();
 	if (!spectral_bins_) throw HostError{ SSX_ERR_STATE, "denoise_spectral: spectral output is off (set_spectral_bins)" };
 	const size_t W = options.res[0], H = options.res[1], pixels = W * H, B = spectral_bins_, M = B / 4, E = B + M, n_dev = ctxs_.size();
@@ -380,7 +412,15 @@ Framebuffer Renderer::denoise_spectral(const DenoiseParams& params, std::vector<
 	dp.struct_size = sizeof dp; dp.levels = params.levels; dp.sigma_l = params.sigma_l; dp.sigma_a = params.sigma_a;
 	std::vector<float> out(pixels * 4), mean(pixels * B);
 	ssx_ctx* root = ctxs_[0];
-	if (n_dev == 1) check_(api_->denoise_spectral(root, &dp, mean.data(), out.data(), nullptr), "ssx_denoise_spectral", root);
+	ssx_demod_params dm{};
+	std::vector<float> wc;
+	if (demod) {
+		dm.struct_size = sizeof dm; dm.supersample = demod->supersample; dm.albedo_floor = demod->albedo_floor;
+		wc = demod_weights_(*demod);
+		dp.sigma_a = 1.0f; // (ignored in this mode: the albedo guide is zero)
+	}
+	if (n_dev == 1 && demod) check_(api_->denoise_spectral_demod(root, &dp, &dm, wc.data(), mean.data(), out.data(), nullptr), "ssx_denoise_spectral_demod", root);
+	else if (n_dev == 1) check_(api_->denoise_spectral(root, &dp, mean.data(), out.data(), nullptr), "ssx_denoise_spectral", root);
 	else {
 		// as denoise() combines image and variance; the sums S and counts N come from the device that owns the pixel, bit for bit (spectral_image's merge)
 		level_devices();
@@ -405,12 +445,42 @@ Framebuffer Renderer::denoise_spectral(const DenoiseParams& params, std::vector<
 				for (size_t m = 0; m < M; ++m) e0[p * E + B + m] = static_cast<float>(static_cast<double>(part_n[p * M + m]) / n);
 			}
 		}
-		check_(api_->denoise_channels(root, &dp, static_cast<uint32_t>(W), static_cast<uint32_t>(H), xyza.data(), var.data(), g.prim.data(), g.albedo.data(),
+		// the demodulated mode: DEMODULATE and REMODULATE of include/ssx.h on the host, in binary32, around the same pure filter with a zero albedo guide
+		std::vector<float> rho, rc, c_in(xyza), zero;
+		std::vector<uint8_t> valid;
+		const float f = demod ? demod->albedo_floor : 0.0f;
+		const auto floored = [f](float r) { return r > f ? r : f; };
+		if (demod) {
+			if (!(f > 0.0f) || !std::isfinite(f)) throw HostError{ SSX_ERR_ARG, "DemodParams.albedo_floor must be finite and positive" };
+			float den[3];
+			for (size_t c = 0; c < 3; ++c) { // the develop's accumulation of all ones
+				volatile float acc = 0.0f;
+				for (size_t b = 0; b < B; ++b) acc = acc + wc[c * B + b];
+				den[c] = acc;
+				if (!(den[c] > 0.0f)) throw HostError{ SSX_ERR_ARG, "denoise_spectral: a row of weights_xyz does not sum to a positive denominator" };
+			}
+			rho = albedo_bins(B, demod->supersample);
+			rc.resize(pixels * 3);
+			check_(api_->develop_images(root, static_cast<uint32_t>(W), static_cast<uint32_t>(H), static_cast<uint32_t>(B), rho.data(), wc.data(), 3, rc.data()), "ssx_develop_images", root);
+			valid.resize(pixels);
+			zero.assign(pixels * 4, 0.0f);
+			for (size_t p = 0; p < pixels; ++p) {
+				for (size_t c = 0; c < 3; ++c) rc[p * 3 + c] = floored(rc[p * 3 + c] / den[c]);
+				valid[p] = std::isfinite(xyza[p * 4]) && std::isfinite(xyza[p * 4 + 1]) && std::isfinite(xyza[p * 4 + 2]) && std::isfinite(var[p]);
+				if (!valid[p]) continue;
+				for (size_t b = 0; b < B; ++b) e0[p * E + b] = e0[p * E + b] / floored(rho[p * B + b]);
+				for (size_t c = 0; c < 3; ++c) c_in[p * 4 + c] = c_in[p * 4 + c] / rc[p * 3 + c];
+				var[p] = var[p] / (rc[p * 3 + 1] * rc[p * 3 + 1]);
+			}
+		}
+		check_(api_->denoise_channels(root, &dp, static_cast<uint32_t>(W), static_cast<uint32_t>(H), c_in.data(), var.data(), g.prim.data(), demod ? zero.data() : g.albedo.data(),
 		                              static_cast<uint32_t>(E), e0.data(), out.data(), nullptr, eL.data()), "ssx_denoise_channels", root);
 		for (size_t p = 0; p < pixels; ++p) for (size_t b = 0; b < B; ++b) {
 			const float den = eL[p * E + B + b % M];
-			mean[p * B + b] = den > 0.0f ? eL[p * E + b] / den : 0.0f;
+			const float r = demod && valid[p] ? floored(rho[p * B + b]) : 1.0f;
+			mean[p * B + b] = den > 0.0f ? (demod ? (eL[p * E + b] / den) * r : eL[p * E + b] / den) : 0.0f;
 		}
+		if (demod) for (size_t p = 0; p < pixels; ++p) if (valid[p]) for (size_t c = 0; c < 3; ++c) out[p * 4 + c] = out[p * 4 + c] * rc[p * 3 + c];
 	}
 	Framebuffer fb(options.res);
 	color->xyza_to_srgba(out.data(), fb.data(), pixels);
@@ -419,7 +489,7 @@ Framebuffer Renderer::denoise_spectral(const DenoiseParams& params, std::vector<
 	return fb;
 }
 
-std::vector<float> Renderer::develop(const float* weights, size_t channels, const DenoiseParams* denoise) {
+std::vector<float> Renderer::develop(const float* weights, size_t channels, const DenoiseParams* denoise, const DemodParams* demod) {
 	wait_workers_();
 	if (!spectral_bins_) throw HostError{ SSX_ERR_STATE, "develop: spectral output is off (set_spectral_bins)" };
 	const size_t W = options.res[0], H = options.res[1], pixels = W * H, B = spectral_bins_, C = channels, n_dev = ctxs_.size();
@@ -428,10 +498,16 @@ std::vector<float> Renderer::develop(const float* weights, size_t channels, cons
 	ssx_ctx* root = ctxs_[0];
 	ssx_denoise_params dp{};
 	if (denoise) { dp.struct_size = sizeof dp; dp.levels = denoise->levels; dp.sigma_l = denoise->sigma_l; dp.sigma_a = denoise->sigma_a; }
-	if (n_dev == 1) check_(api_->spectral_develop(root, denoise ? &dp : nullptr, weights, c32, out.data()), "ssx_spectral_develop", root);
+	if (demod && !denoise) throw HostError{ SSX_ERR_ARG, "develop: the demodulated mode is a mode of the denoised source (pass denoise)" };
+	if (n_dev == 1 && demod) {
+		ssx_demod_params dm{};
+		dm.struct_size = sizeof dm; dm.supersample = demod->supersample; dm.albedo_floor = demod->albedo_floor;
+		const std::vector<float> wc = demod_weights_(*demod);
+		check_(api_->spectral_develop_demod(root, &dp, &dm, wc.data(), weights, c32, out.data()), "ssx_spectral_develop_demod", root);
+	} else if (n_dev == 1) check_(api_->spectral_develop(root, denoise ? &dp : nullptr, weights, c32, out.data()), "ssx_spectral_develop", root);
 	else if (denoise) {
 		std::vector<float> bins;
-		(void)denoise_spectral(*denoise, &bins);
+		(void)denoise_spectral(*denoise, &bins, nullptr, demod);
 		check_(api_->develop_images(root, static_cast<uint32_t>(W), static_cast<uint32_t>(H), static_cast<uint32_t>(B), bins.data(), weights, c32, out.data()), "ssx_develop_images", root);
 	} else {
 		level_devices(); // (a stopped render: one sample count behind every pixel)

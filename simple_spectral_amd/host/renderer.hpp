@@ -119,14 +119,23 @@ public:
 	// the render.  One device: ssx_denoise_spectral, all on the device.  Several: the devices' sums, counts, images and variances combined by ownership, the
 	// channels e0 built here by the header's formula, ssx_denoise_channels on device 0, the ratio formed here -- the same bits.  Returns the filtered image,
 	// which is denoise()'s (xyza_out as there).  Nothing the devices hold changes.
-	Framebuffer denoise_spectral(const DenoiseParams& params, std::vector<float>* bins, std::vector<float>* xyza_out = nullptr);
+	// demod (optional): the demodulated mode (include/ssx.h "Demodulated denoising") -- bins, image and variance divided by the first-hit albedo before the filter
+	// and multiplied by it afterwards; params.sigma_a is ignored then.  One device: ssx_denoise_spectral_demod, all on the device.  Several: as above, with the
+	// albedo bins of device 0 (ssx_albedo_bins; they do not depend on ownership), the channel albedo through ssx_develop_images, the divide and the multiply here by
+	// the header's formulas and ssx_denoise_channels with a zero albedo guide between them -- the same bits.
+	struct DemodParams { uint32_t supersample = 2; float albedo_floor = SSX_DEMOD_DEFAULT_FLOOR; std::vector<float> weights_xyz; }; // weights_xyz [3][B]; empty: the develop weights of the render's own observer
+	Framebuffer denoise_spectral(const DenoiseParams& params, std::vector<float>* bins, std::vector<float>* xyza_out = nullptr, const DemodParams* demod = nullptr);
+	// ssx_albedo_bins of device 0 at the options' resolution: [height][width][bins], row 0 = bottom; supersample x supersample rays per pixel (1, 2 or 4)
+	std::vector<float> albedo_bins(size_t bins, uint32_t supersample = 2);
+	void save_albedo_bins(const std::string& path, size_t bins, uint32_t supersample = 2); // ... as a .npy file
 	void save_spectral_image(const std::string& path, const std::vector<float>& bins); // a [height][width][B] array, e.g. denoise_spectral's, in spectral_image's .npy layout
 
 	// Developing the bins (include/ssx.h "Developing the spectral bins"): weights [channels][B] (host/develop.hpp builds them) -> [height][width][channels], row 0 =
 	// bottom.  denoise == nullptr: the raw source -- every device develops its own pixels (ssx_spectral_develop) and the shares are combined by ownership mask.
 	// Otherwise the denoised source: one device runs ssx_spectral_develop with the parameters, all on the device; several follow denoise_spectral's path and
 	// then ssx_develop_images on device 0.  Either way the same bits as one device.  After render_wait(); nothing the devices hold changes.
-	std::vector<float> develop(const float* weights, size_t channels, const DenoiseParams* denoise = nullptr);
+	// demod (with denoise): the bins filtered in the demodulated mode -- one device: ssx_spectral_develop_demod; several: denoise_spectral's path as above.
+	std::vector<float> develop(const float* weights, size_t channels, const DenoiseParams* denoise = nullptr, const DemodParams* demod = nullptr);
 
 private:
 	struct Api;
@@ -136,6 +145,7 @@ private:
 	bool started_ = false;
 	bool need_join_ = false;    // a worker of every context is running or waits to be joined
 	size_t spectral_bins_ = 0;
+	std::vector<float> demod_weights_(const DemodParams& demod) const; // demod.weights_xyz, or the render's own observer's develop weights over the bins
 	size_t expected_spp_ = 0;   // the count the running (or last) call renders to: what render_wait compares ssx_done_spp with
 	ssx_render_params params_for_(size_t d, size_t spp, size_t spp_per_launch) const;
 	void start_(size_t spp, size_t spp_per_launch);

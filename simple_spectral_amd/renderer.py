@@ -526,34 +526,78 @@ class Renderer:
                                                    None if vout is None else vout.ctypes.data, eout.ctypes.data))
         return (eout, out, vout) if return_image else eout
 
-    def denoise_spectral(self, levels=5, sigma_l=1.0, sigma_a=0.1, return_image=False):
+    def albedo_bins(self, bins, supersample=_capi.SSX_DEMOD_DEFAULT_SUPERSAMPLE, res=None):
+        """ssx_albedo_bins -> float32 [H, W, bins]: the first-hit albedo per wavelength bin, averaged over supersample x supersample rays per pixel (1, 2 or 4),
+        at the options' resolution or `res` = (W, H).  At supersample 1 and 4 bins it is guides()["albedo"]."""
+        W, H = res if res is not None else self.options.res
+        rho = np.zeros((H, W, int(bins)), dtype=np.float32)
+        self._check(self._lib.ssx_albedo_bins(self._ctx, W, H, int(bins), int(supersample), rho.ctypes.data))
+        return rho
+
+    def _demod_args(self, demodulate, bins):
+        """(ssx_demod_params, weights_xyz float32 [3, bins]) from demodulate = True (the defaults) or a dict with any of supersample, albedo_floor, weights_xyz;
+        the weights default to develop_weights of the render's own observer."""
+        d = {} if demodulate is True else dict(demodulate)
+        p = _capi.SsxDemodParams()
+        p.struct_size = C.sizeof(_capi.SsxDemodParams)
+        p.supersample = int(d.pop("supersample", _capi.SSX_DEMOD_DEFAULT_SUPERSAMPLE))
+        p.albedo_floor = float(d.pop("albedo_floor", _capi.SSX_DEMOD_DEFAULT_FLOOR))
+        w = d.pop("weights_xyz", None)
+        if d:
+            raise ValueError("demodulate: unknown key(s) %s" % sorted(d))
+        if w is None:
+            desc = self.scene.desc.contents
+            w = develop_weights(bins, float(desc.lambda_min), float(desc.lambda_step), observer=self.options.observer, data_dir=self.options.data_dir)
+        w = np.ascontiguousarray(w, dtype=np.float32)
+        if w.shape != (3, bins):
+            raise ValueError("demodulate: weights_xyz must have shape [3, %d]" % bins)
+        return p, w
+
+    def denoise_spectral(self, levels=5, sigma_l=None, sigma_a=0.1, return_image=False, demodulate=None):
         """ssx_denoise_spectral: the wavelength bins the context holds, filtered on the device with the weights denoise() applies to the image -> float32
         [H, W, B], the ratio of the filtered per-bin sums to the filtered sample counts (include/ssx.h); with return_image: (bins, xyza, var), the last
-        two those of denoise().  Needs what denoise() needs, and set_spectral_bins before the render; nothing the context holds changes."""
+        two those of denoise().  Needs what denoise() needs, and set_spectral_bins before the render; nothing the context holds changes.
+        demodulate (True, or a dict: _demod_args): ssx_denoise_spectral_demod -- bins, image and variance are divided by the first-hit albedo before the filter
+        and multiplied by it afterwards; sigma_a is ignored.  sigma_l None: 1.0, or the demodulated mode's own default."""
         W, H = self.options.res
         B = getattr(self, "_spectral_bins", 0)                                     # what set_spectral_bins set; 0: off, and ssx_denoise_spectral says so
         mean = np.zeros((H, W, B), dtype=np.float32)
         out = np.zeros((H, W, 4), dtype=np.float32) if return_image else None
         var = np.zeros((H, W), dtype=np.float32) if return_image else None
+        if sigma_l is None:
+            sigma_l = _capi.SSX_DEMOD_DEFAULT_SIGMA_L if demodulate else 1.0
         p = self._denoise_params(levels, sigma_l, sigma_a)
+        if demodulate:
+            dm, w = self._demod_args(demodulate, B if B else 4)
+            self._check(self._lib.ssx_denoise_spectral_demod(self._ctx, C.byref(p), C.byref(dm), w.ctypes.data, mean.ctypes.data if B else None,
+                                                             None if out is None else out.ctypes.data, None if var is None else var.ctypes.data))
+            return (mean, out, var) if return_image else mean
         self._check(self._lib.ssx_denoise_spectral(self._ctx, C.byref(p), mean.ctypes.data if B else None, None if out is None else out.ctypes.data,
                                                    None if var is None else var.ctypes.data))
         return (mean, out, var) if return_image else mean
 
     # ---- developing the bins (include/ssx.h: observers, filters, sensors) ----
 
-    def develop(self, weights, denoise=None):
+    def develop(self, weights, denoise=None, demodulate=None):
         """ssx_spectral_develop: the bins the context holds, mapped on the device by weights [C, B] (develop_weights) -> float32 [H, W, C], row 0 = bottom.
         denoise None: the raw source, q = S * M / n; a dict of denoise_spectral's parameters (levels, sigma_l, sigma_a; {} for the defaults): the filtered bins,
-        developed without leaving the device.  Nothing the context holds changes."""
+        developed without leaving the device.  demodulate (True or a dict, as in denoise_spectral; denoise None counts as {}): ssx_spectral_develop_demod, the
+        bins filtered in the demodulated mode.  Nothing the context holds changes."""
         W, H = self.options.res
         w = np.ascontiguousarray(weights, dtype=np.float32)
         if w.ndim != 2:
             raise ValueError("develop: weights must have shape [C, B]")
         out = np.zeros((H, W, w.shape[0]), dtype=np.float32)
-        p = None if denoise is None else self._denoise_params(denoise.get("levels", 5), denoise.get("sigma_l", 1.0), denoise.get("sigma_a", 0.1))
+        if demodulate and denoise is None:
+            denoise = {}
+        p = None if denoise is None else self._denoise_params(denoise.get("levels", 5), denoise.get("sigma_l", _capi.SSX_DEMOD_DEFAULT_SIGMA_L if demodulate else 1.0),
+                                                              denoise.get("sigma_a", 0.1))
         if getattr(self, "_spectral_bins", 0) not in (0, w.shape[1]):
             raise ValueError("develop: weights for %d bins, the context holds %d" % (w.shape[1], self._spectral_bins))
+        if demodulate:
+            dm, wx = self._demod_args(demodulate, w.shape[1])
+            self._check(self._lib.ssx_spectral_develop_demod(self._ctx, C.byref(p), C.byref(dm), wx.ctypes.data, w.ctypes.data, w.shape[0], out.ctypes.data))
+            return out
         self._check(self._lib.ssx_spectral_develop(self._ctx, None if p is None else C.byref(p), w.ctypes.data, w.shape[0], out.ctypes.data))
         return out
 
