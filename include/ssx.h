@@ -423,8 +423,9 @@ int ssx_noise_info(ssx_ctx* ctx, double* v_out, double summary[4]);
  *   non-finite flux is added as it is; pixels a context does not own read as 0.
  * The state is valid from zero samples or not at all: an ssx_render_start that walks through the samples (tile_major = 0) resets it and accumulates,
  * ssx_render_continue carries it on; whatever invalidates the pixel sums (ssx_upload_scene, ssx_debug_samples, a failed render) and a changed bin
- * count clear it; ssx_sums_import leaves it invalid (the checkpoint file carries no bins: a continue after an import renders normally, and
- * ssx_spectral_read returns SSX_ERR_STATE).  The XYZ image of a render does not depend on whether spectral output is on.
+ * count clear it; ssx_sums_import ALONE leaves it invalid (pixel sums carry no bins: a continue after an import renders normally, and
+ * ssx_spectral_read returns SSX_ERR_STATE) -- ssx_spectral_import, called on top of it with the bins of the same samples, makes it valid again, so that a
+ * checkpoint which carries the bins (libssx_host.so: "SSXCKPT2") resumes with them.  The XYZ image of a render does not depend on whether spectral output is on.
  * While it is on, refused with SSX_ERR_ARG: renders of a scene in SSX_MODE_RGB, libm = SSX_LIBM_GLIBC_2_35, tile_major renders and
  * ssx_render_device.  These are out of scope so far, not limits of the design (the flux-storing kernels exist for the default libm only, and only
  * the sample walk runs the binning kernel between its launches). */
@@ -445,6 +446,19 @@ typedef struct ssx_spectral_info_t {
 /* Row-major (row 0 = bottom) mean [height][width][B] (float), sums [height][width][B] (the binary64 accumulators S) and counts [height][width][M];
  * any of the three may be NULL.  info is filled.  SSX_ERR_STATE: spectral output is off, a render runs, or the context holds no valid bins. */
 int ssx_spectral_read(ssx_ctx* ctx, ssx_spectral_info_t* info, float* mean, double* sums, uint32_t* counts);
+/* The inverse of ssx_spectral_read(sums, counts), for a checkpoint: the context takes, from the whole-image arrays sums [height][width][B] and counts
+ * [height][width][M] (row-major, row 0 = bottom), the tiles it owns under its current parameters -- whoever exported them may have owned other tiles, as long
+ * as the arrays hold every pixel this context owns: one rank's unmerged export holds zeros elsewhere (merge the ranks' exports by ownership first).  One
+ * kernel, a transposition through LDS per owned 8x8 tile; tile lanes outside a ragged image receive +0 / 0, as a fresh render leaves them.
+ * Valid only DIRECTLY ON TOP OF ssx_sums_import: the context is continuable, its pixel sums came from that call and nothing has rendered onto them since
+ * (ssx_sums_import alone behaves as before: the bins invalid).  On success the context is exactly what it would be had it rendered the ssx_done_spp samples
+ * itself: ssx_render_continue carries the bins on, ssx_spectral_read, ssx_denoise_spectral, ssx_spectral_develop and the _demod entry points work from them.
+ * The same kernel checks what it takes: every sample is counted exactly once, so over an owned in-image pixel's M counts the sum is done_spp.
+ * SSX_ERR_STATE: spectral output is off, a render runs, or there is no such import underneath.  SSX_ERR_ARG, ssx_last_error naming the field: width or height
+ * differ from the context's; info->bins from its bin count; info->done_spp from ssx_done_spp; lambda_min or bin_width, compared as bits, from the uploaded
+ * scene's; the check of the counts fails; what a render with spectral output is refused for (SSX_MODE_RGB, libm).  After a refusal the bins are invalid and the
+ * pixel sums of ssx_sums_import are what they were: a continue renders normally.  done_spp == 0 is legal (all arrays zero). */
+int ssx_spectral_import(ssx_ctx* ctx, const ssx_spectral_info_t* info, const double* sums /* [H][W][B] */, const uint32_t* counts /* [H][W][M] */);
 
 /* ---- Denoising: first-hit guide buffers and a variance-guided a-trous filter (appended; same ABI version) -----------------------------------
  * The definitions are this library's (the reference has nothing like them).  Unless said otherwise everything is binary32 with IEEE + - * / and sqrtf,
@@ -532,7 +546,7 @@ int ssx_denoise_channels(ssx_ctx* ctx, const ssx_denoise_params* params, uint32_
                          float* xyza_out, float* var_out, float* extra_out /* [H][W][E] */);
 /* SPECTRAL CHANNELS from the context's own state, without leaving the device: mean_out [height][width][B] receives `out`, xyza_out and var_out what
  * ssx_denoise returns; any of the three may be NULL.  The rules of ssx_denoise, and one more: spectral output must be on and the context must hold valid
- * bins (after ssx_sums_import it holds none) -- otherwise SSX_ERR_STATE with the reason in ssx_last_error.  It reads only: image, sums, noise and spectral
+ * bins (after ssx_sums_import without ssx_spectral_import it holds none) -- otherwise SSX_ERR_STATE with the reason in ssx_last_error.  It reads only: image, sums, noise and spectral
  * state stay as they are, so an ssx_render_continue afterwards leaves the bits of a one-shot render in the image and in ssx_spectral_read. */
 int ssx_denoise_spectral(ssx_ctx* ctx, const ssx_denoise_params* params, float* mean_out /* [H][W][B] */, float* xyza_out, float* var_out);
 
@@ -586,7 +600,7 @@ int ssx_develop_images(ssx_ctx* ctx, uint32_t width, uint32_t height, uint32_t b
  * parameters (the filter runs as in ssx_denoise_spectral and its ratio is developed where it lies).  out: [height][width][channels] of the render's size, row
  * 0 = bottom (NULL: the kernels run and the result stays on the device -- for measurements).  It reads only: image, sums, noise and spectral state stay as they are, so an
  * ssx_render_continue afterwards leaves the bits of a one-shot render in the image and in ssx_spectral_read.  SSX_ERR_STATE, with the reason in
- * ssx_last_error: spectral output is off, a render runs, the context holds no valid bins (nothing rendered, or ssx_sums_import, or a changed bin count),
+ * ssx_last_error: spectral output is off, a render runs, the context holds no valid bins (nothing rendered, or ssx_sums_import alone, or a changed bin count),
  * ssx_done_spp == 0, and, for the denoised source, whatever ssx_denoise_spectral refuses.  SSX_ERR_ARG: channels outside 1..16, a NULL weights. */
 int ssx_spectral_develop(ssx_ctx* ctx, const ssx_denoise_params* denoise, const float* weights /* [C][B] */, uint32_t channels, float* out /* [H][W][C] */);
 

@@ -68,6 +68,21 @@ int ssh_checkpoint_load(const char* path, ssx_sums_info_t* info, char* scene_nam
 /* The combine of the ranks' exports: dst's pixels that src_info's exporter owns (tile_first / tile_stride / tile_skew) <- src's, bit for bit
  * -- by ownership mask, not by adding (-0.0 stays -0.0).  dst_s2 / src_s2: the same for S2, or NULL. */
 int ssh_sums_merge(double* dst, double* dst_s2, const double* src, const double* src_s2, const ssx_sums_info_t* src_info);
+/* A checkpoint that also carries the wavelength bins of a render with spectral output -- what ssx_spectral_read hands out as sums and counts and
+ * ssx_spectral_import takes back (ssx.h) -- so that a resumed render keeps them.  Such a file has the magic "SSXCKPT2": the fields of "SSXCKPT1" up to
+ * and including S2, then the ssx_spectral_info_t preceded by its byte count, the sums [height][width][bins] (binary64), the counts [height][width][bins / 4]
+ * (uint32), then the checksum (host/checkpoint.hpp has the layout).  spectral_info == NULL: exactly ssh_checkpoint_save, byte for byte.  SSX_ERR_ARG:
+ * bins no multiple of 4 in 4..64; a width, height or done_spp that differs from info's; a NULL array. */
+int ssh_checkpoint_save_spectral(const char* path, const ssx_sums_info_t* info, const char* scene_name, const char* options_text, const double* sums, const double* noise_s2,
+                                 const ssx_spectral_info_t* spectral_info, const double* spectral_sums, const uint32_t* spectral_counts);
+/* Reads either kind (so does ssh_checkpoint_load, which passes over the bins).  From an "SSXCKPT1" file spectral_info->bins is 0 and both array outputs
+ * are NULL; otherwise they are malloc'ed like *sums_out: release with ssh_free.  SSX_ERR_DATA also: a bin count outside {4, ..., 64}, arrays whose size does
+ * not follow from the header. */
+int ssh_checkpoint_load_spectral(const char* path, ssx_sums_info_t* info, char* scene_name, size_t scene_name_size, char* options_text, size_t options_text_size,
+                                 double** sums_out, double** noise_s2_out, ssx_spectral_info_t* spectral_info, double** spectral_sums_out, uint32_t** spectral_counts_out);
+/* ssh_sums_merge's rule for the bins: dst's pixels that src_sums_info's exporter owns <- src's, bit for bit, sums [height][width][bins] and counts
+ * [height][width][bins / 4] (either pair may be NULL).  The merged arrays of all ranks are what a context of any ownership imports. */
+int ssh_spectral_merge(double* dst_sums, uint32_t* dst_counts, const double* src_sums, const uint32_t* src_counts, uint32_t bins, const ssx_sums_info_t* src_sums_info);
 
 /* A NumPy .npy file (format version 1.0, '<f4', C order) of `data` with the given shape: what np.load reads, and the bytes np.save writes for the
  * same array.  The CLI's --spectral-output writes the spectral image with it: shape (height, width, bins), row 0 = bottom. */

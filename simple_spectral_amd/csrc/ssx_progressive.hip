@@ -193,7 +193,7 @@ int ssx_sums_import(ssx_ctx* ctx, const ssx_render_params* params, const ssx_sum
 	pp.spp = info->done_spp ? info->done_spp : 1u;
 	if ((rc = ready_to_launch(ctx, &pp, true))) return rc;
 	sums_invalidate(ctx);
-	ctx->spectral_note = "the sums came from ssx_sums_import, which carries no spectral state";
+	ctx->spectral_note = "the sums came from ssx_sums_import, which carries no spectral state (ssx_spectral_import puts the bins of the same samples next to them)";
 	const size_t pixels = (size_t)pp.width * pp.height;
 	const bool s2_given = noise_s2 && info->noise_batches;
 	DeviceBuffer& stage = ctx->d_stage;
@@ -212,6 +212,7 @@ int ssx_sums_import(ssx_ctx* ctx, const ssx_render_params* params, const ssx_sum
 	ctx->total_spp = 0; ctx->k_begin = 0;
 	ctx->done_tiles.store(0);
 	sums_publish(ctx, info->done_spp, !ctx->noise_on ? -1 : s2_given ? (int64_t)info->noise_batches : (info->done_spp ? 1 : 0)); // (the kernel made one batch of sums without S2)
+	ctx->sums.imported = true;
 	return SSX_OK;
 }
 

@@ -1,7 +1,8 @@
 // ssx_spectral.hip -- spectral radiance output: per-pixel wavelength bins of the hero fluxes (include/ssx.h, "Spectral radiance output").  Part of
 // ssx_api.hip's translation unit (included behind its context and launch helpers, like ssx_progressive.hip).  The path kernels' part is one store:
 // the fold of the _flux twins leaves every sample's hero flux in flux[] (ssx_kernels.hip resolve_records).  Everything else is here: the kernel that
-// bins a launch's samples, run after each launch of the sample walk next to the noise estimate's, the export kernel and the entry points.
+// bins a launch's samples, run after each launch of the sample walk next to the noise estimate's, the export kernel, its inverse (ssx_spectral_import: the bins
+// of a checkpoint taken up again) and the entry points.
 
 // What ssx_spectral_bin_kernel needs of a launch: the records [tile slot][k - k0][pixel of the tile] of its flux[] and st[] arrays (st[r].x is lambda_0
 // once the path has ended), and the persistent state S[tile slot][bin][pixel of the tile] (binary64) and N[tile slot][m][pixel of the tile].
@@ -61,6 +62,59 @@ extern "C" __global__ void __launch_bounds__(256) ssx_spectral_export_kernel(con
 	}
 }
 
+// The inverse of the export for the tiles this context owns: row-major whole-image sums [height][width][B] and counts [height][width][M] (row 0 = bottom; whoever
+// exported them may have owned other tiles) -> S[tile slot][bin][pixel of the tile], N[tile slot][m][pixel of the tile].  A transposition through LDS, one
+// 256-lane workgroup per owned tile slot (slot -> tile by tile_of_slot), no atomics: a workgroup writes its own slot only.
+//   in:   the 8 pixel rows of a tile are 8 runs of cols * B consecutive doubles in the source (cols = 8, fewer in the image's last tile column; 4 KB at B = 64).
+//         Consecutive lanes read consecutive 16-byte pairs of a run -- B is a multiple of 4, so every run starts 32-byte aligned in an array that is -- and the
+//         counts' runs of cols * M words word by word (M may be odd: such a run has no alignment to speak of).  Rows and columns outside a ragged image are
+//         never read.
+//   LDS:  [64 pixels][B + 1] doubles, then [64 pixels][M | 1] words.  The strides are ODD numbers of elements: on the way out lane = pixel reads element b of
+//         its row, i.e. 8-byte address (B + 1) * pixel + b.  A ds_read_b64 is served in two groups of 32 lanes over 64 four-byte banks, bank = (address / 4) mod
+//         64, so the 32 lanes of a group need 32 distinct even bank pairs: 2 * (B + 1) * pixel mod 64 distinct for 32 consecutive pixels, which holds exactly
+//         when the stride is odd (one element of padding: the access width); the unpadded stride B -- 4, ..., 64 doubles -- would put 2, ..., 32 lanes on one
+//         bank pair.  The counts' ds_read_b32 has 32 banks for 32 lanes: an odd word stride again, M + 1 for an even M, M itself for an odd one.  The price is on
+//         the way in: with an odd stride a pixel's row starts 8-byte aligned only, so a pair is stored as two 8-byte writes (16 lanes a group, 32 banks, lanes l
+//         and l + 8 on the same ones: 2-way), which the write's own register transfer mostly covers.  33 KB + 4 KB at B = 64.
+//   out:  wave w stores bins w, w + 4, ...: per bin the 64 lanes' doubles are 512 consecutive bytes, per m 256.  Lanes of pixels outside the image store +0 / 0,
+//         what the memset of a fresh render leaves there.
+// The check: every sample is counted exactly once, misses included (ssx_spectral_bin_kernel), so for an in-image pixel the sum of its M counts is done_spp --
+// after a finished render, a stopped one (the walk stops between launches, after the launch's bins) and a levelled one alike.  A pixel that breaks it stores
+// 1 into *bad (a plain store; every writer stores the same value).
+extern "C" __global__ void __launch_bounds__(256) ssx_spectral_import_kernel(const double* sums, const uint32_t* counts, double* S, uint32_t* N, uint32_t* bad, SsxPixelGrid g, uint32_t M, uint32_t done_spp) {
+	extern __shared__ double spectral_lds[];
+	const uint32_t tid = threadIdx.x, slot = blockIdx.x, B = 4u * M, s_stride = B + 1u, n_stride = M | 1u;
+	uint32_t tx, ty;
+	(void)tile_of_slot(g, slot, tx, ty);
+	const uint32_t i0 = tx * 8u, j0 = ty * 8u, cols = min(8u, g.width - i0), rows = min(8u, g.height - j0);
+	double* const ls = spectral_lds;                                                               // [pixel * s_stride + b]
+	uint32_t* const ln = reinterpret_cast<uint32_t*>(spectral_lds + 64u * s_stride);               // [pixel * n_stride + m]
+	const uint32_t pairs = cols * (B / 2u);                                                        // 16-byte pairs of one run
+	for (uint32_t e = tid; e < rows * pairs; e += 256u) {
+		const uint32_t r = e / pairs, v = e - r * pairs, c = (2u * v) / B, b = 2u * v - c * B;       // (B is even: a pair never straddles two pixels)
+		const double2 d = reinterpret_cast<const double2*>(sums + ((size_t)(j0 + r) * g.width + i0) * B)[v];
+		double* const o = ls + (r * 8u + c) * s_stride + b;
+		o[0] = d.x; o[1] = d.y;
+	}
+	const uint32_t words = cols * M;
+	for (uint32_t e = tid; e < rows * words; e += 256u) {
+		const uint32_t r = e / words, v = e - r * words, c = v / M, m = v - c * M;
+		ln[(r * 8u + c) * n_stride + m] = counts[((size_t)(j0 + r) * g.width + i0) * M + v];
+	}
+	__syncthreads();
+	const uint32_t px = tid & 63u, w = tid >> 6;
+	const bool inside = (px & 7u) < cols && (px >> 3) < rows;
+	double* const So = S + (size_t)slot * B * 64u + px;
+	uint32_t* const No = N + (size_t)slot * M * 64u + px;
+	for (uint32_t b = w; b < B; b += 4u) So[(size_t)b * 64u] = inside ? ls[px * s_stride + b] : 0.0;
+	for (uint32_t m = w; m < M; m += 4u) No[(size_t)m * 64u] = inside ? ln[px * n_stride + m] : 0u;
+	if (w == 0u && inside) {
+		uint32_t n = 0u;
+		for (uint32_t m = 0; m < M; ++m) n += ln[px * n_stride + m];
+		if (n != done_spp) *bad = 1u;
+	}
+}
+
 namespace {
 
 size_t spectral_sum_bytes(const ssx_ctx* ctx, uint32_t tiles) { return (size_t)tiles * ctx->spectral_bins * 64u * sizeof(double); }
@@ -76,7 +130,7 @@ int spectral_refuses(ssx_ctx* ctx, const ssx_render_params& p, bool tile_walk) {
 }
 
 // Start of a sample walk.  ssx_render_start: zeroed state for the device's tiles.  A continued render carries valid state on; without it (sums that were
-// imported, or rendered with spectral output off or another bin count) it renders normally and the state stays invalid.  *active: bin this walk's launches.
+// imported without their bins, or rendered with spectral output off or another bin count) it renders normally and the state stays invalid.  *active: bin this walk's launches.
 int spectral_begin(ssx_ctx* ctx, uint32_t my_tiles, bool continuing, bool* active) {
 	*active = ctx->spectral_bins != 0u && (!continuing || ctx->sums.spectral_valid);
 	if (!*active || continuing) return SSX_OK;
@@ -153,6 +207,55 @@ int ssx_spectral_read(ssx_ctx* ctx, ssx_spectral_info_t* info, float* mean, doub
 	if (sums) SSX_HIP(ctx, hipMemcpy(sums, d_sums, b_sums, hipMemcpyDeviceToHost));
 	if (mean) SSX_HIP(ctx, hipMemcpy(mean, d_mean, b_mean, hipMemcpyDeviceToHost));
 	if (counts) SSX_HIP(ctx, hipMemcpy(counts, d_counts, b_counts, hipMemcpyDeviceToHost));
+	return SSX_OK;
+}
+
+int ssx_spectral_import(ssx_ctx* ctx, const ssx_spectral_info_t* info, const double* sums, const uint32_t* counts) {
+	if (!ctx || !info || !sums || !counts) return SSX_ERR_ARG;
+	if (info->struct_size != sizeof *info) return fail(ctx, SSX_ERR_ARG, "ssx_spectral_import: ssx_spectral_info_t.struct_size mismatch");
+	if (!ctx->spectral_bins) return fail(ctx, SSX_ERR_STATE, "ssx_spectral_import: spectral output is off (ssx_set_spectral_bins)");
+	if (ctx->rendering.load()) return fail(ctx, SSX_ERR_STATE, "render in progress");
+	if (!ctx->sums.continuable || !ctx->sums.imported)
+		return fail(ctx, SSX_ERR_STATE, "ssx_spectral_import: the bins go on top of the pixel sums of an ssx_sums_import, directly: the context holds none, or has rendered since");
+	const ssx_render_params& p = ctx->cur;
+	const uint32_t B = ctx->spectral_bins, M = B / 4u, done = ctx->done_spp.load();
+	const float bin_width = ctx->lambda_step / (float)M; // (what ssx_spectral_read reports)
+	if (info->width != p.width || info->height != p.height)
+		return fail(ctx, SSX_ERR_ARG, fmt("ssx_spectral_import: size differs (these bins: %u x %u, this render: %u x %u)", info->width, info->height, p.width, p.height));
+	if (info->bins != B) return fail(ctx, SSX_ERR_ARG, fmt("ssx_spectral_import: bins differs (these bins: %u, this context: %u)", info->bins, B));
+	if (info->done_spp != done) return fail(ctx, SSX_ERR_ARG, fmt("ssx_spectral_import: done_spp differs (these bins: %u, the imported sums: %u)", info->done_spp, done));
+	if (memcmp(&info->lambda_min, &ctx->lambda_min, sizeof(float)) != 0)
+		return fail(ctx, SSX_ERR_ARG, fmt("ssx_spectral_import: lambda_min differs (these bins: %.9g, the uploaded scene: %.9g)", (double)info->lambda_min, (double)ctx->lambda_min));
+	if (memcmp(&info->bin_width, &bin_width, sizeof(float)) != 0)
+		return fail(ctx, SSX_ERR_ARG, fmt("ssx_spectral_import: bin_width differs (these bins: %.9g, the uploaded scene: %.9g)", (double)info->bin_width, (double)bin_width));
+	if (const int rc = spectral_refuses(ctx, p, false)) return rc; // (what a continue with the bins would be refused for)
+	SSX_HIP(ctx, hipSetDevice(ctx->device));
+	if (const int rc = wait_device_pending(ctx)) return rc;
+	const uint32_t tiles = owned_tiles(p);
+	const size_t pixels = (size_t)p.width * p.height, b_sums = pixels * B * sizeof(double), b_counts = pixels * M * sizeof(uint32_t);
+	DeviceBuffer& stage = ctx->d_stage; // sums | counts | the flag of the check
+	SSX_HIP(ctx, stage.reserve(b_sums + b_counts + sizeof(uint32_t)));
+	double* const d_sums = stage.as<double>();
+	uint32_t* const d_counts = reinterpret_cast<uint32_t*>(stage.as<uint8_t>() + b_sums), * const d_bad = d_counts + pixels * M;
+	SSX_HIP(ctx, ctx->d_spectral_sums.reserve(spectral_sum_bytes(ctx, tiles)));
+	SSX_HIP(ctx, ctx->d_spectral_counts.reserve(spectral_count_bytes(ctx, tiles)));
+	// from here on the device state is being replaced: it is valid again only once the check has passed
+	ctx->sums.spectral_valid = false; ctx->spectral_note = "an ssx_spectral_import on top of ssx_sums_import was refused or failed";
+	uint32_t bad = 0;
+	if (tiles) {
+		SSX_HIP(ctx, hipMemcpyAsync(d_sums, sums, b_sums, hipMemcpyHostToDevice, ctx->stream));
+		SSX_HIP(ctx, hipMemcpyAsync(d_counts, counts, b_counts, hipMemcpyHostToDevice, ctx->stream));
+		SSX_HIP(ctx, hipMemsetAsync(d_bad, 0, sizeof(uint32_t), ctx->stream));
+		const size_t lds = 64u * ((size_t)(B + 1u) * sizeof(double) + (size_t)(M | 1u) * sizeof(uint32_t)); // <= 37 KB at 64 bins
+		hipLaunchKernelGGL(ssx_spectral_import_kernel, dim3(tiles), dim3(256), lds, ctx->stream, d_sums, d_counts, ctx->d_spectral_sums.as<double>(),
+		                   ctx->d_spectral_counts.as<uint32_t>(), d_bad, pixel_grid(&p), M, done);
+		SSX_HIP(ctx, hipGetLastError());
+		SSX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+		SSX_HIP(ctx, hipMemcpy(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost));
+	}
+	if (bad) return fail(ctx, SSX_ERR_ARG, fmt("ssx_spectral_import: counts: a pixel this context owns does not hold done_spp = %u samples over its %u counts (every sample is counted once; "
+	                                           "one rank's unmerged export holds zeros where it owned nothing: merge the ranks' exports by ownership first)", done, M));
+	ctx->sums.spectral_valid = true; ctx->spectral_note.clear();
 	return SSX_OK;
 }
 

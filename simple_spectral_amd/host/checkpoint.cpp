@@ -8,6 +8,8 @@ namespace ssx {
 
 namespace {
 const char kMagic[8] = { 'S', 'S', 'X', 'C', 'K', 'P', 'T', '1' };
+const char kMagicSpectral[8] = { 'S', 'S', 'X', 'C', 'K', 'P', 'T', '2' }; // ... with the wavelength bins behind s2
+bool valid_bins(uint32_t bins) { return bins >= 4u && bins <= 64u && bins % 4u == 0u; }
 
 // 64-bit checksum: eight bytes at a time through the splitmix64 finaliser, the length first
 uint64_t mix(uint64_t h, uint64_t w) {
@@ -46,15 +48,25 @@ void checkpoint_save(const std::string& path, const Checkpoint& c) {
 	const size_t pixels = (size_t)c.info.width * c.info.height;
 	if (c.info.struct_size != sizeof(ssx_sums_info_t) || pixels == 0 || c.sums.size() != pixels * 4 || (!c.s2.empty() && c.s2.size() != pixels))
 		throw HostError{ SSX_ERR_ARG, "checkpoint_save: the arrays do not have the size the description names" };
+	const bool spectral = c.spectral.bins != 0u;
+	if (!spectral && (!c.spectral_sums.empty() || !c.spectral_counts.empty())) throw HostError{ SSX_ERR_ARG, "checkpoint_save: wavelength bins without their description" };
+	if (spectral && (c.spectral.struct_size != sizeof(ssx_spectral_info_t) || !valid_bins(c.spectral.bins) || c.spectral.width != c.info.width || c.spectral.height != c.info.height ||
+	                 c.spectral.done_spp != c.info.done_spp || c.spectral_sums.size() != pixels * c.spectral.bins || c.spectral_counts.size() != pixels * (c.spectral.bins / 4u)))
+		throw HostError{ SSX_ERR_ARG, "checkpoint_save: the wavelength bins do not belong to these sums (size, sample count, or a bin count that is no multiple of 4 in 4..64)" };
 	std::vector<uint8_t> b;
-	b.reserve(128 + c.scene_name.size() + c.options_text.size() + (c.sums.size() + c.s2.size()) * 8);
-	put(b, kMagic, 8);
+	b.reserve(160 + c.scene_name.size() + c.options_text.size() + (c.sums.size() + c.s2.size() + c.spectral_sums.size()) * 8 + c.spectral_counts.size() * 4);
+	put(b, spectral ? kMagicSpectral : kMagic, 8);
 	put_u32(b, (uint32_t)sizeof c.info); put(b, &c.info, sizeof c.info);
 	put_u32(b, (uint32_t)c.scene_name.size()); put(b, c.scene_name.data(), c.scene_name.size());
 	put_u32(b, (uint32_t)c.options_text.size()); put(b, c.options_text.data(), c.options_text.size());
 	put_u32(b, c.s2.empty() ? 0u : 1u); put_u32(b, 0u);
 	put(b, c.sums.data(), c.sums.size() * 8);
 	put(b, c.s2.data(), c.s2.size() * 8);
+	if (spectral) {
+		put_u32(b, (uint32_t)sizeof c.spectral); put(b, &c.spectral, sizeof c.spectral);
+		put(b, c.spectral_sums.data(), c.spectral_sums.size() * 8);
+		put(b, c.spectral_counts.data(), c.spectral_counts.size() * 4);
+	}
 	const uint64_t sum = checksum(b.data(), b.size());
 	put(b, &sum, 8);
 	// written next to the target and renamed over it: an interrupted save leaves the previous checkpoint whole
@@ -75,7 +87,8 @@ Checkpoint checkpoint_load(const std::string& path) {
 		if (!f.good()) throw HostError{ SSX_ERR_DATA, "Could not open checkpoint \"" + path + "\"" };
 		b.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
 	}
-	if (b.size() < 8 || std::memcmp(b.data(), kMagic, 8) != 0) throw HostError{ SSX_ERR_DATA, "\"" + path + "\" is not a checkpoint (magic SSXCKPT1 missing)" };
+	const bool spectral = b.size() >= 8 && std::memcmp(b.data(), kMagicSpectral, 8) == 0;
+	if (!spectral && (b.size() < 8 || std::memcmp(b.data(), kMagic, 8) != 0)) throw HostError{ SSX_ERR_DATA, "\"" + path + "\" is not a checkpoint (magic SSXCKPT1 or SSXCKPT2 missing)" };
 	Reader r{ b, 8, path };
 	Checkpoint c;
 	if (r.u32() != sizeof c.info) throw HostError{ SSX_ERR_DATA, "Checkpoint \"" + path + "\": description of another size" };
@@ -87,14 +100,31 @@ Checkpoint checkpoint_load(const std::string& path) {
 	const uint64_t pixels = (uint64_t)c.info.width * c.info.height;
 	if (c.info.struct_size != sizeof c.info || pixels == 0 || pixels > (1ull << 28) || has_s2 > 1u) throw HostError{ SSX_ERR_DATA, "Checkpoint \"" + path + "\" is corrupt (description)" };
 	const uint64_t payload = pixels * (has_s2 ? 5u : 4u) * 8u;
-	if (b.size() - r.at < payload + 8u) throw HostError{ SSX_ERR_DATA, "Checkpoint \"" + path + "\" is truncated" };
-	if (b.size() - r.at != payload + 8u) throw HostError{ SSX_ERR_DATA, "Checkpoint \"" + path + "\" is corrupt (length)" };
+	uint64_t spectral_payload = 0; // the section's bytes; its header lies behind the pixel sums
+	if (spectral) {
+		if (b.size() - r.at < payload + 4u + sizeof c.spectral) throw HostError{ SSX_ERR_DATA, "Checkpoint \"" + path + "\" is truncated" };
+		Reader h{ b, r.at + (size_t)payload, path };
+		if (h.u32() != sizeof c.spectral) throw HostError{ SSX_ERR_DATA, "Checkpoint \"" + path + "\": spectral description of another size" };
+		h.take(&c.spectral, sizeof c.spectral);
+		if (c.spectral.struct_size != sizeof c.spectral || !valid_bins(c.spectral.bins) || c.spectral.width != c.info.width || c.spectral.height != c.info.height || c.spectral.done_spp != c.info.done_spp)
+			throw HostError{ SSX_ERR_DATA, "Checkpoint \"" + path + "\" is corrupt (spectral description: a bin count outside 4..64, or a size or sample count other than the pixel sums')" };
+		spectral_payload = 4u + sizeof c.spectral + pixels * c.spectral.bins * 8u + pixels * (c.spectral.bins / 4u) * 4u;
+	}
+	if (b.size() - r.at < payload + spectral_payload + 8u) throw HostError{ SSX_ERR_DATA, "Checkpoint \"" + path + "\" is truncated" };
+	if (b.size() - r.at != payload + spectral_payload + 8u) throw HostError{ SSX_ERR_DATA, "Checkpoint \"" + path + "\" is corrupt (length)" };
 	uint64_t stored;
 	std::memcpy(&stored, b.data() + b.size() - 8, 8);
 	if (stored != checksum(b.data(), b.size() - 8)) throw HostError{ SSX_ERR_DATA, "Checkpoint \"" + path + "\" is corrupt (checksum)" };
 	c.sums.resize(pixels * 4);
 	r.take(c.sums.data(), c.sums.size() * 8);
 	if (has_s2) { c.s2.resize(pixels); r.take(c.s2.data(), c.s2.size() * 8); }
+	if (spectral) {
+		r.at += 4u + sizeof c.spectral; // (read and checked above)
+		c.spectral_sums.resize(pixels * c.spectral.bins);
+		r.take(c.spectral_sums.data(), c.spectral_sums.size() * 8);
+		c.spectral_counts.resize(pixels * (c.spectral.bins / 4u));
+		r.take(c.spectral_counts.data(), c.spectral_counts.size() * 4);
+	}
 	return c;
 }
 
@@ -104,12 +134,13 @@ bool sums_owner(const ssx_sums_info_t& info, size_t i, size_t j) {
 }
 
 void sums_merge(double* dst, double* dst_s2, const double* src, const double* src_s2, const ssx_sums_info_t& src_info) {
-	for (size_t j = 0; j < src_info.height; ++j) for (size_t i = 0; i < src_info.width; ++i) {
-		if (!sums_owner(src_info, i, j)) continue;
-		const size_t p = j * src_info.width + i;
-		std::memcpy(dst + 4 * p, src + 4 * p, 4 * sizeof(double));
-		if (dst_s2 && src_s2) dst_s2[p] = src_s2[p];
-	}
+	merge_owned(dst, src, 4, src_info);
+	if (dst_s2 && src_s2) merge_owned(dst_s2, src_s2, 1, src_info);
+}
+
+void spectral_merge(double* dst_sums, uint32_t* dst_counts, const double* src_sums, const uint32_t* src_counts, size_t bins, const ssx_sums_info_t& src_info) {
+	if (dst_sums && src_sums) merge_owned(dst_sums, src_sums, bins, src_info);
+	if (dst_counts && src_counts) merge_owned(dst_counts, src_counts, bins / 4u, src_info);
 }
 
 } // namespace ssx

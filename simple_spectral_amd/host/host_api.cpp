@@ -11,6 +11,7 @@
 #include <cstring>
 #include <memory>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 struct ssh_scene {
@@ -115,9 +116,9 @@ int ssh_load_png_rgb8(const char* path, uint8_t** rgb_out, uint32_t* width, uint
 }
 void ssh_free(void* p) { free(p); }
 
-int ssh_checkpoint_save(const char* path, const ssx_sums_info_t* info, const char* scene_name, const char* options_text,
-                        const double* sums, const double* noise_s2) {
-	if (!path || !info || !sums) { g_error = "NULL argument"; return SSX_ERR_ARG; }
+int ssh_checkpoint_save_spectral(const char* path, const ssx_sums_info_t* info, const char* scene_name, const char* options_text, const double* sums, const double* noise_s2,
+                                 const ssx_spectral_info_t* spectral_info, const double* spectral_sums, const uint32_t* spectral_counts) {
+	if (!path || !info || !sums || (spectral_info && (!spectral_sums || !spectral_counts))) { g_error = "NULL argument"; return SSX_ERR_ARG; }
 	try {
 		ssx::Checkpoint c;
 		c.info = *info;
@@ -125,34 +126,76 @@ int ssh_checkpoint_save(const char* path, const ssx_sums_info_t* info, const cha
 		const size_t pixels = (size_t)info->width * info->height;
 		c.sums.assign(sums, sums + pixels * 4);
 		if (noise_s2) c.s2.assign(noise_s2, noise_s2 + pixels);
+		if (spectral_info) {
+			if (spectral_info->bins < 4u || spectral_info->bins > 64u || spectral_info->bins % 4u) { g_error = "ssh_checkpoint_save_spectral: bins must be a multiple of 4 in 4..64"; return SSX_ERR_ARG; }
+			c.spectral = *spectral_info;
+			c.spectral_sums.assign(spectral_sums, spectral_sums + pixels * spectral_info->bins);
+			c.spectral_counts.assign(spectral_counts, spectral_counts + pixels * (spectral_info->bins / 4u));
+		}
 		ssx::checkpoint_save(path, c);
 		return SSX_OK;
 	} catch (const ssx::HostError& e) { return report(e); }
 	catch (const std::exception& e) { g_error = e.what(); return SSX_ERR_DATA; }
 }
 
-int ssh_checkpoint_load(const char* path, ssx_sums_info_t* info, char* scene_name, size_t scene_name_size, char* options_text, size_t options_text_size,
-                        double** sums_out, double** noise_s2_out) {
-	if (!path || !info || !sums_out) { g_error = "NULL argument"; return SSX_ERR_ARG; }
+int ssh_checkpoint_save(const char* path, const ssx_sums_info_t* info, const char* scene_name, const char* options_text,
+                        const double* sums, const double* noise_s2) {
+	return ssh_checkpoint_save_spectral(path, info, scene_name, options_text, sums, noise_s2, nullptr, nullptr, nullptr);
+}
+
+int ssh_checkpoint_load_spectral(const char* path, ssx_sums_info_t* info, char* scene_name, size_t scene_name_size, char* options_text, size_t options_text_size,
+                                 double** sums_out, double** noise_s2_out, ssx_spectral_info_t* spectral_info, double** spectral_sums_out, uint32_t** spectral_counts_out) {
+	if (!path || !info || !sums_out || (spectral_info && (!spectral_sums_out || !spectral_counts_out))) { g_error = "NULL argument"; return SSX_ERR_ARG; }
 	*sums_out = nullptr;
 	if (noise_s2_out) *noise_s2_out = nullptr;
+	if (spectral_info) { memset(spectral_info, 0, sizeof *spectral_info); *spectral_sums_out = nullptr; *spectral_counts_out = nullptr; }
+	double* s2 = nullptr; double* bins = nullptr;
 	try {
 		const ssx::Checkpoint c = ssx::checkpoint_load(path);
 		auto text = [](const std::string& s, char* out, size_t n) { if (out && n) { const size_t k = s.size() < n - 1 ? s.size() : n - 1; memcpy(out, s.data(), k); out[k] = '\0'; } };
-		auto copy = [](const std::vector<double>& v) { double* p = static_cast<double*>(malloc(v.size() * sizeof(double))); if (!p) throw std::bad_alloc(); memcpy(p, v.data(), v.size() * sizeof(double)); return p; };
+		auto copy = [](const auto& v) { // (a malloc'ed copy: ssh_free releases it)
+			using T = typename std::decay_t<decltype(v)>::value_type;
+			T* p = static_cast<T*>(malloc(v.size() * sizeof(T)));
+			if (!p) throw std::bad_alloc();
+			memcpy(p, v.data(), v.size() * sizeof(T));
+			return p;
+		};
 		*info = c.info;
 		text(c.scene_name, scene_name, scene_name_size);
 		text(c.options_text, options_text, options_text_size);
 		*sums_out = copy(c.sums);
-		if (noise_s2_out && !c.s2.empty()) *noise_s2_out = copy(c.s2);
+		if (noise_s2_out && !c.s2.empty()) *noise_s2_out = s2 = copy(c.s2);
+		if (spectral_info && c.spectral.bins) {
+			*spectral_sums_out = bins = copy(c.spectral_sums);
+			*spectral_counts_out = copy(c.spectral_counts);
+			*spectral_info = c.spectral;
+		}
 		return SSX_OK;
 	} catch (const ssx::HostError& e) { return report(e); }
-	catch (const std::exception& e) { free(*sums_out); *sums_out = nullptr; g_error = e.what(); return SSX_ERR_DATA; }
+	catch (const std::exception& e) { // (out of memory half-way: nothing is handed out)
+		free(*sums_out); *sums_out = nullptr; free(s2); free(bins);
+		if (noise_s2_out) *noise_s2_out = nullptr;
+		if (spectral_info) { *spectral_sums_out = nullptr; *spectral_counts_out = nullptr; }
+		g_error = e.what(); return SSX_ERR_DATA;
+	}
+}
+
+int ssh_checkpoint_load(const char* path, ssx_sums_info_t* info, char* scene_name, size_t scene_name_size, char* options_text, size_t options_text_size,
+                        double** sums_out, double** noise_s2_out) {
+	return ssh_checkpoint_load_spectral(path, info, scene_name, scene_name_size, options_text, options_text_size, sums_out, noise_s2_out, nullptr, nullptr, nullptr);
 }
 
 int ssh_sums_merge(double* dst, double* dst_s2, const double* src, const double* src_s2, const ssx_sums_info_t* src_info) {
 	if (!dst || !src || !src_info || src_info->struct_size != sizeof *src_info) { g_error = "NULL argument or ssx_sums_info_t.struct_size mismatch"; return SSX_ERR_ARG; }
 	ssx::sums_merge(dst, dst_s2, src, src_s2, *src_info);
+	return SSX_OK;
+}
+
+int ssh_spectral_merge(double* dst_sums, uint32_t* dst_counts, const double* src_sums, const uint32_t* src_counts, uint32_t bins, const ssx_sums_info_t* src_sums_info) {
+	if (!src_sums_info || src_sums_info->struct_size != sizeof *src_sums_info) { g_error = "NULL argument or ssx_sums_info_t.struct_size mismatch"; return SSX_ERR_ARG; }
+	if (bins < 4u || bins > 64u || bins % 4u) { g_error = "ssh_spectral_merge: bins must be a multiple of 4 in 4..64"; return SSX_ERR_ARG; }
+	if ((!dst_sums) != (!src_sums) || (!dst_counts) != (!src_counts)) { g_error = "ssh_spectral_merge: sums and counts come in pairs of dst and src"; return SSX_ERR_ARG; }
+	ssx::spectral_merge(dst_sums, dst_counts, src_sums, src_counts, bins, *src_sums_info);
 	return SSX_OK;
 }
 

@@ -4,11 +4,14 @@
 // --help; `name=value` or bare flags; unknown arguments produce a warning).  Additive options,
 // long names only so that none collides: --gpus=N --seed=S --observer=1931|2006 --texture=PATH
 // --light-scale=X --data-dir=DIR --uplift=ours|meng|jh --jh-coeff=FILE --meng-grid=FILE --no-explicit-light-sampling --no-flat-field-correction --tile-major --reduce=peer|rccl --rgb.
-// Progressive rendering (not with --tile-major): --checkpoint=PATH writes the pixel sums at the end of the render and on abort; --resume=PATH
+// Progressive rendering (not with --tile-major): --checkpoint=PATH writes the pixel sums at the end of the render and on abort -- and, with --spectral-output,
+// --develop-output or --spectral-denoise, the wavelength bins behind them; --resume=PATH
 // takes them up again, -spp then being the TOTAL wanted (at or below the checkpoint's count: the image is written as it is);
 // --noise-target=X --max-samples=N [--noise-step=S] renders in steps of S samples until the noise estimate falls to X or N samples are done.
 // Spectral output: --spectral-output=PATH.npy [--spectral-bins=N, default 16] also writes the per-pixel wavelength bins (include/ssx.h), a NumPy file of
-// shape (height, width, N), row 0 = bottom, after the image.  Not with --resume (a checkpoint carries no bins), --tile-major, --rgb or --libm=glibc-2.35.
+// shape (height, width, N), row 0 = bottom, after the image.  Not with --tile-major, --rgb or --libm=glibc-2.35.  With --resume the checkpoint must hold the bins
+// (it was written with one of the spectral options): N then defaults to the checkpoint's count, and another N, a checkpoint without bins or an unreadable one is
+// refused before anything renders.
 // Denoising: --denoise [--denoise-levels=N, 1..6, default 5] [--denoise-sigma=L,A, default 1,0.1] writes the image filtered by the variance-guided a-trous filter
 // of include/ssx.h to --output instead of the plain one.  It switches the noise estimate on and renders in launches of --noise-step samples (ceil(spp / 8) when
 // that is not given), so that the estimate has its two batches; not with -spp=1 or --tile-major.  --guides-output=PATH.npy writes the first-hit guide buffers,
@@ -20,12 +23,14 @@
 // device -- through the same XYZ -> sRGB store and writers as --output -- under --develop-observer=1931|2006 (default: the render's), through --develop-filter=FILE.csv
 // (a spectrum in the format of data/*.csv, its range in the name: NAME-LOW+STEP+HIGH.csv) and relit by --develop-relight=NEW.csv (the emitters' spectrum replaced by
 // NEW; refused unless all emissive materials share one spectrum up to a scale).  With --spectral-denoise the filtered bins are developed.  It does not need
-// --spectral-output, and has its refusals (--resume, --tile-major, --rgb, --libm=glibc-2.35).
+// --spectral-output, and has its refusals (--tile-major, --rgb, --libm=glibc-2.35; --resume of a checkpoint without the bins).  With --resume, --spectral-bins may
+// be left out: the checkpoint's count.
 // Demodulated denoising (include/ssx.h "Demodulated denoising"): --demodulate[=K] with --spectral-denoise runs that filter on illumination -- bins, image and
 // variance divided by the first-hit albedo per bin (K x K rays per pixel, K = 1, 2 or 4; default 2) before it and multiplied by it afterwards; the albedo part of
 // --denoise-sigma is ignored then.  --albedo-output=PATH.npy (needs --spectral-bins=N) writes those albedo bins, [height][width][N] float32.
 #include "renderer.hpp"
 
+#include "checkpoint.hpp"
 #include "develop.hpp"
 
 #include <chrono>
@@ -59,7 +64,8 @@ void print_usage() {
 		"    `--gpus=<n>` `--seed=<n>` `--observer=1931|2006` `--uplift=ours|meng|jh` `--jh-coeff=<file>` `--meng-grid=<file>` `--rgb` `--no-explicit-light-sampling` `--no-flat-field-correction` `--tile-major` `--reduce=peer|rccl` `--libm=build|glibc-2.35`\n"
 		"    `--texture=<png>` `--light-scale=<x>` `--data-dir=<dir>`\n"
 		"    `--checkpoint=<file>` `--resume=<file>` (`-spp` is then the total) `--noise-target=<x> --max-samples=<n> [--noise-step=<s>]`\n"
-		"    `--spectral-output=<file.npy>` [`--spectral-bins=<n>`: 4, 8, ..., 64; default 16] (not with `--resume`)\n"
+		"    `--spectral-output=<file.npy>` [`--spectral-bins=<n>`: 4, 8, ..., 64; default 16, with `--resume` the checkpoint's]\n"
+		"          (`--checkpoint` then also keeps the wavelength bins, and `--resume` needs a checkpoint that holds <n> of them)\n"
 		"    `--denoise` [`--denoise-levels=<n>`: 1..6; default 5] [`--denoise-sigma=<l>,<a>`; default 1,0.1] (the output image is the filtered one; not with `-spp=1`)\n"
 		"    `--guides-output=<file.npy>` (first hit per pixel: primitive, depth, normal, albedo)\n"
 		"    `--spectral-denoise` (with `--spectral-output`: the file holds the bins filtered with `--denoise`'s weights, levels and sigmas; not with `-spp=1`)\n"
@@ -191,9 +197,24 @@ void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progress
 		try { g->spectral_bins = to_pos(v); } catch (int) { g->spectral_bins = 0; }
 		if (g->spectral_bins == 0 || g->spectral_bins > 64 || g->spectral_bins % 4) { std::fprintf(stderr, "Invalid value for --spectral-bins (a multiple of 4 up to 64)!\n"); throw -2; }
 	}
-	if (!g->spectral_output.empty() && !g->resume.empty()) {
-		std::fprintf(stderr, "`--spectral-output` cannot be combined with `--resume`: a checkpoint holds the pixel sums only, not the wavelength bins of the samples behind them!\n");
-		throw -2;
+	if (!g->resume.empty() && (!g->spectral_output.empty() || !g->develop_output.empty())) {
+		// the bins of the samples already rendered must come from the checkpoint: it has to hold them, as many as are asked for (default: as many as it holds)
+		const char* const flag = !g->spectral_output.empty() ? "--spectral-output" : "--develop-output";
+		uint32_t held = 0;
+		try { held = ssx::checkpoint_load(g->resume).spectral.bins; }
+		catch (const ssx::HostError& e) {
+			std::fprintf(stderr, "`%s` cannot be combined with `--resume` of a checkpoint that cannot be read: %s\n", flag, e.message.c_str());
+			throw -2;
+		}
+		if (!held) {
+			std::fprintf(stderr, "`%s` cannot be combined with `--resume` of a checkpoint without wavelength bins: \"%s\" holds the pixel sums only (write it with `--checkpoint` and a spectral option)!\n", flag, g->resume.c_str());
+			throw -2;
+		}
+		if (g->spectral_bins_given && g->spectral_bins != held) {
+			std::fprintf(stderr, "`%s` cannot be combined with `--resume` of a checkpoint with another bin count: \"%s\" holds %u wavelength bins, `--spectral-bins=%zu` was asked for!\n", flag, g->resume.c_str(), held, g->spectral_bins);
+			throw -2;
+		}
+		g->spectral_bins = held; g->spectral_bins_given = true;
 	}
 	if (!g->spectral_output.empty() && (o->tile_major || o->rgb_mode || o->libm != SSX_LIBM_BUILD)) {
 		std::fprintf(stderr, "`--spectral-output` cannot be combined with `--tile-major`, `--rgb` or `--libm=glibc-2.35`!\n");
@@ -207,8 +228,8 @@ void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progress
 		std::fprintf(stderr, "`--develop-output` needs `--spectral-bins=<n>`: it develops the wavelength bins of the render!\n");
 		throw -2;
 	}
-	if (!g->develop_output.empty() && (!g->resume.empty() || o->tile_major || o->rgb_mode || o->libm != SSX_LIBM_BUILD)) {
-		std::fprintf(stderr, "`--develop-output` cannot be combined with `--resume`, `--tile-major`, `--rgb` or `--libm=glibc-2.35`: such a render has no wavelength bins!\n");
+	if (!g->develop_output.empty() && (o->tile_major || o->rgb_mode || o->libm != SSX_LIBM_BUILD)) {
+		std::fprintf(stderr, "`--develop-output` cannot be combined with `--tile-major`, `--rgb` or `--libm=glibc-2.35`: such a render has no wavelength bins!\n");
 		throw -2;
 	}
 	if (a.take("--denoise", "", &v)) {
@@ -323,7 +344,11 @@ int main(int argc, char* argv[]) {
 			std::fprintf(stderr, "Noise %.6g after %zu samples per pixel (target %.6g).\n", r.second, r.first, prog.noise_target);
 		} else {
 			if (!prog.resume.empty()) {
-				try { renderer.load_checkpoint(prog.resume); }
+				try {
+					const bool bins = renderer.load_checkpoint(prog.resume);
+					if (!bins && (!prog.spectral_output.empty() || !prog.develop_output.empty())) // (checked when the arguments were read; the file has changed since)
+						throw ssx::HostError{ SSX_ERR_DATA, "it holds no wavelength bins of the count asked for" };
+				}
 				catch (const ssx::HostError& e) { // not this render's checkpoint (or no checkpoint at all): bad data, as the reference exits on it
 					std::fprintf(stderr, "Cannot resume from \"%s\": %s\n", prog.resume.c_str(), e.message.c_str());
 					return -1;

@@ -51,6 +51,7 @@ struct Renderer::Api {
 	int (*noise_info)(ssx_ctx*, double*, double*) = nullptr;
 	int (*set_spectral_bins)(ssx_ctx*, uint32_t) = nullptr;
 	int (*spectral_read)(ssx_ctx*, ssx_spectral_info_t*, float*, double*, uint32_t*) = nullptr;
+	int (*spectral_import)(ssx_ctx*, const ssx_spectral_info_t*, const double*, const uint32_t*) = nullptr;
 	int (*guides)(ssx_ctx*, uint32_t, uint32_t, uint32_t*, float*, float*, float*) = nullptr;
 	int (*denoise_images)(ssx_ctx*, const ssx_denoise_params*, uint32_t, uint32_t, const float*, const float*, const uint32_t*, const float*, float*, float*) = nullptr;
 	int (*denoise)(ssx_ctx*, const ssx_denoise_params*, float*, float*) = nullptr;
@@ -96,6 +97,7 @@ struct Renderer::Api {
 		noise_info = reinterpret_cast<decltype(noise_info)>(sym("ssx_noise_info"));
 		set_spectral_bins = reinterpret_cast<decltype(set_spectral_bins)>(sym("ssx_set_spectral_bins"));
 		spectral_read = reinterpret_cast<decltype(spectral_read)>(sym("ssx_spectral_read"));
+		spectral_import = reinterpret_cast<decltype(spectral_import)>(sym("ssx_spectral_import"));
 		guides = reinterpret_cast<decltype(guides)>(sym("ssx_guides"));
 		denoise_images = reinterpret_cast<decltype(denoise_images)>(sym("ssx_denoise_images"));
 		denoise = reinterpret_cast<decltype(denoise)>(sym("ssx_denoise"));
@@ -196,6 +198,15 @@ ssx_render_params Renderer::params_for_(size_t d, size_t spp, size_t spp_per_lau
 	p.seed = options.seed;
 	p.libm = options.libm;
 	return p;
+}
+
+// whose pixels device d's arrays hold: the description sums_owner / merge_owned (host/checkpoint.hpp) decide by
+ssx_sums_info_t Renderer::owner_(size_t d) const {
+	const ssx_render_params p = params_for_(d, 1, 0); // (what the devices rendered with)
+	ssx_sums_info_t o{};
+	o.struct_size = sizeof o; o.width = p.width; o.height = p.height;
+	o.tile_first = p.tile_first; o.tile_stride = p.tile_stride; o.tile_skew = p.tile_skew;
+	return o;
 }
 
 void Renderer::check_(int rc, const char* what, ssx_ctx* c) const {
@@ -299,20 +310,15 @@ void Renderer::spectral_image(std::vector<float>* mean, std::vector<uint32_t>* c
 	if (counts) counts->assign(W * H * M, 0u);
 	std::vector<float> part(mean ? W * H * B : 0);
 	std::vector<uint32_t> part_n(counts ? W * H * M : 0);
-	const size_t skew = params_for_(0, 1, 0).tile_skew; // (what the devices rendered with)
-	for (size_t d = 0; d < n; ++d) { // every pixel from the device that owns it, bit for bit (a merge by ownership mask, like sums_merge)
+	for (size_t d = 0; d < n; ++d) { // every pixel from the device that owns it, bit for bit (merge_owned: the one merge by ownership mask)
 		ssx_spectral_info_t info{};
 		check_(api_->spectral_read(ctxs_[d], &info, mean ? part.data() : nullptr, nullptr, counts ? part_n.data() : nullptr), "ssx_spectral_read", ctxs_[d]);
 		if (d == 0 && centres) {
 			centres->resize(B);
 			for (size_t b = 0; b < B; ++b) (*centres)[b] = info.lambda_min + (static_cast<float>(b) + 0.5f) * info.bin_width;
 		}
-		for (size_t j = 0; j < H; ++j) for (size_t i = 0; i < W; ++i) {
-			if (shared_tile(W, skew, i, j) % n != d) continue;
-			const size_t p = j * W + i;
-			if (mean) std::memcpy(&(*mean)[p * B], &part[p * B], B * sizeof(float));
-			if (counts) std::memcpy(&(*counts)[p * M], &part_n[p * M], M * sizeof(uint32_t));
-		}
+		if (mean) merge_owned(mean->data(), part.data(), B, owner_(d));
+		if (counts) merge_owned(counts->data(), part_n.data(), M, owner_(d));
 	}
 }
 
@@ -433,13 +439,13 @@ Framebuffer Renderer::denoise_spectral(const DenoiseParams& params, std::vector<
 		std::vector<double> part_s(pixels * B);
 		std::vector<uint32_t> part_n(pixels * M);
 		std::vector<float> e0(pixels * E), eL(pixels * E);
-		const size_t skew = params_for_(0, 1, 0).tile_skew;
 		for (size_t d = 0; d < n_dev; ++d) {
 			ssx_spectral_info_t info{};
 			check_(api_->spectral_read(ctxs_[d], &info, nullptr, part_s.data(), part_n.data()), "ssx_spectral_read", ctxs_[d]);
 			const double n = static_cast<double>(info.done_spp);
+			const ssx_sums_info_t owner = owner_(d);
 			for (size_t j = 0; j < H; ++j) for (size_t i = 0; i < W; ++i) {
-				if (shared_tile(W, skew, i, j) % n_dev != d) continue;
+				if (!sums_owner(owner, i, j)) continue;
 				const size_t p = j * W + i;
 				for (size_t b = 0; b < B; ++b) e0[p * E + b] = static_cast<float>(part_s[p * B + b] / n);                      // binary64 division, then rounded
 				for (size_t m = 0; m < M; ++m) e0[p * E + B + m] = static_cast<float>(static_cast<double>(part_n[p * M + m]) / n);
@@ -512,14 +518,9 @@ std::vector<float> Renderer::develop(const float* weights, size_t channels, cons
 	} else {
 		level_devices(); // (a stopped render: one sample count behind every pixel)
 		std::vector<float> part(out.size());
-		const size_t skew = params_for_(0, 1, 0).tile_skew;
-		for (size_t d = 0; d < n_dev; ++d) { // every pixel from the device that owns it, bit for bit (a merge by ownership mask, like sums_merge)
+		for (size_t d = 0; d < n_dev; ++d) { // every pixel from the device that owns it, bit for bit (merge_owned: the one merge by ownership mask)
 			check_(api_->spectral_develop(ctxs_[d], nullptr, weights, c32, part.data()), "ssx_spectral_develop", ctxs_[d]);
-			for (size_t j = 0; j < H; ++j) for (size_t i = 0; i < W; ++i) {
-				if (shared_tile(W, skew, i, j) % n_dev != d) continue;
-				const size_t p = j * W + i;
-				std::memcpy(&out[p * C], &part[p * C], C * sizeof(float));
-			}
+			merge_owned(out.data(), part.data(), C, owner_(d));
 		}
 	}
 	return out;
@@ -560,6 +561,25 @@ void Renderer::save_checkpoint(const std::string& path) {
 	}
 	ck.info.tile_first = 0; ck.info.tile_stride = 1; ck.info.tile_skew = 0; // the merged array is the whole image
 	if (!have_s2) { ck.s2.clear(); ck.info.noise_batches = 0; }
+	// the wavelength bins, when every device holds valid ones (a render with spectral output, or a resume that took them up): merged by ownership like the sums
+	bool have_bins = spectral_bins_ != 0;
+	for (size_t d = 0; have_bins && d < ctxs_.size(); ++d) {
+		ssx_spectral_info_t si{};
+		have_bins = api_->spectral_read(ctxs_[d], &si, nullptr, nullptr, nullptr) == SSX_OK; // (SSX_ERR_STATE: continuable sums without bins)
+	}
+	if (have_bins) {
+		const size_t B = spectral_bins_, M = B / 4;
+		ck.spectral_sums.assign(pixels * B, 0.0);
+		ck.spectral_counts.assign(pixels * M, 0u);
+		std::vector<double> part_s(pixels * B);
+		std::vector<uint32_t> part_n(pixels * M);
+		for (size_t d = 0; d < ctxs_.size(); ++d) {
+			ssx_spectral_info_t si{};
+			check_(api_->spectral_read(ctxs_[d], &si, nullptr, part_s.data(), part_n.data()), "ssx_spectral_read", ctxs_[d]);
+			if (d == 0) ck.spectral = si;
+			spectral_merge(ck.spectral_sums.data(), ck.spectral_counts.data(), part_s.data(), part_n.data(), B, owner_(d));
+		}
+	}
 	ck.scene_name = options.scene_name;
 	ck.options_text = "observer=" + std::to_string(options.observer) + "\ntexture=" + options.texture_path + "\nlight_scale=" + std::to_string(options.light_scale) +
 	                  "\nuplift=" + std::to_string(options.uplift) + "\nrgb=" + (options.rgb_mode ? "1" : "0") +
@@ -567,16 +587,20 @@ void Renderer::save_checkpoint(const std::string& path) {
 	checkpoint_save(path, ck);
 }
 
-void Renderer::load_checkpoint(const std::string& path) {
+bool Renderer::load_checkpoint(const std::string& path) {
 	wait_workers_();
 	const Checkpoint ck = checkpoint_load(path);
+	const bool take_bins = ck.spectral.bins != 0u && spectral_bins_ == ck.spectral.bins;
 	for (size_t d = 0; d < ctxs_.size(); ++d) {
 		const ssx_render_params p = params_for_(d, ck.info.done_spp ? ck.info.done_spp : 1u, 0);
 		check_(api_->sums_import(ctxs_[d], &p, &ck.info, ck.sums.data(), ck.s2.empty() ? nullptr : ck.s2.data()), "ssx_sums_import", ctxs_[d]);
+		// every device takes its own tiles from the whole array, however many devices wrote it
+		if (take_bins) check_(api_->spectral_import(ctxs_[d], &ck.spectral, ck.spectral_sums.data(), ck.spectral_counts.data()), "ssx_spectral_import", ctxs_[d]);
 	}
 	time_start_ = std::chrono::steady_clock::now();
 	started_ = true; need_join_ = false;
 	expected_spp_ = ck.info.done_spp;
+	return take_bins;
 }
 
 void Renderer::render_stop() { for (ssx_ctx* c : ctxs_) api_->render_stop(c); }

@@ -83,11 +83,16 @@ public:
 	// few launches at most), so that image, checkpoint and whatever follows speak of ONE count.  render_continue and save_checkpoint do it
 	// themselves; call it BEFORE render_wait when the image written there is to be the checkpoint's.
 	void level_devices();
-	// One file with the sums of all devices, merged by ownership (host/checkpoint.hpp), after level_devices().  Not while rendering.
+	// One file with the sums of all devices, merged by ownership (host/checkpoint.hpp), after level_devices().  Not while rendering.  When every device holds
+	// valid wavelength bins (set_spectral_bins before the render, or a load_checkpoint that took them up) the file carries them too, merged the same way
+	// ("SSXCKPT2"); otherwise it is the file it always was.
 	void save_checkpoint(const std::string& path);
 	// Every device takes its own tiles from the file's array; render_wait() then yields the checkpointed image, render_continue goes on from it.
 	// Throws HostError with the library's reason when the file belongs to another scene, size, seed or set of flags.
-	void load_checkpoint(const std::string& path);
+	// A file with wavelength bins, read with set_spectral_bins(its count) in force: every device also takes the bins of its tiles (ssx_spectral_import; the
+	// number of devices may differ from the writer's), and spectral_image, denoise_spectral, develop and a later save_checkpoint go on as after a render of
+	// those samples.  Returns whether the bins were taken up; when not (no bins in the file, spectral output off, another bin count) the resume is the plain one.
+	bool load_checkpoint(const std::string& path);
 	void set_noise_estimate(bool on);        // ssx_set_noise_estimate on every device
 	// sqrt(sum v / n) / (sum A/N / n) over all devices (include/ssx.h ssx_noise_info); v_map: the per-pixel variances [height][width]
 	double noise(std::vector<double>* v_map = nullptr);
@@ -148,6 +153,7 @@ private:
 	std::vector<float> demod_weights_(const DemodParams& demod) const; // demod.weights_xyz, or the render's own observer's develop weights over the bins
 	size_t expected_spp_ = 0;   // the count the running (or last) call renders to: what render_wait compares ssx_done_spp with
 	ssx_render_params params_for_(size_t d, size_t spp, size_t spp_per_launch) const;
+	ssx_sums_info_t owner_(size_t d) const; // device d's ownership (tile_first / tile_stride / tile_skew), as the merges by ownership take it
 	void start_(size_t spp, size_t spp_per_launch);
 	void wait_workers_();
 	void continue_each_(const std::vector<std::pair<ssx_ctx*, uint32_t>>& more);

@@ -265,6 +265,41 @@ def load_checkpoint_file(path):
     return info, sums, s2, name.value.decode(), text.value.decode()
 
 
+def load_checkpoint_file_spectral(path):
+    """ssh_checkpoint_load_spectral -> load_checkpoint_file's five values and (SsxSpectralInfo, sums float64 [H, W, B], counts uint32 [H, W, B / 4]) of the
+    wavelength bins; from a checkpoint without them (magic SSXCKPT1) the info's bins is 0 and both arrays are None."""
+    host = _capi.host_lib()
+    info, sinfo = _capi.SsxSumsInfo(), _capi.SsxSpectralInfo()
+    name, text = C.create_string_buffer(256), C.create_string_buffer(4096)
+    ps, p2, pb, pn = C.POINTER(C.c_double)(), C.POINTER(C.c_double)(), C.POINTER(C.c_double)(), C.POINTER(C.c_uint32)()
+    rc = host.ssh_checkpoint_load_spectral(os.fsencode(path), C.byref(info), name, len(name), text, len(text), C.byref(ps), C.byref(p2),
+                                           C.byref(sinfo), C.byref(pb), C.byref(pn))
+    if rc != 0:
+        raise SsxError(rc, host.ssh_last_error().decode())
+    try:
+        H, W, B = info.height, info.width, sinfo.bins
+        sums = np.ctypeslib.as_array(ps, shape=(H, W, 4)).copy()
+        s2 = np.ctypeslib.as_array(p2, shape=(H, W)).copy() if p2 else None
+        bins = np.ctypeslib.as_array(pb, shape=(H, W, B)).copy() if pb else None
+        counts = np.ctypeslib.as_array(pn, shape=(H, W, B // 4)).copy() if pn else None
+    finally:
+        for p in (ps, p2, pb, pn):
+            if p:
+                host.ssh_free(p)
+    return info, sums, s2, name.value.decode(), text.value.decode(), sinfo, bins, counts
+
+
+def merge_spectral(dst_sums, dst_counts, src_sums, src_counts, src_info):
+    """ssh_spectral_merge: merge_sums' rule for the wavelength bins -- sums float64 [H, W, B] and counts uint32 [H, W, B / 4] of the pixels src_info's exporter
+    owns (an SsxSumsInfo: export_sums' of the same context), bit for bit."""
+    assert dst_sums.dtype == np.float64 and dst_sums.flags.c_contiguous and src_sums.dtype == np.float64 and src_sums.flags.c_contiguous
+    assert dst_counts.dtype == np.uint32 and dst_counts.flags.c_contiguous and src_counts.dtype == np.uint32 and src_counts.flags.c_contiguous
+    assert dst_sums.shape == src_sums.shape and dst_counts.shape == src_counts.shape and src_sums.shape[2] == 4 * src_counts.shape[2]
+    rc = _capi.host_lib().ssh_spectral_merge(dst_sums.ctypes.data, dst_counts.ctypes.data, src_sums.ctypes.data, src_counts.ctypes.data, src_sums.shape[2], C.byref(src_info))
+    if rc != 0:
+        raise SsxError(rc, _capi.host_lib().ssh_last_error().decode())
+
+
 def merge_sums(dst, dst_s2, src, src_s2, src_info):
     """ssh_sums_merge: dst's pixels that src_info's exporter owns <- src's, bit for bit (by ownership mask, not by adding)."""
     assert dst.dtype == np.float64 and dst.flags.c_contiguous and src.dtype == np.float64 and src.flags.c_contiguous
@@ -385,22 +420,52 @@ class Renderer:
         self._check(self._lib.ssx_sums_import(self._ctx, C.byref(p), C.byref(info), sums.ctypes.data, None if s2 is None else s2.ctypes.data))
         self.read_framebuffer()
 
+    def holds_spectral(self):
+        """Whether the context holds valid wavelength bins of exactly the samples behind its sums (what export_spectral and save_checkpoint need)."""
+        if not getattr(self, "_spectral_bins", 0):
+            return False
+        return self._lib.ssx_spectral_read(self._ctx, C.byref(_capi.SsxSpectralInfo()), None, None, None) == 0
+
+    def export_spectral(self):
+        """ssx_spectral_read's raw state -> (SsxSpectralInfo, sums float64 [H, W, B], counts uint32 [H, W, B / 4]): what import_spectral takes back and a
+        checkpoint keeps; zeros for pixels the context does not own (merge_spectral combines the ranks')."""
+        info, _, counts, sums = self.spectral_read(sums=True)
+        return info, sums, counts
+
+    def import_spectral(self, info, sums, counts):
+        """ssx_spectral_import, directly on top of import_sums: the context takes the bins of the tiles it owns from the whole-image arrays and then stands where a
+        render of info.done_spp samples with spectral output would have left it -- render_continue carries the bins on; spectral_read, denoise_spectral and
+        develop work from them.  SsxError with the library's reason when they do not belong to the imported sums."""
+        sums = np.ascontiguousarray(sums, dtype=np.float64)
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        if sums.size != info.width * info.height * info.bins or counts.size * 4 != sums.size:
+            raise ValueError("import_spectral: sums must have shape [info.height, info.width, info.bins], counts [info.height, info.width, info.bins / 4]")
+        self._check(self._lib.ssx_spectral_import(self._ctx, C.byref(info), sums.ctypes.data, counts.ctypes.data))
+
     def save_checkpoint(self, path):
-        """The sums (and the noise estimate's S2) into one file (libssx_host.so ssh_checkpoint_save; host/checkpoint.hpp has the format)."""
+        """The sums (and the noise estimate's S2) into one file (libssx_host.so ssh_checkpoint_save_spectral; host/checkpoint.hpp has the format); with them
+        the wavelength bins when the context holds valid ones -- otherwise the file is the one it always was."""
         info, sums, s2 = self.export_sums()
+        sinfo, bins, counts = self.export_spectral() if self.holds_spectral() else (None, None, None)
         o = self.options
         text = "observer=%d\ntexture=%s\nlight_scale=%r\nuplift=%s\nrender_mode=%s\nexplicit_light_sampling=%d\n" % (
             o.observer, o.texture if isinstance(o.texture, str) else "", o.light_scale, o.uplift, o.render_mode, int(o.explicit_light_sampling))
         host = _capi.host_lib()
-        rc = host.ssh_checkpoint_save(os.fsencode(path), C.byref(info), o.scene_name.encode(), text.encode(), sums.ctypes.data, None if s2 is None else s2.ctypes.data)
+        rc = host.ssh_checkpoint_save_spectral(os.fsencode(path), C.byref(info), o.scene_name.encode(), text.encode(), sums.ctypes.data, None if s2 is None else s2.ctypes.data,
+                                               None if sinfo is None else C.byref(sinfo), None if bins is None else bins.ctypes.data,
+                                               None if counts is None else counts.ctypes.data)
         if rc != 0:
             raise SsxError(rc, host.ssh_last_error().decode())
 
     def load_checkpoint(self, path):
         """Reads a checkpoint and imports it (SsxError SSX_ERR_DATA for a damaged file, SSX_ERR_ARG with the library's reason for one
-        of another scene, size, seed or set of flags).  Returns its SsxSumsInfo."""
-        info, sums, s2, _, _ = load_checkpoint_file(path)
+        of another scene, size, seed or set of flags).  Returns its SsxSumsInfo.  A file with wavelength bins, read while set_spectral_bins(its count) is in
+        force: the bins are taken up too (import_spectral); self.spectral_resumed says whether."""
+        info, sums, s2, _, _, sinfo, bins, counts = load_checkpoint_file_spectral(path)
         self.import_sums(info, sums, s2)
+        self.spectral_resumed = bool(sinfo.bins) and sinfo.bins == getattr(self, "_spectral_bins", 0)
+        if self.spectral_resumed:
+            self.import_spectral(sinfo, bins, counts)
         return info
 
     def noise(self):
