@@ -26,42 +26,21 @@ void Framebuffer::save(const std::string& path) const { save_image(path, pixels_
 
 // The C ABI, resolved from libssx_hip.so at run time so that libssx_host.so itself has no HIP
 // dependency (it must load on machines without a GPU for table/scene/image work).
+// Every entry point the host calls, named once: X(name) stands for ssx_<name> of include/ssx.h.  The member's type is the header's own declaration
+// (decltype of a declared function does not use it: no link dependency), so a prototype that changes there is a compile error at the call here.
+#define SSX_HOST_API(X) \
+	X(create) X(destroy) X(upload_scene) X(render_start) X(render_stop) X(is_rendering) X(progress) X(render_wait) X(last_error) \
+	X(device_framebuffer) X(device_index) X(read_framebuffer) X(accumulate_peer) X(done_spp) X(done_tiles) X(reduce_rccl) \
+	X(render_continue) X(sums_export) X(sums_import) X(set_noise_estimate) X(noise_info) \
+	X(set_spectral_bins) X(spectral_read) X(spectral_import) \
+	X(guides) X(denoise_images) X(denoise) X(denoise_channels) X(denoise_spectral) \
+	X(develop_images) X(spectral_develop) X(albedo_bins) X(denoise_spectral_demod) X(spectral_develop_demod)
+
 struct Renderer::Api {
 	void* handle = nullptr;
-	int (*create)(int, ssx_ctx**) = nullptr;
-	void (*destroy)(ssx_ctx*) = nullptr;
-	int (*upload_scene)(ssx_ctx*, const ssx_scene_desc*) = nullptr;
-	int (*render_start)(ssx_ctx*, const ssx_render_params*) = nullptr;
-	int (*render_stop)(ssx_ctx*) = nullptr;
-	int (*is_rendering)(ssx_ctx*) = nullptr;
-	float (*progress)(ssx_ctx*) = nullptr;
-	int (*render_wait)(ssx_ctx*, float*) = nullptr;
-	const char* (*last_error)(const ssx_ctx*) = nullptr;
-	void* (*device_framebuffer)(ssx_ctx*) = nullptr;
-	int (*device_index)(ssx_ctx*) = nullptr;
-	int (*read_framebuffer)(ssx_ctx*, float*) = nullptr;
-	int (*accumulate_peer)(ssx_ctx*, void*, int, const void*, uint32_t, uint32_t, void*) = nullptr;
-	uint32_t (*done_spp)(ssx_ctx*) = nullptr;
-	uint32_t (*done_tiles)(ssx_ctx*) = nullptr;
-	int (*reduce_rccl)(ssx_ctx**, int, uint32_t, uint32_t) = nullptr;
-	int (*render_continue)(ssx_ctx*, uint32_t) = nullptr;
-	int (*sums_export)(ssx_ctx*, ssx_sums_info_t*, double*, double*) = nullptr;
-	int (*sums_import)(ssx_ctx*, const ssx_render_params*, const ssx_sums_info_t*, const double*, const double*) = nullptr;
-	int (*set_noise_estimate)(ssx_ctx*, int) = nullptr;
-	int (*noise_info)(ssx_ctx*, double*, double*) = nullptr;
-	int (*set_spectral_bins)(ssx_ctx*, uint32_t) = nullptr;
-	int (*spectral_read)(ssx_ctx*, ssx_spectral_info_t*, float*, double*, uint32_t*) = nullptr;
-	int (*spectral_import)(ssx_ctx*, const ssx_spectral_info_t*, const double*, const uint32_t*) = nullptr;
-	int (*guides)(ssx_ctx*, uint32_t, uint32_t, uint32_t*, float*, float*, float*) = nullptr;
-	int (*denoise_images)(ssx_ctx*, const ssx_denoise_params*, uint32_t, uint32_t, const float*, const float*, const uint32_t*, const float*, float*, float*) = nullptr;
-	int (*denoise)(ssx_ctx*, const ssx_denoise_params*, float*, float*) = nullptr;
-	int (*denoise_channels)(ssx_ctx*, const ssx_denoise_params*, uint32_t, uint32_t, const float*, const float*, const uint32_t*, const float*, uint32_t, const float*, float*, float*, float*) = nullptr;
-	int (*denoise_spectral)(ssx_ctx*, const ssx_denoise_params*, float*, float*, float*) = nullptr;
-	int (*develop_images)(ssx_ctx*, uint32_t, uint32_t, uint32_t, const float*, const float*, uint32_t, float*) = nullptr;
-	int (*spectral_develop)(ssx_ctx*, const ssx_denoise_params*, const float*, uint32_t, float*) = nullptr;
-	int (*albedo_bins)(ssx_ctx*, uint32_t, uint32_t, uint32_t, uint32_t, float*) = nullptr;
-	int (*denoise_spectral_demod)(ssx_ctx*, const ssx_denoise_params*, const ssx_demod_params*, const float*, float*, float*, float*) = nullptr;
-	int (*spectral_develop_demod)(ssx_ctx*, const ssx_denoise_params*, const ssx_demod_params*, const float*, const float*, uint32_t, float*) = nullptr;
+#define X(name) decltype(&::ssx_##name) name = nullptr;
+	SSX_HOST_API(X)
+#undef X
 
 	explicit Api(const std::string& path) {
 		handle = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
@@ -72,42 +51,11 @@ struct Renderer::Api {
 			return p;
 		};
 		// one interface version on both sides of the boundary (include/ssx.h: what changed between versions)
-		const int abi = reinterpret_cast<int (*)(void)>(sym("ssx_abi_version"))();
+		const int abi = reinterpret_cast<decltype(&::ssx_abi_version)>(sym("ssx_abi_version"))();
 		if (abi != SSX_ABI_VERSION) throw HostError{ SSX_ERR_DEVICE, "libssx_hip.so implements ABI version " + std::to_string(abi) + ", this host was built against version " + std::to_string(SSX_ABI_VERSION) + " (include/ssx.h)" };
-		create = reinterpret_cast<decltype(create)>(sym("ssx_create"));
-		destroy = reinterpret_cast<decltype(destroy)>(sym("ssx_destroy"));
-		upload_scene = reinterpret_cast<decltype(upload_scene)>(sym("ssx_upload_scene"));
-		render_start = reinterpret_cast<decltype(render_start)>(sym("ssx_render_start"));
-		render_stop = reinterpret_cast<decltype(render_stop)>(sym("ssx_render_stop"));
-		is_rendering = reinterpret_cast<decltype(is_rendering)>(sym("ssx_is_rendering"));
-		progress = reinterpret_cast<decltype(progress)>(sym("ssx_progress"));
-		render_wait = reinterpret_cast<decltype(render_wait)>(sym("ssx_render_wait"));
-		last_error = reinterpret_cast<decltype(last_error)>(sym("ssx_last_error"));
-		device_framebuffer = reinterpret_cast<decltype(device_framebuffer)>(sym("ssx_device_framebuffer"));
-		device_index = reinterpret_cast<decltype(device_index)>(sym("ssx_device_index"));
-		read_framebuffer = reinterpret_cast<decltype(read_framebuffer)>(sym("ssx_read_framebuffer"));
-		accumulate_peer = reinterpret_cast<decltype(accumulate_peer)>(sym("ssx_accumulate_peer"));
-		done_spp = reinterpret_cast<decltype(done_spp)>(sym("ssx_done_spp"));
-		done_tiles = reinterpret_cast<decltype(done_tiles)>(sym("ssx_done_tiles"));
-		reduce_rccl = reinterpret_cast<decltype(reduce_rccl)>(sym("ssx_reduce_rccl"));
-		render_continue = reinterpret_cast<decltype(render_continue)>(sym("ssx_render_continue"));
-		sums_export = reinterpret_cast<decltype(sums_export)>(sym("ssx_sums_export"));
-		sums_import = reinterpret_cast<decltype(sums_import)>(sym("ssx_sums_import"));
-		set_noise_estimate = reinterpret_cast<decltype(set_noise_estimate)>(sym("ssx_set_noise_estimate"));
-		noise_info = reinterpret_cast<decltype(noise_info)>(sym("ssx_noise_info"));
-		set_spectral_bins = reinterpret_cast<decltype(set_spectral_bins)>(sym("ssx_set_spectral_bins"));
-		spectral_read = reinterpret_cast<decltype(spectral_read)>(sym("ssx_spectral_read"));
-		spectral_import = reinterpret_cast<decltype(spectral_import)>(sym("ssx_spectral_import"));
-		guides = reinterpret_cast<decltype(guides)>(sym("ssx_guides"));
-		denoise_images = reinterpret_cast<decltype(denoise_images)>(sym("ssx_denoise_images"));
-		denoise = reinterpret_cast<decltype(denoise)>(sym("ssx_denoise"));
-		denoise_channels = reinterpret_cast<decltype(denoise_channels)>(sym("ssx_denoise_channels"));
-		denoise_spectral = reinterpret_cast<decltype(denoise_spectral)>(sym("ssx_denoise_spectral"));
-		develop_images = reinterpret_cast<decltype(develop_images)>(sym("ssx_develop_images"));
-		spectral_develop = reinterpret_cast<decltype(spectral_develop)>(sym("ssx_spectral_develop"));
-		albedo_bins = reinterpret_cast<decltype(albedo_bins)>(sym("ssx_albedo_bins"));
-		denoise_spectral_demod = reinterpret_cast<decltype(denoise_spectral_demod)>(sym("ssx_denoise_spectral_demod"));
-		spectral_develop_demod = reinterpret_cast<decltype(spectral_develop_demod)>(sym("ssx_spectral_develop_demod"));
+#define X(name) name = reinterpret_cast<decltype(name)>(sym("ssx_" #name));
+		SSX_HOST_API(X)
+#undef X
 	}
 	~Api() { if (handle) dlclose(handle); }
 };
@@ -123,10 +71,9 @@ std::string default_hip_library() {
 	return "libssx_hip.so";
 }
 bool file_exists(const std::string& p) { return std::ifstream(p).good(); }
-} // namespace
 
-Renderer::Renderer(const Options& opts) : options(opts), framebuffer(opts.res), xyza(4 * opts.res[0] * opts.res[1], 0.0f) {
-	// Scene selection and its warnings (src/renderer.cpp:17-38, EXPLICIT_LIGHT_SAMPLING build)
+// Scene selection and its warnings (src/renderer.cpp:17-38, EXPLICIT_LIGHT_SAMPLING build)
+void check_scene_name(const Renderer::Options& options) {
 	if (options.scene_name == "plane-srgb") {
 		if (options.explicit_light_sampling) std::fprintf(stderr, "Warning: Plane converges much faster without explicit light sampling!  (See \"stdafx.hpp\" to disable.)\n");
 	} else if (options.scene_name == "cornell" || options.scene_name == "cornell-srgb") {
@@ -135,6 +82,85 @@ Renderer::Renderer(const Options& opts) : options(opts), framebuffer(opts.res), 
 		std::fprintf(stderr, "Unrecognized scene \"%s\"!  (Supported scenes: \"cornell\", \"cornell-srgb\", \"plane-srgb\")\n", options.scene_name.c_str());
 		throw HostError{ -3, "Unrecognized scene" };
 	}
+}
+
+// The parameter structs of the C ABI from the host's, each in this one place.  demodulated: the mode's filter runs with a zero albedo guide, which sigma_a
+// cannot weigh -- any valid value serves, and the library's own demodulated calls take 1 as well.
+ssx_denoise_params to_abi(const Renderer::DenoiseParams& p, bool demodulated = false) {
+	ssx_denoise_params dp{};
+	dp.struct_size = sizeof dp; dp.levels = p.levels; dp.sigma_l = p.sigma_l; dp.sigma_a = demodulated ? 1.0f : p.sigma_a;
+	return dp;
+}
+ssx_demod_params to_abi(const Renderer::DemodParams& p) {
+	ssx_demod_params dm{};
+	dm.struct_size = sizeof dm; dm.supersample = p.supersample; dm.albedo_floor = p.albedo_floor;
+	return dm;
+}
+
+// ---- The several-device route of denoise_spectral on host arrays: include/ssx.h's formulas restated, every operation in the header's type and order (the tests
+// hold them against the one-device calls bit for bit).  pixels x B bins, M = B / 4 count channels, E = B + M filter channels.
+
+// e0: the channels the filter takes -- per-bin sums and sample counts over the sample count n, divided in binary64 and rounded to binary32 once
+std::vector<float> spectral_channels(const std::vector<double>& sums, const std::vector<uint32_t>& counts, size_t pixels, size_t B, double n) {
+	const size_t M = B / 4, E = B + M;
+	std::vector<float> e0(pixels * E);
+	for (size_t p = 0; p < pixels; ++p) {
+		for (size_t b = 0; b < B; ++b) e0[p * E + b] = static_cast<float>(sums[p * B + b] / n);
+		for (size_t m = 0; m < M; ++m) e0[p * E + B + m] = static_cast<float>(static_cast<double>(counts[p * M + m]) / n);
+	}
+	return e0;
+}
+
+// What DEMODULATE leaves for REMODULATE: the albedo bins rho [pixels][B], the floored channel albedo rc [pixels][3], and which pixels were divided at all.
+struct Demodulation {
+	float floor;
+	std::vector<float> rho, rc;
+	std::vector<uint8_t> valid;
+	float floored(float r) const { return r > floor ? r : floor; }
+};
+
+// The denominators of the channel albedo: the develop's accumulation of all ones over each row of weights_xyz [3][B].
+void channel_denominators(const std::vector<float>& wc, size_t B, float den[3]) {
+	for (size_t c = 0; c < 3; ++c) {
+		volatile float acc = 0.0f;
+		for (size_t b = 0; b < B; ++b) acc = acc + wc[c * B + b];
+		den[c] = acc;
+		if (!(den[c] > 0.0f)) throw HostError{ SSX_ERR_ARG, "denoise_spectral: a row of weights_xyz does not sum to a positive denominator" };
+	}
+}
+
+// DEMODULATE, in binary32.  d.rho holds the albedo bins and d.rc their develop by weights_xyz (not yet normalised); bins (of e0), image and variance of
+// every pixel with a finite image and variance are divided by the floored albedo -- the others pass through as they are and stay out of REMODULATE.
+void demodulate(Demodulation& d, const float den[3], size_t B, std::vector<float>& e0, std::vector<float>& image, std::vector<float>& var) {
+	const size_t pixels = var.size(), E = B + B / 4;
+	d.valid.resize(pixels);
+	for (size_t p = 0; p < pixels; ++p) {
+		for (size_t c = 0; c < 3; ++c) d.rc[p * 3 + c] = d.floored(d.rc[p * 3 + c] / den[c]);
+		d.valid[p] = std::isfinite(image[p * 4]) && std::isfinite(image[p * 4 + 1]) && std::isfinite(image[p * 4 + 2]) && std::isfinite(var[p]);
+		if (!d.valid[p]) continue;
+		for (size_t b = 0; b < B; ++b) e0[p * E + b] = e0[p * E + b] / d.floored(d.rho[p * B + b]);
+		for (size_t c = 0; c < 3; ++c) image[p * 4 + c] = image[p * 4 + c] / d.rc[p * 3 + c];
+		var[p] = var[p] / (d.rc[p * 3 + 1] * d.rc[p * 3 + 1]);
+	}
+}
+
+// The filtered bins: the ratio of the filtered per-bin sums to the filtered counts of their sub-bin (0 where nothing was counted); d (the demodulated mode):
+// times the floored albedo bin, REMODULATE -- and the filtered image `out` times the channel albedo.
+std::vector<float> ratio(const std::vector<float>& eL, size_t pixels, size_t B, const Demodulation* d, std::vector<float>& out) {
+	const size_t M = B / 4, E = B + M;
+	std::vector<float> mean(pixels * B);
+	for (size_t p = 0; p < pixels; ++p) for (size_t b = 0; b < B; ++b) {
+		const float den = eL[p * E + B + b % M];
+		const float r = d && d->valid[p] ? d->floored(d->rho[p * B + b]) : 1.0f;
+		mean[p * B + b] = den > 0.0f ? (d ? (eL[p * E + b] / den) * r : eL[p * E + b] / den) : 0.0f;
+	}
+	if (d) for (size_t p = 0; p < pixels; ++p) if (d->valid[p]) for (size_t c = 0; c < 3; ++c) out[p * 4 + c] = out[p * 4 + c] * d->rc[p * 3 + c];
+	return mean;
+}
+} // namespace
+
+Renderer::Renderer(const Options& opts) : options(opts), framebuffer(opts.res), xyza(4 * opts.res[0] * opts.res[1], 0.0f) {
+	check_scene_name(options);
 	color = std::make_unique<ColorData>(options.data_dir, options.observer);
 	Texture tex;
 	const Texture* texp = nullptr;
@@ -186,7 +212,7 @@ Renderer::~Renderer() {
 ssx_render_params Renderer::params_for_(size_t d, size_t spp, size_t spp_per_launch) const {
 	ssx_render_params p{};
 	p.struct_size = sizeof p;
-	p.width = static_cast<uint32_t>(options.res[0]); p.height = static_cast<uint32_t>(options.res[1]);
+	p.width = w32_(); p.height = h32_();
 	p.spp = static_cast<uint32_t>(spp);
 	p.indirect_only = options.indirect_only ? 1u : 0u;
 	p.no_explicit_light_sampling = options.explicit_light_sampling ? 0u : 1u;
@@ -302,23 +328,37 @@ void Renderer::set_spectral_bins(size_t bins) {
 	spectral_bins_ = bins;
 }
 
+// One loop over the contexts for every reader of the bins: ssx_spectral_read on each, the shares merged by ownership into whichever of the three arrays are
+// asked for (sized here) -- every pixel from the device that owns it, bit for bit (merge_owned: the one merge by ownership mask).  Returns device 0's info.
+// The raw sums mean something under ONE sample count only: with `sums` the devices must be level (level_devices), and devices that are not are refused.
+ssx_spectral_info_t Renderer::gather_bins_(std::vector<float>* mean, std::vector<double>* sums, std::vector<uint32_t>* counts) {
+	const size_t pixels = options.res[0] * options.res[1], B = spectral_bins_, M = B / 4;
+	if (mean) mean->assign(pixels * B, 0.0f);
+	if (sums) sums->assign(pixels * B, 0.0);
+	if (counts) counts->assign(pixels * M, 0u);
+	std::vector<float> part_mean(mean ? pixels * B : 0);
+	std::vector<double> part_sums(sums ? pixels * B : 0);
+	std::vector<uint32_t> part_counts(counts ? pixels * M : 0);
+	ssx_spectral_info_t first{};
+	for (size_t d = 0; d < ctxs_.size(); ++d) {
+		ssx_spectral_info_t info{};
+		check_(api_->spectral_read(ctxs_[d], &info, mean ? part_mean.data() : nullptr, sums ? part_sums.data() : nullptr, counts ? part_counts.data() : nullptr), "ssx_spectral_read", ctxs_[d]);
+		if (d == 0) first = info;
+		if (sums && info.done_spp != first.done_spp) throw HostError{ SSX_ERR_STATE, "the devices' wavelength bins hold different sample counts (level_devices was not run)" };
+		if (mean) merge_owned(mean->data(), part_mean.data(), B, owner_(d));
+		if (sums) merge_owned(sums->data(), part_sums.data(), B, owner_(d));
+		if (counts) merge_owned(counts->data(), part_counts.data(), M, owner_(d));
+	}
+	return first;
+}
+
 void Renderer::spectral_image(std::vector<float>* mean, std::vector<uint32_t>* counts, std::vector<float>* centres) {
 	wait_workers_();
 	if (!spectral_bins_) throw HostError{ SSX_ERR_STATE, "spectral_image: spectral output is off (set_spectral_bins)" };
-	const size_t W = options.res[0], H = options.res[1], B = spectral_bins_, M = B / 4, n = ctxs_.size();
-	if (mean) mean->assign(W * H * B, 0.0f);
-	if (counts) counts->assign(W * H * M, 0u);
-	std::vector<float> part(mean ? W * H * B : 0);
-	std::vector<uint32_t> part_n(counts ? W * H * M : 0);
-	for (size_t d = 0; d < n; ++d) { // every pixel from the device that owns it, bit for bit (merge_owned: the one merge by ownership mask)
-		ssx_spectral_info_t info{};
-		check_(api_->spectral_read(ctxs_[d], &info, mean ? part.data() : nullptr, nullptr, counts ? part_n.data() : nullptr), "ssx_spectral_read", ctxs_[d]);
-		if (d == 0 && centres) {
-			centres->resize(B);
-			for (size_t b = 0; b < B; ++b) (*centres)[b] = info.lambda_min + (static_cast<float>(b) + 0.5f) * info.bin_width;
-		}
-		if (mean) merge_owned(mean->data(), part.data(), B, owner_(d));
-		if (counts) merge_owned(counts->data(), part_n.data(), M, owner_(d));
+	const ssx_spectral_info_t info = gather_bins_(mean, nullptr, counts); // (the library's means, not means recomputed here)
+	if (centres) {
+		centres->resize(spectral_bins_);
+		for (size_t b = 0; b < spectral_bins_; ++b) (*centres)[b] = info.lambda_min + (static_cast<float>(b) + 0.5f) * info.bin_width;
 	}
 }
 
@@ -339,7 +379,7 @@ Renderer::Guides Renderer::guides() {
 	const size_t W = options.res[0], H = options.res[1];
 	Guides g;
 	g.prim.assign(W * H, 0u); g.depth.assign(W * H, 0.0f); g.normal.assign(W * H * 3, 0.0f); g.albedo.assign(W * H * 4, 0.0f);
-	check_(api_->guides(ctxs_[0], static_cast<uint32_t>(W), static_cast<uint32_t>(H), g.prim.data(), g.depth.data(), g.normal.data(), g.albedo.data()), "ssx_guides", ctxs_[0]);
+	check_(api_->guides(ctxs_[0], w32_(), h32_(), g.prim.data(), g.depth.data(), g.normal.data(), g.albedo.data()), "ssx_guides", ctxs_[0]);
 	return g;
 }
 
@@ -358,26 +398,31 @@ void Renderer::save_guides(const std::string& path) {
 	save_npy_f32(path, all.data(), shape, 3);
 }
 
+// What the pure filter calls take from several devices besides the image (render_wait combined it: xyza): the devices are brought level (a stopped render: one
+// sample count behind every pixel's v), the variances are combined (each pixel's v is nonzero on its owner alone) and put into image units --
+// var = (float)(v * (s * s)) in binary64, s = what the image multiplies the mean by -- and the guides, which do not depend on ownership.
+Renderer::FilterInputs Renderer::filter_inputs_() {
+	level_devices();
+	std::vector<double> v;
+	(void)noise(&v);
+	const double s = options.rgb_mode ? 1.0 : 1000.0;
+	FilterInputs in;
+	in.var.resize(v.size());
+	for (size_t p = 0; p < v.size(); ++p) in.var[p] = static_cast<float>(v[p] * (s * s));
+	in.guides = guides();
+	return in;
+}
+
 Framebuffer Renderer::denoise(const DenoiseParams& params, std::vector<float>* xyza_out) {
 	wait_workers_();
-	const size_t W = options.res[0], H = options.res[1], pixels = W * H;
-	ssx_denoise_params dp{};
-	dp.struct_size = sizeof dp; dp.levels = params.levels; dp.sigma_l = params.sigma_l; dp.sigma_a = params.sigma_a;
+	const size_t pixels = options.res[0] * options.res[1];
+	const ssx_denoise_params dp = to_abi(params);
 	std::vector<float> out(pixels * 4);
 	ssx_ctx* root = ctxs_[0];
 	if (ctxs_.size() == 1) check_(api_->denoise(root, &dp, out.data(), nullptr), "ssx_denoise", root);
-	else {
-		// every device holds its own tiles: the image was combined by render_wait (xyza), the variances are combined here (each pixel's v is nonzero on its
-		// owner alone), the guides do not depend on ownership.  var = (float)(v * (s * s)) in binary64, s = what the image multiplies the mean by.
-		level_devices(); // (a stopped render: one sample count behind every pixel's v)
-		std::vector<double> v;
-		(void)noise(&v);
-		const double s = options.rgb_mode ? 1.0 : 1000.0;
-		std::vector<float> var(pixels);
-		for (size_t p = 0; p < pixels; ++p) var[p] = static_cast<float>(v[p] * (s * s));
-		const Guides g = guides();
-		check_(api_->denoise_images(root, &dp, static_cast<uint32_t>(W), static_cast<uint32_t>(H), xyza.data(), var.data(), g.prim.data(), g.albedo.data(), out.data(), nullptr),
-		       "ssx_denoise_images", root);
+	else { // every device holds its own tiles: image and variance combined by ownership, then the pure filter on device 0
+		const FilterInputs in = filter_inputs_();
+		check_(api_->denoise_images(root, &dp, w32_(), h32_(), xyza.data(), in.var.data(), in.guides.prim.data(), in.guides.albedo.data(), out.data(), nullptr), "ssx_denoise_images", root);
 	}
 	Framebuffer fb(options.res);
 	color->xyza_to_srgba(out.data(), fb.data(), pixels);
@@ -387,9 +432,8 @@ Framebuffer Renderer::denoise(const DenoiseParams& params, std::vector<float>* x
 
 std::vector<float> Renderer::albedo_bins(size_t bins, uint32_t supersample) {
 	wait_workers_();
-	const size_t W = options.res[0], H = options.res[1];
-	std::vector<float> rho(W * H * bins);
-	check_(api_->albedo_bins(ctxs_[0], static_cast<uint32_t>(W), static_cast<uint32_t>(H), static_cast<uint32_t>(bins), supersample, rho.data()), "ssx_albedo_bins", ctxs_[0]);
+	std::vector<float> rho(options.res[0] * options.res[1] * bins);
+	check_(api_->albedo_bins(ctxs_[0], w32_(), h32_(), static_cast<uint32_t>(bins), supersample, rho.data()), "ssx_albedo_bins", ctxs_[0]);
 	return rho;
 }
 
@@ -413,81 +457,15 @@ std::vector<float> Renderer::demod_weights_(const DemodParams& demod) const {
 Framebuffer Renderer::denoise_spectral(const DenoiseParams& params, std::vector<float>* bins, std::vector<float>* xyza_out, const DemodParams* demod) {
 	wait_workers_();
 	if (!spectral_bins_) throw HostError{ SSX_ERR_STATE, "denoise_spectral: spectral output is off (set_spectral_bins)" };
-	const size_t W = options.res[0], H = options.res[1], pixels = W * H, B = spectral_bins_, M = B / 4, E = B + M, n_dev = ctxs_.size();
-	ssx_denoise_params dp{};
-	dp.struct_size = sizeof dp; dp.levels = params.levels; dp.sigma_l = params.sigma_l; dp.sigma_a = params.sigma_a;
-	std::vector<float> out(pixels * 4), mean(pixels * B);
+	const size_t pixels = options.res[0] * options.res[1], B = spectral_bins_;
+	const ssx_denoise_params dp = to_abi(params, demod != nullptr);
+	const ssx_demod_params dm = demod ? to_abi(*demod) : ssx_demod_params{};
+	const std::vector<float> wc = demod ? demod_weights_(*demod) : std::vector<float>();
+	std::vector<float> out(pixels * 4), mean(ctxs_.size() == 1 ? pixels * B : 0);
 	ssx_ctx* root = ctxs_[0];
-	ssx_demod_params dm{};
-	std::vector<float> wc;
-	if (demod) {
-		dm.struct_size = sizeof dm; dm.supersample = demod->supersample; dm.albedo_floor = demod->albedo_floor;
-		wc = demod_weights_(*demod);
-		dp.sigma_a = 1.0f; // (ignored in this mode: the albedo guide is zero)
-	}
-	if (n_dev == 1 && demod) check_(api_->denoise_spectral_demod(root, &dp, &dm, wc.data(), mean.data(), out.data(), nullptr), "ssx_denoise_spectral_demod", root);
-	else if (n_dev == 1) check_(api_->denoise_spectral(root, &dp, mean.data(), out.data(), nullptr), "ssx_denoise_spectral", root);
-	else {
-		// as denoise() combines image and variance; the sums S and counts N come from the device that owns the pixel, bit for bit (spectral_image's merge)
-		level_devices();
-		std::vector<double> v;
-		(void)noise(&v);
-		const double s = options.rgb_mode ? 1.0 : 1000.0;
-		std::vector<float> var(pixels);
-		for (size_t p = 0; p < pixels; ++p) var[p] = static_cast<float>(v[p] * (s * s));
-		const Guides g = guides();
-		std::vector<double> part_s(pixels * B);
-		std::vector<uint32_t> part_n(pixels * M);
-		std::vector<float> e0(pixels * E), eL(pixels * E);
-		for (size_t d = 0; d < n_dev; ++d) {
-			ssx_spectral_info_t info{};
-			check_(api_->spectral_read(ctxs_[d], &info, nullptr, part_s.data(), part_n.data()), "ssx_spectral_read", ctxs_[d]);
-			const double n = static_cast<double>(info.done_spp);
-			const ssx_sums_info_t owner = owner_(d);
-			for (size_t j = 0; j < H; ++j) for (size_t i = 0; i < W; ++i) {
-				if (!sums_owner(owner, i, j)) continue;
-				const size_t p = j * W + i;
-				for (size_t b = 0; b < B; ++b) e0[p * E + b] = static_cast<float>(part_s[p * B + b] / n);                      // binary64 division, then rounded
-				for (size_t m = 0; m < M; ++m) e0[p * E + B + m] = static_cast<float>(static_cast<double>(part_n[p * M + m]) / n);
-			}
-		}
-		// the demodulated mode: DEMODULATE and REMODULATE of include/ssx.h on the host, in binary32, around the same pure filter with a zero albedo guide
-		std::vector<float> rho, rc, c_in(xyza), zero;
-		std::vector<uint8_t> valid;
-		const float f = demod ? demod->albedo_floor : 0.0f;
-		const auto floored = [f](float r) { return r > f ? r : f; };
-		if (demod) {
-			if (!(f > 0.0f) || !std::isfinite(f)) throw HostError{ SSX_ERR_ARG, "DemodParams.albedo_floor must be finite and positive" };
-			float den[3];
-			for (size_t c = 0; c < 3; ++c) { // the develop's accumulation of all ones
-				volatile float acc = 0.0f;
-				for (size_t b = 0; b < B; ++b) acc = acc + wc[c * B + b];
-				den[c] = acc;
-				if (!(den[c] > 0.0f)) throw HostError{ SSX_ERR_ARG, "denoise_spectral: a row of weights_xyz does not sum to a positive denominator" };
-			}
-			rho = albedo_bins(B, demod->supersample);
-			rc.resize(pixels * 3);
-			check_(api_->develop_images(root, static_cast<uint32_t>(W), static_cast<uint32_t>(H), static_cast<uint32_t>(B), rho.data(), wc.data(), 3, rc.data()), "ssx_develop_images", root);
-			valid.resize(pixels);
-			zero.assign(pixels * 4, 0.0f);
-			for (size_t p = 0; p < pixels; ++p) {
-				for (size_t c = 0; c < 3; ++c) rc[p * 3 + c] = floored(rc[p * 3 + c] / den[c]);
-				valid[p] = std::isfinite(xyza[p * 4]) && std::isfinite(xyza[p * 4 + 1]) && std::isfinite(xyza[p * 4 + 2]) && std::isfinite(var[p]);
-				if (!valid[p]) continue;
-				for (size_t b = 0; b < B; ++b) e0[p * E + b] = e0[p * E + b] / floored(rho[p * B + b]);
-				for (size_t c = 0; c < 3; ++c) c_in[p * 4 + c] = c_in[p * 4 + c] / rc[p * 3 + c];
-				var[p] = var[p] / (rc[p * 3 + 1] * rc[p * 3 + 1]);
-			}
-		}
-		check_(api_->denoise_channels(root, &dp, static_cast<uint32_t>(W), static_cast<uint32_t>(H), c_in.data(), var.data(), g.prim.data(), demod ? zero.data() : g.albedo.data(),
-		                              static_cast<uint32_t>(E), e0.data(), out.data(), nullptr, eL.data()), "ssx_denoise_channels", root);
-		for (size_t p = 0; p < pixels; ++p) for (size_t b = 0; b < B; ++b) {
-			const float den = eL[p * E + B + b % M];
-			const float r = demod && valid[p] ? floored(rho[p * B + b]) : 1.0f;
-			mean[p * B + b] = den > 0.0f ? (demod ? (eL[p * E + b] / den) * r : eL[p * E + b] / den) : 0.0f;
-		}
-		if (demod) for (size_t p = 0; p < pixels; ++p) if (valid[p]) for (size_t c = 0; c < 3; ++c) out[p * 4 + c] = out[p * 4 + c] * rc[p * 3 + c];
-	}
+	if (ctxs_.size() > 1) mean = denoise_spectral_devices_(dp, demod, wc, out);
+	else if (demod) check_(api_->denoise_spectral_demod(root, &dp, &dm, wc.data(), mean.data(), out.data(), nullptr), "ssx_denoise_spectral_demod", root);
+	else check_(api_->denoise_spectral(root, &dp, mean.data(), out.data(), nullptr), "ssx_denoise_spectral", root);
 	Framebuffer fb(options.res);
 	color->xyza_to_srgba(out.data(), fb.data(), pixels);
 	if (bins) bins->swap(mean);
@@ -495,26 +473,51 @@ Framebuffer Renderer::denoise_spectral(const DenoiseParams& params, std::vector<
 	return fb;
 }
 
+// denoise_spectral's several-device route (renderer.hpp): as denoise() combines image and variance; the sums S and counts N come from the device that owns
+// the pixel, bit for bit.  The demodulated mode: DEMODULATE and REMODULATE of include/ssx.h on the host around the same pure filter with a zero albedo guide.
+// Returns the filtered bins; out: the filtered image.
+std::vector<float> Renderer::denoise_spectral_devices_(const ssx_denoise_params& dp, const DemodParams* demod, const std::vector<float>& wc, std::vector<float>& out) {
+	const size_t pixels = options.res[0] * options.res[1], B = spectral_bins_, E = B + B / 4;
+	ssx_ctx* root = ctxs_[0];
+	FilterInputs in = filter_inputs_();
+	std::vector<double> sums;
+	std::vector<uint32_t> counts;
+	const ssx_spectral_info_t info = gather_bins_(nullptr, &sums, &counts);
+	std::vector<float> e0 = spectral_channels(sums, counts, pixels, B, static_cast<double>(info.done_spp)), eL(pixels * E), image(xyza);
+	Demodulation d{ demod ? demod->albedo_floor : 0.0f, {}, {}, {} };
+	if (demod) {
+		if (!(d.floor > 0.0f) || !std::isfinite(d.floor)) throw HostError{ SSX_ERR_ARG, "DemodParams.albedo_floor must be finite and positive" };
+		float den[3];
+		channel_denominators(wc, B, den);
+		d.rho = albedo_bins(B, demod->supersample);
+		d.rc.resize(pixels * 3);
+		check_(api_->develop_images(root, w32_(), h32_(), static_cast<uint32_t>(B), d.rho.data(), wc.data(), 3, d.rc.data()), "ssx_develop_images", root);
+		demodulate(d, den, B, e0, image, in.var);
+		in.guides.albedo.assign(pixels * 4, 0.0f);
+	}
+	check_(api_->denoise_channels(root, &dp, w32_(), h32_(), image.data(), in.var.data(), in.guides.prim.data(), in.guides.albedo.data(),
+	                              static_cast<uint32_t>(E), e0.data(), out.data(), nullptr, eL.data()), "ssx_denoise_channels", root);
+	return ratio(eL, pixels, B, demod ? &d : nullptr, out);
+}
+
 std::vector<float> Renderer::develop(const float* weights, size_t channels, const DenoiseParams* denoise, const DemodParams* demod) {
 	wait_workers_();
 	if (!spectral_bins_) throw HostError{ SSX_ERR_STATE, "develop: spectral output is off (set_spectral_bins)" };
-	const size_t W = options.res[0], H = options.res[1], pixels = W * H, B = spectral_bins_, C = channels, n_dev = ctxs_.size();
+	if (demod && !denoise) throw HostError{ SSX_ERR_ARG, "develop: the demodulated mode is a mode of the denoised source (pass denoise)" };
+	const size_t pixels = options.res[0] * options.res[1], B = spectral_bins_, C = channels, n_dev = ctxs_.size();
 	const uint32_t c32 = static_cast<uint32_t>(C);
 	std::vector<float> out(pixels * (C ? C : 1));
 	ssx_ctx* root = ctxs_[0];
-	ssx_denoise_params dp{};
-	if (denoise) { dp.struct_size = sizeof dp; dp.levels = denoise->levels; dp.sigma_l = denoise->sigma_l; dp.sigma_a = denoise->sigma_a; }
-	if (demod && !denoise) throw HostError{ SSX_ERR_ARG, "develop: the demodulated mode is a mode of the denoised source (pass denoise)" };
+	const ssx_denoise_params dp = denoise ? to_abi(*denoise, demod != nullptr) : ssx_denoise_params{};
 	if (n_dev == 1 && demod) {
-		ssx_demod_params dm{};
-		dm.struct_size = sizeof dm; dm.supersample = demod->supersample; dm.albedo_floor = demod->albedo_floor;
+		const ssx_demod_params dm = to_abi(*demod);
 		const std::vector<float> wc = demod_weights_(*demod);
 		check_(api_->spectral_develop_demod(root, &dp, &dm, wc.data(), weights, c32, out.data()), "ssx_spectral_develop_demod", root);
 	} else if (n_dev == 1) check_(api_->spectral_develop(root, denoise ? &dp : nullptr, weights, c32, out.data()), "ssx_spectral_develop", root);
 	else if (denoise) {
 		std::vector<float> bins;
 		(void)denoise_spectral(*denoise, &bins, nullptr, demod);
-		check_(api_->develop_images(root, static_cast<uint32_t>(W), static_cast<uint32_t>(H), static_cast<uint32_t>(B), bins.data(), weights, c32, out.data()), "ssx_develop_images", root);
+		check_(api_->develop_images(root, w32_(), h32_(), static_cast<uint32_t>(B), bins.data(), weights, c32, out.data()), "ssx_develop_images", root);
 	} else {
 		level_devices(); // (a stopped render: one sample count behind every pixel)
 		std::vector<float> part(out.size());
@@ -567,19 +570,7 @@ void Renderer::save_checkpoint(const std::string& path) {
 		ssx_spectral_info_t si{};
 		have_bins = api_->spectral_read(ctxs_[d], &si, nullptr, nullptr, nullptr) == SSX_OK; // (SSX_ERR_STATE: continuable sums without bins)
 	}
-	if (have_bins) {
-		const size_t B = spectral_bins_, M = B / 4;
-		ck.spectral_sums.assign(pixels * B, 0.0);
-		ck.spectral_counts.assign(pixels * M, 0u);
-		std::vector<double> part_s(pixels * B);
-		std::vector<uint32_t> part_n(pixels * M);
-		for (size_t d = 0; d < ctxs_.size(); ++d) {
-			ssx_spectral_info_t si{};
-			check_(api_->spectral_read(ctxs_[d], &si, nullptr, part_s.data(), part_n.data()), "ssx_spectral_read", ctxs_[d]);
-			if (d == 0) ck.spectral = si;
-			spectral_merge(ck.spectral_sums.data(), ck.spectral_counts.data(), part_s.data(), part_n.data(), B, owner_(d));
-		}
-	}
+	if (have_bins) ck.spectral = gather_bins_(nullptr, &ck.spectral_sums, &ck.spectral_counts);
 	ck.scene_name = options.scene_name;
 	ck.options_text = "observer=" + std::to_string(options.observer) + "\ntexture=" + options.texture_path + "\nlight_scale=" + std::to_string(options.light_scale) +
 	                  "\nuplift=" + std::to_string(options.uplift) + "\nrgb=" + (options.rgb_mode ? "1" : "0") +
@@ -667,12 +658,12 @@ void Renderer::render_wait() {
 	}
 	ssx_ctx* root = ctxs_[0];
 	if (options.reduce_rccl) { // one RCCL reduce over all devices (a single context: RCCL with one rank)
-		int rc = api_->reduce_rccl(ctxs_.data(), static_cast<int>(ctxs_.size()), static_cast<uint32_t>(options.res[0]), static_cast<uint32_t>(options.res[1]));
+		int rc = api_->reduce_rccl(ctxs_.data(), static_cast<int>(ctxs_.size()), w32_(), h32_());
 		if (rc) throw HostError{ rc, std::string("ssx_reduce_rccl: ") + api_->last_error(root) };
 	} else
 	for (size_t d = 1; d < ctxs_.size(); ++d) {
 		int rc = api_->accumulate_peer(root, api_->device_framebuffer(root), api_->device_index(ctxs_[d]), api_->device_framebuffer(ctxs_[d]),
-		                               static_cast<uint32_t>(options.res[0]), static_cast<uint32_t>(options.res[1]), nullptr);
+		                               w32_(), h32_(), nullptr);
 		if (rc) throw HostError{ rc, std::string("ssx_accumulate_peer: ") + api_->last_error(root) };
 	}
 	{

@@ -154,6 +154,16 @@ private:
 	size_t expected_spp_ = 0;   // the count the running (or last) call renders to: what render_wait compares ssx_done_spp with
 	ssx_render_params params_for_(size_t d, size_t spp, size_t spp_per_launch) const;
 	ssx_sums_info_t owner_(size_t d) const; // device d's ownership (tile_first / tile_stride / tile_skew), as the merges by ownership take it
+	uint32_t w32_() const { return static_cast<uint32_t>(options.res[0]); } // the options' resolution as the C ABI takes it
+	uint32_t h32_() const { return static_cast<uint32_t>(options.res[1]); }
+	// The two gathers of the several-device routes (renderer.cpp).  What the pure filter calls take besides the image, after level_devices(): the
+	// devices' variances combined and in image units, and the guides.
+	struct FilterInputs { std::vector<float> var; Guides guides; };
+	FilterInputs filter_inputs_();
+	// ssx_spectral_read of every device merged by ownership into the arrays asked for (the library's means | the raw sums | the counts); device 0's info
+	ssx_spectral_info_t gather_bins_(std::vector<float>* mean, std::vector<double>* sums, std::vector<uint32_t>* counts);
+	// denoise_spectral's several-device route: the filtered bins, and the filtered image in `out`
+	std::vector<float> denoise_spectral_devices_(const ssx_denoise_params& dp, const DemodParams* demod, const std::vector<float>& wc, std::vector<float>& out);
 	void start_(size_t spp, size_t spp_per_launch);
 	void wait_workers_();
 	void continue_each_(const std::vector<std::pair<ssx_ctx*, uint32_t>>& more);

@@ -257,6 +257,31 @@ def test_cli_two_devices_give_the_bits_of_one(tmp_path):
     assert p.returncode != 0 and "--demodulate" in p.stderr
 
 
+def test_cli_four_devices_with_unequal_shares_give_the_bits_of_one(tmp_path):
+    """20 x 12: 3 x 2 tiles, the last column and the upper row ragged; four devices own 2, 2, 1 and 1 of them (tile_skew = 1).  Every gather of the several-device
+    routes -- image, variance, sums and counts, the checkpoint's bins -- against the same command line on one device: the files byte for byte."""
+    from simple_spectral_amd.renderer import load_checkpoint_file_spectral
+    B = 8
+    common = [CLI, "-s=plane-srgb", "-w=20", "-h=12", "-spp=16", "--seed=%d" % SEED, "--texture=data/scenes/test-img.png", "--spectral-bins=%d" % B, "--denoise",
+              "--spectral-denoise", "--denoise-levels=3", "--denoise-sigma=2,0.2", "--demodulate=2"]
+    names = ("o.pfm", "s.npy", "d.pfm", "a.npy", "c.ckpt")
+    files = []
+    for n, (extra, env) in enumerate((([], {}), (["--gpus=4"], {"SSX_TEST_ONE_GPU": "1"}))):
+        pfm, npy, dev, alb, ck = (str(tmp_path / ("%d%s" % (n, name))) for name in names)
+        p = subprocess.run(common + extra + ["-o=" + pfm, "--spectral-output=" + npy, "--develop-output=" + dev, "--albedo-output=" + alb, "--checkpoint=" + ck],
+                           cwd=ROOT, capture_output=True, text=True, env=dict(os.environ, **env))
+        assert p.returncode == 0, p.stderr
+        *_, sinfo, S, N = load_checkpoint_file_spectral(ck)
+        files.append([open(f, "rb").read() for f in (pfm, npy, dev, alb)] + [(sinfo.bins, sinfo.done_spp), S, N])
+    one, four = files
+    for name, a, b in zip(names, one[:4], four[:4]):
+        assert len(a) > 0 and a == b, name
+    assert np.load(str(tmp_path / "1s.npy")).shape == (12, 20, B)
+    assert one[4] == four[4] == (B, 16)
+    assert S.shape == (12, 20, B) and N.shape == (12, 20, B // 4) and N.any()
+    assert np.array_equal(bits(one[5]), bits(four[5])) and np.array_equal(one[6], four[6])
+
+
 # ---- 6. quality ----------------------------------------------------------------------------------------------------------------------------------------------
 
 QRES, QSEED, QREF_SEED = (72, 40), 3, 1234          # tests/test_denoise_cpu.py's renders: the Y figures here are that test's

@@ -195,6 +195,18 @@ def test_missing_hip_library_fails_loudly(monkeypatch, tmp_path):
         _capi.hip_lib()
 
 
+def test_host_library_links_against_neither_hip_nor_the_device_library():
+    """The host resolves the C ABI at run time (host/renderer.cpp: Renderer::Api), and takes its prototypes from include/ssx.h without using the functions:
+    libssx_host.so needs no HIP runtime and no libssx_hip.so, and loads on a machine without a GPU."""
+    sbuild.build_host()
+    _, needed = _capi._elf_dynamic(sbuild.HOST_LIB)
+    assert needed, "no dynamic section read from libssx_host.so"
+    assert not [n for n in needed if "libamdhip64" in n or "libssx_hip" in n], needed
+    host = C.CDLL(sbuild.HOST_LIB)
+    for s in _capi.HOST_SYMBOLS:
+        getattr(host, s)
+
+
 def test_jakob_hanika_model_host_vs_oracle_and_round_trip(tmp_path):
     """RENDER_MODE_SPECTRAL_JH (config 3): the table is fitted by the build's own optimiser (the
     authors' .coeff blob is missing from the reference); fetch/eval must equal the oracle's
