@@ -290,7 +290,8 @@ int ssx_plan_info(ssx_ctx* ctx, float* frames_per_sample, int* fold_in_path_kern
  * performance choice only: same bits.  The environment variable SSX_PRE_HITS=0/1 at upload overrides it. */
 int ssx_calibration_info(ssx_ctx* ctx, float* frames_per_sample, float* rays_left_per_sample, int* camera_rays_pretraced);
 /* Device scratch the context holds right now: the per-sample arrays of the largest launch so far (48 bytes per sample in
- * flight: camera ray / result, stream / tail word, camera hit; 64 while spectral output is on: + hero flux) and the persistent waves' level logs (a fixed size per
+ * flight: camera ray / result, stream / tail word, camera hit; 64 while spectral output is on: + hero flux; while the spectral moments are on, the second moments Q are counted
+ * with them: owned tiles x bins x 64 x 8 bytes) and the persistent waves' level logs (a fixed size per
  * device and unit size: wave slots x 2 units x cohorts x 128 records x 582 bytes). */
 int ssx_scratch_info(ssx_ctx* ctx, uint64_t* sample_bytes, uint64_t* log_bytes);
 /* How the ordered binary64 pixel sums (src/renderer.cpp:292-295: a pixel's samples are added in ascending k) went, counted since
@@ -663,6 +664,54 @@ int ssx_denoise_spectral_demod(ssx_ctx* ctx, const ssx_denoise_params* params, c
 /* ssx_spectral_develop with this mode's `out` as the source q: the remodulated bins are developed where they lie.  weights [channels][B] and out as there. */
 int ssx_spectral_develop_demod(ssx_ctx* ctx, const ssx_denoise_params* denoise, const ssx_demod_params* demod, const float* weights_xyz /* [3][B] */,
                                const float* weights /* [C][B] */, uint32_t channels, float* out /* [H][W][C] */);
+
+/* ---- Spectral moments and region probes: error bars for the bins (appended; same ABI version) --------------------------------------------------------
+ * A bin mean of "Spectral radiance output" comes without an uncertainty, and the per-sample fluxes exist only between one launch and the next.  With the
+ * moments on, the sample walk keeps a per-pixel, per-bin second moment of the hero fluxes beside the sums S.  The samples of a pixel have independent
+ * streams (the seeding contract above), so a plain sample variance inside each sub-bin is the estimator; no batch means are needed.  Everything below is
+ * binary64 with IEEE + - * / only, no contraction, the operations in the order written: a restatement in numpy gives the same bits
+ * (tests/spectral_stats_ref.py).
+ *
+ * SECOND MOMENT.  With m, i, f[i] as there, for sample k of pixel p, in ascending k:
+ *       Q[p][i*M + m] += (double)f[i] * (double)f[i]          (the product is exact in binary64)
+ *   Q has the shape and the device layout of S; a non-finite flux is added as it is; the counts are N.
+ * VARIANCE OF A BIN MEAN.  For bin b, with n = N[p][b % M]:
+ *       n < 2 :  var[p][b] = +inf (binary32)                  unknown, not zero
+ *       else  :  q = Q - (S*S) / (double)n;   q = (q < 0.0) ? 0.0 : q         (a NaN stays a NaN)
+ *                var[p][b] = (float)((q / (double)(n-1)) / (double)n)
+ *   Pixels the context does not own read as 0 (var and Q).
+ * PROBE.  labels: uint8 [height][width], row 0 = bottom; 0..R-1 names a region (R <= 32), 255 none, any other value is SSX_ERR_ARG.  For region r and bin
+ *   b, with m = b % M, over the pixels p labelled r (n_p = N[p][m], q_p as above):
+ *       SS = sum S[p][b]                NN = sum n_p                                          (uint64)
+ *       VV = sum over n_p >= 2 of (q_p / (double)(n_p - 1)) * (double)n_p
+ *       UU = sum over n_p < 2 of n_p                                                          (uint64: samples whose variance is unestimated)
+ *   The order of the binary64 additions is part of the definition: within a row the pixels are added in ascending i starting from +0.0, one partial per row;
+ *   the row partials are added in ascending j starting from +0.0; a row without a pixel of the region contributes its +0.0.  The four arrays are [R][B];
+ *   NN and UU are repeated over i like the counts.  The hosts derive
+ *       mean = NN ? SS / NN : 0          stderr = sqrt(VV * NN / (NN - UU)) / NN               (NaN when NN - UU == 0)
+ *   Conditional on the counts Var(sum S_p) = sum n_p sigma_p^2, and q_p / (n_p - 1) is unbiased for sigma_p^2; the samples in sub-bins too thin to estimate
+ *   (UU of them) are taken to have the average variance of the others.  The pooled mean weights samples, not pixels.
+ * The state follows the bins' rule -- valid from zero samples or not at all: a sample-walking ssx_render_start resets it, ssx_render_continue carries it on,
+ * whatever clears the bins clears it, and it is invalid when it is switched on over existing bins.  ssx_spectral_import leaves the moments invalid: a checkpoint
+ * does not carry Q (out of scope so far, as the bins first were) -- a continue then renders normally, bins included, and the two read calls below return
+ * SSX_ERR_STATE with the reason.  Image, sums and bins of a render do not depend on whether the moments are on. */
+
+/* enable: 0 = off (default: nothing allocated, nothing launched), else on: the sample walk runs one more small kernel per launch, which reads the launch's
+ * fluxes again, and the context holds Q (as large as S; ssx_scratch_info counts it with the sample arrays).  Needs spectral output on (SSX_ERR_STATE; switching
+ * the bins off switches the moments off); not while a render runs (SSX_ERR_STATE). */
+int ssx_set_spectral_moments(ssx_ctx* ctx, int enable);
+/* Row-major (row 0 = bottom) var [height][width][B] (float) and q [height][width][B] (the binary64 accumulators Q); either may be NULL.  info is filled as
+ * by ssx_spectral_read.  SSX_ERR_STATE: spectral output or the moments are off, a render runs, or the context holds no valid bins or moments. */
+int ssx_spectral_variance(ssx_ctx* ctx, ssx_spectral_info_t* info, float* var, double* q);
+/* The probe of the context's own state: it exports S, Q and N row-major to device temporaries and runs the kernels of ssx_probe_arrays on them -- the same
+ * bits.  Pixels the context does not own add nothing.  SS, NN, VV, UU: [regions][B].  It reads only.  SSX_ERR_STATE as ssx_spectral_variance; SSX_ERR_ARG: a
+ * NULL argument, regions outside 1..32, a label that is neither a region nor 255. */
+int ssx_spectral_probe(ssx_ctx* ctx, const uint8_t* labels /* [H][W] */, uint32_t regions, double* SS, uint64_t* NN, double* VV, uint64_t* UU);
+/* The same probe as a pure function of its arguments (no scene needed, like ssx_denoise_images): sums and q [height][width][bins], counts
+ * [height][width][bins / 4] -- e.g. several devices' exports merged by ownership.  Two kernels: one workgroup per image row walks it in ascending i, then one
+ * lane per region and bin adds the rows in ascending j. */
+int ssx_probe_arrays(ssx_ctx* ctx, uint32_t width, uint32_t height, uint32_t bins, const double* sums, const double* q, const uint32_t* counts,
+                     const uint8_t* labels /* [H][W] */, uint32_t regions, double* SS, uint64_t* NN, double* VV, uint64_t* UU);
 
 /* ---- Diagnostics for the parity tests (not part of the reference's interface) ---------------------
  * ssx_debug_eval runs one building block of the path kernel -- the same device function the kernel

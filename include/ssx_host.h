@@ -88,6 +88,13 @@ int ssh_spectral_merge(double* dst_sums, uint32_t* dst_counts, const double* src
  * same array.  The CLI's --spectral-output writes the spectral image with it: shape (height, width, bins), row 0 = bottom. */
 int ssh_save_npy_f32(const char* path, const float* data, const uint32_t* shape, uint32_t ndim);
 
+/* The region probes' results (ssx.h "Spectral moments and region probes"; SS, NN, VV, UU: [regions][bins] of ssx_spectral_probe / ssx_probe_arrays) as their
+ * readers take them: mean = NN ? SS / NN : 0 and stderr = sqrt(VV * NN / (NN - UU)) / NN (NaN when NN - UU == 0), binary64, in this order; either output may be NULL. */
+int ssh_probe_derive(uint32_t regions, uint32_t bins, const double* SS, const uint64_t* NN, const double* VV, const uint64_t* UU, double* mean, double* std_err);
+/* ... and as a text file, what the CLI's --probe-output writes: the line "region,bin,wavelength,mean,stderr,samples,unestimated", then one line per region and bin
+ * in that order -- the bin's centre lambda_min + (b + 0.5) * bin_width in binary32 ("%.9g"), mean and stderr ("%.17g", "nan" for a NaN), NN and UU. */
+int ssh_probe_save_csv(const char* path, uint32_t regions, uint32_t bins, float lambda_min, float bin_width, const double* SS, const uint64_t* NN, const double* VV, const uint64_t* UU);
+
 /* ---- Developing the spectral bins (ssx.h "Developing the spectral bins": the definitions are there, operation by operation) ----------------------------------- */
 typedef struct ssh_spectrum_t { const float* samples; uint32_t n; float low, high; } ssh_spectrum_t; /* n >= 2 uniform samples over [low, high] */
 enum { SSH_SPACE_XYZ = 0, SSH_SPACE_LRGB = 1 };

@@ -118,7 +118,8 @@ HIP_SYMBOLS = ["ssx_create", "ssx_destroy", "ssx_upload_scene", "ssx_render_star
                "ssx_guides", "ssx_denoise_images", "ssx_denoise", "ssx_denoise_channels", "ssx_denoise_spectral",
                "ssx_develop_images", "ssx_spectral_develop",
                "ssx_albedo_bins", "ssx_denoise_spectral_demod", "ssx_spectral_develop_demod",
-               "ssx_spectral_import"]
+               "ssx_spectral_import",
+               "ssx_set_spectral_moments", "ssx_spectral_variance", "ssx_spectral_probe", "ssx_probe_arrays"]
 (SSX_SWEEP_RCP, SSX_SWEEP_SQRT, SSX_SWEEP_INVERSESQRT, SSX_SWEEP_SIN, SSX_SWEEP_COS, SSX_SWEEP_ACOS, SSX_SWEEP_DIV_PI,
  SSX_SWEEP_RCP64, SSX_SWEEP_DIV_PAIRS, SSX_SWEEP_ACOS_SIN, SSX_SWEEP_SIN_PROOF, SSX_SWEEP_COS_PROOF, SSX_SWEEP_ACOS_PROOF) = range(1, 14)
 # ssx_debug_eval ops (include/ssx.h)
@@ -130,7 +131,8 @@ HIP_SYMBOLS = ["ssx_create", "ssx_destroy", "ssx_upload_scene", "ssx_render_star
 HOST_SYMBOLS = ["ssh_scene_create", "ssh_scene_create_ex", "ssh_scene_destroy", "ssh_scene_desc", "ssh_xyza_to_srgba", "ssh_save_image",
                 "ssh_load_png_rgb8", "ssh_free", "ssh_color_values", "ssh_last_error", "ssh_checkpoint_save", "ssh_checkpoint_load", "ssh_sums_merge", "ssh_save_npy_f32",
                 "ssh_develop_weights", "ssh_relight_gain", "ssh_emitter_spectrum",
-                "ssh_checkpoint_save_spectral", "ssh_checkpoint_load_spectral", "ssh_spectral_merge"]
+                "ssh_checkpoint_save_spectral", "ssh_checkpoint_load_spectral", "ssh_spectral_merge",
+                "ssh_probe_derive", "ssh_probe_save_csv"]
 
 _hip = None
 _host = None
@@ -168,6 +170,8 @@ def host_lib():
                                                      C.POINTER(SsxSpectralInfo), C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.POINTER(C.c_uint32))]
         lib.ssh_spectral_merge.argtypes = [vp, vp, vp, vp, C.c_uint32, C.POINTER(SsxSumsInfo)]
         lib.ssh_save_npy_f32.argtypes = [C.c_char_p, vp, C.POINTER(C.c_uint32), C.c_uint32]
+        lib.ssh_probe_derive.argtypes = [C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp]
+        lib.ssh_probe_save_csv.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_float, C.c_float, vp, vp, vp, vp]
         lib.ssh_develop_weights.argtypes = [C.c_char_p, C.c_int, C.POINTER(SshSpectrum), C.c_uint32, C.POINTER(SshSpectrum), vp, C.c_int, C.c_uint32,
                                             C.c_float, C.c_float, vp, vp]
         lib.ssh_relight_gain.argtypes = [C.POINTER(SshSpectrum), C.POINTER(SshSpectrum), C.c_uint32, C.c_float, C.c_float, vp]
@@ -348,6 +352,11 @@ def hip_lib():
             lib.ssx_spectral_develop_demod.argtypes = [vp, C.POINTER(SsxDenoiseParams), C.POINTER(SsxDemodParams), vp, vp, C.c_uint32, vp]
         if not override or hasattr(lib, "ssx_spectral_import"):  # the bins through checkpoint and resume
             lib.ssx_spectral_import.argtypes = [vp, C.POINTER(SsxSpectralInfo), vp, vp]
+        if not override or hasattr(lib, "ssx_set_spectral_moments"):  # error bars for the bins: second moments, variances, region probes
+            lib.ssx_set_spectral_moments.argtypes = [vp, C.c_int]
+            lib.ssx_spectral_variance.argtypes = [vp, C.POINTER(SsxSpectralInfo), vp, vp]
+            lib.ssx_spectral_probe.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, vp]
+            lib.ssx_probe_arrays.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp]
         lib.ssx_kernel_variant.argtypes = [vp]
         lib.ssx_kernel_name.argtypes = [vp]
         lib.ssx_kernel_name.restype = C.c_char_p

@@ -4,7 +4,8 @@
 // The context, its launches, the render worker (render_sample_walk / render_tile_walk behind start_worker), the render entry points and the
 // diagnostics are here; scene packing is in ssx_pack.h, RCCL in ssx_rccl.h, the pixel ownership rule in ssx_pixel_grid.h, continue / export /
 // import of the sums and the noise estimate (entry points and their kernels) in ssx_progressive.hip, the spectral output in ssx_spectral.hip,
-// the guide buffers and the denoising filter in ssx_denoise.hip, the develop of the spectral bins in ssx_develop.hip.
+// the guide buffers and the denoising filter in ssx_denoise.hip, the develop of the spectral bins in ssx_develop.hip, their second moments, variances and
+// region probes in ssx_spectral_stats.hip.
 #include "ssx_kernels.hip"
 #include "ssx_debug.hip"
 
@@ -128,8 +129,9 @@ struct ssx_ctx {
 	// the sums may be continued or exported; noise_valid: d_noise describes them, after noise_batches batches (B).  Written by sums_invalidate /
 	// sums_publish and, for the estimate, the noise_* helpers; nowhere else.
 	// spectral_valid: d_spectral_sums / d_spectral_counts hold the bins of exactly those samples (valid from zero samples or not at all: ssx_spectral.hip).
+	// moments_valid: d_spectral_moments holds the second moments of exactly those samples too (the same rule: ssx_spectral_stats.hip).
 	// imported: the sums are ssx_sums_import's and nothing has rendered onto them since -- the one state ssx_spectral_import puts the bins next to.
-	struct SumsState { bool continuable = false, noise_valid = false, spectral_valid = false, imported = false; uint32_t noise_batches = 0; } sums;
+	struct SumsState { bool continuable = false, noise_valid = false, spectral_valid = false, moments_valid = false, imported = false; uint32_t noise_batches = 0; } sums;
 	uint32_t k_begin = 0;               // first sample of the running call: 0 (ssx_render_start) or the count ssx_render_continue took up (ssx_progress)
 	uint64_t scene_digest = 0;          // ssx_scene_digest
 	// noise estimate by batch means (ssx_set_noise_estimate): per pixel A_prev | S2 (row-major, 2 x width x height doubles)
@@ -142,6 +144,11 @@ struct ssx_ctx {
 	DeviceBuffer d_spectral_sums, d_spectral_counts;
 	std::string spectral_note;          // why sums that can be continued come without spectral state (ssx_spectral_read says it)
 	float lambda_min = 0.0f, lambda_step = 0.0f; // of the uploaded scene
+	// spectral moments (ssx_set_spectral_moments; csrc/ssx_spectral_stats.hip): off -- then nothing below is allocated and no kernel of it runs.  Q[tile slot][bin][pixel of
+	// the tile] binary64, the layout of S.  d_probe: the row-major arrays, partials and results of ssx_spectral_probe / ssx_probe_arrays; nothing until one of them is called.
+	bool spectral_moments = false;
+	DeviceBuffer d_spectral_moments, d_probe;
+	std::string moments_note;           // why bins that are valid come without moments (ssx_spectral_variance and ssx_spectral_probe say it)
 	// denoising (csrc/ssx_denoise.hip): nothing is allocated until ssx_guides / ssx_denoise / ssx_denoise_images is called.  d_guides holds the guide buffers of
 	// the uploaded scene at guides_width x guides_height (0: none; ssx_upload_scene drops them), d_denoise the filter's inputs and ping-pong buffers,
 	// d_denoise_channels those of the extra channels (ssx_denoise_channels / ssx_denoise_spectral only).
@@ -702,6 +709,13 @@ int noise_batch(ssx_ctx* ctx, const ssx_render_params* p, uint32_t n_k, hipStrea
 int spectral_refuses(ssx_ctx* ctx, const ssx_render_params& p, bool tile_walk);
 int spectral_begin(ssx_ctx* ctx, uint32_t my_tiles, bool continuing, bool* active);
 int spectral_batch(ssx_ctx* ctx, const ssx_render_params* p, const LaunchPlan& pl, uint32_t n_k, hipStream_t stream);
+// ... and the spectral moments' (csrc/ssx_spectral_stats.hip)
+int moments_reserve(ssx_ctx* ctx, uint32_t my_tiles, bool continuing);
+int moments_begin(ssx_ctx* ctx, uint32_t my_tiles, bool continuing, bool spectral, bool* active);
+int moments_batch(ssx_ctx* ctx, const ssx_render_params* p, const LaunchPlan& pl, uint32_t n_k, hipStream_t stream);
+void moments_publish(ssx_ctx* ctx, bool active);
+void moments_invalidate(ssx_ctx* ctx, const char* why);
+void moments_drop(ssx_ctx* ctx);
 
 // The asynchronous render: one worker thread per call of ssx_render_start / ssx_render_continue, walking through the samples or the tiles.  The end
 // of either walk: the image of what the sums hold, on the device, the stream idle.
@@ -746,9 +760,11 @@ int render_sample_walk(ssx_ctx* ctx, const ssx_render_params& p, uint32_t k_begi
 	if (!continuing && (rc = clear_sums(ctx, p.width, p.height, ctx->stream))) return rc;
 	if ((rc = noise_begin(ctx, &p, k_begin, continuing))) return rc;
 	maybe_swap_jit(ctx, 0); // (the scene's own kernels, if they have arrived: the plan is of the blob that is current now)
+	if ((rc = moments_reserve(ctx, owned_tiles(p), continuing))) return rc; // (before the plan asks the device for its free memory)
 	LaunchPlan pl = make_plan(ctx, &p);
-	bool spectral = false;
+	bool spectral = false, moments = false;
 	if ((rc = spectral_begin(ctx, pl.args.my_tiles, continuing, &spectral))) return rc;
+	if ((rc = moments_begin(ctx, pl.args.my_tiles, continuing, spectral, &moments))) return rc;
 	const uint32_t span = p.spp - k_begin, chunk = sample_walk_chunk(p, span, pl);
 	if ((rc = ensure_samples(ctx, pl, chunk < span ? chunk : span))) return rc;
 	for (uint32_t k0 = k_begin; k0 < p.spp && !ctx->stop_flag.load(); k0 += chunk) {
@@ -760,6 +776,7 @@ int render_sample_walk(ssx_ctx* ctx, const ssx_render_params& p, uint32_t k_begi
 		if ((rc = launch_range(ctx, pl, k0, k1, ctx->stream))) return rc;
 		if (ctx->noise_on && (rc = noise_batch(ctx, &p, k1 - k0, ctx->stream))) return rc;
 		if (spectral && (rc = spectral_batch(ctx, &p, pl, k1 - k0, ctx->stream))) return rc;
+		if (moments && (rc = moments_batch(ctx, &p, pl, k1 - k0, ctx->stream))) return rc;
 		SSX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 		ctx->done_spp.store(k1);
 	}
@@ -771,6 +788,7 @@ int render_sample_walk(ssx_ctx* ctx, const ssx_render_params& p, uint32_t k_begi
 	ctx->done_tiles.store(pl.args.my_tiles);
 	ctx->sums.spectral_valid = spectral; // (the bins of the launches that ran: exactly the samples the sums hold)
 	if (!spectral) ctx->spectral_note = "the render that made these sums ran without them (it continued sums that had none)";
+	moments_publish(ctx, moments);
 	sums_publish(ctx, done);
 	return SSX_OK;
 }
@@ -1382,7 +1400,7 @@ int ssx_calibration_info(ssx_ctx* ctx, float* frames_per_sample, float* rays_lef
 
 int ssx_scratch_info(ssx_ctx* ctx, uint64_t* sample_bytes, uint64_t* log_bytes) {
 	if (!ctx) return SSX_ERR_ARG;
-	if (sample_bytes) *sample_bytes = (uint64_t)sample_slots(ctx) * bytes_per_sample(ctx);
+	if (sample_bytes) *sample_bytes = (uint64_t)sample_slots(ctx) * bytes_per_sample(ctx) + (ctx->spectral_moments ? (uint64_t)ctx->d_spectral_moments.bytes : 0u);
 	if (log_bytes) *log_bytes = (uint64_t)ctx->d_logs.bytes;
 	return SSX_OK;
 }
@@ -1455,3 +1473,4 @@ int ssx_kernel_info(ssx_ctx* ctx, int* vgprs, int* sgprs, int* lds_bytes, int* s
 #include "ssx_denoise.hip"
 #include "ssx_develop.hip"
 #include "ssx_demod.hip"
+#include "ssx_spectral_stats.hip"

@@ -175,7 +175,8 @@ int ssx_set_spectral_bins(ssx_ctx* ctx, uint32_t bins) {
 	if (const int rc = wait_device_pending(ctx)) return rc; // (a queued ssx_render_device uses the sample arrays in the layout without flux[])
 	ctx->spectral_bins = bins;
 	ctx->sums.spectral_valid = false; ctx->spectral_note = "the bin count changed after the last render";
-	if (!bins) spectral_drop(ctx);
+	moments_invalidate(ctx, "the bin count changed after the last render"); // (whatever clears the bins clears their moments)
+	if (!bins) { spectral_drop(ctx); ctx->spectral_moments = false; moments_drop(ctx); }
 	return SSX_OK;
 }
 
@@ -256,6 +257,7 @@ int ssx_spectral_import(ssx_ctx* ctx, const ssx_spectral_info_t* info, const dou
 	if (bad) return fail(ctx, SSX_ERR_ARG, fmt("ssx_spectral_import: counts: a pixel this context owns does not hold done_spp = %u samples over its %u counts (every sample is counted once; "
 	                                           "one rank's unmerged export holds zeros where it owned nothing: merge the ranks' exports by ownership first)", done, M));
 	ctx->sums.spectral_valid = true; ctx->spectral_note.clear();
+	moments_invalidate(ctx, "the bins came from ssx_spectral_import, and a checkpoint does not carry their second moments (out of scope so far: render from ssx_render_start to have them)");
 	return SSX_OK;
 }
 

@@ -1,0 +1,310 @@
+// ssx_spectral_stats.hip -- error bars for the spectral output: a per-pixel, per-bin second moment of the hero fluxes beside the sums S, the variance of every
+// bin mean, and region probes (include/ssx.h, "Spectral moments and region probes").  Part of ssx_api.hip's translation unit, behind ssx_spectral.hip (whose
+// state S, N it stands next to) and ssx_denoise.hip (blocks_of, denoise_check_size).  Everything here is binary64 with IEEE + - * /, no contraction (the build's
+// -ffp-contract=off), in the order the header writes: a restatement in numpy gives the same bits (tests/spectral_stats_ref.py).
+
+// What ssx_spectral_moment_kernel needs of a launch: what ssx_spectral_bin_kernel needs (SsxSpectralArgs), with Q[tile slot][bin][pixel of the tile] in place of S
+// and no counts -- they are the bin kernel's N.
+struct SsxMomentArgs {
+	const float4* flux; const uint4* st;
+	double* Q;
+	SsxPixelGrid g;
+	uint32_t n_k, M;
+	float lambda_min, lambda_step;
+};
+
+// The bin kernel's lane mapping: one 256-lane workgroup per owned tile slot, lane = (pixel of the tile, hero slot i), lane (pixel, i) owns the pixel's bins
+// i*M .. i*M + M-1 of Q: no atomics, no barriers.  The lane's M accumulators live in LDS as [M][256] binary64 (a run-time index; lane l of a row is at
+// 8-byte address l: a ds_read_b64 / ds_write_b64 is served in two groups of 32 lanes over 64 four-byte banks, and 32 consecutive 8-byte addresses cover each
+// bank pair once -- conflict-free).  32 KB at 64 bins: S and Q in one kernel would need more than 64 KB, and the bin kernel stays what it was.
+//     m as there;  Q[i*M + m] += (double)f[i] * (double)f[i]      (the product of two binary32 values is exact in binary64)
+// in ascending k.  Lanes outside a ragged image have no records and touch nothing.
+extern "C" __global__ void __launch_bounds__(256) ssx_spectral_moment_kernel(SsxMomentArgs a) {
+	extern __shared__ double moment_lds[];
+	const uint32_t tid = threadIdx.x, px = tid >> 2, i = tid & 3u, slot = blockIdx.x, M = a.M;
+	uint32_t tx, ty;
+	(void)tile_of_slot(a.g, slot, tx, ty);
+	if (tx * 8u + (px & 7u) >= a.g.width || ty * 8u + (px >> 3) >= a.g.height) return;
+	double* const acc = moment_lds + tid;                                                // [m * 256]
+	double* const Q = a.Q + ((size_t)slot * 4u * M + (size_t)i * M) * 64u + px;          // [m * 64]
+	for (uint32_t m = 0; m < M; ++m) acc[m * 256u] = Q[m * 64u];
+	const float fM = (float)M;
+	size_t r = (size_t)slot * a.n_k * 64u + px;
+#pragma unroll 4
+	for (uint32_t kk = 0; kk < a.n_k; ++kk, r += 64u) {
+		const float f = reinterpret_cast<const float*>(a.flux + r)[i], lambda_0 = __uint_as_float(a.st[r].x);
+		const float t = (lambda_0 - a.lambda_min) / a.lambda_step;
+		const uint32_t m = min(M - 1u, (uint32_t)(t * fM));
+		const double d = (double)f;
+		acc[m * 256u] += d * d;
+	}
+	for (uint32_t m = 0; m < M; ++m) Q[m * 64u] = acc[m * 256u];
+}
+
+// q of the header: the sum of squared deviations of a sub-bin's n >= 2 samples from their mean, from Q, S and n; negative rounding residue is 0, a NaN stays one
+__device__ __forceinline__ double moment_deviations(double Q, double S, uint32_t n) {
+	const double q = Q - (S * S) / (double)n;
+	return (q < 0.0) ? 0.0 : q;
+}
+
+// S, Q, N -> row-major [height][width][B] var (binary32) and Q (either may be NULL); 0 for pixels the context does not own.
+//     n = N[b % M];   n < 2: var = +inf;   else var = (float)((q / (double)(n-1)) / (double)n)
+extern "C" __global__ void __launch_bounds__(256) ssx_spectral_variance_kernel(const double* S, const double* Q, const uint32_t* N, float* var, double* q_out, SsxPixelGrid g, uint32_t M) {
+	const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x, n_px = g.width * g.height, B = 4u * M;
+	if (p >= n_px) return;
+	const uint32_t i = p % g.width, j = p / g.width;
+	const bool own = ssx_owns_pixel(g, i, j);
+	const size_t slot = ssx_shared_tile(g, i, j) / g.tile_stride, lane = (j & 7u) * 8u + (i & 7u);
+	for (uint32_t b = 0; b < B; ++b) {
+		float v = 0.0f; double qq = 0.0;
+		if (own) {
+			const size_t at = (slot * B + b) * 64u + lane;
+			const uint32_t n = N[(slot * M + b % M) * 64u + lane];
+			qq = Q[at];
+			v = n < 2u ? __uint_as_float(0x7F800000u) : (float)((moment_deviations(qq, S[at], n) / (double)(n - 1u)) / (double)n);
+		}
+		if (var) var[(size_t)p * B + b] = v;
+		if (q_out) q_out[(size_t)p * B + b] = qq;
+	}
+}
+
+// Region probes on row-major device arrays: sums and q [height][width][B], counts [height][width][M], labels [height][width] (0..R-1, or 255: no region).
+// Stage 1: one workgroup per image row and half h of the quantities (h = 0: SS | NN, h = 1: VV | UU), 2 B lanes, lane = (quantity, bin): the B lanes of a
+// quantity read B consecutive elements of a pixel.  The pixel's label is a run-time index, so the accumulators live in LDS, [R][2 B] eight-byte words (lane l of a
+// row at 8-byte address l: conflict-free, as above; 32 KB at R = 32, B = 64), each lane its own column: no atomics, no barriers.  The workgroup walks the row in
+// ascending i, from +0.0 / 0, and writes its partials part[j][r][quantity 0..3][B]; a region without a pixel in the row leaves its +0.0.
+struct SsxProbeArgs {
+	const double* sums; const double* q; const uint32_t* counts; const uint8_t* labels;
+	uint64_t* part;   // [height][R][4][B]: SS, NN, VV, UU -- binary64 or uint64 by quantity
+	uint64_t* out;    // [4][R][B]
+	uint32_t width, height, B, R;
+};
+
+extern "C" __global__ void __launch_bounds__(128) ssx_probe_rows_kernel(SsxProbeArgs a) {
+	extern __shared__ uint64_t probe_lds[];
+	const uint32_t t = threadIdx.x, B = a.B, M = B / 4u, j = blockIdx.x, half = blockIdx.y, second = t / B, b = t - second * B, lanes = 2u * B;
+	uint64_t* const acc = probe_lds + t;                                                 // [r * lanes]
+	for (uint32_t r = 0; r < a.R; ++r) acc[r * lanes] = 0ull;
+	const size_t row = (size_t)j * a.width;
+	for (uint32_t i = 0; i < a.width; ++i) {
+		const uint32_t r = a.labels[row + i];
+		if (r >= a.R) continue;                                                          // 255: no region (other values never get here: the host refuses them)
+		const size_t p = row + i;
+		const uint32_t n = a.counts[p * M + b % M];
+		uint64_t* const at = acc + r * lanes;
+		if (second) *at += (half == 0u) ? (uint64_t)n : (n < 2u ? (uint64_t)n : 0ull);   // NN | UU
+		else if (half == 0u) *reinterpret_cast<double*>(at) += a.sums[p * B + b];        // SS
+		else if (n >= 2u) *reinterpret_cast<double*>(at) += (moment_deviations(a.q[p * B + b], a.sums[p * B + b], n) / (double)(n - 1u)) * (double)n; // VV
+	}
+	const uint32_t quantity = half * 2u + second;                                        // 0 SS, 1 NN, 2 VV, 3 UU
+	for (uint32_t r = 0; r < a.R; ++r) a.part[(((size_t)j * a.R + r) * 4u + quantity) * B + b] = acc[r * lanes];
+}
+
+// Stage 2: one lane per (quantity, r, b) adds the rows' partials in ascending j, from +0.0 / 0.
+extern "C" __global__ void __launch_bounds__(256) ssx_probe_reduce_kernel(SsxProbeArgs a) {
+	const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x, B = a.B;
+	if (e >= 4u * a.R * B) return;
+	const uint32_t quantity = e / (a.R * B), rb = e - quantity * (a.R * B), r = rb / B, b = rb - r * B;
+	const uint64_t* const src = a.part + ((size_t)r * 4u + quantity) * B + b;
+	const size_t stride = (size_t)a.R * 4u * B;
+	if (quantity & 1u) {
+		uint64_t total = 0ull;
+		for (uint32_t j = 0; j < a.height; ++j) total += src[j * stride];
+		a.out[e] = total;
+	} else {
+		double total = 0.0;
+		for (uint32_t j = 0; j < a.height; ++j) total += reinterpret_cast<const double*>(src)[j * stride];
+		reinterpret_cast<double*>(a.out)[e] = total;
+	}
+}
+
+namespace {
+
+size_t moment_bytes(const ssx_ctx* ctx, uint32_t tiles) { return (size_t)tiles * ctx->spectral_bins * 64u * sizeof(double); }
+
+// Whether the sample walk about to start will keep the moments (what moments_begin decides once the walk runs): so that the allocation of Q precedes the plan
+// of the sample arrays, which asks the device for its free memory.
+int moments_reserve(ssx_ctx* ctx, uint32_t my_tiles, bool continuing) {
+	if (!ctx->spectral_bins || !ctx->spectral_moments || continuing) return SSX_OK;
+	SSX_HIP(ctx, ctx->d_spectral_moments.reserve(moment_bytes(ctx, my_tiles)));
+	return SSX_OK;
+}
+
+// Start of a sample walk, behind spectral_begin (`spectral`: this walk bins its launches).  The moments follow the bins' rule: zeroed by ssx_render_start,
+// carried on by a continue that finds them valid, otherwise left out -- the render is the same, the state stays invalid.
+int moments_begin(ssx_ctx* ctx, uint32_t my_tiles, bool continuing, bool spectral, bool* active) {
+	*active = spectral && ctx->spectral_moments && (!continuing || ctx->sums.moments_valid);
+	if (!*active || continuing || !my_tiles) return SSX_OK;
+	SSX_HIP(ctx, hipMemsetAsync(ctx->d_spectral_moments.ptr, 0, moment_bytes(ctx, my_tiles), ctx->stream));
+	return SSX_OK;
+}
+
+// after the launch of samples [k0, k0 + n_k), next to spectral_batch: the same records, read again
+int moments_batch(ssx_ctx* ctx, const ssx_render_params* p, const LaunchPlan& pl, uint32_t n_k, hipStream_t stream) {
+	if (pl.args.my_tiles == 0 || n_k == 0) return SSX_OK;
+	SsxKernelArgs bound = pl.args;
+	bind_arrays(bound, ctx->d_samples.as<uint8_t>(), (uint64_t)pl.args.my_tiles * n_k * 64u, nullptr, 0, true);
+	SsxMomentArgs a{};
+	a.flux = bound.flux; a.st = bound.st;
+	a.Q = ctx->d_spectral_moments.as<double>();
+	a.g = pixel_grid(p);
+	a.n_k = n_k; a.M = ctx->spectral_bins / 4u;
+	a.lambda_min = ctx->lambda_min; a.lambda_step = ctx->lambda_step;
+	const size_t lds = (size_t)a.M * 256u * sizeof(double); // <= 32 KB at 64 bins
+	hipLaunchKernelGGL(ssx_spectral_moment_kernel, dim3(pl.args.my_tiles), dim3(256), lds, stream, a);
+	SSX_HIP(ctx, hipGetLastError());
+	return SSX_OK;
+}
+
+// the end of a sample walk: the moments of the launches that ran, or why there are none
+void moments_publish(ssx_ctx* ctx, bool active) {
+	ctx->sums.moments_valid = active;
+	if (!active && ctx->spectral_moments) ctx->moments_note = "the render that made these bins ran without them (it continued bins that had none)";
+}
+
+void moments_invalidate(ssx_ctx* ctx, const char* why) { ctx->sums.moments_valid = false; ctx->moments_note = why; }
+void moments_drop(ssx_ctx* ctx) { ctx->d_spectral_moments.release(); }
+
+// What ssx_spectral_variance and ssx_spectral_probe ask first: bins on, moments on, no render, valid bins and valid moments; then the device is the context's.
+int moments_ready(ssx_ctx* ctx, const char* what) {
+	if (!ctx->spectral_bins) return fail(ctx, SSX_ERR_STATE, fmt("%s: spectral output is off (ssx_set_spectral_bins)", what));
+	if (!ctx->spectral_moments) return fail(ctx, SSX_ERR_STATE, fmt("%s: spectral moments are off (ssx_set_spectral_moments)", what));
+	if (ctx->rendering.load()) return fail(ctx, SSX_ERR_STATE, "render in progress");
+	if (!ctx->sums.continuable || !ctx->sums.spectral_valid)
+		return fail(ctx, SSX_ERR_STATE, fmt("%s: the context holds no spectral bins: ", what) + (ctx->sums.continuable ? ctx->spectral_note : std::string("no render has accumulated any (ssx_render_start first)")));
+	if (!ctx->sums.moments_valid) return fail(ctx, SSX_ERR_STATE, fmt("%s: the context holds no spectral moments: ", what) + ctx->moments_note);
+	SSX_HIP(ctx, hipSetDevice(ctx->device));
+	return wait_device_pending(ctx);
+}
+
+void spectral_info_of(const ssx_ctx* ctx, ssx_spectral_info_t* info) {
+	const ssx_render_params& p = ctx->cur;
+	memset(info, 0, sizeof *info);
+	info->struct_size = sizeof *info;
+	info->width = p.width; info->height = p.height; info->bins = ctx->spectral_bins; info->done_spp = ctx->done_spp.load();
+	info->lambda_min = ctx->lambda_min; info->bin_width = ctx->lambda_step / (float)(ctx->spectral_bins / 4u);
+}
+
+// d_probe: sums | q [pixels][B] binary64 | part [height][R][4][B] | out [4][R][B] | counts [pixels][M] | labels [pixels] -- eight-byte quantities first
+struct ProbeBuffers { double* sums; double* q; uint64_t* part; uint64_t* out; uint32_t* counts; uint8_t* labels; };
+int probe_buffers(ssx_ctx* ctx, uint32_t width, uint32_t height, uint32_t B, uint32_t R, ProbeBuffers* d) {
+	const size_t pixels = (size_t)width * height, b_bins = pixels * B * sizeof(double), b_part = (size_t)height * R * 4u * B * 8u, b_out = (size_t)4u * R * B * 8u,
+	             b_counts = pixels * (B / 4u) * sizeof(uint32_t);
+	SSX_HIP(ctx, ctx->d_probe.reserve(2u * b_bins + b_part + b_out + b_counts + pixels));
+	uint8_t* at = ctx->d_probe.as<uint8_t>();
+	d->sums = reinterpret_cast<double*>(at); at += b_bins;
+	d->q = reinterpret_cast<double*>(at); at += b_bins;
+	d->part = reinterpret_cast<uint64_t*>(at); at += b_part;
+	d->out = reinterpret_cast<uint64_t*>(at); at += b_out;
+	d->counts = reinterpret_cast<uint32_t*>(at); at += b_counts;
+	d->labels = at;
+	return SSX_OK;
+}
+
+int probe_check(ssx_ctx* ctx, const char* what, uint32_t width, uint32_t height, const uint8_t* labels, uint32_t R, const void* SS, const void* NN, const void* VV, const void* UU) {
+	if (!labels || !SS || !NN || !VV || !UU) return fail(ctx, SSX_ERR_ARG, fmt("%s: labels and the four outputs must not be NULL", what));
+	if (R < 1u || R > 32u) return fail(ctx, SSX_ERR_ARG, fmt("%s: %u regions: need 1..32", what, R));
+	const size_t pixels = (size_t)width * height;
+	for (size_t p = 0; p < pixels; ++p)
+		if (labels[p] != 255u && labels[p] >= R)
+			return fail(ctx, SSX_ERR_ARG, fmt("%s: labels[%zu][%zu] = %u: need a region 0..%u, or 255 for none", what, p / width, p % width, (unsigned)labels[p], R - 1u));
+	return SSX_OK;
+}
+
+// The one body of both probes: sums, q and counts are in d already; the labels go up, the two kernels run, the four [R][B] arrays come back.
+int probe_device(ssx_ctx* ctx, const ProbeBuffers& d, uint32_t width, uint32_t height, uint32_t B, const uint8_t* labels, uint32_t R, double* SS, uint64_t* NN, double* VV, uint64_t* UU) {
+	SSX_HIP(ctx, hipMemcpyAsync(d.labels, labels, (size_t)width * height, hipMemcpyHostToDevice, ctx->stream));
+	SsxProbeArgs a{};
+	a.sums = d.sums; a.q = d.q; a.counts = d.counts; a.labels = d.labels; a.part = d.part; a.out = d.out;
+	a.width = width; a.height = height; a.B = B; a.R = R;
+	const size_t lds = (size_t)R * 2u * B * sizeof(uint64_t); // <= 32 KB
+	hipLaunchKernelGGL(ssx_probe_rows_kernel, dim3(height, 2), dim3(2u * B), lds, ctx->stream, a);
+	SSX_HIP(ctx, hipGetLastError());
+	hipLaunchKernelGGL(ssx_probe_reduce_kernel, blocks_of((size_t)4u * R * B), dim3(256), 0, ctx->stream, a);
+	SSX_HIP(ctx, hipGetLastError());
+	SSX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	const size_t n = (size_t)R * B * 8u;
+	void* const outs[4] = { SS, NN, VV, UU };
+	for (int k = 0; k < 4; ++k) SSX_HIP(ctx, hipMemcpy(outs[k], d.out + (size_t)k * R * B, n, hipMemcpyDeviceToHost));
+	return SSX_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int ssx_set_spectral_moments(ssx_ctx* ctx, int enable) {
+	if (!ctx) return SSX_ERR_ARG;
+	const bool on = enable != 0;
+	if (on && !ctx->spectral_bins) return fail(ctx, SSX_ERR_STATE, "ssx_set_spectral_moments: spectral output is off (ssx_set_spectral_bins first)");
+	if (ctx->rendering.load()) return fail(ctx, SSX_ERR_STATE, "render in progress");
+	if (on == ctx->spectral_moments) return SSX_OK;
+	SSX_HIP(ctx, hipSetDevice(ctx->device));
+	if (const int rc = wait_device_pending(ctx)) return rc;
+	ctx->spectral_moments = on;
+	moments_invalidate(ctx, "they were switched on after the render that made these bins (valid from zero samples or not at all: ssx_render_start first)");
+	if (!on) moments_drop(ctx);
+	return SSX_OK;
+}
+
+int ssx_spectral_variance(ssx_ctx* ctx, ssx_spectral_info_t* info, float* var, double* q) {
+	if (!ctx || !info) return SSX_ERR_ARG;
+	if (const int rc = moments_ready(ctx, "ssx_spectral_variance")) return rc;
+	spectral_info_of(ctx, info);
+	if (!var && !q) return SSX_OK;
+	const ssx_render_params& p = ctx->cur;
+	const uint32_t B = ctx->spectral_bins, M = B / 4u;
+	const size_t pixels = (size_t)p.width * p.height, b_q = pixels * B * sizeof(double), b_var = pixels * B * sizeof(float);
+	DeviceBuffer& stage = ctx->d_stage;
+	SSX_HIP(ctx, stage.reserve(b_q + b_var));
+	double* const d_q = stage.as<double>();
+	float* const d_var = reinterpret_cast<float*>(stage.as<uint8_t>() + b_q);
+	hipLaunchKernelGGL(ssx_spectral_variance_kernel, pixel_blocks(&p), dim3(256), 0, ctx->stream, ctx->d_spectral_sums.as<const double>(), ctx->d_spectral_moments.as<const double>(),
+	                   ctx->d_spectral_counts.as<const uint32_t>(), var ? d_var : nullptr, q ? d_q : nullptr, pixel_grid(&p), M);
+	SSX_HIP(ctx, hipGetLastError());
+	SSX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	if (q) SSX_HIP(ctx, hipMemcpy(q, d_q, b_q, hipMemcpyDeviceToHost));
+	if (var) SSX_HIP(ctx, hipMemcpy(var, d_var, b_var, hipMemcpyDeviceToHost));
+	return SSX_OK;
+}
+
+int ssx_spectral_probe(ssx_ctx* ctx, const uint8_t* labels, uint32_t regions, double* SS, uint64_t* NN, double* VV, uint64_t* UU) {
+	if (!ctx) return SSX_ERR_ARG;
+	const char* const what = "ssx_spectral_probe";
+	int rc = moments_ready(ctx, what);
+	if (rc) return rc;
+	const ssx_render_params& p = ctx->cur;
+	if ((rc = probe_check(ctx, what, p.width, p.height, labels, regions, SS, NN, VV, UU))) return rc;
+	const uint32_t B = ctx->spectral_bins, M = B / 4u;
+	ProbeBuffers d;
+	if ((rc = probe_buffers(ctx, p.width, p.height, B, regions, &d))) return rc;
+	// the state, row-major, into the arrays the pure call uploads: pixels of other contexts read as 0 and add nothing
+	hipLaunchKernelGGL(ssx_spectral_export_kernel, pixel_blocks(&p), dim3(256), 0, ctx->stream, ctx->d_spectral_sums.as<const double>(), ctx->d_spectral_counts.as<const uint32_t>(),
+	                   (float*)nullptr, d.sums, d.counts, pixel_grid(&p), M);
+	SSX_HIP(ctx, hipGetLastError());
+	hipLaunchKernelGGL(ssx_spectral_variance_kernel, pixel_blocks(&p), dim3(256), 0, ctx->stream, ctx->d_spectral_sums.as<const double>(), ctx->d_spectral_moments.as<const double>(),
+	                   ctx->d_spectral_counts.as<const uint32_t>(), (float*)nullptr, d.q, pixel_grid(&p), M);
+	SSX_HIP(ctx, hipGetLastError());
+	return probe_device(ctx, d, p.width, p.height, B, labels, regions, SS, NN, VV, UU);
+}
+
+int ssx_probe_arrays(ssx_ctx* ctx, uint32_t width, uint32_t height, uint32_t bins, const double* sums, const double* q, const uint32_t* counts, const uint8_t* labels, uint32_t regions,
+                     double* SS, uint64_t* NN, double* VV, uint64_t* UU) {
+	if (!ctx) return SSX_ERR_ARG;
+	const char* const what = "ssx_probe_arrays";
+	if (bins < 4u || bins > 64u || (bins & 3u)) return fail(ctx, SSX_ERR_ARG, fmt("%s: %u bins: need a multiple of 4 up to 64", what, bins));
+	if (!sums || !q || !counts) return fail(ctx, SSX_ERR_ARG, fmt("%s: sums, q and counts must not be NULL", what));
+	int rc = denoise_check_size(ctx, width, height, what);
+	if (rc) return rc;
+	if ((rc = probe_check(ctx, what, width, height, labels, regions, SS, NN, VV, UU))) return rc;
+	if ((rc = idle_on_device(ctx))) return rc;
+	ProbeBuffers d;
+	if ((rc = probe_buffers(ctx, width, height, bins, regions, &d))) return rc;
+	const size_t pixels = (size_t)width * height;
+	SSX_HIP(ctx, hipMemcpyAsync(d.sums, sums, pixels * bins * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+	SSX_HIP(ctx, hipMemcpyAsync(d.q, q, pixels * bins * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+	SSX_HIP(ctx, hipMemcpyAsync(d.counts, counts, pixels * (bins / 4u) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+	return probe_device(ctx, d, width, height, bins, labels, regions, SS, NN, VV, UU);
+}
+
+} // extern "C"

@@ -209,6 +209,18 @@ int ssh_save_npy_f32(const char* path, const float* data, const uint32_t* shape,
 	} catch (const ssx::HostError& e) { return report(e); }
 }
 
+int ssh_probe_derive(uint32_t regions, uint32_t bins, const double* SS, const uint64_t* NN, const double* VV, const uint64_t* UU, double* mean, double* std_err) {
+	if (!SS || !NN || !VV || !UU) { g_error = "NULL argument"; return SSX_ERR_ARG; }
+	ssx::probe_derive(regions, bins, SS, NN, VV, UU, mean, std_err);
+	return SSX_OK;
+}
+
+int ssh_probe_save_csv(const char* path, uint32_t regions, uint32_t bins, float lambda_min, float bin_width, const double* SS, const uint64_t* NN, const double* VV, const uint64_t* UU) {
+	if (!path || !SS || !NN || !VV || !UU) { g_error = "NULL argument"; return SSX_ERR_ARG; }
+	try { ssx::save_probe_csv(path, regions, bins, lambda_min, bin_width, SS, NN, VV, UU); return SSX_OK; }
+	catch (const ssx::HostError& e) { return report(e); }
+}
+
 int ssh_develop_weights(const char* data_dir, int observer, const ssh_spectrum_t* responses, uint32_t channels, const ssh_spectrum_t* filter, const double* gain,
                         int space, uint32_t bins, float lambda_min, float lambda_step, float* weights, double* weights64) {
 	if (!weights) { g_error = "NULL argument"; return SSX_ERR_ARG; }

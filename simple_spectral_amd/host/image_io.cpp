@@ -247,4 +247,33 @@ void save_npy_f32(const std::string& path, const float* data, const size_t* shap
 	if (std::fclose(f) != 0 || !ok) throw HostError{ SSX_ERR_DATA, "Could not write \"" + path + "\"" };
 }
 
+void probe_derive(size_t regions, size_t bins, const double* SS, const uint64_t* NN, const double* VV, const uint64_t* UU, double* mean, double* std_err) {
+	for (size_t e = 0; e < regions * bins; ++e) {
+		const double n = static_cast<double>(NN[e]);
+		if (mean) mean[e] = NN[e] ? SS[e] / n : 0.0;
+		if (std_err) std_err[e] = std::sqrt(VV[e] * n / static_cast<double>(NN[e] - UU[e])) / n;
+	}
+}
+
+void save_probe_csv(const std::string& path, size_t regions, size_t bins, float lambda_min, float bin_width, const double* SS, const uint64_t* NN, const double* VV, const uint64_t* UU) {
+	std::vector<double> mean(regions * bins), std_err(regions * bins);
+	probe_derive(regions, bins, SS, NN, VV, UU, mean.data(), std_err.data());
+	FILE* f = std::fopen(path.c_str(), "w");
+	if (!f) throw HostError{ SSX_ERR_DATA, "Could not open \"" + path + "\" for writing" };
+	auto number = [](double v) { // ("nan" whatever the sign bit: printf would write "-nan" for some)
+		char buf[40];
+		if (std::isnan(v)) return std::string("nan");
+		std::snprintf(buf, sizeof buf, "%.17g", v);
+		return std::string(buf);
+	};
+	bool ok = std::fprintf(f, "region,bin,wavelength,mean,stderr,samples,unestimated\n") > 0;
+	for (size_t r = 0; r < regions; ++r) for (size_t b = 0; b < bins; ++b) {
+		const size_t e = r * bins + b;
+		const float centre = lambda_min + (static_cast<float>(b) + 0.5f) * bin_width;
+		ok = std::fprintf(f, "%zu,%zu,%.9g,%s,%s,%llu,%llu\n", r, b, static_cast<double>(centre), number(mean[e]).c_str(), number(std_err[e]).c_str(),
+		                  static_cast<unsigned long long>(NN[e]), static_cast<unsigned long long>(UU[e])) > 0 && ok;
+	}
+	if (std::fclose(f) != 0 || !ok) throw HostError{ SSX_ERR_DATA, "Could not write \"" + path + "\"" };
+}
+
 } // namespace ssx

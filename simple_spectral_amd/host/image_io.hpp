@@ -29,4 +29,12 @@ void save_image(const std::string& path, const float* srgba, size_t width, size_
 // multiple of 64 bytes), then the values as they lie in memory.  The spectral image: shape (height, width, bins), row 0 = bottom.
 void save_npy_f32(const std::string& path, const float* data, const size_t* shape, size_t ndim);
 
+// The region probes' results for their readers (include/ssx.h "Spectral moments and region probes"), [regions][bins] each:
+//     mean = NN ? SS / NN : 0        stderr = sqrt(VV * NN / (NN - UU)) / NN   (NaN when NN - UU == 0)
+// in binary64, the operations in this order.
+void probe_derive(size_t regions, size_t bins, const double* SS, const uint64_t* NN, const double* VV, const uint64_t* UU, double* mean, double* std_err);
+// ... as a text file: the line "region,bin,wavelength,mean,stderr,samples,unestimated", then one line per region and bin in that order -- the bin's centre
+// wavelength lambda_min + (b + 0.5) * bin_width in binary32 (%.9g), mean and stderr (%.17g: they read back to the same binary64; "nan" for a NaN), the counts.
+void save_probe_csv(const std::string& path, size_t regions, size_t bins, float lambda_min, float bin_width, const double* SS, const uint64_t* NN, const double* VV, const uint64_t* UU);
+
 } // namespace ssx

@@ -28,11 +28,17 @@
 // Demodulated denoising (include/ssx.h "Demodulated denoising"): --demodulate[=K] with --spectral-denoise runs that filter on illumination -- bins, image and
 // variance divided by the first-hit albedo per bin (K x K rays per pixel, K = 1, 2 or 4; default 2) before it and multiplied by it afterwards; the albedo part of
 // --denoise-sigma is ignored then.  --albedo-output=PATH.npy (needs --spectral-bins=N) writes those albedo bins, [height][width][N] float32.
+// Error bars for the bins (include/ssx.h "Spectral moments and region probes"), all with --spectral-bins=N: --spectral-variance-output=PATH.npy writes the variance
+// of every bin mean, float32 [height][width][N] (+inf where a sub-bin holds fewer than two samples); --probe=x0,y0,x1,y1 (half-open, row 0 = bottom; up to 32 of
+// them, region r = the r-th) with --probe-output=PATH.csv writes the pooled mean spectrum of each rectangle with its standard error, one line per region and bin:
+// region, bin, centre wavelength, mean, stderr, samples, unestimated.  Not with --tile-major, --rgb, --libm=glibc-2.35 or --resume (a checkpoint does not carry
+// the second moments).
 #include "renderer.hpp"
 
 #include "checkpoint.hpp"
 #include "develop.hpp"
 
+#include <array>
 #include <chrono>
 #include <csignal>
 #include <memory>
@@ -72,7 +78,9 @@ void print_usage() {
 		"    `--develop-output=<image>` (needs `--spectral-bins=<n>`) [`--develop-observer=1931|2006`] [`--develop-filter=<name-low+step+high.csv>`] [`--develop-relight=<new.csv>`]\n"
 		"          (the image developed from the wavelength bins; with `--spectral-denoise` from the filtered bins)\n"
 		"    `--demodulate[=1|2|4]` (with `--spectral-denoise`: filter illumination -- divide by the first-hit albedo per bin, <k> x <k> rays per pixel, before; multiply after)\n"
-		"    `--albedo-output=<file.npy>` (needs `--spectral-bins=<n>`: the first-hit albedo per wavelength bin)\n");
+		"    `--albedo-output=<file.npy>` (needs `--spectral-bins=<n>`: the first-hit albedo per wavelength bin)\n"
+		"    `--spectral-variance-output=<file.npy>` (needs `--spectral-bins=<n>`: the variance of every bin mean)\n"
+		"    `--probe=<x0>,<y0>,<x1>,<y1>` (up to 32) `--probe-output=<file.csv>` (need `--spectral-bins=<n>`: each rectangle's pooled spectrum with its standard error)\n");
 }
 
 struct ArgList {
@@ -127,6 +135,10 @@ struct Progressive { // the flags of the progressive modes
 	bool demodulate = false;     // --demodulate[=K]
 	ssx::Renderer::DemodParams demod_params;
 	std::string albedo_output;   // --albedo-output: "" = none
+	std::string variance_output; // --spectral-variance-output: "" = none
+	std::vector<std::array<size_t, 4>> probes; // --probe=x0,y0,x1,y1, in the order given
+	std::string probe_output;    // --probe-output: "" = none
+	bool moments() const { return !variance_output.empty() || !probe_output.empty(); } // what needs the second moments
 };
 
 void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progressive* g) {
@@ -280,6 +292,44 @@ void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progress
 	if (filters) o->spp_per_launch = g->noise_step_given ? g->noise_step : (o->spp + 7) / 8; // at least two launches = two batches
 	if (filters && o->spp_per_launch >= o->spp) { std::fprintf(stderr, "`%s` needs `--noise-step` below the number of samples (two batches at least)!\n", flag); throw -2; }
 	if (a.take("--guides-output", "", &v)) g->guides_output = v;
+	if (a.take("--spectral-variance-output", "", &v)) g->variance_output = v;
+	while (a.take("--probe", "", &v)) {
+		std::array<size_t, 4> q{};
+		bool ok = true;
+		try {
+			size_t at = 0;
+			for (int k = 0; k < 4 && ok; ++k) {
+				const size_t comma = k < 3 ? v.find(',', at) : v.size();
+				if (comma == std::string::npos) { ok = false; break; }
+				const std::string part = v.substr(at, comma - at);
+				size_t used = 0;
+				const long long n = std::stoll(part, &used);
+				ok = used == part.size() && n >= 0;
+				q[k] = static_cast<size_t>(n); at = comma + 1;
+			}
+		} catch (...) { ok = false; }
+		if (!ok) { std::fprintf(stderr, "Invalid value for --probe (<x0>,<y0>,<x1>,<y1>)!\n"); throw -2; }
+		if (q[0] >= q[2] || q[1] >= q[3] || q[2] > o->res[0] || q[3] > o->res[1]) {
+			std::fprintf(stderr, "`--probe=%s` is empty or leaves the image: a rectangle is half-open, x0 < x1 <= width and y0 < y1 <= height (row 0 = bottom)!\n", v.c_str());
+			throw -2;
+		}
+		if (g->probes.size() == 32) { std::fprintf(stderr, "`--probe` can be given 32 times at most!\n"); throw -2; }
+		g->probes.push_back(q);
+	}
+	if (a.take("--probe-output", "", &v)) g->probe_output = v;
+	if (g->probes.empty() != g->probe_output.empty()) { std::fprintf(stderr, "`--probe=<x0>,<y0>,<x1>,<y1>` and `--probe-output=<file.csv>` need each other!\n"); throw -2; }
+	if (g->moments()) {
+		const char* const flag = !g->variance_output.empty() ? "--spectral-variance-output" : "--probe";
+		if (!g->resume.empty()) {
+			std::fprintf(stderr, "`%s` cannot be combined with `--resume`: a checkpoint does not carry the second moments of the samples already rendered!\n", flag);
+			throw -2;
+		}
+		if (!g->spectral_bins_given) { std::fprintf(stderr, "`%s` needs `--spectral-bins=<n>`: it speaks of the wavelength bins of the render!\n", flag); throw -2; }
+		if (o->tile_major || o->rgb_mode || o->libm != SSX_LIBM_BUILD) {
+			std::fprintf(stderr, "`%s` cannot be combined with `--tile-major`, `--rgb` or `--libm=glibc-2.35`: such a render has no wavelength bins!\n", flag);
+			throw -2;
+		}
+	}
 	if (a.take("--texture", "", &v)) o->texture_path = v;
 	if (a.take("--data-dir", "", &v)) o->data_dir = v;
 	if (a.args.size() > 1) {
@@ -312,7 +362,8 @@ int main(int argc, char* argv[]) {
 		ssx::Renderer renderer(options);
 		std::signal(SIGINT, on_sigint);
 		if (prog.denoise || prog.spectral_denoise) renderer.set_noise_estimate(true);
-		if (!prog.spectral_output.empty() || !prog.develop_output.empty()) renderer.set_spectral_bins(prog.spectral_bins);
+		if (!prog.spectral_output.empty() || !prog.develop_output.empty() || prog.moments()) renderer.set_spectral_bins(prog.spectral_bins);
+		if (prog.moments()) renderer.set_spectral_moments(true);
 		// what --develop-output applies, built (and refused) before the render: the observer's tables over the bins, times the filter, times the relighting gain
 		std::vector<float> develop_weights;
 		std::unique_ptr<ssx::ColorData> develop_color;
@@ -376,6 +427,8 @@ int main(int argc, char* argv[]) {
 		if (!prog.albedo_output.empty()) renderer.save_albedo_bins(prog.albedo_output, prog.spectral_bins, prog.demod_params.supersample);
 		if (prog.spectral_denoise && !prog.spectral_output.empty()) renderer.save_spectral_image(prog.spectral_output, filtered_bins);
 		else if (!prog.spectral_output.empty()) renderer.save_spectral_image(prog.spectral_output);
+		if (!prog.variance_output.empty()) renderer.save_spectral_variance(prog.variance_output);
+		if (!prog.probe_output.empty()) renderer.save_probe_csv(prog.probe_output, renderer.probe(renderer.labels_from_rects(prog.probes), prog.probes.size()));
 		if (!prog.develop_output.empty()) { // X, Y, Z from the bins, the alpha of the render's image, then the store of --output
 			const std::vector<float> xyz = renderer.develop(develop_weights.data(), 3, prog.spectral_denoise ? &prog.denoise_params : nullptr, prog.demodulate ? &prog.demod_params : nullptr);
 			const size_t pixels = options.res[0] * options.res[1];

@@ -32,7 +32,7 @@ void Framebuffer::save(const std::string& path) const { save_image(path, pixels_
 	X(create) X(destroy) X(upload_scene) X(render_start) X(render_stop) X(is_rendering) X(progress) X(render_wait) X(last_error) \
 	X(device_framebuffer) X(device_index) X(read_framebuffer) X(accumulate_peer) X(done_spp) X(done_tiles) X(reduce_rccl) \
 	X(render_continue) X(sums_export) X(sums_import) X(set_noise_estimate) X(noise_info) \
-	X(set_spectral_bins) X(spectral_read) X(spectral_import) \
+	X(set_spectral_bins) X(spectral_read) X(spectral_import) X(set_spectral_moments) X(spectral_variance) X(spectral_probe) X(probe_arrays) \
 	X(guides) X(denoise_images) X(denoise) X(denoise_channels) X(denoise_spectral) \
 	X(develop_images) X(spectral_develop) X(albedo_bins) X(denoise_spectral_demod) X(spectral_develop_demod)
 
@@ -372,6 +372,76 @@ void Renderer::save_spectral_image(const std::string& path, const std::vector<fl
 	const size_t shape[3] = { options.res[1], options.res[0], spectral_bins_ };
 	if (bins.size() != shape[0] * shape[1] * shape[2]) throw HostError{ SSX_ERR_ARG, "save_spectral_image: the array is not [height][width][bins]" };
 	save_npy_f32(path, bins.data(), shape, 3);
+}
+
+void Renderer::set_spectral_moments(bool on) {
+	wait_workers_();
+	for (ssx_ctx* c : ctxs_) check_(api_->set_spectral_moments(c, on ? 1 : 0), "ssx_set_spectral_moments", c);
+}
+
+std::vector<float> Renderer::spectral_variance() {
+	wait_workers_();
+	if (!spectral_bins_) throw HostError{ SSX_ERR_STATE, "spectral_variance: spectral output is off (set_spectral_bins)" };
+	const size_t pixels = options.res[0] * options.res[1], B = spectral_bins_;
+	std::vector<float> var(pixels * B, 0.0f), part(ctxs_.size() > 1 ? pixels * B : 0);
+	for (size_t d = 0; d < ctxs_.size(); ++d) { // every pixel from the device that owns it (merge_owned: the one merge by ownership mask)
+		ssx_spectral_info_t info{};
+		check_(api_->spectral_variance(ctxs_[d], &info, ctxs_.size() > 1 ? part.data() : var.data(), nullptr), "ssx_spectral_variance", ctxs_[d]);
+		if (ctxs_.size() > 1) merge_owned(var.data(), part.data(), B, owner_(d));
+	}
+	return var;
+}
+
+void Renderer::save_spectral_variance(const std::string& path) { save_spectral_image(path, spectral_variance()); }
+
+Renderer::Probe Renderer::probe(const std::vector<uint8_t>& labels, size_t regions) {
+	wait_workers_();
+	if (!spectral_bins_) throw HostError{ SSX_ERR_STATE, "probe: spectral output is off (set_spectral_bins)" };
+	const size_t pixels = options.res[0] * options.res[1], B = spectral_bins_;
+	if (labels.size() != pixels) throw HostError{ SSX_ERR_ARG, "probe: labels is not [height][width]" };
+	if (regions < 1 || regions > 32) throw HostError{ SSX_ERR_ARG, "probe: need 1..32 regions" };
+	Probe r;
+	r.regions = regions; r.bins = B;
+	r.SS.resize(regions * B); r.VV.resize(regions * B); r.NN.resize(regions * B); r.UU.resize(regions * B);
+	ssx_ctx* root = ctxs_[0];
+	const uint32_t r32 = static_cast<uint32_t>(regions);
+	ssx_spectral_info_t info{};
+	if (ctxs_.size() == 1) {
+		check_(api_->spectral_variance(root, &info, nullptr, nullptr), "ssx_spectral_variance", root);
+		check_(api_->spectral_probe(root, labels.data(), r32, r.SS.data(), r.NN.data(), r.VV.data(), r.UU.data()), "ssx_spectral_probe", root);
+	} else { // S, N (gather_bins_) and Q from the device that owns the pixel, bit for bit; then the pure probe on device 0
+		level_devices(); // (a stopped render: one sample count behind every pixel)
+		std::vector<double> sums, q(pixels * B, 0.0), part(pixels * B);
+		std::vector<uint32_t> counts;
+		info = gather_bins_(nullptr, &sums, &counts);
+		for (size_t d = 0; d < ctxs_.size(); ++d) {
+			ssx_spectral_info_t qi{};
+			check_(api_->spectral_variance(ctxs_[d], &qi, nullptr, part.data()), "ssx_spectral_variance", ctxs_[d]);
+			merge_owned(q.data(), part.data(), B, owner_(d));
+		}
+		check_(api_->probe_arrays(root, w32_(), h32_(), static_cast<uint32_t>(B), sums.data(), q.data(), counts.data(), labels.data(), r32, r.SS.data(), r.NN.data(), r.VV.data(), r.UU.data()),
+		       "ssx_probe_arrays", root);
+	}
+	r.lambda_min = info.lambda_min; r.bin_width = info.bin_width;
+	r.mean.resize(regions * B); r.std_err.resize(regions * B);
+	probe_derive(regions, B, r.SS.data(), r.NN.data(), r.VV.data(), r.UU.data(), r.mean.data(), r.std_err.data());
+	return r;
+}
+
+void Renderer::save_probe_csv(const std::string& path, const Probe& p) const {
+	ssx::save_probe_csv(path, p.regions, p.bins, p.lambda_min, p.bin_width, p.SS.data(), p.NN.data(), p.VV.data(), p.UU.data());
+}
+
+std::vector<uint8_t> Renderer::labels_from_rects(const std::vector<std::array<size_t, 4>>& rects) const {
+	const size_t W = options.res[0], H = options.res[1];
+	if (rects.empty() || rects.size() > 32) throw HostError{ SSX_ERR_ARG, "labels_from_rects: need 1..32 rectangles" };
+	std::vector<uint8_t> labels(W * H, 255u);
+	for (size_t r = 0; r < rects.size(); ++r) {
+		const std::array<size_t, 4>& q = rects[r];
+		if (q[0] >= q[2] || q[1] >= q[3] || q[2] > W || q[3] > H) throw HostError{ SSX_ERR_ARG, "labels_from_rects: rectangle " + std::to_string(r) + " is empty or leaves the image" };
+		for (size_t j = q[1]; j < q[3]; ++j) for (size_t i = q[0]; i < q[2]; ++i) labels[j * W + i] = static_cast<uint8_t>(r);
+	}
+	return labels;
 }
 
 Renderer::Guides Renderer::guides() {

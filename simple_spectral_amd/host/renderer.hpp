@@ -8,6 +8,7 @@
 #include "color.hpp"
 #include "scene.hpp"
 
+#include <array>
 #include <chrono>
 #include <functional>
 #include <memory>
@@ -108,6 +109,23 @@ public:
 	// [height][width][bins / 4] (optional), centres [bins] (optional): lambda_min + (b + 0.5) * bin_width in binary32.  After render_wait().
 	void spectral_image(std::vector<float>* mean, std::vector<uint32_t>* counts = nullptr, std::vector<float>* centres = nullptr);
 	void save_spectral_image(const std::string& path); // spectral_image's mean as a .npy file (image_io.hpp save_npy_f32)
+
+	// Error bars for the bins (include/ssx.h "Spectral moments and region probes").  set_spectral_moments: every device also keeps the second moments of the hero
+	// fluxes, for the renders that follow (after set_spectral_bins; not while rendering).
+	void set_spectral_moments(bool on);
+	// The variance of every bin mean, [height][width][bins] (row 0 = bottom; +inf where a sub-bin holds fewer than two samples), the devices' shares combined by
+	// ownership mask.  After render_wait() of a render that started with the moments on.
+	std::vector<float> spectral_variance();
+	void save_spectral_variance(const std::string& path); // ... as a .npy file in spectral_image's layout
+	// The pooled spectra of labelled sets of pixels: labels [height][width] (row 0 = bottom), 0..regions-1 a region (at most 32), 255 none.  SS, NN, VV, UU
+	// [regions][bins] as the header defines them, reduced on the device in a fixed order; mean and std_err derived from them (image_io.hpp probe_derive).  One
+	// device: ssx_spectral_probe.  Several: S, Q and N of the levelled devices merged by ownership, then ssx_probe_arrays on device 0 -- the same bits.
+	struct Probe { size_t regions = 0, bins = 0; float lambda_min = 0.0f, bin_width = 0.0f; std::vector<double> SS, VV, mean, std_err; std::vector<uint64_t> NN, UU; };
+	Probe probe(const std::vector<uint8_t>& labels, size_t regions);
+	void save_probe_csv(const std::string& path, const Probe& probe) const; // image_io.hpp save_probe_csv
+	// labels for probe(): region r = the half-open rectangle rects[r] = {x0, y0, x1, y1} (row 0 = bottom); where two overlap the later one wins.  Throws for an
+	// empty rectangle or one that leaves the image, and for more than 32.
+	std::vector<uint8_t> labels_from_rects(const std::vector<std::array<size_t, 4>>& rects) const;
 
 
 	// Denoising (include/ssx.h: first-hit guide buffers and the variance-guided a-trous filter).

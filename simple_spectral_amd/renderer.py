@@ -157,6 +157,62 @@ def spectral_bin_index(lambda_0, lambda_min, lambda_step, bins):
     return np.minimum((t * M).astype(np.uint32), np.uint32(bins // 4 - 1))
 
 
+PROBE_NO_REGION, PROBE_MAX_REGIONS = 255, 32   # include/ssx.h "Spectral moments and region probes"
+
+
+def labels_from_rects(res, rects):
+    """Labels for Renderer.probe: uint8 [H, W] (row 0 = bottom), region r = the half-open rectangle rects[r] = (x0, y0, x1, y1), PROBE_NO_REGION elsewhere;
+    where two overlap the later one wins.  ValueError for an empty rectangle, one that leaves the image of res = (W, H), or more than 32."""
+    W, H = res
+    if not 1 <= len(rects) <= PROBE_MAX_REGIONS:
+        raise ValueError("labels_from_rects: need 1..%d rectangles" % PROBE_MAX_REGIONS)
+    labels = np.full((H, W), PROBE_NO_REGION, dtype=np.uint8)
+    for r, (x0, y0, x1, y1) in enumerate(rects):
+        if not (0 <= x0 < x1 <= W and 0 <= y0 < y1 <= H):
+            raise ValueError("labels_from_rects: rectangle %d = %r is empty or leaves the %d x %d image" % (r, (x0, y0, x1, y1), W, H))
+        labels[y0:y1, x0:x1] = r
+    return labels
+
+
+def labels_from_prim(prim, prims):
+    """Labels for Renderer.probe from the guides' "prim" [H, W] (Renderer.guides): region r = the pixels whose first hit is primitive prims[r] (or any of
+    prims[r], when that is a sequence -- a wall made of two primitives), PROBE_NO_REGION elsewhere."""
+    prim = np.asarray(prim)
+    if not 1 <= len(prims) <= PROBE_MAX_REGIONS:
+        raise ValueError("labels_from_prim: need 1..%d regions" % PROBE_MAX_REGIONS)
+    labels = np.full(prim.shape, PROBE_NO_REGION, dtype=np.uint8)
+    for r, which in enumerate(prims):
+        labels[np.isin(prim, np.atleast_1d(which))] = r
+    return labels
+
+
+def probe_derive(SS, NN, VV, UU):
+    """ssh_probe_derive: (mean, stderr) float64 of the probes' four arrays -- mean = NN ? SS / NN : 0, stderr = sqrt(VV * NN / (NN - UU)) / NN (NaN when NN == UU)."""
+    SS, VV = np.ascontiguousarray(SS, dtype=np.float64), np.ascontiguousarray(VV, dtype=np.float64)
+    NN, UU = np.ascontiguousarray(NN, dtype=np.uint64), np.ascontiguousarray(UU, dtype=np.uint64)
+    if SS.ndim != 2 or not (SS.shape == NN.shape == VV.shape == UU.shape):
+        raise ValueError("probe_derive: SS, NN, VV, UU must all have shape [R, B]")
+    mean, err = np.zeros_like(SS), np.zeros_like(SS)
+    host = _capi.host_lib()
+    rc = host.ssh_probe_derive(SS.shape[0], SS.shape[1], SS.ctypes.data, NN.ctypes.data, VV.ctypes.data, UU.ctypes.data, mean.ctypes.data, err.ctypes.data)
+    if rc != 0:
+        raise SsxError(rc, host.ssh_last_error().decode())
+    return mean, err
+
+
+def save_probe_csv(path, lambda_min, bin_width, SS, NN, VV, UU):
+    """ssh_probe_save_csv (libssx_host.so), the writer the CLI's --probe-output uses: the line "region,bin,wavelength,mean,stderr,samples,unestimated", then one
+    line per region and bin."""
+    SS, VV = np.ascontiguousarray(SS, dtype=np.float64), np.ascontiguousarray(VV, dtype=np.float64)
+    NN, UU = np.ascontiguousarray(NN, dtype=np.uint64), np.ascontiguousarray(UU, dtype=np.uint64)
+    if SS.ndim != 2 or not (SS.shape == NN.shape == VV.shape == UU.shape):
+        raise ValueError("save_probe_csv: SS, NN, VV, UU must all have shape [R, B]")
+    host = _capi.host_lib()
+    rc = host.ssh_probe_save_csv(os.fsencode(path), SS.shape[0], SS.shape[1], C.c_float(lambda_min), C.c_float(bin_width), SS.ctypes.data, NN.ctypes.data, VV.ctypes.data, UU.ctypes.data)
+    if rc != 0:
+        raise SsxError(rc, host.ssh_last_error().decode())
+
+
 def save_npy(path, array):
     """ssh_save_npy_f32 (libssx_host.so): `array` as a float32 .npy file, the writer the CLI's --spectral-output uses."""
     a = np.ascontiguousarray(array, dtype=np.float32)
@@ -519,6 +575,66 @@ class Renderer:
         info, mean, counts, _ = self.spectral_read()
         centres = np.float32(info.lambda_min) + (np.arange(info.bins, dtype=np.float32) + np.float32(0.5)) * np.float32(info.bin_width)
         return mean, counts, centres.astype(np.float32)
+
+    # ---- error bars for the bins (include/ssx.h: second moments, variances, region probes) ----
+
+    def set_spectral_moments(self, enable=True):
+        """ssx_set_spectral_moments: keep the second moments of the hero fluxes beside the bins, for the renders that follow (after set_spectral_bins)."""
+        self._check(self._lib.ssx_set_spectral_moments(self._ctx, int(bool(enable))))
+
+    def spectral_variance(self, q=False):
+        """ssx_spectral_variance -> (SsxSpectralInfo, var float32 [H, W, B], Q float64 [H, W, B] or None): the variance of every bin mean (+inf where a sub-bin holds
+        fewer than two samples; 0 for pixels the context does not own) and the raw second moments."""
+        info = _capi.SsxSpectralInfo()
+        self._check(self._lib.ssx_spectral_variance(self._ctx, C.byref(info), None, None))
+        H, W, B = info.height, info.width, info.bins
+        var = np.zeros((H, W, B), dtype=np.float32)
+        Q = np.zeros((H, W, B), dtype=np.float64) if q else None
+        self._check(self._lib.ssx_spectral_variance(self._ctx, C.byref(info), var.ctypes.data, None if Q is None else Q.ctypes.data))
+        return info, var, Q
+
+    @staticmethod
+    def _probe_labels(labels, shape):
+        labels = np.ascontiguousarray(labels, dtype=np.uint8)
+        if labels.shape != shape:
+            raise ValueError("probe: labels must have shape [H, W] = %r" % (shape,))
+        named = labels[labels != PROBE_NO_REGION]
+        return labels, (int(named.max()) + 1 if named.size else 1)
+
+    def probe_raw(self, labels, regions=None):
+        """ssx_spectral_probe -> (SS float64, NN uint64, VV float64, UU uint64), each [R, B]: the four sums of include/ssx.h over the pixels of every region of
+        labels (uint8 [H, W], row 0 = bottom: 0..R-1 a region, 255 none; labels_from_rects, labels_from_prim).  regions None: the largest label + 1."""
+        W, H = self.options.res
+        labels, R = self._probe_labels(labels, (H, W))
+        R = R if regions is None else int(regions)
+        B = getattr(self, "_spectral_bins", 0) or 4
+        SS, VV = np.zeros((R, B), dtype=np.float64), np.zeros((R, B), dtype=np.float64)
+        NN, UU = np.zeros((R, B), dtype=np.uint64), np.zeros((R, B), dtype=np.uint64)
+        self._check(self._lib.ssx_spectral_probe(self._ctx, labels.ctypes.data, R, SS.ctypes.data, NN.ctypes.data, VV.ctypes.data, UU.ctypes.data))
+        return SS, NN, VV, UU
+
+    def probe(self, labels, regions=None):
+        """The pooled spectrum of every region of labels with its error bar -> (mean float64 [R, B], stderr float64 [R, B], samples uint64 [R, B], unestimated
+        uint64 [R, B]): the mean weights samples, not pixels; stderr is NaN where no sub-bin of the region holds two samples."""
+        SS, NN, VV, UU = self.probe_raw(labels, regions)
+        mean, err = probe_derive(SS, NN, VV, UU)
+        return mean, err, NN, UU
+
+    def probe_arrays(self, sums, q, counts, labels, regions=None):
+        """ssx_probe_arrays: probe_raw as a pure function of row-major arrays -- sums and q float64 [H, W, B], counts uint32 [H, W, B / 4] (e.g. several contexts'
+        exports merged by ownership) -> (SS, NN, VV, UU)."""
+        sums, q = np.ascontiguousarray(sums, dtype=np.float64), np.ascontiguousarray(q, dtype=np.float64)
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        if sums.ndim != 3 or q.shape != sums.shape or counts.shape != sums.shape[:2] + (sums.shape[2] // 4,) or sums.shape[2] % 4:
+            raise ValueError("probe_arrays: sums and q must have shape [H, W, B], counts [H, W, B / 4]")
+        H, W, B = sums.shape
+        labels, R = self._probe_labels(labels, (H, W))
+        R = R if regions is None else int(regions)
+        SS, VV = np.zeros((R, B), dtype=np.float64), np.zeros((R, B), dtype=np.float64)
+        NN, UU = np.zeros((R, B), dtype=np.uint64), np.zeros((R, B), dtype=np.uint64)
+        self._check(self._lib.ssx_probe_arrays(self._ctx, W, H, B, sums.ctypes.data, q.ctypes.data, counts.ctypes.data, labels.ctypes.data, R,
+                                               SS.ctypes.data, NN.ctypes.data, VV.ctypes.data, UU.ctypes.data))
+        return SS, NN, VV, UU
 
     # ---- denoising (include/ssx.h: guide buffers and the variance-guided a-trous filter) ----
 
