@@ -713,6 +713,52 @@ int ssx_spectral_probe(ssx_ctx* ctx, const uint8_t* labels /* [H][W] */, uint32_
 int ssx_probe_arrays(ssx_ctx* ctx, uint32_t width, uint32_t height, uint32_t bins, const double* sums, const double* q, const uint32_t* counts,
                      const uint8_t* labels /* [H][W] */, uint32_t regions, double* SS, uint64_t* NN, double* VV, uint64_t* UU);
 
+/* ---- Spectral noise figure: when are the bins converged (appended; same ABI version) -----------------------------------------------------------------
+ * The error bars above, reduced to one number per image or masked region, for a render loop that stops on it (the hosts' render_until_spectral) -- the analogue
+ * for the bins of the batch-means figure of component Y.  Binary64 with IEEE + - * / only, no contraction, the operations in the order written, as above: a
+ * restatement in numpy gives the same bits (tests/spectral_noise_ref.py).  Notation as above.
+ *
+ * PER PIXEL.  For an owned in-image pixel p and bin b, with m = b % M, n = N[p][m] and q as in VARIANCE OF A BIN MEAN:
+ *       n >= 2 (estimable)   :  e = (q / (double)(n-1)) / (double)n      the variance of the bin mean, before its rounding to binary32
+ *                               mu = S[p][b] / (double)n
+ *       n <  2 (unestimated) :  the pixel contributes to neither sum
+ * MASK.  uint8 [height][width], row 0 = bottom; NULL means every pixel, a nonzero value that the pixel is in.
+ * PER 8x8 TILE.  For tile t = ty * tiles_x + tx (tiles_x = (width + 7) / 8) and bin b, over the tile's in-image, in-mask pixels in ascending row, then ascending
+ *   column, every binary64 partial starting from +0.0:
+ *       EV_t[b] = sum of e  over the estimable pixels          PP_t[b] = the number of estimable pixels     (uint32)
+ *       EM_t[b] = sum of mu over the estimable pixels          PU_t[b] = the number of unestimated pixels   (uint32)
+ * IMAGE.  EV[b], EM[b], PP[b], PU[b] (the counts uint64): the tile partials added in ascending t, from +0.0 / 0.  A tile the context does not own contributes
+ *   +0.0 and 0.
+ *   THIS IS BIT-NEUTRAL, and it is why the partials are per tile -- the unit of ownership -- and not per image row, which several devices share: a partial that
+ *   started from +0.0 is never -0.0 (in round-to-nearest a sum is -0.0 only when both operands are), and x + (+0.0) == x for every x other than -0.0; a NaN
+ *   stays a NaN.  So adding a foreign tile's +0.0 changes no bit of the running total.  Several devices' tile partials are
+ *   therefore merged by ownership -- tile t from the device that owns it -- and reduced in the same ascending order by ssx_spectral_noise_reduce: the totals have
+ *   the bits of one device that owned every tile.  (Row partials would have to ADD the devices' shares of a row, in another order than one device adds them.)
+ * DERIVED BY THE HOSTS (ssh_spectral_noise_derive, include/ssx_host.h).  With P = sum over b of PP[b], U = sum over b of PU[b], EVs = sum of EV[b], EMs = sum of
+ *   EM[b], every sum over ascending b from +0.0 / 0, and mean = EMs / (double)P:
+ *       noise    = sqrt(EVs / (double)P) / mean        NaN when P == 0 or mean == 0
+ *       coverage = (double)P / (double)(P + U)         NaN when P + U == 0 (an empty mask)
+ *       rel[b]   = sqrt(EV[b] / PP[b]) / (EM[b] / PP[b])   per bin, NaN when PP[b] == 0 or the bin's mean is 0
+ *   noise is the RMS standard error of the pixels' bin means relative to the mean bin flux.  The unestimated sub-bins are taken to have the others' average
+ *   variance (the assumption behind UU above); coverage says how many there are.  A non-finite flux makes the figure NaN, and NaN <= target is false: such a
+ *   render runs to its sample cap, as does one whose mask is empty.
+ *
+ * ON THE DEVICE: ssx_spectral_noise_tiles_kernel, one workgroup per owned tile slot, reads S, Q and N where they lie -- [slot][bin][64], [slot][m][64]; no
+ * export to row-major, no temporary of the image's size: the stage buffer holds the mask and the [tiles][B] partials -- and writes the four partials at the
+ * tile's image index t; ssx_spectral_noise_reduce_kernel, one lane per (quantity, bin), walks t in ascending order.  No atomics. */
+
+/* The figure of the context's own state.  mask: [height][width] or NULL.  EV, EM (binary64), PP, PU (uint64): [B].  tEV, tEM (binary64), tPP, tPU (uint32):
+ * [tiles][B], tiles = ((width + 7) / 8) * ((height + 7) / 8), the tile partials; each of the four may be NULL.  It reads only: image, sums, bins and moments stay
+ * as they are, so an ssx_render_continue afterwards leaves the bits of a render that was never asked.  SSX_ERR_STATE, with the reasons of ssx_spectral_variance:
+ * spectral output or the moments are off, a render runs, or the context holds no valid bins or moments (after ssx_spectral_import, a changed bin count, ...).
+ * SSX_ERR_ARG: a NULL EV, EM, PP or PU. */
+int ssx_spectral_noise(ssx_ctx* ctx, const uint8_t* mask /* [H][W] or NULL */, double* EV, double* EM, uint64_t* PP, uint64_t* PU /* [B] */,
+                       double* tEV, double* tEM, uint32_t* tPP, uint32_t* tPU /* [tiles][B], each may be NULL */);
+/* IMAGE as a pure function of its arguments (no scene needed, like ssx_probe_arrays): the second kernel on uploaded tile partials -- e.g. several devices'
+ * partials merged by ownership.  SSX_ERR_ARG: bins not a multiple of 4 in 4..64, tiles outside 1..2^22, a NULL pointer.  SSX_ERR_STATE: a render runs. */
+int ssx_spectral_noise_reduce(ssx_ctx* ctx, uint32_t tiles, uint32_t bins, const double* tEV, const double* tEM, const uint32_t* tPP, const uint32_t* tPU /* [tiles][bins] */,
+                              double* EV, double* EM, uint64_t* PP, uint64_t* PU /* [bins] */);
+
 /* ---- Diagnostics for the parity tests (not part of the reference's interface) ---------------------
  * ssx_debug_eval runs one building block of the path kernel -- the same device function the kernel
  * inlines -- on n items, one per lane: `in` holds in_words 32-bit words per item, `out` receives

@@ -95,6 +95,13 @@ int ssh_probe_derive(uint32_t regions, uint32_t bins, const double* SS, const ui
  * in that order -- the bin's centre lambda_min + (b + 0.5) * bin_width in binary32 ("%.9g"), mean and stderr ("%.17g", "nan" for a NaN), NN and UU. */
 int ssh_probe_save_csv(const char* path, uint32_t regions, uint32_t bins, float lambda_min, float bin_width, const double* SS, const uint64_t* NN, const double* VV, const uint64_t* UU);
 
+/* The spectral noise figure's totals (ssx.h "Spectral noise figure"; EV, EM, PP, PU: [bins] of ssx_spectral_noise / ssx_spectral_noise_reduce) as their readers
+ * take them: *noise, *coverage and rel[bins] as DERIVED BY THE HOSTS defines them, binary64, in that order; any of the three outputs may be NULL. */
+int ssh_spectral_noise_derive(uint32_t bins, const double* EV, const double* EM, const uint64_t* PP, const uint64_t* PU, double* noise, double* coverage, double* rel);
+/* ... and as a text file, what the CLI's --spectral-noise-output writes: the line "bin,wavelength,rel,EV,EM,estimable,unestimated", then one line per bin -- the
+ * bin's centre as ssh_probe_save_csv writes it, rel, EV and EM ("%.17g", "nan" for a NaN), PP and PU. */
+int ssh_spectral_noise_save_csv(const char* path, uint32_t bins, float lambda_min, float bin_width, const double* EV, const double* EM, const uint64_t* PP, const uint64_t* PU);
+
 /* ---- Developing the spectral bins (ssx.h "Developing the spectral bins": the definitions are there, operation by operation) ----------------------------------- */
 typedef struct ssh_spectrum_t { const float* samples; uint32_t n; float low, high; } ssh_spectrum_t; /* n >= 2 uniform samples over [low, high] */
 enum { SSH_SPACE_XYZ = 0, SSH_SPACE_LRGB = 1 };

@@ -119,7 +119,8 @@ HIP_SYMBOLS = ["ssx_create", "ssx_destroy", "ssx_upload_scene", "ssx_render_star
                "ssx_develop_images", "ssx_spectral_develop",
                "ssx_albedo_bins", "ssx_denoise_spectral_demod", "ssx_spectral_develop_demod",
                "ssx_spectral_import",
-               "ssx_set_spectral_moments", "ssx_spectral_variance", "ssx_spectral_probe", "ssx_probe_arrays"]
+               "ssx_set_spectral_moments", "ssx_spectral_variance", "ssx_spectral_probe", "ssx_probe_arrays",
+               "ssx_spectral_noise", "ssx_spectral_noise_reduce"]
 (SSX_SWEEP_RCP, SSX_SWEEP_SQRT, SSX_SWEEP_INVERSESQRT, SSX_SWEEP_SIN, SSX_SWEEP_COS, SSX_SWEEP_ACOS, SSX_SWEEP_DIV_PI,
  SSX_SWEEP_RCP64, SSX_SWEEP_DIV_PAIRS, SSX_SWEEP_ACOS_SIN, SSX_SWEEP_SIN_PROOF, SSX_SWEEP_COS_PROOF, SSX_SWEEP_ACOS_PROOF) = range(1, 14)
 # ssx_debug_eval ops (include/ssx.h)
@@ -132,7 +133,7 @@ HOST_SYMBOLS = ["ssh_scene_create", "ssh_scene_create_ex", "ssh_scene_destroy", 
                 "ssh_load_png_rgb8", "ssh_free", "ssh_color_values", "ssh_last_error", "ssh_checkpoint_save", "ssh_checkpoint_load", "ssh_sums_merge", "ssh_save_npy_f32",
                 "ssh_develop_weights", "ssh_relight_gain", "ssh_emitter_spectrum",
                 "ssh_checkpoint_save_spectral", "ssh_checkpoint_load_spectral", "ssh_spectral_merge",
-                "ssh_probe_derive", "ssh_probe_save_csv"]
+                "ssh_probe_derive", "ssh_probe_save_csv", "ssh_spectral_noise_derive", "ssh_spectral_noise_save_csv"]
 
 _hip = None
 _host = None
@@ -172,6 +173,8 @@ def host_lib():
         lib.ssh_save_npy_f32.argtypes = [C.c_char_p, vp, C.POINTER(C.c_uint32), C.c_uint32]
         lib.ssh_probe_derive.argtypes = [C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp]
         lib.ssh_probe_save_csv.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_float, C.c_float, vp, vp, vp, vp]
+        lib.ssh_spectral_noise_derive.argtypes = [C.c_uint32, vp, vp, vp, vp, vp, vp, vp]
+        lib.ssh_spectral_noise_save_csv.argtypes = [C.c_char_p, C.c_uint32, C.c_float, C.c_float, vp, vp, vp, vp]
         lib.ssh_develop_weights.argtypes = [C.c_char_p, C.c_int, C.POINTER(SshSpectrum), C.c_uint32, C.POINTER(SshSpectrum), vp, C.c_int, C.c_uint32,
                                             C.c_float, C.c_float, vp, vp]
         lib.ssh_relight_gain.argtypes = [C.POINTER(SshSpectrum), C.POINTER(SshSpectrum), C.c_uint32, C.c_float, C.c_float, vp]
@@ -357,6 +360,9 @@ def hip_lib():
             lib.ssx_spectral_variance.argtypes = [vp, C.POINTER(SsxSpectralInfo), vp, vp]
             lib.ssx_spectral_probe.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, vp]
             lib.ssx_probe_arrays.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp]
+        if not override or hasattr(lib, "ssx_spectral_noise"):  # the spectral noise figure: tile partials and totals
+            lib.ssx_spectral_noise.argtypes = [vp] * 10
+            lib.ssx_spectral_noise_reduce.argtypes = [vp, C.c_uint32, C.c_uint32] + [vp] * 8
         lib.ssx_kernel_variant.argtypes = [vp]
         lib.ssx_kernel_name.argtypes = [vp]
         lib.ssx_kernel_name.restype = C.c_char_p

@@ -5,7 +5,7 @@
 // diagnostics are here; scene packing is in ssx_pack.h, RCCL in ssx_rccl.h, the pixel ownership rule in ssx_pixel_grid.h, continue / export /
 // import of the sums and the noise estimate (entry points and their kernels) in ssx_progressive.hip, the spectral output in ssx_spectral.hip,
 // the guide buffers and the denoising filter in ssx_denoise.hip, the develop of the spectral bins in ssx_develop.hip, their second moments, variances and
-// region probes in ssx_spectral_stats.hip.
+// region probes in ssx_spectral_stats.hip, the spectral noise figure in ssx_spectral_noise.hip.
 #include "ssx_kernels.hip"
 #include "ssx_debug.hip"
 
@@ -1474,3 +1474,4 @@ int ssx_kernel_info(ssx_ctx* ctx, int* vgprs, int* sgprs, int* lds_bytes, int* s
 #include "ssx_develop.hip"
 #include "ssx_demod.hip"
 #include "ssx_spectral_stats.hip"
+#include "ssx_spectral_noise.hip"

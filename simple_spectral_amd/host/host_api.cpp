@@ -221,6 +221,18 @@ int ssh_probe_save_csv(const char* path, uint32_t regions, uint32_t bins, float 
 	catch (const ssx::HostError& e) { return report(e); }
 }
 
+int ssh_spectral_noise_derive(uint32_t bins, const double* EV, const double* EM, const uint64_t* PP, const uint64_t* PU, double* noise, double* coverage, double* rel) {
+	if (!EV || !EM || !PP || !PU) { g_error = "NULL argument"; return SSX_ERR_ARG; }
+	ssx::spectral_noise_derive(bins, EV, EM, PP, PU, noise, coverage, rel);
+	return SSX_OK;
+}
+
+int ssh_spectral_noise_save_csv(const char* path, uint32_t bins, float lambda_min, float bin_width, const double* EV, const double* EM, const uint64_t* PP, const uint64_t* PU) {
+	if (!path || !EV || !EM || !PP || !PU) { g_error = "NULL argument"; return SSX_ERR_ARG; }
+	try { ssx::save_spectral_noise_csv(path, bins, lambda_min, bin_width, EV, EM, PP, PU); return SSX_OK; }
+	catch (const ssx::HostError& e) { return report(e); }
+}
+
 int ssh_develop_weights(const char* data_dir, int observer, const ssh_spectrum_t* responses, uint32_t channels, const ssh_spectrum_t* filter, const double* gain,
                         int space, uint32_t bins, float lambda_min, float lambda_step, float* weights, double* weights64) {
 	if (!weights) { g_error = "NULL argument"; return SSX_ERR_ARG; }

@@ -8,6 +8,7 @@
 #include <cstring>
 #include <fstream>
 #include <iterator>
+#include <limits>
 
 namespace ssx {
 namespace {
@@ -255,23 +256,56 @@ void probe_derive(size_t regions, size_t bins, const double* SS, const uint64_t*
 	}
 }
 
+namespace {
+std::string csv_number(double v) { // ("nan" whatever the sign bit: printf would write "-nan" for some)
+	char buf[40];
+	if (std::isnan(v)) return std::string("nan");
+	std::snprintf(buf, sizeof buf, "%.17g", v);
+	return std::string(buf);
+}
+} // namespace
+
 void save_probe_csv(const std::string& path, size_t regions, size_t bins, float lambda_min, float bin_width, const double* SS, const uint64_t* NN, const double* VV, const uint64_t* UU) {
 	std::vector<double> mean(regions * bins), std_err(regions * bins);
 	probe_derive(regions, bins, SS, NN, VV, UU, mean.data(), std_err.data());
 	FILE* f = std::fopen(path.c_str(), "w");
 	if (!f) throw HostError{ SSX_ERR_DATA, "Could not open \"" + path + "\" for writing" };
-	auto number = [](double v) { // ("nan" whatever the sign bit: printf would write "-nan" for some)
-		char buf[40];
-		if (std::isnan(v)) return std::string("nan");
-		std::snprintf(buf, sizeof buf, "%.17g", v);
-		return std::string(buf);
-	};
+	const auto number = csv_number;
 	bool ok = std::fprintf(f, "region,bin,wavelength,mean,stderr,samples,unestimated\n") > 0;
 	for (size_t r = 0; r < regions; ++r) for (size_t b = 0; b < bins; ++b) {
 		const size_t e = r * bins + b;
 		const float centre = lambda_min + (static_cast<float>(b) + 0.5f) * bin_width;
 		ok = std::fprintf(f, "%zu,%zu,%.9g,%s,%s,%llu,%llu\n", r, b, static_cast<double>(centre), number(mean[e]).c_str(), number(std_err[e]).c_str(),
 		                  static_cast<unsigned long long>(NN[e]), static_cast<unsigned long long>(UU[e])) > 0 && ok;
+	}
+	if (std::fclose(f) != 0 || !ok) throw HostError{ SSX_ERR_DATA, "Could not write \"" + path + "\"" };
+}
+
+void spectral_noise_derive(size_t bins, const double* EV, const double* EM, const uint64_t* PP, const uint64_t* PU, double* noise, double* coverage, double* rel) {
+	const double nan = std::numeric_limits<double>::quiet_NaN();
+	double evs = 0.0, ems = 0.0;
+	uint64_t P = 0, U = 0;
+	for (size_t b = 0; b < bins; ++b) {
+		evs += EV[b]; ems += EM[b]; P += PP[b]; U += PU[b];
+		if (!rel) continue;
+		const double n = static_cast<double>(PP[b]), mean = EM[b] / n;
+		rel[b] = (PP[b] == 0 || mean == 0.0) ? nan : std::sqrt(EV[b] / n) / mean;
+	}
+	const double p = static_cast<double>(P), mean = ems / p;
+	if (noise) *noise = (P == 0 || mean == 0.0) ? nan : std::sqrt(evs / p) / mean;
+	if (coverage) *coverage = (P + U == 0) ? nan : p / static_cast<double>(P + U);
+}
+
+void save_spectral_noise_csv(const std::string& path, size_t bins, float lambda_min, float bin_width, const double* EV, const double* EM, const uint64_t* PP, const uint64_t* PU) {
+	std::vector<double> rel(bins);
+	spectral_noise_derive(bins, EV, EM, PP, PU, nullptr, nullptr, rel.data());
+	FILE* f = std::fopen(path.c_str(), "w");
+	if (!f) throw HostError{ SSX_ERR_DATA, "Could not open \"" + path + "\" for writing" };
+	bool ok = std::fprintf(f, "bin,wavelength,rel,EV,EM,estimable,unestimated\n") > 0;
+	for (size_t b = 0; b < bins; ++b) {
+		const float centre = lambda_min + (static_cast<float>(b) + 0.5f) * bin_width;
+		ok = std::fprintf(f, "%zu,%.9g,%s,%s,%s,%llu,%llu\n", b, static_cast<double>(centre), csv_number(rel[b]).c_str(), csv_number(EV[b]).c_str(), csv_number(EM[b]).c_str(),
+		                  static_cast<unsigned long long>(PP[b]), static_cast<unsigned long long>(PU[b])) > 0 && ok;
 	}
 	if (std::fclose(f) != 0 || !ok) throw HostError{ SSX_ERR_DATA, "Could not write \"" + path + "\"" };
 }

@@ -37,4 +37,14 @@ void probe_derive(size_t regions, size_t bins, const double* SS, const uint64_t*
 // wavelength lambda_min + (b + 0.5) * bin_width in binary32 (%.9g), mean and stderr (%.17g: they read back to the same binary64; "nan" for a NaN), the counts.
 void save_probe_csv(const std::string& path, size_t regions, size_t bins, float lambda_min, float bin_width, const double* SS, const uint64_t* NN, const double* VV, const uint64_t* UU);
 
+// The spectral noise figure for its readers (include/ssx.h "Spectral noise figure"), from the totals EV, EM, PP, PU [bins]: with P, U, EVs, EMs their sums over
+// ascending b and mean = EMs / P,
+//     noise = sqrt(EVs / P) / mean  (NaN when P == 0 or mean == 0)     coverage = P / (P + U)  (NaN when P + U == 0)
+//     rel[b] = sqrt(EV[b] / PP[b]) / (EM[b] / PP[b])                    (NaN when PP[b] == 0 or the bin's mean is 0)
+// in binary64, the operations in this order; any output may be NULL.
+void spectral_noise_derive(size_t bins, const double* EV, const double* EM, const uint64_t* PP, const uint64_t* PU, double* noise, double* coverage, double* rel);
+// ... as a text file: the line "bin,wavelength,rel,EV,EM,estimable,unestimated", then one line per bin -- the bin's centre wavelength as save_probe_csv writes it,
+// rel, EV and EM (%.17g: they read back to the same binary64; "nan" for a NaN), PP and PU.
+void save_spectral_noise_csv(const std::string& path, size_t bins, float lambda_min, float bin_width, const double* EV, const double* EM, const uint64_t* PP, const uint64_t* PU);
+
 } // namespace ssx

@@ -33,6 +33,12 @@
 // them, region r = the r-th) with --probe-output=PATH.csv writes the pooled mean spectrum of each rectangle with its standard error, one line per region and bin:
 // region, bin, centre wavelength, mean, stderr, samples, unestimated.  Not with --tile-major, --rgb, --libm=glibc-2.35 or --resume (a checkpoint does not carry
 // the second moments).
+// A spectral stopping rule (include/ssx.h "Spectral noise figure"): --spectral-noise-target=X with --spectral-bins=N and --max-samples=K renders --noise-step
+// samples per pixel at a time until the RMS standard error of the pixels' bin means, relative to the mean bin flux, is at most X and the share of sub-bins that
+// hold two samples is at least --spectral-noise-coverage=C (default 0.99; 1.0 is legal but slow to reach), or K samples are done.  --spectral-noise-region=
+// x0,y0,x1,y1 (half-open, row 0 = bottom, repeatable) restricts the figure to the union of the rectangles; --spectral-noise-output=PATH.csv writes it per bin:
+// bin, centre wavelength, rel, EV, EM, estimable, unestimated.  One stopping rule per run: not with --noise-target; not with --resume, --tile-major, --rgb or
+// --libm=glibc-2.35.
 #include "renderer.hpp"
 
 #include "checkpoint.hpp"
@@ -80,7 +86,9 @@ void print_usage() {
 		"    `--demodulate[=1|2|4]` (with `--spectral-denoise`: filter illumination -- divide by the first-hit albedo per bin, <k> x <k> rays per pixel, before; multiply after)\n"
 		"    `--albedo-output=<file.npy>` (needs `--spectral-bins=<n>`: the first-hit albedo per wavelength bin)\n"
 		"    `--spectral-variance-output=<file.npy>` (needs `--spectral-bins=<n>`: the variance of every bin mean)\n"
-		"    `--probe=<x0>,<y0>,<x1>,<y1>` (up to 32) `--probe-output=<file.csv>` (need `--spectral-bins=<n>`: each rectangle's pooled spectrum with its standard error)\n");
+		"    `--probe=<x0>,<y0>,<x1>,<y1>` (up to 32) `--probe-output=<file.csv>` (need `--spectral-bins=<n>`: each rectangle's pooled spectrum with its standard error)\n"
+		"    `--spectral-noise-target=<x> --spectral-bins=<n> --max-samples=<k> [--noise-step=<s>]` [`--spectral-noise-coverage=<c>`; default 0.99]\n"
+		"          [`--spectral-noise-region=<x0>,<y0>,<x1>,<y1>` ...] [`--spectral-noise-output=<file.csv>`] (render until the wavelength bins are converged)\n");
 }
 
 struct ArgList {
@@ -118,6 +126,30 @@ unsigned to_pos(const std::string& s) { // Str::to_pos (src/util/string.hpp:43-5
 	return static_cast<unsigned>(v);
 }
 
+// `--probe` and `--spectral-noise-region`: a half-open rectangle x0,y0,x1,y1 inside a width x height image
+std::array<size_t, 4> to_rect(const char* flag, const std::string& v, size_t width, size_t height) {
+	std::array<size_t, 4> q{};
+	bool ok = true;
+	try {
+		size_t at = 0;
+		for (int k = 0; k < 4 && ok; ++k) {
+			const size_t comma = k < 3 ? v.find(',', at) : v.size();
+			if (comma == std::string::npos) { ok = false; break; }
+			const std::string part = v.substr(at, comma - at);
+			size_t used = 0;
+			const long long n = std::stoll(part, &used);
+			ok = used == part.size() && n >= 0;
+			q[k] = static_cast<size_t>(n); at = comma + 1;
+		}
+	} catch (...) { ok = false; }
+	if (!ok) { std::fprintf(stderr, "Invalid value for %s (<x0>,<y0>,<x1>,<y1>)!\n", flag); throw -2; }
+	if (q[0] >= q[2] || q[1] >= q[3] || q[2] > width || q[3] > height) {
+		std::fprintf(stderr, "`%s=%s` is empty or leaves the image: a rectangle is half-open, x0 < x1 <= width and y0 < y1 <= height (row 0 = bottom)!\n", flag, v.c_str());
+		throw -2;
+	}
+	return q;
+}
+
 struct Progressive { // the flags of the progressive modes
 	std::string checkpoint, resume;
 	double noise_target = -1.0; // < 0: none
@@ -139,6 +171,10 @@ struct Progressive { // the flags of the progressive modes
 	std::vector<std::array<size_t, 4>> probes; // --probe=x0,y0,x1,y1, in the order given
 	std::string probe_output;    // --probe-output: "" = none
 	bool moments() const { return !variance_output.empty() || !probe_output.empty(); } // what needs the second moments
+	double spectral_noise_target = -1.0;   // --spectral-noise-target: < 0 = none
+	double spectral_noise_coverage = 0.99; // --spectral-noise-coverage
+	std::vector<std::array<size_t, 4>> spectral_noise_regions; // --spectral-noise-region=x0,y0,x1,y1: the mask is their union; none = every pixel
+	std::string spectral_noise_output;     // --spectral-noise-output: "" = none
 };
 
 void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progressive* g) {
@@ -294,25 +330,7 @@ void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progress
 	if (a.take("--guides-output", "", &v)) g->guides_output = v;
 	if (a.take("--spectral-variance-output", "", &v)) g->variance_output = v;
 	while (a.take("--probe", "", &v)) {
-		std::array<size_t, 4> q{};
-		bool ok = true;
-		try {
-			size_t at = 0;
-			for (int k = 0; k < 4 && ok; ++k) {
-				const size_t comma = k < 3 ? v.find(',', at) : v.size();
-				if (comma == std::string::npos) { ok = false; break; }
-				const std::string part = v.substr(at, comma - at);
-				size_t used = 0;
-				const long long n = std::stoll(part, &used);
-				ok = used == part.size() && n >= 0;
-				q[k] = static_cast<size_t>(n); at = comma + 1;
-			}
-		} catch (...) { ok = false; }
-		if (!ok) { std::fprintf(stderr, "Invalid value for --probe (<x0>,<y0>,<x1>,<y1>)!\n"); throw -2; }
-		if (q[0] >= q[2] || q[1] >= q[3] || q[2] > o->res[0] || q[3] > o->res[1]) {
-			std::fprintf(stderr, "`--probe=%s` is empty or leaves the image: a rectangle is half-open, x0 < x1 <= width and y0 < y1 <= height (row 0 = bottom)!\n", v.c_str());
-			throw -2;
-		}
+		const std::array<size_t, 4> q = to_rect("--probe", v, o->res[0], o->res[1]);
 		if (g->probes.size() == 32) { std::fprintf(stderr, "`--probe` can be given 32 times at most!\n"); throw -2; }
 		g->probes.push_back(q);
 	}
@@ -325,6 +343,38 @@ void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progress
 			throw -2;
 		}
 		if (!g->spectral_bins_given) { std::fprintf(stderr, "`%s` needs `--spectral-bins=<n>`: it speaks of the wavelength bins of the render!\n", flag); throw -2; }
+		if (o->tile_major || o->rgb_mode || o->libm != SSX_LIBM_BUILD) {
+			std::fprintf(stderr, "`%s` cannot be combined with `--tile-major`, `--rgb` or `--libm=glibc-2.35`: such a render has no wavelength bins!\n", flag);
+			throw -2;
+		}
+	}
+	if (a.take("--spectral-noise-target", "", &v)) {
+		try { size_t used = 0; g->spectral_noise_target = std::stod(v, &used); if (used != v.size() || !(g->spectral_noise_target >= 0.0)) throw -2; }
+		catch (...) { std::fprintf(stderr, "Invalid value for --spectral-noise-target (a number >= 0)!\n"); throw -2; }
+	}
+	const bool spectral_stop = g->spectral_noise_target >= 0.0;
+	if (a.take("--spectral-noise-coverage", "", &v)) {
+		try { size_t used = 0; g->spectral_noise_coverage = std::stod(v, &used); if (used != v.size() || !(g->spectral_noise_coverage >= 0.0 && g->spectral_noise_coverage <= 1.0)) throw -2; }
+		catch (...) { std::fprintf(stderr, "Invalid value for --spectral-noise-coverage (0..1)!\n"); throw -2; }
+		if (!spectral_stop) { std::fprintf(stderr, "`--spectral-noise-coverage` needs `--spectral-noise-target=<x>`: it is part of that stopping rule!\n"); throw -2; }
+	}
+	while (a.take("--spectral-noise-region", "", &v)) {
+		if (!spectral_stop) { std::fprintf(stderr, "`--spectral-noise-region` needs `--spectral-noise-target=<x>`: it is part of that stopping rule!\n"); throw -2; }
+		g->spectral_noise_regions.push_back(to_rect("--spectral-noise-region", v, o->res[0], o->res[1]));
+	}
+	if (a.take("--spectral-noise-output", "", &v)) {
+		if (!spectral_stop) { std::fprintf(stderr, "`--spectral-noise-output` needs `--spectral-noise-target=<x>`: it writes the figure that rule stopped on!\n"); throw -2; }
+		g->spectral_noise_output = v;
+	}
+	if (spectral_stop) {
+		const char* const flag = "--spectral-noise-target";
+		if (g->noise_target >= 0.0) { std::fprintf(stderr, "`%s` cannot be combined with `--noise-target`: one stopping rule per run!\n", flag); throw -2; }
+		if (!g->resume.empty()) {
+			std::fprintf(stderr, "`%s` cannot be combined with `--resume`: a checkpoint does not carry the second moments of the samples already rendered!\n", flag);
+			throw -2;
+		}
+		if (!g->spectral_bins_given) { std::fprintf(stderr, "`%s` needs `--spectral-bins=<n>`: it speaks of the wavelength bins of the render!\n", flag); throw -2; }
+		if (g->max_samples == 0) { std::fprintf(stderr, "`%s` needs `--max-samples=<n>`!\n", flag); throw -2; }
 		if (o->tile_major || o->rgb_mode || o->libm != SSX_LIBM_BUILD) {
 			std::fprintf(stderr, "`%s` cannot be combined with `--tile-major`, `--rgb` or `--libm=glibc-2.35`: such a render has no wavelength bins!\n", flag);
 			throw -2;
@@ -362,7 +412,8 @@ int main(int argc, char* argv[]) {
 		ssx::Renderer renderer(options);
 		std::signal(SIGINT, on_sigint);
 		if (prog.denoise || prog.spectral_denoise) renderer.set_noise_estimate(true);
-		if (!prog.spectral_output.empty() || !prog.develop_output.empty() || prog.moments()) renderer.set_spectral_bins(prog.spectral_bins);
+		const bool spectral_stop = prog.spectral_noise_target >= 0.0;
+		if (!prog.spectral_output.empty() || !prog.develop_output.empty() || prog.moments() || spectral_stop) renderer.set_spectral_bins(prog.spectral_bins);
 		if (prog.moments()) renderer.set_spectral_moments(true);
 		// what --develop-output applies, built (and refused) before the render: the observer's tables over the bins, times the filter, times the relighting gain
 		std::vector<float> develop_weights;
@@ -393,6 +444,16 @@ int main(int argc, char* argv[]) {
 				return true;
 			});
 			std::fprintf(stderr, "Noise %.6g after %zu samples per pixel (target %.6g).\n", r.second, r.first, prog.noise_target);
+		} else if (spectral_stop) {
+			const std::vector<uint8_t> mask = prog.spectral_noise_regions.empty() ? std::vector<uint8_t>() : renderer.mask_from_rects(prog.spectral_noise_regions);
+			const auto r = renderer.render_until_spectral(prog.spectral_noise_target, prog.noise_step, prog.max_samples, mask, prog.spectral_noise_coverage, [&]() {
+				renderer.print_progress();
+				if (!g_abort || stop_sent) return false;
+				stop_sent = true; std::fprintf(stderr, "\nAborting: saving the partial render ...\n");
+				return true;
+			});
+			std::fprintf(stderr, "Spectral noise %.6g (coverage %.6g) after %zu samples per pixel (target %.6g).\n", r.noise, r.coverage, r.spp, prog.spectral_noise_target);
+			if (!prog.spectral_noise_output.empty()) renderer.save_spectral_noise_csv(prog.spectral_noise_output, renderer.spectral_noise(mask));
 		} else {
 			if (!prog.resume.empty()) {
 				try {

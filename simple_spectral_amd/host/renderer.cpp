@@ -32,7 +32,7 @@ void Framebuffer::save(const std::string& path) const { save_image(path, pixels_
 	X(create) X(destroy) X(upload_scene) X(render_start) X(render_stop) X(is_rendering) X(progress) X(render_wait) X(last_error) \
 	X(device_framebuffer) X(device_index) X(read_framebuffer) X(accumulate_peer) X(done_spp) X(done_tiles) X(reduce_rccl) \
 	X(render_continue) X(sums_export) X(sums_import) X(set_noise_estimate) X(noise_info) \
-	X(set_spectral_bins) X(spectral_read) X(spectral_import) X(set_spectral_moments) X(spectral_variance) X(spectral_probe) X(probe_arrays) \
+	X(set_spectral_bins) X(spectral_read) X(spectral_import) X(set_spectral_moments) X(spectral_variance) X(spectral_probe) X(probe_arrays) X(spectral_noise) X(spectral_noise_reduce) \
 	X(guides) X(denoise_images) X(denoise) X(denoise_channels) X(denoise_spectral) \
 	X(develop_images) X(spectral_develop) X(albedo_bins) X(denoise_spectral_demod) X(spectral_develop_demod)
 
@@ -442,6 +442,78 @@ std::vector<uint8_t> Renderer::labels_from_rects(const std::vector<std::array<si
 		for (size_t j = q[1]; j < q[3]; ++j) for (size_t i = q[0]; i < q[2]; ++i) labels[j * W + i] = static_cast<uint8_t>(r);
 	}
 	return labels;
+}
+
+Renderer::SpectralNoise Renderer::spectral_noise(const std::vector<uint8_t>& mask) {
+	wait_workers_();
+	if (!spectral_bins_) throw HostError{ SSX_ERR_STATE, "spectral_noise: spectral output is off (set_spectral_bins)" };
+	const size_t W = options.res[0], H = options.res[1], B = spectral_bins_, tiles_x = (W + 7) / 8, tiles = tiles_x * ((H + 7) / 8);
+	if (!mask.empty() && mask.size() != W * H) throw HostError{ SSX_ERR_ARG, "spectral_noise: mask is not [height][width]" };
+	const uint8_t* const m = mask.empty() ? nullptr : mask.data();
+	SpectralNoise r;
+	r.bins = B;
+	r.EV.resize(B); r.EM.resize(B); r.PP.resize(B); r.PU.resize(B); r.rel.resize(B);
+	ssx_ctx* root = ctxs_[0];
+	if (ctxs_.size() == 1) {
+		check_(api_->spectral_noise(root, m, r.EV.data(), r.EM.data(), r.PP.data(), r.PU.data(), nullptr, nullptr, nullptr, nullptr), "ssx_spectral_noise", root);
+	} else { // every tile's partials from the device that owns the tile, bit for bit; then the pure reduction on device 0
+		level_devices(); // (a stopped render: one sample count behind every pixel)
+		std::vector<double> tEV(tiles * B, 0.0), tEM(tiles * B, 0.0), pEV(tiles * B), pEM(tiles * B);
+		std::vector<uint32_t> tPP(tiles * B, 0u), tPU(tiles * B, 0u), pPP(tiles * B), pPU(tiles * B);
+		for (size_t d = 0; d < ctxs_.size(); ++d) {
+			check_(api_->spectral_noise(ctxs_[d], m, r.EV.data(), r.EM.data(), r.PP.data(), r.PU.data(), pEV.data(), pEM.data(), pPP.data(), pPU.data()), "ssx_spectral_noise", ctxs_[d]);
+			const ssx_sums_info_t owner = owner_(d);
+			for (size_t t = 0; t < tiles; ++t) {
+				if (!sums_owner(owner, (t % tiles_x) * 8, (t / tiles_x) * 8)) continue;
+				std::memcpy(&tEV[t * B], &pEV[t * B], B * sizeof(double)); std::memcpy(&tEM[t * B], &pEM[t * B], B * sizeof(double));
+				std::memcpy(&tPP[t * B], &pPP[t * B], B * sizeof(uint32_t)); std::memcpy(&tPU[t * B], &pPU[t * B], B * sizeof(uint32_t));
+			}
+		}
+		check_(api_->spectral_noise_reduce(root, static_cast<uint32_t>(tiles), static_cast<uint32_t>(B), tEV.data(), tEM.data(), tPP.data(), tPU.data(),
+		                                   r.EV.data(), r.EM.data(), r.PP.data(), r.PU.data()), "ssx_spectral_noise_reduce", root);
+	}
+	ssx_spectral_info_t info{};
+	check_(api_->spectral_variance(root, &info, nullptr, nullptr), "ssx_spectral_variance", root);
+	r.lambda_min = info.lambda_min; r.bin_width = info.bin_width;
+	spectral_noise_derive(B, r.EV.data(), r.EM.data(), r.PP.data(), r.PU.data(), &r.noise, &r.coverage, r.rel.data());
+	return r;
+}
+
+void Renderer::save_spectral_noise_csv(const std::string& path, const SpectralNoise& n) const {
+	ssx::save_spectral_noise_csv(path, n.bins, n.lambda_min, n.bin_width, n.EV.data(), n.EM.data(), n.PP.data(), n.PU.data());
+}
+
+std::vector<uint8_t> Renderer::mask_from_rects(const std::vector<std::array<size_t, 4>>& rects) const {
+	const size_t W = options.res[0], H = options.res[1];
+	std::vector<uint8_t> mask(W * H, 0u);
+	for (size_t r = 0; r < rects.size(); ++r) {
+		const std::array<size_t, 4>& q = rects[r];
+		if (q[0] >= q[2] || q[1] >= q[3] || q[2] > W || q[3] > H) throw HostError{ SSX_ERR_ARG, "mask_from_rects: rectangle " + std::to_string(r) + " is empty or leaves the image" };
+		for (size_t j = q[1]; j < q[3]; ++j) for (size_t i = q[0]; i < q[2]; ++i) mask[j * W + i] = 1u;
+	}
+	return mask;
+}
+
+Renderer::UntilSpectral Renderer::render_until_spectral(double target, size_t step, size_t max_spp, const std::vector<uint8_t>& mask, double min_coverage, const std::function<bool()>& tick) {
+	if (step == 0 || max_spp == 0) throw HostError{ SSX_ERR_ARG, "render_until_spectral: step and max_spp must be positive" };
+	if (!spectral_bins_) throw HostError{ SSX_ERR_STATE, "render_until_spectral: spectral output is off (set_spectral_bins)" };
+	if (!mask.empty() && mask.size() != options.res[0] * options.res[1]) throw HostError{ SSX_ERR_ARG, "render_until_spectral: mask is not [height][width]" };
+	set_spectral_moments(true);
+	UntilSpectral r;
+	r.noise = r.coverage = NAN;
+	bool stopped = false;
+	for (size_t n = 0;; ++n) {
+		if (n == 0) start_(step, step); else render_continue(step);
+		while (tick && is_rendering()) {
+			if (!stopped && tick()) { render_stop(); stopped = true; }
+			std::this_thread::sleep_for(std::chrono::milliseconds(10));
+		}
+		wait_workers_();
+		if (!stopped) { const SpectralNoise now = spectral_noise(mask); r.noise = now.noise; r.coverage = now.coverage; }
+		if (stopped || (r.noise <= target && r.coverage >= min_coverage) || done_spp() >= max_spp) break;
+	}
+	r.spp = done_spp();
+	return r;
 }
 
 Renderer::Guides Renderer::guides() {

@@ -127,6 +127,24 @@ public:
 	// empty rectangle or one that leaves the image, and for more than 32.
 	std::vector<uint8_t> labels_from_rects(const std::vector<std::array<size_t, 4>>& rects) const;
 
+	// The spectral noise figure (include/ssx.h "Spectral noise figure"): mask [height][width] (row 0 = bottom; nonzero = in), empty = every pixel.  EV, EM, PP, PU
+	// [bins] as the header defines them, reduced on the device in a fixed order; noise, coverage and rel derived from them (image_io.hpp spectral_noise_derive).
+	// One device: ssx_spectral_noise.  Several: level_devices(), every device's tile partials merged by ownership, then ssx_spectral_noise_reduce on device 0 --
+	// the same bits.  After render_wait() of a render that started with the moments on.
+	struct SpectralNoise { size_t bins = 0; float lambda_min = 0.0f, bin_width = 0.0f; std::vector<double> EV, EM, rel; std::vector<uint64_t> PP, PU; double noise = 0.0, coverage = 0.0; };
+	SpectralNoise spectral_noise(const std::vector<uint8_t>& mask = {});
+	void save_spectral_noise_csv(const std::string& path, const SpectralNoise& n) const; // image_io.hpp save_spectral_noise_csv
+	// a mask for spectral_noise(): the union of the half-open rectangles {x0, y0, x1, y1} (row 0 = bottom).  Throws for an empty one or one that leaves the image.
+	std::vector<uint8_t> mask_from_rects(const std::vector<std::array<size_t, 4>>& rects) const;
+	// Renders until the bins are converged: switches the moments on (spectral output must be on: set_spectral_bins), starts with `step` samples per pixel and
+	// continues `step` at a time, reads spectral_noise(mask) after EVERY step, the first included, and stops at the first noise <= target && coverage >=
+	// min_coverage, at max_spp, or when tick() returns true (render_until's tick).  min_coverage is the user's parameter, not a tolerance: it keeps a render with
+	// many bins from stopping on the few sub-bins that happen to hold two samples after one step; 1.0 is legal but slow to reach -- it needs two samples in every
+	// sub-bin of every pixel.  A NaN figure (a non-finite flux, an empty mask) never stops the render: it runs to max_spp.  Returns the count and the last
+	// figure read (NaN when the first step was stopped by tick).  Deterministic: the decision reads only S, Q and N.
+	struct UntilSpectral { size_t spp = 0; double noise = 0.0, coverage = 0.0; };
+	UntilSpectral render_until_spectral(double target, size_t step, size_t max_spp, const std::vector<uint8_t>& mask = {}, double min_coverage = 0.99, const std::function<bool()>& tick = {});
+
 
 	// Denoising (include/ssx.h: first-hit guide buffers and the variance-guided a-trous filter).
 	struct Guides { std::vector<uint32_t> prim; std::vector<float> depth, normal, albedo; }; // [height][width] x {1, 1, 3, 4}, row 0 = bottom; prim 0xFFFFFFFF = miss

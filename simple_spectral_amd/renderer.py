@@ -213,6 +213,36 @@ def save_probe_csv(path, lambda_min, bin_width, SS, NN, VV, UU):
         raise SsxError(rc, host.ssh_last_error().decode())
 
 
+def _noise_totals(EV, EM, PP, PU, what):
+    EV, EM = np.ascontiguousarray(EV, dtype=np.float64), np.ascontiguousarray(EM, dtype=np.float64)
+    PP, PU = np.ascontiguousarray(PP, dtype=np.uint64), np.ascontiguousarray(PU, dtype=np.uint64)
+    if EV.ndim != 1 or not (EV.shape == EM.shape == PP.shape == PU.shape):
+        raise ValueError("%s: EV, EM, PP, PU must all have shape [B]" % what)
+    return EV, EM, PP, PU
+
+
+def spectral_noise_derive(EV, EM, PP, PU):
+    """ssh_spectral_noise_derive: (noise, coverage, rel float64 [B]) of the spectral noise figure's totals (include/ssx.h "Spectral noise figure") -- noise =
+    sqrt(sum EV / P) / (sum EM / P), coverage = P / (P + U), rel[b] = sqrt(EV[b] / PP[b]) / (EM[b] / PP[b]); NaN where nothing is estimable or a mean is 0."""
+    EV, EM, PP, PU = _noise_totals(EV, EM, PP, PU, "spectral_noise_derive")
+    noise, coverage, rel = C.c_double(), C.c_double(), np.zeros_like(EV)
+    host = _capi.host_lib()
+    rc = host.ssh_spectral_noise_derive(EV.shape[0], EV.ctypes.data, EM.ctypes.data, PP.ctypes.data, PU.ctypes.data, C.addressof(noise), C.addressof(coverage), rel.ctypes.data)
+    if rc != 0:
+        raise SsxError(rc, host.ssh_last_error().decode())
+    return noise.value, coverage.value, rel
+
+
+def save_spectral_noise_csv(path, lambda_min, bin_width, EV, EM, PP, PU):
+    """ssh_spectral_noise_save_csv (libssx_host.so), the writer the CLI's --spectral-noise-output uses: the line "bin,wavelength,rel,EV,EM,estimable,unestimated",
+    then one line per bin."""
+    EV, EM, PP, PU = _noise_totals(EV, EM, PP, PU, "save_spectral_noise_csv")
+    host = _capi.host_lib()
+    rc = host.ssh_spectral_noise_save_csv(os.fsencode(path), EV.shape[0], C.c_float(lambda_min), C.c_float(bin_width), EV.ctypes.data, EM.ctypes.data, PP.ctypes.data, PU.ctypes.data)
+    if rc != 0:
+        raise SsxError(rc, host.ssh_last_error().decode())
+
+
 def save_npy(path, array):
     """ssh_save_npy_f32 (libssx_host.so): `array` as a float32 .npy file, the writer the CLI's --spectral-output uses."""
     a = np.ascontiguousarray(array, dtype=np.float32)
@@ -635,6 +665,69 @@ class Renderer:
         self._check(self._lib.ssx_probe_arrays(self._ctx, W, H, B, sums.ctypes.data, q.ctypes.data, counts.ctypes.data, labels.ctypes.data, R,
                                                SS.ctypes.data, NN.ctypes.data, VV.ctypes.data, UU.ctypes.data))
         return SS, NN, VV, UU
+
+    # ---- the spectral noise figure and the render loop that stops on it (include/ssx.h "Spectral noise figure") ----
+
+    def _noise_mask(self, mask):
+        if mask is None:
+            return None
+        W, H = self.options.res
+        mask = np.asarray(mask)
+        mask = np.ascontiguousarray(mask if mask.dtype == np.uint8 else mask != 0, dtype=np.uint8)   # (uint8 goes to the library as it is: any nonzero value is in)
+        if mask.shape != (H, W):
+            raise ValueError("spectral_noise: mask must have shape [H, W] = %r" % ((H, W),))
+        return mask
+
+    def spectral_noise_raw(self, mask=None):
+        """ssx_spectral_noise -> ((EV float64, EM float64, PP uint64, PU uint64), each [B], (tEV float64, tEM float64, tPP uint32, tPU uint32), each [tiles, B]):
+        the totals and the per-tile partials (tile t = ty * tiles_x + tx; +0.0 and 0 for tiles the context does not own).  mask: [H, W] (row 0 = bottom, nonzero =
+        in) or None for every pixel."""
+        W, H = self.options.res
+        mask = self._noise_mask(mask)
+        B = getattr(self, "_spectral_bins", 0) or 4
+        tiles = ((W + 7) // 8) * ((H + 7) // 8)
+        EV, EM, PP, PU = np.zeros(B), np.zeros(B), np.zeros(B, dtype=np.uint64), np.zeros(B, dtype=np.uint64)
+        tEV, tEM = np.zeros((tiles, B)), np.zeros((tiles, B))
+        tPP, tPU = np.zeros((tiles, B), dtype=np.uint32), np.zeros((tiles, B), dtype=np.uint32)
+        self._check(self._lib.ssx_spectral_noise(self._ctx, None if mask is None else mask.ctypes.data, EV.ctypes.data, EM.ctypes.data, PP.ctypes.data, PU.ctypes.data,
+                                                 tEV.ctypes.data, tEM.ctypes.data, tPP.ctypes.data, tPU.ctypes.data))
+        return (EV, EM, PP, PU), (tEV, tEM, tPP, tPU)
+
+    def spectral_noise(self, mask=None):
+        """The spectral noise figure -> (noise, coverage, (EV, EM, PP, PU)): noise is the RMS standard error of the pixels' bin means relative to the mean bin
+        flux, over the sub-bins that hold two samples; coverage is their share.  NaN when nothing is estimable, or with a non-finite flux."""
+        totals, _ = self.spectral_noise_raw(mask)
+        noise, coverage, _ = spectral_noise_derive(*totals)
+        return noise, coverage, totals
+
+    def spectral_noise_reduce(self, tEV, tEM, tPP, tPU):
+        """ssx_spectral_noise_reduce: the totals of uploaded tile partials [tiles, B] (e.g. several contexts' partials merged by ownership) -> (EV, EM, PP, PU)."""
+        tEV, tEM = np.ascontiguousarray(tEV, dtype=np.float64), np.ascontiguousarray(tEM, dtype=np.float64)
+        tPP, tPU = np.ascontiguousarray(tPP, dtype=np.uint32), np.ascontiguousarray(tPU, dtype=np.uint32)
+        if tEV.ndim != 2 or not (tEV.shape == tEM.shape == tPP.shape == tPU.shape):
+            raise ValueError("spectral_noise_reduce: the four partials must all have shape [tiles, B]")
+        tiles, B = tEV.shape
+        EV, EM, PP, PU = np.zeros(B), np.zeros(B), np.zeros(B, dtype=np.uint64), np.zeros(B, dtype=np.uint64)
+        self._check(self._lib.ssx_spectral_noise_reduce(self._ctx, tiles, B, tEV.ctypes.data, tEM.ctypes.data, tPP.ctypes.data, tPU.ctypes.data,
+                                                        EV.ctypes.data, EM.ctypes.data, PP.ctypes.data, PU.ctypes.data))
+        return EV, EM, PP, PU
+
+    def render_until_spectral(self, target, step, max_spp, mask=None, min_coverage=0.99):
+        """Renders `step` samples per pixel at a time, with the moments on (set_spectral_bins first), until spectral_noise(mask) gives noise <= target and coverage
+        >= min_coverage -- checked after EVERY step, the first included -- or done_spp() >= max_spp.  Returns (done_spp, noise, coverage).  min_coverage is the
+        user's parameter, not a tolerance: it keeps a render with many bins from stopping on the few sub-bins that hold two samples after one step; 1.0 is legal
+        but slow to reach (two samples in every sub-bin of every pixel).  A NaN figure never stops the render.  Deterministic: the decision reads only S, Q, N."""
+        if step < 1 or max_spp < 1:
+            raise ValueError("render_until_spectral: step and max_spp must be positive")
+        mask = self._noise_mask(mask)
+        self.set_spectral_moments(True)
+        self._check(self._lib.ssx_render_start(self._ctx, C.byref(self.params(spp=int(step), spp_per_launch=int(step)))))
+        while True:
+            self.render_wait()
+            noise, coverage, _ = self.spectral_noise(mask)
+            if (noise <= target and coverage >= min_coverage) or self.done_spp() >= max_spp:
+                return self.done_spp(), noise, coverage
+            self.render_continue(step)
 
     # ---- denoising (include/ssx.h: guide buffers and the variance-guided a-trous filter) ----
 
