@@ -692,9 +692,10 @@ int ssx_spectral_develop_demod(ssx_ctx* ctx, const ssx_denoise_params* denoise, 
  *   Conditional on the counts Var(sum S_p) = sum n_p sigma_p^2, and q_p / (n_p - 1) is unbiased for sigma_p^2; the samples in sub-bins too thin to estimate
  *   (UU of them) are taken to have the average variance of the others.  The pooled mean weights samples, not pixels.
  * The state follows the bins' rule -- valid from zero samples or not at all: a sample-walking ssx_render_start resets it, ssx_render_continue carries it on,
- * whatever clears the bins clears it, and it is invalid when it is switched on over existing bins.  ssx_spectral_import leaves the moments invalid: a checkpoint
- * does not carry Q (out of scope so far, as the bins first were) -- a continue then renders normally, bins included, and the two read calls below return
- * SSX_ERR_STATE with the reason.  Image, sums and bins of a render do not depend on whether the moments are on. */
+ * whatever clears the bins clears it, and it is invalid when it is switched on over existing bins.  ssx_spectral_import ALONE leaves the moments invalid: it does
+ * not carry Q -- a continue then renders normally, bins included, and the read calls below return SSX_ERR_STATE with the reason; ssx_spectral_moments_import,
+ * called on top of it with the Q of the same samples, makes them valid again, so that a checkpoint which carries Q (libssx_host.so: "SSXCKPT3") resumes with
+ * its error bars and its stopping rule.  Image, sums and bins of a render do not depend on whether the moments are on. */
 
 /* enable: 0 = off (default: nothing allocated, nothing launched), else on: the sample walk runs one more small kernel per launch, which reads the launch's
  * fluxes again, and the context holds Q (as large as S; ssx_scratch_info counts it with the sample arrays).  Needs spectral output on (SSX_ERR_STATE; switching
@@ -703,6 +704,24 @@ int ssx_set_spectral_moments(ssx_ctx* ctx, int enable);
 /* Row-major (row 0 = bottom) var [height][width][B] (float) and q [height][width][B] (the binary64 accumulators Q); either may be NULL.  info is filled as
  * by ssx_spectral_read.  SSX_ERR_STATE: spectral output or the moments are off, a render runs, or the context holds no valid bins or moments. */
 int ssx_spectral_variance(ssx_ctx* ctx, ssx_spectral_info_t* info, float* var, double* q);
+/* The inverse of ssx_spectral_variance(q), for a checkpoint: the context takes, from the whole-image array q [height][width][B] (row-major, row 0 = bottom), the
+ * tiles it owns under its current parameters -- whoever exported it may have owned other tiles, as long as the array holds every pixel this context owns (merge
+ * the ranks' exports by ownership first).  One kernel, a transposition through LDS per owned 8x8 tile; tile lanes outside a ragged image receive +0.0.
+ * Valid only DIRECTLY ON TOP OF a successful ssx_spectral_import: spectral output and the moments are on, the bins are valid and came from that call, and nothing
+ * has rendered since (ssx_set_spectral_moments(1) may come before or after the two imports underneath).  On success the context is what it would be had it
+ * rendered the ssx_done_spp samples with the moments on: ssx_render_continue carries Q on; ssx_spectral_variance, ssx_spectral_probe and ssx_spectral_noise work.
+ * The same kernel checks what it takes against the context's own S and N, with rules that hold exactly for everything the moment kernel can produce (Q +=
+ * (double)f * (double)f from +0.0, every product exact), per owned in-image pixel and bin, n = N[p][b % M]:
+ *       n == 0 :  Q is +0.0, bit for bit
+ *       n == 1 :  Q == S * S, or both are NaN
+ *       n >= 2 :  !(Q < 0.0)
+ *   They catch the Q of another render, one rank's unmerged export (zeros against n > 0 pass the third rule but mostly fail the second at low sample counts)
+ *   and S handed in as Q; they cannot vouch for values at n >= 2 -- the file's checksum does that.  No inexact rule is applied.
+ * SSX_ERR_STATE: spectral output or the moments are off, a render runs, or there is no such import underneath.  SSX_ERR_ARG, ssx_last_error naming the field or
+ * the rule: a NULL pointer, struct_size; width or height differ from the context's; info->bins from its bin count; info->done_spp from ssx_done_spp; lambda_min
+ * or bin_width, compared as bits, from the uploaded scene's; the check fails.  After a refusal the moments are invalid; bins and pixel sums are untouched: a
+ * continue renders normally.  done_spp == 0 is legal (q all +0.0).  Q is reserved for the owned tiles before the kernel runs (ssx_scratch_info counts it). */
+int ssx_spectral_moments_import(ssx_ctx* ctx, const ssx_spectral_info_t* info, const double* q /* [H][W][B] */);
 /* The probe of the context's own state: it exports S, Q and N row-major to device temporaries and runs the kernels of ssx_probe_arrays on them -- the same
  * bits.  Pixels the context does not own add nothing.  SS, NN, VV, UU: [regions][B].  It reads only.  SSX_ERR_STATE as ssx_spectral_variance; SSX_ERR_ARG: a
  * NULL argument, regions outside 1..32, a label that is neither a region nor 255. */

@@ -83,6 +83,20 @@ int ssh_checkpoint_load_spectral(const char* path, ssx_sums_info_t* info, char* 
 /* ssh_sums_merge's rule for the bins: dst's pixels that src_sums_info's exporter owns <- src's, bit for bit, sums [height][width][bins] and counts
  * [height][width][bins / 4] (either pair may be NULL).  The merged arrays of all ranks are what a context of any ownership imports. */
 int ssh_spectral_merge(double* dst_sums, uint32_t* dst_counts, const double* src_sums, const uint32_t* src_counts, uint32_t bins, const ssx_sums_info_t* src_sums_info);
+/* A checkpoint that also carries the bins' second moments -- what ssx_spectral_variance hands out as q and ssx_spectral_moments_import takes back (ssx.h) -- so
+ * that a resumed render keeps its error bars and its spectral stopping rule.  Such a file has the magic "SSXCKPT3": the "SSXCKPT2" layout up to and including
+ * the counts, then q [height][width][bins] (binary64), then the checksum over every byte before it.  q == NULL: exactly ssh_checkpoint_save_spectral, byte for
+ * byte.  SSX_ERR_ARG also: q without bins (spectral_info == NULL). */
+int ssh_checkpoint_save_moments(const char* path, const ssx_sums_info_t* info, const char* scene_name, const char* options_text, const double* sums, const double* noise_s2,
+                                const ssx_spectral_info_t* spectral_info, const double* spectral_sums, const uint32_t* spectral_counts, const double* q);
+/* Reads all three kinds (so do ssh_checkpoint_load and ssh_checkpoint_load_spectral, which pass over what they do not return).  *q_out is NULL from a file
+ * without the moments, otherwise malloc'ed like *sums_out: release with ssh_free.  SSX_ERR_DATA also: truncation or an altered bit anywhere in q, one byte
+ * more or less, the "SSXCKPT2" or "SSXCKPT1" magic on the longer file, the "SSXCKPT3" magic on a file without q. */
+int ssh_checkpoint_load_moments(const char* path, ssx_sums_info_t* info, char* scene_name, size_t scene_name_size, char* options_text, size_t options_text_size,
+                                double** sums_out, double** noise_s2_out, ssx_spectral_info_t* spectral_info, double** spectral_sums_out, uint32_t** spectral_counts_out,
+                                double** q_out);
+/* ssh_sums_merge's rule for the second moments: dst_q's pixels that src_sums_info's exporter owns <- src_q's, bit for bit, [height][width][bins]. */
+int ssh_moments_merge(double* dst_q, const double* src_q, uint32_t bins, const ssx_sums_info_t* src_sums_info);
 
 /* A NumPy .npy file (format version 1.0, '<f4', C order) of `data` with the given shape: what np.load reads, and the bytes np.save writes for the
  * same array.  The CLI's --spectral-output writes the spectral image with it: shape (height, width, bins), row 0 = bottom. */

@@ -120,7 +120,8 @@ HIP_SYMBOLS = ["ssx_create", "ssx_destroy", "ssx_upload_scene", "ssx_render_star
                "ssx_albedo_bins", "ssx_denoise_spectral_demod", "ssx_spectral_develop_demod",
                "ssx_spectral_import",
                "ssx_set_spectral_moments", "ssx_spectral_variance", "ssx_spectral_probe", "ssx_probe_arrays",
-               "ssx_spectral_noise", "ssx_spectral_noise_reduce"]
+               "ssx_spectral_noise", "ssx_spectral_noise_reduce",
+               "ssx_spectral_moments_import"]
 (SSX_SWEEP_RCP, SSX_SWEEP_SQRT, SSX_SWEEP_INVERSESQRT, SSX_SWEEP_SIN, SSX_SWEEP_COS, SSX_SWEEP_ACOS, SSX_SWEEP_DIV_PI,
  SSX_SWEEP_RCP64, SSX_SWEEP_DIV_PAIRS, SSX_SWEEP_ACOS_SIN, SSX_SWEEP_SIN_PROOF, SSX_SWEEP_COS_PROOF, SSX_SWEEP_ACOS_PROOF) = range(1, 14)
 # ssx_debug_eval ops (include/ssx.h)
@@ -133,7 +134,8 @@ HOST_SYMBOLS = ["ssh_scene_create", "ssh_scene_create_ex", "ssh_scene_destroy", 
                 "ssh_load_png_rgb8", "ssh_free", "ssh_color_values", "ssh_last_error", "ssh_checkpoint_save", "ssh_checkpoint_load", "ssh_sums_merge", "ssh_save_npy_f32",
                 "ssh_develop_weights", "ssh_relight_gain", "ssh_emitter_spectrum",
                 "ssh_checkpoint_save_spectral", "ssh_checkpoint_load_spectral", "ssh_spectral_merge",
-                "ssh_probe_derive", "ssh_probe_save_csv", "ssh_spectral_noise_derive", "ssh_spectral_noise_save_csv"]
+                "ssh_probe_derive", "ssh_probe_save_csv", "ssh_spectral_noise_derive", "ssh_spectral_noise_save_csv",
+                "ssh_checkpoint_save_moments", "ssh_checkpoint_load_moments", "ssh_moments_merge"]
 
 _hip = None
 _host = None
@@ -170,6 +172,9 @@ def host_lib():
                                                      C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.POINTER(C.c_double)),
                                                      C.POINTER(SsxSpectralInfo), C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.POINTER(C.c_uint32))]
         lib.ssh_spectral_merge.argtypes = [vp, vp, vp, vp, C.c_uint32, C.POINTER(SsxSumsInfo)]
+        lib.ssh_checkpoint_save_moments.argtypes = lib.ssh_checkpoint_save_spectral.argtypes + [vp]
+        lib.ssh_checkpoint_load_moments.argtypes = lib.ssh_checkpoint_load_spectral.argtypes + [C.POINTER(C.POINTER(C.c_double))]
+        lib.ssh_moments_merge.argtypes = [vp, vp, C.c_uint32, C.POINTER(SsxSumsInfo)]
         lib.ssh_save_npy_f32.argtypes = [C.c_char_p, vp, C.POINTER(C.c_uint32), C.c_uint32]
         lib.ssh_probe_derive.argtypes = [C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp]
         lib.ssh_probe_save_csv.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_float, C.c_float, vp, vp, vp, vp]
@@ -363,6 +368,8 @@ def hip_lib():
         if not override or hasattr(lib, "ssx_spectral_noise"):  # the spectral noise figure: tile partials and totals
             lib.ssx_spectral_noise.argtypes = [vp] * 10
             lib.ssx_spectral_noise_reduce.argtypes = [vp, C.c_uint32, C.c_uint32] + [vp] * 8
+        if not override or hasattr(lib, "ssx_spectral_moments_import"):  # the second moments through checkpoint and resume
+            lib.ssx_spectral_moments_import.argtypes = [vp, C.POINTER(SsxSpectralInfo), vp]
         lib.ssx_kernel_variant.argtypes = [vp]
         lib.ssx_kernel_name.argtypes = [vp]
         lib.ssx_kernel_name.restype = C.c_char_p

@@ -131,7 +131,8 @@ struct ssx_ctx {
 	// spectral_valid: d_spectral_sums / d_spectral_counts hold the bins of exactly those samples (valid from zero samples or not at all: ssx_spectral.hip).
 	// moments_valid: d_spectral_moments holds the second moments of exactly those samples too (the same rule: ssx_spectral_stats.hip).
 	// imported: the sums are ssx_sums_import's and nothing has rendered onto them since -- the one state ssx_spectral_import puts the bins next to.
-	struct SumsState { bool continuable = false, noise_valid = false, spectral_valid = false, moments_valid = false, imported = false; uint32_t noise_batches = 0; } sums;
+	// spectral_imported: the bins are ssx_spectral_import's, likewise -- the one state ssx_spectral_moments_import puts the moments next to.
+	struct SumsState { bool continuable = false, noise_valid = false, spectral_valid = false, moments_valid = false, imported = false, spectral_imported = false; uint32_t noise_batches = 0; } sums;
 	uint32_t k_begin = 0;               // first sample of the running call: 0 (ssx_render_start) or the count ssx_render_continue took up (ssx_progress)
 	uint64_t scene_digest = 0;          // ssx_scene_digest
 	// noise estimate by batch means (ssx_set_noise_estimate): per pixel A_prev | S2 (row-major, 2 x width x height doubles)
@@ -842,7 +843,7 @@ int start_worker(ssx_ctx* ctx, const ssx_render_params& p, uint32_t k_begin, boo
 	if (const int rc = ready_to_launch(ctx, &p, true)) return rc;
 	ctx->cur = p; ctx->total_spp = total_spp; ctx->k_begin = k_begin;
 	if (!continuing) { sums_invalidate(ctx); ctx->done_spp.store(0); ctx->done_tiles.store(0); } // (the worker publishes the sums it leaves)
-	ctx->sums.imported = false;
+	ctx->sums.imported = ctx->sums.spectral_imported = false;
 	ctx->stop_flag.store(0); ctx->worker_rc = 0;
 	ctx->rendering.store(1);
 	ctx->worker = std::thread(worker_main, ctx, k_begin, continuing);

@@ -174,7 +174,7 @@ int ssx_set_spectral_bins(ssx_ctx* ctx, uint32_t bins) {
 	SSX_HIP(ctx, hipSetDevice(ctx->device));
 	if (const int rc = wait_device_pending(ctx)) return rc; // (a queued ssx_render_device uses the sample arrays in the layout without flux[])
 	ctx->spectral_bins = bins;
-	ctx->sums.spectral_valid = false; ctx->spectral_note = "the bin count changed after the last render";
+	ctx->sums.spectral_valid = ctx->sums.spectral_imported = false; ctx->spectral_note = "the bin count changed after the last render";
 	moments_invalidate(ctx, "the bin count changed after the last render"); // (whatever clears the bins clears their moments)
 	if (!bins) { spectral_drop(ctx); ctx->spectral_moments = false; moments_drop(ctx); }
 	return SSX_OK;
@@ -241,7 +241,7 @@ int ssx_spectral_import(ssx_ctx* ctx, const ssx_spectral_info_t* info, const dou
 	SSX_HIP(ctx, ctx->d_spectral_sums.reserve(spectral_sum_bytes(ctx, tiles)));
 	SSX_HIP(ctx, ctx->d_spectral_counts.reserve(spectral_count_bytes(ctx, tiles)));
 	// from here on the device state is being replaced: it is valid again only once the check has passed
-	ctx->sums.spectral_valid = false; ctx->spectral_note = "an ssx_spectral_import on top of ssx_sums_import was refused or failed";
+	ctx->sums.spectral_valid = ctx->sums.spectral_imported = false; ctx->spectral_note = "an ssx_spectral_import on top of ssx_sums_import was refused or failed";
 	uint32_t bad = 0;
 	if (tiles) {
 		SSX_HIP(ctx, hipMemcpyAsync(d_sums, sums, b_sums, hipMemcpyHostToDevice, ctx->stream));
@@ -256,8 +256,8 @@ int ssx_spectral_import(ssx_ctx* ctx, const ssx_spectral_info_t* info, const dou
 	}
 	if (bad) return fail(ctx, SSX_ERR_ARG, fmt("ssx_spectral_import: counts: a pixel this context owns does not hold done_spp = %u samples over its %u counts (every sample is counted once; "
 	                                           "one rank's unmerged export holds zeros where it owned nothing: merge the ranks' exports by ownership first)", done, M));
-	ctx->sums.spectral_valid = true; ctx->spectral_note.clear();
-	moments_invalidate(ctx, "the bins came from ssx_spectral_import, and a checkpoint does not carry their second moments (out of scope so far: render from ssx_render_start to have them)");
+	ctx->sums.spectral_valid = ctx->sums.spectral_imported = true; ctx->spectral_note.clear();
+	moments_invalidate(ctx, "the bins came from ssx_spectral_import, which does not carry their second moments (hand the checkpoint's Q to ssx_spectral_moments_import on top of it, or render from ssx_render_start)");
 	return SSX_OK;
 }
 

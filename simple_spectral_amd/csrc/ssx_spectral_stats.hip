@@ -68,6 +68,59 @@ extern "C" __global__ void __launch_bounds__(256) ssx_spectral_variance_kernel(c
 	}
 }
 
+// The inverse of the variance kernel's q for the tiles this context owns (ssx_spectral_moments_import): row-major whole-image q [height][width][B] (row 0 =
+// bottom; whoever exported it may have owned other tiles) -> Q[tile slot][bin][pixel of the tile].  ssx_spectral_import_kernel's geometry for one array, one
+// 256-lane workgroup per owned tile slot (slot -> tile by tile_of_slot), no atomics: a workgroup writes its own slot only.
+//   in:   the 8 pixel rows of a tile are 8 runs of cols * B consecutive doubles (cols = 8, fewer in the image's last tile column); consecutive lanes read
+//         consecutive 16-byte pairs of a run (B is a multiple of 4: every run starts 32-byte aligned).  Rows and columns outside a ragged image are never read.
+//   LDS:  [64 pixels][B + 1] doubles (33 KB at B = 64).  On the way out lane = pixel reads element b of its row, 8-byte address (B + 1) * pixel + b.  A
+//         ds_read_b64 is served in two groups of 32 lanes over 64 four-byte banks, bank = (address / 4) mod 64: the 32 lanes of a group need 32 distinct bank
+//         pairs, i.e. 2 * (B + 1) * pixel mod 64 distinct over 32 consecutive pixels, which holds exactly when the stride B + 1 is odd; the unpadded B -- 4, ...,
+//         64 doubles -- would put 2, ..., 32 lanes on one pair.  The price is on the way in: a row starts 8-byte aligned only, so a pair goes in as two
+//         ds_write_b64 (groups of 16 lanes over 32 banks; the lanes of a group write every other 8-byte word, so lanes l and l + 8 meet: 2-way), which the
+//         write's own register transfer mostly covers.
+//   out:  wave w stores bins w, w + 4, ...: per bin the 64 lanes' doubles are 512 consecutive bytes.  Lanes of pixels outside the image store +0.0, what the
+//         memset of a fresh render leaves there.
+// The check.  On the way out lane = pixel, wave = bin: the lane that stores Q[slot][b][px] reads the context's own S[slot][b][px] and N[slot][b % M][px] where
+// they lie (coalesced, 512 and 256 consecutive bytes per wave) and holds q to what ssx_spectral_moment_kernel can produce -- Q += (double)f * (double)f from
+// +0.0, every product exact:
+//     rule 0   n == 0 :  q is +0.0, bit for bit
+//     rule 1   n == 1 :  q == S * S, or both are NaN      (S is then (double)f, its square exact; -ffp-contract=off: one multiply)
+//     rule 2   n >= 2 :  !(q < 0.0)                       (a sum of squares is non-negative, or NaN)
+// An owned in-image pixel that breaks rule r stores 1 into bad[r] (a plain store; every writer of a word stores the same value).  Nothing inexact is held:
+// values at n >= 2 are the file's checksum's business.
+extern "C" __global__ void __launch_bounds__(256) ssx_spectral_moments_import_kernel(const double* q, const double* S, const uint32_t* N, double* Q, uint32_t* bad, SsxPixelGrid g, uint32_t M) {
+	extern __shared__ double moment_lds[];
+	const uint32_t tid = threadIdx.x, slot = blockIdx.x, B = 4u * M, stride = B + 1u;
+	uint32_t tx, ty;
+	(void)tile_of_slot(g, slot, tx, ty);
+	const uint32_t i0 = tx * 8u, j0 = ty * 8u, cols = min(8u, g.width - i0), rows = min(8u, g.height - j0);
+	const uint32_t pairs = cols * (B / 2u);                                                       // 16-byte pairs of one run
+	for (uint32_t e = tid; e < rows * pairs; e += 256u) {
+		const uint32_t r = e / pairs, v = e - r * pairs, c = (2u * v) / B, b = 2u * v - c * B;      // (B is even: a pair never straddles two pixels)
+		const double2 d = reinterpret_cast<const double2*>(q + ((size_t)(j0 + r) * g.width + i0) * B)[v];
+		double* const o = moment_lds + (r * 8u + c) * stride + b;
+		o[0] = d.x; o[1] = d.y;
+	}
+	__syncthreads();
+	const uint32_t px = tid & 63u, w = tid >> 6;
+	const bool inside = (px & 7u) < cols && (px >> 3) < rows;
+	const size_t at0 = (size_t)slot * B * 64u + px;
+	const uint32_t* const Np = N + (size_t)slot * M * 64u + px;
+	for (uint32_t b = w; b < B; b += 4u) {
+		const size_t at = at0 + (size_t)b * 64u;
+		double v = 0.0;
+		if (inside) {
+			v = moment_lds[px * stride + b];
+			const uint32_t n = Np[(size_t)(b % M) * 64u];
+			if (n == 0u) { if (__double_as_longlong(v) != 0ll) bad[0] = 1u; }
+			else if (n == 1u) { const double s = S[at], ss = s * s; if (!(v == ss) && !(v != v && ss != ss)) bad[1] = 1u; }
+			else if (v < 0.0) bad[2] = 1u;
+		}
+		Q[at] = v;
+	}
+}
+
 // Region probes on row-major device arrays: sums and q [height][width][B], counts [height][width][M], labels [height][width] (0..R-1, or 255: no region).
 // Stage 1: one workgroup per image row and half h of the quantities (h = 0: SS | NN, h = 1: VV | UU), 2 B lanes, lane = (quantity, bin): the B lanes of a
 // quantity read B consecutive elements of a pixel.  The pixel's label is a run-time index, so the accumulators live in LDS, [R][2 B] eight-byte words (lane l of a
@@ -265,6 +318,61 @@ int ssx_spectral_variance(ssx_ctx* ctx, ssx_spectral_info_t* info, float* var, d
 	SSX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	if (q) SSX_HIP(ctx, hipMemcpy(q, d_q, b_q, hipMemcpyDeviceToHost));
 	if (var) SSX_HIP(ctx, hipMemcpy(var, d_var, b_var, hipMemcpyDeviceToHost));
+	return SSX_OK;
+}
+
+int ssx_spectral_moments_import(ssx_ctx* ctx, const ssx_spectral_info_t* info, const double* q) {
+	if (!ctx) return SSX_ERR_ARG;
+	const char* const what = "ssx_spectral_moments_import";
+	if (!ctx->spectral_bins) return fail(ctx, SSX_ERR_STATE, fmt("%s: spectral output is off (ssx_set_spectral_bins)", what));
+	if (!ctx->spectral_moments) return fail(ctx, SSX_ERR_STATE, fmt("%s: spectral moments are off (ssx_set_spectral_moments)", what));
+	if (ctx->rendering.load()) return fail(ctx, SSX_ERR_STATE, "render in progress");
+	if (!ctx->sums.continuable || !ctx->sums.spectral_valid || !ctx->sums.spectral_imported)
+		return fail(ctx, SSX_ERR_STATE, fmt("%s: the moments go on top of the bins of a successful ssx_spectral_import, directly: the context holds none, or has rendered since", what));
+	// from here on a refusal leaves the moments invalid; bins and pixel sums stay what the two imports made them
+	auto refuse = [&](const std::string& why) {
+		moments_invalidate(ctx, "an ssx_spectral_moments_import on top of ssx_spectral_import was refused or failed (ssx_spectral_import itself does not carry them)");
+		return fail(ctx, SSX_ERR_ARG, why);
+	};
+	if (!info || !q) return refuse(fmt("%s: info and q must not be NULL", what));
+	if (info->struct_size != sizeof *info) return refuse(fmt("%s: ssx_spectral_info_t.struct_size mismatch", what));
+	const ssx_render_params& p = ctx->cur;
+	const uint32_t B = ctx->spectral_bins, M = B / 4u, done = ctx->done_spp.load();
+	const float bin_width = ctx->lambda_step / (float)M; // (what ssx_spectral_read reports)
+	if (info->width != p.width || info->height != p.height)
+		return refuse(fmt("%s: size differs (these moments: %u x %u, this render: %u x %u)", what, info->width, info->height, p.width, p.height));
+	if (info->bins != B) return refuse(fmt("%s: bins differs (these moments: %u, this context: %u)", what, info->bins, B));
+	if (info->done_spp != done) return refuse(fmt("%s: done_spp differs (these moments: %u, the imported bins: %u)", what, info->done_spp, done));
+	if (memcmp(&info->lambda_min, &ctx->lambda_min, sizeof(float)) != 0)
+		return refuse(fmt("%s: lambda_min differs (these moments: %.9g, the uploaded scene: %.9g)", what, (double)info->lambda_min, (double)ctx->lambda_min));
+	if (memcmp(&info->bin_width, &bin_width, sizeof(float)) != 0)
+		return refuse(fmt("%s: bin_width differs (these moments: %.9g, the uploaded scene: %.9g)", what, (double)info->bin_width, (double)bin_width));
+	moments_invalidate(ctx, "an ssx_spectral_moments_import on top of ssx_spectral_import was refused or failed (ssx_spectral_import itself does not carry them)");
+	SSX_HIP(ctx, hipSetDevice(ctx->device));
+	if (const int rc = wait_device_pending(ctx)) return rc;
+	const uint32_t tiles = owned_tiles(p);
+	const size_t pixels = (size_t)p.width * p.height, b_q = pixels * B * sizeof(double);
+	SSX_HIP(ctx, ctx->d_spectral_moments.reserve(moment_bytes(ctx, tiles))); // (before the kernel; ssx_scratch_info counts it from here on)
+	uint32_t bad[3] = { 0u, 0u, 0u };
+	if (tiles) {
+		DeviceBuffer& stage = ctx->d_stage; // q | the three flags of the check
+		SSX_HIP(ctx, stage.reserve(b_q + sizeof bad));
+		double* const d_q = stage.as<double>();
+		uint32_t* const d_bad = reinterpret_cast<uint32_t*>(stage.as<uint8_t>() + b_q);
+		SSX_HIP(ctx, hipMemcpyAsync(d_q, q, b_q, hipMemcpyHostToDevice, ctx->stream));
+		SSX_HIP(ctx, hipMemsetAsync(d_bad, 0, sizeof bad, ctx->stream));
+		const size_t lds = 64u * (size_t)(B + 1u) * sizeof(double); // <= 33 KB at 64 bins
+		hipLaunchKernelGGL(ssx_spectral_moments_import_kernel, dim3(tiles), dim3(256), lds, ctx->stream, d_q, ctx->d_spectral_sums.as<const double>(),
+		                   ctx->d_spectral_counts.as<const uint32_t>(), ctx->d_spectral_moments.as<double>(), d_bad, pixel_grid(&p), M);
+		SSX_HIP(ctx, hipGetLastError());
+		SSX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+		SSX_HIP(ctx, hipMemcpy(bad, d_bad, sizeof bad, hipMemcpyDeviceToHost));
+	}
+	const char* const tail = "these are not the second moments of the imported bins (another render's, one rank's unmerged export -- merge the ranks' by ownership first -- or the sums S)";
+	if (bad[0]) return fail(ctx, SSX_ERR_ARG, fmt("%s: q: rule n == 0: a sub-bin this context owns holds no sample, and its Q is not +0.0: %s", what, tail));
+	if (bad[1]) return fail(ctx, SSX_ERR_ARG, fmt("%s: q: rule n == 1: a sub-bin this context owns holds one sample, and its Q is not S * S: %s", what, tail));
+	if (bad[2]) return fail(ctx, SSX_ERR_ARG, fmt("%s: q: rule n >= 2: a sub-bin this context owns holds a negative Q, and a sum of squares has none: %s", what, tail));
+	ctx->sums.moments_valid = true; ctx->moments_note.clear();
 	return SSX_OK;
 }
 

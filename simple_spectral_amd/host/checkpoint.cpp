@@ -9,6 +9,7 @@ namespace ssx {
 namespace {
 const char kMagic[8] = { 'S', 'S', 'X', 'C', 'K', 'P', 'T', '1' };
 const char kMagicSpectral[8] = { 'S', 'S', 'X', 'C', 'K', 'P', 'T', '2' }; // ... with the wavelength bins behind s2
+const char kMagicMoments[8] = { 'S', 'S', 'X', 'C', 'K', 'P', 'T', '3' };  // ... and their second moments behind the counts
 bool valid_bins(uint32_t bins) { return bins >= 4u && bins <= 64u && bins % 4u == 0u; }
 
 // 64-bit checksum: eight bytes at a time through the splitmix64 finaliser, the length first
@@ -53,9 +54,12 @@ void checkpoint_save(const std::string& path, const Checkpoint& c) {
 	if (spectral && (c.spectral.struct_size != sizeof(ssx_spectral_info_t) || !valid_bins(c.spectral.bins) || c.spectral.width != c.info.width || c.spectral.height != c.info.height ||
 	                 c.spectral.done_spp != c.info.done_spp || c.spectral_sums.size() != pixels * c.spectral.bins || c.spectral_counts.size() != pixels * (c.spectral.bins / 4u)))
 		throw HostError{ SSX_ERR_ARG, "checkpoint_save: the wavelength bins do not belong to these sums (size, sample count, or a bin count that is no multiple of 4 in 4..64)" };
+	const bool moments = !c.moments.empty();
+	if (moments && !spectral) throw HostError{ SSX_ERR_ARG, "checkpoint_save: second moments without the wavelength bins they belong to" };
+	if (moments && c.moments.size() != c.spectral_sums.size()) throw HostError{ SSX_ERR_ARG, "checkpoint_save: the second moments do not have the size of the wavelength bins' sums" };
 	std::vector<uint8_t> b;
-	b.reserve(160 + c.scene_name.size() + c.options_text.size() + (c.sums.size() + c.s2.size() + c.spectral_sums.size()) * 8 + c.spectral_counts.size() * 4);
-	put(b, spectral ? kMagicSpectral : kMagic, 8);
+	b.reserve(160 + c.scene_name.size() + c.options_text.size() + (c.sums.size() + c.s2.size() + c.spectral_sums.size() + c.moments.size()) * 8 + c.spectral_counts.size() * 4);
+	put(b, moments ? kMagicMoments : spectral ? kMagicSpectral : kMagic, 8);
 	put_u32(b, (uint32_t)sizeof c.info); put(b, &c.info, sizeof c.info);
 	put_u32(b, (uint32_t)c.scene_name.size()); put(b, c.scene_name.data(), c.scene_name.size());
 	put_u32(b, (uint32_t)c.options_text.size()); put(b, c.options_text.data(), c.options_text.size());
@@ -66,6 +70,7 @@ void checkpoint_save(const std::string& path, const Checkpoint& c) {
 		put_u32(b, (uint32_t)sizeof c.spectral); put(b, &c.spectral, sizeof c.spectral);
 		put(b, c.spectral_sums.data(), c.spectral_sums.size() * 8);
 		put(b, c.spectral_counts.data(), c.spectral_counts.size() * 4);
+		put(b, c.moments.data(), c.moments.size() * 8);
 	}
 	const uint64_t sum = checksum(b.data(), b.size());
 	put(b, &sum, 8);
@@ -87,8 +92,9 @@ Checkpoint checkpoint_load(const std::string& path) {
 		if (!f.good()) throw HostError{ SSX_ERR_DATA, "Could not open checkpoint \"" + path + "\"" };
 		b.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
 	}
-	const bool spectral = b.size() >= 8 && std::memcmp(b.data(), kMagicSpectral, 8) == 0;
-	if (!spectral && (b.size() < 8 || std::memcmp(b.data(), kMagic, 8) != 0)) throw HostError{ SSX_ERR_DATA, "\"" + path + "\" is not a checkpoint (magic SSXCKPT1 or SSXCKPT2 missing)" };
+	const bool moments = b.size() >= 8 && std::memcmp(b.data(), kMagicMoments, 8) == 0;
+	const bool spectral = moments || (b.size() >= 8 && std::memcmp(b.data(), kMagicSpectral, 8) == 0);
+	if (!spectral && (b.size() < 8 || std::memcmp(b.data(), kMagic, 8) != 0)) throw HostError{ SSX_ERR_DATA, "\"" + path + "\" is not a checkpoint (magic SSXCKPT1, SSXCKPT2 or SSXCKPT3 missing)" };
 	Reader r{ b, 8, path };
 	Checkpoint c;
 	if (r.u32() != sizeof c.info) throw HostError{ SSX_ERR_DATA, "Checkpoint \"" + path + "\": description of another size" };
@@ -109,6 +115,7 @@ Checkpoint checkpoint_load(const std::string& path) {
 		if (c.spectral.struct_size != sizeof c.spectral || !valid_bins(c.spectral.bins) || c.spectral.width != c.info.width || c.spectral.height != c.info.height || c.spectral.done_spp != c.info.done_spp)
 			throw HostError{ SSX_ERR_DATA, "Checkpoint \"" + path + "\" is corrupt (spectral description: a bin count outside 4..64, or a size or sample count other than the pixel sums')" };
 		spectral_payload = 4u + sizeof c.spectral + pixels * c.spectral.bins * 8u + pixels * (c.spectral.bins / 4u) * 4u;
+		if (moments) spectral_payload += pixels * c.spectral.bins * 8u; // (the magic decides: the other magic on this file, or this one on the shorter, fails the length)
 	}
 	if (b.size() - r.at < payload + spectral_payload + 8u) throw HostError{ SSX_ERR_DATA, "Checkpoint \"" + path + "\" is truncated" };
 	if (b.size() - r.at != payload + spectral_payload + 8u) throw HostError{ SSX_ERR_DATA, "Checkpoint \"" + path + "\" is corrupt (length)" };
@@ -124,6 +131,7 @@ Checkpoint checkpoint_load(const std::string& path) {
 		r.take(c.spectral_sums.data(), c.spectral_sums.size() * 8);
 		c.spectral_counts.resize(pixels * (c.spectral.bins / 4u));
 		r.take(c.spectral_counts.data(), c.spectral_counts.size() * 4);
+		if (moments) { c.moments.resize(pixels * c.spectral.bins); r.take(c.moments.data(), c.moments.size() * 8); }
 	}
 	return c;
 }
@@ -142,5 +150,7 @@ void spectral_merge(double* dst_sums, uint32_t* dst_counts, const double* src_su
 	if (dst_sums && src_sums) merge_owned(dst_sums, src_sums, bins, src_info);
 	if (dst_counts && src_counts) merge_owned(dst_counts, src_counts, bins / 4u, src_info);
 }
+
+void moments_merge(double* dst_q, const double* src_q, size_t bins, const ssx_sums_info_t& src_info) { merge_owned(dst_q, src_q, bins, src_info); }
 
 } // namespace ssx

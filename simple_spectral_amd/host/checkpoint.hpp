@@ -13,6 +13,12 @@
 //     u32 spectral_info_bytes, ssx_spectral_info_t        (width, height and done_spp those of the ssx_sums_info_t; bins B in {4, 8, ..., 64}, M = B / 4)
 //     f64 S[height][width][B] | u32 N[height][width][M]
 //     u64 checksum of every byte before it
+// A checkpoint that also carries the bins' second moments (ssx_spectral_variance's q) has a third magic and one more array behind the counts; without valid
+// moments the file is, byte for byte, one of the two above:
+//     "SSXCKPT3"
+//     the "SSXCKPT2" layout up to and including N
+//     f64 Q[height][width][B]
+//     u64 checksum of every byte before it
 // A file that is truncated, altered or of another kind, a bin count outside {4, ..., 64} and arrays whose size does not follow from the header are
 // refused with SSX_ERR_DATA.
 #pragma once
@@ -34,10 +40,11 @@ struct Checkpoint {
 	ssx_spectral_info_t spectral{};
 	std::vector<double> spectral_sums;     // [height][width][B]
 	std::vector<uint32_t> spectral_counts; // [height][width][B / 4]
+	std::vector<double> moments;           // the second moments Q [height][width][B] (SSXCKPT3), or empty
 };
 
 void checkpoint_save(const std::string& path, const Checkpoint& c); // throws HostError
-Checkpoint checkpoint_load(const std::string& path);               // throws HostError{SSX_ERR_DATA}; either kind of file
+Checkpoint checkpoint_load(const std::string& path);               // throws HostError{SSX_ERR_DATA}; any of the three kinds of file
 
 // The ownership rule of this library (the kernels': include/ssx.h tile_first / tile_stride / tile_skew): the place of pixel (i, j)'s 8x8 tile in the
 // list the devices share out -- row-major, tile row ty rotated by ty * tile_skew columns.  Tile t belongs to the device with tile_first == t % tile_stride,
@@ -62,5 +69,7 @@ void merge_owned(T* dst, const T* src, size_t n, const ssx_sums_info_t& src_info
 }
 // ... for the wavelength bins: sums [height][width][bins] and counts [height][width][bins / 4] (either pair may be NULL)
 void spectral_merge(double* dst_sums, uint32_t* dst_counts, const double* src_sums, const uint32_t* src_counts, size_t bins, const ssx_sums_info_t& src_info);
+// ... and for their second moments: q [height][width][bins]
+void moments_merge(double* dst_q, const double* src_q, size_t bins, const ssx_sums_info_t& src_info);
 
 } // namespace ssx

@@ -116,9 +116,10 @@ int ssh_load_png_rgb8(const char* path, uint8_t** rgb_out, uint32_t* width, uint
 }
 void ssh_free(void* p) { free(p); }
 
-int ssh_checkpoint_save_spectral(const char* path, const ssx_sums_info_t* info, const char* scene_name, const char* options_text, const double* sums, const double* noise_s2,
-                                 const ssx_spectral_info_t* spectral_info, const double* spectral_sums, const uint32_t* spectral_counts) {
+int ssh_checkpoint_save_moments(const char* path, const ssx_sums_info_t* info, const char* scene_name, const char* options_text, const double* sums, const double* noise_s2,
+                                const ssx_spectral_info_t* spectral_info, const double* spectral_sums, const uint32_t* spectral_counts, const double* q) {
 	if (!path || !info || !sums || (spectral_info && (!spectral_sums || !spectral_counts))) { g_error = "NULL argument"; return SSX_ERR_ARG; }
+	if (q && !spectral_info) { g_error = "ssh_checkpoint_save_moments: q without the wavelength bins it belongs to (spectral_info is NULL)"; return SSX_ERR_ARG; }
 	try {
 		ssx::Checkpoint c;
 		c.info = *info;
@@ -131,6 +132,7 @@ int ssh_checkpoint_save_spectral(const char* path, const ssx_sums_info_t* info, 
 			c.spectral = *spectral_info;
 			c.spectral_sums.assign(spectral_sums, spectral_sums + pixels * spectral_info->bins);
 			c.spectral_counts.assign(spectral_counts, spectral_counts + pixels * (spectral_info->bins / 4u));
+			if (q) c.moments.assign(q, q + pixels * spectral_info->bins);
 		}
 		ssx::checkpoint_save(path, c);
 		return SSX_OK;
@@ -138,18 +140,25 @@ int ssh_checkpoint_save_spectral(const char* path, const ssx_sums_info_t* info, 
 	catch (const std::exception& e) { g_error = e.what(); return SSX_ERR_DATA; }
 }
 
-int ssh_checkpoint_save(const char* path, const ssx_sums_info_t* info, const char* scene_name, const char* options_text,
-                        const double* sums, const double* noise_s2) {
-	return ssh_checkpoint_save_spectral(path, info, scene_name, options_text, sums, noise_s2, nullptr, nullptr, nullptr);
+int ssh_checkpoint_save_spectral(const char* path, const ssx_sums_info_t* info, const char* scene_name, const char* options_text, const double* sums, const double* noise_s2,
+                                 const ssx_spectral_info_t* spectral_info, const double* spectral_sums, const uint32_t* spectral_counts) {
+	return ssh_checkpoint_save_moments(path, info, scene_name, options_text, sums, noise_s2, spectral_info, spectral_sums, spectral_counts, nullptr);
 }
 
-int ssh_checkpoint_load_spectral(const char* path, ssx_sums_info_t* info, char* scene_name, size_t scene_name_size, char* options_text, size_t options_text_size,
-                                 double** sums_out, double** noise_s2_out, ssx_spectral_info_t* spectral_info, double** spectral_sums_out, uint32_t** spectral_counts_out) {
-	if (!path || !info || !sums_out || (spectral_info && (!spectral_sums_out || !spectral_counts_out))) { g_error = "NULL argument"; return SSX_ERR_ARG; }
+int ssh_checkpoint_save(const char* path, const ssx_sums_info_t* info, const char* scene_name, const char* options_text,
+                        const double* sums, const double* noise_s2) {
+	return ssh_checkpoint_save_moments(path, info, scene_name, options_text, sums, noise_s2, nullptr, nullptr, nullptr, nullptr);
+}
+
+int ssh_checkpoint_load_moments(const char* path, ssx_sums_info_t* info, char* scene_name, size_t scene_name_size, char* options_text, size_t options_text_size,
+                                double** sums_out, double** noise_s2_out, ssx_spectral_info_t* spectral_info, double** spectral_sums_out, uint32_t** spectral_counts_out,
+                                double** q_out) {
+	if (!path || !info || !sums_out || (spectral_info && (!spectral_sums_out || !spectral_counts_out)) || (q_out && !spectral_info)) { g_error = "NULL argument"; return SSX_ERR_ARG; }
 	*sums_out = nullptr;
+	if (q_out) *q_out = nullptr;
 	if (noise_s2_out) *noise_s2_out = nullptr;
 	if (spectral_info) { memset(spectral_info, 0, sizeof *spectral_info); *spectral_sums_out = nullptr; *spectral_counts_out = nullptr; }
-	double* s2 = nullptr; double* bins = nullptr;
+	double* s2 = nullptr; double* bins = nullptr; uint32_t* counts = nullptr;
 	try {
 		const ssx::Checkpoint c = ssx::checkpoint_load(path);
 		auto text = [](const std::string& s, char* out, size_t n) { if (out && n) { const size_t k = s.size() < n - 1 ? s.size() : n - 1; memcpy(out, s.data(), k); out[k] = '\0'; } };
@@ -167,22 +176,29 @@ int ssh_checkpoint_load_spectral(const char* path, ssx_sums_info_t* info, char* 
 		if (noise_s2_out && !c.s2.empty()) *noise_s2_out = s2 = copy(c.s2);
 		if (spectral_info && c.spectral.bins) {
 			*spectral_sums_out = bins = copy(c.spectral_sums);
-			*spectral_counts_out = copy(c.spectral_counts);
+			*spectral_counts_out = counts = copy(c.spectral_counts);
+			if (q_out && !c.moments.empty()) *q_out = copy(c.moments);
 			*spectral_info = c.spectral;
 		}
 		return SSX_OK;
 	} catch (const ssx::HostError& e) { return report(e); }
 	catch (const std::exception& e) { // (out of memory half-way: nothing is handed out)
-		free(*sums_out); *sums_out = nullptr; free(s2); free(bins);
+		free(*sums_out); *sums_out = nullptr; free(s2); free(bins); free(counts);
+		if (q_out) *q_out = nullptr; // (the last copy made: when it throws nothing of it exists)
 		if (noise_s2_out) *noise_s2_out = nullptr;
 		if (spectral_info) { *spectral_sums_out = nullptr; *spectral_counts_out = nullptr; }
 		g_error = e.what(); return SSX_ERR_DATA;
 	}
 }
 
+int ssh_checkpoint_load_spectral(const char* path, ssx_sums_info_t* info, char* scene_name, size_t scene_name_size, char* options_text, size_t options_text_size,
+                                 double** sums_out, double** noise_s2_out, ssx_spectral_info_t* spectral_info, double** spectral_sums_out, uint32_t** spectral_counts_out) {
+	return ssh_checkpoint_load_moments(path, info, scene_name, scene_name_size, options_text, options_text_size, sums_out, noise_s2_out, spectral_info, spectral_sums_out, spectral_counts_out, nullptr);
+}
+
 int ssh_checkpoint_load(const char* path, ssx_sums_info_t* info, char* scene_name, size_t scene_name_size, char* options_text, size_t options_text_size,
                         double** sums_out, double** noise_s2_out) {
-	return ssh_checkpoint_load_spectral(path, info, scene_name, scene_name_size, options_text, options_text_size, sums_out, noise_s2_out, nullptr, nullptr, nullptr);
+	return ssh_checkpoint_load_moments(path, info, scene_name, scene_name_size, options_text, options_text_size, sums_out, noise_s2_out, nullptr, nullptr, nullptr, nullptr);
 }
 
 int ssh_sums_merge(double* dst, double* dst_s2, const double* src, const double* src_s2, const ssx_sums_info_t* src_info) {
@@ -196,6 +212,13 @@ int ssh_spectral_merge(double* dst_sums, uint32_t* dst_counts, const double* src
 	if (bins < 4u || bins > 64u || bins % 4u) { g_error = "ssh_spectral_merge: bins must be a multiple of 4 in 4..64"; return SSX_ERR_ARG; }
 	if ((!dst_sums) != (!src_sums) || (!dst_counts) != (!src_counts)) { g_error = "ssh_spectral_merge: sums and counts come in pairs of dst and src"; return SSX_ERR_ARG; }
 	ssx::spectral_merge(dst_sums, dst_counts, src_sums, src_counts, bins, *src_sums_info);
+	return SSX_OK;
+}
+
+int ssh_moments_merge(double* dst_q, const double* src_q, uint32_t bins, const ssx_sums_info_t* src_sums_info) {
+	if (!dst_q || !src_q || !src_sums_info || src_sums_info->struct_size != sizeof *src_sums_info) { g_error = "NULL argument or ssx_sums_info_t.struct_size mismatch"; return SSX_ERR_ARG; }
+	if (bins < 4u || bins > 64u || bins % 4u) { g_error = "ssh_moments_merge: bins must be a multiple of 4 in 4..64"; return SSX_ERR_ARG; }
+	ssx::moments_merge(dst_q, src_q, bins, *src_sums_info);
 	return SSX_OK;
 }
 

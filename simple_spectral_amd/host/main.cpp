@@ -31,14 +31,16 @@
 // Error bars for the bins (include/ssx.h "Spectral moments and region probes"), all with --spectral-bins=N: --spectral-variance-output=PATH.npy writes the variance
 // of every bin mean, float32 [height][width][N] (+inf where a sub-bin holds fewer than two samples); --probe=x0,y0,x1,y1 (half-open, row 0 = bottom; up to 32 of
 // them, region r = the r-th) with --probe-output=PATH.csv writes the pooled mean spectrum of each rectangle with its standard error, one line per region and bin:
-// region, bin, centre wavelength, mean, stderr, samples, unestimated.  Not with --tile-major, --rgb, --libm=glibc-2.35 or --resume (a checkpoint does not carry
-// the second moments).
+// region, bin, centre wavelength, mean, stderr, samples, unestimated.  Not with --tile-major, --rgb or --libm=glibc-2.35.  --checkpoint then also keeps the bins'
+// second moments behind them ("SSXCKPT3"), and --resume needs a checkpoint that holds them for the bin count in force (default: the checkpoint's count): one that
+// cannot be read, has no bins, no moments or another count is refused before anything renders.
 // A spectral stopping rule (include/ssx.h "Spectral noise figure"): --spectral-noise-target=X with --spectral-bins=N and --max-samples=K renders --noise-step
 // samples per pixel at a time until the RMS standard error of the pixels' bin means, relative to the mean bin flux, is at most X and the share of sub-bins that
 // hold two samples is at least --spectral-noise-coverage=C (default 0.99; 1.0 is legal but slow to reach), or K samples are done.  --spectral-noise-region=
 // x0,y0,x1,y1 (half-open, row 0 = bottom, repeatable) restricts the figure to the union of the rectangles; --spectral-noise-output=PATH.csv writes it per bin:
-// bin, centre wavelength, rel, EV, EM, estimable, unestimated.  One stopping rule per run: not with --noise-target; not with --resume, --tile-major, --rgb or
-// --libm=glibc-2.35.
+// bin, centre wavelength, rel, EV, EM, estimable, unestimated.  One stopping rule per run: not with --noise-target; not with --tile-major, --rgb or
+// --libm=glibc-2.35.  With --resume of a checkpoint that holds the second moments (as above) the rule goes on from the checkpoint's samples: the figure is read
+// first -- a render that already meets the target renders nothing -- -spp is ignored as before and --max-samples caps the total.
 #include "renderer.hpp"
 
 #include "checkpoint.hpp"
@@ -86,6 +88,7 @@ void print_usage() {
 		"    `--demodulate[=1|2|4]` (with `--spectral-denoise`: filter illumination -- divide by the first-hit albedo per bin, <k> x <k> rays per pixel, before; multiply after)\n"
 		"    `--albedo-output=<file.npy>` (needs `--spectral-bins=<n>`: the first-hit albedo per wavelength bin)\n"
 		"    `--spectral-variance-output=<file.npy>` (needs `--spectral-bins=<n>`: the variance of every bin mean)\n"
+		"          (with this, `--probe` or `--spectral-noise-target`, `--checkpoint` also keeps the bins' second moments, and `--resume` needs a checkpoint that holds them)\n"
 		"    `--probe=<x0>,<y0>,<x1>,<y1>` (up to 32) `--probe-output=<file.csv>` (need `--spectral-bins=<n>`: each rectangle's pooled spectrum with its standard error)\n"
 		"    `--spectral-noise-target=<x> --spectral-bins=<n> --max-samples=<k> [--noise-step=<s>]` [`--spectral-noise-coverage=<c>`; default 0.99]\n"
 		"          [`--spectral-noise-region=<x0>,<y0>,<x1>,<y1>` ...] [`--spectral-noise-output=<file.csv>`] (render until the wavelength bins are converged)\n");
@@ -150,6 +153,11 @@ std::array<size_t, 4> to_rect(const char* flag, const std::string& v, size_t wid
 	return q;
 }
 
+struct Progressive;
+// `--resume` with an option that needs the second moments of the samples already rendered: the checkpoint has to hold them, for as many bins as are asked for
+// (default: as many as it holds).  Refuses (throws -2) with the reason; otherwise the bin count in force is the file's.
+void resume_needs_moments(const char* flag, Progressive* g);
+
 struct Progressive { // the flags of the progressive modes
 	std::string checkpoint, resume;
 	double noise_target = -1.0; // < 0: none
@@ -176,6 +184,30 @@ struct Progressive { // the flags of the progressive modes
 	std::vector<std::array<size_t, 4>> spectral_noise_regions; // --spectral-noise-region=x0,y0,x1,y1: the mask is their union; none = every pixel
 	std::string spectral_noise_output;     // --spectral-noise-output: "" = none
 };
+
+void resume_needs_moments(const char* flag, Progressive* g) {
+	const char* const head = "`%s` cannot be combined with `--resume`: \"%s\" does not carry the second moments of the samples already rendered";
+	ssx::Checkpoint ck;
+	try { ck = ssx::checkpoint_load(g->resume); }
+	catch (const ssx::HostError& e) {
+		std::fprintf(stderr, head, flag, g->resume.c_str());
+		std::fprintf(stderr, ": the checkpoint cannot be read: %s\n", e.message.c_str());
+		throw -2;
+	}
+	const uint32_t held = ck.spectral.bins;
+	if (!held || ck.moments.empty()) {
+		std::fprintf(stderr, head, flag, g->resume.c_str());
+		std::fprintf(stderr, !held ? ": it holds the pixel sums only, no wavelength bins (write it with `--checkpoint` and this option)!\n"
+		                           : ": it holds %u wavelength bins without their second moments (write it with `--checkpoint` and this option)!\n", held);
+		throw -2;
+	}
+	if (g->spectral_bins_given && g->spectral_bins != held) {
+		std::fprintf(stderr, head, flag, g->resume.c_str());
+		std::fprintf(stderr, " for another bin count: it holds %u wavelength bins, `--spectral-bins=%zu` was asked for!\n", held, g->spectral_bins);
+		throw -2;
+	}
+	g->spectral_bins = held; g->spectral_bins_given = true;
+}
 
 void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progressive* g) {
 	ArgList a;
@@ -338,10 +370,7 @@ void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progress
 	if (g->probes.empty() != g->probe_output.empty()) { std::fprintf(stderr, "`--probe=<x0>,<y0>,<x1>,<y1>` and `--probe-output=<file.csv>` need each other!\n"); throw -2; }
 	if (g->moments()) {
 		const char* const flag = !g->variance_output.empty() ? "--spectral-variance-output" : "--probe";
-		if (!g->resume.empty()) {
-			std::fprintf(stderr, "`%s` cannot be combined with `--resume`: a checkpoint does not carry the second moments of the samples already rendered!\n", flag);
-			throw -2;
-		}
+		if (!g->resume.empty()) resume_needs_moments(flag, g);
 		if (!g->spectral_bins_given) { std::fprintf(stderr, "`%s` needs `--spectral-bins=<n>`: it speaks of the wavelength bins of the render!\n", flag); throw -2; }
 		if (o->tile_major || o->rgb_mode || o->libm != SSX_LIBM_BUILD) {
 			std::fprintf(stderr, "`%s` cannot be combined with `--tile-major`, `--rgb` or `--libm=glibc-2.35`: such a render has no wavelength bins!\n", flag);
@@ -369,10 +398,7 @@ void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progress
 	if (spectral_stop) {
 		const char* const flag = "--spectral-noise-target";
 		if (g->noise_target >= 0.0) { std::fprintf(stderr, "`%s` cannot be combined with `--noise-target`: one stopping rule per run!\n", flag); throw -2; }
-		if (!g->resume.empty()) {
-			std::fprintf(stderr, "`%s` cannot be combined with `--resume`: a checkpoint does not carry the second moments of the samples already rendered!\n", flag);
-			throw -2;
-		}
+		if (!g->resume.empty()) resume_needs_moments(flag, g);
 		if (!g->spectral_bins_given) { std::fprintf(stderr, "`%s` needs `--spectral-bins=<n>`: it speaks of the wavelength bins of the render!\n", flag); throw -2; }
 		if (g->max_samples == 0) { std::fprintf(stderr, "`%s` needs `--max-samples=<n>`!\n", flag); throw -2; }
 		if (o->tile_major || o->rgb_mode || o->libm != SSX_LIBM_BUILD) {
@@ -414,7 +440,7 @@ int main(int argc, char* argv[]) {
 		if (prog.denoise || prog.spectral_denoise) renderer.set_noise_estimate(true);
 		const bool spectral_stop = prog.spectral_noise_target >= 0.0;
 		if (!prog.spectral_output.empty() || !prog.develop_output.empty() || prog.moments() || spectral_stop) renderer.set_spectral_bins(prog.spectral_bins);
-		if (prog.moments()) renderer.set_spectral_moments(true);
+		if (prog.moments() || (spectral_stop && !prog.resume.empty())) renderer.set_spectral_moments(true); // (before load_checkpoint: it takes Q up only with the moments on)
 		// what --develop-output applies, built (and refused) before the render: the observer's tables over the bins, times the filter, times the relighting gain
 		std::vector<float> develop_weights;
 		std::unique_ptr<ssx::ColorData> develop_color;
@@ -436,6 +462,19 @@ int main(int argc, char* argv[]) {
 			develop_weights.assign(w.begin(), w.end()); // (rounded to binary32 here, once)
 		}
 		bool stop_sent = false;
+		const bool needs_moments = prog.moments() || spectral_stop;
+		if (!prog.resume.empty()) {
+			try {
+				const bool bins = renderer.load_checkpoint(prog.resume);
+				if (!bins && (!prog.spectral_output.empty() || !prog.develop_output.empty())) // (checked when the arguments were read; the file has changed since)
+					throw ssx::HostError{ SSX_ERR_DATA, "it holds no wavelength bins of the count asked for" };
+				if (needs_moments && !renderer.moments_resumed()) throw ssx::HostError{ SSX_ERR_DATA, "it holds no second moments for the bin count asked for" };
+			}
+			catch (const ssx::HostError& e) { // not this render's checkpoint (or no checkpoint at all): bad data, as the reference exits on it
+				std::fprintf(stderr, "Cannot resume from \"%s\": %s\n", prog.resume.c_str(), e.message.c_str());
+				return -1;
+			}
+		}
 		if (prog.noise_target >= 0.0) {
 			const auto r = renderer.render_until(prog.noise_target, prog.noise_step, prog.max_samples, [&]() {
 				renderer.print_progress();
@@ -446,25 +485,17 @@ int main(int argc, char* argv[]) {
 			std::fprintf(stderr, "Noise %.6g after %zu samples per pixel (target %.6g).\n", r.second, r.first, prog.noise_target);
 		} else if (spectral_stop) {
 			const std::vector<uint8_t> mask = prog.spectral_noise_regions.empty() ? std::vector<uint8_t>() : renderer.mask_from_rects(prog.spectral_noise_regions);
+			if (!prog.resume.empty()) std::fprintf(stderr, "Resuming \"%s\": %zu samples per pixel done, at most %zu wanted.\n", prog.resume.c_str(), renderer.done_spp(), prog.max_samples);
 			const auto r = renderer.render_until_spectral(prog.spectral_noise_target, prog.noise_step, prog.max_samples, mask, prog.spectral_noise_coverage, [&]() {
 				renderer.print_progress();
 				if (!g_abort || stop_sent) return false;
 				stop_sent = true; std::fprintf(stderr, "\nAborting: saving the partial render ...\n");
 				return true;
-			});
+			}, !prog.resume.empty());
 			std::fprintf(stderr, "Spectral noise %.6g (coverage %.6g) after %zu samples per pixel (target %.6g).\n", r.noise, r.coverage, r.spp, prog.spectral_noise_target);
 			if (!prog.spectral_noise_output.empty()) renderer.save_spectral_noise_csv(prog.spectral_noise_output, renderer.spectral_noise(mask));
 		} else {
 			if (!prog.resume.empty()) {
-				try {
-					const bool bins = renderer.load_checkpoint(prog.resume);
-					if (!bins && (!prog.spectral_output.empty() || !prog.develop_output.empty())) // (checked when the arguments were read; the file has changed since)
-						throw ssx::HostError{ SSX_ERR_DATA, "it holds no wavelength bins of the count asked for" };
-				}
-				catch (const ssx::HostError& e) { // not this render's checkpoint (or no checkpoint at all): bad data, as the reference exits on it
-					std::fprintf(stderr, "Cannot resume from \"%s\": %s\n", prog.resume.c_str(), e.message.c_str());
-					return -1;
-				}
 				const size_t done = renderer.done_spp();
 				std::fprintf(stderr, "Resuming \"%s\": %zu samples per pixel done, %zu wanted.\n", prog.resume.c_str(), done, options.spp);
 				if (options.spp > done) renderer.render_continue(options.spp - done);

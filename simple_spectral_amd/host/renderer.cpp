@@ -32,7 +32,7 @@ void Framebuffer::save(const std::string& path) const { save_image(path, pixels_
 	X(create) X(destroy) X(upload_scene) X(render_start) X(render_stop) X(is_rendering) X(progress) X(render_wait) X(last_error) \
 	X(device_framebuffer) X(device_index) X(read_framebuffer) X(accumulate_peer) X(done_spp) X(done_tiles) X(reduce_rccl) \
 	X(render_continue) X(sums_export) X(sums_import) X(set_noise_estimate) X(noise_info) \
-	X(set_spectral_bins) X(spectral_read) X(spectral_import) X(set_spectral_moments) X(spectral_variance) X(spectral_probe) X(probe_arrays) X(spectral_noise) X(spectral_noise_reduce) \
+	X(set_spectral_bins) X(spectral_read) X(spectral_import) X(set_spectral_moments) X(spectral_variance) X(spectral_moments_import) X(spectral_probe) X(probe_arrays) X(spectral_noise) X(spectral_noise_reduce) \
 	X(guides) X(denoise_images) X(denoise) X(denoise_channels) X(denoise_spectral) \
 	X(develop_images) X(spectral_develop) X(albedo_bins) X(denoise_spectral_demod) X(spectral_develop_demod)
 
@@ -326,6 +326,7 @@ void Renderer::set_spectral_bins(size_t bins) {
 	wait_workers_();
 	for (ssx_ctx* c : ctxs_) check_(api_->set_spectral_bins(c, static_cast<uint32_t>(bins)), "ssx_set_spectral_bins", c);
 	spectral_bins_ = bins;
+	if (!bins) spectral_moments_ = false; // (the library switches the moments off with the bins)
 }
 
 // One loop over the contexts for every reader of the bins: ssx_spectral_read on each, the shares merged by ownership into whichever of the three arrays are
@@ -377,6 +378,18 @@ void Renderer::save_spectral_image(const std::string& path, const std::vector<fl
 void Renderer::set_spectral_moments(bool on) {
 	wait_workers_();
 	for (ssx_ctx* c : ctxs_) check_(api_->set_spectral_moments(c, on ? 1 : 0), "ssx_set_spectral_moments", c);
+	spectral_moments_ = on;
+}
+
+std::vector<double> Renderer::gather_moments_() {
+	const size_t pixels = options.res[0] * options.res[1], B = spectral_bins_;
+	std::vector<double> q(pixels * B, 0.0), part(pixels * B);
+	for (size_t d = 0; d < ctxs_.size(); ++d) { // every pixel from the device that owns it, bit for bit (merge_owned: the one merge by ownership mask)
+		ssx_spectral_info_t qi{};
+		check_(api_->spectral_variance(ctxs_[d], &qi, nullptr, part.data()), "ssx_spectral_variance", ctxs_[d]);
+		merge_owned(q.data(), part.data(), B, owner_(d));
+	}
+	return q;
 }
 
 std::vector<float> Renderer::spectral_variance() {
@@ -411,14 +424,10 @@ Renderer::Probe Renderer::probe(const std::vector<uint8_t>& labels, size_t regio
 		check_(api_->spectral_probe(root, labels.data(), r32, r.SS.data(), r.NN.data(), r.VV.data(), r.UU.data()), "ssx_spectral_probe", root);
 	} else { // S, N (gather_bins_) and Q from the device that owns the pixel, bit for bit; then the pure probe on device 0
 		level_devices(); // (a stopped render: one sample count behind every pixel)
-		std::vector<double> sums, q(pixels * B, 0.0), part(pixels * B);
+		std::vector<double> sums;
 		std::vector<uint32_t> counts;
 		info = gather_bins_(nullptr, &sums, &counts);
-		for (size_t d = 0; d < ctxs_.size(); ++d) {
-			ssx_spectral_info_t qi{};
-			check_(api_->spectral_variance(ctxs_[d], &qi, nullptr, part.data()), "ssx_spectral_variance", ctxs_[d]);
-			merge_owned(q.data(), part.data(), B, owner_(d));
-		}
+		const std::vector<double> q = gather_moments_();
 		check_(api_->probe_arrays(root, w32_(), h32_(), static_cast<uint32_t>(B), sums.data(), q.data(), counts.data(), labels.data(), r32, r.SS.data(), r.NN.data(), r.VV.data(), r.UU.data()),
 		       "ssx_probe_arrays", root);
 	}
@@ -494,16 +503,21 @@ std::vector<uint8_t> Renderer::mask_from_rects(const std::vector<std::array<size
 	return mask;
 }
 
-Renderer::UntilSpectral Renderer::render_until_spectral(double target, size_t step, size_t max_spp, const std::vector<uint8_t>& mask, double min_coverage, const std::function<bool()>& tick) {
+Renderer::UntilSpectral Renderer::render_until_spectral(double target, size_t step, size_t max_spp, const std::vector<uint8_t>& mask, double min_coverage, const std::function<bool()>& tick,
+                                                        bool resume) {
 	if (step == 0 || max_spp == 0) throw HostError{ SSX_ERR_ARG, "render_until_spectral: step and max_spp must be positive" };
 	if (!spectral_bins_) throw HostError{ SSX_ERR_STATE, "render_until_spectral: spectral output is off (set_spectral_bins)" };
 	if (!mask.empty() && mask.size() != options.res[0] * options.res[1]) throw HostError{ SSX_ERR_ARG, "render_until_spectral: mask is not [height][width]" };
-	set_spectral_moments(true);
 	UntilSpectral r;
 	r.noise = r.coverage = NAN;
+	if (resume) { // what the devices hold is taken up: no ssx_render_start, and the figure first -- it may already meet the target
+		const SpectralNoise now = spectral_noise(mask); // (throws SSX_ERR_STATE with the library's reason when the moments are not valid)
+		r.noise = now.noise; r.coverage = now.coverage;
+		if ((r.noise <= target && r.coverage >= min_coverage) || done_spp() >= max_spp) { r.spp = done_spp(); return r; }
+	} else set_spectral_moments(true);
 	bool stopped = false;
 	for (size_t n = 0;; ++n) {
-		if (n == 0) start_(step, step); else render_continue(step);
+		if (n == 0 && !resume) start_(step, step); else render_continue(step);
 		while (tick && is_rendering()) {
 			if (!stopped && tick()) { render_stop(); stopped = true; }
 			std::this_thread::sleep_for(std::chrono::milliseconds(10));
@@ -713,6 +727,13 @@ void Renderer::save_checkpoint(const std::string& path) {
 		have_bins = api_->spectral_read(ctxs_[d], &si, nullptr, nullptr, nullptr) == SSX_OK; // (SSX_ERR_STATE: continuable sums without bins)
 	}
 	if (have_bins) ck.spectral = gather_bins_(nullptr, &ck.spectral_sums, &ck.spectral_counts);
+	// their second moments, when every device holds valid ones: the same merge
+	bool have_moments = have_bins && spectral_moments_;
+	for (size_t d = 0; have_moments && d < ctxs_.size(); ++d) {
+		ssx_spectral_info_t si{};
+		have_moments = api_->spectral_variance(ctxs_[d], &si, nullptr, nullptr) == SSX_OK; // (SSX_ERR_STATE: valid bins without moments)
+	}
+	if (have_moments) ck.moments = gather_moments_();
 	ck.scene_name = options.scene_name;
 	ck.options_text = "observer=" + std::to_string(options.observer) + "\ntexture=" + options.texture_path + "\nlight_scale=" + std::to_string(options.light_scale) +
 	                  "\nuplift=" + std::to_string(options.uplift) + "\nrgb=" + (options.rgb_mode ? "1" : "0") +
@@ -724,12 +745,16 @@ bool Renderer::load_checkpoint(const std::string& path) {
 	wait_workers_();
 	const Checkpoint ck = checkpoint_load(path);
 	const bool take_bins = ck.spectral.bins != 0u && spectral_bins_ == ck.spectral.bins;
+	const bool take_moments = take_bins && spectral_moments_ && !ck.moments.empty();
+	moments_resumed_ = false;
 	for (size_t d = 0; d < ctxs_.size(); ++d) {
 		const ssx_render_params p = params_for_(d, ck.info.done_spp ? ck.info.done_spp : 1u, 0);
 		check_(api_->sums_import(ctxs_[d], &p, &ck.info, ck.sums.data(), ck.s2.empty() ? nullptr : ck.s2.data()), "ssx_sums_import", ctxs_[d]);
 		// every device takes its own tiles from the whole array, however many devices wrote it
 		if (take_bins) check_(api_->spectral_import(ctxs_[d], &ck.spectral, ck.spectral_sums.data(), ck.spectral_counts.data()), "ssx_spectral_import", ctxs_[d]);
+		if (take_moments) check_(api_->spectral_moments_import(ctxs_[d], &ck.spectral, ck.moments.data()), "ssx_spectral_moments_import", ctxs_[d]);
 	}
+	moments_resumed_ = take_moments;
 	time_start_ = std::chrono::steady_clock::now();
 	started_ = true; need_join_ = false;
 	expected_spp_ = ck.info.done_spp;

@@ -86,14 +86,19 @@ public:
 	void level_devices();
 	// One file with the sums of all devices, merged by ownership (host/checkpoint.hpp), after level_devices().  Not while rendering.  When every device holds
 	// valid wavelength bins (set_spectral_bins before the render, or a load_checkpoint that took them up) the file carries them too, merged the same way
-	// ("SSXCKPT2"); otherwise it is the file it always was.
+	// ("SSXCKPT2"); otherwise it is the file it always was.  When every device also holds valid second moments (set_spectral_moments before the render, or a
+	// load_checkpoint that took them up) their Q follows the bins, read through ssx_spectral_variance's q and merged the same way ("SSXCKPT3").
 	void save_checkpoint(const std::string& path);
 	// Every device takes its own tiles from the file's array; render_wait() then yields the checkpointed image, render_continue goes on from it.
 	// Throws HostError with the library's reason when the file belongs to another scene, size, seed or set of flags.
 	// A file with wavelength bins, read with set_spectral_bins(its count) in force: every device also takes the bins of its tiles (ssx_spectral_import; the
 	// number of devices may differ from the writer's), and spectral_image, denoise_spectral, develop and a later save_checkpoint go on as after a render of
 	// those samples.  Returns whether the bins were taken up; when not (no bins in the file, spectral output off, another bin count) the resume is the plain one.
+	// A file with the second moments, read with set_spectral_moments(true) in force and the bins taken up: every device also takes the Q of its tiles
+	// (ssx_spectral_moments_import), and spectral_variance, probe, spectral_noise and render_until_spectral(resume) go on as after a render of those samples with
+	// the moments on; moments_resumed() says whether.
 	bool load_checkpoint(const std::string& path);
+	bool moments_resumed() const { return moments_resumed_; }
 	void set_noise_estimate(bool on);        // ssx_set_noise_estimate on every device
 	// sqrt(sum v / n) / (sum A/N / n) over all devices (include/ssx.h ssx_noise_info); v_map: the per-pixel variances [height][width]
 	double noise(std::vector<double>* v_map = nullptr);
@@ -142,8 +147,13 @@ public:
 	// many bins from stopping on the few sub-bins that happen to hold two samples after one step; 1.0 is legal but slow to reach -- it needs two samples in every
 	// sub-bin of every pixel.  A NaN figure (a non-finite flux, an empty mask) never stops the render: it runs to max_spp.  Returns the count and the last
 	// figure read (NaN when the first step was stopped by tick).  Deterministic: the decision reads only S, Q and N.
+	// resume: the render goes on from what the devices hold -- a load_checkpoint that took the moments up (moments_resumed()), or an earlier run of this loop --
+	// instead of starting over: nothing is reset, valid moments are required (HostError SSX_ERR_STATE otherwise), and the figure is read BEFORE the first step: a
+	// resumed render that already meets the target renders nothing.  Then `step` at a time as above: from a count that is a multiple of `step` the loop reads the
+	// figure at the counts an uninterrupted run reads it at, and ends on the same bits.
 	struct UntilSpectral { size_t spp = 0; double noise = 0.0, coverage = 0.0; };
-	UntilSpectral render_until_spectral(double target, size_t step, size_t max_spp, const std::vector<uint8_t>& mask = {}, double min_coverage = 0.99, const std::function<bool()>& tick = {});
+	UntilSpectral render_until_spectral(double target, size_t step, size_t max_spp, const std::vector<uint8_t>& mask = {}, double min_coverage = 0.99, const std::function<bool()>& tick = {},
+	                                    bool resume = false);
 
 
 	// Denoising (include/ssx.h: first-hit guide buffers and the variance-guided a-trous filter).
@@ -186,6 +196,10 @@ private:
 	bool started_ = false;
 	bool need_join_ = false;    // a worker of every context is running or waits to be joined
 	size_t spectral_bins_ = 0;
+	bool spectral_moments_ = false; // set_spectral_moments is in force (switching the bins off switches it off)
+	bool moments_resumed_ = false;  // the last load_checkpoint took the second moments up
+	// ssx_spectral_variance's q of every device merged by ownership (the devices level): Q [height][width][bins]
+	std::vector<double> gather_moments_();
 	std::vector<float> demod_weights_(const DemodParams& demod) const; // demod.weights_xyz, or the render's own observer's develop weights over the bins
 	size_t expected_spp_ = 0;   // the count the running (or last) call renders to: what render_wait compares ssx_done_spp with
 	ssx_render_params params_for_(size_t d, size_t spp, size_t spp_per_launch) const;

@@ -375,6 +375,40 @@ def load_checkpoint_file_spectral(path):
     return info, sums, s2, name.value.decode(), text.value.decode(), sinfo, bins, counts
 
 
+def load_checkpoint_file_moments(path):
+    """ssh_checkpoint_load_moments -> load_checkpoint_file_spectral's eight values and Q float64 [H, W, B], the bins' second moments; None from a checkpoint
+    without them (magic SSXCKPT1 or SSXCKPT2)."""
+    host = _capi.host_lib()
+    info, sinfo = _capi.SsxSumsInfo(), _capi.SsxSpectralInfo()
+    name, text = C.create_string_buffer(256), C.create_string_buffer(4096)
+    ps, p2, pb, pn, pq = C.POINTER(C.c_double)(), C.POINTER(C.c_double)(), C.POINTER(C.c_double)(), C.POINTER(C.c_uint32)(), C.POINTER(C.c_double)()
+    rc = host.ssh_checkpoint_load_moments(os.fsencode(path), C.byref(info), name, len(name), text, len(text), C.byref(ps), C.byref(p2),
+                                          C.byref(sinfo), C.byref(pb), C.byref(pn), C.byref(pq))
+    if rc != 0:
+        raise SsxError(rc, host.ssh_last_error().decode())
+    try:
+        H, W, B = info.height, info.width, sinfo.bins
+        sums = np.ctypeslib.as_array(ps, shape=(H, W, 4)).copy()
+        s2 = np.ctypeslib.as_array(p2, shape=(H, W)).copy() if p2 else None
+        bins = np.ctypeslib.as_array(pb, shape=(H, W, B)).copy() if pb else None
+        counts = np.ctypeslib.as_array(pn, shape=(H, W, B // 4)).copy() if pn else None
+        q = np.ctypeslib.as_array(pq, shape=(H, W, B)).copy() if pq else None
+    finally:
+        for p in (ps, p2, pb, pn, pq):
+            if p:
+                host.ssh_free(p)
+    return info, sums, s2, name.value.decode(), text.value.decode(), sinfo, bins, counts, q
+
+
+def merge_moments(dst_q, src_q, src_info):
+    """ssh_moments_merge: merge_sums' rule for the bins' second moments -- Q float64 [H, W, B] of the pixels src_info's exporter owns (an SsxSumsInfo: export_sums'
+    of the same context), bit for bit."""
+    assert dst_q.dtype == np.float64 and dst_q.flags.c_contiguous and src_q.dtype == np.float64 and src_q.flags.c_contiguous and dst_q.shape == src_q.shape
+    rc = _capi.host_lib().ssh_moments_merge(dst_q.ctypes.data, src_q.ctypes.data, src_q.shape[2], C.byref(src_info))
+    if rc != 0:
+        raise SsxError(rc, _capi.host_lib().ssh_last_error().decode())
+
+
 def merge_spectral(dst_sums, dst_counts, src_sums, src_counts, src_info):
     """ssh_spectral_merge: merge_sums' rule for the wavelength bins -- sums float64 [H, W, B] and counts uint32 [H, W, B / 4] of the pixels src_info's exporter
     owns (an SsxSumsInfo: export_sums' of the same context), bit for bit."""
@@ -528,30 +562,58 @@ class Renderer:
             raise ValueError("import_spectral: sums must have shape [info.height, info.width, info.bins], counts [info.height, info.width, info.bins / 4]")
         self._check(self._lib.ssx_spectral_import(self._ctx, C.byref(info), sums.ctypes.data, counts.ctypes.data))
 
+    def holds_moments(self):
+        """Whether the context holds valid second moments of exactly the samples behind its bins (what export_moments needs, and save_checkpoint to keep them)."""
+        if not getattr(self, "_spectral_bins", 0):
+            return False
+        return self._lib.ssx_spectral_variance(self._ctx, C.byref(_capi.SsxSpectralInfo()), None, None) == 0
+
+    def export_moments(self):
+        """ssx_spectral_variance's raw state -> (SsxSpectralInfo, Q float64 [H, W, B]): what import_moments takes back and a checkpoint keeps; zeros for pixels the
+        context does not own (merge_moments combines the ranks')."""
+        info, _, q = self.spectral_variance(q=True)
+        return info, q
+
+    def import_moments(self, info, q):
+        """ssx_spectral_moments_import, directly on top of import_spectral (set_spectral_moments before or after the two imports): the context takes the second
+        moments of the tiles it owns from the whole-image array and then stands where a render of info.done_spp samples with the moments on would have left it --
+        render_continue carries Q on; spectral_variance, probe and spectral_noise work.  SsxError with the library's reason -- the field, or the rule of the
+        consistency check -- when they do not belong to the imported bins; the moments are invalid then, bins and sums untouched."""
+        q = np.ascontiguousarray(q, dtype=np.float64)
+        if q.size != info.width * info.height * info.bins:
+            raise ValueError("import_moments: q must have shape [info.height, info.width, info.bins]")
+        self._check(self._lib.ssx_spectral_moments_import(self._ctx, C.byref(info), q.ctypes.data))
+
     def save_checkpoint(self, path):
-        """The sums (and the noise estimate's S2) into one file (libssx_host.so ssh_checkpoint_save_spectral; host/checkpoint.hpp has the format); with them
-        the wavelength bins when the context holds valid ones -- otherwise the file is the one it always was."""
+        """The sums (and the noise estimate's S2) into one file (libssx_host.so ssh_checkpoint_save_moments; host/checkpoint.hpp has the format); with them
+        the wavelength bins when the context holds valid ones, and behind those their second moments when it holds valid ones -- otherwise the file is the one it
+        always was."""
         info, sums, s2 = self.export_sums()
         sinfo, bins, counts = self.export_spectral() if self.holds_spectral() else (None, None, None)
+        q = self.export_moments()[1] if sinfo is not None and self.holds_moments() else None
         o = self.options
         text = "observer=%d\ntexture=%s\nlight_scale=%r\nuplift=%s\nrender_mode=%s\nexplicit_light_sampling=%d\n" % (
             o.observer, o.texture if isinstance(o.texture, str) else "", o.light_scale, o.uplift, o.render_mode, int(o.explicit_light_sampling))
         host = _capi.host_lib()
-        rc = host.ssh_checkpoint_save_spectral(os.fsencode(path), C.byref(info), o.scene_name.encode(), text.encode(), sums.ctypes.data, None if s2 is None else s2.ctypes.data,
-                                               None if sinfo is None else C.byref(sinfo), None if bins is None else bins.ctypes.data,
-                                               None if counts is None else counts.ctypes.data)
+        rc = host.ssh_checkpoint_save_moments(os.fsencode(path), C.byref(info), o.scene_name.encode(), text.encode(), sums.ctypes.data, None if s2 is None else s2.ctypes.data,
+                                              None if sinfo is None else C.byref(sinfo), None if bins is None else bins.ctypes.data,
+                                              None if counts is None else counts.ctypes.data, None if q is None else q.ctypes.data)
         if rc != 0:
             raise SsxError(rc, host.ssh_last_error().decode())
 
     def load_checkpoint(self, path):
         """Reads a checkpoint and imports it (SsxError SSX_ERR_DATA for a damaged file, SSX_ERR_ARG with the library's reason for one
         of another scene, size, seed or set of flags).  Returns its SsxSumsInfo.  A file with wavelength bins, read while set_spectral_bins(its count) is in
-        force: the bins are taken up too (import_spectral); self.spectral_resumed says whether."""
-        info, sums, s2, _, _, sinfo, bins, counts = load_checkpoint_file_spectral(path)
+        force: the bins are taken up too (import_spectral); self.spectral_resumed says whether.  A file with their second moments, read with
+        set_spectral_moments(True) in force and the bins taken up: Q is taken up too (import_moments); self.moments_resumed says whether."""
+        info, sums, s2, _, _, sinfo, bins, counts, q = load_checkpoint_file_moments(path)
         self.import_sums(info, sums, s2)
         self.spectral_resumed = bool(sinfo.bins) and sinfo.bins == getattr(self, "_spectral_bins", 0)
+        self.moments_resumed = self.spectral_resumed and q is not None and getattr(self, "_spectral_moments", False)
         if self.spectral_resumed:
             self.import_spectral(sinfo, bins, counts)
+        if self.moments_resumed:
+            self.import_moments(sinfo, q)
         return info
 
     def noise(self):
@@ -587,6 +649,8 @@ class Renderer:
         """ssx_set_spectral_bins: n wavelength bins per pixel (a multiple of 4 up to 64) for the renders that follow; 0 switches it off."""
         self._check(self._lib.ssx_set_spectral_bins(self._ctx, int(n)))
         self._spectral_bins = int(n)
+        if not n:
+            self._spectral_moments = False   # (the library switches the moments off with the bins)
 
     def spectral_read(self, sums=False):
         """ssx_spectral_read -> (SsxSpectralInfo, mean float32 [H, W, B], counts uint32 [H, W, B/4], sums float64 [H, W, B] or None)."""
@@ -611,6 +675,7 @@ class Renderer:
     def set_spectral_moments(self, enable=True):
         """ssx_set_spectral_moments: keep the second moments of the hero fluxes beside the bins, for the renders that follow (after set_spectral_bins)."""
         self._check(self._lib.ssx_set_spectral_moments(self._ctx, int(bool(enable))))
+        self._spectral_moments = bool(enable)
 
     def spectral_variance(self, q=False):
         """ssx_spectral_variance -> (SsxSpectralInfo, var float32 [H, W, B], Q float64 [H, W, B] or None): the variance of every bin mean (+inf where a sub-bin holds
@@ -712,14 +777,24 @@ class Renderer:
                                                         EV.ctypes.data, EM.ctypes.data, PP.ctypes.data, PU.ctypes.data))
         return EV, EM, PP, PU
 
-    def render_until_spectral(self, target, step, max_spp, mask=None, min_coverage=0.99):
+    def render_until_spectral(self, target, step, max_spp, mask=None, min_coverage=0.99, resume=False):
         """Renders `step` samples per pixel at a time, with the moments on (set_spectral_bins first), until spectral_noise(mask) gives noise <= target and coverage
         >= min_coverage -- checked after EVERY step, the first included -- or done_spp() >= max_spp.  Returns (done_spp, noise, coverage).  min_coverage is the
         user's parameter, not a tolerance: it keeps a render with many bins from stopping on the few sub-bins that hold two samples after one step; 1.0 is legal
-        but slow to reach (two samples in every sub-bin of every pixel).  A NaN figure never stops the render.  Deterministic: the decision reads only S, Q, N."""
+        but slow to reach (two samples in every sub-bin of every pixel).  A NaN figure never stops the render.  Deterministic: the decision reads only S, Q, N.
+        resume=True: the render goes on from what the context holds (a load_checkpoint that took the moments up, or an earlier run of this loop) instead of
+        starting over -- no ssx_render_start; valid moments are required (SsxError SSX_ERR_STATE otherwise); the figure is read FIRST, so a resumed render that
+        already meets the target renders nothing; then `step` at a time as above."""
         if step < 1 or max_spp < 1:
             raise ValueError("render_until_spectral: step and max_spp must be positive")
         mask = self._noise_mask(mask)
+        if resume:
+            while True:
+                noise, coverage, _ = self.spectral_noise(mask)
+                if (noise <= target and coverage >= min_coverage) or self.done_spp() >= max_spp:
+                    return self.done_spp(), noise, coverage
+                self.render_continue(step)
+                self.render_wait()
         self.set_spectral_moments(True)
         self._check(self._lib.ssx_render_start(self._ctx, C.byref(self.params(spp=int(step), spp_per_launch=int(step)))))
         while True:
