@@ -778,6 +778,57 @@ int ssx_spectral_noise(ssx_ctx* ctx, const uint8_t* mask /* [H][W] or NULL */, d
 int ssx_spectral_noise_reduce(ssx_ctx* ctx, uint32_t tiles, uint32_t bins, const double* tEV, const double* tEM, const uint32_t* tPP, const uint32_t* tPU /* [tiles][bins] */,
                               double* EV, double* EM, uint64_t* PP, uint64_t* PU /* [bins] */);
 
+/* ---- Comparing two spectral renders: bin by bin, with error bars and z-scores (appended; same ABI version) -------------------------------------------
+ * Two renders of one view -- two uplifts, two observers, two versions of the code -- differ somewhere; whether the difference exceeds the noise is a question
+ * for S, Q and N of both.  The probes give the difference of two pooled means; they cannot see a structured difference that cancels inside the region, and they
+ * give no per-pixel map.  Binary64 with IEEE + - * / only, no contraction, the operations in the order written, no square root on the device (the hosts take
+ * roots): a restatement in numpy gives the same bits (tests/spectral_compare_ref.py).  Notation as above.
+ *
+ * INPUTS.  Two array sets X in {A, B}, row-major, row 0 = bottom: S_X, Q_X double [height][width][B], N_X uint32 [height][width][M], B in {4, 8, ..., 64}, M = B /
+ *   4; width, height and B are those of both sets, the sample counts may differ (the normal case).  labels as in PROBE (R <= 32, 255: none).  t2: the squared z
+ *   threshold, finite and >= 0.
+ * PER CELL.  For pixel p and bin b, with m = b % M and nX = N_X[p][m]: the cell is COMPARABLE iff nA >= 2 && nB >= 2.  For a comparable cell, with qX, eX =
+ *   (qX / (double)(nX-1)) / (double)nX and muX = S_X[p][b] / (double)nX exactly as in "Spectral noise figure", PER PIXEL:
+ *       d  = muA - muB
+ *       v  = eA + eB
+ *       z2 = (v == 0.0 && d == 0.0) ? 0.0 : (d * d) / v
+ *   The special case is two black cells (samples that hit nothing count with f = 0: common): they agree, and must not produce a NaN.  v == 0 with d != 0 gives
+ *   +inf as IEEE gives it; a NaN stays a NaN.
+ * MAPS (optional, every pixel, labelled or not).  diff [height][width][B] float: (float)d for a comparable cell, 0.0f otherwise.  var [height][width][B] float:
+ *   (float)v for a comparable cell, +inf otherwise -- unknown, not zero, as in VARIANCE OF A BIN MEAN.
+ * PER REGION r AND BIN b, over the pixels labelled r, six arrays [R][B]:
+ *       DD = sum d      VV = sum v      X2 = sum z2             over the comparable cells, binary64
+ *       CC = the number of comparable cells        NC = the number of not-comparable cells        EX = the number of comparable cells with z2 > t2      (uint64)
+ *   The comparison is strict: a NaN does not count.  The order of the binary64 additions is PROBE's and part of the definition: within a row ascending i from
+ *   +0.0, one partial per row; the row partials in ascending j from +0.0; a row without a pixel of the region contributes its +0.0.
+ * DERIVED BY THE HOSTS (ssh_compare_derive, include/ssx_host.h), each NaN where its denominator is 0:
+ *       mean_diff = DD / CC        stderr = sqrt(VV) / CC        z = DD / sqrt(VV)        chi2 = X2 / CC        exceed = EX / CC        coverage = CC / (CC + NC)
+ *   and the per-pixel signed map zmap = diff / sqrt(var), 0 where var is +inf.  stderr uses that the pixels are independent.
+ * WHAT THE NUMBERS MEAN.  The model is Welch's: d / sqrt(v) with the two variances estimated separately, and the two renders must have INDEPENDENT samples.  With
+ *   few samples per sub-bin z2 is the square of a t-like variable with nu degrees of freedom (Welch-Satterthwaite), and under equality E[z2] = nu / (nu - 2),
+ *   not 1: chi2 is to be held against that, and no p-values are promised.  Two renders with the SAME SEED are positively correlated: v then overstates the variance
+ *   of d and every z is too small.  The fluxes are not Gaussian either: at a few samples per sub-bin the figures are indications.
+ *
+ * ON THE DEVICE: ssx_compare_rows_kernel, one workgroup per image row, classifies a chunk of the row 256 lanes wide -- reads and map writes contiguous across
+ * the lanes, every byte of S and Q fetched once -- stages d, v, z2 in LDS and walks the chunk in ascending i with one lane per (quantity pair, bin), the
+ * accumulators in LDS indexed by the label; ssx_compare_reduce_kernel, one lane per (quantity, r, b), walks j in ascending order.  No atomics. */
+
+/* The comparison as a pure function of its arguments (no scene needed, like ssx_probe_arrays): e.g. two checkpoints' arrays, or several devices' exports merged
+ * by ownership.  DD, VV, X2 (binary64), CC, NC, EX (uint64): [regions][bins].  diff, var: [height][width][bins] float, either may be NULL.  SSX_ERR_ARG, with
+ * ssx_last_error naming the field: bins not a multiple of 4 in 4..64, an empty or too large image, a NULL required pointer, regions outside 1..32, a label that is
+ * neither a region nor 255, a t2 that is negative, infinite or NaN.  SSX_ERR_STATE: a render runs. */
+int ssx_spectral_compare_arrays(ssx_ctx* ctx, uint32_t width, uint32_t height, uint32_t bins, const double* SA, const double* QA, const uint32_t* NA,
+                                const double* SB, const double* QB, const uint32_t* NB, const uint8_t* labels /* [H][W] */, uint32_t regions, double t2,
+                                double* DD, double* VV, double* X2, uint64_t* CC, uint64_t* NC, uint64_t* EX, float* diff, float* var);
+/* A is the context's own state: it exports S, Q and N row-major to device temporaries, as ssx_spectral_probe does, and runs the kernels of
+ * ssx_spectral_compare_arrays on them -- the same bits.  Pixels the context does not own have count 0 and are not comparable.  other_info describes B (what
+ * ssx_spectral_read or a checkpoint said of it).  It reads only: image, sums, bins and moments stay as they are, so an ssx_render_continue afterwards leaves the
+ * bits of a render that was never asked.  SSX_ERR_STATE, with the reasons of ssx_spectral_variance: spectral output or the moments are off, a render runs, or the
+ * context holds no valid bins or moments.  SSX_ERR_ARG, naming the field: other_info NULL or differing from the context in struct_size, width, height, bins, or in
+ * lambda_min or bin_width compared as bits (done_spp may differ); and what ssx_spectral_compare_arrays refuses. */
+int ssx_spectral_compare(ssx_ctx* ctx, const ssx_spectral_info_t* other_info, const double* SB, const double* QB, const uint32_t* NB, const uint8_t* labels /* [H][W] */,
+                         uint32_t regions, double t2, double* DD, double* VV, double* X2, uint64_t* CC, uint64_t* NC, uint64_t* EX, float* diff, float* var);
+
 /* ---- Diagnostics for the parity tests (not part of the reference's interface) ---------------------
  * ssx_debug_eval runs one building block of the path kernel -- the same device function the kernel
  * inlines -- on n items, one per lane: `in` holds in_words 32-bit words per item, `out` receives

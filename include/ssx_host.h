@@ -109,6 +109,16 @@ int ssh_probe_derive(uint32_t regions, uint32_t bins, const double* SS, const ui
  * in that order -- the bin's centre lambda_min + (b + 0.5) * bin_width in binary32 ("%.9g"), mean and stderr ("%.17g", "nan" for a NaN), NN and UU. */
 int ssh_probe_save_csv(const char* path, uint32_t regions, uint32_t bins, float lambda_min, float bin_width, const double* SS, const uint64_t* NN, const double* VV, const uint64_t* UU);
 
+/* The comparison of two spectral renders (ssx.h "Comparing two spectral renders"; DD, VV, X2, CC, NC, EX: [regions][bins] of ssx_spectral_compare /
+ * ssx_spectral_compare_arrays) as its readers take it: mean_diff, stderr, z, chi2, exceed and coverage [regions][bins] as DERIVED BY THE HOSTS defines them,
+ * binary64, each NaN where its denominator is 0; any of the six outputs may be NULL. */
+int ssh_compare_derive(uint32_t regions, uint32_t bins, const double* DD, const double* VV, const double* X2, const uint64_t* CC, const uint64_t* NC, const uint64_t* EX,
+                       double* mean_diff, double* std_err, double* z, double* chi2, double* exceed, double* coverage);
+/* ... and as a text file, what the CLI's --compare-output writes: the line "region,bin,wavelength,mean_diff,stderr,z,chi2,exceed,comparable,not_comparable", then
+ * one line per region and bin -- the bin's centre as ssh_probe_save_csv writes it, the five figures ("%.17g", "nan" for a NaN), CC and NC. */
+int ssh_compare_save_csv(const char* path, uint32_t regions, uint32_t bins, float lambda_min, float bin_width, const double* DD, const double* VV, const double* X2,
+                         const uint64_t* CC, const uint64_t* NC, const uint64_t* EX);
+
 /* The spectral noise figure's totals (ssx.h "Spectral noise figure"; EV, EM, PP, PU: [bins] of ssx_spectral_noise / ssx_spectral_noise_reduce) as their readers
  * take them: *noise, *coverage and rel[bins] as DERIVED BY THE HOSTS defines them, binary64, in that order; any of the three outputs may be NULL. */
 int ssh_spectral_noise_derive(uint32_t bins, const double* EV, const double* EM, const uint64_t* PP, const uint64_t* PU, double* noise, double* coverage, double* rel);

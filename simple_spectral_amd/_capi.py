@@ -121,7 +121,8 @@ HIP_SYMBOLS = ["ssx_create", "ssx_destroy", "ssx_upload_scene", "ssx_render_star
                "ssx_spectral_import",
                "ssx_set_spectral_moments", "ssx_spectral_variance", "ssx_spectral_probe", "ssx_probe_arrays",
                "ssx_spectral_noise", "ssx_spectral_noise_reduce",
-               "ssx_spectral_moments_import"]
+               "ssx_spectral_moments_import",
+               "ssx_spectral_compare", "ssx_spectral_compare_arrays"]
 (SSX_SWEEP_RCP, SSX_SWEEP_SQRT, SSX_SWEEP_INVERSESQRT, SSX_SWEEP_SIN, SSX_SWEEP_COS, SSX_SWEEP_ACOS, SSX_SWEEP_DIV_PI,
  SSX_SWEEP_RCP64, SSX_SWEEP_DIV_PAIRS, SSX_SWEEP_ACOS_SIN, SSX_SWEEP_SIN_PROOF, SSX_SWEEP_COS_PROOF, SSX_SWEEP_ACOS_PROOF) = range(1, 14)
 # ssx_debug_eval ops (include/ssx.h)
@@ -135,7 +136,8 @@ HOST_SYMBOLS = ["ssh_scene_create", "ssh_scene_create_ex", "ssh_scene_destroy", 
                 "ssh_develop_weights", "ssh_relight_gain", "ssh_emitter_spectrum",
                 "ssh_checkpoint_save_spectral", "ssh_checkpoint_load_spectral", "ssh_spectral_merge",
                 "ssh_probe_derive", "ssh_probe_save_csv", "ssh_spectral_noise_derive", "ssh_spectral_noise_save_csv",
-                "ssh_checkpoint_save_moments", "ssh_checkpoint_load_moments", "ssh_moments_merge"]
+                "ssh_checkpoint_save_moments", "ssh_checkpoint_load_moments", "ssh_moments_merge",
+                "ssh_compare_derive", "ssh_compare_save_csv"]
 
 _hip = None
 _host = None
@@ -180,6 +182,8 @@ def host_lib():
         lib.ssh_probe_save_csv.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_float, C.c_float, vp, vp, vp, vp]
         lib.ssh_spectral_noise_derive.argtypes = [C.c_uint32, vp, vp, vp, vp, vp, vp, vp]
         lib.ssh_spectral_noise_save_csv.argtypes = [C.c_char_p, C.c_uint32, C.c_float, C.c_float, vp, vp, vp, vp]
+        lib.ssh_compare_derive.argtypes = [C.c_uint32, C.c_uint32] + [vp] * 12
+        lib.ssh_compare_save_csv.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_float, C.c_float] + [vp] * 6
         lib.ssh_develop_weights.argtypes = [C.c_char_p, C.c_int, C.POINTER(SshSpectrum), C.c_uint32, C.POINTER(SshSpectrum), vp, C.c_int, C.c_uint32,
                                             C.c_float, C.c_float, vp, vp]
         lib.ssh_relight_gain.argtypes = [C.POINTER(SshSpectrum), C.POINTER(SshSpectrum), C.c_uint32, C.c_float, C.c_float, vp]
@@ -368,6 +372,9 @@ def hip_lib():
         if not override or hasattr(lib, "ssx_spectral_noise"):  # the spectral noise figure: tile partials and totals
             lib.ssx_spectral_noise.argtypes = [vp] * 10
             lib.ssx_spectral_noise_reduce.argtypes = [vp, C.c_uint32, C.c_uint32] + [vp] * 8
+        if not override or hasattr(lib, "ssx_spectral_compare"):  # comparing two spectral renders: region sums and maps
+            lib.ssx_spectral_compare.argtypes = [vp, C.POINTER(SsxSpectralInfo), vp, vp, vp, vp, C.c_uint32, C.c_double] + [vp] * 8
+            lib.ssx_spectral_compare_arrays.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32] + [vp] * 7 + [C.c_uint32, C.c_double] + [vp] * 8
         if not override or hasattr(lib, "ssx_spectral_moments_import"):  # the second moments through checkpoint and resume
             lib.ssx_spectral_moments_import.argtypes = [vp, C.POINTER(SsxSpectralInfo), vp]
         lib.ssx_kernel_variant.argtypes = [vp]

@@ -5,7 +5,7 @@
 // diagnostics are here; scene packing is in ssx_pack.h, RCCL in ssx_rccl.h, the pixel ownership rule in ssx_pixel_grid.h, continue / export /
 // import of the sums and the noise estimate (entry points and their kernels) in ssx_progressive.hip, the spectral output in ssx_spectral.hip,
 // the guide buffers and the denoising filter in ssx_denoise.hip, the develop of the spectral bins in ssx_develop.hip, their second moments, variances and
-// region probes in ssx_spectral_stats.hip, the spectral noise figure in ssx_spectral_noise.hip.
+// region probes in ssx_spectral_stats.hip, the spectral noise figure in ssx_spectral_noise.hip, the comparison of two spectral renders in ssx_spectral_compare.hip.
 #include "ssx_kernels.hip"
 #include "ssx_debug.hip"
 
@@ -146,7 +146,7 @@ struct ssx_ctx {
 	std::string spectral_note;          // why sums that can be continued come without spectral state (ssx_spectral_read says it)
 	float lambda_min = 0.0f, lambda_step = 0.0f; // of the uploaded scene
 	// spectral moments (ssx_set_spectral_moments; csrc/ssx_spectral_stats.hip): off -- then nothing below is allocated and no kernel of it runs.  Q[tile slot][bin][pixel of
-	// the tile] binary64, the layout of S.  d_probe: the row-major arrays, partials and results of ssx_spectral_probe / ssx_probe_arrays; nothing until one of them is called.
+	// the tile] binary64, the layout of S.  d_probe: the row-major arrays, partials and results of ssx_spectral_probe / ssx_probe_arrays and of ssx_spectral_compare / ssx_spectral_compare_arrays; nothing until one of them is called.
 	bool spectral_moments = false;
 	DeviceBuffer d_spectral_moments, d_probe;
 	std::string moments_note;           // why bins that are valid come without moments (ssx_spectral_variance and ssx_spectral_probe say it)
@@ -1476,3 +1476,4 @@ int ssx_kernel_info(ssx_ctx* ctx, int* vgprs, int* sgprs, int* lds_bytes, int* s
 #include "ssx_demod.hip"
 #include "ssx_spectral_stats.hip"
 #include "ssx_spectral_noise.hip"
+#include "ssx_spectral_compare.hip"

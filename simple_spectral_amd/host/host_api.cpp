@@ -256,6 +256,20 @@ int ssh_spectral_noise_save_csv(const char* path, uint32_t bins, float lambda_mi
 	catch (const ssx::HostError& e) { return report(e); }
 }
 
+int ssh_compare_derive(uint32_t regions, uint32_t bins, const double* DD, const double* VV, const double* X2, const uint64_t* CC, const uint64_t* NC, const uint64_t* EX,
+                       double* mean_diff, double* std_err, double* z, double* chi2, double* exceed, double* coverage) {
+	if (!DD || !VV || !X2 || !CC || !NC || !EX) { g_error = "NULL argument"; return SSX_ERR_ARG; }
+	ssx::compare_derive(regions, bins, DD, VV, X2, CC, NC, EX, mean_diff, std_err, z, chi2, exceed, coverage);
+	return SSX_OK;
+}
+
+int ssh_compare_save_csv(const char* path, uint32_t regions, uint32_t bins, float lambda_min, float bin_width, const double* DD, const double* VV, const double* X2,
+                         const uint64_t* CC, const uint64_t* NC, const uint64_t* EX) {
+	if (!path || !DD || !VV || !X2 || !CC || !NC || !EX) { g_error = "NULL argument"; return SSX_ERR_ARG; }
+	try { ssx::save_compare_csv(path, regions, bins, lambda_min, bin_width, DD, VV, X2, CC, NC, EX); return SSX_OK; }
+	catch (const ssx::HostError& e) { return report(e); }
+}
+
 int ssh_develop_weights(const char* data_dir, int observer, const ssh_spectrum_t* responses, uint32_t channels, const ssh_spectrum_t* filter, const double* gain,
                         int space, uint32_t bins, float lambda_min, float lambda_step, float* weights, double* weights64) {
 	if (!weights) { g_error = "NULL argument"; return SSX_ERR_ARG; }

@@ -310,4 +310,40 @@ void save_spectral_noise_csv(const std::string& path, size_t bins, float lambda_
 	if (std::fclose(f) != 0 || !ok) throw HostError{ SSX_ERR_DATA, "Could not write \"" + path + "\"" };
 }
 
+void compare_derive(size_t regions, size_t bins, const double* DD, const double* VV, const double* X2, const uint64_t* CC, const uint64_t* NC, const uint64_t* EX,
+                    double* mean_diff, double* std_err, double* z, double* chi2, double* exceed, double* coverage) {
+	const double nan = std::numeric_limits<double>::quiet_NaN();
+	for (size_t e = 0; e < regions * bins; ++e) {
+		const double c = static_cast<double>(CC[e]), root = std::sqrt(VV[e]);
+		const bool none = CC[e] == 0;
+		if (mean_diff) mean_diff[e] = none ? nan : DD[e] / c;
+		if (std_err) std_err[e] = none ? nan : root / c;
+		if (z) z[e] = root == 0.0 ? nan : DD[e] / root;
+		if (chi2) chi2[e] = none ? nan : X2[e] / c;
+		if (exceed) exceed[e] = none ? nan : static_cast<double>(EX[e]) / c;
+		if (coverage) coverage[e] = (CC[e] + NC[e] == 0) ? nan : c / static_cast<double>(CC[e] + NC[e]);
+	}
+}
+
+void compare_zmap(size_t n, const float* diff, const float* var, float* zmap) {
+	for (size_t e = 0; e < n; ++e) zmap[e] = std::isinf(var[e]) && var[e] > 0.0f ? 0.0f : diff[e] / std::sqrt(var[e]);
+}
+
+void save_compare_csv(const std::string& path, size_t regions, size_t bins, float lambda_min, float bin_width, const double* DD, const double* VV, const double* X2,
+                      const uint64_t* CC, const uint64_t* NC, const uint64_t* EX) {
+	const size_t n = regions * bins;
+	std::vector<double> mean_diff(n), std_err(n), z(n), chi2(n), exceed(n);
+	compare_derive(regions, bins, DD, VV, X2, CC, NC, EX, mean_diff.data(), std_err.data(), z.data(), chi2.data(), exceed.data(), nullptr);
+	FILE* f = std::fopen(path.c_str(), "w");
+	if (!f) throw HostError{ SSX_ERR_DATA, "Could not open \"" + path + "\" for writing" };
+	bool ok = std::fprintf(f, "region,bin,wavelength,mean_diff,stderr,z,chi2,exceed,comparable,not_comparable\n") > 0;
+	for (size_t r = 0; r < regions; ++r) for (size_t b = 0; b < bins; ++b) {
+		const size_t e = r * bins + b;
+		const float centre = lambda_min + (static_cast<float>(b) + 0.5f) * bin_width;
+		ok = std::fprintf(f, "%zu,%zu,%.9g,%s,%s,%s,%s,%s,%llu,%llu\n", r, b, static_cast<double>(centre), csv_number(mean_diff[e]).c_str(), csv_number(std_err[e]).c_str(),
+		                  csv_number(z[e]).c_str(), csv_number(chi2[e]).c_str(), csv_number(exceed[e]).c_str(), static_cast<unsigned long long>(CC[e]), static_cast<unsigned long long>(NC[e])) > 0 && ok;
+	}
+	if (std::fclose(f) != 0 || !ok) throw HostError{ SSX_ERR_DATA, "Could not write \"" + path + "\"" };
+}
+
 } // namespace ssx

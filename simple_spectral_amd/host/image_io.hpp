@@ -47,4 +47,16 @@ void spectral_noise_derive(size_t bins, const double* EV, const double* EM, cons
 // rel, EV and EM (%.17g: they read back to the same binary64; "nan" for a NaN), PP and PU.
 void save_spectral_noise_csv(const std::string& path, size_t bins, float lambda_min, float bin_width, const double* EV, const double* EM, const uint64_t* PP, const uint64_t* PU);
 
+// The comparison of two spectral renders for its readers (include/ssx.h "Comparing two spectral renders"), from the six [regions][bins] arrays:
+//     mean_diff = DD / CC     stderr = sqrt(VV) / CC     z = DD / sqrt(VV)     chi2 = X2 / CC     exceed = EX / CC     coverage = CC / (CC + NC)
+// in binary64, each NaN where its denominator is 0; any output may be NULL.
+void compare_derive(size_t regions, size_t bins, const double* DD, const double* VV, const double* X2, const uint64_t* CC, const uint64_t* NC, const uint64_t* EX,
+                    double* mean_diff, double* std_err, double* z, double* chi2, double* exceed, double* coverage);
+// the per-pixel signed map of n cells: zmap = diff / sqrt(var) in binary32, 0 where var is +inf (a cell that is not comparable)
+void compare_zmap(size_t n, const float* diff, const float* var, float* zmap);
+// ... as a text file: the line "region,bin,wavelength,mean_diff,stderr,z,chi2,exceed,comparable,not_comparable", then one line per region and bin -- the bin's
+// centre wavelength as save_probe_csv writes it, the five derived figures (%.17g; "nan" for a NaN, "inf" for an infinity), CC and NC.
+void save_compare_csv(const std::string& path, size_t regions, size_t bins, float lambda_min, float bin_width, const double* DD, const double* VV, const double* X2,
+                      const uint64_t* CC, const uint64_t* NC, const uint64_t* EX);
+
 } // namespace ssx

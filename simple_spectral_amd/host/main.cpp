@@ -41,6 +41,13 @@
 // bin, centre wavelength, rel, EV, EM, estimable, unestimated.  One stopping rule per run: not with --noise-target; not with --tile-major, --rgb or
 // --libm=glibc-2.35.  With --resume of a checkpoint that holds the second moments (as above) the rule goes on from the checkpoint's samples: the figure is read
 // first -- a render that already meets the target renders nothing -- -spp is ignored as before and --max-samples caps the total.
+// Comparing with another render (include/ssx.h "Comparing two spectral renders"): --compare-to=FILE.ckpt with --spectral-bins=N holds the finished render against
+// the bins, counts and second moments of that checkpoint, pixel by pixel and bin by bin.  --compare-output=PATH.csv writes one line per region and bin: region, bin,
+// centre wavelength, mean_diff, stderr, z, chi2, exceed, comparable, not_comparable; --compare-map-output=PATH.npy the signed per-pixel map diff / sqrt(var),
+// float32 [height][width][N] (0 where a cell is not comparable); --compare-threshold=Z (default 3) is the z beyond which a cell counts into `exceed`.  The regions
+// are the --probe rectangles (which then do not need --probe-output); without any the whole image is region 0.  It switches the second moments on.  Refused before
+// anything renders: a checkpoint that cannot be read, holds no second moments, or has another size, bin count, lambda_min or bin width; --tile-major, --rgb or
+// --libm=glibc-2.35.  A checkpoint of the same seed only draws a warning: the samples are then not independent and z is not calibrated.
 #include "renderer.hpp"
 
 #include "checkpoint.hpp"
@@ -49,6 +56,7 @@
 #include <array>
 #include <chrono>
 #include <csignal>
+#include <cstring>
 #include <memory>
 #include <cstdio>
 #include <string>
@@ -91,7 +99,9 @@ void print_usage() {
 		"          (with this, `--probe` or `--spectral-noise-target`, `--checkpoint` also keeps the bins' second moments, and `--resume` needs a checkpoint that holds them)\n"
 		"    `--probe=<x0>,<y0>,<x1>,<y1>` (up to 32) `--probe-output=<file.csv>` (need `--spectral-bins=<n>`: each rectangle's pooled spectrum with its standard error)\n"
 		"    `--spectral-noise-target=<x> --spectral-bins=<n> --max-samples=<k> [--noise-step=<s>]` [`--spectral-noise-coverage=<c>`; default 0.99]\n"
-		"          [`--spectral-noise-region=<x0>,<y0>,<x1>,<y1>` ...] [`--spectral-noise-output=<file.csv>`] (render until the wavelength bins are converged)\n");
+		"          [`--spectral-noise-region=<x0>,<y0>,<x1>,<y1>` ...] [`--spectral-noise-output=<file.csv>`] (render until the wavelength bins are converged)\n"
+		"    `--compare-to=<file.ckpt>` (needs `--spectral-bins=<n>`) [`--compare-output=<file.csv>`] [`--compare-map-output=<file.npy>`] [`--compare-threshold=<z>`; default 3]\n"
+		"          (the render against another one's checkpoint, bin by bin, with error bars and z-scores; regions: the `--probe` rectangles, else the whole image)\n");
 }
 
 struct ArgList {
@@ -178,11 +188,14 @@ struct Progressive { // the flags of the progressive modes
 	std::string variance_output; // --spectral-variance-output: "" = none
 	std::vector<std::array<size_t, 4>> probes; // --probe=x0,y0,x1,y1, in the order given
 	std::string probe_output;    // --probe-output: "" = none
-	bool moments() const { return !variance_output.empty() || !probe_output.empty(); } // what needs the second moments
+	bool moments() const { return !variance_output.empty() || !probe_output.empty() || !compare_to.empty(); } // what needs the second moments
 	double spectral_noise_target = -1.0;   // --spectral-noise-target: < 0 = none
 	double spectral_noise_coverage = 0.99; // --spectral-noise-coverage
 	std::vector<std::array<size_t, 4>> spectral_noise_regions; // --spectral-noise-region=x0,y0,x1,y1: the mask is their union; none = every pixel
 	std::string spectral_noise_output;     // --spectral-noise-output: "" = none
+	std::string compare_to, compare_output, compare_map_output; // --compare-to / --compare-output / --compare-map-output: "" = none
+	double compare_threshold = 3.0;        // --compare-threshold: Z; the library takes t2 = Z * Z
+	std::shared_ptr<ssx::Checkpoint> compare_other; // --compare-to's file, read when the arguments are checked
 };
 
 void resume_needs_moments(const char* flag, Progressive* g) {
@@ -367,9 +380,21 @@ void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progress
 		g->probes.push_back(q);
 	}
 	if (a.take("--probe-output", "", &v)) g->probe_output = v;
-	if (g->probes.empty() != g->probe_output.empty()) { std::fprintf(stderr, "`--probe=<x0>,<y0>,<x1>,<y1>` and `--probe-output=<file.csv>` need each other!\n"); throw -2; }
+	if (a.take("--compare-to", "", &v)) g->compare_to = v;
+	if (a.take("--compare-output", "", &v)) g->compare_output = v;
+	if (a.take("--compare-map-output", "", &v)) g->compare_map_output = v;
+	if (a.take("--compare-threshold", "", &v)) {
+		try { size_t used = 0; g->compare_threshold = std::stod(v, &used); if (used != v.size() || !(g->compare_threshold >= 0.0) || g->compare_threshold > 1e150) throw -2; }
+		catch (...) { std::fprintf(stderr, "Invalid value for --compare-threshold (a finite number >= 0)!\n"); throw -2; }
+	}
+	if (g->compare_to.empty() && (!g->compare_output.empty() || !g->compare_map_output.empty())) {
+		std::fprintf(stderr, "`--compare-output` and `--compare-map-output` need `--compare-to=<file.ckpt>`: they write that comparison!\n");
+		throw -2;
+	}
+	if ((g->probes.empty() != g->probe_output.empty()) && (g->compare_to.empty() || g->probes.empty())) { // (--compare-to takes its regions from --probe alone)
+		std::fprintf(stderr, "`--probe=<x0>,<y0>,<x1>,<y1>` and `--probe-output=<file.csv>` need each other!\n"); throw -2; }
 	if (g->moments()) {
-		const char* const flag = !g->variance_output.empty() ? "--spectral-variance-output" : "--probe";
+		const char* const flag = !g->variance_output.empty() ? "--spectral-variance-output" : !g->probe_output.empty() ? "--probe" : "--compare-to";
 		if (!g->resume.empty()) resume_needs_moments(flag, g);
 		if (!g->spectral_bins_given) { std::fprintf(stderr, "`%s` needs `--spectral-bins=<n>`: it speaks of the wavelength bins of the render!\n", flag); throw -2; }
 		if (o->tile_major || o->rgb_mode || o->libm != SSX_LIBM_BUILD) {
@@ -380,6 +405,34 @@ void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progress
 	if (a.take("--spectral-noise-target", "", &v)) {
 		try { size_t used = 0; g->spectral_noise_target = std::stod(v, &used); if (used != v.size() || !(g->spectral_noise_target >= 0.0)) throw -2; }
 		catch (...) { std::fprintf(stderr, "Invalid value for --spectral-noise-target (a number >= 0)!\n"); throw -2; }
+	}
+	if (!g->compare_to.empty()) { // the other render is read now: what cannot be compared is refused before anything renders
+		const char* const head = "`--compare-to` cannot compare with \"%s\": ";
+		ssx::Checkpoint ck;
+		try { ck = ssx::checkpoint_load(g->compare_to); }
+		catch (const ssx::HostError& e) {
+			std::fprintf(stderr, head, g->compare_to.c_str());
+			std::fprintf(stderr, "the checkpoint cannot be read: %s\n", e.message.c_str());
+			throw -2;
+		}
+		if (!ck.spectral.bins || ck.moments.empty()) {
+			std::fprintf(stderr, head, g->compare_to.c_str());
+			if (!ck.spectral.bins) std::fprintf(stderr, "it holds the pixel sums only, no wavelength bins and no second moments Q (write it with `--checkpoint` and `--spectral-variance-output`, `--probe` or `--compare-to`)!\n");
+			else std::fprintf(stderr, "it holds %u wavelength bins without their second moments Q (write it with `--checkpoint` and `--spectral-variance-output`, `--probe` or `--compare-to`)!\n", ck.spectral.bins);
+			throw -2;
+		}
+		if (ck.spectral.width != o->res[0] || ck.spectral.height != o->res[1]) {
+			std::fprintf(stderr, head, g->compare_to.c_str());
+			std::fprintf(stderr, "the size differs: it holds %u x %u pixels, this render has %zu x %zu!\n", ck.spectral.width, ck.spectral.height, static_cast<size_t>(o->res[0]), static_cast<size_t>(o->res[1]));
+			throw -2;
+		}
+		if (ck.spectral.bins != g->spectral_bins) {
+			std::fprintf(stderr, head, g->compare_to.c_str());
+			std::fprintf(stderr, "the bin count differs: it holds %u wavelength bins, `--spectral-bins=%zu` is in force!\n", ck.spectral.bins, g->spectral_bins);
+			throw -2;
+		}
+		if (ck.info.seed == o->seed) std::fprintf(stderr, "Warning: `--compare-to`: same seed: the samples are not independent; z is not calibrated\n");
+		g->compare_other = std::make_shared<ssx::Checkpoint>(std::move(ck));
 	}
 	const bool spectral_stop = g->spectral_noise_target >= 0.0;
 	if (a.take("--spectral-noise-coverage", "", &v)) {
@@ -461,6 +514,16 @@ int main(int argc, char* argv[]) {
 			                                                   prog.develop_filter.empty() ? nullptr : &filter, gain.empty() ? nullptr : gain.data(), nullptr, B, d.lambda_min, d.lambda_step);
 			develop_weights.assign(w.begin(), w.end()); // (rounded to binary32 here, once)
 		}
+		if (prog.compare_other) { // the last refusal of --compare-to needs the scene: still before anything renders
+			const ssx_scene_desc& d = renderer.scene->desc();
+			const float bin_width = d.lambda_step / static_cast<float>(prog.spectral_bins / 4);
+			const ssx_spectral_info_t& other = prog.compare_other->spectral;
+			if (std::memcmp(&other.lambda_min, &d.lambda_min, sizeof(float)) != 0 || std::memcmp(&other.bin_width, &bin_width, sizeof(float)) != 0) {
+				std::fprintf(stderr, "`--compare-to` cannot compare with \"%s\": lambda_min or bin_width differs: its bins start at %.9g nm and are %.9g nm wide, this render's start at %.9g nm and are %.9g nm wide!\n",
+				             prog.compare_to.c_str(), static_cast<double>(other.lambda_min), static_cast<double>(other.bin_width), static_cast<double>(d.lambda_min), static_cast<double>(bin_width));
+				return -1;
+			}
+		}
 		bool stop_sent = false;
 		const bool needs_moments = prog.moments() || spectral_stop;
 		if (!prog.resume.empty()) {
@@ -521,6 +584,19 @@ int main(int argc, char* argv[]) {
 		else if (!prog.spectral_output.empty()) renderer.save_spectral_image(prog.spectral_output);
 		if (!prog.variance_output.empty()) renderer.save_spectral_variance(prog.variance_output);
 		if (!prog.probe_output.empty()) renderer.save_probe_csv(prog.probe_output, renderer.probe(renderer.labels_from_rects(prog.probes), prog.probes.size()));
+		if (prog.compare_other) {
+			const size_t regions = prog.probes.empty() ? 1 : prog.probes.size();
+			const std::vector<uint8_t> labels = prog.probes.empty() ? std::vector<uint8_t>(options.res[0] * options.res[1], 0u) : renderer.labels_from_rects(prog.probes);
+			const ssx::Renderer::Compare c = renderer.compare_spectral(*prog.compare_other, labels, regions, prog.compare_threshold * prog.compare_threshold, !prog.compare_map_output.empty());
+			if (!prog.compare_output.empty()) renderer.save_compare_csv(prog.compare_output, c);
+			if (!prog.compare_map_output.empty()) renderer.save_compare_map(prog.compare_map_output, c);
+			for (size_t r = 0; r < regions; ++r) { // one line per region, the bins added up: the CSV has the figures
+				uint64_t cc = 0, ex = 0;
+				for (size_t b = 0; b < c.bins; ++b) { cc += c.CC[r * c.bins + b]; ex += c.EX[r * c.bins + b]; }
+				std::fprintf(stderr, "Compared with \"%s\", region %zu: %llu comparable cells, %llu beyond z = %.6g.\n", prog.compare_to.c_str(), r, static_cast<unsigned long long>(cc),
+				             static_cast<unsigned long long>(ex), prog.compare_threshold);
+			}
+		}
 		if (!prog.develop_output.empty()) { // X, Y, Z from the bins, the alpha of the render's image, then the store of --output
 			const std::vector<float> xyz = renderer.develop(develop_weights.data(), 3, prog.spectral_denoise ? &prog.denoise_params : nullptr, prog.demodulate ? &prog.demod_params : nullptr);
 			const size_t pixels = options.res[0] * options.res[1];

@@ -32,7 +32,7 @@ void Framebuffer::save(const std::string& path) const { save_image(path, pixels_
 	X(create) X(destroy) X(upload_scene) X(render_start) X(render_stop) X(is_rendering) X(progress) X(render_wait) X(last_error) \
 	X(device_framebuffer) X(device_index) X(read_framebuffer) X(accumulate_peer) X(done_spp) X(done_tiles) X(reduce_rccl) \
 	X(render_continue) X(sums_export) X(sums_import) X(set_noise_estimate) X(noise_info) \
-	X(set_spectral_bins) X(spectral_read) X(spectral_import) X(set_spectral_moments) X(spectral_variance) X(spectral_moments_import) X(spectral_probe) X(probe_arrays) X(spectral_noise) X(spectral_noise_reduce) \
+	X(set_spectral_bins) X(spectral_read) X(spectral_import) X(set_spectral_moments) X(spectral_variance) X(spectral_moments_import) X(spectral_probe) X(probe_arrays) X(spectral_noise) X(spectral_noise_reduce) X(spectral_compare) X(spectral_compare_arrays) \
 	X(guides) X(denoise_images) X(denoise) X(denoise_channels) X(denoise_spectral) \
 	X(develop_images) X(spectral_develop) X(albedo_bins) X(denoise_spectral_demod) X(spectral_develop_demod)
 
@@ -528,6 +528,58 @@ Renderer::UntilSpectral Renderer::render_until_spectral(double target, size_t st
 	}
 	r.spp = done_spp();
 	return r;
+}
+
+Renderer::Compare Renderer::compare_spectral(const Checkpoint& other, const std::vector<uint8_t>& labels, size_t regions, double t2, bool maps) {
+	wait_workers_();
+	if (!spectral_bins_) throw HostError{ SSX_ERR_STATE, "compare_spectral: spectral output is off (set_spectral_bins)" };
+	const size_t W = options.res[0], H = options.res[1], pixels = W * H, B = spectral_bins_;
+	if (labels.size() != pixels) throw HostError{ SSX_ERR_ARG, "compare_spectral: labels is not [height][width]" };
+	if (regions < 1 || regions > 32) throw HostError{ SSX_ERR_ARG, "compare_spectral: need 1..32 regions" };
+	if (!other.spectral.bins || other.moments.empty()) throw HostError{ SSX_ERR_ARG, "compare_spectral: the other render carries no wavelength bins with their second moments" };
+	if (other.spectral.width != W || other.spectral.height != H || other.spectral.bins != B) // (so that the arrays are as large as the library will read them)
+		throw HostError{ SSX_ERR_ARG, "compare_spectral: the other render's size or bin count differs from this render's" };
+	Compare r;
+	r.regions = regions; r.bins = B;
+	r.DD.resize(regions * B); r.VV.resize(regions * B); r.X2.resize(regions * B); r.CC.resize(regions * B); r.NC.resize(regions * B); r.EX.resize(regions * B);
+	if (maps) { r.diff.resize(pixels * B); r.var.resize(pixels * B); }
+	float* const diff = maps ? r.diff.data() : nullptr, * const var = maps ? r.var.data() : nullptr;
+	ssx_ctx* root = ctxs_[0];
+	const uint32_t r32 = static_cast<uint32_t>(regions);
+	ssx_spectral_info_t info{};
+	if (ctxs_.size() == 1) {
+		check_(api_->spectral_variance(root, &info, nullptr, nullptr), "ssx_spectral_variance", root);
+		check_(api_->spectral_compare(root, &other.spectral, other.spectral_sums.data(), other.moments.data(), other.spectral_counts.data(), labels.data(), r32, t2,
+		                              r.DD.data(), r.VV.data(), r.X2.data(), r.CC.data(), r.NC.data(), r.EX.data(), diff, var), "ssx_spectral_compare", root);
+	} else { // S, N (gather_bins_) and Q from the device that owns the pixel, bit for bit; then the pure comparison on device 0, as the probe does
+		level_devices(); // (a stopped render: one sample count behind every pixel)
+		std::vector<double> sums;
+		std::vector<uint32_t> counts;
+		info = gather_bins_(nullptr, &sums, &counts);
+		const std::vector<double> q = gather_moments_();
+		if (std::memcmp(&info.lambda_min, &other.spectral.lambda_min, sizeof(float)) != 0 || std::memcmp(&info.bin_width, &other.spectral.bin_width, sizeof(float)) != 0)
+			throw HostError{ SSX_ERR_ARG, "compare_spectral: lambda_min or bin_width of the other render differs from this render's" };
+		check_(api_->spectral_compare_arrays(root, w32_(), h32_(), static_cast<uint32_t>(B), sums.data(), q.data(), counts.data(), other.spectral_sums.data(), other.moments.data(),
+		                                     other.spectral_counts.data(), labels.data(), r32, t2, r.DD.data(), r.VV.data(), r.X2.data(), r.CC.data(), r.NC.data(), r.EX.data(), diff, var),
+		       "ssx_spectral_compare_arrays", root);
+	}
+	r.lambda_min = info.lambda_min; r.bin_width = info.bin_width;
+	const size_t n = regions * B;
+	r.mean_diff.resize(n); r.std_err.resize(n); r.z.resize(n); r.chi2.resize(n); r.exceed.resize(n); r.coverage.resize(n);
+	compare_derive(regions, B, r.DD.data(), r.VV.data(), r.X2.data(), r.CC.data(), r.NC.data(), r.EX.data(), r.mean_diff.data(), r.std_err.data(), r.z.data(), r.chi2.data(),
+	               r.exceed.data(), r.coverage.data());
+	return r;
+}
+
+void Renderer::save_compare_csv(const std::string& path, const Compare& c) const {
+	ssx::save_compare_csv(path, c.regions, c.bins, c.lambda_min, c.bin_width, c.DD.data(), c.VV.data(), c.X2.data(), c.CC.data(), c.NC.data(), c.EX.data());
+}
+
+void Renderer::save_compare_map(const std::string& path, const Compare& c) {
+	if (c.diff.empty()) throw HostError{ SSX_ERR_ARG, "save_compare_map: the comparison was made without its maps" };
+	std::vector<float> zmap(c.diff.size());
+	compare_zmap(zmap.size(), c.diff.data(), c.var.data(), zmap.data());
+	save_spectral_image(path, zmap);
 }
 
 Renderer::Guides Renderer::guides() {

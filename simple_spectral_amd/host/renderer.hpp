@@ -19,6 +19,8 @@ struct ssx_ctx;
 
 namespace ssx {
 
+struct Checkpoint; // host/checkpoint.hpp
+
 class Framebuffer { // sRGB + linear alpha, float, rows bottom to top (src/framebuffer.hpp:26-34)
 public:
 	explicit Framebuffer(const size_t res[2]); // 8x8 checkerboard 0.7/0.3, alpha 1 (src/framebuffer.cpp:15-32)
@@ -154,6 +156,21 @@ public:
 	struct UntilSpectral { size_t spp = 0; double noise = 0.0, coverage = 0.0; };
 	UntilSpectral render_until_spectral(double target, size_t step, size_t max_spp, const std::vector<uint8_t>& mask = {}, double min_coverage = 0.99, const std::function<bool()>& tick = {},
 	                                    bool resume = false);
+
+	// Comparing this render with another, bin by bin (include/ssx.h "Comparing two spectral renders"): A is what the devices hold, B the bins, counts and second
+	// moments of `other` (checkpoint_load of a file written with the moments on: "SSXCKPT3"); labels and regions as probe() takes them; t2 the squared z
+	// threshold.  DD, VV, X2, CC, NC, EX [regions][bins] as the header defines them, reduced on the device in a fixed order, and the figures derived from them
+	// (image_io.hpp compare_derive); with `maps` also diff and var [height][width][bins].  One device: ssx_spectral_compare.  Several: level_devices(), S, Q and N
+	// merged by ownership, then ssx_spectral_compare_arrays on device 0 -- the same bits.  After render_wait() of a render that started with the moments on.  The
+	// two renders must have independent samples (different seeds) for z to mean anything.
+	struct Compare {
+		size_t regions = 0, bins = 0; float lambda_min = 0.0f, bin_width = 0.0f;
+		std::vector<double> DD, VV, X2, mean_diff, std_err, z, chi2, exceed, coverage; std::vector<uint64_t> CC, NC, EX;
+		std::vector<float> diff, var;
+	};
+	Compare compare_spectral(const Checkpoint& other, const std::vector<uint8_t>& labels, size_t regions, double t2, bool maps = false);
+	void save_compare_csv(const std::string& path, const Compare& c) const; // image_io.hpp save_compare_csv
+	void save_compare_map(const std::string& path, const Compare& c);       // zmap = diff / sqrt(var) (image_io.hpp compare_zmap) as a .npy file in spectral_image's layout
 
 
 	// Denoising (include/ssx.h: first-hit guide buffers and the variance-guided a-trous filter).

@@ -243,6 +243,59 @@ def save_spectral_noise_csv(path, lambda_min, bin_width, EV, EM, PP, PU):
         raise SsxError(rc, host.ssh_last_error().decode())
 
 
+def _compare_sums(DD, VV, X2, CC, NC, EX, what):
+    DD, VV, X2 = (np.ascontiguousarray(a, dtype=np.float64) for a in (DD, VV, X2))
+    CC, NC, EX = (np.ascontiguousarray(a, dtype=np.uint64) for a in (CC, NC, EX))
+    if DD.ndim != 2 or not (DD.shape == VV.shape == X2.shape == CC.shape == NC.shape == EX.shape):
+        raise ValueError("%s: DD, VV, X2, CC, NC, EX must all have shape [R, B]" % what)
+    return DD, VV, X2, CC, NC, EX
+
+
+COMPARE_FIGURES = ("mean_diff", "stderr", "z", "chi2", "exceed", "coverage")
+
+
+def compare_derive(DD, VV, X2, CC, NC, EX):
+    """ssh_compare_derive: a dict of float64 [R, B] arrays from the comparison's six sums (include/ssx.h "Comparing two spectral renders") -- mean_diff = DD / CC,
+    stderr = sqrt(VV) / CC, z = DD / sqrt(VV), chi2 = X2 / CC, exceed = EX / CC, coverage = CC / (CC + NC); each NaN where its denominator is 0."""
+    sums = _compare_sums(DD, VV, X2, CC, NC, EX, "compare_derive")
+    out = [np.zeros_like(sums[0]) for _ in COMPARE_FIGURES]
+    host = _capi.host_lib()
+    rc = host.ssh_compare_derive(sums[0].shape[0], sums[0].shape[1], *[a.ctypes.data for a in sums], *[a.ctypes.data for a in out])
+    if rc != 0:
+        raise SsxError(rc, host.ssh_last_error().decode())
+    return dict(zip(COMPARE_FIGURES, out))
+
+
+def compare_zmap(diff, var):
+    """The comparison's signed per-pixel map, float32: diff / sqrt(var), 0 where var is +inf (a cell that is not comparable)."""
+    diff, var = np.asarray(diff, dtype=np.float32), np.asarray(var, dtype=np.float32)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(np.isposinf(var), np.float32(0.0), diff / np.sqrt(var)).astype(np.float32)
+
+
+def save_compare_csv(path, lambda_min, bin_width, DD, VV, X2, CC, NC, EX):
+    """ssh_compare_save_csv (libssx_host.so), the writer the CLI's --compare-output uses: the line
+    "region,bin,wavelength,mean_diff,stderr,z,chi2,exceed,comparable,not_comparable", then one line per region and bin."""
+    sums = _compare_sums(DD, VV, X2, CC, NC, EX, "save_compare_csv")
+    host = _capi.host_lib()
+    rc = host.ssh_compare_save_csv(os.fsencode(path), sums[0].shape[0], sums[0].shape[1], C.c_float(lambda_min), C.c_float(bin_width), *[a.ctypes.data for a in sums])
+    if rc != 0:
+        raise SsxError(rc, host.ssh_last_error().decode())
+
+
+def compare_other(other):
+    """What a comparison takes of another render: `other` is what load_checkpoint_file_moments returns (nine values), or (SsxSpectralInfo, S, N, Q) -> (SsxSpectralInfo,
+    S float64 [H, W, B], Q float64 [H, W, B], N uint32 [H, W, B / 4]).  ValueError when it carries no bins or no second moments."""
+    info, S, N, Q = other[5:9] if len(other) == 9 else other
+    if not info.bins or S is None or N is None or Q is None:
+        raise ValueError("compare: the other render carries no wavelength bins with their second moments (a checkpoint written with the moments on has them)")
+    S, Q, N = np.ascontiguousarray(S, dtype=np.float64), np.ascontiguousarray(Q, dtype=np.float64), np.ascontiguousarray(N, dtype=np.uint32)
+    shape = (info.height, info.width, info.bins)
+    if S.shape != shape or Q.shape != shape or N.shape != shape[:2] + (info.bins // 4,):
+        raise ValueError("compare: the other render's S and Q must have shape [H, W, B] = %r of its info, N [H, W, B / 4]" % (shape,))
+    return info, S, Q, N
+
+
 def save_npy(path, array):
     """ssh_save_npy_f32 (libssx_host.so): `array` as a float32 .npy file, the writer the CLI's --spectral-output uses."""
     a = np.ascontiguousarray(array, dtype=np.float32)
@@ -730,6 +783,53 @@ class Renderer:
         self._check(self._lib.ssx_probe_arrays(self._ctx, W, H, B, sums.ctypes.data, q.ctypes.data, counts.ctypes.data, labels.ctypes.data, R,
                                                SS.ctypes.data, NN.ctypes.data, VV.ctypes.data, UU.ctypes.data))
         return SS, NN, VV, UU
+
+    # ---- comparing two spectral renders (include/ssx.h "Comparing two spectral renders") ----
+
+    @staticmethod
+    def _compare_outputs(R, shape, maps):
+        sums = [np.zeros((R, shape[2]), dtype=np.float64) for _ in range(3)] + [np.zeros((R, shape[2]), dtype=np.uint64) for _ in range(3)]
+        diff, var = (np.zeros(shape, dtype=np.float32), np.zeros(shape, dtype=np.float32)) if maps else (None, None)
+        return sums, diff, var
+
+    def compare_spectral_raw(self, other, labels, regions=None, threshold=3.0, maps=True):
+        """ssx_spectral_compare: this context's render (A) against another (B) -> ((DD float64, VV float64, X2 float64, CC uint64, NC uint64, EX uint64), each [R, B],
+        diff float32 [H, W, B], var float32 [H, W, B]); the maps are None with maps=False.  other: what load_checkpoint_file_moments returns, or (SsxSpectralInfo, S,
+        N, Q); labels as probe_raw takes them; threshold: the z beyond which a comparable cell counts into EX (the library takes its square)."""
+        info, S, Q, N = compare_other(other)
+        W, H = self.options.res
+        labels, R = self._probe_labels(labels, (H, W))
+        R = R if regions is None else int(regions)
+        B = getattr(self, "_spectral_bins", 0) or 4
+        sums, diff, var = self._compare_outputs(R, (H, W, B), maps)
+        self._check(self._lib.ssx_spectral_compare(self._ctx, C.byref(info), S.ctypes.data, Q.ctypes.data, N.ctypes.data, labels.ctypes.data, R, float(threshold) * float(threshold),
+                                                   *[a.ctypes.data for a in sums], None if diff is None else diff.ctypes.data, None if var is None else var.ctypes.data))
+        return tuple(sums), diff, var
+
+    def compare_spectral(self, other, labels, regions=None, threshold=3.0):
+        """The comparison's derived figures -> a dict of float64 [R, B] arrays mean_diff, stderr, z, chi2, exceed, coverage (compare_derive), with "comparable" and
+        "not_comparable" (uint64 [R, B]) and "zmap" (float32 [H, W, B]: diff / sqrt(var), 0 where a cell is not comparable).  The two renders must have independent
+        samples (different seeds); with few samples per sub-bin chi2 is to be held against nu / (nu - 2), not 1."""
+        sums, diff, var = self.compare_spectral_raw(other, labels, regions, threshold)
+        out = compare_derive(*sums)
+        out.update(comparable=sums[3], not_comparable=sums[4], zmap=compare_zmap(diff, var))
+        return out
+
+    def compare_arrays(self, SA, QA, NA, SB, QB, NB, labels, regions=None, threshold=3.0, maps=True, t2=None):
+        """ssx_spectral_compare_arrays: compare_spectral_raw as a pure function of two row-major array sets -- S and Q float64 [H, W, B], N uint32 [H, W, B / 4] each
+        (e.g. two checkpoints', or several contexts' exports merged by ownership).  t2, when given, is passed as it is instead of threshold squared."""
+        SA, QA, SB, QB = (np.ascontiguousarray(a, dtype=np.float64) for a in (SA, QA, SB, QB))
+        NA, NB = np.ascontiguousarray(NA, dtype=np.uint32), np.ascontiguousarray(NB, dtype=np.uint32)
+        if SA.ndim != 3 or SA.shape[2] % 4 or not (QA.shape == SB.shape == QB.shape == SA.shape) or not (NA.shape == NB.shape == SA.shape[:2] + (SA.shape[2] // 4,)):
+            raise ValueError("compare_arrays: S and Q of both sets must have shape [H, W, B], N [H, W, B / 4]")
+        H, W, B = SA.shape
+        labels, R = self._probe_labels(labels, (H, W))
+        R = R if regions is None else int(regions)
+        sums, diff, var = self._compare_outputs(R, (H, W, B), maps)
+        self._check(self._lib.ssx_spectral_compare_arrays(self._ctx, W, H, B, SA.ctypes.data, QA.ctypes.data, NA.ctypes.data, SB.ctypes.data, QB.ctypes.data, NB.ctypes.data,
+                                                          labels.ctypes.data, R, float(threshold) * float(threshold) if t2 is None else float(t2),
+                                                          *[a.ctypes.data for a in sums], None if diff is None else diff.ctypes.data, None if var is None else var.ctypes.data))
+        return tuple(sums), diff, var
 
     # ---- the spectral noise figure and the render loop that stops on it (include/ssx.h "Spectral noise figure") ----
 
