@@ -62,20 +62,33 @@ extern "C" __global__ void __launch_bounds__(256) ssx_spectral_export_kernel(con
 	}
 }
 
+// Rows into LDS, the first half of both import kernels (this one and ssx_spectral_moments_import_kernel): the tile at (i0, j0) of a row-major whole-image
+// binary64 array src [height][width][B] -> lds [64 pixels][B + 1], by the 256 lanes of a workgroup (the caller's barrier follows).
+//   in:   the 8 pixel rows of a tile are 8 runs of cols * B consecutive doubles in the source (cols = 8, fewer in the image's last tile column; 4 KB at B = 64).
+//         Consecutive lanes read consecutive 16-byte pairs of a run -- B is a multiple of 4, so every run starts 32-byte aligned in an array that is.  Rows and
+//         columns outside a ragged image are never read.
+//   LDS:  the stride B + 1 is an ODD number of elements: on the way out lane = pixel reads element b of its row, i.e. 8-byte address (B + 1) * pixel + b.  A
+//         ds_read_b64 is served in two groups of 32 lanes over 64 four-byte banks, bank = (address / 4) mod 64, so the 32 lanes of a group need 32 distinct even
+//         bank pairs: 2 * (B + 1) * pixel mod 64 distinct for 32 consecutive pixels, which holds exactly when the stride is odd (one element of padding: the
+//         access width); the unpadded stride B -- 4, ..., 64 doubles -- would put 2, ..., 32 lanes on one bank pair.  The price is on the way in: with an odd
+//         stride a pixel's row starts 8-byte aligned only, so a pair is stored as two 8-byte writes (16 lanes a group, 32 banks, lanes l and l + 8 on the same
+//         ones: 2-way), which the write's own register transfer mostly covers.  33 KB at B = 64.
+__device__ __forceinline__ void tile_rows_to_lds(const double* src, double* lds, uint32_t width, uint32_t i0, uint32_t j0, uint32_t cols, uint32_t rows, uint32_t B) {
+	const uint32_t pairs = cols * (B / 2u);                                                        // 16-byte pairs of one run
+	for (uint32_t e = threadIdx.x; e < rows * pairs; e += 256u) {
+		const uint32_t r = e / pairs, v = e - r * pairs, c = (2u * v) / B, b = 2u * v - c * B;       // (B is even: a pair never straddles two pixels)
+		const double2 d = reinterpret_cast<const double2*>(src + ((size_t)(j0 + r) * width + i0) * B)[v];
+		double* const o = lds + (r * 8u + c) * (B + 1u) + b;
+		o[0] = d.x; o[1] = d.y;
+	}
+}
+
 // The inverse of the export for the tiles this context owns: row-major whole-image sums [height][width][B] and counts [height][width][M] (row 0 = bottom; whoever
 // exported them may have owned other tiles) -> S[tile slot][bin][pixel of the tile], N[tile slot][m][pixel of the tile].  A transposition through LDS, one
 // 256-lane workgroup per owned tile slot (slot -> tile by tile_of_slot), no atomics: a workgroup writes its own slot only.
-//   in:   the 8 pixel rows of a tile are 8 runs of cols * B consecutive doubles in the source (cols = 8, fewer in the image's last tile column; 4 KB at B = 64).
-//         Consecutive lanes read consecutive 16-byte pairs of a run -- B is a multiple of 4, so every run starts 32-byte aligned in an array that is -- and the
-//         counts' runs of cols * M words word by word (M may be odd: such a run has no alignment to speak of).  Rows and columns outside a ragged image are
-//         never read.
-//   LDS:  [64 pixels][B + 1] doubles, then [64 pixels][M | 1] words.  The strides are ODD numbers of elements: on the way out lane = pixel reads element b of
-//         its row, i.e. 8-byte address (B + 1) * pixel + b.  A ds_read_b64 is served in two groups of 32 lanes over 64 four-byte banks, bank = (address / 4) mod
-//         64, so the 32 lanes of a group need 32 distinct even bank pairs: 2 * (B + 1) * pixel mod 64 distinct for 32 consecutive pixels, which holds exactly
-//         when the stride is odd (one element of padding: the access width); the unpadded stride B -- 4, ..., 64 doubles -- would put 2, ..., 32 lanes on one
-//         bank pair.  The counts' ds_read_b32 has 32 banks for 32 lanes: an odd word stride again, M + 1 for an even M, M itself for an odd one.  The price is on
-//         the way in: with an odd stride a pixel's row starts 8-byte aligned only, so a pair is stored as two 8-byte writes (16 lanes a group, 32 banks, lanes l
-//         and l + 8 on the same ones: 2-way), which the write's own register transfer mostly covers.  33 KB + 4 KB at B = 64.
+//   in:   the sums by tile_rows_to_lds; the counts' runs of cols * M words word by word (M may be odd: such a run has no alignment to speak of).
+//   LDS:  [64 pixels][B + 1] doubles, then [64 pixels][M | 1] words.  The counts' ds_read_b32 has 32 banks for 32 lanes: an odd word stride again, M + 1 for an
+//         even M, M itself for an odd one.  33 KB + 4 KB at B = 64.
 //   out:  wave w stores bins w, w + 4, ...: per bin the 64 lanes' doubles are 512 consecutive bytes, per m 256.  Lanes of pixels outside the image store +0 / 0,
 //         what the memset of a fresh render leaves there.
 // The check: every sample is counted exactly once, misses included (ssx_spectral_bin_kernel), so for an in-image pixel the sum of its M counts is done_spp --
@@ -89,13 +102,7 @@ extern "C" __global__ void __launch_bounds__(256) ssx_spectral_import_kernel(con
 	const uint32_t i0 = tx * 8u, j0 = ty * 8u, cols = min(8u, g.width - i0), rows = min(8u, g.height - j0);
 	double* const ls = spectral_lds;                                                               // [pixel * s_stride + b]
 	uint32_t* const ln = reinterpret_cast<uint32_t*>(spectral_lds + 64u * s_stride);               // [pixel * n_stride + m]
-	const uint32_t pairs = cols * (B / 2u);                                                        // 16-byte pairs of one run
-	for (uint32_t e = tid; e < rows * pairs; e += 256u) {
-		const uint32_t r = e / pairs, v = e - r * pairs, c = (2u * v) / B, b = 2u * v - c * B;       // (B is even: a pair never straddles two pixels)
-		const double2 d = reinterpret_cast<const double2*>(sums + ((size_t)(j0 + r) * g.width + i0) * B)[v];
-		double* const o = ls + (r * 8u + c) * s_stride + b;
-		o[0] = d.x; o[1] = d.y;
-	}
+	tile_rows_to_lds(sums, ls, g.width, i0, j0, cols, rows, B);
 	const uint32_t words = cols * M;
 	for (uint32_t e = tid; e < rows * words; e += 256u) {
 		const uint32_t r = e / words, v = e - r * words, c = v / M, m = v - c * M;
@@ -112,6 +119,29 @@ extern "C" __global__ void __launch_bounds__(256) ssx_spectral_import_kernel(con
 		uint32_t n = 0u;
 		for (uint32_t m = 0; m < M; ++m) n += ln[px * n_stride + m];
 		if (n != done_spp) *bad = 1u;
+	}
+}
+
+// The ordered reduce behind the probes and the comparison: part [rows][R][K][B] -> out [K][R][B], one lane per (quantity, r, b) adds the rows' partials in
+// ascending row order, from +0.0 / 0; bit q of integer_mask says that quantity q is uint64, not binary64.  The additions stay in order; the loads do not depend
+// on them, so the loop is unrolled to keep 16 of them in flight.  (ssx_spectral_noise_reduce_kernel stays its own: its partials are four arrays of two widths
+// in a [tiles][B] layout that the ABI hands out; a width parameter and an indirection would cost more than its 15 lines.)
+extern "C" __global__ void __launch_bounds__(256) ssx_ordered_reduce_kernel(const uint64_t* part, uint64_t* out, uint32_t rows, uint32_t R, uint32_t B, uint32_t K, uint32_t integer_mask) {
+	const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+	if (e >= K * R * B) return;
+	const uint32_t quantity = e / (R * B), rb = e - quantity * (R * B), r = rb / B, b = rb - r * B;
+	const uint64_t* const src = part + ((size_t)r * K + quantity) * B + b;
+	const size_t stride = (size_t)R * K * B;
+	if ((integer_mask >> quantity) & 1u) {
+		uint64_t total = 0ull;
+#pragma unroll 16
+		for (uint32_t j = 0; j < rows; ++j) total += src[j * stride];
+		out[e] = total;
+	} else {
+		double total = 0.0;
+#pragma unroll 16
+		for (uint32_t j = 0; j < rows; ++j) total += reinterpret_cast<const double*>(src)[j * stride];
+		reinterpret_cast<double*>(out)[e] = total;
 	}
 }
 
@@ -162,13 +192,79 @@ int spectral_batch(ssx_ctx* ctx, const ssx_render_params* p, const LaunchPlan& p
 
 void spectral_drop(ssx_ctx* ctx) { ctx->d_spectral_sums.release(); ctx->d_spectral_counts.release(); }
 
+// ---- what the four spectral fragments share on the host ----
+
+bool valid_bins(uint32_t bins) { return bins >= 4u && bins <= 64u && !(bins & 3u); } // a multiple of 4 up to 64
+
+// One DeviceBuffer carved into typed arrays, each aligned for its type whatever the order: `layout` runs once to size the reservation and once to hand out pointers.
+struct Carver {
+	uint8_t* base; size_t at;
+	template <class T> T* take(size_t count) {
+		at = (at + alignof(T) - 1u) / alignof(T) * alignof(T);
+		T* const p = base ? reinterpret_cast<T*>(base + at) : nullptr;
+		at += count * sizeof(T);
+		return p;
+	}
+};
+template <class Layout> int carve(ssx_ctx* ctx, DeviceBuffer& buf, Layout layout) {
+	Carver c{nullptr, 0};
+	layout(c);
+	SSX_HIP(ctx, buf.reserve(c.at));
+	c = Carver{buf.as<uint8_t>(), 0};
+	layout(c);
+	return SSX_OK;
+}
+
+// planes of n eight-byte words, one behind the other on the device, back to their host pointers
+int copy_planes(ssx_ctx* ctx, const uint64_t* d_out, size_t n, std::initializer_list<void*> outs) {
+	for (void* const o : outs) { SSX_HIP(ctx, hipMemcpy(o, d_out, n * 8u, hipMemcpyDeviceToHost)); d_out += n; }
+	return SSX_OK;
+}
+
+// What every spectral read-out asks first: bins on, (moments on,) no render, valid bins (and valid moments); then the device is the context's.
+int spectral_ready(ssx_ctx* ctx, const char* what, bool moments) {
+	if (!ctx->spectral_bins) return fail(ctx, SSX_ERR_STATE, fmt("%s: spectral output is off (ssx_set_spectral_bins)", what));
+	if (moments && !ctx->spectral_moments) return fail(ctx, SSX_ERR_STATE, fmt("%s: spectral moments are off (ssx_set_spectral_moments)", what));
+	if (ctx->rendering.load()) return fail(ctx, SSX_ERR_STATE, "render in progress");
+	if (!ctx->sums.continuable || !ctx->sums.spectral_valid)
+		return fail(ctx, SSX_ERR_STATE, fmt("%s: the context holds no spectral bins: ", what) + (ctx->sums.continuable ? ctx->spectral_note : std::string("no render has accumulated any (ssx_render_start first)")));
+	if (moments && !ctx->sums.moments_valid) return fail(ctx, SSX_ERR_STATE, fmt("%s: the context holds no spectral moments: ", what) + ctx->moments_note);
+	SSX_HIP(ctx, hipSetDevice(ctx->device));
+	return wait_device_pending(ctx);
+}
+
+void spectral_info_of(const ssx_ctx* ctx, ssx_spectral_info_t* info) {
+	const ssx_render_params& p = ctx->cur;
+	memset(info, 0, sizeof *info);
+	info->struct_size = sizeof *info;
+	info->width = p.width; info->height = p.height; info->bins = ctx->spectral_bins; info->done_spp = ctx->done_spp.load();
+	info->lambda_min = ctx->lambda_min; info->bin_width = ctx->lambda_step / (float)(ctx->spectral_bins / 4u);
+}
+
+// Whether `info` (`whose`: "these bins", "the other render") belongs to what the context holds: the refusal's text, or nothing.  done_against names what done_spp
+// is held against; NULL: it is not.  The floats are compared as bits.
+std::string spectral_info_mismatch(const ssx_ctx* ctx, const char* what, const char* whose, const char* done_against, const ssx_spectral_info_t* info) {
+	ssx_spectral_info_t own;
+	spectral_info_of(ctx, &own);
+	if (info->struct_size != sizeof *info) return fmt("%s: ssx_spectral_info_t.struct_size mismatch", what);
+	if (info->width != own.width || info->height != own.height)
+		return fmt("%s: size differs (%s: %u x %u, this render: %u x %u)", what, whose, info->width, info->height, own.width, own.height);
+	if (info->bins != own.bins) return fmt("%s: bins differs (%s: %u, this context: %u)", what, whose, info->bins, own.bins);
+	if (done_against && info->done_spp != own.done_spp) return fmt("%s: done_spp differs (%s: %u, %s: %u)", what, whose, info->done_spp, done_against, own.done_spp);
+	if (memcmp(&info->lambda_min, &own.lambda_min, sizeof(float)) != 0)
+		return fmt("%s: lambda_min differs (%s: %.9g, the uploaded scene: %.9g)", what, whose, (double)info->lambda_min, (double)own.lambda_min);
+	if (memcmp(&info->bin_width, &own.bin_width, sizeof(float)) != 0)
+		return fmt("%s: bin_width differs (%s: %.9g, the uploaded scene: %.9g)", what, whose, (double)info->bin_width, (double)own.bin_width);
+	return std::string();
+}
+
 } // namespace
 
 extern "C" {
 
 int ssx_set_spectral_bins(ssx_ctx* ctx, uint32_t bins) {
 	if (!ctx) return SSX_ERR_ARG;
-	if (bins > 64u || (bins & 3u)) return fail(ctx, SSX_ERR_ARG, fmt("ssx_set_spectral_bins: %u bins: need 0 (off) or a multiple of 4 up to 64", bins));
+	if (bins && !valid_bins(bins)) return fail(ctx, SSX_ERR_ARG, fmt("ssx_set_spectral_bins: %u bins: need 0 (off) or a multiple of 4 up to 64", bins));
 	if (ctx->rendering.load()) return fail(ctx, SSX_ERR_STATE, "render in progress");
 	if (bins == ctx->spectral_bins) return SSX_OK;
 	SSX_HIP(ctx, hipSetDevice(ctx->device));
@@ -182,70 +278,51 @@ int ssx_set_spectral_bins(ssx_ctx* ctx, uint32_t bins) {
 
 int ssx_spectral_read(ssx_ctx* ctx, ssx_spectral_info_t* info, float* mean, double* sums, uint32_t* counts) {
 	if (!ctx || !info) return SSX_ERR_ARG;
-	if (!ctx->spectral_bins) return fail(ctx, SSX_ERR_STATE, "ssx_spectral_read: spectral output is off (ssx_set_spectral_bins)");
-	if (ctx->rendering.load()) return fail(ctx, SSX_ERR_STATE, "render in progress");
-	if (!ctx->sums.continuable || !ctx->sums.spectral_valid)
-		return fail(ctx, SSX_ERR_STATE, "ssx_spectral_read: the context holds no spectral bins: " + (ctx->sums.continuable ? ctx->spectral_note : std::string("no render has accumulated any (ssx_render_start first)")));
-	SSX_HIP(ctx, hipSetDevice(ctx->device));
-	if (const int rc = wait_device_pending(ctx)) return rc;
+	if (const int rc = spectral_ready(ctx, "ssx_spectral_read", false)) return rc;
+	spectral_info_of(ctx, info);
+	if (!mean && !sums && !counts) return SSX_OK;
 	const ssx_render_params& p = ctx->cur;
 	const uint32_t B = ctx->spectral_bins, M = B / 4u;
-	memset(info, 0, sizeof *info);
-	info->struct_size = sizeof *info;
-	info->width = p.width; info->height = p.height; info->bins = B; info->done_spp = ctx->done_spp.load();
-	info->lambda_min = ctx->lambda_min; info->bin_width = ctx->lambda_step / (float)M;
-	if (!mean && !sums && !counts) return SSX_OK;
-	const size_t pixels = (size_t)p.width * p.height, b_sums = pixels * B * sizeof(double), b_mean = pixels * B * sizeof(float), b_counts = pixels * M * sizeof(uint32_t);
-	DeviceBuffer& stage = ctx->d_stage;
-	SSX_HIP(ctx, stage.reserve(b_sums + b_mean + b_counts));
-	double* const d_sums = stage.as<double>();
-	float* const d_mean = reinterpret_cast<float*>(stage.as<uint8_t>() + b_sums);
-	uint32_t* const d_counts = reinterpret_cast<uint32_t*>(stage.as<uint8_t>() + b_sums + b_mean);
+	const size_t pixels = (size_t)p.width * p.height;
+	double* d_sums; float* d_mean; uint32_t* d_counts;
+	if (const int rc = carve(ctx, ctx->d_stage, [&](Carver& c) { d_sums = c.take<double>(pixels * B); d_mean = c.take<float>(pixels * B); d_counts = c.take<uint32_t>(pixels * M); })) return rc;
 	hipLaunchKernelGGL(ssx_spectral_export_kernel, pixel_blocks(&p), dim3(256), 0, ctx->stream, ctx->d_spectral_sums.as<const double>(), ctx->d_spectral_counts.as<const uint32_t>(),
 	                   mean ? d_mean : nullptr, sums ? d_sums : nullptr, counts ? d_counts : nullptr, pixel_grid(&p), M);
 	SSX_HIP(ctx, hipGetLastError());
 	SSX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	if (sums) SSX_HIP(ctx, hipMemcpy(sums, d_sums, b_sums, hipMemcpyDeviceToHost));
-	if (mean) SSX_HIP(ctx, hipMemcpy(mean, d_mean, b_mean, hipMemcpyDeviceToHost));
-	if (counts) SSX_HIP(ctx, hipMemcpy(counts, d_counts, b_counts, hipMemcpyDeviceToHost));
+	if (sums) SSX_HIP(ctx, hipMemcpy(sums, d_sums, pixels * B * sizeof(double), hipMemcpyDeviceToHost));
+	if (mean) SSX_HIP(ctx, hipMemcpy(mean, d_mean, pixels * B * sizeof(float), hipMemcpyDeviceToHost));
+	if (counts) SSX_HIP(ctx, hipMemcpy(counts, d_counts, pixels * M * sizeof(uint32_t), hipMemcpyDeviceToHost));
 	return SSX_OK;
 }
 
 int ssx_spectral_import(ssx_ctx* ctx, const ssx_spectral_info_t* info, const double* sums, const uint32_t* counts) {
 	if (!ctx || !info || !sums || !counts) return SSX_ERR_ARG;
-	if (info->struct_size != sizeof *info) return fail(ctx, SSX_ERR_ARG, "ssx_spectral_import: ssx_spectral_info_t.struct_size mismatch");
+	const char* const what = "ssx_spectral_import";
+	if (info->struct_size != sizeof *info) return fail(ctx, SSX_ERR_ARG, fmt("%s: ssx_spectral_info_t.struct_size mismatch", what)); // (before the state is looked at)
 	if (!ctx->spectral_bins) return fail(ctx, SSX_ERR_STATE, "ssx_spectral_import: spectral output is off (ssx_set_spectral_bins)");
 	if (ctx->rendering.load()) return fail(ctx, SSX_ERR_STATE, "render in progress");
 	if (!ctx->sums.continuable || !ctx->sums.imported)
 		return fail(ctx, SSX_ERR_STATE, "ssx_spectral_import: the bins go on top of the pixel sums of an ssx_sums_import, directly: the context holds none, or has rendered since");
+	const std::string why = spectral_info_mismatch(ctx, what, "these bins", "the imported sums", info);
+	if (!why.empty()) return fail(ctx, SSX_ERR_ARG, why);
 	const ssx_render_params& p = ctx->cur;
 	const uint32_t B = ctx->spectral_bins, M = B / 4u, done = ctx->done_spp.load();
-	const float bin_width = ctx->lambda_step / (float)M; // (what ssx_spectral_read reports)
-	if (info->width != p.width || info->height != p.height)
-		return fail(ctx, SSX_ERR_ARG, fmt("ssx_spectral_import: size differs (these bins: %u x %u, this render: %u x %u)", info->width, info->height, p.width, p.height));
-	if (info->bins != B) return fail(ctx, SSX_ERR_ARG, fmt("ssx_spectral_import: bins differs (these bins: %u, this context: %u)", info->bins, B));
-	if (info->done_spp != done) return fail(ctx, SSX_ERR_ARG, fmt("ssx_spectral_import: done_spp differs (these bins: %u, the imported sums: %u)", info->done_spp, done));
-	if (memcmp(&info->lambda_min, &ctx->lambda_min, sizeof(float)) != 0)
-		return fail(ctx, SSX_ERR_ARG, fmt("ssx_spectral_import: lambda_min differs (these bins: %.9g, the uploaded scene: %.9g)", (double)info->lambda_min, (double)ctx->lambda_min));
-	if (memcmp(&info->bin_width, &bin_width, sizeof(float)) != 0)
-		return fail(ctx, SSX_ERR_ARG, fmt("ssx_spectral_import: bin_width differs (these bins: %.9g, the uploaded scene: %.9g)", (double)info->bin_width, (double)bin_width));
 	if (const int rc = spectral_refuses(ctx, p, false)) return rc; // (what a continue with the bins would be refused for)
 	SSX_HIP(ctx, hipSetDevice(ctx->device));
 	if (const int rc = wait_device_pending(ctx)) return rc;
 	const uint32_t tiles = owned_tiles(p);
-	const size_t pixels = (size_t)p.width * p.height, b_sums = pixels * B * sizeof(double), b_counts = pixels * M * sizeof(uint32_t);
-	DeviceBuffer& stage = ctx->d_stage; // sums | counts | the flag of the check
-	SSX_HIP(ctx, stage.reserve(b_sums + b_counts + sizeof(uint32_t)));
-	double* const d_sums = stage.as<double>();
-	uint32_t* const d_counts = reinterpret_cast<uint32_t*>(stage.as<uint8_t>() + b_sums), * const d_bad = d_counts + pixels * M;
+	const size_t pixels = (size_t)p.width * p.height;
+	double* d_sums; uint32_t* d_counts; uint32_t* d_bad; // d_stage: the sums, the counts and the flag of the check
+	if (const int rc = carve(ctx, ctx->d_stage, [&](Carver& c) { d_sums = c.take<double>(pixels * B); d_counts = c.take<uint32_t>(pixels * M); d_bad = c.take<uint32_t>(1); })) return rc;
 	SSX_HIP(ctx, ctx->d_spectral_sums.reserve(spectral_sum_bytes(ctx, tiles)));
 	SSX_HIP(ctx, ctx->d_spectral_counts.reserve(spectral_count_bytes(ctx, tiles)));
 	// from here on the device state is being replaced: it is valid again only once the check has passed
 	ctx->sums.spectral_valid = ctx->sums.spectral_imported = false; ctx->spectral_note = "an ssx_spectral_import on top of ssx_sums_import was refused or failed";
 	uint32_t bad = 0;
 	if (tiles) {
-		SSX_HIP(ctx, hipMemcpyAsync(d_sums, sums, b_sums, hipMemcpyHostToDevice, ctx->stream));
-		SSX_HIP(ctx, hipMemcpyAsync(d_counts, counts, b_counts, hipMemcpyHostToDevice, ctx->stream));
+		SSX_HIP(ctx, hipMemcpyAsync(d_sums, sums, pixels * B * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+		SSX_HIP(ctx, hipMemcpyAsync(d_counts, counts, pixels * M * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
 		SSX_HIP(ctx, hipMemsetAsync(d_bad, 0, sizeof(uint32_t), ctx->stream));
 		const size_t lds = 64u * ((size_t)(B + 1u) * sizeof(double) + (size_t)(M | 1u) * sizeof(uint32_t)); // <= 37 KB at 64 bins
 		hipLaunchKernelGGL(ssx_spectral_import_kernel, dim3(tiles), dim3(256), lds, ctx->stream, d_sums, d_counts, ctx->d_spectral_sums.as<double>(),

@@ -68,8 +68,8 @@ __device__ __forceinline__ void compare_rows(const SsxCompareArgs& a) {
 			double d = 0.0, v = 0.0, z2 = 0.0;
 			float fd = 0.0f, fv = __uint_as_float(0x7F800000u);
 			if (comparable) {
-				const double eA = (moment_deviations(qA, sA, nA) / (double)(nA - 1u)) / (double)nA, muA = sA / (double)nA;
-				const double eB = (moment_deviations(qB, sB, nB) / (double)(nB - 1u)) / (double)nB, muB = sB / (double)nB;
+				double muA, muB;
+				const double eA = cell_variance(qA, sA, nA, &muA), eB = cell_variance(qB, sB, nB, &muB);
 				d = muA - muB;
 				v = eA + eB;
 				z2 = (v == 0.0 && d == 0.0) ? 0.0 : (d * d) / v;
@@ -110,46 +110,23 @@ __device__ __forceinline__ void compare_rows(const SsxCompareArgs& a) {
 extern "C" __global__ void __launch_bounds__(256) ssx_compare_rows_kernel(SsxCompareArgs a) { compare_rows<256u>(a); }         // R * B <= 256
 extern "C" __global__ void __launch_bounds__(256) ssx_compare_rows_wide_kernel(SsxCompareArgs a) { compare_rows<2048u>(a); }  // R * B <= 2048: any legal R and B
 
-// Stage 2: one lane per (quantity, r, b) adds the rows' partials in ascending j, from +0.0 / 0.  ssx_probe_reduce_kernel does not fit unchanged: its four
-// quantities and their alternating types are built into its indexing.  The additions stay in order; the loads do not depend on them, so the loop is unrolled to
-// keep 16 of them in flight.
-extern "C" __global__ void __launch_bounds__(256) ssx_compare_reduce_kernel(SsxCompareArgs a) {
-	const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x, B = a.B;
-	if (e >= 6u * a.R * B) return;
-	const uint32_t quantity = e / (a.R * B), rb = e - quantity * (a.R * B), r = rb / B, b = rb - r * B;
-	const uint64_t* const src = a.part + ((size_t)r * 6u + quantity) * B + b;
-	const size_t stride = (size_t)a.R * 6u * B;
-	if (quantity >= 3u) {
-		uint64_t total = 0ull;
-#pragma unroll 16
-		for (uint32_t j = 0; j < a.height; ++j) total += src[j * stride];
-		a.out[e] = total;
-	} else {
-		double total = 0.0;
-#pragma unroll 16
-		for (uint32_t j = 0; j < a.height; ++j) total += reinterpret_cast<const double*>(src)[j * stride];
-		reinterpret_cast<double*>(a.out)[e] = total;
-	}
-}
+// Stage 2 is ssx_ordered_reduce_kernel (ssx_spectral.hip) with 6 quantities, CC, NC and EX (3, 4 and 5) the integers.
 
 namespace {
 
-// d_probe (shared with the probes: both are temporaries of one call): SA | QA | SB | QB [pixels][B] binary64 | part [height][R][6][B] | out [6][R][B] | NA | NB
-// [pixels][M] | diff | var [pixels][B] binary32 | labels [pixels] -- eight-byte quantities first
+// d_probe (shared with the probes: both are temporaries of one call): S and Q of A and B [pixels][B] binary64, part [height][R][6][B], out [6][R][B], NA and NB [pixels][M], diff and var [pixels][B] binary32, labels [pixels]
 struct CompareBuffers { double* S[2]; double* Q[2]; uint64_t* part; uint64_t* out; uint32_t* N[2]; float* diff; float* var; uint8_t* labels; };
 int compare_buffers(ssx_ctx* ctx, uint32_t width, uint32_t height, uint32_t B, uint32_t R, CompareBuffers* d) {
-	const size_t pixels = (size_t)width * height, b_bins = pixels * B * sizeof(double), b_part = (size_t)height * R * 6u * B * 8u, b_out = (size_t)6u * R * B * 8u,
-	             b_counts = pixels * (B / 4u) * sizeof(uint32_t), b_map = pixels * B * sizeof(float);
-	SSX_HIP(ctx, ctx->d_probe.reserve(4u * b_bins + b_part + b_out + 2u * b_counts + 2u * b_map + pixels));
-	uint8_t* at = ctx->d_probe.as<uint8_t>();
-	for (int x = 0; x < 2; ++x) { d->S[x] = reinterpret_cast<double*>(at); at += b_bins; d->Q[x] = reinterpret_cast<double*>(at); at += b_bins; }
-	d->part = reinterpret_cast<uint64_t*>(at); at += b_part;
-	d->out = reinterpret_cast<uint64_t*>(at); at += b_out;
-	for (int x = 0; x < 2; ++x) { d->N[x] = reinterpret_cast<uint32_t*>(at); at += b_counts; }
-	d->diff = reinterpret_cast<float*>(at); at += b_map;
-	d->var = reinterpret_cast<float*>(at); at += b_map;
-	d->labels = at;
-	return SSX_OK;
+	const size_t pixels = (size_t)width * height;
+	return carve(ctx, ctx->d_probe, [&](Carver& c) {
+		for (int x = 0; x < 2; ++x) { d->S[x] = c.take<double>(pixels * B); d->Q[x] = c.take<double>(pixels * B); }
+		d->part = c.take<uint64_t>((size_t)height * R * 6u * B);
+		d->out = c.take<uint64_t>((size_t)6u * R * B);
+		for (int x = 0; x < 2; ++x) d->N[x] = c.take<uint32_t>(pixels * (B / 4u));
+		d->diff = c.take<float>(pixels * B);
+		d->var = c.take<float>(pixels * B);
+		d->labels = c.take<uint8_t>(pixels);
+	});
 }
 
 int compare_check(ssx_ctx* ctx, const char* what, uint32_t width, uint32_t height, const double* SB, const double* QB, const uint32_t* NB, const uint8_t* labels, uint32_t R, double t2,
@@ -171,12 +148,11 @@ int compare_device(ssx_ctx* ctx, const CompareBuffers& d, uint32_t width, uint32
 	if (R * B <= 256u) hipLaunchKernelGGL(ssx_compare_rows_kernel, dim3(height), dim3(256), 0, ctx->stream, a);
 	else hipLaunchKernelGGL(ssx_compare_rows_wide_kernel, dim3(height), dim3(256), 0, ctx->stream, a);
 	SSX_HIP(ctx, hipGetLastError());
-	hipLaunchKernelGGL(ssx_compare_reduce_kernel, blocks_of((size_t)6u * R * B), dim3(256), 0, ctx->stream, a);
+	hipLaunchKernelGGL(ssx_ordered_reduce_kernel, blocks_of((size_t)6u * R * B), dim3(256), 0, ctx->stream, d.part, d.out, height, R, B, 6u, 0x38u);
 	SSX_HIP(ctx, hipGetLastError());
 	SSX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	const size_t n = (size_t)R * B * 8u, b_map = (size_t)width * height * B * sizeof(float);
-	void* const outs[6] = { DD, VV, X2, CC, NC, EX };
-	for (int q = 0; q < 6; ++q) SSX_HIP(ctx, hipMemcpy(outs[q], d.out + (size_t)q * R * B, n, hipMemcpyDeviceToHost));
+	if (const int rc = copy_planes(ctx, d.out, (size_t)R * B, { DD, VV, X2, CC, NC, EX })) return rc;
+	const size_t b_map = (size_t)width * height * B * sizeof(float);
 	if (diff) SSX_HIP(ctx, hipMemcpy(diff, d.diff, b_map, hipMemcpyDeviceToHost));
 	if (var) SSX_HIP(ctx, hipMemcpy(var, d.var, b_map, hipMemcpyDeviceToHost));
 	return SSX_OK;
@@ -198,7 +174,7 @@ int ssx_spectral_compare_arrays(ssx_ctx* ctx, uint32_t width, uint32_t height, u
                                 double* DD, double* VV, double* X2, uint64_t* CC, uint64_t* NC, uint64_t* EX, float* diff, float* var) {
 	if (!ctx) return SSX_ERR_ARG;
 	const char* const what = "ssx_spectral_compare_arrays";
-	if (bins < 4u || bins > 64u || (bins & 3u)) return fail(ctx, SSX_ERR_ARG, fmt("%s: %u bins: need a multiple of 4 up to 64", what, bins));
+	if (!valid_bins(bins)) return fail(ctx, SSX_ERR_ARG, fmt("%s: %u bins: need a multiple of 4 up to 64", what, bins));
 	if (!SA || !QA || !NA) return fail(ctx, SSX_ERR_ARG, fmt("%s: SA, QA and NA must not be NULL", what));
 	int rc = denoise_check_size(ctx, width, height, what);
 	if (rc) return rc;
@@ -219,27 +195,14 @@ int ssx_spectral_compare(ssx_ctx* ctx, const ssx_spectral_info_t* other_info, co
 	int rc = moments_ready(ctx, what);
 	if (rc) return rc;
 	const ssx_render_params& p = ctx->cur;
-	const uint32_t B = ctx->spectral_bins, M = B / 4u;
-	const float bin_width = ctx->lambda_step / (float)M; // (what ssx_spectral_read reports)
+	const uint32_t B = ctx->spectral_bins;
 	if (!other_info) return fail(ctx, SSX_ERR_ARG, fmt("%s: other_info must not be NULL", what));
-	if (other_info->struct_size != sizeof *other_info) return fail(ctx, SSX_ERR_ARG, fmt("%s: ssx_spectral_info_t.struct_size mismatch", what));
-	if (other_info->width != p.width || other_info->height != p.height)
-		return fail(ctx, SSX_ERR_ARG, fmt("%s: size differs (the other render: %u x %u, this render: %u x %u)", what, other_info->width, other_info->height, p.width, p.height));
-	if (other_info->bins != B) return fail(ctx, SSX_ERR_ARG, fmt("%s: bins differs (the other render: %u, this context: %u)", what, other_info->bins, B));
-	if (memcmp(&other_info->lambda_min, &ctx->lambda_min, sizeof(float)) != 0)
-		return fail(ctx, SSX_ERR_ARG, fmt("%s: lambda_min differs (the other render: %.9g, the uploaded scene: %.9g)", what, (double)other_info->lambda_min, (double)ctx->lambda_min));
-	if (memcmp(&other_info->bin_width, &bin_width, sizeof(float)) != 0)
-		return fail(ctx, SSX_ERR_ARG, fmt("%s: bin_width differs (the other render: %.9g, the uploaded scene: %.9g)", what, (double)other_info->bin_width, (double)bin_width));
+	const std::string why = spectral_info_mismatch(ctx, what, "the other render", nullptr, other_info);
+	if (!why.empty()) return fail(ctx, SSX_ERR_ARG, why);
 	if ((rc = compare_check(ctx, what, p.width, p.height, SB, QB, NB, labels, regions, t2, DD, VV, X2, CC, NC, EX))) return rc;
 	CompareBuffers d;
 	if ((rc = compare_buffers(ctx, p.width, p.height, B, regions, &d))) return rc;
-	// the state, row-major, into the arrays the pure call uploads as A: pixels of other contexts read as 0 -- count 0, not comparable
-	hipLaunchKernelGGL(ssx_spectral_export_kernel, pixel_blocks(&p), dim3(256), 0, ctx->stream, ctx->d_spectral_sums.as<const double>(), ctx->d_spectral_counts.as<const uint32_t>(),
-	                   (float*)nullptr, d.S[0], d.N[0], pixel_grid(&p), M);
-	SSX_HIP(ctx, hipGetLastError());
-	hipLaunchKernelGGL(ssx_spectral_variance_kernel, pixel_blocks(&p), dim3(256), 0, ctx->stream, ctx->d_spectral_sums.as<const double>(), ctx->d_spectral_moments.as<const double>(),
-	                   ctx->d_spectral_counts.as<const uint32_t>(), (float*)nullptr, d.Q[0], pixel_grid(&p), M);
-	SSX_HIP(ctx, hipGetLastError());
+	if ((rc = state_to_rows(ctx, d.S[0], d.N[0], d.Q[0]))) return rc;                        // the context's own render is A
 	if ((rc = compare_upload(ctx, d, 1, (size_t)p.width * p.height, B, SB, QB, NB))) return rc;
 	return compare_device(ctx, d, p.width, p.height, B, labels, regions, t2, DD, VV, X2, CC, NC, EX, diff, var);
 }

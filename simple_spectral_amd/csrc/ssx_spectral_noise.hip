@@ -50,9 +50,7 @@ extern "C" __global__ void __launch_bounds__(256) ssx_spectral_noise_tiles_kerne
 				cls = n >= 2u ? 1u : 2u;
 				if (n >= 2u) {
 					const size_t at = ((size_t)slot * B + b) * 64u + px;
-					const double s = a.S[at];
-					e = (moment_deviations(a.Q[at], s, n) / (double)(n - 1u)) / (double)n;
-					mu = s / (double)n;
+					e = cell_variance(a.Q[at], a.S[at], n, &mu);
 				}
 			}
 			noise_e[bl * SSX_NOISE_STRIDE + px] = e;
@@ -104,21 +102,19 @@ extern "C" __global__ void __launch_bounds__(256) ssx_spectral_noise_reduce_kern
 
 namespace {
 
-// d_stage: tEV | tEM [tiles][B] binary64 | out [4][B] | tPP | tPU [tiles][B] uint32 | mask [pixels] -- eight-byte quantities first.  Nothing of the image's size
-// but the mask: S, Q and N are read where they lie.
+// d_stage: tEV and tEM [tiles][B] binary64, out [4][B], tPP and tPU [tiles][B] uint32, mask [pixels]: nothing of the image's size but the mask (S, Q, N are read where they lie)
 struct NoiseBuffers { double* tEV; double* tEM; uint64_t* out; uint32_t* tPP; uint32_t* tPU; uint8_t* mask; size_t partial_bytes; };
 int noise_buffers(ssx_ctx* ctx, size_t tiles, uint32_t B, size_t pixels, NoiseBuffers* d) {
-	const size_t n = tiles * B, b_out = (size_t)4u * B * 8u;
-	SSX_HIP(ctx, ctx->d_stage.reserve(n * 24u + b_out + pixels));
-	uint8_t* at = ctx->d_stage.as<uint8_t>();
-	d->tEV = reinterpret_cast<double*>(at); at += n * 8u;
-	d->tEM = reinterpret_cast<double*>(at); at += n * 8u;
-	d->out = reinterpret_cast<uint64_t*>(at); at += b_out;
-	d->tPP = reinterpret_cast<uint32_t*>(at); at += n * 4u;
-	d->tPU = reinterpret_cast<uint32_t*>(at); at += n * 4u;
-	d->mask = at;
-	d->partial_bytes = n * 24u + b_out;
-	return SSX_OK;
+	const size_t n = tiles * B;
+	return carve(ctx, ctx->d_stage, [&](Carver& c) {
+		d->tEV = c.take<double>(n);
+		d->tEM = c.take<double>(n);
+		d->out = c.take<uint64_t>((size_t)4u * B);
+		d->tPP = c.take<uint32_t>(n);
+		d->tPU = c.take<uint32_t>(n);
+		d->partial_bytes = c.at;                                                             // (from tEV on: what ssx_spectral_noise zeroes in one go)
+		d->mask = c.take<uint8_t>(pixels);
+	});
 }
 
 // The one body of both entry points: the partials are in d already; the second kernel runs, the four [B] arrays come back.
@@ -126,9 +122,7 @@ int noise_reduce_device(ssx_ctx* ctx, const NoiseBuffers& d, uint32_t tiles, uin
 	hipLaunchKernelGGL(ssx_spectral_noise_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, d.tEV, d.tEM, d.tPP, d.tPU, d.out, tiles, B);
 	SSX_HIP(ctx, hipGetLastError());
 	SSX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	void* const outs[4] = { EV, EM, PP, PU };
-	for (int k = 0; k < 4; ++k) SSX_HIP(ctx, hipMemcpy(outs[k], d.out + (size_t)k * B, (size_t)B * 8u, hipMemcpyDeviceToHost));
-	return SSX_OK;
+	return copy_planes(ctx, d.out, B, { EV, EM, PP, PU });
 }
 
 } // namespace
@@ -170,7 +164,7 @@ int ssx_spectral_noise_reduce(ssx_ctx* ctx, uint32_t tiles, uint32_t bins, const
                               double* EV, double* EM, uint64_t* PP, uint64_t* PU) {
 	if (!ctx) return SSX_ERR_ARG;
 	const char* const what = "ssx_spectral_noise_reduce";
-	if (bins < 4u || bins > 64u || (bins & 3u)) return fail(ctx, SSX_ERR_ARG, fmt("%s: %u bins: need a multiple of 4 up to 64", what, bins));
+	if (!valid_bins(bins)) return fail(ctx, SSX_ERR_ARG, fmt("%s: %u bins: need a multiple of 4 up to 64", what, bins));
 	if (tiles < 1u || tiles > (1u << 22)) return fail(ctx, SSX_ERR_ARG, fmt("%s: %u tiles: need 1..2^22 (an image of at most 2^28 pixels)", what, tiles));
 	if (!tEV || !tEM || !tPP || !tPU || !EV || !EM || !PP || !PU) return fail(ctx, SSX_ERR_ARG, fmt("%s: the partials and the four outputs must not be NULL", what));
 	int rc = idle_on_device(ctx);

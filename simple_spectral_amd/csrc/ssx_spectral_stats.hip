@@ -47,6 +47,13 @@ __device__ __forceinline__ double moment_deviations(double Q, double S, uint32_t
 	return (q < 0.0) ? 0.0 : q;
 }
 
+// The estimate of one cell from Q, S and n >= 2: the variance of its mean, (q / (n - 1)) / n, and -- where the caller wants it -- the mean S / n
+__device__ __forceinline__ double cell_variance(double Q, double S, uint32_t n, double* mean = nullptr) {
+	const double e = (moment_deviations(Q, S, n) / (double)(n - 1u)) / (double)n;
+	if (mean) *mean = S / (double)n;
+	return e;
+}
+
 // S, Q, N -> row-major [height][width][B] var (binary32) and Q (either may be NULL); 0 for pixels the context does not own.
 //     n = N[b % M];   n < 2: var = +inf;   else var = (float)((q / (double)(n-1)) / (double)n)
 extern "C" __global__ void __launch_bounds__(256) ssx_spectral_variance_kernel(const double* S, const double* Q, const uint32_t* N, float* var, double* q_out, SsxPixelGrid g, uint32_t M) {
@@ -61,7 +68,7 @@ extern "C" __global__ void __launch_bounds__(256) ssx_spectral_variance_kernel(c
 			const size_t at = (slot * B + b) * 64u + lane;
 			const uint32_t n = N[(slot * M + b % M) * 64u + lane];
 			qq = Q[at];
-			v = n < 2u ? __uint_as_float(0x7F800000u) : (float)((moment_deviations(qq, S[at], n) / (double)(n - 1u)) / (double)n);
+			v = n < 2u ? __uint_as_float(0x7F800000u) : (float)cell_variance(qq, S[at], n);
 		}
 		if (var) var[(size_t)p * B + b] = v;
 		if (q_out) q_out[(size_t)p * B + b] = qq;
@@ -71,14 +78,7 @@ extern "C" __global__ void __launch_bounds__(256) ssx_spectral_variance_kernel(c
 // The inverse of the variance kernel's q for the tiles this context owns (ssx_spectral_moments_import): row-major whole-image q [height][width][B] (row 0 =
 // bottom; whoever exported it may have owned other tiles) -> Q[tile slot][bin][pixel of the tile].  ssx_spectral_import_kernel's geometry for one array, one
 // 256-lane workgroup per owned tile slot (slot -> tile by tile_of_slot), no atomics: a workgroup writes its own slot only.
-//   in:   the 8 pixel rows of a tile are 8 runs of cols * B consecutive doubles (cols = 8, fewer in the image's last tile column); consecutive lanes read
-//         consecutive 16-byte pairs of a run (B is a multiple of 4: every run starts 32-byte aligned).  Rows and columns outside a ragged image are never read.
-//   LDS:  [64 pixels][B + 1] doubles (33 KB at B = 64).  On the way out lane = pixel reads element b of its row, 8-byte address (B + 1) * pixel + b.  A
-//         ds_read_b64 is served in two groups of 32 lanes over 64 four-byte banks, bank = (address / 4) mod 64: the 32 lanes of a group need 32 distinct bank
-//         pairs, i.e. 2 * (B + 1) * pixel mod 64 distinct over 32 consecutive pixels, which holds exactly when the stride B + 1 is odd; the unpadded B -- 4, ...,
-//         64 doubles -- would put 2, ..., 32 lanes on one pair.  The price is on the way in: a row starts 8-byte aligned only, so a pair goes in as two
-//         ds_write_b64 (groups of 16 lanes over 32 banks; the lanes of a group write every other 8-byte word, so lanes l and l + 8 meet: 2-way), which the
-//         write's own register transfer mostly covers.
+//   in:   by tile_rows_to_lds (ssx_spectral.hip), into [64 pixels][B + 1] doubles of LDS (33 KB at B = 64).
 //   out:  wave w stores bins w, w + 4, ...: per bin the 64 lanes' doubles are 512 consecutive bytes.  Lanes of pixels outside the image store +0.0, what the
 //         memset of a fresh render leaves there.
 // The check.  On the way out lane = pixel, wave = bin: the lane that stores Q[slot][b][px] reads the context's own S[slot][b][px] and N[slot][b % M][px] where
@@ -95,13 +95,7 @@ extern "C" __global__ void __launch_bounds__(256) ssx_spectral_moments_import_ke
 	uint32_t tx, ty;
 	(void)tile_of_slot(g, slot, tx, ty);
 	const uint32_t i0 = tx * 8u, j0 = ty * 8u, cols = min(8u, g.width - i0), rows = min(8u, g.height - j0);
-	const uint32_t pairs = cols * (B / 2u);                                                       // 16-byte pairs of one run
-	for (uint32_t e = tid; e < rows * pairs; e += 256u) {
-		const uint32_t r = e / pairs, v = e - r * pairs, c = (2u * v) / B, b = 2u * v - c * B;      // (B is even: a pair never straddles two pixels)
-		const double2 d = reinterpret_cast<const double2*>(q + ((size_t)(j0 + r) * g.width + i0) * B)[v];
-		double* const o = moment_lds + (r * 8u + c) * stride + b;
-		o[0] = d.x; o[1] = d.y;
-	}
+	tile_rows_to_lds(q, moment_lds, g.width, i0, j0, cols, rows, B);
 	__syncthreads();
 	const uint32_t px = tid & 63u, w = tid >> 6;
 	const bool inside = (px & 7u) < cols && (px >> 3) < rows;
@@ -153,25 +147,23 @@ extern "C" __global__ void __launch_bounds__(128) ssx_probe_rows_kernel(SsxProbe
 	for (uint32_t r = 0; r < a.R; ++r) a.part[(((size_t)j * a.R + r) * 4u + quantity) * B + b] = acc[r * lanes];
 }
 
-// Stage 2: one lane per (quantity, r, b) adds the rows' partials in ascending j, from +0.0 / 0.
-extern "C" __global__ void __launch_bounds__(256) ssx_probe_reduce_kernel(SsxProbeArgs a) {
-	const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x, B = a.B;
-	if (e >= 4u * a.R * B) return;
-	const uint32_t quantity = e / (a.R * B), rb = e - quantity * (a.R * B), r = rb / B, b = rb - r * B;
-	const uint64_t* const src = a.part + ((size_t)r * 4u + quantity) * B + b;
-	const size_t stride = (size_t)a.R * 4u * B;
-	if (quantity & 1u) {
-		uint64_t total = 0ull;
-		for (uint32_t j = 0; j < a.height; ++j) total += src[j * stride];
-		a.out[e] = total;
-	} else {
-		double total = 0.0;
-		for (uint32_t j = 0; j < a.height; ++j) total += reinterpret_cast<const double*>(src)[j * stride];
-		reinterpret_cast<double*>(a.out)[e] = total;
-	}
-}
+// Stage 2 is ssx_ordered_reduce_kernel (ssx_spectral.hip) with 4 quantities, NN and UU (1 and 3) the integers.
 
 namespace {
+
+// The state, row-major, into the arrays a pure call uploads (ssx_spectral_probe, ssx_spectral_compare): pixels of other contexts read as +0.0 and count 0 --
+// they add nothing to a probe and are not comparable.
+int state_to_rows(ssx_ctx* ctx, double* S, uint32_t* N, double* Q) {
+	const ssx_render_params& p = ctx->cur;
+	const uint32_t M = ctx->spectral_bins / 4u;
+	hipLaunchKernelGGL(ssx_spectral_export_kernel, pixel_blocks(&p), dim3(256), 0, ctx->stream, ctx->d_spectral_sums.as<const double>(), ctx->d_spectral_counts.as<const uint32_t>(),
+	                   (float*)nullptr, S, N, pixel_grid(&p), M);
+	SSX_HIP(ctx, hipGetLastError());
+	hipLaunchKernelGGL(ssx_spectral_variance_kernel, pixel_blocks(&p), dim3(256), 0, ctx->stream, ctx->d_spectral_sums.as<const double>(), ctx->d_spectral_moments.as<const double>(),
+	                   ctx->d_spectral_counts.as<const uint32_t>(), (float*)nullptr, Q, pixel_grid(&p), M);
+	SSX_HIP(ctx, hipGetLastError());
+	return SSX_OK;
+}
 
 size_t moment_bytes(const ssx_ctx* ctx, uint32_t tiles) { return (size_t)tiles * ctx->spectral_bins * 64u * sizeof(double); }
 
@@ -218,40 +210,21 @@ void moments_publish(ssx_ctx* ctx, bool active) {
 void moments_invalidate(ssx_ctx* ctx, const char* why) { ctx->sums.moments_valid = false; ctx->moments_note = why; }
 void moments_drop(ssx_ctx* ctx) { ctx->d_spectral_moments.release(); }
 
-// What ssx_spectral_variance and ssx_spectral_probe ask first: bins on, moments on, no render, valid bins and valid moments; then the device is the context's.
-int moments_ready(ssx_ctx* ctx, const char* what) {
-	if (!ctx->spectral_bins) return fail(ctx, SSX_ERR_STATE, fmt("%s: spectral output is off (ssx_set_spectral_bins)", what));
-	if (!ctx->spectral_moments) return fail(ctx, SSX_ERR_STATE, fmt("%s: spectral moments are off (ssx_set_spectral_moments)", what));
-	if (ctx->rendering.load()) return fail(ctx, SSX_ERR_STATE, "render in progress");
-	if (!ctx->sums.continuable || !ctx->sums.spectral_valid)
-		return fail(ctx, SSX_ERR_STATE, fmt("%s: the context holds no spectral bins: ", what) + (ctx->sums.continuable ? ctx->spectral_note : std::string("no render has accumulated any (ssx_render_start first)")));
-	if (!ctx->sums.moments_valid) return fail(ctx, SSX_ERR_STATE, fmt("%s: the context holds no spectral moments: ", what) + ctx->moments_note);
-	SSX_HIP(ctx, hipSetDevice(ctx->device));
-	return wait_device_pending(ctx);
-}
+// what every read-out of the moments asks first
+int moments_ready(ssx_ctx* ctx, const char* what) { return spectral_ready(ctx, what, true); }
 
-void spectral_info_of(const ssx_ctx* ctx, ssx_spectral_info_t* info) {
-	const ssx_render_params& p = ctx->cur;
-	memset(info, 0, sizeof *info);
-	info->struct_size = sizeof *info;
-	info->width = p.width; info->height = p.height; info->bins = ctx->spectral_bins; info->done_spp = ctx->done_spp.load();
-	info->lambda_min = ctx->lambda_min; info->bin_width = ctx->lambda_step / (float)(ctx->spectral_bins / 4u);
-}
-
-// d_probe: sums | q [pixels][B] binary64 | part [height][R][4][B] | out [4][R][B] | counts [pixels][M] | labels [pixels] -- eight-byte quantities first
+// d_probe: sums and q [pixels][B] binary64, part [height][R][4][B], out [4][R][B], counts [pixels][M], labels [pixels]
 struct ProbeBuffers { double* sums; double* q; uint64_t* part; uint64_t* out; uint32_t* counts; uint8_t* labels; };
 int probe_buffers(ssx_ctx* ctx, uint32_t width, uint32_t height, uint32_t B, uint32_t R, ProbeBuffers* d) {
-	const size_t pixels = (size_t)width * height, b_bins = pixels * B * sizeof(double), b_part = (size_t)height * R * 4u * B * 8u, b_out = (size_t)4u * R * B * 8u,
-	             b_counts = pixels * (B / 4u) * sizeof(uint32_t);
-	SSX_HIP(ctx, ctx->d_probe.reserve(2u * b_bins + b_part + b_out + b_counts + pixels));
-	uint8_t* at = ctx->d_probe.as<uint8_t>();
-	d->sums = reinterpret_cast<double*>(at); at += b_bins;
-	d->q = reinterpret_cast<double*>(at); at += b_bins;
-	d->part = reinterpret_cast<uint64_t*>(at); at += b_part;
-	d->out = reinterpret_cast<uint64_t*>(at); at += b_out;
-	d->counts = reinterpret_cast<uint32_t*>(at); at += b_counts;
-	d->labels = at;
-	return SSX_OK;
+	const size_t pixels = (size_t)width * height;
+	return carve(ctx, ctx->d_probe, [&](Carver& c) {
+		d->sums = c.take<double>(pixels * B);
+		d->q = c.take<double>(pixels * B);
+		d->part = c.take<uint64_t>((size_t)height * R * 4u * B);
+		d->out = c.take<uint64_t>((size_t)4u * R * B);
+		d->counts = c.take<uint32_t>(pixels * (B / 4u));
+		d->labels = c.take<uint8_t>(pixels);
+	});
 }
 
 int probe_check(ssx_ctx* ctx, const char* what, uint32_t width, uint32_t height, const uint8_t* labels, uint32_t R, const void* SS, const void* NN, const void* VV, const void* UU) {
@@ -273,13 +246,10 @@ int probe_device(ssx_ctx* ctx, const ProbeBuffers& d, uint32_t width, uint32_t h
 	const size_t lds = (size_t)R * 2u * B * sizeof(uint64_t); // <= 32 KB
 	hipLaunchKernelGGL(ssx_probe_rows_kernel, dim3(height, 2), dim3(2u * B), lds, ctx->stream, a);
 	SSX_HIP(ctx, hipGetLastError());
-	hipLaunchKernelGGL(ssx_probe_reduce_kernel, blocks_of((size_t)4u * R * B), dim3(256), 0, ctx->stream, a);
+	hipLaunchKernelGGL(ssx_ordered_reduce_kernel, blocks_of((size_t)4u * R * B), dim3(256), 0, ctx->stream, d.part, d.out, height, R, B, 4u, 0xAu);
 	SSX_HIP(ctx, hipGetLastError());
 	SSX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	const size_t n = (size_t)R * B * 8u;
-	void* const outs[4] = { SS, NN, VV, UU };
-	for (int k = 0; k < 4; ++k) SSX_HIP(ctx, hipMemcpy(outs[k], d.out + (size_t)k * R * B, n, hipMemcpyDeviceToHost));
-	return SSX_OK;
+	return copy_planes(ctx, d.out, (size_t)R * B, { SS, NN, VV, UU });
 }
 
 } // namespace
@@ -307,17 +277,15 @@ int ssx_spectral_variance(ssx_ctx* ctx, ssx_spectral_info_t* info, float* var, d
 	if (!var && !q) return SSX_OK;
 	const ssx_render_params& p = ctx->cur;
 	const uint32_t B = ctx->spectral_bins, M = B / 4u;
-	const size_t pixels = (size_t)p.width * p.height, b_q = pixels * B * sizeof(double), b_var = pixels * B * sizeof(float);
-	DeviceBuffer& stage = ctx->d_stage;
-	SSX_HIP(ctx, stage.reserve(b_q + b_var));
-	double* const d_q = stage.as<double>();
-	float* const d_var = reinterpret_cast<float*>(stage.as<uint8_t>() + b_q);
+	const size_t n = (size_t)p.width * p.height * B;
+	double* d_q; float* d_var;
+	if (const int rc = carve(ctx, ctx->d_stage, [&](Carver& c) { d_q = c.take<double>(n); d_var = c.take<float>(n); })) return rc;
 	hipLaunchKernelGGL(ssx_spectral_variance_kernel, pixel_blocks(&p), dim3(256), 0, ctx->stream, ctx->d_spectral_sums.as<const double>(), ctx->d_spectral_moments.as<const double>(),
 	                   ctx->d_spectral_counts.as<const uint32_t>(), var ? d_var : nullptr, q ? d_q : nullptr, pixel_grid(&p), M);
 	SSX_HIP(ctx, hipGetLastError());
 	SSX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	if (q) SSX_HIP(ctx, hipMemcpy(q, d_q, b_q, hipMemcpyDeviceToHost));
-	if (var) SSX_HIP(ctx, hipMemcpy(var, d_var, b_var, hipMemcpyDeviceToHost));
+	if (q) SSX_HIP(ctx, hipMemcpy(q, d_q, n * sizeof(double), hipMemcpyDeviceToHost));
+	if (var) SSX_HIP(ctx, hipMemcpy(var, d_var, n * sizeof(float), hipMemcpyDeviceToHost));
 	return SSX_OK;
 }
 
@@ -335,31 +303,21 @@ int ssx_spectral_moments_import(ssx_ctx* ctx, const ssx_spectral_info_t* info, c
 		return fail(ctx, SSX_ERR_ARG, why);
 	};
 	if (!info || !q) return refuse(fmt("%s: info and q must not be NULL", what));
-	if (info->struct_size != sizeof *info) return refuse(fmt("%s: ssx_spectral_info_t.struct_size mismatch", what));
+	const std::string why = spectral_info_mismatch(ctx, what, "these moments", "the imported bins", info);
+	if (!why.empty()) return refuse(why);
 	const ssx_render_params& p = ctx->cur;
-	const uint32_t B = ctx->spectral_bins, M = B / 4u, done = ctx->done_spp.load();
-	const float bin_width = ctx->lambda_step / (float)M; // (what ssx_spectral_read reports)
-	if (info->width != p.width || info->height != p.height)
-		return refuse(fmt("%s: size differs (these moments: %u x %u, this render: %u x %u)", what, info->width, info->height, p.width, p.height));
-	if (info->bins != B) return refuse(fmt("%s: bins differs (these moments: %u, this context: %u)", what, info->bins, B));
-	if (info->done_spp != done) return refuse(fmt("%s: done_spp differs (these moments: %u, the imported bins: %u)", what, info->done_spp, done));
-	if (memcmp(&info->lambda_min, &ctx->lambda_min, sizeof(float)) != 0)
-		return refuse(fmt("%s: lambda_min differs (these moments: %.9g, the uploaded scene: %.9g)", what, (double)info->lambda_min, (double)ctx->lambda_min));
-	if (memcmp(&info->bin_width, &bin_width, sizeof(float)) != 0)
-		return refuse(fmt("%s: bin_width differs (these moments: %.9g, the uploaded scene: %.9g)", what, (double)info->bin_width, (double)bin_width));
+	const uint32_t B = ctx->spectral_bins, M = B / 4u;
 	moments_invalidate(ctx, "an ssx_spectral_moments_import on top of ssx_spectral_import was refused or failed (ssx_spectral_import itself does not carry them)");
 	SSX_HIP(ctx, hipSetDevice(ctx->device));
 	if (const int rc = wait_device_pending(ctx)) return rc;
 	const uint32_t tiles = owned_tiles(p);
-	const size_t pixels = (size_t)p.width * p.height, b_q = pixels * B * sizeof(double);
+	const size_t n = (size_t)p.width * p.height * B;
 	SSX_HIP(ctx, ctx->d_spectral_moments.reserve(moment_bytes(ctx, tiles))); // (before the kernel; ssx_scratch_info counts it from here on)
 	uint32_t bad[3] = { 0u, 0u, 0u };
 	if (tiles) {
-		DeviceBuffer& stage = ctx->d_stage; // q | the three flags of the check
-		SSX_HIP(ctx, stage.reserve(b_q + sizeof bad));
-		double* const d_q = stage.as<double>();
-		uint32_t* const d_bad = reinterpret_cast<uint32_t*>(stage.as<uint8_t>() + b_q);
-		SSX_HIP(ctx, hipMemcpyAsync(d_q, q, b_q, hipMemcpyHostToDevice, ctx->stream));
+		double* d_q; uint32_t* d_bad; // d_stage: q and the three flags of the check
+		if (const int rc = carve(ctx, ctx->d_stage, [&](Carver& c) { d_q = c.take<double>(n); d_bad = c.take<uint32_t>(3); })) return rc;
+		SSX_HIP(ctx, hipMemcpyAsync(d_q, q, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
 		SSX_HIP(ctx, hipMemsetAsync(d_bad, 0, sizeof bad, ctx->stream));
 		const size_t lds = 64u * (size_t)(B + 1u) * sizeof(double); // <= 33 KB at 64 bins
 		hipLaunchKernelGGL(ssx_spectral_moments_import_kernel, dim3(tiles), dim3(256), lds, ctx->stream, d_q, ctx->d_spectral_sums.as<const double>(),
@@ -383,24 +341,17 @@ int ssx_spectral_probe(ssx_ctx* ctx, const uint8_t* labels, uint32_t regions, do
 	if (rc) return rc;
 	const ssx_render_params& p = ctx->cur;
 	if ((rc = probe_check(ctx, what, p.width, p.height, labels, regions, SS, NN, VV, UU))) return rc;
-	const uint32_t B = ctx->spectral_bins, M = B / 4u;
 	ProbeBuffers d;
-	if ((rc = probe_buffers(ctx, p.width, p.height, B, regions, &d))) return rc;
-	// the state, row-major, into the arrays the pure call uploads: pixels of other contexts read as 0 and add nothing
-	hipLaunchKernelGGL(ssx_spectral_export_kernel, pixel_blocks(&p), dim3(256), 0, ctx->stream, ctx->d_spectral_sums.as<const double>(), ctx->d_spectral_counts.as<const uint32_t>(),
-	                   (float*)nullptr, d.sums, d.counts, pixel_grid(&p), M);
-	SSX_HIP(ctx, hipGetLastError());
-	hipLaunchKernelGGL(ssx_spectral_variance_kernel, pixel_blocks(&p), dim3(256), 0, ctx->stream, ctx->d_spectral_sums.as<const double>(), ctx->d_spectral_moments.as<const double>(),
-	                   ctx->d_spectral_counts.as<const uint32_t>(), (float*)nullptr, d.q, pixel_grid(&p), M);
-	SSX_HIP(ctx, hipGetLastError());
-	return probe_device(ctx, d, p.width, p.height, B, labels, regions, SS, NN, VV, UU);
+	if ((rc = probe_buffers(ctx, p.width, p.height, ctx->spectral_bins, regions, &d))) return rc;
+	if ((rc = state_to_rows(ctx, d.sums, d.counts, d.q))) return rc;
+	return probe_device(ctx, d, p.width, p.height, ctx->spectral_bins, labels, regions, SS, NN, VV, UU);
 }
 
 int ssx_probe_arrays(ssx_ctx* ctx, uint32_t width, uint32_t height, uint32_t bins, const double* sums, const double* q, const uint32_t* counts, const uint8_t* labels, uint32_t regions,
                      double* SS, uint64_t* NN, double* VV, uint64_t* UU) {
 	if (!ctx) return SSX_ERR_ARG;
 	const char* const what = "ssx_probe_arrays";
-	if (bins < 4u || bins > 64u || (bins & 3u)) return fail(ctx, SSX_ERR_ARG, fmt("%s: %u bins: need a multiple of 4 up to 64", what, bins));
+	if (!valid_bins(bins)) return fail(ctx, SSX_ERR_ARG, fmt("%s: %u bins: need a multiple of 4 up to 64", what, bins));
 	if (!sums || !q || !counts) return fail(ctx, SSX_ERR_ARG, fmt("%s: sums, q and counts must not be NULL", what));
 	int rc = denoise_check_size(ctx, width, height, what);
 	if (rc) return rc;

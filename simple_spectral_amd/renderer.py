@@ -28,6 +28,28 @@ class SsxError(RuntimeError):
         self.code = code
 
 
+def _host(fn, *args):
+    """libssx_host.so's `fn`(*args); SsxError with the library's reason unless it returns 0."""
+    host = _capi.host_lib()
+    rc = getattr(host, fn)(*args)
+    if rc != 0:
+        raise SsxError(rc, host.ssh_last_error().decode())
+
+
+def _same_shape(what, names, ndim, arrays, dtypes):
+    """The arrays, C-contiguous in their dtypes; ValueError "`what`: `names`" unless all of them have one shape of ndim dimensions."""
+    arrays = [np.ascontiguousarray(a, dtype=t) for a, t in zip(arrays, dtypes)]
+    if arrays[0].ndim != ndim or any(a.shape != arrays[0].shape for a in arrays):
+        raise ValueError("%s: %s" % (what, names))
+    return arrays
+
+
+_F8, _U8 = np.float64, np.uint64
+_PROBE_SUMS = ("SS, NN, VV, UU must all have shape [R, B]", 2)
+_NOISE_TOTALS = ("EV, EM, PP, PU must all have shape [B]", 1)
+_COMPARE_SUMS = ("DD, VV, X2, CC, NC, EX must all have shape [R, B]", 2)
+
+
 @dataclass
 class Options:
     """Renderer::Options (src/renderer.hpp:16-29) plus the additive options of this build."""
@@ -101,12 +123,10 @@ class Scene:
             raise SsxError(_capi.SSX_ERR_SCENE, "unsupported render mode %r (spectral | rgb)" % (render_mode,))
         code = {"ours": _capi.SSX_UPLIFT_OURS, "meng": _capi.SSX_UPLIFT_MENG, "jh": _capi.SSX_UPLIFT_JH}[uplift]
         table_path = (meng_grid_path or os.path.join(data_dir, "meng-et-al-2015-grid.bin")) if uplift == "meng" else jh_coeff_path
-        rc = lib.ssh_scene_create_ex(name.encode(), data_dir.encode(), observer, tp, tw, th,
-                                     tex_path.encode() if tex_path else None, C.c_float(light_scale),
-                                     code | (0 if explicit_light_sampling else 0x100) | (0x200 if render_mode == "rgb" else 0),
-                                     table_path.encode() if table_path else None, jh_res, C.byref(self._h))
-        if rc != 0:
-            raise SsxError(rc, lib.ssh_last_error().decode())
+        _host("ssh_scene_create_ex", name.encode(), data_dir.encode(), observer, tp, tw, th,
+              tex_path.encode() if tex_path else None, C.c_float(light_scale),
+              code | (0 if explicit_light_sampling else 0x100) | (0x200 if render_mode == "rgb" else 0),
+              table_path.encode() if table_path else None, jh_res, C.byref(self._h))
         self.name = name
 
     @property
@@ -125,9 +145,7 @@ class Scene:
     def xyza_to_srgba(self, xyza):
         xyza = np.ascontiguousarray(xyza, dtype=np.float32)
         out = np.empty_like(xyza)
-        rc = self._lib.ssh_xyza_to_srgba(self._h, xyza.ctypes.data, out.ctypes.data, xyza.size // 4)
-        if rc != 0:
-            raise SsxError(rc, self._lib.ssh_last_error().decode())
+        _host("ssh_xyza_to_srgba", self._h, xyza.ctypes.data, out.ctypes.data, xyza.size // 4)
         return out
 
     def color_values(self, name):
@@ -188,67 +206,33 @@ def labels_from_prim(prim, prims):
 
 def probe_derive(SS, NN, VV, UU):
     """ssh_probe_derive: (mean, stderr) float64 of the probes' four arrays -- mean = NN ? SS / NN : 0, stderr = sqrt(VV * NN / (NN - UU)) / NN (NaN when NN == UU)."""
-    SS, VV = np.ascontiguousarray(SS, dtype=np.float64), np.ascontiguousarray(VV, dtype=np.float64)
-    NN, UU = np.ascontiguousarray(NN, dtype=np.uint64), np.ascontiguousarray(UU, dtype=np.uint64)
-    if SS.ndim != 2 or not (SS.shape == NN.shape == VV.shape == UU.shape):
-        raise ValueError("probe_derive: SS, NN, VV, UU must all have shape [R, B]")
+    SS, NN, VV, UU = _same_shape("probe_derive", *_PROBE_SUMS, (SS, NN, VV, UU), (_F8, _U8, _F8, _U8))
     mean, err = np.zeros_like(SS), np.zeros_like(SS)
-    host = _capi.host_lib()
-    rc = host.ssh_probe_derive(SS.shape[0], SS.shape[1], SS.ctypes.data, NN.ctypes.data, VV.ctypes.data, UU.ctypes.data, mean.ctypes.data, err.ctypes.data)
-    if rc != 0:
-        raise SsxError(rc, host.ssh_last_error().decode())
+    _host("ssh_probe_derive", SS.shape[0], SS.shape[1], SS.ctypes.data, NN.ctypes.data, VV.ctypes.data, UU.ctypes.data, mean.ctypes.data, err.ctypes.data)
     return mean, err
 
 
 def save_probe_csv(path, lambda_min, bin_width, SS, NN, VV, UU):
     """ssh_probe_save_csv (libssx_host.so), the writer the CLI's --probe-output uses: the line "region,bin,wavelength,mean,stderr,samples,unestimated", then one
     line per region and bin."""
-    SS, VV = np.ascontiguousarray(SS, dtype=np.float64), np.ascontiguousarray(VV, dtype=np.float64)
-    NN, UU = np.ascontiguousarray(NN, dtype=np.uint64), np.ascontiguousarray(UU, dtype=np.uint64)
-    if SS.ndim != 2 or not (SS.shape == NN.shape == VV.shape == UU.shape):
-        raise ValueError("save_probe_csv: SS, NN, VV, UU must all have shape [R, B]")
-    host = _capi.host_lib()
-    rc = host.ssh_probe_save_csv(os.fsencode(path), SS.shape[0], SS.shape[1], C.c_float(lambda_min), C.c_float(bin_width), SS.ctypes.data, NN.ctypes.data, VV.ctypes.data, UU.ctypes.data)
-    if rc != 0:
-        raise SsxError(rc, host.ssh_last_error().decode())
-
-
-def _noise_totals(EV, EM, PP, PU, what):
-    EV, EM = np.ascontiguousarray(EV, dtype=np.float64), np.ascontiguousarray(EM, dtype=np.float64)
-    PP, PU = np.ascontiguousarray(PP, dtype=np.uint64), np.ascontiguousarray(PU, dtype=np.uint64)
-    if EV.ndim != 1 or not (EV.shape == EM.shape == PP.shape == PU.shape):
-        raise ValueError("%s: EV, EM, PP, PU must all have shape [B]" % what)
-    return EV, EM, PP, PU
+    SS, NN, VV, UU = _same_shape("save_probe_csv", *_PROBE_SUMS, (SS, NN, VV, UU), (_F8, _U8, _F8, _U8))
+    _host("ssh_probe_save_csv", os.fsencode(path), SS.shape[0], SS.shape[1], C.c_float(lambda_min), C.c_float(bin_width), SS.ctypes.data, NN.ctypes.data, VV.ctypes.data, UU.ctypes.data)
 
 
 def spectral_noise_derive(EV, EM, PP, PU):
     """ssh_spectral_noise_derive: (noise, coverage, rel float64 [B]) of the spectral noise figure's totals (include/ssx.h "Spectral noise figure") -- noise =
     sqrt(sum EV / P) / (sum EM / P), coverage = P / (P + U), rel[b] = sqrt(EV[b] / PP[b]) / (EM[b] / PP[b]); NaN where nothing is estimable or a mean is 0."""
-    EV, EM, PP, PU = _noise_totals(EV, EM, PP, PU, "spectral_noise_derive")
+    EV, EM, PP, PU = _same_shape("spectral_noise_derive", *_NOISE_TOTALS, (EV, EM, PP, PU), (_F8, _F8, _U8, _U8))
     noise, coverage, rel = C.c_double(), C.c_double(), np.zeros_like(EV)
-    host = _capi.host_lib()
-    rc = host.ssh_spectral_noise_derive(EV.shape[0], EV.ctypes.data, EM.ctypes.data, PP.ctypes.data, PU.ctypes.data, C.addressof(noise), C.addressof(coverage), rel.ctypes.data)
-    if rc != 0:
-        raise SsxError(rc, host.ssh_last_error().decode())
+    _host("ssh_spectral_noise_derive", EV.shape[0], EV.ctypes.data, EM.ctypes.data, PP.ctypes.data, PU.ctypes.data, C.addressof(noise), C.addressof(coverage), rel.ctypes.data)
     return noise.value, coverage.value, rel
 
 
 def save_spectral_noise_csv(path, lambda_min, bin_width, EV, EM, PP, PU):
     """ssh_spectral_noise_save_csv (libssx_host.so), the writer the CLI's --spectral-noise-output uses: the line "bin,wavelength,rel,EV,EM,estimable,unestimated",
     then one line per bin."""
-    EV, EM, PP, PU = _noise_totals(EV, EM, PP, PU, "save_spectral_noise_csv")
-    host = _capi.host_lib()
-    rc = host.ssh_spectral_noise_save_csv(os.fsencode(path), EV.shape[0], C.c_float(lambda_min), C.c_float(bin_width), EV.ctypes.data, EM.ctypes.data, PP.ctypes.data, PU.ctypes.data)
-    if rc != 0:
-        raise SsxError(rc, host.ssh_last_error().decode())
-
-
-def _compare_sums(DD, VV, X2, CC, NC, EX, what):
-    DD, VV, X2 = (np.ascontiguousarray(a, dtype=np.float64) for a in (DD, VV, X2))
-    CC, NC, EX = (np.ascontiguousarray(a, dtype=np.uint64) for a in (CC, NC, EX))
-    if DD.ndim != 2 or not (DD.shape == VV.shape == X2.shape == CC.shape == NC.shape == EX.shape):
-        raise ValueError("%s: DD, VV, X2, CC, NC, EX must all have shape [R, B]" % what)
-    return DD, VV, X2, CC, NC, EX
+    EV, EM, PP, PU = _same_shape("save_spectral_noise_csv", *_NOISE_TOTALS, (EV, EM, PP, PU), (_F8, _F8, _U8, _U8))
+    _host("ssh_spectral_noise_save_csv", os.fsencode(path), EV.shape[0], C.c_float(lambda_min), C.c_float(bin_width), EV.ctypes.data, EM.ctypes.data, PP.ctypes.data, PU.ctypes.data)
 
 
 COMPARE_FIGURES = ("mean_diff", "stderr", "z", "chi2", "exceed", "coverage")
@@ -257,12 +241,9 @@ COMPARE_FIGURES = ("mean_diff", "stderr", "z", "chi2", "exceed", "coverage")
 def compare_derive(DD, VV, X2, CC, NC, EX):
     """ssh_compare_derive: a dict of float64 [R, B] arrays from the comparison's six sums (include/ssx.h "Comparing two spectral renders") -- mean_diff = DD / CC,
     stderr = sqrt(VV) / CC, z = DD / sqrt(VV), chi2 = X2 / CC, exceed = EX / CC, coverage = CC / (CC + NC); each NaN where its denominator is 0."""
-    sums = _compare_sums(DD, VV, X2, CC, NC, EX, "compare_derive")
+    sums = _same_shape("compare_derive", *_COMPARE_SUMS, (DD, VV, X2, CC, NC, EX), (_F8,) * 3 + (_U8,) * 3)
     out = [np.zeros_like(sums[0]) for _ in COMPARE_FIGURES]
-    host = _capi.host_lib()
-    rc = host.ssh_compare_derive(sums[0].shape[0], sums[0].shape[1], *[a.ctypes.data for a in sums], *[a.ctypes.data for a in out])
-    if rc != 0:
-        raise SsxError(rc, host.ssh_last_error().decode())
+    _host("ssh_compare_derive", sums[0].shape[0], sums[0].shape[1], *[a.ctypes.data for a in sums], *[a.ctypes.data for a in out])
     return dict(zip(COMPARE_FIGURES, out))
 
 
@@ -276,11 +257,8 @@ def compare_zmap(diff, var):
 def save_compare_csv(path, lambda_min, bin_width, DD, VV, X2, CC, NC, EX):
     """ssh_compare_save_csv (libssx_host.so), the writer the CLI's --compare-output uses: the line
     "region,bin,wavelength,mean_diff,stderr,z,chi2,exceed,comparable,not_comparable", then one line per region and bin."""
-    sums = _compare_sums(DD, VV, X2, CC, NC, EX, "save_compare_csv")
-    host = _capi.host_lib()
-    rc = host.ssh_compare_save_csv(os.fsencode(path), sums[0].shape[0], sums[0].shape[1], C.c_float(lambda_min), C.c_float(bin_width), *[a.ctypes.data for a in sums])
-    if rc != 0:
-        raise SsxError(rc, host.ssh_last_error().decode())
+    sums = _same_shape("save_compare_csv", *_COMPARE_SUMS, (DD, VV, X2, CC, NC, EX), (_F8,) * 3 + (_U8,) * 3)
+    _host("ssh_compare_save_csv", os.fsencode(path), sums[0].shape[0], sums[0].shape[1], C.c_float(lambda_min), C.c_float(bin_width), *[a.ctypes.data for a in sums])
 
 
 def compare_other(other):
@@ -300,10 +278,7 @@ def save_npy(path, array):
     """ssh_save_npy_f32 (libssx_host.so): `array` as a float32 .npy file, the writer the CLI's --spectral-output uses."""
     a = np.ascontiguousarray(array, dtype=np.float32)
     shape = (C.c_uint32 * a.ndim)(*a.shape)
-    host = _capi.host_lib()
-    rc = host.ssh_save_npy_f32(os.fsencode(path), a.ctypes.data, shape, a.ndim)
-    if rc != 0:
-        raise SsxError(rc, host.ssh_last_error().decode())
+    _host("ssh_save_npy_f32", os.fsencode(path), a.ctypes.data, shape, a.ndim)
 
 
 def _spectrum_arg(spec):
@@ -353,12 +328,8 @@ def develop_weights(bins, lambda_min, lambda_step, observer=1931, responses=None
         raise ValueError("develop_weights: gain must have shape [bins]")
     w = np.zeros((n_ch, bins), dtype=np.float32)
     w64 = np.zeros((n_ch, bins), dtype=np.float64)
-    host = _capi.host_lib()
-    rc = host.ssh_develop_weights(os.fsencode(data_dir), int(observer), resp, n_ch, None if flt is None else C.byref(flt), None if g is None else g.ctypes.data,
-                                  _capi.SSH_SPACE_LRGB if space == "lrgb" else _capi.SSH_SPACE_XYZ, int(bins), C.c_float(lambda_min), C.c_float(lambda_step),
-                                  w.ctypes.data, w64.ctypes.data)
-    if rc != 0:
-        raise SsxError(rc, host.ssh_last_error().decode())
+    _host("ssh_develop_weights", os.fsencode(data_dir), int(observer), resp, n_ch, None if flt is None else C.byref(flt), None if g is None else g.ctypes.data,
+          _capi.SSH_SPACE_LRGB if space == "lrgb" else _capi.SSH_SPACE_XYZ, int(bins), C.c_float(lambda_min), C.c_float(lambda_step), w.ctypes.data, w64.ctypes.data)
     return (w, w64) if return_float64 else w
 
 
@@ -368,98 +339,58 @@ def relight_gain(old, new, bins, lambda_min, lambda_step):
     a, ka = _spectrum_arg(old)
     b, kb = _spectrum_arg(new)
     g = np.zeros(bins, dtype=np.float64)
-    host = _capi.host_lib()
-    rc = host.ssh_relight_gain(C.byref(a), C.byref(b), int(bins), C.c_float(lambda_min), C.c_float(lambda_step), g.ctypes.data)
-    if rc != 0:
-        raise SsxError(rc, host.ssh_last_error().decode())
+    _host("ssh_relight_gain", C.byref(a), C.byref(b), int(bins), C.c_float(lambda_min), C.c_float(lambda_step), g.ctypes.data)
     return g
 
 
 def emitter_spectrum(desc):
     """ssh_emitter_spectrum: the index (in desc.spectra) of the emission spectrum all emissive materials share up to a scale; SsxError SSX_ERR_SCENE otherwise."""
     idx = C.c_uint32()
-    host = _capi.host_lib()
-    rc = host.ssh_emitter_spectrum(desc if hasattr(desc, "contents") else C.byref(desc), C.byref(idx))
-    if rc != 0:
-        raise SsxError(rc, host.ssh_last_error().decode())
+    _host("ssh_emitter_spectrum", desc if hasattr(desc, "contents") else C.byref(desc), C.byref(idx))
     return idx.value
+
+
+def _load_checkpoint(fn, path, extra):
+    """The one body of the three loaders below: libssx_host.so's `fn` with the out-pointers of the pixel sums and of `extra` (0, 2 or 3) of bins, counts and Q."""
+    host = _capi.host_lib()
+    info, sinfo = _capi.SsxSumsInfo(), _capi.SsxSpectralInfo()
+    name, text = C.create_string_buffer(256), C.create_string_buffer(4096)
+    ptrs = [C.POINTER(t)() for t in (C.c_double, C.c_double, C.c_double, C.c_uint32, C.c_double)[:2 + extra]]
+    tail = [C.byref(sinfo)] + [C.byref(p) for p in ptrs[2:]] if extra else []
+    _host(fn, os.fsencode(path), C.byref(info), name, len(name), text, len(text), C.byref(ptrs[0]), C.byref(ptrs[1]), *tail)
+    try:
+        H, W, B = info.height, info.width, sinfo.bins
+        shapes = ((H, W, 4), (H, W), (H, W, B), (H, W, B // 4), (H, W, B))
+        arrays = [np.ctypeslib.as_array(p, shape=s).copy() if p else None for p, s in zip(ptrs, shapes)]
+    finally:
+        for p in ptrs:
+            if p:
+                host.ssh_free(p)
+    return (info, arrays[0], arrays[1], name.value.decode(), text.value.decode()) + ((sinfo,) + tuple(arrays[2:]) if extra else ())
 
 
 def load_checkpoint_file(path):
     """ssh_checkpoint_load -> (SsxSumsInfo, sums [H, W, 4], S2 [H, W] or None, scene name, options text)."""
-    host = _capi.host_lib()
-    info = _capi.SsxSumsInfo()
-    name, text = C.create_string_buffer(256), C.create_string_buffer(4096)
-    ps, p2 = C.POINTER(C.c_double)(), C.POINTER(C.c_double)()
-    rc = host.ssh_checkpoint_load(os.fsencode(path), C.byref(info), name, len(name), text, len(text), C.byref(ps), C.byref(p2))
-    if rc != 0:
-        raise SsxError(rc, host.ssh_last_error().decode())
-    try:
-        sums = np.ctypeslib.as_array(ps, shape=(info.height, info.width, 4)).copy()
-        s2 = np.ctypeslib.as_array(p2, shape=(info.height, info.width)).copy() if p2 else None
-    finally:
-        host.ssh_free(ps)
-        if p2:
-            host.ssh_free(p2)
-    return info, sums, s2, name.value.decode(), text.value.decode()
+    return _load_checkpoint("ssh_checkpoint_load", path, 0)
 
 
 def load_checkpoint_file_spectral(path):
     """ssh_checkpoint_load_spectral -> load_checkpoint_file's five values and (SsxSpectralInfo, sums float64 [H, W, B], counts uint32 [H, W, B / 4]) of the
     wavelength bins; from a checkpoint without them (magic SSXCKPT1) the info's bins is 0 and both arrays are None."""
-    host = _capi.host_lib()
-    info, sinfo = _capi.SsxSumsInfo(), _capi.SsxSpectralInfo()
-    name, text = C.create_string_buffer(256), C.create_string_buffer(4096)
-    ps, p2, pb, pn = C.POINTER(C.c_double)(), C.POINTER(C.c_double)(), C.POINTER(C.c_double)(), C.POINTER(C.c_uint32)()
-    rc = host.ssh_checkpoint_load_spectral(os.fsencode(path), C.byref(info), name, len(name), text, len(text), C.byref(ps), C.byref(p2),
-                                           C.byref(sinfo), C.byref(pb), C.byref(pn))
-    if rc != 0:
-        raise SsxError(rc, host.ssh_last_error().decode())
-    try:
-        H, W, B = info.height, info.width, sinfo.bins
-        sums = np.ctypeslib.as_array(ps, shape=(H, W, 4)).copy()
-        s2 = np.ctypeslib.as_array(p2, shape=(H, W)).copy() if p2 else None
-        bins = np.ctypeslib.as_array(pb, shape=(H, W, B)).copy() if pb else None
-        counts = np.ctypeslib.as_array(pn, shape=(H, W, B // 4)).copy() if pn else None
-    finally:
-        for p in (ps, p2, pb, pn):
-            if p:
-                host.ssh_free(p)
-    return info, sums, s2, name.value.decode(), text.value.decode(), sinfo, bins, counts
+    return _load_checkpoint("ssh_checkpoint_load_spectral", path, 2)
 
 
 def load_checkpoint_file_moments(path):
     """ssh_checkpoint_load_moments -> load_checkpoint_file_spectral's eight values and Q float64 [H, W, B], the bins' second moments; None from a checkpoint
     without them (magic SSXCKPT1 or SSXCKPT2)."""
-    host = _capi.host_lib()
-    info, sinfo = _capi.SsxSumsInfo(), _capi.SsxSpectralInfo()
-    name, text = C.create_string_buffer(256), C.create_string_buffer(4096)
-    ps, p2, pb, pn, pq = C.POINTER(C.c_double)(), C.POINTER(C.c_double)(), C.POINTER(C.c_double)(), C.POINTER(C.c_uint32)(), C.POINTER(C.c_double)()
-    rc = host.ssh_checkpoint_load_moments(os.fsencode(path), C.byref(info), name, len(name), text, len(text), C.byref(ps), C.byref(p2),
-                                          C.byref(sinfo), C.byref(pb), C.byref(pn), C.byref(pq))
-    if rc != 0:
-        raise SsxError(rc, host.ssh_last_error().decode())
-    try:
-        H, W, B = info.height, info.width, sinfo.bins
-        sums = np.ctypeslib.as_array(ps, shape=(H, W, 4)).copy()
-        s2 = np.ctypeslib.as_array(p2, shape=(H, W)).copy() if p2 else None
-        bins = np.ctypeslib.as_array(pb, shape=(H, W, B)).copy() if pb else None
-        counts = np.ctypeslib.as_array(pn, shape=(H, W, B // 4)).copy() if pn else None
-        q = np.ctypeslib.as_array(pq, shape=(H, W, B)).copy() if pq else None
-    finally:
-        for p in (ps, p2, pb, pn, pq):
-            if p:
-                host.ssh_free(p)
-    return info, sums, s2, name.value.decode(), text.value.decode(), sinfo, bins, counts, q
+    return _load_checkpoint("ssh_checkpoint_load_moments", path, 3)
 
 
 def merge_moments(dst_q, src_q, src_info):
     """ssh_moments_merge: merge_sums' rule for the bins' second moments -- Q float64 [H, W, B] of the pixels src_info's exporter owns (an SsxSumsInfo: export_sums'
     of the same context), bit for bit."""
     assert dst_q.dtype == np.float64 and dst_q.flags.c_contiguous and src_q.dtype == np.float64 and src_q.flags.c_contiguous and dst_q.shape == src_q.shape
-    rc = _capi.host_lib().ssh_moments_merge(dst_q.ctypes.data, src_q.ctypes.data, src_q.shape[2], C.byref(src_info))
-    if rc != 0:
-        raise SsxError(rc, _capi.host_lib().ssh_last_error().decode())
+    _host("ssh_moments_merge", dst_q.ctypes.data, src_q.ctypes.data, src_q.shape[2], C.byref(src_info))
 
 
 def merge_spectral(dst_sums, dst_counts, src_sums, src_counts, src_info):
@@ -468,18 +399,14 @@ def merge_spectral(dst_sums, dst_counts, src_sums, src_counts, src_info):
     assert dst_sums.dtype == np.float64 and dst_sums.flags.c_contiguous and src_sums.dtype == np.float64 and src_sums.flags.c_contiguous
     assert dst_counts.dtype == np.uint32 and dst_counts.flags.c_contiguous and src_counts.dtype == np.uint32 and src_counts.flags.c_contiguous
     assert dst_sums.shape == src_sums.shape and dst_counts.shape == src_counts.shape and src_sums.shape[2] == 4 * src_counts.shape[2]
-    rc = _capi.host_lib().ssh_spectral_merge(dst_sums.ctypes.data, dst_counts.ctypes.data, src_sums.ctypes.data, src_counts.ctypes.data, src_sums.shape[2], C.byref(src_info))
-    if rc != 0:
-        raise SsxError(rc, _capi.host_lib().ssh_last_error().decode())
+    _host("ssh_spectral_merge", dst_sums.ctypes.data, dst_counts.ctypes.data, src_sums.ctypes.data, src_counts.ctypes.data, src_sums.shape[2], C.byref(src_info))
 
 
 def merge_sums(dst, dst_s2, src, src_s2, src_info):
     """ssh_sums_merge: dst's pixels that src_info's exporter owns <- src's, bit for bit (by ownership mask, not by adding)."""
     assert dst.dtype == np.float64 and dst.flags.c_contiguous and src.dtype == np.float64 and src.flags.c_contiguous
-    rc = _capi.host_lib().ssh_sums_merge(dst.ctypes.data, None if dst_s2 is None or src_s2 is None else dst_s2.ctypes.data, src.ctypes.data,
-                                         None if dst_s2 is None or src_s2 is None else src_s2.ctypes.data, C.byref(src_info))
-    if rc != 0:
-        raise SsxError(rc, _capi.host_lib().ssh_last_error().decode())
+    _host("ssh_sums_merge", dst.ctypes.data, None if dst_s2 is None or src_s2 is None else dst_s2.ctypes.data, src.ctypes.data,
+          None if dst_s2 is None or src_s2 is None else src_s2.ctypes.data, C.byref(src_info))
 
 
 class Renderer:
@@ -501,6 +428,7 @@ class Renderer:
         W, H = options.res
         self.xyza = np.zeros((H, W, 4), dtype=np.float32)
         self.framebuffer = np.zeros((H, W, 4), dtype=np.float32)
+        self._spectral_bins, self._spectral_moments = 0, False   # what set_spectral_bins / set_spectral_moments last set
 
     def _check(self, rc):
         if rc != 0:
@@ -595,7 +523,7 @@ class Renderer:
 
     def holds_spectral(self):
         """Whether the context holds valid wavelength bins of exactly the samples behind its sums (what export_spectral and save_checkpoint need)."""
-        if not getattr(self, "_spectral_bins", 0):
+        if not self._spectral_bins:
             return False
         return self._lib.ssx_spectral_read(self._ctx, C.byref(_capi.SsxSpectralInfo()), None, None, None) == 0
 
@@ -617,7 +545,7 @@ class Renderer:
 
     def holds_moments(self):
         """Whether the context holds valid second moments of exactly the samples behind its bins (what export_moments needs, and save_checkpoint to keep them)."""
-        if not getattr(self, "_spectral_bins", 0):
+        if not self._spectral_bins:
             return False
         return self._lib.ssx_spectral_variance(self._ctx, C.byref(_capi.SsxSpectralInfo()), None, None) == 0
 
@@ -647,12 +575,9 @@ class Renderer:
         o = self.options
         text = "observer=%d\ntexture=%s\nlight_scale=%r\nuplift=%s\nrender_mode=%s\nexplicit_light_sampling=%d\n" % (
             o.observer, o.texture if isinstance(o.texture, str) else "", o.light_scale, o.uplift, o.render_mode, int(o.explicit_light_sampling))
-        host = _capi.host_lib()
-        rc = host.ssh_checkpoint_save_moments(os.fsencode(path), C.byref(info), o.scene_name.encode(), text.encode(), sums.ctypes.data, None if s2 is None else s2.ctypes.data,
-                                              None if sinfo is None else C.byref(sinfo), None if bins is None else bins.ctypes.data,
-                                              None if counts is None else counts.ctypes.data, None if q is None else q.ctypes.data)
-        if rc != 0:
-            raise SsxError(rc, host.ssh_last_error().decode())
+        _host("ssh_checkpoint_save_moments", os.fsencode(path), C.byref(info), o.scene_name.encode(), text.encode(), sums.ctypes.data, None if s2 is None else s2.ctypes.data,
+              None if sinfo is None else C.byref(sinfo), None if bins is None else bins.ctypes.data,
+              None if counts is None else counts.ctypes.data, None if q is None else q.ctypes.data)
 
     def load_checkpoint(self, path):
         """Reads a checkpoint and imports it (SsxError SSX_ERR_DATA for a damaged file, SSX_ERR_ARG with the library's reason for one
@@ -661,8 +586,8 @@ class Renderer:
         set_spectral_moments(True) in force and the bins taken up: Q is taken up too (import_moments); self.moments_resumed says whether."""
         info, sums, s2, _, _, sinfo, bins, counts, q = load_checkpoint_file_moments(path)
         self.import_sums(info, sums, s2)
-        self.spectral_resumed = bool(sinfo.bins) and sinfo.bins == getattr(self, "_spectral_bins", 0)
-        self.moments_resumed = self.spectral_resumed and q is not None and getattr(self, "_spectral_moments", False)
+        self.spectral_resumed = bool(sinfo.bins) and sinfo.bins == self._spectral_bins
+        self.moments_resumed = self.spectral_resumed and q is not None and self._spectral_moments
         if self.spectral_resumed:
             self.import_spectral(sinfo, bins, counts)
         if self.moments_resumed:
@@ -742,10 +667,13 @@ class Renderer:
         return info, var, Q
 
     @staticmethod
-    def _probe_labels(labels, shape):
+    def _regions(labels, shape, regions):
+        """(labels uint8 of `shape`, R): `regions`, or for None the largest label + 1"""
         labels = np.ascontiguousarray(labels, dtype=np.uint8)
         if labels.shape != shape:
             raise ValueError("probe: labels must have shape [H, W] = %r" % (shape,))
+        if regions is not None:
+            return labels, int(regions)
         named = labels[labels != PROBE_NO_REGION]
         return labels, (int(named.max()) + 1 if named.size else 1)
 
@@ -753,9 +681,8 @@ class Renderer:
         """ssx_spectral_probe -> (SS float64, NN uint64, VV float64, UU uint64), each [R, B]: the four sums of include/ssx.h over the pixels of every region of
         labels (uint8 [H, W], row 0 = bottom: 0..R-1 a region, 255 none; labels_from_rects, labels_from_prim).  regions None: the largest label + 1."""
         W, H = self.options.res
-        labels, R = self._probe_labels(labels, (H, W))
-        R = R if regions is None else int(regions)
-        B = getattr(self, "_spectral_bins", 0) or 4
+        labels, R = self._regions(labels, (H, W), regions)
+        B = self._spectral_bins or 4
         SS, VV = np.zeros((R, B), dtype=np.float64), np.zeros((R, B), dtype=np.float64)
         NN, UU = np.zeros((R, B), dtype=np.uint64), np.zeros((R, B), dtype=np.uint64)
         self._check(self._lib.ssx_spectral_probe(self._ctx, labels.ctypes.data, R, SS.ctypes.data, NN.ctypes.data, VV.ctypes.data, UU.ctypes.data))
@@ -776,8 +703,7 @@ class Renderer:
         if sums.ndim != 3 or q.shape != sums.shape or counts.shape != sums.shape[:2] + (sums.shape[2] // 4,) or sums.shape[2] % 4:
             raise ValueError("probe_arrays: sums and q must have shape [H, W, B], counts [H, W, B / 4]")
         H, W, B = sums.shape
-        labels, R = self._probe_labels(labels, (H, W))
-        R = R if regions is None else int(regions)
+        labels, R = self._regions(labels, (H, W), regions)
         SS, VV = np.zeros((R, B), dtype=np.float64), np.zeros((R, B), dtype=np.float64)
         NN, UU = np.zeros((R, B), dtype=np.uint64), np.zeros((R, B), dtype=np.uint64)
         self._check(self._lib.ssx_probe_arrays(self._ctx, W, H, B, sums.ctypes.data, q.ctypes.data, counts.ctypes.data, labels.ctypes.data, R,
@@ -798,9 +724,8 @@ class Renderer:
         N, Q); labels as probe_raw takes them; threshold: the z beyond which a comparable cell counts into EX (the library takes its square)."""
         info, S, Q, N = compare_other(other)
         W, H = self.options.res
-        labels, R = self._probe_labels(labels, (H, W))
-        R = R if regions is None else int(regions)
-        B = getattr(self, "_spectral_bins", 0) or 4
+        labels, R = self._regions(labels, (H, W), regions)
+        B = self._spectral_bins or 4
         sums, diff, var = self._compare_outputs(R, (H, W, B), maps)
         self._check(self._lib.ssx_spectral_compare(self._ctx, C.byref(info), S.ctypes.data, Q.ctypes.data, N.ctypes.data, labels.ctypes.data, R, float(threshold) * float(threshold),
                                                    *[a.ctypes.data for a in sums], None if diff is None else diff.ctypes.data, None if var is None else var.ctypes.data))
@@ -823,8 +748,7 @@ class Renderer:
         if SA.ndim != 3 or SA.shape[2] % 4 or not (QA.shape == SB.shape == QB.shape == SA.shape) or not (NA.shape == NB.shape == SA.shape[:2] + (SA.shape[2] // 4,)):
             raise ValueError("compare_arrays: S and Q of both sets must have shape [H, W, B], N [H, W, B / 4]")
         H, W, B = SA.shape
-        labels, R = self._probe_labels(labels, (H, W))
-        R = R if regions is None else int(regions)
+        labels, R = self._regions(labels, (H, W), regions)
         sums, diff, var = self._compare_outputs(R, (H, W, B), maps)
         self._check(self._lib.ssx_spectral_compare_arrays(self._ctx, W, H, B, SA.ctypes.data, QA.ctypes.data, NA.ctypes.data, SB.ctypes.data, QB.ctypes.data, NB.ctypes.data,
                                                           labels.ctypes.data, R, float(threshold) * float(threshold) if t2 is None else float(t2),
@@ -849,7 +773,7 @@ class Renderer:
         in) or None for every pixel."""
         W, H = self.options.res
         mask = self._noise_mask(mask)
-        B = getattr(self, "_spectral_bins", 0) or 4
+        B = self._spectral_bins or 4
         tiles = ((W + 7) // 8) * ((H + 7) // 8)
         EV, EM, PP, PU = np.zeros(B), np.zeros(B), np.zeros(B, dtype=np.uint64), np.zeros(B, dtype=np.uint64)
         tEV, tEM = np.zeros((tiles, B)), np.zeros((tiles, B))
@@ -867,10 +791,7 @@ class Renderer:
 
     def spectral_noise_reduce(self, tEV, tEM, tPP, tPU):
         """ssx_spectral_noise_reduce: the totals of uploaded tile partials [tiles, B] (e.g. several contexts' partials merged by ownership) -> (EV, EM, PP, PU)."""
-        tEV, tEM = np.ascontiguousarray(tEV, dtype=np.float64), np.ascontiguousarray(tEM, dtype=np.float64)
-        tPP, tPU = np.ascontiguousarray(tPP, dtype=np.uint32), np.ascontiguousarray(tPU, dtype=np.uint32)
-        if tEV.ndim != 2 or not (tEV.shape == tEM.shape == tPP.shape == tPU.shape):
-            raise ValueError("spectral_noise_reduce: the four partials must all have shape [tiles, B]")
+        tEV, tEM, tPP, tPU = _same_shape("spectral_noise_reduce", "the four partials must all have shape [tiles, B]", 2, (tEV, tEM, tPP, tPU), (_F8, _F8, np.uint32, np.uint32))
         tiles, B = tEV.shape
         EV, EM, PP, PU = np.zeros(B), np.zeros(B), np.zeros(B, dtype=np.uint64), np.zeros(B, dtype=np.uint64)
         self._check(self._lib.ssx_spectral_noise_reduce(self._ctx, tiles, B, tEV.ctypes.data, tEM.ctypes.data, tPP.ctypes.data, tPU.ctypes.data,
@@ -1009,7 +930,7 @@ class Renderer:
         demodulate (True, or a dict: _demod_args): ssx_denoise_spectral_demod -- bins, image and variance are divided by the first-hit albedo before the filter
         and multiplied by it afterwards; sigma_a is ignored.  sigma_l None: 1.0, or the demodulated mode's own default."""
         W, H = self.options.res
-        B = getattr(self, "_spectral_bins", 0)                                     # what set_spectral_bins set; 0: off, and ssx_denoise_spectral says so
+        B = self._spectral_bins                                     # what set_spectral_bins set; 0: off, and ssx_denoise_spectral says so
         mean = np.zeros((H, W, B), dtype=np.float32)
         out = np.zeros((H, W, 4), dtype=np.float32) if return_image else None
         var = np.zeros((H, W), dtype=np.float32) if return_image else None
@@ -1041,7 +962,7 @@ class Renderer:
             denoise = {}
         p = None if denoise is None else self._denoise_params(denoise.get("levels", 5), denoise.get("sigma_l", _capi.SSX_DEMOD_DEFAULT_SIGMA_L if demodulate else 1.0),
                                                               denoise.get("sigma_a", 0.1))
-        if getattr(self, "_spectral_bins", 0) not in (0, w.shape[1]):
+        if self._spectral_bins not in (0, w.shape[1]):
             raise ValueError("develop: weights for %d bins, the context holds %d" % (w.shape[1], self._spectral_bins))
         if demodulate:
             dm, wx = self._demod_args(demodulate, w.shape[1])
@@ -1170,9 +1091,7 @@ class Renderer:
 
     def save(self, path):
         fb = np.ascontiguousarray(self.framebuffer, dtype=np.float32)
-        rc = _capi.host_lib().ssh_save_image(path.encode(), fb.ctypes.data, fb.shape[1], fb.shape[0])
-        if rc != 0:
-            raise SsxError(rc, _capi.host_lib().ssh_last_error().decode())
+        _host("ssh_save_image", path.encode(), fb.ctypes.data, fb.shape[1], fb.shape[0])
 
     def close(self):
         if self._ctx:
