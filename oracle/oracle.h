@@ -247,6 +247,8 @@ orc_v3 orc_get_rotated_to(orc_v3 dir, orc_v3 normal);                      /* ma
 int orc_tri_intersect(const orc_tri*, const orc_ray*, orc_hit*, int prim_id, orc_stats*); /* geometry.cpp:12-101 */
 int orc_scene_intersect(const orc_scene*, const orc_ray*, orc_hit*, int ignore, orc_stats*); /* scene.cpp:433-445 */
 void orc_lrgb_to_specrefl(const orc_color*, const float lrgb[3], float lambda_0, float out[4]); /* color.cpp:167-173 */
+/* the albedo of primitive `quad`'s material at st, at the four hero wavelengths (material.cpp:45-97,120-143); -1: no such primitive */
+int orc_quad_albedo(const orc_color*, const orc_scene*, int quad, const float st[2], float lambda_0, float out[4]);
 void orc_specradflux_to_ciexyz_hero(const orc_color*, const float flux[4], float lambda_0, float out[3]); /* color.hpp:115-139 */
 void orc_srgb_to_lrgb(const float srgb[3], float lrgb[3]);    /* color.hpp:91-97 */
 void orc_lrgb_to_srgb(const float lrgb[3], float srgb[3]);    /* color.hpp:84-90 */

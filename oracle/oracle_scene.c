@@ -190,6 +190,14 @@ ORC_VIRTUAL void orc_material_albedo(const orc_color* cd, const orc_scene* sc, c
 	}
 }
 
+/* unit-level entry (see oracle.h): orc_material_albedo of the primitive's material, as evaluate_bsdf / interact_bsdf call it */
+int orc_quad_albedo(const orc_color* cd, const orc_scene* sc, int quad, const float st[2], float lambda_0, float out[4]) {
+	if (quad < 0 || quad >= sc->n_prims) return -1;
+	orc_v2 st2; st2.x = st[0]; st2.y = st[1];
+	orc_material_albedo(cd, sc, &sc->materials[sc->prims[quad].material], st2, lambda_0, out, NULL);
+	return 0;
+}
+
 /* material.cpp:100-106 */
 static int material_is_emissive(int rgb_mode, const orc_material* m) {
 	if (rgb_mode) return m->rgb_emission[0] > 0.0f || m->rgb_emission[1] > 0.0f || m->rgb_emission[2] > 0.0f;

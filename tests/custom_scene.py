@@ -95,8 +95,8 @@ class CustomScene:
         self.cam_dir = (f / np.linalg.norm(f)).astype(np.float32)   # camera.dir (both sides receive these three floats)
 
     # ---- the two sides -------------------------------------------------------------------------
-    def oracle(self):
-        """ol.Oracle over orc_scene_create_custom of this description."""
+    def oracle(self, **uplift):
+        """ol.Oracle over orc_scene_create_custom of this description; `uplift`: its jh= or meng= (default: "ours")."""
         def make(lib, color):
             keep = []
             sp = (ol.SpectrumIn * len(self.spectra))()
@@ -127,7 +127,7 @@ class CustomScene:
             if sc:
                 lib.orc_scene_set_camera_dir(sc, (C.c_float * 3)(*[float(x) for x in self.cam_dir]))
             return sc
-        return ol.Oracle(observer=self.observer, custom=make)
+        return ol.Oracle(observer=self.observer, custom=make, **uplift)
 
     def desc(self, orc):
         """ssx_scene_desc of this description (normals and light list as the oracle `orc` derived them)."""

@@ -168,6 +168,7 @@ def load(variant=""):
     lib.orc_scene_intersect.restype = C.c_int
     lib.orc_scene_intersect.argtypes = [vp, C.POINTER(Ray), C.POINTER(Hit), C.c_int, vp]
     lib.orc_lrgb_to_specrefl.argtypes = [vp, f32p, C.c_float, f32p]
+    lib.orc_quad_albedo.argtypes = [vp, vp, C.c_int, f32p, C.c_float, f32p]
     lib.orc_specradflux_to_ciexyz_hero.argtypes = [vp, f32p, C.c_float, f32p]
     lib.orc_srgb_to_lrgb.argtypes = [f32p, f32p]
     lib.orc_lrgb_to_srgb.argtypes = [f32p, f32p]
@@ -294,6 +295,22 @@ class Oracle:
                     xyza[j - j0, i - i0, k] = out[:]
                     state[j - j0, i - i0, k] = rng.state
         return xyza, state, st
+
+    def albedo(self, quads, st, lambda_0):
+        """orc_quad_albedo per item: quads [n] int, st [n, 2] and lambda_0 [n] float32 -> [n, 4] float32."""
+        quads = np.asarray(quads, dtype=np.int64)
+        st = np.ascontiguousarray(st, dtype=np.float32)
+        lambda_0 = np.asarray(lambda_0, dtype=np.float32)
+        assert st.shape == (len(quads), 2) and lambda_0.shape == (len(quads),)
+        out = np.zeros((len(quads), 4), dtype=np.float32)
+        st2, o4 = (C.c_float * 2)(), (C.c_float * 4)()
+        o4_view = np.frombuffer(o4, dtype=np.float32)
+        for k, (q, (s, t), l0) in enumerate(zip(quads.tolist(), st.tolist(), lambda_0.tolist())):   # (float32 -> Python float -> c_float is exact)
+            st2[0], st2[1] = s, t
+            if self.lib.orc_quad_albedo(self.color, self.scene, q, st2, l0, o4) != 0:
+                raise IndexError("orc_quad_albedo: no primitive %d" % q)
+            out[k] = o4_view
+        return out
 
     def to_srgba(self, xyza):
         xyza = np.ascontiguousarray(xyza, dtype=np.float32)

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as ol
+from unit_cases import same_or_both_nan
 from simple_spectral_amd import Options, Renderer, SsxError, _capi
 from simple_spectral_amd import dist as sdist
 
@@ -224,12 +225,6 @@ def test_error_codes():
     bad = _capi.SsxSceneDesc(); bad.struct_size = 12
     assert lib.ssx_upload_scene(ctx, C.byref(bad)) == _capi.SSX_ERR_ARG
     lib.ssx_destroy(ctx)
-
-
-def same_or_both_nan(a, b):
-    """Bit equality, except that NaN matches NaN of any payload (black texels make the reference's
-    Jakob-Hanika path divide by zero, rgb2spec.c:88-91, so both sides hold NaN there)."""
-    return ((bits(a) == bits(b)) | (np.isnan(a) & np.isnan(b))).all()
 
 
 @pytest.mark.parametrize("scene", ["cornell-srgb", "plane-srgb"])

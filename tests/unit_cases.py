@@ -18,6 +18,12 @@ def u2f(a):
     return np.ascontiguousarray(a, dtype=np.uint32).view(np.float32)
 
 
+def same_or_both_nan(a, b):
+    """Bit equality, except that NaN matches NaN of any payload (black texels make the reference's
+    Jakob-Hanika path divide by zero, rgb2spec.c:88-91, so both sides hold NaN there)."""
+    return ((f2u(a) == f2u(b)) | (np.isnan(a) & np.isnan(b))).all()
+
+
 def rng_words(n, seed):
     """n PCG32 streams {state lo, state hi, inc lo, inc hi} (inc odd)."""
     g = np.random.default_rng(seed)
