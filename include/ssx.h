@@ -33,7 +33,7 @@ extern "C" {
  *      ssx_jit_counters, ssx_sums_info, ssx_rccl_groups_made, ssx_done_tiles and ssx_render_params.tile_major and tile_skew (the
  *      struct grew by 8 bytes) are new.  Added since without a change of existing entry points or structures (same version): ssx_units_info,
  *      ssx_rccl_probe (round 6); ssx_render_params.libm, appended (a caller with the struct_size before it gets SSX_LIBM_BUILD); the progressive
- *      rendering, spectral output, denoising, develop and demodulated-denoising entry points below. */
+ *      rendering, spectral output, denoising, develop and demodulated-denoising entry points below; ssx_debug_tile_mask and SSX_DBG_TRACE_MASKED. */
 #define SSX_ABI_VERSION 2
 
 enum {
@@ -846,7 +846,12 @@ enum {
 	SSX_DBG_RAND_1F = 10,     /* in: rng[4]                             out: rand_1f, rng state lo, hi (src/util/random.hpp:68-70) */
 	/* libm = glibc-2.35 (ssx_render_params.libm): the units the _glibc kernels inline, same inputs and outputs as the op above them */
 	SSX_DBG_GLIBC_MATH = 11,  /* in: x                                  out: sinf, cosf, acosf, sincosf.s, sincosf.c (include/ssx_glibc_math.h) */
-	SSX_DBG_SPHTRI_GLIBC = 12, SSX_DBG_ARVO_GLIBC = 13, SSX_DBG_SAMPLE_LIGHT_GLIBC = 14, SSX_DBG_COSHEMI_GLIBC = 15
+	SSX_DBG_SPHTRI_GLIBC = 12, SSX_DBG_ARVO_GLIBC = 13, SSX_DBG_SAMPLE_LIGHT_GLIBC = 14, SSX_DBG_COSHEMI_GLIBC = 15,
+	/* SSX_DBG_TRACE restricted to a set of primitives, as ssx_generate_kernel traces a tile's camera rays (default libm's kernel).  mask[4]: bit q & 31 of word
+	 * q >> 5 = primitive q may be hit; a primitive whose bit is clear is left out.  The device function reads the mask ONCE PER WAVE (through the first lane:
+	 * in a render it is the tile's), so the items are taken in blocks of 64 -- items 64 b .. 64 b + 63 -- and every item of a block must carry the same four
+	 * words: the caller pads its last block, e.g. with copies of its final row.  Bits at or above the number of primitives are ignored. */
+	SSX_DBG_TRACE_MASKED = 16 /* in: orig[3], dir[3], ignore quad (int), mask[4]   out: as SSX_DBG_TRACE */
 };
 /* rng[4] = PCG32 {state lo, state hi, inc lo, inc hi} */
 /* ssx_debug_sweep: device-side comparison of a cheaper device function with the function that DEFINES the
@@ -891,6 +896,11 @@ int ssx_debug_samples(ssx_ctx* ctx, const ssx_render_params* params, float* xyza
 /* The same launch with spectral output on (ssx_set_spectral_bins; off: SSX_ERR_STATE): flux [j][i][k][4] = every sample's hero flux as handed to
  * flux_to_xyz, lambda_0 [j][i][k] = its first hero wavelength.  Either may be NULL. */
 int ssx_debug_sample_flux(ssx_ctx* ctx, const ssx_render_params* params, float* flux, float* lambda_0);
+/* The per-tile primitive masks the generate kernel's trace is restricted to where camera rays are pre-traced (ssx_calibration_info): exactly
+ * ssx_tile_mask_kernel, launched for the plan a render with `params` gets (tile_first / tile_stride / tile_skew included; spp is not looked at),
+ * whichever way the uploaded scene traces its camera rays.  out: 4 words per tile slot of the device (slot s = tile tile_first + s * tile_stride of
+ * the skewed tile list), word g = primitives 32 g .. 32 g + 31.  Touches neither the sample arrays nor the sums: the continuable state stays. */
+int ssx_debug_tile_mask(ssx_ctx* ctx, const ssx_render_params* params, uint32_t* out);
 
 #ifdef __cplusplus
 }

@@ -122,7 +122,8 @@ HIP_SYMBOLS = ["ssx_create", "ssx_destroy", "ssx_upload_scene", "ssx_render_star
                "ssx_set_spectral_moments", "ssx_spectral_variance", "ssx_spectral_probe", "ssx_probe_arrays",
                "ssx_spectral_noise", "ssx_spectral_noise_reduce",
                "ssx_spectral_moments_import",
-               "ssx_spectral_compare", "ssx_spectral_compare_arrays"]
+               "ssx_spectral_compare", "ssx_spectral_compare_arrays",
+               "ssx_debug_tile_mask"]
 (SSX_SWEEP_RCP, SSX_SWEEP_SQRT, SSX_SWEEP_INVERSESQRT, SSX_SWEEP_SIN, SSX_SWEEP_COS, SSX_SWEEP_ACOS, SSX_SWEEP_DIV_PI,
  SSX_SWEEP_RCP64, SSX_SWEEP_DIV_PAIRS, SSX_SWEEP_ACOS_SIN, SSX_SWEEP_SIN_PROOF, SSX_SWEEP_COS_PROOF, SSX_SWEEP_ACOS_PROOF) = range(1, 14)
 # ssx_debug_eval ops (include/ssx.h)
@@ -131,6 +132,7 @@ HIP_SYMBOLS = ["ssx_create", "ssx_destroy", "ssx_upload_scene", "ssx_render_star
 # ... and of libm = glibc-2.35 (the _glibc kernels' units), with the sweeps of include/ssx_glibc_math.h on the device
 (SSX_DBG_GLIBC_MATH, SSX_DBG_SPHTRI_GLIBC, SSX_DBG_ARVO_GLIBC, SSX_DBG_SAMPLE_LIGHT_GLIBC, SSX_DBG_COSHEMI_GLIBC) = range(11, 16)
 (SSX_SWEEP_GLIBC_SIN, SSX_SWEEP_GLIBC_COS, SSX_SWEEP_GLIBC_ACOS, SSX_SWEEP_GLIBC_COS_LDS) = range(14, 18)
+SSX_DBG_TRACE_MASKED = 16   # SSX_DBG_TRACE's row + mask[4]: the masked pass 1 of the generate kernel's trace (rows in blocks of 64 sharing one mask)
 HOST_SYMBOLS = ["ssh_scene_create", "ssh_scene_create_ex", "ssh_scene_destroy", "ssh_scene_desc", "ssh_xyza_to_srgba", "ssh_save_image",
                 "ssh_load_png_rgb8", "ssh_free", "ssh_color_values", "ssh_last_error", "ssh_checkpoint_save", "ssh_checkpoint_load", "ssh_sums_merge", "ssh_save_npy_f32",
                 "ssh_develop_weights", "ssh_relight_gain", "ssh_emitter_spectrum",
@@ -377,6 +379,8 @@ def hip_lib():
             lib.ssx_spectral_compare_arrays.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32] + [vp] * 7 + [C.c_uint32, C.c_double] + [vp] * 8
         if not override or hasattr(lib, "ssx_spectral_moments_import"):  # the second moments through checkpoint and resume
             lib.ssx_spectral_moments_import.argtypes = [vp, C.POINTER(SsxSpectralInfo), vp]
+        if not override or hasattr(lib, "ssx_debug_tile_mask"):  # the camera-ray pre-trace's tile masks, read back
+            lib.ssx_debug_tile_mask.argtypes = [vp, C.POINTER(SsxRenderParams), vp]
         lib.ssx_kernel_variant.argtypes = [vp]
         lib.ssx_kernel_name.argtypes = [vp]
         lib.ssx_kernel_name.restype = C.c_char_p

@@ -1276,7 +1276,8 @@ int ssx_debug_eval(ssx_ctx* ctx, uint32_t op, const void* in, uint32_t in_words,
 	SsxKernelArgs a{};
 	a.blob = ctx->d_blob.as<uint32_t>(); a.blob_words = ctx->blob_words; a.rgb_mode = ctx->rgb_mode ? 1u : 0u;
 	const size_t lds = staged_blob_lds(ctx->blob_words);
-	const auto kernel = op >= SSX_DBG_GLIBC_MATH ? ssx_debug_eval_glibc_kernel : ssx_debug_eval_kernel; // the units of libm = glibc-2.35: a kernel that stages the _glibc kernels' LDS table
+	if (op == SSX_DBG_TRACE_MASKED && in_words < 11u) return fail(ctx, SSX_ERR_ARG, "SSX_DBG_TRACE_MASKED: a row is orig[3], dir[3], ignore, mask[4]");
+	const auto kernel = op >= SSX_DBG_GLIBC_MATH && op <= SSX_DBG_COSHEMI_GLIBC ? ssx_debug_eval_glibc_kernel : ssx_debug_eval_kernel; // the units of libm = glibc-2.35: a kernel that stages the _glibc kernels' LDS table
 	hipLaunchKernelGGL(kernel, dim3((n + 255u) / 256u), dim3(256), lds, ctx->stream, a, op, d_in.as<uint32_t>(), in_words, d_out.as<uint32_t>(), out_words, n);
 	SSX_HIP(ctx, hipGetLastError());
 	SSX_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1337,6 +1338,31 @@ int ssx_debug_samples(ssx_ctx* ctx, const ssx_render_params* p_in, float* xyza, 
 			if (levels) levels[o] = (st[r].y >> 2) & 0xFu;
 		}
 	}
+	return SSX_OK;
+}
+
+// The tile masks of a render with these parameters: the launch plan as a render builds it (make_plan), ssx_tile_mask_kernel as enqueue_generate
+// launches it, into a buffer of the call's own -- the context's sample arrays, sums and continuable state are not touched, and the scene need
+// not be one whose camera rays are pre-traced.
+int ssx_debug_tile_mask(ssx_ctx* ctx, const ssx_render_params* p_in, uint32_t* out) {
+	if (!ctx || !out) return SSX_ERR_ARG;
+	ssx_render_params pp;
+	int rc = begin_render(ctx, p_in, &pp, "render in progress");
+	if (rc) return rc;
+	SSX_HIP(ctx, hipSetDevice(ctx->device));
+	if ((rc = wait_device_pending(ctx))) return rc;
+	const LaunchPlan pl = make_plan(ctx, &pp);
+	SsxKernelArgs ga = pl.args;
+	if (ga.my_tiles == 0u) return SSX_OK;
+	ga.blob_words = ctx->blob_words;
+	const size_t bytes = (size_t)ga.my_tiles * 4u * sizeof(uint32_t);
+	DeviceBuffer d_mask;
+	if (d_mask.reserve(bytes) != hipSuccess) { (void)hipGetLastError(); return fail(ctx, SSX_ERR_DEVICE, "out of device memory (ssx_debug_tile_mask)"); }
+	ga.tile_mask = d_mask.as<uint32_t>();
+	hipLaunchKernelGGL(ssx_tile_mask_kernel, dim3((ga.my_tiles + 3u) / 4u), dim3(256), 0, ctx->stream, ga);
+	SSX_HIP(ctx, hipGetLastError());
+	SSX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	SSX_HIP(ctx, hipMemcpy(out, d_mask.ptr, bytes, hipMemcpyDeviceToHost));
 	return SSX_OK;
 }
 

@@ -169,6 +169,18 @@ extern "C" __global__ void __launch_bounds__(256) ssx_debug_eval_kernel(SsxKerne
 		if (h.tri >= 0) { float sx, sy; hit_st(L.quad((uint32_t)h.tri >> 1), (uint32_t)h.tri & 1u, h, sx, sy); o[3] = u(sx); o[4] = u(sy); }
 		break;
 	}
+	case SSX_DBG_TRACE_MASKED: { // in: SSX_DBG_TRACE's row, mask[4] -> as SSX_DBG_TRACE
+		// The masked pass 1 of ssx_generate_kernel's trace (there the mask is the tile's, ssx_tile_mask_kernel).  trace() reads the mask
+		// through readfirstlane -- it is wave-uniform by contract -- so the wave works with the four words of its FIRST lane's row: the
+		// caller lays its rows out in blocks of 64 that share one mask (include/ssx.h), and the lanes past the end redo item n - 1.
+		HitInfo h;
+		trace<0>(L, mk(f(x[0]), f(x[1]), f(x[2])), mk(f(x[3]), f(x[4]), f(x[5])), (int)x[6], true, h, 0, x + 7);
+		o[0] = h.tri < 0 ? 0xFFFFFFFFu : (uint32_t)h.tri >> 1;
+		o[1] = h.tri < 0 ? 0u : (uint32_t)h.tri & 1u;
+		o[2] = u(h.dist);
+		if (h.tri >= 0) { float sx, sy; hit_st(L.quad((uint32_t)h.tri >> 1), (uint32_t)h.tri & 1u, h, sx, sy); o[3] = u(sx); o[4] = u(sy); }
+		break;
+	}
 	case SSX_DBG_RAND_CHOICE: { // in: rng[4], n -> choice, rng state
 		Rng r = load_rng(x);
 		o[0] = rand_choice(r, x[4]); o[1] = (uint32_t)r.state; o[2] = (uint32_t)(r.state >> 32);

@@ -1040,6 +1040,16 @@ class Renderer:
         self._check(self._lib.ssx_debug_samples(self._ctx, C.byref(p), xyza.ctypes.data, state.ctypes.data, levels.ctypes.data))
         return xyza, state, levels
 
+    def debug_tile_mask(self, **over):
+        """ssx_debug_tile_mask: uint32 [slots, 4], the primitives ssx_tile_mask_kernel leaves to the camera rays of each of the device's tile slots (slot s =
+        tile tile_first + s * tile_stride of the skewed tile list; bit q & 31 of word q >> 5 = primitive q), for a render with these options."""
+        p = self.params(**over)
+        tx, ty = (p.width + 7) // 8, (p.height + 7) // 8
+        slots = (tx * ty - p.tile_first + p.tile_stride - 1) // p.tile_stride if tx * ty > p.tile_first else 0
+        out = np.zeros((slots, 4), dtype=np.uint32)
+        self._check(self._lib.ssx_debug_tile_mask(self._ctx, C.byref(p), out.ctypes.data))
+        return out
+
     def set_timing(self, enable=True):
         self._check(self._lib.ssx_set_timing(self._ctx, int(enable)))
 
