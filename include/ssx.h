@@ -33,7 +33,8 @@ extern "C" {
  *      ssx_jit_counters, ssx_sums_info, ssx_rccl_groups_made, ssx_done_tiles and ssx_render_params.tile_major and tile_skew (the
  *      struct grew by 8 bytes) are new.  Added since without a change of existing entry points or structures (same version): ssx_units_info,
  *      ssx_rccl_probe (round 6); ssx_render_params.libm, appended (a caller with the struct_size before it gets SSX_LIBM_BUILD); the progressive
- *      rendering, spectral output, denoising, develop and demodulated-denoising entry points below; ssx_debug_tile_mask and SSX_DBG_TRACE_MASKED. */
+ *      rendering, spectral output, denoising, develop and demodulated-denoising entry points below; ssx_debug_tile_mask and SSX_DBG_TRACE_MASKED;
+ *      ssx_debug_spectral_accumulate. */
 #define SSX_ABI_VERSION 2
 
 enum {
@@ -901,6 +902,22 @@ int ssx_debug_sample_flux(ssx_ctx* ctx, const ssx_render_params* params, float* 
  * whichever way the uploaded scene traces its camera rays.  out: 4 words per tile slot of the device (slot s = tile tile_first + s * tile_stride of
  * the skewed tile list), word g = primitives 32 g .. 32 g + 31.  Touches neither the sample arrays nor the sums: the continuable state stays. */
 int ssx_debug_tile_mask(ssx_ctx* ctx, const ssx_render_params* params, uint32_t* out);
+/* ssx_spectral_bin_kernel and, with q given, ssx_spectral_moment_kernel -- the very kernels a render launches after each launch of its sample walk, through the
+ * launch helpers the render uses -- on sample records the caller supplies, as a pure function of its arguments (no scene needed, like ssx_probe_arrays).  n_k
+ * [launches]: the samples per pixel of each launch, K their sum; flux [height][width][K][4]: every sample's hero flux; lambda_0 [height][width][K]: its first hero
+ * wavelength (to be kept within [lambda_min, lambda_min + lambda_step]: outside it the index of "Spectral radiance output" is not defined).  From S, N, Q zeroed
+ * as ssx_render_start leaves them, launch l hands the kernels samples [k0, k0 + n_k[l]) of every pixel the tile list of tile_first / tile_stride / tile_skew
+ * owns, laid out as the path kernels leave them ([tile slot][k - k0][pixel of the tile]); then the export and variance kernels bring back sums [height][width][bins],
+ * counts [height][width][bins / 4] and q [height][width][bins] (the raw second-moment sums of ssx_spectral_variance; may be NULL: the moment kernel does not
+ * run).  Pixels of other tiles come back as +0.0 / 0.  The bits are those of "Spectral radiance output" and "Spectral moments" restated sequentially in ascending
+ * k, whatever the split into launches (tests/spectral_accumulate_cases.py).  It touches nothing of the context's: sums, bins, moments and what is valid stay.
+ * SSX_ERR_ARG, ssx_last_error naming the field: bins not a multiple of 4 in 4..64; an empty or too large image, or more than 2^30 records (tiles * 64 * K);
+ * tile_stride == 0 or tile_first >= tile_stride; lambda_min not finite, lambda_step not finite and positive; launches == 0 or an n_k of 0; a NULL n_k, flux,
+ * lambda_0, sums or counts.  SSX_ERR_STATE: a render runs. */
+int ssx_debug_spectral_accumulate(ssx_ctx* ctx, uint32_t width, uint32_t height, uint32_t bins, uint32_t tile_first, uint32_t tile_stride, uint32_t tile_skew,
+                                  float lambda_min, float lambda_step, uint32_t launches, const uint32_t* n_k /* [launches] */,
+                                  const float* flux /* [H][W][K][4] */, const float* lambda_0 /* [H][W][K] */,
+                                  double* sums /* [H][W][B] */, uint32_t* counts /* [H][W][M] */, double* q /* [H][W][B] or NULL */);
 
 #ifdef __cplusplus
 }

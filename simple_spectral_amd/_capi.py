@@ -123,7 +123,7 @@ HIP_SYMBOLS = ["ssx_create", "ssx_destroy", "ssx_upload_scene", "ssx_render_star
                "ssx_spectral_noise", "ssx_spectral_noise_reduce",
                "ssx_spectral_moments_import",
                "ssx_spectral_compare", "ssx_spectral_compare_arrays",
-               "ssx_debug_tile_mask"]
+               "ssx_debug_tile_mask", "ssx_debug_spectral_accumulate"]
 (SSX_SWEEP_RCP, SSX_SWEEP_SQRT, SSX_SWEEP_INVERSESQRT, SSX_SWEEP_SIN, SSX_SWEEP_COS, SSX_SWEEP_ACOS, SSX_SWEEP_DIV_PI,
  SSX_SWEEP_RCP64, SSX_SWEEP_DIV_PAIRS, SSX_SWEEP_ACOS_SIN, SSX_SWEEP_SIN_PROOF, SSX_SWEEP_COS_PROOF, SSX_SWEEP_ACOS_PROOF) = range(1, 14)
 # ssx_debug_eval ops (include/ssx.h)
@@ -381,6 +381,8 @@ def hip_lib():
             lib.ssx_spectral_moments_import.argtypes = [vp, C.POINTER(SsxSpectralInfo), vp]
         if not override or hasattr(lib, "ssx_debug_tile_mask"):  # the camera-ray pre-trace's tile masks, read back
             lib.ssx_debug_tile_mask.argtypes = [vp, C.POINTER(SsxRenderParams), vp]
+        if not override or hasattr(lib, "ssx_debug_spectral_accumulate"):  # the bin and moment kernels on the caller's sample records
+            lib.ssx_debug_spectral_accumulate.argtypes = [vp] + [C.c_uint32] * 6 + [C.c_float, C.c_float, C.c_uint32] + [vp] * 6
         lib.ssx_kernel_variant.argtypes = [vp]
         lib.ssx_kernel_name.argtypes = [vp]
         lib.ssx_kernel_name.restype = C.c_char_p

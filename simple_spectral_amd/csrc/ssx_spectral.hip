@@ -173,6 +173,14 @@ int spectral_begin(ssx_ctx* ctx, uint32_t my_tiles, bool continuing, bool* activ
 	return SSX_OK;
 }
 
+// The one launch of ssx_spectral_bin_kernel, dynamic-LDS size included: a render's (spectral_batch) and ssx_debug_spectral_accumulate's (ssx_spectral_stats.hip).
+int launch_spectral_bin(ssx_ctx* ctx, const SsxSpectralArgs& a, uint32_t tiles, hipStream_t stream) {
+	const size_t lds = (size_t)a.M * (256u * sizeof(double) + 64u * sizeof(uint32_t)); // <= 36 KB at 64 bins
+	hipLaunchKernelGGL(ssx_spectral_bin_kernel, dim3(tiles), dim3(256), lds, stream, a);
+	SSX_HIP(ctx, hipGetLastError());
+	return SSX_OK;
+}
+
 // after the launch of samples [k0, k0 + n_k) of every owned pixel, in stream order: its records are in the sample arrays until the next launch
 int spectral_batch(ssx_ctx* ctx, const ssx_render_params* p, const LaunchPlan& pl, uint32_t n_k, hipStream_t stream) {
 	if (pl.args.my_tiles == 0 || n_k == 0) return SSX_OK;
@@ -184,10 +192,7 @@ int spectral_batch(ssx_ctx* ctx, const ssx_render_params* p, const LaunchPlan& p
 	a.g = pixel_grid(p);
 	a.n_k = n_k; a.M = ctx->spectral_bins / 4u;
 	a.lambda_min = ctx->lambda_min; a.lambda_step = ctx->lambda_step;
-	const size_t lds = (size_t)a.M * (256u * sizeof(double) + 64u * sizeof(uint32_t)); // <= 36 KB at 64 bins
-	hipLaunchKernelGGL(ssx_spectral_bin_kernel, dim3(pl.args.my_tiles), dim3(256), lds, stream, a);
-	SSX_HIP(ctx, hipGetLastError());
-	return SSX_OK;
+	return launch_spectral_bin(ctx, a, pl.args.my_tiles, stream);
 }
 
 void spectral_drop(ssx_ctx* ctx) { ctx->d_spectral_sums.release(); ctx->d_spectral_counts.release(); }

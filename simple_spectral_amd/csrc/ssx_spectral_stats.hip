@@ -184,6 +184,14 @@ int moments_begin(ssx_ctx* ctx, uint32_t my_tiles, bool continuing, bool spectra
 	return SSX_OK;
 }
 
+// The one launch of ssx_spectral_moment_kernel, dynamic-LDS size included: a render's (moments_batch) and ssx_debug_spectral_accumulate's.
+int launch_spectral_moment(ssx_ctx* ctx, const SsxMomentArgs& a, uint32_t tiles, hipStream_t stream) {
+	const size_t lds = (size_t)a.M * 256u * sizeof(double); // <= 32 KB at 64 bins
+	hipLaunchKernelGGL(ssx_spectral_moment_kernel, dim3(tiles), dim3(256), lds, stream, a);
+	SSX_HIP(ctx, hipGetLastError());
+	return SSX_OK;
+}
+
 // after the launch of samples [k0, k0 + n_k), next to spectral_batch: the same records, read again
 int moments_batch(ssx_ctx* ctx, const ssx_render_params* p, const LaunchPlan& pl, uint32_t n_k, hipStream_t stream) {
 	if (pl.args.my_tiles == 0 || n_k == 0) return SSX_OK;
@@ -195,10 +203,7 @@ int moments_batch(ssx_ctx* ctx, const ssx_render_params* p, const LaunchPlan& pl
 	a.g = pixel_grid(p);
 	a.n_k = n_k; a.M = ctx->spectral_bins / 4u;
 	a.lambda_min = ctx->lambda_min; a.lambda_step = ctx->lambda_step;
-	const size_t lds = (size_t)a.M * 256u * sizeof(double); // <= 32 KB at 64 bins
-	hipLaunchKernelGGL(ssx_spectral_moment_kernel, dim3(pl.args.my_tiles), dim3(256), lds, stream, a);
-	SSX_HIP(ctx, hipGetLastError());
-	return SSX_OK;
+	return launch_spectral_moment(ctx, a, pl.args.my_tiles, stream);
 }
 
 // the end of a sample walk: the moments of the launches that ran, or why there are none
@@ -364,6 +369,86 @@ int ssx_probe_arrays(ssx_ctx* ctx, uint32_t width, uint32_t height, uint32_t bin
 	SSX_HIP(ctx, hipMemcpyAsync(d.q, q, pixels * bins * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
 	SSX_HIP(ctx, hipMemcpyAsync(d.counts, counts, pixels * (bins / 4u) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
 	return probe_device(ctx, d, width, height, bins, labels, regions, SS, NN, VV, UU);
+}
+
+// ssx_spectral_bin_kernel and ssx_spectral_moment_kernel on the caller's records (include/ssx.h): the records of each launch go up in the path kernels' layout
+// [tile slot][k - k0][pixel of the tile] -- slot and lane of a pixel by ssx_shared_tile, as the export kernel finds them --, the two kernels run through the launch
+// helpers a render uses, on S, N, Q of the call's own, and the export and variance kernels bring the state back row-major.  Everything lives in d_probe, the
+// temporaries of one pure call: the context's bins, moments, sums and flags are not looked at.
+int ssx_debug_spectral_accumulate(ssx_ctx* ctx, uint32_t width, uint32_t height, uint32_t bins, uint32_t tile_first, uint32_t tile_stride, uint32_t tile_skew,
+                                  float lambda_min, float lambda_step, uint32_t launches, const uint32_t* n_k, const float* flux, const float* lambda_0,
+                                  double* sums, uint32_t* counts, double* q) {
+	if (!ctx) return SSX_ERR_ARG;
+	const char* const what = "ssx_debug_spectral_accumulate";
+	if (!valid_bins(bins)) return fail(ctx, SSX_ERR_ARG, fmt("%s: %u bins: need a multiple of 4 up to 64", what, bins));
+	int rc = denoise_check_size(ctx, width, height, what);
+	if (rc) return rc;
+	if (tile_stride == 0u || tile_first >= tile_stride) return fail(ctx, SSX_ERR_ARG, fmt("%s: need tile_first < tile_stride", what));
+	if (!std::isfinite(lambda_min) || !std::isfinite(lambda_step) || !(lambda_step > 0.0f)) return fail(ctx, SSX_ERR_ARG, fmt("%s: lambda_min must be finite, lambda_step finite and positive", what));
+	if (!n_k || !flux || !lambda_0 || !sums || !counts) return fail(ctx, SSX_ERR_ARG, fmt("%s: n_k, flux, lambda_0, sums and counts must not be NULL", what));
+	if (launches == 0u) return fail(ctx, SSX_ERR_ARG, fmt("%s: launches must be positive", what));
+	ssx_render_params p{};
+	p.struct_size = sizeof p; p.width = width; p.height = height; p.tile_first = tile_first; p.tile_stride = tile_stride; p.tile_skew = tile_skew;
+	const uint64_t all_tiles = (uint64_t)tiles_across(width) * tiles_across(height);
+	uint64_t K = 0; uint32_t max_nk = 0;
+	for (uint32_t l = 0; l < launches; ++l) {
+		if (n_k[l] == 0u) return fail(ctx, SSX_ERR_ARG, fmt("%s: n_k[%u] = 0: every launch needs a sample", what, l));
+		K += n_k[l]; max_nk = n_k[l] > max_nk ? n_k[l] : max_nk;
+		if (all_tiles * 64u * K > (1ull << 30)) return fail(ctx, SSX_ERR_ARG, fmt("%s: too many records (tiles * 64 * samples per pixel: at most 2^30)", what));
+	}
+	if ((rc = idle_on_device(ctx))) return rc;
+	const SsxPixelGrid g = pixel_grid(&p);
+	const uint32_t tiles = owned_tiles(p), B = bins, M = bins / 4u;
+	const size_t pixels = (size_t)width * height, records = (size_t)tiles * max_nk * 64u, cells = (size_t)tiles * B * 64u;
+	float4* d_flux; uint4* d_st; double* d_S; double* d_Q; uint32_t* d_N; double* d_sums; double* d_q; uint32_t* d_counts;
+	if ((rc = carve(ctx, ctx->d_probe, [&](Carver& c) {
+		d_flux = c.take<float4>(records); d_st = c.take<uint4>(records);
+		d_S = c.take<double>(cells); d_Q = c.take<double>(cells); d_N = c.take<uint32_t>((size_t)tiles * M * 64u);
+		d_sums = c.take<double>(pixels * B); d_q = c.take<double>(pixels * B); d_counts = c.take<uint32_t>(pixels * M);
+	}))) return rc;
+	if (tiles) { // as spectral_begin and moments_begin leave a fresh render
+		SSX_HIP(ctx, hipMemsetAsync(d_S, 0, cells * sizeof(double), ctx->stream));
+		SSX_HIP(ctx, hipMemsetAsync(d_Q, 0, cells * sizeof(double), ctx->stream));
+		SSX_HIP(ctx, hipMemsetAsync(d_N, 0, (size_t)tiles * M * 64u * sizeof(uint32_t), ctx->stream));
+	}
+	std::vector<float4> fl; std::vector<uint4> st;
+	uint64_t k0 = 0;
+	for (uint32_t l = 0; l < launches && tiles; k0 += n_k[l], ++l) {
+		const uint32_t n = n_k[l];
+		const size_t n_rec = (size_t)tiles * n * 64u;
+		fl.assign(n_rec, float4{ 0.0f, 0.0f, 0.0f, 0.0f }); st.assign(n_rec, uint4{ 0u, 0u, 0u, 0u });
+		for (uint32_t j = 0; j < height; ++j) for (uint32_t i = 0; i < width; ++i) {
+			if (!ssx_owns_pixel(g, i, j)) continue;
+			const size_t slot = ssx_shared_tile(g, i, j) / g.tile_stride, lane = (j & 7u) * 8u + (i & 7u);
+			for (uint32_t kk = 0; kk < n; ++kk) {
+				const size_t r = (slot * n + kk) * 64u + lane, o = ((size_t)j * width + i) * K + k0 + kk;
+				memcpy(&fl[r], flux + 4u * o, sizeof(float4)); // (bits, not values: a signalling NaN stays what the caller wrote)
+				memcpy(&st[r].x, lambda_0 + o, sizeof(float));
+			}
+		}
+		SSX_HIP(ctx, hipMemcpy(d_flux, fl.data(), n_rec * sizeof(float4), hipMemcpyHostToDevice)); // (synchronous: the host vectors are refilled for the next launch)
+		SSX_HIP(ctx, hipMemcpy(d_st, st.data(), n_rec * sizeof(uint4), hipMemcpyHostToDevice));
+		SsxSpectralArgs a{};
+		a.flux = d_flux; a.st = d_st; a.S = d_S; a.N = d_N; a.g = g; a.n_k = n; a.M = M; a.lambda_min = lambda_min; a.lambda_step = lambda_step;
+		if ((rc = launch_spectral_bin(ctx, a, tiles, ctx->stream))) return rc;
+		if (q) {
+			SsxMomentArgs b{};
+			b.flux = d_flux; b.st = d_st; b.Q = d_Q; b.g = g; b.n_k = n; b.M = M; b.lambda_min = lambda_min; b.lambda_step = lambda_step;
+			if ((rc = launch_spectral_moment(ctx, b, tiles, ctx->stream))) return rc;
+		}
+		SSX_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the records are overwritten by the next launch's
+	}
+	hipLaunchKernelGGL(ssx_spectral_export_kernel, pixel_blocks(&p), dim3(256), 0, ctx->stream, (const double*)d_S, (const uint32_t*)d_N, (float*)nullptr, d_sums, d_counts, g, M);
+	SSX_HIP(ctx, hipGetLastError());
+	if (q) {
+		hipLaunchKernelGGL(ssx_spectral_variance_kernel, pixel_blocks(&p), dim3(256), 0, ctx->stream, (const double*)d_S, (const double*)d_Q, (const uint32_t*)d_N, (float*)nullptr, d_q, g, M);
+		SSX_HIP(ctx, hipGetLastError());
+	}
+	SSX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	SSX_HIP(ctx, hipMemcpy(sums, d_sums, pixels * B * sizeof(double), hipMemcpyDeviceToHost));
+	SSX_HIP(ctx, hipMemcpy(counts, d_counts, pixels * M * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	if (q) SSX_HIP(ctx, hipMemcpy(q, d_q, pixels * B * sizeof(double), hipMemcpyDeviceToHost));
+	return SSX_OK;
 }
 
 } // extern "C"

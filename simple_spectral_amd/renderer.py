@@ -1050,6 +1050,26 @@ class Renderer:
         self._check(self._lib.ssx_debug_tile_mask(self._ctx, C.byref(p), out.ctypes.data))
         return out
 
+    def debug_spectral_accumulate(self, flux, lambda_0, bins, lambda_min, lambda_step, n_k=None, tile_first=0, tile_stride=1, tile_skew=0, moments=True):
+        """ssx_debug_spectral_accumulate: the render's bin and moment kernels on the caller's records -- flux float32 [H, W, K, 4], lambda_0 float32 [H, W, K],
+        given to the kernels as len(n_k) launches of n_k[l] samples per pixel (None: one launch of K) -> (sums float64 [H, W, B], counts uint32 [H, W, B / 4],
+        q float64 [H, W, B] or None without moments); +0.0 / 0 for pixels the tile list of tile_first / tile_stride / tile_skew does not own.  The arrays go to
+        the library as they are: their bits, NaN payloads included, are what the kernels read."""
+        flux, lambda_0 = np.ascontiguousarray(flux, dtype=np.float32), np.ascontiguousarray(lambda_0, dtype=np.float32)
+        if flux.ndim != 4 or flux.shape[3] != 4 or lambda_0.shape != flux.shape[:3]:
+            raise ValueError("debug_spectral_accumulate: flux must have shape [H, W, K, 4], lambda_0 [H, W, K]")
+        H, W, K = lambda_0.shape
+        n_k = np.ascontiguousarray([K] if n_k is None else n_k, dtype=np.uint32)
+        if n_k.ndim != 1 or int(n_k.astype(np.uint64).sum()) != K:
+            raise ValueError("debug_spectral_accumulate: the launch lengths n_k must add up to K = %d" % K)
+        B = int(bins)
+        sums, counts = np.zeros((H, W, B), dtype=np.float64), np.zeros((H, W, max(B // 4, 1)), dtype=np.uint32)
+        q = np.zeros((H, W, B), dtype=np.float64) if moments else None
+        self._check(self._lib.ssx_debug_spectral_accumulate(self._ctx, W, H, B, int(tile_first), int(tile_stride), int(tile_skew), float(lambda_min), float(lambda_step),
+                                                            len(n_k), n_k.ctypes.data, flux.ctypes.data, lambda_0.ctypes.data, sums.ctypes.data, counts.ctypes.data,
+                                                            None if q is None else q.ctypes.data))
+        return sums, counts, q
+
     def set_timing(self, enable=True):
         self._check(self._lib.ssx_set_timing(self._ctx, int(enable)))
 

@@ -26,6 +26,22 @@ def restate_bins(flux, lam, lambda_min, lambda_step, bins):
     return S, N, mean
 
 
+def restate_moments(flux, lam, lambda_min, lambda_step, bins):
+    """include/ssx.h "Spectral moments", sequentially: Q float64 [H, W, B], Q[i * M + m] += (double)f[i] * (double)f[i] in ascending k from +0.0 -- the product
+    of the two converted binary32 values, taken in binary64 (where it is exact)."""
+    H, W, spp = lam.shape
+    M = bins // 4
+    m = spectral_bin_index(lam, lambda_min, lambda_step, bins)
+    Q = np.zeros((H, W, bins), dtype=np.float64)
+    J, I = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
+    with np.errstate(over="ignore", invalid="ignore"):
+        for k in range(spp):                   # ascending k; every pixel appears once per statement
+            for i in range(4):
+                d = flux[:, :, k, i].astype(np.float64)
+                Q[J, I, i * M + m[:, :, k]] += d * d
+    return Q
+
+
 def project_flux(o, flux, lam, seed, lambda_min, lambda_step):
     """(proj float32 [H, W, spp, 3], lambda_0 restated [H, W, spp]): every sample's flux through orc_specradflux_to_ciexyz_hero of the oracle `o`, and the draw of
     its first hero wavelength restated (renderer.cpp:113,138: two doubles of sub-pixel offset, then the wavelength)."""
