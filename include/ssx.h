@@ -34,7 +34,7 @@ extern "C" {
  *      struct grew by 8 bytes) are new.  Added since without a change of existing entry points or structures (same version): ssx_units_info,
  *      ssx_rccl_probe (round 6); ssx_render_params.libm, appended (a caller with the struct_size before it gets SSX_LIBM_BUILD); the progressive
  *      rendering, spectral output, denoising, develop and demodulated-denoising entry points below; ssx_debug_tile_mask and SSX_DBG_TRACE_MASKED;
- *      ssx_debug_spectral_accumulate. */
+ *      ssx_debug_spectral_accumulate; SSX_DBG_TRACE_TOPO. */
 #define SSX_ABI_VERSION 2
 
 enum {
@@ -852,7 +852,15 @@ enum {
 	 * q >> 5 = primitive q may be hit; a primitive whose bit is clear is left out.  The device function reads the mask ONCE PER WAVE (through the first lane:
 	 * in a render it is the tile's), so the items are taken in blocks of 64 -- items 64 b .. 64 b + 63 -- and every item of a block must carry the same four
 	 * words: the caller pads its last block, e.g. with copies of its final row.  Bits at or above the number of primitives are ignored. */
-	SSX_DBG_TRACE_MASKED = 16 /* in: orig[3], dir[3], ignore quad (int), mask[4]   out: as SSX_DBG_TRACE */
+	SSX_DBG_TRACE_MASKED = 16, /* in: orig[3], dir[3], ignore quad (int), mask[4]   out: as SSX_DBG_TRACE */
+	/* The trace the context's renders run for bounce and shadow rays.  SSX_DBG_TRACE and SSX_DBG_TRACE_MASKED run the generic loop whatever the scene; this op
+	 * runs the body specialised to the context's mesh topology (ssx_kernel_variant(): 1 Cornell, 2 plane, 3 the scene's own pattern, e.g. after
+	 * ssx_set_jit(ctx, SSX_JIT_AT_UPLOAD)): its generated pass 1, and the pass 2 that finds a candidate's vertices in the distinct-vertex table.  Same upload,
+	 * same rows, same answers as SSX_DBG_TRACE is the contract the tests hold it to.  has_ray = 0: the lane takes part in the wave's pass 1 and traces
+	 * nothing, as an idle lane of a shadow-ray flush; its answer is "none", distance +inf, st 0.  SSX_ERR_STATE on a context that runs the generic kernel
+	 * (topology 0; the op would be SSX_DBG_TRACE), and where the debug kernel of a scene's own pattern cannot be compiled: that kernel lives in a debug-only
+	 * variant of the pattern's run-time program, compiled (or loaded from the disk cache) at the first call; the production variants are untouched by it. */
+	SSX_DBG_TRACE_TOPO = 17   /* in: orig[3], dir[3], ignore quad (int), has_ray (0 / 1)   out: as SSX_DBG_TRACE */
 };
 /* rng[4] = PCG32 {state lo, state hi, inc lo, inc hi} */
 /* ssx_debug_sweep: device-side comparison of a cheaper device function with the function that DEFINES the

@@ -132,6 +132,7 @@ HIP_SYMBOLS = ["ssx_create", "ssx_destroy", "ssx_upload_scene", "ssx_render_star
 # ... and of libm = glibc-2.35 (the _glibc kernels' units), with the sweeps of include/ssx_glibc_math.h on the device
 (SSX_DBG_GLIBC_MATH, SSX_DBG_SPHTRI_GLIBC, SSX_DBG_ARVO_GLIBC, SSX_DBG_SAMPLE_LIGHT_GLIBC, SSX_DBG_COSHEMI_GLIBC) = range(11, 16)
 (SSX_SWEEP_GLIBC_SIN, SSX_SWEEP_GLIBC_COS, SSX_SWEEP_GLIBC_ACOS, SSX_SWEEP_GLIBC_COS_LDS) = range(14, 18)
+SSX_DBG_TRACE_TOPO = 17     # SSX_DBG_TRACE's row + has_ray: the trace specialised to the context's topology (1, 2, or 3 = the scene's own pattern), as its renders run it
 SSX_DBG_TRACE_MASKED = 16   # SSX_DBG_TRACE's row + mask[4]: the masked pass 1 of the generate kernel's trace (rows in blocks of 64 sharing one mask)
 HOST_SYMBOLS = ["ssh_scene_create", "ssh_scene_create_ex", "ssh_scene_destroy", "ssh_scene_desc", "ssh_xyza_to_srgba", "ssh_save_image",
                 "ssh_load_png_rgb8", "ssh_free", "ssh_color_values", "ssh_last_error", "ssh_checkpoint_save", "ssh_checkpoint_load", "ssh_sums_merge", "ssh_save_npy_f32",

@@ -1277,7 +1277,27 @@ int ssx_debug_eval(ssx_ctx* ctx, uint32_t op, const void* in, uint32_t in_words,
 	a.blob = ctx->d_blob.as<uint32_t>(); a.blob_words = ctx->blob_words; a.rgb_mode = ctx->rgb_mode ? 1u : 0u;
 	const size_t lds = staged_blob_lds(ctx->blob_words);
 	if (op == SSX_DBG_TRACE_MASKED && in_words < 11u) return fail(ctx, SSX_ERR_ARG, "SSX_DBG_TRACE_MASKED: a row is orig[3], dir[3], ignore, mask[4]");
-	const auto kernel = op >= SSX_DBG_GLIBC_MATH && op <= SSX_DBG_COSHEMI_GLIBC ? ssx_debug_eval_glibc_kernel : ssx_debug_eval_kernel; // the units of libm = glibc-2.35: a kernel that stages the _glibc kernels' LDS table
+	if (op == SSX_DBG_TRACE_TOPO) {
+		// the trace of the context's topology, in a kernel of its own (csrc/ssx_debug.hip); a scene on its own pattern's kernels gets the debug-only
+		// variant of its run-time program, compiled -- or found in memory / on disk -- at the first call (csrc/ssx_jit.h kVariantDebug)
+		if (in_words < 8u) return fail(ctx, SSX_ERR_ARG, "SSX_DBG_TRACE_TOPO: a row is orig[3], dir[3], ignore, has_ray");
+		if (ctx->topology == 0u) return fail(ctx, SSX_ERR_STATE, "SSX_DBG_TRACE_TOPO: the context runs the generic trace (topology 0); that is SSX_DBG_TRACE");
+		const uint32_t* d_rows = d_in.as<uint32_t>(); uint32_t* d_res = d_out.as<uint32_t>();
+		void* args[] = { &a, &d_rows, &in_words, &d_res, &out_words, &n };
+		if (ctx->topology == 3u) {
+			std::string err;
+			const ssx_jit::Kernels* k = ssx_jit::get(ctx->device, ctx->jit_vid, &err, ssx_jit::kVariantDebug);
+			if (!k || !k->debug_trace) return fail(ctx, SSX_ERR_STATE, "SSX_DBG_TRACE_TOPO: the debug kernel of the scene's pattern could not be compiled: " + err);
+			SSX_HIP(ctx, hipModuleLaunchKernel(k->debug_trace, (n + 255u) / 256u, 1, 1, 256, 1, 1, (unsigned)lds, ctx->stream, args, nullptr));
+		} else {
+			const void* host = ctx->topology == 1u ? (const void*)ssx_debug_trace_cornell_kernel : (const void*)ssx_debug_trace_plane_kernel;
+			SSX_HIP(ctx, hipLaunchKernel(host, dim3((n + 255u) / 256u), dim3(256), args, lds, ctx->stream));
+		}
+		SSX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+		SSX_HIP(ctx, hipMemcpy(out, d_out.ptr, (size_t)n * out_words * 4, hipMemcpyDeviceToHost));
+		return SSX_OK;
+	}
+	const auto kernel =op >= SSX_DBG_GLIBC_MATH && op <= SSX_DBG_COSHEMI_GLIBC ? ssx_debug_eval_glibc_kernel : ssx_debug_eval_kernel; // the units of libm = glibc-2.35: a kernel that stages the _glibc kernels' LDS table
 	hipLaunchKernelGGL(kernel, dim3((n + 255u) / 256u), dim3(256), lds, ctx->stream, a, op, d_in.as<uint32_t>(), in_words, d_out.as<uint32_t>(), out_words, n);
 	SSX_HIP(ctx, hipGetLastError());
 	SSX_HIP(ctx, hipStreamSynchronize(ctx->stream));

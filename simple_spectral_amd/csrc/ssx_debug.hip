@@ -3,7 +3,9 @@
 // function the megakernel inlines (this file is part of the same translation unit), one item per
 // lane, on inputs the test supplies, so the tests can compare it with the oracle's unit-level
 // functions on edge cases the renders reach rarely or never (degenerate spherical triangles, rays
-// through shared vertices, the Lemire redraw, ...).  Nothing here runs during a render.
+// through shared vertices, the Lemire redraw, ...).  SSX_DBG_TRACE and SSX_DBG_TRACE_MASKED run the generic trace<0> whatever the
+// context's topology; SSX_DBG_TRACE_TOPO (ssx_debug_trace_cornell_kernel / _plane_kernel below, and ssx_debug_trace_jit of csrc/ssx_kernels.hip for a scene's
+// own pattern) runs the topology-specialised trace the context's renders run.  Nothing here runs during a render.
 #include "../../include/ssx.h"
 #include "ssx_ddmath.h" // the independent evaluation of sin / cos / acos that ssx_fmath.h is proved against (SSX_SWEEP_*_PROOF)
 
@@ -208,6 +210,18 @@ extern "C" __global__ void __launch_bounds__(256) ssx_debug_eval_kernel(SsxKerne
 	if (gid < n)
 		for (uint32_t k = 0; k < out_words && k < 12u; ++k) out[(size_t)gid * out_words + k] = o[k];
 }
+
+// SSX_DBG_TRACE_TOPO: the trace the context's renders run -- trace<1> (Cornell topology) or trace<2> (plane topology): the generated pass 1 of
+// csrc/ssx_pass1_gen.h and the pass 2 that finds a candidate's vertices through triofs / vtab4 -- where SSX_DBG_TRACE above always runs the generic body.
+// A kernel of its own: two more inlined traces in ssx_debug_eval_kernel's switch would change that kernel's registers for every other op.  It stages the
+// whole blob, as ssx_debug_eval_kernel does, so one upload answers both ops.  (Topology 3: ssx_debug_trace_jit, csrc/ssx_kernels.hip, compiled at run time.)
+#define SSX_DEBUG_TRACE_TOPO_KERNEL(name, topo) \
+	extern "C" __global__ void __launch_bounds__(256) name(SsxKernelArgs a, const uint32_t* in, uint32_t in_words, uint32_t* out, uint32_t out_words, uint32_t n) { \
+		debug_trace_rows<topo>(a, in, in_words, out, out_words, n); \
+	}
+SSX_DEBUG_TRACE_TOPO_KERNEL(ssx_debug_trace_cornell_kernel, 1)
+SSX_DEBUG_TRACE_TOPO_KERNEL(ssx_debug_trace_plane_kernel, 2)
+#undef SSX_DEBUG_TRACE_TOPO_KERNEL
 
 // ---- libm = glibc-2.35: the same diagnostics for the _glibc kernels, in kernels of their own (they stage the LDS table of the _glibc
 // kernels, stage_lds<true>: the glibc coefficients over ssx_fmath.h's arc-cosine slots)

@@ -1037,6 +1037,25 @@ __device__ __forceinline__ void hit_st(const SsxBlobQuad& Q, uint32_t which, con
 	st_y = (bx * s0[1] + by * s1[1]) + bz * s2[1];
 }
 
+// SSX_DBG_TRACE_TOPO (include/ssx.h): trace<TOPO> -- the trace the context's renders run for bounce and shadow rays -- one row per lane.  A row is
+// orig[3], dir[3], ignore quad, has_ray; the answer is SSX_DBG_TRACE's five words.  Every lane of a wave calls trace() (uniform control flow; the lanes
+// past the end redo item n - 1), a lane without a ray takes part in pass 1 and must come back empty, as the idle lanes of shadow_flush do.  The body of
+// ssx_debug_trace_cornell_kernel / _plane_kernel (csrc/ssx_debug.hip) and of ssx_debug_trace_jit below (the scene's own pattern); no render calls it.
+template <int TOPO>
+__device__ __forceinline__ void debug_trace_rows(const SsxKernelArgs& a, const uint32_t* in, uint32_t in_words, uint32_t* out, uint32_t out_words, uint32_t n) {
+	Lds L; L.w = stage_lds(a);
+	const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
+	const uint32_t item = gid < n ? gid : n - 1u;
+	const uint32_t* x = in + (size_t)item * in_words;
+	HitInfo h;
+	trace<TOPO>(L, mk(__uint_as_float(x[0]), __uint_as_float(x[1]), __uint_as_float(x[2])), mk(__uint_as_float(x[3]), __uint_as_float(x[4]), __uint_as_float(x[5])),
+	            (int)x[6], x[7] != 0u, h);
+	uint32_t o[5] = { h.tri < 0 ? 0xFFFFFFFFu : (uint32_t)h.tri >> 1, h.tri < 0 ? 0u : (uint32_t)h.tri & 1u, __float_as_uint(h.dist), 0u, 0u };
+	if (h.tri >= 0) { float sx, sy; hit_st(L.quad((uint32_t)h.tri >> 1), (uint32_t)h.tri & 1u, h, sx, sy); o[3] = __float_as_uint(sx); o[4] = __float_as_uint(sy); }
+	if (gid < n)
+		for (uint32_t k = 0; k < out_words && k < 5u; ++k) out[(size_t)gid * out_words + k] = o[k];
+}
+
 // One level of the recursion L() (renderer.cpp:147-255) for the lane's current ray and the hit it found (p.hit_*):
 // emission (camera ray only), next-event estimation with its shadow ray, BSDF sample.  Writes the
 // level's emission term if it has one (`direct`), parks its shadow ray (whose flush writes `nee`) and,
@@ -1908,8 +1927,14 @@ __device__ __forceinline__ void render_body(const SsxKernelArgs& a) {
 	extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SSX_WAVES_PER_EU))) name(SsxKernelArgs a) { render_body<topo, narrow, false, glibc, flux>(a); }
 #ifdef SSX_JIT_BUILD // the run-time compilation holds the two path kernels of the uploaded scene's topology, nothing else; the libm mode is
 // a compile flag of it, and so part of its cache key (csrc/ssx_jit.h)
+#ifdef SSX_JIT_DEBUG // ... except in the debug-only variant of the program (csrc/ssx_jit.h kVariantDebug): SSX_DBG_TRACE_TOPO's kernel for the pattern, and no path kernel
+extern "C" __global__ void __launch_bounds__(256) ssx_debug_trace_jit(SsxKernelArgs a, const uint32_t* in, uint32_t in_words, uint32_t* out, uint32_t out_words, uint32_t n) {
+	debug_trace_rows<3>(a, in, in_words, out, out_words, n);
+}
+#else
 SSX_PATH_KERNEL(ssx_render_kernel_jit, 3, false, SSX_JIT_GLIBC, SSX_JIT_FLUX)
 SSX_PATH_KERNEL(ssx_render_kernel_jit_nq, 3, true, SSX_JIT_GLIBC, SSX_JIT_FLUX)
+#endif
 #else
 SSX_PATH_KERNEL(ssx_render_kernel, 0, false, false, false)
 SSX_PATH_KERNEL(ssx_render_kernel_cornell, 1, false, false, false)

@@ -238,6 +238,93 @@ def warped_builtin(seed):
     return c, base, opts
 
 
+def islands_scene(seed=21):
+    """32 quads that share no corner at all: 128 distinct vertices, the most a topology-specialised trace can meet (both flag accumulators of pass 1
+    full, the largest offsets of the distinct-vertex table).  A room whose six sides are each tiled by four overlapping quads in front of a fifth
+    that backs them -- every corner jittered, so no two coincide and no quad is planar or a rectangle -- with a light under the ceiling and a
+    tilted quad in the middle.  Rays from inside hit something almost always; most meet two or three candidates per side."""
+    g = np.random.default_rng(seed)
+    c = cs.CustomScene("cornell", keep_quads=False)
+    mats = (WHITE, GREEN, RED)
+    R = 4.0
+    frames = []   # (outward axis, sign): the side's plane is x[axis] = sign * R, its quads wind like _room's (normals inward is not required here)
+    for axis in range(3):
+        for sign in (-1.0, 1.0):
+            frames.append((axis, sign))
+    jit = lambda p: tuple(np.asarray(p, dtype=np.float64) + g.uniform(-0.08, 0.08, size=3))
+    for axis, sign in frames:
+        u, v = [k for k in range(3) if k != axis]
+        def corner(s, t, depth):
+            p = np.zeros(3); p[axis] = sign * (R + depth); p[u] = s; p[v] = t
+            return jit(p)
+        for i, (s0, t0) in enumerate(((-R, -R), (-0.3, -R), (-R, -0.3), (-0.3, -0.3))):       # four tiles of 4.3 x 4.3: they overlap by 0.6 in the middle
+            s1, t1 = s0 + R + 0.3, t0 + R + 0.3
+            c.add_quad(corner(s0, t0, 0.0), corner(s1, t0, 0.0), corner(s1, t1, 0.0), corner(s0, t1, 0.0), mats[(i + axis) % 3])
+        c.add_quad(corner(-R - 0.5, -R - 0.5, 0.4), corner(R + 0.5, -R - 0.5, 0.4), corner(R + 0.5, R + 0.5, 0.4), corner(-R - 0.5, R + 0.5, 0.4), WHITE)
+    c.add_quad(jit((-1, 3.5, -1)), jit((1, 3.5, -1)), jit((1, 3.5, 1)), jit((-1, 3.5, 1)), LIGHT)
+    c.add_quad(jit((-1.5, -1.0, -0.5)), jit((1.0, -1.5, 0.5)), jit((1.5, 1.0, 1.0)), jit((-1.0, 1.5, -1.0)), GREEN)
+    assert len(c.quads) == 32 and len(_distinct_corners(c)) == 128
+    c.set_camera((3.0, 0.5, -3.0), (0.0, 0.0, 0.0), up=(0, 1, 0), vfov_deg=60.0)
+    return c
+
+
+def fan_scene():
+    """One vertex that belongs to eight quads, and quads that share two edges: a cone of eight quads around its apex -- each shares an edge with
+    both neighbours, and the apex takes every one of the four corner slots in turn, so the shared edges are diagonals, first and last edges -- inside
+    a closed room (eight corners shared three ways), under a light, next to a pair of quads that share two edges WITH EACH OTHER (v00-v10 and v10-v11)."""
+    c = cs.CustomScene("cornell", keep_quads=False)
+    _room(c)
+    c.add_quad((-1, 3.9, -1), (1, 3.9, -1), (1, 3.9, 1), (-1, 3.9, 1), LIGHT)
+    apex = (0.25, 1.0, -0.5)
+    ang = [2.0 * np.pi * k / 8 + 0.1 for k in range(8)]
+    ring = [(0.25 + 1.5 * np.cos(t), -0.5, -0.5 + 1.5 * np.sin(t)) for t in ang]
+    outer = [(0.25 + 3.0 * np.cos(t + np.pi / 8), -2.0, -0.5 + 3.0 * np.sin(t + np.pi / 8)) for t in ang]
+    mats = (WHITE, GREEN, RED)
+    for k in range(8):
+        four = [apex, ring[k], outer[k], ring[(k + 1) % 8]]
+        four = four[-(k % 4):] + four[:-(k % 4)] if k % 4 else four             # the apex as v00, v10, v11, v01 in turn
+        c.add_quad(*four, mats[k % 3])
+    A, B, Cc = (-3.0, -3.0, 2.0), (-1.0, -3.5, 2.5), (-1.0, -1.0, 3.0)
+    c.add_quad(A, B, Cc, (-3.0, -1.0, 2.0), RED)
+    c.add_quad(A, B, Cc, (-3.5, -0.5, 3.5), GREEN)
+    n_apex = sum(1 for pos, _, _ in c.quads if any(np.asarray(p, dtype=np.float32).tobytes() == np.asarray(apex, dtype=np.float32).tobytes() for p in pos))
+    assert n_apex == 8 and len(c.quads) == 17
+    c.set_camera((3.4, 2.5, -3.4), (0.0, -0.5, 0.0), up=(0, 1, 0), vfov_deg=65.0)
+    return c
+
+
+# ---- the scenes of tests/test_trace_topology_{cpu,gpu}.py: (name, topology the context must report) ------------------------------------------------------
+TRACE_TOPO_SCENES = (("cornell-srgb", 1), ("cornell", 1), ("warped-cornell-a", 1), ("warped-cornell-b", 1),
+                     ("plane-srgb", 2), ("warped-plane-a", 2), ("warped-plane-b", 2),
+                     ("moved-corner", 3), ("islands32", 3), ("fan", 3))
+# seeds of warped_builtin: seed % 3 picks the base scene (0 cornell-srgb, 1 plane-srgb, 2 cornell), (seed // 3) % 4 the kind of warp
+_TRACE_TOPO_WARPS = {"warped-cornell-a": 6, "warped-cornell-b": 11, "warped-plane-a": 7, "warped-plane-b": 22}
+
+
+def trace_topo_scene(name):
+    """(CustomScene, renderer options) of one entry of TRACE_TOPO_SCENES; one object per process (matrix_case's rule)."""
+    key = ("trace-topo", name)
+    if key in _matrix_cache:
+        return _matrix_cache[key]
+    T = MATRIX_TEX
+    if name in ("cornell-srgb", "cornell", "plane-srgb"):
+        c, base = cs.CustomScene(name), name
+    elif name in _TRACE_TOPO_WARPS:
+        c, base, _ = warped_builtin(_TRACE_TOPO_WARPS[name])
+    elif name == "moved-corner":
+        c, base = matrix_case("moved-corner").scene, "cornell-srgb"
+    elif name == "islands32":
+        c, base = islands_scene(), "cornell"
+    elif name == "fan":
+        c, base = fan_scene(), "cornell"
+    else:
+        raise KeyError(name)
+    topo = dict(TRACE_TOPO_SCENES)[name]
+    opts = dict(scene_name=base, observer=c.observer, texture=None if base == "cornell" else T, res=(8, 8), spp=1, jit_pass1=topo == 3)
+    _matrix_cache[key] = (c, opts)
+    return c, opts
+
+
 # ---- the scene and option matrix of tests/test_pipeline_matrix_{cpu,gpu}.py -------------------------------------------------------------------------------
 # Every scene and switch the path kernel is tested on, as (oracle, renderer) pairs for the kernels behind it: the _flux twins, the bin kernel, the guides,
 # the noise estimate, the filter chain and the develop.

@@ -108,11 +108,11 @@ def scene_quads(c):
     return [q[0] for q in c.quads]
 
 
-@pytest.mark.parametrize("which", ["cornell-srgb", "shared-edge", "degenerate"])
+@pytest.mark.parametrize("which", ["cornell-srgb", "shared-edge", "degenerate", "plane-srgb"])
 def test_scene_intersect_on_vertices_edges_and_random_rays(which):
     """src/scene.cpp:433-445, src/geometry.cpp:12-139: closest quad, distance and st, incl. rays aimed
     exactly at vertices / edge midpoints / the diagonal, axis-parallel rays, rays leaving a quad"""
-    c = {"cornell-srgb": lambda: cs.CustomScene("cornell-srgb"), "shared-edge": crafted.shared_edge_scene,
+    c = {"cornell-srgb": lambda: cs.CustomScene("cornell-srgb"), "plane-srgb": lambda: cs.CustomScene("plane-srgb"), "shared-edge": crafted.shared_edge_scene,
          "degenerate": lambda: crafted.degenerate_light_scene("room")}[which]()
     r, orc = custom_pair(c)
     w = uc.trace_inputs(scene_quads(c))

@@ -251,6 +251,146 @@ def oracle_trace(orc, words):
     return out, st
 
 
+# ------------------------------------------------------------- trace, topology-specialised bodies ----
+TRACE_FAMILIES = ("a", "b", "c", "d", "e")
+EMPTY_TRACE = (0xFFFFFFFF, 0, 0x7F800000, 0, 0)   # what a lane without a ray returns: no quad, triangle 0, distance +inf, st 0
+
+
+def _special_dirs():
+    """family (d): ties in the dominant axis, -0.0 components, a denormal dominant component, the zero vector, NaN and +-inf components"""
+    n, i, z = np.nan, np.inf, -0.0
+    return np.array([
+        (1, 1, 0.3), (1, -1, 0.3), (-1, -1, -0.25), (0.3, 1, 1), (0.3, 1, -1), (-0.5, -1, -1), (1, 0.2, 1), (-1, 0.2, 1), (1, -0.7, -1),   # |dx|==|dy|, |dy|==|dz|, |dx|==|dz|
+        (1, 1, 1), (-1, 1, -1), (1, -1, 1), (-1, -1, -1), (0.5, 0.5, 0.5),                                                                    # all three equal
+        (z, 1, 0), (1, z, z), (z, z, 1), (0.5, z, 1), (z, -1, z), (z, z, -1), (-1, z, 0.25), (z, 1, 1), (1, 1, z),                            # -0.0 components
+        (1e-40, 1e-42, 0), (0, -1e-45, 0), (1e-39, -1e-39, 1e-41), (z, z, 1e-45), (-1e-38 / 4, 0, 1e-44), (1e-41, 1e-41, 1e-41),              # denormal dominant component
+        (0, 0, 0), (z, z, z), (0, z, 0),                                                                                                       # the zero vector
+        (n, 1, 0), (1, n, 0), (0, 1, n), (n, n, n), (n, 0, 0), (0.5, 0.5, n), (n, -1, n),                                                     # NaN components
+        (i, 1, 0), (-i, 0, 1), (1, i, i), (i, -i, i), (0, 0, i), (0, -i, 0), (0.5, 1, -i), (-i, -i, 0.5),                                     # +-inf components
+    ], dtype=np.float32)
+
+
+def trace_topo_inputs(quads, seed=5, n_random=1000):
+    """Rows of SSX_DBG_TRACE_TOPO -- orig[3], dir[3], ignore, has_ray -- against a scene's quads, and what each row is:
+    returns (words [n, 8] uint32, family [n] of 'a'..'e', live [n] bool).  The families:
+      a  everything trace_inputs makes (same seed, same rows, same order);
+      b  origins exactly ON a quad -- its vertices, edge midpoints and interior points, so depths along kz are +-0 for that quad -- along the six axis
+         directions and a random one, with and without `ignore` naming the quad;
+      c  origins that share exactly one coordinate with a vertex, that coordinate's axis dominant in the direction (both signs): the vertex lies in
+         the origin's kz plane;
+      d  the directions of _special_dirs from origins inside the scene and on vertices, and NaN origins;
+      e  per quad: rays leaving along its normal from in front of it (the whole quad behind the origin) and rays inside its plane through its centre
+         (the quad straddles the origin's kz plane).
+    Every fourth row is followed by a copy of itself with has_ray = 0 (family f of the issue: idle lanes interleaved with live ones inside a wave), and
+    a whole wave of such rows plus a ragged end close the array; `live` is the has_ray word."""
+    g = np.random.default_rng(seed + 1000)
+    verts = np.array([q for q in quads], dtype=np.float32).astype(np.float64)  # [nq, 4, 3], exactly the float32 positions
+    nq = len(verts)
+    lo, hi = verts.reshape(-1, 3).min(0), verts.reshape(-1, 3).max(0)
+    span = hi - lo
+    a = trace_inputs(quads, seed=seed, n_random=n_random)
+    fam = [np.full(len(a), "a")]
+    rows = []   # (orig [k, 3] float, dir [k, 3] float, ignore [k] int)
+    axes6 = np.concatenate([np.eye(3), -np.eye(3)])
+    # ---- b
+    O, D, I = [], [], []
+    for q in range(nq):
+        v = verts[q]
+        pts = np.array([v[0], v[1], v[2], v[3], (v[0] + v[1]) / 2, (v[2] + v[3]) / 2, (v[0] + v[2]) / 2, 0.5 * v[1] + 0.25 * (v[0] + v[2]), 0.5 * v[3] + 0.25 * (v[0] + v[2])])
+        dirs = np.concatenate([axes6, unit(g.normal(size=(1, 3)))])
+        for ign in (q, -1):
+            O.append(np.repeat(pts, len(dirs), axis=0)); D.append(np.tile(dirs, (len(pts), 1))); I.append(np.full(len(pts) * len(dirs), ign))
+    rows.append((np.concatenate(O), np.concatenate(D), np.concatenate(I)))
+    fam.append(np.full(len(rows[-1][0]), "b"))
+    # ---- c
+    distinct = np.unique(verts.reshape(-1, 3), axis=0)
+    O, D = [], []
+    for k in range(3):
+        for sign in (1.0, -1.0):
+            o = g.uniform(lo + 0.1 * span, hi - 0.1 * span, size=(len(distinct), 3))
+            o[:, k] = distinct[:, k]
+            d = g.uniform(-0.6, 0.6, size=(len(distinct), 3))
+            d[:, k] = sign
+            O.append(o); D.append(d)
+    rows.append((np.concatenate(O), np.concatenate(D), np.full(6 * len(distinct), -1)))
+    fam.append(np.full(len(rows[-1][0]), "c"))
+    # ---- d
+    sd = _special_dirs()
+    origins = np.concatenate([g.uniform(lo + 0.2 * span, hi - 0.2 * span, size=(10, 3)), distinct[:: max(1, len(distinct) // 6)][:6]])
+    O = np.repeat(origins, len(sd), axis=0); D = np.tile(sd, (len(origins), 1))
+    nan_o = g.uniform(lo, hi, size=(9, 3)); nan_o[np.arange(9), np.arange(9) % 3] = np.nan; nan_o[6:] = np.nan
+    O = np.concatenate([O, nan_o]); D = np.concatenate([D, unit(g.normal(size=(9, 3)))])
+    rows.append((O, D, np.full(len(O), -1)))
+    fam.append(np.full(len(O), "d"))
+    # ---- e
+    O, D, I = [], [], []
+    for q in range(nq):
+        v = verts[q]
+        c = v.mean(0)
+        nrm = np.cross(v[1] - v[0], v[2] - v[0]); nrm /= np.linalg.norm(nrm)
+        size = np.linalg.norm(v[2] - v[0])
+        tang = (v[1] - v[0]) / np.linalg.norm(v[1] - v[0])
+        for s in (1.0, -1.0):
+            O.append(c + s * 0.3 * size * nrm); D.append(s * nrm + 0.2 * g.normal(size=3)); I.append(-1)        # the quad wholly behind
+            O.append(c + s * 1e-3 * size * nrm); D.append(s * tang + 0.05 * g.normal(size=3)); I.append(-1)     # in (almost) its plane: it straddles
+        O.append(c); D.append(tang); I.append(q)                                                                  # exactly through its centre, leaving it
+        O.append(c); D.append(-tang + 0.1 * nrm); I.append(-1)
+    rows.append((np.array(O), unit(np.array(D)), np.array(I)))
+    fam.append(np.full(len(O), "e"))
+    O = np.concatenate([r[0] for r in rows]).astype(np.float32)
+    D = np.concatenate([np.asarray(r[1], dtype=np.float32) for r in rows]).astype(np.float32)
+    I = np.concatenate([r[2] for r in rows]).astype(np.int32)
+    w7 = np.concatenate([a, np.concatenate([f2u(O), f2u(D), I.view(np.uint32)[:, None]], axis=1)])
+    fam = np.concatenate(fam)
+    # ---- f: idle lanes between live ones, a wave of them, a ragged end
+    idx, live = [], []
+    for i in range(len(w7)):
+        idx.append(i); live.append(1)
+        if i % 4 == 1:
+            idx.append(i); live.append(0)
+    while len(idx) % 64:                                       # (up to a wave boundary, so that the idle rows below fill one wave exactly)
+        idx.append((len(idx) * 31) % len(w7)); live.append(len(idx) & 1)
+    for i in range(0, 64 + 37):
+        idx.append((i * 53) % len(w7)); live.append(0 if i < 64 else i & 1)
+    idx, live = np.array(idx), np.array(live, dtype=np.uint32)
+    words = np.ascontiguousarray(np.concatenate([w7[idx], live[:, None]], axis=1), dtype=np.uint32)
+    return words, fam[idx], live.astype(bool)
+
+
+def oracle_trace_detail(orc, words, quads, st_of_quads):
+    """oracle_trace, plus per row the accepted triangle of the quad (column 1, as the device ops report it) and the number of triangles whose float
+    edge values held a zero (the f64 fallback, src/geometry.cpp:57-67).  quads / st_of_quads: the scene's [nq][4][3] positions and [nq][4][2] texture
+    coordinates.  The triangle: tri0 of the hit quad is what was accepted iff, tested alone, it accepts with the hit's distance -- tri1 is tested only
+    after tri0 declined (src/geometry.cpp:128-139), and a later primitive never replaces an equal distance (strict '<')."""
+    lib = orc.lib
+    fl = u2f(words[:, :6])
+    ign = words[:, 6].view(np.int32)
+    out = np.zeros((len(words), 5), dtype=np.uint32)
+    f64 = np.zeros(len(words), dtype=np.int64)
+    st = ol.Stats()
+    hit, h0 = ol.Hit(), ol.Hit()
+    tri0 = []
+    for pos, tex in zip(quads, st_of_quads):
+        t = ol.Tri()
+        for k, v in enumerate((0, 1, 2)):
+            t.verts[k].pos = ol.V3(*[float(x) for x in pos[v]]); t.verts[k].st = ol.V2(*[float(x) for x in tex[v]])
+        tri0.append(t)
+    for i in range(len(words)):
+        ray = ol.Ray(ol.V3(*fl[i, :3]), ol.V3(*fl[i, 3:6]))
+        before = st.tri_f64
+        got = lib.orc_scene_intersect(orc.scene, C.byref(ray), C.byref(hit), int(ign[i]), C.byref(st))
+        f64[i] = st.tri_f64 - before
+        if got:
+            h0.prim = -1; h0.dist = float("inf")
+            first = lib.orc_tri_intersect(C.byref(tri0[hit.prim]), C.byref(ray), C.byref(h0), hit.prim, None)
+            out[i, 0] = hit.prim
+            out[i, 1] = 0 if (first and f2u([h0.dist])[0] == f2u([hit.dist])[0]) else 1
+            out[i, 2] = f2u([hit.dist])[0]; out[i, 3:5] = f2u([hit.st.x, hit.st.y])
+        else:
+            out[i, 0] = 0xFFFFFFFF; out[i, 2] = f2u([np.inf])[0]
+    return out, f64
+
+
 # ------------------------------------------------------------------------------------ rand_choice ----
 def rand_choice_inputs(seed=6, n=4000):
     """stream + n; the large n make Lemire's redraw (bits/uniform_int_dist.h) common (probability
