@@ -830,6 +830,75 @@ int ssx_spectral_compare_arrays(ssx_ctx* ctx, uint32_t width, uint32_t height, u
 int ssx_spectral_compare(ssx_ctx* ctx, const ssx_spectral_info_t* other_info, const double* SB, const double* QB, const uint32_t* NB, const uint8_t* labels /* [H][W] */,
                          uint32_t regions, double t2, double* DD, double* VV, double* X2, uint64_t* CC, uint64_t* NC, uint64_t* EX, float* diff, float* var);
 
+/* ---- Colour difference of two developments: CIELAB, dE*ab and CIEDE2000 maps with region figures (appended; same ABI version) ---------------------------
+ * Two developments of one render -- two observers, raw against denoised, a relight against a re-render -- differ somewhere; whether the difference can be SEEN
+ * is not a question for the bins (a 3-sigma difference in one bin may be invisible, a visible hue shift may be spread over bins so that none is significant)
+ * but for a colour-difference formula on the developed images.  The definition is this library's; tests/delta_e_ref.py restates it in numpy.
+ *
+ * INPUTS PER PIXEL.  Two XYZ triples A, B in binary32 (DEVELOP with C = 3 in the xyz space), two reference whites wA[3], wB[3] in binary64, every component
+ *   finite and > 0.  labels as in PROBE (R <= 32, 255: none); labels NULL: the whole image is region 0, R = 1.  Two thresholds t[2], finite and >= 0.
+ * LAB.  Per side, binary64, with x = (double)X / w[0], y = (double)Y / w[1], z = (double)Z / w[2]:
+ *       f(u) = cbrt(u) for u > 216.0 / 24389.0 ((6/29)^3), else u / (108.0 / 841.0) + 4.0 / 29.0            (108/841 = 3 (6/29)^2)
+ *       L = 116.0 * f(y) - 16.0        a = 500.0 * (f(x) - f(y))        b = 200.0 * (f(y) - f(z))
+ *   Negative and non-finite inputs go through as the arithmetic gives them (a NaN fails the comparison and takes the line).
+ * dE*ab.  dL = L_A - L_B, da = a_A - a_B, db = b_A - b_B;  dEab = sqrt((dL * dL + da * da) + db * db).
+ * dE00.  CIEDE2000 with kL = kC = kH = 1 as Sharma, Wu and Dalal state it (Color Res. Appl. 30 (2005) 21-30); 1 is side A, 2 is side B, angles in degrees, rad
+ *   = 0.017453292519943295, deg = 57.29577951308232, p7(c) = (((c * c) * (c * c)) * (c * c)) * c, K = 6103515625.0 (25^7):
+ *       C_i  = sqrt(a_i * a_i + b_i * b_i)                         m7 = p7(0.5 * (C_1 + C_2))              G = 0.5 * (1.0 - sqrt(m7 / (m7 + K)))
+ *       a'_i = (1.0 + G) * a_i                                     C'_i = sqrt(a'_i * a'_i + b_i * b_i)
+ *       h'_i = 0 where a'_i == 0 && b_i == 0; else h = atan2(b_i, a'_i) * deg, and h + 360.0 where h < 0.0
+ *       dL' = L_2 - L_1        dC' = C'_2 - C'_1        P = C'_1 * C'_2        d = h'_2 - h'_1        s = h'_1 + h'_2        far = |h'_1 - h'_2| > 180.0
+ *       dh' = 0.0 where P == 0.0;  else d where !far;  else d - 360.0 where d > 180.0;  else d + 360.0
+ *       dH' = (2.0 * sqrt(P)) * sin((0.5 * dh') * rad)
+ *       Lm = 0.5 * (L_1 + L_2)        Cm = 0.5 * (C'_1 + C'_2)
+ *       hm = s where P == 0.0;  else 0.5 * s where !far;  else 0.5 * (s + 360.0) where s < 360.0;  else 0.5 * (s - 360.0)
+ *       T  = (((1.0 - 0.17 * cos((hm - 30.0) * rad)) + 0.24 * cos((2.0 * hm) * rad)) + 0.32 * cos((3.0 * hm + 6.0) * rad)) - 0.20 * cos((4.0 * hm - 63.0) * rad)
+ *       u  = (hm - 275.0) / 25.0        dtheta = 30.0 * exp(-(u * u))        c7 = p7(Cm)        RC = 2.0 * sqrt(c7 / (c7 + K))
+ *       l  = (Lm - 50.0) * (Lm - 50.0)  SL = 1.0 + (0.015 * l) / sqrt(20.0 + l)        SC = 1.0 + 0.045 * Cm        SH = 1.0 + (0.015 * Cm) * T
+ *       RT = -sin((2.0 * dtheta) * rad) * RC
+ *       tl = dL' / SL        tc = dC' / SC        th = dH' / SH        dE00 = sqrt(((tl * tl + tc * tc) + th * th) + (RT * tc) * th)
+ *   The formula JUMPS at its branch points (P = 0, |h'_1 - h'_2| = 180, s = 360 where far): a last-place difference in atan2 there moves the result visibly.
+ * MAP.  de [height][width][2] float, row 0 = bottom: (float)dEab, (float)dE00 for every pixel, labelled or not.  Optionally lab [height][width][6] float: (float)
+ *   of L, a, b of A, then of B.  In the state entry pixels the context does not own read +0 in both and belong to no region.
+ * PER REGION r AND METRIC k (0: ab, 1: 00), over the pixels labelled r, with v = de[p][k] (the FLOAT), six arrays [R][2]:
+ *       NF = the number of pixels with v finite        NX = the number with v not finite                                              (uint64)
+ *       SUM = sum (double)v        SSQ = sum (double)v * (double)v   (the product is exact)        over the pixels with v finite, binary64
+ *       MAX = the largest finite v, +0 where there is none (float)        EX = the number of pixels with (double)v > t[k], strict: +inf counts, a NaN does not (uint64)
+ *   The order of the binary64 additions is PROBE's and part of the definition: within a row ascending i from +0.0, one partial per row; the row partials in
+ *   ascending j from +0.0; a row without a pixel of the region contributes its +0.0.
+ * DERIVED BY THE HOSTS (ssh_delta_e_derive, include/ssx_host.h), each NaN where its denominator is 0:
+ *       mean = SUM / NF        rms = sqrt(SSQ / NF)        max = MAX        exceed = EX / NF        coverage = NF / (NF + NX)
+ * THE WHITES set the absolute size of every dE: they are a viewing decision, like exposure, and the hosts' policy (include/ssx_host.h ssh_develop_white), not
+ *   this library's.  No chromatic adaptation is applied between wA and wB.
+ * TWO CLASSES OF GUARANTEE.  This is the first section that uses the device library's cbrt, atan2, sin, cos, exp and sqrt in binary64:
+ *   SAME BITS   the six region arrays are exactly the ordered reduction above of the map the same call returned -- a numpy walk over the returned de reproduces
+ *               them bit for bit; ssx_spectral_delta_e gives the bits of ssx_delta_e_images fed with ssx_spectral_develop's two outputs (for a context that owns
+ *               the whole image); several devices (each side developed by its owners, the pure entry on one) give the bits of one.
+ *   WITHIN A BOUND   de and lab against the numpy restatement in binary64: the device functions are accurate to a few ulp, not correctly rounded; the bound is
+ *               derived from their documented errors and the formula's partial derivatives in tests/test_delta_e_gpu.py.  Pairs within 1 degree of a branch
+ *               point of dE00 are outside the bound.
+ *
+ * ON THE DEVICE: ssx_delta_e_rows_kernel, one workgroup per image row, takes the row in chunks of 256 pixels, one lane per pixel, writes the maps, stages the two
+ * floats and the label in LDS and walks the chunk in ascending i with one lane per (quantity, metric), the accumulators in LDS indexed by the label;
+ * ssx_delta_e_reduce_kernel, one lane per (quantity, r, k), walks j in ascending order (MAX takes the larger, everything else adds).  No atomics.  With the
+ * feature unused nothing is allocated and nothing is launched. */
+
+/* The colour difference as a pure function of its arguments (needs no scene): xyz_a, xyz_b [height][width][3] floats.  SUM, SSQ (binary64), MAX (float), NF, NX, EX
+ * (uint64): [regions][2].  de [height][width][2], lab [height][width][6]: either may be NULL.  SSX_ERR_ARG, with ssx_last_error naming the field: a NULL required
+ * pointer, an empty or too large image, regions outside 1..32 (or not 1 with labels NULL), a label that is neither a region nor 255, a white component that is not
+ * finite and > 0, a threshold that is negative, infinite or NaN.  SSX_ERR_STATE: a render runs. */
+int ssx_delta_e_images(ssx_ctx* ctx, uint32_t width, uint32_t height, const float* xyz_a, const float* xyz_b, const double white_a[3], const double white_b[3],
+                       const uint8_t* labels /* [H][W] or NULL */, uint32_t regions, const double t[2], float* de /* [H][W][2] or NULL */, float* lab /* [H][W][6] or NULL */,
+                       double* SUM, double* SSQ, float* MAX, uint64_t* NF, uint64_t* NX, uint64_t* EX /* [R][2] */);
+/* Both sides developed from the context's own state by the develop kernels, weights_x [3][B] each, side x raw (denoised_x == 0) or denoised with `denoise`'s
+ * parameters (the filter runs once when both sides ask for it), into device staging; then the kernels of ssx_delta_e_images on that -- the same bits.  It reads
+ * only: image, sums, noise and spectral state stay as they are, so an ssx_render_continue afterwards leaves the bits of a render that was never asked.
+ * SSX_ERR_STATE with ssx_spectral_develop's reasons.  SSX_ERR_ARG: what ssx_delta_e_images refuses, NULL weights, and denoised_x != 0 with denoise == NULL. */
+int ssx_spectral_delta_e(ssx_ctx* ctx, const ssx_denoise_params* denoise /* or NULL */, int denoised_a, int denoised_b, const float* weights_a /* [3][B] */,
+                         const float* weights_b /* [3][B] */, const double white_a[3], const double white_b[3], const uint8_t* labels /* [H][W] or NULL */, uint32_t regions,
+                         const double t[2], float* de /* [H][W][2] or NULL */, float* lab /* [H][W][6] or NULL */,
+                         double* SUM, double* SSQ, float* MAX, uint64_t* NF, uint64_t* NX, uint64_t* EX /* [R][2] */);
+
 /* ---- Diagnostics for the parity tests (not part of the reference's interface) ---------------------
  * ssx_debug_eval runs one building block of the path kernel -- the same device function the kernel
  * inlines -- on n items, one per lane: `in` holds in_words 32-bit words per item, `out` receives

@@ -119,6 +119,15 @@ int ssh_compare_derive(uint32_t regions, uint32_t bins, const double* DD, const 
 int ssh_compare_save_csv(const char* path, uint32_t regions, uint32_t bins, float lambda_min, float bin_width, const double* DD, const double* VV, const double* X2,
                          const uint64_t* CC, const uint64_t* NC, const uint64_t* EX);
 
+/* The colour difference of two developments (ssx.h "Colour difference of two developments"; SUM, SSQ, MAX, NF, NX, EX: [regions][2] of ssx_delta_e_images /
+ * ssx_spectral_delta_e, metric 0 dE*ab, 1 dE00) as its readers take it: mean, rms, max, exceed and coverage [regions][2] as DERIVED BY THE HOSTS defines them,
+ * binary64, each NaN where its denominator is 0; any of the five outputs may be NULL. */
+int ssh_delta_e_derive(uint32_t regions, const double* SUM, const double* SSQ, const float* MAX, const uint64_t* NF, const uint64_t* NX, const uint64_t* EX,
+                       double* mean, double* rms, double* max, double* exceed, double* coverage);
+/* ... and as a text file: the line "region,metric,mean,rms,max,exceed,coverage,finite,nonfinite", then one line per region and metric ("ab", then "00") -- the
+ * five figures ("%.17g", "nan" for a NaN), NF and NX. */
+int ssh_delta_e_save_csv(const char* path, uint32_t regions, const double* SUM, const double* SSQ, const float* MAX, const uint64_t* NF, const uint64_t* NX, const uint64_t* EX);
+
 /* The spectral noise figure's totals (ssx.h "Spectral noise figure"; EV, EM, PP, PU: [bins] of ssx_spectral_noise / ssx_spectral_noise_reduce) as their readers
  * take them: *noise, *coverage and rel[bins] as DERIVED BY THE HOSTS defines them, binary64, in that order; any of the three outputs may be NULL. */
 int ssh_spectral_noise_derive(uint32_t bins, const double* EV, const double* EM, const uint64_t* PP, const uint64_t* PU, double* noise, double* coverage, double* rel);
@@ -140,6 +149,10 @@ int ssh_develop_weights(const char* data_dir, int observer, const ssh_spectrum_t
  * by to_spectrum -- exactly only when every emitter of the scene carries from_spectrum up to a scale (ssh_emitter_spectrum), and up to the variation of the ratio
  * inside a bin. */
 int ssh_relight_gain(const ssh_spectrum_t* from_spectrum, const ssh_spectrum_t* to_spectrum, uint32_t bins, float lambda_min, float lambda_step, double* gain);
+/* A reference white for the colour difference: the development, by weights [3][bins] (ssh_develop_weights, xyz space), of the illuminant's mean over each bin --
+ * out[c] = sum over b of (double)weights[c][b] * (integral of the illuminant over bin b / the bin's width), binary64, ascending b, integrated as ssh_relight_gain
+ * integrates.  illuminant NULL: equal energy.  Which white a comparison uses is the caller's viewing decision, like exposure: it sets the absolute size of every dE. */
+int ssh_develop_white(const float* weights, uint32_t bins, float lambda_min, float lambda_step, const ssh_spectrum_t* illuminant, double out[3]);
 /* *spectrum = index (in desc->spectra) of the emission spectrum that all emissive materials of the scene share up to a scale.  SSX_ERR_SCENE, with the reason in
  * ssh_last_error, when two of them differ or none is emissive: what the CLI's --develop-relight refuses. */
 int ssh_emitter_spectrum(const ssx_scene_desc* desc, uint32_t* spectrum);

@@ -123,6 +123,7 @@ HIP_SYMBOLS = ["ssx_create", "ssx_destroy", "ssx_upload_scene", "ssx_render_star
                "ssx_spectral_noise", "ssx_spectral_noise_reduce",
                "ssx_spectral_moments_import",
                "ssx_spectral_compare", "ssx_spectral_compare_arrays",
+               "ssx_delta_e_images", "ssx_spectral_delta_e",
                "ssx_debug_tile_mask", "ssx_debug_spectral_accumulate"]
 (SSX_SWEEP_RCP, SSX_SWEEP_SQRT, SSX_SWEEP_INVERSESQRT, SSX_SWEEP_SIN, SSX_SWEEP_COS, SSX_SWEEP_ACOS, SSX_SWEEP_DIV_PI,
  SSX_SWEEP_RCP64, SSX_SWEEP_DIV_PAIRS, SSX_SWEEP_ACOS_SIN, SSX_SWEEP_SIN_PROOF, SSX_SWEEP_COS_PROOF, SSX_SWEEP_ACOS_PROOF) = range(1, 14)
@@ -140,7 +141,8 @@ HOST_SYMBOLS = ["ssh_scene_create", "ssh_scene_create_ex", "ssh_scene_destroy", 
                 "ssh_checkpoint_save_spectral", "ssh_checkpoint_load_spectral", "ssh_spectral_merge",
                 "ssh_probe_derive", "ssh_probe_save_csv", "ssh_spectral_noise_derive", "ssh_spectral_noise_save_csv",
                 "ssh_checkpoint_save_moments", "ssh_checkpoint_load_moments", "ssh_moments_merge",
-                "ssh_compare_derive", "ssh_compare_save_csv"]
+                "ssh_compare_derive", "ssh_compare_save_csv",
+                "ssh_delta_e_derive", "ssh_delta_e_save_csv", "ssh_develop_white"]
 
 _hip = None
 _host = None
@@ -187,6 +189,9 @@ def host_lib():
         lib.ssh_spectral_noise_save_csv.argtypes = [C.c_char_p, C.c_uint32, C.c_float, C.c_float, vp, vp, vp, vp]
         lib.ssh_compare_derive.argtypes = [C.c_uint32, C.c_uint32] + [vp] * 12
         lib.ssh_compare_save_csv.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_float, C.c_float] + [vp] * 6
+        lib.ssh_delta_e_derive.argtypes = [C.c_uint32] + [vp] * 11
+        lib.ssh_delta_e_save_csv.argtypes = [C.c_char_p, C.c_uint32] + [vp] * 6
+        lib.ssh_develop_white.argtypes = [vp, C.c_uint32, C.c_float, C.c_float, C.POINTER(SshSpectrum), vp]
         lib.ssh_develop_weights.argtypes = [C.c_char_p, C.c_int, C.POINTER(SshSpectrum), C.c_uint32, C.POINTER(SshSpectrum), vp, C.c_int, C.c_uint32,
                                             C.c_float, C.c_float, vp, vp]
         lib.ssh_relight_gain.argtypes = [C.POINTER(SshSpectrum), C.POINTER(SshSpectrum), C.c_uint32, C.c_float, C.c_float, vp]
@@ -378,6 +383,9 @@ def hip_lib():
         if not override or hasattr(lib, "ssx_spectral_compare"):  # comparing two spectral renders: region sums and maps
             lib.ssx_spectral_compare.argtypes = [vp, C.POINTER(SsxSpectralInfo), vp, vp, vp, vp, C.c_uint32, C.c_double] + [vp] * 8
             lib.ssx_spectral_compare_arrays.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32] + [vp] * 7 + [C.c_uint32, C.c_double] + [vp] * 8
+        if not override or hasattr(lib, "ssx_delta_e_images"):  # the colour difference of two developments: maps and region figures
+            lib.ssx_delta_e_images.argtypes = [vp, C.c_uint32, C.c_uint32] + [vp] * 5 + [C.c_uint32] + [vp] * 9
+            lib.ssx_spectral_delta_e.argtypes = [vp, C.POINTER(SsxDenoiseParams), C.c_int, C.c_int] + [vp] * 5 + [C.c_uint32] + [vp] * 9
         if not override or hasattr(lib, "ssx_spectral_moments_import"):  # the second moments through checkpoint and resume
             lib.ssx_spectral_moments_import.argtypes = [vp, C.POINTER(SsxSpectralInfo), vp]
         if not override or hasattr(lib, "ssx_debug_tile_mask"):  # the camera-ray pre-trace's tile masks, read back

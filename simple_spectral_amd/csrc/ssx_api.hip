@@ -1523,3 +1523,4 @@ int ssx_kernel_info(ssx_ctx* ctx, int* vgprs, int* sgprs, int* lds_bytes, int* s
 #include "ssx_spectral_stats.hip"
 #include "ssx_spectral_noise.hip"
 #include "ssx_spectral_compare.hip"
+#include "ssx_delta_e.hip"

@@ -136,6 +136,18 @@ int develop_read_back(ssx_ctx* ctx, const DevelopBuffers& d, size_t pixels, uint
 	return SSX_OK;
 }
 
+// What a develop from the context's own state asks first (ssx_spectral_develop, ssx_spectral_delta_e): the refusals, then the device is the context's.
+int develop_state_ready(ssx_ctx* ctx, const char* what, bool denoised) {
+	if (!ctx->spectral_bins) return fail(ctx, SSX_ERR_STATE, fmt("%s: spectral output is off (ssx_set_spectral_bins)", what));
+	if (ctx->rendering.load()) return fail(ctx, SSX_ERR_STATE, "render in progress");
+	if (!ctx->sums.continuable || !ctx->sums.spectral_valid)
+		return fail(ctx, SSX_ERR_STATE, fmt("%s: the context holds no spectral bins: ", what) + (ctx->sums.continuable ? ctx->spectral_note : std::string("no render has accumulated any (ssx_render_start first)")));
+	if (ctx->done_spp.load() == 0u) return fail(ctx, SSX_ERR_STATE, fmt("%s: no sample has been accumulated yet (ssx_done_spp is 0)", what));
+	if (denoised) { if (const int rc = denoise_own_state_ready(ctx, what, true)) return rc; }
+	else if (const int rc = sums_ready(ctx, what)) return rc;
+	return SSX_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -166,14 +178,8 @@ int ssx_spectral_develop(ssx_ctx* ctx, const ssx_denoise_params* denoise, const 
 	if (rc) return rc;
 	ssx_denoise_params dp;
 	if (denoise && (rc = denoise_take_params(ctx, denoise, &dp))) return rc;
-	if (!ctx->spectral_bins) return fail(ctx, SSX_ERR_STATE, fmt("%s: spectral output is off (ssx_set_spectral_bins)", what));
-	if (ctx->rendering.load()) return fail(ctx, SSX_ERR_STATE, "render in progress");
-	if (!ctx->sums.continuable || !ctx->sums.spectral_valid)
-		return fail(ctx, SSX_ERR_STATE, fmt("%s: the context holds no spectral bins: ", what) + (ctx->sums.continuable ? ctx->spectral_note : std::string("no render has accumulated any (ssx_render_start first)")));
+	if ((rc = develop_state_ready(ctx, what, denoise != nullptr))) return rc;
 	const uint32_t done = ctx->done_spp.load();
-	if (done == 0u) return fail(ctx, SSX_ERR_STATE, fmt("%s: no sample has been accumulated yet (ssx_done_spp is 0)", what));
-	if (denoise) { if ((rc = denoise_own_state_ready(ctx, what, true))) return rc; }
-	else if ((rc = sums_ready(ctx, what))) return rc;
 	const ssx_render_params& p = ctx->cur;
 	const size_t pixels = (size_t)p.width * p.height;
 	const uint32_t B = ctx->spectral_bins;

@@ -89,6 +89,16 @@ std::vector<double> relight_gain(const Spectrum& from, const Spectrum& to, uint3
 	return g;
 }
 
+void develop_white(const float* weights, uint32_t bins, float lambda_min, float lambda_step, const Spectrum* illuminant, double out[3]) {
+	if (bins < 4 || bins > 64 || bins % 4) throw HostError{ -2, "develop white: the bin count must be a multiple of 4 up to 64" };
+	out[0] = out[1] = out[2] = 0.0;
+	for (uint32_t b = 0; b < bins; ++b) {
+		const double a = bin_edge(b, bins, lambda_min, lambda_step), z = bin_edge(b + 1, bins, lambda_min, lambda_step);
+		const double mean = illuminant ? table_integral(*illuminant, nullptr, a, z) / (z - a) : 1.0;
+		for (size_t c = 0; c < 3; ++c) out[c] = out[c] + static_cast<double>(weights[c * bins + b]) * mean;
+	}
+}
+
 uint32_t emitter_spectrum(const ssx_scene_desc& d) {
 	auto emissive = [&d](const ssx_spectrum& s) {
 		for (uint32_t i = 0; i < s.n; ++i) if (d.samples[s.offset + i] != 0.0f) return true;

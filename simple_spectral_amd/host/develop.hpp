@@ -24,6 +24,9 @@ std::vector<double> develop_weights(const std::vector<Spectrum>& responses, cons
                                     uint32_t bins, float lambda_min, float lambda_step);
 // [B]: integral of `to` over the bin / integral of `from`, 0 where the latter is 0
 std::vector<double> relight_gain(const Spectrum& from, const Spectrum& to, uint32_t bins, float lambda_min, float lambda_step);
+// The development of an illuminant's per-bin mean, the reference white of a colour difference (ssx.h "Colour difference of two developments"): out[c] = sum over b
+// of (double)weights[c][b] * (integral of the illuminant over bin b / the bin's width), binary64, ascending b from 0.0; illuminant NULL: equal energy, mean 1.
+void develop_white(const float* weights, uint32_t bins, float lambda_min, float lambda_step, const Spectrum* illuminant, double out[3]);
 
 // The emission spectrum all emissive materials of the scene share up to a scale: its index in desc.spectra.  Throws HostError (-3) when there is no emissive
 // material or when two of them carry different spectra -- a relighting by a gain per bin is then not exact.

@@ -270,6 +270,30 @@ int ssh_compare_save_csv(const char* path, uint32_t regions, uint32_t bins, floa
 	catch (const ssx::HostError& e) { return report(e); }
 }
 
+int ssh_delta_e_derive(uint32_t regions, const double* SUM, const double* SSQ, const float* MAX, const uint64_t* NF, const uint64_t* NX, const uint64_t* EX,
+                       double* mean, double* rms, double* max, double* exceed, double* coverage) {
+	if (!SUM || !SSQ || !MAX || !NF || !NX || !EX) { g_error = "NULL argument"; return SSX_ERR_ARG; }
+	ssx::delta_e_derive(regions, SUM, SSQ, MAX, NF, NX, EX, mean, rms, max, exceed, coverage);
+	return SSX_OK;
+}
+
+int ssh_delta_e_save_csv(const char* path, uint32_t regions, const double* SUM, const double* SSQ, const float* MAX, const uint64_t* NF, const uint64_t* NX, const uint64_t* EX) {
+	if (!path || !SUM || !SSQ || !MAX || !NF || !NX || !EX) { g_error = "NULL argument"; return SSX_ERR_ARG; }
+	try { ssx::save_delta_e_csv(path, regions, SUM, SSQ, MAX, NF, NX, EX); return SSX_OK; }
+	catch (const ssx::HostError& e) { return report(e); }
+}
+
+int ssh_develop_white(const float* weights, uint32_t bins, float lambda_min, float lambda_step, const ssh_spectrum_t* illuminant, double* out) {
+	if (!weights || !out || (illuminant && !illuminant->samples)) { g_error = "NULL argument"; return SSX_ERR_ARG; }
+	try {
+		ssx::Spectrum e;
+		if (illuminant) e = ssx::Spectrum(std::vector<float>(illuminant->samples, illuminant->samples + illuminant->n), illuminant->low, illuminant->high);
+		ssx::develop_white(weights, bins, lambda_min, lambda_step, illuminant ? &e : nullptr, out);
+		return SSX_OK;
+	} catch (const ssx::HostError& e) { return report(e); }
+	catch (const std::exception& e) { g_error = e.what(); return SSX_ERR_DATA; }
+}
+
 int ssh_develop_weights(const char* data_dir, int observer, const ssh_spectrum_t* responses, uint32_t channels, const ssh_spectrum_t* filter, const double* gain,
                         int space, uint32_t bins, float lambda_min, float lambda_step, float* weights, double* weights64) {
 	if (!weights) { g_error = "NULL argument"; return SSX_ERR_ARG; }

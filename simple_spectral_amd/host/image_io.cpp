@@ -346,4 +346,33 @@ void save_compare_csv(const std::string& path, size_t regions, size_t bins, floa
 	if (std::fclose(f) != 0 || !ok) throw HostError{ SSX_ERR_DATA, "Could not write \"" + path + "\"" };
 }
 
+void delta_e_derive(size_t regions, const double* SUM, const double* SSQ, const float* MAX, const uint64_t* NF, const uint64_t* NX, const uint64_t* EX,
+                    double* mean, double* rms, double* max, double* exceed, double* coverage) {
+	const double nan = std::numeric_limits<double>::quiet_NaN();
+	for (size_t e = 0; e < regions * 2; ++e) {
+		const double n = static_cast<double>(NF[e]);
+		const bool none = NF[e] == 0;
+		if (mean) mean[e] = none ? nan : SUM[e] / n;
+		if (rms) rms[e] = none ? nan : std::sqrt(SSQ[e] / n);
+		if (max) max[e] = static_cast<double>(MAX[e]);
+		if (exceed) exceed[e] = none ? nan : static_cast<double>(EX[e]) / n;
+		if (coverage) coverage[e] = (NF[e] + NX[e] == 0) ? nan : n / static_cast<double>(NF[e] + NX[e]);
+	}
+}
+
+void save_delta_e_csv(const std::string& path, size_t regions, const double* SUM, const double* SSQ, const float* MAX, const uint64_t* NF, const uint64_t* NX, const uint64_t* EX) {
+	const size_t n = regions * 2;
+	std::vector<double> mean(n), rms(n), max(n), exceed(n), coverage(n);
+	delta_e_derive(regions, SUM, SSQ, MAX, NF, NX, EX, mean.data(), rms.data(), max.data(), exceed.data(), coverage.data());
+	FILE* f = std::fopen(path.c_str(), "w");
+	if (!f) throw HostError{ SSX_ERR_DATA, "Could not open \"" + path + "\" for writing" };
+	bool ok = std::fprintf(f, "region,metric,mean,rms,max,exceed,coverage,finite,nonfinite\n") > 0;
+	for (size_t r = 0; r < regions; ++r) for (size_t k = 0; k < 2; ++k) {
+		const size_t e = r * 2 + k;
+		ok = std::fprintf(f, "%zu,%s,%s,%s,%s,%s,%s,%llu,%llu\n", r, k ? "00" : "ab", csv_number(mean[e]).c_str(), csv_number(rms[e]).c_str(), csv_number(max[e]).c_str(),
+		                  csv_number(exceed[e]).c_str(), csv_number(coverage[e]).c_str(), static_cast<unsigned long long>(NF[e]), static_cast<unsigned long long>(NX[e])) > 0 && ok;
+	}
+	if (std::fclose(f) != 0 || !ok) throw HostError{ SSX_ERR_DATA, "Could not write \"" + path + "\"" };
+}
+
 } // namespace ssx

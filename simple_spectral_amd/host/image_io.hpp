@@ -59,4 +59,12 @@ void compare_zmap(size_t n, const float* diff, const float* var, float* zmap);
 void save_compare_csv(const std::string& path, size_t regions, size_t bins, float lambda_min, float bin_width, const double* DD, const double* VV, const double* X2,
                       const uint64_t* CC, const uint64_t* NC, const uint64_t* EX);
 
+// The colour difference's region arrays (ssx.h "Colour difference of two developments"; [regions][2]: metric 0 dE*ab, 1 dE00) as their readers take them: mean =
+// SUM / NF, rms = sqrt(SSQ / NF), max = MAX, exceed = EX / NF, coverage = NF / (NF + NX), each NaN where its denominator is 0; any output may be nullptr.
+void delta_e_derive(size_t regions, const double* SUM, const double* SSQ, const float* MAX, const uint64_t* NF, const uint64_t* NX, const uint64_t* EX,
+                    double* mean, double* rms, double* max, double* exceed, double* coverage);
+// ... as a text file: the line "region,metric,mean,rms,max,exceed,coverage,finite,nonfinite", then one line per region and metric ("ab", "00"), the figures as
+// save_compare_csv writes them.
+void save_delta_e_csv(const std::string& path, size_t regions, const double* SUM, const double* SSQ, const float* MAX, const uint64_t* NF, const uint64_t* NX, const uint64_t* EX);
+
 } // namespace ssx

@@ -28,6 +28,14 @@
 // Demodulated denoising (include/ssx.h "Demodulated denoising"): --demodulate[=K] with --spectral-denoise runs that filter on illumination -- bins, image and
 // variance divided by the first-hit albedo per bin (K x K rays per pixel, K = 1, 2 or 4; default 2) before it and multiplied by it afterwards; the albedo part of
 // --denoise-sigma is ignored then.  --albedo-output=PATH.npy (needs --spectral-bins=N) writes those albedo bins, [height][width][N] float32.
+// Colour difference of two developments (include/ssx.h "Colour difference of two developments"), with --spectral-bins=N: --delta-e-output=PATH.npy writes the map
+// float32 [height][width][2] (dE*ab, dE00), --delta-e-csv=PATH.csv one line per region and metric "region,metric,mean,rms,max,exceed,coverage,finite,nonfinite".
+// Side A is the development --develop-observer / --develop-filter / --develop-relight / --spectral-denoise / --demodulate describe (these then do not need
+// --develop-output), side B the one --delta-e-observer / --delta-e-filter / --delta-e-relight / --delta-e-denoise describe.  The whites are host policy and a
+// viewing decision, like exposure -- they set the absolute size of every dE: chromaticity = the side's weights applied to its illuminant (the relight's, else the
+// scene's emitter spectrum, else D65), one scale for both so that side A's mean finite Y is 0.18 of its white's Y, or --delta-e-white-y=Y as side A's white's Y.
+// --delta-e-threshold=ab,00 (default 2.3,1): what "exceed" counts beyond.  Regions: the --probe rectangles, else the whole image.  Refused before anything
+// renders with --rgb, --tile-major, --libm=glibc-2.35, --resume, or without --spectral-bins.
 // Error bars for the bins (include/ssx.h "Spectral moments and region probes"), all with --spectral-bins=N: --spectral-variance-output=PATH.npy writes the variance
 // of every bin mean, float32 [height][width][N] (+inf where a sub-bin holds fewer than two samples); --probe=x0,y0,x1,y1 (half-open, row 0 = bottom; up to 32 of
 // them, region r = the r-th) with --probe-output=PATH.csv writes the pooled mean spectrum of each rectangle with its standard error, one line per region and bin:
@@ -56,6 +64,7 @@
 #include <array>
 #include <chrono>
 #include <csignal>
+#include <cmath>
 #include <cstring>
 #include <memory>
 #include <cstdio>
@@ -101,7 +110,11 @@ void print_usage() {
 		"    `--spectral-noise-target=<x> --spectral-bins=<n> --max-samples=<k> [--noise-step=<s>]` [`--spectral-noise-coverage=<c>`; default 0.99]\n"
 		"          [`--spectral-noise-region=<x0>,<y0>,<x1>,<y1>` ...] [`--spectral-noise-output=<file.csv>`] (render until the wavelength bins are converged)\n"
 		"    `--compare-to=<file.ckpt>` (needs `--spectral-bins=<n>`) [`--compare-output=<file.csv>`] [`--compare-map-output=<file.npy>`] [`--compare-threshold=<z>`; default 3]\n"
-		"          (the render against another one's checkpoint, bin by bin, with error bars and z-scores; regions: the `--probe` rectangles, else the whole image)\n");
+		"          (the render against another one's checkpoint, bin by bin, with error bars and z-scores; regions: the `--probe` rectangles, else the whole image)\n"
+		"    `--delta-e-output=<file.npy>` `--delta-e-csv=<file.csv>` (need `--spectral-bins=<n>`) [`--delta-e-observer=1931|2006`] [`--delta-e-filter=<file.csv>`] [`--delta-e-relight=<file.csv>`]\n"
+		"          [`--delta-e-denoise`] [`--delta-e-threshold=<ab>,<00>`; default 2.3,1] [`--delta-e-white-y=<Y>`; default: side A's mean Y is 0.18 of it]\n"
+		"          (CIELAB dE*ab and CIEDE2000 between two developments of the render: side A as `--develop-*`, `--spectral-denoise` and `--demodulate` say, side B as these say;\n"
+		"           the whites set the absolute size of every dE: a viewing decision, like exposure; regions: the `--probe` rectangles, else the whole image)\n");
 }
 
 struct ArgList {
@@ -195,6 +208,14 @@ struct Progressive { // the flags of the progressive modes
 	std::string spectral_noise_output;     // --spectral-noise-output: "" = none
 	std::string compare_to, compare_output, compare_map_output; // --compare-to / --compare-output / --compare-map-output: "" = none
 	double compare_threshold = 3.0;        // --compare-threshold: Z; the library takes t2 = Z * Z
+	// the colour difference of two developments (include/ssx.h "Colour difference of two developments"): side A is what --develop-*, --spectral-denoise and
+	// --demodulate describe, side B what these do
+	std::string delta_e_output, delta_e_csv, delta_e_filter, delta_e_relight; // --delta-e-output / --delta-e-csv / --delta-e-filter / --delta-e-relight: "" = none
+	int delta_e_observer = 0;              // --delta-e-observer: 0 = the render's
+	bool delta_e_denoise = false;          // --delta-e-denoise: side B from the filtered bins
+	double delta_e_threshold[2] = { 2.3, 1.0 }; // --delta-e-threshold=ab,00: the customary just-noticeable differences; user parameters
+	double delta_e_white_y = 0.0;          // --delta-e-white-y: 0 = side A's mean finite Y is 0.18 of the white's
+	bool delta_e() const { return !delta_e_output.empty() || !delta_e_csv.empty(); }
 	std::shared_ptr<ssx::Checkpoint> compare_other; // --compare-to's file, read when the arguments are checked
 };
 
@@ -285,6 +306,43 @@ void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progress
 		if (v == "1931") g->develop_observer = 1931; else if (v == "2006") g->develop_observer = 2006;
 		else { std::fprintf(stderr, "Invalid value for --develop-observer (1931|2006)!\n"); throw -2; }
 	}
+	if (a.take("--delta-e-output", "", &v)) g->delta_e_output = v;
+	if (a.take("--delta-e-csv", "", &v)) g->delta_e_csv = v;
+	if (a.take("--delta-e-filter", "", &v)) g->delta_e_filter = v;
+	if (a.take("--delta-e-relight", "", &v)) g->delta_e_relight = v;
+	bool delta_e_side = !g->delta_e_filter.empty() || !g->delta_e_relight.empty();
+	if (a.take("--delta-e-observer", "", &v)) {
+		if (v == "1931") g->delta_e_observer = 1931; else if (v == "2006") g->delta_e_observer = 2006;
+		else { std::fprintf(stderr, "Invalid value for --delta-e-observer (1931|2006)!\n"); throw -2; }
+		delta_e_side = true;
+	}
+	if (a.take("--delta-e-denoise", "", &v)) {
+		if (v != "--delta-e-denoise") { std::fprintf(stderr, "`--delta-e-denoise` does not take a value!\n"); throw -2; }
+		g->delta_e_denoise = delta_e_side = true;
+	}
+	if (a.take("--delta-e-threshold", "", &v)) {
+		bool ok = false;
+		try {
+			const size_t comma = v.find(',');
+			if (comma != std::string::npos) {
+				const std::string x = v.substr(0, comma), y = v.substr(comma + 1);
+				size_t u0 = 0, u1 = 0;
+				g->delta_e_threshold[0] = std::stod(x, &u0); g->delta_e_threshold[1] = std::stod(y, &u1);
+				ok = u0 == x.size() && u1 == y.size() && g->delta_e_threshold[0] >= 0.0 && g->delta_e_threshold[1] >= 0.0 && g->delta_e_threshold[0] < 1e300 && g->delta_e_threshold[1] < 1e300;
+			}
+		} catch (...) { ok = false; }
+		if (!ok) { std::fprintf(stderr, "Invalid value for --delta-e-threshold (<ab>,<00>, both finite and >= 0)!\n"); throw -2; }
+		delta_e_side = true;
+	}
+	if (a.take("--delta-e-white-y", "", &v)) {
+		try { size_t used = 0; g->delta_e_white_y = std::stod(v, &used); if (used != v.size() || !(g->delta_e_white_y > 0.0) || g->delta_e_white_y > 1e300) throw -2; }
+		catch (...) { std::fprintf(stderr, "Invalid value for --delta-e-white-y (finite and > 0)!\n"); throw -2; }
+		delta_e_side = true;
+	}
+	if (delta_e_side && !g->delta_e()) {
+		std::fprintf(stderr, "`--delta-e-observer`, `--delta-e-filter`, `--delta-e-relight`, `--delta-e-denoise`, `--delta-e-threshold` and `--delta-e-white-y` need `--delta-e-output=<file.npy>` or `--delta-e-csv=<file.csv>`!\n");
+		throw -2;
+	}
 	if (a.take("--spectral-bins", "", &v)) {
 		g->spectral_bins_given = true;
 		try { g->spectral_bins = to_pos(v); } catch (int) { g->spectral_bins = 0; }
@@ -313,10 +371,19 @@ void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progress
 		std::fprintf(stderr, "`--spectral-output` cannot be combined with `--tile-major`, `--rgb` or `--libm=glibc-2.35`!\n");
 		throw -2;
 	}
-	if (g->develop_output.empty() && (!g->develop_filter.empty() || !g->develop_relight.empty() || g->develop_observer)) {
+	if (g->develop_output.empty() && !g->delta_e() && (!g->develop_filter.empty() || !g->develop_relight.empty() || g->develop_observer)) {
 		std::fprintf(stderr, "`--develop-observer`, `--develop-filter` and `--develop-relight` need `--develop-output=<image>`!\n");
 		throw -2;
 	}
+	if (g->delta_e() && !g->spectral_bins_given) {
+		std::fprintf(stderr, "`--delta-e-output` and `--delta-e-csv` need `--spectral-bins=<n>`: they compare two developments of the render's wavelength bins!\n");
+		throw -2;
+	}
+	if (g->delta_e() && (o->tile_major || o->rgb_mode || o->libm != SSX_LIBM_BUILD)) {
+		std::fprintf(stderr, "`--delta-e-output` and `--delta-e-csv` cannot be combined with `--tile-major`, `--rgb` or `--libm=glibc-2.35`: such a render has no wavelength bins!\n");
+		throw -2;
+	}
+	if (g->delta_e() && !g->resume.empty()) { std::fprintf(stderr, "`--delta-e-output` and `--delta-e-csv` cannot be combined with `--resume`!\n"); throw -2; }
 	if (!g->develop_output.empty() && !g->spectral_bins_given) {
 		std::fprintf(stderr, "`--develop-output` needs `--spectral-bins=<n>`: it develops the wavelength bins of the render!\n");
 		throw -2;
@@ -351,7 +418,7 @@ void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progress
 	}
 	if (a.take("--spectral-denoise", "", &v)) {
 		if (v != "--spectral-denoise") { std::fprintf(stderr, "`--spectral-denoise` does not take a value!\n"); throw -2; }
-		if (g->spectral_output.empty() && g->develop_output.empty()) { std::fprintf(stderr, "`--spectral-denoise` needs `--spectral-output=<file.npy>`: it filters the bins written there!\n"); throw -2; }
+		if (g->spectral_output.empty() && g->develop_output.empty() && !g->delta_e()) { std::fprintf(stderr, "`--spectral-denoise` needs `--spectral-output=<file.npy>`: it filters the bins written there!\n"); throw -2; }
 		g->spectral_denoise = true;
 	}
 	if (a.take("--demodulate", "", &v)) {
@@ -366,8 +433,8 @@ void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progress
 		if (!g->spectral_bins_given || o->rgb_mode) { std::fprintf(stderr, "`--albedo-output` needs `--spectral-bins=<n>` and a spectral render: it writes the albedo of those bins!\n"); throw -2; }
 		g->albedo_output = v;
 	}
-	const bool filters = g->denoise || g->spectral_denoise; // both render for the filter: the noise estimate on, two batches at least
-	const char* const flag = g->denoise ? "--denoise" : "--spectral-denoise";
+	const bool filters = g->denoise || g->spectral_denoise || g->delta_e_denoise; // both render for the filter: the noise estimate on, two batches at least
+	const char* const flag = g->denoise ? "--denoise" : g->spectral_denoise ? "--spectral-denoise" : "--delta-e-denoise";
 	if (filters && o->spp < 2) { std::fprintf(stderr, "`%s` needs at least two samples per pixel: its variance estimate compares batches of samples!\n", flag); throw -2; }
 	if (filters && o->tile_major) { std::fprintf(stderr, "`%s` cannot be combined with `--tile-major`: only a render that walks through the samples takes batches!\n", flag); throw -2; }
 	if (filters) o->spp_per_launch = g->noise_step_given ? g->noise_step : (o->spp + 7) / 8; // at least two launches = two batches
@@ -391,7 +458,7 @@ void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progress
 		std::fprintf(stderr, "`--compare-output` and `--compare-map-output` need `--compare-to=<file.ckpt>`: they write that comparison!\n");
 		throw -2;
 	}
-	if ((g->probes.empty() != g->probe_output.empty()) && (g->compare_to.empty() || g->probes.empty())) { // (--compare-to takes its regions from --probe alone)
+	if ((g->probes.empty() != g->probe_output.empty()) && ((g->compare_to.empty() && !g->delta_e()) || g->probes.empty())) { // (--compare-to and --delta-e-* take their regions from --probe alone)
 		std::fprintf(stderr, "`--probe=<x0>,<y0>,<x1>,<y1>` and `--probe-output=<file.csv>` need each other!\n"); throw -2; }
 	if (g->moments()) {
 		const char* const flag = !g->variance_output.empty() ? "--spectral-variance-output" : !g->probe_output.empty() ? "--probe" : "--compare-to";
@@ -490,29 +557,57 @@ int main(int argc, char* argv[]) {
 		if (prog.denoise) options.output_path.clear(); // (render_wait writes the plain image there; the filtered one is written below)
 		ssx::Renderer renderer(options);
 		std::signal(SIGINT, on_sigint);
-		if (prog.denoise || prog.spectral_denoise) renderer.set_noise_estimate(true);
+		if (prog.denoise || prog.spectral_denoise || prog.delta_e_denoise) renderer.set_noise_estimate(true);
 		const bool spectral_stop = prog.spectral_noise_target >= 0.0;
-		if (!prog.spectral_output.empty() || !prog.develop_output.empty() || prog.moments() || spectral_stop) renderer.set_spectral_bins(prog.spectral_bins);
+		if (!prog.spectral_output.empty() || !prog.develop_output.empty() || prog.delta_e() || prog.moments() || spectral_stop) renderer.set_spectral_bins(prog.spectral_bins);
 		if (prog.moments() || (spectral_stop && !prog.resume.empty())) renderer.set_spectral_moments(true); // (before load_checkpoint: it takes Q up only with the moments on)
 		// what --develop-output applies, built (and refused) before the render: the observer's tables over the bins, times the filter, times the relighting gain
 		std::vector<float> develop_weights;
 		std::unique_ptr<ssx::ColorData> develop_color;
-		if (!prog.develop_output.empty()) {
+		// one development's weights: the observer's tables over the bins, times the filter, times the relighting gain (`relit` false: without the gain)
+		auto weights_of = [&](const ssx::ColorData& color, const std::string& filter_path, const std::string& relight_path, bool relit) {
 			const ssx_scene_desc& d = renderer.scene->desc();
-			develop_color = std::make_unique<ssx::ColorData>(options.data_dir, prog.develop_observer ? prog.develop_observer : options.observer);
-			develop_color->meng_output_transform = renderer.color->meng_output_transform;
 			const uint32_t B = static_cast<uint32_t>(prog.spectral_bins);
 			ssx::Spectrum filter;
-			if (!prog.develop_filter.empty()) filter = ssx::load_spectrum_csv(prog.develop_filter);
+			if (!filter_path.empty()) filter = ssx::load_spectrum_csv(filter_path);
 			std::vector<double> gain;
-			if (!prog.develop_relight.empty()) {
+			if (relit && !relight_path.empty()) {
 				const ssx_spectrum& e = d.spectra[ssx::emitter_spectrum(d)];
 				const ssx::Spectrum from(std::vector<float>(d.samples + e.offset, d.samples + e.offset + e.n), e.low, e.high);
-				gain = ssx::relight_gain(from, ssx::load_spectrum_csv(prog.develop_relight), B, d.lambda_min, d.lambda_step);
+				gain = ssx::relight_gain(from, ssx::load_spectrum_csv(relight_path), B, d.lambda_min, d.lambda_step);
 			}
-			const std::vector<double> w = ssx::develop_weights({ develop_color->std_obs_xbar, develop_color->std_obs_ybar, develop_color->std_obs_zbar },
-			                                                   prog.develop_filter.empty() ? nullptr : &filter, gain.empty() ? nullptr : gain.data(), nullptr, B, d.lambda_min, d.lambda_step);
-			develop_weights.assign(w.begin(), w.end()); // (rounded to binary32 here, once)
+			const std::vector<double> w = ssx::develop_weights({ color.std_obs_xbar, color.std_obs_ybar, color.std_obs_zbar },
+			                                                   filter_path.empty() ? nullptr : &filter, gain.empty() ? nullptr : gain.data(), nullptr, B, d.lambda_min, d.lambda_step);
+			return std::vector<float>(w.begin(), w.end()); // (rounded to binary32 here, once)
+		};
+		if (!prog.develop_output.empty() || prog.delta_e()) {
+			develop_color = std::make_unique<ssx::ColorData>(options.data_dir, prog.develop_observer ? prog.develop_observer : options.observer);
+			develop_color->meng_output_transform = renderer.color->meng_output_transform;
+			develop_weights = weights_of(*develop_color, prog.develop_filter, prog.develop_relight, true);
+		}
+		// side B of --delta-e-*, and both sides' whites up to the common scale (host policy: the chromaticity is the development, by the side's weights without a
+		// relighting gain, of the side's illuminant -- the relight's new one, else the scene's emitter spectrum where it has one, else D65)
+		std::vector<float> delta_e_weights;
+		double delta_e_white[2][3] = {};
+		if (prog.delta_e()) {
+			const ssx_scene_desc& d = renderer.scene->desc();
+			const uint32_t B = static_cast<uint32_t>(prog.spectral_bins);
+			const ssx::ColorData color_b(options.data_dir, prog.delta_e_observer ? prog.delta_e_observer : options.observer);
+			delta_e_weights = weights_of(color_b, prog.delta_e_filter, prog.delta_e_relight, true);
+			ssx::Spectrum scene_light;
+			try {
+				const ssx_spectrum& e = d.spectra[ssx::emitter_spectrum(d)];
+				scene_light = ssx::Spectrum(std::vector<float>(d.samples + e.offset, d.samples + e.offset + e.n), e.low, e.high);
+			} catch (const ssx::HostError&) { scene_light = ssx::load_spectrum_csv(options.data_dir + "/d65-300+5+780.csv"); }
+			const struct { const ssx::ColorData* color; const std::string* filter; const std::string* relight; } sides[2] = {
+				{ develop_color.get(), &prog.develop_filter, &prog.develop_relight }, { &color_b, &prog.delta_e_filter, &prog.delta_e_relight } };
+			for (int x = 0; x < 2; ++x) {
+				const std::vector<float> plain = weights_of(*sides[x].color, *sides[x].filter, *sides[x].relight, false);
+				const ssx::Spectrum light = sides[x].relight->empty() ? scene_light : ssx::load_spectrum_csv(*sides[x].relight);
+				ssx::develop_white(plain.data(), B, d.lambda_min, d.lambda_step, &light, delta_e_white[x]);
+				for (int c = 0; c < 3; ++c)
+					if (!(delta_e_white[x][c] > 0.0)) throw ssx::HostError{ SSX_ERR_ARG, "--delta-e: a side's white has a component that is not positive (its filter or illuminant leaves a channel dark)" };
+			}
 		}
 		if (prog.compare_other) { // the last refusal of --compare-to needs the scene: still before anything renders
 			const ssx_scene_desc& d = renderer.scene->desc();
@@ -596,6 +691,31 @@ int main(int argc, char* argv[]) {
 				std::fprintf(stderr, "Compared with \"%s\", region %zu: %llu comparable cells, %llu beyond z = %.6g.\n", prog.compare_to.c_str(), r, static_cast<unsigned long long>(cc),
 				             static_cast<unsigned long long>(ex), prog.compare_threshold);
 			}
+		}
+		if (prog.delta_e()) {
+			const size_t regions = prog.probes.empty() ? 1 : prog.probes.size(), pixels = options.res[0] * options.res[1];
+			const std::vector<uint8_t> labels = prog.probes.empty() ? std::vector<uint8_t>() : renderer.labels_from_rects(prog.probes);
+			const ssx::Renderer::DenoiseParams* const dn = (prog.spectral_denoise || prog.delta_e_denoise) ? &prog.denoise_params : nullptr;
+			const ssx::Renderer::DemodParams* const dm = prog.demodulate ? &prog.demod_params : nullptr;
+			// the whites' common scale: --delta-e-white-y is side A's white's Y; without it side A's mean finite Y is 0.18 of its white's Y
+			double scale = 0.0;
+			if (prog.delta_e_white_y > 0.0) scale = prog.delta_e_white_y / delta_e_white[0][1];
+			else {
+				const std::vector<float> xyz = renderer.develop(develop_weights.data(), 3, prog.spectral_denoise ? dn : nullptr, prog.spectral_denoise ? dm : nullptr);
+				double sum = 0.0; size_t n = 0;
+				for (size_t p = 0; p < pixels; ++p) if (std::isfinite(xyz[3 * p + 1])) { sum += static_cast<double>(xyz[3 * p + 1]); ++n; }
+				const double mean = n ? sum / static_cast<double>(n) : 0.0;
+				if (!(mean > 0.0)) throw ssx::HostError{ SSX_ERR_ARG, "--delta-e: side A's development has no positive mean Y to scale the whites by; give `--delta-e-white-y=<Y>`" };
+				scale = (mean / 0.18) / delta_e_white[0][1];
+			}
+			for (int x = 0; x < 2; ++x) for (int c = 0; c < 3; ++c) delta_e_white[x][c] *= scale;
+			const ssx::Renderer::DeltaESide side_a{ develop_weights.data(), prog.spectral_denoise }, side_b{ delta_e_weights.data(), prog.delta_e_denoise };
+			const ssx::Renderer::DeltaE e = renderer.delta_e(side_a, side_b, delta_e_white[0], delta_e_white[1], labels, regions, prog.delta_e_threshold, !prog.delta_e_output.empty(), dn,
+			                                                 (prog.spectral_denoise || prog.delta_e_denoise) ? dm : nullptr);
+			if (!prog.delta_e_csv.empty()) renderer.save_delta_e_csv(prog.delta_e_csv, e);
+			if (!prog.delta_e_output.empty()) renderer.save_delta_e_map(prog.delta_e_output, e);
+			for (size_t r = 0; r < regions; ++r)
+				std::fprintf(stderr, "Colour difference, region %zu: mean dE*ab %.4g, mean dE00 %.4g, max dE00 %.4g (whites' Y %.6g).\n", r, e.mean[2 * r], e.mean[2 * r + 1], e.max[2 * r + 1], delta_e_white[0][1]);
 		}
 		if (!prog.develop_output.empty()) { // X, Y, Z from the bins, the alpha of the render's image, then the store of --output
 			const std::vector<float> xyz = renderer.develop(develop_weights.data(), 3, prog.spectral_denoise ? &prog.denoise_params : nullptr, prog.demodulate ? &prog.demod_params : nullptr);

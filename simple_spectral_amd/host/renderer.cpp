@@ -32,7 +32,7 @@ void Framebuffer::save(const std::string& path) const { save_image(path, pixels_
 	X(create) X(destroy) X(upload_scene) X(render_start) X(render_stop) X(is_rendering) X(progress) X(render_wait) X(last_error) \
 	X(device_framebuffer) X(device_index) X(read_framebuffer) X(accumulate_peer) X(done_spp) X(done_tiles) X(reduce_rccl) \
 	X(render_continue) X(sums_export) X(sums_import) X(set_noise_estimate) X(noise_info) \
-	X(set_spectral_bins) X(spectral_read) X(spectral_import) X(set_spectral_moments) X(spectral_variance) X(spectral_moments_import) X(spectral_probe) X(probe_arrays) X(spectral_noise) X(spectral_noise_reduce) X(spectral_compare) X(spectral_compare_arrays) \
+	X(set_spectral_bins) X(spectral_read) X(spectral_import) X(set_spectral_moments) X(spectral_variance) X(spectral_moments_import) X(spectral_probe) X(probe_arrays) X(spectral_noise) X(spectral_noise_reduce) X(spectral_compare) X(spectral_compare_arrays) X(delta_e_images) X(spectral_delta_e) \
 	X(guides) X(denoise_images) X(denoise) X(denoise_channels) X(denoise_spectral) \
 	X(develop_images) X(spectral_develop) X(albedo_bins) X(denoise_spectral_demod) X(spectral_develop_demod)
 
@@ -573,6 +573,76 @@ Renderer::Compare Renderer::compare_spectral(const Checkpoint& other, const std:
 
 void Renderer::save_compare_csv(const std::string& path, const Compare& c) const {
 	ssx::save_compare_csv(path, c.regions, c.bins, c.lambda_min, c.bin_width, c.DD.data(), c.VV.data(), c.X2.data(), c.CC.data(), c.NC.data(), c.EX.data());
+}
+
+namespace {
+// the outputs of a colour difference, sized; what both routes hand to the library
+Renderer::DeltaE delta_e_result(size_t pixels, size_t regions, bool maps) {
+	Renderer::DeltaE r;
+	r.regions = regions;
+	const size_t n = regions * 2;
+	r.SUM.resize(n); r.SSQ.resize(n); r.MAX.resize(n); r.NF.resize(n); r.NX.resize(n); r.EX.resize(n);
+	if (maps) r.de.resize(pixels * 2);
+	return r;
+}
+void delta_e_finish(Renderer::DeltaE& r) {
+	const size_t n = r.regions * 2;
+	r.mean.resize(n); r.rms.resize(n); r.max.resize(n); r.exceed.resize(n); r.coverage.resize(n);
+	delta_e_derive(r.regions, r.SUM.data(), r.SSQ.data(), r.MAX.data(), r.NF.data(), r.NX.data(), r.EX.data(), r.mean.data(), r.rms.data(), r.max.data(), r.exceed.data(), r.coverage.data());
+}
+void delta_e_check_labels(const char* what, const std::vector<uint8_t>& labels, size_t pixels, size_t regions) {
+	if (!labels.empty() && labels.size() != pixels) throw HostError{ SSX_ERR_ARG, std::string(what) + ": labels is not [height][width]" };
+	if (regions < 1 || regions > 32 || (labels.empty() && regions != 1)) throw HostError{ SSX_ERR_ARG, std::string(what) + ": need 1..32 regions (1 without labels)" };
+}
+} // namespace
+
+Renderer::DeltaE Renderer::delta_e_images(const float* xyz_a, const float* xyz_b, const double white_a[3], const double white_b[3], const std::vector<uint8_t>& labels, size_t regions,
+                                          const double t[2], bool maps) {
+	wait_workers_();
+	const size_t pixels = options.res[0] * options.res[1];
+	delta_e_check_labels("delta_e_images", labels, pixels, regions);
+	DeltaE r = delta_e_result(pixels, regions, maps);
+	ssx_ctx* root = ctxs_[0];
+	check_(api_->delta_e_images(root, w32_(), h32_(), xyz_a, xyz_b, white_a, white_b, labels.empty() ? nullptr : labels.data(), static_cast<uint32_t>(regions), t,
+	                            maps ? r.de.data() : nullptr, nullptr, r.SUM.data(), r.SSQ.data(), r.MAX.data(), r.NF.data(), r.NX.data(), r.EX.data()), "ssx_delta_e_images", root);
+	delta_e_finish(r);
+	return r;
+}
+
+Renderer::DeltaE Renderer::delta_e(const DeltaESide& side_a, const DeltaESide& side_b, const double white_a[3], const double white_b[3], const std::vector<uint8_t>& labels,
+                                   size_t regions, const double t[2], bool maps, const DenoiseParams* denoise, const DemodParams* demod) {
+	wait_workers_();
+	if (!spectral_bins_) throw HostError{ SSX_ERR_STATE, "delta_e: spectral output is off (set_spectral_bins)" };
+	if (!side_a.weights || !side_b.weights) throw HostError{ SSX_ERR_ARG, "delta_e: a side without weights" };
+	const bool filtered = side_a.denoised || side_b.denoised;
+	if (filtered && !denoise) throw HostError{ SSX_ERR_ARG, "delta_e: a denoised side needs the filter's parameters (pass denoise)" };
+	if (demod && !filtered) throw HostError{ SSX_ERR_ARG, "delta_e: the demodulated mode is a mode of a denoised side" };
+	const size_t pixels = options.res[0] * options.res[1];
+	delta_e_check_labels("delta_e", labels, pixels, regions);
+	if (ctxs_.size() == 1 && !demod) {
+		DeltaE r = delta_e_result(pixels, regions, maps);
+		ssx_ctx* root = ctxs_[0];
+		const ssx_denoise_params dp = denoise ? to_abi(*denoise, false) : ssx_denoise_params{};
+		check_(api_->spectral_delta_e(root, filtered ? &dp : nullptr, side_a.denoised ? 1 : 0, side_b.denoised ? 1 : 0, side_a.weights, side_b.weights, white_a, white_b,
+		                              labels.empty() ? nullptr : labels.data(), static_cast<uint32_t>(regions), t, maps ? r.de.data() : nullptr, nullptr,
+		                              r.SUM.data(), r.SSQ.data(), r.MAX.data(), r.NF.data(), r.NX.data(), r.EX.data()), "ssx_spectral_delta_e", root);
+		delta_e_finish(r);
+		return r;
+	}
+	// each side by the develop's own route (several devices: every pixel from its owner; the demodulated filter), then the pure entry on device 0
+	const std::vector<float> xyz_a = develop(side_a.weights, 3, side_a.denoised ? denoise : nullptr, side_a.denoised ? demod : nullptr);
+	const std::vector<float> xyz_b = develop(side_b.weights, 3, side_b.denoised ? denoise : nullptr, side_b.denoised ? demod : nullptr);
+	return delta_e_images(xyz_a.data(), xyz_b.data(), white_a, white_b, labels, regions, t, maps);
+}
+
+void Renderer::save_delta_e_csv(const std::string& path, const DeltaE& d) const {
+	ssx::save_delta_e_csv(path, d.regions, d.SUM.data(), d.SSQ.data(), d.MAX.data(), d.NF.data(), d.NX.data(), d.EX.data());
+}
+
+void Renderer::save_delta_e_map(const std::string& path, const DeltaE& d) {
+	if (d.de.empty()) throw HostError{ SSX_ERR_ARG, "save_delta_e_map: the colour difference was made without its map" };
+	const size_t shape[3] = { options.res[1], options.res[0], 2 };
+	save_npy_f32(path, d.de.data(), shape, 3);
 }
 
 void Renderer::save_compare_map(const std::string& path, const Compare& c) {

@@ -205,6 +205,25 @@ public:
 	// demod (with denoise): the bins filtered in the demodulated mode -- one device: ssx_spectral_develop_demod; several: denoise_spectral's path as above.
 	std::vector<float> develop(const float* weights, size_t channels, const DenoiseParams* denoise = nullptr, const DemodParams* demod = nullptr);
 
+	// The colour difference of two developments of this render (include/ssx.h "Colour difference of two developments"): the six [regions][2] arrays (metric 0
+	// dE*ab, 1 dE00), the five derived figures (image_io.hpp delta_e_derive) and, with `maps`, de [height][width][2].  A side is its [3][bins] weights (xyz space)
+	// and whether the bins are filtered first (then `denoise`, and `demod` for the demodulated mode, say how -- for both sides alike).  labels empty: the whole
+	// image is region 0 and regions must be 1.  One device and no demodulated side: ssx_spectral_delta_e.  Otherwise each side through develop() -- every pixel
+	// from the device that owns it -- then ssx_delta_e_images on device 0: the same bits.  The whites are the caller's (they set the absolute size of every dE).
+	struct DeltaESide { const float* weights = nullptr; bool denoised = false; };
+	struct DeltaE {
+		size_t regions = 0;
+		std::vector<double> SUM, SSQ, mean, rms, max, exceed, coverage; std::vector<float> MAX; std::vector<uint64_t> NF, NX, EX;
+		std::vector<float> de;
+	};
+	DeltaE delta_e(const DeltaESide& side_a, const DeltaESide& side_b, const double white_a[3], const double white_b[3], const std::vector<uint8_t>& labels, size_t regions,
+	               const double t[2], bool maps = false, const DenoiseParams* denoise = nullptr, const DemodParams* demod = nullptr);
+	// ... of two XYZ images [height][width][3] of the options' size, as a pure function (ssx_delta_e_images on device 0)
+	DeltaE delta_e_images(const float* xyz_a, const float* xyz_b, const double white_a[3], const double white_b[3], const std::vector<uint8_t>& labels, size_t regions,
+	                      const double t[2], bool maps = false);
+	void save_delta_e_csv(const std::string& path, const DeltaE& d) const; // image_io.hpp save_delta_e_csv
+	void save_delta_e_map(const std::string& path, const DeltaE& d);       // de as a float32 .npy file [height][width][2], row 0 = bottom
+
 private:
 	struct Api;
 	std::unique_ptr<Api> api_;

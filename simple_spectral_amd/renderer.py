@@ -261,6 +261,44 @@ def save_compare_csv(path, lambda_min, bin_width, DD, VV, X2, CC, NC, EX):
     _host("ssh_compare_save_csv", os.fsencode(path), sums[0].shape[0], sums[0].shape[1], C.c_float(lambda_min), C.c_float(bin_width), *[a.ctypes.data for a in sums])
 
 
+DELTA_E_FIGURES = ("mean", "rms", "max", "exceed", "coverage")
+DELTA_E_THRESHOLDS = (2.3, 1.0)   # the customary just-noticeable differences of dE*ab and dE00: user parameters
+_DELTA_E_SUMS = ("SUM, SSQ, MAX, NF, NX, EX must all have shape [R, 2]", 2)
+_DELTA_E_TYPES = (np.float64, np.float64, np.float32, np.uint64, np.uint64, np.uint64)
+
+
+def delta_e_derive(SUM, SSQ, MAX, NF, NX, EX):
+    """ssh_delta_e_derive: a dict of float64 [R, 2] arrays (metric 0 dE*ab, 1 dE00) from the colour difference's six region arrays (include/ssx.h "Colour difference
+    of two developments") -- mean = SUM / NF, rms = sqrt(SSQ / NF), max = MAX, exceed = EX / NF, coverage = NF / (NF + NX); each NaN where its denominator is 0."""
+    sums = _same_shape("delta_e_derive", *_DELTA_E_SUMS, (SUM, SSQ, MAX, NF, NX, EX), _DELTA_E_TYPES)
+    if sums[0].shape[1] != 2:
+        raise ValueError("delta_e_derive: " + _DELTA_E_SUMS[0])
+    out = [np.zeros(sums[0].shape, dtype=np.float64) for _ in DELTA_E_FIGURES]
+    _host("ssh_delta_e_derive", sums[0].shape[0], *[a.ctypes.data for a in sums], *[a.ctypes.data for a in out])
+    return dict(zip(DELTA_E_FIGURES, out))
+
+
+def save_delta_e_csv(path, SUM, SSQ, MAX, NF, NX, EX):
+    """ssh_delta_e_save_csv (libssx_host.so): the line "region,metric,mean,rms,max,exceed,coverage,finite,nonfinite", then one line per region and metric."""
+    sums = _same_shape("save_delta_e_csv", *_DELTA_E_SUMS, (SUM, SSQ, MAX, NF, NX, EX), _DELTA_E_TYPES)
+    if sums[0].shape[1] != 2:
+        raise ValueError("save_delta_e_csv: " + _DELTA_E_SUMS[0])
+    _host("ssh_delta_e_save_csv", os.fsencode(path), sums[0].shape[0], *[a.ctypes.data for a in sums])
+
+
+def develop_white(weights, lambda_min, lambda_step, illuminant=None):
+    """ssh_develop_white: the reference white float64 [3] that weights [3, B] (develop_weights, xyz space) give the illuminant (samples, low, high) -- the
+    development of its mean over every bin; None: equal energy.  Which white a comparison uses, and at which scale, is a viewing decision like exposure: it sets
+    the absolute size of every dE."""
+    w = np.ascontiguousarray(weights, dtype=np.float32)
+    if w.ndim != 2 or w.shape[0] != 3:
+        raise ValueError("develop_white: weights must have shape [3, B]")
+    spec, keep = (None, None) if illuminant is None else _spectrum_arg(illuminant)
+    out = np.zeros(3, dtype=np.float64)
+    _host("ssh_develop_white", w.ctypes.data, w.shape[1], C.c_float(lambda_min), C.c_float(lambda_step), None if spec is None else C.byref(spec), out.ctypes.data)
+    return out
+
+
 def compare_other(other):
     """What a comparison takes of another render: `other` is what load_checkpoint_file_moments returns (nine values), or (SsxSpectralInfo, S, N, Q) -> (SsxSpectralInfo,
     S float64 [H, W, B], Q float64 [H, W, B], N uint32 [H, W, B / 4]).  ValueError when it carries no bins or no second moments."""
@@ -754,6 +792,60 @@ class Renderer:
                                                           labels.ctypes.data, R, float(threshold) * float(threshold) if t2 is None else float(t2),
                                                           *[a.ctypes.data for a in sums], None if diff is None else diff.ctypes.data, None if var is None else var.ctypes.data))
         return tuple(sums), diff, var
+
+    # ---- the colour difference of two developments (include/ssx.h "Colour difference of two developments") ----
+
+    def _delta_e_args(self, what, shape, white_a, white_b, labels, regions, thresholds, maps, lab):
+        H, W = shape
+        wa, wb = np.ascontiguousarray(white_a, dtype=np.float64), np.ascontiguousarray(white_b, dtype=np.float64)
+        t = np.ascontiguousarray(thresholds, dtype=np.float64)
+        if wa.shape != (3,) or wb.shape != (3,) or t.shape != (2,):
+            raise ValueError("%s: the whites must have shape [3], the thresholds [2]" % what)
+        if labels is None:
+            R = 1 if regions is None else int(regions)
+        else:
+            labels, R = self._regions(labels, (H, W), regions)
+        sums = [np.zeros((R, 2), dtype=d) for d in _DELTA_E_TYPES]
+        de = np.zeros((H, W, 2), dtype=np.float32) if maps else None
+        lab6 = np.zeros((H, W, 6), dtype=np.float32) if lab else None
+        ptr = lambda a: None if a is None else a.ctypes.data
+        return (wa, wb, labels, t, sums, de, lab6), [wa.ctypes.data, wb.ctypes.data, ptr(labels), R, t.ctypes.data, ptr(de), ptr(lab6)] + [a.ctypes.data for a in sums]
+
+    def delta_e_images(self, xyz_a, xyz_b, white_a, white_b, labels=None, regions=None, thresholds=DELTA_E_THRESHOLDS, maps=True, lab=False):
+        """ssx_delta_e_images: two XYZ images float32 [H, W, 3] (develop with xyz weights) under their whites float64 [3] -> ((SUM float64, SSQ float64, MAX float32,
+        NF uint64, NX uint64, EX uint64), each [R, 2] -- metric 0 dE*ab, 1 dE00 --, de float32 [H, W, 2] or None with maps=False, lab float32 [H, W, 6] or None).
+        labels as probe_raw takes them, None: the whole image is region 0.  thresholds: (ab, 00), what EX counts the pixels beyond."""
+        xa, xb = np.ascontiguousarray(xyz_a, dtype=np.float32), np.ascontiguousarray(xyz_b, dtype=np.float32)
+        if xa.ndim != 3 or xa.shape[2] != 3 or xb.shape != xa.shape:
+            raise ValueError("delta_e_images: xyz_a and xyz_b must have one shape [H, W, 3]")
+        keep, args = self._delta_e_args("delta_e_images", xa.shape[:2], white_a, white_b, labels, regions, thresholds, maps, lab)
+        self._check(self._lib.ssx_delta_e_images(self._ctx, xa.shape[1], xa.shape[0], xa.ctypes.data, xb.ctypes.data, *args))
+        return tuple(keep[4]), keep[5], keep[6]
+
+    def delta_e_raw(self, weights_a, weights_b, white_a, white_b, labels=None, regions=None, thresholds=DELTA_E_THRESHOLDS, denoise=None, denoised=(False, False),
+                    maps=True, lab=False):
+        """ssx_spectral_delta_e: the bins the context holds developed twice on the device, by weights_a and weights_b [3, B], side x raw or -- denoised[x] -- filtered
+        with `denoise`'s parameters (a dict as Renderer.develop takes it), and compared where they lie -> delta_e_images' result, the same bits.  Nothing the
+        context holds changes."""
+        W, H = self.options.res
+        wa, wb = np.ascontiguousarray(weights_a, dtype=np.float32), np.ascontiguousarray(weights_b, dtype=np.float32)
+        if wa.ndim != 2 or wa.shape[0] != 3 or wb.shape != wa.shape:
+            raise ValueError("delta_e: weights_a and weights_b must have one shape [3, B]")
+        if self._spectral_bins not in (0, wa.shape[1]):
+            raise ValueError("delta_e: weights for %d bins, the context holds %d" % (wa.shape[1], self._spectral_bins))
+        p = None if denoise is None else self._denoise_params(denoise.get("levels", 5), denoise.get("sigma_l", 1.0), denoise.get("sigma_a", 0.1))
+        keep, args = self._delta_e_args("delta_e", (H, W), white_a, white_b, labels, regions, thresholds, maps, lab)
+        self._check(self._lib.ssx_spectral_delta_e(self._ctx, None if p is None else C.byref(p), int(bool(denoised[0])), int(bool(denoised[1])),
+                                                   wa.ctypes.data, wb.ctypes.data, *args))
+        return tuple(keep[4]), keep[5], keep[6]
+
+    def delta_e(self, weights_a, weights_b, white_a, white_b, labels=None, regions=None, thresholds=DELTA_E_THRESHOLDS, denoise=None, denoised=(False, False)):
+        """The colour difference's derived figures -> a dict of float64 [R, 2] arrays mean, rms, max, exceed, coverage (delta_e_derive), with "finite" and
+        "nonfinite" (uint64 [R, 2]) and "map" (float32 [H, W, 2]: dE*ab, dE00)."""
+        sums, de, _ = self.delta_e_raw(weights_a, weights_b, white_a, white_b, labels, regions, thresholds, denoise, denoised)
+        out = delta_e_derive(*sums)
+        out.update(finite=sums[3], nonfinite=sums[4], map=de)
+        return out
 
     # ---- the spectral noise figure and the render loop that stops on it (include/ssx.h "Spectral noise figure") ----
 
