@@ -34,7 +34,7 @@ extern "C" {
  *      struct grew by 8 bytes) are new.  Added since without a change of existing entry points or structures (same version): ssx_units_info,
  *      ssx_rccl_probe (round 6); ssx_render_params.libm, appended (a caller with the struct_size before it gets SSX_LIBM_BUILD); the progressive
  *      rendering, spectral output, denoising, develop and demodulated-denoising entry points below; ssx_debug_tile_mask and SSX_DBG_TRACE_MASKED;
- *      ssx_debug_spectral_accumulate; SSX_DBG_TRACE_TOPO. */
+ *      ssx_debug_spectral_accumulate; SSX_DBG_TRACE_TOPO; ssx_debug_fold. */
 #define SSX_ABI_VERSION 2
 
 enum {
@@ -995,6 +995,41 @@ int ssx_debug_spectral_accumulate(ssx_ctx* ctx, uint32_t width, uint32_t height,
                                   float lambda_min, float lambda_step, uint32_t launches, const uint32_t* n_k /* [launches] */,
                                   const float* flux /* [H][W][K][4] */, const float* lambda_0 /* [H][W][K] */,
                                   double* sums /* [H][W][B] */, uint32_t* counts /* [H][W][M] */, double* q /* [H][W][B] or NULL */);
+/* The path kernel's FOLD on levels the caller supplies: what a render computes from a path's logged levels once every ray is traced -- the way back up of
+ * the recursion (renderer.cpp:147-255: per level emission + next-event term + ((radiance below * n_dot_l) * f_s) / pdf), the flat-field multiply, flux -> XYZ,
+ * alpha, and the pixel's binary64 sums (renderer.cpp:292-295) in ascending k.  A sample is one row of SSX_FOLD_ROW_WORDS 32-bit words, independent of the log
+ * layout (the oracle's orc_fold_sample is the same row):
+ *   lambda_0 | camera ray direction [3] | hit anything (0 / 1) | n = continued levels, 0..9 | 4 words not read | level 0 .. level 9, each
+ *   f_s[4], n_dot_l, pdf | flags | emission[4] | next-event term[4]
+ * Level n is the path's last; only the levels below it use f_s, n_dot_l, pdf; levels above n are not read.  flags: SSX_FOLD_EMISSION, SSX_FOLD_NEE (the level
+ * parked a shadow ray for this term), SSX_FOLD_NEE_VISIBLE (the ray reached its light).
+ * levels: [n_pixels][spp] rows, n_pixels a multiple of 64, spp in 1..8.  One wave takes 64 pixels: it writes the rows into a log region of the call's own with the
+ * functions the path kernel's write side calls, the wide or narrow queue entries' way, and folds one cohort per pass as a work unit's wave does -- the kernel twin
+ * (queue entries, libm, flux) a render of this context with `params` would run, and `params`' switches (no_flat_field_correction; width, height and spp are only
+ * checked).  order_seed: the order in which a cohort's log slots are handed out (any value gives the same results).  parked = 0: the samples are added as they are
+ * folded; 1: they are parked as a unit's are whose turn has not come, and added from there in ascending k.
+ * out_flux [n_pixels][spp][4]: the hero flux handed to flux -> XYZ (NULL, or with spectral output on: ssx_set_spectral_bins; otherwise SSX_ERR_STATE);
+ * out_xyza [n_pixels][spp][4]; out_sums [n_pixels][4] binary64, from +0.0.  Either may be NULL.  Touches none of the context's render state.
+ * SSX_ERR_ARG: n_pixels no multiple of 64 or above 2^20, spp outside 1..8, parked above 1, or so many pixels and samples that the call's level logs would reach
+ * 4 GiB (the kernels address them with 32-bit offsets; 582 bytes per pixel, cohort and sample of the cohort, twice). */
+#define SSX_FOLD_ROW_WORDS 160u
+#define SSX_FOLD_LAMBDA0 0u
+#define SSX_FOLD_CAM_DIR 1u
+#define SSX_FOLD_HIT 4u
+#define SSX_FOLD_N 5u
+#define SSX_FOLD_LEVEL0 10u
+#define SSX_FOLD_LEVEL_WORDS 15u
+#define SSX_FOLD_L_FS 0u
+#define SSX_FOLD_L_NDL 4u
+#define SSX_FOLD_L_PDF 5u
+#define SSX_FOLD_L_FLAGS 6u
+#define SSX_FOLD_L_EMISSION 7u
+#define SSX_FOLD_L_NEE 11u
+#define SSX_FOLD_EMISSION 1u
+#define SSX_FOLD_NEE 2u
+#define SSX_FOLD_NEE_VISIBLE 4u
+int ssx_debug_fold(ssx_ctx* ctx, const ssx_render_params* params, uint32_t n_pixels, uint32_t spp, const uint32_t* levels, uint32_t order_seed, uint32_t parked,
+                   float* out_flux, float* out_xyza, double* out_sums);
 
 #ifdef __cplusplus
 }

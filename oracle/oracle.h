@@ -216,6 +216,33 @@ void orc_scene_set_camera_dir(orc_scene*, const float dir[3]);
 void orc_render_sample(const orc_color*, const orc_scene*, orc_rng*, size_t i, size_t j,
                        size_t W, size_t H, int indirect_only, float out_xyza[4], orc_stats*);
 
+/* One sample's levels, independent of any log layout: what the recursion L() (renderer.cpp:147-255) knows on its way back up.  Every member
+ * is one 32-bit word, so a record is also a row of ORC_FOLD_WORDS words (tests/fold_cases.py builds them as such; include/ssx.h
+ * ssx_debug_fold takes the same rows).  level[n] is the path's last level; levels 0..n-1 continued, and only they use fs, n_dot_l, pdf. */
+#define ORC_FOLD_EMISSION 1u    /* the level adds emission[] (:171) */
+#define ORC_FOLD_NEE 2u         /* the level sampled a light from its front side: nee[] = ((emitted * n_dot_l) * f_s) / pdf (:216) ... */
+#define ORC_FOLD_NEE_VISIBLE 4u /* ... and the shadow ray reached it: only then is nee[] added */
+typedef struct {
+	float fs[4], n_dot_l, pdf; /* the continuation's factors (:247); pdf as used: 1 for a mirror, whose n_dot_l is 1 too (:238-241) */
+	uint32_t flags;
+	float emission[4], nee[4];
+} orc_fold_level;
+typedef struct {
+	float lambda_0, cam_dir[3];
+	uint32_t hit_anything, n;  /* n: continued levels, 0..ORC_MAX_DEPTH-1 */
+	float flux[4];             /* written by the recorder only: the hero flux behind the flat-field multiply (orc_fold_levels does not read it) */
+	orc_fold_level level[ORC_MAX_DEPTH];
+} orc_fold_sample;
+#define ORC_FOLD_WORDS (sizeof(orc_fold_sample) / 4u)
+/* Level recorder, off by default (NULL): while set, orc_render_sample on this thread writes the sample's levels to *rec -- the occluded
+ * next-event terms too, which L() itself never evaluates.  Recording changes no result, draw or counter. */
+void orc_debug_set_level_log(orc_fold_sample* rec);
+/* The fold of n_samples records: per sample the hero flux [4] behind the flat-field multiply (out_flux may be NULL) and {X, Y, Z, alpha}
+ * ({R, G, B, alpha} in RGB mode) -- orc_render_sample's arithmetic from the recursion's way back up on.  flags: bit 2 (4) = built
+ * without FLAT_FIELD_CORRECTION, as in orc_render_sample; the other bits decided the levels and are not read. */
+void orc_fold_levels(const orc_color*, const orc_scene*, const orc_fold_sample* samples, size_t n_samples, int flags,
+                     float* out_flux, float* out_xyza);
+
 /* Renderer::_render_pixel accumulation (renderer.cpp:292-296) with per-sample streams, for the
  * pixel rectangle [i0,i1)x[j0,j1); out is float4 XYZA per pixel, row 0 = bottom, full W*H
  * indexing (j*W+i).  sample range [k0,k1) of spp_total (the mean divides by spp_total).
@@ -223,6 +250,8 @@ void orc_render_sample(const orc_color*, const orc_scene*, orc_rng*, size_t i, s
 /* the reference's own one-thread ordering: thread 0's stream through the whole image in render_start's tile order (oracle_render.c) */
 int orc_render_reference_native(const orc_color*, const orc_scene*, size_t W, size_t H, size_t spp, int indirect_only,
                                 float* out_xyza, orc_rng* rng_out);
+/* the binary64 sums of one pixel that orc_render divides: X, Y, Z, alpha over samples 0..spp-1 of the pixel's streams (renderer.cpp:292-295; :301-303 in RGB mode) */
+void orc_pixel_sums(const orc_color*, const orc_scene*, uint64_t seed, size_t i, size_t j, size_t W, size_t H, size_t spp, int indirect_only, double out[4]);
 int orc_render(const orc_color*, const orc_scene*, uint64_t seed, size_t W, size_t H,
                size_t i0, size_t j0, size_t i1, size_t j1, size_t spp, int indirect_only,
                int nthreads, float* out_xyza, orc_stats* stats_or_null);

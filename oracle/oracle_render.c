@@ -18,7 +18,12 @@ typedef struct {
 	int hit_anything;
 	orc_stats* st;
 	unsigned interactions;
+	orc_fold_sample* lg; /* orc_debug_set_level_log: the sample's levels are written here on the way down (NULL: off) */
 } path_ctx;
+
+/* The level recorder (oracle.h): off unless a test points it at a record. */
+static __thread orc_fold_sample* orc_tls_level_log = NULL;
+void orc_debug_set_level_log(orc_fold_sample* rec) { orc_tls_level_log = rec; }
 
 /* renderer.cpp:147-255: the recursive radiance lambda `L`.  (-DORACLE_REFERENCE_SHAPED, oracle_scene.c: the lambda lives in a
  * std::function and calls itself through it -- an indirect call per level that the compiler cannot see through.) */
@@ -33,6 +38,10 @@ static orc_hero radiance_L(path_ctx* c, const orc_ray* ray, int last_was_delta, 
 	orc_hero radiance = { { 0, 0, 0, 0 } };
 	const float pi = 3.14159265358979323846f;
 
+	/* recorder: this call is level `depth`, so far the path's last, with no term and no continuation */
+	orc_fold_level* const lv = (c->lg && depth < ORC_MAX_DEPTH) ? &c->lg->level[depth] : NULL;
+	if (lv) { memset(lv, 0, sizeof *lv); c->lg->n = depth; }
+
 	orc_hit hitrec;
 	if (orc_scene_intersect(c->sc, ray, &hitrec, ignore, c->st)) {
 		c->hit_anything = 1;
@@ -44,6 +53,7 @@ static orc_hero radiance_L(path_ctx* c, const orc_ray* ray, int last_was_delta, 
 			orc_material_emission(c->cd, mtl, c->lambda_0, em); /* material.hpp:101-103 */
 			if (c->st) c->st->spectrum_lookups++;
 			for (int i = 0; i < 4; ++i) radiance.v[i] += em[i];
+			if (lv) { lv->flags |= ORC_FOLD_EMISSION; memcpy(lv->emission, em, sizeof em); }
 		}
 
 		if (depth + 1u < ORC_MAX_DEPTH) { /* :178 */
@@ -75,6 +85,22 @@ static orc_hero radiance_L(path_ctx* c, const orc_ray* ray, int last_was_delta, 
 						}
 						/* radiance += emitted * n_dot_l * f_s / shad_pdf (:216) */
 						for (int i = 0; i < 4; ++i) radiance.v[i] += ((emitted[i] * n_dot_l) * f_s[i]) / shad_pdf;
+						if (lv) {
+							lv->flags |= ORC_FOLD_NEE | ORC_FOLD_NEE_VISIBLE;
+							for (int i = 0; i < 4; ++i) lv->nee[i] = ((emitted[i] * n_dot_l) * f_s[i]) / shad_pdf;
+						}
+					} else if (lv) {
+						/* recorder only: the term the occluded ray would have added (L() adds nothing and counts nothing here), so that a
+						 * record also says what a fold that keeps term and visibility apart has to leave out */
+						const orc_material* lm = &c->sc->materials[c->sc->prims[light].material];
+						float emitted[4], f_s[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
+						orc_material_emission(c->cd, lm, c->lambda_0, emitted);
+						if (mtl->kind == ORC_MTL_LAMBERTIAN) {
+							orc_material_albedo(c->cd, c->sc, mtl, hitrec.st, c->lambda_0, f_s, NULL);
+							for (int i = 0; i < 4; ++i) f_s[i] /= pi;
+						}
+						lv->flags |= ORC_FOLD_NEE;
+						for (int i = 0; i < 4; ++i) lv->nee[i] = ((emitted[i] * n_dot_l) * f_s[i]) / shad_pdf;
 					}
 				}
 			}
@@ -103,6 +129,7 @@ static orc_hero radiance_L(path_ctx* c, const orc_ray* ray, int last_was_delta, 
 				}
 				if (n_dot_l > 0.0f) {
 					orc_ray ray_next = { hit_pos, w_i };
+					if (lv) { memcpy(lv->fs, f_s, sizeof f_s); lv->n_dot_l = n_dot_l; lv->pdf = pdf_w_i; }
 					orc_hero Lr = ORC_CALL_L(c, &ray_next, 0, depth + 1u, hitrec.prim);
 					for (int i = 0; i < 4; ++i) radiance.v[i] += ((Lr.v[i] * n_dot_l) * f_s[i]) / pdf_w_i;
 				}
@@ -144,7 +171,8 @@ void orc_render_sample(const orc_color* cd, const orc_scene* sc, orc_rng* rng, s
 	float lambda_0 = cd->rgb_mode ? 0.0f : cd->lambda_min + orc_rand_1f(rng) * cd->lambda_step;
 
 	/* `indirect_only` carries two flags: bit 0 = Options::indirect_only, bit 1 = build without ELS */
-	path_ctx c = { cd, sc, rng, lambda_0, indirect_only & 1, !(indirect_only & 2), 0, st, 0 };
+	path_ctx c = { cd, sc, rng, lambda_0, indirect_only & 1, !(indirect_only & 2), 0, st, 0, orc_tls_level_log };
+	if (c.lg) { c.lg->lambda_0 = lambda_0; c.lg->cam_dir[0] = camera_ray_dir.x; c.lg->cam_dir[1] = camera_ray_dir.y; c.lg->cam_dir[2] = camera_ray_dir.z; c.lg->n = 0; }
 	orc_ray ray_camera = { sc->camera.pos, camera_ray_dir };
 	orc_hero rad = ORC_CALL_L(&c, &ray_camera, 1, 0u, -1);
 
@@ -161,6 +189,7 @@ void orc_render_sample(const orc_color* cd, const orc_scene* sc, orc_rng* rng, s
 	orc_specradflux_to_ciexyz_hero(cd, rad.v, lambda_0, xyz);
 	out_xyza[0] = xyz[0]; out_xyza[1] = xyz[1]; out_xyza[2] = xyz[2];
 	out_xyza[3] = c.hit_anything ? 1.0f : 0.0f;
+	if (c.lg) { c.lg->hit_anything = (uint32_t)c.hit_anything; memcpy(c.lg->flux, rad.v, sizeof c.lg->flux); }
 	if (st) {
 		st->samples++;
 		st->hits += (uint64_t)c.hit_anything;
@@ -171,10 +200,45 @@ void orc_render_sample(const orc_color* cd, const orc_scene* sc, orc_rng* rng, s
 	orc_tls_stats = tls_saved;
 }
 
+/* The way back up of L() (renderer.cpp:147-255) and the end of _render_sample (:262-277) on levels that are given instead of traced: what
+ * orc_render_sample computes once every ray is known.  Level s->n is the path's last; the levels below it continue.  Each level's
+ * radiance starts from 0 (:149), takes its emission (:171) and its next-event term where the light is visible (:216), in that order, and then
+ * the indirect term ((L(next) * n_dot_l) * f_s) / pdf (:247) -- the statements of radiance_L above, in their order. */
+void orc_fold_levels(const orc_color* cd, const orc_scene* sc, const orc_fold_sample* samples, size_t n_samples, int flags,
+                     float* out_flux, float* out_xyza) {
+	for (size_t q = 0; q < n_samples; ++q) {
+		const orc_fold_sample* s = &samples[q];
+		const unsigned n = s->n < ORC_MAX_DEPTH ? s->n : ORC_MAX_DEPTH - 1u;
+		orc_hero below = { { 0, 0, 0, 0 } };
+		for (unsigned d = n + 1u; d-- > 0u;) {
+			const orc_fold_level* lv = &s->level[d];
+			orc_hero radiance = { { 0, 0, 0, 0 } }; /* :149 */
+			if (lv->flags & ORC_FOLD_EMISSION) for (int i = 0; i < 4; ++i) radiance.v[i] += lv->emission[i]; /* :171 */
+			if ((lv->flags & ORC_FOLD_NEE) && (lv->flags & ORC_FOLD_NEE_VISIBLE)) for (int i = 0; i < 4; ++i) radiance.v[i] += lv->nee[i]; /* :216 */
+			if (d < n) for (int i = 0; i < 4; ++i) radiance.v[i] += ((below.v[i] * lv->n_dot_l) * lv->fs[i]) / lv->pdf; /* :247 */
+			below = radiance;
+		}
+		orc_hero rad = below;
+		if (flags & 4) { /* :264-265, as in orc_render_sample */
+			const orc_v3 cd_ = sc->camera.dir;
+			const float tx = s->cam_dir[0] * cd_.x, ty = s->cam_dir[1] * cd_.y, tz = s->cam_dir[2] * cd_.z;
+			const float d = tx + ty + tz;
+			for (int k = 0; k < ORC_NWAVE; ++k) rad.v[k] = rad.v[k] * d;
+		}
+		float xyz[3];
+		if (cd->rgb_mode) { xyz[0] = rad.v[0]; xyz[1] = rad.v[1]; xyz[2] = rad.v[2]; } /* :274-276 */
+		else orc_specradflux_to_ciexyz_hero(cd, rad.v, s->lambda_0, xyz);
+		if (out_flux) memcpy(out_flux + 4 * q, rad.v, 4 * sizeof(float));
+		out_xyza[4 * q + 0] = xyz[0]; out_xyza[4 * q + 1] = xyz[1]; out_xyza[4 * q + 2] = xyz[2];
+		out_xyza[4 * q + 3] = s->hit_anything ? 1.0f : 0.0f;
+	}
+}
+
 /* renderer.cpp:278-299 with the per-sample seeding contract; returns float(avg) XYZA */
-static void render_pixel(const orc_color* cd, const orc_scene* sc, uint64_t seed, size_t i, size_t j,
-                         size_t W, size_t H, size_t spp, int indirect_only, float out[4], orc_stats* st) {
-	double avg[4] = { 0, 0, 0, 0 };
+/* the accumulation of _render_pixel alone (:292-295, :301-303): the pixel's four binary64 sums over samples 0..spp-1, before the division */
+static void pixel_sums(const orc_color* cd, const orc_scene* sc, uint64_t seed, size_t i, size_t j,
+                       size_t W, size_t H, size_t spp, int indirect_only, double avg[4], orc_stats* st) {
+	avg[0] = avg[1] = avg[2] = avg[3] = 0;
 	for (size_t k = 0; k < spp; ++k) {
 		orc_rng rng;
 		orc_seed_sample(seed, (uint64_t)(j * W + i), (uint64_t)k, &rng);
@@ -183,6 +247,14 @@ static void render_pixel(const orc_color* cd, const orc_scene* sc, uint64_t seed
 		if (cd->rgb_mode) for (int c = 0; c < 4; ++c) avg[c] += (double)s[c];            /* :301-303 */
 		else for (int c = 0; c < 4; ++c) avg[c] += (double)(s[c] * 0.001f);              /* :292-294 */
 	}
+}
+void orc_pixel_sums(const orc_color* cd, const orc_scene* sc, uint64_t seed, size_t i, size_t j, size_t W, size_t H, size_t spp, int indirect_only, double out[4]) {
+	pixel_sums(cd, sc, seed, i, j, W, H, spp, indirect_only, out, NULL);
+}
+static void render_pixel(const orc_color* cd, const orc_scene* sc, uint64_t seed, size_t i, size_t j,
+                         size_t W, size_t H, size_t spp, int indirect_only, float out[4], orc_stats* st) {
+	double avg[4];
+	pixel_sums(cd, sc, seed, i, j, W, H, spp, indirect_only, avg, st);
 	if (cd->rgb_mode) { for (int c = 0; c < 4; ++c) out[c] = (float)(avg[c] / (double)spp); return; } /* :304 avg /= double(spp) */
 	double sc_ = 1000.0 / (double)spp;
 	for (int c = 0; c < 4; ++c) out[c] = (float)(avg[c] * sc_);

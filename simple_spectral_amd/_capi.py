@@ -124,7 +124,11 @@ HIP_SYMBOLS = ["ssx_create", "ssx_destroy", "ssx_upload_scene", "ssx_render_star
                "ssx_spectral_moments_import",
                "ssx_spectral_compare", "ssx_spectral_compare_arrays",
                "ssx_delta_e_images", "ssx_spectral_delta_e",
-               "ssx_debug_tile_mask", "ssx_debug_spectral_accumulate"]
+               "ssx_debug_tile_mask", "ssx_debug_spectral_accumulate", "ssx_debug_fold"]
+# ssx_debug_fold: a sample's row of levels (include/ssx.h)
+SSX_FOLD_ROW_WORDS, SSX_FOLD_LAMBDA0, SSX_FOLD_CAM_DIR, SSX_FOLD_HIT, SSX_FOLD_N, SSX_FOLD_LEVEL0, SSX_FOLD_LEVEL_WORDS = 160, 0, 1, 4, 5, 10, 15
+SSX_FOLD_L_FS, SSX_FOLD_L_NDL, SSX_FOLD_L_PDF, SSX_FOLD_L_FLAGS, SSX_FOLD_L_EMISSION, SSX_FOLD_L_NEE = 0, 4, 5, 6, 7, 11
+SSX_FOLD_EMISSION, SSX_FOLD_NEE, SSX_FOLD_NEE_VISIBLE = 1, 2, 4
 (SSX_SWEEP_RCP, SSX_SWEEP_SQRT, SSX_SWEEP_INVERSESQRT, SSX_SWEEP_SIN, SSX_SWEEP_COS, SSX_SWEEP_ACOS, SSX_SWEEP_DIV_PI,
  SSX_SWEEP_RCP64, SSX_SWEEP_DIV_PAIRS, SSX_SWEEP_ACOS_SIN, SSX_SWEEP_SIN_PROOF, SSX_SWEEP_COS_PROOF, SSX_SWEEP_ACOS_PROOF) = range(1, 14)
 # ssx_debug_eval ops (include/ssx.h)
@@ -392,6 +396,8 @@ def hip_lib():
             lib.ssx_debug_tile_mask.argtypes = [vp, C.POINTER(SsxRenderParams), vp]
         if not override or hasattr(lib, "ssx_debug_spectral_accumulate"):  # the bin and moment kernels on the caller's sample records
             lib.ssx_debug_spectral_accumulate.argtypes = [vp] + [C.c_uint32] * 6 + [C.c_float, C.c_float, C.c_uint32] + [vp] * 6
+        if not override or hasattr(lib, "ssx_debug_fold"):  # the path kernel's fold on the caller's levels
+            lib.ssx_debug_fold.argtypes = [vp, C.POINTER(SsxRenderParams), C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, vp, vp]
         lib.ssx_kernel_variant.argtypes = [vp]
         lib.ssx_kernel_name.argtypes = [vp]
         lib.ssx_kernel_name.restype = C.c_char_p

@@ -1386,6 +1386,78 @@ int ssx_debug_tile_mask(ssx_ctx* ctx, const ssx_render_params* p_in, uint32_t* o
 	return SSX_OK;
 }
 
+// The fold on the caller's levels (csrc/ssx_debug.hip debug_fold_body): the twin a render of this context with these parameters runs -- queue entries as
+// pick_queue finds them for that render's path kernel, its libm, its _flux twin while spectral output is on -- in buffers of the call's own: sample arrays,
+// level logs and sums.  Neither the context's arrays nor its libm, plan or continuable state are touched.
+int ssx_debug_fold(ssx_ctx* ctx, const ssx_render_params* p_in, uint32_t n_pixels, uint32_t spp, const uint32_t* levels, uint32_t order_seed, uint32_t parked,
+                   float* out_flux, float* out_xyza, double* out_sums) {
+	if (!ctx || !levels) return SSX_ERR_ARG;
+	ssx_render_params pp;
+	int rc = begin_render(ctx, p_in, &pp, "render in progress");
+	if (rc) return rc;
+	if (n_pixels == 0 || (n_pixels & 63u) || n_pixels > (1u << 20)) return fail(ctx, SSX_ERR_ARG, "ssx_debug_fold: n_pixels must be a multiple of 64, at most 2^20");
+	if (spp == 0 || spp > SSX_MAX_UNIT_KS) return fail(ctx, SSX_ERR_ARG, "ssx_debug_fold: spp must be 1..8, the samples per pixel of a work unit");
+	if (parked > 1u) return fail(ctx, SSX_ERR_ARG, "ssx_debug_fold: parked is 0 or 1");
+	const bool flux = ctx->spectral_bins && pp.libm == SSX_LIBM_BUILD && !ctx->rgb_mode; // (ready_to_launch)
+	if (ctx->spectral_bins && !flux) return fail(ctx, SSX_ERR_STATE, "ssx_debug_fold: spectral output is on, and it renders spectral scenes with the default libm only");
+	if (out_flux && !flux) return fail(ctx, SSX_ERR_STATE, "ssx_debug_fold: out_flux needs spectral output (ssx_set_spectral_bins)");
+	SSX_HIP(ctx, hipSetDevice(ctx->device));
+	if ((rc = wait_device_pending(ctx))) return rc;
+	// the queue entries of that render's path kernel (pick_queue looks at the kernels of ctx->variant: lent for the question, and put back)
+	const uint32_t variant = flux ? (uint32_t)ssx_jit::kVariantFlux : pp.libm, variant_was = ctx->variant;
+	uint32_t qw = 0;
+	ctx->variant = variant;
+	rc = pick_queue(ctx, ctx->path_blob_words, &qw, nullptr);
+	ctx->variant = variant_was;
+	if (rc) return rc;
+	const bool narrow = qw == SSX_QUEUE_WORDS_NARROW;
+	const uint32_t n_tiles = n_pixels / 64u, cohorts = (spp + SSX_COHORT_KS - 1u) / SSX_COHORT_KS;
+	const size_t n_rec = (size_t)n_pixels * spp, log_records = (size_t)n_tiles * 2u * cohorts * SSX_COHORT_RECORDS;
+	const size_t row_bytes = n_rec * SSX_FOLD_ROW_WORDS * 4u;
+	// (the kernels address the logs with 32-bit byte offsets: ensure_logs)
+	if (log_records * SSX_LOG_BYTES_PER_RECORD >= ((size_t)1 << 32)) return fail(ctx, SSX_ERR_ARG, "ssx_debug_fold: level logs beyond 4 GiB for this many pixels and samples; fold fewer pixels per call");
+	DeviceBuffer d_rows, d_samples, d_logs, d_sums;
+	if (d_rows.reserve(row_bytes) != hipSuccess || d_samples.reserve(n_rec * SSX_BYTES_PER_SAMPLE_FLUX) != hipSuccess ||
+	    d_logs.reserve(log_records * SSX_LOG_BYTES_PER_RECORD) != hipSuccess || d_sums.reserve((size_t)n_tiles * 256u * sizeof(double)) != hipSuccess) {
+		(void)hipGetLastError();
+		return fail(ctx, SSX_ERR_DEVICE, "out of device memory (ssx_debug_fold)");
+	}
+	SSX_HIP(ctx, hipMemcpy(d_rows.ptr, levels, row_bytes, hipMemcpyHostToDevice));
+	SsxKernelArgs a{};
+	a.blob = ctx->d_blob.as<uint32_t>(); a.blob_words = ctx->path_blob_words;
+	a.rgb_mode = ctx->rgb_mode ? 1u : 0u;
+	a.no_flat_field = pp.no_flat_field_correction ? 1u : 0u;
+	a.keep_samples = 1u; // {X, Y, Z, alpha} of every sample stays in ray[]: where a parked sample waits, too
+	a.unit_cohorts = cohorts; a.group_spp = spp; a.n_records = n_rec;
+	bind_arrays(a, d_samples.as<uint8_t>(), n_rec, d_logs.as<uint8_t>(), log_records, flux);
+	a.accum = d_sums.as<double>();
+	static const void* const kFoldKernels[ssx_jit::kVariants][2] = {
+		{ (const void*)ssx_debug_fold_kernel, (const void*)ssx_debug_fold_kernel_nq }, { (const void*)ssx_debug_fold_kernel_glibc, (const void*)ssx_debug_fold_kernel_nq_glibc },
+		{ (const void*)ssx_debug_fold_kernel_flux, (const void*)ssx_debug_fold_kernel_nq_flux } };
+	const uint32_t* d_in = d_rows.as<uint32_t>();
+	void* args[] = { &a, &d_in, (void*)&n_tiles, &spp, &order_seed, &parked };
+	const size_t lds = staged_blob_lds(a.blob_words) + 4u * SSX_WAVE_COUNTER_WORDS * 4u; // the four waves' hand-over words behind the blob, where the path kernel's queues begin
+	SSX_HIP(ctx, hipLaunchKernel(kFoldKernels[variant][narrow], dim3((n_tiles + 3u) / 4u), dim3(256), args, lds, ctx->stream));
+	SSX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	std::vector<float4> rec(n_rec);
+	std::vector<double> sums((size_t)n_tiles * 256u);
+	// device order [tile][k][pixel of the tile] -> the caller's [pixel][k]
+	auto gather = [&](const void* d_src, float* out) -> int {
+		SSX_HIP(ctx, hipMemcpy(rec.data(), d_src, n_rec * sizeof(float4), hipMemcpyDeviceToHost));
+		for (uint32_t t = 0; t < n_tiles; ++t) for (uint32_t k = 0; k < spp; ++k) for (uint32_t l = 0; l < 64u; ++l)
+			memcpy(out + 4u * (((size_t)t * 64u + l) * spp + k), &rec[((size_t)t * spp + k) * 64u + l], sizeof(float4));
+		return SSX_OK;
+	};
+	if (out_flux && (rc = gather(a.flux, out_flux))) return rc;
+	if (out_xyza && (rc = gather(a.ray, out_xyza))) return rc;
+	if (out_sums) {
+		SSX_HIP(ctx, hipMemcpy(sums.data(), d_sums.ptr, sums.size() * sizeof(double), hipMemcpyDeviceToHost));
+		for (uint32_t t = 0; t < n_tiles; ++t) for (uint32_t l = 0; l < 64u; ++l) for (uint32_t c = 0; c < 4u; ++c)
+			out_sums[((size_t)t * 64u + l) * 4u + c] = sums[(size_t)t * 256u + c * 64u + l];
+	}
+	return SSX_OK;
+}
+
 #ifdef SSX_LANESTAT // profiling build only (tools/lanestat.py)
 int ssx_lanestat(unsigned long long* out, int reset) {
 	if (reset) { unsigned long long z[2 * SSX_NSTAT] = {}; return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_lanestat), z, sizeof z); }

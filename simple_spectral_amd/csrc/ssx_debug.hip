@@ -223,6 +223,105 @@ SSX_DEBUG_TRACE_TOPO_KERNEL(ssx_debug_trace_cornell_kernel, 1)
 SSX_DEBUG_TRACE_TOPO_KERNEL(ssx_debug_trace_plane_kernel, 2)
 #undef SSX_DEBUG_TRACE_TOPO_KERNEL
 
+// ssx_debug_fold (include/ssx.h): the path kernel's fold -- resolve_records, in the loop of unit_fold -- on levels the caller supplies.  One wave per 64
+// pixels ("tile"), n_k samples per pixel, one cohort of SSX_COHORT_KS samples per pixel per pass.  The wave first writes the rows' levels into its own log
+// regions, the way the path kernel's lanes do: through the store_* / *_word functions of csrc/ssx_kernels.hip that path_step, shadow_flush and the end of a
+// path call, addressed through a LogRef as theirs; then it hands over to itself as the path kernel's lanes do (wave_release / wave_acquire and unit_fold's two
+// fences) and folds cohort by cohort.  A kernel of its own per (queue entries, libm, flux) as the path kernels are: ssx_debug_eval_kernel keeps its registers.
+//   rows [tile][pixel][k][SSX_FOLD_ROW_WORDS] (include/ssx.h); a.ray / a.st / a.flux: [tile][k][pixel] as a render's; a.accum [tile][component][pixel]
+// Slots: the samples of a cohort take their level-entry and next-event slots one sample after the other in the order of a permutation of the cohort's 128
+// places made from order_seed; bit 7 of the seed turns the order of a sample's own levels round.  Which slot an entry gets must not matter to the fold.
+__device__ __forceinline__ uint32_t fold_rank(uint32_t rc, uint32_t seed) { return (rc * ((seed << 1) | 1u) + (seed >> 8)) & (SSX_COHORT_RECORDS - 1u); }
+template <bool NARROW, bool GLIBC, bool FLUX>
+__device__ __forceinline__ void debug_fold_body(const SsxKernelArgs& a, const uint32_t* rows, uint32_t n_tiles, uint32_t n_k, uint32_t order_seed, uint32_t parked) {
+	static_assert((SSX_COHORT_RECORDS & (SSX_COHORT_RECORDS - 1u)) == 0u, "fold_rank permutes a power of two");
+	uint32_t* const lds_words = stage_lds<GLIBC>(a);
+	Lds L; L.w = lds_words;
+	const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+	const uint32_t wave_slot = blockIdx.x * 4u + wave; // = the tile
+	if (wave_slot >= n_tiles) return;
+	uint32_t* const cnt = lds_words + a.blob_words + wave * SSX_WAVE_COUNTER_WORDS; // the wave's hand-over word lives behind 4 * SSX_UNIT_COHORTS counters, as in the path kernel
+	const uint32_t rec_base = wave_slot * n_k * 64u;
+	const uint32_t* const tile_rows = rows + (size_t)wave_slot * 64u * n_k * SSX_FOLD_ROW_WORDS;
+	LogRef lg; lg.cnt = cnt; lg.wave_base = wave_slot * 2u * a.unit_cohorts;
+	for (uint32_t kq = 0; kq < n_k; kq += SSX_COHORT_KS) {
+		const uint32_t cohort = kq / SSX_COHORT_KS, ways = min(SSX_COHORT_KS, n_k - kq);
+		for (uint32_t s = 0; s < ways; ++s) {
+			const uint32_t rc = s * 64u + lane, my_rank = fold_rank(rc, order_seed);
+			// slots in front of this sample's: the entries of the cohort's samples that come before it in the seed's order
+			uint32_t fs0 = 0, ne0 = 0;
+			for (uint32_t o = 0; o < ways * 64u; ++o) {
+				if (fold_rank(o, order_seed) >= my_rank) continue;
+				const uint32_t* y = tile_rows + ((size_t)(o & 63u) * n_k + kq + (o >> 6)) * SSX_FOLD_ROW_WORDS;
+				const uint32_t on = min(y[SSX_FOLD_N], SSX_MAX_FRAMES);
+				fs0 += on;
+				for (uint32_t l = 0; l <= on; ++l) ne0 += (y[SSX_FOLD_LEVEL0 + l * SSX_FOLD_LEVEL_WORDS + SSX_FOLD_L_FLAGS] & SSX_FOLD_NEE) ? 1u : 0u;
+			}
+			const uint32_t* x = tile_rows + ((size_t)lane * n_k + kq + s) * SSX_FOLD_ROW_WORDS;
+			const uint32_t n = min(x[SSX_FOLD_N], SSX_MAX_FRAMES), r = rec_base + (kq + s) * 64u + lane;
+			uint32_t n_ne = 0;
+			for (uint32_t l = 0; l <= n; ++l) n_ne += (x[SSX_FOLD_LEVEL0 + l * SSX_FOLD_LEVEL_WORDS + SSX_FOLD_L_FLAGS] & SSX_FOLD_NEE) ? 1u : 0u;
+			lg.tagw = log_tag_word(cohort, 0u, a.unit_cohorts, s); // unit tag 0
+			const bool turned = ((order_seed >> 7) & 1u) != 0u;
+			uint32_t prev_slot = SSX_NO_SLOT, tail = 0u, ne_seen = 0u;
+			for (uint32_t l = 0; l <= n; ++l) { // what path_step stores for level l, the flush for its shadow ray, and the path's end for the last level
+				const uint32_t* v = x + SSX_FOLD_LEVEL0 + l * SSX_FOLD_LEVEL_WORDS;
+				const uint32_t flags = v[SSX_FOLD_L_FLAGS];
+				uint32_t level_word = level_word_none();
+				if (flags & SSX_FOLD_EMISSION) {
+					const float e[4] = { f(v[SSX_FOLD_L_EMISSION]), f(v[SSX_FOLD_L_EMISSION + 1]), f(v[SSX_FOLD_L_EMISSION + 2]), f(v[SSX_FOLD_L_EMISSION + 3]) };
+					store_emission(a, lg, l, r, e);
+					level_word = level_word_emission(level_word);
+				}
+				if (flags & SSX_FOLD_NEE) {
+					const float c[4] = { f(v[SSX_FOLD_L_NEE]), f(v[SSX_FOLD_L_NEE + 1]), f(v[SSX_FOLD_L_NEE + 2]), f(v[SSX_FOLD_L_NEE + 3]) };
+					const uint32_t nslot = ne0 + (turned ? n_ne - 1u - ne_seen : ne_seen);
+					const uint32_t ni = nee_index(lg, nslot);
+					if (NARROW) store_parked_term(a, ni, c);
+					store_shadow_outcome<NARROW>(a, ni, (flags & SSX_FOLD_NEE_VISIBLE) != 0u, c[0], c[1], c[2], c[3]);
+					level_word = level_word_nee(level_word, nslot);
+					++ne_seen;
+				}
+				if (l < n) {
+					const float fs[4] = { f(v[SSX_FOLD_L_FS]), f(v[SSX_FOLD_L_FS + 1]), f(v[SSX_FOLD_L_FS + 2]), f(v[SSX_FOLD_L_FS + 3]) };
+					const uint32_t slot = fs0 + (turned ? n - 1u - l : l);
+					store_level_entry(a, lg, slot, fs, f(v[SSX_FOLD_L_NDL]), f(v[SSX_FOLD_L_PDF]), prev_slot, level_word);
+					prev_slot = slot;
+				} else tail = tail_word(level_word, x[SSX_FOLD_HIT] ? 1u : 0u, n, prev_slot);
+			}
+			// the sample's records as the generate kernel and the path's end leave them: {camera ray, lambda_0}, {lambda_0, tail word, final stream}
+			a.ray[r] = make_float4(f(x[SSX_FOLD_CAM_DIR]), f(x[SSX_FOLD_CAM_DIR + 1]), f(x[SSX_FOLD_CAM_DIR + 2]), f(x[SSX_FOLD_LAMBDA0]));
+			a.st[r] = make_uint4(x[SSX_FOLD_LAMBDA0], tail, 0u, 0u);
+			wave_release(cnt);
+		}
+	}
+	// unit_fold from here on: the hand-over, then one cohort per pass
+	wave_acquire(cnt);
+	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+	double acc[4] = { 0.0, 0.0, 0.0, 0.0 };
+	for (uint32_t kq = 0; kq < n_k; kq += SSX_COHORT_KS) {
+		const uint32_t log_rec = log_region(a, wave_slot, 0u, kq / SSX_COHORT_KS);
+		resolve_records<SSX_COHORT_KS, NARROW, FLUX>(L, a, rec_base + kq * 64u + lane, 64u, min(SSX_COHORT_KS, n_k - kq), log_rec * SSX_MAX_FRAMES, log_rec * SSX_MAX_LEVELS, lane, acc, parked != 0u);
+	}
+	// a parked unit's samples are added by the wave whose turn reaches them, in ascending k (sums_chain)
+	if (parked)
+		for (uint32_t kq = 0; kq < n_k; ++kq) add_staged_sample(a.rgb_mode != 0u, acc, a.ray + (rec_base + kq * 64u + lane));
+	double* const px = a.accum + (size_t)wave_slot * 256u + lane;
+	px[0] = acc[0]; px[64] = acc[1]; px[128] = acc[2]; px[192] = acc[3];
+}
+#define SSX_DEBUG_FOLD_KERNEL(name, narrow, glibc, flux) \
+	extern "C" __global__ void __launch_bounds__(256) name(SsxKernelArgs a, const uint32_t* rows, uint32_t n_tiles, uint32_t n_k, uint32_t order_seed, uint32_t parked) { \
+		debug_fold_body<narrow, glibc, flux>(a, rows, n_tiles, n_k, order_seed, parked); \
+	}
+SSX_DEBUG_FOLD_KERNEL(ssx_debug_fold_kernel, false, false, false)
+SSX_DEBUG_FOLD_KERNEL(ssx_debug_fold_kernel_nq, true, false, false)
+SSX_DEBUG_FOLD_KERNEL(ssx_debug_fold_kernel_glibc, false, true, false)
+SSX_DEBUG_FOLD_KERNEL(ssx_debug_fold_kernel_nq_glibc, true, true, false)
+SSX_DEBUG_FOLD_KERNEL(ssx_debug_fold_kernel_flux, false, false, true)
+SSX_DEBUG_FOLD_KERNEL(ssx_debug_fold_kernel_nq_flux, true, false, true)
+#undef SSX_DEBUG_FOLD_KERNEL
+
 // ---- libm = glibc-2.35: the same diagnostics for the _glibc kernels, in kernels of their own (they stage the LDS table of the _glibc
 // kernels, stage_lds<true>: the glibc coefficients over ssx_fmath.h's arc-cosine slots)
 // Digest word of one input and its result (include/ssx.h SSX_SWEEP_GLIBC_*; tests/glibc_math_check.c computes the same on the host).

@@ -947,6 +947,10 @@ struct LogRef {
 	// the lane's sample within its cohort: k in the cohort << 6 | pixel of the tile
 	__device__ __forceinline__ uint32_t rc(uint32_t rec_index) const { return ((tagw >> 8) << 6) | (rec_index & 63u); }
 };
+// the tag word of a sample (LogRef::tagw): its cohort within the unit, the unit's tag, and its place k_in_cohort among its pixel's samples of the cohort
+__device__ __forceinline__ uint32_t log_tag_word(uint32_t cohort, uint32_t tag, uint32_t unit_cohorts, uint32_t k_in_cohort) {
+	return cohort | (tag << 2) | ((tag * unit_cohorts + cohort) << 3) | (k_in_cohort << 8);
+}
 // first log record of cohort `cohort` of the unit with tag `tag` this wave has in flight (ssx_blob.h)
 __device__ __forceinline__ uint32_t log_region(const SsxKernelArgs& a, uint32_t wave_slot, uint32_t tag, uint32_t cohort) {
 	return ((wave_slot * 2u + tag) * a.unit_cohorts + cohort) * SSX_COHORT_RECORDS;
@@ -960,6 +964,39 @@ __device__ __forceinline__ void wave_release(uint32_t* cnt) { (void)__hip_atomic
 __device__ __forceinline__ void wave_acquire(uint32_t* cnt) { (void)__hip_atomic_load(cnt + 4u * SSX_UNIT_COHORTS, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WAVEFRONT); }
 __device__ __forceinline__ uint32_t log_append(const LogRef& lg, uint32_t which) {
 	return __hip_atomic_fetch_add(lg.cnt + 2u * lg.group() + which, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+}
+// The WRITE SIDE of the level logs, one statement each: what path_step, shadow_flush and the end of a path store for the fold (resolve_records) to
+// read, and the words they pack (ssx_blob.h).  ssx_debug_fold_kernel (csrc/ssx_debug.hip) writes a caller's levels through the same functions, so the
+// layout stands in one place.
+// what a level's entry (or the path's tail word) says about the level: slot of its next-event term << 13 | has an emission term << 26
+__device__ __forceinline__ uint32_t level_word_none() { return SSX_NO_SLOT << 13; }
+__device__ __forceinline__ uint32_t level_word_emission(uint32_t w) { return w | (1u << 26); }
+__device__ __forceinline__ uint32_t level_word_nee(uint32_t w, uint32_t nslot) { return (w & ~(SSX_NO_SLOT << 13)) | (nslot << 13); }
+// the tail word of a path that ends at level `depth` (ssx_blob.h): hit_anything | the level has an emission term << 1 | depth << 2 | slot of the
+// entry of level depth-1 << 6 | slot of the level's next-event term << 19
+__device__ __forceinline__ uint32_t tail_word(uint32_t level_word, uint32_t hit_anything, uint32_t depth, uint32_t prev_slot) {
+	return hit_anything | ((level_word >> 26) << 1) | (depth << 2) | (prev_slot << 6) | ((level_word >> 13) << 19);
+}
+// the emission term of the lane's level `depth`
+__device__ __forceinline__ void store_emission(const SsxKernelArgs& a, const LogRef& lg, uint32_t depth, uint32_t rec_index, const float (&e)[4]) {
+	log_direct(a, lg.log_rec() * SSX_MAX_LEVELS + depth * SSX_COHORT_RECORDS + lg.rc(rec_index)) = make_float4(e[0], e[1], e[2], e[3]);
+}
+// index of the next-event term in slot `nslot` of the lane's cohort
+__device__ __forceinline__ uint32_t nee_index(const LogRef& lg, uint32_t nslot) { return lg.log_rec() * SSX_MAX_LEVELS + nslot; }
+// narrow queue entries: the contribution goes to the log when its shadow ray is parked
+__device__ __forceinline__ void store_parked_term(const SsxKernelArgs& a, uint32_t ni, const float (&c)[4]) { log_nee(a, ni) = make_float4(c[0], c[1], c[2], c[3]); }
+// what the flush stores once the ray is traced: the visibility byte (narrow entries) or the finished term, contribution or zeros (wide)
+template <bool NARROW>
+__device__ __forceinline__ void store_shadow_outcome(const SsxKernelArgs& a, uint32_t ni, bool visible, float c0, float c1, float c2, float c3) {
+	if (NARROW) log_vis(a, ni) = visible ? (uint8_t)1 : (uint8_t)0;
+	else log_nee(a, ni) = visible ? make_float4(c0, c1, c2, c3) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+// the entry of a continued level in slot `slot` of the lane's cohort: the continuation's factors and the chain word
+__device__ __forceinline__ void store_level_entry(const SsxKernelArgs& a, const LogRef& lg, uint32_t slot, const float (&f_s)[4], float n_dot_l, float pdf, uint32_t prev_slot, uint32_t level_word) {
+	const uint32_t entry = lg.log_rec() * SSX_MAX_FRAMES + slot;
+	log_fs(a, entry) = make_float4(f_s[0], f_s[1], f_s[2], f_s[3]);
+	log_np(a, entry) = make_float2(n_dot_l, pdf);
+	log_link(a, entry) = prev_slot | level_word;
 }
 
 // renderer.cpp:113-138: camera ray (f64, as the reference) and hero wavelength of sample k of
@@ -1069,7 +1106,7 @@ template <bool NARROW, bool BLACK, bool GLIBC = false>
 __device__ __forceinline__ bool path_step(const Lds& L, const ShadowQ& q, const SsxKernelArgs& a, const LogRef& lg, Path& p, bool& pushed, uint32_t& level_word) {
 	const SsxBlobHeader& h = L.hdr();
 	// what the level's entry (or the path's tail word) says about this level: slot of its next-event term << 13 | has an emission term << 26
-	level_word = SSX_NO_SLOT << 13;
+	level_word = level_word_none();
 	SSX_STAT(4); // lanes shading a hit
 	const uint32_t hq = (uint32_t)p.hit_tri >> 1, which = (uint32_t)p.hit_tri & 1u;
 	const SsxBlobQuad& Q = L.quad(hq);
@@ -1088,8 +1125,8 @@ __device__ __forceinline__ bool path_step(const Lds& L, const ShadowQ& q, const 
 #pragma unroll
 		for (int k = 0; k < 4; ++k) direct[k] += em.v[k];
 		// the level's emission term, read back by the fold (levels without it have none: 0 + x == x)
-		log_direct(a, lg.log_rec() * SSX_MAX_LEVELS + p.depth * SSX_COHORT_RECORDS + lg.rc(p.rec_index)) = make_float4(direct[0], direct[1], direct[2], direct[3]);
-		level_word |= 1u << 26;
+		store_emission(a, lg, p.depth, p.rec_index, direct);
+		level_word = level_word_emission(level_word);
 	}
 	// :178 `if (depth+1u<MAX_DEPTH)`: with ELS a ray at depth MAX_DEPTH-1 is never started (below);
 	// without it that ray exists (its hit may emit) and ends here
@@ -1148,9 +1185,9 @@ __device__ __forceinline__ bool path_step(const Lds& L, const ShadowQ& q, const 
 				const uint32_t slot = q.count + __builtin_amdgcn_mbcnt_hi((uint32_t)(pushing >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)pushing, 0u));
 				// the contribution's place in its cohort's log (parking order = flush order: a flush writes runs of consecutive bytes)
 				const uint32_t nslot = log_append(lg, 1u);
-				const uint32_t ni = lg.log_rec() * SSX_MAX_LEVELS + nslot;
+				const uint32_t ni = nee_index(lg, nslot);
 				if (NARROW) {
-					log_nee(a, ni) = make_float4(c[0], c[1], c[2], c[3]);
+					store_parked_term(a, ni, c);
 					float4* E = q.e + 2u * slot;
 					E[0] = make_float4(hit_pos.x, hit_pos.y, hit_pos.z, sdir.x);
 					E[1] = make_float4(sdir.y, sdir.z, __uint_as_float((light << 8) | hq), __uint_as_float(ni));
@@ -1160,7 +1197,7 @@ __device__ __forceinline__ bool path_step(const Lds& L, const ShadowQ& q, const 
 					E[1] = make_float4(sdir.y, sdir.z, c[0], c[1]);
 					E[2] = make_float4(c[2], c[3], __uint_as_float((light << 8) | hq), __uint_as_float(ni));
 				}
-				level_word = (level_word & ~(SSX_NO_SLOT << 13)) | (nslot << 13);
+				level_word = level_word_nee(level_word, nslot);
 				pushed = true;
 			}
 		}
@@ -1197,10 +1234,7 @@ __device__ __forceinline__ bool path_step(const Lds& L, const ShadowQ& q, const 
 	// the factors of the continuation for the backward fold (resolve_record, when the wave's unit is complete)
 	SSX_STAT(12); // continuing lanes
 	const uint32_t slot = log_append(lg, 0u);
-	const uint32_t entry = lg.log_rec() * SSX_MAX_FRAMES + slot;
-	log_fs(a, entry) = make_float4(f_s[0], f_s[1], f_s[2], f_s[3]);
-	log_np(a, entry) = make_float2(n_dot_l, pdf_w_i);
-	log_link(a, entry) = p.prev_slot | level_word;
+	store_level_entry(a, lg, slot, f_s, n_dot_l, pdf_w_i, p.prev_slot, level_word);
 	wave_release(lg.cnt); // publishes this lane's stores of the level to the lane of this wave that will fold them ("Memory-ordering contract")
 	p.prev_slot = slot;
 	p.dir = w_i; p.ignore = (int)hq;
@@ -1226,8 +1260,7 @@ __device__ __forceinline__ void shadow_flush(const Lds& L, const SsxKernelArgs& 
 	trace<TOPO>(L, mk(e0.x, e0.y, e0.z), mk(e0.w, e1.x, e1.y), (int)(tag & 0xFFu), have, sh, 2, nullptr, &tm);
 	if (have) {
 		const bool visible = sh.tri >= 0 && ((uint32_t)sh.tri >> 1) == (tag >> 8);
-		if (narrow) log_vis(a, __float_as_uint(e2.w)) = visible ? (uint8_t)1 : (uint8_t)0;
-		else log_nee(a, __float_as_uint(e2.w)) = visible ? make_float4(e1.z, e1.w, e2.x, e2.y) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+		store_shadow_outcome<NARROW>(a, __float_as_uint(e2.w), visible, e1.z, e1.w, e2.x, e2.y);
 		wave_release(q.cnt);
 	}
 }
@@ -1320,10 +1353,14 @@ __device__ __forceinline__ void resolve_records(const Lds& L, const SsxKernelArg
 			const uint32_t dep = (y >> 2) & 0xFu;
 			depth[s] = dep | ((y & 1u) << 4);
 			at[s] = (y >> 6) & SSX_NO_SLOT;
-			// the last level's radiance: 0 + its emission term (if any) + its next-event term (if it parked a shadow ray)
+			// the last level's radiance: 0 + its emission term (if any) + its next-event term (if it parked a shadow ray).  The 0 is L()'s own
+			// (renderer.cpp:149) and is added: 0 + -0 = +0, so an emission of -0 under a next-event term of -0 gives +0 as there, not -0
 			const uint32_t ns = y >> 19;
 			float4 last = zero4;
-			if ((y >> 1) & 1u) last = log_direct(a, nee_base + dep * SSX_COHORT_RECORDS + rc0 + s * 64u);
+			if ((y >> 1) & 1u) {
+				last = log_direct(a, nee_base + dep * SSX_COHORT_RECORDS + rc0 + s * 64u);
+				last = make_float4(0.0f + last.x, 0.0f + last.y, 0.0f + last.z, 0.0f + last.w);
+			}
 			const float4 ne = nee_term<NARROW>(a, nee_base + ns, ns != SSX_NO_SLOT);
 			if (dep) K[s] = log_link(a, fs_base + at[s]);
 			rad[s][0] = last.x + ne.x; rad[s][1] = last.y + ne.y; rad[s][2] = last.z + ne.z; rad[s][3] = last.w + ne.w;
@@ -1337,13 +1374,14 @@ __device__ __forceinline__ void resolve_records(const Lds& L, const SsxKernelArg
 			if (d < (depth[s] & 0xFu)) {
 				const uint32_t i = fs_base + at[s];
 				F[s] = log_fs(a, i); NP[s] = log_np(a, i);
-				// emission + next-event term, the order of renderer.cpp:171,216 (0 + x == x where a term is absent)
+				// 0 + emission + next-event term, the order of renderer.cpp:149,171,216.  The level's 0 is added, not assumed away: 0 + x == x for every
+				// x but -0, and a level whose terms are -0 over a -0 indirect term is +0 in L() (tests/test_fold_gpu.py; an absent term is +0 here)
 				const uint32_t ns = (K[s] >> 13) & SSX_NO_SLOT;
 				const bool has_ne = ns != SSX_NO_SLOT;
 				D[s] = nee_term<NARROW>(a, nee_base + ns, has_ne);
 				if ((K[s] >> 26) & 1u) { // rare: an emission term below the last level (non-ELS build)
 					const float4 em = log_direct(a, nee_base + d * SSX_COHORT_RECORDS + rc0 + s * 64u);
-					D[s] = has_ne ? make_float4(em.x + D[s].x, em.y + D[s].y, em.z + D[s].z, em.w + D[s].w) : em;
+					D[s] = make_float4((0.0f + em.x) + D[s].x, (0.0f + em.y) + D[s].y, (0.0f + em.z) + D[s].z, (0.0f + em.w) + D[s].w);
 				}
 				// the chain word of the level below, one round trip ahead of its use
 				at[s] = K[s] & SSX_NO_SLOT;
@@ -1354,11 +1392,12 @@ __device__ __forceinline__ void resolve_records(const Lds& L, const SsxKernelArg
 			if (d < (depth[s] & 0xFu)) {
 				SSX_STAT(14); // fold: level x way x lanes
 				const double pdf_recip = ssx_exact::div64_rcp_any(NP[s].y);
-				// ... + indirect term (renderer.cpp:247)
-				rad[s][0] = D[s].x + ssx_exact::div64_by((rad[s][0] * NP[s].x) * F[s].x, pdf_recip);
-				rad[s][1] = D[s].y + ssx_exact::div64_by((rad[s][1] * NP[s].x) * F[s].y, pdf_recip);
-				rad[s][2] = D[s].z + ssx_exact::div64_by((rad[s][2] * NP[s].x) * F[s].z, pdf_recip);
-				rad[s][3] = D[s].w + ssx_exact::div64_by((rad[s][3] * NP[s].x) * F[s].w, pdf_recip);
+				// ... + indirect term (renderer.cpp:247).  The level's 0 goes in front of its terms HERE, where they are consumed: added where they are loaded, in
+				// the loop above, it measured 1.1 % slower on the headline (profiles/r25/NOTES.md; why, was not established)
+				rad[s][0] = (0.0f + D[s].x) + ssx_exact::div64_by((rad[s][0] * NP[s].x) * F[s].x, pdf_recip);
+				rad[s][1] = (0.0f + D[s].y) + ssx_exact::div64_by((rad[s][1] * NP[s].x) * F[s].y, pdf_recip);
+				rad[s][2] = (0.0f + D[s].z) + ssx_exact::div64_by((rad[s][2] * NP[s].x) * F[s].z, pdf_recip);
+				rad[s][3] = (0.0f + D[s].w) + ssx_exact::div64_by((rad[s][3] * NP[s].x) * F[s].w, pdf_recip);
 			}
 	}
 	const __attribute__((address_space(4))) SsxKernelArgs& c = cold_args(); // (the render's switches: read where they are needed, once per pass)
@@ -1450,7 +1489,7 @@ __device__ __forceinline__ void generate_body(const SsxKernelArgs& a) {
 				const SsxBlobQuad& Q = L.quad((uint32_t)hit.tri >> 1);
 				if (Q.albedo_mode != 0u) hit_st(Q, (uint32_t)hit.tri & 1u, hit, st_x, st_y);
 			} else {
-				st = make_uint4(__float_as_uint(ray.w), (SSX_NO_SLOT << 6) | (SSX_NO_SLOT << 19), st.x, st.y); // see render_body: the tail word of a path that ends at level 0 without a hit
+				st = make_uint4(__float_as_uint(ray.w), tail_word(level_word_none(), 0u, 0u, SSX_NO_SLOT), st.x, st.y); // see render_body: the tail word of a path that ends at level 0 without a hit
 			}
 			a.ray[r] = ray;
 			a.st[r] = st;
@@ -1741,7 +1780,7 @@ __device__ __forceinline__ void render_body(const SsxKernelArgs& a) {
 	// p.depth-1 << 6 | slot of the level's next-event term << 19; lambda_0 and the final PCG32 state replace the sample's
 	// stream.  The fold happens when the sample's unit is complete.
 	auto end_path = [&](uint32_t level_word, uint32_t hit_anything) {
-		const uint32_t tail = hit_anything | ((level_word >> 26) << 1) | (p.depth << 2) | (p.prev_slot << 6) | ((level_word >> 13) << 19);
+		const uint32_t tail = tail_word(level_word, hit_anything, p.depth, p.prev_slot);
 		a.st[p.rec_index] = make_uint4(__float_as_uint(p.lambda_0), tail, (uint32_t)p.rng.state, (uint32_t)(p.rng.state >> 32));
 		wave_release(log_cnt);
 		active = false;
@@ -1786,7 +1825,7 @@ __device__ __forceinline__ void render_body(const SsxKernelArgs& a) {
 				p.depth = 0;
 				p.prev_slot = SSX_NO_SLOT;
 				const uint32_t cohort = kq / SSX_COHORT_KS;
-				p_tag = cohort | (cur_tag << 2) | ((cur_tag * a.unit_cohorts + cohort) << 3) | ((kq % SSX_COHORT_KS) << 8);
+				p_tag = log_tag_word(cohort, cur_tag, a.unit_cohorts, kq % SSX_COHORT_KS);
 				active = true;
 				if (with_hit) {
 					const float4 ht = a.hit[p.rec_index];
@@ -1890,7 +1929,7 @@ __device__ __forceinline__ void render_body(const SsxKernelArgs& a) {
 			float st_x = 0.0f, st_y = 0.0f;
 			if (CALIB) { const uint32_t left = (uint32_t)__popcll(__ballot(active && hit.tri < 0)); if (lane == 0u && left) atomicAdd(a.unit_counter + 1, left); }
 			if (active) {
-				if (hit.tri < 0) end_path(SSX_NO_SLOT << 13, p.depth ? 1u : 0u); // the ray left the scene: this level's radiance is 0, no term of either kind (a camera ray: no hit at all)
+				if (hit.tri < 0) end_path(level_word_none(), p.depth ? 1u : 0u); // the ray left the scene: this level's radiance is 0, no term of either kind (a camera ray: no hit at all)
 				else {
 					const SsxBlobQuad& Q = L.quad((uint32_t)hit.tri >> 1);
 					if (Q.albedo_mode != 0u) hit_st(Q, (uint32_t)hit.tri & 1u, hit, st_x, st_y);

@@ -1142,6 +1142,19 @@ class Renderer:
         self._check(self._lib.ssx_debug_tile_mask(self._ctx, C.byref(p), out.ctypes.data))
         return out
 
+    def debug_fold(self, levels, spp, order_seed=0, parked=False, flux=False, **over):
+        """ssx_debug_fold: the path kernel's fold on `levels`, uint32 [n_pixels * spp, SSX_FOLD_ROW_WORDS] rows in [pixel][k] order (n_pixels a multiple of 64)
+        -> (flux uint32 [n, 4] or None, xyza uint32 [n, 4], sums float64 [n_pixels, 4]): the float32 results as their bits."""
+        x = np.ascontiguousarray(levels, dtype=np.uint32)
+        if x.ndim != 2 or x.shape[1] != _capi.SSX_FOLD_ROW_WORDS or spp < 1 or x.shape[0] % spp:
+            raise ValueError("debug_fold: levels must be [n_pixels * spp, %d] words" % _capi.SSX_FOLD_ROW_WORDS)
+        n, n_pixels = x.shape[0], x.shape[0] // spp
+        fl = np.zeros((n, 4), dtype=np.uint32) if flux else None
+        xyza, sums = np.zeros((n, 4), dtype=np.uint32), np.zeros((n_pixels, 4), dtype=np.float64)
+        self._check(self._lib.ssx_debug_fold(self._ctx, C.byref(self.params(**over)), n_pixels, int(spp), x.ctypes.data, int(order_seed) & 0xFFFFFFFF, int(bool(parked)),
+                                             None if fl is None else fl.ctypes.data, xyza.ctypes.data, sums.ctypes.data))
+        return fl, xyza, sums
+
     def debug_spectral_accumulate(self, flux, lambda_0, bins, lambda_min, lambda_step, n_k=None, tile_first=0, tile_stride=1, tile_skew=0, moments=True):
         """ssx_debug_spectral_accumulate: the render's bin and moment kernels on the caller's records -- flux float32 [H, W, K, 4], lambda_0 float32 [H, W, K],
         given to the kernels as len(n_k) launches of n_k[l] samples per pixel (None: one launch of K) -> (sums float64 [H, W, B], counts uint32 [H, W, B / 4],
