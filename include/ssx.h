@@ -34,7 +34,7 @@ extern "C" {
  *      struct grew by 8 bytes) are new.  Added since without a change of existing entry points or structures (same version): ssx_units_info,
  *      ssx_rccl_probe (round 6); ssx_render_params.libm, appended (a caller with the struct_size before it gets SSX_LIBM_BUILD); the progressive
  *      rendering, spectral output, denoising, develop and demodulated-denoising entry points below; ssx_debug_tile_mask and SSX_DBG_TRACE_MASKED;
- *      ssx_debug_spectral_accumulate; SSX_DBG_TRACE_TOPO; ssx_debug_fold. */
+ *      ssx_debug_spectral_accumulate; SSX_DBG_TRACE_TOPO; ssx_debug_fold; ssx_debug_step. */
 #define SSX_ABI_VERSION 2
 
 enum {
@@ -1030,6 +1030,60 @@ int ssx_debug_spectral_accumulate(ssx_ctx* ctx, uint32_t width, uint32_t height,
 #define SSX_FOLD_NEE_VISIBLE 4u
 int ssx_debug_fold(ssx_ctx* ctx, const ssx_render_params* params, uint32_t n_pixels, uint32_t spp, const uint32_t* levels, uint32_t order_seed, uint32_t parked,
                    float* out_flux, float* out_xyza, double* out_sums);
+/* The path kernel's STEP on rays the caller supplies: one level of L() (renderer.cpp:147-255) per row, as one iteration of the path kernel's loop runs it --
+ * trace<TOPO> of the ray, hit_st where the hit quad's albedo is a texture, path_step (emission, light sample, parked shadow ray, BSDF sample, the level's
+ * entry), the end of a path that ends (its tail word), and the flush of the parked shadow rays (shadow_flush, through the loop a render's flush runs) -- in
+ * kernels of their own, the twin (topology 0 / 1 / 2, queue entries, libm) a render of this context with `params` would run; `params`' switches
+ * no_explicit_light_sampling and indirect_only are honoured (width, height, spp are only checked), the SSX_NARROW_QUEUE switch too.
+ * Topology 3 (kernels compiled for the scene's own pattern) is refused with SSX_ERR_STATE: its path_step is the BLACK = true instance that topologies 0 and 2
+ * run here, and its trace is SSX_DBG_TRACE_TOPO's.
+ * rows: [n_tiles][n_rounds][64][SSX_STEP_ROW_WORDS] -- a row is one lane's path in front of the trace: ray origin[3], direction[3], quad to ignore (-1: none),
+ * depth, lambda_0, PCG32 {state, inc} as four words, prev_slot (the slot of the level below's entry, SSX_STEP_NO_SLOT at depth 0; carried, never followed).
+ * One wave takes a tile; round k of a tile is sample k of its 64 pixels (the level logs' cohorts, regions and record indices are a render's).  After every
+ * round the wave flushes as a render does (64 or more parked rays: a wave's worth from the top of the queue), after the last round it drains the queue.
+ * out: [n_tiles][n_rounds][64][SSX_STEP_OUT_WORDS], read back THROUGH THE LEVEL LOGS AND THE TAIL WORD, as the fold reads them, after the last flush:
+ *   flags (SSX_STEP_HIT | _CONTINUED | _EMISSION | _PARKED | _VISIBLE) | hit triangle (2 * quad + which; -1), distance, the st handed to path_step [2] |
+ *   emission[4] | the next-event term as logged [4] (narrow entries: the parked term; wide: the finished term) | the term the fold adds [4] (nee_term) |
+ *   f_s[4], n_dot_l, pdf, prev_slot of the level's entry (continued rows) | the tail word's depth, hit-anything and prev_slot (ended rows) |
+ *   next ray origin[3], direction[3], quad to ignore, depth | PCG32 state [2] | slot of the level's entry (which slot a row gets is immaterial)
+ * SSX_ERR_ARG (ssx_last_error names the field): n_rows 0, no multiple of 64 or of 64 * n_rounds, or more than 65536 tiles; n_rounds outside 1..8 (the samples per
+ * pixel of a work unit: SSX_COHORT_KS x unit_cohorts); a row's depth >= 10, ignore neither -1 nor a quad of the
+ * scene, prev_slot above SSX_STEP_NO_SLOT, lambda_0 outside [lambda_min, lambda_min + lambda_step] of the scene, or level logs of 4 GiB or more. */
+#define SSX_STEP_ROW_WORDS 16u
+#define SSX_STEP_R_ORIG 0u
+#define SSX_STEP_R_DIR 3u
+#define SSX_STEP_R_IGNORE 6u
+#define SSX_STEP_R_DEPTH 7u
+#define SSX_STEP_R_LAMBDA0 8u
+#define SSX_STEP_R_RNG 9u
+#define SSX_STEP_R_PREV_SLOT 13u
+#define SSX_STEP_NO_SLOT 0x1FFFu
+#define SSX_STEP_OUT_WORDS 40u
+#define SSX_STEP_O_FLAGS 0u
+#define SSX_STEP_O_HIT_TRI 1u
+#define SSX_STEP_O_HIT_DIST 2u
+#define SSX_STEP_O_HIT_ST 3u
+#define SSX_STEP_O_EMISSION 5u
+#define SSX_STEP_O_NEE 9u
+#define SSX_STEP_O_NEE_TERM 13u
+#define SSX_STEP_O_FS 17u
+#define SSX_STEP_O_NDL 21u
+#define SSX_STEP_O_PDF 22u
+#define SSX_STEP_O_PREV_SLOT 23u
+#define SSX_STEP_O_TAIL_DEPTH 24u
+#define SSX_STEP_O_TAIL_HIT 25u
+#define SSX_STEP_O_NEXT_ORIG 26u
+#define SSX_STEP_O_NEXT_DIR 29u
+#define SSX_STEP_O_NEXT_IGNORE 32u
+#define SSX_STEP_O_NEXT_DEPTH 33u
+#define SSX_STEP_O_RNG 34u
+#define SSX_STEP_O_SLOT 36u
+#define SSX_STEP_HIT 1u
+#define SSX_STEP_CONTINUED 2u
+#define SSX_STEP_EMISSION 4u
+#define SSX_STEP_PARKED 8u
+#define SSX_STEP_VISIBLE 16u
+int ssx_debug_step(ssx_ctx* ctx, const ssx_render_params* params, uint32_t n_rows /* n_tiles * n_rounds * 64 */, uint32_t n_rounds, const uint32_t* rows, uint32_t* out);
 
 #ifdef __cplusplus
 }

@@ -23,7 +23,9 @@
  * self-contained C sources it vendors, compiled in place into oracle/_ref/ (Makefile target
  * `ref`; tests/test_ref_pins.py).  The integrator itself (intersection,
  * light sampling, recursion) has no reference-held vector: PARITY UNPINNED for those, checked
- * only against the survey's recorded constants and per-sample work statistics.
+ * only against the survey's recorded constants and per-sample work statistics.  orc_debug_level (one level of L() for a given ray)
+ * runs radiance_L's own body and is tied to orc_render_sample by tests/test_step_cpu.py: chained from the camera ray it gives the
+ * sample's levels, draws and result.
  */
 #ifndef SSX_ORACLE_H
 #define SSX_ORACLE_H
@@ -242,6 +244,28 @@ void orc_debug_set_level_log(orc_fold_sample* rec);
  * without FLAT_FIELD_CORRECTION, as in orc_render_sample; the other bits decided the levels and are not read. */
 void orc_fold_levels(const orc_color*, const orc_scene*, const orc_fold_sample* samples, size_t n_samples, int flags,
                      float* out_flux, float* out_xyza);
+
+/* ONE LEVEL of L() (renderer.cpp:147-255) for a ray the caller gives: radiance_L's own body, stopped where it would call itself.  depth < ORC_MAX_DEPTH;
+ * last_was_delta = depth == 0 (the camera ray; no level below a delta bounce is asked for: a mirror's continuation is followed by the caller as depth + 1,
+ * as the kernel follows it).  flags: the word of orc_render_sample (1 indirect-only, 2 without explicit light sampling).  Every member of the answer is one 32-bit word.
+ * The draws L() makes on this level are made on *rng; st (may be NULL) takes the level's counters. */
+typedef struct {
+	int32_t hit_prim;          /* -1: the ray left the scene, and nothing below is set */
+	float hit_dist, hit_st[2];
+	uint32_t recurse;          /* L() would call itself with {next_orig, next_dir}, ignoring hit_prim, at depth + 1 */
+	float next_orig[3], next_dir[3];
+	int32_t light_prim;        /* the light L() sampled (-1: it sampled none), the cosine at the hit and the sample's pdf */
+	float light_n_dot_l, light_pdf;
+	uint32_t shadow;           /* L() started a shadow ray (light_n_dot_l > 0) along shadow_dir; it met shadow_hit_prim (-1: nothing) */
+	float shadow_dir[3];
+	int32_t shadow_hit_prim;
+	uint32_t interactions;     /* 1: the level passed `depth + 1 < MAX_DEPTH` (:178) */
+	uint32_t hit_which, light_which, shadow_hit_which; /* the triangle (0 / 1) of its quad: that the ray met, that the light sampler picked (geometry.cpp:143), that the shadow ray met */
+	orc_fold_level level;      /* the level as the recorder writes it (orc_debug_set_level_log), occluded next-event terms included */
+} orc_level_out;
+#define ORC_LEVEL_WORDS (sizeof(orc_level_out) / 4u)
+void orc_debug_level(const orc_color*, const orc_scene*, orc_rng*, const float orig[3], const float dir[3], int ignore, unsigned depth,
+                     float lambda_0, int flags, orc_level_out* out, orc_stats*);
 
 /* Renderer::_render_pixel accumulation (renderer.cpp:292-296) with per-sample streams, for the
  * pixel rectangle [i0,i1)x[j0,j1); out is float4 XYZA per pixel, row 0 = bottom, full W*H

@@ -10,6 +10,7 @@ void orc_set_error(const char* fmt, const char* arg);
 /* branch-coverage counters: orc_render_sample points this at its stats block for the duration of a
  * sample (NULL otherwise); the unit-level functions bump through it */
 extern __thread orc_stats* orc_tls_stats;
+extern __thread int* orc_tls_tri_note; /* oracle_scene.c */
 #define ORC_COUNT(field) do { if (orc_tls_stats) orc_tls_stats->field++; } while (0)
 
 /* spectrum.cpp */

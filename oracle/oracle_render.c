@@ -19,6 +19,7 @@ typedef struct {
 	orc_stats* st;
 	unsigned interactions;
 	orc_fold_sample* lg; /* orc_debug_set_level_log: the sample's levels are written here on the way down (NULL: off) */
+	orc_level_out* stop; /* orc_debug_level: this call is the only level -- what it decides is noted here, and it does not call itself (NULL: off) */
 } path_ctx;
 
 /* The level recorder (oracle.h): off unless a test points it at a record. */
@@ -45,6 +46,7 @@ static orc_hero radiance_L(path_ctx* c, const orc_ray* ray, int last_was_delta, 
 	orc_hit hitrec;
 	if (orc_scene_intersect(c->sc, ray, &hitrec, ignore, c->st)) {
 		c->hit_anything = 1;
+		if (c->stop) { c->stop->hit_which = (uint32_t)orc_tls_tri_note[1]; c->stop->hit_prim = hitrec.prim; c->stop->hit_dist = hitrec.dist; c->stop->hit_st[0] = hitrec.st.x; c->stop->hit_st[1] = hitrec.st.y; }
 		const orc_material* mtl = &c->sc->materials[c->sc->prims[hitrec.prim].material];
 
 		/* Emission (:166-175); the condition exists only #ifdef EXPLICIT_LIGHT_SAMPLING */
@@ -65,11 +67,17 @@ static orc_hero radiance_L(path_ctx* c, const orc_ray* ray, int last_was_delta, 
 				orc_v3 shad_ray_dir; int light; float shad_pdf;
 				orc_scene_get_rand_toward_light(c->sc, c->rng, hit_pos, &shad_ray_dir, &light, &shad_pdf);
 				float n_dot_l = v3_dot(shad_ray_dir, hitrec.normal);
+				if (c->stop) { c->stop->light_which = (uint32_t)orc_tls_tri_note[0]; c->stop->light_prim = light; c->stop->light_n_dot_l = n_dot_l; c->stop->light_pdf = shad_pdf; }
 				if (n_dot_l > 0.0f) {
 					ORC_COUNT(nee_front);
 					orc_ray ray_shad = { hit_pos, shad_ray_dir };
 					orc_hit hitrec_shad;
-					orc_scene_intersect(c->sc, &ray_shad, &hitrec_shad, hitrec.prim, c->st);
+					const int shad_hit = orc_scene_intersect(c->sc, &ray_shad, &hitrec_shad, hitrec.prim, c->st);
+					if (c->stop) {
+						c->stop->shadow = 1u; c->stop->shadow_hit_prim = shad_hit ? hitrec_shad.prim : -1;
+						c->stop->shadow_hit_which = shad_hit ? (uint32_t)orc_tls_tri_note[1] : 0u;
+						c->stop->shadow_dir[0] = shad_ray_dir.x; c->stop->shadow_dir[1] = shad_ray_dir.y; c->stop->shadow_dir[2] = shad_ray_dir.z;
+					}
 					if (hitrec_shad.prim == light) {
 						ORC_COUNT(nee_visible);
 						const orc_material* lm = &c->sc->materials[c->sc->prims[hitrec_shad.prim].material];
@@ -130,7 +138,13 @@ static orc_hero radiance_L(path_ctx* c, const orc_ray* ray, int last_was_delta, 
 				if (n_dot_l > 0.0f) {
 					orc_ray ray_next = { hit_pos, w_i };
 					if (lv) { memcpy(lv->fs, f_s, sizeof f_s); lv->n_dot_l = n_dot_l; lv->pdf = pdf_w_i; }
-					orc_hero Lr = ORC_CALL_L(c, &ray_next, 0, depth + 1u, hitrec.prim);
+					orc_hero Lr = { { 0, 0, 0, 0 } };
+					if (c->stop) { /* orc_debug_level: L() would call itself here, with this ray */
+						c->stop->recurse = 1u;
+						c->stop->next_orig[0] = ray_next.orig.x; c->stop->next_orig[1] = ray_next.orig.y; c->stop->next_orig[2] = ray_next.orig.z;
+						c->stop->next_dir[0] = ray_next.dir.x; c->stop->next_dir[1] = ray_next.dir.y; c->stop->next_dir[2] = ray_next.dir.z;
+					} else
+					Lr = ORC_CALL_L(c, &ray_next, 0, depth + 1u, hitrec.prim);
 					for (int i = 0; i < 4; ++i) radiance.v[i] += ((Lr.v[i] * n_dot_l) * f_s[i]) / pdf_w_i;
 				}
 			}
@@ -171,7 +185,7 @@ void orc_render_sample(const orc_color* cd, const orc_scene* sc, orc_rng* rng, s
 	float lambda_0 = cd->rgb_mode ? 0.0f : cd->lambda_min + orc_rand_1f(rng) * cd->lambda_step;
 
 	/* `indirect_only` carries two flags: bit 0 = Options::indirect_only, bit 1 = build without ELS */
-	path_ctx c = { cd, sc, rng, lambda_0, indirect_only & 1, !(indirect_only & 2), 0, st, 0, orc_tls_level_log };
+	path_ctx c = { cd, sc, rng, lambda_0, indirect_only & 1, !(indirect_only & 2), 0, st, 0, orc_tls_level_log, NULL };
 	if (c.lg) { c.lg->lambda_0 = lambda_0; c.lg->cam_dir[0] = camera_ray_dir.x; c.lg->cam_dir[1] = camera_ray_dir.y; c.lg->cam_dir[2] = camera_ray_dir.z; c.lg->n = 0; }
 	orc_ray ray_camera = { sc->camera.pos, camera_ray_dir };
 	orc_hero rad = ORC_CALL_L(&c, &ray_camera, 1, 0u, -1);
@@ -197,6 +211,27 @@ void orc_render_sample(const orc_color* cd, const orc_scene* sc, orc_rng* rng, s
 		st->path_len_hist[c.interactions]++;
 		st->spectrum_lookups += 3;
 	}
+	orc_tls_stats = tls_saved;
+}
+
+/* One level of L(): the body of radiance_L itself for one given ray, stopped where it would call itself (path_ctx::stop). */
+void orc_debug_level(const orc_color* cd, const orc_scene* sc, orc_rng* rng, const float orig[3], const float dir[3], int ignore, unsigned depth,
+                     float lambda_0, int flags, orc_level_out* out, orc_stats* st) {
+	if (depth >= ORC_MAX_DEPTH) depth = ORC_MAX_DEPTH - 1u;
+	orc_stats* const tls_saved = orc_tls_stats;
+	orc_tls_stats = st;
+	orc_fold_sample rec;
+	memset(&rec, 0, sizeof rec);
+	memset(out, 0, sizeof *out);
+	out->hit_prim = out->light_prim = out->shadow_hit_prim = -1;
+	path_ctx c = { cd, sc, rng, lambda_0, flags & 1, !(flags & 2), 0, st, 0, &rec, out };
+	const orc_ray ray = { v3_make(orig[0], orig[1], orig[2]), v3_make(dir[0], dir[1], dir[2]) };
+	int tri_note[2] = { 0, 0 };
+	orc_tls_tri_note = tri_note;
+	(void)radiance_L(&c, &ray, depth == 0u, depth, ignore);
+	orc_tls_tri_note = NULL;
+	out->level = rec.level[depth];
+	out->interactions = c.interactions;
 	orc_tls_stats = tls_saved;
 }
 

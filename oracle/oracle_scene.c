@@ -103,11 +103,15 @@ ORC_VIRTUAL int orc_tri_intersect(const orc_tri* tri, const orc_ray* ray, orc_hi
 	return 0;
 }
 
+/* orc_debug_level only (NULL otherwise): [0] = the triangle of its quad the light sampler picked last, [1] = the triangle of its quad that the
+ * intersection accepted last -- the closest hit so far, since a triangle is accepted only in front of it.  Notes; no result depends on them. */
+__thread int* orc_tls_tri_note = NULL;
+
 /* geometry.cpp:128-139; a PrimTri primitive (geometry.cpp:12-101) is its one triangle */
 ORC_VIRTUAL static int quad_intersect(const orc_quad* q, int prim_id, const orc_ray* ray, orc_hit* hitrec, orc_stats* st) {
-	if (q->is_tri) return orc_tri_intersect(&q->tri0, ray, hitrec, prim_id, st);
-	if (orc_tri_intersect(&q->tri0, ray, hitrec, prim_id, st)) goto HIT;
-	if (orc_tri_intersect(&q->tri1, ray, hitrec, prim_id, st)) goto HIT;
+	if (q->is_tri) { const int h = orc_tri_intersect(&q->tri0, ray, hitrec, prim_id, st); if (h && orc_tls_tri_note) orc_tls_tri_note[1] = 0; return h; }
+	if (orc_tri_intersect(&q->tri0, ray, hitrec, prim_id, st)) { if (orc_tls_tri_note) orc_tls_tri_note[1] = 0; goto HIT; }
+	if (orc_tri_intersect(&q->tri1, ray, hitrec, prim_id, st)) { if (orc_tls_tri_note) orc_tls_tri_note[1] = 1; goto HIT; }
 	return 0;
 HIT:
 	hitrec->prim = prim_id;
@@ -146,12 +150,14 @@ static void tri_get_rand_toward(const orc_tri* tri, orc_rng* rng, orc_v3 from, o
 /* geometry.cpp:141-145 */
 static void quad_get_rand_toward(const orc_quad* q, orc_rng* rng, orc_v3 from, orc_v3* dir, float* pdf) {
 	const orc_tri* t = (orc_rand_1f(rng) <= 0.5f) ? &q->tri0 : &q->tri1;
+	if (orc_tls_tri_note) orc_tls_tri_note[0] = t == &q->tri1;
 	tri_get_rand_toward(t, rng, from, dir, pdf);
 	*pdf *= 0.5f;
 }
 /* scene.cpp:417-431 */
 void orc_scene_get_rand_toward_light(const orc_scene* sc, orc_rng* rng, orc_v3 from, orc_v3* dir, int* light, float* pdf) {
 	*light = sc->lights[orc_rand_choice(rng, (size_t)sc->n_lights)];
+	if (orc_tls_tri_note) orc_tls_tri_note[0] = 0;
 	if (sc->prims[*light].is_tri) tri_get_rand_toward(&sc->prims[*light].tri0, rng, from, dir, pdf); /* virtual dispatch: PrimTri::get_rand_toward */
 	else
 	quad_get_rand_toward(&sc->prims[*light], rng, from, dir, pdf);

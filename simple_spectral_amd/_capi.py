@@ -124,11 +124,18 @@ HIP_SYMBOLS = ["ssx_create", "ssx_destroy", "ssx_upload_scene", "ssx_render_star
                "ssx_spectral_moments_import",
                "ssx_spectral_compare", "ssx_spectral_compare_arrays",
                "ssx_delta_e_images", "ssx_spectral_delta_e",
-               "ssx_debug_tile_mask", "ssx_debug_spectral_accumulate", "ssx_debug_fold"]
+               "ssx_debug_tile_mask", "ssx_debug_spectral_accumulate", "ssx_debug_fold", "ssx_debug_step"]
 # ssx_debug_fold: a sample's row of levels (include/ssx.h)
 SSX_FOLD_ROW_WORDS, SSX_FOLD_LAMBDA0, SSX_FOLD_CAM_DIR, SSX_FOLD_HIT, SSX_FOLD_N, SSX_FOLD_LEVEL0, SSX_FOLD_LEVEL_WORDS = 160, 0, 1, 4, 5, 10, 15
 SSX_FOLD_L_FS, SSX_FOLD_L_NDL, SSX_FOLD_L_PDF, SSX_FOLD_L_FLAGS, SSX_FOLD_L_EMISSION, SSX_FOLD_L_NEE = 0, 4, 5, 6, 7, 11
 SSX_FOLD_EMISSION, SSX_FOLD_NEE, SSX_FOLD_NEE_VISIBLE = 1, 2, 4
+# ssx_debug_step: a row (one lane's path in front of the trace) and its answer (include/ssx.h)
+SSX_STEP_ROW_WORDS, SSX_STEP_R_ORIG, SSX_STEP_R_DIR, SSX_STEP_R_IGNORE, SSX_STEP_R_DEPTH, SSX_STEP_R_LAMBDA0, SSX_STEP_R_RNG, SSX_STEP_R_PREV_SLOT = 16, 0, 3, 6, 7, 8, 9, 13
+SSX_STEP_NO_SLOT, SSX_STEP_OUT_WORDS = 0x1FFF, 40
+(SSX_STEP_O_FLAGS, SSX_STEP_O_HIT_TRI, SSX_STEP_O_HIT_DIST, SSX_STEP_O_HIT_ST, SSX_STEP_O_EMISSION, SSX_STEP_O_NEE, SSX_STEP_O_NEE_TERM, SSX_STEP_O_FS, SSX_STEP_O_NDL,
+ SSX_STEP_O_PDF, SSX_STEP_O_PREV_SLOT, SSX_STEP_O_TAIL_DEPTH, SSX_STEP_O_TAIL_HIT, SSX_STEP_O_NEXT_ORIG, SSX_STEP_O_NEXT_DIR, SSX_STEP_O_NEXT_IGNORE,
+ SSX_STEP_O_NEXT_DEPTH, SSX_STEP_O_RNG, SSX_STEP_O_SLOT) = 0, 1, 2, 3, 5, 9, 13, 17, 21, 22, 23, 24, 25, 26, 29, 32, 33, 34, 36
+SSX_STEP_HIT, SSX_STEP_CONTINUED, SSX_STEP_EMISSION, SSX_STEP_PARKED, SSX_STEP_VISIBLE = 1, 2, 4, 8, 16
 (SSX_SWEEP_RCP, SSX_SWEEP_SQRT, SSX_SWEEP_INVERSESQRT, SSX_SWEEP_SIN, SSX_SWEEP_COS, SSX_SWEEP_ACOS, SSX_SWEEP_DIV_PI,
  SSX_SWEEP_RCP64, SSX_SWEEP_DIV_PAIRS, SSX_SWEEP_ACOS_SIN, SSX_SWEEP_SIN_PROOF, SSX_SWEEP_COS_PROOF, SSX_SWEEP_ACOS_PROOF) = range(1, 14)
 # ssx_debug_eval ops (include/ssx.h)
@@ -398,6 +405,8 @@ def hip_lib():
             lib.ssx_debug_spectral_accumulate.argtypes = [vp] + [C.c_uint32] * 6 + [C.c_float, C.c_float, C.c_uint32] + [vp] * 6
         if not override or hasattr(lib, "ssx_debug_fold"):  # the path kernel's fold on the caller's levels
             lib.ssx_debug_fold.argtypes = [vp, C.POINTER(SsxRenderParams), C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, vp, vp]
+        if not override or hasattr(lib, "ssx_debug_step"):  # one iteration of the path loop on the caller's paths
+            lib.ssx_debug_step.argtypes = [vp, C.POINTER(SsxRenderParams), C.c_uint32, C.c_uint32, vp, vp]
         lib.ssx_kernel_variant.argtypes = [vp]
         lib.ssx_kernel_name.argtypes = [vp]
         lib.ssx_kernel_name.restype = C.c_char_p

@@ -145,6 +145,7 @@ struct ssx_ctx {
 	DeviceBuffer d_spectral_sums, d_spectral_counts;
 	std::string spectral_note;          // why sums that can be continued come without spectral state (ssx_spectral_read says it)
 	float lambda_min = 0.0f, lambda_step = 0.0f; // of the uploaded scene
+	uint32_t n_quads = 0;      // primitives of the uploaded scene (ssx_debug_step checks its rows against it)
 	// spectral moments (ssx_set_spectral_moments; csrc/ssx_spectral_stats.hip): off -- then nothing below is allocated and no kernel of it runs.  Q[tile slot][bin][pixel of
 	// the tile] binary64, the layout of S.  d_probe: the row-major arrays, partials and results of ssx_spectral_probe / ssx_probe_arrays and of ssx_spectral_compare / ssx_spectral_compare_arrays; nothing until one of them is called.
 	bool spectral_moments = false;
@@ -1093,6 +1094,7 @@ int ssx_upload_scene(ssx_ctx* ctx, const ssx_scene_desc* s) {
 	}
 	ctx->have_cam_dir = have_cam_dir;
 	ctx->lambda_min = s->lambda_min; ctx->lambda_step = s->lambda_step;
+	ctx->n_quads = s->n_quads;
 	ctx->resident_blocks = 0; ctx->gen_blocks = 0; // depend on the blob's LDS footprint
 	ctx->have_scene = true;
 	ctx->scene_digest = scene_digest_of(s);
@@ -1455,6 +1457,78 @@ int ssx_debug_fold(ssx_ctx* ctx, const ssx_render_params* p_in, uint32_t n_pixel
 		for (uint32_t t = 0; t < n_tiles; ++t) for (uint32_t l = 0; l < 64u; ++l) for (uint32_t c = 0; c < 4u; ++c)
 			out_sums[((size_t)t * 64u + l) * 4u + c] = sums[(size_t)t * 256u + c * 64u + l];
 	}
+	return SSX_OK;
+}
+
+// One iteration of the path loop per round on the caller's paths (csrc/ssx_debug.hip debug_step_body): the twin a render of this context with these parameters
+// runs -- its topology (0, 1, 2), the queue entries pick_queue finds for that render's path kernel, its libm -- in buffers of the call's own: rows, answers,
+// sample records, level logs.  Every row is checked before anything is launched: what a row may index (its level's emission slot by depth, a quad's record
+// by ignore, the tables by lambda_0) and what its words are packed into (prev_slot's 13 bits).
+int ssx_debug_step(ssx_ctx* ctx, const ssx_render_params* p_in, uint32_t n_rows, uint32_t n_rounds, const uint32_t* rows, uint32_t* out) {
+	if (!ctx || !rows || !out) return SSX_ERR_ARG;
+	ssx_render_params pp;
+	int rc = begin_render(ctx, p_in, &pp, "render in progress");
+	if (rc) return rc;
+	if (n_rounds == 0 || n_rounds > SSX_MAX_UNIT_KS) return fail(ctx, SSX_ERR_ARG, "ssx_debug_step: n_rounds must be 1..8, the samples per pixel of a work unit (SSX_COHORT_KS x unit_cohorts)");
+	if (n_rows == 0 || (n_rows & 63u)) return fail(ctx, SSX_ERR_ARG, "ssx_debug_step: n_rows must be a multiple of 64");
+	if (n_rows % (64u * n_rounds)) return fail(ctx, SSX_ERR_ARG, "ssx_debug_step: n_rows must be a multiple of 64 * n_rounds (whole tiles)");
+	const uint32_t n_tiles = n_rows / (64u * n_rounds), cohorts = (n_rounds + SSX_COHORT_KS - 1u) / SSX_COHORT_KS;
+	if (n_tiles > 65536u) return fail(ctx, SSX_ERR_ARG, "ssx_debug_step: n_rows is more than 65536 tiles of rows");
+	const size_t log_records = (size_t)n_tiles * 2u * cohorts * SSX_COHORT_RECORDS;
+	// (the kernels address the logs with 32-bit byte offsets: ensure_logs)
+	if (log_records * SSX_LOG_BYTES_PER_RECORD >= ((size_t)1 << 32)) return fail(ctx, SSX_ERR_ARG, "ssx_debug_step: level logs beyond 4 GiB for this many rows; step fewer rows per call");
+	if (ctx->topology > 2u) return fail(ctx, SSX_ERR_STATE, "ssx_debug_step: the context runs kernels compiled for its scene's own pattern (topology 3), which this op leaves out");
+	if (pp.libm > 1u) return fail(ctx, SSX_ERR_STATE, "internal: ssx_debug_step with an unknown libm"); // (kStepKernels below has the two modes check_params lets through)
+	const float lam_lo = ctx->rgb_mode ? 0.0f : ctx->lambda_min, lam_hi = ctx->rgb_mode ? 0.0f : ctx->lambda_min + ctx->lambda_step;
+	for (uint32_t i = 0; i < n_rows; ++i) {
+		const uint32_t* x = rows + (size_t)i * SSX_STEP_ROW_WORDS;
+		float lam;
+		memcpy(&lam, x + SSX_STEP_R_LAMBDA0, sizeof lam);
+		const char* what = nullptr;
+		if (x[SSX_STEP_R_DEPTH] >= SSX_MAX_DEPTH_) what = "depth must be below MAX_DEPTH (csrc/ssx_kernels.hip SSX_MAX_DEPTH_)";
+		else if ((int32_t)x[SSX_STEP_R_IGNORE] != -1 && x[SSX_STEP_R_IGNORE] >= ctx->n_quads) what = "ignore must be -1 or a quad of the scene";
+		else if (x[SSX_STEP_R_PREV_SLOT] > SSX_NO_SLOT) what = "prev_slot must be at most SSX_STEP_NO_SLOT";
+		else if (!(lam >= lam_lo && lam <= lam_hi)) what = "lambda_0 must lie in the scene's [lambda_min, lambda_min + lambda_step] (0 in RGB mode)";
+		if (what) return fail(ctx, SSX_ERR_ARG, fmt("ssx_debug_step: row %u: %s", i, what));
+	}
+	SSX_HIP(ctx, hipSetDevice(ctx->device));
+	if ((rc = wait_device_pending(ctx))) return rc;
+	// the queue entries of that render's path kernel (pick_queue looks at the kernels of ctx->variant: lent for the question, and put back)
+	const uint32_t variant = pp.libm, variant_was = ctx->variant;
+	uint32_t qw = 0;
+	ctx->variant = variant;
+	rc = pick_queue(ctx, ctx->path_blob_words, &qw, nullptr);
+	ctx->variant = variant_was;
+	if (rc) return rc;
+	const bool narrow = qw == SSX_QUEUE_WORDS_NARROW;
+	const size_t row_bytes = (size_t)n_rows * SSX_STEP_ROW_WORDS * 4u, out_bytes = (size_t)n_rows * SSX_STEP_OUT_WORDS * 4u;
+	DeviceBuffer d_rows, d_out, d_samples, d_logs;
+	if (d_rows.reserve(row_bytes) != hipSuccess || d_out.reserve(out_bytes) != hipSuccess || d_samples.reserve((size_t)n_rows * SSX_BYTES_PER_SAMPLE) != hipSuccess ||
+	    d_logs.reserve(log_records * SSX_LOG_BYTES_PER_RECORD) != hipSuccess) {
+		(void)hipGetLastError();
+		return fail(ctx, SSX_ERR_DEVICE, "out of device memory (ssx_debug_step)");
+	}
+	SSX_HIP(ctx, hipMemcpy(d_rows.ptr, rows, row_bytes, hipMemcpyHostToDevice));
+	SSX_HIP(ctx, hipMemsetAsync(d_out.ptr, 0, out_bytes, ctx->stream));
+	SsxKernelArgs a{};
+	a.blob = ctx->d_blob.as<uint32_t>(); a.blob_words = ctx->path_blob_words;
+	a.rgb_mode = ctx->rgb_mode ? 1u : 0u;
+	a.indirect_only = pp.indirect_only ? 1u : 0u;
+	a.no_els = pp.no_explicit_light_sampling ? 1u : 0u;
+	a.unit_cohorts = cohorts; a.group_spp = n_rounds; a.n_records = n_rows;
+	a.queue_words = qw;
+	bind_arrays(a, d_samples.as<uint8_t>(), n_rows, d_logs.as<uint8_t>(), log_records, false);
+	static const void* const kStepKernels[2][3][2] = {
+		{ { (const void*)ssx_debug_step_kernel, (const void*)ssx_debug_step_kernel_nq }, { (const void*)ssx_debug_step_kernel_cornell, (const void*)ssx_debug_step_kernel_cornell_nq },
+		  { (const void*)ssx_debug_step_kernel_plane, (const void*)ssx_debug_step_kernel_plane_nq } },
+		{ { (const void*)ssx_debug_step_kernel_glibc, (const void*)ssx_debug_step_kernel_nq_glibc }, { (const void*)ssx_debug_step_kernel_cornell_glibc, (const void*)ssx_debug_step_kernel_cornell_nq_glibc },
+		  { (const void*)ssx_debug_step_kernel_plane_glibc, (const void*)ssx_debug_step_kernel_plane_nq_glibc } } };
+	const uint32_t* d_in = d_rows.as<uint32_t>();
+	uint32_t* d_o = d_out.as<uint32_t>();
+	void* args[] = { &a, &d_in, (void*)&n_tiles, &n_rounds, &d_o };
+	SSX_HIP(ctx, hipLaunchKernel(kStepKernels[variant][ctx->topology][narrow], dim3((n_tiles + 3u) / 4u), dim3(256), args, path_lds_bytes(a.blob_words, qw), ctx->stream));
+	SSX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	SSX_HIP(ctx, hipMemcpy(out, d_out.ptr, out_bytes, hipMemcpyDeviceToHost));
 	return SSX_OK;
 }
 

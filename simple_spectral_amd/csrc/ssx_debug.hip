@@ -322,6 +322,147 @@ SSX_DEBUG_FOLD_KERNEL(ssx_debug_fold_kernel_flux, false, false, true)
 SSX_DEBUG_FOLD_KERNEL(ssx_debug_fold_kernel_nq_flux, true, false, true)
 #undef SSX_DEBUG_FOLD_KERNEL
 
+// ssx_debug_step (include/ssx.h): one iteration of render_body's loop per round, on paths the caller supplies -- a row is a lane's Path in front of step (4).
+// One wave per tile; round k is sample k of the tile's 64 pixels, so rec_index, the tag word (log_tag_word), the cohort's counters and its log region
+// (LogRef, log_region) are what a render's refill hands a lane.  Per round, in render_body's order: (4) trace<TOPO> with every lane taking part, a miss ends the
+// path, a hit takes hit_st only where the quad's albedo is a texture; (1) path_step<NARROW, TOPO != 1, GLIBC> -- the instance the render kernel of this
+// topology runs: BLACK compiled out of the Cornell topology's -- and the end of a path that does not continue (end_path's statement: tail_word, the final
+// stream, wave_release); sq.count += popc(ballot(pushed)); (2) the flush loop of render_body's flush_fold (restated below), with drain only after the last round.
+// Then the hand-over as the fold begins it (wave_acquire, unit_fold's two fences) and the read-back THROUGH WHAT THE FOLD READS: the tail word of an ended
+// path (a.st[r].y, decoded as resolve_records decodes it), the entry of a continued one (log_fs, log_np, log_link at its slot), log_direct at the fold's
+// index, nee_term<NARROW>.  LDS as a path kernel's workgroup: [coefficients][blob][4 queues][4 x counters].
+// Topology 3 has no twin here: its path_step is the BLACK = true instance TOPO 0 and 2 run, its trace is ssx_debug_trace_jit's (SSX_DBG_TRACE_TOPO).
+template <int TOPO, bool NARROW, bool GLIBC>
+__device__ __forceinline__ void debug_step_body(const SsxKernelArgs& a, const uint32_t* rows, uint32_t n_tiles, uint32_t n_k, uint32_t* out) {
+	uint32_t* const lds_words = stage_lds<GLIBC>(a);
+	Lds L; L.w = lds_words;
+	const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+	const uint32_t wave_slot = blockIdx.x * 4u + wave; // = the tile
+	if (wave_slot >= n_tiles) return;
+	constexpr uint32_t queue_words = SSX_QUEUE_ENTRIES * (NARROW ? SSX_QUEUE_WORDS_NARROW : SSX_QUEUE_WORDS_WIDE);
+	uint32_t* const log_cnt = lds_words + a.blob_words + 4u * queue_words + wave * SSX_WAVE_COUNTER_WORDS;
+	if (lane < SSX_WAVE_COUNTER_WORDS) log_cnt[lane] = 0u; // the logs of the unit's cohorts are empty (rotate_fetch)
+	SsxTimer tm;
+	ShadowQ sq;
+	sq.e = reinterpret_cast<float4*>(lds_words + a.blob_words + wave * queue_words);
+	sq.count = 0; sq.cnt = log_cnt;
+	const uint32_t rec_base = wave_slot * n_k * 64u;
+	for (uint32_t k = 0; k < n_k; ++k) {
+		const uint32_t r = rec_base + k * 64u + lane;
+		const uint32_t* x = rows + (size_t)r * SSX_STEP_ROW_WORDS;
+		uint32_t* o = out + (size_t)r * SSX_STEP_OUT_WORDS;
+		Path p;
+		p.orig = mk(f(x[SSX_STEP_R_ORIG]), f(x[SSX_STEP_R_ORIG + 1]), f(x[SSX_STEP_R_ORIG + 2]));
+		p.dir = mk(f(x[SSX_STEP_R_DIR]), f(x[SSX_STEP_R_DIR + 1]), f(x[SSX_STEP_R_DIR + 2]));
+		p.ignore = (int)x[SSX_STEP_R_IGNORE]; p.depth = x[SSX_STEP_R_DEPTH]; p.lambda_0 = f(x[SSX_STEP_R_LAMBDA0]);
+		p.rng = load_rng(x + SSX_STEP_R_RNG);
+		p.prev_slot = x[SSX_STEP_R_PREV_SLOT];
+		p.rec_index = r;
+		LogRef lg;
+		lg.cnt = log_cnt; lg.wave_base = wave_slot * 2u * a.unit_cohorts; lg.tagw = log_tag_word(k / SSX_COHORT_KS, 0u, a.unit_cohorts, k % SSX_COHORT_KS); // unit tag 0
+		bool active = true;
+		auto end_path = [&](uint32_t level_word, uint32_t hit_anything) { // render_body's, word for word
+			const uint32_t tail = tail_word(level_word, hit_anything, p.depth, p.prev_slot);
+			a.st[p.rec_index] = make_uint4(__float_as_uint(p.lambda_0), tail, (uint32_t)p.rng.state, (uint32_t)(p.rng.state >> 32));
+			wave_release(log_cnt);
+			active = false;
+		};
+		// (4)
+		HitInfo hit;
+		trace<TOPO>(L, p.orig, p.dir, p.ignore, true, hit);
+		p.hit_tri = hit.tri; p.hit_dist = hit.dist;
+		float st_x = 0.0f, st_y = 0.0f;
+		if (hit.tri < 0) end_path(level_word_none(), p.depth ? 1u : 0u);
+		else {
+			const SsxBlobQuad& Q = L.quad((uint32_t)hit.tri >> 1);
+			if (Q.albedo_mode != 0u) hit_st(Q, (uint32_t)hit.tri & 1u, hit, st_x, st_y);
+		}
+		p.hit_st_x = st_x; p.hit_st_y = st_y;
+		o[SSX_STEP_O_HIT_TRI] = (uint32_t)hit.tri; o[SSX_STEP_O_HIT_DIST] = u(hit.dist); o[SSX_STEP_O_HIT_ST] = u(st_x); o[SSX_STEP_O_HIT_ST + 1] = u(st_y);
+		// (1)
+		bool pushed = false, cont = false;
+		if (active) {
+			uint32_t level_word;
+			cont = path_step<NARROW, TOPO != 1, GLIBC>(L, sq, a, lg, p, pushed, level_word);
+			if (!cont) end_path(level_word, 1u);
+		}
+		sq.count += (uint32_t)__popcll(__ballot(pushed));
+		// the lane's path as the next iteration would find it
+		o[SSX_STEP_O_FLAGS] = (hit.tri >= 0 ? SSX_STEP_HIT : 0u) | (cont ? SSX_STEP_CONTINUED : 0u);
+		o[SSX_STEP_O_NEXT_ORIG] = u(p.orig.x); o[SSX_STEP_O_NEXT_ORIG + 1] = u(p.orig.y); o[SSX_STEP_O_NEXT_ORIG + 2] = u(p.orig.z);
+		o[SSX_STEP_O_NEXT_DIR] = u(p.dir.x); o[SSX_STEP_O_NEXT_DIR + 1] = u(p.dir.y); o[SSX_STEP_O_NEXT_DIR + 2] = u(p.dir.z);
+		o[SSX_STEP_O_NEXT_IGNORE] = (uint32_t)p.ignore; o[SSX_STEP_O_NEXT_DEPTH] = p.depth;
+		o[SSX_STEP_O_RNG] = (uint32_t)p.rng.state; o[SSX_STEP_O_RNG + 1] = (uint32_t)(p.rng.state >> 32);
+		o[SSX_STEP_O_SLOT] = cont ? p.prev_slot : SSX_NO_SLOT;
+		// (2) the flush loop of render_body's flush_fold (csrc/ssx_kernels.hip), RESTATED: calling one function from both changed the code objects of all 19 path
+		// kernels (same instruction counts, other instructions: profiles/r26/NOTES.md), and those stay as they are.  Keep the two loops the same.
+		const bool drain = k + 1u == n_k;
+		while (sq.count >= SSX_SQ_FLUSH_AT || (drain && sq.count)) {
+			const uint32_t take = min(sq.count, 64u);
+			sq.count -= take;
+			shadow_flush<TOPO, NARROW>(L, a, sq, sq.count, take, tm);
+		}
+	}
+	// the fold's side from here on
+	wave_acquire(log_cnt);
+	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+	for (uint32_t k = 0; k < n_k; ++k) {
+		const uint32_t r = rec_base + k * 64u + lane, s = k % SSX_COHORT_KS;
+		const uint32_t* x = rows + (size_t)r * SSX_STEP_ROW_WORDS;
+		uint32_t* o = out + (size_t)r * SSX_STEP_OUT_WORDS;
+		const uint32_t log_rec = log_region(a, wave_slot, 0u, k / SSX_COHORT_KS), fs_base = log_rec * SSX_MAX_FRAMES, nee_base = log_rec * SSX_MAX_LEVELS;
+		uint32_t flags = o[SSX_STEP_O_FLAGS], ns, depth, has_em;
+		const float4 zero4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+		float4 F = zero4; float2 NP = make_float2(0.0f, 0.0f);
+		uint32_t prev = 0u, tail_depth = 0u, tail_hit = 0u;
+		if (flags & SSX_STEP_CONTINUED) { // the level's entry, as the level pass of resolve_records reads it
+			const uint32_t i = fs_base + o[SSX_STEP_O_SLOT];
+			F = log_fs(a, i); NP = log_np(a, i);
+			const uint32_t K = log_link(a, i);
+			prev = K & SSX_NO_SLOT; ns = (K >> 13) & SSX_NO_SLOT; has_em = (K >> 26) & 1u;
+			depth = x[SSX_STEP_R_DEPTH];
+		} else { // the tail word, as its first loop does
+			const uint4 rec = a.st[r];
+			const uint32_t y = rec.y;
+			tail_depth = depth = (y >> 2) & 0xFu; tail_hit = y & 1u;
+			prev = (y >> 6) & SSX_NO_SLOT; ns = y >> 19; has_em = (y >> 1) & 1u;
+			o[SSX_STEP_O_RNG] = rec.z; o[SSX_STEP_O_RNG + 1] = rec.w; // the sample's final stream, where the path's end left it
+		}
+		const float4 em = has_em ? log_direct(a, nee_base + depth * SSX_COHORT_RECORDS + lane + s * 64u) : zero4;
+		const bool parked = ns != SSX_NO_SLOT;
+		const float4 raw = parked ? log_nee(a, nee_base + ns) : zero4;
+		const float4 ne = nee_term<NARROW>(a, nee_base + ns, parked);
+		// visible: the visibility byte (narrow entries); wide entries hold the finished term, and a parked term is never four zeros
+		const bool visible = parked && (NARROW ? log_vis(a, nee_base + ns) != 0 : (raw.x != 0.0f || raw.y != 0.0f || raw.z != 0.0f || raw.w != 0.0f));
+		flags |= (has_em ? SSX_STEP_EMISSION : 0u) | (parked ? SSX_STEP_PARKED : 0u) | (visible ? SSX_STEP_VISIBLE : 0u);
+		o[SSX_STEP_O_FLAGS] = flags;
+		o[SSX_STEP_O_EMISSION] = u(em.x); o[SSX_STEP_O_EMISSION + 1] = u(em.y); o[SSX_STEP_O_EMISSION + 2] = u(em.z); o[SSX_STEP_O_EMISSION + 3] = u(em.w);
+		o[SSX_STEP_O_NEE] = u(raw.x); o[SSX_STEP_O_NEE + 1] = u(raw.y); o[SSX_STEP_O_NEE + 2] = u(raw.z); o[SSX_STEP_O_NEE + 3] = u(raw.w);
+		o[SSX_STEP_O_NEE_TERM] = u(ne.x); o[SSX_STEP_O_NEE_TERM + 1] = u(ne.y); o[SSX_STEP_O_NEE_TERM + 2] = u(ne.z); o[SSX_STEP_O_NEE_TERM + 3] = u(ne.w);
+		o[SSX_STEP_O_FS] = u(F.x); o[SSX_STEP_O_FS + 1] = u(F.y); o[SSX_STEP_O_FS + 2] = u(F.z); o[SSX_STEP_O_FS + 3] = u(F.w);
+		o[SSX_STEP_O_NDL] = u(NP.x); o[SSX_STEP_O_PDF] = u(NP.y);
+		o[SSX_STEP_O_PREV_SLOT] = prev; o[SSX_STEP_O_TAIL_DEPTH] = tail_depth; o[SSX_STEP_O_TAIL_HIT] = tail_hit;
+	}
+}
+#define SSX_DEBUG_STEP_KERNEL(name, topo, narrow, glibc) \
+	extern "C" __global__ void __launch_bounds__(256) name(SsxKernelArgs a, const uint32_t* rows, uint32_t n_tiles, uint32_t n_k, uint32_t* out) { \
+		debug_step_body<topo, narrow, glibc>(a, rows, n_tiles, n_k, out); \
+	}
+SSX_DEBUG_STEP_KERNEL(ssx_debug_step_kernel, 0, false, false)
+SSX_DEBUG_STEP_KERNEL(ssx_debug_step_kernel_nq, 0, true, false)
+SSX_DEBUG_STEP_KERNEL(ssx_debug_step_kernel_cornell, 1, false, false)
+SSX_DEBUG_STEP_KERNEL(ssx_debug_step_kernel_cornell_nq, 1, true, false)
+SSX_DEBUG_STEP_KERNEL(ssx_debug_step_kernel_plane, 2, false, false)
+SSX_DEBUG_STEP_KERNEL(ssx_debug_step_kernel_plane_nq, 2, true, false)
+SSX_DEBUG_STEP_KERNEL(ssx_debug_step_kernel_glibc, 0, false, true)
+SSX_DEBUG_STEP_KERNEL(ssx_debug_step_kernel_nq_glibc, 0, true, true)
+SSX_DEBUG_STEP_KERNEL(ssx_debug_step_kernel_cornell_glibc, 1, false, true)
+SSX_DEBUG_STEP_KERNEL(ssx_debug_step_kernel_cornell_nq_glibc, 1, true, true)
+SSX_DEBUG_STEP_KERNEL(ssx_debug_step_kernel_plane_glibc, 2, false, true)
+SSX_DEBUG_STEP_KERNEL(ssx_debug_step_kernel_plane_nq_glibc, 2, true, true)
+#undef SSX_DEBUG_STEP_KERNEL
+
 // ---- libm = glibc-2.35: the same diagnostics for the _glibc kernels, in kernels of their own (they stage the LDS table of the _glibc
 // kernels, stage_lds<true>: the glibc coefficients over ssx_fmath.h's arc-cosine slots)
 // Digest word of one input and its result (include/ssx.h SSX_SWEEP_GLIBC_*; tests/glibc_math_check.c computes the same on the host).

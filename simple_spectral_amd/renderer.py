@@ -1155,6 +1155,16 @@ class Renderer:
                                              None if fl is None else fl.ctypes.data, xyza.ctypes.data, sums.ctypes.data))
         return fl, xyza, sums
 
+    def debug_step(self, rows, n_rounds, **over):
+        """ssx_debug_step: one iteration of the path loop per round on `rows`, uint32 [n_tiles * n_rounds * 64, SSX_STEP_ROW_WORDS] in [tile][round][lane] order
+        -> uint32 [n, SSX_STEP_OUT_WORDS] (float32 results as their bits); `over`: fields of ssx_render_params (no_explicit_light_sampling, indirect_only, libm)."""
+        x = np.ascontiguousarray(rows, dtype=np.uint32)
+        if x.ndim != 2 or x.shape[1] != _capi.SSX_STEP_ROW_WORDS:
+            raise ValueError("debug_step: rows must be [n, %d] words" % _capi.SSX_STEP_ROW_WORDS)
+        out = np.zeros((x.shape[0], _capi.SSX_STEP_OUT_WORDS), dtype=np.uint32)
+        self._check(self._lib.ssx_debug_step(self._ctx, C.byref(self.params(**over)), x.shape[0], int(n_rounds), x.ctypes.data, out.ctypes.data))
+        return out
+
     def debug_spectral_accumulate(self, flux, lambda_0, bins, lambda_min, lambda_step, n_k=None, tile_first=0, tile_stride=1, tile_skew=0, moments=True):
         """ssx_debug_spectral_accumulate: the render's bin and moment kernels on the caller's records -- flux float32 [H, W, K, 4], lambda_0 float32 [H, W, K],
         given to the kernels as len(n_k) launches of n_k[l] samples per pixel (None: one launch of K) -> (sums float64 [H, W, B], counts uint32 [H, W, B / 4],
