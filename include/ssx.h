@@ -899,6 +899,63 @@ int ssx_spectral_delta_e(ssx_ctx* ctx, const ssx_denoise_params* denoise /* or N
                          const double t[2], float* de /* [H][W][2] or NULL */, float* lab /* [H][W][6] or NULL */,
                          double* SUM, double* SSQ, float* MAX, uint64_t* NF, uint64_t* NX, uint64_t* EX /* [R][2] */);
 
+/* ---- Developing through a lens: per-bin lateral magnification and blur (appended; same ABI version) ---------------------------------------------------
+ * DEVELOP is one linear map per pixel: a sensor with no optics in front of it.  This section puts a lens there, after the render: each wavelength bin is resampled
+ * about the optical centre with its own magnification (lateral chromatic aberration: colour fringes at high-contrast edges) and blurred with its own separable
+ * kernel (a focus that moves with wavelength, diffraction growing with lambda).  The result is again q [height][width][B], so the develop kernels, the denoiser
+ * and ssx_delta_e_images take it unchanged.  The definition is this library's; a restatement in numpy gives the same bits (tests/optics_ref.py).
+ *
+ * All arithmetic is binary32 IEEE in the order written, every product rounded before the add, no contraction, no reassociation; non-finite values go through
+ * the arithmetic as they are.  max(a, b) is a > b ? a : b and min(a, b) is a < b ? a : b (a NaN a gives b); clamp(k, lo, hi) on integers.  Input q[H][W][B]
+ * row-major, row 0 = bottom, B in {4, 8, ..., 64}; pixel (i, j) has its centre at (i + 0.5, j + 0.5).  Parameters: ssx_optics_params below, R = max_radius.
+ *
+ * WARP.  A bin with s_b == 1.0f is copied bit for bit.  Otherwise, for pixel (i, j):
+ *       dx = ((float)i + 0.5f) - cx;   x = (cx + dx * s_b) - 0.5f;   x = min(max(x, -1.0f), (float)W)
+ *       i0 = floorf(x);   fx = x - i0;   ia = clamp((int)i0, 0, W-1);   ib = clamp((int)i0 + 1, 0, W-1)
+ *   the same for y with j, cy, H: j0, fy, ja, jb.  Then
+ *       lo = q[ja][ia][b] * (1.0f - fx) + q[ja][ib][b] * fx
+ *       hi = q[jb][ia][b] * (1.0f - fx) + q[jb][ib][b] * fx
+ *       w[j][i][b] = lo * (1.0f - fy) + hi * fy
+ *   s_b > 1 reads further from the centre: the bin's image shrinks towards it.  The border is replicated: the field outside the render is unknown, and
+ *   replicating it keeps the frame from darkening.
+ * BLUR.  Separable, the horizontal pass first, then the vertical.  A bin with r_b == 0 is copied bit for bit in both passes and its taps are not read.  Otherwise
+ *       acc = 0.0f;   for d = -r_b .. r_b ascending:   acc = acc + (w[j][clamp(i+d, 0, W-1)][b] * k_b[d+R])
+ *   gives t[j][i][b], and the same walk over clamp(j+d, 0, H-1) on t gives out[j][i][b].  r_b may exceed the image: the clamp repeats the border.
+ * THE LENS MODEL is the hosts' (libssx_host.so ssh_optics_lens, include/ssx_host.h): it makes s_b, r_b and the taps from a lateral coefficient, a blur at a
+ *   reference wavelength and an axial coefficient, in binary64, rounded to binary32 once at the end.  This library takes any parameters.
+ * SAME BITS: the numpy restatement; ssx_spectral_develop_optics against ssx_optics_images fed with q rebuilt from the exported sums (raw) or with
+ *   ssx_denoise_spectral's output (denoised), and its `out` against ssx_develop_images of that; identity parameters (every s_b == 1, every r_b == 0) against
+ *   ssx_spectral_develop.
+ *
+ * ON THE DEVICE (csrc/ssx_optics.hip) four kernels, none with atomics, a lane writing only its own output: ssx_optics_unpack_kernel, one wave per owned tile,
+ * writes the raw source row-major; ssx_optics_warp_kernel and the two blur kernels run their lanes along the interleaved (pixel, bin) axis, so that stores and the
+ * aligned part of the gathers are whole cache lines; ssx_optics_blur_h_kernel stages a row segment with its apron of R pixels either side in LDS,
+ * ssx_optics_blur_v_kernel reads whole rows at the same (i, b).  A pass no bin needs (every s_b == 1; every r_b == 0) is not launched.  With the feature unused
+ * nothing is allocated and nothing is launched. */
+#define SSX_OPTICS_MAX_RADIUS 12u
+typedef struct ssx_optics_params {
+	uint32_t struct_size;      /* sizeof(ssx_optics_params) */
+	float cx, cy;              /* optical centre in pixel units; finite */
+	uint32_t max_radius;       /* R, 0..SSX_OPTICS_MAX_RADIUS */
+	const float* scale;        /* [B]   lateral magnification s_b of bin b; finite, > 0 */
+	const uint32_t* radius;    /* [B]   r_b <= R: taps visited for bin b */
+	const float* taps;         /* [B][2R+1]  k_b[d+R], d = -R..R; only |d| <= r_b is read */
+} ssx_optics_params;
+
+/* WARP, then BLUR, as a pure function of its arguments (needs no scene): q [height][width][bins] -> out [height][width][bins], row-major floats.  SSX_ERR_ARG,
+ * with ssx_last_error naming the field: a NULL pointer (q, out, optics, scale, radius, taps), a wrong struct_size, max_radius above 12, an r_b above max_radius, an
+ * s_b that is not finite and > 0, a cx or cy that is not finite, bins not a multiple of 4 in 4..64, an empty or too large image.  SSX_ERR_STATE: a render runs. */
+int ssx_optics_images(ssx_ctx* ctx, uint32_t width, uint32_t height, uint32_t bins, const float* q /* [H][W][B] */, const ssx_optics_params* optics,
+                      float* out /* [H][W][B] */);
+/* The bins of the context's own state through the lens and then through DEVELOP, without leaving the device: the source raw (denoise == NULL) or denoised, as in
+ * ssx_spectral_develop; WARP and BLUR on it; then the develop kernels with weights [channels][B] on the result.  bins_out [H][W][B]: the bins behind the lens;
+ * out [H][W][channels]: their development; either may be NULL (both NULL: the kernels run and the results stay on the device -- for measurements), and with
+ * out == NULL the weights may be NULL too: nothing is developed.  It reads only: image, sums, noise and spectral state stay as they are, so an ssx_render_continue
+ * afterwards leaves the bits of a one-shot render in the image and in ssx_spectral_read.  SSX_ERR_STATE with ssx_spectral_develop's reasons, and where the context
+ * does not own every tile (tile_stride != 1): a blur needs its neighbours.  SSX_ERR_ARG: what ssx_optics_images and ssx_spectral_develop refuse. */
+int ssx_spectral_develop_optics(ssx_ctx* ctx, const ssx_denoise_params* denoise /* or NULL */, const ssx_optics_params* optics, const float* weights /* [C][B] */,
+                                uint32_t channels, float* out /* [H][W][C] or NULL */, float* bins_out /* [H][W][B] or NULL */);
+
 /* ---- Diagnostics for the parity tests (not part of the reference's interface) ---------------------
  * ssx_debug_eval runs one building block of the path kernel -- the same device function the kernel
  * inlines -- on n items, one per lane: `in` holds in_words 32-bit words per item, `out` receives

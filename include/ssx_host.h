@@ -153,6 +153,18 @@ int ssh_relight_gain(const ssh_spectrum_t* from_spectrum, const ssh_spectrum_t* 
  * out[c] = sum over b of (double)weights[c][b] * (integral of the illuminant over bin b / the bin's width), binary64, ascending b, integrated as ssh_relight_gain
  * integrates.  illuminant NULL: equal energy.  Which white a comparison uses is the caller's viewing decision, like exposure: it sets the absolute size of every dE. */
 int ssh_develop_white(const float* weights, uint32_t bins, float lambda_min, float lambda_step, const ssh_spectrum_t* illuminant, double out[3]);
+/* A lens for ssx_optics_images / ssx_spectral_develop_optics (ssx.h "Developing through a lens"): the per-bin tables of ssx_optics_params for bins of a render
+ * with this lambda_min and lambda_step, from a lateral chromatic coefficient, a blur sigma_ref (pixels) at lambda_ref and an axial coefficient (pixels of defocus
+ * blur per unit of relative wavelength offset).  Binary64, IEEE operations in the order written, rounded to binary32 once at the end.  M = bins / 4:
+ *     lc_b = (double)lambda_min + (b + 0.5) * ((double)lambda_step / M)        the bin's centre;        u = (lc_b - lambda_ref) / lambda_ref
+ *     s_b = (float)(1.0 + lateral * u)                                         refused unless finite and > 0
+ *     sd = sigma_ref * lc_b / lambda_ref   (diffraction grows with lambda);    ax = axial * u;    sigma_b = sqrt(sd * sd + ax * ax)
+ *     r_b = min(max_radius, ceil(3.0 * sigma_b)), 0 where sigma_b * sigma_b == 0 (sigma_b is 0 or its square underflows; the bin's taps are then all 0 and never read)
+ *     k_b[d] = exp(-(double)(d * d) / (2.0 * (sigma_b * sigma_b))) for d = -r_b .. r_b;  total = their sum in ascending d from 0.0;  taps[b][d + R] = (float)(k_b[d] / total)
+ * taps outside |d| <= r_b are 0.  lateral = axial = sigma_ref = 0 gives identity parameters.  scale_out [bins], radius_out [bins], taps_out [bins][2 max_radius + 1].
+ * SSX_ERR_ARG: NULL pointers, bins not a multiple of 4 in 4..64, max_radius above 12, a non-finite argument, lambda_step or lambda_ref not positive, sigma_ref < 0. */
+int ssh_optics_lens(uint32_t bins, float lambda_min, float lambda_step, double lambda_ref, double lateral, double sigma_ref, double axial, uint32_t max_radius,
+                    float* scale_out, uint32_t* radius_out, float* taps_out);
 /* *spectrum = index (in desc->spectra) of the emission spectrum that all emissive materials of the scene share up to a scale.  SSX_ERR_SCENE, with the reason in
  * ssh_last_error, when two of them differ or none is emissive: what the CLI's --develop-relight refuses. */
 int ssh_emitter_spectrum(const ssx_scene_desc* desc, uint32_t* spectrum);

@@ -90,6 +90,15 @@ class SsxDenoiseParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("levels", C.c_uint32), ("sigma_l", C.c_float), ("sigma_a", C.c_float)]
 
 
+class SsxOpticsParams(C.Structure):
+    """ssx_optics_params: the optical centre and the per-bin magnification, radius and taps of the lens."""
+    _fields_ = [("struct_size", C.c_uint32), ("cx", C.c_float), ("cy", C.c_float), ("max_radius", C.c_uint32),
+                ("scale", C.c_void_p), ("radius", C.c_void_p), ("taps", C.c_void_p)]
+
+
+SSX_OPTICS_MAX_RADIUS = 12  # include/ssx.h
+
+
 class SshSpectrum(C.Structure):
     """ssh_spectrum_t: n uniform samples over [low, high] (include/ssx_host.h)."""
     _fields_ = [("samples", C.POINTER(C.c_float)), ("n", C.c_uint32), ("low", C.c_float), ("high", C.c_float)]
@@ -124,6 +133,7 @@ HIP_SYMBOLS = ["ssx_create", "ssx_destroy", "ssx_upload_scene", "ssx_render_star
                "ssx_spectral_moments_import",
                "ssx_spectral_compare", "ssx_spectral_compare_arrays",
                "ssx_delta_e_images", "ssx_spectral_delta_e",
+               "ssx_optics_images", "ssx_spectral_develop_optics",
                "ssx_debug_tile_mask", "ssx_debug_spectral_accumulate", "ssx_debug_fold", "ssx_debug_step"]
 # ssx_debug_fold: a sample's row of levels (include/ssx.h)
 SSX_FOLD_ROW_WORDS, SSX_FOLD_LAMBDA0, SSX_FOLD_CAM_DIR, SSX_FOLD_HIT, SSX_FOLD_N, SSX_FOLD_LEVEL0, SSX_FOLD_LEVEL_WORDS = 160, 0, 1, 4, 5, 10, 15
@@ -153,7 +163,8 @@ HOST_SYMBOLS = ["ssh_scene_create", "ssh_scene_create_ex", "ssh_scene_destroy", 
                 "ssh_probe_derive", "ssh_probe_save_csv", "ssh_spectral_noise_derive", "ssh_spectral_noise_save_csv",
                 "ssh_checkpoint_save_moments", "ssh_checkpoint_load_moments", "ssh_moments_merge",
                 "ssh_compare_derive", "ssh_compare_save_csv",
-                "ssh_delta_e_derive", "ssh_delta_e_save_csv", "ssh_develop_white"]
+                "ssh_delta_e_derive", "ssh_delta_e_save_csv", "ssh_develop_white",
+                "ssh_optics_lens"]
 
 _hip = None
 _host = None
@@ -207,6 +218,7 @@ def host_lib():
                                             C.c_float, C.c_float, vp, vp]
         lib.ssh_relight_gain.argtypes = [C.POINTER(SshSpectrum), C.POINTER(SshSpectrum), C.c_uint32, C.c_float, C.c_float, vp]
         lib.ssh_emitter_spectrum.argtypes = [C.POINTER(SsxSceneDesc), C.POINTER(C.c_uint32)]
+        lib.ssh_optics_lens.argtypes = [C.c_uint32, C.c_float, C.c_float, C.c_double, C.c_double, C.c_double, C.c_double, C.c_uint32, vp, vp, vp]
         _host = lib
     return _host
 
@@ -397,6 +409,9 @@ def hip_lib():
         if not override or hasattr(lib, "ssx_delta_e_images"):  # the colour difference of two developments: maps and region figures
             lib.ssx_delta_e_images.argtypes = [vp, C.c_uint32, C.c_uint32] + [vp] * 5 + [C.c_uint32] + [vp] * 9
             lib.ssx_spectral_delta_e.argtypes = [vp, C.POINTER(SsxDenoiseParams), C.c_int, C.c_int] + [vp] * 5 + [C.c_uint32] + [vp] * 9
+        if not override or hasattr(lib, "ssx_optics_images"):  # developing through a lens: per-bin warp and blur
+            lib.ssx_optics_images.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.POINTER(SsxOpticsParams), vp]
+            lib.ssx_spectral_develop_optics.argtypes = [vp, C.POINTER(SsxDenoiseParams), C.POINTER(SsxOpticsParams), vp, C.c_uint32, vp, vp]
         if not override or hasattr(lib, "ssx_spectral_moments_import"):  # the second moments through checkpoint and resume
             lib.ssx_spectral_moments_import.argtypes = [vp, C.POINTER(SsxSpectralInfo), vp]
         if not override or hasattr(lib, "ssx_debug_tile_mask"):  # the camera-ray pre-trace's tile masks, read back

@@ -7,6 +7,7 @@
 #include "image_io.hpp"
 #include "scene.hpp"
 
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
@@ -330,6 +331,37 @@ int ssh_relight_gain(const ssh_spectrum_t* from_spectrum, const ssh_spectrum_t* 
 		return SSX_OK;
 	} catch (const ssx::HostError& e) { return report(e); }
 	catch (const std::exception& e) { g_error = e.what(); return SSX_ERR_DATA; }
+}
+
+int ssh_optics_lens(uint32_t bins, float lambda_min, float lambda_step, double lambda_ref, double lateral, double sigma_ref, double axial, uint32_t max_radius,
+                    float* scale_out, uint32_t* radius_out, float* taps_out) {
+	if (!scale_out || !radius_out || !taps_out) { g_error = "NULL argument"; return SSX_ERR_ARG; }
+	if (bins < 4u || bins > 64u || (bins & 3u)) { g_error = "ssh_optics_lens: bins must be a multiple of 4 up to 64"; return SSX_ERR_ARG; }
+	if (max_radius > SSX_OPTICS_MAX_RADIUS) { g_error = "ssh_optics_lens: max_radius must be 0..12"; return SSX_ERR_ARG; }
+	if (!std::isfinite(lambda_min) || !std::isfinite(lambda_step) || !(lambda_step > 0.0f)) { g_error = "ssh_optics_lens: lambda_min must be finite, lambda_step finite and positive"; return SSX_ERR_ARG; }
+	if (!std::isfinite(lambda_ref) || !(lambda_ref > 0.0)) { g_error = "ssh_optics_lens: lambda_ref must be finite and positive"; return SSX_ERR_ARG; }
+	if (!std::isfinite(lateral) || !std::isfinite(axial) || !std::isfinite(sigma_ref) || sigma_ref < 0.0) { g_error = "ssh_optics_lens: lateral and axial must be finite, sigma_ref finite and >= 0"; return SSX_ERR_ARG; }
+	const uint32_t R = max_radius, K = 2u * R + 1u;
+	const double width = static_cast<double>(lambda_step) / (bins / 4u);
+	for (uint32_t b = 0; b < bins; ++b) {
+		const double lc = static_cast<double>(lambda_min) + (b + 0.5) * width;
+		const double u = (lc - lambda_ref) / lambda_ref;
+		const float s = static_cast<float>(1.0 + lateral * u);
+		if (!(s > 0.0f) || !std::isfinite(s)) { g_error = "ssh_optics_lens: the lateral coefficient gives bin " + std::to_string(b) + " a magnification that is not finite and > 0"; return SSX_ERR_ARG; }
+		scale_out[b] = s;
+		const double sd = sigma_ref * lc / lambda_ref, ax = axial * u;
+		const double sigma = std::sqrt(sd * sd + ax * ax);
+		for (uint32_t k = 0; k < K; ++k) taps_out[b * K + k] = 0.0f;
+		radius_out[b] = 0u;
+		if (sigma * sigma == 0.0) continue; // (sigma 0, or so small that its square underflows: no blur, not 0 / 0)
+		const uint32_t r = static_cast<uint32_t>(std::fmin(static_cast<double>(R), std::ceil(3.0 * sigma)));
+		radius_out[b] = r;
+		double k[2u * SSX_OPTICS_MAX_RADIUS + 1u], total = 0.0;
+		for (int d = -static_cast<int>(r); d <= static_cast<int>(r); ++d) k[d + static_cast<int>(r)] = std::exp(-static_cast<double>(d * d) / (2.0 * (sigma * sigma)));
+		for (uint32_t t = 0; t < 2u * r + 1u; ++t) total = total + k[t];
+		for (uint32_t t = 0; t < 2u * r + 1u; ++t) taps_out[b * K + (R - r) + t] = static_cast<float>(k[t] / total);
+	}
+	return SSX_OK;
 }
 
 int ssh_emitter_spectrum(const ssx_scene_desc* desc, uint32_t* spectrum) {

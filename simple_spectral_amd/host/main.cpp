@@ -21,6 +21,7 @@
 // filtered one only if --denoise is given too.
 // Developing the bins (include/ssx.h "Developing the spectral bins"): --develop-output=PATH with --spectral-bins=N writes the image developed from the bins on the
 // device -- through the same XYZ -> sRGB store and writers as --output -- under --develop-observer=1931|2006 (default: the render's), through --develop-filter=FILE.csv
+// (--develop-lens=lateral,sigma,axial[,lambda_ref] with --develop-lens-radius=R puts a lens in front: include/ssx.h "Developing through a lens")
 // (a spectrum in the format of data/*.csv, its range in the name: NAME-LOW+STEP+HIGH.csv) and relit by --develop-relight=NEW.csv (the emitters' spectrum replaced by
 // NEW; refused unless all emissive materials share one spectrum up to a scale).  With --spectral-denoise the filtered bins are developed.  It does not need
 // --spectral-output, and has its refusals (--tile-major, --rgb, --libm=glibc-2.35; --resume of a checkpoint without the bins).  With --resume, --spectral-bins may
@@ -60,6 +61,7 @@
 
 #include "checkpoint.hpp"
 #include "develop.hpp"
+#include "../../include/ssx_host.h"
 
 #include <array>
 #include <chrono>
@@ -102,6 +104,9 @@ void print_usage() {
 		"    `--spectral-denoise` (with `--spectral-output`: the file holds the bins filtered with `--denoise`'s weights, levels and sigmas; not with `-spp=1`)\n"
 		"    `--develop-output=<image>` (needs `--spectral-bins=<n>`) [`--develop-observer=1931|2006`] [`--develop-filter=<name-low+step+high.csv>`] [`--develop-relight=<new.csv>`]\n"
 		"          (the image developed from the wavelength bins; with `--spectral-denoise` from the filtered bins)\n"
+		"    [`--develop-lens=<lateral>,<sigma>,<axial>[,<lambda_ref=550>]`] [`--develop-lens-radius=<0..12, default 8>`] [`--delta-e-lens=...`]\n"
+		"          (the bins through a lens before they are developed: lateral chromatic aberration, a blur of <sigma> pixels at <lambda_ref> growing with the\n"
+		"           wavelength, <axial> pixels of defocus per relative wavelength offset; for `--develop-output` and side A of `--delta-e-*`, `--delta-e-lens` for side B)\n"
 		"    `--demodulate[=1|2|4]` (with `--spectral-denoise`: filter illumination -- divide by the first-hit albedo per bin, <k> x <k> rays per pixel, before; multiply after)\n"
 		"    `--albedo-output=<file.npy>` (needs `--spectral-bins=<n>`: the first-hit albedo per wavelength bin)\n"
 		"    `--spectral-variance-output=<file.npy>` (needs `--spectral-bins=<n>`: the variance of every bin mean)\n"
@@ -194,6 +199,11 @@ struct Progressive { // the flags of the progressive modes
 	std::string guides_output;   // --guides-output: "" = none
 	std::string develop_output, develop_filter, develop_relight; // --develop-output / --develop-filter / --develop-relight: "" = none
 	int develop_observer = 0;    // --develop-observer: 0 = the render's
+	// the lens in front of the development (include/ssx.h "Developing through a lens"; ssh_optics_lens): --develop-lens=lateral,sigma,axial[,lambda_ref] for
+	// --develop-output and side A of --delta-e-*, --delta-e-lens=... for side B, --develop-lens-radius=R (the largest blur radius, for both)
+	struct Lens { bool on = false; double lateral = 0.0, sigma = 0.0, axial = 0.0, lambda_ref = 550.0; };
+	Lens develop_lens, delta_e_lens;
+	unsigned develop_lens_radius = 8;
 	bool spectral_bins_given = false;
 	bool demodulate = false;     // --demodulate[=K]
 	ssx::Renderer::DemodParams demod_params;
@@ -306,6 +316,36 @@ void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progress
 		if (v == "1931") g->develop_observer = 1931; else if (v == "2006") g->develop_observer = 2006;
 		else { std::fprintf(stderr, "Invalid value for --develop-observer (1931|2006)!\n"); throw -2; }
 	}
+	auto take_lens = [&](const char* flag, Progressive::Lens* lens) {
+		if (!a.take(flag, "", &v)) return;
+		double x[4] = { 0.0, 0.0, 0.0, 550.0 };
+		size_t n = 0, at = 0;
+		bool ok = true;
+		try {
+			while (ok && n < 4) {
+				const size_t comma = v.find(',', at);
+				const std::string part = v.substr(at, comma == std::string::npos ? std::string::npos : comma - at);
+				size_t used = 0;
+				x[n++] = std::stod(part, &used);
+				ok = used == part.size() && std::isfinite(x[n - 1]);
+				if (comma == std::string::npos) break;
+				at = comma + 1;
+				if (n == 4) ok = false;
+			}
+		} catch (...) { ok = false; }
+		if (!ok || n < 3 || x[1] < 0.0 || !(x[3] > 0.0)) { std::fprintf(stderr, "Invalid value for %s (<lateral>,<sigma>,<axial>[,<lambda_ref>]: finite, sigma >= 0, lambda_ref > 0)!\n", flag); throw -2; }
+		lens->on = true; lens->lateral = x[0]; lens->sigma = x[1]; lens->axial = x[2]; lens->lambda_ref = x[3];
+	};
+	take_lens("--develop-lens", &g->develop_lens);
+	take_lens("--delta-e-lens", &g->delta_e_lens);
+	bool lens_radius_given = false;
+	if (a.take("--develop-lens-radius", "", &v)) {
+		size_t r = 99;
+		try { r = v == "0" ? 0 : to_pos(v); } catch (int) { r = 99; }
+		if (r > SSX_OPTICS_MAX_RADIUS) { std::fprintf(stderr, "Invalid value for --develop-lens-radius (0..12)!\n"); throw -2; }
+		g->develop_lens_radius = static_cast<unsigned>(r);
+		lens_radius_given = true;
+	}
 	if (a.take("--delta-e-output", "", &v)) g->delta_e_output = v;
 	if (a.take("--delta-e-csv", "", &v)) g->delta_e_csv = v;
 	if (a.take("--delta-e-filter", "", &v)) g->delta_e_filter = v;
@@ -339,8 +379,10 @@ void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progress
 		catch (...) { std::fprintf(stderr, "Invalid value for --delta-e-white-y (finite and > 0)!\n"); throw -2; }
 		delta_e_side = true;
 	}
+	if (g->delta_e_lens.on) delta_e_side = true;
+	if (lens_radius_given && !g->develop_lens.on && !g->delta_e_lens.on) { std::fprintf(stderr, "`--develop-lens-radius` needs `--develop-lens` or `--delta-e-lens`!\n"); throw -2; }
 	if (delta_e_side && !g->delta_e()) {
-		std::fprintf(stderr, "`--delta-e-observer`, `--delta-e-filter`, `--delta-e-relight`, `--delta-e-denoise`, `--delta-e-threshold` and `--delta-e-white-y` need `--delta-e-output=<file.npy>` or `--delta-e-csv=<file.csv>`!\n");
+		std::fprintf(stderr, "`--delta-e-observer`, `--delta-e-filter`, `--delta-e-relight`, `--delta-e-denoise`, `--delta-e-threshold`, `--delta-e-white-y` and `--delta-e-lens` need `--delta-e-output=<file.npy>` or `--delta-e-csv=<file.csv>`!\n");
 		throw -2;
 	}
 	if (a.take("--spectral-bins", "", &v)) {
@@ -371,8 +413,8 @@ void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progress
 		std::fprintf(stderr, "`--spectral-output` cannot be combined with `--tile-major`, `--rgb` or `--libm=glibc-2.35`!\n");
 		throw -2;
 	}
-	if (g->develop_output.empty() && !g->delta_e() && (!g->develop_filter.empty() || !g->develop_relight.empty() || g->develop_observer)) {
-		std::fprintf(stderr, "`--develop-observer`, `--develop-filter` and `--develop-relight` need `--develop-output=<image>`!\n");
+	if (g->develop_output.empty() && !g->delta_e() && (!g->develop_filter.empty() || !g->develop_relight.empty() || g->develop_observer || g->develop_lens.on)) {
+		std::fprintf(stderr, "`--develop-observer`, `--develop-filter`, `--develop-relight` and `--develop-lens` need `--develop-output=<image>`!\n");
 		throw -2;
 	}
 	if (g->delta_e() && !g->spectral_bins_given) {
@@ -585,6 +627,20 @@ int main(int argc, char* argv[]) {
 			develop_color->meng_output_transform = renderer.color->meng_output_transform;
 			develop_weights = weights_of(*develop_color, prog.develop_filter, prog.develop_relight, true);
 		}
+		// the lenses, built (and refused) before the render
+		ssx::Renderer::Optics lens_a, lens_b;
+		auto make_lens = [&](const Progressive::Lens& l, ssx::Renderer::Optics* o) {
+			if (!l.on) return;
+			const ssx_scene_desc& d = renderer.scene->desc();
+			const uint32_t B = static_cast<uint32_t>(prog.spectral_bins), R = prog.develop_lens_radius;
+			o->max_radius = R; o->scale.resize(B); o->radius.resize(B); o->taps.resize(static_cast<size_t>(B) * (2u * R + 1u));
+			if (ssh_optics_lens(B, d.lambda_min, d.lambda_step, l.lambda_ref, l.lateral, l.sigma, l.axial, R, o->scale.data(), o->radius.data(), o->taps.data()) != SSX_OK)
+				throw ssx::HostError{ SSX_ERR_ARG, std::string("--develop-lens / --delta-e-lens: ") + ssh_last_error() };
+		};
+		make_lens(prog.develop_lens, &lens_a);
+		make_lens(prog.delta_e_lens, &lens_b);
+		const ssx::Renderer::Optics* const optics_a = prog.develop_lens.on ? &lens_a : nullptr;
+		const ssx::Renderer::Optics* const optics_b = prog.delta_e_lens.on ? &lens_b : nullptr;
 		// side B of --delta-e-*, and both sides' whites up to the common scale (host policy: the chromaticity is the development, by the side's weights without a
 		// relighting gain, of the side's illuminant -- the relight's new one, else the scene's emitter spectrum where it has one, else D65)
 		std::vector<float> delta_e_weights;
@@ -701,7 +757,7 @@ int main(int argc, char* argv[]) {
 			double scale = 0.0;
 			if (prog.delta_e_white_y > 0.0) scale = prog.delta_e_white_y / delta_e_white[0][1];
 			else {
-				const std::vector<float> xyz = renderer.develop(develop_weights.data(), 3, prog.spectral_denoise ? dn : nullptr, prog.spectral_denoise ? dm : nullptr);
+				const std::vector<float> xyz = renderer.develop(develop_weights.data(), 3, prog.spectral_denoise ? dn : nullptr, prog.spectral_denoise ? dm : nullptr, optics_a);
 				double sum = 0.0; size_t n = 0;
 				for (size_t p = 0; p < pixels; ++p) if (std::isfinite(xyz[3 * p + 1])) { sum += static_cast<double>(xyz[3 * p + 1]); ++n; }
 				const double mean = n ? sum / static_cast<double>(n) : 0.0;
@@ -709,7 +765,7 @@ int main(int argc, char* argv[]) {
 				scale = (mean / 0.18) / delta_e_white[0][1];
 			}
 			for (int x = 0; x < 2; ++x) for (int c = 0; c < 3; ++c) delta_e_white[x][c] *= scale;
-			const ssx::Renderer::DeltaESide side_a{ develop_weights.data(), prog.spectral_denoise }, side_b{ delta_e_weights.data(), prog.delta_e_denoise };
+			const ssx::Renderer::DeltaESide side_a{ develop_weights.data(), prog.spectral_denoise, optics_a }, side_b{ delta_e_weights.data(), prog.delta_e_denoise, optics_b };
 			const ssx::Renderer::DeltaE e = renderer.delta_e(side_a, side_b, delta_e_white[0], delta_e_white[1], labels, regions, prog.delta_e_threshold, !prog.delta_e_output.empty(), dn,
 			                                                 (prog.spectral_denoise || prog.delta_e_denoise) ? dm : nullptr);
 			if (!prog.delta_e_csv.empty()) renderer.save_delta_e_csv(prog.delta_e_csv, e);
@@ -718,7 +774,7 @@ int main(int argc, char* argv[]) {
 				std::fprintf(stderr, "Colour difference, region %zu: mean dE*ab %.4g, mean dE00 %.4g, max dE00 %.4g (whites' Y %.6g).\n", r, e.mean[2 * r], e.mean[2 * r + 1], e.max[2 * r + 1], delta_e_white[0][1]);
 		}
 		if (!prog.develop_output.empty()) { // X, Y, Z from the bins, the alpha of the render's image, then the store of --output
-			const std::vector<float> xyz = renderer.develop(develop_weights.data(), 3, prog.spectral_denoise ? &prog.denoise_params : nullptr, prog.demodulate ? &prog.demod_params : nullptr);
+			const std::vector<float> xyz = renderer.develop(develop_weights.data(), 3, prog.spectral_denoise ? &prog.denoise_params : nullptr, prog.demodulate ? &prog.demod_params : nullptr, optics_a);
 			const size_t pixels = options.res[0] * options.res[1];
 			std::vector<float> xyza(pixels * 4);
 			for (size_t p = 0; p < pixels; ++p) { xyza[4 * p] = xyz[3 * p]; xyza[4 * p + 1] = xyz[3 * p + 1]; xyza[4 * p + 2] = xyz[3 * p + 2]; xyza[4 * p + 3] = renderer.xyza[4 * p + 3]; }

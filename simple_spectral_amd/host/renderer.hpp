@@ -8,6 +8,7 @@
 #include "color.hpp"
 #include "scene.hpp"
 
+#include <cmath>
 #include <array>
 #include <chrono>
 #include <functional>
@@ -203,14 +204,20 @@ public:
 	// Otherwise the denoised source: one device runs ssx_spectral_develop with the parameters, all on the device; several follow denoise_spectral's path and
 	// then ssx_develop_images on device 0.  Either way the same bits as one device.  After render_wait(); nothing the devices hold changes.
 	// demod (with denoise): the bins filtered in the demodulated mode -- one device: ssx_spectral_develop_demod; several: denoise_spectral's path as above.
-	std::vector<float> develop(const float* weights, size_t channels, const DenoiseParams* denoise = nullptr, const DemodParams* demod = nullptr);
+	// optics (include/ssx.h "Developing through a lens"): the source goes through the lens before it is developed.  One device and no demodulated source:
+	// ssx_spectral_develop_optics, all on the device.  Otherwise the host gathers q by its existing gather (every pixel's sums from the device that owns it, q = (float)((S *
+	// M) / n); the denoised source by denoise_spectral's path), then ssx_optics_images and ssx_develop_images on device 0: the same bits.
+	struct Optics { float cx = NAN, cy = NAN; uint32_t max_radius = 0; std::vector<float> scale; std::vector<uint32_t> radius; std::vector<float> taps; }; // a NaN centre: the image's middle; scale, radius [B], taps [B][2 R + 1]
+	std::vector<float> develop(const float* weights, size_t channels, const DenoiseParams* denoise = nullptr, const DemodParams* demod = nullptr, const Optics* optics = nullptr);
+	// the lens as a pure function on q [height][width][B] of the options' size (ssx_optics_images on device 0)
+	std::vector<float> optics_images(const float* q, const Optics& optics);
 
 	// The colour difference of two developments of this render (include/ssx.h "Colour difference of two developments"): the six [regions][2] arrays (metric 0
 	// dE*ab, 1 dE00), the five derived figures (image_io.hpp delta_e_derive) and, with `maps`, de [height][width][2].  A side is its [3][bins] weights (xyz space)
 	// and whether the bins are filtered first (then `denoise`, and `demod` for the demodulated mode, say how -- for both sides alike).  labels empty: the whole
 	// image is region 0 and regions must be 1.  One device and no demodulated side: ssx_spectral_delta_e.  Otherwise each side through develop() -- every pixel
 	// from the device that owns it -- then ssx_delta_e_images on device 0: the same bits.  The whites are the caller's (they set the absolute size of every dE).
-	struct DeltaESide { const float* weights = nullptr; bool denoised = false; };
+	struct DeltaESide { const float* weights = nullptr; bool denoised = false; const Optics* optics = nullptr; }; // optics: the side seen through a lens (develop)
 	struct DeltaE {
 		size_t regions = 0;
 		std::vector<double> SUM, SSQ, mean, rms, max, exceed, coverage; std::vector<float> MAX; std::vector<uint64_t> NF, NX, EX;

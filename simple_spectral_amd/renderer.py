@@ -381,6 +381,39 @@ def relight_gain(old, new, bins, lambda_min, lambda_step):
     return g
 
 
+def lens_optics(bins, lambda_min, lambda_step, lateral=0.0, sigma=0.0, axial=0.0, lambda_ref=550.0, max_radius=8, centre=None):
+    """ssh_optics_lens (include/ssx_host.h): the lens Renderer.develop(..., optics=) and Renderer.optics_images put in front of the bins of a render with this
+    lambda_min and lambda_step, as a dict {cx, cy, max_radius, scale [B], radius [B], taps [B, 2 R + 1]} -- what include/ssx.h's ssx_optics_params carries; any
+    dict of that form is a lens.  lateral: the magnification's relative change per relative wavelength offset from lambda_ref (lateral chromatic aberration);
+    sigma: the blur's standard deviation in pixels at lambda_ref, growing in proportion to the wavelength; axial: pixels of defocus blur per relative wavelength
+    offset.  centre (cx, cy) in pixel units; None: the middle of whatever image the lens is applied to."""
+    R = int(max_radius)
+    scale, radius, taps = np.zeros(bins, dtype=np.float32), np.zeros(bins, dtype=np.uint32), np.zeros((bins, 2 * max(R, 0) + 1), dtype=np.float32)
+    _host("ssh_optics_lens", int(bins), C.c_float(lambda_min), C.c_float(lambda_step), float(lambda_ref), float(lateral), float(sigma), float(axial), R,
+          scale.ctypes.data, radius.ctypes.data, taps.ctypes.data)
+    cx, cy = (None, None) if centre is None else centre
+    return {"cx": cx, "cy": cy, "max_radius": R, "scale": scale, "radius": radius, "taps": taps}
+
+
+def _optics_arg(optics, W, H):
+    """A lens dict (lens_optics) -> (SsxOpticsParams, the arrays that keep its tables alive).  The tables' shapes are the caller's business as far as the library
+    can check them itself; here only what would make it read past an array."""
+    R = int(optics["max_radius"])
+    scale = np.ascontiguousarray(optics["scale"], dtype=np.float32)
+    radius = np.ascontiguousarray(optics["radius"], dtype=np.uint32)
+    taps = np.ascontiguousarray(optics["taps"], dtype=np.float32)
+    B = scale.size
+    if scale.ndim != 1 or radius.shape != (B,) or (0 <= R <= _capi.SSX_OPTICS_MAX_RADIUS and taps.size != B * (2 * R + 1)):
+        raise ValueError("optics: scale and radius must have shape [B], taps [B, 2 * max_radius + 1]")
+    p = _capi.SsxOpticsParams()
+    p.struct_size = C.sizeof(_capi.SsxOpticsParams)
+    p.cx = W / 2.0 if optics.get("cx") is None else float(optics["cx"])
+    p.cy = H / 2.0 if optics.get("cy") is None else float(optics["cy"])
+    p.max_radius = R & 0xFFFFFFFF
+    p.scale, p.radius, p.taps = scale.ctypes.data, radius.ctypes.data, taps.ctypes.data
+    return p, (scale, radius, taps)
+
+
 def emitter_spectrum(desc):
     """ssh_emitter_spectrum: the index (in desc.spectra) of the emission spectrum all emissive materials share up to a scale; SsxError SSX_ERR_SCENE otherwise."""
     idx = C.c_uint32()
@@ -1040,11 +1073,13 @@ class Renderer:
 
     # ---- developing the bins (include/ssx.h: observers, filters, sensors) ----
 
-    def develop(self, weights, denoise=None, demodulate=None):
+    def develop(self, weights, denoise=None, demodulate=None, optics=None, return_bins=False):
         """ssx_spectral_develop: the bins the context holds, mapped on the device by weights [C, B] (develop_weights) -> float32 [H, W, C], row 0 = bottom.
         denoise None: the raw source, q = S * M / n; a dict of denoise_spectral's parameters (levels, sigma_l, sigma_a; {} for the defaults): the filtered bins,
         developed without leaving the device.  demodulate (True or a dict, as in denoise_spectral; denoise None counts as {}): ssx_spectral_develop_demod, the
-        bins filtered in the demodulated mode.  Nothing the context holds changes."""
+        bins filtered in the demodulated mode.  optics (a lens: lens_optics): ssx_spectral_develop_optics, the source through the lens before it is developed,
+        still on the device; with return_bins: (image, the bins behind the lens float32 [H, W, B]).  A demodulated source goes through the lens by way of the
+        host: denoise_spectral(demodulate=), optics_images, develop_images.  Nothing the context holds changes."""
         W, H = self.options.res
         w = np.ascontiguousarray(weights, dtype=np.float32)
         if w.ndim != 2:
@@ -1056,6 +1091,20 @@ class Renderer:
                                                               denoise.get("sigma_a", 0.1))
         if self._spectral_bins not in (0, w.shape[1]):
             raise ValueError("develop: weights for %d bins, the context holds %d" % (w.shape[1], self._spectral_bins))
+        if return_bins and optics is None:
+            raise ValueError("develop: return_bins needs optics")
+        if optics is not None and demodulate:
+            q = self.optics_images(self.denoise_spectral(levels=p.levels, sigma_l=p.sigma_l, sigma_a=p.sigma_a, demodulate=demodulate), optics)
+            out = self.develop_images(q, w)
+            return (out, q) if return_bins else out
+        if optics is not None:
+            op, keep = _optics_arg(optics, W, H)
+            if keep[0].size != w.shape[1]:
+                raise ValueError("develop: a lens for %d bins, weights for %d" % (keep[0].size, w.shape[1]))
+            bins_out = np.zeros((H, W, w.shape[1]), dtype=np.float32) if return_bins else None
+            self._check(self._lib.ssx_spectral_develop_optics(self._ctx, None if p is None else C.byref(p), C.byref(op), w.ctypes.data, w.shape[0], out.ctypes.data,
+                                                              None if bins_out is None else bins_out.ctypes.data))
+            return (out, bins_out) if return_bins else out
         if demodulate:
             dm, wx = self._demod_args(demodulate, w.shape[1])
             self._check(self._lib.ssx_spectral_develop_demod(self._ctx, C.byref(p), C.byref(dm), wx.ctypes.data, w.ctypes.data, w.shape[0], out.ctypes.data))
@@ -1072,6 +1121,20 @@ class Renderer:
         H, W, B = q.shape
         out = np.zeros((H, W, w.shape[0]), dtype=np.float32)
         self._check(self._lib.ssx_develop_images(self._ctx, W, H, B, q.ctypes.data, w.ctypes.data, w.shape[0], out.ctypes.data))
+        return out
+
+    def optics_images(self, q, optics):
+        """ssx_optics_images: the lens (lens_optics) as a pure function: q [H, W, B] -> float32 [H, W, B], each bin resampled about the optical centre with its
+        own magnification and blurred with its own separable kernel (include/ssx.h "Developing through a lens")."""
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        if q.ndim != 3:
+            raise ValueError("optics_images: q must have shape [H, W, B]")
+        H, W, B = q.shape
+        op, keep = _optics_arg(optics, W, H)
+        if keep[0].size != B:
+            raise ValueError("optics_images: a lens for %d bins, q has %d" % (keep[0].size, B))
+        out = np.zeros((H, W, B), dtype=np.float32)
+        self._check(self._lib.ssx_optics_images(self._ctx, W, H, B, q.ctypes.data, C.byref(op), out.ctypes.data))
         return out
 
     def debug_sample_flux(self, **over):

@@ -1,0 +1,49 @@
+"""The lens from the command line (include/ssx.h "Developing through a lens"): --develop-lens with --develop-output writes the bytes the Python path writes,
+on one device and on two (SSX_TEST_ONE_GPU=1: both on the one GPU), where the host gathers the bins and runs the pure entries."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from simple_spectral_amd import Options, Renderer
+from simple_spectral_amd.renderer import develop_weights, lens_optics
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CLI = os.path.join(ROOT, "simple-spectral")
+W, H, SEED, SPP, BINS = 24, 16, 5, 8, 8
+
+
+def test_cli_develops_through_the_lens(tmp_path):
+    r = Renderer(Options(scene_name="cornell-srgb", res=(W, H), seed=SEED, texture="test-img.png"))
+    r.set_spectral_bins(BINS)
+    r._check(r._lib.ssx_render_start(r._ctx, C.byref(r.params(spp=SPP))))
+    r.render_wait()
+    d = r.scene.desc.contents
+    lmin, lstep = float(d.lambda_min), float(d.lambda_step)
+    w = develop_weights(BINS, lmin, lstep)
+    lens = lens_optics(BINS, lmin, lstep, lateral=0.02, sigma=0.7, axial=3.0, lambda_ref=520.0, max_radius=5)
+    assert (lens["scale"] != 1).any() and lens["radius"].max() == 5 and len(set(lens["radius"].tolist())) > 1
+
+    def save(xyz, name):
+        r.framebuffer = r.scene.xyza_to_srgba(np.concatenate([xyz, r.xyza[..., 3:]], axis=2))
+        r.save(str(tmp_path / name))
+        return open(str(tmp_path / name), "rb").read()
+
+    plain, through = save(r.develop(w), "plain.pfm"), save(r.develop(w, optics=lens), "lens.pfm")
+    assert plain != through
+    common = [CLI, "-s=cornell-srgb", "-w=%d" % W, "-h=%d" % H, "-spp=%d" % SPP, "--seed=%d" % SEED, "--texture=data/scenes/test-img.png", "-o=" + str(tmp_path / "o.pfm"),
+              "--spectral-bins=%d" % BINS]
+    flags = ["--develop-lens=0.02,0.7,3,520", "--develop-lens-radius=5"]
+    env = dict(os.environ, SSX_TEST_ONE_GPU="1")
+    for n, (want, extra) in enumerate(((through, flags), (through, flags + ["--gpus=2"]), (plain, []))):
+        path = str(tmp_path / ("d%d.pfm" % n))
+        p = subprocess.run(common + ["--develop-output=" + path] + extra, cwd=ROOT, capture_output=True, text=True, env=env)
+        assert p.returncode == 0, p.stderr
+        assert open(path, "rb").read() == want, extra
+    # refused where --develop-output is refused, and without it
+    for extra in (flags, ["--develop-output=" + str(tmp_path / "x.pfm"), "--rgb"] + flags, ["--develop-output=" + str(tmp_path / "x.pfm"), "--develop-lens=1,2"]):
+        p = subprocess.run(common[:-1] + (["--spectral-bins=%d" % BINS] if "--rgb" not in extra else []) + extra, cwd=ROOT, capture_output=True, text=True, env=env)
+        assert p.returncode != 0, extra

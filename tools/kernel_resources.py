@@ -15,7 +15,7 @@ with tempfile.TemporaryDirectory() as td:
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-S", "--cuda-device-only", "-o", asm,
                            os.path.join(ROOT, "simple_spectral_amd", "csrc", "ssx_kernels.hip" if probe else "ssx_api.hip")] + (["-DSSX_PROBE_BUILD"] if probe else []) + sys.argv[1:], stderr=subprocess.DEVNULL)
     t = open(asm).read()
-print("%-28s %6s %6s %6s %6s %8s" % ("kernel", "vgpr", "vspill", "sgpr", "sspill", "scratch"))
+print("%-28s %6s %6s %6s %6s %8s %8s" % ("kernel", "vgpr", "vspill", "sgpr", "sspill", "scratch", "lds"))
 for b in t.split("  - .agpr_count:")[1:]:
     g = lambda k: re.search(r"\." + k + r":\s+(\S+)", b).group(1)
-    print("%-28s %6s %6s %6s %6s %8s" % (g("name"), g("vgpr_count"), g("vgpr_spill_count"), g("sgpr_count"), g("sgpr_spill_count"), g("private_segment_fixed_size")))
+    print("%-28s %6s %6s %6s %6s %8s %8s" % (g("name"), g("vgpr_count"), g("vgpr_spill_count"), g("sgpr_count"), g("sgpr_spill_count"), g("private_segment_fixed_size"), g("group_segment_fixed_size")))
