@@ -956,6 +956,67 @@ int ssx_optics_images(ssx_ctx* ctx, uint32_t width, uint32_t height, uint32_t bi
 int ssx_spectral_develop_optics(ssx_ctx* ctx, const ssx_denoise_params* denoise /* or NULL */, const ssx_optics_params* optics, const float* weights /* [C][B] */,
                                 uint32_t channels, float* out /* [H][W][C] or NULL */, float* bins_out /* [H][W][B] or NULL */);
 
+/* ---- Depth of field after the render: per-bin defocus from the depth guide (appended; same ABI version) -------------------------------------------------
+ * The lens above has no aperture: its blur is the same everywhere in the frame.  This section gives it one, still after the render (the camera of the path
+ * kernels is a pinhole and stays one): every (pixel, bin) is spread over a disc whose radius -- the circle of confusion -- grows with the distance, in inverse
+ * depth, between the pixel's surface (the depth guide of ssx_guides) and the bin's focus.  A focus that moves with the wavelength is longitudinal chromatic
+ * aberration: surfaces in front of and behind the focus fringe in different colours.  The result is again q [height][width][B].  The definition is this
+ * library's; a restatement in numpy gives the same bits (tests/defocus_ref.py).
+ *
+ * All arithmetic is binary32 IEEE in the order written, every product rounded before the add, no contraction, no reassociation; min and max as above
+ * (a NaN first argument gives the second); sqrtf and / are correctly rounded; non-finite values go through the arithmetic as they are.  Input q[H][W][B]
+ * row-major, row 0 = bottom, B in {4, 8, ..., 64}; depth[H][W]; parameters: ssx_defocus_params below, R = max_radius, K = gain, f_b = focus[b].
+ *
+ * DEFOCUS.  Per pixel s:
+ *       inv[s] = depth[s] > 0.0f ? 1.0f / depth[s] : 0.0f
+ *   a miss (depth 0), a NaN, a negative depth and +inf are all "infinitely far".  Per pixel s and bin b:
+ *       c[s][b] = min(fabsf(inv[s] - f_b) * K, (float)R)                          the circle of confusion, in pixels
+ *       a[s][b] = 1.0f / (3.14159274f * ((c * c + c) + 0.333333343f))             c = c[s][b]
+ *   the divisor is the integral over the plane of the cover function below (a disc of radius c with a linear skirt one pixel wide): a wide disc is
+ *   correspondingly faint.  Per destination pixel p = (i, j) and bin b:
+ *       sw = 0.0f;   sq = 0.0f
+ *       for dy = -R .. R ascending, and inside it for dx = -R .. R ascending:   s = (i + dx, j + dy), skipped where it lies outside the image
+ *           ce = inv[s] < inv[p] ? min(c[s][b], c[p][b]) : c[s][b]
+ *           dist = sqrtf((float)(dx * dx + dy * dy));   cover = min(max((ce + 1.0f) - dist, 0.0f), 1.0f)
+ *           taken only if cover > 0.0f:   w = cover * a[s][b];   sw = sw + w;   sq = sq + w * q[s][b]
+ *       out[p][b] = sq / sw
+ *   The border is NOT replicated: the sum is normalised, so the frame does not darken.  ce: a source behind the destination cannot spread over it further than
+ *   the destination's own blur, so a sharp foreground stays clean against a blurred background (and a blurred foreground still spreads over a sharp
+ *   background).  A non-finite q outside its own disc poisons nothing: its tap is not taken.  The centre tap always counts (cover == 1, a > 0): sw > 0.
+ *   With K == 0 or R == 0 the stage is a bit-for-bit copy and nothing is launched.  ELSEWHERE AN IN-FOCUS PIXEL IS NOT COPIED: a pixel that only its own tap
+ *   reaches comes out as (a * q) / a with a = a[p][b] -- two roundings from q, not q.
+ * THE THIN LENS is the hosts' (libssx_host.so ssh_defocus_thin_lens, include/ssx_host.h): K and f_b from an aperture, a focus distance and an axial
+ *   coefficient.  The guide's depth is a RAY LENGTH from the eye, not a distance along the optical axis: the surface in focus is a sphere about the eye.
+ * SAME BITS: the numpy restatement; ssx_spectral_develop_lens against ssx_defocus_images (q rebuilt from the exported sums or ssx_denoise_spectral's output,
+ *   depth from ssx_guides), ssx_optics_images and ssx_develop_images in a chain; defocus == NULL against ssx_spectral_develop_optics; both NULL against
+ *   ssx_spectral_develop.
+ *
+ * ON THE DEVICE (csrc/ssx_defocus.hip) two kernels, neither with atomics, a lane writing only its own output: ssx_defocus_prepare_kernel writes inv[H][W] and
+ * a[H][W][B] (c is three operations on inv and f_b, and the gather redoes them in registers, to the same bits, instead of reading a third array);
+ * ssx_defocus_gather_kernel stages a tile of 16 x 16 pixels with its apron of R pixels, four bins at a time, in LDS and walks (dy, dx) uniformly across the wave.
+ * With the feature unused nothing is allocated and nothing is launched. */
+#define SSX_DEFOCUS_MAX_RADIUS 12u
+typedef struct ssx_defocus_params {
+	uint32_t struct_size;      /* sizeof(ssx_defocus_params) */
+	uint32_t max_radius;       /* R, 0..SSX_DEFOCUS_MAX_RADIUS: the largest circle of confusion, in pixels */
+	float gain;                /* K: pixels of blur radius per unit of inverse-depth offset; finite, >= 0 */
+	const float* focus;        /* [B]   f_b: the inverse focus distance of bin b; finite, >= 0 (0: focused at infinity) */
+} ssx_defocus_params;
+
+/* DEFOCUS as a pure function of its arguments (needs no scene): q [height][width][bins], depth [height][width] -> out [height][width][bins], row-major floats.
+ * SSX_ERR_ARG, with ssx_last_error naming the field: a NULL pointer (q, depth, out, defocus, focus), a wrong struct_size, max_radius above 12, a gain or a
+ * focus[b] that is not finite or is negative, bins not a multiple of 4 in 4..64, an empty or too large image.  SSX_ERR_STATE: a render runs. */
+int ssx_defocus_images(ssx_ctx* ctx, uint32_t width, uint32_t height, uint32_t bins, const float* q /* [H][W][B] */, const float* depth /* [H][W] */,
+                       const ssx_defocus_params* defocus, float* out /* [H][W][B] */);
+/* ssx_spectral_develop_optics with an aperture: the source as there (raw through the same unpack kernel, or denoised); DEFOCUS on it with the context's own
+ * guide depth (the guides are computed if they are not yet held); then WARP and BLUR; then the develop kernels.  DEFOCUS comes first because the depth map is
+ * registered to the unwarped pixels.  defocus NULL: no DEFOCUS -- the bits of ssx_spectral_develop_optics; optics NULL: no WARP or BLUR; both NULL: the bits of
+ * ssx_spectral_develop.  out, bins_out and weights as in ssx_spectral_develop_optics.  It reads only.  SSX_ERR_STATE with ssx_spectral_develop_optics's
+ * reasons, tile_stride != 1 among them (whatever is NULL); SSX_ERR_ARG: what ssx_defocus_images, ssx_optics_images and ssx_spectral_develop refuse. */
+int ssx_spectral_develop_lens(ssx_ctx* ctx, const ssx_denoise_params* denoise /* or NULL */, const ssx_defocus_params* defocus /* or NULL */,
+                              const ssx_optics_params* optics /* or NULL */, const float* weights /* [C][B] */, uint32_t channels,
+                              float* out /* [H][W][C] or NULL */, float* bins_out /* [H][W][B] or NULL */);
+
 /* ---- Diagnostics for the parity tests (not part of the reference's interface) ---------------------
  * ssx_debug_eval runs one building block of the path kernel -- the same device function the kernel
  * inlines -- on n items, one per lane: `in` holds in_words 32-bit words per item, `out` receives

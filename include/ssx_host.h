@@ -165,6 +165,22 @@ int ssh_develop_white(const float* weights, uint32_t bins, float lambda_min, flo
  * SSX_ERR_ARG: NULL pointers, bins not a multiple of 4 in 4..64, max_radius above 12, a non-finite argument, lambda_step or lambda_ref not positive, sigma_ref < 0. */
 int ssh_optics_lens(uint32_t bins, float lambda_min, float lambda_step, double lambda_ref, double lateral, double sigma_ref, double axial, uint32_t max_radius,
                     float* scale_out, uint32_t* radius_out, float* taps_out);
+/* A thin lens for ssx_defocus_images / ssx_spectral_develop_lens (ssx.h "Depth of field after the render"): the gain K and the per-bin inverse focus distances of
+ * ssx_defocus_params for a render with this vertical field of view (ssh_scene_vfov), `height` rows and `bins` bins of this lambda_min and lambda_step, from an aperture diameter and a focus distance in scene units and an axial
+ * coefficient (inverse scene units per unit of relative wavelength offset: longitudinal chromatic aberration).  Binary64, IEEE operations in the order written,
+ * libm's tan, rounded to binary32 once at the end.  M = bins / 4:
+ *     vfov = (double)vfov_deg * (3.14159265358979323846 / 180.0);     v_px = ((double)height / 2.0) / tan(vfov / 2.0)     the image distance in pixels
+ *     gain = (float)(0.5 * aperture * v_px)                                                  the blur RADIUS in pixels per unit of inverse-depth offset
+ *     lc_b = (double)lambda_min + (b + 0.5) * ((double)lambda_step / M);   u = (lc_b - lambda_ref) / lambda_ref
+ *     focus_b = (float)max(0.0, 1.0 / focus_distance + axial * u)
+ * A point at distance z then has the circle of confusion 0.5 * aperture * v_px * |1 / z - focus_b| pixels: the thin lens focused far beyond its focal length.  The
+ * depth guide is a RAY LENGTH from the eye, so the surface in focus is a sphere about the eye of radius 1 / focus_b, not a plane; a planar focus is out of scope.
+ * aperture = 0 gives gain 0: the identity.  focus_out [bins].  SSX_ERR_ARG: NULL pointers, a vfov_deg outside (0, 180), bins not a multiple of 4 in 4..64, height 0, a lambda_step not positive, an aperture that is not
+ * finite or negative, a focus_distance or lambda_ref not finite and positive, an axial that is not finite, a result that is not finite in binary32. */
+int ssh_defocus_thin_lens(float vfov_deg, uint32_t height, uint32_t bins, float lambda_min, float lambda_step, double aperture, double focus_distance, double axial,
+                          double lambda_ref, float* gain_out, float* focus_out);
+/* *vfov_deg = the vertical field of view of the scene's camera in degrees (what ssh_defocus_thin_lens takes; the scene description carries only the matrix). */
+int ssh_scene_vfov(const ssh_scene* scene, float* vfov_deg);
 /* *spectrum = index (in desc->spectra) of the emission spectrum that all emissive materials of the scene share up to a scale.  SSX_ERR_SCENE, with the reason in
  * ssh_last_error, when two of them differ or none is emissive: what the CLI's --develop-relight refuses. */
 int ssh_emitter_spectrum(const ssx_scene_desc* desc, uint32_t* spectrum);

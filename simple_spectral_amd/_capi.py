@@ -99,6 +99,14 @@ class SsxOpticsParams(C.Structure):
 SSX_OPTICS_MAX_RADIUS = 12  # include/ssx.h
 
 
+class SsxDefocusParams(C.Structure):
+    """ssx_defocus_params: the largest circle of confusion, the gain and the per-bin inverse focus distances of the aperture."""
+    _fields_ = [("struct_size", C.c_uint32), ("max_radius", C.c_uint32), ("gain", C.c_float), ("focus", C.c_void_p)]
+
+
+SSX_DEFOCUS_MAX_RADIUS = 12  # include/ssx.h
+
+
 class SshSpectrum(C.Structure):
     """ssh_spectrum_t: n uniform samples over [low, high] (include/ssx_host.h)."""
     _fields_ = [("samples", C.POINTER(C.c_float)), ("n", C.c_uint32), ("low", C.c_float), ("high", C.c_float)]
@@ -134,6 +142,7 @@ HIP_SYMBOLS = ["ssx_create", "ssx_destroy", "ssx_upload_scene", "ssx_render_star
                "ssx_spectral_compare", "ssx_spectral_compare_arrays",
                "ssx_delta_e_images", "ssx_spectral_delta_e",
                "ssx_optics_images", "ssx_spectral_develop_optics",
+               "ssx_defocus_images", "ssx_spectral_develop_lens",
                "ssx_debug_tile_mask", "ssx_debug_spectral_accumulate", "ssx_debug_fold", "ssx_debug_step"]
 # ssx_debug_fold: a sample's row of levels (include/ssx.h)
 SSX_FOLD_ROW_WORDS, SSX_FOLD_LAMBDA0, SSX_FOLD_CAM_DIR, SSX_FOLD_HIT, SSX_FOLD_N, SSX_FOLD_LEVEL0, SSX_FOLD_LEVEL_WORDS = 160, 0, 1, 4, 5, 10, 15
@@ -164,7 +173,7 @@ HOST_SYMBOLS = ["ssh_scene_create", "ssh_scene_create_ex", "ssh_scene_destroy", 
                 "ssh_checkpoint_save_moments", "ssh_checkpoint_load_moments", "ssh_moments_merge",
                 "ssh_compare_derive", "ssh_compare_save_csv",
                 "ssh_delta_e_derive", "ssh_delta_e_save_csv", "ssh_develop_white",
-                "ssh_optics_lens"]
+                "ssh_optics_lens", "ssh_defocus_thin_lens", "ssh_scene_vfov"]
 
 _hip = None
 _host = None
@@ -219,6 +228,8 @@ def host_lib():
         lib.ssh_relight_gain.argtypes = [C.POINTER(SshSpectrum), C.POINTER(SshSpectrum), C.c_uint32, C.c_float, C.c_float, vp]
         lib.ssh_emitter_spectrum.argtypes = [C.POINTER(SsxSceneDesc), C.POINTER(C.c_uint32)]
         lib.ssh_optics_lens.argtypes = [C.c_uint32, C.c_float, C.c_float, C.c_double, C.c_double, C.c_double, C.c_double, C.c_uint32, vp, vp, vp]
+        lib.ssh_defocus_thin_lens.argtypes = [C.c_float, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp]
+        lib.ssh_scene_vfov.argtypes = [vp, vp]
         _host = lib
     return _host
 
@@ -412,6 +423,9 @@ def hip_lib():
         if not override or hasattr(lib, "ssx_optics_images"):  # developing through a lens: per-bin warp and blur
             lib.ssx_optics_images.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.POINTER(SsxOpticsParams), vp]
             lib.ssx_spectral_develop_optics.argtypes = [vp, C.POINTER(SsxDenoiseParams), C.POINTER(SsxOpticsParams), vp, C.c_uint32, vp, vp]
+        if not override or hasattr(lib, "ssx_defocus_images"):  # depth of field after the render: per-bin defocus from the depth guide
+            lib.ssx_defocus_images.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(SsxDefocusParams), vp]
+            lib.ssx_spectral_develop_lens.argtypes = [vp, C.POINTER(SsxDenoiseParams), C.POINTER(SsxDefocusParams), C.POINTER(SsxOpticsParams), vp, C.c_uint32, vp, vp]
         if not override or hasattr(lib, "ssx_spectral_moments_import"):  # the second moments through checkpoint and resume
             lib.ssx_spectral_moments_import.argtypes = [vp, C.POINTER(SsxSpectralInfo), vp]
         if not override or hasattr(lib, "ssx_debug_tile_mask"):  # the camera-ray pre-trace's tile masks, read back

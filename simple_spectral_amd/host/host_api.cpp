@@ -364,6 +364,39 @@ int ssh_optics_lens(uint32_t bins, float lambda_min, float lambda_step, double l
 	return SSX_OK;
 }
 
+int ssh_scene_vfov(const ssh_scene* scene, float* vfov_deg) {
+	if (!scene || !vfov_deg) { g_error = "NULL argument"; return SSX_ERR_ARG; }
+	*vfov_deg = scene->scene->camera.vfov_deg;
+	return SSX_OK;
+}
+
+int ssh_defocus_thin_lens(float vfov_deg, uint32_t height, uint32_t bins, float lambda_min, float lambda_step, double aperture, double focus_distance, double axial,
+                          double lambda_ref, float* gain_out, float* focus_out) {
+	if (!gain_out || !focus_out) { g_error = "NULL argument"; return SSX_ERR_ARG; }
+	if (!(vfov_deg > 0.0f) || !(vfov_deg < 180.0f)) { g_error = "ssh_defocus_thin_lens: vfov_deg must lie in (0, 180)"; return SSX_ERR_ARG; }
+	if (!std::isfinite(lambda_min) || !std::isfinite(lambda_step) || !(lambda_step > 0.0f)) { g_error = "ssh_defocus_thin_lens: lambda_min must be finite, lambda_step finite and positive"; return SSX_ERR_ARG; }
+	if (bins < 4u || bins > 64u || (bins & 3u)) { g_error = "ssh_defocus_thin_lens: bins must be a multiple of 4 up to 64"; return SSX_ERR_ARG; }
+	if (height == 0u) { g_error = "ssh_defocus_thin_lens: height must be positive"; return SSX_ERR_ARG; }
+	if (!std::isfinite(aperture) || aperture < 0.0) { g_error = "ssh_defocus_thin_lens: aperture must be finite and >= 0"; return SSX_ERR_ARG; }
+	if (!std::isfinite(focus_distance) || !(focus_distance > 0.0)) { g_error = "ssh_defocus_thin_lens: focus_distance must be finite and positive"; return SSX_ERR_ARG; }
+	if (!std::isfinite(axial)) { g_error = "ssh_defocus_thin_lens: axial must be finite"; return SSX_ERR_ARG; }
+	if (!std::isfinite(lambda_ref) || !(lambda_ref > 0.0)) { g_error = "ssh_defocus_thin_lens: lambda_ref must be finite and positive"; return SSX_ERR_ARG; }
+	const double vfov = static_cast<double>(vfov_deg) * (3.14159265358979323846 / 180.0);
+	const double v_px = (static_cast<double>(height) / 2.0) / std::tan(vfov / 2.0);
+	const float K = static_cast<float>(0.5 * aperture * v_px);
+	if (!std::isfinite(K)) { g_error = "ssh_defocus_thin_lens: the aperture gives a gain that is not finite"; return SSX_ERR_ARG; }
+	*gain_out = K;
+	const double width = static_cast<double>(lambda_step) / (bins / 4u);
+	for (uint32_t b = 0; b < bins; ++b) {
+		const double lc = static_cast<double>(lambda_min) + (b + 0.5) * width;
+		const double u = (lc - lambda_ref) / lambda_ref;
+		const double f = 1.0 / focus_distance + axial * u;
+		focus_out[b] = static_cast<float>(f > 0.0 ? f : 0.0);
+		if (!std::isfinite(focus_out[b])) { g_error = "ssh_defocus_thin_lens: bin " + std::to_string(b) + " gets an inverse focus distance that is not finite"; return SSX_ERR_ARG; }
+	}
+	return SSX_OK;
+}
+
 int ssh_emitter_spectrum(const ssx_scene_desc* desc, uint32_t* spectrum) {
 	if (!desc || !spectrum) { g_error = "NULL argument"; return SSX_ERR_ARG; }
 	try { *spectrum = ssx::emitter_spectrum(*desc); return SSX_OK; }

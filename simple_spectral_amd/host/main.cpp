@@ -21,7 +21,8 @@
 // filtered one only if --denoise is given too.
 // Developing the bins (include/ssx.h "Developing the spectral bins"): --develop-output=PATH with --spectral-bins=N writes the image developed from the bins on the
 // device -- through the same XYZ -> sRGB store and writers as --output -- under --develop-observer=1931|2006 (default: the render's), through --develop-filter=FILE.csv
-// (--develop-lens=lateral,sigma,axial[,lambda_ref] with --develop-lens-radius=R puts a lens in front: include/ssx.h "Developing through a lens")
+// (--develop-lens=lateral,sigma,axial[,lambda_ref] with --develop-lens-radius=R puts a lens in front: include/ssx.h "Developing through a lens";
+// --develop-defocus=aperture,focus_distance[,axial[,lambda_ref]] with --develop-defocus-radius=R gives it an aperture: "Depth of field after the render")
 // (a spectrum in the format of data/*.csv, its range in the name: NAME-LOW+STEP+HIGH.csv) and relit by --develop-relight=NEW.csv (the emitters' spectrum replaced by
 // NEW; refused unless all emissive materials share one spectrum up to a scale).  With --spectral-denoise the filtered bins are developed.  It does not need
 // --spectral-output, and has its refusals (--tile-major, --rgb, --libm=glibc-2.35; --resume of a checkpoint without the bins).  With --resume, --spectral-bins may
@@ -107,6 +108,9 @@ void print_usage() {
 		"    [`--develop-lens=<lateral>,<sigma>,<axial>[,<lambda_ref=550>]`] [`--develop-lens-radius=<0..12, default 8>`] [`--delta-e-lens=...`]\n"
 		"          (the bins through a lens before they are developed: lateral chromatic aberration, a blur of <sigma> pixels at <lambda_ref> growing with the\n"
 		"           wavelength, <axial> pixels of defocus per relative wavelength offset; for `--develop-output` and side A of `--delta-e-*`, `--delta-e-lens` for side B)\n"
+		"    [`--develop-defocus=<aperture>,<focus_distance>[,<axial=0>[,<lambda_ref=550>]]`] [`--develop-defocus-radius=<0..12, default 8>`] [`--delta-e-defocus=...`]\n"
+		"          (depth of field from the depth guide before the lens: an aperture of diameter <aperture> focused at <focus_distance>, both in scene units, the\n"
+		"           inverse focus distance moving by <axial> per relative wavelength offset; sides as for `--develop-lens`)\n"
 		"    `--demodulate[=1|2|4]` (with `--spectral-denoise`: filter illumination -- divide by the first-hit albedo per bin, <k> x <k> rays per pixel, before; multiply after)\n"
 		"    `--albedo-output=<file.npy>` (needs `--spectral-bins=<n>`: the first-hit albedo per wavelength bin)\n"
 		"    `--spectral-variance-output=<file.npy>` (needs `--spectral-bins=<n>`: the variance of every bin mean)\n"
@@ -204,6 +208,11 @@ struct Progressive { // the flags of the progressive modes
 	struct Lens { bool on = false; double lateral = 0.0, sigma = 0.0, axial = 0.0, lambda_ref = 550.0; };
 	Lens develop_lens, delta_e_lens;
 	unsigned develop_lens_radius = 8;
+	// the aperture (include/ssx.h "Depth of field after the render"; ssh_defocus_thin_lens): --develop-defocus=aperture,focus_distance[,axial[,lambda_ref]] and
+	// --delta-e-defocus=... for the same sides, --develop-defocus-radius=R (the largest circle of confusion, for both)
+	struct Aperture { bool on = false; double aperture = 0.0, focus_distance = 1.0, axial = 0.0, lambda_ref = 550.0; };
+	Aperture develop_defocus, delta_e_defocus;
+	unsigned develop_defocus_radius = 8;
 	bool spectral_bins_given = false;
 	bool demodulate = false;     // --demodulate[=K]
 	ssx::Renderer::DemodParams demod_params;
@@ -346,6 +355,36 @@ void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progress
 		g->develop_lens_radius = static_cast<unsigned>(r);
 		lens_radius_given = true;
 	}
+	auto take_aperture = [&](const char* flag, Progressive::Aperture* ap) {
+		if (!a.take(flag, "", &v)) return;
+		double x[4] = { 0.0, 1.0, 0.0, 550.0 };
+		size_t n = 0, at = 0;
+		bool ok = true;
+		try {
+			while (ok && n < 4) {
+				const size_t comma = v.find(',', at);
+				const std::string part = v.substr(at, comma == std::string::npos ? std::string::npos : comma - at);
+				size_t used = 0;
+				x[n++] = std::stod(part, &used);
+				ok = used == part.size() && std::isfinite(x[n - 1]);
+				if (comma == std::string::npos) break;
+				at = comma + 1;
+				if (n == 4) ok = false;
+			}
+		} catch (...) { ok = false; }
+		if (!ok || n < 2 || x[0] < 0.0 || !(x[1] > 0.0) || !(x[3] > 0.0)) { std::fprintf(stderr, "Invalid value for %s (<aperture>,<focus_distance>[,<axial>[,<lambda_ref>]]: finite, aperture >= 0, focus_distance > 0, lambda_ref > 0)!\n", flag); throw -2; }
+		ap->on = true; ap->aperture = x[0]; ap->focus_distance = x[1]; ap->axial = x[2]; ap->lambda_ref = x[3];
+	};
+	take_aperture("--develop-defocus", &g->develop_defocus);
+	take_aperture("--delta-e-defocus", &g->delta_e_defocus);
+	bool defocus_radius_given = false;
+	if (a.take("--develop-defocus-radius", "", &v)) {
+		size_t r = 99;
+		try { r = v == "0" ? 0 : to_pos(v); } catch (int) { r = 99; }
+		if (r > SSX_DEFOCUS_MAX_RADIUS) { std::fprintf(stderr, "Invalid value for --develop-defocus-radius (0..12)!\n"); throw -2; }
+		g->develop_defocus_radius = static_cast<unsigned>(r);
+		defocus_radius_given = true;
+	}
 	if (a.take("--delta-e-output", "", &v)) g->delta_e_output = v;
 	if (a.take("--delta-e-csv", "", &v)) g->delta_e_csv = v;
 	if (a.take("--delta-e-filter", "", &v)) g->delta_e_filter = v;
@@ -379,10 +418,11 @@ void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progress
 		catch (...) { std::fprintf(stderr, "Invalid value for --delta-e-white-y (finite and > 0)!\n"); throw -2; }
 		delta_e_side = true;
 	}
-	if (g->delta_e_lens.on) delta_e_side = true;
+	if (g->delta_e_lens.on || g->delta_e_defocus.on) delta_e_side = true;
+	if (defocus_radius_given && !g->develop_defocus.on && !g->delta_e_defocus.on) { std::fprintf(stderr, "`--develop-defocus-radius` needs `--develop-defocus` or `--delta-e-defocus`!\n"); throw -2; }
 	if (lens_radius_given && !g->develop_lens.on && !g->delta_e_lens.on) { std::fprintf(stderr, "`--develop-lens-radius` needs `--develop-lens` or `--delta-e-lens`!\n"); throw -2; }
 	if (delta_e_side && !g->delta_e()) {
-		std::fprintf(stderr, "`--delta-e-observer`, `--delta-e-filter`, `--delta-e-relight`, `--delta-e-denoise`, `--delta-e-threshold`, `--delta-e-white-y` and `--delta-e-lens` need `--delta-e-output=<file.npy>` or `--delta-e-csv=<file.csv>`!\n");
+		std::fprintf(stderr, "`--delta-e-observer`, `--delta-e-filter`, `--delta-e-relight`, `--delta-e-denoise`, `--delta-e-threshold`, `--delta-e-white-y`, `--delta-e-lens` and `--delta-e-defocus` need `--delta-e-output=<file.npy>` or `--delta-e-csv=<file.csv>`!\n");
 		throw -2;
 	}
 	if (a.take("--spectral-bins", "", &v)) {
@@ -413,8 +453,8 @@ void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progress
 		std::fprintf(stderr, "`--spectral-output` cannot be combined with `--tile-major`, `--rgb` or `--libm=glibc-2.35`!\n");
 		throw -2;
 	}
-	if (g->develop_output.empty() && !g->delta_e() && (!g->develop_filter.empty() || !g->develop_relight.empty() || g->develop_observer || g->develop_lens.on)) {
-		std::fprintf(stderr, "`--develop-observer`, `--develop-filter`, `--develop-relight` and `--develop-lens` need `--develop-output=<image>`!\n");
+	if (g->develop_output.empty() && !g->delta_e() && (!g->develop_filter.empty() || !g->develop_relight.empty() || g->develop_observer || g->develop_lens.on || g->develop_defocus.on)) {
+		std::fprintf(stderr, "`--develop-observer`, `--develop-filter`, `--develop-relight`, `--develop-lens` and `--develop-defocus` need `--develop-output=<image>`!\n");
 		throw -2;
 	}
 	if (g->delta_e() && !g->spectral_bins_given) {
@@ -641,6 +681,21 @@ int main(int argc, char* argv[]) {
 		make_lens(prog.delta_e_lens, &lens_b);
 		const ssx::Renderer::Optics* const optics_a = prog.develop_lens.on ? &lens_a : nullptr;
 		const ssx::Renderer::Optics* const optics_b = prog.delta_e_lens.on ? &lens_b : nullptr;
+		// ... and the apertures
+		ssx::Renderer::Defocus aperture_a, aperture_b;
+		auto make_aperture = [&](const Progressive::Aperture& ap, ssx::Renderer::Defocus* f) {
+			if (!ap.on) return;
+			const ssx_scene_desc& d = renderer.scene->desc();
+			const uint32_t B = static_cast<uint32_t>(prog.spectral_bins);
+			f->max_radius = prog.develop_defocus_radius; f->focus.resize(B);
+			if (ssh_defocus_thin_lens(renderer.scene->camera.vfov_deg, static_cast<uint32_t>(options.res[1]), B, d.lambda_min, d.lambda_step, ap.aperture, ap.focus_distance, ap.axial,
+			                          ap.lambda_ref, &f->gain, f->focus.data()) != SSX_OK)
+				throw ssx::HostError{ SSX_ERR_ARG, std::string("--develop-defocus / --delta-e-defocus: ") + ssh_last_error() };
+		};
+		make_aperture(prog.develop_defocus, &aperture_a);
+		make_aperture(prog.delta_e_defocus, &aperture_b);
+		const ssx::Renderer::Defocus* const defocus_a = prog.develop_defocus.on ? &aperture_a : nullptr;
+		const ssx::Renderer::Defocus* const defocus_b = prog.delta_e_defocus.on ? &aperture_b : nullptr;
 		// side B of --delta-e-*, and both sides' whites up to the common scale (host policy: the chromaticity is the development, by the side's weights without a
 		// relighting gain, of the side's illuminant -- the relight's new one, else the scene's emitter spectrum where it has one, else D65)
 		std::vector<float> delta_e_weights;
@@ -757,7 +812,7 @@ int main(int argc, char* argv[]) {
 			double scale = 0.0;
 			if (prog.delta_e_white_y > 0.0) scale = prog.delta_e_white_y / delta_e_white[0][1];
 			else {
-				const std::vector<float> xyz = renderer.develop(develop_weights.data(), 3, prog.spectral_denoise ? dn : nullptr, prog.spectral_denoise ? dm : nullptr, optics_a);
+				const std::vector<float> xyz = renderer.develop(develop_weights.data(), 3, prog.spectral_denoise ? dn : nullptr, prog.spectral_denoise ? dm : nullptr, optics_a, defocus_a);
 				double sum = 0.0; size_t n = 0;
 				for (size_t p = 0; p < pixels; ++p) if (std::isfinite(xyz[3 * p + 1])) { sum += static_cast<double>(xyz[3 * p + 1]); ++n; }
 				const double mean = n ? sum / static_cast<double>(n) : 0.0;
@@ -765,7 +820,7 @@ int main(int argc, char* argv[]) {
 				scale = (mean / 0.18) / delta_e_white[0][1];
 			}
 			for (int x = 0; x < 2; ++x) for (int c = 0; c < 3; ++c) delta_e_white[x][c] *= scale;
-			const ssx::Renderer::DeltaESide side_a{ develop_weights.data(), prog.spectral_denoise, optics_a }, side_b{ delta_e_weights.data(), prog.delta_e_denoise, optics_b };
+			const ssx::Renderer::DeltaESide side_a{ develop_weights.data(), prog.spectral_denoise, optics_a, defocus_a }, side_b{ delta_e_weights.data(), prog.delta_e_denoise, optics_b, defocus_b };
 			const ssx::Renderer::DeltaE e = renderer.delta_e(side_a, side_b, delta_e_white[0], delta_e_white[1], labels, regions, prog.delta_e_threshold, !prog.delta_e_output.empty(), dn,
 			                                                 (prog.spectral_denoise || prog.delta_e_denoise) ? dm : nullptr);
 			if (!prog.delta_e_csv.empty()) renderer.save_delta_e_csv(prog.delta_e_csv, e);
@@ -774,7 +829,7 @@ int main(int argc, char* argv[]) {
 				std::fprintf(stderr, "Colour difference, region %zu: mean dE*ab %.4g, mean dE00 %.4g, max dE00 %.4g (whites' Y %.6g).\n", r, e.mean[2 * r], e.mean[2 * r + 1], e.max[2 * r + 1], delta_e_white[0][1]);
 		}
 		if (!prog.develop_output.empty()) { // X, Y, Z from the bins, the alpha of the render's image, then the store of --output
-			const std::vector<float> xyz = renderer.develop(develop_weights.data(), 3, prog.spectral_denoise ? &prog.denoise_params : nullptr, prog.demodulate ? &prog.demod_params : nullptr, optics_a);
+			const std::vector<float> xyz = renderer.develop(develop_weights.data(), 3, prog.spectral_denoise ? &prog.denoise_params : nullptr, prog.demodulate ? &prog.demod_params : nullptr, optics_a, defocus_a);
 			const size_t pixels = options.res[0] * options.res[1];
 			std::vector<float> xyza(pixels * 4);
 			for (size_t p = 0; p < pixels; ++p) { xyza[4 * p] = xyz[3 * p]; xyza[4 * p + 1] = xyz[3 * p + 1]; xyza[4 * p + 2] = xyz[3 * p + 2]; xyza[4 * p + 3] = renderer.xyza[4 * p + 3]; }

@@ -34,7 +34,7 @@ void Framebuffer::save(const std::string& path) const { save_image(path, pixels_
 	X(render_continue) X(sums_export) X(sums_import) X(set_noise_estimate) X(noise_info) \
 	X(set_spectral_bins) X(spectral_read) X(spectral_import) X(set_spectral_moments) X(spectral_variance) X(spectral_moments_import) X(spectral_probe) X(probe_arrays) X(spectral_noise) X(spectral_noise_reduce) X(spectral_compare) X(spectral_compare_arrays) X(delta_e_images) X(spectral_delta_e) \
 	X(guides) X(denoise_images) X(denoise) X(denoise_channels) X(denoise_spectral) \
-	X(develop_images) X(spectral_develop) X(albedo_bins) X(denoise_spectral_demod) X(spectral_develop_demod) X(optics_images) X(spectral_develop_optics)
+	X(develop_images) X(spectral_develop) X(albedo_bins) X(denoise_spectral_demod) X(spectral_develop_demod) X(optics_images) X(spectral_develop_optics) X(defocus_images) X(spectral_develop_lens)
 
 struct Renderer::Api {
 	void* handle = nullptr;
@@ -619,7 +619,7 @@ Renderer::DeltaE Renderer::delta_e(const DeltaESide& side_a, const DeltaESide& s
 	if (demod && !filtered) throw HostError{ SSX_ERR_ARG, "delta_e: the demodulated mode is a mode of a denoised side" };
 	const size_t pixels = options.res[0] * options.res[1];
 	delta_e_check_labels("delta_e", labels, pixels, regions);
-	if (ctxs_.size() == 1 && !demod && !side_a.optics && !side_b.optics) {
+	if (ctxs_.size() == 1 && !demod && !side_a.optics && !side_b.optics && !side_a.defocus && !side_b.defocus) {
 		DeltaE r = delta_e_result(pixels, regions, maps);
 		ssx_ctx* root = ctxs_[0];
 		const ssx_denoise_params dp = denoise ? to_abi(*denoise, false) : ssx_denoise_params{};
@@ -630,8 +630,8 @@ Renderer::DeltaE Renderer::delta_e(const DeltaESide& side_a, const DeltaESide& s
 		return r;
 	}
 	// each side by the develop's own route (several devices: every pixel from its owner; the demodulated filter), then the pure entry on device 0
-	const std::vector<float> xyz_a = develop(side_a.weights, 3, side_a.denoised ? denoise : nullptr, side_a.denoised ? demod : nullptr, side_a.optics);
-	const std::vector<float> xyz_b = develop(side_b.weights, 3, side_b.denoised ? denoise : nullptr, side_b.denoised ? demod : nullptr, side_b.optics);
+	const std::vector<float> xyz_a = develop(side_a.weights, 3, side_a.denoised ? denoise : nullptr, side_a.denoised ? demod : nullptr, side_a.optics, side_a.defocus);
+	const std::vector<float> xyz_b = develop(side_b.weights, 3, side_b.denoised ? denoise : nullptr, side_b.denoised ? demod : nullptr, side_b.optics, side_b.defocus);
 	return delta_e_images(xyz_a.data(), xyz_b.data(), white_a, white_b, labels, regions, t, maps);
 }
 
@@ -791,7 +791,25 @@ ssx_optics_params to_abi(const Renderer::Optics& o, size_t width, size_t height,
 	p.scale = o.scale.data(); p.radius = o.radius.data(); p.taps = o.taps.data();
 	return p;
 }
+// the aperture as the C ABI takes it
+ssx_defocus_params to_abi(const Renderer::Defocus& f, size_t B) {
+	if (f.focus.size() != B) throw HostError{ SSX_ERR_ARG, "Defocus: focus must hold one entry per wavelength bin" };
+	ssx_defocus_params p{};
+	p.struct_size = sizeof p;
+	p.max_radius = f.max_radius; p.gain = f.gain; p.focus = f.focus.data();
+	return p;
+}
 } // namespace
+
+std::vector<float> Renderer::defocus_images(const float* q, const float* depth, const Defocus& defocus) {
+	wait_workers_();
+	if (!spectral_bins_) throw HostError{ SSX_ERR_STATE, "defocus_images: spectral output is off (set_spectral_bins)" };
+	const size_t pixels = options.res[0] * options.res[1], B = spectral_bins_;
+	const ssx_defocus_params df = to_abi(defocus, B);
+	std::vector<float> out(pixels * B);
+	check_(api_->defocus_images(ctxs_[0], w32_(), h32_(), static_cast<uint32_t>(B), q, depth, &df, out.data()), "ssx_defocus_images", ctxs_[0]);
+	return out;
+}
 
 std::vector<float> Renderer::optics_images(const float* q, const Optics& optics) {
 	wait_workers_();
@@ -803,7 +821,7 @@ std::vector<float> Renderer::optics_images(const float* q, const Optics& optics)
 	return out;
 }
 
-std::vector<float> Renderer::develop(const float* weights, size_t channels, const DenoiseParams* denoise, const DemodParams* demod, const Optics* optics) {
+std::vector<float> Renderer::develop(const float* weights, size_t channels, const DenoiseParams* denoise, const DemodParams* demod, const Optics* optics, const Defocus* defocus) {
 	wait_workers_();
 	if (!spectral_bins_) throw HostError{ SSX_ERR_STATE, "develop: spectral output is off (set_spectral_bins)" };
 	if (demod && !denoise) throw HostError{ SSX_ERR_ARG, "develop: the demodulated mode is a mode of the denoised source (pass denoise)" };
@@ -812,10 +830,14 @@ std::vector<float> Renderer::develop(const float* weights, size_t channels, cons
 	std::vector<float> out(pixels * (C ? C : 1));
 	ssx_ctx* root = ctxs_[0];
 	const ssx_denoise_params dp = denoise ? to_abi(*denoise, demod != nullptr) : ssx_denoise_params{};
-	if (optics && n_dev == 1 && !demod) {
+	if (defocus && n_dev == 1 && !demod) {
+		const ssx_defocus_params df = to_abi(*defocus, B);
+		const ssx_optics_params op = optics ? to_abi(*optics, options.res[0], options.res[1], B) : ssx_optics_params{};
+		check_(api_->spectral_develop_lens(root, denoise ? &dp : nullptr, &df, optics ? &op : nullptr, weights, c32, out.data(), nullptr), "ssx_spectral_develop_lens", root);
+	} else if (optics && n_dev == 1 && !demod) {
 		const ssx_optics_params op = to_abi(*optics, options.res[0], options.res[1], B);
 		check_(api_->spectral_develop_optics(root, denoise ? &dp : nullptr, &op, weights, c32, out.data(), nullptr), "ssx_spectral_develop_optics", root);
-	} else if (optics) { // q by the host's gather, then the pure entries on device 0
+	} else if (optics || defocus) { // q by the host's gather, then the pure entries on device 0 (the depth guide does not depend on ownership)
 		std::vector<float> bins;
 		if (denoise) (void)denoise_spectral(*denoise, &bins, nullptr, demod);
 		else {
@@ -826,7 +848,8 @@ std::vector<float> Renderer::develop(const float* weights, size_t channels, cons
 			bins.resize(pixels * B);
 			for (size_t e = 0; e < bins.size(); ++e) bins[e] = static_cast<float>((sums[e] * M) / n); // the raw source of include/ssx.h
 		}
-		const std::vector<float> behind = optics_images(bins.data(), *optics);
+		if (defocus) bins = defocus_images(bins.data(), guides().depth.data(), *defocus);
+		const std::vector<float> behind = optics ? optics_images(bins.data(), *optics) : std::move(bins);
 		check_(api_->develop_images(root, w32_(), h32_(), static_cast<uint32_t>(B), behind.data(), weights, c32, out.data()), "ssx_develop_images", root);
 	} else if (n_dev == 1 && demod) {
 		const ssx_demod_params dm = to_abi(*demod);

@@ -208,7 +208,14 @@ public:
 	// ssx_spectral_develop_optics, all on the device.  Otherwise the host gathers q by its existing gather (every pixel's sums from the device that owns it, q = (float)((S *
 	// M) / n); the denoised source by denoise_spectral's path), then ssx_optics_images and ssx_develop_images on device 0: the same bits.
 	struct Optics { float cx = NAN, cy = NAN; uint32_t max_radius = 0; std::vector<float> scale; std::vector<uint32_t> radius; std::vector<float> taps; }; // a NaN centre: the image's middle; scale, radius [B], taps [B][2 R + 1]
-	std::vector<float> develop(const float* weights, size_t channels, const DenoiseParams* denoise = nullptr, const DemodParams* demod = nullptr, const Optics* optics = nullptr);
+	// defocus (include/ssx.h "Depth of field after the render"): the source is defocused with the depth guide first, then goes through the lens if there is one.
+	// One device and no demodulated source: ssx_spectral_develop_lens.  Otherwise q by the same gather, then ssx_defocus_images with guides().depth (the guides
+	// do not depend on ownership), ssx_optics_images and ssx_develop_images on device 0: the same bits.
+	struct Defocus { uint32_t max_radius = 0; float gain = 0.0f; std::vector<float> focus; }; // R, K and f_b [B] of ssx_defocus_params (ssh_defocus_thin_lens makes them)
+	std::vector<float> develop(const float* weights, size_t channels, const DenoiseParams* denoise = nullptr, const DemodParams* demod = nullptr, const Optics* optics = nullptr,
+	                           const Defocus* defocus = nullptr);
+	// the aperture as a pure function on q [height][width][B] and depth [height][width] of the options' size (ssx_defocus_images on device 0)
+	std::vector<float> defocus_images(const float* q, const float* depth, const Defocus& defocus);
 	// the lens as a pure function on q [height][width][B] of the options' size (ssx_optics_images on device 0)
 	std::vector<float> optics_images(const float* q, const Optics& optics);
 
@@ -217,7 +224,7 @@ public:
 	// and whether the bins are filtered first (then `denoise`, and `demod` for the demodulated mode, say how -- for both sides alike).  labels empty: the whole
 	// image is region 0 and regions must be 1.  One device and no demodulated side: ssx_spectral_delta_e.  Otherwise each side through develop() -- every pixel
 	// from the device that owns it -- then ssx_delta_e_images on device 0: the same bits.  The whites are the caller's (they set the absolute size of every dE).
-	struct DeltaESide { const float* weights = nullptr; bool denoised = false; const Optics* optics = nullptr; }; // optics: the side seen through a lens (develop)
+	struct DeltaESide { const float* weights = nullptr; bool denoised = false; const Optics* optics = nullptr; const Defocus* defocus = nullptr; }; // optics, defocus: the side seen through a lens, with an aperture (develop)
 	struct DeltaE {
 		size_t regions = 0;
 		std::vector<double> SUM, SSQ, mean, rms, max, exceed, coverage; std::vector<float> MAX; std::vector<uint64_t> NF, NX, EX;

@@ -414,6 +414,33 @@ def _optics_arg(optics, W, H):
     return p, (scale, radius, taps)
 
 
+def thin_lens_defocus(scene, height, bins, aperture, focus_distance, axial=0.0, lambda_ref=550.0, max_radius=8):
+    """ssh_defocus_thin_lens (include/ssx_host.h): the aperture Renderer.develop(..., defocus=) and Renderer.defocus_images put in front of the bins of a render
+    of `scene` (a Scene) with `height` rows, as a dict {max_radius, gain, focus [B]} -- what include/ssx.h's ssx_defocus_params carries; any dict of that form
+    is an aperture.  aperture: the lens's diameter and focus_distance: the distance in focus at lambda_ref, both in scene units; axial: the shift of the
+    inverse focus distance per unit of relative wavelength offset (longitudinal chromatic aberration); max_radius: the largest circle of confusion in pixels.
+    The depth is a ray length: the surface in focus is a sphere about the eye."""
+    vfov, gain, focus = C.c_float(), C.c_float(), np.zeros(bins, dtype=np.float32)
+    _host("ssh_scene_vfov", scene._h, C.byref(vfov))
+    d = scene.desc.contents
+    _host("ssh_defocus_thin_lens", vfov, int(height), int(bins), C.c_float(d.lambda_min), C.c_float(d.lambda_step), float(aperture), float(focus_distance), float(axial),
+          float(lambda_ref), C.byref(gain), focus.ctypes.data)
+    return {"max_radius": int(max_radius), "gain": float(gain.value), "focus": focus}
+
+
+def _defocus_arg(defocus):
+    """An aperture dict (thin_lens_defocus) -> (SsxDefocusParams, the array that keeps its table alive)."""
+    focus = np.ascontiguousarray(defocus["focus"], dtype=np.float32)
+    if focus.ndim != 1:
+        raise ValueError("defocus: focus must have shape [B]")
+    p = _capi.SsxDefocusParams()
+    p.struct_size = C.sizeof(_capi.SsxDefocusParams)
+    p.max_radius = int(defocus["max_radius"]) & 0xFFFFFFFF
+    p.gain = float(defocus["gain"])
+    p.focus = focus.ctypes.data
+    return p, (focus,)
+
+
 def emitter_spectrum(desc):
     """ssh_emitter_spectrum: the index (in desc.spectra) of the emission spectrum all emissive materials share up to a scale; SsxError SSX_ERR_SCENE otherwise."""
     idx = C.c_uint32()
@@ -1073,13 +1100,15 @@ class Renderer:
 
     # ---- developing the bins (include/ssx.h: observers, filters, sensors) ----
 
-    def develop(self, weights, denoise=None, demodulate=None, optics=None, return_bins=False):
+    def develop(self, weights, denoise=None, demodulate=None, optics=None, return_bins=False, defocus=None):
         """ssx_spectral_develop: the bins the context holds, mapped on the device by weights [C, B] (develop_weights) -> float32 [H, W, C], row 0 = bottom.
         denoise None: the raw source, q = S * M / n; a dict of denoise_spectral's parameters (levels, sigma_l, sigma_a; {} for the defaults): the filtered bins,
         developed without leaving the device.  demodulate (True or a dict, as in denoise_spectral; denoise None counts as {}): ssx_spectral_develop_demod, the
         bins filtered in the demodulated mode.  optics (a lens: lens_optics): ssx_spectral_develop_optics, the source through the lens before it is developed,
         still on the device; with return_bins: (image, the bins behind the lens float32 [H, W, B]).  A demodulated source goes through the lens by way of the
-        host: denoise_spectral(demodulate=), optics_images, develop_images.  Nothing the context holds changes."""
+        host: denoise_spectral(demodulate=), optics_images, develop_images.  defocus (an aperture: thin_lens_defocus): ssx_spectral_develop_lens, the source
+        defocused with the context's own depth guide, then through the lens if there is one, then developed, still on the device; return_bins as with optics; a
+        demodulated source by way of the host again (defocus_images with guides()["depth"]).  Nothing the context holds changes."""
         W, H = self.options.res
         w = np.ascontiguousarray(weights, dtype=np.float32)
         if w.ndim != 2:
@@ -1091,8 +1120,25 @@ class Renderer:
                                                               denoise.get("sigma_a", 0.1))
         if self._spectral_bins not in (0, w.shape[1]):
             raise ValueError("develop: weights for %d bins, the context holds %d" % (w.shape[1], self._spectral_bins))
-        if return_bins and optics is None:
-            raise ValueError("develop: return_bins needs optics")
+        if return_bins and optics is None and defocus is None:
+            raise ValueError("develop: return_bins needs optics or defocus")
+        if defocus is not None and demodulate:
+            q = self.defocus_images(self.denoise_spectral(levels=p.levels, sigma_l=p.sigma_l, sigma_a=p.sigma_a, demodulate=demodulate), self.guides()["depth"], defocus)
+            if optics is not None:
+                q = self.optics_images(q, optics)
+            out = self.develop_images(q, w)
+            return (out, q) if return_bins else out
+        if defocus is not None:
+            df, keep_f = _defocus_arg(defocus)
+            if keep_f[0].size != w.shape[1]:
+                raise ValueError("develop: an aperture for %d bins, weights for %d" % (keep_f[0].size, w.shape[1]))
+            op, keep = _optics_arg(optics, W, H) if optics is not None else (None, None)
+            if keep is not None and keep[0].size != w.shape[1]:
+                raise ValueError("develop: a lens for %d bins, weights for %d" % (keep[0].size, w.shape[1]))
+            bins_out = np.zeros((H, W, w.shape[1]), dtype=np.float32) if return_bins else None
+            self._check(self._lib.ssx_spectral_develop_lens(self._ctx, None if p is None else C.byref(p), C.byref(df), None if op is None else C.byref(op), w.ctypes.data,
+                                                            w.shape[0], out.ctypes.data, None if bins_out is None else bins_out.ctypes.data))
+            return (out, bins_out) if return_bins else out
         if optics is not None and demodulate:
             q = self.optics_images(self.denoise_spectral(levels=p.levels, sigma_l=p.sigma_l, sigma_a=p.sigma_a, demodulate=demodulate), optics)
             out = self.develop_images(q, w)
@@ -1135,6 +1181,21 @@ class Renderer:
             raise ValueError("optics_images: a lens for %d bins, q has %d" % (keep[0].size, B))
         out = np.zeros((H, W, B), dtype=np.float32)
         self._check(self._lib.ssx_optics_images(self._ctx, W, H, B, q.ctypes.data, C.byref(op), out.ctypes.data))
+        return out
+
+    def defocus_images(self, q, depth, defocus):
+        """ssx_defocus_images: the aperture (thin_lens_defocus) as a pure function: q [H, W, B], depth [H, W] -> float32 [H, W, B], every (pixel, bin) gathered
+        over its neighbours' circles of confusion (include/ssx.h "Depth of field after the render")."""
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        depth = np.ascontiguousarray(depth, dtype=np.float32)
+        if q.ndim != 3 or depth.shape != q.shape[:2]:
+            raise ValueError("defocus_images: q must have shape [H, W, B], depth [H, W]")
+        H, W, B = q.shape
+        df, keep = _defocus_arg(defocus)
+        if keep[0].size != B:
+            raise ValueError("defocus_images: an aperture for %d bins, q has %d" % (keep[0].size, B))
+        out = np.zeros((H, W, B), dtype=np.float32)
+        self._check(self._lib.ssx_defocus_images(self._ctx, W, H, B, q.ctypes.data, depth.ctypes.data, C.byref(df), out.ctypes.data))
         return out
 
     def debug_sample_flux(self, **over):
