@@ -1017,6 +1017,85 @@ int ssx_spectral_develop_lens(ssx_ctx* ctx, const ssx_denoise_params* denoise /*
                               const ssx_optics_params* optics /* or NULL */, const float* weights /* [C][B] */, uint32_t channels,
                               float* out /* [H][W][C] or NULL */, float* bins_out /* [H][W][B] or NULL */);
 
+/* ---- Developing onto a sensor: colour filter array, noise, ADC and demosaic (appended; same ABI version) ------------------------------------------------
+ * DEVELOP evaluates complete response curves at every pixel, without noise and without quantisation.  A camera's sensor does none of that: each photosite sits
+ * behind ONE filter of a colour filter array, counts electrons (shot noise, read noise), the count goes through an ADC, and the three colours are then
+ * interpolated from one channel per pixel -- which is where zipper and false-colour artefacts come from.  A photosite integrates the spectrum under its own
+ * filter, and the bins hold exactly that: a mosaic taken from the bins is right, one taken from a developed RGB image is not.  Two stages, SENSOR and
+ * DEMOSAIC; the definition is this library's; a restatement in numpy gives the same bits (tests/sensor_ref.py).
+ *
+ * All arithmetic is binary32 IEEE in the order written, every product rounded before the add, no contraction, no reassociation; max(a, b) is a > b ? a : b and
+ * min(a, b) is a < b ? a : b (a NaN a gives b); sqrtf and / are correctly rounded, floorf is exact; non-finite values go through the arithmetic as they are.
+ * Images are row-major, row 0 = bottom; B in {4, 8, ..., 64}; W >= 3 and H >= 3.  Parameters: ssx_sensor_params below.
+ *
+ * SENSOR.  q[H][W][B] -> raw[H][W] (and dn[H][W] with an ADC).  For pixel (i, j), p = j * W + i (uint32):
+ *       c = cfa[(j & 1) * 2 + (i & 1)]                                            the photosite's filter, 0..2
+ *       v = 0.0f;   for b = 0 .. B-1 ascending:   v = v + (q[j][i][b] * weights[c][b])          DEVELOP's accumulation for that one channel
+ *       e = v * exposure                                                          electrons
+ *   only with noise != 0:
+ *       sd = sqrtf(max(e, 0.0f) + read_var);   e = e + sd * z(p)
+ *   only with white > 0.0f (an ADC):
+ *       d = floorf((e * dn_per_e + black) + 0.5f);   d = min(max(d, 0.0f), white);   dn[j][i] = d;   e = (d - black) * e_per_dn
+ *   then
+ *       raw[j][i] = e * inv_exposure                                              back in the units of q * weights: comparable with a plain develop
+ *   z(p) is a stateless standard normal made of integers only, so that every implementation gives the same bits.  On uint32, wrapping:
+ *       h(x):   x ^= x >> 16;   x *= 0x7feb352d;   x ^= x >> 15;   x *= 0x846ca68b;   x ^= x >> 16
+ *       u_k = h(h(h(h(seed) + frame) + p) + k)   for k = 0 .. 5;      S = the integer sum of the twelve 16-bit halves of u_0 .. u_5
+ *       z = ((float)S - 393210.0f) * 1.52587890625e-05f
+ *   the classic sum of twelve uniforms: both operations are exact, the mean is 0, the variance 1 - 2^-32, the tails end at +-6.  THE SHOT NOISE IS THEREFORE
+ *   GAUSSIAN WITH THE POISSON VARIANCE: that is wrong below a few electrons (a count is a non-negative integer and its distribution is skewed; here e may go
+ *   negative before the ADC clamps it), and exact Poisson counts are out of scope.  A NaN e takes sd = sqrtf(read_var) and stays NaN; with an ADC a NaN d
+ *   becomes 0.  Fixed-pattern noise, dark current, blooming and cross-talk are out of scope.
+ * DEMOSAIC.  raw[H][W] -> out[H][W][3], with any tables taps[4][3][25] -- indexed by phase, output channel and (dy + 2) * 5 + (dx + 2) -- and ccm[3][3].
+ *   m(k, n) = k < 0 ? -k : (k >= n ? 2 * (n - 1) - k : k): the border is mirrored about the edge pixel without repeating it, which keeps the parity of the
+ *   colour filter array (a clamp would break it).  For pixel (i, j), phase = (j & 1) * 2 + (i & 1), for c = 0 .. 2:
+ *       acc = 0.0f;   for dy = -2 .. 2 ascending, and inside it for dx = -2 .. 2 ascending:
+ *           acc = acc + (raw[m(j + dy, H)][m(i + dx, W)] * taps[phase][c][(dy + 2) * 5 + (dx + 2)])           every tap is visited, zero coefficients included
+ *       rgb[c] = acc
+ *   and for c' = 0 .. 2:   out[j][i][c'] = ((0.0f + rgb[0] * ccm[c'][0]) + rgb[1] * ccm[c'][1]) + rgb[2] * ccm[c'][2]
+ *   (a zero coefficient on a non-finite raw gives NaN, as the arithmetic says; -0 through an identity ccm comes out as +0).
+ * THE TABLES are the hosts' (libssx_host.so, include/ssx_host.h): ssh_sensor_bayer makes cfa and taps for the four Bayer patterns, bilinear or
+ *   Malvar-He-Cutler; ssh_sensor_exposure the electron and ADC scales; ssh_sensor_ccm the least-squares matrix.  This library takes any tables.
+ * SAME BITS: the numpy restatement; SENSOR with noise off, no ADC and exposure == inv_exposure == 1 against ssx_develop_images at [j][i][cfa]; DEMOSAIC with
+ *   identity taps and an identity ccm against raw (up to -0); ssx_spectral_develop_sensor against ssx_defocus_images, ssx_optics_images, ssx_sensor_images
+ *   and ssx_demosaic_images in a chain.
+ *
+ * ON THE DEVICE (csrc/ssx_sensor.hip) two kernels, neither with atomics, a lane writing only its own output: ssx_sensor_kernel, one lane per pixel, reads q
+ * once with the weights at wave-uniform addresses (all three channels accumulated, the photosite's selected); ssx_demosaic_kernel, one lane per 2 x 2 quad,
+ * stages a tile of 64 x 16 pixels with its apron of 2 in LDS, mirroring while it stages, with all four phases' tables at wave-uniform addresses.  With the
+ * feature unused nothing is allocated and nothing is launched. */
+typedef struct ssx_sensor_params {
+	uint32_t struct_size;      /* sizeof(ssx_sensor_params) */
+	uint32_t cfa[4];           /* the filter (0..2: the row of `weights`, the channel of `taps`) at phase (j & 1) * 2 + (i & 1); row 0 = bottom */
+	uint32_t noise;            /* 0: no noise */
+	uint32_t seed, frame;      /* of z(p): another frame of the same seed is an independent exposure */
+	float exposure;            /* electrons per unit of q * weights; finite, >= 0 */
+	float inv_exposure;        /* finite; the hosts pass 1 / exposure */
+	float read_var;            /* the read noise's variance in electrons^2; finite, >= 0 */
+	float dn_per_e, e_per_dn;  /* the ADC's gain and its inverse; finite */
+	float black, white;        /* the ADC's offset and its largest number, in DN; finite, white >= 0, white == 0: no ADC; black <= white with an ADC */
+	const float* weights;      /* [3][B]     SENSOR: the three filters' response per bin (ssh_develop_weights with a camera's curves) */
+	const float* taps;         /* [4][3][25] DEMOSAIC; finite */
+	const float* ccm;          /* [3][3]     DEMOSAIC; finite */
+} ssx_sensor_params;
+
+/* SENSOR as a pure function of its arguments (needs no scene): q [height][width][bins] -> raw [height][width], dn [height][width] or NULL (dn needs an ADC).
+ * taps and ccm are not read.  SSX_ERR_ARG, with ssx_last_error naming the field: a NULL pointer (q, raw, sensor, weights), a wrong struct_size, a cfa entry
+ * above 2, an exposure, inv_exposure, read_var, dn_per_e, e_per_dn, black or white that is not finite, a negative exposure, read_var or white, black > white
+ * with white > 0, dn without an ADC, bins not a multiple of 4 in 4..64, width or height below 3, a too large image.  SSX_ERR_STATE: a render runs. */
+int ssx_sensor_images(ssx_ctx* ctx, uint32_t width, uint32_t height, uint32_t bins, const float* q /* [H][W][B] */, const ssx_sensor_params* sensor,
+                      float* raw /* [H][W] */, float* dn /* [H][W] or NULL */);
+/* DEMOSAIC as a pure function of its arguments: raw [height][width] -> out [height][width][3].  weights is not read.  SSX_ERR_ARG: a NULL pointer (raw, out,
+ * sensor, taps, ccm), a tap or a ccm entry that is not finite, and what ssx_sensor_images refuses in the struct and the size.  SSX_ERR_STATE: a render runs. */
+int ssx_demosaic_images(ssx_ctx* ctx, uint32_t width, uint32_t height, const float* raw /* [H][W] */, const ssx_sensor_params* sensor, float* out /* [H][W][3] */);
+/* ssx_spectral_develop_lens onto a sensor: the source and the stages of ssx_spectral_develop_lens (raw or denoised; DEFOCUS; WARP and BLUR; either may be
+ * NULL), then SENSOR instead of the develop kernels, then DEMOSAIC; nothing leaves the device in between.  out [H][W][3], raw_out [H][W], dn_out [H][W]
+ * (needs an ADC): any may be NULL.  It reads only, as ssx_spectral_develop_optics does.  SSX_ERR_STATE with ssx_spectral_develop_lens's reasons, tile_stride != 1
+ * among them; SSX_ERR_ARG: what ssx_defocus_images, ssx_optics_images, ssx_sensor_images and ssx_demosaic_images refuse. */
+int ssx_spectral_develop_sensor(ssx_ctx* ctx, const ssx_denoise_params* denoise /* or NULL */, const ssx_defocus_params* defocus /* or NULL */,
+                                const ssx_optics_params* optics /* or NULL */, const ssx_sensor_params* sensor, float* out /* [H][W][3] or NULL */,
+                                float* raw_out /* [H][W] or NULL */, float* dn_out /* [H][W] or NULL */);
+
 /* ---- Diagnostics for the parity tests (not part of the reference's interface) ---------------------
  * ssx_debug_eval runs one building block of the path kernel -- the same device function the kernel
  * inlines -- on n items, one per lane: `in` holds in_words 32-bit words per item, `out` receives

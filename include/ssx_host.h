@@ -181,6 +181,36 @@ int ssh_defocus_thin_lens(float vfov_deg, uint32_t height, uint32_t bins, float 
                           double lambda_ref, float* gain_out, float* focus_out);
 /* *vfov_deg = the vertical field of view of the scene's camera in degrees (what ssh_defocus_thin_lens takes; the scene description carries only the matrix). */
 int ssh_scene_vfov(const ssh_scene* scene, float* vfov_deg);
+/* ---- A sensor for ssx_sensor_images / ssx_demosaic_images / ssx_spectral_develop_sensor (ssx.h "Developing onto a sensor").  All of it binary64, rounded to
+ * binary32 once at the end. */
+enum { SSH_DEMOSAIC_BILINEAR = 0, SSH_DEMOSAIC_MHC = 1 };
+/* cfa_out [4] and taps_out [4][3][25] of ssx_sensor_params for a 2 x 2 Bayer pattern, "RGGB", "BGGR", "GRBG" or "GBRG": the first two letters are row j = 0, THE
+ * BOTTOM ROW, at i = 0 and i = 1, the last two row j = 1; channels R = 0, G = 1, B = 2.  SSH_DEMOSAIC_MHC: the 5 x 5 filters of Malvar, He and Cutler
+ * ("High-quality linear interpolation for demosaicing of Bayer-patterned color images", ICASSP 2004), all over 8:
+ *     G at an R or B site: centre 4, the four edge neighbours 2, the four axis taps at distance two -1;
+ *     R or B at a G site whose row neighbours carry that colour: centre 5, the two row neighbours 4, the four diagonals -1, the two row taps at distance two -1,
+ *       the two column taps at distance two 1/2; at a G site of the other kind the transpose;
+ *     R at a B site and B at an R site: centre 6, the four diagonals 2, the four axis taps at distance two -3/2;
+ *     a site's own colour: the centre tap alone.
+ * SSH_DEMOSAIC_BILINEAR: the same without the centre and the distance-two corrections (the neighbours' mean).  Every coefficient is dyadic, every (phase,
+ * channel) sums to 1.  Other colour filter arrays are out of scope here (the library takes any tables).  SSX_ERR_ARG: NULL, another pattern, another method. */
+int ssh_sensor_bayer(const char* pattern, int method, uint32_t* cfa_out, float* taps_out);
+/* The scales of ssx_sensor_params, out[7] = { exposure, inv_exposure, read_var, dn_per_e, e_per_dn, black, white } in the struct's order:
+ *     exposure = full_well / white_level      a development that gives white_level fills the well;      inv_exposure = 1 / exposure;      read_var = read_e * read_e
+ *     white = 2^bits - 1;   dn_per_e = (white - black) / full_well;   e_per_dn = full_well / (white - black)          a full well lands on white
+ * bits = 0: no ADC (white = 0, dn_per_e = e_per_dn = 1, unused).  SSX_ERR_ARG: NULL, a full_well or white_level not finite and positive, bits above 24, a black
+ * that is not finite, negative or (with an ADC) not below white, a read_e not finite or negative, a result that is not finite in binary32. */
+int ssh_sensor_exposure(double full_well, double white_level, uint32_t bits, double black, double read_e, float* out);
+/* The least-squares 3 x 3 that takes the camera's channels to a target's: ccm = target * cam^T * (cam * cam^T)^-1 for cam, target [3][bins] (the weights of
+ * ssh_develop_weights: the camera's curves, and the observer's in the space --develop-output writes), by the adjugate.  It is a fit over equal-energy bins, not a
+ * white balance.  SSX_ERR_ARG: NULL, bins 0, a singular cam * cam^T (det <= 1e-12 * the product of its diagonal), a result not finite in binary32. */
+int ssh_sensor_ccm(const float* cam, const float* target, uint32_t bins, float* ccm_out);
+/* STAND-IN response curves for a sensor whose curves nobody supplied (the CLI's --develop-sensor without --develop-sensor-curves).  THEY ARE NO CAMERA'S: three
+ * Gaussians, channel 0 (R) peaking at 600 nm, 1 (G) at 540 nm, 2 (B) at 460 nm, each with a standard deviation of 35 nm and a peak of 1, sampled every 5 nm from
+ * 380 to 730 nm: samples[k] = (float)exp(-0.5 * ((380 + 5 k - peak) / 35)^2), k = 0 .. 70, binary64 with libm's exp.  samples [SSH_SENSOR_STANDIN_SAMPLES];
+ * *low = 380, *high = 730: an ssh_spectrum_t for ssh_develop_weights.  SSX_ERR_ARG: NULL, a channel above 2. */
+#define SSH_SENSOR_STANDIN_SAMPLES 71u
+int ssh_sensor_standin_curve(uint32_t channel, float* samples, float* low, float* high);
 /* *spectrum = index (in desc->spectra) of the emission spectrum that all emissive materials of the scene share up to a scale.  SSX_ERR_SCENE, with the reason in
  * ssh_last_error, when two of them differ or none is emissive: what the CLI's --develop-relight refuses. */
 int ssh_emitter_spectrum(const ssx_scene_desc* desc, uint32_t* spectrum);

@@ -107,6 +107,16 @@ class SsxDefocusParams(C.Structure):
 SSX_DEFOCUS_MAX_RADIUS = 12  # include/ssx.h
 
 
+class SsxSensorParams(C.Structure):
+    """ssx_sensor_params: the colour filter array, the noise, the electron and ADC scales, and the three tables of a sensor."""
+    _fields_ = [("struct_size", C.c_uint32), ("cfa", C.c_uint32 * 4), ("noise", C.c_uint32), ("seed", C.c_uint32), ("frame", C.c_uint32),
+                ("exposure", C.c_float), ("inv_exposure", C.c_float), ("read_var", C.c_float), ("dn_per_e", C.c_float), ("e_per_dn", C.c_float),
+                ("black", C.c_float), ("white", C.c_float), ("weights", C.c_void_p), ("taps", C.c_void_p), ("ccm", C.c_void_p)]
+
+
+SSH_DEMOSAIC_BILINEAR, SSH_DEMOSAIC_MHC = 0, 1  # include/ssx_host.h
+
+
 class SshSpectrum(C.Structure):
     """ssh_spectrum_t: n uniform samples over [low, high] (include/ssx_host.h)."""
     _fields_ = [("samples", C.POINTER(C.c_float)), ("n", C.c_uint32), ("low", C.c_float), ("high", C.c_float)]
@@ -143,6 +153,7 @@ HIP_SYMBOLS = ["ssx_create", "ssx_destroy", "ssx_upload_scene", "ssx_render_star
                "ssx_delta_e_images", "ssx_spectral_delta_e",
                "ssx_optics_images", "ssx_spectral_develop_optics",
                "ssx_defocus_images", "ssx_spectral_develop_lens",
+               "ssx_sensor_images", "ssx_demosaic_images", "ssx_spectral_develop_sensor",
                "ssx_debug_tile_mask", "ssx_debug_spectral_accumulate", "ssx_debug_fold", "ssx_debug_step"]
 # ssx_debug_fold: a sample's row of levels (include/ssx.h)
 SSX_FOLD_ROW_WORDS, SSX_FOLD_LAMBDA0, SSX_FOLD_CAM_DIR, SSX_FOLD_HIT, SSX_FOLD_N, SSX_FOLD_LEVEL0, SSX_FOLD_LEVEL_WORDS = 160, 0, 1, 4, 5, 10, 15
@@ -173,7 +184,8 @@ HOST_SYMBOLS = ["ssh_scene_create", "ssh_scene_create_ex", "ssh_scene_destroy", 
                 "ssh_checkpoint_save_moments", "ssh_checkpoint_load_moments", "ssh_moments_merge",
                 "ssh_compare_derive", "ssh_compare_save_csv",
                 "ssh_delta_e_derive", "ssh_delta_e_save_csv", "ssh_develop_white",
-                "ssh_optics_lens", "ssh_defocus_thin_lens", "ssh_scene_vfov"]
+                "ssh_optics_lens", "ssh_defocus_thin_lens", "ssh_scene_vfov",
+                "ssh_sensor_bayer", "ssh_sensor_exposure", "ssh_sensor_ccm", "ssh_sensor_standin_curve"]
 
 _hip = None
 _host = None
@@ -230,6 +242,10 @@ def host_lib():
         lib.ssh_optics_lens.argtypes = [C.c_uint32, C.c_float, C.c_float, C.c_double, C.c_double, C.c_double, C.c_double, C.c_uint32, vp, vp, vp]
         lib.ssh_defocus_thin_lens.argtypes = [C.c_float, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp]
         lib.ssh_scene_vfov.argtypes = [vp, vp]
+        lib.ssh_sensor_bayer.argtypes = [C.c_char_p, C.c_int, vp, vp]
+        lib.ssh_sensor_exposure.argtypes = [C.c_double, C.c_double, C.c_uint32, C.c_double, C.c_double, vp]
+        lib.ssh_sensor_ccm.argtypes = [vp, vp, C.c_uint32, vp]
+        lib.ssh_sensor_standin_curve.argtypes = [C.c_uint32, vp, vp, vp]
         _host = lib
     return _host
 
@@ -426,6 +442,10 @@ def hip_lib():
         if not override or hasattr(lib, "ssx_defocus_images"):  # depth of field after the render: per-bin defocus from the depth guide
             lib.ssx_defocus_images.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(SsxDefocusParams), vp]
             lib.ssx_spectral_develop_lens.argtypes = [vp, C.POINTER(SsxDenoiseParams), C.POINTER(SsxDefocusParams), C.POINTER(SsxOpticsParams), vp, C.c_uint32, vp, vp]
+        if not override or hasattr(lib, "ssx_sensor_images"):  # developing onto a sensor: mosaic, noise, ADC and demosaic
+            lib.ssx_sensor_images.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.POINTER(SsxSensorParams), vp, vp]
+            lib.ssx_demosaic_images.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.POINTER(SsxSensorParams), vp]
+            lib.ssx_spectral_develop_sensor.argtypes = [vp, C.POINTER(SsxDenoiseParams), C.POINTER(SsxDefocusParams), C.POINTER(SsxOpticsParams), C.POINTER(SsxSensorParams), vp, vp, vp]
         if not override or hasattr(lib, "ssx_spectral_moments_import"):  # the second moments through checkpoint and resume
             lib.ssx_spectral_moments_import.argtypes = [vp, C.POINTER(SsxSpectralInfo), vp]
         if not override or hasattr(lib, "ssx_debug_tile_mask"):  # the camera-ray pre-trace's tile masks, read back

@@ -364,6 +364,100 @@ int ssh_optics_lens(uint32_t bins, float lambda_min, float lambda_step, double l
 	return SSX_OK;
 }
 
+int ssh_sensor_bayer(const char* pattern, int method, uint32_t* cfa_out, float* taps_out) {
+	if (!pattern || !cfa_out || !taps_out) { g_error = "NULL argument"; return SSX_ERR_ARG; }
+	if (method != SSH_DEMOSAIC_BILINEAR && method != SSH_DEMOSAIC_MHC) { g_error = "ssh_sensor_bayer: method must be SSH_DEMOSAIC_BILINEAR or SSH_DEMOSAIC_MHC"; return SSX_ERR_ARG; }
+	const std::string name(pattern);
+	if (name != "RGGB" && name != "BGGR" && name != "GRBG" && name != "GBRG") { g_error = "ssh_sensor_bayer: pattern must be RGGB, BGGR, GRBG or GBRG"; return SSX_ERR_ARG; }
+	uint32_t cfa[4];
+	for (int k = 0; k < 4; ++k) cfa[k] = name[k] == 'R' ? 0u : (name[k] == 'G' ? 1u : 2u);
+	const bool mhc = method == SSH_DEMOSAIC_MHC;
+	for (int phase = 0; phase < 4; ++phase) {
+		const uint32_t own = cfa[phase];
+		for (uint32_t c = 0; c < 3u; ++c) {
+			double k[5][5] = {};                                    // [dy + 2][dx + 2], in eighths
+			auto at = [&](int dx, int dy) -> double& { return k[dy + 2][dx + 2]; };
+			if (c == own) at(0, 0) = 8.0;
+			else if (c == 1u) {                                      // G at an R or B site
+				at(-1, 0) = at(1, 0) = at(0, -1) = at(0, 1) = 2.0;
+				if (mhc) { at(0, 0) = 4.0; at(-2, 0) = at(2, 0) = at(0, -2) = at(0, 2) = -1.0; }
+			} else if (own == 1u) {                                  // R or B at a G site: its sites are this row's neighbours, or this column's
+				const bool in_row = cfa[phase ^ 1] == c;
+				auto along = [&](int d) -> double& { return in_row ? at(d, 0) : at(0, d); };
+				auto across = [&](int d) -> double& { return in_row ? at(0, d) : at(d, 0); };
+				along(-1) = along(1) = 4.0;
+				if (mhc) { at(0, 0) = 5.0; at(-1, -1) = at(1, -1) = at(-1, 1) = at(1, 1) = -1.0; along(-2) = along(2) = -1.0; across(-2) = across(2) = 0.5; }
+			} else {                                                 // R at B, B at R
+				at(-1, -1) = at(1, -1) = at(-1, 1) = at(1, 1) = 2.0;
+				if (mhc) { at(0, 0) = 6.0; at(-2, 0) = at(2, 0) = at(0, -2) = at(0, 2) = -1.5; }
+			}
+			for (int t = 0; t < 25; ++t) taps_out[(phase * 3 + static_cast<int>(c)) * 25 + t] = static_cast<float>(k[t / 5][t % 5] / 8.0);
+		}
+	}
+	for (int k = 0; k < 4; ++k) cfa_out[k] = cfa[k];
+	return SSX_OK;
+}
+
+int ssh_sensor_exposure(double full_well, double white_level, uint32_t bits, double black, double read_e, float* out) {
+	if (!out) { g_error = "NULL argument"; return SSX_ERR_ARG; }
+	if (!std::isfinite(full_well) || !(full_well > 0.0)) { g_error = "ssh_sensor_exposure: full_well must be finite and positive"; return SSX_ERR_ARG; }
+	if (!std::isfinite(white_level) || !(white_level > 0.0)) { g_error = "ssh_sensor_exposure: white_level must be finite and positive"; return SSX_ERR_ARG; }
+	if (bits > 24u) { g_error = "ssh_sensor_exposure: bits must be 0..24 (a binary32 holds every integer up to 2^24)"; return SSX_ERR_ARG; }
+	if (!std::isfinite(read_e) || read_e < 0.0) { g_error = "ssh_sensor_exposure: read_e must be finite and >= 0"; return SSX_ERR_ARG; }
+	const double white = bits ? static_cast<double>((1u << bits) - 1u) : 0.0;
+	if (!std::isfinite(black) || black < 0.0 || (bits && !(black < white))) { g_error = "ssh_sensor_exposure: black must be finite, >= 0 and below 2^bits - 1"; return SSX_ERR_ARG; }
+	const double exposure = full_well / white_level;
+	out[0] = static_cast<float>(exposure);
+	out[1] = static_cast<float>(1.0 / exposure);
+	out[2] = static_cast<float>(read_e * read_e);
+	out[3] = bits ? static_cast<float>((white - black) / full_well) : 1.0f;
+	out[4] = bits ? static_cast<float>(full_well / (white - black)) : 1.0f;
+	out[5] = static_cast<float>(black);
+	out[6] = static_cast<float>(white);
+	for (int k = 0; k < 7; ++k) if (!std::isfinite(out[k])) { g_error = "ssh_sensor_exposure: a result is not finite in binary32"; return SSX_ERR_ARG; }
+	return SSX_OK;
+}
+
+int ssh_sensor_ccm(const float* cam, const float* target, uint32_t bins, float* ccm_out) {
+	if (!cam || !target || !ccm_out) { g_error = "NULL argument"; return SSX_ERR_ARG; }
+	if (bins == 0u) { g_error = "ssh_sensor_ccm: bins must be positive"; return SSX_ERR_ARG; }
+	double G[3][3] = {}, M[3][3] = {};
+	for (int r = 0; r < 3; ++r)
+		for (int c = 0; c < 3; ++c)
+			for (uint32_t b = 0; b < bins; ++b) {
+				G[r][c] = G[r][c] + static_cast<double>(cam[r * bins + b]) * static_cast<double>(cam[c * bins + b]);
+				M[r][c] = M[r][c] + static_cast<double>(target[r * bins + b]) * static_cast<double>(cam[c * bins + b]);
+			}
+	double adj[3][3];                                               // the adjugate of the symmetric G: adj[r][c] = cofactor(c, r)
+	for (int r = 0; r < 3; ++r)
+		for (int c = 0; c < 3; ++c) {
+			const int r1 = (c + 1) % 3, r2 = (c + 2) % 3, c1 = (r + 1) % 3, c2 = (r + 2) % 3;
+			adj[r][c] = G[r1][c1] * G[r2][c2] - G[r1][c2] * G[r2][c1];
+		}
+	const double det = (G[0][0] * adj[0][0] + G[0][1] * adj[1][0]) + G[0][2] * adj[2][0];
+	const double scale = G[0][0] * G[1][1] * G[2][2];               // Hadamard: det <= scale for a Gram matrix
+	if (!std::isfinite(det) || !std::isfinite(scale) || !(det > 1e-12 * scale)) { g_error = "ssh_sensor_ccm: cam * cam^T is singular (the three curves are not linearly independent over these bins)"; return SSX_ERR_ARG; }
+	for (int r = 0; r < 3; ++r)
+		for (int c = 0; c < 3; ++c) {
+			const double v = ((M[r][0] * adj[0][c] + M[r][1] * adj[1][c]) + M[r][2] * adj[2][c]) / det;
+			ccm_out[r * 3 + c] = static_cast<float>(v);
+			if (!std::isfinite(ccm_out[r * 3 + c])) { g_error = "ssh_sensor_ccm: a result is not finite in binary32"; return SSX_ERR_ARG; }
+		}
+	return SSX_OK;
+}
+
+int ssh_sensor_standin_curve(uint32_t channel, float* samples, float* low, float* high) {
+	if (!samples || !low || !high) { g_error = "NULL argument"; return SSX_ERR_ARG; }
+	if (channel > 2u) { g_error = "ssh_sensor_standin_curve: channel must be 0..2"; return SSX_ERR_ARG; }
+	const double peak = channel == 0u ? 600.0 : (channel == 1u ? 540.0 : 460.0);
+	for (uint32_t k = 0; k < SSH_SENSOR_STANDIN_SAMPLES; ++k) {
+		const double t = ((380.0 + 5.0 * k) - peak) / 35.0;
+		samples[k] = static_cast<float>(std::exp(-0.5 * (t * t)));
+	}
+	*low = 380.0f; *high = 730.0f;
+	return SSX_OK;
+}
+
 int ssh_scene_vfov(const ssh_scene* scene, float* vfov_deg) {
 	if (!scene || !vfov_deg) { g_error = "NULL argument"; return SSX_ERR_ARG; }
 	*vfov_deg = scene->scene->camera.vfov_deg;

@@ -22,7 +22,9 @@
 // Developing the bins (include/ssx.h "Developing the spectral bins"): --develop-output=PATH with --spectral-bins=N writes the image developed from the bins on the
 // device -- through the same XYZ -> sRGB store and writers as --output -- under --develop-observer=1931|2006 (default: the render's), through --develop-filter=FILE.csv
 // (--develop-lens=lateral,sigma,axial[,lambda_ref] with --develop-lens-radius=R puts a lens in front: include/ssx.h "Developing through a lens";
-// --develop-defocus=aperture,focus_distance[,axial[,lambda_ref]] with --develop-defocus-radius=R gives it an aperture: "Depth of field after the render")
+// --develop-defocus=aperture,focus_distance[,axial[,lambda_ref]] with --develop-defocus-radius=R gives it an aperture: "Depth of field after the render";
+// --develop-sensor=PATTERN[,mhc|bilinear] with --develop-sensor-curves / -exposure / -noise / -bits and --sensor-raw-output puts a sensor behind both: "Developing
+// onto a sensor")
 // (a spectrum in the format of data/*.csv, its range in the name: NAME-LOW+STEP+HIGH.csv) and relit by --develop-relight=NEW.csv (the emitters' spectrum replaced by
 // NEW; refused unless all emissive materials share one spectrum up to a scale).  With --spectral-denoise the filtered bins are developed.  It does not need
 // --spectral-output, and has its refusals (--tile-major, --rgb, --libm=glibc-2.35; --resume of a checkpoint without the bins).  With --resume, --spectral-bins may
@@ -62,6 +64,7 @@
 
 #include "checkpoint.hpp"
 #include "develop.hpp"
+#include "image_io.hpp"
 #include "../../include/ssx_host.h"
 
 #include <array>
@@ -111,6 +114,11 @@ void print_usage() {
 		"    [`--develop-defocus=<aperture>,<focus_distance>[,<axial=0>[,<lambda_ref=550>]]`] [`--develop-defocus-radius=<0..12, default 8>`] [`--delta-e-defocus=...`]\n"
 		"          (depth of field from the depth guide before the lens: an aperture of diameter <aperture> focused at <focus_distance>, both in scene units, the\n"
 		"           inverse focus distance moving by <axial> per relative wavelength offset; sides as for `--develop-lens`)\n"
+		"    [`--develop-sensor=<RGGB|BGGR|GRBG|GBRG>[,mhc|bilinear]`] [`--develop-sensor-curves=<R.csv>,<G.csv>,<B.csv>`] [`--develop-sensor-exposure=<full_well=15000>,<white_level=1>`]\n"
+		"    [`--develop-sensor-noise=<read_e>[,<seed=0>]`] [`--develop-sensor-bits=<1..24>[,<black=0>]`] [`--sensor-raw-output=<raw.npy>`]\n"
+		"          (behind the aperture and the lens the bins fall on a Bayer sensor -- the pattern's first two letters are the bottom row -- are counted with shot and\n"
+		"           read noise, digitised and demosaiced; `--develop-output` then writes the demosaiced image.  Without curves: three Gaussian stand-ins, no camera's.\n"
+		"           `--develop-sensor-curves` on its own: an ordinary develop with the camera's curves in the observer's place)\n"
 		"    `--demodulate[=1|2|4]` (with `--spectral-denoise`: filter illumination -- divide by the first-hit albedo per bin, <k> x <k> rays per pixel, before; multiply after)\n"
 		"    `--albedo-output=<file.npy>` (needs `--spectral-bins=<n>`: the first-hit albedo per wavelength bin)\n"
 		"    `--spectral-variance-output=<file.npy>` (needs `--spectral-bins=<n>`: the variance of every bin mean)\n"
@@ -213,6 +221,17 @@ struct Progressive { // the flags of the progressive modes
 	struct Aperture { bool on = false; double aperture = 0.0, focus_distance = 1.0, axial = 0.0, lambda_ref = 550.0; };
 	Aperture develop_defocus, delta_e_defocus;
 	unsigned develop_defocus_radius = 8;
+	// the sensor (include/ssx.h "Developing onto a sensor"): --develop-sensor=PATTERN[,mhc|bilinear], --develop-sensor-curves=R.csv,G.csv,B.csv (also on its own: an
+	// ordinary develop with a camera's curves), --develop-sensor-exposure=full_well,white_level, --develop-sensor-noise=read_e[,seed], --develop-sensor-bits=N[,black],
+	// --sensor-raw-output=raw.npy
+	struct SensorFlags {
+		bool on = false, noise = false, exposure_given = false, bits_given = false;
+		std::string pattern; int method = SSH_DEMOSAIC_MHC;
+		std::vector<std::string> curves;                     // three paths, or none: the stand-in curves of ssx_host.h
+		double full_well = 15000.0, white_level = 1.0, read_e = 0.0, black = 0.0;
+		unsigned bits = 0, seed = 0;
+		std::string raw_output;
+	} sensor;
 	bool spectral_bins_given = false;
 	bool demodulate = false;     // --demodulate[=K]
 	ssx::Renderer::DemodParams demod_params;
@@ -385,6 +404,53 @@ void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progress
 		g->develop_defocus_radius = static_cast<unsigned>(r);
 		defocus_radius_given = true;
 	}
+	{ // the sensor's options
+		auto split = [](const std::string& s) {
+			std::vector<std::string> parts;
+			size_t at = 0;
+			for (;;) {
+				const size_t comma = s.find(',', at);
+				parts.push_back(s.substr(at, comma == std::string::npos ? std::string::npos : comma - at));
+				if (comma == std::string::npos) break;
+				at = comma + 1;
+			}
+			return parts;
+		};
+		auto number = [](const std::string& part, double* x) {
+			try { size_t used = 0; *x = std::stod(part, &used); return used == part.size() && std::isfinite(*x); } catch (...) { return false; }
+		};
+		Progressive::SensorFlags& s = g->sensor;
+		bool any = false;
+		if (a.take("--develop-sensor", "", &v)) {
+			const std::vector<std::string> p = split(v);
+			const bool pattern_ok = p[0] == "RGGB" || p[0] == "BGGR" || p[0] == "GRBG" || p[0] == "GBRG";
+			if (!pattern_ok || p.size() > 2 || (p.size() == 2 && p[1] != "mhc" && p[1] != "bilinear")) { std::fprintf(stderr, "Invalid value for --develop-sensor (RGGB|BGGR|GRBG|GBRG[,mhc|bilinear])!\n"); throw -2; }
+			s.on = true; s.pattern = p[0]; s.method = p.size() == 2 && p[1] == "bilinear" ? SSH_DEMOSAIC_BILINEAR : SSH_DEMOSAIC_MHC;
+		}
+		if (a.take("--develop-sensor-curves", "", &v)) {
+			s.curves = split(v);
+			if (s.curves.size() != 3 || s.curves[0].empty() || s.curves[1].empty() || s.curves[2].empty()) { std::fprintf(stderr, "Invalid value for --develop-sensor-curves (<R.csv>,<G.csv>,<B.csv>)!\n"); throw -2; }
+		}
+		if (a.take("--develop-sensor-exposure", "", &v)) {
+			const std::vector<std::string> p = split(v);
+			if (p.size() != 2 || !number(p[0], &s.full_well) || !number(p[1], &s.white_level) || !(s.full_well > 0.0) || !(s.white_level > 0.0)) { std::fprintf(stderr, "Invalid value for --develop-sensor-exposure (<full_well>,<white_level>: finite and > 0)!\n"); throw -2; }
+			s.exposure_given = any = true;
+		}
+		if (a.take("--develop-sensor-noise", "", &v)) {
+			const std::vector<std::string> p = split(v);
+			double seed = 0.0;
+			if (p.size() > 2 || !number(p[0], &s.read_e) || s.read_e < 0.0 || (p.size() == 2 && (!number(p[1], &seed) || seed < 0.0 || seed > 4294967295.0 || seed != std::floor(seed)))) { std::fprintf(stderr, "Invalid value for --develop-sensor-noise (<read_e>[,<seed>]: read_e >= 0, seed a 32-bit number)!\n"); throw -2; }
+			s.noise = any = true; s.seed = static_cast<unsigned>(seed);
+		}
+		if (a.take("--develop-sensor-bits", "", &v)) {
+			const std::vector<std::string> p = split(v);
+			double bits = 0.0;
+			if (p.size() > 2 || !number(p[0], &bits) || bits < 1.0 || bits > 24.0 || bits != std::floor(bits) || (p.size() == 2 && (!number(p[1], &s.black) || s.black < 0.0))) { std::fprintf(stderr, "Invalid value for --develop-sensor-bits (<1..24>[,<black>= 0>])!\n"); throw -2; }
+			s.bits = static_cast<unsigned>(bits); s.bits_given = any = true;
+		}
+		if (a.take("--sensor-raw-output", "", &v)) { s.raw_output = v; any = true; }
+		if (any && !s.on) { std::fprintf(stderr, "`--develop-sensor-exposure`, `--develop-sensor-noise`, `--develop-sensor-bits` and `--sensor-raw-output` need `--develop-sensor=<pattern>`!\n"); throw -2; }
+	}
 	if (a.take("--delta-e-output", "", &v)) g->delta_e_output = v;
 	if (a.take("--delta-e-csv", "", &v)) g->delta_e_csv = v;
 	if (a.take("--delta-e-filter", "", &v)) g->delta_e_filter = v;
@@ -453,10 +519,12 @@ void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progress
 		std::fprintf(stderr, "`--spectral-output` cannot be combined with `--tile-major`, `--rgb` or `--libm=glibc-2.35`!\n");
 		throw -2;
 	}
-	if (g->develop_output.empty() && !g->delta_e() && (!g->develop_filter.empty() || !g->develop_relight.empty() || g->develop_observer || g->develop_lens.on || g->develop_defocus.on)) {
-		std::fprintf(stderr, "`--develop-observer`, `--develop-filter`, `--develop-relight`, `--develop-lens` and `--develop-defocus` need `--develop-output=<image>`!\n");
+	if (g->develop_output.empty() && !g->delta_e() && (!g->develop_filter.empty() || !g->develop_relight.empty() || g->develop_observer || g->develop_lens.on || g->develop_defocus.on || !g->sensor.curves.empty())) {
+		std::fprintf(stderr, "`--develop-observer`, `--develop-filter`, `--develop-relight`, `--develop-lens`, `--develop-defocus` and `--develop-sensor-curves` need `--develop-output=<image>`!\n");
 		throw -2;
 	}
+	if (g->sensor.on && g->develop_output.empty()) { std::fprintf(stderr, "`--develop-sensor` needs `--develop-output=<image>`: it writes the demosaiced image there!\n"); throw -2; }
+	if (g->sensor.on && g->delta_e()) { std::fprintf(stderr, "`--develop-sensor` cannot be combined with `--delta-e-output` or `--delta-e-csv`: compare two developments with Renderer.delta_e_images instead!\n"); throw -2; }
 	if (g->delta_e() && !g->spectral_bins_given) {
 		std::fprintf(stderr, "`--delta-e-output` and `--delta-e-csv` need `--spectral-bins=<n>`: they compare two developments of the render's wavelength bins!\n");
 		throw -2;
@@ -647,7 +715,8 @@ int main(int argc, char* argv[]) {
 		std::vector<float> develop_weights;
 		std::unique_ptr<ssx::ColorData> develop_color;
 		// one development's weights: the observer's tables over the bins, times the filter, times the relighting gain (`relit` false: without the gain)
-		auto weights_of = [&](const ssx::ColorData& color, const std::string& filter_path, const std::string& relight_path, bool relit) {
+		// (`responses`: a camera's three curves in the observer's place)
+		auto weights_of = [&](const ssx::ColorData& color, const std::string& filter_path, const std::string& relight_path, bool relit, const std::vector<ssx::Spectrum>* responses = nullptr) {
 			const ssx_scene_desc& d = renderer.scene->desc();
 			const uint32_t B = static_cast<uint32_t>(prog.spectral_bins);
 			ssx::Spectrum filter;
@@ -658,7 +727,7 @@ int main(int argc, char* argv[]) {
 				const ssx::Spectrum from(std::vector<float>(d.samples + e.offset, d.samples + e.offset + e.n), e.low, e.high);
 				gain = ssx::relight_gain(from, ssx::load_spectrum_csv(relight_path), B, d.lambda_min, d.lambda_step);
 			}
-			const std::vector<double> w = ssx::develop_weights({ color.std_obs_xbar, color.std_obs_ybar, color.std_obs_zbar },
+			const std::vector<double> w = ssx::develop_weights(responses ? *responses : std::vector<ssx::Spectrum>{ color.std_obs_xbar, color.std_obs_ybar, color.std_obs_zbar },
 			                                                   filter_path.empty() ? nullptr : &filter, gain.empty() ? nullptr : gain.data(), nullptr, B, d.lambda_min, d.lambda_step);
 			return std::vector<float>(w.begin(), w.end()); // (rounded to binary32 here, once)
 		};
@@ -666,6 +735,33 @@ int main(int argc, char* argv[]) {
 			develop_color = std::make_unique<ssx::ColorData>(options.data_dir, prog.develop_observer ? prog.develop_observer : options.observer);
 			develop_color->meng_output_transform = renderer.color->meng_output_transform;
 			develop_weights = weights_of(*develop_color, prog.develop_filter, prog.develop_relight, true);
+		}
+		// the sensor, built (and refused) before the render; --develop-sensor-curves on its own: an ordinary develop with the camera's curves in the observer's place
+		ssx::Renderer::Sensor sensor;
+		if (prog.sensor.on || !prog.sensor.curves.empty()) {
+			std::vector<ssx::Spectrum> curves;
+			for (const std::string& path : prog.sensor.curves) curves.push_back(ssx::load_spectrum_csv(path));
+			for (uint32_t c = 0; curves.size() < 3; ++c) { // the stand-in curves of include/ssx_host.h: no camera's
+				std::vector<float> samples(SSH_SENSOR_STANDIN_SAMPLES);
+				float low = 0.0f, high = 0.0f;
+				if (ssh_sensor_standin_curve(c, samples.data(), &low, &high) != SSX_OK) throw ssx::HostError{ SSX_ERR_ARG, std::string("--develop-sensor: ") + ssh_last_error() };
+				curves.emplace_back(std::move(samples), low, high);
+			}
+			const std::vector<float> cam = weights_of(*develop_color, prog.develop_filter, prog.develop_relight, true, &curves);
+			if (!prog.sensor.on) develop_weights = cam;
+			else {
+				const Progressive::SensorFlags& f = prog.sensor;
+				const uint32_t B = static_cast<uint32_t>(prog.spectral_bins);
+				sensor.weights = cam; sensor.taps.resize(300); sensor.ccm.resize(9);
+				float scales[7];
+				if (ssh_sensor_bayer(f.pattern.c_str(), f.method, sensor.cfa, sensor.taps.data()) != SSX_OK ||
+				    ssh_sensor_exposure(f.full_well, f.white_level, f.bits, f.black, f.read_e, scales) != SSX_OK ||
+				    ssh_sensor_ccm(cam.data(), develop_weights.data(), B, sensor.ccm.data()) != SSX_OK) // to the space --develop-output writes: the observer's X, Y, Z
+					throw ssx::HostError{ SSX_ERR_ARG, std::string("--develop-sensor: ") + ssh_last_error() };
+				sensor.exposure = scales[0]; sensor.inv_exposure = scales[1]; sensor.read_var = scales[2]; sensor.dn_per_e = scales[3]; sensor.e_per_dn = scales[4];
+				sensor.black = scales[5]; sensor.white = scales[6];
+				sensor.noise = f.noise ? 1u : 0u; sensor.seed = f.seed;
+			}
 		}
 		// the lenses, built (and refused) before the render
 		ssx::Renderer::Optics lens_a, lens_b;
@@ -829,7 +925,15 @@ int main(int argc, char* argv[]) {
 				std::fprintf(stderr, "Colour difference, region %zu: mean dE*ab %.4g, mean dE00 %.4g, max dE00 %.4g (whites' Y %.6g).\n", r, e.mean[2 * r], e.mean[2 * r + 1], e.max[2 * r + 1], delta_e_white[0][1]);
 		}
 		if (!prog.develop_output.empty()) { // X, Y, Z from the bins, the alpha of the render's image, then the store of --output
-			const std::vector<float> xyz = renderer.develop(develop_weights.data(), 3, prog.spectral_denoise ? &prog.denoise_params : nullptr, prog.demodulate ? &prog.demod_params : nullptr, optics_a, defocus_a);
+			std::vector<float> xyz;
+			if (prog.sensor.on) { // through the sensor: the ccm has taken the demosaiced image to X, Y, Z
+				ssx::Renderer::SensorImage img = renderer.develop_sensor(sensor, prog.spectral_denoise ? &prog.denoise_params : nullptr, prog.demodulate ? &prog.demod_params : nullptr, optics_a, defocus_a);
+				if (!prog.sensor.raw_output.empty()) {
+					const size_t shape[2] = { options.res[1], options.res[0] };
+					ssx::save_npy_f32(prog.sensor.raw_output, img.raw.data(), shape, 2);
+				}
+				xyz = std::move(img.out);
+			} else xyz = renderer.develop(develop_weights.data(), 3, prog.spectral_denoise ? &prog.denoise_params : nullptr, prog.demodulate ? &prog.demod_params : nullptr, optics_a, defocus_a);
 			const size_t pixels = options.res[0] * options.res[1];
 			std::vector<float> xyza(pixels * 4);
 			for (size_t p = 0; p < pixels; ++p) { xyza[4 * p] = xyz[3 * p]; xyza[4 * p + 1] = xyz[3 * p + 1]; xyza[4 * p + 2] = xyz[3 * p + 2]; xyza[4 * p + 3] = renderer.xyza[4 * p + 3]; }

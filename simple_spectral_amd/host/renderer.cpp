@@ -34,7 +34,7 @@ void Framebuffer::save(const std::string& path) const { save_image(path, pixels_
 	X(render_continue) X(sums_export) X(sums_import) X(set_noise_estimate) X(noise_info) \
 	X(set_spectral_bins) X(spectral_read) X(spectral_import) X(set_spectral_moments) X(spectral_variance) X(spectral_moments_import) X(spectral_probe) X(probe_arrays) X(spectral_noise) X(spectral_noise_reduce) X(spectral_compare) X(spectral_compare_arrays) X(delta_e_images) X(spectral_delta_e) \
 	X(guides) X(denoise_images) X(denoise) X(denoise_channels) X(denoise_spectral) \
-	X(develop_images) X(spectral_develop) X(albedo_bins) X(denoise_spectral_demod) X(spectral_develop_demod) X(optics_images) X(spectral_develop_optics) X(defocus_images) X(spectral_develop_lens)
+	X(develop_images) X(spectral_develop) X(albedo_bins) X(denoise_spectral_demod) X(spectral_develop_demod) X(optics_images) X(spectral_develop_optics) X(defocus_images) X(spectral_develop_lens) X(sensor_images) X(demosaic_images) X(spectral_develop_sensor)
 
 struct Renderer::Api {
 	void* handle = nullptr;
@@ -821,6 +821,85 @@ std::vector<float> Renderer::optics_images(const float* q, const Optics& optics)
 	return out;
 }
 
+std::vector<float> Renderer::source_bins_(const DenoiseParams* denoise, const DemodParams* demod) {
+	const size_t pixels = options.res[0] * options.res[1], B = spectral_bins_;
+	std::vector<float> bins;
+	if (denoise) (void)denoise_spectral(*denoise, &bins, nullptr, demod);
+	else {
+		level_devices(); // (a stopped render: one sample count behind every pixel)
+		std::vector<double> sums;
+		const ssx_spectral_info_t info = gather_bins_(nullptr, &sums, nullptr);
+		const double M = static_cast<double>(B / 4), n = static_cast<double>(info.done_spp);
+		bins.resize(pixels * B);
+		for (size_t e = 0; e < bins.size(); ++e) bins[e] = static_cast<float>((sums[e] * M) / n); // the raw source of include/ssx.h
+	}
+	return bins;
+}
+
+namespace {
+// the sensor as the C ABI takes it (B == 0: the weights are not needed)
+ssx_sensor_params to_abi(const Renderer::Sensor& s, size_t B, bool demosaics) {
+	if (B && s.weights.size() != 3 * B) throw HostError{ SSX_ERR_ARG, "Sensor: weights must hold three rows of one entry per wavelength bin" };
+	if (demosaics && (s.taps.size() != 300 || s.ccm.size() != 9)) throw HostError{ SSX_ERR_ARG, "Sensor: taps must hold [4][3][25] entries and ccm [3][3]" };
+	ssx_sensor_params p{};
+	p.struct_size = sizeof p;
+	for (int k = 0; k < 4; ++k) p.cfa[k] = s.cfa[k];
+	p.noise = s.noise; p.seed = s.seed; p.frame = s.frame;
+	p.exposure = s.exposure; p.inv_exposure = s.inv_exposure; p.read_var = s.read_var;
+	p.dn_per_e = s.dn_per_e; p.e_per_dn = s.e_per_dn; p.black = s.black; p.white = s.white;
+	p.weights = B ? s.weights.data() : nullptr;
+	p.taps = demosaics ? s.taps.data() : nullptr; p.ccm = demosaics ? s.ccm.data() : nullptr;
+	return p;
+}
+} // namespace
+
+std::vector<float> Renderer::sensor_images(const float* q, const Sensor& sensor, std::vector<float>* dn) {
+	wait_workers_();
+	if (!spectral_bins_) throw HostError{ SSX_ERR_STATE, "sensor_images: spectral output is off (set_spectral_bins)" };
+	const size_t pixels = options.res[0] * options.res[1], B = spectral_bins_;
+	const ssx_sensor_params sp = to_abi(sensor, B, false);
+	std::vector<float> raw(pixels);
+	const bool adc = dn && sensor.white > 0.0f;
+	if (dn) dn->assign(adc ? pixels : 0, 0.0f);
+	check_(api_->sensor_images(ctxs_[0], w32_(), h32_(), static_cast<uint32_t>(B), q, &sp, raw.data(), adc ? dn->data() : nullptr), "ssx_sensor_images", ctxs_[0]);
+	return raw;
+}
+
+std::vector<float> Renderer::demosaic_images(const float* raw, const Sensor& sensor) {
+	wait_workers_();
+	const size_t pixels = options.res[0] * options.res[1];
+	const ssx_sensor_params sp = to_abi(sensor, 0, true);
+	std::vector<float> out(pixels * 3);
+	check_(api_->demosaic_images(ctxs_[0], w32_(), h32_(), raw, &sp, out.data()), "ssx_demosaic_images", ctxs_[0]);
+	return out;
+}
+
+Renderer::SensorImage Renderer::develop_sensor(const Sensor& sensor, const DenoiseParams* denoise, const DemodParams* demod, const Optics* optics, const Defocus* defocus) {
+	wait_workers_();
+	if (!spectral_bins_) throw HostError{ SSX_ERR_STATE, "develop_sensor: spectral output is off (set_spectral_bins)" };
+	if (demod && !denoise) throw HostError{ SSX_ERR_ARG, "develop_sensor: the demodulated mode is a mode of the denoised source (pass denoise)" };
+	const size_t pixels = options.res[0] * options.res[1], B = spectral_bins_;
+	SensorImage r;
+	if (ctxs_.size() == 1 && !demod) {
+		ssx_ctx* root = ctxs_[0];
+		const ssx_sensor_params sp = to_abi(sensor, B, true);
+		const ssx_denoise_params dp = denoise ? to_abi(*denoise, false) : ssx_denoise_params{};
+		const ssx_defocus_params df = defocus ? to_abi(*defocus, B) : ssx_defocus_params{};
+		const ssx_optics_params op = optics ? to_abi(*optics, options.res[0], options.res[1], B) : ssx_optics_params{};
+		r.out.resize(pixels * 3); r.raw.resize(pixels);
+		if (sensor.white > 0.0f) r.dn.resize(pixels);
+		check_(api_->spectral_develop_sensor(root, denoise ? &dp : nullptr, defocus ? &df : nullptr, optics ? &op : nullptr, &sp, r.out.data(), r.raw.data(),
+		                                     r.dn.empty() ? nullptr : r.dn.data()), "ssx_spectral_develop_sensor", root);
+		return r;
+	}
+	std::vector<float> bins = source_bins_(denoise, demod); // then the pure entries on device 0
+	if (defocus) bins = defocus_images(bins.data(), guides().depth.data(), *defocus);
+	if (optics) bins = optics_images(bins.data(), *optics);
+	r.raw = sensor_images(bins.data(), sensor, &r.dn);
+	r.out = demosaic_images(r.raw.data(), sensor);
+	return r;
+}
+
 std::vector<float> Renderer::develop(const float* weights, size_t channels, const DenoiseParams* denoise, const DemodParams* demod, const Optics* optics, const Defocus* defocus) {
 	wait_workers_();
 	if (!spectral_bins_) throw HostError{ SSX_ERR_STATE, "develop: spectral output is off (set_spectral_bins)" };
@@ -838,16 +917,7 @@ std::vector<float> Renderer::develop(const float* weights, size_t channels, cons
 		const ssx_optics_params op = to_abi(*optics, options.res[0], options.res[1], B);
 		check_(api_->spectral_develop_optics(root, denoise ? &dp : nullptr, &op, weights, c32, out.data(), nullptr), "ssx_spectral_develop_optics", root);
 	} else if (optics || defocus) { // q by the host's gather, then the pure entries on device 0 (the depth guide does not depend on ownership)
-		std::vector<float> bins;
-		if (denoise) (void)denoise_spectral(*denoise, &bins, nullptr, demod);
-		else {
-			level_devices(); // (a stopped render: one sample count behind every pixel)
-			std::vector<double> sums;
-			const ssx_spectral_info_t info = gather_bins_(nullptr, &sums, nullptr);
-			const double M = static_cast<double>(B / 4), n = static_cast<double>(info.done_spp);
-			bins.resize(pixels * B);
-			for (size_t e = 0; e < bins.size(); ++e) bins[e] = static_cast<float>((sums[e] * M) / n); // the raw source of include/ssx.h
-		}
+		std::vector<float> bins = source_bins_(denoise, demod);
 		if (defocus) bins = defocus_images(bins.data(), guides().depth.data(), *defocus);
 		const std::vector<float> behind = optics ? optics_images(bins.data(), *optics) : std::move(bins);
 		check_(api_->develop_images(root, w32_(), h32_(), static_cast<uint32_t>(B), behind.data(), weights, c32, out.data()), "ssx_develop_images", root);

@@ -218,6 +218,20 @@ public:
 	std::vector<float> defocus_images(const float* q, const float* depth, const Defocus& defocus);
 	// the lens as a pure function on q [height][width][B] of the options' size (ssx_optics_images on device 0)
 	std::vector<float> optics_images(const float* q, const Optics& optics);
+	// Developing onto a sensor (include/ssx.h "Developing onto a sensor"): behind the aperture and the lens the bins fall on a colour filter array, are counted,
+	// digitised and demosaiced.  One device and no demodulated source: ssx_spectral_develop_sensor, all on the device.  Otherwise q by develop()'s gather, then
+	// ssx_defocus_images, ssx_optics_images, ssx_sensor_images and ssx_demosaic_images on device 0: the same bits.
+	struct Sensor { // ssx_sensor_params (ssh_sensor_bayer, ssh_sensor_exposure, ssh_sensor_ccm make them); weights [3][B], taps [4][3][25], ccm [3][3]
+		uint32_t cfa[4] = { 0, 1, 1, 2 }; uint32_t noise = 0, seed = 0, frame = 0;
+		float exposure = 1.0f, inv_exposure = 1.0f, read_var = 0.0f, dn_per_e = 1.0f, e_per_dn = 1.0f, black = 0.0f, white = 0.0f;
+		std::vector<float> weights, taps, ccm;
+	};
+	struct SensorImage { std::vector<float> out, raw, dn; }; // [height][width][3], the mosaic [height][width], the ADC's numbers [height][width] (empty without an ADC)
+	SensorImage develop_sensor(const Sensor& sensor, const DenoiseParams* denoise = nullptr, const DemodParams* demod = nullptr, const Optics* optics = nullptr,
+	                           const Defocus* defocus = nullptr);
+	// the two stages as pure functions on arrays of the options' size (ssx_sensor_images, ssx_demosaic_images on device 0); dn may be NULL
+	std::vector<float> sensor_images(const float* q, const Sensor& sensor, std::vector<float>* dn = nullptr);
+	std::vector<float> demosaic_images(const float* raw, const Sensor& sensor);
 
 	// The colour difference of two developments of this render (include/ssx.h "Colour difference of two developments"): the six [regions][2] arrays (metric 0
 	// dE*ab, 1 dE00), the five derived figures (image_io.hpp delta_e_derive) and, with `maps`, de [height][width][2].  A side is its [3][bins] weights (xyz space)
@@ -250,6 +264,7 @@ private:
 	bool moments_resumed_ = false;  // the last load_checkpoint took the second moments up
 	// ssx_spectral_variance's q of every device merged by ownership (the devices level): Q [height][width][bins]
 	std::vector<double> gather_moments_();
+	std::vector<float> source_bins_(const DenoiseParams* denoise, const DemodParams* demod); // q [height][width][B] on the host: the raw source from every pixel's owner, or denoise_spectral's
 	std::vector<float> demod_weights_(const DemodParams& demod) const; // demod.weights_xyz, or the render's own observer's develop weights over the bins
 	size_t expected_spp_ = 0;   // the count the running (or last) call renders to: what render_wait compares ssx_done_spp with
 	ssx_render_params params_for_(size_t d, size_t spp, size_t spp_per_launch) const;

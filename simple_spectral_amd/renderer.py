@@ -441,6 +441,74 @@ def _defocus_arg(defocus):
     return p, (focus,)
 
 
+def sensor_bayer(pattern, method="mhc"):
+    """ssh_sensor_bayer (include/ssx_host.h): {"cfa": uint32 [4], "taps": float32 [4, 3, 25]} for a Bayer pattern "RGGB", "BGGR", "GRBG" or "GBRG" -- the first
+    two letters are row 0, THE BOTTOM ROW -- and the demosaic `method`, "mhc" (Malvar-He-Cutler) or "bilinear".  Merged with sensor_exposure's dict, "weights"
+    (develop_weights(responses=) of the camera's three curves) and "ccm" (sensor_ccm) it is a sensor for Renderer.develop(sensor=)."""
+    if method not in ("mhc", "bilinear"):
+        raise ValueError("sensor_bayer: method must be 'mhc' or 'bilinear'")
+    cfa, taps = np.zeros(4, dtype=np.uint32), np.zeros((4, 3, 25), dtype=np.float32)
+    _host("ssh_sensor_bayer", str(pattern).encode(), _capi.SSH_DEMOSAIC_MHC if method == "mhc" else _capi.SSH_DEMOSAIC_BILINEAR, cfa.ctypes.data, taps.ctypes.data)
+    return {"cfa": cfa, "taps": taps}
+
+
+_SENSOR_SCALES = ("exposure", "inv_exposure", "read_var", "dn_per_e", "e_per_dn", "black", "white")
+
+
+def sensor_exposure(full_well, white_level, bits=0, black=0.0, read_e=0.0):
+    """ssh_sensor_exposure: the scales of a sensor whose well of `full_well` electrons is filled by a development of `white_level`, read with `read_e` electrons
+    of noise through an ADC of `bits` bits above `black` (bits 0: no ADC), as a dict {exposure, inv_exposure, read_var, dn_per_e, e_per_dn, black, white}."""
+    out = np.zeros(7, dtype=np.float32)
+    _host("ssh_sensor_exposure", float(full_well), float(white_level), int(bits), float(black), float(read_e), out.ctypes.data)
+    return {k: float(v) for k, v in zip(_SENSOR_SCALES, out)}
+
+
+def sensor_ccm(cam, target):
+    """ssh_sensor_ccm: float32 [3, 3], the least-squares matrix target * cam^T * (cam * cam^T)^-1 that takes a camera's channels (cam [3, B], its weights) to a
+    target's (target [3, B], e.g. develop_weights(space="lrgb")); SsxError where the camera's curves are linearly dependent over the bins."""
+    cam, target = np.ascontiguousarray(cam, dtype=np.float32), np.ascontiguousarray(target, dtype=np.float32)
+    if cam.ndim != 2 or cam.shape[0] != 3 or target.shape != cam.shape:
+        raise ValueError("sensor_ccm: cam and target must have shape [3, B]")
+    ccm = np.zeros((3, 3), dtype=np.float32)
+    _host("ssh_sensor_ccm", cam.ctypes.data, target.ctypes.data, cam.shape[1], ccm.ctypes.data)
+    return ccm
+
+
+def sensor_standin_curves():
+    """ssh_sensor_standin_curve: the three stand-in response curves [(samples, low, high)] x 3 the CLI's --develop-sensor uses when no curves are given -- Gaussians
+    peaking at 600, 540 and 460 nm with a standard deviation of 35 nm.  THEY ARE NO CAMERA'S.  For develop_weights(responses=)."""
+    out = []
+    for ch in range(3):
+        s, low, high = np.zeros(71, dtype=np.float32), C.c_float(), C.c_float()
+        _host("ssh_sensor_standin_curve", ch, s.ctypes.data, C.byref(low), C.byref(high))
+        out.append((s, float(low.value), float(high.value)))
+    return out
+
+
+def _sensor_arg(sensor):
+    """A sensor dict -> (SsxSensorParams, the arrays that keep its tables alive: weights, taps, ccm, each None where the dict has none).  cfa is required; the
+    scales default to a sensor that counts in the units of the develop (exposure 1, no noise, no ADC)."""
+    p = _capi.SsxSensorParams()
+    p.struct_size = C.sizeof(_capi.SsxSensorParams)
+    cfa = [int(v) & 0xFFFFFFFF for v in sensor["cfa"]]
+    if len(cfa) != 4:
+        raise ValueError("sensor: cfa must hold four entries")
+    p.cfa = (C.c_uint32 * 4)(*cfa)
+    p.noise, p.seed, p.frame = int(bool(sensor.get("noise", 0))), int(sensor.get("seed", 0)) & 0xFFFFFFFF, int(sensor.get("frame", 0)) & 0xFFFFFFFF
+    for k, default in zip(_SENSOR_SCALES, (1.0, 1.0, 0.0, 1.0, 1.0, 0.0, 0.0)):
+        setattr(p, k, float(sensor.get(k, default)))
+    keep = []
+    for k, shape in (("weights", None), ("taps", (4, 3, 25)), ("ccm", (3, 3))):
+        a = sensor.get(k)
+        if a is not None:
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if (shape is not None and a.shape != shape) or (shape is None and (a.ndim != 2 or a.shape[0] != 3)):
+                raise ValueError("sensor: %s must have shape %s" % (k, "[3, B]" if shape is None else list(shape)))
+            setattr(p, k, a.ctypes.data)
+        keep.append(a)
+    return p, tuple(keep)
+
+
 def emitter_spectrum(desc):
     """ssh_emitter_spectrum: the index (in desc.spectra) of the emission spectrum all emissive materials share up to a scale; SsxError SSX_ERR_SCENE otherwise."""
     idx = C.c_uint32()
@@ -1100,7 +1168,68 @@ class Renderer:
 
     # ---- developing the bins (include/ssx.h: observers, filters, sensors) ----
 
-    def develop(self, weights, denoise=None, demodulate=None, optics=None, return_bins=False, defocus=None):
+    def _develop_sensor(self, sensor, denoise, demodulate, optics, defocus, return_raw):
+        """develop(sensor=): ssx_spectral_develop_sensor, or for a demodulated source the pure entries by way of the host."""
+        W, H = self.options.res
+        sp, keep = _sensor_arg(sensor)
+        if keep[0] is None:
+            raise ValueError("develop: a sensor needs weights [3, B]")
+        B = keep[0].shape[1]
+        if self._spectral_bins not in (0, B):
+            raise ValueError("develop: a sensor for %d bins, the context holds %d" % (B, self._spectral_bins))
+        if demodulate and denoise is None:
+            denoise = {}
+        p = None if denoise is None else self._denoise_params(denoise.get("levels", 5), denoise.get("sigma_l", _capi.SSX_DEMOD_DEFAULT_SIGMA_L if demodulate else 1.0),
+                                                              denoise.get("sigma_a", 0.1))
+        adc = sp.white > 0
+        if demodulate:
+            q = self.denoise_spectral(levels=p.levels, sigma_l=p.sigma_l, sigma_a=p.sigma_a, demodulate=demodulate)
+            if defocus is not None:
+                q = self.defocus_images(q, self.guides()["depth"], defocus)
+            if optics is not None:
+                q = self.optics_images(q, optics)
+            raw, dn = self.sensor_images(q, sensor, return_dn=True) if adc else (self.sensor_images(q, sensor), None)
+            out = self.demosaic_images(raw, sensor)
+            return (out, raw, dn) if return_raw else out
+        df, keep_f = _defocus_arg(defocus) if defocus is not None else (None, None)
+        op, keep_o = _optics_arg(optics, W, H) if optics is not None else (None, None)
+        if (keep_f is not None and keep_f[0].size != B) or (keep_o is not None and keep_o[0].size != B):
+            raise ValueError("develop: the aperture, the lens and the sensor must be made for the same number of bins")
+        out = np.zeros((H, W, 3), dtype=np.float32)
+        raw = np.zeros((H, W), dtype=np.float32) if return_raw else None
+        dn = np.zeros((H, W), dtype=np.float32) if return_raw and adc else None
+        self._check(self._lib.ssx_spectral_develop_sensor(self._ctx, None if p is None else C.byref(p), None if df is None else C.byref(df), None if op is None else C.byref(op),
+                                                          C.byref(sp), out.ctypes.data, None if raw is None else raw.ctypes.data, None if dn is None else dn.ctypes.data))
+        return (out, raw, dn) if return_raw else out
+
+    def sensor_images(self, q, sensor, return_dn=False):
+        """ssx_sensor_images: SENSOR (include/ssx.h "Developing onto a sensor") as a pure function: q [H, W, B] -> the mosaic raw float32 [H, W], one filter of
+        the sensor's colour filter array per photosite, in the units of a develop with sensor["weights"]; with return_dn (needs an ADC): (raw, the ADC's numbers
+        float32 [H, W])."""
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        if q.ndim != 3:
+            raise ValueError("sensor_images: q must have shape [H, W, B]")
+        H, W, B = q.shape
+        sp, keep = _sensor_arg(sensor)
+        if keep[0] is not None and keep[0].shape[1] != B:
+            raise ValueError("sensor_images: a sensor for %d bins, q has %d" % (keep[0].shape[1], B))
+        raw = np.zeros((H, W), dtype=np.float32)
+        dn = np.zeros((H, W), dtype=np.float32) if return_dn else None
+        self._check(self._lib.ssx_sensor_images(self._ctx, W, H, B, q.ctypes.data, C.byref(sp), raw.ctypes.data, None if dn is None else dn.ctypes.data))
+        return (raw, dn) if return_dn else raw
+
+    def demosaic_images(self, raw, sensor):
+        """ssx_demosaic_images: DEMOSAIC as a pure function: raw [H, W] -> float32 [H, W, 3] by the sensor's taps [4, 3, 25] and ccm [3, 3]."""
+        raw = np.ascontiguousarray(raw, dtype=np.float32)
+        if raw.ndim != 2:
+            raise ValueError("demosaic_images: raw must have shape [H, W]")
+        H, W = raw.shape
+        sp, keep = _sensor_arg(sensor)
+        out = np.zeros((H, W, 3), dtype=np.float32)
+        self._check(self._lib.ssx_demosaic_images(self._ctx, W, H, raw.ctypes.data, C.byref(sp), out.ctypes.data))
+        return out
+
+    def develop(self, weights, denoise=None, demodulate=None, optics=None, return_bins=False, defocus=None, sensor=None, return_raw=False):
         """ssx_spectral_develop: the bins the context holds, mapped on the device by weights [C, B] (develop_weights) -> float32 [H, W, C], row 0 = bottom.
         denoise None: the raw source, q = S * M / n; a dict of denoise_spectral's parameters (levels, sigma_l, sigma_a; {} for the defaults): the filtered bins,
         developed without leaving the device.  demodulate (True or a dict, as in denoise_spectral; denoise None counts as {}): ssx_spectral_develop_demod, the
@@ -1108,7 +1237,16 @@ class Renderer:
         still on the device; with return_bins: (image, the bins behind the lens float32 [H, W, B]).  A demodulated source goes through the lens by way of the
         host: denoise_spectral(demodulate=), optics_images, develop_images.  defocus (an aperture: thin_lens_defocus): ssx_spectral_develop_lens, the source
         defocused with the context's own depth guide, then through the lens if there is one, then developed, still on the device; return_bins as with optics; a
-        demodulated source by way of the host again (defocus_images with guides()["depth"]).  Nothing the context holds changes."""
+        demodulated source by way of the host again (defocus_images with guides()["depth"]).  sensor (a dict: sensor_bayer's and sensor_exposure's entries,
+        "weights" [3, B], "ccm" [3, 3], and "noise", "seed", "frame"): ssx_spectral_develop_sensor -- behind the aperture and the lens the bins fall on a colour
+        filter array, are counted, digitised and demosaiced on the device; `weights` is then not used (None will do), the result is float32 [H, W, 3], and with
+        return_raw: (image, the mosaic [H, W], the ADC's numbers [H, W] or None).  Nothing the context holds changes."""
+        if sensor is not None:
+            if return_bins:
+                raise ValueError("develop: return_bins is not offered with a sensor (return_raw is)")
+            return self._develop_sensor(sensor, denoise, demodulate, optics, defocus, return_raw)
+        if return_raw:
+            raise ValueError("develop: return_raw needs a sensor")
         W, H = self.options.res
         w = np.ascontiguousarray(weights, dtype=np.float32)
         if w.ndim != 2:
