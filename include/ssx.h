@@ -34,7 +34,7 @@ extern "C" {
  *      struct grew by 8 bytes) are new.  Added since without a change of existing entry points or structures (same version): ssx_units_info,
  *      ssx_rccl_probe (round 6); ssx_render_params.libm, appended (a caller with the struct_size before it gets SSX_LIBM_BUILD); the progressive
  *      rendering, spectral output, denoising, develop and demodulated-denoising entry points below; ssx_debug_tile_mask and SSX_DBG_TRACE_MASKED;
- *      ssx_debug_spectral_accumulate; SSX_DBG_TRACE_TOPO; ssx_debug_fold; ssx_debug_step. */
+ *      ssx_debug_spectral_accumulate; SSX_DBG_TRACE_TOPO; ssx_debug_fold; ssx_debug_step; ssx_debug_generate and ssx_generate_info. */
 #define SSX_ABI_VERSION 2
 
 enum {
@@ -306,6 +306,10 @@ int ssx_sums_info(ssx_ctx* ctx, uint64_t* units_parked, uint64_t* units_chained)
  * the calibration render of ssx_upload_scene not counted): the denominator of the counts above, from the code that sizes the
  * launches -- a host need not re-derive the unit size (bench.py did, and was wrong for a render split into batches). */
 int ssx_units_info(ssx_ctx* ctx, uint64_t* units_enqueued);
+/* ... and how those launches got their samples, counted the same way: launches in front of which ssx_generate_kernel ran, and launches whose path kernel
+ * made its samples itself in its refill (kernels of the plane topology with camera rays traced in the path loop; SSX_FUSE_GEN=0 under SSX_DEBUG_ENV=1
+ * keeps the generate kernel).  From the code that decides it, per launch.  Either may be NULL. */
+int ssx_generate_info(ssx_ctx* ctx, uint64_t* generate_launches, uint64_t* fused_launches);
 /* Which path kernel the uploaded scene runs: 0 = the generic one (pass 1 of the intersection loops over the
  * quads), 1 / 2 = the kernel whose pass 1 is specialised to the mesh topology of the reference's Cornell box /
  * plane scene (the scene's quad corners coincide in exactly that pattern; positions are free), 3 = specialised to
@@ -1176,6 +1180,27 @@ int ssx_debug_sample_flux(ssx_ctx* ctx, const ssx_render_params* params, float* 
  * whichever way the uploaded scene traces its camera rays.  out: 4 words per tile slot of the device (slot s = tile tile_first + s * tile_stride of
  * the skewed tile list), word g = primitives 32 g .. 32 g + 31.  Touches neither the sample arrays nor the sums: the continuable state stays. */
 int ssx_debug_tile_mask(ssx_ctx* ctx, const ssx_render_params* params, uint32_t* out);
+/* SAMPLE GENERATION, the first stage of a render, read back: ssx_generate_kernel -- the kernel a render launches, through the launch path a render takes
+ * (the plan a render with `params` gets, ssx_tile_mask_kernel first where camera rays are pre-traced) -- for samples [k0, k0 + n_k) of every pixel of the
+ * device's tiles (tile_first / tile_stride / tile_skew of `params`; its spp is only checked).  No path kernel runs.  pre_hits: 1 = trace the camera rays
+ * (SSX_PRE_HITS=1's mode), 0 = leave them to the path loop, -1 = what the uploaded scene's calibration chose (ssx_calibration_info).
+ * Records come back in the kernel's own order, [tile slot][k - k0][pixel of the tile: 8 * row + column], 4 words each:
+ *   ray = {camera ray direction [3] (binary64 arithmetic, rounded once), lambda_0 (0 in RGB mode)}
+ *   st  = the sample's PCG32 {state lo, state hi, inc lo, inc hi} after its draws (two for the sub-pixel, one for lambda_0 unless RGB mode) -- or, with
+ *         pre_hits and a ray that leaves the scene, the end-of-path form the fold reads: {bits of lambda_0, tail word (no hit, no emission, zero levels,
+ *         previous slot 0x1FFF), state lo, state hi}
+ *   hit = pre_hits only: {dist, st.x, st.y, 2 * primitive + triangle as int bits}; st is +0 unless the primitive's albedo is a texture; a ray that leaves
+ *         the scene has {+inf, 0, 0, -1}
+ * The three arrays are the call's own and are filled with the byte SSX_GENERATE_FILL_BYTE before the launch, so a word that no lane wrote comes back as
+ * 0xA6A6A6A6: all of hit[] without pre_hits, and every record of a lane outside a ragged image.  No record a lane writes is the fill in all its words: as a
+ * float the word is negative, and ray's lambda_0, hit's dist and the end-of-path st's first word are not; a live st's third word is odd (inc), the fill even.
+ * ray, st: [owned tiles * n_k * 64][4]; hit: the same, may be NULL unless camera rays are pre-traced.  Touches neither the context's sample arrays nor its
+ * sums: a render can be continued across the call.
+ * SSX_ERR_ARG with a message: n_k == 0; k0 + n_k beyond 32 bits; pre_hits outside -1..1; hit == NULL where camera rays are pre-traced; more samples per
+ * pixel than one launch of that plan may cover (its sample arrays' budget, at most 65536). */
+#define SSX_GENERATE_FILL_BYTE 0xA6u
+int ssx_debug_generate(ssx_ctx* ctx, const ssx_render_params* params, uint32_t k0, uint32_t n_k, int pre_hits,
+                       float* ray /* [n_rec][4] */, uint32_t* st /* [n_rec][4] */, float* hit /* [n_rec][4] or NULL */);
 /* ssx_spectral_bin_kernel and, with q given, ssx_spectral_moment_kernel -- the very kernels a render launches after each launch of its sample walk, through the
  * launch helpers the render uses -- on sample records the caller supplies, as a pure function of its arguments (no scene needed, like ssx_probe_arrays).  n_k
  * [launches]: the samples per pixel of each launch, K their sum; flux [height][width][K][4]: every sample's hero flux; lambda_0 [height][width][K]: its first hero

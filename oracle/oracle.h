@@ -218,6 +218,15 @@ void orc_scene_set_camera_dir(orc_scene*, const float dir[3]);
 void orc_render_sample(const orc_color*, const orc_scene*, orc_rng*, size_t i, size_t j,
                        size_t W, size_t H, int indirect_only, float out_xyza[4], orc_stats*);
 
+/* The camera part of _render_sample (renderer.cpp:113-138) on its own: the two rand_1d draws (y first), the binary64 ray through pixel (i, j)'s
+ * image point rounded once to float, and -- spectral build only -- the draw of lambda_0 (0 in RGB mode, no draw).  *rng, already seeded, advances by
+ * exactly those draws.  orc_render_sample calls it: one copy of the arithmetic. */
+void orc_camera_sample(const orc_color*, const orc_scene*, orc_rng*, size_t i, size_t j, size_t W, size_t H, float dir[3], float* lambda_0);
+/* Scene::intersect (scene.cpp:433-445) from the camera position along `dir`, nothing ignored.  prim -1: the ray left the scene (which 0, dist +inf,
+ * st 0).  which: the triangle (0 / 1) of the quad that was accepted.  Every member is one 32-bit word. */
+typedef struct { int32_t prim; uint32_t which; float dist, st[2]; } orc_camera_hit;
+void orc_debug_camera_hit(const orc_scene*, const float dir[3], orc_camera_hit* out);
+
 /* One sample's levels, independent of any log layout: what the recursion L() (renderer.cpp:147-255) knows on its way back up.  Every member
  * is one 32-bit word, so a record is also a row of ORC_FOLD_WORDS words (tests/fold_cases.py builds them as such; include/ssx.h
  * ssx_debug_fold takes the same rows).  level[n] is the path's last level; levels 0..n-1 continued, and only they use fs, n_dot_l, pdf. */

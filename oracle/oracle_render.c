@@ -158,11 +158,9 @@ static void dmat4_mul_vec4(const double* m, const double v[4], double o[4]) {
 	for (int r = 0; r < 4; ++r) o[r] = (m[0 * 4 + r] * v[0] + m[1 * 4 + r] * v[1]) + (m[2 * 4 + r] * v[2] + m[3 * 4 + r] * v[3]);
 }
 
-/* renderer.cpp:104-277 */
-void orc_render_sample(const orc_color* cd, const orc_scene* sc, orc_rng* rng, size_t i, size_t j,
-                       size_t W, size_t H, int indirect_only, float out_xyza[4], orc_stats* st) {
-	orc_stats* const tls_saved = orc_tls_stats;
-	orc_tls_stats = st;
+/* renderer.cpp:113-138, the camera part of _render_sample: the two sub-pixel draws, the binary64 ray through the image point rounded once to
+ * float, and (#ifdef RENDER_MODE_SPECTRAL only) the hero wavelength.  *rng advances by exactly those draws. */
+void orc_camera_sample(const orc_color* cd, const orc_scene* sc, orc_rng* rng, size_t i, size_t j, size_t W, size_t H, float dir[3], float* lambda_0) {
 	/* :113 glm::dvec2 subpixel(rand_1d(rng),rand_1d(rng)) -- g++ evaluates the constructor
 	 * arguments right to left, so .y takes the first two draws. */
 	double sub_y = orc_rand_1d(rng);
@@ -171,18 +169,42 @@ void orc_render_sample(const orc_color* cd, const orc_scene* sc, orc_rng* rng, s
 	double st_y = ((double)j + sub_y) / (double)H;
 	double ndc_x = st_x * 2.0 - 1.0, ndc_y = st_y * 2.0 - 1.0;
 
-	orc_v3 camera_ray_dir;
 	{
 		double v[4] = { ndc_x, ndc_y, 0.0, 1.0 }, point[4];
 		dmat4_mul_vec4(sc->camera.matr_PV_inv, v, point);
 		for (int k = 0; k < 4; ++k) point[k] /= point[3]; /* point /= point.w: scalar copied first */
 		double dx = point[0] - (double)sc->camera.pos.x, dy = point[1] - (double)sc->camera.pos.y, dz = point[2] - (double)sc->camera.pos.z;
 		double inv = 1.0 / sqrt((dx * dx + dy * dy) + dz * dz); /* glm::normalize(dvec3) */
-		camera_ray_dir = v3_make((float)(dx * inv), (float)(dy * inv), (float)(dz * inv));
+		dir[0] = (float)(dx * inv); dir[1] = (float)(dy * inv); dir[2] = (float)(dz * inv);
 	}
 
 	/* :138, #ifdef RENDER_MODE_SPECTRAL only: the RGB build draws no wavelength */
-	float lambda_0 = cd->rgb_mode ? 0.0f : cd->lambda_min + orc_rand_1f(rng) * cd->lambda_step;
+	*lambda_0 = cd->rgb_mode ? 0.0f : cd->lambda_min + orc_rand_1f(rng) * cd->lambda_step;
+}
+
+/* What the camera ray along `dir` meets: Scene::intersect (scene.cpp:433-445) from the camera position, nothing ignored. */
+void orc_debug_camera_hit(const orc_scene* sc, const float dir[3], orc_camera_hit* out) {
+	const orc_ray ray = { sc->camera.pos, v3_make(dir[0], dir[1], dir[2]) };
+	orc_hit hitrec;
+	int tri_note[2] = { 0, 0 };
+	int* const note_saved = orc_tls_tri_note;
+	orc_tls_tri_note = tri_note;
+	const int hit = orc_scene_intersect(sc, &ray, &hitrec, -1, NULL);
+	orc_tls_tri_note = note_saved;
+	memset(out, 0, sizeof *out);
+	out->prim = hit ? hitrec.prim : -1;
+	out->dist = hitrec.dist; /* +inf where nothing was met */
+	if (hit) { out->which = (uint32_t)tri_note[1]; out->st[0] = hitrec.st.x; out->st[1] = hitrec.st.y; }
+}
+
+/* renderer.cpp:104-277 */
+void orc_render_sample(const orc_color* cd, const orc_scene* sc, orc_rng* rng, size_t i, size_t j,
+                       size_t W, size_t H, int indirect_only, float out_xyza[4], orc_stats* st) {
+	orc_stats* const tls_saved = orc_tls_stats;
+	orc_tls_stats = st;
+	float cam_dir[3], lambda_0;
+	orc_camera_sample(cd, sc, rng, i, j, W, H, cam_dir, &lambda_0); /* :113-138 */
+	const orc_v3 camera_ray_dir = v3_make(cam_dir[0], cam_dir[1], cam_dir[2]);
 
 	/* `indirect_only` carries two flags: bit 0 = Options::indirect_only, bit 1 = build without ELS */
 	path_ctx c = { cd, sc, rng, lambda_0, indirect_only & 1, !(indirect_only & 2), 0, st, 0, orc_tls_level_log, NULL };

@@ -154,7 +154,9 @@ HIP_SYMBOLS = ["ssx_create", "ssx_destroy", "ssx_upload_scene", "ssx_render_star
                "ssx_optics_images", "ssx_spectral_develop_optics",
                "ssx_defocus_images", "ssx_spectral_develop_lens",
                "ssx_sensor_images", "ssx_demosaic_images", "ssx_spectral_develop_sensor",
-               "ssx_debug_tile_mask", "ssx_debug_spectral_accumulate", "ssx_debug_fold", "ssx_debug_step"]
+               "ssx_debug_tile_mask", "ssx_debug_spectral_accumulate", "ssx_debug_fold", "ssx_debug_step",
+               "ssx_debug_generate", "ssx_generate_info"]
+SSX_GENERATE_FILL_BYTE = 0xA6   # ssx_debug_generate: what a word no lane wrote holds, byte by byte (include/ssx.h)
 # ssx_debug_fold: a sample's row of levels (include/ssx.h)
 SSX_FOLD_ROW_WORDS, SSX_FOLD_LAMBDA0, SSX_FOLD_CAM_DIR, SSX_FOLD_HIT, SSX_FOLD_N, SSX_FOLD_LEVEL0, SSX_FOLD_LEVEL_WORDS = 160, 0, 1, 4, 5, 10, 15
 SSX_FOLD_L_FS, SSX_FOLD_L_NDL, SSX_FOLD_L_PDF, SSX_FOLD_L_FLAGS, SSX_FOLD_L_EMISSION, SSX_FOLD_L_NEE = 0, 4, 5, 6, 7, 11
@@ -456,6 +458,9 @@ def hip_lib():
             lib.ssx_debug_fold.argtypes = [vp, C.POINTER(SsxRenderParams), C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, vp, vp]
         if not override or hasattr(lib, "ssx_debug_step"):  # one iteration of the path loop on the caller's paths
             lib.ssx_debug_step.argtypes = [vp, C.POINTER(SsxRenderParams), C.c_uint32, C.c_uint32, vp, vp]
+        if not override or hasattr(lib, "ssx_debug_generate"):  # the generate kernel's records, read back; which launches made their samples where
+            lib.ssx_debug_generate.argtypes = [vp, C.POINTER(SsxRenderParams), C.c_uint32, C.c_uint32, C.c_int, vp, vp, vp]
+            lib.ssx_generate_info.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         lib.ssx_kernel_variant.argtypes = [vp]
         lib.ssx_kernel_name.argtypes = [vp]
         lib.ssx_kernel_name.restype = C.c_char_p

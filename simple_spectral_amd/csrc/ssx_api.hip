@@ -124,6 +124,7 @@ struct ssx_ctx {
 	uint32_t total_spp = 0;
 	int worker_rc = 0;
 	std::atomic<uint64_t> units_enqueued{0}; // work units of every path-kernel launch so far: added to by the worker, read by ssx_units_info
+	std::atomic<uint64_t> launches_generated{0}, launches_fused{0}; // launches of a render whose samples ssx_generate_kernel made / the path kernel's refill made (ssx_generate_info)
 	ssx_render_params cur{};
 	// Progressive rendering (csrc/ssx_progressive.hip).  What d_accum holds -- continuable: every owned pixel holds samples [0, done_spp) of `cur`,
 	// the sums may be continued or exported; noise_valid: d_noise describes them, after noise_batches batches (B).  Written by sums_invalidate /
@@ -582,6 +583,7 @@ int launch_batch(ssx_ctx* ctx, Batch& b, hipStream_t stream) {
 	if (plan && (rc = blocks_that_fit(ctx, path_kernel, path_lds_bytes(b.a.blob_words, ctx->queue_words), &ctx->resident_blocks))) return rc;
 	if ((rc = enqueue_path(ctx, b, path_kernel, ctx->queue_words, b.a.blob_words, ctx->resident_blocks, stream))) return rc;
 	ctx->units_enqueued.fetch_add(b.units);
+	(b.a.fuse_gen ? ctx->launches_fused : ctx->launches_generated).fetch_add(1u);
 	if (ctx->timing) for (int k = 2; k < 6; ++k) SSX_HIP(ctx, hipEventRecord(b.tev[k], stream)); // (fold and pixel sums ran inside the path kernel: their slots stay ~0)
 	return SSX_OK;
 }
@@ -1391,6 +1393,49 @@ int ssx_debug_tile_mask(ssx_ctx* ctx, const ssx_render_params* p_in, uint32_t* o
 	return SSX_OK;
 }
 
+// Samples [k0, k0 + n_k) of every owned pixel as the first stage of a render makes them: the launch plan of a render with these parameters (make_plan), then
+// enqueue_generate itself -- ssx_tile_mask_kernel where camera rays are pre-traced, ssx_generate_kernel with the grid a render gives it -- on sample arrays and
+// tile masks of the call's own, filled with SSX_GENERATE_FILL_BYTE beforehand: a word no lane wrote comes back as the fill.  No path kernel runs; the context's
+// sample arrays, sums and continuable state are not touched.  pre_hits: 0 / 1, or -1 for what the uploaded scene's calibration chose.
+int ssx_debug_generate(ssx_ctx* ctx, const ssx_render_params* p_in, uint32_t k0, uint32_t n_k, int pre_hits, float* ray, uint32_t* st, float* hit) {
+	if (!ctx || !ray || !st) return SSX_ERR_ARG;
+	ssx_render_params pp;
+	int rc = begin_render(ctx, p_in, &pp, "render in progress");
+	if (rc) return rc;
+	if (n_k == 0) return fail(ctx, SSX_ERR_ARG, "ssx_debug_generate: n_k must be positive");
+	if ((uint64_t)k0 + n_k > 0xFFFFFFFFull) return fail(ctx, SSX_ERR_ARG, "ssx_debug_generate: k0 + n_k does not fit in 32 bits");
+	if (pre_hits < -1 || pre_hits > 1) return fail(ctx, SSX_ERR_ARG, "ssx_debug_generate: pre_hits is 0, 1 or -1 (the context's own choice)");
+	const bool pre = pre_hits < 0 ? ctx->pre_hits : pre_hits == 1;
+	if (pre && !hit) return fail(ctx, SSX_ERR_ARG, "ssx_debug_generate: camera rays are pre-traced, hit must not be NULL");
+	SSX_HIP(ctx, hipSetDevice(ctx->device));
+	if ((rc = wait_device_pending(ctx))) return rc;
+	const LaunchPlan pl = make_plan(ctx, &pp);
+	if (n_k > pl.max_spp_per_launch) return fail(ctx, SSX_ERR_ARG, fmt("ssx_debug_generate: %u samples per pixel are more than one launch may cover (%u)", n_k, pl.max_spp_per_launch));
+	Batch b{};
+	b.a = pl.args;
+	SsxKernelArgs& a = b.a;
+	if (a.my_tiles == 0u) return SSX_OK;
+	a.k0 = k0; a.k1 = k0 + n_k;
+	a.n_records = (uint64_t)a.my_tiles * n_k * 64u;
+	a.pre_hits = pre ? 1u : 0u;
+	b.n_rec = a.n_records;
+	const size_t rec_bytes = (size_t)a.n_records * 16u, mask_bytes = (size_t)a.my_tiles * 4u * sizeof(uint32_t);
+	DeviceBuffer d_rec, d_mask;
+	if (d_rec.reserve(3u * rec_bytes) != hipSuccess || d_mask.reserve(mask_bytes) != hipSuccess) { (void)hipGetLastError(); return fail(ctx, SSX_ERR_DEVICE, "out of device memory (ssx_debug_generate)"); }
+	SSX_HIP(ctx, hipMemsetAsync(d_rec.ptr, (int)SSX_GENERATE_FILL_BYTE, 3u * rec_bytes, ctx->stream));
+	SSX_HIP(ctx, hipMemsetAsync(d_mask.ptr, 0, mask_bytes, ctx->stream));
+	a.ray = reinterpret_cast<float4*>(d_rec.as<uint8_t>());
+	a.st = reinterpret_cast<uint4*>(d_rec.as<uint8_t>() + rec_bytes);
+	a.hit = reinterpret_cast<float4*>(d_rec.as<uint8_t>() + 2u * rec_bytes);
+	a.tile_mask = d_mask.as<uint32_t>();
+	if ((rc = enqueue_generate(ctx, b, ctx->stream))) return rc;
+	SSX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	SSX_HIP(ctx, hipMemcpy(ray, a.ray, rec_bytes, hipMemcpyDeviceToHost));
+	SSX_HIP(ctx, hipMemcpy(st, a.st, rec_bytes, hipMemcpyDeviceToHost));
+	if (hit) SSX_HIP(ctx, hipMemcpy(hit, a.hit, rec_bytes, hipMemcpyDeviceToHost));
+	return SSX_OK;
+}
+
 // The fold on the caller's levels (csrc/ssx_debug.hip debug_fold_body): the twin a render of this context with these parameters runs -- queue entries as
 // pick_queue finds them for that render's path kernel, its libm, its _flux twin while spectral output is on -- in buffers of the call's own: sample arrays,
 // level logs and sums.  Neither the context's arrays nor its libm, plan or continuable state are touched.
@@ -1618,6 +1663,13 @@ int ssx_sums_info(ssx_ctx* ctx, uint64_t* units_parked, uint64_t* units_chained)
 int ssx_units_info(ssx_ctx* ctx, uint64_t* units_enqueued) {
 	if (!ctx) return SSX_ERR_ARG;
 	if (units_enqueued) *units_enqueued = ctx->units_enqueued.load();
+	return SSX_OK;
+}
+
+int ssx_generate_info(ssx_ctx* ctx, uint64_t* generate_launches, uint64_t* fused_launches) {
+	if (!ctx) return SSX_ERR_ARG;
+	if (generate_launches) *generate_launches = ctx->launches_generated.load();
+	if (fused_launches) *fused_launches = ctx->launches_fused.load();
 	return SSX_OK;
 }
 

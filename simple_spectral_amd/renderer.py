@@ -1404,6 +1404,23 @@ class Renderer:
         self._check(self._lib.ssx_debug_tile_mask(self._ctx, C.byref(p), out.ctypes.data))
         return out
 
+    def debug_generate(self, k0=0, n_k=1, pre_hits=-1, **over):
+        """ssx_debug_generate: ssx_generate_kernel's records for samples [k0, k0 + n_k) of the device's tiles, in the kernel's own order -> (ray, st, hit), each
+        uint32 [slots, n_k, 64, 4] (float32 words as their bits; lane = 8 * row + column of the tile).  pre_hits: 0 / 1 / -1 (the context's own choice).  Words no
+        lane wrote hold _capi.SSX_GENERATE_FILL_BYTE in every byte: all of hit without pre_hits, and the lanes outside a ragged image."""
+        p = self.params(**over)
+        tx, ty = (p.width + 7) // 8, (p.height + 7) // 8
+        slots = (tx * ty - p.tile_first + p.tile_stride - 1) // p.tile_stride if tx * ty > p.tile_first else 0
+        ray, st, hit = (np.zeros((slots, int(n_k), 64, 4), dtype=np.uint32) for _ in range(3))
+        self._check(self._lib.ssx_debug_generate(self._ctx, C.byref(p), int(k0), int(n_k), int(pre_hits), ray.ctypes.data, st.ctypes.data, hit.ctypes.data))
+        return ray, st, hit
+
+    def generate_info(self):
+        """ssx_generate_info: launches of this context's renders in front of which the generate kernel ran, and launches whose path kernel made its samples itself."""
+        a, b = C.c_uint64(), C.c_uint64()
+        self._check(self._lib.ssx_generate_info(self._ctx, C.byref(a), C.byref(b)))
+        return {"generate_launches": a.value, "fused_launches": b.value}
+
     def debug_fold(self, levels, spp, order_seed=0, parked=False, flux=False, **over):
         """ssx_debug_fold: the path kernel's fold on `levels`, uint32 [n_pixels * spp, SSX_FOLD_ROW_WORDS] rows in [pixel][k] order (n_pixels a multiple of 64)
         -> (flux uint32 [n, 4] or None, xyza uint32 [n, 4], sums float64 [n_pixels, 4]): the float32 results as their bits."""

@@ -52,6 +52,10 @@ class Hit(C.Structure):
     _fields_ = [("prim", C.c_int), ("normal", V3), ("st", V2), ("dist", C.c_float)]
 
 
+class CameraHit(C.Structure):   # orc_camera_hit
+    _fields_ = [("prim", C.c_int32), ("which", C.c_uint32), ("dist", C.c_float), ("st", C.c_float * 2)]
+
+
 class Stats(C.Structure):
     _fields_ = [
         (n, C.c_uint64)
@@ -137,6 +141,10 @@ def load(variant=""):
     lib.orc_seed_sample.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(Rng)]
     lib.orc_render_sample.argtypes = [vp, vp, C.POINTER(Rng), C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
                                       C.c_int, f32p, C.POINTER(Stats)]
+    lib.orc_camera_sample.restype = None
+    lib.orc_camera_sample.argtypes = [vp, vp, C.POINTER(Rng), C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, f32p, f32p]
+    lib.orc_debug_camera_hit.restype = None
+    lib.orc_debug_camera_hit.argtypes = [vp, f32p, C.POINTER(CameraHit)]
     lib.orc_render.restype = C.c_int
     lib.orc_render.argtypes = [vp, vp, C.c_uint64] + [C.c_size_t] * 7 + [C.c_int, C.c_int, vp, C.POINTER(Stats)]
     lib.orc_xyza_to_srgba.argtypes = [vp, vp, vp, C.c_size_t]
@@ -295,6 +303,25 @@ class Oracle:
                     xyza[j - j0, i - i0, k] = out[:]
                     state[j - j0, i - i0, k] = rng.state
         return xyza, state, st
+
+    def camera_samples(self, pixels, ks, W, H, seed=0):
+        """orc_seed_sample + orc_camera_sample + orc_debug_camera_hit per item: pixels [n, 2] of (i, j), ks [n] -> dict of
+        dir float32 [n, 3], lambda_0 float32 [n], state / inc uint64 [n] (the stream after the sample's draws), prim int32 [n] (-1: the ray
+        left the scene), which uint32 [n], dist float32 [n], st float32 [n, 2]."""
+        pixels = np.asarray(pixels, dtype=np.int64).reshape(-1, 2)
+        ks = np.asarray(ks, dtype=np.uint64).reshape(-1)
+        n = len(ks)
+        assert len(pixels) == n
+        out = {"dir": np.zeros((n, 3), np.float32), "lambda_0": np.zeros(n, np.float32), "state": np.zeros(n, np.uint64), "inc": np.zeros(n, np.uint64),
+               "prim": np.zeros(n, np.int32), "which": np.zeros(n, np.uint32), "dist": np.zeros(n, np.float32), "st": np.zeros((n, 2), np.float32)}
+        rng, d, lam, hit = Rng(), (C.c_float * 3)(), C.c_float(), CameraHit()
+        for r, ((i, j), k) in enumerate(zip(pixels.tolist(), ks.tolist())):
+            self.lib.orc_seed_sample(seed, j * W + i, k, C.byref(rng))
+            self.lib.orc_camera_sample(self.color, self.scene, C.byref(rng), i, j, W, H, d, C.byref(lam))
+            self.lib.orc_debug_camera_hit(self.scene, d, C.byref(hit))
+            out["dir"][r] = d[:]; out["lambda_0"][r] = lam.value; out["state"][r] = rng.state; out["inc"][r] = rng.inc
+            out["prim"][r] = hit.prim; out["which"][r] = hit.which; out["dist"][r] = hit.dist; out["st"][r] = hit.st[:]
+        return out
 
     def albedo(self, quads, st, lambda_0):
         """orc_quad_albedo per item: quads [n] int, st [n, 2] and lambda_0 [n] float32 -> [n, 4] float32."""
