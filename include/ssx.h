@@ -350,6 +350,20 @@ void ssx_jit_counters(uint64_t* compiled, uint64_t* disk_hits);
  * the same names with "_glibc" appended, after one with spectral output on with "_flux" -- the run-time compiled "ssx_render_kernel_jit" keeps
  * its name).  NULL: no scene. */
 const char* ssx_kernel_name(ssx_ctx* ctx);
+/* Render switches compiled into the path kernel.  The reference fixes its switches when it is built (src/stdafx.hpp); here each is a run-time
+ * variant.  A render and a scene that are the reference's default build on Lambertian surfaces and quad lights -- none of the traits below -- run
+ * the "_plain" twin of the kernel ssx_kernel_name names (same bits: the tests on the switches are compiled out of its loop, nothing else changes;
+ * ssx_kernel_name keeps reporting the name without the suffix).  Any trait sends the render to the general kernel.
+ * ssx_scene_traits / ssx_render_traits: the traits of a scene description / of render parameters, 0 = plain; host arithmetic only, no device and no
+ * context (-1: bad argument).  ssx_switches_info: 1 = the context's current (or last) render ran, or a render with default parameters would run,
+ * the kernel with the switches compiled in; 0 = the general kernel; -1 = no scene.  ssx_debug_samples always runs the general kernel (its
+ * renders keep every sample).  SSX_PLAIN_KERNEL=0 under SSX_DEBUG_ENV=1 forces the general kernels (A/B runs, tests). */
+enum { SSX_TRAIT_INDIRECT_ONLY = 1u, SSX_TRAIT_NO_ELS = 2u, SSX_TRAIT_MIRROR = 4u, SSX_TRAIT_TRI_LIGHT = 8u, SSX_TRAIT_UPLIFT = 16u,
+       SSX_TRAIT_RGB_MODE = 32u, SSX_TRAIT_NO_FLAT_FIELD = 64u, SSX_TRAIT_KEEP_SAMPLES = 128u,
+       SSX_TRAIT_LIBM = 256u, SSX_TRAIT_SPECTRAL_BINS = 512u, SSX_TRAIT_FORCED_OFF = 1024u }; /* (the last three: kernels that keep the general body, and the switch) */
+int ssx_scene_traits(const ssx_scene_desc* scene);
+int ssx_render_traits(const ssx_render_params* params);
+int ssx_switches_info(ssx_ctx* ctx);
 
 /* ---- Progressive rendering: continue, checkpoint / resume, noise estimate (appended; same ABI version) --------------------------------
  * A pixel's sum is double += float(sample * 0.001f) in ascending k and is scaled by 1000 / spp only when the image is made (seeding

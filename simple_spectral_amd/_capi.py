@@ -132,6 +132,9 @@ SSX_PRIM_LIGHT, SSX_PRIM_TRI = 1, 0x100
 SSX_OK, SSX_ERR_DATA, SSX_ERR_ARG, SSX_ERR_SCENE, SSX_ERR_DEVICE, SSX_ERR_STATE = 0, -1, -2, -3, -10, -11
 SSX_ABI_VERSION = 2   # include/ssx.h; checked against the library at load
 SSX_JIT_OFF, SSX_JIT_AT_UPLOAD, SSX_JIT_BACKGROUND = 0, 1, 2
+# ssx_scene_traits / ssx_render_traits (include/ssx.h): what keeps a render off the kernels with the render switches compiled in
+(SSX_TRAIT_INDIRECT_ONLY, SSX_TRAIT_NO_ELS, SSX_TRAIT_MIRROR, SSX_TRAIT_TRI_LIGHT, SSX_TRAIT_UPLIFT, SSX_TRAIT_RGB_MODE, SSX_TRAIT_NO_FLAT_FIELD,
+ SSX_TRAIT_KEEP_SAMPLES, SSX_TRAIT_LIBM, SSX_TRAIT_SPECTRAL_BINS, SSX_TRAIT_FORCED_OFF) = (1 << i for i in range(11))
 SSX_JIT_STATE_NONE, SSX_JIT_STATE_GENERIC_MEANWHILE, SSX_JIT_STATE_SPECIALISED, SSX_JIT_STATE_FAILED = 0, 1, 2, -1
 
 # every symbol include/ssx.h and include/ssx_host.h declare (tests check the libraries export them)
@@ -155,7 +158,8 @@ HIP_SYMBOLS = ["ssx_create", "ssx_destroy", "ssx_upload_scene", "ssx_render_star
                "ssx_defocus_images", "ssx_spectral_develop_lens",
                "ssx_sensor_images", "ssx_demosaic_images", "ssx_spectral_develop_sensor",
                "ssx_debug_tile_mask", "ssx_debug_spectral_accumulate", "ssx_debug_fold", "ssx_debug_step",
-               "ssx_debug_generate", "ssx_generate_info"]
+               "ssx_debug_generate", "ssx_generate_info",
+               "ssx_scene_traits", "ssx_render_traits", "ssx_switches_info"]
 SSX_GENERATE_FILL_BYTE = 0xA6   # ssx_debug_generate: what a word no lane wrote holds, byte by byte (include/ssx.h)
 # ssx_debug_fold: a sample's row of levels (include/ssx.h)
 SSX_FOLD_ROW_WORDS, SSX_FOLD_LAMBDA0, SSX_FOLD_CAM_DIR, SSX_FOLD_HIT, SSX_FOLD_N, SSX_FOLD_LEVEL0, SSX_FOLD_LEVEL_WORDS = 160, 0, 1, 4, 5, 10, 15
@@ -464,5 +468,9 @@ def hip_lib():
         lib.ssx_kernel_variant.argtypes = [vp]
         lib.ssx_kernel_name.argtypes = [vp]
         lib.ssx_kernel_name.restype = C.c_char_p
+        if hasattr(lib, "ssx_switches_info"):  # (an older build loaded through SSX_HIP_LIB_OVERRIDE for an A/B run has none of the three)
+            lib.ssx_switches_info.argtypes = [vp]
+            lib.ssx_scene_traits.argtypes = [vp]
+            lib.ssx_render_traits.argtypes = [vp]
         _hip = lib
     return _hip

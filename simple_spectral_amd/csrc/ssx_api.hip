@@ -86,7 +86,8 @@ struct ssx_ctx {
 	int jit_mode = SSX_JIT_BACKGROUND; // ssx_set_jit: how pass 1 gets specialised for scenes that match no built-in topology
 	const ssx_jit::Kernels* jit_kernels[ssx_jit::kVariants] = {}; // [variant: libm, or ssx_jit::kVariantFlux] the run-time compiled kernels of the uploaded scene (topology 3), a mode's when its first render needs them
 	uint32_t libm = SSX_LIBM_BUILD; // the libm of the current (or last) render
-	uint32_t variant = SSX_LIBM_BUILD; // which kernel twins that render runs (path_kernel_ref): its libm, or ssx_jit::kVariantFlux -- the default libm's _flux twins -- while spectral output is on
+	uint32_t variant = SSX_LIBM_BUILD; // which kernel twins that render runs (path_kernel_ref): its libm, or ssx_jit::kVariantFlux -- the default libm's _flux twins -- while spectral output is on,
+	                                   // or ssx_jit::kVariantPlain -- the default libm's _plain twins -- for a plain render of a plain scene (variant_of)
 	// A scene waiting for its own kernels runs the generic one meanwhile: its second blob (packed for topology 3 at upload, the
 	// caller's description is gone later) waits on the device, and the context swaps at the start of a render once the code is
 	// there (maybe_swap_jit).  The compilation is asked for once the context has launched kJitAfterSamples on the generic kernel.
@@ -98,6 +99,7 @@ struct ssx_ctx {
 	std::vector<DeviceBuffer> d_textures;
 	DeviceBuffer d_jh_data;         // the uplift's table (Jakob-Hanika coefficients / Meng grid)
 	bool rgb_mode = false;     // scene uploaded with uplift == SSX_MODE_RGB
+	uint32_t scene_traits = 0; // SSX_TRAIT_* of the uploaded scene (scene_traits_of): 0 = its renders may run the kernels with the switches compiled in (variant_of)
 	bool fuse_resolve = true;  // false only during the calibration render (no fold: its tail words are read back)
 	float calib_frames = 0.0f; // frames per sample measured by the calibration render of ssx_upload_scene
 	float calib_left = 0.0f;   // rays per sample that left the scene in it (camera and continuation rays)
@@ -295,6 +297,37 @@ constexpr uint64_t kSamplesPerSync = (uint64_t)32 << 20;
 
 struct LaunchPlan { SsxKernelArgs args; uint32_t max_spp_per_launch; };
 
+// The render switches the reference fixes at compile time (stdafx.hpp) and this library takes at run time.  A scene and a render
+// with none of these traits are "plain": the path kernels exist a second time with exactly that compiled in (render_body's PLAIN, the _plain
+// twins), without the tests on the switches in their loop.
+// Scene side, from the description (what pack_blob writes into the quad records and the header): a quad on a mirror material, a top-level
+// triangle among the lights, an uplift other than "ours".  (Malformed indices are pack_blob's to refuse: skipped here.)
+uint32_t scene_traits_of(const ssx_scene_desc* s) {
+	uint32_t t = 0;
+	for (uint32_t q = 0; q < s->n_quads; ++q) if (s->quads[q].material < s->n_materials && s->materials[s->quads[q].material].kind != SSX_MTL_LAMBERTIAN) t |= SSX_TRAIT_MIRROR;
+	for (uint32_t i = 0; i < s->n_lights; ++i) if (s->lights[i] < s->n_quads && (s->quads[s->lights[i]].flags & SSX_PRIM_TRI)) t |= SSX_TRAIT_TRI_LIGHT;
+	if (s->uplift == SSX_MODE_RGB) t |= SSX_TRAIT_RGB_MODE;
+	else if (s->uplift != SSX_UPLIFT_OURS) t |= SSX_TRAIT_UPLIFT;
+	return t;
+}
+// Render side, from the parameters (take_params' struct); keep_samples is the entry point's (ssx_debug_samples).
+uint32_t render_traits_of(const ssx_render_params* p, bool keep_samples) {
+	return (p->indirect_only ? SSX_TRAIT_INDIRECT_ONLY : 0u) | (p->no_explicit_light_sampling ? SSX_TRAIT_NO_ELS : 0u) |
+	       (p->no_flat_field_correction ? SSX_TRAIT_NO_FLAT_FIELD : 0u) | (keep_samples ? SSX_TRAIT_KEEP_SAMPLES : 0u) | (p->libm != SSX_LIBM_BUILD ? SSX_TRAIT_LIBM : 0u);
+}
+// Everything that keeps a render of the context off the _plain kernels: the two above, spectral output (its _flux twins keep the general body) and
+// SSX_PLAIN_KERNEL=0 (under SSX_DEBUG_ENV=1: A/B runs and tests).
+uint32_t traits_of(const ssx_ctx* ctx, const ssx_render_params* p, bool keep_samples) {
+	const char* e = debug_env("SSX_PLAIN_KERNEL");
+	return ctx->scene_traits | render_traits_of(p, keep_samples) | (ctx->spectral_bins ? SSX_TRAIT_SPECTRAL_BINS : 0u) | (e && e[0] == '0' ? SSX_TRAIT_FORCED_OFF : 0u);
+}
+// Which kernel twins a render runs (ssx_ctx::variant).  Decided for EVERY render from its own parameters and the context's state at that moment
+// (ready_to_launch): nothing of an earlier render's choice is kept.
+uint32_t variant_of(const ssx_ctx* ctx, const ssx_render_params* p, bool keep_samples = false) {
+	if (ctx->spectral_bins && p->libm == SSX_LIBM_BUILD && !ctx->rgb_mode) return ssx_jit::kVariantFlux;
+	return traits_of(ctx, p, keep_samples) == 0u ? (uint32_t)ssx_jit::kVariantPlain : p->libm;
+}
+
 LaunchPlan make_plan(ssx_ctx* ctx, const ssx_render_params* p, bool ask_device = true) {
 	LaunchPlan pl{};
 	SsxKernelArgs& a = pl.args;
@@ -462,7 +495,7 @@ size_t path_lds_bytes(uint32_t blob_words, uint32_t queue_words) {
 #endif
 	return n;
 }
-// The path megakernels of this library: [variant: libm 0 / 1, or 2 = the default libm's _flux twins (spectral output)][pass-1 variant: 0 generic, 1 Cornell
+// The path megakernels of this library: [variant: libm 0 / 1, 2 = the default libm's _flux twins (spectral output), or 3 = its _plain twins (the render switches compiled in: variant_of)][pass-1 variant: 0 generic, 1 Cornell
 // topology, 2 plane topology][narrow queue entries].
 // Topology 3 runs the run-time compiled pair of the scene's pattern (ssx_ctx::jit_kernels), named the same in both modes (other modules).
 struct PathKernel { const char* name; void (*host)(SsxKernelArgs); };
@@ -473,7 +506,9 @@ static const PathKernel kPathKernels[ssx_jit::kVariants][3][2] = {
 	{ { SSX_PK(ssx_render_kernel_glibc), SSX_PK(ssx_render_kernel_nq_glibc) }, { SSX_PK(ssx_render_kernel_cornell_glibc), SSX_PK(ssx_render_kernel_cornell_nq_glibc) },
 	  { SSX_PK(ssx_render_kernel_plane_glibc), SSX_PK(ssx_render_kernel_plane_nq_glibc) } },
 	{ { SSX_PK(ssx_render_kernel_flux), SSX_PK(ssx_render_kernel_nq_flux) }, { SSX_PK(ssx_render_kernel_cornell_flux), SSX_PK(ssx_render_kernel_cornell_nq_flux) },
-	  { SSX_PK(ssx_render_kernel_plane_flux), SSX_PK(ssx_render_kernel_plane_nq_flux) } } };
+	  { SSX_PK(ssx_render_kernel_plane_flux), SSX_PK(ssx_render_kernel_plane_nq_flux) } },
+	{ { SSX_PK(ssx_render_kernel_plain), SSX_PK(ssx_render_kernel_nq_plain) }, { SSX_PK(ssx_render_kernel_cornell_plain), SSX_PK(ssx_render_kernel_cornell_nq_plain) },
+	  { SSX_PK(ssx_render_kernel_plane_plain), SSX_PK(ssx_render_kernel_plane_nq_plain) } } };
 #undef SSX_PK
 static const char* const kJitKernelNames[2] = { "ssx_render_kernel_jit", "ssx_render_kernel_jit_nq" };
 // this library's kernel for the context's libm and topology (a scene still waiting for its own kernels runs the generic one)
@@ -572,6 +607,9 @@ int enqueue_path(ssx_ctx* ctx, Batch& b, const KernelRef& kernel, uint32_t queue
 int launch_batch(ssx_ctx* ctx, Batch& b, hipStream_t stream) {
 	if (b.rc) return b.rc; // make_batch refused the launch, or could not get the waves' logs
 	int rc;
+	// (a _plain kernel does not look at the switches: a launch that carries one must never reach it)
+	if (ctx->variant == ssx_jit::kVariantPlain && (b.a.indirect_only | b.a.no_els | b.a.no_flat_field | b.a.rgb_mode | b.a.keep_samples | ctx->scene_traits))
+		return fail(ctx, SSX_ERR_STATE, "internal: a render with a switch set was about to launch the kernel with the switches compiled in");
 	if (ctx->timing) { if ((rc = timing_events(ctx, &b.tev))) return rc; SSX_HIP(ctx, hipEventRecord(b.tev[0], stream)); }
 	b.a.fuse_gen = fuses_generate(ctx, b.a) ? 1u : 0u;
 	if (!b.a.fuse_gen && (rc = enqueue_generate(ctx, b, stream))) return rc;
@@ -632,10 +670,12 @@ int ensure_libm_kernels(ssx_ctx* ctx, uint32_t libm) {
 
 // The context ready to launch a render with `p`: the kernels of its libm there and current (the plan of the resident workgroups is
 // redone when the libm changes: the twins are different kernels), the pixel sums and -- asked for -- the output image sized.
-int ready_to_launch(ssx_ctx* ctx, const ssx_render_params* p, bool need_out) {
+int ready_to_launch(ssx_ctx* ctx, const ssx_render_params* p, bool need_out, bool keep_samples = false) {
 	// spectral output on: the _flux twins (a specialised scene's are compiled here, on the calling thread, at its first spectral render).  They exist for the
 	// default libm and spectral scenes only; the entry points refuse the rest while it is on (spectral_refuses)
-	const uint32_t variant = (ctx->spectral_bins && p->libm == SSX_LIBM_BUILD && !ctx->rgb_mode) ? ssx_jit::kVariantFlux : p->libm;
+	// A plain render of a plain scene: the _plain twins, likewise.  The choice is made here for every render, so a switch flipped on a context that has
+	// rendered plain changes kernels (and the plan of the resident workgroups) at the next render.
+	const uint32_t variant = variant_of(ctx, p, keep_samples);
 	const int rc = ensure_libm_kernels(ctx, variant);
 	if (rc) return rc;
 	// (a scene still waiting for its own kernels asks again, for this mode's: maybe_swap_jit)
@@ -1016,6 +1056,7 @@ int ssx_upload_scene(ssx_ctx* ctx, const ssx_scene_desc* s) {
 	if (s->uplift != SSX_MODE_RGB && s->uplift != SSX_UPLIFT_OURS && s->uplift != SSX_UPLIFT_JH && s->uplift != SSX_UPLIFT_MENG)
 		return fail(ctx, SSX_ERR_SCENE, "unsupported uplift variant (0 = RGB mode, 1 = basis, 2 = Meng et al., 3 = Jakob-Hanika)");
 	ctx->rgb_mode = (s->uplift == SSX_MODE_RGB);
+	ctx->scene_traits = scene_traits_of(s);
 	ctx->d_jh_data.release();
 	if (s->uplift == SSX_UPLIFT_MENG) {
 		// device table: 16 header words, cells, points (layout documented at meng_uplift in ssx_kernels.hip)
@@ -1064,17 +1105,23 @@ int ssx_upload_scene(ssx_ctx* ctx, const ssx_scene_desc* s) {
 	// process's memory or the disk cache at once; else compiled here (mode 1) or by the background thread later (mode 2), the
 	// generic kernel serving meanwhile.  A failure of any kind leaves the scene on the generic kernel: same bits.
 	const int jit_mode = env_on("SSX_JIT_PASS1") ? SSX_JIT_AT_UPLOAD : ctx->jit_mode;
+	// The kernels looked for (and, asked for at upload, compiled) here are those a render with default parameters will run: the scene's _plain twins if
+	// its traits allow them.  A render with other switches gets its own at its start (ensure_libm_kernels), as a glibc-mode render does.  The context's
+	// variant follows, unless its last render chose glibc mode or spectral output: what the introspection calls report until the next render decides again.
+	ssx_render_params defaults{};
+	const uint32_t upload_variant = variant_of(ctx, &defaults) == ssx_jit::kVariantPlain ? (uint32_t)ssx_jit::kVariantPlain : (uint32_t)SSX_LIBM_BUILD;
+	if (ctx->variant == SSX_LIBM_BUILD || ctx->variant == ssx_jit::kVariantPlain) ctx->variant = upload_variant;
 	if (info.candidate && jit_mode != SSX_JIT_OFF) {
 		std::string err;
 		const ssx_jit::Kernels* k = nullptr;
-		ssx_jit::State st = ssx_jit::lookup(ctx->device, info.vid, &k, &err);
+		ssx_jit::State st = ssx_jit::lookup(ctx->device, info.vid, &k, &err, upload_variant);
 		if (st != ssx_jit::State::Ready && st != ssx_jit::State::Failed && jit_mode == SSX_JIT_AT_UPLOAD) {
-			k = ssx_jit::get(ctx->device, info.vid, &err);
+			k = ssx_jit::get(ctx->device, info.vid, &err, upload_variant);
 			st = k ? ssx_jit::State::Ready : ssx_jit::State::Failed;
 		}
 		if (st == ssx_jit::State::Failed) { ctx->jit_state = SSX_JIT_STATE_FAILED; ctx->jit_message = err; }
 		else if ((rc = pack_blob(s, tex, ctx->d_jh_data.ptr, blob_jit, pack_err, 3))) return fail(ctx, rc, pack_err);
-		else if (st == ssx_jit::State::Ready) { blob.swap(blob_jit); blob_jit.clear(); ctx->jit_kernels[SSX_LIBM_BUILD] = k; ctx->jit_vid = info.vid; ctx->jit_state = SSX_JIT_STATE_SPECIALISED; }
+		else if (st == ssx_jit::State::Ready) { blob.swap(blob_jit); blob_jit.clear(); ctx->jit_kernels[upload_variant] = k; ctx->jit_vid = info.vid; ctx->jit_state = SSX_JIT_STATE_SPECIALISED; }
 		else { ctx->jit_pending = true; ctx->jit_vid = info.vid; ctx->jit_state = SSX_JIT_STATE_GENERIC_MEANWHILE; ctx->jit_requested = (st == ssx_jit::State::Pending); }
 	}
 	if (ctx->jit_pending) {
@@ -1142,7 +1189,7 @@ int ssx_render_device(ssx_ctx* ctx, const ssx_render_params* p_in, void* d_xyza_
 	const bool capturing = capture == hipStreamCaptureStatusActive;
 	if (ctx->device_pending && capturing) return fail(ctx, SSX_ERR_STATE, "a render of this context may still be queued: ssx_render_device_wait before capturing another into a graph");
 	// (the kernels of another libm may need a compilation and change the plan of the resident workgroups: not while capturing)
-	if (capturing && ctx->variant != p->libm) return fail(ctx, SSX_ERR_STATE, "ssx_render_params.libm differs from the context's last render: run it once outside the stream capture first");
+	if (capturing && ctx->variant != variant_of(ctx, p)) return fail(ctx, SSX_ERR_STATE, "ssx_render_params.libm differs from the context's last render: run it once outside the stream capture first");
 	if (ctx->device_pending) SSX_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev_device_done, 0));
 	{
 		LaunchPlan probe = make_plan(ctx, p, !capturing);
@@ -1341,7 +1388,7 @@ int ssx_debug_samples(ssx_ctx* ctx, const ssx_render_params* p_in, float* xyza, 
 	if ((rc = spectral_refuses(ctx, pp, false))) return rc;
 	SSX_HIP(ctx, hipSetDevice(ctx->device));
 	if ((rc = wait_device_pending(ctx))) return rc;
-	if ((rc = ready_to_launch(ctx, p, false))) return rc;
+	if ((rc = ready_to_launch(ctx, p, false, true))) return rc; // (keep_samples below: the general kernels)
 	LaunchPlan pl = make_plan(ctx, p);
 	if (p->spp > pl.max_spp_per_launch) return fail(ctx, SSX_ERR_ARG, "ssx_debug_samples: too many samples for one launch");
 	if ((rc = ensure_samples(ctx, pl, p->spp))) return rc;
@@ -1681,7 +1728,19 @@ const char* ssx_kernel_name(ssx_ctx* ctx) {
 	uint32_t qw = 0;
 	if (pick_queue(ctx, ctx->path_blob_words, &qw, nullptr) != SSX_OK) return nullptr;
 	const bool narrow = qw == SSX_QUEUE_WORDS_NARROW;
-	return ctx->topology == 3u ? kJitKernelNames[narrow] : path_kernel_of(ctx, narrow).name;
+	// (the _plain twins go by the general kernels' names here: ssx_switches_info says which of the two runs)
+	const uint32_t named = ctx->variant == ssx_jit::kVariantPlain ? (uint32_t)SSX_LIBM_BUILD : ctx->variant;
+	return ctx->topology == 3u ? kJitKernelNames[narrow] : kPathKernels[named][ctx->topology][narrow].name;
+}
+
+int ssx_switches_info(ssx_ctx* ctx) { return (ctx && ctx->have_scene) ? (ctx->variant == ssx_jit::kVariantPlain ? 1 : 0) : -1; }
+int ssx_scene_traits(const ssx_scene_desc* s) {
+	if (!s || s->struct_size != sizeof(ssx_scene_desc) || (s->n_quads && (!s->quads || !s->materials)) || (s->n_lights && !s->lights)) return -1;
+	return (int)scene_traits_of(s);
+}
+int ssx_render_traits(const ssx_render_params* p) {
+	if (!p || p->struct_size != sizeof(ssx_render_params)) return -1;
+	return (int)render_traits_of(p, false);
 }
 
 int ssx_plan_info(ssx_ctx* ctx, float* frames_per_sample, int* fold_in_path_kernel) {

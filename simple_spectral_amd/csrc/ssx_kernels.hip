@@ -386,13 +386,17 @@ __device__ __forceinline__ void texel_lrgb(const Lds& L, uint32_t tex_index, flo
 }
 
 // material.cpp:45-64 + util/color.cpp:167-232: texel -> hero reflectance through the build's uplift
+// PLAIN (render_body): the scene's uplift is "ours", known when the kernel was compiled -- the other three are not part of it
+template <bool PLAIN = false>
 __device__ __forceinline__ Hero texture_sample(const Lds& L, uint32_t tex_index, float st_x, float st_y, float lambda_0) {
 	float r, g, b;
 	texel_lrgb(L, tex_index, st_x, st_y, r, g, b);
 	const SsxBlobHeader& h = L.hdr();
-	if (h.uplift == 0u) { Hero o; o.v[0] = r; o.v[1] = g; o.v[2] = b; o.v[3] = 0.0f; return o; } // RENDER_MODE_RGB: material.cpp:61-63
-	if (h.uplift == 3u) return jh_uplift(L, r, g, b, lambda_0); // RENDER_MODE_SPECTRAL_JH (wave-uniform)
-	if (h.uplift == 2u) return meng_uplift(L, r, g, b, lambda_0); // RENDER_MODE_SPECTRAL_MENG
+	if constexpr (!PLAIN) {
+		if (h.uplift == 0u) { Hero o; o.v[0] = r; o.v[1] = g; o.v[2] = b; o.v[3] = 0.0f; return o; } // RENDER_MODE_RGB: material.cpp:61-63
+		if (h.uplift == 3u) return jh_uplift(L, r, g, b, lambda_0); // RENDER_MODE_SPECTRAL_JH (wave-uniform)
+		if (h.uplift == 2u) return meng_uplift(L, r, g, b, lambda_0); // RENDER_MODE_SPECTRAL_MENG
+	}
 	Hero br, bg, bb;
 	const SsxBlobSpectrum sr = L.spectrum(h.spec_basis_r), sg = L.spectrum(h.spec_basis_g), sb = L.spectrum(h.spec_basis_b);
 	if (h.basis_one_grid) { // wave-uniform: r, g, b tables have the same (low, delta_recip, n)
@@ -408,9 +412,10 @@ __device__ __forceinline__ Hero texture_sample(const Lds& L, uint32_t tex_index,
 	return out;
 }
 
+template <bool PLAIN = false>
 __device__ __forceinline__ Hero material_albedo(const Lds& L, const SsxBlobQuad& Q, float st_x, float st_y, float lambda_0) {
 	const SsxBlobHeader& h = L.hdr();
-	if (h.uplift == 1u && h.basis_one_grid) {
+	if ((PLAIN || h.uplift == 1u) && h.basis_one_grid) {
 		// The default build ("ours" uplift, basis tables on one grid; wave-uniform test).  A wave nearly always holds
 		// lanes of both kinds, so the grid lookup (hero_index) is done once for all of them -- each lane on the
 		// descriptor of ITS table, fetched by address -- and only the gathers differ: one table for a constant
@@ -429,7 +434,7 @@ __device__ __forceinline__ Hero material_albedo(const Lds& L, const SsxBlobQuad&
 		return out;
 	}
 	if (Q.albedo_mode == 0u) return spectrum_hero(L, Q.albedo, lambda_0, h.lambda_step);
-	return texture_sample(L, Q.albedo_tex, st_x, st_y, lambda_0);
+	return texture_sample<PLAIN>(L, Q.albedo_tex, st_x, st_y, lambda_0);
 }
 
 // util/color.hpp:115-139
@@ -823,7 +828,8 @@ __device__ __forceinline__ V3 rand_toward_sphericaltri(Rng& rng, const SphTri& t
 }
 
 // scene.cpp:417-431 -> geometry.cpp:141-145 -> geometry.cpp:103-116
-template <bool GLIBC = false>
+// PLAIN (render_body): no top-level triangle light in the scene -- every light is a quad
+template <bool GLIBC = false, bool PLAIN = false>
 __device__ __forceinline__ void sample_light(const Lds& L, Rng& rng, V3 from, V3& dir, uint32_t& light_quad, float& pdf) {
 	const uint32_t nl = L.hdr().n_lights;
 	// one light (wave-uniform test): uniform_int_distribution(0, 0) still draws once (range 1: product = draw, its low
@@ -834,7 +840,7 @@ __device__ __forceinline__ void sample_light(const Lds& L, Rng& rng, V3 from, V3
 	const SsxBlobQuad& Q = L.quad(light_quad);
 	// PrimQuad::get_rand_toward (geometry.cpp:141-145) picks one of its triangles with a random number and halves the
 	// pdf; a PrimTri light (:103-116) does neither
-	const bool is_tri = Q.is_tri != 0u;
+	const bool is_tri = !PLAIN && Q.is_tri != 0u;
 	bool first = true;
 	if (!is_tri) first = rand_1f(rng) <= 0.5f;
 	const float* p0 = Q.pos[0];
@@ -853,11 +859,12 @@ __device__ __forceinline__ void sample_light(const Lds& L, Rng& rng, V3 from, V3
 // The draws of sample_light without its arithmetic: what a BLACK surface needs of it (path_step).  scene.cpp:423 (light pick, Lemire),
 // geometry.cpp:143 (the quad's triangle pick; a PrimTri light has none), util/random.cpp:103-104 (Arvo's two numbers, drawn before
 // anything is computed).
+template <bool PLAIN = false>
 __device__ __forceinline__ void skip_light_draws(const Lds& L, Rng& rng) {
 	const uint32_t nl = L.hdr().n_lights;
 	uint32_t pick = 0u;
 	if (nl == 1u) (void)rng_next(rng); else pick = rand_choice(rng, nl);
-	if (L.quad(L.light(pick)).is_tri == 0u) (void)rng_next(rng);
+	if (PLAIN || L.quad(L.light(pick)).is_tri == 0u) (void)rng_next(rng);
 	(void)rng_next(rng); (void)rng_next(rng);
 }
 // ... and of rand_coshemi (util/random.cpp:29-49): the angle's draw, the radius' draw, and the rejection test on the same float
@@ -1021,7 +1028,7 @@ __device__ __forceinline__ void camera_dir(const SsxBlobHeader& h, const Args& a
 	double px = q[0] / w, py = q[1] / w, pz = q[2] / w;
 	dx = px - h.cam_pos_d[0]; dy = py - h.cam_pos_d[1]; dz = pz - h.cam_pos_d[2];
 }
-template <typename Args>
+template <bool PLAIN = false, typename Args>
 __device__ __forceinline__ void generate_sample(const SsxBlobHeader& h, const Args& a, uint32_t i, uint32_t j, uint32_t k, float4& ray, uint4& st) {
 	const uint64_t pixel = (uint64_t)j * (uint64_t)a.width + (uint64_t)i;
 	const uint64_t pa = mix64(a.seed + 0x9E3779B97F4A7C15ull * (pixel + 1ull));
@@ -1037,7 +1044,7 @@ __device__ __forceinline__ void generate_sample(const SsxBlobHeader& h, const Ar
 	double inv = 1.0 / __builtin_sqrt((dx * dx + dy * dy) + dz * dz);
 	// :138 exists #ifdef RENDER_MODE_SPECTRAL only: the RGB build draws no wavelength (its "spectra" are
 	// 4-sample tables {r,g,b,0} on the grid 0,1,2,3 and lambda_0 = 0, lambda_step = 1 pick them out exactly)
-	const float lambda_0 = a.rgb_mode ? 0.0f : h.lambda_min + rand_1f(rng) * h.lambda_step;
+	const float lambda_0 = (!PLAIN && a.rgb_mode) ? 0.0f : h.lambda_min + rand_1f(rng) * h.lambda_step;
 	ray = make_float4((float)(dx * inv), (float)(dy * inv), (float)(dz * inv), lambda_0);
 	st = make_uint4((uint32_t)rng.state, (uint32_t)(rng.state >> 32), (uint32_t)rng.inc, (uint32_t)(rng.inc >> 32));
 }
@@ -1102,7 +1109,9 @@ __device__ __forceinline__ void debug_trace_rows(const SsxKernelArgs& a, const u
 // BLACK: the kernel knows the shortcut for black surfaces (below).  It changes no result, so a kernel may leave it out: the kernels of the Cornell
 // topology do -- the scenes that have it rarely hold a black surface, and the test and the merge behind the branch cost their loop 25 instructions
 // per iteration (+0.7 % of the headline's time, profiles/r06/NOTES.md section 8).
-template <bool NARROW, bool BLACK, bool GLIBC = false>
+// PLAIN: the render's switches are the reference's defaults and were known when the kernel was compiled (render_body) -- explicit light sampling, not
+// indirect_only, no mirror in the scene: the tests on them fold away, and with them what only the other side needs (p.dir through the shading, for the mirror).
+template <bool NARROW, bool BLACK, bool GLIBC = false, bool PLAIN = false>
 __device__ __forceinline__ bool path_step(const Lds& L, const ShadowQ& q, const SsxKernelArgs& a, const LogRef& lg, Path& p, bool& pushed, uint32_t& level_word) {
 	const SsxBlobHeader& h = L.hdr();
 	// what the level's entry (or the path's tail word) says about this level: slot of its next-event term << 13 | has an emission term << 26
@@ -1118,8 +1127,9 @@ __device__ __forceinline__ bool path_step(const Lds& L, const ShadowQ& q, const 
 	// table is all zeros (MaterialBase's default) would add exactly +0, so its lookup is skipped.
 	// Without EXPLICIT_LIGHT_SAMPLING (a.no_els; a compile-time switch in the reference,
 	// stdafx.hpp:44) every hit adds its emission unconditionally (:166-175).
-	const bool els = a.no_els == 0u;
-	if ((els ? (p.depth == 0u && !a.indirect_only) : true) && M.is_emissive != 0u) {
+	const bool els = PLAIN || a.no_els == 0u, indirect_only = !PLAIN && a.indirect_only != 0u;
+	const bool lambert = PLAIN || M.kind == 0u; // MaterialBase::Type: Lambertian, else mirror
+	if ((els ? (p.depth == 0u && !indirect_only) : true) && M.is_emissive != 0u) {
 		SSX_STAT(5); // emission lookup
 		Hero em = spectrum_hero(L, M.emission, p.lambda_0, h.lambda_step);
 #pragma unroll
@@ -1138,7 +1148,7 @@ __device__ __forceinline__ bool path_step(const Lds& L, const ShadowQ& q, const 
 	p.orig = hit_pos;
 	if (M.albedo_mode != 0u) { SSX_STAT(6); } else { SSX_STAT(7); } // textured / constant albedo
 	// albedo(lambda) is shared by evaluate_bsdf and interact_bsdf (material.cpp:120-143)
-	Hero alb = material_albedo(L, Q, p.hit_st_x, p.hit_st_y, p.lambda_0);
+	Hero alb = material_albedo<PLAIN>(L, Q, p.hit_st_x, p.hit_st_y, p.lambda_0);
 	float f_lamb[4];
 #pragma unroll
 	for (int k = 0; k < 4; ++k) f_lamb[k] = SSX_DIV_CONST(alb.v[k], SSX_PI_F);
@@ -1154,17 +1164,17 @@ __device__ __forceinline__ bool path_step(const Lds& L, const ShadowQ& q, const 
 	// parity contract): the light sampler's and the hemisphere sampler's draws are made, rejection loops included, their arithmetic --
 	// six binary64 arc cosines, Arvo's sampler, a sine and a cosine: ~55 % of a level's instructions -- is not.  In plane-srgb every path's
 	// second hit is such a wall (wave-uniform there); a wave of the Cornell box never takes the branch.
-	if (BLACK && M.kind == 0u && h.black_ends_path != 0u && f_lamb[0] == 0.0f && f_lamb[1] == 0.0f && f_lamb[2] == 0.0f && f_lamb[3] == 0.0f) {
+	if (BLACK && lambert && h.black_ends_path != 0u && f_lamb[0] == 0.0f && f_lamb[1] == 0.0f && f_lamb[2] == 0.0f && f_lamb[3] == 0.0f) {
 		SSX_STAT(18); // black surface: draws only
-		if (els && (!a.indirect_only || p.depth > 0u)) skip_light_draws(L, p.rng);
+		if (els && (!indirect_only || p.depth > 0u)) skip_light_draws<PLAIN>(L, p.rng);
 		skip_coshemi_draws(p.rng);
 		return false;
 	}
 	// direct lighting (:182-219): sample the light; the shadow ray is parked (see ShadowQ)
-	if (els && (!a.indirect_only || p.depth > 0u)) {
+	if (els && (!indirect_only || p.depth > 0u)) {
 		V3 sdir; uint32_t light; float spdf;
 		SSX_STAT(8); // light sampling
-		sample_light<GLIBC>(L, p.rng, hit_pos, sdir, light, spdf);
+		sample_light<GLIBC, PLAIN>(L, p.rng, hit_pos, sdir, light, spdf);
 		float n_dot_l = dot3(sdir, N);
 		if (n_dot_l > 0.0f) {
 			SSX_STAT(9); // next-event contribution
@@ -1173,7 +1183,7 @@ __device__ __forceinline__ bool path_step(const Lds& L, const ShadowQ& q, const 
 			const double spdf_recip = ssx_exact::div64_rcp_any(spdf); // spdf may be +inf (zero-area light triangle)
 #pragma unroll
 			for (int k = 0; k < 4; ++k) {
-				float fs = (M.kind == 0u) ? f_lamb[k] : 0.0f; // Mirror::evaluate_bsdf -> 0
+				float fs = lambert ? f_lamb[k] : 0.0f; // Mirror::evaluate_bsdf -> 0
 				c[k] = ssx_exact::div64_by((emitted.v[k] * n_dot_l) * fs, spdf_recip);
 			}
 			// A contribution of four zeros (zero-area light triangle: pdf = +inf, src/geometry.cpp:115; black or mirror
@@ -1205,7 +1215,7 @@ __device__ __forceinline__ bool path_step(const Lds& L, const ShadowQ& q, const 
 
 	// indirect lighting (:222-250)
 	V3 w_i; float pdf_w_i; float f_s[4];
-	if (M.kind == 0u) {
+	if (lambert) {
 		SSX_STAT(11); // BSDF sample
 		w_i = rand_coshemi<GLIBC>(p.rng, pdf_w_i);
 		w_i = get_rotated_to(w_i, N);
@@ -1336,7 +1346,8 @@ __device__ __forceinline__ float4 nee_term(const SsxKernelArgs& a, uint32_t i, b
 // (its first sample within the cohort; way s is sample rc0 + 64 s); acc: the lane's pixel sums (unit_fold)
 // FLUX (the _flux kernels: spectral output, include/ssx.h ssx_set_spectral_bins): every sample's Hero flux -- what flux_to_xyz is handed, i.e. behind
 // the no_flat_field multiply -- also goes to flux[r], the sample's own record of a fourth per-sample array; parked samples included.
-template <uint32_t WAYS, bool NARROW, bool FLUX = false>
+// PLAIN (render_body): XYZ mode, flat-field correction on, no keep_samples -- known when the kernel was compiled, not read from the arguments.
+template <uint32_t WAYS, bool NARROW, bool FLUX = false, bool PLAIN = false>
 __device__ __forceinline__ void resolve_records(const Lds& L, const SsxKernelArgs& a, uint32_t r0, uint32_t stride, uint32_t count, uint32_t fs_base, uint32_t nee_base, uint32_t rc0, double acc[4], bool stage) {
 	float rad[WAYS][4];
 	uint32_t depth[WAYS]; // hit_anything << 4 | number of continued levels
@@ -1401,7 +1412,7 @@ __device__ __forceinline__ void resolve_records(const Lds& L, const SsxKernelArg
 			}
 	}
 	const __attribute__((address_space(4))) SsxKernelArgs& c = cold_args(); // (the render's switches: read where they are needed, once per pass)
-	const bool rgb_mode = c.rgb_mode != 0u, keep_samples = c.keep_samples != 0u, no_flat_field = c.no_flat_field != 0u;
+	const bool rgb_mode = !PLAIN && c.rgb_mode != 0u, keep_samples = !PLAIN && c.keep_samples != 0u, no_flat_field = !PLAIN && c.no_flat_field != 0u;
 #pragma unroll
 	for (uint32_t s = 0; s < WAYS; ++s)
 		if (s < count) {
@@ -1651,6 +1662,7 @@ __device__ __forceinline__ void sums_acquire(uint32_t* cnt) {
 #endif
 // The unit (slot, grp) has the turn and its samples are parked, and nobody else will add them: add them, give the turn to the unit
 // behind, and go on while that one is parked too.
+template <bool PLAIN = false>
 __device__ __forceinline__ void sums_chain(uint32_t slot, uint32_t grp, uint32_t lane, uint32_t* cnt) {
 	const __attribute__((address_space(4))) SsxKernelArgs& a = cold_args();
 	uint32_t tx, ty;
@@ -1664,7 +1676,7 @@ __device__ __forceinline__ void sums_chain(uint32_t slot, uint32_t grp, uint32_t
 	for (;;) {
 		const uint32_t n = min(a.group_spp, (a.k1 - a.k0) - grp * a.group_spp);
 		if (has_px) {
-			for (uint32_t kq = 0; kq < n; ++kq) add_staged_sample(a.rgb_mode != 0u, acc, a.ray + (rec_at + kq * 64u + lane));
+			for (uint32_t kq = 0; kq < n; ++kq) add_staged_sample(!PLAIN && a.rgb_mode != 0u, acc, a.ray + (rec_at + kq * 64u + lane));
 			st_agent(px, acc[0]); st_agent(px + 64, acc[1]); st_agent(px + 128, acc[2]); st_agent(px + 192, acc[3]);
 		}
 		if (++grp >= a.n_groups) return; // that was the tile's last unit of the launch
@@ -1678,7 +1690,7 @@ __device__ __forceinline__ void sums_chain(uint32_t slot, uint32_t grp, uint32_t
 		if (lane == 0u) atomicAdd(a.unit_counter + 3, 1u); // statistics (ssx_sums_info): parked units added by the wave in front of them
 	}
 }
-template <bool NARROW, bool FLUX = false>
+template <bool NARROW, bool FLUX = false, bool PLAIN = false>
 __device__ __forceinline__ void unit_fold(const Lds& L, const SsxKernelArgs& a, const WorkUnit& u, uint32_t wave_slot, uint32_t tag, uint32_t* cnt) {
 	// see "Memory-ordering contract" above: the acquire side of the wave's hand-over; then wait for this wave's stores and
 	// drop the CU's L1 lines
@@ -1701,7 +1713,7 @@ __device__ __forceinline__ void unit_fold(const Lds& L, const SsxKernelArgs& a, 
 	if (has_px)
 		for (uint32_t kq = 0, n_kq = u.n_kq(), rec_base = u.rec_base(a); kq < n_kq; kq += SSX_COHORT_KS) { // one cohort per pass
 			const uint32_t log_rec = log_region(a, wave_slot, tag, kq / SSX_COHORT_KS);
-			resolve_records<SSX_COHORT_KS, NARROW, FLUX>(L, a, rec_base + kq * 64u + lane, 64u, min(SSX_COHORT_KS, n_kq - kq), log_rec * SSX_MAX_FRAMES, log_rec * SSX_MAX_LEVELS, lane, acc, !mine);
+			resolve_records<SSX_COHORT_KS, NARROW, FLUX, PLAIN>(L, a, rec_base + kq * 64u + lane, 64u, min(SSX_COHORT_KS, n_kq - kq), log_rec * SSX_MAX_FRAMES, log_rec * SSX_MAX_LEVELS, lane, acc, !mine);
 		}
 	if (mine) {
 		if (has_px) { st_agent(px, acc[0]); st_agent(px + 64, acc[1]); st_agent(px + 128, acc[2]); st_agent(px + 192, acc[3]); }
@@ -1714,7 +1726,7 @@ __device__ __forceinline__ void unit_fold(const Lds& L, const SsxKernelArgs& a, 
 		sums_acquire(cnt);
 		if (was != SSX_UNIT_PARKED) return;
 		if (lane == 0u) atomicAdd(c.unit_counter + 3, 1u); // statistics (ssx_sums_info): parked units added by the wave in front of them
-		sums_chain(u.slot, u.grp + 1u, lane, cnt);
+		sums_chain<PLAIN>(u.slot, u.grp + 1u, lane, cnt);
 	} else {
 		// the samples are parked: say so -- unless the turn has come in the meantime: then nobody else will add them
 		sums_release(cnt);
@@ -1727,14 +1739,19 @@ __device__ __forceinline__ void unit_fold(const Lds& L, const SsxKernelArgs& a, 
 		}
 		was = (uint32_t)__builtin_amdgcn_readfirstlane((int)was);
 		sums_acquire(cnt);
-		if (was == SSX_UNIT_TURN) sums_chain(u.slot, u.grp, lane, cnt);
+		if (was == SSX_UNIT_TURN) sums_chain<PLAIN>(u.slot, u.grp, lane, cnt);
 	}
 }
 
 // CALIB: the calibration render of ssx_upload_scene (ssx_calibrate_kernel) also counts the rays that leave the scene
 // GLIBC: libm = glibc-2.35 (the _glibc kernels): glibc's transcendentals instead of ssx_fmath.h's
 // FLUX: the _flux kernels (spectral output): the fold also stores every sample's hero flux (resolve_records)
-template <int TOPO, bool NARROW, bool CALIB = false, bool GLIBC = false, bool FLUX = false>
+// PLAIN: the _plain kernels.  The reference fixes its render switches when it is compiled (stdafx.hpp); here each is a run-time variant, tested or kept
+// live in every iteration of every render.  A _plain kernel is compiled for the reference's default build on a scene of Lambertian surfaces and quad
+// lights: explicit light sampling on, not indirect_only, no mirror material, no top-level triangle light, uplift "ours", XYZ mode, flat-field correction
+// on, no keep_samples.  The host launches it only for a render and a scene that are all of that (csrc/ssx_api.hip: render_is_plain); what remains is the
+// same expressions on the same operands in the same order.
+template <int TOPO, bool NARROW, bool CALIB = false, bool GLIBC = false, bool FLUX = false, bool PLAIN = false>
 __device__ __forceinline__ void render_body(const SsxKernelArgs& a) {
 	constexpr bool FUSE_GEN = TOPO == 2; // the kernels that can make their samples themselves (SsxKernelArgs::fuse_gen): the plane topology's, whose scenes trace camera rays in the path loop
 	uint32_t* const lds_words = stage_lds<GLIBC>(a);
@@ -1810,8 +1827,8 @@ __device__ __forceinline__ void render_body(const SsxKernelArgs& a) {
 					// (the arguments it needs -- seed, image size, first sample -- from the kernarg segment where they are used: held in SGPRs
 					// across the loop they cost the shading code 13 spilled SGPRs and, through those, 9 spilled VGPRs)
 					const __attribute__((address_space(4))) SsxKernelArgs& c = cold_args();
-					generate_sample(L.hdr(), c, (cur.txy & 0xFFFFu) * 8u + (in_tile & 7u), (cur.txy >> 16) * 8u + (in_tile >> 3), c.k0 + cur.grp * c.group_spp + kq, ray, st);
-					if (c.no_flat_field) c.ray[p.rec_index] = ray; // (the fold of that mode reads the camera ray's direction back)
+					generate_sample<PLAIN>(L.hdr(), c, (cur.txy & 0xFFFFu) * 8u + (in_tile & 7u), (cur.txy >> 16) * 8u + (in_tile >> 3), c.k0 + cur.grp * c.group_spp + kq, ray, st);
+					if (!PLAIN && c.no_flat_field) c.ray[p.rec_index] = ray; // (the fold of that mode reads the camera ray's direction back)
 				} else {
 					ray = a.ray[p.rec_index];
 					st = a.st[p.rec_index];
@@ -1850,7 +1867,7 @@ __device__ __forceinline__ void render_body(const SsxKernelArgs& a) {
 			SSX_TIME(tm, 5); // (shadow flush: queue read, result store; its trace is timed inside)
 		}
 		if (fold_old) {
-			if (a.fuse_resolve) unit_fold<NARROW, FLUX>(L, a, old, wave_slot, old_tag, log_cnt);
+			if (a.fuse_resolve) unit_fold<NARROW, FLUX, PLAIN>(L, a, old, wave_slot, old_tag, log_cnt);
 			old_pending = false;
 			SSX_TIME(tm, 6); // (fold)
 		}
@@ -1910,7 +1927,7 @@ __device__ __forceinline__ void render_body(const SsxKernelArgs& a) {
 				LogRef lg;
 				lg.cnt = log_cnt; lg.wave_base = wave_slot * 2u * a.unit_cohorts; lg.tagw = p_tag;
 				uint32_t level_word;
-				if (!path_step<NARROW, TOPO != 1, GLIBC>(L, sq, a, lg, p, pushed, level_word)) end_path(level_word, 1u);
+				if (!path_step<NARROW, TOPO != 1, GLIBC, PLAIN>(L, sq, a, lg, p, pushed, level_word)) end_path(level_word, 1u);
 			}
 			sq.count += (uint32_t)__popcll(__ballot(pushed));
 		}
@@ -1962,38 +1979,50 @@ __device__ __forceinline__ void render_body(const SsxKernelArgs& a) {
 #ifndef SSX_JIT_FLUX
 #define SSX_JIT_FLUX 0
 #endif
-#define SSX_PATH_KERNEL(name, topo, narrow, glibc, flux) \
-	extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SSX_WAVES_PER_EU))) name(SsxKernelArgs a) { render_body<topo, narrow, false, glibc, flux>(a); }
-#ifdef SSX_JIT_BUILD // the run-time compilation holds the two path kernels of the uploaded scene's topology, nothing else; the libm mode is
-// a compile flag of it, and so part of its cache key (csrc/ssx_jit.h)
+// plain: the kernel with the reference's default render switches compiled in (render_body's PLAIN), named <default name>_plain
+#ifndef SSX_JIT_PLAIN
+#define SSX_JIT_PLAIN 0
+#endif
+#define SSX_PATH_KERNEL(name, topo, narrow, glibc, flux, plain) \
+	extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SSX_WAVES_PER_EU))) name(SsxKernelArgs a) { render_body<topo, narrow, false, glibc, flux, plain>(a); }
+#ifdef SSX_JIT_BUILD // the run-time compilation holds the two path kernels of the uploaded scene's topology, nothing else; the libm mode and the compiled-in
+// switches are compile flags of it, and so part of its cache key (csrc/ssx_jit.h)
 #ifdef SSX_JIT_DEBUG // ... except in the debug-only variant of the program (csrc/ssx_jit.h kVariantDebug): SSX_DBG_TRACE_TOPO's kernel for the pattern, and no path kernel
 extern "C" __global__ void __launch_bounds__(256) ssx_debug_trace_jit(SsxKernelArgs a, const uint32_t* in, uint32_t in_words, uint32_t* out, uint32_t out_words, uint32_t n) {
 	debug_trace_rows<3>(a, in, in_words, out, out_words, n);
 }
 #else
-SSX_PATH_KERNEL(ssx_render_kernel_jit, 3, false, SSX_JIT_GLIBC, SSX_JIT_FLUX)
-SSX_PATH_KERNEL(ssx_render_kernel_jit_nq, 3, true, SSX_JIT_GLIBC, SSX_JIT_FLUX)
+SSX_PATH_KERNEL(ssx_render_kernel_jit, 3, false, SSX_JIT_GLIBC, SSX_JIT_FLUX, SSX_JIT_PLAIN)
+SSX_PATH_KERNEL(ssx_render_kernel_jit_nq, 3, true, SSX_JIT_GLIBC, SSX_JIT_FLUX, SSX_JIT_PLAIN)
 #endif
 #else
-SSX_PATH_KERNEL(ssx_render_kernel, 0, false, false, false)
-SSX_PATH_KERNEL(ssx_render_kernel_cornell, 1, false, false, false)
-#ifndef SSX_PROBE_BUILD // tools/kernel_resources.py --probe: the two kernels above only (register pressure experiments)
-SSX_PATH_KERNEL(ssx_render_kernel_plane, 2, false, false, false)
-SSX_PATH_KERNEL(ssx_render_kernel_nq, 0, true, false, false)
-SSX_PATH_KERNEL(ssx_render_kernel_cornell_nq, 1, true, false, false)
-SSX_PATH_KERNEL(ssx_render_kernel_plane_nq, 2, true, false, false)
-SSX_PATH_KERNEL(ssx_render_kernel_glibc, 0, false, true, false)
-SSX_PATH_KERNEL(ssx_render_kernel_cornell_glibc, 1, false, true, false)
-SSX_PATH_KERNEL(ssx_render_kernel_plane_glibc, 2, false, true, false)
-SSX_PATH_KERNEL(ssx_render_kernel_nq_glibc, 0, true, true, false)
-SSX_PATH_KERNEL(ssx_render_kernel_cornell_nq_glibc, 1, true, true, false)
-SSX_PATH_KERNEL(ssx_render_kernel_plane_nq_glibc, 2, true, true, false)
-SSX_PATH_KERNEL(ssx_render_kernel_flux, 0, false, false, true)
-SSX_PATH_KERNEL(ssx_render_kernel_cornell_flux, 1, false, false, true)
-SSX_PATH_KERNEL(ssx_render_kernel_plane_flux, 2, false, false, true)
-SSX_PATH_KERNEL(ssx_render_kernel_nq_flux, 0, true, false, true)
-SSX_PATH_KERNEL(ssx_render_kernel_cornell_nq_flux, 1, true, false, true)
-SSX_PATH_KERNEL(ssx_render_kernel_plane_nq_flux, 2, true, false, true)
+SSX_PATH_KERNEL(ssx_render_kernel, 0, false, false, false, false)
+SSX_PATH_KERNEL(ssx_render_kernel_cornell, 1, false, false, false, false)
+SSX_PATH_KERNEL(ssx_render_kernel_plain, 0, false, false, false, true)
+SSX_PATH_KERNEL(ssx_render_kernel_cornell_plain, 1, false, false, false, true)
+#if !defined(SSX_PROBE_BUILD) || defined(SSX_PROBE_PLANE) // tools/kernel_resources.py --probe: the four kernels above only (register pressure experiments); -DSSX_PROBE_PLANE: the plane topology's pair as well
+SSX_PATH_KERNEL(ssx_render_kernel_plane, 2, false, false, false, false)
+SSX_PATH_KERNEL(ssx_render_kernel_plane_plain, 2, false, false, false, true)
+#endif
+#ifndef SSX_PROBE_BUILD
+SSX_PATH_KERNEL(ssx_render_kernel_nq, 0, true, false, false, false)
+SSX_PATH_KERNEL(ssx_render_kernel_cornell_nq, 1, true, false, false, false)
+SSX_PATH_KERNEL(ssx_render_kernel_plane_nq, 2, true, false, false, false)
+SSX_PATH_KERNEL(ssx_render_kernel_nq_plain, 0, true, false, false, true)
+SSX_PATH_KERNEL(ssx_render_kernel_cornell_nq_plain, 1, true, false, false, true)
+SSX_PATH_KERNEL(ssx_render_kernel_plane_nq_plain, 2, true, false, false, true)
+SSX_PATH_KERNEL(ssx_render_kernel_glibc, 0, false, true, false, false)
+SSX_PATH_KERNEL(ssx_render_kernel_cornell_glibc, 1, false, true, false, false)
+SSX_PATH_KERNEL(ssx_render_kernel_plane_glibc, 2, false, true, false, false)
+SSX_PATH_KERNEL(ssx_render_kernel_nq_glibc, 0, true, true, false, false)
+SSX_PATH_KERNEL(ssx_render_kernel_cornell_nq_glibc, 1, true, true, false, false)
+SSX_PATH_KERNEL(ssx_render_kernel_plane_nq_glibc, 2, true, true, false, false)
+SSX_PATH_KERNEL(ssx_render_kernel_flux, 0, false, false, true, false)
+SSX_PATH_KERNEL(ssx_render_kernel_cornell_flux, 1, false, false, true, false)
+SSX_PATH_KERNEL(ssx_render_kernel_plane_flux, 2, false, false, true, false)
+SSX_PATH_KERNEL(ssx_render_kernel_nq_flux, 0, true, false, true, false)
+SSX_PATH_KERNEL(ssx_render_kernel_cornell_nq_flux, 1, true, false, true, false)
+SSX_PATH_KERNEL(ssx_render_kernel_plane_nq_flux, 2, true, false, true, false)
 #endif
 // The generic kernel under another name for the calibration render of ssx_upload_scene (64x64x4 samples), so that
 // kernel traces and statistics of ssx_render_kernel* contain real launches only.  It stays on ssx_fmath.h's functions in glibc mode too:

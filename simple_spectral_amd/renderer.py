@@ -1493,7 +1493,10 @@ class Renderer:
         return {"frames_per_sample": round(f.value, 3), "fold": "path kernel", "pass1": variant,
                 "rays_left_per_sample": round(left.value, 3), "camera_rays": "pre-traced (generate kernel)" if pre.value else "path loop",
                 "samples_made_in": "path kernel (refill)" if fused else "generate kernel",
-                "kernel": name.decode() if name else None}
+                "kernel": name.decode() if name else None,
+                # the render switches (explicit light sampling, indirect_only, mirror / triangle-light scene, uplift, RGB mode, flat field): compiled into
+                # the kernel the current (or last) render ran -- its "_plain" twin, named as "kernel" above -- or tested at run time (ssx_switches_info)
+                "switches": "compiled in" if hasattr(self._lib, "ssx_switches_info") and self._lib.ssx_switches_info(self._ctx) == 1 else "run time"}
 
     def scratch_info(self):
         """Device scratch held: bytes of per-sample arrays (largest launch so far) and of the persistent waves' level logs."""

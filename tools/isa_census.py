@@ -124,7 +124,7 @@ def source_ranges():
     r["fold_levels"] = (a, block_end(a))
     a = find("if ((els ? (p.depth == 0u")
     r["emission"] = (a, block_end(a))
-    a = find("if (els && (!a.indirect_only || p.depth > 0u)) {")
+    a = find("if (els && (!indirect_only || p.depth > 0u)) {")
     r["nee"] = (a, block_end(a))
     a = find("if (n_dot_l > 0.0f) {", r["nee"][0])
     r["nee_contrib"] = (a, block_end(a))
@@ -153,7 +153,7 @@ def source_ranges():
     one("flux_to_xyz", "bar[1] = spectrum_hero(L, h.spec_ybar")
     one("flux_to_xyz", "bar[2] = spectrum_hero(L, h.spec_zbar")
     one("material_albedo", "if (Q.albedo_mode == 0u) return spectrum_hero(L, Q.albedo")
-    one("material_albedo", "return texture_sample(L, Q.albedo_tex")
+    one("material_albedo", "return texture_sample<PLAIN>(L, Q.albedo_tex")
     a = find("w_i = reflect3(mk(-p.dir.x")
     cold.append(("path_step", a, a + 4))                                                  # MaterialMirror
     one("sample_light", "if (nl == 1u) (void)rng_next(rng); else pick = rand_choice(rng, nl);")  # priced at its one-light cost below (see RNG_LINE)

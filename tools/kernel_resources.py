@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Registers, spills, scratch and static LDS of every kernel in csrc/ssx_api.hip (hipcc -S, no GPU needed).
     python tools/kernel_resources.py [--probe] [-D MACRO ...]      --probe: csrc/ssx_kernels.hip alone with -DSSX_PROBE_BUILD (generic and
-    Cornell path kernels only: a third of the compile time, for register-pressure experiments)"""
+    Cornell path kernels and their _plain twins only: a fraction of the compile time, for register-pressure experiments; -D SSX_PROBE_PLANE adds the
+    plane topology's pair)"""
 import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
