@@ -1114,6 +1114,68 @@ int ssx_spectral_develop_sensor(ssx_ctx* ctx, const ssx_denoise_params* denoise 
                                 const ssx_optics_params* optics /* or NULL */, const ssx_sensor_params* sensor, float* out /* [H][W][3] or NULL */,
                                 float* raw_out /* [H][W] or NULL */, float* dn_out /* [H][W] or NULL */);
 
+/* ---- Glare: per-bin convolution by FFT ------------------------------------------------------------
+ * Veiling glare, diffraction rings and spikes: wide, non-separable, wavelength-dependent point spread functions that neither BLUR (separable, radius 12) nor
+ * DEFOCUS (a gather, (2 R + 1)^2 taps) can reach.  Per wavelength bin the image is padded, transformed, multiplied by the psf's transform, transformed back
+ * and cropped.  The conventions are those of "Developing through a lens": binary32 IEEE in the order written, every product rounded before the add, no
+ * contraction, no reassociation.  Input q[H][W][B], row 0 at the bottom, B in {4, 8, ..., 64}.  The library takes any tables; the host policy that makes an
+ * aperture's is ssh_glare_aperture (include/ssx_host.h).
+ *
+ * TWIDDLES are the caller's (ssh_glare_twiddles): no sine or cosine of the device or of a libm enters the bits.
+ *
+ * FFT(x[0..P), T, inverse) on complex binary32 values is defined by its butterfly graph.  n = log2 P.
+ *   y[k] = x[bitrev_n(k)]
+ *   for s = 1..n, h = 2^(s-1), step = P / (2 h), every block base g = 0, 2h, 4h, ... and every k in 0..h-1:
+ *     w = T[k * step]                           (inverse: w.im = -w.im)
+ *     a = y[g+k];  b = y[g+k+h]
+ *     t.re = (w.re * b.re) - (w.im * b.im)
+ *     t.im = (w.re * b.im) + (w.im * b.re)
+ *     y[g+k]   = (a.re + t.re, a.im + t.im)
+ *     y[g+k+h] = (a.re - t.re, a.im - t.im)
+ * The product with T[0] is performed like any other: the table need not hold (1, 0).  Any schedule that executes this graph gives these bits.
+ *
+ * GLARE, per bin b with on[b] != 0 (a bin with on[b] == 0 is copied bit for bit and its psf is not read):
+ *   PAD       X[jj][ii], jj < py, ii < px.  i' = ii < W + R ? ii : ii - px, j' likewise with H and py.  Where -R <= i' < W + R and -R <= j' < H + R:
+ *             X = (q[clamp(j', 0, H-1)][clamp(i', 0, W-1)][b], 0), elsewhere (0, 0).  The border is replicated, so the frame does not darken; px >= W + 2 R, so
+ *             the two aprons never meet.
+ *   KERNEL    Kp = 0, then Kp[dy mod py][dx mod px] = (psf_b[dy+R][dx+R], 0) for |dy|, |dx| <= R.
+ *   FORWARD   of both: every row with twiddle_x, then every column with twiddle_y.
+ *   MULTIPLY  Y = X (x) Kf, the complex product written as t above.
+ *   INVERSE   every column, then every row, with the conjugated twiddles.
+ *   CROP      out[j][i][b] = Y[j][i].re * inv, inv = 1 / (px py), which is exact.  The imaginary part is dropped.
+ * That is out(j, i) = sum psf(dy, dx) q(j - dy, i - dx): a convolution, not a correlation.
+ * The result is not clamped: where the true value is ~0 it may come out slightly negative.  A non-finite value anywhere in a bin makes that whole bin's output
+ * non-finite; other bins are not touched.  With every on[b] == 0 nothing is allocated or launched and out is a copy.
+ * Scratch on the device: 16 px py bytes per bin in flight; bins are processed in chunks of whole groups of four that fit 256 MiB, at least one group
+ * (64 px py bytes: 1 GiB at the largest plan, at most 256 MiB wherever px py <= 2^22); beside these planes the context keeps the packed twiddles
+ * (16 (px + py) bytes), the psf (4 B (2R+1)^2 bytes: 67 MB at B = 64, R = 256), out (4 B W H bytes) and, for ssx_glare_images, q (4 B W H bytes), all of it
+ * from the first glare until ssx_destroy. */
+#define SSX_GLARE_MAX_RADIUS 256u
+#define SSX_GLARE_MAX_EXTENT 4096u
+typedef struct ssx_glare_params {
+	uint32_t struct_size;
+	uint32_t radius;           /* R, 0..SSX_GLARE_MAX_RADIUS; K = 2R+1 */
+	uint32_t px, py;           /* padded extents: the smallest powers of two >= max(2, W+2R) and max(2, H+2R); <= SSX_GLARE_MAX_EXTENT (ssh_glare_plan) */
+	const uint8_t* on;         /* [B]  0: the bin is copied bit for bit, its psf is not read */
+	const float* psf;          /* [B][K][K]  psf_b[dy+R][dx+R]; finite */
+	const float* twiddle_x;    /* [px/2][2]  (re, im) of the forward twiddle T[m]; finite */
+	const float* twiddle_y;    /* [py/2][2] */
+} ssx_glare_params;
+
+/* GLARE as a pure function of its arguments (needs no scene): q [height][width][bins] -> out [height][width][bins].  SSX_ERR_ARG, with ssx_last_error naming the
+ * field: bins not a multiple of 4 in 4..64, a NULL pointer (q, out, glare, on, psf, twiddle_x, twiddle_y), an empty or too large image, a wrong struct_size, a
+ * radius above SSX_GLARE_MAX_RADIUS, px or py not the defined value or above SSX_GLARE_MAX_EXTENT, a psf entry of an `on` bin or (with some bin on) a twiddle
+ * entry that is not finite.  SSX_ERR_STATE: a render runs. */
+int ssx_glare_images(ssx_ctx* ctx, uint32_t width, uint32_t height, uint32_t bins, const float* q /* [H][W][B] */, const ssx_glare_params* glare, float* out /* [H][W][B] */);
+/* ssx_spectral_develop_lens with GLARE between the lens and the develop kernels: the source and the stages of ssx_spectral_develop_lens (raw or denoised;
+ * DEFOCUS; WARP and BLUR; either may be NULL), then GLARE, then the develop kernels; nothing leaves the device in between.  glare == NULL gives the bits of
+ * ssx_spectral_develop_lens.  out, weights and bins_out as there; bins_out holds the bins behind the glare.  It reads only.  Glare in front of a sensor goes
+ * by way of bins_out and ssx_sensor_images / ssx_demosaic_images.  SSX_ERR_STATE with ssx_spectral_develop_lens's reasons, tile_stride != 1 among them;
+ * SSX_ERR_ARG: what ssx_spectral_develop_lens and ssx_glare_images refuse. */
+int ssx_spectral_develop_glare(ssx_ctx* ctx, const ssx_denoise_params* denoise /* or NULL */, const ssx_defocus_params* defocus /* or NULL */,
+                               const ssx_optics_params* optics /* or NULL */, const ssx_glare_params* glare /* or NULL */, const float* weights /* [C][B] */,
+                               uint32_t channels, float* out /* [H][W][C] or NULL */, float* bins_out /* [H][W][B] or NULL */);
+
 /* ---- Diagnostics for the parity tests (not part of the reference's interface) ---------------------
  * ssx_debug_eval runs one building block of the path kernel -- the same device function the kernel
  * inlines -- on n items, one per lane: `in` holds in_words 32-bit words per item, `out` receives

@@ -181,6 +181,32 @@ int ssh_defocus_thin_lens(float vfov_deg, uint32_t height, uint32_t bins, float 
                           double lambda_ref, float* gain_out, float* focus_out);
 /* *vfov_deg = the vertical field of view of the scene's camera in degrees (what ssh_defocus_thin_lens takes; the scene description carries only the matrix). */
 int ssh_scene_vfov(const ssh_scene* scene, float* vfov_deg);
+/* ---- Glare for ssx_glare_images / ssx_spectral_develop_glare (ssx.h "Glare: per-bin convolution by FFT").  All of it binary64, rounded to binary32 once at
+ * the end.  The library itself takes any psf and any twiddles. */
+/* *px, *py = the padded extents of ssx_glare_params: the smallest powers of two >= max(2, width + 2 radius) and max(2, height + 2 radius).  SSX_ERR_ARG: NULL, an
+ * empty image, a radius above SSX_GLARE_MAX_RADIUS, an extent above SSX_GLARE_MAX_EXTENT. */
+int ssh_glare_plan(uint32_t width, uint32_t height, uint32_t radius, uint32_t* px, uint32_t* py);
+/* out [P / 2][2]: T[m] = ((float)cos(x), (float)-sin(x)) with x = (2.0 * 3.14159265358979323846 * m) / P in binary64 and libm's cos and sin; T[0] = (1, 0) and
+ * T[P / 4] = (0, -1) exactly.  SSX_ERR_ARG: NULL, a P that is no power of two in 2..SSX_GLARE_MAX_EXTENT. */
+int ssh_glare_twiddles(uint32_t P, float* out);
+/* psf_out [bins][2 radius + 1][2 radius + 1] and on_out [bins] of ssx_glare_params for an iris of `blades` straight blades (fewer than 3: a disc), for bins of a
+ * render with this lambda_min and lambda_step.  THE MODEL: Fraunhofer diffraction of a uniformly lit aperture, whose pattern grows linearly with the wavelength.
+ *   - The aperture is a regular polygon of circumradius SSH_GLARE_PUPIL cells about the centre of a SSH_GLARE_GRID^2 grid, first vertex at `rotation` radians; a
+ *     cell's value is the fraction of its SSH_GLARE_SUBSAMPLES^2 regularly placed samples that lie inside (anti-aliased edges on a fixed grid).
+ *   - I = |DFT|^2 of that grid, by a binary64 radix-2 FFT of this library's own (libm's cos and sin).
+ *   - A disc of radius a on a grid of N has its first dark ring at SSH_GLARE_AIRY_ZERO * N / (2 a) frequency samples; the pattern is scaled so that this ring lies
+ *     ring_px pixels out at lambda_ref: bin b, centre lc_b = (double)lambda_min + (b + 0.5) * ((double)lambda_step / (bins / 4)), samples I bilinearly at
+ *     (dy, dx) * kappa_b, kappa_b = (ring0 / ring_px) * (lambda_ref / lc_b); beyond the grid's Nyquist range (about SSH_GLARE_PUPIL / 1.22 rings) the pattern is 0.
+ *   - Each bin's pattern is divided by its sum over the K x K window (ascending dy, dx from 0.0), and psf_b = (1 - strength) * delta + strength * pattern:
+ *     `strength` is the share of the light that leaves the geometric image.
+ * strength == 0: on_out[b] = 0 for every bin and psf_b = delta.  SSX_ERR_ARG: NULL, bins not a multiple of 4 in 4..64, a radius above SSX_GLARE_MAX_RADIUS, more
+ * than 64 blades, a strength outside 0..1, a ring_px, lambda_ref, lambda_min or lambda_step not finite and positive, a rotation not finite. */
+#define SSH_GLARE_GRID 1024u
+#define SSH_GLARE_PUPIL 128.0
+#define SSH_GLARE_SUBSAMPLES 4u
+#define SSH_GLARE_AIRY_ZERO 1.2196698912665045
+int ssh_glare_aperture(uint32_t bins, float lambda_min, float lambda_step, double lambda_ref, int blades, double rotation, double ring_px, double strength,
+                       uint32_t radius, float* psf_out, uint8_t* on_out);
 /* ---- A sensor for ssx_sensor_images / ssx_demosaic_images / ssx_spectral_develop_sensor (ssx.h "Developing onto a sensor").  All of it binary64, rounded to
  * binary32 once at the end. */
 enum { SSH_DEMOSAIC_BILINEAR = 0, SSH_DEMOSAIC_MHC = 1 };

@@ -117,6 +117,15 @@ class SsxSensorParams(C.Structure):
 SSH_DEMOSAIC_BILINEAR, SSH_DEMOSAIC_MHC = 0, 1  # include/ssx_host.h
 
 
+class SsxGlareParams(C.Structure):
+    """ssx_glare_params: the radius, the padded extents, and the per-bin switches, point spread functions and the twiddle tables of a glare."""
+    _fields_ = [("struct_size", C.c_uint32), ("radius", C.c_uint32), ("px", C.c_uint32), ("py", C.c_uint32),
+                ("on", C.c_void_p), ("psf", C.c_void_p), ("twiddle_x", C.c_void_p), ("twiddle_y", C.c_void_p)]
+
+
+SSX_GLARE_MAX_RADIUS, SSX_GLARE_MAX_EXTENT = 256, 4096  # include/ssx.h
+
+
 class SshSpectrum(C.Structure):
     """ssh_spectrum_t: n uniform samples over [low, high] (include/ssx_host.h)."""
     _fields_ = [("samples", C.POINTER(C.c_float)), ("n", C.c_uint32), ("low", C.c_float), ("high", C.c_float)]
@@ -157,6 +166,7 @@ HIP_SYMBOLS = ["ssx_create", "ssx_destroy", "ssx_upload_scene", "ssx_render_star
                "ssx_optics_images", "ssx_spectral_develop_optics",
                "ssx_defocus_images", "ssx_spectral_develop_lens",
                "ssx_sensor_images", "ssx_demosaic_images", "ssx_spectral_develop_sensor",
+               "ssx_glare_images", "ssx_spectral_develop_glare",
                "ssx_debug_tile_mask", "ssx_debug_spectral_accumulate", "ssx_debug_fold", "ssx_debug_step",
                "ssx_debug_generate", "ssx_generate_info",
                "ssx_scene_traits", "ssx_render_traits", "ssx_switches_info"]
@@ -191,7 +201,8 @@ HOST_SYMBOLS = ["ssh_scene_create", "ssh_scene_create_ex", "ssh_scene_destroy", 
                 "ssh_compare_derive", "ssh_compare_save_csv",
                 "ssh_delta_e_derive", "ssh_delta_e_save_csv", "ssh_develop_white",
                 "ssh_optics_lens", "ssh_defocus_thin_lens", "ssh_scene_vfov",
-                "ssh_sensor_bayer", "ssh_sensor_exposure", "ssh_sensor_ccm", "ssh_sensor_standin_curve"]
+                "ssh_sensor_bayer", "ssh_sensor_exposure", "ssh_sensor_ccm", "ssh_sensor_standin_curve",
+                "ssh_glare_plan", "ssh_glare_twiddles", "ssh_glare_aperture"]
 
 _hip = None
 _host = None
@@ -252,6 +263,9 @@ def host_lib():
         lib.ssh_sensor_exposure.argtypes = [C.c_double, C.c_double, C.c_uint32, C.c_double, C.c_double, vp]
         lib.ssh_sensor_ccm.argtypes = [vp, vp, C.c_uint32, vp]
         lib.ssh_sensor_standin_curve.argtypes = [C.c_uint32, vp, vp, vp]
+        lib.ssh_glare_plan.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]
+        lib.ssh_glare_twiddles.argtypes = [C.c_uint32, vp]
+        lib.ssh_glare_aperture.argtypes = [C.c_uint32, C.c_float, C.c_float, C.c_double, C.c_int, C.c_double, C.c_double, C.c_double, C.c_uint32, vp, vp]
         _host = lib
     return _host
 
@@ -452,6 +466,9 @@ def hip_lib():
             lib.ssx_sensor_images.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.POINTER(SsxSensorParams), vp, vp]
             lib.ssx_demosaic_images.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.POINTER(SsxSensorParams), vp]
             lib.ssx_spectral_develop_sensor.argtypes = [vp, C.POINTER(SsxDenoiseParams), C.POINTER(SsxDefocusParams), C.POINTER(SsxOpticsParams), C.POINTER(SsxSensorParams), vp, vp, vp]
+        if not override or hasattr(lib, "ssx_glare_images"):  # veiling glare and diffraction: per-bin convolution by FFT
+            lib.ssx_glare_images.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.POINTER(SsxGlareParams), vp]
+            lib.ssx_spectral_develop_glare.argtypes = [vp, C.POINTER(SsxDenoiseParams), C.POINTER(SsxDefocusParams), C.POINTER(SsxOpticsParams), C.POINTER(SsxGlareParams), vp, C.c_uint32, vp, vp]
         if not override or hasattr(lib, "ssx_spectral_moments_import"):  # the second moments through checkpoint and resume
             lib.ssx_spectral_moments_import.argtypes = [vp, C.POINTER(SsxSpectralInfo), vp]
         if not override or hasattr(lib, "ssx_debug_tile_mask"):  # the camera-ray pre-trace's tile masks, read back

@@ -364,6 +364,135 @@ int ssh_optics_lens(uint32_t bins, float lambda_min, float lambda_step, double l
 	return SSX_OK;
 }
 
+int ssh_glare_plan(uint32_t width, uint32_t height, uint32_t radius, uint32_t* px, uint32_t* py) {
+	if (!px || !py) { g_error = "NULL argument"; return SSX_ERR_ARG; }
+	if (width == 0u || height == 0u) { g_error = "ssh_glare_plan: width and height must be positive"; return SSX_ERR_ARG; }
+	if (radius > SSX_GLARE_MAX_RADIUS) { g_error = "ssh_glare_plan: radius must be 0..256"; return SSX_ERR_ARG; }
+	if (width > SSX_GLARE_MAX_EXTENT || height > SSX_GLARE_MAX_EXTENT) { g_error = "ssh_glare_plan: a padded extent would exceed 4096"; return SSX_ERR_ARG; }
+	uint32_t x = 2u, y = 2u;
+	while (x < width + 2u * radius) x <<= 1;
+	while (y < height + 2u * radius) y <<= 1;
+	if (x > SSX_GLARE_MAX_EXTENT || y > SSX_GLARE_MAX_EXTENT) { g_error = "ssh_glare_plan: a padded extent would exceed 4096"; return SSX_ERR_ARG; }
+	*px = x; *py = y;
+	return SSX_OK;
+}
+
+int ssh_glare_twiddles(uint32_t P, float* out) {
+	if (!out) { g_error = "NULL argument"; return SSX_ERR_ARG; }
+	if (P < 2u || P > SSX_GLARE_MAX_EXTENT || (P & (P - 1u))) { g_error = "ssh_glare_twiddles: P must be a power of two in 2..4096"; return SSX_ERR_ARG; }
+	for (uint32_t m = 0; m < P / 2u; ++m) {
+		const double x = (2.0 * 3.14159265358979323846 * static_cast<double>(m)) / static_cast<double>(P);
+		out[2u * m] = static_cast<float>(std::cos(x));
+		out[2u * m + 1u] = static_cast<float>(-std::sin(x));
+	}
+	out[0] = 1.0f; out[1] = 0.0f;
+	if (P >= 4u) { out[2u * (P / 4u)] = 0.0f; out[2u * (P / 4u) + 1u] = -1.0f; }
+	return SSX_OK;
+}
+
+namespace {
+
+// in-place binary64 radix-2 FFT of n = 2^k values with stride `stride` (decimation in time, libm twiddles): ssh_glare_aperture's own
+void glare_fft64(double* re, double* im, uint32_t n, size_t stride, const std::vector<double>& c, const std::vector<double>& s) {
+	for (uint32_t i = 1, j = 0; i < n; ++i) {
+		uint32_t bit = n >> 1;
+		for (; j & bit; bit >>= 1) j ^= bit;
+		j ^= bit;
+		if (i < j) { std::swap(re[i * stride], re[j * stride]); std::swap(im[i * stride], im[j * stride]); }
+	}
+	for (uint32_t h = 1; h < n; h <<= 1) {
+		const uint32_t step = n / (2u * h);
+		for (uint32_t g = 0; g < n; g += 2u * h)
+			for (uint32_t k = 0; k < h; ++k) {
+				const double wr = c[k * step], wi = -s[k * step];
+				double& ar = re[(g + k) * stride]; double& ai = im[(g + k) * stride];
+				double& br = re[(g + k + h) * stride]; double& bi = im[(g + k + h) * stride];
+				const double tr = wr * br - wi * bi, ti = wr * bi + wi * br;
+				br = ar - tr; bi = ai - ti; ar = ar + tr; ai = ai + ti;
+			}
+	}
+}
+
+} // namespace
+
+int ssh_glare_aperture(uint32_t bins, float lambda_min, float lambda_step, double lambda_ref, int blades, double rotation, double ring_px, double strength,
+                       uint32_t radius, float* psf_out, uint8_t* on_out) {
+	if (!psf_out || !on_out) { g_error = "NULL argument"; return SSX_ERR_ARG; }
+	if (bins < 4u || bins > 64u || (bins & 3u)) { g_error = "ssh_glare_aperture: bins must be a multiple of 4 up to 64"; return SSX_ERR_ARG; }
+	if (radius > SSX_GLARE_MAX_RADIUS) { g_error = "ssh_glare_aperture: radius must be 0..256"; return SSX_ERR_ARG; }
+	if (!std::isfinite(lambda_min) || !(lambda_min > 0.0f) || !std::isfinite(lambda_step) || !(lambda_step > 0.0f)) { g_error = "ssh_glare_aperture: lambda_min and lambda_step must be finite and positive"; return SSX_ERR_ARG; }
+	if (!std::isfinite(lambda_ref) || !(lambda_ref > 0.0)) { g_error = "ssh_glare_aperture: lambda_ref must be finite and positive"; return SSX_ERR_ARG; }
+	if (!std::isfinite(rotation)) { g_error = "ssh_glare_aperture: rotation must be finite"; return SSX_ERR_ARG; }
+	if (!std::isfinite(ring_px) || !(ring_px > 0.0)) { g_error = "ssh_glare_aperture: ring_px must be finite and positive"; return SSX_ERR_ARG; }
+	if (!(strength >= 0.0) || !(strength <= 1.0)) { g_error = "ssh_glare_aperture: strength must be 0..1"; return SSX_ERR_ARG; }
+	if (blades > 64) { g_error = "ssh_glare_aperture: at most 64 blades"; return SSX_ERR_ARG; }
+	const uint32_t R = radius, K = 2u * R + 1u;
+	const size_t KK = static_cast<size_t>(K) * K;
+	for (uint32_t b = 0; b < bins; ++b) {
+		on_out[b] = strength != 0.0;
+		for (size_t k = 0; k < KK; ++k) psf_out[b * KK + k] = 0.0f;
+		psf_out[b * KK + static_cast<size_t>(R) * K + R] = 1.0f;
+	}
+	if (strength == 0.0) return SSX_OK;
+	constexpr uint32_t N = SSH_GLARE_GRID, SUB = SSH_GLARE_SUBSAMPLES;
+	constexpr double A = SSH_GLARE_PUPIL, pi = 3.14159265358979323846;
+	// the aperture: coverage of each cell by the polygon (circumradius A about the grid's centre), SUB x SUB samples per cell
+	std::vector<double> re(static_cast<size_t>(N) * N, 0.0), im(static_cast<size_t>(N) * N, 0.0);
+	const bool disc = blades < 3;
+	std::vector<double> nx, ny;
+	const double apothem = disc ? A : A * std::cos(pi / blades);
+	for (int k = 0; !disc && k < blades; ++k) {
+		const double t = rotation + (2.0 * k + 1.0) * pi / blades;
+		nx.push_back(std::cos(t)); ny.push_back(std::sin(t));
+	}
+	const int lo = static_cast<int>(N / 2u) - static_cast<int>(A) - 2, hi = static_cast<int>(N / 2u) + static_cast<int>(A) + 2;
+	for (int y = lo; y < hi; ++y)
+		for (int x = lo; x < hi; ++x) {
+			uint32_t inside = 0;
+			for (uint32_t v = 0; v < SUB; ++v)
+				for (uint32_t u = 0; u < SUB; ++u) {
+					const double sx = (x + (u + 0.5) / SUB) - N / 2.0, sy = (y + (v + 0.5) / SUB) - N / 2.0;
+					bool in = true;
+					if (disc) in = sx * sx + sy * sy <= A * A;
+					else for (size_t k = 0; k < nx.size() && in; ++k) in = sx * nx[k] + sy * ny[k] <= apothem;
+					inside += in;
+				}
+			re[static_cast<size_t>(y) * N + x] = static_cast<double>(inside) / (SUB * SUB);
+		}
+	std::vector<double> c(N / 2u), s(N / 2u);
+	for (uint32_t m = 0; m < N / 2u; ++m) { c[m] = std::cos(2.0 * pi * m / N); s[m] = std::sin(2.0 * pi * m / N); }
+	for (uint32_t y = 0; y < N; ++y) glare_fft64(&re[static_cast<size_t>(y) * N], &im[static_cast<size_t>(y) * N], N, 1, c, s);
+	for (uint32_t x = 0; x < N; ++x) glare_fft64(&re[x], &im[x], N, N, c, s);
+	for (size_t k = 0; k < re.size(); ++k) re[k] = re[k] * re[k] + im[k] * im[k];             // the far-field intensity, frequency (fy, fx) at [fy mod N][fx mod N]
+	auto at = [&re](int fy, int fx) { return re[static_cast<size_t>((fy + static_cast<int>(N)) % static_cast<int>(N)) * N + static_cast<size_t>((fx + static_cast<int>(N)) % static_cast<int>(N))]; };
+	const double ring0 = SSH_GLARE_AIRY_ZERO * N / (2.0 * A);                                   // a disc's first dark ring, in frequency samples
+	const double width = static_cast<double>(lambda_step) / (bins / 4u), limit = N / 2.0 - 1.0;
+	std::vector<double> pat(KK);
+	for (uint32_t b = 0; b < bins; ++b) {
+		const double lc = static_cast<double>(lambda_min) + (b + 0.5) * width;
+		const double kappa = (ring0 / ring_px) * (lambda_ref / lc);
+		double total = 0.0;
+		for (uint32_t j = 0; j < K; ++j)
+			for (uint32_t i = 0; i < K; ++i) {
+				const double fy = (static_cast<double>(j) - R) * kappa, fx = (static_cast<double>(i) - R) * kappa;
+				double v = 0.0;
+				if (std::fabs(fy) < limit && std::fabs(fx) < limit) {
+					const double y0 = std::floor(fy), x0 = std::floor(fx), ty = fy - y0, tx = fx - x0;
+					const int iy = static_cast<int>(y0), ix = static_cast<int>(x0);
+					const double l = at(iy, ix) * (1.0 - tx) + at(iy, ix + 1) * tx, h = at(iy + 1, ix) * (1.0 - tx) + at(iy + 1, ix + 1) * tx;
+					v = l * (1.0 - ty) + h * ty;
+				}
+				pat[static_cast<size_t>(j) * K + i] = v;
+				total = total + v;
+			}
+		for (size_t k = 0; k < KK; ++k) {
+			const double delta = k == static_cast<size_t>(R) * K + R ? 1.0 : 0.0;
+			psf_out[b * KK + k] = static_cast<float>((1.0 - strength) * delta + strength * (pat[k] / total));
+		}
+	}
+	return SSX_OK;
+}
+
 int ssh_sensor_bayer(const char* pattern, int method, uint32_t* cfa_out, float* taps_out) {
 	if (!pattern || !cfa_out || !taps_out) { g_error = "NULL argument"; return SSX_ERR_ARG; }
 	if (method != SSH_DEMOSAIC_BILINEAR && method != SSH_DEMOSAIC_MHC) { g_error = "ssh_sensor_bayer: method must be SSH_DEMOSAIC_BILINEAR or SSH_DEMOSAIC_MHC"; return SSX_ERR_ARG; }

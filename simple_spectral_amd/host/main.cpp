@@ -23,6 +23,7 @@
 // device -- through the same XYZ -> sRGB store and writers as --output -- under --develop-observer=1931|2006 (default: the render's), through --develop-filter=FILE.csv
 // (--develop-lens=lateral,sigma,axial[,lambda_ref] with --develop-lens-radius=R puts a lens in front: include/ssx.h "Developing through a lens";
 // --develop-defocus=aperture,focus_distance[,axial[,lambda_ref]] with --develop-defocus-radius=R gives it an aperture: "Depth of field after the render";
+// --develop-glare=blades,ring_px,strength[,rotation[,lambda_ref]] with --develop-glare-radius=R puts an iris's diffraction behind the lens: "Glare: per-bin convolution by FFT";
 // --develop-sensor=PATTERN[,mhc|bilinear] with --develop-sensor-curves / -exposure / -noise / -bits and --sensor-raw-output puts a sensor behind both: "Developing
 // onto a sensor")
 // (a spectrum in the format of data/*.csv, its range in the name: NAME-LOW+STEP+HIGH.csv) and relit by --develop-relight=NEW.csv (the emitters' spectrum replaced by
@@ -111,6 +112,10 @@ void print_usage() {
 		"    [`--develop-lens=<lateral>,<sigma>,<axial>[,<lambda_ref=550>]`] [`--develop-lens-radius=<0..12, default 8>`] [`--delta-e-lens=...`]\n"
 		"          (the bins through a lens before they are developed: lateral chromatic aberration, a blur of <sigma> pixels at <lambda_ref> growing with the\n"
 		"           wavelength, <axial> pixels of defocus per relative wavelength offset; for `--develop-output` and side A of `--delta-e-*`, `--delta-e-lens` for side B)\n"
+		"    [`--develop-glare=<blades>,<ring_px>,<strength>[,<rotation=0>[,<lambda_ref=550>]]`] [`--develop-glare-radius=<0..256, default 64>`] [`--delta-e-glare=...`]\n"
+		"          (veiling glare and diffraction behind the lens: every bin convolved with the far-field pattern of an iris of <blades> blades (fewer than 3: a\n"
+		"           disc), a disc's first dark ring <ring_px> pixels out at <lambda_ref> and growing with the wavelength, <strength> of the light leaving the\n"
+		"           geometric image, the iris turned by <rotation> radians; sides as for `--develop-lens`)\n"
 		"    [`--develop-defocus=<aperture>,<focus_distance>[,<axial=0>[,<lambda_ref=550>]]`] [`--develop-defocus-radius=<0..12, default 8>`] [`--delta-e-defocus=...`]\n"
 		"          (depth of field from the depth guide before the lens: an aperture of diameter <aperture> focused at <focus_distance>, both in scene units, the\n"
 		"           inverse focus distance moving by <axial> per relative wavelength offset; sides as for `--develop-lens`)\n"
@@ -221,6 +226,11 @@ struct Progressive { // the flags of the progressive modes
 	struct Aperture { bool on = false; double aperture = 0.0, focus_distance = 1.0, axial = 0.0, lambda_ref = 550.0; };
 	Aperture develop_defocus, delta_e_defocus;
 	unsigned develop_defocus_radius = 8;
+	// the glare behind the lens (include/ssx.h "Glare: per-bin convolution by FFT"; ssh_glare_aperture): --develop-glare=blades,ring_px,strength[,rotation[,lambda_ref]]
+	// and --delta-e-glare=... for the same sides, --develop-glare-radius=R (the psf's radius, for both)
+	struct Iris { bool on = false; int blades = 0; double ring_px = 1.0, strength = 0.0, rotation = 0.0, lambda_ref = 550.0; };
+	Iris develop_glare, delta_e_glare;
+	unsigned develop_glare_radius = 64;
 	// the sensor (include/ssx.h "Developing onto a sensor"): --develop-sensor=PATTERN[,mhc|bilinear], --develop-sensor-curves=R.csv,G.csv,B.csv (also on its own: an
 	// ordinary develop with a camera's curves), --develop-sensor-exposure=full_well,white_level, --develop-sensor-noise=read_e[,seed], --develop-sensor-bits=N[,black],
 	// --sensor-raw-output=raw.npy
@@ -404,6 +414,39 @@ void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progress
 		g->develop_defocus_radius = static_cast<unsigned>(r);
 		defocus_radius_given = true;
 	}
+	auto take_glare = [&](const char* flag, Progressive::Iris* iris) {
+		if (!a.take(flag, "", &v)) return;
+		double x[5] = { 0.0, 1.0, 0.0, 0.0, 550.0 };
+		size_t n = 0, at = 0;
+		bool ok = true;
+		try {
+			while (ok && n < 5) {
+				const size_t comma = v.find(',', at);
+				const std::string part = v.substr(at, comma == std::string::npos ? std::string::npos : comma - at);
+				size_t used = 0;
+				x[n++] = std::stod(part, &used);
+				ok = used == part.size() && std::isfinite(x[n - 1]);
+				if (comma == std::string::npos) break;
+				at = comma + 1;
+				if (n == 5) ok = false;
+			}
+		} catch (...) { ok = false; }
+		if (!ok || n < 3 || x[0] < 0.0 || x[0] > 64.0 || x[0] != std::floor(x[0]) || !(x[1] > 0.0) || x[2] < 0.0 || x[2] > 1.0 || !(x[4] > 0.0)) {
+			std::fprintf(stderr, "Invalid value for %s (<blades>,<ring_px>,<strength>[,<rotation>[,<lambda_ref>]]: finite, blades an integer 0..64, ring_px > 0, strength 0..1, lambda_ref > 0)!\n", flag);
+			throw -2;
+		}
+		iris->on = true; iris->blades = static_cast<int>(x[0]); iris->ring_px = x[1]; iris->strength = x[2]; iris->rotation = x[3]; iris->lambda_ref = x[4];
+	};
+	take_glare("--develop-glare", &g->develop_glare);
+	take_glare("--delta-e-glare", &g->delta_e_glare);
+	bool glare_radius_given = false;
+	if (a.take("--develop-glare-radius", "", &v)) {
+		size_t r = 999;
+		try { r = v == "0" ? 0 : to_pos(v); } catch (int) { r = 999; }
+		if (r > SSX_GLARE_MAX_RADIUS) { std::fprintf(stderr, "Invalid value for --develop-glare-radius (0..256)!\n"); throw -2; }
+		g->develop_glare_radius = static_cast<unsigned>(r);
+		glare_radius_given = true;
+	}
 	{ // the sensor's options
 		auto split = [](const std::string& s) {
 			std::vector<std::string> parts;
@@ -485,6 +528,8 @@ void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progress
 		delta_e_side = true;
 	}
 	if (g->delta_e_lens.on || g->delta_e_defocus.on) delta_e_side = true;
+	if (glare_radius_given && !g->develop_glare.on && !g->delta_e_glare.on) { std::fprintf(stderr, "`--develop-glare-radius` needs `--develop-glare` or `--delta-e-glare`!\n"); throw -2; }
+	if (g->delta_e_glare.on && !g->delta_e()) { std::fprintf(stderr, "`--delta-e-glare` needs `--delta-e-output=<file.npy>` or `--delta-e-csv=<file.csv>`!\n"); throw -2; }
 	if (defocus_radius_given && !g->develop_defocus.on && !g->delta_e_defocus.on) { std::fprintf(stderr, "`--develop-defocus-radius` needs `--develop-defocus` or `--delta-e-defocus`!\n"); throw -2; }
 	if (lens_radius_given && !g->develop_lens.on && !g->delta_e_lens.on) { std::fprintf(stderr, "`--develop-lens-radius` needs `--develop-lens` or `--delta-e-lens`!\n"); throw -2; }
 	if (delta_e_side && !g->delta_e()) {
@@ -523,6 +568,7 @@ void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progress
 		std::fprintf(stderr, "`--develop-observer`, `--develop-filter`, `--develop-relight`, `--develop-lens`, `--develop-defocus` and `--develop-sensor-curves` need `--develop-output=<image>`!\n");
 		throw -2;
 	}
+	if (g->develop_glare.on && g->develop_output.empty() && !g->delta_e()) { std::fprintf(stderr, "`--develop-glare` needs `--develop-output=<image>`!\n"); throw -2; }
 	if (g->sensor.on && g->develop_output.empty()) { std::fprintf(stderr, "`--develop-sensor` needs `--develop-output=<image>`: it writes the demosaiced image there!\n"); throw -2; }
 	if (g->sensor.on && g->delta_e()) { std::fprintf(stderr, "`--develop-sensor` cannot be combined with `--delta-e-output` or `--delta-e-csv`: compare two developments with Renderer.delta_e_images instead!\n"); throw -2; }
 	if (g->delta_e() && !g->spectral_bins_given) {
@@ -792,6 +838,24 @@ int main(int argc, char* argv[]) {
 		make_aperture(prog.delta_e_defocus, &aperture_b);
 		const ssx::Renderer::Defocus* const defocus_a = prog.develop_defocus.on ? &aperture_a : nullptr;
 		const ssx::Renderer::Defocus* const defocus_b = prog.delta_e_defocus.on ? &aperture_b : nullptr;
+		// ... and the glares, with the plan and the twiddles of this image
+		ssx::Renderer::Glare glare_store_a, glare_store_b;
+		auto make_glare = [&](const Progressive::Iris& iris, ssx::Renderer::Glare* gl) {
+			if (!iris.on) return;
+			const ssx_scene_desc& d = renderer.scene->desc();
+			const uint32_t B = static_cast<uint32_t>(prog.spectral_bins), R = prog.develop_glare_radius, K = 2u * R + 1u;
+			gl->radius = R; gl->on.resize(B); gl->psf.resize(static_cast<size_t>(B) * K * K);
+			if (ssh_glare_plan(static_cast<uint32_t>(options.res[0]), static_cast<uint32_t>(options.res[1]), R, &gl->px, &gl->py) != SSX_OK)
+				throw ssx::HostError{ SSX_ERR_ARG, std::string("--develop-glare / --delta-e-glare: ") + ssh_last_error() };
+			gl->twiddle_x.resize(gl->px); gl->twiddle_y.resize(gl->py);
+			if (ssh_glare_twiddles(gl->px, gl->twiddle_x.data()) != SSX_OK || ssh_glare_twiddles(gl->py, gl->twiddle_y.data()) != SSX_OK ||
+			    ssh_glare_aperture(B, d.lambda_min, d.lambda_step, iris.lambda_ref, iris.blades, iris.rotation, iris.ring_px, iris.strength, R, gl->psf.data(), gl->on.data()) != SSX_OK)
+				throw ssx::HostError{ SSX_ERR_ARG, std::string("--develop-glare / --delta-e-glare: ") + ssh_last_error() };
+		};
+		make_glare(prog.develop_glare, &glare_store_a);
+		make_glare(prog.delta_e_glare, &glare_store_b);
+		const ssx::Renderer::Glare* const glare_a = prog.develop_glare.on ? &glare_store_a : nullptr;
+		const ssx::Renderer::Glare* const glare_b = prog.delta_e_glare.on ? &glare_store_b : nullptr;
 		// side B of --delta-e-*, and both sides' whites up to the common scale (host policy: the chromaticity is the development, by the side's weights without a
 		// relighting gain, of the side's illuminant -- the relight's new one, else the scene's emitter spectrum where it has one, else D65)
 		std::vector<float> delta_e_weights;
@@ -908,7 +972,8 @@ int main(int argc, char* argv[]) {
 			double scale = 0.0;
 			if (prog.delta_e_white_y > 0.0) scale = prog.delta_e_white_y / delta_e_white[0][1];
 			else {
-				const std::vector<float> xyz = renderer.develop(develop_weights.data(), 3, prog.spectral_denoise ? dn : nullptr, prog.spectral_denoise ? dm : nullptr, optics_a, defocus_a);
+				const std::vector<float> xyz = glare_a ? renderer.develop_glare(develop_weights.data(), 3, *glare_a, prog.spectral_denoise ? dn : nullptr, prog.spectral_denoise ? dm : nullptr, optics_a, defocus_a)
+				                                       : renderer.develop(develop_weights.data(), 3, prog.spectral_denoise ? dn : nullptr, prog.spectral_denoise ? dm : nullptr, optics_a, defocus_a);
 				double sum = 0.0; size_t n = 0;
 				for (size_t p = 0; p < pixels; ++p) if (std::isfinite(xyz[3 * p + 1])) { sum += static_cast<double>(xyz[3 * p + 1]); ++n; }
 				const double mean = n ? sum / static_cast<double>(n) : 0.0;
@@ -916,7 +981,7 @@ int main(int argc, char* argv[]) {
 				scale = (mean / 0.18) / delta_e_white[0][1];
 			}
 			for (int x = 0; x < 2; ++x) for (int c = 0; c < 3; ++c) delta_e_white[x][c] *= scale;
-			const ssx::Renderer::DeltaESide side_a{ develop_weights.data(), prog.spectral_denoise, optics_a, defocus_a }, side_b{ delta_e_weights.data(), prog.delta_e_denoise, optics_b, defocus_b };
+			const ssx::Renderer::DeltaESide side_a{ develop_weights.data(), prog.spectral_denoise, optics_a, defocus_a, glare_a }, side_b{ delta_e_weights.data(), prog.delta_e_denoise, optics_b, defocus_b, glare_b };
 			const ssx::Renderer::DeltaE e = renderer.delta_e(side_a, side_b, delta_e_white[0], delta_e_white[1], labels, regions, prog.delta_e_threshold, !prog.delta_e_output.empty(), dn,
 			                                                 (prog.spectral_denoise || prog.delta_e_denoise) ? dm : nullptr);
 			if (!prog.delta_e_csv.empty()) renderer.save_delta_e_csv(prog.delta_e_csv, e);
@@ -927,13 +992,14 @@ int main(int argc, char* argv[]) {
 		if (!prog.develop_output.empty()) { // X, Y, Z from the bins, the alpha of the render's image, then the store of --output
 			std::vector<float> xyz;
 			if (prog.sensor.on) { // through the sensor: the ccm has taken the demosaiced image to X, Y, Z
-				ssx::Renderer::SensorImage img = renderer.develop_sensor(sensor, prog.spectral_denoise ? &prog.denoise_params : nullptr, prog.demodulate ? &prog.demod_params : nullptr, optics_a, defocus_a);
+				ssx::Renderer::SensorImage img = renderer.develop_sensor(sensor, prog.spectral_denoise ? &prog.denoise_params : nullptr, prog.demodulate ? &prog.demod_params : nullptr, optics_a, defocus_a, glare_a);
 				if (!prog.sensor.raw_output.empty()) {
 					const size_t shape[2] = { options.res[1], options.res[0] };
 					ssx::save_npy_f32(prog.sensor.raw_output, img.raw.data(), shape, 2);
 				}
 				xyz = std::move(img.out);
-			} else xyz = renderer.develop(develop_weights.data(), 3, prog.spectral_denoise ? &prog.denoise_params : nullptr, prog.demodulate ? &prog.demod_params : nullptr, optics_a, defocus_a);
+			} else if (glare_a) xyz = renderer.develop_glare(develop_weights.data(), 3, *glare_a, prog.spectral_denoise ? &prog.denoise_params : nullptr, prog.demodulate ? &prog.demod_params : nullptr, optics_a, defocus_a);
+			else xyz = renderer.develop(develop_weights.data(), 3, prog.spectral_denoise ? &prog.denoise_params : nullptr, prog.demodulate ? &prog.demod_params : nullptr, optics_a, defocus_a);
 			const size_t pixels = options.res[0] * options.res[1];
 			std::vector<float> xyza(pixels * 4);
 			for (size_t p = 0; p < pixels; ++p) { xyza[4 * p] = xyz[3 * p]; xyza[4 * p + 1] = xyz[3 * p + 1]; xyza[4 * p + 2] = xyz[3 * p + 2]; xyza[4 * p + 3] = renderer.xyza[4 * p + 3]; }

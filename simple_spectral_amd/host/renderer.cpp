@@ -34,7 +34,7 @@ void Framebuffer::save(const std::string& path) const { save_image(path, pixels_
 	X(render_continue) X(sums_export) X(sums_import) X(set_noise_estimate) X(noise_info) \
 	X(set_spectral_bins) X(spectral_read) X(spectral_import) X(set_spectral_moments) X(spectral_variance) X(spectral_moments_import) X(spectral_probe) X(probe_arrays) X(spectral_noise) X(spectral_noise_reduce) X(spectral_compare) X(spectral_compare_arrays) X(delta_e_images) X(spectral_delta_e) \
 	X(guides) X(denoise_images) X(denoise) X(denoise_channels) X(denoise_spectral) \
-	X(develop_images) X(spectral_develop) X(albedo_bins) X(denoise_spectral_demod) X(spectral_develop_demod) X(optics_images) X(spectral_develop_optics) X(defocus_images) X(spectral_develop_lens) X(sensor_images) X(demosaic_images) X(spectral_develop_sensor)
+	X(develop_images) X(spectral_develop) X(albedo_bins) X(denoise_spectral_demod) X(spectral_develop_demod) X(optics_images) X(spectral_develop_optics) X(defocus_images) X(spectral_develop_lens) X(sensor_images) X(demosaic_images) X(spectral_develop_sensor) X(glare_images) X(spectral_develop_glare)
 
 struct Renderer::Api {
 	void* handle = nullptr;
@@ -619,7 +619,7 @@ Renderer::DeltaE Renderer::delta_e(const DeltaESide& side_a, const DeltaESide& s
 	if (demod && !filtered) throw HostError{ SSX_ERR_ARG, "delta_e: the demodulated mode is a mode of a denoised side" };
 	const size_t pixels = options.res[0] * options.res[1];
 	delta_e_check_labels("delta_e", labels, pixels, regions);
-	if (ctxs_.size() == 1 && !demod && !side_a.optics && !side_b.optics && !side_a.defocus && !side_b.defocus) {
+	if (ctxs_.size() == 1 && !demod && !side_a.optics && !side_b.optics && !side_a.defocus && !side_b.defocus && !side_a.glare && !side_b.glare) {
 		DeltaE r = delta_e_result(pixels, regions, maps);
 		ssx_ctx* root = ctxs_[0];
 		const ssx_denoise_params dp = denoise ? to_abi(*denoise, false) : ssx_denoise_params{};
@@ -630,8 +630,12 @@ Renderer::DeltaE Renderer::delta_e(const DeltaESide& side_a, const DeltaESide& s
 		return r;
 	}
 	// each side by the develop's own route (several devices: every pixel from its owner; the demodulated filter), then the pure entry on device 0
-	const std::vector<float> xyz_a = develop(side_a.weights, 3, side_a.denoised ? denoise : nullptr, side_a.denoised ? demod : nullptr, side_a.optics, side_a.defocus);
-	const std::vector<float> xyz_b = develop(side_b.weights, 3, side_b.denoised ? denoise : nullptr, side_b.denoised ? demod : nullptr, side_b.optics, side_b.defocus);
+	auto side = [&](const DeltaESide& x) {
+		const DenoiseParams* const dn = x.denoised ? denoise : nullptr;
+		const DemodParams* const dm = x.denoised ? demod : nullptr;
+		return x.glare ? develop_glare(x.weights, 3, *x.glare, dn, dm, x.optics, x.defocus) : develop(x.weights, 3, dn, dm, x.optics, x.defocus);
+	};
+	const std::vector<float> xyz_a = side(side_a), xyz_b = side(side_b);
 	return delta_e_images(xyz_a.data(), xyz_b.data(), white_a, white_b, labels, regions, t, maps);
 }
 
@@ -874,12 +878,20 @@ std::vector<float> Renderer::demosaic_images(const float* raw, const Sensor& sen
 	return out;
 }
 
-Renderer::SensorImage Renderer::develop_sensor(const Sensor& sensor, const DenoiseParams* denoise, const DemodParams* demod, const Optics* optics, const Defocus* defocus) {
+Renderer::SensorImage Renderer::develop_sensor(const Sensor& sensor, const DenoiseParams* denoise, const DemodParams* demod, const Optics* optics, const Defocus* defocus,
+                                               const Glare* glare) {
 	wait_workers_();
 	if (!spectral_bins_) throw HostError{ SSX_ERR_STATE, "develop_sensor: spectral output is off (set_spectral_bins)" };
 	if (demod && !denoise) throw HostError{ SSX_ERR_ARG, "develop_sensor: the demodulated mode is a mode of the denoised source (pass denoise)" };
 	const size_t pixels = options.res[0] * options.res[1], B = spectral_bins_;
 	SensorImage r;
+	if (glare) { // the bins behind the glare, then the pure entries on device 0
+		std::vector<float> bins;
+		(void)develop_glare(nullptr, 0, *glare, denoise, demod, optics, defocus, &bins);
+		r.raw = sensor_images(bins.data(), sensor, &r.dn);
+		r.out = demosaic_images(r.raw.data(), sensor);
+		return r;
+	}
 	if (ctxs_.size() == 1 && !demod) {
 		ssx_ctx* root = ctxs_[0];
 		const ssx_sensor_params sp = to_abi(sensor, B, true);
@@ -898,6 +910,61 @@ Renderer::SensorImage Renderer::develop_sensor(const Sensor& sensor, const Denoi
 	r.raw = sensor_images(bins.data(), sensor, &r.dn);
 	r.out = demosaic_images(r.raw.data(), sensor);
 	return r;
+}
+
+namespace {
+// the glare as the C ABI takes it
+ssx_glare_params to_abi(const Renderer::Glare& g, size_t B) {
+	const size_t K = 2u * static_cast<size_t>(g.radius) + 1u;
+	if (g.on.size() != B || (g.radius <= SSX_GLARE_MAX_RADIUS && g.psf.size() != B * K * K))
+		throw HostError{ SSX_ERR_ARG, "Glare: on must hold one entry per wavelength bin, psf (2 * radius + 1)^2 per bin" };
+	if ((g.px && g.px <= SSX_GLARE_MAX_EXTENT && g.twiddle_x.size() != g.px) || (g.py && g.py <= SSX_GLARE_MAX_EXTENT && g.twiddle_y.size() != g.py))
+		throw HostError{ SSX_ERR_ARG, "Glare: twiddle_x must hold [px / 2][2] entries and twiddle_y [py / 2][2]" };
+	ssx_glare_params p{};
+	p.struct_size = sizeof p;
+	p.radius = g.radius; p.px = g.px; p.py = g.py;
+	p.on = g.on.data(); p.psf = g.psf.data(); p.twiddle_x = g.twiddle_x.data(); p.twiddle_y = g.twiddle_y.data();
+	return p;
+}
+} // namespace
+
+std::vector<float> Renderer::glare_images(const float* q, const Glare& glare) {
+	wait_workers_();
+	if (!spectral_bins_) throw HostError{ SSX_ERR_STATE, "glare_images: spectral output is off (set_spectral_bins)" };
+	const size_t pixels = options.res[0] * options.res[1], B = spectral_bins_;
+	const ssx_glare_params gp = to_abi(glare, B);
+	std::vector<float> out(pixels * B);
+	check_(api_->glare_images(ctxs_[0], w32_(), h32_(), static_cast<uint32_t>(B), q, &gp, out.data()), "ssx_glare_images", ctxs_[0]);
+	return out;
+}
+
+std::vector<float> Renderer::develop_glare(const float* weights, size_t channels, const Glare& glare, const DenoiseParams* denoise, const DemodParams* demod, const Optics* optics,
+                                           const Defocus* defocus, std::vector<float>* bins_out) {
+	wait_workers_();
+	if (!spectral_bins_) throw HostError{ SSX_ERR_STATE, "develop_glare: spectral output is off (set_spectral_bins)" };
+	if (demod && !denoise) throw HostError{ SSX_ERR_ARG, "develop_glare: the demodulated mode is a mode of the denoised source (pass denoise)" };
+	if (!weights != !channels) throw HostError{ SSX_ERR_ARG, "develop_glare: weights and channels go together (NULL and 0: the bins alone)" };
+	const size_t pixels = options.res[0] * options.res[1], B = spectral_bins_, C = channels;
+	const uint32_t c32 = static_cast<uint32_t>(C);
+	std::vector<float> out(pixels * C);
+	ssx_ctx* root = ctxs_[0];
+	if (ctxs_.size() == 1 && !demod) {
+		const ssx_glare_params gp = to_abi(glare, B);
+		const ssx_denoise_params dp = denoise ? to_abi(*denoise, false) : ssx_denoise_params{};
+		const ssx_defocus_params df = defocus ? to_abi(*defocus, B) : ssx_defocus_params{};
+		const ssx_optics_params op = optics ? to_abi(*optics, options.res[0], options.res[1], B) : ssx_optics_params{};
+		if (bins_out) bins_out->assign(pixels * B, 0.0f);
+		check_(api_->spectral_develop_glare(root, denoise ? &dp : nullptr, defocus ? &df : nullptr, optics ? &op : nullptr, &gp, weights, c32, C ? out.data() : nullptr,
+		                                    bins_out ? bins_out->data() : nullptr), "ssx_spectral_develop_glare", root);
+		return out;
+	}
+	std::vector<float> bins = source_bins_(denoise, demod); // then the pure entries on device 0 (the depth guide does not depend on ownership)
+	if (defocus) bins = defocus_images(bins.data(), guides().depth.data(), *defocus);
+	if (optics) bins = optics_images(bins.data(), *optics);
+	bins = glare_images(bins.data(), glare);
+	if (C) check_(api_->develop_images(root, w32_(), h32_(), static_cast<uint32_t>(B), bins.data(), weights, c32, out.data()), "ssx_develop_images", root);
+	if (bins_out) *bins_out = std::move(bins);
+	return out;
 }
 
 std::vector<float> Renderer::develop(const float* weights, size_t channels, const DenoiseParams* denoise, const DemodParams* demod, const Optics* optics, const Defocus* defocus) {

@@ -218,6 +218,19 @@ public:
 	std::vector<float> defocus_images(const float* q, const float* depth, const Defocus& defocus);
 	// the lens as a pure function on q [height][width][B] of the options' size (ssx_optics_images on device 0)
 	std::vector<float> optics_images(const float* q, const Optics& optics);
+	// Glare (include/ssx.h "Glare: per-bin convolution by FFT"): behind the aperture and the lens every `on` bin is convolved with its own point spread function,
+	// then developed.  One device and no demodulated source: ssx_spectral_develop_glare, all on the device.  Otherwise q by develop()'s gather, then
+	// ssx_defocus_images, ssx_optics_images, ssx_glare_images and ssx_develop_images on device 0: the same bits.  weights NULL with channels 0: no development,
+	// the result is empty.  bins_out: the bins behind the glare [height][width][B].
+	struct Glare { // ssx_glare_params (ssh_glare_aperture, ssh_glare_plan, ssh_glare_twiddles make them); on [B], psf [B][2 R + 1][2 R + 1], twiddles [px / 2][2], [py / 2][2]
+		uint32_t radius = 0, px = 0, py = 0;
+		std::vector<uint8_t> on;
+		std::vector<float> psf, twiddle_x, twiddle_y;
+	};
+	std::vector<float> develop_glare(const float* weights, size_t channels, const Glare& glare, const DenoiseParams* denoise = nullptr, const DemodParams* demod = nullptr,
+	                                 const Optics* optics = nullptr, const Defocus* defocus = nullptr, std::vector<float>* bins_out = nullptr);
+	// the glare as a pure function on q [height][width][B] of the options' size (ssx_glare_images on device 0)
+	std::vector<float> glare_images(const float* q, const Glare& glare);
 	// Developing onto a sensor (include/ssx.h "Developing onto a sensor"): behind the aperture and the lens the bins fall on a colour filter array, are counted,
 	// digitised and demosaiced.  One device and no demodulated source: ssx_spectral_develop_sensor, all on the device.  Otherwise q by develop()'s gather, then
 	// ssx_defocus_images, ssx_optics_images, ssx_sensor_images and ssx_demosaic_images on device 0: the same bits.
@@ -227,8 +240,9 @@ public:
 		std::vector<float> weights, taps, ccm;
 	};
 	struct SensorImage { std::vector<float> out, raw, dn; }; // [height][width][3], the mosaic [height][width], the ADC's numbers [height][width] (empty without an ADC)
+	// glare: the bins behind the glare (develop_glare's bins_out) fall on the sensor by way of ssx_sensor_images and ssx_demosaic_images on device 0
 	SensorImage develop_sensor(const Sensor& sensor, const DenoiseParams* denoise = nullptr, const DemodParams* demod = nullptr, const Optics* optics = nullptr,
-	                           const Defocus* defocus = nullptr);
+	                           const Defocus* defocus = nullptr, const Glare* glare = nullptr);
 	// the two stages as pure functions on arrays of the options' size (ssx_sensor_images, ssx_demosaic_images on device 0); dn may be NULL
 	std::vector<float> sensor_images(const float* q, const Sensor& sensor, std::vector<float>* dn = nullptr);
 	std::vector<float> demosaic_images(const float* raw, const Sensor& sensor);
@@ -238,7 +252,7 @@ public:
 	// and whether the bins are filtered first (then `denoise`, and `demod` for the demodulated mode, say how -- for both sides alike).  labels empty: the whole
 	// image is region 0 and regions must be 1.  One device and no demodulated side: ssx_spectral_delta_e.  Otherwise each side through develop() -- every pixel
 	// from the device that owns it -- then ssx_delta_e_images on device 0: the same bits.  The whites are the caller's (they set the absolute size of every dE).
-	struct DeltaESide { const float* weights = nullptr; bool denoised = false; const Optics* optics = nullptr; const Defocus* defocus = nullptr; }; // optics, defocus: the side seen through a lens, with an aperture (develop)
+	struct DeltaESide { const float* weights = nullptr; bool denoised = false; const Optics* optics = nullptr; const Defocus* defocus = nullptr; const Glare* glare = nullptr; }; // optics, defocus, glare: the side seen through a lens, with an aperture (develop), behind a glare (develop_glare)
 	struct DeltaE {
 		size_t regions = 0;
 		std::vector<double> SUM, SSQ, mean, rms, max, exceed, coverage; std::vector<float> MAX; std::vector<uint64_t> NF, NX, EX;

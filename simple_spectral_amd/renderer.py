@@ -441,6 +441,53 @@ def _defocus_arg(defocus):
     return p, (focus,)
 
 
+def glare_plan(width, height, radius):
+    """ssh_glare_plan: (px, py), the padded extents ssx_glare_params needs for an image of width x height and a psf of this radius."""
+    px, py = C.c_uint32(), C.c_uint32()
+    _host("ssh_glare_plan", int(width), int(height), int(radius), C.byref(px), C.byref(py))
+    return px.value, py.value
+
+
+def glare_twiddles(P):
+    """ssh_glare_twiddles: the forward twiddles T[m] = (cos, -sin)(2 pi m / P) as float32 [P / 2, 2]."""
+    t = np.zeros((max(int(P) // 2, 1), 2), dtype=np.float32)
+    _host("ssh_glare_twiddles", int(P), t.ctypes.data)
+    return t
+
+
+def glare_aperture(bins, lambda_min, lambda_step, width, height, blades=6, ring_px=1.5, strength=0.1, rotation=0.0, lambda_ref=550.0, radius=64):
+    """ssh_glare_aperture, ssh_glare_plan and ssh_glare_twiddles (include/ssx_host.h): the glare Renderer.develop(..., glare=) and Renderer.glare_images put behind
+    the lens for bins of a render with this lambda_min and lambda_step and an image of width x height, as a dict {radius, px, py, on [B], psf [B, K, K],
+    twiddle_x [px / 2, 2], twiddle_y [py / 2, 2]} -- what include/ssx.h's ssx_glare_params carries; any dict of that form is a glare.  blades: the iris's
+    straight blades (fewer than 3: a disc); ring_px: where a disc's first dark ring lies at lambda_ref, in pixels; strength: the share of the light that leaves
+    the geometric image; rotation in radians."""
+    R = int(radius)
+    K = 2 * max(R, 0) + 1
+    psf, on = np.zeros((bins, K, K), dtype=np.float32), np.zeros(bins, dtype=np.uint8)
+    _host("ssh_glare_aperture", int(bins), C.c_float(lambda_min), C.c_float(lambda_step), float(lambda_ref), int(blades), float(rotation), float(ring_px), float(strength),
+          R, psf.ctypes.data, on.ctypes.data)
+    px, py = glare_plan(width, height, R)
+    return {"radius": R, "px": px, "py": py, "on": on, "psf": psf, "twiddle_x": glare_twiddles(px), "twiddle_y": glare_twiddles(py)}
+
+
+def _glare_arg(glare):
+    """A glare dict (glare_aperture) -> (SsxGlareParams, the arrays that keep its tables alive).  Here only what would make the library read past an array."""
+    R, px, py = int(glare["radius"]), int(glare["px"]), int(glare["py"])
+    on = np.ascontiguousarray(glare["on"], dtype=np.uint8)
+    psf = np.ascontiguousarray(glare["psf"], dtype=np.float32)
+    tx = np.ascontiguousarray(glare["twiddle_x"], dtype=np.float32)
+    ty = np.ascontiguousarray(glare["twiddle_y"], dtype=np.float32)
+    if on.ndim != 1 or (0 <= R <= _capi.SSX_GLARE_MAX_RADIUS and psf.size != on.size * (2 * R + 1) ** 2):
+        raise ValueError("glare: on must have shape [B], psf [B, 2 * radius + 1, 2 * radius + 1]")
+    if (0 < px <= _capi.SSX_GLARE_MAX_EXTENT and tx.size != px) or (0 < py <= _capi.SSX_GLARE_MAX_EXTENT and ty.size != py):
+        raise ValueError("glare: twiddle_x must have shape [px / 2, 2], twiddle_y [py / 2, 2]")
+    p = _capi.SsxGlareParams()
+    p.struct_size = C.sizeof(_capi.SsxGlareParams)
+    p.radius, p.px, p.py = R & 0xFFFFFFFF, px & 0xFFFFFFFF, py & 0xFFFFFFFF
+    p.on, p.psf, p.twiddle_x, p.twiddle_y = on.ctypes.data, psf.ctypes.data, tx.ctypes.data, ty.ctypes.data
+    return p, (on, psf, tx, ty)
+
+
 def sensor_bayer(pattern, method="mhc"):
     """ssh_sensor_bayer (include/ssx_host.h): {"cfa": uint32 [4], "taps": float32 [4, 3, 25]} for a Bayer pattern "RGGB", "BGGR", "GRBG" or "GBRG" -- the first
     two letters are row 0, THE BOTTOM ROW -- and the demosaic `method`, "mhc" (Malvar-He-Cutler) or "bilinear".  Merged with sensor_exposure's dict, "weights"
@@ -1229,7 +1276,69 @@ class Renderer:
         self._check(self._lib.ssx_demosaic_images(self._ctx, W, H, raw.ctypes.data, C.byref(sp), out.ctypes.data))
         return out
 
-    def develop(self, weights, denoise=None, demodulate=None, optics=None, return_bins=False, defocus=None, sensor=None, return_raw=False):
+    def _develop_glare(self, weights, denoise, demodulate, optics, defocus, glare, sensor, return_bins, return_raw):
+        """develop(glare=): ssx_spectral_develop_glare; a sensor or a demodulated source by way of the bins behind the glare and the pure entries."""
+        W, H = self.options.res
+        gp, keep_g = _glare_arg(glare)
+        B = keep_g[0].size
+        if self._spectral_bins not in (0, B):
+            raise ValueError("develop: a glare for %d bins, the context holds %d" % (B, self._spectral_bins))
+        if sensor is not None and return_bins:
+            raise ValueError("develop: return_bins is not offered with a sensor (return_raw is)")
+        if sensor is None and return_raw:
+            raise ValueError("develop: return_raw needs a sensor")
+        if demodulate and denoise is None:
+            denoise = {}
+        p = None if denoise is None else self._denoise_params(denoise.get("levels", 5), denoise.get("sigma_l", _capi.SSX_DEMOD_DEFAULT_SIGMA_L if demodulate else 1.0),
+                                                              denoise.get("sigma_a", 0.1))
+        w = None
+        if sensor is None:
+            w = np.ascontiguousarray(weights, dtype=np.float32)
+            if w.ndim != 2 or w.shape[1] != B:
+                raise ValueError("develop: weights must have shape [C, B], B that of the glare")
+        if demodulate:
+            q = self.denoise_spectral(levels=p.levels, sigma_l=p.sigma_l, sigma_a=p.sigma_a, demodulate=demodulate)
+            if defocus is not None:
+                q = self.defocus_images(q, self.guides()["depth"], defocus)
+            if optics is not None:
+                q = self.optics_images(q, optics)
+            q = self.glare_images(q, glare)
+        else:
+            df, keep_f = _defocus_arg(defocus) if defocus is not None else (None, None)
+            op, keep_o = _optics_arg(optics, W, H) if optics is not None else (None, None)
+            if (keep_f is not None and keep_f[0].size != B) or (keep_o is not None and keep_o[0].size != B):
+                raise ValueError("develop: the aperture, the lens and the glare must be made for the same number of bins")
+            out = None if sensor is not None else np.zeros((H, W, w.shape[0]), dtype=np.float32)
+            q = np.zeros((H, W, B), dtype=np.float32) if sensor is not None or return_bins else None
+            self._check(self._lib.ssx_spectral_develop_glare(self._ctx, None if p is None else C.byref(p), None if df is None else C.byref(df), None if op is None else C.byref(op),
+                                                             C.byref(gp), None if w is None else w.ctypes.data, 0 if w is None else w.shape[0],
+                                                             None if out is None else out.ctypes.data, None if q is None else q.ctypes.data))
+            if sensor is None:
+                return (out, q) if return_bins else out
+        if sensor is None:
+            out = self.develop_images(q, w)
+            return (out, q) if return_bins else out
+        sp, _keep = _sensor_arg(sensor)
+        adc = sp.white > 0
+        raw, dn = self.sensor_images(q, sensor, return_dn=True) if adc else (self.sensor_images(q, sensor), None)
+        out = self.demosaic_images(raw, sensor)
+        return (out, raw, dn) if return_raw else out
+
+    def glare_images(self, q, glare):
+        """ssx_glare_images: the glare (glare_aperture) as a pure function: q [H, W, B] -> float32 [H, W, B], every `on` bin convolved with its own point spread
+        function by a padded FFT (include/ssx.h "Glare: per-bin convolution by FFT"), the other bins copied."""
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        if q.ndim != 3:
+            raise ValueError("glare_images: q must have shape [H, W, B]")
+        H, W, B = q.shape
+        gp, keep = _glare_arg(glare)
+        if keep[0].size != B:
+            raise ValueError("glare_images: a glare for %d bins, q has %d" % (keep[0].size, B))
+        out = np.zeros((H, W, B), dtype=np.float32)
+        self._check(self._lib.ssx_glare_images(self._ctx, W, H, B, q.ctypes.data, C.byref(gp), out.ctypes.data))
+        return out
+
+    def develop(self, weights, denoise=None, demodulate=None, optics=None, return_bins=False, defocus=None, sensor=None, return_raw=False, glare=None):
         """ssx_spectral_develop: the bins the context holds, mapped on the device by weights [C, B] (develop_weights) -> float32 [H, W, C], row 0 = bottom.
         denoise None: the raw source, q = S * M / n; a dict of denoise_spectral's parameters (levels, sigma_l, sigma_a; {} for the defaults): the filtered bins,
         developed without leaving the device.  demodulate (True or a dict, as in denoise_spectral; denoise None counts as {}): ssx_spectral_develop_demod, the
@@ -1240,7 +1349,11 @@ class Renderer:
         demodulated source by way of the host again (defocus_images with guides()["depth"]).  sensor (a dict: sensor_bayer's and sensor_exposure's entries,
         "weights" [3, B], "ccm" [3, 3], and "noise", "seed", "frame"): ssx_spectral_develop_sensor -- behind the aperture and the lens the bins fall on a colour
         filter array, are counted, digitised and demosaiced on the device; `weights` is then not used (None will do), the result is float32 [H, W, 3], and with
-        return_raw: (image, the mosaic [H, W], the ADC's numbers [H, W] or None).  Nothing the context holds changes."""
+        return_raw: (image, the mosaic [H, W], the ADC's numbers [H, W] or None).  glare (a dict: glare_aperture): ssx_spectral_develop_glare -- behind the
+        aperture and the lens every bin is convolved with its own point spread function, then developed, still on the device; return_bins gives the bins behind
+        the glare; with a sensor, or a demodulated source, the bins go by way of the host and the pure entries.  Nothing the context holds changes."""
+        if glare is not None:
+            return self._develop_glare(weights, denoise, demodulate, optics, defocus, glare, sensor, return_bins, return_raw)
         if sensor is not None:
             if return_bins:
                 raise ValueError("develop: return_bins is not offered with a sensor (return_raw is)")
