@@ -1176,6 +1176,92 @@ int ssx_spectral_develop_glare(ssx_ctx* ctx, const ssx_denoise_params* denoise /
                                const ssx_optics_params* optics /* or NULL */, const ssx_glare_params* glare /* or NULL */, const float* weights /* [C][B] */,
                                uint32_t channels, float* out /* [H][W][C] or NULL */, float* bins_out /* [H][W][B] or NULL */);
 
+/* ---- Finishing a development for a display: meter, local tone map, tone curve (appended; same ABI version) ----------------------------------------
+ * A development is a linear image with the dynamic range of the scene: a light hundreds of times brighter than the walls it lights, and the glare around it.  A
+ * display takes [0, 1] through a transfer function.  Three stages take one to the other: METER counts what the image holds, LOCAL compresses its large-scale
+ * contrast and keeps the detail, TONE applies channel gains, a matrix and a curve.  What to aim for -- the exposure, the white point, the curve -- is the hosts'
+ * policy (include/ssx_host.h: ssh_meter_derive, ssh_tone_curve, ssh_display_matrix); this library takes any numbers.  NO log, exp OR pow RUNS ON THE DEVICE: the
+ * logarithm is the integer one a binary32's bit pattern already is, the curve with the display's transfer function is the caller's table, counts are integers.
+ * So every output has the bits of a restatement in numpy (tests/display_ref.py), not "within a bound".
+ *
+ * Binary32 IEEE in the order written, every product rounded before the add, no contraction, no reassociation; max(a, b) is a > b ? a : b and min(a, b) is
+ * a < b ? a : b (a NaN a gives b); / is correctly rounded, floorf is exact; bits(x) is x's pattern as uint32, frombits its inverse.  Images are row-major, row
+ * 0 = bottom.  Luminance of a pixel x[3]:   y = ((0.0f + x[0] * luma[0]) + x[1] * luma[1]) + x[2] * luma[2];   luma[3] finite.
+ *
+ * METER.  img[H][W][3], luma, mask (uint8 [H][W] or NULL; 0 = the pixel is not counted) -> hist uint32 [4][SSX_METER_KEYS], special uint32 [4][4].  The
+ *   quantities are k = 0 .. 2, the channels, and k = 3, y.  For a counted pixel's value x with u = bits(x):
+ *       x == +-0 -> special[k][0];   a NaN -> special[k][3];   else negative (-inf too) -> special[k][1];   +inf -> special[k][2];   else hist[k][u >> 19] += 1
+ *   sixteen keys per octave (the exponent and the top four bits of the significand), subnormals in keys 0 .. 15; keys 4080 and above stay 0.  Key K's lower edge
+ *   is frombits(K << 19).  Counts are integers (modulo 2^32: an image has at most 2^28 pixels), so any order of addition gives these numbers.
+ * LOCAL.  img, luma, ssx_local_params -> gain[H][W] and, where asked for, base[H][W].  Per pixel
+ *       yc = min(max(y * exposure, y_lo), y_hi)                                     a NaN gives y_lo; y_lo <= y_hi are positive, normal and finite
+ *       L  = (float)((int32)(bits(yc) >> 7) - 8323072) * 0x1p-16f                  the piecewise-linear log2: exponent - 127 + the top 16 bits of the fraction; exact
+ *   then the self-guided filter of He, Sun and Tang ("Guided image filtering", ECCV 2010) on L, radius r = 1 .. SSX_LOCAL_MAX_RADIUS, n = (float)((2r+1) * (2r+1)),
+ *   the window's coordinates clamped to the image (the count stays n), c(k, n) = min(max(k, 0), n - 1):
+ *       box(P)[j][i]:   h[j][i] = 0.0f, then for dx = -r .. r ascending   h = h + P[j][c(i + dx, W)];      s[j][i] = 0.0f, then for dy = -r .. r ascending   s = s + h[c(j + dy, H)][i]
+ *       S1 = box(L);   S2 = box(LL), LL[j][i] = (L * L) rounded
+ *       m = S1 / n;   v = max(S2 / n - (m * m), 0.0f);   a = v / (v + eps);   b = m - (a * m)                 eps finite and positive
+ *       A = box(a) / n;   Bm = box(b) / n;   base = (A * L) + Bm
+ *   and the compression about a pivot, with detail kept:
+ *       t = ((base - pivot) * compress) + pivot;   Lo = t + ((L - base) * boost);   gain = E(Lo - L)
+ *       E(d):   f = floorf(d * 65536.0f);   f = min(max(f, -16777216.0f), 16777216.0f)  (a NaN gives the lower bound);   frombits(min(max((int32)f + 8323072, 0x10000), 0xFEFFFF) << 7)
+ *   E is L's inverse: E(L(y)) is y with its low 7 bits cleared, and a gain is always a positive normal number.  The clamp in binary32 in front of the conversion is
+ *   there because an int32 conversion of a NaN or of 2^31 is nobody's definition; pivot, compress and boost need only be finite.  compress = boost = 1 gives gain = 1.
+ * TONE.  img, local[H][W] or NULL, ssx_tone_params -> out[H][W][3].  Per pixel, for c = 0 .. 2:   v[c] = img[c] * gains[c];   with local:   v[c] = v[c] * local[j][i];
+ *       x[c'] = ((0.0f + v[0] * matrix[c'][0]) + v[1] * matrix[c'][1]) + v[2] * matrix[c'][2]
+ *       xc = min(max(x, lo), hi);   k = bits(xc) - bits(lo);   idx = k >> shift;   f = (float)(k & ((1u << shift) - 1u)) * 2^-shift          (exact)
+ *       out = curve[idx] + ((curve[idx + 1] - curve[idx]) * f)
+ *   The table has curve_len = ((bits(hi) - bits(lo)) >> shift) + 2 entries, at most SSX_TONE_MAX_CURVE; shift is 12 .. 23; lo <= hi are positive, normal and finite.
+ *   Node idx stands at frombits(bits(lo) + (idx << shift)): 2^(23 - shift) nodes per octave, interpolated linearly in the bit pattern (so linearly in x within an
+ *   octave).  A NaN, a negative value and -0 are taken at lo.  The table holds the tone curve and the display's transfer function composed (ssh_tone_curve); this
+ *   library takes any finite table, and does not clamp the result.
+ * SAME BITS: the numpy restatement, on every case of tests/display_cases.py (a zero may differ in sign where the arithmetic leaves that open to -0 + 0 orders:
+ *   none is known).  ssx_meter_images's counts are equal as integers.
+ *
+ * ON THE DEVICE (csrc/ssx_display.hip): ssx_meter_kernel keeps one quantity's 4096 + 4 counters in LDS per workgroup (16 KB: eight workgroups per CU), adds with
+ * integer LDS atomics -- equal keys of a wave are counted first and added once, two rounds, the rest lane by lane -- and flushes its non-zero counters with integer
+ * global atomics.  LOCAL is four launches of two kernels, rows then columns, twice, each staging its window through LDS with both planes in one pass; m, v, a, b
+ * end the first column pass, base, Lo and the gain the second.  ssx_tone_kernel is one lane per pixel with the table read through the caches.  A lane writes only
+ * its own output; no float atomics.  With the feature unused nothing is allocated and nothing is launched. */
+#define SSX_METER_KEYS 4096u
+#define SSX_LOCAL_MAX_RADIUS 32u
+#define SSX_TONE_MAX_CURVE 16384u
+typedef struct ssx_local_params {
+	uint32_t struct_size;      /* sizeof(ssx_local_params) */
+	uint32_t radius;           /* r, 1..SSX_LOCAL_MAX_RADIUS */
+	float exposure;            /* finite */
+	float y_lo, y_hi;          /* positive, normal, finite, y_lo <= y_hi */
+	float eps;                 /* finite, > 0: the variance of L (octaves squared) below which a window counts as flat */
+	float pivot;               /* finite: the L that keeps its place (the hosts pass L of the key value) */
+	float compress, boost;     /* finite: the factor on the base layer's distance from the pivot, and on the detail */
+} ssx_local_params;
+typedef struct ssx_tone_params {
+	uint32_t struct_size;      /* sizeof(ssx_tone_params) */
+	uint32_t shift;            /* 12..23 */
+	uint32_t curve_len;        /* ((bits(hi) - bits(lo)) >> shift) + 2, at most SSX_TONE_MAX_CURVE */
+	float lo, hi;              /* positive, normal, finite, lo <= hi */
+	float gains[3];            /* finite */
+	float matrix[9];           /* [c'][c], finite */
+	const float* curve;        /* [curve_len], finite */
+} ssx_tone_params;
+
+/* METER as a pure function of its arguments (needs no scene): img [height][width][3], luma [3], mask [height][width] or NULL -> hist [4][SSX_METER_KEYS],
+ * special [4][4].  SSX_ERR_ARG, with ssx_last_error naming the field: a NULL pointer (img, luma, hist, special), a luma entry that is not finite, an empty or too
+ * large image.  SSX_ERR_STATE: a render runs. */
+int ssx_meter_images(ssx_ctx* ctx, uint32_t width, uint32_t height, const float* img /* [H][W][3] */, const float* luma /* [3] */, const uint8_t* mask /* [H][W] or NULL */,
+                     uint32_t* hist /* [4][4096] */, uint32_t* special /* [4][4] */);
+/* LOCAL as a pure function of its arguments: img [height][width][3], luma [3] -> gain [height][width], base [height][width] or NULL.  SSX_ERR_ARG: a NULL pointer
+ * (img, luma, local, gain), a wrong struct_size, a radius outside 1..SSX_LOCAL_MAX_RADIUS, an exposure, pivot, compress or boost that is not finite, a y_lo or
+ * y_hi that is not a positive normal number, y_lo > y_hi, an eps that is not finite and positive, a luma entry that is not finite, an empty or too large image.
+ * SSX_ERR_STATE: a render runs. */
+int ssx_local_images(ssx_ctx* ctx, uint32_t width, uint32_t height, const float* img /* [H][W][3] */, const float* luma /* [3] */, const ssx_local_params* local,
+                     float* gain /* [H][W] */, float* base /* [H][W] or NULL */);
+/* TONE as a pure function of its arguments: img [height][width][3], local [height][width] or NULL -> out [height][width][3].  SSX_ERR_ARG: a NULL pointer (img,
+ * tone, curve, out), a wrong struct_size, a shift outside 12..23, a lo or hi that is not a positive normal number, lo > hi, a curve_len that is not the defined
+ * value or above SSX_TONE_MAX_CURVE, a gains, matrix or curve entry that is not finite, an empty or too large image.  SSX_ERR_STATE: a render runs. */
+int ssx_tone_images(ssx_ctx* ctx, uint32_t width, uint32_t height, const float* img /* [H][W][3] */, const float* local /* [H][W] or NULL */, const ssx_tone_params* tone,
+                    float* out /* [H][W][3] */);
+
 /* ---- Diagnostics for the parity tests (not part of the reference's interface) ---------------------
  * ssx_debug_eval runs one building block of the path kernel -- the same device function the kernel
  * inlines -- on n items, one per lane: `in` holds in_words 32-bit words per item, `out` receives

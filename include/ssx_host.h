@@ -237,6 +237,45 @@ int ssh_sensor_ccm(const float* cam, const float* target, uint32_t bins, float* 
  * *low = 380, *high = 730: an ssh_spectrum_t for ssh_develop_weights.  SSX_ERR_ARG: NULL, a channel above 2. */
 #define SSH_SENSOR_STANDIN_SAMPLES 71u
 int ssh_sensor_standin_curve(uint32_t channel, float* samples, float* low, float* high);
+/* ---- The policy of a display for ssx_meter_images / ssx_local_images / ssx_tone_images (ssx.h "Finishing a development for a display").  All of it binary64,
+ * rounded to binary32 once at the end. */
+/* What a metering says, from hist [4][SSX_METER_KEYS] and special [4][4] of ssx_meter_images.  Quantity 3 is the luminance.  Only the finite positive values (the
+ * histogram) are looked at; N_k is their number.
+ *   percentile(k, p): with rank = min(max(ceil(p * N_k), 1), N_k), the smallest key whose cumulative count reaches rank, as that key's LOWER EDGE
+ *     frombits(key << 19): at most one key (a sixteenth of its octave's start: 6.25 %) below the value a sort of the data finds at that rank.  N_k == 0 gives 0.
+ *     percentile_out [4][n_percentiles] for percentiles [n_percentiles] (each in 0..1); both may be NULL with n_percentiles == 0.
+ *   out [SSH_METER_OUT]:
+ *     [SSH_METER_LOG_AVERAGE]   the log-average of the luminance IN THE PIECEWISE-LINEAR LOGARITHM OF LOCAL, every value taken at its key's centre: with the
+ *                               integer S = sum of count * (2 key + 1), q = S div 2N, f = (S mod 2N) / 2N:  2^((q >> 4) - 127) * (1 + ((q & 15) + f) / 16) -- 127 + 1/32 less
+ *                               than the mean key over 16 is the mean L.  An image scaled by 2^k has every key moved by 16 k, so q moves by 16 k and f stays: its
+ *                               log-average is 2^k times this one EXACTLY (while nothing leaves the normal range).  0 without a finite positive luminance.
+ *     [SSH_METER_EXPOSURE]      key_value / log-average (1 where that is 0): the factor that puts the log-average on key_value, 0.18 by convention
+ *     [SSH_METER_WHITE]         percentile(3, white_percentile): the highlight that is to reach white;   [SSH_METER_WHITE_EXPOSED] the same times the exposure
+ *     [SSH_METER_PIVOT]         L(key_value) as LOCAL defines it: ssx_local_params.pivot
+ *     [SSH_METER_GREY + c]      grey-world channel gains: mean_1 / mean_c, the means taken with every value at its key's centre frombits((key << 19) + (1 << 18))
+ *     [SSH_METER_PATCH + c]     white-patch channel gains: percentile(1, white_percentile) / percentile(c, white_percentile)
+ *                               a gain whose numerator or denominator is 0 is 1; the gains multiply the image's own channels (TONE's gains): a white balance proper
+ *                               wants a development in linear RGB
+ *     [SSH_METER_COUNT]         N_3 as a float; the rest 0
+ * SSX_ERR_ARG: NULL, a key_value that is not finite and positive, a percentile outside 0..1, a result that is not finite in binary32. */
+enum { SSH_METER_LOG_AVERAGE = 0, SSH_METER_EXPOSURE = 1, SSH_METER_WHITE = 2, SSH_METER_WHITE_EXPOSED = 3, SSH_METER_PIVOT = 4, SSH_METER_GREY = 5, SSH_METER_PATCH = 8,
+       SSH_METER_COUNT = 11 };
+#define SSH_METER_OUT 16u
+int ssh_meter_derive(const uint32_t* hist, const uint32_t* special, double key_value, double white_percentile, const double* percentiles, uint32_t n_percentiles,
+                     float* percentile_out, float* out);
+/* curve_out [curve_len] of ssx_tone_params for lo, hi and shift: node idx stands at x = frombits(bits(lo) + (idx << shift)) (the last node may lie beyond hi) and holds
+ * oetf(min(max(t(x), 0), 1)), oetf the sRGB transfer function (v <= 0.0031308 ? 12.92 v : 1.055 v^(1/2.4) - 0.055, libm's pow), and t
+ *   SSH_TONE_CLIP      t = x
+ *   SSH_TONE_REINHARD  t = x (1 + x / white^2) / (1 + x)                      Reinhard et al. 2002, eq. 4: x == white gives 1
+ *   SSH_TONE_FILMIC    t = h(2 x) / h(white), h(x) = (x (A x + C B) + D E) / (x (A x + B) + D F) - E / F with A .15, B .5, C .1, D .2, E .02, F .3    (Hable 2010)
+ *                      HERE `white` IS HABLE'S W, the linear white of his curve, NOT the value that reaches 1: with his exposure bias of 2 that is x = white / 2, and
+ *                      everything above it is clipped.  Renderer.finish and the CLI pass the metered white point all the same: filmic gives its top octave to the clip.
+ * SSX_ERR_ARG: NULL, another kind, a white that is not finite and positive, lo, hi, shift or curve_len that ssx_tone_images would refuse. */
+enum { SSH_TONE_CLIP = 0, SSH_TONE_REINHARD = 1, SSH_TONE_FILMIC = 2 };
+int ssh_tone_curve(int kind, double white, float lo, float hi, uint32_t shift, float* curve_out, uint32_t curve_len);
+/* out [3][3], row-major: ssx_tone_params.matrix for an image in CIE XYZ -- the observer's XYZ -> linear sRGB (BT.709 primaries, the project's D65), the matrix
+ * ssh_xyza_to_srgba applies.  SSX_ERR_ARG: NULL; SSX_ERR_DATA / SSX_ERR_SCENE: the tables of data_dir. */
+int ssh_display_matrix(const char* data_dir, int observer, float* out);
 /* *spectrum = index (in desc->spectra) of the emission spectrum that all emissive materials of the scene share up to a scale.  SSX_ERR_SCENE, with the reason in
  * ssh_last_error, when two of them differ or none is emissive: what the CLI's --develop-relight refuses. */
 int ssh_emitter_spectrum(const ssx_scene_desc* desc, uint32_t* spectrum);

@@ -126,6 +126,24 @@ class SsxGlareParams(C.Structure):
 SSX_GLARE_MAX_RADIUS, SSX_GLARE_MAX_EXTENT = 256, 4096  # include/ssx.h
 
 
+class SsxLocalParams(C.Structure):
+    """ssx_local_params: the radius and the scales of LOCAL, the local tone map of a finish."""
+    _fields_ = [("struct_size", C.c_uint32), ("radius", C.c_uint32), ("exposure", C.c_float), ("y_lo", C.c_float), ("y_hi", C.c_float), ("eps", C.c_float),
+                ("pivot", C.c_float), ("compress", C.c_float), ("boost", C.c_float)]
+
+
+class SsxToneParams(C.Structure):
+    """ssx_tone_params: the channel gains, the matrix and the curve table of TONE."""
+    _fields_ = [("struct_size", C.c_uint32), ("shift", C.c_uint32), ("curve_len", C.c_uint32), ("lo", C.c_float), ("hi", C.c_float), ("gains", C.c_float * 3),
+                ("matrix", C.c_float * 9), ("curve", C.c_void_p)]
+
+
+SSX_METER_KEYS, SSX_LOCAL_MAX_RADIUS, SSX_TONE_MAX_CURVE = 4096, 32, 16384  # include/ssx.h
+SSH_TONE_CLIP, SSH_TONE_REINHARD, SSH_TONE_FILMIC = 0, 1, 2  # include/ssx_host.h
+(SSH_METER_LOG_AVERAGE, SSH_METER_EXPOSURE, SSH_METER_WHITE, SSH_METER_WHITE_EXPOSED, SSH_METER_PIVOT, SSH_METER_GREY, SSH_METER_PATCH, SSH_METER_COUNT,
+ SSH_METER_OUT) = 0, 1, 2, 3, 4, 5, 8, 11, 16
+
+
 class SshSpectrum(C.Structure):
     """ssh_spectrum_t: n uniform samples over [low, high] (include/ssx_host.h)."""
     _fields_ = [("samples", C.POINTER(C.c_float)), ("n", C.c_uint32), ("low", C.c_float), ("high", C.c_float)]
@@ -167,6 +185,7 @@ HIP_SYMBOLS = ["ssx_create", "ssx_destroy", "ssx_upload_scene", "ssx_render_star
                "ssx_defocus_images", "ssx_spectral_develop_lens",
                "ssx_sensor_images", "ssx_demosaic_images", "ssx_spectral_develop_sensor",
                "ssx_glare_images", "ssx_spectral_develop_glare",
+               "ssx_meter_images", "ssx_local_images", "ssx_tone_images",
                "ssx_debug_tile_mask", "ssx_debug_spectral_accumulate", "ssx_debug_fold", "ssx_debug_step",
                "ssx_debug_generate", "ssx_generate_info",
                "ssx_scene_traits", "ssx_render_traits", "ssx_switches_info"]
@@ -202,7 +221,8 @@ HOST_SYMBOLS = ["ssh_scene_create", "ssh_scene_create_ex", "ssh_scene_destroy", 
                 "ssh_delta_e_derive", "ssh_delta_e_save_csv", "ssh_develop_white",
                 "ssh_optics_lens", "ssh_defocus_thin_lens", "ssh_scene_vfov",
                 "ssh_sensor_bayer", "ssh_sensor_exposure", "ssh_sensor_ccm", "ssh_sensor_standin_curve",
-                "ssh_glare_plan", "ssh_glare_twiddles", "ssh_glare_aperture"]
+                "ssh_glare_plan", "ssh_glare_twiddles", "ssh_glare_aperture",
+                "ssh_meter_derive", "ssh_tone_curve", "ssh_display_matrix"]
 
 _hip = None
 _host = None
@@ -266,6 +286,9 @@ def host_lib():
         lib.ssh_glare_plan.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]
         lib.ssh_glare_twiddles.argtypes = [C.c_uint32, vp]
         lib.ssh_glare_aperture.argtypes = [C.c_uint32, C.c_float, C.c_float, C.c_double, C.c_int, C.c_double, C.c_double, C.c_double, C.c_uint32, vp, vp]
+        lib.ssh_meter_derive.argtypes = [vp, vp, C.c_double, C.c_double, vp, C.c_uint32, vp, vp]
+        lib.ssh_tone_curve.argtypes = [C.c_int, C.c_double, C.c_float, C.c_float, C.c_uint32, vp, C.c_uint32]
+        lib.ssh_display_matrix.argtypes = [C.c_char_p, C.c_int, vp]
         _host = lib
     return _host
 
@@ -469,6 +492,10 @@ def hip_lib():
         if not override or hasattr(lib, "ssx_glare_images"):  # veiling glare and diffraction: per-bin convolution by FFT
             lib.ssx_glare_images.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.POINTER(SsxGlareParams), vp]
             lib.ssx_spectral_develop_glare.argtypes = [vp, C.POINTER(SsxDenoiseParams), C.POINTER(SsxDefocusParams), C.POINTER(SsxOpticsParams), C.POINTER(SsxGlareParams), vp, C.c_uint32, vp, vp]
+        if not override or hasattr(lib, "ssx_meter_images"):  # finishing a development for a display: meter, local tone map, tone curve
+            lib.ssx_meter_images.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]
+            lib.ssx_local_images.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(SsxLocalParams), vp, vp]
+            lib.ssx_tone_images.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(SsxToneParams), vp]
         if not override or hasattr(lib, "ssx_spectral_moments_import"):  # the second moments through checkpoint and resume
             lib.ssx_spectral_moments_import.argtypes = [vp, C.POINTER(SsxSpectralInfo), vp]
         if not override or hasattr(lib, "ssx_debug_tile_mask"):  # the camera-ray pre-trace's tile masks, read back

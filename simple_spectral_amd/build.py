@@ -19,7 +19,7 @@ HIP_LIB_FORMAL = os.path.join(PKG, "libssx_hip_formal.so")
 HOST_LIB = os.path.join(PKG, "libssx_host.so")
 
 HIP_SRC = [os.path.join(PKG, "csrc", f) for f in ("ssx_api.hip",)]
-HIP_DEPS = [os.path.join(PKG, "csrc", f) for f in ("ssx_api.hip", "ssx_kernels.hip", "ssx_debug.hip", "ssx_progressive.hip", "ssx_spectral.hip", "ssx_spectral_stats.hip", "ssx_spectral_noise.hip", "ssx_spectral_compare.hip", "ssx_delta_e.hip", "ssx_denoise.hip", "ssx_develop.hip", "ssx_optics.hip", "ssx_defocus.hip", "ssx_sensor.hip", "ssx_glare.hip", "ssx_demod.hip", "ssx_pixel_grid.h", "ssx_blob.h", "ssx_exact.h", "ssx_lanestat.h", "ssx_pass1_gen.h", "ssx_jit.h", "ssx_pack.h", "ssx_rccl.h", "ssx_ddmath.h")] + [
+HIP_DEPS = [os.path.join(PKG, "csrc", f) for f in ("ssx_api.hip", "ssx_kernels.hip", "ssx_debug.hip", "ssx_progressive.hip", "ssx_spectral.hip", "ssx_spectral_stats.hip", "ssx_spectral_noise.hip", "ssx_spectral_compare.hip", "ssx_delta_e.hip", "ssx_denoise.hip", "ssx_develop.hip", "ssx_optics.hip", "ssx_defocus.hip", "ssx_sensor.hip", "ssx_glare.hip", "ssx_display.hip", "ssx_demod.hip", "ssx_pixel_grid.h", "ssx_blob.h", "ssx_exact.h", "ssx_lanestat.h", "ssx_pass1_gen.h", "ssx_jit.h", "ssx_pack.h", "ssx_rccl.h", "ssx_ddmath.h")] + [
     os.path.join(ROOT, "include", f) for f in ("ssx.h", "ssx_fmath.h", "ssx_glibc_math.h")]
 HOST_SRC = [os.path.join(PKG, "host", f) for f in
             ("spectrum.cpp", "color.cpp", "jh2019.cpp", "meng2015.cpp", "scene.cpp", "image_io.cpp", "renderer.cpp", "checkpoint.cpp", "develop.cpp", "host_api.cpp")]

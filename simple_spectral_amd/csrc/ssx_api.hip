@@ -163,6 +163,7 @@ struct ssx_ctx {
 	DeviceBuffer d_defocus;             // ssx_defocus_images / ssx_spectral_develop_lens (csrc/ssx_defocus.hip): output | a | inv | focus | distances (| the caller's bins and depth); nothing until a defocus runs
 	DeviceBuffer d_sensor;              // ssx_sensor_images / ssx_demosaic_images / ssx_spectral_develop_sensor (csrc/ssx_sensor.hip): the tables | raw | dn | out (| the caller's bins); nothing until one of them is called
 	DeviceBuffer d_glare;               // ssx_glare_images / ssx_spectral_develop_glare (csrc/ssx_glare.hip): the chunk's planes X | Kf | the packed twiddles | psf | out (| the caller's bins); nothing until a glare runs
+	DeviceBuffer d_display;             // ssx_meter_images / ssx_local_images / ssx_tone_images (csrc/ssx_display.hip): the caller's image | that entry's planes, counters or table; nothing until one of them is called
 	uint32_t guides_width = 0, guides_height = 0;
 	// demodulated denoising (csrc/ssx_demod.hip): nothing is allocated until ssx_albedo_bins or one of the two _demod entry points is called.  d_albedo_bins
 	// holds the albedo bins of the uploaded scene at abins_width x abins_height, abins_bins bins, abins_supersample^2 rays per pixel (0 x 0: none;
@@ -1784,6 +1785,7 @@ int ssx_kernel_info(ssx_ctx* ctx, int* vgprs, int* sgprs, int* lds_bytes, int* s
 #include "ssx_defocus.hip"
 #include "ssx_sensor.hip"
 #include "ssx_glare.hip"
+#include "ssx_display.hip"
 #include "ssx_demod.hip"
 #include "ssx_spectral_stats.hip"
 #include "ssx_spectral_noise.hip"

@@ -620,6 +620,100 @@ int ssh_defocus_thin_lens(float vfov_deg, uint32_t height, uint32_t bins, float 
 	return SSX_OK;
 }
 
+namespace {
+float display_frombits(uint32_t u) { float v; memcpy(&v, &u, sizeof v); return v; }
+uint32_t display_bits(float v) { uint32_t u; memcpy(&u, &v, sizeof u); return u; }
+// percentile(k, p) of ssx_host.h on one quantity's histogram
+double meter_percentile(const uint32_t* h, double p) {
+	uint64_t N = 0;
+	for (uint32_t k = 0; k < SSX_METER_KEYS; ++k) N += h[k];
+	if (!N) return 0.0;
+	double rank = std::ceil(p * static_cast<double>(N));
+	rank = std::min(std::max(rank, 1.0), static_cast<double>(N));
+	uint64_t cum = 0;
+	for (uint32_t k = 0; k < SSX_METER_KEYS; ++k) {
+		cum += h[k];
+		if (static_cast<double>(cum) >= rank) return static_cast<double>(display_frombits(k << 19));
+	}
+	return 0.0;
+}
+double meter_mean(const uint32_t* h) {
+	uint64_t N = 0; double s = 0.0;
+	for (uint32_t k = 0; k < 4080u; ++k) if (h[k]) { N += h[k]; s += static_cast<double>(h[k]) * static_cast<double>(display_frombits((k << 19) + (1u << 18))); }
+	return N ? s / static_cast<double>(N) : 0.0;
+}
+double srgb_oetf(double v) { return v <= 0.0031308 ? 12.92 * v : 1.055 * std::pow(v, 1.0 / 2.4) - 0.055; }
+double hable(double x) { const double A = 0.15, B = 0.50, C = 0.10, D = 0.20, E = 0.02, F = 0.30; return (x * (A * x + C * B) + D * E) / (x * (A * x + B) + D * F) - E / F; }
+} // namespace
+
+int ssh_meter_derive(const uint32_t* hist, const uint32_t* special, double key_value, double white_percentile, const double* percentiles, uint32_t n_percentiles,
+                     float* percentile_out, float* out) {
+	if (!hist || !special || !out || (n_percentiles && (!percentiles || !percentile_out))) { g_error = "NULL argument"; return SSX_ERR_ARG; }
+	if (!std::isfinite(key_value) || !(key_value > 0.0)) { g_error = "ssh_meter_derive: key_value must be finite and positive"; return SSX_ERR_ARG; }
+	if (!(white_percentile >= 0.0) || !(white_percentile <= 1.0)) { g_error = "ssh_meter_derive: white_percentile must lie in 0..1"; return SSX_ERR_ARG; }
+	for (uint32_t i = 0; i < n_percentiles; ++i)
+		if (!(percentiles[i] >= 0.0) || !(percentiles[i] <= 1.0)) { g_error = "ssh_meter_derive: percentiles[" + std::to_string(i) + "] must lie in 0..1"; return SSX_ERR_ARG; }
+	for (uint32_t k = 0; k < 4u; ++k)
+		for (uint32_t i = 0; i < n_percentiles; ++i) percentile_out[k * n_percentiles + i] = static_cast<float>(meter_percentile(hist + k * SSX_METER_KEYS, percentiles[i]));
+	const uint32_t* const hy = hist + 3u * SSX_METER_KEYS;
+	uint64_t N = 0, S = 0;
+	for (uint32_t k = 0; k < SSX_METER_KEYS; ++k) { N += hy[k]; S += static_cast<uint64_t>(hy[k]) * (2u * k + 1u); }
+	double log_average = 0.0;
+	if (N) {
+		const uint64_t q = S / (2u * N);
+		const double f = static_cast<double>(S % (2u * N)) / static_cast<double>(2u * N);
+		log_average = std::ldexp(1.0 + (static_cast<double>(q & 15u) + f) / 16.0, static_cast<int>(q >> 4) - 127);
+	}
+	const double exposure = log_average > 0.0 ? key_value / log_average : 1.0;
+	const double white = meter_percentile(hy, white_percentile);
+	for (uint32_t i = 0; i < SSH_METER_OUT; ++i) out[i] = 0.0f;
+	out[SSH_METER_LOG_AVERAGE] = static_cast<float>(log_average);
+	out[SSH_METER_EXPOSURE] = static_cast<float>(exposure);
+	out[SSH_METER_WHITE] = static_cast<float>(white);
+	out[SSH_METER_WHITE_EXPOSED] = static_cast<float>(white * exposure);
+	const float kf = static_cast<float>(key_value);
+	out[SSH_METER_PIVOT] = std::isnormal(kf) ? static_cast<float>(static_cast<int32_t>(display_bits(kf) >> 7) - 8323072) * 0x1p-16f : 0.0f;
+	double mean[3], patch[3];
+	for (uint32_t c = 0; c < 3u; ++c) { mean[c] = meter_mean(hist + c * SSX_METER_KEYS); patch[c] = meter_percentile(hist + c * SSX_METER_KEYS, white_percentile); }
+	for (uint32_t c = 0; c < 3u; ++c) {
+		out[SSH_METER_GREY + c] = static_cast<float>(mean[1] > 0.0 && mean[c] > 0.0 ? mean[1] / mean[c] : 1.0);
+		out[SSH_METER_PATCH + c] = static_cast<float>(patch[1] > 0.0 && patch[c] > 0.0 ? patch[1] / patch[c] : 1.0);
+	}
+	out[SSH_METER_COUNT] = static_cast<float>(N);
+	for (uint32_t i = 0; i < SSH_METER_OUT; ++i) if (!std::isfinite(out[i])) { g_error = "ssh_meter_derive: a result is not finite in binary32"; return SSX_ERR_ARG; }
+	return SSX_OK;
+}
+
+int ssh_tone_curve(int kind, double white, float lo, float hi, uint32_t shift, float* curve_out, uint32_t curve_len) {
+	if (!curve_out) { g_error = "NULL argument"; return SSX_ERR_ARG; }
+	if (kind != SSH_TONE_CLIP && kind != SSH_TONE_REINHARD && kind != SSH_TONE_FILMIC) { g_error = "ssh_tone_curve: kind must be SSH_TONE_CLIP, SSH_TONE_REINHARD or SSH_TONE_FILMIC"; return SSX_ERR_ARG; }
+	if (!std::isfinite(white) || !(white > 0.0)) { g_error = "ssh_tone_curve: white must be finite and positive"; return SSX_ERR_ARG; }
+	if (shift < 12u || shift > 23u) { g_error = "ssh_tone_curve: shift must be 12..23"; return SSX_ERR_ARG; }
+	if (!std::isnormal(lo) || !std::isnormal(hi) || !(lo > 0.0f) || !(hi >= lo)) { g_error = "ssh_tone_curve: lo and hi must be positive normal numbers, lo <= hi"; return SSX_ERR_ARG; }
+	const uint32_t len = ((display_bits(hi) - display_bits(lo)) >> shift) + 2u;
+	if (len > SSX_TONE_MAX_CURVE || curve_len != len) { g_error = "ssh_tone_curve: lo, hi and shift define a curve_len of " + std::to_string(len) + " (at most " + std::to_string(SSX_TONE_MAX_CURVE) + ")"; return SSX_ERR_ARG; }
+	const double hw = hable(white);
+	for (uint32_t idx = 0; idx < len; ++idx) {
+		const uint32_t u = display_bits(lo) + (idx << shift);
+		const double x = u < 0x7F800000u ? static_cast<double>(display_frombits(u)) : static_cast<double>(hi);
+		double t = x;
+		if (kind == SSH_TONE_REINHARD) t = x * (1.0 + x / (white * white)) / (1.0 + x);
+		else if (kind == SSH_TONE_FILMIC) t = hable(2.0 * x) / hw;
+		curve_out[idx] = static_cast<float>(srgb_oetf(std::min(std::max(t, 0.0), 1.0)));
+	}
+	return SSX_OK;
+}
+
+int ssh_display_matrix(const char* data_dir, int observer, float* out) {
+	if (!data_dir || !out) { g_error = "NULL argument"; return SSX_ERR_ARG; }
+	try {
+		const ssx::ColorData color(data_dir, observer);
+		for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) out[3 * r + c] = color.matr_xyz_to_lrgb.m[c][r];
+		return SSX_OK;
+	} catch (const ssx::HostError& e) { return report(e); }
+	catch (const std::exception& e) { g_error = e.what(); return SSX_ERR_DATA; }
+}
+
 int ssh_emitter_spectrum(const ssx_scene_desc* desc, uint32_t* spectrum) {
 	if (!desc || !spectrum) { g_error = "NULL argument"; return SSX_ERR_ARG; }
 	try { *spectrum = ssx::emitter_spectrum(*desc); return SSX_OK; }

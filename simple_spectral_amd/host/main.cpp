@@ -116,6 +116,10 @@ void print_usage() {
 		"          (veiling glare and diffraction behind the lens: every bin convolved with the far-field pattern of an iris of <blades> blades (fewer than 3: a\n"
 		"           disc), a disc's first dark ring <ring_px> pixels out at <lambda_ref> and growing with the wavelength, <strength> of the light leaving the\n"
 		"           geometric image, the iris turned by <rotation> radians; sides as for `--develop-lens`)\n"
+		"    [`--develop-display=clip|reinhard|filmic[,<key=0.18>[,<white_percentile=0.99>]]`] [`--develop-display-local=<radius 1..32>,<compress>[,<boost=1>[,<eps=0.25>]]`]\n"
+		"    [`--develop-display-wb=none|grey|white-patch`] [`--meter-output=<hist.csv>`]\n"
+		"          (finish `--develop-output` for a display: the image is metered, exposed for a log-average of <key>, its <white_percentile> taken as white, large-scale\n"
+		"           contrast compressed about the key with detail kept, and a tone curve with the sRGB transfer function applied; `--meter-output` writes the metering)\n"
 		"    [`--develop-defocus=<aperture>,<focus_distance>[,<axial=0>[,<lambda_ref=550>]]`] [`--develop-defocus-radius=<0..12, default 8>`] [`--delta-e-defocus=...`]\n"
 		"          (depth of field from the depth guide before the lens: an aperture of diameter <aperture> focused at <focus_distance>, both in scene units, the\n"
 		"           inverse focus distance moving by <axial> per relative wavelength offset; sides as for `--develop-lens`)\n"
@@ -231,6 +235,11 @@ struct Progressive { // the flags of the progressive modes
 	struct Iris { bool on = false; int blades = 0; double ring_px = 1.0, strength = 0.0, rotation = 0.0, lambda_ref = 550.0; };
 	Iris develop_glare, delta_e_glare;
 	unsigned develop_glare_radius = 64;
+	// the finish for a display (include/ssx.h "Finishing a development for a display"): --develop-display=clip|reinhard|filmic[,key[,white_percentile]],
+	// --develop-display-local=radius,compress[,boost[,eps]], --develop-display-wb=none|grey|white-patch, --meter-output=hist.csv
+	bool display_on = false;
+	ssx::Renderer::Display display;
+	std::string meter_output;
 	// the sensor (include/ssx.h "Developing onto a sensor"): --develop-sensor=PATTERN[,mhc|bilinear], --develop-sensor-curves=R.csv,G.csv,B.csv (also on its own: an
 	// ordinary develop with a camera's curves), --develop-sensor-exposure=full_well,white_level, --develop-sensor-noise=read_e[,seed], --develop-sensor-bits=N[,black],
 	// --sensor-raw-output=raw.npy
@@ -447,6 +456,58 @@ void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progress
 		g->develop_glare_radius = static_cast<unsigned>(r);
 		glare_radius_given = true;
 	}
+	{ // the display's options
+		auto numbers = [&](const std::string& text, double* x, size_t most) { // comma-separated finite numbers: how many, or 0 for a malformed list
+			size_t n = 0, at = 0;
+			try {
+				for (;;) {
+					if (n == most) return static_cast<size_t>(0);
+					const size_t comma = text.find(',', at);
+					const std::string part = text.substr(at, comma == std::string::npos ? std::string::npos : comma - at);
+					size_t used = 0;
+					x[n++] = std::stod(part, &used);
+					if (used != part.size() || !std::isfinite(x[n - 1])) return static_cast<size_t>(0);
+					if (comma == std::string::npos) return n;
+					at = comma + 1;
+				}
+			} catch (...) { return static_cast<size_t>(0); }
+		};
+		bool local_given = false, wb_given = false;
+		if (a.take("--develop-display", "", &v)) {
+			const size_t comma = v.find(',');
+			const std::string kind = v.substr(0, comma);
+			double x[2] = { 0.18, 0.99 };
+			const bool ok = comma == std::string::npos || numbers(v.substr(comma + 1), x, 2) != 0;
+			if (!ok || (kind != "clip" && kind != "reinhard" && kind != "filmic") || !(x[0] > 0.0) || x[1] < 0.0 || x[1] > 1.0) {
+				std::fprintf(stderr, "Invalid value for --develop-display (clip|reinhard|filmic[,<key>[,<white_percentile>]]: key finite and > 0, white_percentile 0..1)!\n");
+				throw -2;
+			}
+			g->display_on = true;
+			g->display.curve = kind == "clip" ? SSH_TONE_CLIP : (kind == "reinhard" ? SSH_TONE_REINHARD : SSH_TONE_FILMIC);
+			g->display.key = x[0]; g->display.white_percentile = x[1];
+		}
+		if (a.take("--develop-display-local", "", &v)) {
+			double x[4] = { 0.0, 0.0, 1.0, 0.25 };
+			const size_t n = numbers(v, x, 4);
+			if (n < 2 || x[0] < 1.0 || x[0] > static_cast<double>(SSX_LOCAL_MAX_RADIUS) || x[0] != std::floor(x[0]) || !std::isfinite(static_cast<float>(x[1])) ||
+			    !std::isfinite(static_cast<float>(x[2])) || !std::isfinite(static_cast<float>(x[3])) || !(static_cast<float>(x[3]) > 0.0f)) {
+				std::fprintf(stderr, "Invalid value for --develop-display-local (<radius>,<compress>[,<boost>[,<eps>]]: finite, radius an integer 1..32, eps > 0)!\n");
+				throw -2;
+			}
+			g->display.local = true; g->display.radius = static_cast<uint32_t>(x[0]);
+			g->display.compress = static_cast<float>(x[1]); g->display.boost = static_cast<float>(x[2]); g->display.eps = static_cast<float>(x[3]);
+			local_given = true;
+		}
+		if (a.take("--develop-display-wb", "", &v)) {
+			if (v == "none") g->display.wb = ssx::Renderer::WhiteBalance::None;
+			else if (v == "grey") g->display.wb = ssx::Renderer::WhiteBalance::Grey;
+			else if (v == "white-patch") g->display.wb = ssx::Renderer::WhiteBalance::WhitePatch;
+			else { std::fprintf(stderr, "Invalid value for --develop-display-wb (none|grey|white-patch)!\n"); throw -2; }
+			wb_given = true;
+		}
+		if (a.take("--meter-output", "", &v)) g->meter_output = v;
+		if ((local_given || wb_given) && !g->display_on) { std::fprintf(stderr, "`--develop-display-local` and `--develop-display-wb` need `--develop-display=clip|reinhard|filmic`!\n"); throw -2; }
+	}
 	{ // the sensor's options
 		auto split = [](const std::string& s) {
 			std::vector<std::string> parts;
@@ -566,6 +627,10 @@ void parse_arguments(int argc, char* argv[], ssx::Renderer::Options* o, Progress
 	}
 	if (g->develop_output.empty() && !g->delta_e() && (!g->develop_filter.empty() || !g->develop_relight.empty() || g->develop_observer || g->develop_lens.on || g->develop_defocus.on || !g->sensor.curves.empty())) {
 		std::fprintf(stderr, "`--develop-observer`, `--develop-filter`, `--develop-relight`, `--develop-lens`, `--develop-defocus` and `--develop-sensor-curves` need `--develop-output=<image>`!\n");
+		throw -2;
+	}
+	if ((g->display_on || !g->meter_output.empty()) && g->develop_output.empty()) {
+		std::fprintf(stderr, "`--develop-display` and `--meter-output` need `--develop-output=<image>`: they finish and meter the image written there!\n");
 		throw -2;
 	}
 	if (g->develop_glare.on && g->develop_output.empty() && !g->delta_e()) { std::fprintf(stderr, "`--develop-glare` needs `--develop-output=<image>`!\n"); throw -2; }
@@ -738,6 +803,25 @@ namespace {
 volatile std::sig_atomic_t g_abort = 0;
 void on_sigint(int) { g_abort = 1; }
 } // namespace
+
+// --meter-output: the line "quantity,key,lower_edge,count", then one line per non-zero counter -- quantity 0..2 the channels, 3 the luminance; key 0..4095 with
+// its lower edge frombits(key << 19) (%.9g), or one of zero, negative, inf, nan with an empty edge
+static void save_meter_csv(const std::string& path, const ssx::Renderer::Meter& m) {
+	FILE* const f = std::fopen(path.c_str(), "w");
+	if (!f) throw ssx::HostError{ SSX_ERR_DATA, "cannot write " + path };
+	std::fprintf(f, "quantity,key,lower_edge,count\n");
+	static const char* const classes[4] = { "zero", "negative", "inf", "nan" };
+	for (uint32_t k = 0; k < 4u; ++k) {
+		for (uint32_t key = 0; key < SSX_METER_KEYS; ++key) {
+			const uint32_t n = m.hist[k * SSX_METER_KEYS + key];
+			if (!n) continue;
+			const uint32_t u = key << 19; float edge; std::memcpy(&edge, &u, sizeof edge);
+			std::fprintf(f, "%u,%u,%.9g,%u\n", k, key, static_cast<double>(edge), n);
+		}
+		for (uint32_t c = 0; c < 4u; ++c) if (m.special[k * 4u + c]) std::fprintf(f, "%u,%s,,%u\n", k, classes[c], m.special[k * 4u + c]);
+	}
+	std::fclose(f);
+}
 
 int main(int argc, char* argv[]) {
 	ssx::Renderer::Options options;
@@ -1001,11 +1085,31 @@ int main(int argc, char* argv[]) {
 			} else if (glare_a) xyz = renderer.develop_glare(develop_weights.data(), 3, *glare_a, prog.spectral_denoise ? &prog.denoise_params : nullptr, prog.demodulate ? &prog.demod_params : nullptr, optics_a, defocus_a);
 			else xyz = renderer.develop(develop_weights.data(), 3, prog.spectral_denoise ? &prog.denoise_params : nullptr, prog.demodulate ? &prog.demod_params : nullptr, optics_a, defocus_a);
 			const size_t pixels = options.res[0] * options.res[1];
-			std::vector<float> xyza(pixels * 4);
-			for (size_t p = 0; p < pixels; ++p) { xyza[4 * p] = xyz[3 * p]; xyza[4 * p + 1] = xyz[3 * p + 1]; xyza[4 * p + 2] = xyz[3 * p + 2]; xyza[4 * p + 3] = renderer.xyza[4 * p + 3]; }
 			ssx::Framebuffer fb(options.res);
-			develop_color->xyza_to_srgba(xyza.data(), fb.data(), pixels);
-			fb.save(prog.develop_output);
+			if (prog.display_on || !prog.meter_output.empty()) { // X, Y, Z -> linear sRGB is the finish's matrix (row-major [c'][c]; Mat3 is m[col][row])
+				ssx::Renderer::Display display = prog.display;
+				for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) display.matrix[3 * r + c] = develop_color->matr_xyz_to_lrgb.m[c][r];
+				if (prog.display_on) { // already display-encoded: it goes to the store of --output as it is, past the observer's matrix and transfer function
+					ssx::Renderer::Meter meter;
+					const std::vector<float> finished = renderer.finish(xyz.data(), display, &meter);
+					if (!prog.meter_output.empty()) save_meter_csv(prog.meter_output, meter);
+					for (size_t p = 0; p < pixels; ++p) {
+						for (int c = 0; c < 3; ++c) fb.data()[4 * p + c] = finished[3 * p + c];
+						fb.data()[4 * p + 3] = renderer.xyza[4 * p + 3];
+					}
+					fb.save(prog.develop_output);
+				} else { // --meter-output alone: the metering a finish would start with, nothing else
+					float luma[3];
+					ssx::Renderer::display_luma(display.matrix, luma);
+					save_meter_csv(prog.meter_output, renderer.meter_images(xyz.data(), luma));
+				}
+			}
+			if (!prog.display_on) {
+				std::vector<float> xyza(pixels * 4);
+				for (size_t p = 0; p < pixels; ++p) { xyza[4 * p] = xyz[3 * p]; xyza[4 * p + 1] = xyz[3 * p + 1]; xyza[4 * p + 2] = xyz[3 * p + 2]; xyza[4 * p + 3] = renderer.xyza[4 * p + 3]; }
+				develop_color->xyza_to_srgba(xyza.data(), fb.data(), pixels);
+				fb.save(prog.develop_output);
+			}
 		}
 		if (!prog.checkpoint.empty()) renderer.save_checkpoint(prog.checkpoint);
 	} catch (const ssx::HostError& e) {

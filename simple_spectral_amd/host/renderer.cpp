@@ -3,6 +3,7 @@
 #include "checkpoint.hpp"
 #include "develop.hpp"
 #include "image_io.hpp"
+#include "../../include/ssx_host.h"
 
 #include <dlfcn.h>
 
@@ -34,7 +35,8 @@ void Framebuffer::save(const std::string& path) const { save_image(path, pixels_
 	X(render_continue) X(sums_export) X(sums_import) X(set_noise_estimate) X(noise_info) \
 	X(set_spectral_bins) X(spectral_read) X(spectral_import) X(set_spectral_moments) X(spectral_variance) X(spectral_moments_import) X(spectral_probe) X(probe_arrays) X(spectral_noise) X(spectral_noise_reduce) X(spectral_compare) X(spectral_compare_arrays) X(delta_e_images) X(spectral_delta_e) \
 	X(guides) X(denoise_images) X(denoise) X(denoise_channels) X(denoise_spectral) \
-	X(develop_images) X(spectral_develop) X(albedo_bins) X(denoise_spectral_demod) X(spectral_develop_demod) X(optics_images) X(spectral_develop_optics) X(defocus_images) X(spectral_develop_lens) X(sensor_images) X(demosaic_images) X(spectral_develop_sensor) X(glare_images) X(spectral_develop_glare)
+	X(develop_images) X(spectral_develop) X(albedo_bins) X(denoise_spectral_demod) X(spectral_develop_demod) X(optics_images) X(spectral_develop_optics) X(defocus_images) X(spectral_develop_lens) X(sensor_images) X(demosaic_images) X(spectral_develop_sensor) X(glare_images) X(spectral_develop_glare) \
+	X(meter_images) X(local_images) X(tone_images)
 
 struct Renderer::Api {
 	void* handle = nullptr;
@@ -927,6 +929,73 @@ ssx_glare_params to_abi(const Renderer::Glare& g, size_t B) {
 	return p;
 }
 } // namespace
+
+Renderer::Meter Renderer::meter_images(const float* img, const float luma[3], const uint8_t* mask) {
+	wait_workers_();
+	Meter m;
+	m.hist.assign(4u * SSX_METER_KEYS, 0u); m.special.assign(16u, 0u);
+	check_(api_->meter_images(ctxs_[0], w32_(), h32_(), img, luma, mask, m.hist.data(), m.special.data()), "ssx_meter_images", ctxs_[0]);
+	return m;
+}
+
+std::vector<float> Renderer::local_images(const float* img, const float luma[3], const Local& local, std::vector<float>* base) {
+	wait_workers_();
+	const size_t pixels = options.res[0] * options.res[1];
+	ssx_local_params p{};
+	p.struct_size = sizeof p; p.radius = local.radius; p.exposure = local.exposure; p.y_lo = local.y_lo; p.y_hi = local.y_hi; p.eps = local.eps;
+	p.pivot = local.pivot; p.compress = local.compress; p.boost = local.boost;
+	std::vector<float> gain(pixels);
+	if (base) base->assign(pixels, 0.0f);
+	check_(api_->local_images(ctxs_[0], w32_(), h32_(), img, luma, &p, gain.data(), base ? base->data() : nullptr), "ssx_local_images", ctxs_[0]);
+	return gain;
+}
+
+std::vector<float> Renderer::tone_images(const float* img, const Tone& tone, const float* local) {
+	wait_workers_();
+	const size_t pixels = options.res[0] * options.res[1];
+	ssx_tone_params p{};
+	p.struct_size = sizeof p; p.shift = tone.shift; p.curve_len = static_cast<uint32_t>(tone.curve.size()); p.lo = tone.lo; p.hi = tone.hi;
+	for (int c = 0; c < 3; ++c) p.gains[c] = tone.gains[c];
+	for (int k = 0; k < 9; ++k) p.matrix[k] = tone.matrix[k];
+	p.curve = tone.curve.data();
+	std::vector<float> out(pixels * 3);
+	check_(api_->tone_images(ctxs_[0], w32_(), h32_(), img, local, &p, out.data()), "ssx_tone_images", ctxs_[0]);
+	return out;
+}
+
+void Renderer::display_luma(const float matrix[9], float luma[3]) {
+	for (int c = 0; c < 3; ++c)
+		luma[c] = static_cast<float>((0.2126 * static_cast<double>(matrix[c]) + 0.7152 * static_cast<double>(matrix[3 + c])) + 0.0722 * static_cast<double>(matrix[6 + c]));
+}
+
+std::vector<float> Renderer::finish(const float* img, const Display& d, Meter* meter) {
+	float luma[3];
+	display_luma(d.matrix, luma);
+	Meter m = meter_images(img, luma);
+	float out[SSH_METER_OUT];
+	if (ssh_meter_derive(m.hist.data(), m.special.data(), d.key, d.white_percentile, nullptr, 0, nullptr, out) != SSX_OK) throw HostError{ SSX_ERR_ARG, std::string("finish: ") + ssh_last_error() };
+	Tone tone;
+	for (int c = 0; c < 3; ++c) {
+		const float wb = d.wb == WhiteBalance::Grey ? out[SSH_METER_GREY + c] : (d.wb == WhiteBalance::WhitePatch ? out[SSH_METER_PATCH + c] : 1.0f);
+		tone.gains[c] = out[SSH_METER_EXPOSURE] * wb;
+	}
+	for (int k = 0; k < 9; ++k) tone.matrix[k] = d.matrix[k];
+	std::vector<float> gain;
+	if (d.local) {
+		Local l;
+		l.radius = d.radius; l.compress = d.compress; l.boost = d.boost; l.eps = d.eps; l.exposure = out[SSH_METER_EXPOSURE]; l.pivot = out[SSH_METER_PIVOT];
+		gain = local_images(img, luma, l);
+	}
+	uint32_t lo_bits, hi_bits;
+	std::memcpy(&lo_bits, &tone.lo, 4); std::memcpy(&hi_bits, &tone.hi, 4);
+	tone.curve.assign(((hi_bits - lo_bits) >> tone.shift) + 2u, 0.0f);
+	const double white = out[SSH_METER_WHITE_EXPOSED] > 0.0f ? static_cast<double>(out[SSH_METER_WHITE_EXPOSED]) : 1.0;
+	if (ssh_tone_curve(d.curve, white, tone.lo, tone.hi, tone.shift, tone.curve.data(), static_cast<uint32_t>(tone.curve.size())) != SSX_OK)
+		throw HostError{ SSX_ERR_ARG, std::string("finish: ") + ssh_last_error() };
+	std::vector<float> result = tone_images(img, tone, d.local ? gain.data() : nullptr);
+	if (meter) *meter = std::move(m);
+	return result;
+}
 
 std::vector<float> Renderer::glare_images(const float* q, const Glare& glare) {
 	wait_workers_();

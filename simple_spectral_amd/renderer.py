@@ -532,6 +532,92 @@ def sensor_standin_curves():
     return out
 
 
+def tone_curve_len(lo, hi, shift):
+    """curve_len of ssx_tone_params (include/ssx.h): ((bits(hi) - bits(lo)) >> shift) + 2."""
+    b = np.array([lo, hi], dtype=np.float32).view(np.uint32)
+    return ((int(b[1]) - int(b[0])) >> int(shift)) + 2
+
+
+def meter_derive(hist, special, key=0.18, white_percentile=0.99, percentiles=()):
+    """ssh_meter_derive (include/ssx_host.h): what a metering (Renderer.meter_images) says -- {"log_average", "exposure" (puts the log-average on `key`), "white" (the
+    luminance's white_percentile, a key's lower edge), "white_exposed", "pivot" (L of `key`, for LOCAL), "grey" and "patch" (float32 [3]: grey-world and white-patch
+    channel gains), "count", "percentiles" (float32 [4, len(percentiles)]: the channels' and the luminance's)}."""
+    hist = np.ascontiguousarray(hist, dtype=np.uint32)
+    special = np.ascontiguousarray(special, dtype=np.uint32)
+    if hist.shape != (4, _capi.SSX_METER_KEYS) or special.shape != (4, 4):
+        raise ValueError("meter_derive: hist must have shape [4, 4096], special [4, 4]")
+    pc = np.ascontiguousarray(percentiles, dtype=np.float64).reshape(-1)
+    po = np.zeros((4, pc.size), dtype=np.float32)
+    out = np.zeros(_capi.SSH_METER_OUT, dtype=np.float32)
+    _host("ssh_meter_derive", hist.ctypes.data, special.ctypes.data, float(key), float(white_percentile), pc.ctypes.data if pc.size else None, pc.size,
+          po.ctypes.data if pc.size else None, out.ctypes.data)
+    return {"log_average": out[_capi.SSH_METER_LOG_AVERAGE], "exposure": out[_capi.SSH_METER_EXPOSURE], "white": out[_capi.SSH_METER_WHITE],
+            "white_exposed": out[_capi.SSH_METER_WHITE_EXPOSED], "pivot": out[_capi.SSH_METER_PIVOT], "grey": out[_capi.SSH_METER_GREY:_capi.SSH_METER_GREY + 3].copy(),
+            "patch": out[_capi.SSH_METER_PATCH:_capi.SSH_METER_PATCH + 3].copy(), "count": out[_capi.SSH_METER_COUNT], "percentiles": po}
+
+
+TONE_CURVES = {"clip": _capi.SSH_TONE_CLIP, "reinhard": _capi.SSH_TONE_REINHARD, "filmic": _capi.SSH_TONE_FILMIC}
+
+
+def tone_curve(kind, lo, hi, shift, white=1.0):
+    """ssh_tone_curve: float32 [tone_curve_len(lo, hi, shift)], the tone curve `kind` ("clip", "reinhard" with its white point, "filmic") composed with the sRGB
+    transfer function, one entry per node of ssx_tone_params' table."""
+    if kind not in TONE_CURVES:
+        raise ValueError("tone_curve: kind must be one of %s" % ", ".join(sorted(TONE_CURVES)))
+    n = tone_curve_len(lo, hi, shift)
+    out = np.zeros(max(n, 0), dtype=np.float32)
+    _host("ssh_tone_curve", TONE_CURVES[kind], float(white), float(lo), float(hi), int(shift), out.ctypes.data, n & 0xFFFFFFFF)
+    return out
+
+
+def display_matrix(observer=1931, data_dir=DEFAULT_DATA_DIR):
+    """ssh_display_matrix: float32 [3, 3], XYZ -> linear sRGB: ssx_tone_params.matrix for a development in CIE XYZ."""
+    out = np.zeros((3, 3), dtype=np.float32)
+    _host("ssh_display_matrix", data_dir.encode(), int(observer), out.ctypes.data)
+    return out
+
+
+DISPLAY_LO, DISPLAY_HI, DISPLAY_SHIFT = 2.0 ** -12, 16.0, 19   # the finish's own table: sixteen nodes per octave over sixteen octaves, 258 entries
+DISPLAY_Y_LO, DISPLAY_Y_HI = 2.0 ** -20, 2.0 ** 20             # LOCAL's range of exposed luminance
+DISPLAY_LOCAL_EPS = 0.25                                       # (half an octave)^2
+
+
+def display_luma(matrix):
+    """float32 [3]: the BT.709 luminance of what `matrix` [3, 3] makes of an image's channels, (0.2126 row 0 + 0.7152 row 1) + 0.0722 row 2 in binary64, rounded once -- for the
+    project's XYZ -> linear sRGB that is Y up to its radiometric scale, so that a metered exposure lands where the display sees it."""
+    m = np.asarray(matrix, dtype=np.float64).reshape(3, 3)
+    return ((0.2126 * m[0] + 0.7152 * m[1]) + 0.0722 * m[2]).astype(np.float32)
+
+
+def _display_arg(display, observer=1931, data_dir=DEFAULT_DATA_DIR):
+    """A display dict with its defaults filled in: "curve" ("reinhard"), "key" (0.18), "white_percentile" (0.99), "wb" ("none", "grey" or "white-patch"), "local" (None, or
+    {"radius", "compress", "boost" (1), "eps" (0.25)}), "space" ("xyz": the matrix is display_matrix; "lrgb": the identity),
+    "matrix" and "luma" (override the space's matrix and display_luma(matrix)), "lo", "hi", "shift" (the table: 2^-12, 16, 19), "mask" (uint8 [H, W]: what is metered)."""
+    d = dict(display)
+    unknown = set(d) - {"curve", "key", "white_percentile", "wb", "local", "space", "matrix", "luma", "lo", "hi", "shift", "mask"}
+    if unknown:
+        raise ValueError("display: unknown entries %s" % ", ".join(sorted(unknown)))
+    d.setdefault("curve", "reinhard"); d.setdefault("key", 0.18); d.setdefault("white_percentile", 0.99); d.setdefault("wb", "none"); d.setdefault("local", None)
+    d.setdefault("space", "xyz"); d.setdefault("lo", DISPLAY_LO); d.setdefault("hi", DISPLAY_HI); d.setdefault("shift", DISPLAY_SHIFT); d.setdefault("mask", None)
+    if d["curve"] not in TONE_CURVES:
+        raise ValueError("display: curve must be one of %s" % ", ".join(sorted(TONE_CURVES)))
+    if d["wb"] not in ("none", "grey", "white-patch"):
+        raise ValueError("display: wb must be 'none', 'grey' or 'white-patch'")
+    if d["space"] not in ("xyz", "lrgb"):
+        raise ValueError("display: space must be 'xyz' or 'lrgb'")
+    if d.get("matrix") is None:
+        d["matrix"] = display_matrix(observer, data_dir) if d["space"] == "xyz" else np.eye(3, dtype=np.float32)
+    if d.get("luma") is None:
+        d["luma"] = display_luma(d["matrix"])
+    if d["local"] is not None:
+        loc = dict(d["local"])
+        if "radius" not in loc or "compress" not in loc:
+            raise ValueError("display: local needs radius and compress")
+        loc.setdefault("boost", 1.0); loc.setdefault("eps", DISPLAY_LOCAL_EPS)
+        d["local"] = loc
+    return d
+
+
 def _sensor_arg(sensor):
     """A sensor dict -> (SsxSensorParams, the arrays that keep its tables alive: weights, taps, ccm, each None where the dict has none).  cfa is required; the
     scales default to a sensor that counts in the units of the develop (exposure 1, no noise, no ADC)."""
@@ -1338,7 +1424,106 @@ class Renderer:
         self._check(self._lib.ssx_glare_images(self._ctx, W, H, B, q.ctypes.data, C.byref(gp), out.ctypes.data))
         return out
 
-    def develop(self, weights, denoise=None, demodulate=None, optics=None, return_bins=False, defocus=None, sensor=None, return_raw=False, glare=None):
+    # ---- finishing a development for a display (include/ssx.h: meter, local tone map, tone curve) ----
+
+    @staticmethod
+    def _display_image(what, image):
+        image = np.ascontiguousarray(image, dtype=np.float32)
+        if image.ndim != 3 or image.shape[2] != 3:
+            raise ValueError("%s: the image must have shape [H, W, 3]" % what)
+        return image
+
+    def meter_images(self, image, luma, mask=None):
+        """ssx_meter_images: METER (include/ssx.h "Finishing a development for a display") as a pure function: image [H, W, 3], luma [3], mask uint8 [H, W] or None (0:
+        not counted) -> (hist uint32 [4, 4096], special uint32 [4, 4]): the channels' and the luminance's counts in sixteen keys per octave, and of +-0, negative, +inf
+        and NaN values."""
+        image = self._display_image("meter_images", image)
+        H, W, _ = image.shape
+        luma = np.ascontiguousarray(luma, dtype=np.float32)
+        if luma.shape != (3,):
+            raise ValueError("meter_images: luma must hold three entries")
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, dtype=np.uint8)
+            if mask.shape != (H, W):
+                raise ValueError("meter_images: mask must have shape [H, W]")
+        hist = np.zeros((4, _capi.SSX_METER_KEYS), dtype=np.uint32)
+        special = np.zeros((4, 4), dtype=np.uint32)
+        self._check(self._lib.ssx_meter_images(self._ctx, W, H, image.ctypes.data, luma.ctypes.data, None if mask is None else mask.ctypes.data, hist.ctypes.data,
+                                               special.ctypes.data))
+        return hist, special
+
+    def local_images(self, image, luma, radius, compress, boost=1.0, eps=DISPLAY_LOCAL_EPS, exposure=1.0, pivot=0.0, y_lo=DISPLAY_Y_LO, y_hi=DISPLAY_Y_HI, return_base=False):
+        """ssx_local_images: LOCAL as a pure function: image [H, W, 3] -> the gain float32 [H, W] that compresses the base layer of the integer log-luminance (a
+        self-guided filter of radius `radius`, flatness `eps`) about `pivot` by `compress` and scales the detail by `boost`; with return_base: (gain, base [H, W])."""
+        image = self._display_image("local_images", image)
+        H, W, _ = image.shape
+        luma = np.ascontiguousarray(luma, dtype=np.float32)
+        if luma.shape != (3,):
+            raise ValueError("local_images: luma must hold three entries")
+        p = _capi.SsxLocalParams()
+        p.struct_size = C.sizeof(_capi.SsxLocalParams)
+        p.radius = int(radius) & 0xFFFFFFFF
+        p.exposure, p.y_lo, p.y_hi, p.eps, p.pivot, p.compress, p.boost = float(exposure), float(y_lo), float(y_hi), float(eps), float(pivot), float(compress), float(boost)
+        gain = np.zeros((H, W), dtype=np.float32)
+        base = np.zeros((H, W), dtype=np.float32) if return_base else None
+        self._check(self._lib.ssx_local_images(self._ctx, W, H, image.ctypes.data, luma.ctypes.data, C.byref(p), gain.ctypes.data, None if base is None else base.ctypes.data))
+        return (gain, base) if return_base else gain
+
+    def tone_images(self, image, curve, lo=DISPLAY_LO, hi=DISPLAY_HI, shift=DISPLAY_SHIFT, gains=(1.0, 1.0, 1.0), matrix=None, local=None):
+        """ssx_tone_images: TONE as a pure function: image [H, W, 3] -> float32 [H, W, 3]: channel gains, the local gain [H, W] if there is one, the matrix [3, 3]
+        (None: identity), then the table `curve` (tone_curve) over [lo, hi] with 2^(23 - shift) nodes per octave."""
+        image = self._display_image("tone_images", image)
+        H, W, _ = image.shape
+        curve = np.ascontiguousarray(curve, dtype=np.float32)
+        matrix = np.eye(3, dtype=np.float32) if matrix is None else np.ascontiguousarray(matrix, dtype=np.float32)
+        gains = np.ascontiguousarray(gains, dtype=np.float32)
+        if curve.ndim != 1 or matrix.shape != (3, 3) or gains.shape != (3,):
+            raise ValueError("tone_images: curve must have shape [n], matrix [3, 3], gains [3]")
+        if local is not None:
+            local = np.ascontiguousarray(local, dtype=np.float32)
+            if local.shape != (H, W):
+                raise ValueError("tone_images: local must have shape [H, W]")
+        p = _capi.SsxToneParams()
+        p.struct_size = C.sizeof(_capi.SsxToneParams)
+        p.shift, p.curve_len, p.lo, p.hi = int(shift) & 0xFFFFFFFF, curve.size, float(lo), float(hi)
+        p.gains = (C.c_float * 3)(*gains.tolist())
+        p.matrix = (C.c_float * 9)(*matrix.reshape(-1).tolist())
+        p.curve = curve.ctypes.data
+        out = np.zeros((H, W, 3), dtype=np.float32)
+        self._check(self._lib.ssx_tone_images(self._ctx, W, H, image.ctypes.data, None if local is None else local.ctypes.data, C.byref(p), out.ctypes.data))
+        return out
+
+    def finish(self, image, display, return_meter=False):
+        """A development finished for a display: METER, ssh_meter_derive, LOCAL where display["local"] asks for it, TONE.  image [H, W, 3] (in display["space"]) ->
+        float32 [H, W, 3], display-encoded (the curve holds the sRGB transfer function): nothing further is to be applied.  display: see _display_arg; {} gives an
+        extended Reinhard curve whose white point is the luminance's 99th percentile, exposed for a log-average of 0.18.  With return_meter: (image, (hist, special))."""
+        d = _display_arg(display, self.options.observer, self.options.data_dir)
+        image = self._display_image("finish", image)
+        hist, special = self.meter_images(image, d["luma"], d["mask"])
+        m = meter_derive(hist, special, key=d["key"], white_percentile=d["white_percentile"])
+        wb = {"none": np.ones(3, dtype=np.float32), "grey": m["grey"], "white-patch": m["patch"]}[d["wb"]]
+        gains = np.float32(m["exposure"]) * wb.astype(np.float32)
+        local = None
+        if d["local"] is not None:
+            loc = d["local"]
+            local = self.local_images(image, d["luma"], loc["radius"], loc["compress"], boost=loc["boost"], eps=loc["eps"], exposure=m["exposure"], pivot=m["pivot"])
+        white = float(m["white_exposed"]) if m["white_exposed"] > 0 else 1.0
+        curve = tone_curve(d["curve"], d["lo"], d["hi"], d["shift"], white=white)
+        out = self.tone_images(image, curve, lo=d["lo"], hi=d["hi"], shift=d["shift"], gains=gains, matrix=d["matrix"], local=local)
+        return (out, (hist, special)) if return_meter else out
+
+    def develop(self, weights, denoise=None, demodulate=None, optics=None, return_bins=False, defocus=None, sensor=None, return_raw=False, glare=None, display=None):
+        """_develop (below: every argument but `display` is its own) and, with a display dict, finish() on the image it returns (three channels: in display["space"]);
+        what else it returns (return_bins, return_raw) stays as it is.  display None: _develop's result."""
+        r = self._develop(weights, denoise=denoise, demodulate=demodulate, optics=optics, return_bins=return_bins, defocus=defocus, sensor=sensor, return_raw=return_raw,
+                          glare=glare)
+        if display is None:
+            return r
+        if isinstance(r, tuple):
+            return (self.finish(r[0], display),) + tuple(r[1:])
+        return self.finish(r, display)
+
+    def _develop(self, weights, denoise=None, demodulate=None, optics=None, return_bins=False, defocus=None, sensor=None, return_raw=False, glare=None):
         """ssx_spectral_develop: the bins the context holds, mapped on the device by weights [C, B] (develop_weights) -> float32 [H, W, C], row 0 = bottom.
         denoise None: the raw source, q = S * M / n; a dict of denoise_spectral's parameters (levels, sigma_l, sigma_a; {} for the defaults): the filtered bins,
         developed without leaving the device.  demodulate (True or a dict, as in denoise_spectral; denoise None counts as {}): ssx_spectral_develop_demod, the
